@@ -20,11 +20,18 @@ the >= 70 %-of-HBM-roofline target on (config 2's 10^6 points is 448 MB, of whic
 in the 256 MB Infinity Cache between steps; scripts/bench_extra.py reports it). Scaling is weak: with N > 1 every
 rank owns its own cell block of 1.25*10^7 points (BASELINE config 3: 10^8 points over 8 GPUs).
 
+A plain run measures the headline and nothing else: set-up, W warm-up steps, ONE batch of exactly K timed steps, the outputs of
+the last step written with `--dump-outputs DIR`, one result line. Everything beside the headline runs with `--full` only: the
+cpu_baseline leg, the live HBM-counter passes, the stream probe, the side figures (plain allocation, factory), end_to_end, the
+`secondary` block, the output checks, the median of 5 batches, and at N > 1 the other gather modes of a fixed --gather-mode,
+the separate roofline launches and libdxo's own RCCL cross-check.
+
 stdout carries the contract line (rank 0): a BOUNDED extract (tools/bench_line.py, <= 6 000 bytes) of the full record, which goes
-to `bench_full.json` beside this file and to stderr. With one GPU the line is written as soon as the timed region is over and
-again — a superset each time — when `cpu_baseline` + the live HBM-counter passes are in and when the end_to_end / secondary legs
-are done; the LAST line is the result. Under torch.distributed (N > 1) the line is written once and repeated with
-`gather_check` (the verdict of libdxo's own RCCL path, run after the result) filled in.
+to `bench_full.json` beside this file. A plain run writes it once. With `--full` and one GPU the line is written as soon as the
+timed region is over and again — a superset each time — when `cpu_baseline` + the live HBM-counter passes are in and when the
+end_to_end / secondary legs are done (the full record then also goes to stderr); the LAST line is the result. Under
+torch.distributed (N > 1) with `--full` the line is written once and repeated with `gather_check` (the verdict of libdxo's own
+RCCL path, run after the result) filled in.
 """
 from __future__ import annotations
 
@@ -44,10 +51,30 @@ if str(ROOT) not in sys.path:
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 BYTES_PER_QP = {4: 240, 6: 448}  # algorithmic fp64 traffic per point, SURVEY.md 8(d)
 PROBE_MIX = {4: (9, 21), 6: (13, 43)}  # 16-byte chunks read / written per pair of points
+DUMP_POINTS = 1 << 17  # --dump-outputs: points written at most (45 MB at d = 6)
+DUMP_SEED = 5
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(torch, out_dir, C_tang, sigma, dp, d):
+    """--dump-outputs: (C_tang, sigma, dp) of the last timed step as float64 .npy files, (P, d, d), (P, d), (P,). P = every point when
+    there are at most DUMP_POINTS, otherwise a sorted sample of DUMP_POINTS points drawn with DUMP_SEED: the same points in every run of
+    the same size, so that two builds can be compared output for output."""
+    import numpy as np
+
+    n = dp.numel()
+    out_dir = pathlib.Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"C_tang": C_tang.view(n, d, d), "sigma": sigma.view(n, d), "dp": dp.view(n)}
+    if n > DUMP_POINTS:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, size=DUMP_POINTS, replace=False))
+        idx_dev = torch.from_numpy(idx).to(dp.device)
+        arrays = {k: a.index_select(0, idx_dev) for k, a in arrays.items()}
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a.cpu().numpy().astype(np.float64, copy=False))
 
 
 def synth_inputs(torch, n, d, seed, device):
@@ -399,9 +426,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batches", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline (see the module docstring); a plain run times exactly --steps steps "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/C_tang.npy, sigma.npy, dp.npy (float64; rank 0's arrays): "
+                         f"all points up to {DUMP_POINTS}, above that the same seeded sample of {DUMP_POINTS} points in every run")
+    ap.add_argument("--batches", type=int, default=None,
                     help="timed batches of --steps steps each, every batch between its own fences; value / ms_per_step are the median batch's "
-                         "(SURVEY.md 8d timing protocol)")
+                         "(SURVEY.md 8d timing protocol). Default 1, 5 with --full")
     ap.add_argument("--nqp", type=int, default=0,
                     help="quadrature points per GPU; default 10^7 at --gpus 1 (north_star's target size) and 1.25*10^7 at "
                          "--gpus N > 1 (BASELINE config 3: 10^8 points over 8 GPUs)")
@@ -451,6 +484,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if not args.full:   # a plain run: the headline alone
+        args.no_cpu = args.no_probe = args.no_e2e = args.no_traffic = args.no_secondary = args.no_side = args.no_library_gather = True
     if args.gather_vmm:
         # the experiment this flag names hands chunk-backed arena blocks to the collectives, which sharding.py refuses by default
         # (set here, before anything is imported, and inherited by the ranks a parent launches); libdxo's own forms refuse such
@@ -627,7 +662,7 @@ def main():
     # batch whose wall time and kernel time disagree shows where the time went: `step_gap_us_max` is the largest interval between
     # the end of one step's launch and the start of the next one's. Nothing is allocated or freed between warm-up and the last batch,
     # Python's collector is off, and the events already exist (an event is created by its first record).
-    B = max(1, args.batches)
+    B = max(1, args.batches if args.batches is not None else (5 if args.full else 1))
     import gc
 
     def run_batches(step_fn, warm):
@@ -678,8 +713,9 @@ def main():
     if gather_on:
         # in the compact forms the step's own launch is the (sigma, dp)-only kernel; `roofline` and `kernel_only_value` are
         # about the FULL kernel (448 B/point), so with a gather on it is timed here, K launches back to back into this
-        # rank's slice of the same arrays (outside the timed steps; the next step overwrites the slice anyway)
-        kernel_ms_avg = bytes_per_launch_of(d, n) / time_kernel(ptrs[3:], K) / 1e6
+        # rank's slice of the same arrays (outside the timed steps; the next step overwrites the slice anyway). A plain run
+        # leaves them out (null).
+        kernel_ms_avg = bytes_per_launch_of(d, n) / time_kernel(ptrs[3:], K) / 1e6 if args.full else None
     total_points = n * world
     bytes_per_launch = BYTES_PER_QP[d] * n
     MODES = ("compact", "compact_pipelined", "compact_direct", "full")
@@ -705,7 +741,7 @@ def main():
         if rank != 0 or not emitted.acquire(blocking=False):
             return
         mode = mode or args.gather_mode
-        achieved = bytes_per_launch / (kernel_ms_ * 1e-3) / 1e9
+        achieved = bytes_per_launch / (kernel_ms_ * 1e-3) / 1e9 if kernel_ms_ is not None else None
         result = {
             "metric": "quadrature-points/sec (von Mises return-map + tangent)",
             "value": total_points * K / elapsed_, "unit": "qp/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -757,7 +793,7 @@ def main():
             },
             "roofline": {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": None, "traffic_detail": None,
+                "frac": achieved / HBM_PEAK_GBS if achieved is not None else None, "traffic": None, "traffic_detail": None,
                 "traffic_over_algorithmic": None,
                 "kernel": f"vm_tile<{d}>" if args.variant else f"vm_point<{d}>",
                 "kernel_ms_avg": kernel_ms_, "algorithmic_bytes_per_launch": bytes_per_launch,
@@ -770,14 +806,16 @@ def main():
                 "factory_placement": factory_placement, "factory_detail": factory_detail,
                 "stream_probe_GBps": probe_GBps,
             },
-            "kernel_only_value": total_points / (kernel_ms_ * 1e-3),
+            "kernel_only_value": total_points / (kernel_ms_ * 1e-3) if kernel_ms_ is not None else None,
         }
         if dist_on:
             result["gather_check"] = ({"status": "skipped", "why": "dry_collective: libdxo's own RCCL path needs one GPU per rank"} if args.dry_collective
-                                      else {"status": "skipped", "why": "--no-library-gather"} if args.no_library_gather
+                                      else {"status": "skipped", "why": "--no-library-gather" if args.full else "runs with --full"} if args.no_library_gather
                                       else {"status": "pending", "why": "runs after this line; a second, final line repeats this one with the verdict"})
         last_result.update(result)
-        single = extras and world == 1 and not dist_on      # under torch.distributed (also a world of one) the line is written once, then once more with gather_check
+        # a plain run, and under torch.distributed (also a world of one) every run: the line is written once (with --full under
+        # torch.distributed, then once more with gather_check)
+        single = extras and world == 1 and not dist_on and args.full
         t_extras = time.perf_counter()
         if not single:
             write_line(result, "final")
@@ -847,8 +885,8 @@ def main():
                             stats=stats_)
                 os._exit(3)
         threading.Thread(target=_compare_watchdog, daemon=True).start()
-    if gather_on:
-        if world > 1:   # remote tangents rebuilt from (sigma, dp) must be usable: finite and symmetric
+    if gather_on and (auto_mode or args.full):      # a plain run with a fixed --gather-mode times that mode alone
+        if world > 1 and args.full:   # remote tangents rebuilt from (sigma, dp) must be usable: finite and symmetric
             nb = (rank + 1) % world
             chk = C_full[nb * n * d * d: nb * n * d * d + 4096 * d * d].view(-1, d, d)
             if not bool(torch.isfinite(chk).all()) or float((chk - chk.transpose(1, 2)).abs().max()) > 1e-9 * E:
@@ -869,9 +907,11 @@ def main():
             other_elapsed[mode], other_stats[mode] = w2[bm], st
 
     if dist_on:
-        t = torch.tensor([kernel_ms_avg], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        kernel_ms_avg_max = float(t[0])
+        kernel_ms_avg_max = None
+        if kernel_ms_avg is not None:
+            t = torch.tensor([kernel_ms_avg], dtype=torch.float64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            kernel_ms_avg_max = float(t[0])
         if auto_mode and gather_on:
             # the reduced times are identical on every rank, so every rank picks the same headline
             best = min({args.gather_mode: elapsed, **other_elapsed}.items(), key=lambda kv: kv[1])
@@ -884,9 +924,13 @@ def main():
         kernel_ms_avg_max = kernel_ms_avg
     compare_done.set()
 
-    # correctness tripwire inside the bench itself (not timed): plastic points sit on the yield surface — checked on
+    # what the caller of the timed path receives after its last step: the full-length arrays with the gather on, else this rank's own
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, *((C_full, sigma_full, dp_full) if gather_on else (C_tang, sigma, dp)), d)
+
+    # correctness tripwire inside the bench itself (not timed, --full): plastic points sit on the yield surface — checked on
     # the first and on the LAST 4096 points (the tail exercises the 64-bit index arithmetic of very large batches)
-    for lo in sorted({0, max(n - 4096, 0)}):
+    for lo in sorted({0, max(n - 4096, 0)}) if args.full else ():
         sl = slice(lo, lo + 4096)
         s_chk = sigma.view(n, d)[sl]
         dev_chk = s_chk.clone()
@@ -897,7 +941,7 @@ def main():
             raise SystemExit("bench: yield condition violated by the kernel output — refusing to report a number")
         if not bool(torch.isfinite(C_tang[lo * d * d:(lo + 4096) * d * d]).all()):
             raise SystemExit("bench: non-finite tangent in the kernel output — refusing to report a number")
-    del s_chk, dev_chk, f_chk, plastic      # s_chk is a view into the headline's output block: it must not outlive the block's release below
+        del s_chk, dev_chk, f_chk, plastic      # s_chk is a view into the headline's output block: it must not outlive the block's release below
 
     # side figures (never `value`), measured AFTER the timed batches so that their allocations and frees cannot disturb them
     if rank == 0 and not gather_on and not args.no_side:

@@ -7,7 +7,7 @@ python3 -c "import __graft_entry__ as g; g.build()" > /dev/null 2>&1
 for d in 6 4; do
   for n in 100000 1000000 10000000 100000000; do
     steps=20; [ "$n" -ge 100000000 ] && steps=10
-    timeout 900 python3 bench.py --nqp $n --d $d --steps $steps --no-cpu --placement 4 2>/dev/null | python3 -c "
+    timeout 900 python3 bench.py --full --nqp $n --d $d --steps $steps --no-cpu --placement 4 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.readline())
 r = j['roofline']

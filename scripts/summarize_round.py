@@ -36,7 +36,7 @@ if rows:
         fh.write("kernel,calls,total_ns,average_ns,min_ns,max_ns\n")
         for r in rows:
             fh.write(f"\"{r[0]}\",{r[1]},{r[2]:.0f},{r[3]:.1f},{r[4]:.0f},{r[5]:.0f}\n")
-    print("== kernel stats (rocprofv3 --kernel-trace --stats of `python3 bench.py --no-cpu --no-probe --no-e2e`)")
+    print("== kernel stats (rocprofv3 --kernel-trace --stats of `python3 bench.py --full --no-cpu --no-probe --no-e2e`)")
     for r in rows[:14]:
         print(f"  {r[0][:70]:70s} calls {r[1]:4d}  avg {r[3] / 1e3:9.1f} us")
 # ---- kernel trace: the stats file averages ALL dispatches of a kernel (calibration launches, small input-generation
@@ -55,7 +55,7 @@ if trace:
     pj = out / "bench_profiled.json"
     if pj.exists() and pj.read_text().strip().startswith("{"):
         prof = json.loads(pj.read_text().strip().splitlines()[-1])
-    lines = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu --no-probe --no-e2e   (scripts/profile_round.sh {tag})",
+    lines = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu --no-probe --no-e2e   (scripts/profile_round.sh {tag})",
              "# <tag>_kernel_stats.csv averages ALL dispatches of a kernel; this file separates the timed ones."]
     K = int(prof.get("steps", 20))
     for name, ds in sorted(disp.items(), key=lambda kv: -sum(d[1] for d in kv[1])):

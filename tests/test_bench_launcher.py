@@ -83,7 +83,7 @@ def test_multi_rank_path_logic_on_one_gpu(ranks):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
                           "--master-port", str(29571 + ranks), str(ROOT / "bench.py"), "--gpus", str(ranks), "--dry-collective", "--steps", "2",
-                          "--warmup", "1", "--nqp", "500000", "--no-probe"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                          "--warmup", "1", "--nqp", "500000", "--no-probe", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                       # dry mode: no second line (the library check needs one GPU per rank)
@@ -112,7 +112,7 @@ def test_single_rank_under_torchrun_prints_the_gather_check_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
                           "--master-port", "29579", str(ROOT / "bench.py"), "--gpus", "1", "--gather", "1", "--steps", "2", "--warmup", "1",
-                          "--nqp", "500000", "--no-probe", "--no-cpu", "--no-e2e", "--no-secondary", "--no-traffic"],
+                          "--nqp", "500000", "--no-probe", "--no-cpu", "--no-e2e", "--no-secondary", "--no-traffic", "--full"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [json.loads(ln) for ln in res.stdout.splitlines() if ln.startswith("{")]
