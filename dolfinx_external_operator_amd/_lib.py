@@ -151,6 +151,8 @@ _SIGNATURES = {
     "dxo_operand_adjoint": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
     "dxo_tangent_apply": (C.c_int, [_P, _P, _P, _P, _P]),
     "dxo_tangent_diagonal": (C.c_int, [_P, _P, _P, _P]),
+    "dxo_bilinear_apply": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "dxo_bilinear_diagonal": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dxo_tangent_apply_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P, _P]),
     "dxo_von_mises_residual": (C.c_int, [_P, C.POINTER(VmParams), _P, _P, _P, _P, _P, _P, _P]),
     "dxo_tangent_diagonal_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P]),

@@ -9,6 +9,7 @@
 //   virtual work f     = sum_q w_q |det J_q| B_q^T s_q                                                  dxo_operand_adjoint
 //   tangent      K v   = sum_q w_q |det J_q| B_q^T C_q B_q v   (never forming K)                        dxo_tangent_apply[_vm]
 //   its diagonal                                                                                        dxo_tangent_diagonal[_vm]
+//   any pair     K v   = sum_q w_q |det J_q| B_test,q^T C_q B_trial,q v, and its diagonal                 dxo_bilinear_* (bilinear.h)
 // so with these entry points a Newton-Krylov solver can keep sigma and C_tang in HBM and move only dof vectors.
 //
 // Shape of every call (whole mesh): TWO PASSES, no atomics, bit-reproducible.
@@ -1487,3 +1488,6 @@ extern "C" int dxo_tangent_diagonal_vm(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_v
     if (!vm_state_src(ctx, mesh, prm, sigma, dp, vs)) return DXO_E_NULL;
     return tangent_diagonal_impl(ctx, mesh, nullptr, &vs, out, "dxo_tangent_diagonal_vm");
 }
+
+// dxo_bilinear_apply / dxo_bilinear_diagonal: the same two operators for a general pair of linear operand kinds (bilinear.h)
+#include "bilinear.h"

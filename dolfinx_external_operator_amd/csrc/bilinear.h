@@ -1,0 +1,494 @@
+// bilinear.h — the action and the diagonal of a bilinear form between two linear operand kinds of one field, with a per-point
+// block C_q (dxo_bilinear_apply / dxo_bilinear_diagonal). Included at the end of adjoint.hip: it reuses that file's gather,
+// geometry, dual_tensor, adjoint_scatter and the two-pass scatter (element vectors fe + node_sum).
+//   out[dof]  += sum_q w_q |det J_q| B_test,q^T C_q B_trial,q v           C_q: [D_test][D_trial] row-major fp64 per point
+//   diag[dof] += sum_q w_q |det J_q| (B_test,q^T C_q B_trial,q)_(dof,dof)
+// dxo_tangent_apply is the pair (eps, eps) with bs = gdim; the finite-strain Jacobian of the hyperelasticity demo is (grad, grad) with
+// C = dP/dF, the heat demo's Jacobian (grad, value_grad) with bs = 1 and C = [dq/dT | dq/dsigma].
+#pragma once
+
+#include <cstdio>
+#include <type_traits>
+
+#ifndef DXO_BL_WAVES
+#define DXO_BL_WAVES 2       // waves per SIMD the kernels are compiled for (as tangent_apply)
+#endif
+#ifndef DXO_BL_BLOCKS_PER_CU
+#define DXO_BL_BLOCKS_PER_CU 8
+#endif
+
+namespace {
+
+// ---- the C blocks of a wave group. The group's points are consecutive, so its blocks are one contiguous run of npts * DT * DR doubles:
+// it is requested LANE-LINEAR (consecutive lanes, consecutive 16-byte pieces: every cache line is fetched once, as TangentRows does for
+// dxo_tangent_apply) and passes through the wave's LDS region in chunks of PC points, where every lane of the chunk picks up its own
+// block. Small blocks (at most 40 doubles per lane for the whole group) are requested at the top of the iteration and sit in registers
+// until the region is free; large ones (3-D grad / grad with bs = 3: 81 doubles per point) are STREAMED, one chunk of 8 points in
+// registers at a time, the next chunk requested as soon as the current one is in LDS. Blocks of an odd number of doubles (1, 9, 81)
+// cannot all start on a 16-byte boundary and are read 8 bytes at a time.
+template <int DT, int DR>
+struct BlockRows {
+    static constexpr int DD = DT * DR;
+    static constexpr int U = DD % 2 == 0 ? 2 : 1;                 // doubles per load
+    using unit = typename std::conditional<U == 2, dxo_f64x2, double>::type;
+    static constexpr int PC = DD <= 36 ? 32 : 8;                  // points per chunk
+    static constexpr int NCH = DXO_WAVE / PC;
+    static constexpr int UPP = DD / U;                            // units per point
+    static constexpr int UPC = PC * UPP;                          // units per chunk
+    static constexpr int LPC = (UPC + DXO_WAVE - 1) / DXO_WAVE;   // loads per lane and chunk
+    static constexpr bool HOLD = NCH * LPC * U <= 40;
+    static constexpr int NB = HOLD ? NCH : 1;
+    static constexpr int RSU = U == 2 ? (UPP | 1) : UPP;          // staged stride of a point in units: odd (bank spread of the lanes' reads)
+    static constexpr int LDS_DOUBLES = PC * RSU * U;
+    unit r[NB][LPC];
+    const unit* base;
+    int nunits;
+
+    static __device__ __forceinline__ unit zero() {
+        if constexpr (U == 2) return dxo_f64x2{0.0, 0.0};
+        else return 0.0;
+    }
+    __device__ __forceinline__ void request(int k, int b, int lane) {
+#pragma unroll
+        for (int j = 0; j < LPC; ++j) {
+            const int w = j * DXO_WAVE + lane, u = k * UPC + w;
+            r[b][j] = (w < UPC && u < nunits) ? base[u] : zero();
+        }
+    }
+    // p0: first point of the group, npts: its points. C is 16-byte aligned and DD even when U = 2, so every piece is.
+    __device__ __forceinline__ void begin(const double* __restrict__ C, int64_t p0, int npts, int lane) {
+        base = reinterpret_cast<const unit*>(C + p0 * DD);
+        nunits = npts * UPP;
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) request(k, k, lane);
+        } else {
+            request(0, 0, lane);
+        }
+    }
+    // f(R) on the lane's own block R[DD] (row-major, in LDS), chunk by chunk; S = the wave's region (16-byte aligned). Ends fenced.
+    template <class Fn>
+    __device__ __forceinline__ void chunk(double* S, int lane, int k, int b, Fn& f) {
+        unit* Su = reinterpret_cast<unit*>(S);
+#pragma unroll
+        for (int j = 0; j < LPC; ++j) {
+            const int w = j * DXO_WAVE + lane;
+            if (w < UPC) {
+                const int p = w / UPP;
+                Su[p * RSU + (w - p * UPP)] = r[b][j];
+            }
+        }
+        if constexpr (!HOLD) {
+            if (k + 1 < NCH) request(k + 1, 0, lane);
+        }
+        op_fence();
+        if (lane / PC == k) f(static_cast<const double*>(S) + (lane - k * PC) * RSU * U);
+        op_fence();
+    }
+    template <class Fn>
+    __device__ __forceinline__ void for_each(double* S, int lane, Fn&& f) {
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) chunk(S, lane, k, k, f);
+        } else {
+            // a rolled loop: unrolled, the compiler hoists every chunk's loads to the top and runs out of registers
+#pragma unroll 1
+            for (int k = 0; k < NCH; ++k) chunk(S, lane, k, 0, f);
+        }
+    }
+    // t = C e for the lane's point
+    __device__ __forceinline__ void times(double* S, int lane, const double (&e)[DR], double (&t)[DT]) {
+#pragma unroll
+        for (int i = 0; i < DT; ++i) t[i] = 0.0;
+        for_each(S, lane, [&](const double* R) {
+            const unit* Ru = reinterpret_cast<const unit*>(R);
+#pragma unroll
+            for (int u = 0; u < UPP; ++u) {
+                const unit c = Ru[u];
+                if constexpr (U == 2) {
+                    t[(2 * u) / DR] += c.x * e[(2 * u) % DR];
+                    t[(2 * u + 1) / DR] += c.y * e[(2 * u + 1) % DR];
+                } else {
+                    t[u / DR] += c * e[u % DR];
+                }
+            }
+        });
+    }
+};
+
+// d(slot r of operand KIND) / d z for the unit dof of component i, z = 0: the basis function's value, z = 1 + j: its derivative along
+// x_j. Compile-time constants once the callers' loops are unrolled: the zero terms are never formed.
+template <int G, int BS, int KIND>
+__device__ __forceinline__ constexpr double op_coef(int r, int i, int z) {
+    if constexpr (KIND == DXO_OPERAND_VALUE) return (r == i && z == 0) ? 1.0 : 0.0;
+    else if constexpr (KIND == DXO_OPERAND_GRAD) return (z > 0 && r == i * G + z - 1) ? 1.0 : 0.0;
+    else if constexpr (KIND == DXO_OPERAND_VALUE_GRAD) return ((z == 0 && r == i) || (z > 0 && r == BS + i * G + z - 1)) ? 1.0 : 0.0;
+    else {   // EPS_MANDEL (BS == G): e_i = g_ii, e_m(i,j) = (g_ij + g_ji) / sqrt2
+        if (z == 0) return 0.0;
+        const int j = z - 1;
+        if (i == j) return r == i ? 1.0 : 0.0;
+        return r == (G == 2 ? 3 : i + j + 2) ? 0.70710678118654752440 : 0.0;
+    }
+}
+
+template <int KIND>
+constexpr bool op_has_value() { return KIND == DXO_OPERAND_VALUE || KIND == DXO_OPERAND_VALUE_GRAD; }
+
+// K v: gather v, the trial operand e = B_trial v per point, t = C e through the staged blocks, scatter B_test^T t (adjoint_scatter).
+// The shape of tangent_apply's general form (register-pipelined gather, C requested before the contraction).
+template <int G, int BS, int TEST, int TRIAL>
+__global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_apply(OperandDev m, const double* __restrict__ wq, int lds_wave,
+                                                                         const double* __restrict__ C, const double* __restrict__ v,
+                                                                         int64_t n_cells, double* __restrict__ out, double* __restrict__ fe) {
+    constexpr int DT = OperandShape<G, BS, TEST>::D, DR = OperandShape<G, BS, TRIAL>::D;
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* tab = lds;
+    operand_load_tables<G>(m, tab);
+    __syncthreads();
+    const int lane = threadIdx.x & (DXO_WAVE - 1);
+    const int wave = threadIdx.x >> 6;
+    double* W = lds + m.table_doubles + wave * lds_wave;
+    const int cpw = m.cells_per_wave;
+    double* Tm = W + cpw * (op_odd(m.ndofs * BS) + op_odd(m.ngeom * G));
+    const int64_t n_groups = (n_cells + cpw - 1) / cpw;
+    const GroupWalk walk = xcd_group_walk(n_groups, DXO_BLOCK / DXO_WAVE, wave);
+    const int64_t stride = walk.stride;
+    auto cells_in = [&](int64_t g) -> int {
+        if (g >= walk.end) return 0;
+        const int64_t left = n_cells - g * cpw;
+        return left < cpw ? (int)left : cpw;
+    };
+    const bool piped = operand_can_pipe(m);
+    OperandPipe<G, BS> pf;
+    int64_t grp = walk.first;
+    if (piped) {
+        pipe_load_indices<G, BS>(m, pf, grp * cpw, cells_in(grp), lane);
+        pipe_load_values<G, BS>(m, pf, v);
+        pipe_load_indices<G, BS>(m, pf, (grp + stride) * cpw, cells_in(grp + stride), lane);
+    }
+    const int q_l = lane - (lane / m.nq) * m.nq;
+    const double w_l = lane < cpw * m.nq ? wq[q_l] : 0.0;
+    for (; grp < walk.end; grp += stride) {
+        const int64_t c0 = grp * cpw;
+        const int ncell = cells_in(grp);
+        BlockRows<DT, DR> rows;
+        rows.begin(C, c0 * m.nq, ncell * m.nq, lane);
+        if (piped) {
+            pipe_commit<G, BS>(m, pf, W, ncell, lane);
+            pipe_load_values<G, BS>(m, pf, v);
+            pipe_load_indices<G, BS>(m, pf, (grp + 2 * stride) * cpw, cells_in(grp + 2 * stride), lane);
+        } else {
+            operand_gather<G, BS>(m, W, v, nullptr, c0, ncell, lane);
+        }
+        double e[DR], K[G][G], det = 0.0;
+#pragma unroll
+        for (int i = 0; i < G; ++i)
+#pragma unroll
+            for (int j = 0; j < G; ++j) K[i][j] = 0.0;
+        const bool active = operand_compute_geo<G, BS, TRIAL>(m, tab, W, ncell, lane, e, K, det);
+        if (!active) {
+#pragma unroll
+            for (int k = 0; k < DR; ++k) e[k] = 0.0;
+        }
+        double t[DT];
+        rows.times(W, lane, e, t);      // compute_geo has fenced: the gather buffer is free, the parked tensors are not written yet
+        double vh[BS], gh[BS][G], scale = 0.0;
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            vh[i] = 0.0;
+#pragma unroll
+            for (int j = 0; j < G; ++j) gh[i][j] = 0.0;
+        }
+        if (active) {
+            scale = w_l * fabs(det);
+            dual_tensor<G, BS, TEST>(t, vh, gh);
+        }
+        adjoint_scatter<G, BS>(m, tab, Tm, active, lane, vh, gh, K, scale, c0, ncell, nullptr, out, fe);
+    }
+}
+
+// diag(K): the unit dof (node a, component i) has the operand slots sum_z coef(r, i, z) z_phys with z_phys = (phi_a, grad phi_a), so its
+// entry is z_phys^T M_i z_phys, M_i[z1][z2] = sum_rc coef_test(r, i, z1) C[r][c] coef_trial(c, i, z2). Phase 1, lane = (cell, point):
+// M_i pulled back to reference derivatives (z_phys = P z_ref, P = diag(1, K^T)) and symmetrised, NZ (NZ + 1) / 2 numbers per component,
+// parked in LDS; phase 2, lane = (cell, node): sum over the cell's points of z_ref^T NS_i z_ref. tangent_diag's scheme for any pair.
+template <int G, int BS, int TEST, int TRIAL>
+__global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_diag(OperandDev m, const double* __restrict__ wq, int lds_wave,
+                                                                        const double* __restrict__ C, int64_t n_cells,
+                                                                        double* __restrict__ out, double* __restrict__ fe) {
+    constexpr int DT = OperandShape<G, BS, TEST>::D, DR = OperandShape<G, BS, TRIAL>::D;
+    constexpr int Z0 = (op_has_value<TEST>() || op_has_value<TRIAL>()) ? 0 : 1;    // z = 0 (the value) only where a kind has it
+    constexpr int NZ = G + 1 - Z0;
+    constexpr int NS1 = NZ * (NZ + 1) / 2;
+    constexpr int PT = (BS * NS1) | 1;
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* tab = lds;
+    operand_load_tables<G>(m, tab);
+    __syncthreads();
+    const OperandLayout<G> L(m);
+    const int lane = threadIdx.x & (DXO_WAVE - 1);
+    const int wave = threadIdx.x >> 6;
+    double* W = lds + m.table_doubles + wave * lds_wave;
+    const int cpw = m.cells_per_wave, nd = m.ndofs, nq = m.nq, ng = m.ngeom;
+    const int sx = op_odd(ng * G);
+    double* X = W;
+    double* Pm = X + ((cpw * sx + 1) & ~1);          // staging of the C blocks, then the parked matrices [point][PT]
+    const int64_t n_groups = (n_cells + cpw - 1) / cpw;
+    const GroupWalk walk = xcd_group_walk(n_groups, DXO_BLOCK / DXO_WAVE, wave);
+    const int c_l = lane / nq, q_l = lane - c_l * nq;
+    const double w_l = lane < cpw * nq ? wq[q_l] : 0.0;
+    for (int64_t grp = walk.first; grp < walk.end; grp += walk.stride) {
+        const int64_t c0 = grp * cpw;
+        const int ncell = (n_cells - c0 < cpw) ? (int)(n_cells - c0) : cpw;
+        const bool has_point = c_l < ncell;
+        BlockRows<DT, DR> rows;
+        rows.begin(C, c0 * nq, ncell * nq, lane);
+        for (int idx = lane; idx < ncell * ng; idx += DXO_WAVE) {
+            const int c = idx / ng, vv = idx - c * ng;
+            const int64_t node = m.geom_dofmap[(c0 + c) * ng + vv];
+#pragma unroll
+            for (int j = 0; j < G; ++j) X[c * sx + vv * G + j] = m.x[node * G + j];
+        }
+        op_fence();
+        double K[G][G], scale = 0.0;
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+#pragma unroll
+            for (int k = 0; k < G; ++k) K[j][k] = 0.0;
+        if (has_point) {
+            const double* dpsi = tab + L.o_dpsi + q_l * L.sdpsi;
+            const double* Xc = X + c_l * sx;
+            double J[G][G];
+#pragma unroll
+            for (int j = 0; j < G; ++j)
+#pragma unroll
+                for (int k = 0; k < G; ++k) J[j][k] = 0.0;
+            for (int vv = 0; vv < ng; ++vv)
+#pragma unroll
+                for (int j = 0; j < G; ++j)
+#pragma unroll
+                    for (int k = 0; k < G; ++k) J[j][k] += Xc[vv * G + j] * dpsi[vv * G + k];
+            scale = w_l * fabs(invert<G>(J, K));
+        }
+        double NSr[BS * NS1];
+#pragma unroll
+        for (int k = 0; k < BS * NS1; ++k) NSr[k] = 0.0;
+        rows.for_each(Pm, lane, [&](const double* R) {      // the vertex buffer X lies before Pm: untouched by the staging
+            if (!has_point) return;
+#pragma unroll
+            for (int i = 0; i < BS; ++i) {
+                double M[NZ][NZ];
+#pragma unroll
+                for (int z1 = 0; z1 < NZ; ++z1)
+#pragma unroll
+                    for (int z2 = 0; z2 < NZ; ++z2) {
+                        double acc = 0.0;
+#pragma unroll
+                        for (int r = 0; r < DT; ++r) {
+                            const double a = op_coef<G, BS, TEST>(r, i, z1 + Z0);
+                            if (a == 0.0) continue;
+#pragma unroll
+                            for (int c = 0; c < DR; ++c) {
+                                const double b = op_coef<G, BS, TRIAL>(c, i, z2 + Z0);
+                                if (b == 0.0) continue;
+                                acc += (a * b) * R[r * DR + c];
+                            }
+                        }
+                        M[z1][z2] = acc;
+                    }
+                // P^T M P: rows / columns 1 + j of the physical derivatives become sum_j K[k][j] (.)_(1+j)
+                double KM[NZ][NZ], Mr[NZ][NZ];
+#pragma unroll
+                for (int a = 0; a < NZ; ++a)
+#pragma unroll
+                    for (int z2 = 0; z2 < NZ; ++z2) {
+                        if (a + Z0 == 0) { KM[a][z2] = M[a][z2]; continue; }
+                        const int k = a + Z0 - 1;
+                        double s = 0.0;
+#pragma unroll
+                        for (int j = 0; j < G; ++j) s += K[k][j] * M[1 + j - Z0][z2];
+                        KM[a][z2] = s;
+                    }
+#pragma unroll
+                for (int a = 0; a < NZ; ++a)
+#pragma unroll
+                    for (int b = 0; b < NZ; ++b) {
+                        if (b + Z0 == 0) { Mr[a][b] = KM[a][b]; continue; }
+                        const int k = b + Z0 - 1;
+                        double s = 0.0;
+#pragma unroll
+                        for (int j = 0; j < G; ++j) s += KM[a][1 + j - Z0] * K[k][j];
+                        Mr[a][b] = s;
+                    }
+                int slot = 0;
+#pragma unroll
+                for (int a = 0; a < NZ; ++a)
+#pragma unroll
+                    for (int b = a; b < NZ; ++b) {
+                        NSr[i * NS1 + slot] = scale * (a == b ? Mr[a][a] : Mr[a][b] + Mr[b][a]);
+                        ++slot;
+                    }
+            }
+        });
+        if (has_point) {
+#pragma unroll
+            for (int k = 0; k < BS * NS1; ++k) Pm[lane * PT + k] = NSr[k];
+        }
+        op_fence();
+        for (int idx = lane; idx < ncell * nd; idx += DXO_WAVE) {
+            const int c = idx / nd, a = idx - c * nd;
+            double acc[BS];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+            for (int q = 0; q < nq; ++q) {
+                const double* P = Pm + (c * nq + q) * PT;
+                const double* dp = tab + L.o_dphi + q * L.sdphi + a * G;
+                double z[NZ], pp[NS1];
+                if constexpr (Z0 == 0) z[0] = tab[q * L.sphi + a];
+#pragma unroll
+                for (int k = 0; k < G; ++k) z[1 + k - Z0] = dp[k];
+                int slot = 0;
+#pragma unroll
+                for (int k = 0; k < NZ; ++k)
+#pragma unroll
+                    for (int kk = k; kk < NZ; ++kk) pp[slot++] = z[k] * z[kk];
+#pragma unroll
+                for (int i = 0; i < BS; ++i) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int s2 = 0; s2 < NS1; ++s2) t += pp[s2] * P[i * NS1 + s2];
+                    acc[i] += t;
+                }
+            }
+            const int64_t cell = c0 + c;
+            if (fe) {
+#pragma unroll
+                for (int i = 0; i < BS; ++i) fe[((int64_t)a * m.num_cells_fe + cell) * BS + i] = acc[i];
+            } else {
+                const int64_t node = m.dofmap[cell * nd + a];
+#pragma unroll
+                for (int i = 0; i < BS; ++i) unsafeAtomicAdd(out + node * BS + i, acc[i]);
+            }
+        }
+        op_fence();      // the parked matrices are overwritten by the next group's staged blocks
+    }
+}
+
+// host side: LDS per wave and launch of one (G, BS, TEST, TRIAL)
+template <int G, int BS, int TEST, int TRIAL>
+struct Bilinear {
+    using Rows = BlockRows<OperandShape<G, BS, TEST>::D, OperandShape<G, BS, TRIAL>::D>;
+    static int lds_wave(const dxo_mesh* mesh, bool diag) {
+        const OperandDev& d = mesh->dev;
+        int wd;
+        if (diag) {
+            constexpr int NZ = G + 1 - ((op_has_value<TEST>() || op_has_value<TRIAL>()) ? 0 : 1);
+            const int park = DXO_WAVE * ((BS * NZ * (NZ + 1) / 2) | 1);
+            wd = ((d.cells_per_wave * op_odd(d.ngeom * G) + 1) & ~1) + (park > Rows::LDS_DOUBLES ? park : Rows::LDS_DOUBLES);
+        } else {
+            wd = d.cells_per_wave * (op_odd(d.ndofs * BS) + op_odd(d.ngeom * G)) + DXO_WAVE * (DXO_ADJ_PAD ? ((BS * (G + 1)) | 1) : BS * (G + 1));
+            if (wd < Rows::LDS_DOUBLES) wd = Rows::LDS_DOUBLES;
+        }
+        return (wd + 1) & ~1;        // even: every wave's region starts on a 16-byte boundary
+    }
+    static void launch(const dxo_mesh* mesh, bool diag, int wd, int blocks, size_t shm, const double* C, const double* v, double* out,
+                       double* fe, hipStream_t s) {
+        if (diag) hipLaunchKernelGGL((bilinear_diag<G, BS, TEST, TRIAL>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C,
+                                     mesh->num_cells, out, fe);
+        else hipLaunchKernelGGL((bilinear_apply<G, BS, TEST, TRIAL>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C, v,
+                                mesh->num_cells, out, fe);
+    }
+};
+
+struct BilinearOps {
+    int (*lds_wave)(const dxo_mesh*, bool) = nullptr;
+    void (*launch)(const dxo_mesh*, bool, int, int, size_t, const double*, const double*, double*, double*, hipStream_t) = nullptr;
+};
+
+template <int G, int BS, int TEST, int TRIAL>
+BilinearOps bilinear_ops() {
+    return {&Bilinear<G, BS, TEST, TRIAL>::lds_wave, &Bilinear<G, BS, TEST, TRIAL>::launch};
+}
+
+// the supported pairs (include/dxo.h); DEFGRAD is taken as its linearisation, GRAD
+template <int G>
+BilinearOps bilinear_select_g(int bs, int test, int trial) {
+    constexpr int V = DXO_OPERAND_VALUE, GR = DXO_OPERAND_GRAD, VG = DXO_OPERAND_VALUE_GRAD, EPS = DXO_OPERAND_EPS_MANDEL;
+    if (bs == G) {
+        if (test == GR && trial == GR) return bilinear_ops<G, G, GR, GR>();
+        if (test == EPS && trial == EPS) return bilinear_ops<G, G, EPS, EPS>();
+    } else if (bs == 1) {
+        if (test == GR && trial == VG) return bilinear_ops<G, 1, GR, VG>();
+        if (test == GR && trial == GR) return bilinear_ops<G, 1, GR, GR>();
+        if (test == V && trial == V) return bilinear_ops<G, 1, V, V>();
+        if (test == VG && trial == VG) return bilinear_ops<G, 1, VG, VG>();
+    }
+    return {};
+}
+
+int bilinear_impl(dxo_ctx* ctx, dxo_mesh* mesh, int test, int trial, int bs, const double* C, const double* v, double* out, bool diag) {
+    const char* who = diag ? "dxo_bilinear_diagonal" : "dxo_bilinear_apply";
+    char msg[256];
+    if (!mesh) return dxo_fail(ctx, DXO_E_NULL, diag ? "dxo_bilinear_diagonal: mesh is NULL" : "dxo_bilinear_apply: mesh is NULL");
+    auto nonlinear = [](int k) { return k == DXO_OPERAND_CAUCHY_GREEN || k == DXO_OPERAND_I1 || k == DXO_OPERAND_DETF; };
+    if (nonlinear(test) || nonlinear(trial)) {
+        snprintf(msg, sizeof msg, "%s: a nonlinear operand (C, I1, det F) has no bilinear form — pass its linearisation's block", who);
+        return dxo_fail(ctx, DXO_E_OPTION, msg);
+    }
+    const int t = test == DXO_OPERAND_DEFGRAD ? DXO_OPERAND_GRAD : test, r = trial == DXO_OPERAND_DEFGRAD ? DXO_OPERAND_GRAD : trial;
+    const bool defgrad_ok = (test != DXO_OPERAND_DEFGRAD && trial != DXO_OPERAND_DEFGRAD) || bs == mesh->gdim;
+    const BilinearOps ops = !defgrad_ok ? BilinearOps{} : mesh->gdim == 2 ? bilinear_select_g<2>(bs, t, r) : bilinear_select_g<3>(bs, t, r);
+    if (!ops.launch) {
+        snprintf(msg, sizeof msg, "%s: unsupported pair (test kind %d, trial kind %d, bs %d) on gdim %d: bs = gdim takes (grad|F, grad|F) and "
+                 "(eps, eps); bs = 1 takes (grad, value_grad), (grad, grad), (value, value), (value_grad, value_grad)", who, test, trial, bs, mesh->gdim);
+        return dxo_fail(ctx, DXO_E_OPTION, msg);
+    }
+    if (!mesh->d_wq) {
+        snprintf(msg, sizeof msg, "%s: quadrature weights not set (dxo_mesh_set_weights)", who);
+        return dxo_fail(ctx, DXO_E_OPTION, msg);
+    }
+    if (mesh->num_cells == 0) return DXO_OK;
+    if (!C || !out || (!diag && !v)) {
+        snprintf(msg, sizeof msg, "%s: NULL array", who);
+        return dxo_fail(ctx, DXO_E_NULL, msg);
+    }
+    if (((uintptr_t)C & 15u) != 0) {
+        snprintf(msg, sizeof msg, "%s: C must be 16-byte aligned", who);
+        return dxo_fail(ctx, DXO_E_ALIGN, msg);
+    }
+    const int wd = ops.lds_wave(mesh, diag);
+    const size_t shm = (size_t)(mesh->dev.table_doubles + (DXO_BLOCK / DXO_WAVE) * wd) * sizeof(double);
+    if (shm > 64 * 1024) {
+        snprintf(msg, sizeof msg, "%s: element too large for the LDS budget", who);
+        return dxo_fail(ctx, DXO_E_SIZE, msg);
+    }
+    hipStream_t s = dxo_launch_stream(ctx);
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    double* fe = two_pass_buffer(ctx, mesh, bs, nullptr, mesh->num_cells);
+    int rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    rc = clear_for_atomics(ctx, mesh, bs, out, fe, s);
+    if (rc != DXO_OK) return rc;
+    const int64_t n_groups = (mesh->num_cells + mesh->dev.cells_per_wave - 1) / mesh->dev.cells_per_wave;
+    int64_t blocks = (n_groups + 3) / 4;
+    const int64_t cap = (int64_t)ctx->compute_units * DXO_BL_BLOCKS_PER_CU;
+    if (blocks > cap) blocks = cap;
+    blocks = (blocks + 7) / 8 * 8;
+    ops.launch(mesh, diag, wd, (int)blocks, shm, C, v, out, fe, s);
+    if (fe) launch_node_sum(ctx, mesh, bs, out, s);
+    return dxo_device_end(ctx, s);
+}
+
+}  // namespace
+
+extern "C" int dxo_bilinear_apply(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, const double* v,
+                                  double* out) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    return bilinear_impl(ctx, mesh, test_kind, trial_kind, bs, C, v, out, false);
+}
+
+extern "C" int dxo_bilinear_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, double* out) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    return bilinear_impl(ctx, mesh, test_kind, trial_kind, bs, C, nullptr, out, true);
+}

@@ -268,6 +268,30 @@ class DeviceMesh:
         rc = self.ctx.lib.dxo_tangent_diagonal(self.ctx._h, self._h, C.c_void_p(C_tang_ptr), C.c_void_p(out_ptr))
         self.ctx.check(rc, "dxo_tangent_diagonal")
 
+    # (test, trial, bs == gdim) pairs of dxo_bilinear_apply; "F" stands for its linearisation, grad
+    BILINEAR_PAIRS_VECTOR = {("grad", "grad"), ("grad", "F"), ("F", "grad"), ("F", "F"), ("eps", "eps")}
+    BILINEAR_PAIRS_SCALAR = {("grad", "value_grad"), ("grad", "grad"), ("value", "value"), ("value_grad", "value_grad")}
+
+    def _bilinear_kinds(self, test: str, trial: str, bs: int) -> tuple[int, int]:
+        pairs = self.BILINEAR_PAIRS_VECTOR if int(bs) == self.gdim else self.BILINEAR_PAIRS_SCALAR if int(bs) == 1 else set()
+        if (test, trial) not in pairs:
+            raise ValueError(f"bilinear form: unsupported pair ({test!r}, {trial!r}) with bs = {bs} on gdim {self.gdim}; bs = gdim takes "
+                             f"{sorted(self.BILINEAR_PAIRS_VECTOR)}, bs = 1 takes {sorted(self.BILINEAR_PAIRS_SCALAR)}")
+        return KINDS[test], KINDS[trial]
+
+    def bilinear_apply(self, test: str, trial: str, bs: int, C_ptr: int, v_ptr: int, out_ptr: int) -> None:
+        """out += sum_q w |det J| B_test^T C B_trial v (DEVICE pointers; C [num_cells*nq][D_test][D_trial], 16-byte aligned): the action of
+        the bilinear form inner(C : trial(u_hat), test(v)) dx — e.g. ("grad", "grad", gdim) with C = dP/dF, the hyperelastic Jacobian."""
+        t, r = self._bilinear_kinds(test, trial, bs)
+        rc = self.ctx.lib.dxo_bilinear_apply(self.ctx._h, self._h, t, r, int(bs), C.c_void_p(C_ptr), C.c_void_p(v_ptr), C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_bilinear_apply")
+
+    def bilinear_diagonal(self, test: str, trial: str, bs: int, C_ptr: int, out_ptr: int) -> None:
+        """out += diag of the same operator as bilinear_apply (DEVICE pointers): Jacobi preconditioner."""
+        t, r = self._bilinear_kinds(test, trial, bs)
+        rc = self.ctx.lib.dxo_bilinear_diagonal(self.ctx._h, self._h, t, r, int(bs), C.c_void_p(C_ptr), C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_bilinear_diagonal")
+
     def tangent_apply_vm(self, prm, sigma_ptr: int, dp_ptr: int, v_ptr: int, out_ptr: int) -> None:
         """out += K v with the von Mises consistent tangent formed per point from the operator's returned (sigma, dp) — no C_tang
         array (dxo_tangent_apply_vm; DEVICE pointers, e.g. VmState.pointers()): 56 instead of 288 bytes per point."""

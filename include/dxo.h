@@ -527,6 +527,22 @@ int dxo_von_mises_residual(dxo_ctx* ctx, const dxo_vm_params* prm, dxo_mesh* mes
                            const double* p, double* sigma, double* dp, double* R);
 /* out[dof] += K_(dof,dof): the diagonal of the same operator (Jacobi preconditioner of a matrix-free Krylov solve). */
 int dxo_tangent_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, double* out);
+/* The bilinear form of a general PAIR of linear operand kinds of one field with block size bs, per-point block C (DEVICE pointers):
+ *   dxo_bilinear_apply    : out[dof] += sum_q w_q |det J_q| B_test,q^T C_q B_trial,q v
+ *   dxo_bilinear_diagonal : out[dof] += sum_q w_q |det J_q| (B_test,q^T C_q B_trial,q)_(dof,dof)
+ * C: [n][D_test][D_trial] row-major fp64, n = num_cells*nq points of ALL cells of the mesh in cell order (no entity subsets), D_* the
+ * value size of the kind (dxo_operand_value_size); 16-byte aligned, as the operator outputs are. Supported pairs (test, trial):
+ *   bs = gdim : (GRAD | DEFGRAD, GRAD | DEFGRAD)  finite strain, C = dP/dF of dxo_isihara[_field] / dxo_icnn[_field] ([n][4][4] in 2-D);
+ *                                                 DEFGRAD stands for its linearisation, grad
+ *               (EPS_MANDEL, EPS_MANDEL)          agrees with dxo_tangent_apply / dxo_tangent_diagonal on the same C_tang
+ *   bs = 1    : (GRAD, VALUE_GRAD)                heat: C = [dq/dT | dq/dsigma], [n][gdim][1 + gdim]
+ *               (GRAD, GRAD), (VALUE, VALUE), (VALUE_GRAD, VALUE_GRAD)
+ * Any other pair, and the nonlinear kinds (C, I1, det F), return DXO_E_OPTION with a message in dxo_last_error. The quadrature weights
+ * must be set (dxo_mesh_set_weights; DXO_E_OPTION otherwise). `out` is accumulated into, or SET with option "consumer_overwrite" = 1;
+ * option "adjoint_atomics" as for dxo_tangent_apply (default: element vectors + node sums, bit-reproducible). The first call on a mesh
+ * allocates the element-vector buffer; later calls allocate nothing (capture-safe). */
+int dxo_bilinear_apply(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, const double* v, double* out);
+int dxo_bilinear_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, double* out);
 
 /* ---- coefficient assigners on the device, DEVICE memory only --------------------------
  * One scatter for the reference's three dofmap assigners (src/dolfinx_external_operator/external_operator.py):
