@@ -174,6 +174,7 @@ static int64_t* option_slot(dxo_ctx* c, const char* key) {
     if (!std::strcmp(key, "mc_waves_per_simd")) return &c->mc_waves_per_simd;
     if (!std::strcmp(key, "icnn_variant")) return &c->icnn_variant;
     if (!std::strcmp(key, "adjoint_atomics")) return &c->adjoint_atomics;
+    if (!std::strcmp(key, "assemble_chunk_cells")) return &c->assemble_chunk_cells;
     if (!std::strcmp(key, "adjoint_patch")) return &c->adjoint_patch;
     if (!std::strcmp(key, "adjoint_mfma")) return &c->adjoint_mfma;
     if (!std::strcmp(key, "mgpu_chunks")) return &c->mgpu_chunks;

@@ -14,10 +14,11 @@ reference's Expression re-reads the Function's vector.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 
-from ._lib import MEM_DEVICE, MEM_HOST, Context, DxoError, default_context
+from ._lib import MEM_DEVICE, MEM_HOST, Context, DxoError, _CudaArrayView, default_context
 
 KINDS = {"value": 0, "grad": 1, "eps": 2, "F": 3, "value_grad": 4,
          # nonlinear operands of F = I + grad u (the reference's own operand test, test/test_operands_evaluation.py:32-36): forward only
@@ -292,6 +293,37 @@ class DeviceMesh:
         rc = self.ctx.lib.dxo_bilinear_diagonal(self.ctx._h, self._h, t, r, int(bs), C.c_void_p(C_ptr), C.c_void_p(out_ptr))
         self.ctx.check(rc, "dxo_bilinear_diagonal")
 
+    def csr_pattern(self, bs: int) -> "CsrPattern":
+        """The CSR pattern of this mesh's field with block size bs (dxo_csr_create): built once per block size and kept by the mesh."""
+        pats = self.__dict__.setdefault("_csr", {})
+        if int(bs) not in pats:
+            pats[int(bs)] = CsrPattern(self, int(bs))
+        return pats[int(bs)]
+
+    def bilinear_assemble(self, test: str, trial: str, bs: int, C_ptr: int, pattern: "CsrPattern", values=None, bcs=None,
+                          diagonal: float = 1.0) -> "DeviceCSR":
+        """The bilinear form of bilinear_apply ASSEMBLED on `pattern` (dxo_bilinear_assemble): values (+)= sum_cells sum_q w |det J|
+        B_test^T C B_trial, C a DEVICE pointer as for bilinear_apply. `values`: a float64 CUDA tensor of pattern.nnz entries, accumulated
+        into (SET with option consumer_overwrite); None: a new zero tensor. `bcs`: an int32 CUDA tensor of constrained dofs, whose rows and
+        columns are then zeroed and whose diagonal is set to `diagonal` (dxo_csr_dirichlet), as assemble_matrix(J, bcs) does."""
+        import torch
+
+        t, r = self._bilinear_kinds(test, trial, bs)
+        if values is None:
+            values = torch.zeros(pattern.nnz, dtype=torch.float64, device=torch.device("cuda", self.ctx.device))
+        if not (values.dtype == torch.float64 and values.is_cuda and values.is_contiguous() and values.numel() == pattern.nnz):
+            raise ValueError(f"bilinear_assemble: values must be a contiguous float64 CUDA tensor of {pattern.nnz} entries")
+        rc = self.ctx.lib.dxo_bilinear_assemble(self.ctx._h, self._h, pattern._h, t, r, int(bs), C.c_void_p(C_ptr),
+                                                C.c_void_p(values.data_ptr()))
+        self.ctx.check(rc, "dxo_bilinear_assemble")
+        if bcs is not None:
+            if not (bcs.dtype == torch.int32 and bcs.is_cuda and bcs.is_contiguous()):
+                raise ValueError("bilinear_assemble: bcs must be a contiguous int32 CUDA tensor")
+            rc = self.ctx.lib.dxo_csr_dirichlet(self.ctx._h, pattern._h, C.c_void_p(bcs.data_ptr()), int(bcs.numel()), float(diagonal),
+                                                C.c_void_p(values.data_ptr()))
+            self.ctx.check(rc, "dxo_csr_dirichlet")
+        return DeviceCSR(pattern, values)
+
     def tangent_apply_vm(self, prm, sigma_ptr: int, dp_ptr: int, v_ptr: int, out_ptr: int) -> None:
         """out += K v with the von Mises consistent tangent formed per point from the operator's returned (sigma, dp) — no C_tang
         array (dxo_tangent_apply_vm; DEVICE pointers, e.g. VmState.pointers()): 56 instead of 288 bytes per point."""
@@ -321,6 +353,8 @@ class DeviceMesh:
         self.ctx.check(rc, "dxo_heat_field")
 
     def close(self) -> None:
+        for pat in self.__dict__.pop("_csr", {}).values():
+            pat.close()
         if getattr(self, "_h", None) and self.ctx._h:
             self.ctx.lib.dxo_mesh_destroy(self.ctx._h, self._h)
         self._h = None
@@ -330,6 +364,77 @@ class DeviceMesh:
             self.close()
         except Exception:
             pass
+
+
+class CsrPattern:
+    """dxo_csr: the CSR pattern of one Lagrange field with block size bs on a DeviceMesh. Rows and columns are the blocked dofs
+    node*bs + i; a row holds the columns of every node that shares a cell with its node, sorted, diagonal included (DOLFINx's layout for
+    a serial blocked space). `indptr` (int64) / `indices` (int32) are device copies of the library's arrays; `build_ms` the build time."""
+
+    def __init__(self, mesh: DeviceMesh, bs: int):
+        self.ctx, self.bs, self.gdim = mesh.ctx, int(bs), mesh.gdim
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.dxo_csr_create(self.ctx._h, mesh._h, self.bs, C.byref(h)), "dxo_csr_create")
+        self._h = h
+        self._fin = weakref.finalize(self, CsrPattern._destroy, self.ctx, h)
+        n_rows, nnz, rp, col, ms = C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_double()
+        self.ctx.check(self.ctx.lib.dxo_csr_info(self.ctx._h, h, C.byref(n_rows), C.byref(nnz), C.byref(rp), C.byref(col), C.byref(ms)),
+                       "dxo_csr_info")
+        self.n_rows, self.nnz, self.build_ms = n_rows.value, nnz.value, ms.value
+        self._rp, self._col = rp.value, col.value
+        self._indptr = self._indices = None
+
+    @staticmethod
+    def _destroy(ctx, h):
+        ctx.lib.dxo_csr_destroy(ctx._h, h)      # a closed context passes NULL: the pattern's device arrays are still freed
+
+    def _copy(self, ptr: int, n: int, typestr: str):
+        import torch
+
+        dev = torch.device("cuda", self.ctx.device)
+        if n == 0:
+            return torch.empty(0, dtype=torch.int64 if typestr == "<i8" else torch.int32, device=dev)
+        return torch.as_tensor(_CudaArrayView(self, ptr, n, typestr), device=dev).clone()
+
+    @property
+    def indptr(self):
+        if self._indptr is None:
+            self._indptr = self._copy(self._rp, self.n_rows + 1, "<i8")
+        return self._indptr
+
+    @property
+    def indices(self):
+        if self._indices is None:
+            self._indices = self._copy(self._col, self.nnz, "<i4")
+        return self._indices
+
+    def close(self) -> None:
+        self._fin()
+
+
+class DeviceCSR:
+    """An assembled matrix: `values` (float64 CUDA tensor, nnz) on `pattern`."""
+
+    def __init__(self, pattern: CsrPattern, values):
+        self.pattern, self.values = pattern, values
+        self.shape = (pattern.n_rows, pattern.n_rows)
+
+    def to_torch(self):
+        """torch.sparse_csr_tensor on the device (both index arrays int64, as torch requires one index dtype)."""
+        import torch
+
+        return torch.sparse_csr_tensor(self.pattern.indptr, self.pattern.indices.to(torch.int64), self.values, size=self.shape)
+
+    def to_numpy(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(indptr, indices, values) copied to the host."""
+        return self.pattern.indptr.cpu().numpy(), self.pattern.indices.cpu().numpy(), self.values.cpu().numpy()
+
+    def to_scipy(self):
+        """scipy.sparse.csr_matrix, copied to the host."""
+        import scipy.sparse
+
+        indptr, indices, values = self.to_numpy()
+        return scipy.sparse.csr_matrix((values, indices, indptr), shape=self.shape)
 
 
 class DeviceOperand:

@@ -543,6 +543,32 @@ int dxo_tangent_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, dou
  * allocates the element-vector buffer; later calls allocate nothing (capture-safe). */
 int dxo_bilinear_apply(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, const double* v, double* out);
 int dxo_bilinear_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, double* out);
+/* The same bilinear form ASSEMBLED into a sparse matrix on the device: what the demos hand to their LU solve,
+ * assemble_matrix(J_replaced, bcs) (demo_plasticity_von_mises.py:422-434, demo_plasticity_mohr_coulomb.py:662-675,
+ * demo_hyperelasticity.py:560-573; the heat demo compares assembled matrices, demo_nonlinear_heat_equation_part2.py:313-335).
+ * dxo_csr_create  : the CSR pattern of one Lagrange field with block size bs (1 or gdim) on `mesh`, built once on the host from the
+ *                   mesh's dofmap. Rows and columns are the blocked dofs node*bs + i (DOLFINx's numbering of a serial blocked space);
+ *                   row r holds every column whose node shares a cell with r's node, for all bs components, sorted ascending; the
+ *                   diagonal is always present. row_ptr is int64 [n_rows + 1], col int32 [nnz] (2^31 dofs or more: DXO_E_SIZE).
+ * dxo_csr_info    : sizes, the DEVICE arrays owned by the pattern, and the pattern's build time in ms; any pointer may be NULL.
+ * dxo_bilinear_assemble : values[nnz] += sum_cells sum_q w_q |det J_q| B_test,q^T C_q B_trial,q, for the pairs and the C layout of
+ *                   dxo_bilinear_apply (DEVICE pointers; all cells of the mesh). DXO_E_OPTION for other pairs or missing weights,
+ *                   DXO_E_DIM for a pattern of another mesh or block size. Option "consumer_overwrite" = 1 SETs values. Default form:
+ *                   element matrices of a chunk of cells (option "assemble_chunk_cells", 0 = as many as fit 1 GiB of scratch) go to a
+ *                   scratch buffer, then one thread per row adds them in ascending cell order: atomic-free, bit-reproducible and
+ *                   bitwise independent of the chunk size. Option "adjoint_atomics" = 1: fp64 atomics into values (reproducible to
+ *                   rounding only). The first call on a pattern allocates the scratch; later calls allocate nothing (capture-safe).
+ * dxo_csr_dirichlet : the rows and columns of the constrained dofs (DEVICE int32 list; out-of-range entries are ignored) are zeroed
+ *                   and their diagonal entries set to `diagonal`, as assemble_matrix(a, bcs, diagonal) does (one thread per row,
+ *                   deterministic, capture-safe). */
+typedef struct dxo_csr dxo_csr;
+int dxo_csr_create(dxo_ctx* ctx, dxo_mesh* mesh, int bs, dxo_csr** out);
+int dxo_csr_destroy(dxo_ctx* ctx, dxo_csr* csr);
+int dxo_csr_info(dxo_ctx* ctx, const dxo_csr* csr, int64_t* n_rows, int64_t* nnz, const int64_t** row_ptr, const int32_t** col,
+                 double* build_ms);
+int dxo_bilinear_assemble(dxo_ctx* ctx, dxo_mesh* mesh, dxo_csr* csr, int test_kind, int trial_kind, int bs, const double* C,
+                          double* values);
+int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n_dofs, double diagonal, double* values);
 
 /* ---- coefficient assigners on the device, DEVICE memory only --------------------------
  * One scatter for the reference's three dofmap assigners (src/dolfinx_external_operator/external_operator.py):
