@@ -158,6 +158,12 @@ _SIGNATURES = {
     "dxo_csr_info": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_double)]),
     "dxo_bilinear_assemble": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dxo_csr_dirichlet": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, _P]),
+    "dxo_mesh_set_facet_geometry": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "dxo_facet_set_create": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
+    "dxo_facet_set_destroy": (C.c_int, [_P, _P]),
+    "dxo_eval_facet_geometry": (C.c_int, [_P, _P, _P, _P, _P]),
+    "dxo_facet_adjoint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "dxo_facet_pressure": (C.c_int, [_P, _P, _P, _P, C.c_double, _P]),
     "dxo_tangent_apply_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P, _P]),
     "dxo_von_mises_residual": (C.c_int, [_P, C.POINTER(VmParams), _P, _P, _P, _P, _P, _P, _P]),
     "dxo_tangent_diagonal_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P]),

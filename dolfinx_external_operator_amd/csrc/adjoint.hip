@@ -201,45 +201,6 @@ struct VmPoint {
     }
 };
 
-// Mandel / row-major operand value -> dual tensor Ghat[i][j] = d(pairing)/d(grad u)_ij, and the value part
-template <int G, int BS, int KIND>
-__device__ __forceinline__ void dual_tensor(const double (&s)[OperandShape<G, BS, KIND>::D], double (&vh)[BS],
-                                            double (&gh)[BS][G]) {
-    constexpr double r2 = 0.70710678118654752440;
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-        vh[i] = 0.0;
-#pragma unroll
-        for (int j = 0; j < G; ++j) gh[i][j] = 0.0;
-    }
-    if constexpr (KIND == DXO_OPERAND_VALUE) {
-#pragma unroll
-        for (int i = 0; i < BS; ++i) vh[i] = s[i];
-    } else if constexpr (KIND == DXO_OPERAND_GRAD || KIND == DXO_OPERAND_DEFGRAD) {
-#pragma unroll
-        for (int i = 0; i < BS; ++i)
-#pragma unroll
-            for (int j = 0; j < G; ++j) gh[i][j] = s[i * G + j];
-    } else if constexpr (KIND == DXO_OPERAND_VALUE_GRAD) {
-#pragma unroll
-        for (int i = 0; i < BS; ++i) {
-            vh[i] = s[i];
-#pragma unroll
-            for (int j = 0; j < G; ++j) gh[i][j] = s[BS + i * G + j];
-        }
-    } else if constexpr (KIND == DXO_OPERAND_DIV) {      // pairing s div v: Ghat = s I
-#pragma unroll
-        for (int i = 0; i < G; ++i) gh[i % BS][i] = s[0];
-    } else {   // EPS_MANDEL: e = [g00, g11, (g22 | 0), r(g01+g10), r(g02+g20), r(g12+g21)]
-        if constexpr (G == 2) {
-            gh[0][0] = s[0]; gh[1][1] = s[1]; gh[0][1] = gh[1][0] = r2 * s[3];
-        } else {
-            gh[0][0] = s[0]; gh[1][1] = s[1]; gh[2][2] = s[2];
-            gh[0][1] = gh[1][0] = r2 * s[3]; gh[0][2] = gh[2][0] = r2 * s[4]; gh[1][2] = gh[2][1] = r2 * s[5];
-        }
-    }
-}
-
 // Phase 1 tail + phase 2: park (vh, T) of this lane's point, then scatter the cell-node sums. W layout behind the
 // gathered data: Tm[point][BS*(G+1)].
 template <int G, int BS>

@@ -1,0 +1,456 @@
+// facet_form.hip — boundary-facet integrals (ds): facet normals, the facet measure, and the load vectors of a residual's
+// boundary term. The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253)
+// is dxo_operand_adjoint(EPS_MANDEL) + dxo_facet_pressure(scale = loading).
+//
+// Geometry at a facet point of the entity (cell, f): J = sum_v X_v dpsi_f,v (the facet dpsi table, exactly as operand_facet.hip
+// rebuilds it), J_f = J J_ref_f, dS = w_q sqrt(det(J_f^T J_f)), n = J^-T n_ref / |J^-T n_ref|. J^-T maps a covector, so n is outward
+// for either sign of det J (J v points out of the cell when v points out of the reference cell, and n . J v = n_ref . v / |.|).
+//
+// Boundary work is O(N^((d-1)/d)): this is not a bandwidth kernel. Every call is two launches:
+//   facet_element : a workgroup takes floor(256 / nq) entities. Phase 1, lane = (entity, point): geometry and the point's dual data
+//                   (vh[BS], T[BS][G] = dS * the dual tensor pulled back to reference gradients; for the pressure vh = dS p n) into LDS.
+//                   Phase 2, lane = (entity, local dof): the fixed-order sum over the entity's points into fe[entity][a][i].
+//   facet_node_sum: lane = touched node, adds the node's entries of fe in ascending entity order (the set's transposed incidence).
+// No atomics: the result is bit-reproducible. The calls always accumulate into out.
+#include "dxo_common.h"
+#include "operand_core.h"
+
+#include <algorithm>
+
+struct dxo_facet_set {
+    const dxo_mesh* mesh = nullptr;
+    int64_t n = 0;
+    int nd = 0, nf = 0;
+    int32_t* d_ents = nullptr;       // [n][2] (cell, local facet)
+    double* d_fe = nullptr;          // [n][nd][gdim] element vectors of the last call
+    int64_t n_touched = 0;           // nodes with at least one incidence
+    int32_t* d_tnode = nullptr;      // [n_touched] the nodes, ascending
+    int64_t* d_tptr = nullptr;       // [n_touched + 1]
+    uint32_t* d_tent = nullptr;      // [n * nd] entries e * nd + a of each node, ascending entity order
+};
+
+namespace {
+
+constexpr int FACET_PRESSURE = -1;   // facet_element's "kind" for the pressure load
+
+// the facet tables and geometry of a mesh, as device pointers
+template <int G>
+struct FacetTabs {
+    int nqf, nd, ng;
+    const double* phi;      // [nf][nqf][nd]
+    const double* dphi;     // [nf][nqf][nd][G]
+    const double* dpsi;     // [nf][nqf][ng][G]
+    const double* w;        // [nqf]
+    const double* nref;     // [nf][G]
+    const double* jref;     // [nf][G][G-1]
+};
+
+template <int G>
+FacetTabs<G> facet_tabs(const dxo_mesh* m) {
+    const size_t nd = (size_t)m->dev.ndofs, nf = (size_t)m->n_local_facets, nqf = (size_t)m->nq_facet;
+    FacetTabs<G> t;
+    t.nqf = (int)nqf;
+    t.nd = (int)nd;
+    t.ng = m->dev.ngeom;
+    t.phi = m->d_facet_tab;
+    t.dphi = t.phi + nf * nqf * nd;
+    t.dpsi = t.dphi + nf * nqf * nd * G;
+    t.w = m->d_facet_geom;
+    t.nref = t.w + nqf;
+    t.jref = t.nref + nf * G;
+    return t;
+}
+
+// J^-1 (K), the outward unit normal and the point measure at point q of facet f of `cell`
+template <int G>
+__device__ __forceinline__ void facet_point_geometry(const OperandDev& m, const FacetTabs<G>& t, int64_t cell, int f, int q,
+                                                     double (&K)[G][G], double (&nrm)[G], double& dS) {
+    const double* dpsi = t.dpsi + ((size_t)f * t.nqf + q) * t.ng * G;
+    double J[G][G];
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+#pragma unroll
+        for (int k = 0; k < G; ++k) J[j][k] = 0.0;
+    for (int v = 0; v < t.ng; ++v) {
+        const int64_t node = m.geom_dofmap[cell * t.ng + v];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const double xj = m.x[node * G + j];
+#pragma unroll
+            for (int k = 0; k < G; ++k) J[j][k] += xj * dpsi[v * G + k];
+        }
+    }
+    (void)invert<G>(J, K);
+    // n ~ J^-T n_ref: n_j = sum_k K[k][j] n_ref_k
+    const double* nr = t.nref + (size_t)f * G;
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        double v = 0.0;
+#pragma unroll
+        for (int k = 0; k < G; ++k) v += K[k][j] * nr[k];
+        nrm[j] = v;
+        s += v * v;
+    }
+    const double inv = 1.0 / sqrt(s);
+#pragma unroll
+    for (int j = 0; j < G; ++j) nrm[j] *= inv;
+    // J_f = J J_ref_f (G x (G-1)); sqrt(det(J_f^T J_f)) = |column| in 2-D, |a x b| in 3-D
+    const double* jr = t.jref + (size_t)f * G * (G - 1);
+    double Jf[G][G - 1];
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+#pragma unroll
+        for (int l = 0; l < G - 1; ++l) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k) v += J[j][k] * jr[k * (G - 1) + l];
+            Jf[j][l] = v;
+        }
+    double meas;
+    if constexpr (G == 2) {
+        meas = sqrt(Jf[0][0] * Jf[0][0] + Jf[1][0] * Jf[1][0]);
+    } else {
+        const double c0 = Jf[1][0] * Jf[2][1] - Jf[2][0] * Jf[1][1];
+        const double c1 = Jf[2][0] * Jf[0][1] - Jf[0][0] * Jf[2][1];
+        const double c2 = Jf[0][0] * Jf[1][1] - Jf[1][0] * Jf[0][1];
+        meas = sqrt(c0 * c0 + c1 * c1 + c2 * c2);
+    }
+    dS = t.w[q] * meas;
+}
+
+template <int G>
+__global__ __launch_bounds__(DXO_BLOCK) void facet_geometry(OperandDev m, FacetTabs<G> t, const int32_t* __restrict__ ents, int64_t n,
+                                                            double* __restrict__ normals, double* __restrict__ dS) {
+    const int64_t total = n * t.nqf, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t e = i / t.nqf;
+        const int q = (int)(i - e * t.nqf);
+        double K[G][G], nrm[G], ds;
+        facet_point_geometry<G>(m, t, ents[2 * e], ents[2 * e + 1], q, K, nrm, ds);
+        if (normals) {
+#pragma unroll
+            for (int j = 0; j < G; ++j) normals[i * G + j] = nrm[j];
+        }
+        if (dS) dS[i] = ds;
+    }
+}
+
+// element vectors of the entities: fe[e][a][i] = sum_q (vh_q[i] phi_a + sum_k T_q[i][k] dphi_a,k) at the entity's facet points.
+// KIND: a linear operand kind (S [n][nq][D]) or FACET_PRESSURE (p [n][nq] or NULL, vh = scale p n dS, no gradient part).
+template <int G, int BS, int KIND>
+__global__ __launch_bounds__(DXO_BLOCK) void facet_element(OperandDev m, FacetTabs<G> t, const int32_t* __restrict__ ents, int64_t n,
+                                                           const double* __restrict__ S, double scale, double* __restrict__ fe) {
+    constexpr bool GRAD_PART = KIND != FACET_PRESSURE && KIND != DXO_OPERAND_VALUE;
+    constexpr int PW = GRAD_PART ? BS * (1 + G) : BS;    // doubles parked per point
+    extern __shared__ double lds[];
+    const int nqf = t.nqf, nd = t.nd;
+    const int epb = DXO_BLOCK / nqf;                      // entities per workgroup and round
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < n; e0 += (int64_t)gridDim.x * epb) {
+        const int ne = (int)(n - e0 < epb ? n - e0 : epb);
+        if ((int)threadIdx.x < ne * nqf) {
+            const int le = threadIdx.x / nqf, q = threadIdx.x - le * nqf;
+            const int64_t e = e0 + le;
+            double K[G][G], nrm[G], ds;
+            facet_point_geometry<G>(m, t, ents[2 * e], ents[2 * e + 1], q, K, nrm, ds);
+            double* P = lds + threadIdx.x * PW;
+            if constexpr (KIND == FACET_PRESSURE) {
+                const double pv = scale * ds * (S ? S[e * nqf + q] : 1.0);
+#pragma unroll
+                for (int i = 0; i < G; ++i) P[i] = pv * nrm[i];
+            } else {
+                constexpr int D = OperandShape<G, BS, KIND>::D;
+                double s[D], vh[BS], gh[BS][G];
+#pragma unroll
+                for (int k = 0; k < D; ++k) s[k] = S[(e * nqf + q) * D + k];
+                dual_tensor<G, BS, KIND>(s, vh, gh);
+#pragma unroll
+                for (int i = 0; i < BS; ++i) P[i] = ds * vh[i];
+                if constexpr (GRAD_PART) {
+                    // pulled back to reference gradients: T[i][k] = dS sum_j gh[i][j] K[k][j]
+#pragma unroll
+                    for (int i = 0; i < BS; ++i)
+#pragma unroll
+                        for (int k = 0; k < G; ++k) {
+                            double v = 0.0;
+#pragma unroll
+                            for (int j = 0; j < G; ++j) v += gh[i][j] * K[k][j];
+                            P[BS + i * G + k] = ds * v;
+                        }
+                }
+            }
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < ne * nd; idx += blockDim.x) {
+            const int le = idx / nd, a = idx - le * nd;
+            const int64_t e = e0 + le;
+            const int f = ents[2 * e + 1];
+            double acc[BS];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+            for (int q = 0; q < nqf; ++q) {
+                const double* P = lds + (le * nqf + q) * PW;
+                const size_t row = ((size_t)f * nqf + q) * nd + a;
+                const double ph = t.phi[row];
+#pragma unroll
+                for (int i = 0; i < BS; ++i) acc[i] += P[i] * ph;
+                if constexpr (GRAD_PART) {
+#pragma unroll
+                    for (int k = 0; k < G; ++k) {
+                        const double dk = t.dphi[row * G + k];
+#pragma unroll
+                        for (int i = 0; i < BS; ++i) acc[i] += P[BS + i * G + k] * dk;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < BS; ++i) fe[(e * nd + a) * BS + i] = acc[i];
+        }
+        __syncthreads();     // the next round overwrites the parked points
+    }
+}
+
+// out[node] += the node's element-vector entries, added in ascending entity order
+template <int BS>
+__global__ __launch_bounds__(DXO_BLOCK) void facet_node_sum(int64_t n_touched, const int32_t* __restrict__ tnode,
+                                                            const int64_t* __restrict__ tptr, const uint32_t* __restrict__ tent,
+                                                            const double* __restrict__ fe, double* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_touched; t += stride) {
+        double acc[BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+        for (int64_t j = tptr[t]; j < tptr[t + 1]; ++j) {
+            const double* src = fe + (int64_t)tent[j] * BS;
+#pragma unroll
+            for (int i = 0; i < BS; ++i) acc[i] += src[i];
+        }
+        const int64_t node = tnode[t];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) out[node * BS + i] += acc[i];
+    }
+}
+
+int grid(const dxo_ctx* ctx, int64_t units) {
+    int64_t blocks = std::max<int64_t>(1, (units + DXO_BLOCK - 1) / DXO_BLOCK);
+    return (int)std::min<int64_t>(blocks, (int64_t)ctx->compute_units * 8);
+}
+
+template <int G, int BS, int KIND>
+void launch_element(const dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, const double* S, double scale, hipStream_t s) {
+    constexpr int PW = (KIND != FACET_PRESSURE && KIND != DXO_OPERAND_VALUE) ? BS * (1 + G) : BS;
+    const FacetTabs<G> t = facet_tabs<G>(m);
+    const int epb = DXO_BLOCK / t.nqf;
+    int64_t blocks = (set->n + epb - 1) / epb;
+    blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)ctx->compute_units * 8));
+    const size_t shm = (size_t)epb * t.nqf * PW * sizeof(double);
+    hipLaunchKernelGGL((facet_element<G, BS, KIND>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents, set->n, S, scale,
+                       set->d_fe);
+}
+
+void launch_node_sum(const dxo_ctx* ctx, const dxo_facet_set* set, int bs, double* out, hipStream_t s) {
+    const int blocks = grid(ctx, set->n_touched);
+    if (bs == 1) hipLaunchKernelGGL(facet_node_sum<1>, dim3(blocks), dim3(DXO_BLOCK), 0, s, set->n_touched, set->d_tnode, set->d_tptr, set->d_tent, set->d_fe, out);
+    else if (bs == 2) hipLaunchKernelGGL(facet_node_sum<2>, dim3(blocks), dim3(DXO_BLOCK), 0, s, set->n_touched, set->d_tnode, set->d_tptr, set->d_tent, set->d_fe, out);
+    else hipLaunchKernelGGL(facet_node_sum<3>, dim3(blocks), dim3(DXO_BLOCK), 0, s, set->n_touched, set->d_tnode, set->d_tptr, set->d_tent, set->d_fe, out);
+}
+
+template <int G, int BS>
+int dispatch_adjoint(const dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, int kind, const double* S, hipStream_t s) {
+    switch (kind) {
+        case DXO_OPERAND_VALUE: launch_element<G, BS, DXO_OPERAND_VALUE>(ctx, m, set, S, 1.0, s); return DXO_OK;
+        case DXO_OPERAND_GRAD: launch_element<G, BS, DXO_OPERAND_GRAD>(ctx, m, set, S, 1.0, s); return DXO_OK;
+        case DXO_OPERAND_VALUE_GRAD: launch_element<G, BS, DXO_OPERAND_VALUE_GRAD>(ctx, m, set, S, 1.0, s); return DXO_OK;
+        case DXO_OPERAND_EPS_MANDEL:
+            if constexpr (BS == G) { launch_element<G, BS, DXO_OPERAND_EPS_MANDEL>(ctx, m, set, S, 1.0, s); return DXO_OK; }
+            return DXO_E_DIM;
+        case DXO_OPERAND_DEFGRAD:
+            if constexpr (BS == G) { launch_element<G, BS, DXO_OPERAND_DEFGRAD>(ctx, m, set, S, 1.0, s); return DXO_OK; }
+            return DXO_E_DIM;
+        case DXO_OPERAND_DIV:
+            if constexpr (BS == G) { launch_element<G, BS, DXO_OPERAND_DIV>(ctx, m, set, S, 1.0, s); return DXO_OK; }
+            return DXO_E_DIM;
+    }
+    return DXO_E_OPTION;
+}
+
+// checks shared by the three calls; DXO_OK when the set may be used on the mesh
+int facet_ready(dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, const char* who) {
+    char buf[160];
+    if (!m || !set) {
+        std::snprintf(buf, sizeof buf, "%s: mesh or facet set is NULL", who);
+        return dxo_fail(ctx, DXO_E_NULL, buf);
+    }
+    if (!m->d_facet_tab || !m->d_facet_geom) {
+        std::snprintf(buf, sizeof buf, "%s: facet tables or facet geometry not set (dxo_mesh_set_facet_tables, dxo_mesh_set_facet_geometry)", who);
+        return dxo_fail(ctx, DXO_E_OPTION, buf);
+    }
+    if (set->mesh != m) {
+        std::snprintf(buf, sizeof buf, "%s: the facet set was created on another mesh", who);
+        return dxo_fail(ctx, DXO_E_DIM, buf);
+    }
+    if (m->nf_geom != m->n_local_facets || m->nq_geom != m->nq_facet || set->nf > m->n_local_facets || m->nq_facet > DXO_BLOCK) {
+        std::snprintf(buf, sizeof buf, "%s: facet tables, facet geometry and facet set disagree on (n_local_facets, nq)", who);
+        return dxo_fail(ctx, DXO_E_DIM, buf);
+    }
+    return DXO_OK;
+}
+
+void set_free(dxo_facet_set* set) {
+    if (set->d_ents) (void)hipFree(set->d_ents);
+    if (set->d_fe) (void)hipFree(set->d_fe);
+    if (set->d_tnode) (void)hipFree(set->d_tnode);
+    if (set->d_tptr) (void)hipFree(set->d_tptr);
+    if (set->d_tent) (void)hipFree(set->d_tent);
+    delete set;
+}
+
+int set_build(dxo_ctx* ctx, dxo_facet_set* set, const dxo_mesh* m, const int32_t* ents) {
+    const int64_t n = set->n, nd = set->nd;
+    const std::vector<int32_t>& dm = m->h_dofmap;
+    // transposed incidence over the touched nodes: entries visited in ascending (entity, a)
+    std::vector<int64_t> count((size_t)m->num_field_nodes + 1, 0);
+    for (int64_t e = 0; e < n; ++e)
+        for (int64_t a = 0; a < nd; ++a) ++count[(size_t)dm[(size_t)(ents[2 * e] * nd + a)] + 1];
+    std::vector<int32_t> tnode;
+    std::vector<int64_t> slot((size_t)m->num_field_nodes, -1), tptr(1, 0);
+    for (int64_t v = 0; v < m->num_field_nodes; ++v)
+        if (count[(size_t)v + 1]) {
+            slot[(size_t)v] = tptr.back();
+            tnode.push_back((int32_t)v);
+            tptr.push_back(tptr.back() + count[(size_t)v + 1]);
+        }
+    std::vector<uint32_t> tent((size_t)(n * nd));
+    for (int64_t e = 0; e < n; ++e)
+        for (int64_t a = 0; a < nd; ++a) tent[(size_t)slot[(size_t)dm[(size_t)(ents[2 * e] * nd + a)]]++] = (uint32_t)(e * nd + a);
+    set->n_touched = (int64_t)tnode.size();
+    const size_t G = (size_t)m->gdim;
+    DXO_HIP(ctx, hipMalloc((void**)&set->d_ents, (size_t)n * 2 * sizeof(int32_t)));
+    DXO_HIP(ctx, hipMalloc((void**)&set->d_fe, (size_t)(n * nd) * G * sizeof(double)));
+    DXO_HIP(ctx, hipMalloc((void**)&set->d_tnode, tnode.size() * sizeof(int32_t)));
+    DXO_HIP(ctx, hipMalloc((void**)&set->d_tptr, tptr.size() * sizeof(int64_t)));
+    DXO_HIP(ctx, hipMalloc((void**)&set->d_tent, tent.size() * sizeof(uint32_t)));
+    DXO_HIP(ctx, hipMemcpy(set->d_ents, ents, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
+    DXO_HIP(ctx, hipMemcpy(set->d_tnode, tnode.data(), tnode.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    DXO_HIP(ctx, hipMemcpy(set->d_tptr, tptr.data(), tptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    DXO_HIP(ctx, hipMemcpy(set->d_tent, tent.data(), tent.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return DXO_OK;
+}
+
+}  // namespace
+
+extern "C" int dxo_mesh_set_facet_geometry(dxo_ctx* ctx, dxo_mesh* m, int n_local_facets, int nq, const double* weights,
+                                           const double* ref_normals, const double* ref_jacobians) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!m || !weights || !ref_normals || !ref_jacobians) return dxo_fail(ctx, DXO_E_NULL, "dxo_mesh_set_facet_geometry: NULL argument");
+    if (!m->d_facet_tab) return dxo_fail(ctx, DXO_E_OPTION, "dxo_mesh_set_facet_geometry: call dxo_mesh_set_facet_tables first");
+    if (n_local_facets != m->n_local_facets || nq != m->nq_facet)
+        return dxo_fail(ctx, DXO_E_DIM, "dxo_mesh_set_facet_geometry: n_local_facets / nq differ from the facet tables'");
+    const size_t G = (size_t)m->gdim, nf = (size_t)n_local_facets, n_w = (size_t)nq, n_n = nf * G, n_j = nf * G * (G - 1);
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    DXO_HIP(ctx, hipDeviceSynchronize());
+    if (m->d_facet_geom) DXO_HIP(ctx, hipFree(m->d_facet_geom));
+    m->d_facet_geom = nullptr;
+    m->nf_geom = m->nq_geom = 0;
+    DXO_HIP(ctx, hipMalloc((void**)&m->d_facet_geom, (n_w + n_n + n_j) * sizeof(double)));
+    DXO_HIP(ctx, hipMemcpy(m->d_facet_geom, weights, n_w * sizeof(double), hipMemcpyHostToDevice));
+    DXO_HIP(ctx, hipMemcpy(m->d_facet_geom + n_w, ref_normals, n_n * sizeof(double), hipMemcpyHostToDevice));
+    DXO_HIP(ctx, hipMemcpy(m->d_facet_geom + n_w + n_n, ref_jacobians, n_j * sizeof(double), hipMemcpyHostToDevice));
+    m->nf_geom = n_local_facets;
+    m->nq_geom = nq;
+    return DXO_OK;
+}
+
+extern "C" int dxo_facet_set_create(dxo_ctx* ctx, dxo_mesh* m, const int32_t* entities, int64_t n, dxo_facet_set** out) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!m || !out || (n > 0 && !entities)) return dxo_fail(ctx, DXO_E_NULL, "dxo_facet_set_create: NULL argument");
+    *out = nullptr;
+    if (!m->d_facet_tab) return dxo_fail(ctx, DXO_E_OPTION, "dxo_facet_set_create: call dxo_mesh_set_facet_tables first");
+    if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_facet_set_create: n < 0");
+    if (n * m->dev.ndofs >= ((int64_t)1 << 32)) return dxo_fail(ctx, DXO_E_SIZE, "dxo_facet_set_create: 2^32 or more (entity, dof) entries");
+    for (int64_t i = 0; i < n; ++i)
+        if (entities[2 * i] < 0 || entities[2 * i] >= m->num_cells || entities[2 * i + 1] < 0 || entities[2 * i + 1] >= m->n_local_facets)
+            return dxo_fail(ctx, DXO_E_SIZE, "dxo_facet_set_create: entity outside [0, num_cells) x [0, n_local_facets)");
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    dxo_facet_set* set = new dxo_facet_set;
+    set->mesh = m;
+    set->n = n;
+    set->nd = m->dev.ndofs;
+    set->nf = m->n_local_facets;
+    if (n > 0) {
+        const int rc = set_build(ctx, set, m, entities);
+        if (rc != DXO_OK) {
+            set_free(set);
+            return rc;
+        }
+    }
+    *out = set;
+    return DXO_OK;
+}
+
+extern "C" int dxo_facet_set_destroy(dxo_ctx* ctx, dxo_facet_set* set) {
+    if (!set) return DXO_OK;
+    DXO_LOCK(ctx);
+    if (ctx) (void)hipSetDevice(ctx->device);
+    (void)hipDeviceSynchronize();       // the scratch may still be read by a queued launch
+    set_free(set);
+    return DXO_OK;
+}
+
+extern "C" int dxo_eval_facet_geometry(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set* set, double* normals, double* dS) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    int rc = facet_ready(ctx, m, set, "dxo_eval_facet_geometry");
+    if (rc != DXO_OK) return rc;
+    if (((uintptr_t)normals | (uintptr_t)dS) & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_eval_facet_geometry: arrays must be 8-byte aligned");
+    if (set->n == 0 || (!normals && !dS)) return DXO_OK;
+    hipStream_t s = dxo_launch_stream(ctx);
+    rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    const int blocks = grid(ctx, set->n * m->nq_facet);
+    if (m->gdim == 2) hipLaunchKernelGGL(facet_geometry<2>, dim3(blocks), dim3(DXO_BLOCK), 0, s, m->dev, facet_tabs<2>(m), set->d_ents, set->n, normals, dS);
+    else              hipLaunchKernelGGL(facet_geometry<3>, dim3(blocks), dim3(DXO_BLOCK), 0, s, m->dev, facet_tabs<3>(m), set->d_ents, set->n, normals, dS);
+    return dxo_device_end(ctx, s);
+}
+
+extern "C" int dxo_facet_adjoint(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set* set, int kind, int bs, const double* S, double* out) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    int rc = facet_ready(ctx, m, set, "dxo_facet_adjoint");
+    if (rc != DXO_OK) return rc;
+    if (kind == DXO_OPERAND_CAUCHY_GREEN || kind == DXO_OPERAND_I1 || kind == DXO_OPERAND_DETF)
+        return dxo_fail(ctx, DXO_E_OPTION, "dxo_facet_adjoint: a nonlinear operand (C, I1, det F) has no adjoint");
+    const int D = dxo_operand_value_size(m->gdim, bs, kind);
+    if (D == DXO_E_OPTION) return dxo_fail(ctx, DXO_E_OPTION, "dxo_facet_adjoint: unknown operand kind");
+    if (D < 0 || (bs != 1 && bs != m->gdim)) return dxo_fail(ctx, DXO_E_DIM, "dxo_facet_adjoint: block size does not fit the operand kind / gdim (bs = 1 or gdim)");
+    if (set->n == 0) return DXO_OK;
+    if (!S || !out) return dxo_fail(ctx, DXO_E_NULL, "dxo_facet_adjoint: NULL array");
+    if (((uintptr_t)S | (uintptr_t)out) & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_facet_adjoint: arrays must be 8-byte aligned");
+    hipStream_t s = dxo_launch_stream(ctx);
+    rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    if (m->gdim == 2) rc = bs == 1 ? dispatch_adjoint<2, 1>(ctx, m, set, kind, S, s) : dispatch_adjoint<2, 2>(ctx, m, set, kind, S, s);
+    else              rc = bs == 1 ? dispatch_adjoint<3, 1>(ctx, m, set, kind, S, s) : dispatch_adjoint<3, 3>(ctx, m, set, kind, S, s);
+    if (rc != DXO_OK) return dxo_fail(ctx, rc, "dxo_facet_adjoint: unsupported (gdim, bs, kind)");
+    launch_node_sum(ctx, set, bs, out, s);
+    return dxo_device_end(ctx, s);
+}
+
+extern "C" int dxo_facet_pressure(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set* set, const double* p, double scale, double* out) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    int rc = facet_ready(ctx, m, set, "dxo_facet_pressure");
+    if (rc != DXO_OK) return rc;
+    if (set->n == 0) return DXO_OK;
+    if (!out) return dxo_fail(ctx, DXO_E_NULL, "dxo_facet_pressure: out is NULL");
+    if (((uintptr_t)p | (uintptr_t)out) & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_facet_pressure: arrays must be 8-byte aligned");
+    hipStream_t s = dxo_launch_stream(ctx);
+    rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    if (m->gdim == 2) launch_element<2, 2, FACET_PRESSURE>(ctx, m, set, p, scale, s);
+    else              launch_element<3, 3, FACET_PRESSURE>(ctx, m, set, p, scale, s);
+    launch_node_sum(ctx, set, m->gdim, out, s);
+    return dxo_device_end(ctx, s);
+}

@@ -303,6 +303,7 @@ extern "C" int dxo_mesh_destroy(dxo_ctx* ctx, dxo_mesh* m) {
     if (m->d_cells) (void)hipFree(m->d_cells);
     if (m->d_out) (void)hipFree(m->d_out);
     if (m->d_facet_tab) (void)hipFree(m->d_facet_tab);
+    if (m->d_facet_geom) (void)hipFree(m->d_facet_geom);
     if (m->d_ents) (void)hipFree(m->d_ents);
     if (m->d_wq) (void)hipFree(m->d_wq);
     if (m->d_psi) (void)hipFree(m->d_psi);

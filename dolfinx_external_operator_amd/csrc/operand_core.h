@@ -139,6 +139,45 @@ __device__ __forceinline__ void shape_operand(const double (&val)[BS], const dou
     }
 }
 
+// (adjoint.hip, facet_form.hip) Mandel / row-major operand value -> dual tensor Ghat[i][j] = d(pairing)/d(grad u)_ij, and the value part
+template <int G, int BS, int KIND>
+__device__ __forceinline__ void dual_tensor(const double (&s)[OperandShape<G, BS, KIND>::D], double (&vh)[BS],
+                                            double (&gh)[BS][G]) {
+    constexpr double r2 = 0.70710678118654752440;
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+        vh[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < G; ++j) gh[i][j] = 0.0;
+    }
+    if constexpr (KIND == DXO_OPERAND_VALUE) {
+#pragma unroll
+        for (int i = 0; i < BS; ++i) vh[i] = s[i];
+    } else if constexpr (KIND == DXO_OPERAND_GRAD || KIND == DXO_OPERAND_DEFGRAD) {
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < G; ++j) gh[i][j] = s[i * G + j];
+    } else if constexpr (KIND == DXO_OPERAND_VALUE_GRAD) {
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            vh[i] = s[i];
+#pragma unroll
+            for (int j = 0; j < G; ++j) gh[i][j] = s[BS + i * G + j];
+        }
+    } else if constexpr (KIND == DXO_OPERAND_DIV) {      // pairing s div v: Ghat = s I
+#pragma unroll
+        for (int i = 0; i < G; ++i) gh[i % BS][i] = s[0];
+    } else {   // EPS_MANDEL: e = [g00, g11, (g22 | 0), r(g01+g10), r(g02+g20), r(g12+g21)]
+        if constexpr (G == 2) {
+            gh[0][0] = s[0]; gh[1][1] = s[1]; gh[0][1] = gh[1][0] = r2 * s[3];
+        } else {
+            gh[0][0] = s[0]; gh[1][1] = s[1]; gh[2][2] = s[2];
+            gh[0][1] = gh[1][0] = r2 * s[3]; gh[0][2] = gh[2][0] = r2 * s[4]; gh[1][2] = gh[2][1] = r2 * s[5];
+        }
+    }
+}
+
 // ---- LDS layout. Lanes of one wave read, in the same instruction, the SAME slot of up to 64/nq different cells
 // (U, X) or of nq different points (tables): a per-cell / per-point stride that is an ODD number of doubles sends
 // those addresses to different banks (an even stride such as 24 doubles = 48 dwords collides 4-way on 32 banks).
@@ -443,6 +482,9 @@ struct dxo_mesh {
     double* d_facet_tab = nullptr;      // phi_f [nf][nqf][ndofs] | dphi_f [nf][nqf][ndofs][G] | dpsi_f [nf][nqf][ngeom][G]
     int32_t* d_ents = nullptr;          // staging for host-resident (cell, local facet) lists
     size_t ents_cap = 0;
+    // boundary-facet integrals (facet_form.hip, dxo_mesh_set_facet_geometry): per LOCAL facet, matching the facet tables
+    int nf_geom = 0, nq_geom = 0;
+    double* d_facet_geom = nullptr;     // w_f [nqf] | n_ref [nf][G] | J_ref [nf][G][G-1]
     // adjoint kernels, two-pass form: element vectors + the transposed dofmap (node -> its (cell, local node) entries)
     std::vector<int32_t> h_dofmap;     // host copy kept for building the transpose on first use
     int64_t* d_node_ptr = nullptr;     // [num_field_nodes + 1]

@@ -324,6 +324,58 @@ class DeviceMesh:
             self.ctx.check(rc, "dxo_csr_dirichlet")
         return DeviceCSR(pattern, values)
 
+    def set_facet_geometry(self, weights, ref_normals, ref_jacobians) -> None:
+        """Reference facet data for the boundary integrals (dxo_mesh_set_facet_geometry), one entry per LOCAL facet, matching
+        set_facet_tables (call it first): weights (nq,) = basix.make_quadrature(facet_cell, deg)[1], ref_normals (nf, gdim) =
+        basix.cell.facet_outward_normals(cell), ref_jacobians (nf, gdim, gdim - 1) = basix.cell.facet_jacobians(cell)."""
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        nrm = np.ascontiguousarray(ref_normals, dtype=np.float64)
+        jac = np.ascontiguousarray(ref_jacobians, dtype=np.float64)
+        G = self.gdim
+        if nrm.ndim != 2 or nrm.shape[1] != G or jac.shape != (nrm.shape[0], G, G - 1):
+            raise ValueError("facet geometry: weights (nq,), ref_normals (nf, gdim), ref_jacobians (nf, gdim, gdim - 1)")
+        rc = self.ctx.lib.dxo_mesh_set_facet_geometry(self.ctx._h, self._h, nrm.shape[0], w.size, w.ctypes.data, nrm.ctypes.data,
+                                                      jac.ctypes.data)
+        self.ctx.check(rc, "dxo_mesh_set_facet_geometry")
+
+    def facet_set(self, entities) -> "FacetSet":
+        """The device facet set of the (cell, local facet) pairs `entities` (n, 2) (dxo_facet_set_create), e.g. the facets of one tag:
+        built once and kept by the mesh, keyed by the entity array's bytes."""
+        ents = np.ascontiguousarray(entities, dtype=np.int32)
+        if ents.ndim != 2 or ents.shape[1] != 2:
+            raise ValueError("facet entities must have shape (n, 2): (cell, local facet)")
+        sets = self.__dict__.setdefault("_facet_sets", {})
+        key = ents.tobytes()
+        if key not in sets:
+            sets[key] = FacetSet(self, ents)
+        return sets[key]
+
+    def facet_geometry(self, facet_set: "FacetSet", normals_ptr: int | None = None, dS_ptr: int | None = None) -> None:
+        """FacetNormal (n, nq, gdim) and the point measure dS = w |det J_f| (n, nq) at the set's facet points (dxo_eval_facet_geometry;
+        DEVICE pointers, either may be None), asynchronous on the context's stream."""
+        rc = self.ctx.lib.dxo_eval_facet_geometry(self.ctx._h, self._h, facet_set._h, None if normals_ptr is None else C.c_void_p(normals_ptr),
+                                                  None if dS_ptr is None else C.c_void_p(dS_ptr))
+        self.ctx.check(rc, "dxo_eval_facet_geometry")
+
+    FACET_ADJOINT_KINDS = ("value", "grad", "value_grad", "eps", "div", "F")
+
+    def facet_adjoint(self, kind: str, bs: int, S_ptr: int, facet_set: "FacetSet", out_ptr: int) -> None:
+        """out += sum_e sum_q dS B^T S over the set's facets (dxo_facet_adjoint; DEVICE pointers, S (n, nq, value_size)): the assembled
+        vector of inner(S, operand(v)) ds. ("value", gdim) with S = t is a traction load. Always accumulates."""
+        if kind not in self.FACET_ADJOINT_KINDS:
+            raise ValueError(f"facet_adjoint: kind {kind!r} has no adjoint; linear kinds: {self.FACET_ADJOINT_KINDS}")
+        if int(bs) not in (1, self.gdim) or (kind in ("eps", "div", "F") and int(bs) != self.gdim):
+            raise ValueError(f"facet_adjoint: bs = {bs} does not fit kind {kind!r} on gdim {self.gdim} (bs = 1 or gdim; eps / div / F: gdim)")
+        rc = self.ctx.lib.dxo_facet_adjoint(self.ctx._h, self._h, facet_set._h, KINDS[kind], int(bs), C.c_void_p(S_ptr), C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_facet_adjoint")
+
+    def facet_pressure(self, facet_set: "FacetSet", out_ptr: int, p_ptr: int | None = None, scale: float = 1.0) -> None:
+        """out[node*gdim + i] += scale * sum_e sum_q dS p phi_a n_i (dxo_facet_pressure; DEVICE pointers, p (n, nq) or None for p = 1):
+        the demo's boundary term -inner(loading * -n, v) ds is facet_pressure(scale=loading). Always accumulates."""
+        rc = self.ctx.lib.dxo_facet_pressure(self.ctx._h, self._h, facet_set._h, None if p_ptr is None else C.c_void_p(p_ptr), float(scale),
+                                             C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_facet_pressure")
+
     def tangent_apply_vm(self, prm, sigma_ptr: int, dp_ptr: int, v_ptr: int, out_ptr: int) -> None:
         """out += K v with the von Mises consistent tangent formed per point from the operator's returned (sigma, dp) — no C_tang
         array (dxo_tangent_apply_vm; DEVICE pointers, e.g. VmState.pointers()): 56 instead of 288 bytes per point."""
@@ -355,6 +407,8 @@ class DeviceMesh:
     def close(self) -> None:
         for pat in self.__dict__.pop("_csr", {}).values():
             pat.close()
+        for fs in self.__dict__.pop("_facet_sets", {}).values():
+            fs.close()
         if getattr(self, "_h", None) and self.ctx._h:
             self.ctx.lib.dxo_mesh_destroy(self.ctx._h, self._h)
         self._h = None
@@ -410,6 +464,34 @@ class CsrPattern:
 
     def close(self) -> None:
         self._fin()
+
+
+class FacetSet:
+    """dxo_facet_set: a fixed list of (cell, local facet) entities of a DeviceMesh on the device, with its element-vector scratch and
+    transposed incidence (built once). `n` entities; `entities` keeps the host array."""
+
+    def __init__(self, mesh: DeviceMesh, entities: np.ndarray):
+        self.ctx, self.mesh_handle = mesh.ctx, mesh._h
+        self.entities = np.ascontiguousarray(entities, dtype=np.int32)
+        self.n = self.entities.shape[0]
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.dxo_facet_set_create(self.ctx._h, mesh._h, self.entities.ctypes.data, self.n, C.byref(h)),
+                       "dxo_facet_set_create")
+        self._h = h
+        self._fin = weakref.finalize(self, FacetSet._destroy, self.ctx, h)
+
+    @staticmethod
+    def _destroy(ctx, h):
+        ctx.lib.dxo_facet_set_destroy(ctx._h, h)
+
+    def close(self) -> None:
+        self._fin()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceCSR:

@@ -570,6 +570,41 @@ int dxo_bilinear_assemble(dxo_ctx* ctx, dxo_mesh* mesh, dxo_csr* csr, int test_k
                           double* values);
 int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n_dofs, double diagonal, double* values);
 
+/* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
+ * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is
+ * dxo_operand_adjoint(EPS_MANDEL) followed by dxo_facet_pressure(scale = loading) on the facets of the tag.
+ * dxo_mesh_set_facet_geometry : reference facet data, one entry per LOCAL facet, matching the facet tables (dxo_mesh_set_facet_tables
+ *     first: DXO_E_OPTION otherwise; n_local_facets and nq must equal the tables': DXO_E_DIM otherwise). Host pointers, copied:
+ *       weights       [nq]                reference facet quadrature weights (basix.make_quadrature(facet_cell, deg)[1])
+ *       ref_normals   [nf][gdim]          outward unit normals of the reference cell (basix.cell.facet_outward_normals)
+ *       ref_jacobians [nf][gdim][gdim-1]  reference facet -> reference cell Jacobians (basix.cell.facet_jacobians)
+ * dxo_facet_set_create : a fixed list of (cell, local facet) entities (host int32 [n][2], e.g. the facets of one tag), built ONCE:
+ *     validated (outside [0, num_cells) x [0, n_local_facets): DXO_E_SIZE; facet tables not set: DXO_E_OPTION), copied to the device,
+ *     with the element-vector scratch and the transposed incidence node -> (entity, local dof) in ascending entity order. The
+ *     calls below allocate nothing and synchronise nothing: they are capture-safe once the set exists.
+ * Geometry at a facet point: J is rebuilt from the facet dpsi table exactly as dxo_eval_operand_facets does; J_f = J J_ref_f,
+ *     dS = w_q sqrt(det(J_f^T J_f)) (the point measure of ds), n = J^-T n_ref / |J^-T n_ref| — outward whatever the sign of det J.
+ * dxo_eval_facet_geometry : UFL's FacetNormal and dS at the facet points, DEVICE pointers; either may be NULL.
+ *     normals [n][nq][gdim], dS [n][nq].
+ * dxo_facet_adjoint : out[dof] += sum_e sum_q dS_eq B_eq^T S_eq, the facet adjoint of dxo_eval_operand_facets for the linear kinds and
+ *     block sizes dxo_operand_adjoint takes (VALUE, GRAD, VALUE_GRAD with bs = 1 or gdim; EPS_MANDEL, DIV, DEFGRAD (as its
+ *     linearisation, grad) with bs = gdim); S [n][nq][value_size]. Nonlinear kinds (C, I1, det F): DXO_E_OPTION. VALUE with bs = gdim
+ *     and S = t is the load vector of a traction t.
+ * dxo_facet_pressure : out[node*gdim + i] += scale * sum_e sum_q dS_eq p_eq phi_a(x_eq) n_i(x_eq), p [n][nq] or NULL for p = 1, n the
+ *     outward unit normal formed in the kernel.
+ * The facet calls always ACCUMULATE into out: options "consumer_overwrite" and "adjoint_atomics" do not apply to them. Element vectors
+ * go to the set's scratch, then one lane per touched node adds that node's entries in ascending entity order: no atomics,
+ * bit-reproducible. Facet geometry not set: DXO_E_OPTION; a set created on another mesh, or tables / geometry changed to another
+ * (nf, nq) since: DXO_E_DIM; NULL arrays DXO_E_NULL, arrays not 8-byte aligned DXO_E_ALIGN. */
+int dxo_mesh_set_facet_geometry(dxo_ctx* ctx, dxo_mesh* mesh, int n_local_facets, int nq, const double* weights,
+                                const double* ref_normals, const double* ref_jacobians);
+typedef struct dxo_facet_set dxo_facet_set;
+int dxo_facet_set_create(dxo_ctx* ctx, dxo_mesh* mesh, const int32_t* entities, int64_t n, dxo_facet_set** out);
+int dxo_facet_set_destroy(dxo_ctx* ctx, dxo_facet_set* set);
+int dxo_eval_facet_geometry(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_set* set, double* normals, double* dS);
+int dxo_facet_adjoint(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_set* set, int kind, int bs, const double* S, double* out);
+int dxo_facet_pressure(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_set* set, const double* p, double scale, double* out);
+
 /* ---- coefficient assigners on the device, DEVICE memory only --------------------------
  * One scatter for the reference's three dofmap assigners (src/dolfinx_external_operator/external_operator.py):
  * _assign_non_mixed :286-287, _assign_mixed_2d :292-311, _assign_mixed_3d :313-335. For cell c, point p < n_pts,

@@ -277,3 +277,75 @@ def facet_physical_points(mesh: "SyntheticMesh", entities: np.ndarray, ref_point
         psi, _ = geo.tabulate(ref_points[f])
         out[i] = psi @ mesh.x[mesh.geom_dofmap[c]]
     return out
+
+
+# ---------------------------------------------------------------------------------------------- boundary facets (ds)
+def facet_geometry(cell: str):
+    """Reference data of the boundary integrals, one entry per local facet of FACETS (what DeviceMesh.set_facet_geometry takes):
+    weights (nq,) of facet_quadrature_degree2, outward unit normals (nf, tdim) of the reference cell, and the Jacobians (nf, tdim,
+    tdim - 1) of the maps reference facet -> reference cell that facet_points_in_cell applies (its bilinear quadrilateral map is affine
+    on the reference hexahedron's faces). On DOLFINx: basix.make_quadrature, basix.cell.facet_outward_normals, facet_jacobians."""
+    _, weights = facet_quadrature_degree2(cell)
+    verts = LagrangeElement(cell, 1).nodes
+    centre = verts.mean(axis=0)
+    normals, jacobians = [], []
+    for f in FACETS[cell]:
+        v = verts[list(f)]
+        J = np.stack([v[1] - v[0]] + ([v[2] - v[0]] if len(f) > 2 else []), axis=1)        # (tdim, tdim - 1)
+        if J.shape[0] == 2:
+            n = np.array([J[1, 0], -J[0, 0]])
+        else:
+            n = np.cross(J[:, 0], J[:, 1])
+        n = n / np.linalg.norm(n)
+        if np.dot(n, v.mean(axis=0) - centre) < 0:
+            n = -n
+        normals.append(n)
+        jacobians.append(J)
+    return np.ascontiguousarray(weights), np.array(normals), np.array(jacobians)
+
+
+def exterior_facets(mesh: "SyntheticMesh", where=None) -> np.ndarray:
+    """(n, 2) int32 (cell, local facet) pairs of the facets that belong to exactly one cell, in ascending (cell, facet) order.
+    `where`: optional predicate on the facets' vertex coordinates, called once with an array (n, vertices per facet, gdim) and
+    returning a boolean mask (n,), e.g. `lambda X: np.all(np.abs(X[..., 1]) < 1e-12, axis=1)` for the facets on y = 0."""
+    fl = np.array(FACETS[mesh.cell])                                      # (nf, nvf)
+    nc, nf = mesh.num_cells, fl.shape[0]
+    verts = mesh.geom_dofmap[:, fl]                                       # (nc, nf, nvf) global vertex ids
+    keys = np.sort(verts.reshape(nc * nf, -1), axis=1)
+    order = np.lexsort(keys.T[::-1])
+    sk = keys[order]
+    same = np.all(sk[1:] == sk[:-1], axis=1)
+    shared = np.zeros(len(sk), dtype=bool)
+    shared[1:] |= same
+    shared[:-1] |= same
+    ext = np.sort(order[~shared])                                         # flat index cell * nf + facet, ascending
+    ents = np.stack([ext // nf, ext % nf], axis=1).astype(np.int32)
+    if where is not None and len(ents):
+        X = mesh.x[mesh.geom_dofmap[ents[:, 0][:, None], fl[ents[:, 1]]]]   # (n, nvf, gdim)
+        ents = ents[np.asarray(where(X), dtype=bool)]
+    return np.ascontiguousarray(ents)
+
+
+def quarter_annulus(n_r: int, n_theta: int, R_i: float = 1.0, R_e: float = 1.3, degree: int = 2):
+    """The von Mises demo's domain, a quarter of the thick-walled cylinder (doc/demo/utilities.py build_cylinder_quarter), as
+    P`degree` triangles: a structured triangle mesh of the unit square whose VERTICES are mapped s -> r = R_i + s (R_e - R_i),
+    t -> theta = t pi / 2; the field nodes are then placed by the affine cells (node_x from the degree-1 geometry), so the boundary arcs
+    are polygons. Returns (mesh, tags) with tags "Lx" (y = 0), "Ly" (x = 0), "inner" (r = R_i), "outer" (r = R_e) as (n, 2) int32
+    (cell, local facet) arrays."""
+    import dataclasses
+
+    base = structured_mesh("triangle", (n_r, n_theta), degree=degree)
+    s, t = base.x[:, 0], base.x[:, 1]
+    on = lambda sel: (lambda X: np.all(sel(X), axis=1))                   # noqa: E731
+    tags = {"Lx": exterior_facets(base, on(lambda X: X[..., 1] == 0.0)),
+            "Ly": exterior_facets(base, on(lambda X: X[..., 1] == 1.0)),
+            "inner": exterior_facets(base, on(lambda X: X[..., 0] == 0.0)),
+            "outer": exterior_facets(base, on(lambda X: X[..., 0] == 1.0))}
+    r, theta = R_i + s * (R_e - R_i), t * (np.pi / 2)
+    x = np.stack([r * np.cos(theta), r * np.sin(theta)], axis=1)
+    x[t == 1.0, 0] = 0.0                                                  # x = 0 exactly on the symmetry edge Ly
+    fe, geo = LagrangeElement("triangle", degree), LagrangeElement("triangle", 1)
+    psi_nodes, _ = geo.tabulate(fe.nodes)
+    node_x = np.zeros_like(base.node_x)
+    node_x[base.dofmap.reshape(-1)] = np.einsum("av,cvj->caj", psi_nodes, x[base.geom_dofmap]).reshape(-1, 2)
+    return dataclasses.replace(base, x=np.ascontiguousarray(x), node_x=node_x), tags
