@@ -21,7 +21,7 @@ MEM_DEVICE = 1
 
 ERRORS = {
     -1: "DXO_E_NULL", -2: "DXO_E_DIM", -3: "DXO_E_SIZE", -4: "DXO_E_MEM",
-    -5: "DXO_E_ALIGN", -6: "DXO_E_OPTION", -7: "DXO_E_NODEVICE",
+    -5: "DXO_E_ALIGN", -6: "DXO_E_OPTION", -7: "DXO_E_NODEVICE", -8: "DXO_E_SINGULAR",
 }
 
 
@@ -79,6 +79,27 @@ class DeviceInfo(C.Structure):
 
 
 _P = C.c_void_p
+
+# dxo_krylov_apply_fn: sets out = A v on the context's stream; 0 on success
+KRYLOV_APPLY_FN = C.CFUNCTYPE(C.c_int, _P, _P, _P)
+
+
+class KrylovOp(C.Structure):
+    """dxo_krylov_op: a CSR matrix (csr + values) or a callback."""
+    _fields_ = [("n", C.c_int64), ("csr", _P), ("values", _P), ("apply", KRYLOV_APPLY_FN), ("user", _P)]
+
+
+class KrylovPc(C.Structure):
+    """dxo_krylov_pc: DXO_PC_NONE (0), DXO_PC_JACOBI (1, inv [n]) or DXO_PC_BLOCK_JACOBI (2, inv [n/bs][bs][bs])."""
+    _fields_ = [("kind", C.c_int), ("bs", C.c_int), ("n", C.c_int64), ("inv", _P)]
+
+
+class KrylovInfo(C.Structure):
+    """dxo_krylov_info."""
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("breakdown", C.c_int32), ("restarts", C.c_int32),
+                ("residual", C.c_double), ("ms", C.c_double)]
+
+
 _SIGNATURES = {
     "dxo_abi_version": (C.c_int, []),
     "dxo_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -158,6 +179,15 @@ _SIGNATURES = {
     "dxo_csr_info": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_double)]),
     "dxo_bilinear_assemble": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dxo_csr_dirichlet": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, _P]),
+    "dxo_csr_spmv": (C.c_int, [_P, _P, _P, C.c_double, _P, C.c_double, _P]),
+    "dxo_csr_block_jacobi": (C.c_int, [_P, _P, _P, _P]),
+    "dxo_block_jacobi_apply": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P]),
+    "dxo_krylov_create": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(_P)]),
+    "dxo_krylov_destroy": (C.c_int, [_P, _P]),
+    "dxo_krylov_gmres": (C.c_int, [_P, _P, C.POINTER(KrylovOp), C.POINTER(KrylovPc), _P, _P, C.c_double, C.c_double, C.c_int, C.c_int,
+                                   C.POINTER(KrylovInfo)]),
+    "dxo_krylov_cg": (C.c_int, [_P, _P, C.POINTER(KrylovOp), C.POINTER(KrylovPc), _P, _P, C.c_double, C.c_double, C.c_int, C.c_int,
+                                C.POINTER(KrylovInfo)]),
     "dxo_mesh_set_facet_geometry": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "dxo_facet_set_create": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "dxo_facet_set_destroy": (C.c_int, [_P, _P]),
@@ -372,6 +402,7 @@ class Context:
         self._pinned: list[tuple[int, np.ndarray]] = []
         self._pool = _PinnedPool(self.lib)
         self._lock = threading.RLock()   # dxo_ctx itself also serialises its entry points (include/dxo.h)
+        self._krylov_ws: dict = {}       # krylov.py: Krylov workspaces by (n, restart), freed by close()
 
     @classmethod
     def borrow(cls, handle: int, device: int = 0) -> "Context":
@@ -384,6 +415,7 @@ class Context:
         self._pinned = []
         self._pool = _PinnedPool(self.lib)
         self._lock = threading.RLock()
+        self._krylov_ws = {}
         self._borrowed = True
         return self
 
@@ -399,6 +431,9 @@ class Context:
 
     def close(self) -> None:
         if getattr(self, "_h", None):
+            for ws in self.__dict__.get("_krylov_ws", {}).values():   # before the context goes
+                ws.close()
+            self.__dict__.get("_krylov_ws", {}).clear()
             for addr, _ in self._pinned:
                 self.lib.dxo_host_free(self._h, _P(addr))
             self._pinned.clear()

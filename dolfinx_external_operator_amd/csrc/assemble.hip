@@ -21,6 +21,7 @@
 //     "assemble_chunk_cells"): chunk k + 1 continues the chains chunk k left in `values`.
 // Option "adjoint_atomics" = 1: pass 1 adds its blocks straight into `values` with fp64 atomics (one launch, no scratch,
 // reproducible to rounding only). Option "consumer_overwrite" = 1 clears `values` first (SET instead of accumulate).
+#include "csr.h"
 #include "dxo_common.h"
 #include "operand_core.h"
 #include "operand_coef.h"
@@ -30,21 +31,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
-
-struct dxo_csr {
-    const dxo_mesh* mesh = nullptr;
-    int bs = 0, nd = 0;
-    int64_t n_nodes = 0, n_cells = 0, n_rows = 0, nnz = 0;
-    int64_t* d_row_ptr = nullptr;      // [n_rows + 1]
-    int32_t* d_col = nullptr;          // [nnz]
-    int64_t* d_inc_ptr = nullptr;      // [n_nodes + 1] incidences of a node
-    uint32_t* d_inc = nullptr;         // cell * nd + a, ascending cell per node
-    uint16_t* d_pos = nullptr;         // [n_cells][nd][nd] column block of b's node in the rows of a's node
-    uint8_t* d_mask = nullptr;         // [n_rows] constrained dofs of the last dxo_csr_dirichlet
-    double* d_ae = nullptr;            // element-matrix scratch of one chunk
-    size_t ae_cap = 0;
-    double build_ms = 0.0;
-};
 
 #ifndef DXO_AS_BLOCKS_PER_CU
 #define DXO_AS_BLOCKS_PER_CU 8

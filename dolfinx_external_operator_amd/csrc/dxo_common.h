@@ -92,6 +92,8 @@ struct dxo_ctx {
     int64_t adjoint_mfma = 1;           // Q2 / Q1 hexahedra, 2x2x2 rule: the consumer-side scatter B^T t as f64 MFMAs (c8m_contract in adjoint.hip); 0 = DPP reduce-scatter (cell8_dpp.h)
     int64_t adjoint_atomics = 0;        // adjoint kernels and dxo_bilinear_assemble: 1 = fp64 atomics into the dof vector, 0 = element vectors + node sums
     int64_t assemble_chunk_cells = 0;   // dxo_bilinear_assemble: cells per chunk of the element-matrix scratch (0: as many as fit 1 GiB)
+    int64_t krylov_reorth = 1;          // dxo_krylov_gmres: 1 = classical Gram-Schmidt with one reorthogonalisation pass, 0 = one pass
+    int64_t spmv_lanes = 0;             // dxo_csr_spmv and the Krylov solves: lanes per node (8, 16, 32, 64; 0 = from the mean neighbour count)
     int64_t mc_part_points = (int64_t)1 << 30;   // Mohr-Coulomb: points per classify/Newton pass (int32 list entries)
     int64_t mc_waves_per_simd = 1;      // kept for option compatibility: mc_newton keeps its lane state in LDS (mc_core.h LaneLds) and
                                         // fits two waves per SIMD (240 VGPRs, no scratch) whatever this says

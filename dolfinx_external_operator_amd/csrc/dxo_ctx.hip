@@ -175,6 +175,8 @@ static int64_t* option_slot(dxo_ctx* c, const char* key) {
     if (!std::strcmp(key, "icnn_variant")) return &c->icnn_variant;
     if (!std::strcmp(key, "adjoint_atomics")) return &c->adjoint_atomics;
     if (!std::strcmp(key, "assemble_chunk_cells")) return &c->assemble_chunk_cells;
+    if (!std::strcmp(key, "krylov_reorth")) return &c->krylov_reorth;
+    if (!std::strcmp(key, "spmv_lanes")) return &c->spmv_lanes;
     if (!std::strcmp(key, "adjoint_patch")) return &c->adjoint_patch;
     if (!std::strcmp(key, "adjoint_mfma")) return &c->adjoint_mfma;
     if (!std::strcmp(key, "mgpu_chunks")) return &c->mgpu_chunks;
@@ -220,6 +222,9 @@ int dxo_ctx_set_option(dxo_ctx* c, const char* key, int64_t value) {
         return dxo_fail(c, DXO_E_OPTION, "adjoint_patch: the patch form exists only in a -DDXO_EXPERIMENTS build (scripts/exp/adjoint_patch.h)");
     if (slot == &c->assign_plan_form && value > 2) return dxo_fail(c, DXO_E_OPTION, "assign_plan_form: 0 (both, the first apply chooses), 1 (dof order), 2 (source order)");
     if (slot == &c->assign_owner_bits && value != 0 && value != 64) return dxo_fail(c, DXO_E_OPTION, "assign_owner_bits: 0 (32-bit while the entry count fits) or 64");
+    if (slot == &c->krylov_reorth && value > 1) return dxo_fail(c, DXO_E_OPTION, "krylov_reorth: 0 (one Gram-Schmidt pass) or 1 (two)");
+    if (slot == &c->spmv_lanes && value != 0 && value != 8 && value != 16 && value != 32 && value != 64)
+        return dxo_fail(c, DXO_E_OPTION, "spmv_lanes: 0 (automatic), 8, 16, 32 or 64");
     if (slot == &c->mc_blocks_per_cu && value < 1) return dxo_fail(c, DXO_E_OPTION, "mc_blocks_per_cu < 1");
     if (slot == &c->vm_rebuild_chunk_points && value < DXO_WAVE) return dxo_fail(c, DXO_E_OPTION, "vm_rebuild_chunk_points < 64");
     if (slot == &c->host_chunk_points && value < DXO_WAVE) return dxo_fail(c, DXO_E_OPTION, "host_chunk_points < 64");

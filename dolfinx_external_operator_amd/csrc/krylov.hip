@@ -1,0 +1,814 @@
+// krylov.hip — linear solves on the device for the matrices of dxo_bilinear_assemble and for matrix-free operators
+// (dxo_csr_spmv / dxo_csr_block_jacobi / dxo_block_jacobi_apply / dxo_krylov_*).
+//
+// SpMV on a dxo_csr pattern, y = alpha A x + beta y. The rows node*bs + i, i < bs, of one node share their columns, and the columns
+// come in runs m*bs + j. A group of LW lanes (LW from the mean neighbour count of the pattern, option "spmv_lanes") owns one node:
+// lane l takes the neighbour blocks k = l, l + LW, ... in ascending order, reads ONE column index per block (col[r0 + k*bs]), the bs
+// entries of x at it and the bs contiguous values of each of the node's bs rows, and keeps bs sums. A fixed xor-butterfly over the
+// LW lanes then adds them. Index traffic is 4 B per bs^2 nonzeros; no atomics: the result is bit-reproducible.
+//
+// Block Jacobi: one thread per node finds the diagonal block (binary search for the node's own column run), inverts it in closed
+// form (bs <= 3) and writes inv[node][bs][bs]. A block whose |det| is at most 1e-14 of the product of its row norms (Hadamard's bound)
+// is singular: its inverse is written as zero, a flag is raised and the call returns DXO_E_SINGULAR after its one synchronisation.
+//
+// Restarted GMRES(m), right preconditioning, classical Gram-Schmidt with one reorthogonalisation pass (option "krylov_reorth",
+// default 1). One Arnoldi step is a fixed sequence of launches on the context's stream: z = M v_j, v_{j+1} = A z, h = V^T v_{j+1}
+// (multi-dot: every workgroup reads its rows of w once for all j + 1 products and writes per-block partials, a one-workgroup-per-
+// product pass adds them in a fixed order), v_{j+1} -= V h (also the partials of |w|^2), the same again for the second pass, the
+// norm, the scaling and a one-wave kernel that applies the previous Givens rotations to the new column, forms the next one, updates
+// g and records the first step whose estimate |g_{j+1}| fell below the tolerance. The host reads that record every check_every
+// steps only; the solution update uses the recorded step, so steps run past it change nothing. Every reduction has a fixed shape
+// (fixed grid for a workspace, fixed butterflies, fixed order across waves): a solve is bit-reproducible.
+// CG runs on the same kernels; once its residual test passes on the device, alpha is 0 for the steps that follow.
+#include "csr.h"
+#include "dxo_common.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+
+#ifndef DXO_KR_BLOCK
+#define DXO_KR_BLOCK 256
+#endif
+
+struct dxo_krylov {
+    int64_t n = 0, ld = 0;     // vector length and its padded stride (a multiple of 32 doubles)
+    int m = 0;                 // restart length
+    int nb = 0;                // workgroups of the row kernels = partials per product (fixed for the workspace)
+    double* vec = nullptr;     // [m + 1 + 4][ld]: the basis V, then Z, R, T, Q
+    double* part = nullptr;    // [m + 2][nb] per-block partials (the last row: |w|^2)
+    double* sc = nullptr;      // small state (offsets below)
+    int* st = nullptr;         // status words
+    double* V() const { return vec; }
+    double* Z() const { return vec + (int64_t)(m + 1) * ld; }
+    double* R() const { return vec + (int64_t)(m + 2) * ld; }
+    double* T() const { return vec + (int64_t)(m + 3) * ld; }
+    double* Q() const { return vec + (int64_t)(m + 4) * ld; }
+    // state layout: H [m][m + 1] (column j at j*(m+1)), g [m + 1], cs [m], sn [m], y [m], c [m + 1], scalars [16]
+    int64_t o_g() const { return (int64_t)m * (m + 1); }
+    int64_t o_cs() const { return o_g() + m + 1; }
+    int64_t o_sn() const { return o_cs() + m; }
+    int64_t o_y() const { return o_sn() + m; }
+    int64_t o_c() const { return o_y() + m; }
+    int64_t o_s() const { return o_c() + m + 1; }
+    int64_t sc_doubles() const { return o_s() + 16; }
+};
+
+namespace {
+
+constexpr int KR_MAX_RESTART = 64;
+// scalar slots (sc + o_s())
+enum { S_NORM = 0, S_INV = 1, S_ONE = 2, S_HNORM = 3, S_HINV = 4, S_RZ = 5, S_PQ = 6, S_ALPHA = 7, S_BETA = 8, S_RR = 9, S_EST = 10 };
+// status words
+enum { W_CONV = 0, W_BREAK = 1, W_SING = 2 };
+
+// ---- reductions with a fixed shape
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// sum over the workgroup; the result is valid in thread 0. lds: DXO_KR_BLOCK / 64 doubles
+__device__ __forceinline__ double block_sum(double v, double* lds) {
+    v = wave_sum(v);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) lds[w] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int k = 0; k < DXO_KR_BLOCK / 64; ++k) s += lds[k];
+    __syncthreads();
+    return s;
+}
+
+// ---- SpMV
+template <int BS, int LW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void csr_spmv(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                         const double* __restrict__ values, double alpha, const double* __restrict__ x,
+                                                         double beta, double* __restrict__ y) {
+    constexpr int NPB = DXO_KR_BLOCK / LW;
+    const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
+    const int lane = threadIdx.x % LW;
+    double acc[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+    if (node < n_nodes) {
+        const int64_t r0 = row_ptr[node * BS];
+        const int64_t len = row_ptr[node * BS + 1] - r0;      // BS * neighbours
+        const int nnb = (int)(len / BS);
+        for (int k = lane; k < nnb; k += LW) {
+            const int64_t c = col[r0 + (int64_t)k * BS];
+            double xb[BS];
+#pragma unroll
+            for (int j = 0; j < BS; ++j) xb[j] = x[c + j];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) {
+                const double* v = values + r0 + i * len + (int64_t)k * BS;
+#pragma unroll
+                for (int j = 0; j < BS; ++j) acc[i] = fma(v[j], xb[j], acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = LW / 2; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    if (node < n_nodes && lane == 0) {
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            const int64_t r = node * BS + i;
+            y[r] = beta == 0.0 ? alpha * acc[i] : alpha * acc[i] + beta * y[r];
+        }
+    }
+}
+
+// ---- block Jacobi
+template <int BS>
+__device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (&b)[BS][BS]) {
+    double had = 1.0;
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) s += a[i][j] * a[i][j];
+        had *= sqrt(s);
+    }
+    double det;
+    if constexpr (BS == 1) {
+        det = a[0][0];
+        b[0][0] = 1.0 / det;
+    } else if constexpr (BS == 2) {
+        det = a[0][0] * a[1][1] - a[0][1] * a[1][0];
+        const double id = 1.0 / det;
+        b[0][0] = a[1][1] * id;
+        b[0][1] = -a[0][1] * id;
+        b[1][0] = -a[1][0] * id;
+        b[1][1] = a[0][0] * id;
+    } else {
+        const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1];
+        const double c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2];
+        const double c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];
+        det = a[0][0] * c00 + a[0][1] * c01 + a[0][2] * c02;
+        const double id = 1.0 / det;
+        b[0][0] = c00 * id;
+        b[1][0] = c01 * id;
+        b[2][0] = c02 * id;
+        b[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) * id;
+        b[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) * id;
+        b[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) * id;
+        b[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) * id;
+        b[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) * id;
+        b[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) * id;
+    }
+    return fabs(det) > 1e-14 * had;     // false for a zero, NaN or nearly singular block
+}
+
+template <int BS>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void bj_setup(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                         const double* __restrict__ values, double* __restrict__ inv, int* __restrict__ singular) {
+    const int64_t node = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x;
+    if (node >= n_nodes) return;
+    const int64_t r0 = row_ptr[node * BS];
+    const int64_t len = row_ptr[node * BS + 1] - r0;
+    int lo = 0, hi = (int)(len / BS) - 1;
+    const int64_t self = node * BS;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (col[r0 + (int64_t)mid * BS] < self) lo = mid + 1;
+        else hi = mid;
+    }
+    double a[BS][BS], b[BS][BS];
+    bool ok = hi >= 0 && col[r0 + (int64_t)lo * BS] == self;     // an empty row has no block to read
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) a[i][j] = values[r0 + i * len + (int64_t)lo * BS + j];
+        ok = invert_block<BS>(a, b);
+    }
+    double* out = inv + node * BS * BS;
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) out[i * BS + j] = ok ? b[i][j] : 0.0;
+    if (!ok) singular[0] = 1;     // every writer stores the same word
+}
+
+template <int BS>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void bj_apply(int64_t n_nodes, const double* __restrict__ inv, const double* __restrict__ r,
+                                                         double* __restrict__ z) {
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
+    for (int64_t node = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; node < n_nodes; node += stride) {
+        const double* B = inv + node * BS * BS;
+        double rb[BS];
+#pragma unroll
+        for (int j = 0; j < BS; ++j) rb[j] = r[node * BS + j];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < BS; ++j) s = fma(B[i * BS + j], rb[j], s);
+            z[node * BS + i] = s;
+        }
+    }
+}
+
+// ---- Krylov building blocks. Row kernels run on exactly nb workgroups (grid stride): the rows a thread adds are fixed.
+// part[k * nb + block] = sum over the block's rows of V_k[i] w[i], k < nk; w is read once for all nk products
+template <int KMAX>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_multidot(int64_t n, const double* __restrict__ V, int64_t ld, int nk,
+                                                            const double* __restrict__ w, double* __restrict__ part) {
+    __shared__ double lds[DXO_KR_BLOCK / 64][KMAX];
+    double acc[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double wi = w[i];
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < nk) acc[k] = fma(V[k * ld + i], wi, acc[k]);
+    }
+    const int wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        if (k < nk) {
+            const double s = wave_sum(acc[k]);
+            if ((threadIdx.x & 63) == 0) lds[wv][k] = s;
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nk; k += DXO_KR_BLOCK) {
+        double s = 0.0;
+        for (int q = 0; q < DXO_KR_BLOCK / 64; ++q) s += lds[q][k];
+        part[(int64_t)k * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// one workgroup per product k: out[k] = sum_b part[k * nb + b]; acc (optional) += out; norm mode (nk = 1): out[0] = sqrt(sum),
+// inv_out[0] = 1 / out[0] (0 for a zero sum)
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_reduce(const double* __restrict__ part, int nb, double* __restrict__ out,
+                                                          double* __restrict__ acc, int norm, double* __restrict__ inv_out) {
+    __shared__ double lds[DXO_KR_BLOCK / 64];
+    const int k = blockIdx.x;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += DXO_KR_BLOCK) s += part[(int64_t)k * nb + b];
+    s = block_sum(s, lds);
+    if (threadIdx.x == 0) {
+        if (norm) {
+            const double r = sqrt(s);
+            out[k] = r;
+            inv_out[k] = r > 0.0 ? 1.0 / r : 0.0;
+        } else {
+            out[k] = s;
+            if (acc) acc[k] += s;
+        }
+    }
+}
+
+// w -= sum_k V_k h_k (k ascending), and npart[block] = the block's share of |w|^2
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_update(int64_t n, const double* __restrict__ V, int64_t ld, int nk, const double* __restrict__ h,
+                                                          double* __restrict__ w, double* __restrict__ npart) {
+    __shared__ double lds[DXO_KR_BLOCK / 64];
+    double acc = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) {
+        double s = w[i];
+        for (int k = 0; k < nk; ++k) s = fma(-V[k * ld + i], h[k], s);
+        w[i] = s;
+        acc = fma(s, s, acc);
+    }
+    acc = block_sum(acc, lds);
+    if (threadIdx.x == 0) npart[blockIdx.x] = acc;
+}
+
+// out = sum_k V_k y_k (k ascending)
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_combine(int64_t n, const double* __restrict__ V, int64_t ld, int nk, const double* __restrict__ y,
+                                                           double* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) {
+        double s = 0.0;
+        for (int k = 0; k < nk; ++k) s = fma(V[k * ld + i], y[k], s);
+        out[i] = s;
+    }
+}
+
+// y = x * s[0] (in place allowed)
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_scale(int64_t n, const double* x, const double* __restrict__ s, double* y) {
+    const double a = s[0];
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) y[i] = x[i] * a;
+}
+
+// y += sign * a[0] * x
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_axpy(int64_t n, const double* __restrict__ a, double sign, const double* __restrict__ x,
+                                                        double* __restrict__ y) {
+    const double s = sign * a[0];
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) y[i] = fma(s, x[i], y[i]);
+}
+
+// y = x + b[0] * y
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_xpay(int64_t n, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ y) {
+    const double s = b[0];
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) y[i] = fma(s, y[i], x[i]);
+}
+
+// y = b - y
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_bminus(int64_t n, const double* __restrict__ b, double* __restrict__ y) {
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) y[i] = b[i] - y[i];
+}
+
+// start of a GMRES cycle: g = (beta, 0, ...), no converged step, no breakdown
+__global__ void kr_cycle_init(double* __restrict__ sc, int* __restrict__ st, int m, int64_t o_g, int64_t o_s) {
+    for (int i = threadIdx.x; i <= m; i += blockDim.x) sc[o_g + i] = i == 0 ? sc[o_s + S_NORM] : 0.0;
+    if (threadIdx.x == 0) {
+        st[W_CONV] = -1;
+        st[W_BREAK] = 0;
+    }
+}
+
+// one thread: the Givens step of column j. H[j+1][j] is in S_HNORM
+__global__ void kr_givens(double* __restrict__ sc, int* __restrict__ st, int j, int m, int64_t o_g, int64_t o_cs, int64_t o_sn, int64_t o_s,
+                          double tol) {
+    if (threadIdx.x != 0) return;
+    double* h = sc + (int64_t)j * (m + 1);
+    double* g = sc + o_g;
+    double* cs = sc + o_cs;
+    double* sn = sc + o_sn;
+    const double hn = sc[o_s + S_HNORM];
+    h[j + 1] = hn;
+    for (int i = 0; i < j; ++i) {
+        const double t = cs[i] * h[i] + sn[i] * h[i + 1];
+        h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1];
+        h[i] = t;
+    }
+    const double r = hypot(h[j], hn);
+    double c = 1.0, s = 0.0;
+    if (r > 0.0) {
+        c = h[j] / r;
+        s = hn / r;
+    }
+    cs[j] = c;
+    sn[j] = s;
+    h[j] = r;
+    h[j + 1] = 0.0;
+    g[j + 1] = -s * g[j];
+    g[j] = c * g[j];
+    const double est = fabs(g[j + 1]);
+    sc[o_s + S_EST] = est;
+    if (!(hn > 0.0)) st[W_BREAK] = 1;
+    if (st[W_CONV] < 0 && (est <= tol || !(hn > 0.0))) st[W_CONV] = j + 1;
+}
+
+// one thread: R y = g on the first k columns (back substitution); a zero pivot gives y_i = 0
+__global__ void kr_trisolve(double* __restrict__ sc, int k, int m, int64_t o_g, int64_t o_y) {
+    if (threadIdx.x != 0) return;
+    const double* g = sc + o_g;
+    double* y = sc + o_y;
+    for (int i = k - 1; i >= 0; --i) {
+        double s = g[i];
+        for (int c = i + 1; c < k; ++c) s -= sc[(int64_t)c * (m + 1) + i] * y[c];
+        const double d = sc[(int64_t)i * (m + 1) + i];
+        y[i] = d != 0.0 ? s / d : 0.0;
+    }
+}
+
+// CG scalars, one workgroup: reduce the partials of one dot product, then
+//   phase 0: S_RZ = (r, z);  phase 1: S_ALPHA = rz / (p, q) (0 once converged or at (p, q) = 0);
+//   phase 2: (r, r) -> records the first step `it` with |r| <= tol;  phase 3: S_BETA = (r, z)_new / S_RZ, S_RZ = (r, z)_new
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_cg_scalar(const double* __restrict__ part, int nb, double* __restrict__ s, int* __restrict__ st,
+                                                             int phase, int it, double tol) {
+    __shared__ double lds[DXO_KR_BLOCK / 64];
+    double v = 0.0;
+    for (int b = threadIdx.x; b < nb; b += DXO_KR_BLOCK) v += part[b];
+    v = block_sum(v, lds);
+    if (threadIdx.x != 0) return;
+    const bool done = st[W_CONV] >= 0;
+    if (phase == 0) {
+        s[S_RZ] = v;
+    } else if (phase == 1) {
+        s[S_PQ] = v;
+        if (!done && !(v != 0.0 && std::isfinite(v))) {
+            st[W_BREAK] = 1;
+            st[W_CONV] = it - 1;
+        }
+        s[S_ALPHA] = (st[W_CONV] >= 0) ? 0.0 : s[S_RZ] / v;
+    } else if (phase == 2) {
+        s[S_RR] = v;
+        s[S_EST] = sqrt(v);
+        if (!done && sqrt(v) <= tol) st[W_CONV] = it;
+    } else {
+        s[S_BETA] = s[S_RZ] != 0.0 ? v / s[S_RZ] : 0.0;
+        s[S_RZ] = v;
+    }
+}
+
+// ---- host side
+int kr_grid(const dxo_ctx* ctx, int64_t n, int per_cu) {
+    int64_t blocks = (n + DXO_KR_BLOCK - 1) / DXO_KR_BLOCK;
+    const int64_t cap = (int64_t)ctx->compute_units * per_cu;
+    if (blocks > cap) blocks = cap;
+    return blocks < 1 ? 1 : (int)blocks;
+}
+
+template <int BS>
+void spmv_bs(int lw, int64_t n_nodes, const dxo_csr* A, const double* values, double alpha, const double* x, double beta, double* y, hipStream_t s) {
+    auto grid = [&](int per) { return dim3((unsigned)((n_nodes + per - 1) / per)); };
+    switch (lw) {
+        case 8: hipLaunchKernelGGL((csr_spmv<BS, 8>), grid(DXO_KR_BLOCK / 8), dim3(DXO_KR_BLOCK), 0, s, n_nodes, A->d_row_ptr, A->d_col, values, alpha, x, beta, y); break;
+        case 16: hipLaunchKernelGGL((csr_spmv<BS, 16>), grid(DXO_KR_BLOCK / 16), dim3(DXO_KR_BLOCK), 0, s, n_nodes, A->d_row_ptr, A->d_col, values, alpha, x, beta, y); break;
+        case 32: hipLaunchKernelGGL((csr_spmv<BS, 32>), grid(DXO_KR_BLOCK / 32), dim3(DXO_KR_BLOCK), 0, s, n_nodes, A->d_row_ptr, A->d_col, values, alpha, x, beta, y); break;
+        default: hipLaunchKernelGGL((csr_spmv<BS, 64>), grid(DXO_KR_BLOCK / 64), dim3(DXO_KR_BLOCK), 0, s, n_nodes, A->d_row_ptr, A->d_col, values, alpha, x, beta, y); break;
+    }
+}
+
+// lanes per node: the option, or the smallest of 8 / 16 / 32 / 64 that covers the mean neighbour count
+int spmv_lanes(const dxo_ctx* ctx, const dxo_csr* A) {
+    if (ctx->spmv_lanes == 8 || ctx->spmv_lanes == 16 || ctx->spmv_lanes == 32 || ctx->spmv_lanes == 64) return (int)ctx->spmv_lanes;
+    const double mean = A->n_nodes > 0 ? (double)A->nnz / ((double)A->bs * A->bs * (double)A->n_nodes) : 1.0;
+    int lw = 8;
+    while (lw < 64 && lw < mean) lw *= 2;
+    return lw;
+}
+
+void spmv_launch(const dxo_ctx* ctx, const dxo_csr* A, const double* values, double alpha, const double* x, double beta, double* y, hipStream_t s) {
+    if (A->n_nodes == 0) return;
+    const int lw = spmv_lanes(ctx, A);
+    if (A->bs == 1) spmv_bs<1>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
+    else if (A->bs == 2) spmv_bs<2>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
+    else spmv_bs<3>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
+}
+
+void bj_apply_launch(const dxo_ctx* ctx, int bs, int64_t n, const double* inv, const double* r, double* z, hipStream_t s) {
+    const int64_t nn = n / bs;
+    if (nn == 0) return;
+    const dim3 g(kr_grid(ctx, nn, 8)), b(DXO_KR_BLOCK);
+    if (bs == 1) hipLaunchKernelGGL(bj_apply<1>, g, b, 0, s, nn, inv, r, z);
+    else if (bs == 2) hipLaunchKernelGGL(bj_apply<2>, g, b, 0, s, nn, inv, r, z);
+    else hipLaunchKernelGGL(bj_apply<3>, g, b, 0, s, nn, inv, r, z);
+}
+
+bool misaligned(const void* p) { return ((uintptr_t)p & 7u) != 0; }
+
+// the operator and preconditioner of one solve, validated
+struct KrCall {
+    dxo_ctx* ctx;
+    dxo_krylov* ws;
+    const dxo_krylov_op* op;
+    const dxo_krylov_pc* pc;
+    hipStream_t s;
+    int apply(const double* v, double* out) {
+        if (op->csr) {
+            spmv_launch(ctx, op->csr, op->values, 1.0, v, 0.0, out, s);
+            return DXO_OK;
+        }
+        const int rc = op->apply(op->user, v, out);
+        if (rc != DXO_OK) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "dxo_krylov: the operator callback returned %d", rc);
+            return dxo_fail(ctx, rc < 0 ? rc : DXO_E_OPTION, msg);
+        }
+        return DXO_OK;
+    }
+    void precond(const double* r, double* z) {
+        if (!pc || pc->kind == DXO_PC_NONE) {
+            (void)hipMemcpyAsync(z, r, (size_t)ws->n * sizeof(double), hipMemcpyDeviceToDevice, s);
+            return;
+        }
+        bj_apply_launch(ctx, pc->kind == DXO_PC_JACOBI ? 1 : pc->bs, ws->n, pc->inv, r, z, s);
+    }
+    // part[0..nb) = partials of (a, b); reduce into out (norm: sqrt and inverse into out[0], out[1])
+    void dot_partials(const double* a, const double* b, double* part) {
+        hipLaunchKernelGGL((kr_multidot<1>), dim3(ws->nb), dim3(DXO_KR_BLOCK), 0, s, ws->n, a, ws->ld, 1, b, part);
+    }
+    void norm(const double* a, double* out) {
+        dot_partials(a, a, ws->part);
+        hipLaunchKernelGGL(kr_reduce, dim3(1), dim3(DXO_KR_BLOCK), 0, s, ws->part, ws->nb, out, (double*)nullptr, 1, out + 1);
+    }
+    int read(void* host, const void* dev, size_t bytes) {
+        DXO_HIP(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+        DXO_HIP(ctx, hipStreamSynchronize(s));
+        return DXO_OK;
+    }
+    // R = b - A x, its norm into S_NORM / S_INV; host copy in *beta
+    int residual(const double* b, const double* x, double* beta) {
+        int rc = apply(x, ws->R());
+        if (rc != DXO_OK) return rc;
+        hipLaunchKernelGGL(kr_bminus, dim3(ws->nb), dim3(DXO_KR_BLOCK), 0, s, ws->n, b, ws->R());
+        norm(ws->R(), ws->sc + ws->o_s() + S_NORM);
+        return read(beta, ws->sc + ws->o_s() + S_NORM, sizeof(double));
+    }
+};
+
+int kr_validate(dxo_ctx* ctx, const char* who, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
+                double rtol, double atol, int max_it, int check_every) {
+    char msg[256];
+    if (!ws || !op || !b || !x) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": NULL argument").c_str());
+    if (!op->csr && !op->apply) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the operator has neither a matrix nor a callback").c_str());
+    if (op->csr && !op->values) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the operator's matrix has no values").c_str());
+    if (op->n != ws->n || (op->csr && op->csr->n_rows != ws->n)) {
+        snprintf(msg, sizeof msg, "%s: operator size %lld (matrix rows %lld) differs from the workspace's %lld", who, (long long)op->n,
+                 (long long)(op->csr ? op->csr->n_rows : op->n), (long long)ws->n);
+        return dxo_fail(ctx, DXO_E_SIZE, msg);
+    }
+    if (pc && pc->kind != DXO_PC_NONE) {
+        if (pc->kind != DXO_PC_JACOBI && pc->kind != DXO_PC_BLOCK_JACOBI) return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": unknown preconditioner kind").c_str());
+        if (!pc->inv) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the preconditioner has no inverse").c_str());
+        if (misaligned(pc->inv)) return dxo_fail(ctx, DXO_E_ALIGN, (std::string(who) + ": the preconditioner's inverse is not 8-byte aligned").c_str());
+        if (pc->n != ws->n) {
+            snprintf(msg, sizeof msg, "%s: the preconditioner covers %lld rows, the operator has %lld", who, (long long)pc->n, (long long)ws->n);
+            return dxo_fail(ctx, DXO_E_SIZE, msg);
+        }
+        if (pc->kind == DXO_PC_BLOCK_JACOBI) {
+            if (pc->bs < 1 || pc->bs > 3) return dxo_fail(ctx, DXO_E_DIM, (std::string(who) + ": block Jacobi takes bs 1, 2 or 3").c_str());
+            if (op->csr && op->csr->bs != pc->bs) {
+                snprintf(msg, sizeof msg, "%s: block Jacobi of bs %d on a pattern of bs %d", who, pc->bs, op->csr->bs);
+                return dxo_fail(ctx, DXO_E_DIM, msg);
+            }
+            if (ws->n % pc->bs != 0) return dxo_fail(ctx, DXO_E_SIZE, (std::string(who) + ": n is not a multiple of the preconditioner's bs").c_str());
+        }
+    }
+    if ((op->values && misaligned(op->values)) || misaligned(b) || misaligned(x))
+        return dxo_fail(ctx, DXO_E_ALIGN, (std::string(who) + ": arrays must be 8-byte aligned").c_str());
+    if (max_it < 0 || check_every < 1) return dxo_fail(ctx, DXO_E_SIZE, (std::string(who) + ": max_it < 0 or check_every < 1").c_str());
+    if (!(rtol >= 0.0) || !(atol >= 0.0)) return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": negative or NaN tolerance").c_str());
+    return DXO_OK;
+}
+
+void kr_multidot_launch(const KrCall& K, int nk, const double* w) {
+    dxo_krylov* ws = K.ws;
+    const dim3 g(ws->nb), b(DXO_KR_BLOCK);
+    if (nk <= 4) hipLaunchKernelGGL((kr_multidot<4>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
+    else if (nk <= 8) hipLaunchKernelGGL((kr_multidot<8>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
+    else if (nk <= 16) hipLaunchKernelGGL((kr_multidot<16>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
+    else if (nk <= 32) hipLaunchKernelGGL((kr_multidot<32>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
+    else hipLaunchKernelGGL((kr_multidot<64>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
+}
+
+int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
+    dxo_ctx* ctx = K.ctx;
+    dxo_krylov* ws = K.ws;
+    const hipStream_t s = K.s;
+    const int m = ws->m;
+    const int64_t n = ws->n;
+    double* sc = ws->sc;
+    double* S = sc + ws->o_s();
+    double* npart = ws->part + (int64_t)(m + 1) * ws->nb;
+    const dim3 G(ws->nb), B(DXO_KR_BLOCK);
+    const bool reorth = ctx->krylov_reorth != 0;
+    // |b|
+    K.norm(b, S + S_NORM);
+    double bnorm = 0.0;
+    int rc = K.read(&bnorm, S + S_NORM, sizeof(double));
+    if (rc != DXO_OK) return rc;
+    if (bnorm == 0.0) {
+        DXO_HIP(ctx, hipMemsetAsync(x, 0, (size_t)n * sizeof(double), s));
+        DXO_HIP(ctx, hipStreamSynchronize(s));
+        info->converged = 1;
+        return DXO_OK;
+    }
+    const double tol = std::max(rtol * bnorm, atol);
+    int total = 0;
+    double beta = 0.0;
+    for (;;) {
+        if ((rc = K.residual(b, x, &beta)) != DXO_OK) return rc;
+        info->residual = beta / bnorm;
+        if (beta <= tol) {
+            info->converged = 1;
+            break;
+        }
+        if (total >= max_it || info->breakdown) break;
+        ++info->restarts;
+        hipLaunchKernelGGL(kr_scale, G, B, 0, s, n, ws->R(), S + S_INV, ws->V());
+        hipLaunchKernelGGL(kr_cycle_init, dim3(1), dim3(64), 0, s, sc, ws->st, m, ws->o_g(), ws->o_s());
+        int done = 0, status[2] = {-1, 0};
+        for (int j = 0; j < m && total + j < max_it; ++j) {
+            double* w = ws->V() + (int64_t)(j + 1) * ws->ld;
+            double* h = sc + (int64_t)j * (m + 1);
+            K.precond(ws->V() + (int64_t)j * ws->ld, ws->Z());
+            if ((rc = K.apply(ws->Z(), w)) != DXO_OK) return rc;
+            kr_multidot_launch(K, j + 1, w);
+            hipLaunchKernelGGL(kr_reduce, dim3(j + 1), B, 0, s, ws->part, ws->nb, h, (double*)nullptr, 0, (double*)nullptr);
+            hipLaunchKernelGGL(kr_update, G, B, 0, s, n, ws->V(), ws->ld, j + 1, h, w, npart);
+            if (reorth) {
+                double* c = sc + ws->o_c();
+                kr_multidot_launch(K, j + 1, w);
+                hipLaunchKernelGGL(kr_reduce, dim3(j + 1), B, 0, s, ws->part, ws->nb, c, h, 0, (double*)nullptr);
+                hipLaunchKernelGGL(kr_update, G, B, 0, s, n, ws->V(), ws->ld, j + 1, c, w, npart);
+            }
+            hipLaunchKernelGGL(kr_reduce, dim3(1), B, 0, s, npart, ws->nb, S + S_HNORM, (double*)nullptr, 1, S + S_HINV);
+            hipLaunchKernelGGL(kr_scale, G, B, 0, s, n, w, S + S_HINV, w);
+            hipLaunchKernelGGL(kr_givens, dim3(1), dim3(64), 0, s, sc, ws->st, j, m, ws->o_g(), ws->o_cs(), ws->o_sn(), ws->o_s(), tol);
+            done = j + 1;
+            if ((total + done) % check_every == 0 || done == m || total + done == max_it) {
+                if ((rc = K.read(status, ws->st, sizeof status)) != DXO_OK) return rc;
+                if (status[W_CONV] >= 0) break;
+            }
+        }
+        if (status[W_CONV] < 0 && (rc = K.read(status, ws->st, sizeof status)) != DXO_OK) return rc;
+        const int k = status[W_CONV] >= 0 ? status[W_CONV] : done;
+        if (status[W_BREAK]) info->breakdown = 1;
+        total += k;
+        if (k > 0) {
+            hipLaunchKernelGGL(kr_trisolve, dim3(1), dim3(64), 0, s, sc, k, m, ws->o_g(), ws->o_y());
+            hipLaunchKernelGGL(kr_combine, G, B, 0, s, n, ws->V(), ws->ld, k, sc + ws->o_y(), ws->T());
+            K.precond(ws->T(), ws->Z());
+            hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ONE, 1.0, ws->Z(), x);
+        }
+        if (k == 0) break;
+    }
+    info->iterations = total;
+    return DXO_OK;
+}
+
+int cg_impl(KrCall& K, const double* b, double* x, double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
+    dxo_ctx* ctx = K.ctx;
+    dxo_krylov* ws = K.ws;
+    const hipStream_t s = K.s;
+    const int64_t n = ws->n;
+    double* S = ws->sc + ws->o_s();
+    int* st = ws->st;
+    const dim3 G(ws->nb), B(DXO_KR_BLOCK), One(1);
+    K.norm(b, S + S_NORM);
+    double bnorm = 0.0;
+    int rc = K.read(&bnorm, S + S_NORM, sizeof(double));
+    if (rc != DXO_OK) return rc;
+    if (bnorm == 0.0) {
+        DXO_HIP(ctx, hipMemsetAsync(x, 0, (size_t)n * sizeof(double), s));
+        DXO_HIP(ctx, hipStreamSynchronize(s));
+        info->converged = 1;
+        return DXO_OK;
+    }
+    const double tol = std::max(rtol * bnorm, atol);
+    double* r = ws->R();
+    double* z = ws->Z();
+    double* p = ws->T();
+    double* q = ws->Q();
+    double beta = 0.0;
+    if ((rc = K.residual(b, x, &beta)) != DXO_OK) return rc;
+    int it = 0;
+    if (beta > tol && max_it > 0) {
+        info->restarts = 1;
+        hipLaunchKernelGGL(kr_cycle_init, One, dim3(64), 0, s, ws->sc, st, 0, ws->o_g(), ws->o_s());
+        K.precond(r, z);
+        DXO_HIP(ctx, hipMemcpyAsync(p, z, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        K.dot_partials(r, z, ws->part);
+        hipLaunchKernelGGL(kr_cg_scalar, One, B, 0, s, ws->part, ws->nb, S, st, 0, 0, tol);
+        int status[2] = {-1, 0};
+        for (it = 1; it <= max_it; ++it) {
+            if ((rc = K.apply(p, q)) != DXO_OK) return rc;
+            K.dot_partials(p, q, ws->part);
+            hipLaunchKernelGGL(kr_cg_scalar, One, B, 0, s, ws->part, ws->nb, S, st, 1, it, tol);
+            hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ALPHA, 1.0, p, x);
+            hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ALPHA, -1.0, q, r);
+            K.dot_partials(r, r, ws->part);
+            hipLaunchKernelGGL(kr_cg_scalar, One, B, 0, s, ws->part, ws->nb, S, st, 2, it, tol);
+            K.precond(r, z);
+            K.dot_partials(r, z, ws->part);
+            hipLaunchKernelGGL(kr_cg_scalar, One, B, 0, s, ws->part, ws->nb, S, st, 3, it, tol);
+            hipLaunchKernelGGL(kr_xpay, G, B, 0, s, n, z, S + S_BETA, p);
+            if (it % check_every == 0 || it == max_it) {
+                if ((rc = K.read(status, st, sizeof status)) != DXO_OK) return rc;
+                if (status[W_CONV] >= 0) break;
+            }
+        }
+        it = status[W_CONV] >= 0 ? status[W_CONV] : max_it;
+        if (status[W_BREAK]) info->breakdown = 1;
+        if ((rc = K.residual(b, x, &beta)) != DXO_OK) return rc;
+    }
+    info->iterations = it;
+    info->residual = beta / bnorm;
+    info->converged = beta <= tol;
+    return DXO_OK;
+}
+
+typedef int (*kr_solver)(KrCall&, const double*, double*, double, double, int, int, dxo_krylov_info*);
+
+int kr_solve(dxo_ctx* ctx, const char* who, kr_solver solver, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b,
+             double* x, double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = kr_validate(ctx, who, ws, op, pc, b, x, rtol, atol, max_it, check_every);
+    if (rc != DXO_OK) return rc;
+    dxo_krylov_info local;
+    dxo_krylov_info* inf = info ? info : &local;
+    *inf = dxo_krylov_info{};
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    KrCall K{ctx, ws, op, pc, dxo_launch_stream(ctx)};
+    rc = solver(K, b, x, rtol, atol, max_it, check_every, inf);
+    inf->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!csr || !values || !x || !y) return dxo_fail(ctx, DXO_E_NULL, "dxo_csr_spmv: NULL argument");
+    if (misaligned(values) || misaligned(x) || misaligned(y)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_csr_spmv: arrays must be 8-byte aligned");
+    hipStream_t s = dxo_launch_stream(ctx);
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    spmv_launch(ctx, csr, values, alpha, x, beta, y, s);
+    return dxo_device_end(ctx, s);
+}
+
+extern "C" int dxo_csr_block_jacobi(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double* inv) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!csr || !values || !inv) return dxo_fail(ctx, DXO_E_NULL, "dxo_csr_block_jacobi: NULL argument");
+    if (misaligned(values) || misaligned(inv)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_csr_block_jacobi: arrays must be 8-byte aligned");
+    if (csr->n_nodes == 0) return DXO_OK;
+    hipStream_t s = dxo_launch_stream(ctx);
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    int* flag = (int*)dxo_scratch(ctx, s, 16);
+    if (!flag) return dxo_fail(ctx, DXO_E_SIZE, "dxo_csr_block_jacobi: scratch allocation failed");
+    DXO_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int), s));
+    const dim3 g((unsigned)((csr->n_nodes + DXO_KR_BLOCK - 1) / DXO_KR_BLOCK)), b(DXO_KR_BLOCK);
+    if (csr->bs == 1) hipLaunchKernelGGL(bj_setup<1>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+    else if (csr->bs == 2) hipLaunchKernelGGL(bj_setup<2>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+    else hipLaunchKernelGGL(bj_setup<3>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+    int h = 0;
+    DXO_HIP(ctx, hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    DXO_HIP(ctx, hipStreamSynchronize(s));
+    if (h) return dxo_fail(ctx, DXO_E_SINGULAR, "dxo_csr_block_jacobi: a diagonal block is singular (its inverse was set to zero)");
+    return DXO_OK;
+}
+
+extern "C" int dxo_block_jacobi_apply(dxo_ctx* ctx, int bs, int64_t n, const double* inv, const double* r, double* z) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!inv || !r || !z) return dxo_fail(ctx, DXO_E_NULL, "dxo_block_jacobi_apply: NULL argument");
+    if (bs < 1 || bs > 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_block_jacobi_apply: bs must be 1, 2 or 3");
+    if (n < 0 || n % bs != 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_block_jacobi_apply: n < 0 or not a multiple of bs");
+    if (misaligned(inv) || misaligned(r) || misaligned(z)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_block_jacobi_apply: arrays must be 8-byte aligned");
+    hipStream_t s = dxo_launch_stream(ctx);
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    bj_apply_launch(ctx, bs, n, inv, r, z, s);
+    return dxo_device_end(ctx, s);
+}
+
+extern "C" int dxo_krylov_create(dxo_ctx* ctx, int64_t n, int restart, dxo_krylov** out) {
+    if (!ctx || !out) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    *out = nullptr;
+    if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_krylov_create: n < 0");
+    if (restart < 1 || restart > KR_MAX_RESTART) return dxo_fail(ctx, DXO_E_SIZE, "dxo_krylov_create: restart must lie in [1, 64]");
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    dxo_krylov* w = new dxo_krylov;
+    w->n = n;
+    w->m = restart;
+    w->ld = std::max<int64_t>(32, (n + 31) / 32 * 32);
+    w->nb = kr_grid(ctx, n, 4);
+    auto fail = [&](hipError_t e, const char* what) {
+        for (void* p : {(void*)w->vec, (void*)w->part, (void*)w->sc, (void*)w->st})
+            if (p) (void)hipFree(p);
+        delete w;
+        return dxo_hip_fail(ctx, e, what);
+    };
+    hipError_t e;
+    if ((e = hipMalloc((void**)&w->vec, (size_t)(w->m + 5) * w->ld * sizeof(double))) != hipSuccess) return fail(e, "dxo_krylov_create: basis");
+    if ((e = hipMalloc((void**)&w->part, (size_t)(w->m + 2) * w->nb * sizeof(double))) != hipSuccess) return fail(e, "dxo_krylov_create: partials");
+    if ((e = hipMalloc((void**)&w->sc, (size_t)w->sc_doubles() * sizeof(double))) != hipSuccess) return fail(e, "dxo_krylov_create: state");
+    if ((e = hipMalloc((void**)&w->st, 16 * sizeof(int))) != hipSuccess) return fail(e, "dxo_krylov_create: status");
+    std::vector<double> init((size_t)w->sc_doubles(), 0.0);
+    init[(size_t)(w->o_s() + S_ONE)] = 1.0;
+    if ((e = hipMemcpy(w->sc, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "dxo_krylov_create: state");
+    if ((e = hipMemset(w->vec, 0, (size_t)(w->m + 5) * w->ld * sizeof(double))) != hipSuccess) return fail(e, "dxo_krylov_create: basis");
+    if ((e = hipMemset(w->st, 0, 16 * sizeof(int))) != hipSuccess) return fail(e, "dxo_krylov_create: status");
+    *out = w;
+    return DXO_OK;
+}
+
+extern "C" int dxo_krylov_destroy(dxo_ctx* ctx, dxo_krylov* ws) {
+    if (!ws) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (ctx) (void)hipSetDevice(ctx->device);
+    (void)hipDeviceSynchronize();
+    for (void* p : {(void*)ws->vec, (void*)ws->part, (void*)ws->sc, (void*)ws->st})
+        if (p) (void)hipFree(p);
+    delete ws;
+    return DXO_OK;
+}
+
+extern "C" int dxo_krylov_gmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
+                                double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    return kr_solve(ctx, "dxo_krylov_gmres", gmres_impl, ws, op, pc, b, x, rtol, atol, max_it, check_every, info);
+}
+
+extern "C" int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
+                             double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    return kr_solve(ctx, "dxo_krylov_cg", cg_impl, ws, op, pc, b, x, rtol, atol, max_it, check_every, info);
+}

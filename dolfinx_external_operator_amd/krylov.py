@@ -1,0 +1,212 @@
+"""Linear solves on the device (csrc/krylov.hip): CSR SpMV, block Jacobi, restarted GMRES and CG.
+
+All vectors are contiguous float64 CUDA tensors on the context's device. The calls run on torch's current stream of that device,
+which they make the context's stream (the convention of the examples and tests: ctx.set_stream(torch.cuda.current_stream())), so
+torch work before and after them is ordered without a synchronisation. A solve synchronises only to read its residual estimate,
+every `check_every` iterations.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import weakref
+from dataclasses import dataclass
+
+from ._lib import KRYLOV_APPLY_FN, KrylovInfo, KrylovOp, KrylovPc, _CudaArrayView
+
+PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI = 0, 1, 2
+
+
+def _torch():
+    import torch
+
+    return torch
+
+
+def _check_vec(v, n: int, dev, what: str):
+    torch = _torch()
+    if not (isinstance(v, torch.Tensor) and v.dtype == torch.float64 and v.is_cuda and v.is_contiguous() and v.numel() == n
+            and v.device == dev):
+        raise ValueError(f"{what}: expected a contiguous float64 CUDA tensor of {n} entries on {dev}")
+
+
+def _use_current_stream(ctx) -> None:
+    torch = _torch()
+    ctx.set_stream(torch.cuda.current_stream(torch.device("cuda", ctx.device)).cuda_stream)
+
+
+@dataclass
+class KrylovResult:
+    """What gmres / cg return: the solution, the iterations up to the converged step, the true relative residual |b - A x| / |b|,
+    whether it met the tolerance, whether the iteration broke down, the cycles started and the wall ms of the solve."""
+    x: object
+    iterations: int
+    residual: float
+    converged: bool
+    breakdown: bool = False
+    restarts: int = 0
+    ms: float = 0.0
+
+
+class BlockJacobi:
+    """Inverses of the bs x bs diagonal blocks of an assembled matrix, inv [n/bs][bs][bs] (dxo_csr_block_jacobi). bs = 1 is point
+    Jacobi. `apply(r, out)` sets out = M^-1 r."""
+
+    def __init__(self, ctx, bs: int, inv):
+        self.ctx, self.bs, self.inv = ctx, int(bs), inv
+        self.n = inv.numel() // self.bs
+
+    @classmethod
+    def from_csr(cls, A) -> "BlockJacobi":
+        torch = _torch()
+        ctx, bs = A.pattern.ctx, A.pattern.bs
+        inv = torch.empty(A.pattern.n_rows * bs, dtype=torch.float64, device=A.values.device)
+        _use_current_stream(ctx)
+        rc = ctx.lib.dxo_csr_block_jacobi(ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), C.c_void_p(inv.data_ptr()))
+        ctx.check(rc, "dxo_csr_block_jacobi")
+        return cls(ctx, bs, inv)
+
+    def apply(self, r, out=None):
+        torch = _torch()
+        _check_vec(r, self.n, self.inv.device, "BlockJacobi.apply: r")
+        if out is None:
+            out = torch.empty_like(r)
+        _check_vec(out, self.n, self.inv.device, "BlockJacobi.apply: out")
+        _use_current_stream(self.ctx)
+        rc = self.ctx.lib.dxo_block_jacobi_apply(self.ctx._h, self.bs, self.n, C.c_void_p(self.inv.data_ptr()), C.c_void_p(r.data_ptr()),
+                                                 C.c_void_p(out.data_ptr()))
+        self.ctx.check(rc, "dxo_block_jacobi_apply")
+        return out
+
+    def _pc(self) -> KrylovPc:
+        return KrylovPc(PC_BLOCK_JACOBI, self.bs, self.n, C.c_void_p(self.inv.data_ptr()))
+
+
+def csr_matvec(A, x, y=None, alpha: float = 1.0, beta: float = 0.0):
+    """y = alpha A x + beta y on the device (dxo_csr_spmv); with beta == 0, y is not read. Returns y."""
+    torch = _torch()
+    ctx, n = A.pattern.ctx, A.pattern.n_rows
+    _check_vec(x, n, A.values.device, "matvec: x")
+    if y is None:
+        if beta != 0.0:
+            raise ValueError("matvec: beta != 0 needs y")
+        y = torch.empty_like(x)
+    _check_vec(y, n, A.values.device, "matvec: y")
+    _use_current_stream(ctx)
+    rc = ctx.lib.dxo_csr_spmv(ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), float(alpha), C.c_void_p(x.data_ptr()), float(beta),
+                              C.c_void_p(y.data_ptr()))
+    ctx.check(rc, "dxo_csr_spmv")
+    return y
+
+
+class _Workspace:
+    """dxo_krylov of one (n, restart). The context keeps a few of them (Context._krylov_ws) for later solves of the same size;
+    Context.close() frees them. The finalizer holds the library and the raw context handle, not the Context."""
+
+    def __init__(self, ctx, n: int, restart: int):
+        h = C.c_void_p()
+        ctx.check(ctx.lib.dxo_krylov_create(ctx._h, int(n), int(restart), C.byref(h)), "dxo_krylov_create")
+        self._h = h
+        self._fin = weakref.finalize(self, ctx.lib.dxo_krylov_destroy, C.c_void_p(ctx._h.value), h)
+        self._fin.atexit = False   # at interpreter exit the device memory goes with the process
+
+    def close(self) -> None:
+        self._fin()
+
+
+def _workspace(ctx, n: int, restart: int) -> _Workspace:
+    cache = ctx.__dict__.setdefault("_krylov_ws", {})
+    key = (int(n), int(restart))
+    if key not in cache:
+        if len(cache) >= 4:    # a few sizes per context: the oldest basis is freed
+            cache.pop(next(iter(cache))).close()
+        cache[key] = _Workspace(ctx, n, restart)
+    return cache[key]
+
+
+def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxiter, check_every: int, ctx=None) -> KrylovResult:
+    torch = _torch()
+    from .operand_eval import DeviceCSR
+
+    if isinstance(A, DeviceCSR):
+        ctx, n = A.pattern.ctx, A.pattern.n_rows
+        op = KrylovOp(n, A.pattern._h, C.c_void_p(A.values.data_ptr()), KRYLOV_APPLY_FN(), None)
+        failure: list = []
+        cb = None
+    elif callable(A):
+        if ctx is None:
+            from ._lib import default_context
+
+            ctx = default_context()
+        if not isinstance(b, torch.Tensor):
+            raise ValueError(f"{entry}: b must be a float64 CUDA tensor")
+        n = b.numel()
+        views: dict = {}
+        failure = []
+
+        def view(ptr: int):
+            t = views.get(ptr)
+            if t is None:
+                t = views[ptr] = torch.as_tensor(_CudaArrayView(ctx, ptr, n, "<f8"), device=torch.device("cuda", ctx.device))
+            return t
+
+        def cb(_user, v, out):
+            try:
+                A(view(v), view(out))
+                return 0
+            except BaseException as e:      # noqa: BLE001 — re-raised after the solve returns
+                failure.append(e)
+                return 1
+
+        cb = KRYLOV_APPLY_FN(cb)
+        op = KrylovOp(n, None, None, cb, None)
+    else:
+        raise TypeError(f"{entry}: A must be a DeviceCSR or a callable (v, out) that sets out = A v")
+    dev = torch.device("cuda", ctx.device)
+    _check_vec(b, n, dev, f"{entry}: b")
+    if x is None:
+        x = torch.zeros_like(b)
+    _check_vec(x, n, dev, f"{entry}: x")
+    if M is None:
+        pc = KrylovPc(PC_NONE, 1, n, None)
+    elif isinstance(M, BlockJacobi):
+        if M.n != n or M.inv.device != dev:
+            raise ValueError(f"{entry}: the preconditioner covers {M.n} rows on {M.inv.device}, the operator has {n} on {dev}")
+        pc = M._pc()
+    elif isinstance(M, torch.Tensor):
+        _check_vec(M, n, dev, f"{entry}: M (inverse diagonal)")
+        pc = KrylovPc(PC_JACOBI, 1, n, C.c_void_p(M.data_ptr()))
+    else:
+        raise TypeError(f"{entry}: M must be None, a BlockJacobi or a tensor holding an inverse diagonal")
+    if maxiter is None:
+        maxiter = max(1000, 10 * restart)
+    ws = _workspace(ctx, n, restart)
+    info = KrylovInfo()
+    _use_current_stream(ctx)
+    rc = getattr(ctx.lib, entry)(ctx._h, ws._h, C.byref(op), C.byref(pc), C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), float(rtol),
+                                 float(atol), int(maxiter), int(check_every), C.byref(info))
+    if failure:
+        raise failure[0]
+    ctx.check(rc, entry)
+    return KrylovResult(x=x, iterations=int(info.iterations), residual=float(info.residual), converged=bool(info.converged),
+                        breakdown=bool(info.breakdown), restarts=int(info.restarts), ms=float(info.ms))
+
+
+def gmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: float = 0.0, maxiter: int | None = None,
+          check_every: int = 8, ctx=None) -> KrylovResult:
+    """Solve A x = b by restarted GMRES(restart) with right preconditioning on the device (dxo_krylov_gmres).
+
+    A: a DeviceCSR, or a callable (v, out) that sets out = A v on the device (e.g. DeviceMesh.bilinear_apply with option
+    consumer_overwrite = 1; `ctx` then names the context, default_context() otherwise). M: None, a BlockJacobi, or a float64 CUDA
+    tensor holding an inverse diagonal (1 / bilinear_diagonal for the matrix-free path). x: the initial guess, overwritten with the
+    solution (zeros if None). Converged when |b - A x| <= max(rtol |b|, atol); not converging within maxiter gives converged False,
+    not an exception."""
+    return _solve("dxo_krylov_gmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx)
+
+
+def cg(A, b, x=None, M=None, rtol: float = 1e-10, atol: float = 0.0, maxiter: int | None = None, check_every: int = 8,
+       ctx=None) -> KrylovResult:
+    """Preconditioned conjugate gradients for symmetric positive definite A and M, same arguments as gmres (dxo_krylov_cg)."""
+    return _solve("dxo_krylov_cg", A, b, x, M, 1, rtol, atol, maxiter, check_every, ctx)
+
+
+__all__ = ["BlockJacobi", "KrylovResult", "cg", "csr_matvec", "gmres"]

@@ -518,6 +518,19 @@ class DeviceCSR:
         indptr, indices, values = self.to_numpy()
         return scipy.sparse.csr_matrix((values, indices, indptr), shape=self.shape)
 
+    def matvec(self, x, y=None, alpha: float = 1.0, beta: float = 0.0):
+        """y = alpha A x + beta y on the device (dxo_csr_spmv, BLAS semantics: with beta == 0, y is not read); returns y."""
+        from .krylov import csr_matvec
+
+        return csr_matvec(self, x, y, alpha, beta)
+
+    def block_jacobi(self) -> "BlockJacobi":
+        """The inverses of the bs x bs diagonal blocks (dxo_csr_block_jacobi) as a preconditioner for krylov.gmres / krylov.cg.
+        A singular block raises ValueError (DXO_E_SINGULAR)."""
+        from .krylov import BlockJacobi
+
+        return BlockJacobi.from_csr(self)
+
 
 class DeviceOperand:
     """Plays the role of a UFL operand in `evaluation.evaluate_operands`: `.eval(entities)` returns what

@@ -43,6 +43,7 @@ extern "C" {
 #define DXO_E_ALIGN (-5)     /* device pointer not 8-byte aligned   */
 #define DXO_E_OPTION (-6)    /* unknown option / bad value          */
 #define DXO_E_NODEVICE (-7)  /* no usable HIP device                */
+#define DXO_E_SINGULAR (-8)  /* singular diagonal block (dxo_csr_block_jacobi) */
 
 #define DXO_MEM_HOST 0
 #define DXO_MEM_DEVICE 1
@@ -569,6 +570,68 @@ int dxo_csr_info(dxo_ctx* ctx, const dxo_csr* csr, int64_t* n_rows, int64_t* nnz
 int dxo_bilinear_assemble(dxo_ctx* ctx, dxo_mesh* mesh, dxo_csr* csr, int test_kind, int trial_kind, int bs, const double* C,
                           double* values);
 int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n_dofs, double diagonal, double* values);
+
+/* ---- linear solves on the device (csrc/krylov.hip), DEVICE memory only ----------------------------------------
+ * dxo_csr_spmv    : y = alpha A x + beta y for the matrix `values` on a dxo_csr pattern (BLAS semantics: with beta == 0, y is not
+ *                   read). A group of lanes owns one node and forms all bs rows of it, reading one column index per neighbouring node;
+ *                   no atomics, bit-reproducible. Option "spmv_lanes": lanes per node (8, 16, 32, 64; default 0 = from the mean
+ *                   neighbour count). Capture-safe.
+ * dxo_csr_block_jacobi : inv[n_rows/bs][bs][bs] = the inverses of the bs x bs diagonal blocks (closed form, bs <= 3; bs = 1 is point
+ *                   Jacobi). A Dirichlet row of dxo_csr_dirichlet keeps its block invertible. A block with |det| <= 1e-14 of the product
+ *                   of its row norms gets a zero inverse and the call returns DXO_E_SINGULAR; it synchronises the stream once for that.
+ * dxo_block_jacobi_apply : z = inv r per block of bs (bs = 1: an inverse diagonal, e.g. 1 / dxo_bilinear_diagonal). Capture-safe.
+ * dxo_krylov_create : a workspace for vectors of n entries and restart length `restart` (1..64): the basis, four work vectors, the
+ *                   Hessenberg matrix and the partials of the reductions, allocated once. The solves allocate nothing.
+ * dxo_krylov_gmres : restarted GMRES(restart) with right preconditioning, classical Gram-Schmidt with one reorthogonalisation pass
+ *                   (option "krylov_reorth" = 0: one pass). x is the initial guess and is overwritten by the solution. Converged when
+ *                   |b - A x| <= max(rtol |b|, atol). The host reads the residual estimate every `check_every` iterations only; the
+ *                   update uses the first step whose estimate met the tolerance, so iterations run past it cost time, not accuracy.
+ *                   The true residual b - A x is formed with the operator at every restart and at the end. b = 0 gives x = 0 after
+ *                   0 iterations. Not converging within max_it is NOT an error: info->converged = 0. Every reduction has a fixed
+ *                   shape: a solve is bit-reproducible.
+ * dxo_krylov_cg   : preconditioned CG on the same kernels and arguments (A and M symmetric positive definite).
+ * Operator: a CSR matrix (csr + values) or a callback that SETS out = A v on the context's stream (e.g. dxo_bilinear_apply with option
+ * "consumer_overwrite" = 1). The callback runs on the calling thread while the context's (recursive) lock is held, so it may call
+ * other dxo_* entry points on the same context; a nonzero return ends the solve with that code. Preconditioner: NULL or kind
+ * DXO_PC_NONE, DXO_PC_JACOBI (inv [n]) or DXO_PC_BLOCK_JACOBI (inv [n/bs][bs][bs], bs equal to the pattern's).
+ * Errors: NULL arguments DXO_E_NULL; operator, matrix, workspace and preconditioner sizes that differ, n not a multiple of bs, max_it < 0 or
+ * check_every < 1 DXO_E_SIZE; a preconditioner of another block size DXO_E_DIM; arrays not 8-byte aligned DXO_E_ALIGN; negative
+ * tolerances or an unknown preconditioner kind DXO_E_OPTION. */
+#define DXO_PC_NONE 0
+#define DXO_PC_JACOBI 1
+#define DXO_PC_BLOCK_JACOBI 2
+typedef struct dxo_krylov dxo_krylov;
+typedef int (*dxo_krylov_apply_fn)(void* user, const double* v, double* out);
+typedef struct dxo_krylov_op {
+    int64_t n;                     /* rows = columns                                      */
+    const dxo_csr* csr;            /* a matrix on this pattern ...                        */
+    const double* values;          /* ... with these values (nnz)                         */
+    dxo_krylov_apply_fn apply;     /* or, with csr NULL, this callback                    */
+    void* user;                    /* passed to apply                                     */
+} dxo_krylov_op;
+typedef struct dxo_krylov_pc {
+    int kind;                      /* DXO_PC_*                                            */
+    int bs;                        /* DXO_PC_BLOCK_JACOBI: block size (1, 2, 3)           */
+    int64_t n;                     /* rows the inverse covers: must equal the operator's  */
+    const double* inv;             /* inverse diagonal [n] or block inverses [n/bs][bs][bs] */
+} dxo_krylov_pc;
+typedef struct dxo_krylov_info {
+    int32_t iterations;            /* Krylov iterations up to the converged step          */
+    int32_t converged;             /* true relative residual met the tolerance            */
+    int32_t breakdown;             /* h_{j+1,j} == 0 (GMRES) or (p, A p) == 0 (CG)        */
+    int32_t restarts;              /* cycles started                                      */
+    double residual;               /* |b - A x| / |b| of the returned x (0 for b = 0)     */
+    double ms;                     /* wall time of the solve                              */
+} dxo_krylov_info;
+int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y);
+int dxo_csr_block_jacobi(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double* inv);
+int dxo_block_jacobi_apply(dxo_ctx* ctx, int bs, int64_t n, const double* inv, const double* r, double* z);
+int dxo_krylov_create(dxo_ctx* ctx, int64_t n, int restart, dxo_krylov** out);
+int dxo_krylov_destroy(dxo_ctx* ctx, dxo_krylov* ws);
+int dxo_krylov_gmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
+                     double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info);
+int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
+                  double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info);
 
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is
