@@ -90,7 +90,8 @@ class KrylovOp(C.Structure):
 
 
 class KrylovPc(C.Structure):
-    """dxo_krylov_pc: DXO_PC_NONE (0), DXO_PC_JACOBI (1, inv [n]) or DXO_PC_BLOCK_JACOBI (2, inv [n/bs][bs][bs])."""
+    """dxo_krylov_pc: DXO_PC_NONE (0), DXO_PC_JACOBI (1, inv [n]), DXO_PC_BLOCK_JACOBI (2, inv [n/bs][bs][bs]) or DXO_PC_AMG (3, inv
+    carries the dxo_amg handle)."""
     _fields_ = [("kind", C.c_int), ("bs", C.c_int), ("n", C.c_int64), ("inv", _P)]
 
 
@@ -98,6 +99,13 @@ class KrylovInfo(C.Structure):
     """dxo_krylov_info."""
     _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("breakdown", C.c_int32), ("restarts", C.c_int32),
                 ("residual", C.c_double), ("ms", C.c_double)]
+
+
+class AmgLevelInfo(C.Structure):
+    """dxo_amg_level_info: counts and the device arrays of one multigrid level."""
+    _fields_ = [("n_rows", C.c_int64), ("n_nodes", C.c_int64), ("nnz_blocks", C.c_int64), ("csr", _P), ("values", _P), ("dinv", _P),
+                ("omega", _P), ("n_aggregates", C.c_int64), ("aggregate", _P), ("p_blocks", C.c_int64), ("p_ptr", _P), ("p_col", _P),
+                ("p_values", _P), ("ap_blocks", C.c_int64), ("ap_ptr", _P), ("ap_col", _P)]
 
 
 _SIGNATURES = {
@@ -186,6 +194,11 @@ _SIGNATURES = {
     "dxo_krylov_destroy": (C.c_int, [_P, _P]),
     "dxo_krylov_gmres": (C.c_int, [_P, _P, C.POINTER(KrylovOp), C.POINTER(KrylovPc), _P, _P, C.c_double, C.c_double, C.c_int, C.c_int,
                                    C.POINTER(KrylovInfo)]),
+    "dxo_amg_create": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "dxo_amg_destroy": (C.c_int, [_P, _P]),
+    "dxo_amg_setup": (C.c_int, [_P, _P, _P]),
+    "dxo_amg_apply": (C.c_int, [_P, _P, _P, _P]),
+    "dxo_amg_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(AmgLevelInfo)]),
     "dxo_krylov_cg": (C.c_int, [_P, _P, C.POINTER(KrylovOp), C.POINTER(KrylovPc), _P, _P, C.c_double, C.c_double, C.c_int, C.c_int,
                                 C.POINTER(KrylovInfo)]),
     "dxo_mesh_set_facet_geometry": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

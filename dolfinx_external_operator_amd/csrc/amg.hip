@@ -1,0 +1,1014 @@
+// amg.hip — smoothed-aggregation multigrid for matrices on a dxo_csr pattern (dxo_amg_*), the preconditioner DXO_PC_AMG of
+// dxo_krylov_gmres / dxo_krylov_cg.
+//
+// Symbolic phase (dxo_amg_create, host C++ once per pattern): the node graph of the block pattern, aggregates in three passes in
+// ascending node order, and per level the block patterns of P (node -> the aggregates of its neighbours), of A P, of the coarse matrix
+// P^T A P as a dxo_csr without a mesh, and the transposed incidence of P. Every level keeps the block size of the fine matrix.
+//
+// Numeric phase (dxo_amg_setup, every time the values change): per level the block-Jacobi inverses (the kernel of
+// dxo_csr_block_jacobi), rho = |Dinv A|_inf by one pass over the matrix and a max-reduction, omega = (4/3) / rho kept on the device,
+// P = T - omega Dinv A T (one thread per block of P), A P (one thread per block: the neighbours j of its node in ascending order, the
+// block of P in row j found by search), P^T (A P) (one thread per coarse block: the blocks of P in its column in ascending fine-node
+// order, the block of A P in that row found by search). The source blocks of a sum are not stored as lists: they are found in the
+// same fixed ascending order from the patterns, which keeps the tables at the size of the patterns themselves. The coarsest matrix is
+// expanded to dense [A | I] and inverted by Gauss-Jordan with partial pivoting, one launch per pivot, out of place between two
+// buffers (every workgroup finds the pivot of the step itself, so a step needs no grid-wide wait). No atomics: a setup is
+// bit-reproducible. The host waits once, at the end, for one flag word.
+//
+// Apply (dxo_amg_cycle): per level x = omega Dinv r, then x <- x + omega Dinv (r - A x) in the lane-group shape of csr_spmv (LW lanes
+// own a node, fixed xor-butterfly) with the update in the epilogue, t = r - A x by the same kernel, r_c = P^T t gathered through the
+// transposed incidence in ascending fine-node order, x += P x_c, the same sweeps again; the coarsest level is one dense product.
+#include "krylov_internal.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+
+#ifndef DXO_AMG_BLOCK
+#define DXO_AMG_BLOCK 256
+#endif
+
+namespace {
+
+constexpr int64_t AMG_MAX_DENSE = 4096;
+
+struct amg_level {
+    const dxo_csr* A = nullptr;        // pattern (level 0: the caller's, coarser: own)
+    dxo_csr* own = nullptr;
+    int64_t n_nodes = 0, n_rows = 0, nnzb = 0;
+    int lw = 8;                        // lanes per node of the sweeps
+    const double* values = nullptr;    // level 0: the pointer of the last setup
+    double* dinv = nullptr;            // [n_nodes][bs][bs]
+    uint8_t* mask = nullptr;           // [n_rows] 1: the dof's row of T is zero
+    // transfer to the next level (absent on the coarsest)
+    int64_t n_agg = 0, p_blocks = 0, ap_blocks = 0, c_blocks = 0;
+    int32_t* agg = nullptr;            // [n_nodes]
+    int64_t* p_ptr = nullptr;          // [n_nodes + 1]
+    int32_t *p_col = nullptr, *p_row = nullptr;
+    double* p_val = nullptr;           // [p_blocks][bs][bs]
+    int64_t *pt_ptr = nullptr, *pt_blk = nullptr;     // column a of P: its blocks, ascending fine node
+    int64_t* ap_ptr = nullptr;
+    int32_t *ap_col = nullptr, *ap_row = nullptr;
+    double* ap_val = nullptr;
+    int64_t* c_bptr = nullptr;         // [n_agg + 1] first block of a coarse node
+    int32_t* c_row = nullptr;          // [c_blocks] coarse node of a block
+    // vectors [n_rows]
+    double *r = nullptr, *xa = nullptr, *xb = nullptr, *t = nullptr;
+    double* cur = nullptr;             // the iterate of the running cycle
+};
+
+}  // namespace
+
+struct dxo_amg {
+    int device = 0, bs = 0, sweeps = 1;
+    std::vector<amg_level> L;
+    std::vector<void*> allocs;         // everything hipMalloc'ed here
+    double* omega = nullptr;           // [levels]
+    double* part = nullptr;            // partial maxima of the rho pass
+    int64_t part_cap = 0;
+    int* flag = nullptr;               // [0] singular diagonal block, [1] zero pivot
+    double* dense[2] = {nullptr, nullptr};   // [nc][2 nc] each: [W | B], B ends as the inverse
+    int64_t nc = 0;                    // rows of the coarsest level
+    bool ready = false;
+    double build_ms = 0.0, complexity = 1.0;
+};
+
+namespace {
+
+// ---- device helpers
+template <int BS>
+struct NodeRow {
+    int64_t r0, len;
+    int nnb;
+    __device__ __forceinline__ NodeRow(const int64_t* __restrict__ row_ptr, int64_t node) {
+        r0 = row_ptr[node * BS];
+        len = row_ptr[node * BS + 1] - r0;
+        nnb = (int)(len / BS);
+    }
+};
+
+// position of v in the ascending run col[lo, hi), or -1
+__device__ __forceinline__ int64_t amg_find(const int32_t* __restrict__ col, int64_t lo, int64_t hi, int32_t v) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        const int32_t c = col[mid];
+        if (c < v) lo = mid + 1;
+        else if (c > v) hi = mid;
+        else return mid;
+    }
+    return -1;
+}
+
+// ---- numeric phase
+// part[block] = max over the block's nodes of the absolute row sums of Dinv A
+template <int BS, int LW>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_rho(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const double* __restrict__ values,
+                                                         const double* __restrict__ dinv, double* __restrict__ part) {
+    __shared__ double lds[DXO_AMG_BLOCK / 64];
+    constexpr int NPB = DXO_AMG_BLOCK / LW;
+    const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
+    const int lane = threadIdx.x % LW;
+    double acc[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+    if (node < n_nodes) {
+        const NodeRow<BS> R(row_ptr, node);
+        double D[BS][BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) D[i][j] = dinv[node * BS * BS + i * BS + j];
+        for (int k = lane; k < R.nnb; k += LW) {
+            double a[BS][BS];
+#pragma unroll
+            for (int i = 0; i < BS; ++i)
+#pragma unroll
+                for (int j = 0; j < BS; ++j) a[i][j] = values[R.r0 + i * R.len + (int64_t)k * BS + j];
+#pragma unroll
+            for (int i = 0; i < BS; ++i)
+#pragma unroll
+                for (int j = 0; j < BS; ++j) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int q = 0; q < BS; ++q) s = fma(D[i][q], a[q][j], s);
+                    acc[i] += fabs(s);
+                }
+        }
+    }
+#pragma unroll
+    for (int off = LW / 2; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    double m = 0.0;
+#pragma unroll
+    for (int i = 0; i < BS; ++i) m = fmax(m, acc[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < DXO_AMG_BLOCK / 64; ++k) m = fmax(m, lds[k]);
+        part[blockIdx.x] = m;
+    }
+}
+
+// one workgroup: omega = (4/3) / max(part)
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_omega(const double* __restrict__ part, int64_t n, double* __restrict__ omega) {
+    __shared__ double lds[DXO_AMG_BLOCK / 64];
+    double m = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += DXO_AMG_BLOCK) m = fmax(m, part[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < DXO_AMG_BLOCK / 64; ++k) m = fmax(m, lds[k]);
+        omega[0] = m > 0.0 ? (4.0 / 3.0) / m : 0.0;
+    }
+}
+
+// coarse levels: a dof whose row has no nonzero off-diagonal entry takes no part in the tentative prolongator
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_row_mask(int64_t n_rows, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                              const double* __restrict__ values, uint8_t* __restrict__ mask) {
+    const int64_t row = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (row >= n_rows) return;
+    bool any = false;
+    for (int64_t e = row_ptr[row]; e < row_ptr[row + 1]; ++e) any = any || (col[e] != row && values[e] != 0.0);
+    mask[row] = any ? 0 : 1;
+}
+
+// P = T - omega Dinv (A T), one thread per block (i, a): the neighbours j of i with aggregate a, ascending
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_p(int64_t p_blocks, const int32_t* __restrict__ p_row, const int32_t* __restrict__ p_col,
+                                                             const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                             const double* __restrict__ values, const double* __restrict__ dinv,
+                                                             const int32_t* __restrict__ agg, const uint8_t* __restrict__ mask,
+                                                             const double* __restrict__ omega, double* __restrict__ p_val) {
+    const int64_t e = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (e >= p_blocks) return;
+    const int64_t i = p_row[e];
+    const int32_t a = p_col[e];
+    const NodeRow<BS> R(row_ptr, i);
+    double acc[BS][BS];
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) acc[r][c] = 0.0;
+    for (int k = 0; k < R.nnb; ++k) {
+        const int64_t j = col[R.r0 + (int64_t)k * BS] / BS;
+        if (agg[j] != a) continue;
+#pragma unroll
+        for (int c = 0; c < BS; ++c) {
+            if (mask[j * BS + c]) continue;
+#pragma unroll
+            for (int r = 0; r < BS; ++r) acc[r][c] += values[R.r0 + r * R.len + (int64_t)k * BS + c];
+        }
+    }
+    const double om = omega[0];
+    const bool own = agg[i] == a;
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) {
+            double s = 0.0;
+#pragma unroll
+            for (int q = 0; q < BS; ++q) s = fma(dinv[i * BS * BS + r * BS + q], acc[q][c], s);
+            const double t = (own && r == c && !mask[i * BS + r]) ? 1.0 : 0.0;
+            p_val[e * BS * BS + r * BS + c] = t - om * s;
+        }
+}
+
+// (A P)(i, a) = sum over the neighbours j of i, ascending, of A_ij P_ja
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_ap(int64_t ap_blocks, const int32_t* __restrict__ ap_row, const int32_t* __restrict__ ap_col,
+                                                              const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                              const double* __restrict__ values, const int64_t* __restrict__ p_ptr,
+                                                              const int32_t* __restrict__ p_col, const double* __restrict__ p_val,
+                                                              double* __restrict__ ap_val) {
+    const int64_t e = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (e >= ap_blocks) return;
+    const int64_t i = ap_row[e];
+    const int32_t a = ap_col[e];
+    const NodeRow<BS> R(row_ptr, i);
+    double acc[BS][BS];
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) acc[r][c] = 0.0;
+    for (int k = 0; k < R.nnb; ++k) {
+        const int64_t j = col[R.r0 + (int64_t)k * BS] / BS;
+        const int64_t f = amg_find(p_col, p_ptr[j], p_ptr[j + 1], a);
+        if (f < 0) continue;
+        double pb[BS][BS];
+#pragma unroll
+        for (int q = 0; q < BS; ++q)
+#pragma unroll
+            for (int c = 0; c < BS; ++c) pb[q][c] = p_val[f * BS * BS + q * BS + c];
+#pragma unroll
+        for (int r = 0; r < BS; ++r)
+#pragma unroll
+            for (int q = 0; q < BS; ++q) {
+                const double v = values[R.r0 + r * R.len + (int64_t)k * BS + q];
+#pragma unroll
+                for (int c = 0; c < BS; ++c) acc[r][c] = fma(v, pb[q][c], acc[r][c]);
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) ap_val[e * BS * BS + r * BS + c] = acc[r][c];
+}
+
+// A_c(a, b) = sum over the blocks (i, a) of P, ascending i, of P_ia^T (A P)_ib; an exactly zero diagonal entry becomes 1
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_c(int64_t c_blocks, const int32_t* __restrict__ c_row, const int64_t* __restrict__ c_bptr,
+                                                             const int64_t* __restrict__ c_row_ptr, const int32_t* __restrict__ c_col,
+                                                             const int64_t* __restrict__ pt_ptr, const int64_t* __restrict__ pt_blk,
+                                                             const int32_t* __restrict__ p_row, const double* __restrict__ p_val,
+                                                             const int64_t* __restrict__ ap_ptr, const int32_t* __restrict__ ap_col,
+                                                             const double* __restrict__ ap_val, double* __restrict__ c_val) {
+    const int64_t g = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (g >= c_blocks) return;
+    const int64_t a = c_row[g];
+    const int64_t k = g - c_bptr[a];
+    const NodeRow<BS> R(c_row_ptr, a);
+    const int32_t b = c_col[R.r0 + k * BS] / BS;
+    double acc[BS][BS];
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) acc[r][c] = 0.0;
+    for (int64_t e = pt_ptr[a]; e < pt_ptr[a + 1]; ++e) {
+        const int64_t pb = pt_blk[e];
+        const int64_t i = p_row[pb];
+        const int64_t f = amg_find(ap_col, ap_ptr[i], ap_ptr[i + 1], b);
+        if (f < 0) continue;
+#pragma unroll
+        for (int q = 0; q < BS; ++q) {
+            double w[BS];
+#pragma unroll
+            for (int c = 0; c < BS; ++c) w[c] = ap_val[f * BS * BS + q * BS + c];
+#pragma unroll
+            for (int r = 0; r < BS; ++r) {
+                const double p = p_val[pb * BS * BS + q * BS + r];
+#pragma unroll
+                for (int c = 0; c < BS; ++c) acc[r][c] = fma(p, w[c], acc[r][c]);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) {
+            double v = acc[r][c];
+            if (a == b && r == c && v == 0.0) v = 1.0;
+            c_val[R.r0 + r * R.len + k * BS + c] = v;
+        }
+}
+
+// ---- the dense coarsest level. W is [n][2 n] = [A | I]
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_dense_fill(int64_t n, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                                const double* __restrict__ values, double* __restrict__ W) {
+    const int64_t row = blockIdx.x;
+    double* w = W + row * 2 * n;
+    for (int64_t c = threadIdx.x; c < 2 * n; c += DXO_AMG_BLOCK) w[c] = c == n + row ? 1.0 : 0.0;
+    __syncthreads();
+    for (int64_t e = row_ptr[row] + threadIdx.x; e < row_ptr[row + 1]; e += DXO_AMG_BLOCK) w[col[e]] = values[e];
+}
+
+// step k of Gauss-Jordan with partial pivoting, out of place: workgroup i forms row i of `out`. Every workgroup finds the pivot row
+// (largest |in[i][k]|, i >= k, the lowest i among equals) itself.
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_dense_step(int64_t n, int64_t k, const double* __restrict__ in, double* __restrict__ out,
+                                                                int* __restrict__ flag) {
+    __shared__ double lv[DXO_AMG_BLOCK];
+    __shared__ int64_t li[DXO_AMG_BLOCK];
+    const int64_t ld = 2 * n;
+    double best = -1.0;
+    int64_t bi = k;
+    for (int64_t i = k + threadIdx.x; i < n; i += DXO_AMG_BLOCK) {
+        const double v = fabs(in[i * ld + k]);
+        if (v > best) {
+            best = v;
+            bi = i;
+        }
+    }
+    lv[threadIdx.x] = best;
+    li[threadIdx.x] = bi;
+    __syncthreads();
+    for (int off = DXO_AMG_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            const double v = lv[threadIdx.x + off];
+            const int64_t j = li[threadIdx.x + off];
+            if (v > lv[threadIdx.x] || (v == lv[threadIdx.x] && j < li[threadIdx.x])) {
+                lv[threadIdx.x] = v;
+                li[threadIdx.x] = j;
+            }
+        }
+        __syncthreads();
+    }
+    const int64_t p = li[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0 && !(lv[0] > 0.0)) flag[1] = 1;
+    const double piv = in[p * ld + k];
+    const int64_t row = blockIdx.x;
+    const double* pr = in + p * ld;
+    double* o = out + row * ld;
+    if (row == k) {
+        for (int64_t c = threadIdx.x; c < ld; c += DXO_AMG_BLOCK) o[c] = pr[c] / piv;
+    } else {
+        const double* sr = in + (row == p ? k : row) * ld;
+        const double f = sr[k];
+        for (int64_t c = threadIdx.x; c < ld; c += DXO_AMG_BLOCK) o[c] = fma(-f, pr[c] / piv, sr[c]);
+    }
+}
+
+// x = B r with B the right half of W: one wave per row
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_dense_apply(int64_t n, const double* __restrict__ W, const double* __restrict__ r,
+                                                                 double* __restrict__ x) {
+    const int64_t row = (int64_t)blockIdx.x * (DXO_AMG_BLOCK / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    double s = 0.0;
+    if (row < n) {
+        const double* b = W + row * 2 * n + n;
+        for (int64_t c = lane; c < n; c += 64) s = fma(b[c], r[c], s);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (row < n && lane == 0) x[row] = s;
+}
+
+// ---- the cycle
+// x = omega Dinv r: the first sweep, from x = 0
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_jacobi0(int64_t n_nodes, const double* __restrict__ dinv, const double* __restrict__ omega,
+                                                             const double* __restrict__ r, double* __restrict__ x) {
+    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (node >= n_nodes) return;
+    const double om = omega[0];
+    double rb[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j) rb[j] = r[node * BS + j];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], rb[j], s);
+        x[node * BS + i] = om * s;
+    }
+}
+
+// RESID: out = r - A x; otherwise out = x + omega Dinv (r - A x). LW lanes own a node (the shape of csr_spmv). out may be r: a node's
+// entries of r are read by its own lane 0 only, before it writes.
+template <int BS, int LW, bool RESID>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_sweep(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                           const double* __restrict__ values, const double* __restrict__ dinv,
+                                                           const double* __restrict__ omega, const double* r, const double* __restrict__ x,
+                                                           double* out) {
+    constexpr int NPB = DXO_AMG_BLOCK / LW;
+    const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
+    const int lane = threadIdx.x % LW;
+    double acc[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+    if (node < n_nodes) {
+        const NodeRow<BS> R(row_ptr, node);
+        for (int k = lane; k < R.nnb; k += LW) {
+            const int64_t c = col[R.r0 + (int64_t)k * BS];
+            double xb[BS];
+#pragma unroll
+            for (int j = 0; j < BS; ++j) xb[j] = x[c + j];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) {
+                const double* v = values + R.r0 + i * R.len + (int64_t)k * BS;
+#pragma unroll
+                for (int j = 0; j < BS; ++j) acc[i] = fma(v[j], xb[j], acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = LW / 2; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    if (node < n_nodes && lane == 0) {
+        double d[BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) d[i] = r[node * BS + i] - acc[i];
+        if constexpr (RESID) {
+#pragma unroll
+            for (int i = 0; i < BS; ++i) out[node * BS + i] = d[i];
+        } else {
+            const double om = omega[0];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) {
+                double s = 0.0;
+#pragma unroll
+                for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], d[j], s);
+                out[node * BS + i] = fma(om, s, x[node * BS + i]);
+            }
+        }
+    }
+}
+
+// r_c[a] = sum over the blocks (i, a) of P, ascending i, of P_ia^T t_i
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_restrict(int64_t n_agg, const int64_t* __restrict__ pt_ptr, const int64_t* __restrict__ pt_blk,
+                                                              const int32_t* __restrict__ p_row, const double* __restrict__ p_val,
+                                                              const double* __restrict__ t, double* __restrict__ rc) {
+    const int64_t a = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (a >= n_agg) return;
+    double acc[BS];
+#pragma unroll
+    for (int c = 0; c < BS; ++c) acc[c] = 0.0;
+    for (int64_t e = pt_ptr[a]; e < pt_ptr[a + 1]; ++e) {
+        const int64_t pb = pt_blk[e];
+        const int64_t i = p_row[pb];
+#pragma unroll
+        for (int q = 0; q < BS; ++q) {
+            const double tv = t[i * BS + q];
+#pragma unroll
+            for (int c = 0; c < BS; ++c) acc[c] = fma(p_val[pb * BS * BS + q * BS + c], tv, acc[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < BS; ++c) rc[a * BS + c] = acc[c];
+}
+
+// x_i += sum over the blocks of row i of P, ascending aggregate, of P_ia xc_a
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_prolong(int64_t n_nodes, const int64_t* __restrict__ p_ptr, const int32_t* __restrict__ p_col,
+                                                             const double* __restrict__ p_val, const double* __restrict__ xc, double* __restrict__ x) {
+    const int64_t i = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (i >= n_nodes) return;
+    double acc[BS];
+#pragma unroll
+    for (int r = 0; r < BS; ++r) acc[r] = 0.0;
+    for (int64_t e = p_ptr[i]; e < p_ptr[i + 1]; ++e) {
+        const int64_t a = p_col[e];
+#pragma unroll
+        for (int c = 0; c < BS; ++c) {
+            const double v = xc[a * BS + c];
+#pragma unroll
+            for (int r = 0; r < BS; ++r) acc[r] = fma(p_val[e * BS * BS + r * BS + c], v, acc[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < BS; ++r) x[i * BS + r] += acc[r];
+}
+
+// ---- host: launch helpers
+inline dim3 amg_grid(int64_t items, int per_block = DXO_AMG_BLOCK) { return dim3((unsigned)std::max<int64_t>(1, (items + per_block - 1) / per_block)); }
+
+#define AMG_BS(bs, kernel, ...)                                               \
+    do {                                                                      \
+        if ((bs) == 1) hipLaunchKernelGGL(kernel<1>, __VA_ARGS__);            \
+        else if ((bs) == 2) hipLaunchKernelGGL(kernel<2>, __VA_ARGS__);       \
+        else hipLaunchKernelGGL(kernel<3>, __VA_ARGS__);                      \
+    } while (0)
+
+template <int BS, bool RESID>
+void sweep_bs(const amg_level& v, const double* omega, const double* r, const double* x, double* out, hipStream_t s) {
+    const dim3 b(DXO_AMG_BLOCK);
+    if (v.lw == 8)
+        hipLaunchKernelGGL((amg_sweep<BS, 8, RESID>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv,
+                           omega, r, x, out);
+    else
+        hipLaunchKernelGGL((amg_sweep<BS, 32, RESID>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values,
+                           v.dinv, omega, r, x, out);
+}
+
+template <bool RESID>
+void sweep_launch(int bs, const amg_level& v, const double* omega, const double* r, const double* x, double* out, hipStream_t s) {
+    if (bs == 1) sweep_bs<1, RESID>(v, omega, r, x, out, s);
+    else if (bs == 2) sweep_bs<2, RESID>(v, omega, r, x, out, s);
+    else sweep_bs<3, RESID>(v, omega, r, x, out, s);
+}
+
+template <int BS>
+void rho_bs(const amg_level& v, double* part, hipStream_t s) {
+    const dim3 b(DXO_AMG_BLOCK);
+    if (v.lw == 8) hipLaunchKernelGGL((amg_rho<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.values, v.dinv, part);
+    else hipLaunchKernelGGL((amg_rho<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.values, v.dinv, part);
+}
+
+int64_t rho_parts(const amg_level& v) { return std::max<int64_t>(1, (v.n_nodes + DXO_AMG_BLOCK / v.lw - 1) / (DXO_AMG_BLOCK / v.lw)); }
+
+// ---- host: the symbolic phase
+struct HostGraph {                      // node graph of a block pattern: sorted neighbours, the node itself included
+    int64_t n = 0;
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> nb;
+};
+
+HostGraph graph_of(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& col, int64_t n_nodes, int bs) {
+    HostGraph g;
+    g.n = n_nodes;
+    g.ptr.assign((size_t)n_nodes + 1, 0);
+    for (int64_t i = 0; i < n_nodes; ++i) g.ptr[(size_t)i + 1] = g.ptr[(size_t)i] + (row_ptr[(size_t)(i * bs) + 1] - row_ptr[(size_t)(i * bs)]) / bs;
+    g.nb.resize((size_t)g.ptr.back());
+    for (int64_t i = 0; i < n_nodes; ++i) {
+        const int64_t r0 = row_ptr[(size_t)(i * bs)];
+        const int64_t nnb = g.ptr[(size_t)i + 1] - g.ptr[(size_t)i];
+        for (int64_t k = 0; k < nnb; ++k) g.nb[(size_t)(g.ptr[(size_t)i] + k)] = col[(size_t)(r0 + k * bs)] / bs;
+    }
+    return g;
+}
+
+// three passes in ascending node order; inactive nodes keep -1. Returns the number of aggregates
+int64_t aggregate(const HostGraph& g, const std::vector<uint8_t>& active, std::vector<int32_t>& agg) {
+    const int64_t n = g.n;
+    agg.assign((size_t)n, -1);
+    int32_t na = 0;
+    for (int64_t i = 0; i < n; ++i) {                    // 1: a free neighbourhood founds an aggregate
+        if (!active[(size_t)i]) continue;
+        bool free_nb = true;
+        for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1] && free_nb; ++e) {
+            const int32_t j = g.nb[(size_t)e];
+            if (active[(size_t)j] && agg[(size_t)j] >= 0) free_nb = false;
+        }
+        if (!free_nb) continue;
+        for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1]; ++e) {
+            const int32_t j = g.nb[(size_t)e];
+            if (active[(size_t)j]) agg[(size_t)j] = na;
+        }
+        agg[(size_t)i] = na++;
+    }
+    const std::vector<int32_t> first(agg);
+    for (int64_t i = 0; i < n; ++i) {                    // 2: join the lowest pass-1 aggregate of a neighbour
+        if (!active[(size_t)i] || first[(size_t)i] >= 0) continue;
+        int32_t best = -1;
+        for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1]; ++e) {
+            const int32_t a = first[(size_t)g.nb[(size_t)e]];
+            if (a >= 0 && (best < 0 || a < best)) best = a;
+        }
+        agg[(size_t)i] = best;
+    }
+    for (int64_t i = 0; i < n; ++i) {                    // 3: the rest found aggregates with their free neighbours
+        if (!active[(size_t)i] || agg[(size_t)i] >= 0) continue;
+        for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1]; ++e) {
+            const int32_t j = g.nb[(size_t)e];
+            if (active[(size_t)j] && agg[(size_t)j] < 0) agg[(size_t)j] = na;
+        }
+        agg[(size_t)i] = na++;
+    }
+    return na;
+}
+
+struct HostTransfer {
+    std::vector<int64_t> p_ptr, pt_ptr, pt_blk, ap_ptr, c_bptr;
+    std::vector<int32_t> p_col, p_row, ap_col, ap_row, c_row;
+    HostGraph coarse;
+};
+
+void sort_unique(std::vector<int32_t>& v) {
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+}
+
+HostTransfer transfer_of(const HostGraph& g, const std::vector<int32_t>& agg, int64_t na) {
+    HostTransfer t;
+    const int64_t n = g.n;
+    std::vector<int32_t> tmp;
+    t.p_ptr.assign((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {                    // P: the aggregates of the neighbours
+        tmp.clear();
+        for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1]; ++e)
+            if (agg[(size_t)g.nb[(size_t)e]] >= 0) tmp.push_back(agg[(size_t)g.nb[(size_t)e]]);
+        sort_unique(tmp);
+        t.p_col.insert(t.p_col.end(), tmp.begin(), tmp.end());
+        t.p_row.insert(t.p_row.end(), tmp.size(), (int32_t)i);
+        t.p_ptr[(size_t)i + 1] = (int64_t)t.p_col.size();
+    }
+    t.pt_ptr.assign((size_t)na + 1, 0);                  // its transposed incidence, ascending block = ascending fine node
+    for (int32_t a : t.p_col) ++t.pt_ptr[(size_t)a + 1];
+    for (int64_t a = 0; a < na; ++a) t.pt_ptr[(size_t)a + 1] += t.pt_ptr[(size_t)a];
+    t.pt_blk.resize(t.p_col.size());
+    {
+        std::vector<int64_t> fill(t.pt_ptr.begin(), t.pt_ptr.end() - 1);
+        for (size_t e = 0; e < t.p_col.size(); ++e) t.pt_blk[(size_t)fill[(size_t)t.p_col[e]]++] = (int64_t)e;
+    }
+    t.ap_ptr.assign((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {                    // A P: the union of the rows of P of the neighbours
+        tmp.clear();
+        for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1]; ++e) {
+            const int64_t j = g.nb[(size_t)e];
+            tmp.insert(tmp.end(), t.p_col.begin() + t.p_ptr[(size_t)j], t.p_col.begin() + t.p_ptr[(size_t)j + 1]);
+        }
+        sort_unique(tmp);
+        t.ap_col.insert(t.ap_col.end(), tmp.begin(), tmp.end());
+        t.ap_row.insert(t.ap_row.end(), tmp.size(), (int32_t)i);
+        t.ap_ptr[(size_t)i + 1] = (int64_t)t.ap_col.size();
+    }
+    t.coarse.n = na;                                     // P^T (A P): the union of the rows of A P over a column of P, and the diagonal
+    t.coarse.ptr.assign((size_t)na + 1, 0);
+    for (int64_t a = 0; a < na; ++a) {
+        tmp.clear();
+        tmp.push_back((int32_t)a);
+        for (int64_t e = t.pt_ptr[(size_t)a]; e < t.pt_ptr[(size_t)a + 1]; ++e) {
+            const int64_t i = t.p_row[(size_t)t.pt_blk[(size_t)e]];
+            tmp.insert(tmp.end(), t.ap_col.begin() + t.ap_ptr[(size_t)i], t.ap_col.begin() + t.ap_ptr[(size_t)i + 1]);
+        }
+        sort_unique(tmp);
+        t.coarse.nb.insert(t.coarse.nb.end(), tmp.begin(), tmp.end());
+        t.c_row.insert(t.c_row.end(), tmp.size(), (int32_t)a);
+        t.coarse.ptr[(size_t)a + 1] = (int64_t)t.coarse.nb.size();
+    }
+    t.c_bptr = t.coarse.ptr;
+    return t;
+}
+
+// the csr.h layout of a node graph
+void rows_of(const HostGraph& g, int bs, std::vector<int64_t>& row_ptr, std::vector<int32_t>& col) {
+    row_ptr.assign((size_t)(g.n * bs) + 1, 0);
+    for (int64_t i = 0; i < g.n; ++i)
+        for (int r = 0; r < bs; ++r) row_ptr[(size_t)(i * bs + r) + 1] = row_ptr[(size_t)(i * bs + r)] + bs * (g.ptr[(size_t)i + 1] - g.ptr[(size_t)i]);
+    col.resize((size_t)row_ptr.back());
+    for (int64_t i = 0; i < g.n; ++i)
+        for (int r = 0; r < bs; ++r) {
+            int64_t w = row_ptr[(size_t)(i * bs + r)];
+            for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1]; ++e)
+                for (int c = 0; c < bs; ++c) col[(size_t)w++] = g.nb[(size_t)e] * bs + c;
+        }
+}
+
+struct Uploader {
+    dxo_ctx* ctx;
+    dxo_amg* amg;
+    int rc = DXO_OK;
+    template <class T>
+    T* alloc(size_t n) {
+        if (rc != DXO_OK) return nullptr;
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T) + 16);
+        if (e != hipSuccess) {
+            rc = dxo_hip_fail(ctx, e, "dxo_amg_create: hipMalloc");
+            return nullptr;
+        }
+        amg->allocs.push_back(p);
+        return (T*)p;
+    }
+    template <class T>
+    T* up(const std::vector<T>& v) {
+        T* p = alloc<T>(v.size());
+        if (p && !v.empty()) {
+            const hipError_t e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+            if (e != hipSuccess) rc = dxo_hip_fail(ctx, e, "dxo_amg_create: hipMemcpy");
+        }
+        return p;
+    }
+};
+
+void amg_free(dxo_amg* a) {
+    for (void* p : a->allocs) (void)hipFree(p);
+    for (amg_level& v : a->L) delete v.own;
+    delete a;
+}
+
+int lanes_for(int64_t nnzb, int64_t n_nodes) { return n_nodes > 0 && (double)nnzb / (double)n_nodes > 16.0 ? 32 : 8; }
+
+int amg_build(dxo_ctx* ctx, dxo_amg* amg, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, int max_levels, int coarse_rows) {
+    const int bs = csr->bs;
+    Uploader U{ctx, amg};
+    std::vector<int64_t> row_ptr((size_t)csr->n_rows + 1);
+    std::vector<int32_t> col((size_t)csr->nnz);
+    DXO_HIP(ctx, hipMemcpy(row_ptr.data(), csr->d_row_ptr, row_ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (csr->nnz > 0) DXO_HIP(ctx, hipMemcpy(col.data(), csr->d_col, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<uint8_t> mask((size_t)csr->n_rows, 0);
+    if (n_constrained > 0) {
+        std::vector<int32_t> dofs((size_t)n_constrained);
+        DXO_HIP(ctx, hipMemcpy(dofs.data(), constrained, dofs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t d : dofs)
+            if (d >= 0 && d < csr->n_rows) mask[(size_t)d] = 1;
+    }
+    HostGraph g = graph_of(row_ptr, col, csr->n_nodes, bs);
+    std::vector<uint8_t> active((size_t)g.n, 1);
+    for (int64_t i = 0; i < g.n; ++i) {
+        bool all = true;
+        for (int r = 0; r < bs; ++r) all = all && mask[(size_t)(i * bs + r)];
+        active[(size_t)i] = all ? 0 : 1;
+    }
+    amg_level lev;
+    lev.A = csr;
+    lev.n_nodes = csr->n_nodes;
+    lev.n_rows = csr->n_rows;
+    lev.nnzb = (int64_t)g.nb.size();
+    lev.mask = U.up(mask);
+    const int64_t nnzb0 = std::max<int64_t>(1, lev.nnzb);
+    int64_t total = 0;
+    for (;;) {
+        lev.lw = lanes_for(lev.nnzb, lev.n_nodes);
+        total += lev.nnzb;
+        bool last = lev.n_rows <= coarse_rows || (int)amg->L.size() + 1 >= max_levels;
+        std::vector<int32_t> agg;
+        int64_t na = 0;
+        if (!last) {
+            na = aggregate(g, active, agg);
+            last = na == 0 || (double)(na * bs) > 0.8 * (double)lev.n_rows;
+        }
+        lev.r = U.alloc<double>((size_t)lev.n_rows);
+        lev.xa = U.alloc<double>((size_t)lev.n_rows);
+        if (last) {
+            amg->L.push_back(lev);
+            break;
+        }
+        lev.xb = U.alloc<double>((size_t)lev.n_rows);
+        lev.t = U.alloc<double>((size_t)lev.n_rows);
+        lev.dinv = U.alloc<double>((size_t)(lev.n_nodes * bs * bs));
+        HostTransfer t = transfer_of(g, agg, na);
+        lev.n_agg = na;
+        lev.p_blocks = (int64_t)t.p_col.size();
+        lev.ap_blocks = (int64_t)t.ap_col.size();
+        lev.c_blocks = (int64_t)t.c_row.size();
+        lev.agg = U.up(agg);
+        lev.p_ptr = U.up(t.p_ptr);
+        lev.p_col = U.up(t.p_col);
+        lev.p_row = U.up(t.p_row);
+        lev.pt_ptr = U.up(t.pt_ptr);
+        lev.pt_blk = U.up(t.pt_blk);
+        lev.ap_ptr = U.up(t.ap_ptr);
+        lev.ap_col = U.up(t.ap_col);
+        lev.ap_row = U.up(t.ap_row);
+        lev.c_bptr = U.up(t.c_bptr);
+        lev.c_row = U.up(t.c_row);
+        lev.p_val = U.alloc<double>((size_t)(lev.p_blocks * bs * bs));
+        lev.ap_val = U.alloc<double>((size_t)(lev.ap_blocks * bs * bs));
+        amg->L.push_back(lev);
+        // the coarse level: a dxo_csr without a mesh
+        std::vector<int64_t> crp;
+        std::vector<int32_t> ccol;
+        rows_of(t.coarse, bs, crp, ccol);
+        amg_level c;
+        c.own = new dxo_csr;
+        c.own->bs = bs;
+        c.own->n_nodes = na;
+        c.own->n_rows = na * bs;
+        c.own->nnz = crp.back();
+        c.own->d_row_ptr = U.up(crp);
+        c.own->d_col = U.up(ccol);
+        c.A = c.own;
+        c.n_nodes = na;
+        c.n_rows = na * bs;
+        c.nnzb = (int64_t)t.coarse.nb.size();
+        double* cv = U.alloc<double>((size_t)c.own->nnz);
+        c.values = cv;
+        c.mask = U.alloc<uint8_t>((size_t)c.n_rows);
+        if (U.rc != DXO_OK) {
+            amg->L.push_back(c);       // owned: freed with the object
+            return U.rc;
+        }
+        lev = c;
+        g = std::move(t.coarse);
+        active.assign((size_t)g.n, 1);
+    }
+    if (U.rc != DXO_OK) return U.rc;
+    amg->complexity = (double)total / (double)nnzb0;
+    amg->nc = amg->L.back().n_rows;
+    if (amg->nc > AMG_MAX_DENSE) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "dxo_amg_create: the coarsest level keeps %lld rows, the dense solve takes at most %lld (raise max_levels)",
+                 (long long)amg->nc, (long long)AMG_MAX_DENSE);
+        return dxo_fail(ctx, DXO_E_SIZE, msg);
+    }
+    for (const amg_level& v : amg->L) amg->part_cap = std::max(amg->part_cap, rho_parts(v));
+    amg->omega = U.alloc<double>(amg->L.size());
+    amg->part = U.alloc<double>((size_t)amg->part_cap);
+    amg->flag = U.alloc<int>(4);
+    amg->dense[0] = U.alloc<double>((size_t)(2 * amg->nc * amg->nc));
+    amg->dense[1] = U.alloc<double>((size_t)(2 * amg->nc * amg->nc));
+    return U.rc;
+}
+
+bool amg_misaligned(const void* p) { return ((uintptr_t)p & 7u) != 0; }
+
+}  // namespace
+
+// ---- shared with krylov.hip
+int dxo_amg_pc_check(dxo_ctx* ctx, const char* who, const dxo_amg* amg, const dxo_csr* op_csr, int bs, int64_t n) {
+    char msg[256];
+    if (!amg) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the preconditioner carries no dxo_amg").c_str());
+    if (bs != amg->bs || (op_csr && op_csr->bs != amg->bs)) {
+        snprintf(msg, sizeof msg, "%s: multigrid of bs %d on a pattern of bs %d", who, amg->bs, op_csr ? op_csr->bs : bs);
+        return dxo_fail(ctx, DXO_E_DIM, msg);
+    }
+    if (n != amg->L[0].n_rows) {
+        snprintf(msg, sizeof msg, "%s: the multigrid covers %lld rows, the operator has %lld", who, (long long)amg->L[0].n_rows, (long long)n);
+        return dxo_fail(ctx, DXO_E_SIZE, msg);
+    }
+    if (!amg->ready) return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": dxo_amg_setup has not run (or failed)").c_str());
+    return DXO_OK;
+}
+
+void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipStream_t s) {
+    (void)ctx;
+    const int bs = amg->bs, nl = (int)amg->L.size(), nu = amg->sweeps;
+    const dim3 B(DXO_AMG_BLOCK);
+    if (amg->L[0].n_rows == 0) return;
+    for (int l = 0; l + 1 < nl; ++l) {
+        amg_level& v = amg->L[(size_t)l];
+        const double* rin = l == 0 ? r : v.r;
+        const double* om = amg->omega + l;
+        double *cur = v.xa, *other = v.xb;
+        AMG_BS(bs, amg_jacobi0, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.dinv, om, rin, cur);
+        for (int k = 1; k < nu; ++k) {
+            sweep_launch<false>(bs, v, om, rin, cur, other, s);
+            std::swap(cur, other);
+        }
+        sweep_launch<true>(bs, v, om, rin, cur, v.t, s);
+        AMG_BS(bs, amg_restrict, amg_grid(v.n_agg), B, 0, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, v.p_val, v.t, amg->L[(size_t)l + 1].r);
+        v.cur = cur;
+    }
+    amg_level& c = amg->L.back();
+    const double* W = amg->dense[amg->nc % 2];
+    hipLaunchKernelGGL(amg_dense_apply, amg_grid(amg->nc, DXO_AMG_BLOCK / 64), B, 0, s, amg->nc, W, nl == 1 ? r : c.r, c.xa);
+    c.cur = c.xa;
+    if (nl == 1) {
+        (void)hipMemcpyAsync(z, c.xa, (size_t)c.n_rows * sizeof(double), hipMemcpyDeviceToDevice, s);
+        return;
+    }
+    for (int l = nl - 2; l >= 0; --l) {
+        amg_level& v = amg->L[(size_t)l];
+        const double* rin = l == 0 ? r : v.r;
+        const double* om = amg->omega + l;
+        double* cur = v.cur;
+        double* other = cur == v.xa ? v.xb : v.xa;
+        AMG_BS(bs, amg_prolong, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, amg->L[(size_t)l + 1].cur, cur);
+        for (int k = 0; k < nu; ++k) {
+            double* out = (l == 0 && k == nu - 1) ? z : other;      // the last sweep of the fine level writes the result
+            sweep_launch<false>(bs, v, om, rin, cur, out, s);
+            other = cur;
+            cur = out;
+        }
+        v.cur = cur;
+    }
+}
+
+// ---- C ABI
+extern "C" int dxo_amg_create(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, int max_levels, int coarse_rows,
+                              int sweeps, dxo_amg** out) {
+    if (!ctx || !out) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    *out = nullptr;
+    if (!csr || (n_constrained > 0 && !constrained)) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_create: NULL argument");
+    if (csr->bs < 1 || csr->bs > 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create: bs must be 1, 2 or 3");
+    if (n_constrained < 0 || max_levels < 1 || coarse_rows < 1 || sweeps < 1)
+        return dxo_fail(ctx, DXO_E_SIZE, "dxo_amg_create: n_constrained < 0, or max_levels, coarse_rows or sweeps < 1");
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    DXO_HIP(ctx, hipStreamSynchronize(dxo_launch_stream(ctx)));      // the list may have been written on the stream
+    const auto t0 = std::chrono::steady_clock::now();
+    dxo_amg* a = new dxo_amg;
+    a->device = ctx->device;
+    a->bs = csr->bs;
+    a->sweeps = sweeps;
+    const int rc = amg_build(ctx, a, csr, constrained, n_constrained, max_levels, coarse_rows);
+    if (rc != DXO_OK) {
+        amg_free(a);
+        return rc;
+    }
+    a->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = a;
+    return DXO_OK;
+}
+
+extern "C" int dxo_amg_destroy(dxo_ctx* ctx, dxo_amg* amg) {
+    if (!amg) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    (void)hipSetDevice(amg->device);
+    (void)hipDeviceSynchronize();
+    amg_free(amg);
+    return DXO_OK;
+}
+
+extern "C" int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!amg || !values) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_setup: NULL argument");
+    if (amg_misaligned(values)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_amg_setup: values must be 8-byte aligned");
+    hipStream_t s = dxo_launch_stream(ctx);
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    amg->ready = false;
+    const int bs = amg->bs, nl = (int)amg->L.size();
+    const dim3 B(DXO_AMG_BLOCK);
+    amg->L[0].values = values;
+    int rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    DXO_HIP(ctx, hipMemsetAsync(amg->flag, 0, 4 * sizeof(int), s));
+    for (int l = 0; l + 1 < nl; ++l) {
+        amg_level& v = amg->L[(size_t)l];
+        amg_level& c = amg->L[(size_t)l + 1];
+        if (v.n_nodes == 0) continue;
+        dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
+        if (bs == 1) rho_bs<1>(v, amg->part, s);
+        else if (bs == 2) rho_bs<2>(v, amg->part, s);
+        else rho_bs<3>(v, amg->part, s);
+        hipLaunchKernelGGL(amg_omega, dim3(1), B, 0, s, amg->part, rho_parts(v), amg->omega + l);
+        AMG_BS(bs, amg_build_p, amg_grid(v.p_blocks), B, 0, s, v.p_blocks, v.p_row, v.p_col, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, v.agg, v.mask,
+               amg->omega + l, v.p_val);
+        AMG_BS(bs, amg_build_ap, amg_grid(v.ap_blocks), B, 0, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr, v.p_col,
+               v.p_val, v.ap_val);
+        double* cv = const_cast<double*>(c.values);
+        AMG_BS(bs, amg_build_c, amg_grid(v.c_blocks), B, 0, s, v.c_blocks, v.c_row, v.c_bptr, c.A->d_row_ptr, c.A->d_col, v.pt_ptr, v.pt_blk, v.p_row,
+               v.p_val, v.ap_ptr, v.ap_col, v.ap_val, cv);
+        hipLaunchKernelGGL(amg_row_mask, amg_grid(c.n_rows), B, 0, s, c.n_rows, c.A->d_row_ptr, c.A->d_col, c.values, c.mask);
+    }
+    const amg_level& c = amg->L.back();
+    const int64_t n = amg->nc;
+    if (n > 0) {
+        hipLaunchKernelGGL(amg_dense_fill, dim3((unsigned)n), B, 0, s, n, c.A->d_row_ptr, c.A->d_col, c.values, amg->dense[0]);
+        for (int64_t k = 0; k < n; ++k)
+            hipLaunchKernelGGL(amg_dense_step, dim3((unsigned)n), B, 0, s, n, k, amg->dense[k % 2], amg->dense[(k + 1) % 2], amg->flag);
+    }
+    int h[2] = {0, 0};
+    DXO_HIP(ctx, hipMemcpyAsync(h, amg->flag, sizeof h, hipMemcpyDeviceToHost, s));
+    DXO_HIP(ctx, hipStreamSynchronize(s));
+    rc = dxo_device_end(ctx, s);
+    if (h[0]) return dxo_fail(ctx, DXO_E_SINGULAR, "dxo_amg_setup: a diagonal block of a level is singular");
+    if (h[1]) return dxo_fail(ctx, DXO_E_SINGULAR, "dxo_amg_setup: zero pivot in the coarsest matrix");
+    if (rc != DXO_OK) return rc;
+    amg->ready = true;
+    return DXO_OK;
+}
+
+extern "C" int dxo_amg_apply(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!amg || !r || !z) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_apply: NULL argument");
+    if (amg_misaligned(r) || amg_misaligned(z)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_amg_apply: arrays must be 8-byte aligned");
+    if (!amg->ready) return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_apply: dxo_amg_setup has not run (or failed)");
+    hipStream_t s = dxo_launch_stream(ctx);
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    dxo_amg_cycle(ctx, amg, r, z, s);
+    return dxo_device_end(ctx, s);
+}
+
+extern "C" int dxo_amg_info(dxo_ctx* ctx, const dxo_amg* amg, int* n_levels, double* build_ms, double* operator_complexity, int level,
+                            dxo_amg_level_info* out) {
+    if (!amg) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (n_levels) *n_levels = (int)amg->L.size();
+    if (build_ms) *build_ms = amg->build_ms;
+    if (operator_complexity) *operator_complexity = amg->complexity;
+    if (!out) return DXO_OK;
+    if (level < 0 || level >= (int)amg->L.size()) return dxo_fail(ctx, DXO_E_SIZE, "dxo_amg_info: no such level");
+    const amg_level& v = amg->L[(size_t)level];
+    const bool last = level + 1 == (int)amg->L.size();
+    *out = dxo_amg_level_info{};
+    out->n_rows = v.n_rows;
+    out->n_nodes = v.n_nodes;
+    out->nnz_blocks = v.nnzb;
+    out->csr = v.A;
+    out->values = v.values;
+    if (!last) {
+        out->dinv = v.dinv;
+        out->omega = amg->omega + level;
+        out->n_aggregates = v.n_agg;
+        out->aggregate = v.agg;
+        out->p_blocks = v.p_blocks;
+        out->p_ptr = v.p_ptr;
+        out->p_col = v.p_col;
+        out->p_values = v.p_val;
+        out->ap_blocks = v.ap_blocks;
+        out->ap_ptr = v.ap_ptr;
+        out->ap_col = v.ap_col;
+    }
+    return DXO_OK;
+}

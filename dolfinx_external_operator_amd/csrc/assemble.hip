@@ -525,6 +525,7 @@ extern "C" int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs
     DXO_LOCK(ctx);
     if (!csr || !values || (n_dofs > 0 && !dofs)) return dxo_fail(ctx, DXO_E_NULL, "dxo_csr_dirichlet: NULL argument");
     if (n_dofs < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_csr_dirichlet: n_dofs < 0");
+    if (!csr->mesh) return dxo_fail(ctx, DXO_E_DIM, "dxo_csr_dirichlet: a pattern without a mesh (a multigrid level) keeps no mask");
     hipStream_t s = dxo_launch_stream(ctx);
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     int rc = dxo_device_begin(ctx, s);

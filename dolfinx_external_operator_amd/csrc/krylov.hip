@@ -22,6 +22,7 @@
 // CG runs on the same kernels; once its residual test passes on the device, alpha is 0 for the steps that follow.
 #include "csr.h"
 #include "dxo_common.h"
+#include "krylov_internal.h"
 
 #include <algorithm>
 #include <chrono>
@@ -480,6 +481,10 @@ struct KrCall {
             (void)hipMemcpyAsync(z, r, (size_t)ws->n * sizeof(double), hipMemcpyDeviceToDevice, s);
             return;
         }
+        if (pc->kind == DXO_PC_AMG) {
+            dxo_amg_cycle(ctx, (dxo_amg*)pc->inv, r, z, s);
+            return;
+        }
         bj_apply_launch(ctx, pc->kind == DXO_PC_JACOBI ? 1 : pc->bs, ws->n, pc->inv, r, z, s);
     }
     // part[0..nb) = partials of (a, b); reduce into out (norm: sqrt and inverse into out[0], out[1])
@@ -516,7 +521,14 @@ int kr_validate(dxo_ctx* ctx, const char* who, dxo_krylov* ws, const dxo_krylov_
                  (long long)(op->csr ? op->csr->n_rows : op->n), (long long)ws->n);
         return dxo_fail(ctx, DXO_E_SIZE, msg);
     }
-    if (pc && pc->kind != DXO_PC_NONE) {
+    if (pc && pc->kind == DXO_PC_AMG) {      // pc->inv carries the dxo_amg*
+        if (pc->n != ws->n) {
+            snprintf(msg, sizeof msg, "%s: the preconditioner covers %lld rows, the operator has %lld", who, (long long)pc->n, (long long)ws->n);
+            return dxo_fail(ctx, DXO_E_SIZE, msg);
+        }
+        const int rc = dxo_amg_pc_check(ctx, who, (const dxo_amg*)pc->inv, op->csr, pc->bs, pc->n);
+        if (rc != DXO_OK) return rc;
+    } else if (pc && pc->kind != DXO_PC_NONE) {
         if (pc->kind != DXO_PC_JACOBI && pc->kind != DXO_PC_BLOCK_JACOBI) return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": unknown preconditioner kind").c_str());
         if (!pc->inv) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the preconditioner has no inverse").c_str());
         if (misaligned(pc->inv)) return dxo_fail(ctx, DXO_E_ALIGN, (std::string(who) + ": the preconditioner's inverse is not 8-byte aligned").c_str());
@@ -706,6 +718,14 @@ int kr_solve(dxo_ctx* ctx, const char* who, kr_solver solver, dxo_krylov* ws, co
 
 }  // namespace
 
+void dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv, int* flag, hipStream_t s) {
+    if (csr->n_nodes == 0) return;
+    const dim3 g((unsigned)((csr->n_nodes + DXO_KR_BLOCK - 1) / DXO_KR_BLOCK)), b(DXO_KR_BLOCK);
+    if (csr->bs == 1) hipLaunchKernelGGL(bj_setup<1>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+    else if (csr->bs == 2) hipLaunchKernelGGL(bj_setup<2>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+    else hipLaunchKernelGGL(bj_setup<3>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+}
+
 extern "C" int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
@@ -730,10 +750,7 @@ extern "C" int dxo_csr_block_jacobi(dxo_ctx* ctx, const dxo_csr* csr, const doub
     int* flag = (int*)dxo_scratch(ctx, s, 16);
     if (!flag) return dxo_fail(ctx, DXO_E_SIZE, "dxo_csr_block_jacobi: scratch allocation failed");
     DXO_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int), s));
-    const dim3 g((unsigned)((csr->n_nodes + DXO_KR_BLOCK - 1) / DXO_KR_BLOCK)), b(DXO_KR_BLOCK);
-    if (csr->bs == 1) hipLaunchKernelGGL(bj_setup<1>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
-    else if (csr->bs == 2) hipLaunchKernelGGL(bj_setup<2>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
-    else hipLaunchKernelGGL(bj_setup<3>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+    dxo_kr_bj_setup_launch(csr, values, inv, flag, s);
     int h = 0;
     DXO_HIP(ctx, hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s));
     DXO_HIP(ctx, hipStreamSynchronize(s));

@@ -11,9 +11,9 @@ import ctypes as C
 import weakref
 from dataclasses import dataclass
 
-from ._lib import KRYLOV_APPLY_FN, KrylovInfo, KrylovOp, KrylovPc, _CudaArrayView
+from ._lib import KRYLOV_APPLY_FN, AmgLevelInfo, KrylovInfo, KrylovOp, KrylovPc, _CudaArrayView
 
-PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI = 0, 1, 2
+PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI, PC_AMG = 0, 1, 2, 3
 
 
 def _torch():
@@ -79,6 +79,135 @@ class BlockJacobi:
 
     def _pc(self) -> KrylovPc:
         return KrylovPc(PC_BLOCK_JACOBI, self.bs, self.n, C.c_void_p(self.inv.data_ptr()))
+
+
+class AMG:
+    """Smoothed-aggregation multigrid preconditioner of an assembled matrix (dxo_amg_*, csrc/amg.hip), applied as one V-cycle.
+
+    The constructor runs the symbolic phase on the host (aggregates and the patterns of every level, once per pattern) and the first
+    setup(). After the values of the matrix changed (a Newton iteration: the same DeviceCSR, or another on the same pattern) call
+    setup() again; it runs on the device only. `constrained`: the dofs given to bilinear_assemble(bcs=...) (an int32 CUDA tensor,
+    or anything numpy converts), None for none. Pass it as M to gmres / cg (cg: symmetric positive definite A)."""
+
+    def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1):
+        torch = _torch()
+        import numpy as np
+
+        self.ctx, self.A, self.bs, self.n = A.pattern.ctx, A, A.pattern.bs, A.pattern.n_rows
+        self.device = A.values.device
+        if int(max_levels) < 1 or int(coarse_rows) < 1 or int(sweeps) < 1:
+            raise ValueError("AMG: max_levels, coarse_rows and sweeps must be at least 1")
+        if constrained is None:
+            bc = torch.empty(0, dtype=torch.int32, device=self.device)
+        elif isinstance(constrained, torch.Tensor):
+            bc = constrained.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            bc = torch.from_numpy(np.ascontiguousarray(constrained, dtype=np.int32)).to(self.device)
+        h = C.c_void_p()
+        _use_current_stream(self.ctx)
+        rc = self.ctx.lib.dxo_amg_create(self.ctx._h, A.pattern._h, C.c_void_p(bc.data_ptr()) if bc.numel() else None, int(bc.numel()),
+                                         int(max_levels), int(coarse_rows), int(sweeps), C.byref(h))
+        self.ctx.check(rc, "dxo_amg_create")
+        self._h = h
+        self._fin = weakref.finalize(self, self.ctx.lib.dxo_amg_destroy, None, h)
+        self._fin.atexit = False
+        nl, ms, oc = C.c_int(), C.c_double(), C.c_double()
+        self.ctx.check(self.ctx.lib.dxo_amg_info(self.ctx._h, h, C.byref(nl), C.byref(ms), C.byref(oc), 0, None), "dxo_amg_info")
+        self.n_levels, self.build_ms, self.operator_complexity = nl.value, ms.value, oc.value
+        self.setup()
+
+    def close(self) -> None:
+        self._fin()
+
+    def setup(self, A=None) -> "AMG":
+        """The numeric phase for the current values of the matrix (dxo_amg_setup); `A`: another DeviceCSR on the same pattern.
+        Synchronises once. A singular diagonal block or coarsest matrix raises ValueError (DXO_E_SINGULAR)."""
+        if A is not None:
+            if A.pattern is not self.A.pattern:
+                raise ValueError("AMG.setup: the matrix lies on another pattern than the one this object was made for")
+            self.A = A
+        _use_current_stream(self.ctx)
+        rc = self.ctx.lib.dxo_amg_setup(self.ctx._h, self._h, C.c_void_p(self.A.values.data_ptr()))
+        self.ctx.check(rc, "dxo_amg_setup")
+        return self
+
+    def apply(self, r, out=None):
+        """out = V(r), one V-cycle (dxo_amg_apply); returns out."""
+        torch = _torch()
+        _check_vec(r, self.n, self.device, "AMG.apply: r")
+        if out is None:
+            out = torch.empty_like(r)
+        _check_vec(out, self.n, self.device, "AMG.apply: out")
+        _use_current_stream(self.ctx)
+        rc = self.ctx.lib.dxo_amg_apply(self.ctx._h, self._h, C.c_void_p(r.data_ptr()), C.c_void_p(out.data_ptr()))
+        self.ctx.check(rc, "dxo_amg_apply")
+        return out
+
+    def _pc(self) -> KrylovPc:
+        return KrylovPc(PC_AMG, self.bs, self.n, C.c_void_p(self._h.value))
+
+    # ---- inspection (copies; for tests and reports)
+    def _info(self, level: int) -> AmgLevelInfo:
+        info = AmgLevelInfo()
+        self.ctx.check(self.ctx.lib.dxo_amg_info(self.ctx._h, self._h, None, None, None, int(level), C.byref(info)), "dxo_amg_info")
+        return info
+
+    def _array(self, ptr, n: int, typestr: str):
+        import numpy as np
+
+        torch = _torch()
+        if not n:
+            return np.empty(0, dtype=np.dtype(typestr))
+        torch.cuda.current_stream(self.device).synchronize()
+        return torch.as_tensor(_CudaArrayView(self, ptr, int(n), typestr), device=self.device).cpu().numpy().copy()
+
+    @property
+    def levels(self) -> list:
+        """Per level: rows, block nonzeros and omega (None on the coarsest level). Reading omega synchronises the stream."""
+        out = []
+        for l in range(self.n_levels):
+            i = self._info(l)
+            om = float(self._array(i.omega, 1, "<f8")[0]) if i.omega else None
+            out.append({"rows": int(i.n_rows), "nodes": int(i.n_nodes), "block_nnz": int(i.nnz_blocks), "omega": om})
+        return out
+
+    def aggregates(self, level: int):
+        """The aggregate of every node of `level` (-1: none), int32."""
+        i = self._info(level)
+        return self._array(i.aggregate, i.n_nodes if i.aggregate else 0, "<i4")
+
+    def level_matrix(self, level: int):
+        """A_level as a scipy.sparse.csr_matrix on the level's pattern (explicit zeros kept)."""
+        import scipy.sparse
+
+        i = self._info(level)
+        n_rows, nnz, rp, col = C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.dxo_csr_info(self.ctx._h, i.csr, C.byref(n_rows), C.byref(nnz), C.byref(rp), C.byref(col), None), "dxo_csr_info")
+        indptr = self._array(rp.value, n_rows.value + 1, "<i8")
+        return scipy.sparse.csr_matrix((self._array(i.values, nnz.value, "<f8"), self._array(col.value, nnz.value, "<i4"), indptr),
+                                       shape=(n_rows.value, n_rows.value))
+
+    def level_dinv(self, level: int):
+        """The block-Jacobi inverses of `level`, (nodes, bs, bs)."""
+        i = self._info(level)
+        return self._array(i.dinv, i.n_nodes * self.bs * self.bs if i.dinv else 0, "<f8").reshape(-1, self.bs, self.bs)
+
+    def prolongator(self, level: int):
+        """P_level (rows of `level`, rows of `level + 1`) as a scipy.sparse.bsr_matrix with bs x bs blocks (explicit zeros kept)."""
+        import scipy.sparse
+
+        i = self._info(level)
+        if not i.p_ptr:
+            raise ValueError(f"AMG.prolongator: level {level} is the coarsest")
+        bs = self.bs
+        data = self._array(i.p_values, i.p_blocks * bs * bs, "<f8").reshape(-1, bs, bs)
+        return scipy.sparse.bsr_matrix((data, self._array(i.p_col, i.p_blocks, "<i4"), self._array(i.p_ptr, i.n_nodes + 1, "<i8")),
+                                       shape=(i.n_rows, i.n_aggregates * bs))
+
+    def ap_pattern(self, level: int):
+        """(indptr, indices) of the block pattern of A_level P_level."""
+        i = self._info(level)
+        return self._array(i.ap_ptr, i.n_nodes + 1 if i.ap_ptr else 0, "<i8"), self._array(i.ap_col, i.ap_blocks, "<i4")
 
 
 def csr_matvec(A, x, y=None, alpha: float = 1.0, beta: float = 0.0):
@@ -172,11 +301,15 @@ def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxit
         if M.n != n or M.inv.device != dev:
             raise ValueError(f"{entry}: the preconditioner covers {M.n} rows on {M.inv.device}, the operator has {n} on {dev}")
         pc = M._pc()
+    elif isinstance(M, AMG):
+        if M.n != n or M.device != dev or not isinstance(A, DeviceCSR) or A.pattern.bs != M.bs:
+            raise ValueError(f"{entry}: the multigrid preconditioner covers {M.n} rows (bs {M.bs}) on {M.device}, the operator has {n} on {dev}")
+        pc = M._pc()
     elif isinstance(M, torch.Tensor):
         _check_vec(M, n, dev, f"{entry}: M (inverse diagonal)")
         pc = KrylovPc(PC_JACOBI, 1, n, C.c_void_p(M.data_ptr()))
     else:
-        raise TypeError(f"{entry}: M must be None, a BlockJacobi or a tensor holding an inverse diagonal")
+        raise TypeError(f"{entry}: M must be None, a BlockJacobi, an AMG or a tensor holding an inverse diagonal")
     if maxiter is None:
         maxiter = max(1000, 10 * restart)
     ws = _workspace(ctx, n, restart)
@@ -196,8 +329,8 @@ def gmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: fl
     """Solve A x = b by restarted GMRES(restart) with right preconditioning on the device (dxo_krylov_gmres).
 
     A: a DeviceCSR, or a callable (v, out) that sets out = A v on the device (e.g. DeviceMesh.bilinear_apply with option
-    consumer_overwrite = 1; `ctx` then names the context, default_context() otherwise). M: None, a BlockJacobi, or a float64 CUDA
-    tensor holding an inverse diagonal (1 / bilinear_diagonal for the matrix-free path). x: the initial guess, overwritten with the
+    consumer_overwrite = 1; `ctx` then names the context, default_context() otherwise). M: None, a BlockJacobi, an AMG (one V-cycle
+    per iteration; A must then be a DeviceCSR), or a float64 CUDA tensor holding an inverse diagonal (1 / bilinear_diagonal for the matrix-free path). x: the initial guess, overwritten with the
     solution (zeros if None). Converged when |b - A x| <= max(rtol |b|, atol); not converging within maxiter gives converged False,
     not an exception."""
     return _solve("dxo_krylov_gmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx)
@@ -209,4 +342,4 @@ def cg(A, b, x=None, M=None, rtol: float = 1e-10, atol: float = 0.0, maxiter: in
     return _solve("dxo_krylov_cg", A, b, x, M, 1, rtol, atol, maxiter, check_every, ctx)
 
 
-__all__ = ["BlockJacobi", "KrylovResult", "cg", "csr_matvec", "gmres"]
+__all__ = ["AMG", "BlockJacobi", "KrylovResult", "cg", "csr_matvec", "gmres"]

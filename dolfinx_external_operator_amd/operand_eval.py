@@ -531,6 +531,13 @@ class DeviceCSR:
 
         return BlockJacobi.from_csr(self)
 
+    def amg(self, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1) -> "AMG":
+        """A smoothed-aggregation multigrid preconditioner of this matrix (krylov.AMG: the symbolic phase and the first setup), for
+        krylov.gmres / krylov.cg. `constrained`: the dofs given as bcs to bilinear_assemble. After the values changed: `.setup()`."""
+        from .krylov import AMG
+
+        return AMG(self, constrained, max_levels, coarse_rows, sweeps)
+
 
 class DeviceOperand:
     """Plays the role of a UFL operand in `evaluation.evaluate_operands`: `.eval(entities)` returns what

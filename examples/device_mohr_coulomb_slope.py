@@ -7,7 +7,7 @@ A 1.2 x 1.0 rectangle of P2 triangles, bottom and right edges clamped, body forc
     sigma, C_tang = MC(eps(Du), sigma_n)        dxo_mohr_coulomb_field (mem = DEVICE)
     R = adjoint(eps, sigma) - adjoint(value, q) dxo_operand_adjoint, zero on the clamped dofs
     J = assembled (eps, eps) form with C_tang   dxo_bilinear_assemble + dxo_csr_dirichlet (identity rows)
-    solve J dDu = -R                            gmres with block Jacobi (dxo_krylov_gmres), or --solver lu: splu on the host
+    solve J dDu = -R                            gmres with block Jacobi (dxo_krylov_gmres), --solver amg: gmres with the multigrid cycle, --solver lu: splu on the host
     Du += dDu
 and at the end of a load step u += Du, sigma_n <- sigma. C_tang is the derivative through the return map and is not symmetric in
 general, hence GMRES. Newton stops at |R| <= max(1e-8, 1e-8 |R_0|) (the demo's snes_atol / snes_rtol). Each step starts from
@@ -16,7 +16,7 @@ Du = 0, where the return map has no tangent: with deps = 0 its initial residual 
 the same reason, :639-646). The first Newton iteration of a step therefore uses the elastic tangent, the others C_tang. A step
 whose GMRES or Newton does not converge is reported and ends the loading.
 
-    python3 examples/device_mohr_coulomb_slope.py [--n 25] [--steps K] [--solver gmres|lu]
+    python3 examples/device_mohr_coulomb_slope.py [--n 25] [--steps K] [--solver gmres|amg|lu]
 """
 import argparse
 import pathlib
@@ -89,6 +89,7 @@ def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: 
         dm.adjoint("value", G, q.data_ptr(), Rq.data_ptr())
         return torch.where(free, R - Rq, torch.zeros_like(R))
 
+    amg = None
     loads = load_schedule()[: steps if steps else None]
     report = {"dofs": nn * G, "nnz": pattern.nnz, "solver": solver, "steps": [], "failed": None}
     for i, load in enumerate(loads):
@@ -110,9 +111,13 @@ def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: 
                 d = torch.from_numpy(scipy.sparse.linalg.splu(S).solve(rhs.cpu().numpy())).to(dev)
             else:
                 try:
-                    M = A.block_jacobi()
+                    if solver == "amg":          # the symbolic phase once, the numeric setup at every Newton iteration
+                        amg = A.amg(bcs) if amg is None else amg.setup(A)
+                        M = amg
+                    else:
+                        M = A.block_jacobi()
                 except ValueError as e:          # DXO_E_SINGULAR: a node whose tangent blocks vanish
-                    failed = f"block Jacobi failed at load {load:.3f} (step {i}, Newton iteration {it}): {e}"
+                    failed = f"preconditioner setup failed at load {load:.3f} (step {i}, Newton iteration {it}): {e}"
                     break
                 out = gmres(A, rhs, M=M, restart=restart, rtol=lin_rtol, maxiter=lin_maxiter)
                 lin_its.append(out.iterations)
@@ -138,7 +143,7 @@ def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: 
                                 "residuals": history})
         if verbose:
             print(f"step {i:2d} load {load:6.3f}: u_x(0, H) = {ux: .6e}, {len(history) - 1} Newton its"
-                  + (f", GMRES its {lin_its}" if solver == "gmres" else "") + f", {ms:.0f} ms")
+                  + (f", GMRES its {lin_its}" if solver != "lu" else "") + f", {ms:.0f} ms")
     done = report["steps"]
     report["load_reached"] = done[-1]["load"] if done else 0.0
     report["stability_factor"] = report["load_reached"] * GAMMA * H / COH
@@ -155,6 +160,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--n", type=int, default=25, help="cells per side (the demo: 25)")
     ap.add_argument("--steps", type=int, default=None, help="first K load steps only")
-    ap.add_argument("--solver", choices=["gmres", "lu"], default="gmres")
+    ap.add_argument("--solver", choices=["gmres", "amg", "lu"], default="gmres")
     a = ap.parse_args()
     main(a.n, a.steps, a.solver)

@@ -594,12 +594,14 @@ int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n
  * "consumer_overwrite" = 1). The callback runs on the calling thread while the context's (recursive) lock is held, so it may call
  * other dxo_* entry points on the same context; a nonzero return ends the solve with that code. Preconditioner: NULL or kind
  * DXO_PC_NONE, DXO_PC_JACOBI (inv [n]) or DXO_PC_BLOCK_JACOBI (inv [n/bs][bs][bs], bs equal to the pattern's).
+ * DXO_PC_AMG: a dxo_amg (below) after dxo_amg_setup, applied as one V-cycle.
  * Errors: NULL arguments DXO_E_NULL; operator, matrix, workspace and preconditioner sizes that differ, n not a multiple of bs, max_it < 0 or
  * check_every < 1 DXO_E_SIZE; a preconditioner of another block size DXO_E_DIM; arrays not 8-byte aligned DXO_E_ALIGN; negative
  * tolerances or an unknown preconditioner kind DXO_E_OPTION. */
 #define DXO_PC_NONE 0
 #define DXO_PC_JACOBI 1
 #define DXO_PC_BLOCK_JACOBI 2
+#define DXO_PC_AMG 3               /* dxo_krylov_pc::inv carries the dxo_amg* (cast to const double*), bs and n as for block Jacobi */
 typedef struct dxo_krylov dxo_krylov;
 typedef int (*dxo_krylov_apply_fn)(void* user, const double* v, double* out);
 typedef struct dxo_krylov_op {
@@ -632,6 +634,58 @@ int dxo_krylov_gmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, cons
                      double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info);
 int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
                   double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info);
+
+/* ---- smoothed-aggregation multigrid preconditioner (csrc/amg.hip), DEVICE memory only ---------------------------
+ * A V-cycle for a matrix on a dxo_csr pattern; the block size bs (1, 2, 3) is the same on every level, so every level is a matrix in
+ * the layout of dxo_csr_spmv. Nothing but the matrix is needed (no mesh hierarchy).
+ * dxo_amg_create  : the symbolic phase, host C++, once per pattern. `constrained` is the DEVICE int32 list given to dxo_csr_dirichlet
+ *                   (may be NULL with n_constrained = 0; out-of-range entries are ignored). A node all of whose dofs are constrained
+ *                   joins no aggregate. Aggregation in three passes in ascending node order (a node whose whole neighbourhood is free
+ *                   founds an aggregate with it; a left-over node joins the lowest pass-1 aggregate among its neighbours; the rest
+ *                   found aggregates with their free neighbours): a function of the pattern and the list alone. Block patterns of
+ *                   P, A P and P^T A P and the transposed incidence of P are built and uploaded; the coarse patterns are dxo_csr
+ *                   objects without a mesh (dxo_bilinear_assemble and dxo_csr_dirichlet answer DXO_E_DIM on them). Coarsening stops at
+ *                   n_rows <= coarse_rows, at max_levels, or when a coarse level would keep more than 0.8 of its parent's rows. A
+ *                   coarsest level of more than 4096 rows: DXO_E_SIZE. max_levels, coarse_rows or sweeps < 1: DXO_E_SIZE; bs outside
+ *                   1..3: DXO_E_DIM. All device memory of setup and apply is allocated here.
+ * dxo_amg_setup   : the numeric phase for the matrix `values` on the pattern of the creation, on the context's stream: per level the
+ *                   block-Jacobi inverses, rho = |Dinv A|_inf and omega = (4/3) / rho (kept on the device), P = T - omega Dinv A T,
+ *                   A_c = P^T (A P); the coarsest matrix is inverted densely (Gauss-Jordan, partial pivoting). Sums run in ascending
+ *                   source order, no atomics: two setups from the same values give bit-identical hierarchies. One synchronisation at
+ *                   the end reads one flag: a singular diagonal block or a zero pivot gives DXO_E_SINGULAR. `values` is read again by
+ *                   dxo_amg_apply and must stay alive and unchanged until the next setup.
+ * dxo_amg_apply   : z = V(r): `sweeps` damped block-Jacobi sweeps before and after the coarse correction on every level (the first
+ *                   from x = 0), restriction by P^T, the dense inverse on the coarsest level. r may equal z. A fixed linear operator,
+ *                   symmetric for a symmetric matrix. Capture-safe, allocation-free, bit-reproducible. Before a successful setup:
+ *                   DXO_E_OPTION.
+ * dxo_amg_info    : counts and the DEVICE arrays of one level (any pointer may be NULL; `level` outside [0, n_levels): DXO_E_SIZE).
+ * In dxo_krylov_gmres / dxo_krylov_cg: kind DXO_PC_AMG, inv = (const double*)amg, bs and n those of the matrix; an object made for a
+ * pattern of another size is DXO_E_SIZE, of another block size DXO_E_DIM, one without a setup DXO_E_OPTION. */
+typedef struct dxo_amg dxo_amg;
+typedef struct dxo_amg_level_info {
+    int64_t n_rows, n_nodes;       /* of A_l                                              */
+    int64_t nnz_blocks;            /* bs x bs blocks of A_l                               */
+    const dxo_csr* csr;            /* pattern of A_l (level 0: the caller's)              */
+    const double* values;          /* A_l (level 0: the pointer of the last setup)        */
+    const double* dinv;            /* [n_nodes][bs][bs]; NULL on the coarsest level       */
+    const double* omega;           /* one double on the device; NULL on the coarsest      */
+    int64_t n_aggregates;          /* nodes of level l + 1; 0 on the coarsest level       */
+    const int32_t* aggregate;      /* [n_nodes] aggregate of a node, -1: none             */
+    int64_t p_blocks;              /* blocks of P_l, block CSR over nodes x aggregates    */
+    const int64_t* p_ptr;          /* [n_nodes + 1]                                       */
+    const int32_t* p_col;          /* [p_blocks] aggregate                                */
+    const double* p_values;        /* [p_blocks][bs][bs]                                  */
+    int64_t ap_blocks;             /* blocks of A_l P_l                                   */
+    const int64_t* ap_ptr;         /* [n_nodes + 1]                                       */
+    const int32_t* ap_col;         /* [ap_blocks]                                         */
+} dxo_amg_level_info;
+int dxo_amg_create(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, int max_levels, int coarse_rows,
+                   int sweeps, dxo_amg** out);
+int dxo_amg_destroy(dxo_ctx* ctx, dxo_amg* amg);
+int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values);
+int dxo_amg_apply(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z);
+int dxo_amg_info(dxo_ctx* ctx, const dxo_amg* amg, int* n_levels, double* build_ms, double* operator_complexity, int level,
+                 dxo_amg_level_info* out);
 
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Standalone timing of the multigrid preconditioner (csrc/amg.hip; not a bench.py leg).
+    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE]
+Systems (distorted meshes, the lower side clamped so that the matrices are regular):
+  p2       ("grad", "grad", 2) on P2 triangles with C = I + 0.3 N(0, 1) per point (1291 per side: 10^7 points), as tools/bench_krylov.py
+  q2hex    ("eps", "eps", 3) on Q2 hexahedra (40^3 boxes), the same kind of C
+  heat_*   the heat-type Jacobian of tools/bench_krylov.py (P1, ("grad", "value_grad"), Dirichlet boundary) at two sizes (256, 1024)
+Per system: dxo_csr_spmv ms, dxo_bilinear_assemble ms, the symbolic phase (host, once), dxo_amg_setup ms, dxo_amg_apply ms and its ratio
+to one SpMV beside the model 2 + 3 (c - 1) (c the operator complexity), rows per level, and one GMRES(30) solve to rtol 1e-8 (at most
+`maxiter` iterations) with block Jacobi and with the cycle (iterations, ms; the cycle's total adds one setup).
+Timing: warm-up, then 5 batches timed with HIP events on the launch stream, the MEDIAN batch reported (tools/bench_krylov._batches).
+Prints one JSON line."""
+from __future__ import annotations
+
+import json
+import pathlib
+import sys
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+
+def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000) -> dict:
+    import numpy as np
+    import torch
+
+    from dolfinx_external_operator_amd import Context, DeviceMesh, gmres
+    from tools.bench_krylov import _batches
+    from tools.synthetic import structured_mesh
+
+    ctx = Context(0)
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_option("consumer_overwrite", 1)
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    res = {"maxiter": maxiter, "systems": {}}
+
+    def timed(fn, per_batch):
+        ms, _ = _batches(torch, stream, fn, per_batch=per_batch, warm=2)
+        return round(ms, 4)
+
+    def system(tag, m, test, trial, bs, Cd, bnd):
+        dm = DeviceMesh.from_synthetic(m, ctx=ctx)
+        try:
+            with torch.cuda.stream(stream):
+                pat = dm.csr_pattern(bs)
+                bcs = torch.from_numpy(bnd.astype(np.int32)).to(dev)
+                A = dm.bilinear_assemble(test, trial, bs, Cd.data_ptr(), pat, bcs=bcs)
+                n = A.shape[0]
+                x = torch.randn(n, generator=gen, device=dev, dtype=torch.float64)
+                y = torch.empty_like(x)
+                r = {"dofs": n, "nnz": pat.nnz, "points": m.num_cells * m.nq}
+                r["spmv_ms"] = timed(lambda: A.matvec(x, y), 20)
+                r["assemble_ms"] = timed(lambda: dm.bilinear_assemble(test, trial, bs, Cd.data_ptr(), pat, values=A.values, bcs=bcs), 3)
+                amg = A.amg(bcs)
+                r["symbolic_ms"] = round(amg.build_ms, 1)
+                r["setup_ms"] = timed(lambda: amg.setup(), 3)
+                r["apply_ms"] = timed(lambda: amg.apply(x, y), 20)
+                c = amg.operator_complexity
+                r["levels"] = amg.levels
+                r["operator_complexity"] = round(c, 4)
+                r["apply_over_spmv"] = round(r["apply_ms"] / r["spmv_ms"], 2)
+                r["apply_over_spmv_model"] = round(2 + 3 * (c - 1), 2)
+                b = torch.randn(n, generator=gen, device=dev, dtype=torch.float64)
+                for name, M in (("block_jacobi", A.block_jacobi()), ("amg", amg)):
+                    gmres(A, b, M=M, rtol=1e-8, maxiter=30)                  # warm-up
+                    out = gmres(A, b, M=M, restart=30, rtol=1e-8, maxiter=maxiter)
+                    r[f"gmres30_{name}"] = {"iterations": out.iterations, "converged": out.converged, "residual": out.residual,
+                                            "ms": round(out.ms, 2)}
+                r["gmres30_amg"]["ms_with_setup"] = round(r["gmres30_amg"]["ms"] + r["setup_ms"], 2)
+                amg.close()
+            stream.synchronize()
+            res["systems"][tag] = r
+            print(tag, json.dumps(r), file=sys.stderr, flush=True)
+        finally:
+            dm.close()
+            torch.cuda.empty_cache()
+
+    def lower_side(m, bs):
+        on = np.flatnonzero(np.abs(m.node_x[:, 1] - m.node_x[:, 1].min()) < 1e-12)
+        return (on[:, None] * bs + np.arange(bs)).reshape(-1)
+
+    for n in (n_heat, n_heat_large):
+        if n <= 0:
+            continue
+        m = structured_mesh("triangle", (n, n), 1, distort=0.2, seed=0)
+        npts = m.num_cells * m.nq
+        Cb = np.zeros((npts, 2, 3))
+        Cb[:, :, 0] = 0.5                                            # dq/dT part: makes it non-symmetric
+        Cb[:, 0, 1] = Cb[:, 1, 2] = 1.0 + 0.5 * np.random.Generator(np.random.PCG64(0)).random(npts)
+        bnd = np.flatnonzero((m.node_x.min(axis=1) < 1e-12) | (m.node_x.max(axis=1) > 1 - 1e-12))
+        system(f"heat_{n}", m, "grad", "value_grad", 1, torch.from_numpy(Cb.reshape(-1)).to(dev), bnd)
+    for tag, cell, n, test, trial, bs in (("p2", "triangle", (n_side, n_side), "grad", "grad", 2),
+                                          ("q2hex", "hexahedron", (n_hex, n_hex, n_hex), "eps", "eps", 3)):
+        if n[0] <= 0:
+            continue
+        m = structured_mesh(cell, n, 2, distort=0.2, seed=0)
+        G = m.gdim
+        D = {"grad": bs * G, "eps": 4 if G == 2 else 6}[test]
+        npts = m.num_cells * m.nq
+        Cd = 0.3 * torch.randn(npts * D * D, generator=gen, device=dev, dtype=torch.float64)
+        Cd.view(npts, D, D).add_(torch.eye(D, device=dev, dtype=torch.float64))
+        system(tag, m, test, trial, bs, Cd, lower_side(m, bs))
+    ctx.close()
+    return res
+
+
+if __name__ == "__main__":
+    args = sys.argv[1:]
+    out_file = None
+    if "--out" in args:
+        i = args.index("--out")
+        out_file = args[i + 1]
+        del args[i:i + 2]
+    r = main(*(int(a) for a in args))
+    line = json.dumps(r)
+    print(line)
+    if out_file:
+        pathlib.Path(out_file).write_text(line + "\n")
