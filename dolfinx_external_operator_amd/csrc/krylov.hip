@@ -362,8 +362,11 @@ __global__ void kr_givens(double* __restrict__ sc, int* __restrict__ st, int j, 
     g[j] = c * g[j];
     const double est = fabs(g[j + 1]);
     sc[o_s + S_EST] = est;
-    if (!(hn > 0.0)) st[W_BREAK] = 1;
-    if (st[W_CONV] < 0 && (est <= tol || !(hn > 0.0))) st[W_CONV] = j + 1;
+    // steps run past the recorded one (check_every > 1) are not part of the solve: a zero vector there is no breakdown
+    if (st[W_CONV] < 0 && (est <= tol || !(hn > 0.0))) {
+        st[W_CONV] = j + 1;
+        if (!(hn > 0.0)) st[W_BREAK] = 1;
+    }
 }
 
 // one thread: R y = g on the first k columns (back substitution); a zero pivot gives y_i = 0
