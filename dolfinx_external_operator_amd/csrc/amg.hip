@@ -18,11 +18,23 @@
 // Apply (dxo_amg_cycle): per level x = omega Dinv r, then x <- x + omega Dinv (r - A x) in the lane-group shape of csr_spmv (LW lanes
 // own a node, fixed xor-butterfly) with the update in the epilogue, t = r - A x by the same kernel, r_c = P^T t gathered through the
 // transposed incidence in ascending fine-node order, x += P x_c, the same sweeps again; the coarsest level is one dense product.
+//
+// With a near-null space (dxo_amg_create_nns: B [n_rows][k], the rigid-body modes of dxo_rigid_body_modes, k = 3 for bs 2 and 6 for
+// bs 3) the tentative prolongator is not an identity per node: after the symbolic phase, once, amg_tentative orthonormalises the rows of
+// B of every aggregate (ascending node order; Gram-Schmidt in column order with a second pass; a lane group owns an aggregate, column
+// products by the xor-butterfly), keeps the Q factors as the blocks of T ([n_nodes][bs_l][k]) and the R factors as the B of the next
+// level. A column that keeps no more than rank_tol of its norm is dead: its Q column and its row of the next B are zero, so it stays out
+// on every coarser level and its coarse diagonal entry, exactly zero, becomes 1. Every coarse level then has block size k; the kernels
+// of P, A P, P^T A P, restriction and prolongation take <BSR, BSC> (rows of the level, rows of the next), and the levels of block
+// size 6 invert their diagonal blocks by Gauss-Jordan with partial pivoting in registers (rows exchanged by compare-and-select).
+// T and B depend on B_0, the aggregates and the constraints alone: dxo_amg_setup does not touch them.
 #include "krylov_internal.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 
 #ifndef DXO_AMG_BLOCK
 #define DXO_AMG_BLOCK 256
@@ -35,6 +47,7 @@ constexpr int64_t AMG_MAX_DENSE = 4096;
 struct amg_level {
     const dxo_csr* A = nullptr;        // pattern (level 0: the caller's, coarser: own)
     dxo_csr* own = nullptr;
+    int bs = 0, bsc = 0;               // block size of this level and of the next (equal without a near-null space)
     int64_t n_nodes = 0, n_rows = 0, nnzb = 0;
     int lw = 8;                        // lanes per node of the sweeps
     const double* values = nullptr;    // level 0: the pointer of the last setup
@@ -55,6 +68,14 @@ struct amg_level {
     // vectors [n_rows]
     double *r = nullptr, *xa = nullptr, *xb = nullptr, *t = nullptr;
     double* cur = nullptr;             // the iterate of the running cycle
+    // near-null space path only
+    double* b_val = nullptr;           // [n_rows][k] B of this level
+    double* t_val = nullptr;           // [n_nodes][bs][k] blocks of T (absent on the coarsest)
+    int64_t* agg_ptr = nullptr;        // [n_agg + 1] the nodes of an aggregate ...
+    int32_t* agg_node = nullptr;       // ... ascending
+    uint8_t* dead_a = nullptr;         // [n_agg] dead columns of an aggregate
+    int tl = 8;                        // lanes per aggregate of amg_tentative
+    int64_t dead = 0;                  // dead columns of T (host, after creation)
 };
 
 }  // namespace
@@ -71,6 +92,7 @@ struct dxo_amg {
     int64_t nc = 0;                    // rows of the coarsest level
     bool ready = false;
     double build_ms = 0.0, complexity = 1.0;
+    int k = 0;                         // columns of the near-null space; 0: none (an identity per node)
 };
 
 namespace {
@@ -177,49 +199,69 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_row_mask(int64_t n_rows, co
     mask[row] = any ? 0 : 1;
 }
 
-// P = T - omega Dinv (A T), one thread per block (i, a): the neighbours j of i with aggregate a, ascending
-template <int BS>
+// P = T - omega Dinv (A T), one thread per block (i, a): the neighbours j of i with aggregate a, ascending. NNS: the block of T of
+// node j is t_val[j] (BSR x BSC); otherwise an identity without the masked dofs (BSR == BSC)
+template <int BSR, int BSC, bool NNS>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_p(int64_t p_blocks, const int32_t* __restrict__ p_row, const int32_t* __restrict__ p_col,
                                                              const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                              const double* __restrict__ values, const double* __restrict__ dinv,
                                                              const int32_t* __restrict__ agg, const uint8_t* __restrict__ mask,
-                                                             const double* __restrict__ omega, double* __restrict__ p_val) {
+                                                             const double* __restrict__ t_val, const double* __restrict__ omega,
+                                                             double* __restrict__ p_val) {
+    static_assert(NNS || BSR == BSC, "an identity per node needs square blocks");
     const int64_t e = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
     if (e >= p_blocks) return;
     const int64_t i = p_row[e];
     const int32_t a = p_col[e];
-    const NodeRow<BS> R(row_ptr, i);
-    double acc[BS][BS];
+    const NodeRow<BSR> R(row_ptr, i);
+    double acc[BSR][BSC];
 #pragma unroll
-    for (int r = 0; r < BS; ++r)
+    for (int r = 0; r < BSR; ++r)
 #pragma unroll
-        for (int c = 0; c < BS; ++c) acc[r][c] = 0.0;
+        for (int c = 0; c < BSC; ++c) acc[r][c] = 0.0;
     for (int k = 0; k < R.nnb; ++k) {
-        const int64_t j = col[R.r0 + (int64_t)k * BS] / BS;
+        const int64_t j = col[R.r0 + (int64_t)k * BSR] / BSR;
         if (agg[j] != a) continue;
+        if constexpr (NNS) {
 #pragma unroll
-        for (int c = 0; c < BS; ++c) {
-            if (mask[j * BS + c]) continue;
+            for (int q = 0; q < BSR; ++q) {
+                double tq[BSC];
 #pragma unroll
-            for (int r = 0; r < BS; ++r) acc[r][c] += values[R.r0 + r * R.len + (int64_t)k * BS + c];
+                for (int c = 0; c < BSC; ++c) tq[c] = t_val[(j * BSR + q) * BSC + c];
+#pragma unroll
+                for (int r = 0; r < BSR; ++r) {
+                    const double v = values[R.r0 + r * R.len + (int64_t)k * BSR + q];
+#pragma unroll
+                    for (int c = 0; c < BSC; ++c) acc[r][c] = fma(v, tq[c], acc[r][c]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < BSC; ++c) {
+                if (mask[j * BSR + c]) continue;
+#pragma unroll
+                for (int r = 0; r < BSR; ++r) acc[r][c] += values[R.r0 + r * R.len + (int64_t)k * BSR + c];
+            }
         }
     }
     const double om = omega[0];
     const bool own = agg[i] == a;
 #pragma unroll
-    for (int r = 0; r < BS; ++r)
+    for (int r = 0; r < BSR; ++r)
 #pragma unroll
-        for (int c = 0; c < BS; ++c) {
+        for (int c = 0; c < BSC; ++c) {
             double s = 0.0;
 #pragma unroll
-            for (int q = 0; q < BS; ++q) s = fma(dinv[i * BS * BS + r * BS + q], acc[q][c], s);
-            const double t = (own && r == c && !mask[i * BS + r]) ? 1.0 : 0.0;
-            p_val[e * BS * BS + r * BS + c] = t - om * s;
+            for (int q = 0; q < BSR; ++q) s = fma(dinv[i * BSR * BSR + r * BSR + q], acc[q][c], s);
+            double t;
+            if constexpr (NNS) t = own ? t_val[(i * BSR + r) * BSC + c] : 0.0;
+            else t = (own && r == c && !mask[i * BSR + r]) ? 1.0 : 0.0;
+            p_val[e * BSR * BSC + r * BSC + c] = t - om * s;
         }
 }
 
 // (A P)(i, a) = sum over the neighbours j of i, ascending, of A_ij P_ja
-template <int BS>
+template <int BSR, int BSC>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_ap(int64_t ap_blocks, const int32_t* __restrict__ ap_row, const int32_t* __restrict__ ap_col,
                                                               const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                               const double* __restrict__ values, const int64_t* __restrict__ p_ptr,
@@ -229,38 +271,38 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_ap(int64_t ap_blocks,
     if (e >= ap_blocks) return;
     const int64_t i = ap_row[e];
     const int32_t a = ap_col[e];
-    const NodeRow<BS> R(row_ptr, i);
-    double acc[BS][BS];
+    const NodeRow<BSR> R(row_ptr, i);
+    double acc[BSR][BSC];
 #pragma unroll
-    for (int r = 0; r < BS; ++r)
+    for (int r = 0; r < BSR; ++r)
 #pragma unroll
-        for (int c = 0; c < BS; ++c) acc[r][c] = 0.0;
+        for (int c = 0; c < BSC; ++c) acc[r][c] = 0.0;
     for (int k = 0; k < R.nnb; ++k) {
-        const int64_t j = col[R.r0 + (int64_t)k * BS] / BS;
+        const int64_t j = col[R.r0 + (int64_t)k * BSR] / BSR;
         const int64_t f = amg_find(p_col, p_ptr[j], p_ptr[j + 1], a);
         if (f < 0) continue;
-        double pb[BS][BS];
+        // one row of the block of P at a time: an entry of acc still takes its terms in ascending q
 #pragma unroll
-        for (int q = 0; q < BS; ++q)
+        for (int q = 0; q < BSR; ++q) {
+            double pq[BSC];
 #pragma unroll
-            for (int c = 0; c < BS; ++c) pb[q][c] = p_val[f * BS * BS + q * BS + c];
+            for (int c = 0; c < BSC; ++c) pq[c] = p_val[f * BSR * BSC + q * BSC + c];
 #pragma unroll
-        for (int r = 0; r < BS; ++r)
+            for (int r = 0; r < BSR; ++r) {
+                const double v = values[R.r0 + r * R.len + (int64_t)k * BSR + q];
 #pragma unroll
-            for (int q = 0; q < BS; ++q) {
-                const double v = values[R.r0 + r * R.len + (int64_t)k * BS + q];
-#pragma unroll
-                for (int c = 0; c < BS; ++c) acc[r][c] = fma(v, pb[q][c], acc[r][c]);
+                for (int c = 0; c < BSC; ++c) acc[r][c] = fma(v, pq[c], acc[r][c]);
             }
+        }
     }
 #pragma unroll
-    for (int r = 0; r < BS; ++r)
+    for (int r = 0; r < BSR; ++r)
 #pragma unroll
-        for (int c = 0; c < BS; ++c) ap_val[e * BS * BS + r * BS + c] = acc[r][c];
+        for (int c = 0; c < BSC; ++c) ap_val[e * BSR * BSC + r * BSC + c] = acc[r][c];
 }
 
 // A_c(a, b) = sum over the blocks (i, a) of P, ascending i, of P_ia^T (A P)_ib; an exactly zero diagonal entry becomes 1
-template <int BS>
+template <int BSR, int BSC>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_c(int64_t c_blocks, const int32_t* __restrict__ c_row, const int64_t* __restrict__ c_bptr,
                                                              const int64_t* __restrict__ c_row_ptr, const int32_t* __restrict__ c_col,
                                                              const int64_t* __restrict__ pt_ptr, const int64_t* __restrict__ pt_blk,
@@ -271,39 +313,232 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_c(int64_t c_blocks, c
     if (g >= c_blocks) return;
     const int64_t a = c_row[g];
     const int64_t k = g - c_bptr[a];
-    const NodeRow<BS> R(c_row_ptr, a);
-    const int32_t b = c_col[R.r0 + k * BS] / BS;
-    double acc[BS][BS];
+    const NodeRow<BSC> R(c_row_ptr, a);
+    const int32_t b = c_col[R.r0 + k * BSC] / BSC;
+    double acc[BSC][BSC];
 #pragma unroll
-    for (int r = 0; r < BS; ++r)
+    for (int r = 0; r < BSC; ++r)
 #pragma unroll
-        for (int c = 0; c < BS; ++c) acc[r][c] = 0.0;
+        for (int c = 0; c < BSC; ++c) acc[r][c] = 0.0;
     for (int64_t e = pt_ptr[a]; e < pt_ptr[a + 1]; ++e) {
         const int64_t pb = pt_blk[e];
         const int64_t i = p_row[pb];
         const int64_t f = amg_find(ap_col, ap_ptr[i], ap_ptr[i + 1], b);
         if (f < 0) continue;
 #pragma unroll
-        for (int q = 0; q < BS; ++q) {
-            double w[BS];
+        for (int q = 0; q < BSR; ++q) {
+            double w[BSC];
 #pragma unroll
-            for (int c = 0; c < BS; ++c) w[c] = ap_val[f * BS * BS + q * BS + c];
+            for (int c = 0; c < BSC; ++c) w[c] = ap_val[f * BSR * BSC + q * BSC + c];
 #pragma unroll
-            for (int r = 0; r < BS; ++r) {
-                const double p = p_val[pb * BS * BS + q * BS + r];
+            for (int r = 0; r < BSC; ++r) {
+                const double p = p_val[pb * BSR * BSC + q * BSC + r];
 #pragma unroll
-                for (int c = 0; c < BS; ++c) acc[r][c] = fma(p, w[c], acc[r][c]);
+                for (int c = 0; c < BSC; ++c) acc[r][c] = fma(p, w[c], acc[r][c]);
             }
         }
     }
 #pragma unroll
-    for (int r = 0; r < BS; ++r)
+    for (int r = 0; r < BSC; ++r)
 #pragma unroll
-        for (int c = 0; c < BS; ++c) {
+        for (int c = 0; c < BSC; ++c) {
             double v = acc[r][c];
             if (a == b && r == c && v == 0.0) v = 1.0;
-            c_val[R.r0 + r * R.len + k * BS + c] = v;
+            c_val[R.r0 + r * R.len + k * BSC + c] = v;
         }
+}
+
+// ---- the block inverses of a level of block size 6: Gauss-Jordan on [A | I] with partial pivoting (the lowest row among equals),
+// one thread per node. Rows are exchanged by compare-and-select over static indices, so the 72 doubles stay in registers. A block
+// with |det| <= 1e-14 of the product of its row norms (the rule of dxo_csr_block_jacobi) gets a zero inverse and raises the flag.
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_bj6(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                         const double* __restrict__ values, double* __restrict__ inv, int* __restrict__ singular) {
+    constexpr int BS = 6;
+    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (node >= n_nodes) return;
+    const NodeRow<BS> R(row_ptr, node);
+    int lo = 0, hi = R.nnb - 1;
+    const int64_t self = node * BS;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (col[R.r0 + (int64_t)mid * BS] < self) lo = mid + 1;
+        else hi = mid;
+    }
+    bool ok = hi >= 0 && col[R.r0 + (int64_t)lo * BS] == self;
+    double M[BS][2 * BS];
+    double had = 1.0, det = 1.0;
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+        double n2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) {
+            M[i][j] = ok ? values[R.r0 + i * R.len + (int64_t)lo * BS + j] : 0.0;
+            M[i][BS + j] = i == j ? 1.0 : 0.0;
+            n2 = fma(M[i][j], M[i][j], n2);
+        }
+        had *= sqrt(n2);
+    }
+#pragma unroll
+    for (int k = 0; k < BS; ++k) {
+        int p = k;
+        double best = fabs(M[k][k]);
+#pragma unroll
+        for (int i = k + 1; i < BS; ++i) {
+            const double v = fabs(M[i][k]);
+            if (v > best) {
+                best = v;
+                p = i;
+            }
+        }
+#pragma unroll
+        for (int i = k + 1; i < BS; ++i) {
+            const bool sw = p == i;
+#pragma unroll
+            for (int c = k; c < 2 * BS; ++c) {
+                const double x = M[k][c], y = M[i][c];
+                M[k][c] = sw ? y : x;
+                M[i][c] = sw ? x : y;
+            }
+        }
+        if (p != k) det = -det;
+        const double piv = M[k][k];
+        det *= piv;
+#pragma unroll
+        for (int c = k; c < 2 * BS; ++c) M[k][c] = M[k][c] / piv;
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            if (i == k) continue;
+            const double fct = M[i][k];
+#pragma unroll
+            for (int c = k; c < 2 * BS; ++c) M[i][c] = fma(-fct, M[k][c], M[i][c]);
+        }
+    }
+    ok = ok && fabs(det) > 1e-14 * had;     // false for a zero, NaN or nearly singular block
+    double* out = inv + node * BS * BS;
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) out[i * BS + j] = ok ? M[i][BS + j] : 0.0;
+    if (!ok) singular[0] = 1;     // every writer stores the same word
+}
+
+// ---- the near-null space, at creation
+// the rows of constrained dofs of B_0 are zero
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_zero_rows(int64_t n_rows, int k, const uint8_t* __restrict__ mask, double* __restrict__ B) {
+    const int64_t row = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (row >= n_rows || !mask[row]) return;
+    for (int c = 0; c < k; ++c) B[row * k + c] = 0.0;
+}
+
+// LG lanes own one aggregate: its rows (BSR per node, the nodes ascending) go to the lanes in turn, row t to lane t % LG. Column j of
+// the aggregate's rows of B is copied to column j of its T blocks and worked on there (a lane reads back only what it wrote itself):
+// twice c = Q_{<j}^T v, v -= Q_{<j} c, R_{<j, j} += c; a column that keeps no more than tol of its norm is dead (Q column and R
+// diagonal zero). Every column product is a lane's partial sum in ascending row order, then the fixed xor-butterfly over the group.
+template <int LG>
+__device__ __forceinline__ double amg_group_sum(double s) {
+#pragma unroll
+    for (int off = LG / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, LG);
+    return s;
+}
+
+template <int BSR, int K, int LG>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_tentative(int64_t n_agg, const int64_t* __restrict__ agg_ptr, const int32_t* __restrict__ agg_node,
+                                                               const double* __restrict__ B, double tol, double* t_val, double* __restrict__ Bn,
+                                                               uint8_t* __restrict__ dead_a) {
+    constexpr int APB = DXO_AMG_BLOCK / LG;
+    const int64_t a = (int64_t)blockIdx.x * APB + threadIdx.x / LG;
+    const int lane = threadIdx.x % LG;
+    const bool valid = a < n_agg;                              // the lanes of an absent aggregate run along with no rows
+    const int64_t first = valid ? agg_ptr[a] : 0;
+    const int64_t m = valid ? (agg_ptr[a + 1] - first) * BSR : 0;
+    int n_dead = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        double s = 0.0;
+        for (int64_t t = lane; t < m; t += LG) {
+            const int64_t row = (int64_t)agg_node[first + t / BSR] * BSR + t % BSR;
+            const double v = B[row * K + j];
+            t_val[row * K + j] = v;
+            s = fma(v, v, s);
+        }
+        const double n0 = sqrt(amg_group_sum<LG>(s));
+        double racc[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) racc[i] = 0.0;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            double c[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) c[i] = 0.0;
+            for (int64_t t = lane; t < m; t += LG) {
+                const int64_t row = (int64_t)agg_node[first + t / BSR] * BSR + t % BSR;
+                const double v = t_val[row * K + j];
+#pragma unroll
+                for (int i = 0; i < j; ++i) c[i] = fma(t_val[row * K + i], v, c[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < j; ++i) {
+                c[i] = amg_group_sum<LG>(c[i]);
+                racc[i] += c[i];
+            }
+            for (int64_t t = lane; t < m; t += LG) {
+                const int64_t row = (int64_t)agg_node[first + t / BSR] * BSR + t % BSR;
+                double v = t_val[row * K + j];
+#pragma unroll
+                for (int i = 0; i < j; ++i) v = fma(-c[i], t_val[row * K + i], v);
+                t_val[row * K + j] = v;
+            }
+        }
+        s = 0.0;
+        for (int64_t t = lane; t < m; t += LG) {
+            const int64_t row = (int64_t)agg_node[first + t / BSR] * BSR + t % BSR;
+            const double v = t_val[row * K + j];
+            s = fma(v, v, s);
+        }
+        const double nv = sqrt(amg_group_sum<LG>(s));
+        const bool dead = n0 == 0.0 || !(nv > tol * n0);
+        n_dead += dead ? 1 : 0;
+        for (int64_t t = lane; t < m; t += LG) {
+            const int64_t row = (int64_t)agg_node[first + t / BSR] * BSR + t % BSR;
+            t_val[row * K + j] = dead ? 0.0 : t_val[row * K + j] / nv;
+        }
+        if (valid && lane == 0) {
+#pragma unroll
+            for (int i = 0; i < K; ++i) Bn[(a * K + i) * K + j] = i < j ? racc[i] : (i == j && !dead ? nv : 0.0);
+        }
+    }
+    if (valid && lane == 0) dead_a[a] = (uint8_t)n_dead;
+}
+
+// B of the rigid-body modes from node coordinates x [n_nodes][G]: the G translations, then (-y, x) or (-y, x, 0), (0, -z, y), (z, 0, -x)
+template <int G>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_rigid_body_modes(int64_t n_nodes, const double* __restrict__ x, double* __restrict__ B) {
+    constexpr int K = G == 2 ? 3 : 6;
+    const int64_t i = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (i >= n_nodes) return;
+    double p[G];
+#pragma unroll
+    for (int d = 0; d < G; ++d) p[d] = x[i * G + d];
+    double b[G][K];
+#pragma unroll
+    for (int d = 0; d < G; ++d)
+#pragma unroll
+        for (int c = 0; c < K; ++c) b[d][c] = d == c ? 1.0 : 0.0;
+    if constexpr (G == 2) {
+        b[0][2] = -p[1];
+        b[1][2] = p[0];
+    } else {
+        b[0][3] = -p[1];
+        b[1][3] = p[0];
+        b[1][4] = -p[2];
+        b[2][4] = p[1];
+        b[0][5] = p[2];
+        b[2][5] = -p[0];
+    }
+#pragma unroll
+    for (int d = 0; d < G; ++d)
+#pragma unroll
+        for (int c = 0; c < K; ++c) B[(i * G + d) * K + c] = b[d][c];
 }
 
 // ---- the dense coarsest level. W is [n][2 n] = [A | I]
@@ -449,59 +684,80 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_sweep(int64_t n_nodes, cons
 }
 
 // r_c[a] = sum over the blocks (i, a) of P, ascending i, of P_ia^T t_i
-template <int BS>
+template <int BSR, int BSC>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_restrict(int64_t n_agg, const int64_t* __restrict__ pt_ptr, const int64_t* __restrict__ pt_blk,
                                                               const int32_t* __restrict__ p_row, const double* __restrict__ p_val,
                                                               const double* __restrict__ t, double* __restrict__ rc) {
     const int64_t a = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
     if (a >= n_agg) return;
-    double acc[BS];
+    double acc[BSC];
 #pragma unroll
-    for (int c = 0; c < BS; ++c) acc[c] = 0.0;
+    for (int c = 0; c < BSC; ++c) acc[c] = 0.0;
     for (int64_t e = pt_ptr[a]; e < pt_ptr[a + 1]; ++e) {
         const int64_t pb = pt_blk[e];
         const int64_t i = p_row[pb];
 #pragma unroll
-        for (int q = 0; q < BS; ++q) {
-            const double tv = t[i * BS + q];
+        for (int q = 0; q < BSR; ++q) {
+            const double tv = t[i * BSR + q];
 #pragma unroll
-            for (int c = 0; c < BS; ++c) acc[c] = fma(p_val[pb * BS * BS + q * BS + c], tv, acc[c]);
+            for (int c = 0; c < BSC; ++c) acc[c] = fma(p_val[pb * BSR * BSC + q * BSC + c], tv, acc[c]);
         }
     }
 #pragma unroll
-    for (int c = 0; c < BS; ++c) rc[a * BS + c] = acc[c];
+    for (int c = 0; c < BSC; ++c) rc[a * BSC + c] = acc[c];
 }
 
 // x_i += sum over the blocks of row i of P, ascending aggregate, of P_ia xc_a
-template <int BS>
+template <int BSR, int BSC>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_prolong(int64_t n_nodes, const int64_t* __restrict__ p_ptr, const int32_t* __restrict__ p_col,
                                                              const double* __restrict__ p_val, const double* __restrict__ xc, double* __restrict__ x) {
     const int64_t i = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
     if (i >= n_nodes) return;
-    double acc[BS];
+    double acc[BSR];
 #pragma unroll
-    for (int r = 0; r < BS; ++r) acc[r] = 0.0;
+    for (int r = 0; r < BSR; ++r) acc[r] = 0.0;
     for (int64_t e = p_ptr[i]; e < p_ptr[i + 1]; ++e) {
         const int64_t a = p_col[e];
 #pragma unroll
-        for (int c = 0; c < BS; ++c) {
-            const double v = xc[a * BS + c];
+        for (int c = 0; c < BSC; ++c) {
+            const double v = xc[a * BSC + c];
 #pragma unroll
-            for (int r = 0; r < BS; ++r) acc[r] = fma(p_val[e * BS * BS + r * BS + c], v, acc[r]);
+            for (int r = 0; r < BSR; ++r) acc[r] = fma(p_val[e * BSR * BSC + r * BSC + c], v, acc[r]);
         }
     }
 #pragma unroll
-    for (int r = 0; r < BS; ++r) x[i * BS + r] += acc[r];
+    for (int r = 0; r < BSR; ++r) x[i * BSR + r] += acc[r];
 }
 
 // ---- host: launch helpers
+// a level shape without an instantiation is a defect of this file, not of the caller: the entry points admit (1..3) and the pairs below
+[[noreturn]] inline void amg_no_shape(int bsr, int bsc) {
+    fprintf(stderr, "amg.hip: no kernel instantiation for block sizes (%d, %d)\n", bsr, bsc);
+    std::abort();
+}
+
 inline dim3 amg_grid(int64_t items, int per_block = DXO_AMG_BLOCK) { return dim3((unsigned)std::max<int64_t>(1, (items + per_block - 1) / per_block)); }
 
 #define AMG_BS(bs, kernel, ...)                                               \
     do {                                                                      \
         if ((bs) == 1) hipLaunchKernelGGL(kernel<1>, __VA_ARGS__);            \
         else if ((bs) == 2) hipLaunchKernelGGL(kernel<2>, __VA_ARGS__);       \
-        else hipLaunchKernelGGL(kernel<3>, __VA_ARGS__);                      \
+        else if ((bs) == 3) hipLaunchKernelGGL(kernel<3>, __VA_ARGS__);       \
+        else if ((bs) == 6) hipLaunchKernelGGL(kernel<6>, __VA_ARGS__);       \
+        else amg_no_shape((bs), (bs));                                        \
+    } while (0)
+
+// (rows of the level, rows of the next): square without a near-null space, (2, 3) -> (3, 3) and (3, 6) -> (6, 6) with one
+#define AMG_PAIR(bsr, bsc, kernel, ...)                                                    \
+    do {                                                                                   \
+        const int pair_ = (bsr) * 8 + (bsc);                                               \
+        if (pair_ == 9) hipLaunchKernelGGL((kernel<1, 1>), __VA_ARGS__);                   \
+        else if (pair_ == 18) hipLaunchKernelGGL((kernel<2, 2>), __VA_ARGS__);             \
+        else if (pair_ == 27) hipLaunchKernelGGL((kernel<3, 3>), __VA_ARGS__);             \
+        else if (pair_ == 19) hipLaunchKernelGGL((kernel<2, 3>), __VA_ARGS__);             \
+        else if (pair_ == 30) hipLaunchKernelGGL((kernel<3, 6>), __VA_ARGS__);             \
+        else if (pair_ == 54) hipLaunchKernelGGL((kernel<6, 6>), __VA_ARGS__);             \
+        else amg_no_shape((bsr), (bsc));                                                   \
     } while (0)
 
 template <int BS, bool RESID>
@@ -519,7 +775,9 @@ template <bool RESID>
 void sweep_launch(int bs, const amg_level& v, const double* omega, const double* r, const double* x, double* out, hipStream_t s) {
     if (bs == 1) sweep_bs<1, RESID>(v, omega, r, x, out, s);
     else if (bs == 2) sweep_bs<2, RESID>(v, omega, r, x, out, s);
-    else sweep_bs<3, RESID>(v, omega, r, x, out, s);
+    else if (bs == 3) sweep_bs<3, RESID>(v, omega, r, x, out, s);
+    else if (bs == 6) sweep_bs<6, RESID>(v, omega, r, x, out, s);
+    else amg_no_shape(bs, bs);
 }
 
 template <int BS>
@@ -527,6 +785,41 @@ void rho_bs(const amg_level& v, double* part, hipStream_t s) {
     const dim3 b(DXO_AMG_BLOCK);
     if (v.lw == 8) hipLaunchKernelGGL((amg_rho<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.values, v.dinv, part);
     else hipLaunchKernelGGL((amg_rho<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.values, v.dinv, part);
+}
+
+#define AMG_P_ARGS amg_grid(v.p_blocks), dim3(DXO_AMG_BLOCK), 0, s, v.p_blocks, v.p_row, v.p_col, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, v.agg, v.mask, \
+                   v.t_val, omega, v.p_val
+void build_p_launch(const amg_level& v, bool nns, const double* omega, hipStream_t s) {
+    if (!nns) {
+        if (v.bs == 1) hipLaunchKernelGGL((amg_build_p<1, 1, false>), AMG_P_ARGS);
+        else if (v.bs == 2) hipLaunchKernelGGL((amg_build_p<2, 2, false>), AMG_P_ARGS);
+        else if (v.bs == 3) hipLaunchKernelGGL((amg_build_p<3, 3, false>), AMG_P_ARGS);
+        else amg_no_shape(v.bs, v.bsc);
+    } else if (v.bs == 2 && v.bsc == 3) hipLaunchKernelGGL((amg_build_p<2, 3, true>), AMG_P_ARGS);
+    else if (v.bs == 3 && v.bsc == 3) hipLaunchKernelGGL((amg_build_p<3, 3, true>), AMG_P_ARGS);
+    else if (v.bs == 3 && v.bsc == 6) hipLaunchKernelGGL((amg_build_p<3, 6, true>), AMG_P_ARGS);
+    else if (v.bs == 6 && v.bsc == 6) hipLaunchKernelGGL((amg_build_p<6, 6, true>), AMG_P_ARGS);
+    else amg_no_shape(v.bs, v.bsc);
+}
+#undef AMG_P_ARGS
+
+template <int BSR, int K>
+void tentative_bs(const amg_level& v, double* b_next, double tol, hipStream_t s) {
+    const dim3 b(DXO_AMG_BLOCK);
+#define AMG_T_ARGS(lg) amg_grid(v.n_agg, DXO_AMG_BLOCK / lg), b, 0, s, v.n_agg, v.agg_ptr, v.agg_node, v.b_val, tol, v.t_val, b_next, v.dead_a
+    if (v.tl == 8) hipLaunchKernelGGL((amg_tentative<BSR, K, 8>), AMG_T_ARGS(8));
+    else if (v.tl == 16) hipLaunchKernelGGL((amg_tentative<BSR, K, 16>), AMG_T_ARGS(16));
+    else if (v.tl == 32) hipLaunchKernelGGL((amg_tentative<BSR, K, 32>), AMG_T_ARGS(32));
+    else hipLaunchKernelGGL((amg_tentative<BSR, K, 64>), AMG_T_ARGS(64));
+#undef AMG_T_ARGS
+}
+
+void tentative_launch(const amg_level& v, double* b_next, double tol, hipStream_t s) {
+    if (v.bs == 2 && v.bsc == 3) tentative_bs<2, 3>(v, b_next, tol, s);
+    else if (v.bs == 3 && v.bsc == 3) tentative_bs<3, 3>(v, b_next, tol, s);
+    else if (v.bs == 3 && v.bsc == 6) tentative_bs<3, 6>(v, b_next, tol, s);
+    else if (v.bs == 6 && v.bsc == 6) tentative_bs<6, 6>(v, b_next, tol, s);
+    else amg_no_shape(v.bs, v.bsc);
 }
 
 int64_t rho_parts(const amg_level& v) { return std::max<int64_t>(1, (v.n_nodes + DXO_AMG_BLOCK / v.lw - 1) / (DXO_AMG_BLOCK / v.lw)); }
@@ -672,6 +965,7 @@ void rows_of(const HostGraph& g, int bs, std::vector<int64_t>& row_ptr, std::vec
 struct Uploader {
     dxo_ctx* ctx;
     dxo_amg* amg;
+    const char* who;                   // the entry point, for the error text
     int rc = DXO_OK;
     template <class T>
     T* alloc(size_t n) {
@@ -679,7 +973,7 @@ struct Uploader {
         void* p = nullptr;
         const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T) + 16);
         if (e != hipSuccess) {
-            rc = dxo_hip_fail(ctx, e, "dxo_amg_create: hipMalloc");
+            rc = dxo_hip_fail(ctx, e, (std::string(who) + ": hipMalloc").c_str());
             return nullptr;
         }
         amg->allocs.push_back(p);
@@ -690,7 +984,7 @@ struct Uploader {
         T* p = alloc<T>(v.size());
         if (p && !v.empty()) {
             const hipError_t e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-            if (e != hipSuccess) rc = dxo_hip_fail(ctx, e, "dxo_amg_create: hipMemcpy");
+            if (e != hipSuccess) rc = dxo_hip_fail(ctx, e, (std::string(who) + ": hipMemcpy").c_str());
         }
         return p;
     }
@@ -704,9 +998,30 @@ void amg_free(dxo_amg* a) {
 
 int lanes_for(int64_t nnzb, int64_t n_nodes) { return n_nodes > 0 && (double)nnzb / (double)n_nodes > 16.0 ? 32 : 8; }
 
-int amg_build(dxo_ctx* ctx, dxo_amg* amg, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, int max_levels, int coarse_rows) {
-    const int bs = csr->bs;
-    Uploader U{ctx, amg};
+// lanes per aggregate of amg_tentative from the mean number of rows of an aggregate
+int tentative_lanes(int64_t rows, int64_t n_agg) {
+    const double mean = n_agg > 0 ? (double)rows / (double)n_agg : 0.0;
+    return mean > 32.0 ? 64 : mean > 16.0 ? 32 : mean > 8.0 ? 16 : 8;
+}
+
+// the nodes of every aggregate, ascending
+void nodes_of_aggregates(const std::vector<int32_t>& agg, int64_t na, std::vector<int64_t>& ptr, std::vector<int32_t>& node) {
+    ptr.assign((size_t)na + 1, 0);
+    for (int32_t a : agg)
+        if (a >= 0) ++ptr[(size_t)a + 1];
+    for (int64_t a = 0; a < na; ++a) ptr[(size_t)a + 1] += ptr[(size_t)a];
+    node.resize((size_t)ptr.back());
+    std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
+    for (size_t i = 0; i < agg.size(); ++i)
+        if (agg[i] >= 0) node[(size_t)fill[(size_t)agg[i]]++] = (int32_t)i;
+}
+
+// k: columns of the near-null space (every coarse level then has block size k), 0: none (every level keeps the block size)
+int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, int max_levels,
+              int coarse_rows, int k) {
+    int bs = csr->bs;
+    const int bsc = k > 0 ? k : bs;
+    Uploader U{ctx, amg, who};
     std::vector<int64_t> row_ptr((size_t)csr->n_rows + 1);
     std::vector<int32_t> col((size_t)csr->nnz);
     DXO_HIP(ctx, hipMemcpy(row_ptr.data(), csr->d_row_ptr, row_ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -731,17 +1046,20 @@ int amg_build(dxo_ctx* ctx, dxo_amg* amg, const dxo_csr* csr, const int32_t* con
     lev.n_rows = csr->n_rows;
     lev.nnzb = (int64_t)g.nb.size();
     lev.mask = U.up(mask);
-    const int64_t nnzb0 = std::max<int64_t>(1, lev.nnzb);
+    lev.bs = bs;
+    lev.bsc = bsc;
+    if (k > 0) lev.b_val = U.alloc<double>((size_t)(lev.n_rows * k));
+    const int64_t nnzb0 = std::max<int64_t>(1, lev.nnzb * bs * bs);
     int64_t total = 0;
     for (;;) {
         lev.lw = lanes_for(lev.nnzb, lev.n_nodes);
-        total += lev.nnzb;
+        total += lev.nnzb * bs * bs;
         bool last = lev.n_rows <= coarse_rows || (int)amg->L.size() + 1 >= max_levels;
         std::vector<int32_t> agg;
         int64_t na = 0;
         if (!last) {
             na = aggregate(g, active, agg);
-            last = na == 0 || (double)(na * bs) > 0.8 * (double)lev.n_rows;
+            last = na == 0 || (double)(na * bsc) > 0.8 * (double)lev.n_rows;
         }
         lev.r = U.alloc<double>((size_t)lev.n_rows);
         lev.xa = U.alloc<double>((size_t)lev.n_rows);
@@ -768,33 +1086,46 @@ int amg_build(dxo_ctx* ctx, dxo_amg* amg, const dxo_csr* csr, const int32_t* con
         lev.ap_row = U.up(t.ap_row);
         lev.c_bptr = U.up(t.c_bptr);
         lev.c_row = U.up(t.c_row);
-        lev.p_val = U.alloc<double>((size_t)(lev.p_blocks * bs * bs));
-        lev.ap_val = U.alloc<double>((size_t)(lev.ap_blocks * bs * bs));
+        lev.p_val = U.alloc<double>((size_t)(lev.p_blocks * bs * bsc));
+        lev.ap_val = U.alloc<double>((size_t)(lev.ap_blocks * bs * bsc));
+        if (k > 0) {
+            std::vector<int64_t> aptr;
+            std::vector<int32_t> anode;
+            nodes_of_aggregates(agg, na, aptr, anode);
+            lev.tl = tentative_lanes((int64_t)anode.size() * bs, na);
+            lev.agg_ptr = U.up(aptr);
+            lev.agg_node = U.up(anode);
+            lev.t_val = U.alloc<double>((size_t)(lev.n_nodes * bs * k));
+            lev.dead_a = U.alloc<uint8_t>((size_t)na);
+        }
         amg->L.push_back(lev);
         // the coarse level: a dxo_csr without a mesh
         std::vector<int64_t> crp;
         std::vector<int32_t> ccol;
-        rows_of(t.coarse, bs, crp, ccol);
+        rows_of(t.coarse, bsc, crp, ccol);
         amg_level c;
         c.own = new dxo_csr;
-        c.own->bs = bs;
+        c.own->bs = bsc;
         c.own->n_nodes = na;
-        c.own->n_rows = na * bs;
+        c.own->n_rows = na * bsc;
         c.own->nnz = crp.back();
         c.own->d_row_ptr = U.up(crp);
         c.own->d_col = U.up(ccol);
         c.A = c.own;
         c.n_nodes = na;
-        c.n_rows = na * bs;
+        c.n_rows = na * bsc;
         c.nnzb = (int64_t)t.coarse.nb.size();
+        c.bs = c.bsc = bsc;
         double* cv = U.alloc<double>((size_t)c.own->nnz);
         c.values = cv;
-        c.mask = U.alloc<uint8_t>((size_t)c.n_rows);
+        if (k > 0) c.b_val = U.alloc<double>((size_t)(c.n_rows * k));      // T is fixed at creation: no values-dependent mask
+        else c.mask = U.alloc<uint8_t>((size_t)c.n_rows);
         if (U.rc != DXO_OK) {
             amg->L.push_back(c);       // owned: freed with the object
             return U.rc;
         }
         lev = c;
+        bs = bsc;
         g = std::move(t.coarse);
         active.assign((size_t)g.n, 1);
     }
@@ -803,7 +1134,7 @@ int amg_build(dxo_ctx* ctx, dxo_amg* amg, const dxo_csr* csr, const int32_t* con
     amg->nc = amg->L.back().n_rows;
     if (amg->nc > AMG_MAX_DENSE) {
         char msg[200];
-        snprintf(msg, sizeof msg, "dxo_amg_create: the coarsest level keeps %lld rows, the dense solve takes at most %lld (raise max_levels)",
+        snprintf(msg, sizeof msg, "%s: the coarsest level keeps %lld rows, the dense solve takes at most %lld (raise max_levels)", who,
                  (long long)amg->nc, (long long)AMG_MAX_DENSE);
         return dxo_fail(ctx, DXO_E_SIZE, msg);
     }
@@ -817,6 +1148,32 @@ int amg_build(dxo_ctx* ctx, dxo_amg* amg, const dxo_csr* csr, const int32_t* con
 }
 
 bool amg_misaligned(const void* p) { return ((uintptr_t)p & 7u) != 0; }
+
+// B_0 = the caller's B with the rows of constrained dofs zero, then level by level T_l and B_{l+1}; once, at creation
+int amg_near_nullspace(dxo_ctx* ctx, dxo_amg* amg, const double* B, hipStream_t s) {
+    const int k = amg->k, nl = (int)amg->L.size();
+    const double tol = std::pow(10.0, -(double)ctx->amg_rank_tol);
+    amg_level& f = amg->L[0];
+    if (f.n_rows > 0) {
+        DXO_HIP(ctx, hipMemcpyAsync(f.b_val, B, (size_t)(f.n_rows * k) * sizeof(double), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(amg_zero_rows, amg_grid(f.n_rows), dim3(DXO_AMG_BLOCK), 0, s, f.n_rows, k, f.mask, f.b_val);
+    }
+    for (int l = 0; l + 1 < nl; ++l) {
+        amg_level& v = amg->L[(size_t)l];
+        DXO_HIP(ctx, hipMemsetAsync(v.t_val, 0, (size_t)(v.n_nodes * v.bs * k) * sizeof(double), s));      // nodes without an aggregate
+        if (v.n_agg > 0) tentative_launch(v, amg->L[(size_t)l + 1].b_val, tol, s);
+    }
+    DXO_HIP(ctx, hipGetLastError());
+    DXO_HIP(ctx, hipStreamSynchronize(s));
+    for (int l = 0; l + 1 < nl; ++l) {
+        amg_level& v = amg->L[(size_t)l];
+        std::vector<uint8_t> d((size_t)v.n_agg);
+        if (v.n_agg > 0) DXO_HIP(ctx, hipMemcpy(d.data(), v.dead_a, d.size(), hipMemcpyDeviceToHost));
+        v.dead = 0;
+        for (uint8_t x : d) v.dead += x;
+    }
+    return DXO_OK;
+}
 
 }  // namespace
 
@@ -838,7 +1195,7 @@ int dxo_amg_pc_check(dxo_ctx* ctx, const char* who, const dxo_amg* amg, const dx
 
 void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipStream_t s) {
     (void)ctx;
-    const int bs = amg->bs, nl = (int)amg->L.size(), nu = amg->sweeps;
+    const int nl = (int)amg->L.size(), nu = amg->sweeps;
     const dim3 B(DXO_AMG_BLOCK);
     if (amg->L[0].n_rows == 0) return;
     for (int l = 0; l + 1 < nl; ++l) {
@@ -846,13 +1203,13 @@ void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipSt
         const double* rin = l == 0 ? r : v.r;
         const double* om = amg->omega + l;
         double *cur = v.xa, *other = v.xb;
-        AMG_BS(bs, amg_jacobi0, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.dinv, om, rin, cur);
+        AMG_BS(v.bs, amg_jacobi0, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.dinv, om, rin, cur);
         for (int k = 1; k < nu; ++k) {
-            sweep_launch<false>(bs, v, om, rin, cur, other, s);
+            sweep_launch<false>(v.bs, v, om, rin, cur, other, s);
             std::swap(cur, other);
         }
-        sweep_launch<true>(bs, v, om, rin, cur, v.t, s);
-        AMG_BS(bs, amg_restrict, amg_grid(v.n_agg), B, 0, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, v.p_val, v.t, amg->L[(size_t)l + 1].r);
+        sweep_launch<true>(v.bs, v, om, rin, cur, v.t, s);
+        AMG_PAIR(v.bs, v.bsc, amg_restrict, amg_grid(v.n_agg), B, 0, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, v.p_val, v.t, amg->L[(size_t)l + 1].r);
         v.cur = cur;
     }
     amg_level& c = amg->L.back();
@@ -869,10 +1226,10 @@ void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipSt
         const double* om = amg->omega + l;
         double* cur = v.cur;
         double* other = cur == v.xa ? v.xb : v.xa;
-        AMG_BS(bs, amg_prolong, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, amg->L[(size_t)l + 1].cur, cur);
+        AMG_PAIR(v.bs, v.bsc, amg_prolong, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, amg->L[(size_t)l + 1].cur, cur);
         for (int k = 0; k < nu; ++k) {
             double* out = (l == 0 && k == nu - 1) ? z : other;      // the last sweep of the fine level writes the result
-            sweep_launch<false>(bs, v, om, rin, cur, out, s);
+            sweep_launch<false>(v.bs, v, om, rin, cur, out, s);
             other = cur;
             cur = out;
         }
@@ -881,6 +1238,35 @@ void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipSt
 }
 
 // ---- C ABI
+namespace {
+
+// the symbolic phase and, with a near-null space (k > 0, B on the device), T and B of every level
+int amg_create(dxo_ctx* ctx, const char* who, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, const double* Bnns, int k,
+               int max_levels, int coarse_rows, int sweeps, dxo_amg** out) {
+    if (n_constrained < 0 || max_levels < 1 || coarse_rows < 1 || sweeps < 1)
+        return dxo_fail(ctx, DXO_E_SIZE, (std::string(who) + ": n_constrained < 0, or max_levels, coarse_rows or sweeps < 1").c_str());
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = dxo_launch_stream(ctx);
+    DXO_HIP(ctx, hipStreamSynchronize(s));      // the list may have been written on the stream
+    const auto t0 = std::chrono::steady_clock::now();
+    dxo_amg* a = new dxo_amg;
+    a->device = ctx->device;
+    a->bs = csr->bs;
+    a->sweeps = sweeps;
+    a->k = k;
+    int rc = amg_build(ctx, who, a, csr, constrained, n_constrained, max_levels, coarse_rows, k);
+    if (rc == DXO_OK && k > 0) rc = amg_near_nullspace(ctx, a, Bnns, s);
+    if (rc != DXO_OK) {
+        amg_free(a);
+        return rc;
+    }
+    a->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = a;
+    return DXO_OK;
+}
+
+}  // namespace
+
 extern "C" int dxo_amg_create(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, int max_levels, int coarse_rows,
                               int sweeps, dxo_amg** out) {
     if (!ctx || !out) return DXO_E_NULL;
@@ -888,22 +1274,49 @@ extern "C" int dxo_amg_create(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* c
     *out = nullptr;
     if (!csr || (n_constrained > 0 && !constrained)) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_create: NULL argument");
     if (csr->bs < 1 || csr->bs > 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create: bs must be 1, 2 or 3");
-    if (n_constrained < 0 || max_levels < 1 || coarse_rows < 1 || sweeps < 1)
-        return dxo_fail(ctx, DXO_E_SIZE, "dxo_amg_create: n_constrained < 0, or max_levels, coarse_rows or sweeps < 1");
+    return amg_create(ctx, "dxo_amg_create", csr, constrained, n_constrained, nullptr, 0, max_levels, coarse_rows, sweeps, out);
+}
+
+extern "C" int dxo_amg_create_nns(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, const double* B, int n_modes,
+                                  int max_levels, int coarse_rows, int sweeps, dxo_amg** out) {
+    if (!ctx || !out) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    *out = nullptr;
+    if (!csr || !B || (n_constrained > 0 && !constrained)) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_create_nns: NULL argument");
+    if (!((csr->bs == 2 && n_modes == 3) || (csr->bs == 3 && n_modes == 6)))
+        return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create_nns: (bs, n_modes) must be (2, 3) or (3, 6)");
+    if (amg_misaligned(B)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_amg_create_nns: B must be 8-byte aligned");
+    return amg_create(ctx, "dxo_amg_create_nns", csr, constrained, n_constrained, B, n_modes, max_levels, coarse_rows, sweeps, out);
+}
+
+extern "C" int dxo_rigid_body_modes(dxo_ctx* ctx, const double* x, int64_t n_nodes, int gdim, double* B) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!x || !B) return dxo_fail(ctx, DXO_E_NULL, "dxo_rigid_body_modes: NULL argument");
+    if (gdim != 2 && gdim != 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_rigid_body_modes: gdim must be 2 or 3");
+    if (n_nodes < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_rigid_body_modes: n_nodes < 0");
+    if (amg_misaligned(x) || amg_misaligned(B)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_rigid_body_modes: arrays must be 8-byte aligned");
+    if (n_nodes == 0) return DXO_OK;
+    hipStream_t s = dxo_launch_stream(ctx);
     DXO_HIP(ctx, hipSetDevice(ctx->device));
-    DXO_HIP(ctx, hipStreamSynchronize(dxo_launch_stream(ctx)));      // the list may have been written on the stream
-    const auto t0 = std::chrono::steady_clock::now();
-    dxo_amg* a = new dxo_amg;
-    a->device = ctx->device;
-    a->bs = csr->bs;
-    a->sweeps = sweeps;
-    const int rc = amg_build(ctx, a, csr, constrained, n_constrained, max_levels, coarse_rows);
-    if (rc != DXO_OK) {
-        amg_free(a);
-        return rc;
-    }
-    a->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *out = a;
+    int rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    if (gdim == 2) hipLaunchKernelGGL(amg_rigid_body_modes<2>, amg_grid(n_nodes), dim3(DXO_AMG_BLOCK), 0, s, n_nodes, x, B);
+    else hipLaunchKernelGGL(amg_rigid_body_modes<3>, amg_grid(n_nodes), dim3(DXO_AMG_BLOCK), 0, s, n_nodes, x, B);
+    return dxo_device_end(ctx, s);
+}
+
+extern "C" int dxo_amg_nns_info(dxo_ctx* ctx, const dxo_amg* amg, int level, int* bs, int* bs_coarse, int64_t* dead_columns, const double** t_val,
+                                const double** b_val) {
+    if (!amg) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (level < 0 || level >= (int)amg->L.size()) return dxo_fail(ctx, DXO_E_SIZE, "dxo_amg_nns_info: no such level");
+    const amg_level& v = amg->L[(size_t)level];
+    if (bs) *bs = v.bs;
+    if (bs_coarse) *bs_coarse = v.bsc;
+    if (dead_columns) *dead_columns = v.dead;
+    if (t_val) *t_val = v.t_val;
+    if (b_val) *b_val = v.b_val;
     return DXO_OK;
 }
 
@@ -924,7 +1337,8 @@ extern "C" int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values) {
     hipStream_t s = dxo_launch_stream(ctx);
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     amg->ready = false;
-    const int bs = amg->bs, nl = (int)amg->L.size();
+    const int nl = (int)amg->L.size();
+    const bool nns = amg->k > 0;
     const dim3 B(DXO_AMG_BLOCK);
     amg->L[0].values = values;
     int rc = dxo_device_begin(ctx, s);
@@ -934,19 +1348,23 @@ extern "C" int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values) {
         amg_level& v = amg->L[(size_t)l];
         amg_level& c = amg->L[(size_t)l + 1];
         if (v.n_nodes == 0) continue;
-        dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
+        const int bs = v.bs;
+        if (bs == 6) hipLaunchKernelGGL(amg_bj6, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, amg->flag);
+        else dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
         if (bs == 1) rho_bs<1>(v, amg->part, s);
         else if (bs == 2) rho_bs<2>(v, amg->part, s);
-        else rho_bs<3>(v, amg->part, s);
+        else if (bs == 3) rho_bs<3>(v, amg->part, s);
+        else if (bs == 6) rho_bs<6>(v, amg->part, s);
+        else amg_no_shape(bs, bs);
         hipLaunchKernelGGL(amg_omega, dim3(1), B, 0, s, amg->part, rho_parts(v), amg->omega + l);
-        AMG_BS(bs, amg_build_p, amg_grid(v.p_blocks), B, 0, s, v.p_blocks, v.p_row, v.p_col, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, v.agg, v.mask,
-               amg->omega + l, v.p_val);
-        AMG_BS(bs, amg_build_ap, amg_grid(v.ap_blocks), B, 0, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr, v.p_col,
-               v.p_val, v.ap_val);
+        build_p_launch(v, nns, amg->omega + l, s);
+        AMG_PAIR(bs, v.bsc, amg_build_ap, amg_grid(v.ap_blocks), B, 0, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr,
+                 v.p_col, v.p_val, v.ap_val);
         double* cv = const_cast<double*>(c.values);
-        AMG_BS(bs, amg_build_c, amg_grid(v.c_blocks), B, 0, s, v.c_blocks, v.c_row, v.c_bptr, c.A->d_row_ptr, c.A->d_col, v.pt_ptr, v.pt_blk, v.p_row,
-               v.p_val, v.ap_ptr, v.ap_col, v.ap_val, cv);
-        hipLaunchKernelGGL(amg_row_mask, amg_grid(c.n_rows), B, 0, s, c.n_rows, c.A->d_row_ptr, c.A->d_col, c.values, c.mask);
+        AMG_PAIR(bs, v.bsc, amg_build_c, amg_grid(v.c_blocks), B, 0, s, v.c_blocks, v.c_row, v.c_bptr, c.A->d_row_ptr, c.A->d_col, v.pt_ptr, v.pt_blk,
+                 v.p_row, v.p_val, v.ap_ptr, v.ap_col, v.ap_val, cv);
+        // the values-dependent mask belongs to the identity form of T; with a near-null space T is fixed at creation
+        if (!nns) hipLaunchKernelGGL(amg_row_mask, amg_grid(c.n_rows), B, 0, s, c.n_rows, c.A->d_row_ptr, c.A->d_col, c.values, c.mask);
     }
     const amg_level& c = amg->L.back();
     const int64_t n = amg->nc;

@@ -81,15 +81,43 @@ class BlockJacobi:
         return KrylovPc(PC_BLOCK_JACOBI, self.bs, self.n, C.c_void_p(self.inv.data_ptr()))
 
 
+def rigid_body_modes(x, ctx=None):
+    """The rigid-body modes of node coordinates x (n_nodes, gdim), a NumPy array or a tensor: a float64 CUDA tensor
+    (n_nodes * gdim, k), k = 3 in 2-D and 6 in 3-D (dxo_rigid_body_modes): the translations, then (-y, x), or (-y, x, 0), (0, -z, y),
+    (z, 0, -x). The near-null space of elasticity for DeviceCSR.amg(near_nullspace=...)."""
+    torch = _torch()
+    import numpy as np
+
+    if ctx is None:
+        from ._lib import default_context
+
+        ctx = default_context()
+    dev = torch.device("cuda", ctx.device)
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+    if x.dim() != 2 or x.shape[1] not in (2, 3):
+        raise ValueError("rigid_body_modes: x must have the shape (n_nodes, 2) or (n_nodes, 3)")
+    x = x.to(device=dev, dtype=torch.float64).contiguous()
+    n, g = int(x.shape[0]), int(x.shape[1])
+    B = torch.empty((n * g, 3 if g == 2 else 6), dtype=torch.float64, device=dev)
+    _use_current_stream(ctx)
+    ctx.check(ctx.lib.dxo_rigid_body_modes(ctx._h, C.c_void_p(x.data_ptr()), n, g, C.c_void_p(B.data_ptr())), "dxo_rigid_body_modes")
+    return B
+
+
 class AMG:
     """Smoothed-aggregation multigrid preconditioner of an assembled matrix (dxo_amg_*, csrc/amg.hip), applied as one V-cycle.
 
     The constructor runs the symbolic phase on the host (aggregates and the patterns of every level, once per pattern) and the first
     setup(). After the values of the matrix changed (a Newton iteration: the same DeviceCSR, or another on the same pattern) call
     setup() again; it runs on the device only. `constrained`: the dofs given to bilinear_assemble(bcs=...) (an int32 CUDA tensor,
-    or anything numpy converts), None for none. Pass it as M to gmres / cg (cg: symmetric positive definite A)."""
+    or anything numpy converts), None for none. Pass it as M to gmres / cg (cg: symmetric positive definite A).
 
-    def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1):
+    `near_nullspace`: a float64 CUDA tensor (n_rows, k), k = 3 for bs 2 and 6 for bs 3 (rigid_body_modes(x) for elasticity). The
+    tentative prolongator then carries these vectors, orthonormalised per aggregate, and every coarse level has block size k
+    (dxo_amg_create_nns); it is made once, here, and setup() leaves it alone."""
+
+    def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None):
         torch = _torch()
         import numpy as np
 
@@ -105,9 +133,24 @@ class AMG:
             bc = torch.from_numpy(np.ascontiguousarray(constrained, dtype=np.int32)).to(self.device)
         h = C.c_void_p()
         _use_current_stream(self.ctx)
-        rc = self.ctx.lib.dxo_amg_create(self.ctx._h, A.pattern._h, C.c_void_p(bc.data_ptr()) if bc.numel() else None, int(bc.numel()),
-                                         int(max_levels), int(coarse_rows), int(sweeps), C.byref(h))
-        self.ctx.check(rc, "dxo_amg_create")
+        bcp = C.c_void_p(bc.data_ptr()) if bc.numel() else None
+        self.n_modes = 0
+        if near_nullspace is None:
+            rc = self.ctx.lib.dxo_amg_create(self.ctx._h, A.pattern._h, bcp, int(bc.numel()), int(max_levels), int(coarse_rows), int(sweeps),
+                                             C.byref(h))
+            self.ctx.check(rc, "dxo_amg_create")
+        else:
+            B = near_nullspace
+            k = {2: 3, 3: 6}.get(self.bs)
+            if not (isinstance(B, torch.Tensor) and B.dtype == torch.float64 and B.is_cuda and B.device == self.device and B.dim() == 2
+                    and k is not None and tuple(B.shape) == (self.n, k)):
+                raise ValueError(f"AMG: near_nullspace must be a float64 CUDA tensor of shape ({self.n}, {k}) on {self.device} "
+                                 f"(bs 2: 3 vectors, bs 3: 6 vectors; this matrix has bs {self.bs})")
+            B = B.contiguous()
+            rc = self.ctx.lib.dxo_amg_create_nns(self.ctx._h, A.pattern._h, bcp, int(bc.numel()), C.c_void_p(B.data_ptr()), k, int(max_levels),
+                                                 int(coarse_rows), int(sweeps), C.byref(h))
+            self.ctx.check(rc, "dxo_amg_create_nns")
+            self.n_modes = k
         self._h = h
         self._fin = weakref.finalize(self, self.ctx.lib.dxo_amg_destroy, None, h)
         self._fin.atexit = False
@@ -161,15 +204,29 @@ class AMG:
         torch.cuda.current_stream(self.device).synchronize()
         return torch.as_tensor(_CudaArrayView(self, ptr, int(n), typestr), device=self.device).cpu().numpy().copy()
 
+    def _nns(self, level: int):
+        """(bs, bs_coarse, dead columns, T pointer, B pointer) of a level (dxo_amg_nns_info)."""
+        bs, bsc, dead, t, b = C.c_int(), C.c_int(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.dxo_amg_nns_info(self.ctx._h, self._h, int(level), C.byref(bs), C.byref(bsc), C.byref(dead), C.byref(t),
+                                                     C.byref(b)), "dxo_amg_nns_info")
+        return bs.value, bsc.value, dead.value, t.value, b.value
+
     @property
     def levels(self) -> list:
-        """Per level: rows, block nonzeros and omega (None on the coarsest level). Reading omega synchronises the stream."""
+        """Per level: rows, block nonzeros, the block size and omega (None on the coarsest level). Reading omega synchronises the
+        stream."""
         out = []
         for l in range(self.n_levels):
             i = self._info(l)
             om = float(self._array(i.omega, 1, "<f8")[0]) if i.omega else None
-            out.append({"rows": int(i.n_rows), "nodes": int(i.n_nodes), "block_nnz": int(i.nnz_blocks), "omega": om})
+            out.append({"rows": int(i.n_rows), "nodes": int(i.n_nodes), "block_nnz": int(i.nnz_blocks), "omega": om, "bs": self._nns(l)[0]})
         return out
+
+    @property
+    def dead_columns(self) -> list:
+        """Per level but the coarsest: the columns of the tentative prolongator that an aggregate could not carry (0 without a
+        near-null space)."""
+        return [self._nns(l)[2] for l in range(self.n_levels - 1)]
 
     def aggregates(self, level: int):
         """The aggregate of every node of `level` (-1: none), int32."""
@@ -188,26 +245,52 @@ class AMG:
                                        shape=(n_rows.value, n_rows.value))
 
     def level_dinv(self, level: int):
-        """The block-Jacobi inverses of `level`, (nodes, bs, bs)."""
+        """The block-Jacobi inverses of `level`, (nodes, bs, bs) with the level's block size."""
         i = self._info(level)
-        return self._array(i.dinv, i.n_nodes * self.bs * self.bs if i.dinv else 0, "<f8").reshape(-1, self.bs, self.bs)
+        bs = self._nns(level)[0]
+        return self._array(i.dinv, i.n_nodes * bs * bs if i.dinv else 0, "<f8").reshape(-1, bs, bs)
 
     def prolongator(self, level: int):
-        """P_level (rows of `level`, rows of `level + 1`) as a scipy.sparse.bsr_matrix with bs x bs blocks (explicit zeros kept)."""
+        """P_level (rows of `level`, rows of `level + 1`) as a scipy.sparse.bsr_matrix with bs x bs_coarse blocks (explicit zeros
+        kept)."""
         import scipy.sparse
 
         i = self._info(level)
         if not i.p_ptr:
             raise ValueError(f"AMG.prolongator: level {level} is the coarsest")
-        bs = self.bs
-        data = self._array(i.p_values, i.p_blocks * bs * bs, "<f8").reshape(-1, bs, bs)
+        bs, bsc = self._nns(level)[:2]
+        data = self._array(i.p_values, i.p_blocks * bs * bsc, "<f8").reshape(-1, bs, bsc)
         return scipy.sparse.bsr_matrix((data, self._array(i.p_col, i.p_blocks, "<i4"), self._array(i.p_ptr, i.n_nodes + 1, "<i8")),
-                                       shape=(i.n_rows, i.n_aggregates * bs))
+                                       shape=(i.n_rows, i.n_aggregates * bsc))
 
     def ap_pattern(self, level: int):
         """(indptr, indices) of the block pattern of A_level P_level."""
         i = self._info(level)
         return self._array(i.ap_ptr, i.n_nodes + 1 if i.ap_ptr else 0, "<i8"), self._array(i.ap_col, i.ap_blocks, "<i4")
+
+    def tentative(self, level: int):
+        """T_level of a hierarchy with a near-null space as a scipy.sparse.csr_matrix (rows of `level`, rows of `level + 1`): the
+        bs x k block of every node in the block column of its aggregate (explicit zeros kept)."""
+        import numpy as np
+        import scipy.sparse
+
+        i = self._info(level)
+        bs, bsc, _, t, _ = self._nns(level)
+        if not t:
+            raise ValueError(f"AMG.tentative: level {level} is the coarsest, or the hierarchy has no near-null space")
+        agg = self.aggregates(level)
+        on = np.flatnonzero(agg >= 0)
+        data = self._array(t, i.n_nodes * bs * bsc, "<f8").reshape(-1, bs, bsc)
+        ptr = np.concatenate([[0], np.cumsum(agg >= 0)])
+        return scipy.sparse.bsr_matrix((data[on], agg[on], ptr), shape=(i.n_rows, i.n_aggregates * bsc)).tocsr()
+
+    def near_nullspace(self, level: int):
+        """B_level (rows of `level`, k) of a hierarchy with a near-null space (level 0: the given one, rows of constrained dofs zero)."""
+        i = self._info(level)
+        b = self._nns(level)[4]
+        if not b:
+            raise ValueError("AMG.near_nullspace: the hierarchy has no near-null space")
+        return self._array(b, i.n_rows * self.n_modes, "<f8").reshape(-1, self.n_modes)
 
 
 def csr_matvec(A, x, y=None, alpha: float = 1.0, beta: float = 0.0):
@@ -342,4 +425,4 @@ def cg(A, b, x=None, M=None, rtol: float = 1e-10, atol: float = 0.0, maxiter: in
     return _solve("dxo_krylov_cg", A, b, x, M, 1, rtol, atol, maxiter, check_every, ctx)
 
 
-__all__ = ["AMG", "BlockJacobi", "KrylovResult", "cg", "csr_matvec", "gmres"]
+__all__ = ["AMG", "BlockJacobi", "KrylovResult", "cg", "csr_matvec", "gmres", "rigid_body_modes"]

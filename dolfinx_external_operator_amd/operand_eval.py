@@ -531,12 +531,14 @@ class DeviceCSR:
 
         return BlockJacobi.from_csr(self)
 
-    def amg(self, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1) -> "AMG":
+    def amg(self, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None) -> "AMG":
         """A smoothed-aggregation multigrid preconditioner of this matrix (krylov.AMG: the symbolic phase and the first setup), for
-        krylov.gmres / krylov.cg. `constrained`: the dofs given as bcs to bilinear_assemble. After the values changed: `.setup()`."""
+        krylov.gmres / krylov.cg. `constrained`: the dofs given as bcs to bilinear_assemble. `near_nullspace`: a float64 CUDA tensor
+        (n_rows, k), e.g. krylov.rigid_body_modes(x) for elasticity (k = 3 for bs 2, 6 for bs 3). After the values changed:
+        `.setup()`."""
         from .krylov import AMG
 
-        return AMG(self, constrained, max_levels, coarse_rows, sweeps)
+        return AMG(self, constrained, max_levels, coarse_rows, sweeps, near_nullspace)
 
 
 class DeviceOperand:

@@ -660,7 +660,27 @@ int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const d
  *                   DXO_E_OPTION.
  * dxo_amg_info    : counts and the DEVICE arrays of one level (any pointer may be NULL; `level` outside [0, n_levels): DXO_E_SIZE).
  * In dxo_krylov_gmres / dxo_krylov_cg: kind DXO_PC_AMG, inv = (const double*)amg, bs and n those of the matrix; an object made for a
- * pattern of another size is DXO_E_SIZE, of another block size DXO_E_DIM, one without a setup DXO_E_OPTION. */
+ * pattern of another size is DXO_E_SIZE, of another block size DXO_E_DIM, one without a setup DXO_E_OPTION.
+ *
+ * With a near-null space (elasticity: the rigid-body modes) the coarse spaces carry rotations as well as translations:
+ * dxo_rigid_body_modes : B [n_nodes * gdim][k] from node coordinates x [n_nodes][gdim] (both DEVICE), k = 3 for gdim 2, 6 for gdim 3:
+ *                   the gdim translations, then (-y, x) in 2-D and (-y, x, 0), (0, -z, y), (z, 0, -x) in 3-D. The coordinates are
+ *                   used as given. gdim outside 2..3: DXO_E_DIM. Capture-safe.
+ * dxo_amg_create_nns : dxo_amg_create with the near-null space B [n_rows][n_modes] (DEVICE, copied); (bs, n_modes) must be (2, 3) or
+ *                   (3, 6): DXO_E_DIM otherwise; B not 8-byte aligned: DXO_E_ALIGN. Non-finite entries are the caller's problem. The
+ *                   rows of B of constrained dofs are set to zero. The aggregates and all block patterns are those of
+ *                   dxo_amg_create. Per level and aggregate the rows of B of its nodes (ascending) are orthonormalised on the
+ *                   device (Gram-Schmidt in column order with a second pass); the Q factors are the blocks of the tentative
+ *                   prolongator T (bs_l x n_modes per node), the R factors the B of the next level. A column that keeps no more
+ *                   than 10^-n of its norm (option "amg_rank_tol" = n, default 10) is dead: its column of Q and its row of the next
+ *                   B are zero, its coarse diagonal entry becomes 1. Every coarse level has block size n_modes; the coarsening
+ *                   stops when a level would keep more than 0.8 of its parent's rows (n_aggregates * n_modes rows). T and B are
+ *                   made once, here; dxo_amg_setup, dxo_amg_apply and dxo_amg_destroy are used as before and have the same
+ *                   properties. In dxo_amg_level_info n_rows, nnz_blocks, dinv and p_values describe a level with its own block
+ *                   size: dinv [n_nodes][bs_l][bs_l], p_values [p_blocks][bs_l][bs_coarse].
+ * dxo_amg_nns_info : the block size of `level` and of the next one, the dead columns of its T, and the DEVICE arrays T
+ *                   [n_nodes][bs][bs_coarse] (NULL on the coarsest level) and B [n_rows][n_modes]; any pointer may be NULL. On an
+ *                   object of dxo_amg_create: bs_coarse = bs, 0 dead columns, NULL arrays. */
 typedef struct dxo_amg dxo_amg;
 typedef struct dxo_amg_level_info {
     int64_t n_rows, n_nodes;       /* of A_l                                              */
@@ -686,6 +706,11 @@ int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values);
 int dxo_amg_apply(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z);
 int dxo_amg_info(dxo_ctx* ctx, const dxo_amg* amg, int* n_levels, double* build_ms, double* operator_complexity, int level,
                  dxo_amg_level_info* out);
+int dxo_rigid_body_modes(dxo_ctx* ctx, const double* x, int64_t n_nodes, int gdim, double* B);
+int dxo_amg_create_nns(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, const double* B, int n_modes,
+                       int max_levels, int coarse_rows, int sweeps, dxo_amg** out);
+int dxo_amg_nns_info(dxo_ctx* ctx, const dxo_amg* amg, int level, int* bs, int* bs_coarse, int64_t* dead_columns, const double** t_val,
+                     const double** b_val);
 
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Standalone timing of the multigrid preconditioner (csrc/amg.hip; not a bench.py leg).
-    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE]
+    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm]
 Systems (distorted meshes, the lower side clamped so that the matrices are regular):
   p2       ("grad", "grad", 2) on P2 triangles with C = I + 0.3 N(0, 1) per point (1291 per side: 10^7 points), as tools/bench_krylov.py
   q2hex    ("eps", "eps", 3) on Q2 hexahedra (40^3 boxes), the same kind of C
@@ -8,6 +8,8 @@ Systems (distorted meshes, the lower side clamped so that the matrices are regul
 Per system: dxo_csr_spmv ms, dxo_bilinear_assemble ms, the symbolic phase (host, once), dxo_amg_setup ms, dxo_amg_apply ms and its ratio
 to one SpMV beside the model 2 + 3 (c - 1) (c the operator complexity), rows per level, and one GMRES(30) solve to rtol 1e-8 (at most
 `maxiter` iterations) with block Jacobi and with the cycle (iterations, ms; the cycle's total adds one setup).
+--rbm adds, for the two elasticity-type systems and an ("eps", "eps", 2) system p2eps on the p2 mesh, the same figures for the hierarchy
+with the rigid-body modes as near-null space (keys ending in _rbm; symbolic_ms_rbm includes the tentative prolongators).
 Timing: warm-up, then 5 batches timed with HIP events on the launch stream, the MEDIAN batch reported (tools/bench_krylov._batches).
 Prints one JSON line."""
 from __future__ import annotations
@@ -21,11 +23,11 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 
-def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000) -> dict:
+def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000, rbm: bool = False) -> dict:
     import numpy as np
     import torch
 
-    from dolfinx_external_operator_amd import Context, DeviceMesh, gmres
+    from dolfinx_external_operator_amd import Context, DeviceMesh, gmres, rigid_body_modes
     from tools.bench_krylov import _batches
     from tools.synthetic import structured_mesh
 
@@ -72,6 +74,19 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                                             "ms": round(out.ms, 2)}
                 r["gmres30_amg"]["ms_with_setup"] = round(r["gmres30_amg"]["ms"] + r["setup_ms"], 2)
                 amg.close()
+                if rbm and bs == m.gdim:
+                    amg = A.amg(bcs, near_nullspace=rigid_body_modes(m.node_x, ctx=ctx))
+                    r["symbolic_ms_rbm"] = round(amg.build_ms, 1)
+                    r["setup_ms_rbm"] = timed(lambda: amg.setup(), 3)
+                    r["apply_ms_rbm"] = timed(lambda: amg.apply(x, y), 20)
+                    r["levels_rbm"] = amg.levels
+                    r["dead_columns_rbm"] = amg.dead_columns
+                    r["operator_complexity_rbm"] = round(amg.operator_complexity, 4)
+                    gmres(A, b, M=amg, rtol=1e-8, maxiter=30)
+                    out = gmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
+                    r["gmres30_amg_rbm"] = {"iterations": out.iterations, "converged": out.converged, "residual": out.residual,
+                                            "ms": round(out.ms, 2), "ms_with_setup": round(out.ms + r["setup_ms_rbm"], 2)}
+                    amg.close()
             stream.synchronize()
             res["systems"][tag] = r
             print(tag, json.dumps(r), file=sys.stderr, flush=True)
@@ -93,8 +108,10 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
         Cb[:, 0, 1] = Cb[:, 1, 2] = 1.0 + 0.5 * np.random.Generator(np.random.PCG64(0)).random(npts)
         bnd = np.flatnonzero((m.node_x.min(axis=1) < 1e-12) | (m.node_x.max(axis=1) > 1 - 1e-12))
         system(f"heat_{n}", m, "grad", "value_grad", 1, torch.from_numpy(Cb.reshape(-1)).to(dev), bnd)
-    for tag, cell, n, test, trial, bs in (("p2", "triangle", (n_side, n_side), "grad", "grad", 2),
-                                          ("q2hex", "hexahedron", (n_hex, n_hex, n_hex), "eps", "eps", 3)):
+    cases = [("p2", "triangle", (n_side, n_side), "grad", "grad", 2), ("q2hex", "hexahedron", (n_hex, n_hex, n_hex), "eps", "eps", 3)]
+    if rbm:
+        cases.append(("p2eps", "triangle", (n_side, n_side), "eps", "eps", 2))
+    for tag, cell, n, test, trial, bs in cases:
         if n[0] <= 0:
             continue
         m = structured_mesh(cell, n, 2, distort=0.2, seed=0)
@@ -115,7 +132,10 @@ if __name__ == "__main__":
         i = args.index("--out")
         out_file = args[i + 1]
         del args[i:i + 2]
-    r = main(*(int(a) for a in args))
+    rbm = "--rbm" in args
+    if rbm:
+        args.remove("--rbm")
+    r = main(*(int(a) for a in args), rbm=rbm)
     line = json.dumps(r)
     print(line)
     if out_file:
