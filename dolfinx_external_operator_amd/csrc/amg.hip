@@ -28,6 +28,14 @@
 // of P, A P, P^T A P, restriction and prolongation take <BSR, BSC> (rows of the level, rows of the next), and the levels of block
 // size 6 invert their diagonal blocks by Gauss-Jordan with partial pivoting in registers (rows exchanged by compare-and-select).
 // T and B depend on B_0, the aggregates and the constraints alone: dxo_amg_setup does not touch them.
+//
+// The relaxation (dxo_amg_set_smoother; the default is what is described above). rho from the power iteration: amg_power_init writes
+// the fixed start vector, amg_power_step forms w = Dinv (A (s v)) in the shape of amg_sweep together with the workgroup's partial of
+// |w|^2, and the one-workgroup amg_power_norm adds the partials in a fixed order and leaves s = 1 / |w| on the device for the next step;
+// after the last step it stores rho = safety |w|, omega = (4/3) / rho and the level's Chebyshev pairs. The vectors are xa and xb of the
+// level, free during a setup; the setup still waits once, at its end. Chebyshev smoothing: amg_cheby0 (the first step from x = 0, no
+// SpMV) and amg_cheby_sweep (d = c1 d + c2 Dinv (r - A x), x_out = x + d; d in place, x between xa and xb as the Jacobi sweeps) with
+// the pairs (c1, c2) read from the device like omega; the post-smoothing is the same polynomial started from the corrected x.
 #include "krylov_internal.h"
 
 #include <algorithm>
@@ -43,6 +51,8 @@
 namespace {
 
 constexpr int64_t AMG_MAX_DENSE = 4096;
+constexpr int AMG_MAX_DEGREE = 8;
+constexpr int AMG_CHEB_STRIDE = 2 * AMG_MAX_DEGREE;
 
 struct amg_level {
     const dxo_csr* A = nullptr;        // pattern (level 0: the caller's, coarser: own)
@@ -67,6 +77,7 @@ struct amg_level {
     int32_t* c_row = nullptr;          // [c_blocks] coarse node of a block
     // vectors [n_rows]
     double *r = nullptr, *xa = nullptr, *xb = nullptr, *t = nullptr;
+    double* d = nullptr;               // the Chebyshev direction (absent on the coarsest)
     double* cur = nullptr;             // the iterate of the running cycle
     // near-null space path only
     double* b_val = nullptr;           // [n_rows][k] B of this level
@@ -93,6 +104,12 @@ struct dxo_amg {
     bool ready = false;
     double build_ms = 0.0, complexity = 1.0;
     int k = 0;                         // columns of the near-null space; 0: none (an identity per node)
+    // the relaxation (dxo_amg_set_smoother)
+    int smooth_kind = DXO_AMG_SMOOTH_JACOBI, degree = 1, rho_kind = DXO_AMG_RHO_INF_NORM, rho_iters = 10;
+    double lower = 0.1, safety = 1.1;
+    double* rho = nullptr;             // [levels] the estimate omega was made from
+    double* cheb = nullptr;            // [levels][AMG_CHEB_STRIDE] the pairs (c1, c2) of the Chebyshev steps
+    double* scal = nullptr;            // power iteration: [0] 1 / |w|, the scale of the next step, [1] |w|
 };
 
 namespace {
@@ -174,8 +191,9 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_rho(int64_t n_nodes, const 
     }
 }
 
-// one workgroup: omega = (4/3) / max(part)
-__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_omega(const double* __restrict__ part, int64_t n, double* __restrict__ omega) {
+// one workgroup: rho = max(part), omega = (4/3) / rho
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_omega(const double* __restrict__ part, int64_t n, double* __restrict__ omega,
+                                                           double* __restrict__ rho) {
     __shared__ double lds[DXO_AMG_BLOCK / 64];
     double m = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += DXO_AMG_BLOCK) m = fmax(m, part[i]);
@@ -185,8 +203,129 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_omega(const double* __restr
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int k = 1; k < DXO_AMG_BLOCK / 64; ++k) m = fmax(m, lds[k]);
+        rho[0] = m;
         omega[0] = m > 0.0 ? (4.0 / 3.0) / m : 0.0;
     }
+}
+
+// ---- rho by power iteration on Dinv A, and the Chebyshev coefficients
+// the sum of s over the workgroup, on every thread: the xor-butterfly of a wave, then the waves in ascending order
+__device__ __forceinline__ double amg_block_sum(double s, double* lds) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    double t = lds[0];
+    for (int k = 1; k < DXO_AMG_BLOCK / 64; ++k) t += lds[k];
+    return t;
+}
+
+// the start vector, the same on every level and exact in fp64: v[i] = 0.5 + ((uint32)(i * 2654435761) >> 8) * 2^-24, and the
+// workgroup's partial of |v|^2
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_init(int64_t n_rows, double* __restrict__ v, double* __restrict__ part) {
+    __shared__ double lds[DXO_AMG_BLOCK / 64];
+    const int64_t row = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    double q = 0.0;
+    if (row < n_rows) {
+        const double x = 0.5 + (double)(((uint32_t)row * 2654435761u) >> 8) * 0x1p-24;
+        v[row] = x;
+        q = x * x;
+    }
+    q = amg_block_sum(q, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = q;
+}
+
+// w = Dinv (A (s v)) with s = scal[0], in the lane-group shape of amg_sweep, and the workgroup's partial of |w|^2
+template <int BS, int LW>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_step(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                                const double* __restrict__ values, const double* __restrict__ dinv,
+                                                                const double* __restrict__ scal, const double* __restrict__ v,
+                                                                double* __restrict__ w, double* __restrict__ part) {
+    __shared__ double lds[DXO_AMG_BLOCK / 64];
+    constexpr int NPB = DXO_AMG_BLOCK / LW;
+    const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
+    const int lane = threadIdx.x % LW;
+    const double sc = scal[0];
+    double acc[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+    if (node < n_nodes) {
+        const NodeRow<BS> R(row_ptr, node);
+        for (int k = lane; k < R.nnb; k += LW) {
+            const int64_t c = col[R.r0 + (int64_t)k * BS];
+            double xb[BS];
+#pragma unroll
+            for (int j = 0; j < BS; ++j) xb[j] = sc * v[c + j];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) {
+                const double* a = values + R.r0 + i * R.len + (int64_t)k * BS;
+#pragma unroll
+                for (int j = 0; j < BS; ++j) acc[i] = fma(a[j], xb[j], acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = LW / 2; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    double q = 0.0;
+    if (node < n_nodes && lane == 0) {
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], acc[j], s);
+            w[node * BS + i] = s;
+            q = fma(s, s, q);
+        }
+    }
+    q = amg_block_sum(q, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = q;
+}
+
+// the pairs (c1, c2) of the steps d = c1 d + c2 Dinv (r - A x), x += d of the Chebyshev polynomial of the given degree on
+// [lower rho, rho]; the first step has c1 = 0. rho == 0: no relaxation, as omega = 0
+__device__ __forceinline__ void amg_cheby_table(double rho, double lower, int degree, double* __restrict__ c) {
+    if (!(rho > 0.0)) {
+        for (int k = 0; k < 2 * degree; ++k) c[k] = 0.0;
+        return;
+    }
+    const double a = lower * rho, theta = 0.5 * (a + rho), delta = 0.5 * (rho - a), sigma = theta / delta;
+    double r0 = 1.0 / sigma;
+    c[0] = 0.0;
+    c[1] = 1.0 / theta;
+    for (int k = 1; k < degree; ++k) {
+        const double r1 = 1.0 / (2.0 * sigma - r0);
+        c[2 * k] = r1 * r0;
+        c[2 * k + 1] = 2.0 * r1 / delta;
+        r0 = r1;
+    }
+}
+
+// one workgroup: |w| from the n partials (a thread's partials in ascending order, then amg_block_sum); scal = (1 / |w|, |w|) for
+// the next step. After the last step rho = safety |w|, omega = (4/3) / rho and the Chebyshev pairs
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_norm(const double* __restrict__ part, int64_t n, int last, double safety, double lower,
+                                                                int degree, double* __restrict__ scal, double* __restrict__ rho,
+                                                                double* __restrict__ omega, double* __restrict__ cheb) {
+    __shared__ double lds[DXO_AMG_BLOCK / 64];
+    double q = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += DXO_AMG_BLOCK) q += part[i];
+    q = amg_block_sum(q, lds);
+    if (threadIdx.x != 0) return;
+    const double lam = sqrt(q);
+    scal[0] = lam > 0.0 ? 1.0 / lam : 0.0;
+    scal[1] = lam;
+    if (last) {
+        const double r = safety * lam;
+        rho[0] = r;
+        omega[0] = r > 0.0 ? (4.0 / 3.0) / r : 0.0;
+        amg_cheby_table(r, lower, degree, cheb);
+    }
+}
+
+// the Chebyshev pairs from the rho of amg_omega (Chebyshev smoothing on the interval of the infinity norm)
+__global__ void amg_cheby_coeffs(const double* __restrict__ rho, double lower, int degree, double* __restrict__ cheb) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) amg_cheby_table(rho[0], lower, degree, cheb);
 }
 
 // coarse levels: a dof whose row has no nonzero off-diagonal entry takes no part in the tentative prolongator
@@ -683,6 +822,77 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_sweep(int64_t n_nodes, cons
     }
 }
 
+// d = c2 Dinv r, x = d with (c1, c2) = c[0..1]: the first Chebyshev step of the pre-smoothing, from x = 0
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_cheby0(int64_t n_nodes, const double* __restrict__ dinv, const double* __restrict__ c,
+                                                            const double* __restrict__ r, double* __restrict__ d, double* __restrict__ x) {
+    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (node >= n_nodes) return;
+    const double c2 = c[1];
+    double rb[BS];
+#pragma unroll
+    for (int j = 0; j < BS; ++j) rb[j] = r[node * BS + j];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], rb[j], s);
+        const double dn = c2 * s;
+        d[node * BS + i] = dn;
+        x[node * BS + i] = dn;
+    }
+}
+
+// d = c1 d + c2 Dinv (r - A x), out = x + d with (c1, c2) = c[0..1], in the lane-group shape of amg_sweep. d is updated in place: a
+// node's entries are touched by its own lane 0 only. With c1 == 0 (the first step of the post-smoothing) d is not read. out may be r,
+// as in amg_sweep.
+template <int BS, int LW>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_cheby_sweep(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                                 const double* __restrict__ values, const double* __restrict__ dinv,
+                                                                 const double* __restrict__ c, const double* r, const double* __restrict__ x,
+                                                                 double* __restrict__ d, double* out) {
+    constexpr int NPB = DXO_AMG_BLOCK / LW;
+    const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
+    const int lane = threadIdx.x % LW;
+    double acc[BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+    if (node < n_nodes) {
+        const NodeRow<BS> R(row_ptr, node);
+        for (int k = lane; k < R.nnb; k += LW) {
+            const int64_t cb = col[R.r0 + (int64_t)k * BS];
+            double xb[BS];
+#pragma unroll
+            for (int j = 0; j < BS; ++j) xb[j] = x[cb + j];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) {
+                const double* v = values + R.r0 + i * R.len + (int64_t)k * BS;
+#pragma unroll
+                for (int j = 0; j < BS; ++j) acc[i] = fma(v[j], xb[j], acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = LW / 2; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    if (node < n_nodes && lane == 0) {
+        const double c1 = c[0], c2 = c[1];
+        double res[BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) res[i] = r[node * BS + i] - acc[i];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], res[j], s);
+            const double dn = fma(c2, s, c1 != 0.0 ? c1 * d[node * BS + i] : 0.0);
+            d[node * BS + i] = dn;
+            out[node * BS + i] = x[node * BS + i] + dn;
+        }
+    }
+}
+
 // r_c[a] = sum over the blocks (i, a) of P, ascending i, of P_ia^T t_i
 template <int BSR, int BSC>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_restrict(int64_t n_agg, const int64_t* __restrict__ pt_ptr, const int64_t* __restrict__ pt_blk,
@@ -781,6 +991,36 @@ void sweep_launch(int bs, const amg_level& v, const double* omega, const double*
 }
 
 template <int BS>
+void cheby_bs(const amg_level& v, const double* c, const double* r, const double* x, double* out, hipStream_t s) {
+    const dim3 b(DXO_AMG_BLOCK);
+    if (v.lw == 8)
+        hipLaunchKernelGGL((amg_cheby_sweep<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv,
+                           c, r, x, v.d, out);
+    else
+        hipLaunchKernelGGL((amg_cheby_sweep<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values,
+                           v.dinv, c, r, x, v.d, out);
+}
+
+void cheby_launch(const amg_level& v, const double* c, const double* r, const double* x, double* out, hipStream_t s) {
+    if (v.bs == 1) cheby_bs<1>(v, c, r, x, out, s);
+    else if (v.bs == 2) cheby_bs<2>(v, c, r, x, out, s);
+    else if (v.bs == 3) cheby_bs<3>(v, c, r, x, out, s);
+    else if (v.bs == 6) cheby_bs<6>(v, c, r, x, out, s);
+    else amg_no_shape(v.bs, v.bs);
+}
+
+template <int BS>
+void power_bs(const amg_level& v, const double* scal, const double* x, double* w, double* part, hipStream_t s) {
+    const dim3 b(DXO_AMG_BLOCK);
+    if (v.lw == 8)
+        hipLaunchKernelGGL((amg_power_step<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv,
+                           scal, x, w, part);
+    else
+        hipLaunchKernelGGL((amg_power_step<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values,
+                           v.dinv, scal, x, w, part);
+}
+
+template <int BS>
 void rho_bs(const amg_level& v, double* part, hipStream_t s) {
     const dim3 b(DXO_AMG_BLOCK);
     if (v.lw == 8) hipLaunchKernelGGL((amg_rho<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.values, v.dinv, part);
@@ -823,6 +1063,7 @@ void tentative_launch(const amg_level& v, double* b_next, double tol, hipStream_
 }
 
 int64_t rho_parts(const amg_level& v) { return std::max<int64_t>(1, (v.n_nodes + DXO_AMG_BLOCK / v.lw - 1) / (DXO_AMG_BLOCK / v.lw)); }
+int64_t init_parts(const amg_level& v) { return std::max<int64_t>(1, (v.n_rows + DXO_AMG_BLOCK - 1) / DXO_AMG_BLOCK); }
 
 // ---- host: the symbolic phase
 struct HostGraph {                      // node graph of a block pattern: sorted neighbours, the node itself included
@@ -1069,6 +1310,7 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
         }
         lev.xb = U.alloc<double>((size_t)lev.n_rows);
         lev.t = U.alloc<double>((size_t)lev.n_rows);
+        lev.d = U.alloc<double>((size_t)lev.n_rows);
         lev.dinv = U.alloc<double>((size_t)(lev.n_nodes * bs * bs));
         HostTransfer t = transfer_of(g, agg, na);
         lev.n_agg = na;
@@ -1138,8 +1380,11 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
                  (long long)amg->nc, (long long)AMG_MAX_DENSE);
         return dxo_fail(ctx, DXO_E_SIZE, msg);
     }
-    for (const amg_level& v : amg->L) amg->part_cap = std::max(amg->part_cap, rho_parts(v));
+    for (const amg_level& v : amg->L) amg->part_cap = std::max({amg->part_cap, rho_parts(v), init_parts(v)});
     amg->omega = U.alloc<double>(amg->L.size());
+    amg->rho = U.alloc<double>(amg->L.size());
+    amg->cheb = U.alloc<double>(amg->L.size() * AMG_CHEB_STRIDE);
+    amg->scal = U.alloc<double>(2);
     amg->part = U.alloc<double>((size_t)amg->part_cap);
     amg->flag = U.alloc<int>(4);
     amg->dense[0] = U.alloc<double>((size_t)(2 * amg->nc * amg->nc));
@@ -1195,17 +1440,21 @@ int dxo_amg_pc_check(dxo_ctx* ctx, const char* who, const dxo_amg* amg, const dx
 
 void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipStream_t s) {
     (void)ctx;
-    const int nl = (int)amg->L.size(), nu = amg->sweeps;
+    const bool cheby = amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV;
+    const int nl = (int)amg->L.size(), nu = cheby ? amg->degree : amg->sweeps;
     const dim3 B(DXO_AMG_BLOCK);
     if (amg->L[0].n_rows == 0) return;
     for (int l = 0; l + 1 < nl; ++l) {
         amg_level& v = amg->L[(size_t)l];
         const double* rin = l == 0 ? r : v.r;
         const double* om = amg->omega + l;
+        const double* ch = amg->cheb + (size_t)l * AMG_CHEB_STRIDE;
         double *cur = v.xa, *other = v.xb;
-        AMG_BS(v.bs, amg_jacobi0, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.dinv, om, rin, cur);
+        if (cheby) AMG_BS(v.bs, amg_cheby0, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.dinv, ch, rin, v.d, cur);
+        else AMG_BS(v.bs, amg_jacobi0, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.dinv, om, rin, cur);
         for (int k = 1; k < nu; ++k) {
-            sweep_launch<false>(v.bs, v, om, rin, cur, other, s);
+            if (cheby) cheby_launch(v, ch + 2 * k, rin, cur, other, s);
+            else sweep_launch<false>(v.bs, v, om, rin, cur, other, s);
             std::swap(cur, other);
         }
         sweep_launch<true>(v.bs, v, om, rin, cur, v.t, s);
@@ -1229,7 +1478,8 @@ void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipSt
         AMG_PAIR(v.bs, v.bsc, amg_prolong, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, amg->L[(size_t)l + 1].cur, cur);
         for (int k = 0; k < nu; ++k) {
             double* out = (l == 0 && k == nu - 1) ? z : other;      // the last sweep of the fine level writes the result
-            sweep_launch<false>(v.bs, v, om, rin, cur, out, s);
+            if (cheby) cheby_launch(v, amg->cheb + (size_t)l * AMG_CHEB_STRIDE + 2 * k, rin, cur, out, s);
+            else sweep_launch<false>(v.bs, v, om, rin, cur, out, s);
             other = cur;
             cur = out;
         }
@@ -1320,6 +1570,38 @@ extern "C" int dxo_amg_nns_info(dxo_ctx* ctx, const dxo_amg* amg, int level, int
     return DXO_OK;
 }
 
+extern "C" int dxo_amg_set_smoother(dxo_ctx* ctx, dxo_amg* amg, int kind, int degree, int rho_kind, int rho_iters, double lower, double safety) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!amg) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_set_smoother: NULL argument");
+    const bool cheby = kind == DXO_AMG_SMOOTH_CHEBYSHEV;
+    if ((!cheby && kind != DXO_AMG_SMOOTH_JACOBI) || (rho_kind != DXO_AMG_RHO_INF_NORM && rho_kind != DXO_AMG_RHO_POWER))
+        return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_set_smoother: unknown smoother or rho kind");
+    if ((cheby && (degree < 1 || degree > AMG_MAX_DEGREE)) || rho_iters < 1 || !(lower > 0.0 && lower < 1.0) || !(safety >= 1.0))
+        return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_set_smoother: degree outside 1..8, rho_iters < 1, lower outside (0, 1) or safety < 1");
+    amg->ready = false;      // omega, P, the coarse matrices and the Chebyshev pairs are those of the last setup
+    amg->smooth_kind = kind;
+    if (cheby) amg->degree = degree;
+    amg->rho_kind = rho_kind;
+    amg->rho_iters = rho_iters;
+    amg->lower = lower;
+    amg->safety = safety;
+    return DXO_OK;
+}
+
+extern "C" int dxo_amg_smoother_info(dxo_ctx* ctx, const dxo_amg* amg, int level, int* kind, int* degree, int* rho_kind, int* rho_iters,
+                                     const double** rho) {
+    if (!amg) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (level < 0 || level >= (int)amg->L.size()) return dxo_fail(ctx, DXO_E_SIZE, "dxo_amg_smoother_info: no such level");
+    if (kind) *kind = amg->smooth_kind;
+    if (degree) *degree = amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV ? amg->degree : amg->sweeps;
+    if (rho_kind) *rho_kind = amg->rho_kind;
+    if (rho_iters) *rho_iters = amg->rho_iters;
+    if (rho) *rho = level + 1 < (int)amg->L.size() ? amg->rho + level : nullptr;
+    return DXO_OK;
+}
+
 extern "C" int dxo_amg_destroy(dxo_ctx* ctx, dxo_amg* amg) {
     if (!amg) return DXO_E_NULL;
     DXO_LOCK(ctx);
@@ -1351,12 +1633,33 @@ extern "C" int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values) {
         const int bs = v.bs;
         if (bs == 6) hipLaunchKernelGGL(amg_bj6, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, amg->flag);
         else dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
-        if (bs == 1) rho_bs<1>(v, amg->part, s);
-        else if (bs == 2) rho_bs<2>(v, amg->part, s);
-        else if (bs == 3) rho_bs<3>(v, amg->part, s);
-        else if (bs == 6) rho_bs<6>(v, amg->part, s);
-        else amg_no_shape(bs, bs);
-        hipLaunchKernelGGL(amg_omega, dim3(1), B, 0, s, amg->part, rho_parts(v), amg->omega + l);
+        double* cheb = amg->cheb + (size_t)l * AMG_CHEB_STRIDE;
+        if (amg->rho_kind == DXO_AMG_RHO_POWER) {
+            // v_0 in xa, then w = Dinv A (v / |v|) back and forth between xa and xb: the cycle's vectors are free during a setup
+            double *from = v.xa, *to = v.xb;
+            hipLaunchKernelGGL(amg_power_init, amg_grid(v.n_rows), B, 0, s, v.n_rows, from, amg->part);
+            hipLaunchKernelGGL(amg_power_norm, dim3(1), B, 0, s, amg->part, init_parts(v), 0, amg->safety, amg->lower, amg->degree, amg->scal,
+                               amg->rho + l, amg->omega + l, cheb);
+            for (int it = 0; it < amg->rho_iters; ++it) {
+                if (bs == 1) power_bs<1>(v, amg->scal, from, to, amg->part, s);
+                else if (bs == 2) power_bs<2>(v, amg->scal, from, to, amg->part, s);
+                else if (bs == 3) power_bs<3>(v, amg->scal, from, to, amg->part, s);
+                else if (bs == 6) power_bs<6>(v, amg->scal, from, to, amg->part, s);
+                else amg_no_shape(bs, bs);
+                hipLaunchKernelGGL(amg_power_norm, dim3(1), B, 0, s, amg->part, rho_parts(v), it + 1 == amg->rho_iters ? 1 : 0, amg->safety,
+                                   amg->lower, amg->degree, amg->scal, amg->rho + l, amg->omega + l, cheb);
+                std::swap(from, to);
+            }
+        } else {
+            if (bs == 1) rho_bs<1>(v, amg->part, s);
+            else if (bs == 2) rho_bs<2>(v, amg->part, s);
+            else if (bs == 3) rho_bs<3>(v, amg->part, s);
+            else if (bs == 6) rho_bs<6>(v, amg->part, s);
+            else amg_no_shape(bs, bs);
+            hipLaunchKernelGGL(amg_omega, dim3(1), B, 0, s, amg->part, rho_parts(v), amg->omega + l, amg->rho + l);
+            if (amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV)
+                hipLaunchKernelGGL(amg_cheby_coeffs, dim3(1), dim3(64), 0, s, amg->rho + l, amg->lower, amg->degree, cheb);
+        }
         build_p_launch(v, nns, amg->omega + l, s);
         AMG_PAIR(bs, v.bsc, amg_build_ap, amg_grid(v.ap_blocks), B, 0, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr,
                  v.p_col, v.p_val, v.ap_val);

@@ -14,6 +14,8 @@ from dataclasses import dataclass
 from ._lib import KRYLOV_APPLY_FN, AmgLevelInfo, KrylovInfo, KrylovOp, KrylovPc, _CudaArrayView
 
 PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI, PC_AMG = 0, 1, 2, 3
+_SMOOTHERS = {"jacobi": 0, "chebyshev": 1}           # DXO_AMG_SMOOTH_*
+_RHO_KINDS = {"inf-norm": 0, "power": 1}             # DXO_AMG_RHO_*
 
 
 def _torch():
@@ -115,9 +117,19 @@ class AMG:
 
     `near_nullspace`: a float64 CUDA tensor (n_rows, k), k = 3 for bs 2 and 6 for bs 3 (rigid_body_modes(x) for elasticity). The
     tentative prolongator then carries these vectors, orthonormalised per aggregate, and every coarse level has block size k
-    (dxo_amg_create_nns); it is made once, here, and setup() leaves it alone."""
+    (dxo_amg_create_nns); it is made once, here, and setup() leaves it alone.
 
-    def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None):
+    The relaxation (dxo_amg_set_smoother). `rho`: where the estimate of the spectral radius of Dinv A comes from, which sets
+    omega = (4/3) / rho of the prolongator smoothing and of the Jacobi sweeps: "inf-norm" (|Dinv A|_inf, a bound, often 2x too large
+    on elasticity) or "power" (`rho_iters` steps of the power iteration on the device, times `safety`; an estimate from below, not a
+    bound). `smoother`: "jacobi" (`sweeps` damped block-Jacobi sweeps) or "chebyshev" (the polynomial of `degree` in Dinv A on
+    [lower rho, rho] before and after the coarse correction; `degree` None: `sweeps`, at most 8). The defaults rho_iters 10,
+    lower 0.1 and safety 1.1 are the customary rule (PETSc's), not measurements on this library. With the default smoother and rho
+    the object is the one of earlier versions bit for bit."""
+
+    def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None,
+                 smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10, lower: float = 0.1,
+                 safety: float = 1.1):
         torch = _torch()
         import numpy as np
 
@@ -125,6 +137,8 @@ class AMG:
         self.device = A.values.device
         if int(max_levels) < 1 or int(coarse_rows) < 1 or int(sweeps) < 1:
             raise ValueError("AMG: max_levels, coarse_rows and sweeps must be at least 1")
+        self.sweeps = int(sweeps)
+        relax = self._relaxation(smoother, degree, rho, rho_iters, lower, safety)
         if constrained is None:
             bc = torch.empty(0, dtype=torch.int32, device=self.device)
         elif isinstance(constrained, torch.Tensor):
@@ -157,7 +171,32 @@ class AMG:
         nl, ms, oc = C.c_int(), C.c_double(), C.c_double()
         self.ctx.check(self.ctx.lib.dxo_amg_info(self.ctx._h, h, C.byref(nl), C.byref(ms), C.byref(oc), 0, None), "dxo_amg_info")
         self.n_levels, self.build_ms, self.operator_complexity = nl.value, ms.value, oc.value
+        self._lower, self._safety = 0.1, 1.1
+        if relax[0] or relax[2]:         # the defaults call nothing that earlier versions did not call
+            self._set_smoother(*relax)
         self.setup()
+
+    def _relaxation(self, smoother, degree, rho, rho_iters, lower, safety) -> tuple:
+        if smoother not in _SMOOTHERS or rho not in _RHO_KINDS:
+            raise ValueError(f"AMG: smoother must be one of {sorted(_SMOOTHERS)} and rho one of {sorted(_RHO_KINDS)}")
+        degree = self.sweeps if degree is None else int(degree)
+        if smoother == "chebyshev" and not 1 <= degree <= 8:
+            raise ValueError("AMG: the Chebyshev degree (sweeps if degree is None) must lie in 1..8")
+        if int(rho_iters) < 1 or not 0.0 < float(lower) < 1.0 or not float(safety) >= 1.0:
+            raise ValueError("AMG: rho_iters must be at least 1, lower inside (0, 1) and safety at least 1")
+        return _SMOOTHERS[smoother], degree, _RHO_KINDS[rho], int(rho_iters), float(lower), float(safety)
+
+    def _set_smoother(self, kind, degree, rho_kind, rho_iters, lower, safety) -> None:
+        rc = self.ctx.lib.dxo_amg_set_smoother(self.ctx._h, self._h, kind, degree, rho_kind, rho_iters, lower, safety)
+        self.ctx.check(rc, "dxo_amg_set_smoother")
+        self._lower, self._safety = lower, safety
+
+    def set_smoother(self, smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10,
+                     lower: float = 0.1, safety: float = 1.1) -> "AMG":
+        """Another relaxation for this hierarchy (the keywords of the constructor); allocates nothing. apply() and the solvers raise
+        ValueError (DXO_E_OPTION) until the next setup()."""
+        self._set_smoother(*self._relaxation(smoother, degree, rho, rho_iters, lower, safety))
+        return self
 
     def close(self) -> None:
         self._fin()
@@ -221,6 +260,27 @@ class AMG:
             om = float(self._array(i.omega, 1, "<f8")[0]) if i.omega else None
             out.append({"rows": int(i.n_rows), "nodes": int(i.n_nodes), "block_nnz": int(i.nnz_blocks), "omega": om, "bs": self._nns(l)[0]})
         return out
+
+    def _smoother_info(self, level: int):
+        """(kind, degree, rho kind, rho_iters, rho pointer) of a level (dxo_amg_smoother_info)."""
+        kind, degree, rk, it, rho = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.dxo_amg_smoother_info(self.ctx._h, self._h, int(level), C.byref(kind), C.byref(degree), C.byref(rk),
+                                                          C.byref(it), C.byref(rho)), "dxo_amg_smoother_info")
+        return kind.value, degree.value, rk.value, it.value, rho.value
+
+    @property
+    def smoother(self) -> dict:
+        """The relaxation: smoother, degree (the sweeps of Jacobi), rho, rho_iters, lower and safety."""
+        kind, degree, rk, it, _ = self._smoother_info(0)
+        return {"smoother": {v: k for k, v in _SMOOTHERS.items()}[kind], "degree": degree, "rho": {v: k for k, v in _RHO_KINDS.items()}[rk],
+                "rho_iters": it, "lower": self._lower, "safety": self._safety}
+
+    @property
+    def rho(self) -> list:
+        """Per level the estimate of the spectral radius of Dinv A that omega was made from at the last setup (None on the coarsest
+        level). Reading it synchronises the stream."""
+        ptrs = [self._smoother_info(l)[4] for l in range(self.n_levels)]
+        return [float(self._array(p, 1, "<f8")[0]) if p else None for p in ptrs]
 
     @property
     def dead_columns(self) -> list:

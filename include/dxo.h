@@ -649,7 +649,8 @@ int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const d
  *                   coarsest level of more than 4096 rows: DXO_E_SIZE. max_levels, coarse_rows or sweeps < 1: DXO_E_SIZE; bs outside
  *                   1..3: DXO_E_DIM. All device memory of setup and apply is allocated here.
  * dxo_amg_setup   : the numeric phase for the matrix `values` on the pattern of the creation, on the context's stream: per level the
- *                   block-Jacobi inverses, rho = |Dinv A|_inf and omega = (4/3) / rho (kept on the device), P = T - omega Dinv A T,
+ *                   block-Jacobi inverses, rho = |Dinv A|_inf (or the estimate chosen by dxo_amg_set_smoother, below) and
+ *                   omega = (4/3) / rho (kept on the device), P = T - omega Dinv A T,
  *                   A_c = P^T (A P); the coarsest matrix is inverted densely (Gauss-Jordan, partial pivoting). Sums run in ascending
  *                   source order, no atomics: two setups from the same values give bit-identical hierarchies. One synchronisation at
  *                   the end reads one flag: a singular diagonal block or a zero pivot gives DXO_E_SINGULAR. `values` is read again by
@@ -680,7 +681,29 @@ int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const d
  *                   size: dinv [n_nodes][bs_l][bs_l], p_values [p_blocks][bs_l][bs_coarse].
  * dxo_amg_nns_info : the block size of `level` and of the next one, the dead columns of its T, and the DEVICE arrays T
  *                   [n_nodes][bs][bs_coarse] (NULL on the coarsest level) and B [n_rows][n_modes]; any pointer may be NULL. On an
- *                   object of dxo_amg_create: bs_coarse = bs, 0 dead columns, NULL arrays. */
+ *                   object of dxo_amg_create: bs_coarse = bs, 0 dead columns, NULL arrays.
+ *
+ * The relaxation (every object starts with DXO_AMG_SMOOTH_JACOBI and DXO_AMG_RHO_INF_NORM, which is all of the above):
+ * dxo_amg_set_smoother : the smoother and the source of rho for the NEXT dxo_amg_setup; until then dxo_amg_apply and the Krylov calls
+ *                   answer DXO_E_OPTION. rho_kind DXO_AMG_RHO_POWER: rho = safety * |w_m|, m = rho_iters steps
+ *                   w_k = Dinv A (w_{k-1} / |w_{k-1}|) from w_0[i] = 0.5 + ((uint32)(i * 2654435761) >> 8) * 2^-24 on every level, on
+ *                   the device, with fixed reduction orders (bit-reproducible, no additional synchronisation). It is an estimate of
+ *                   the spectral radius from below times `safety`, not a bound. omega = (4/3) / rho of the prolongator smoothing and
+ *                   of the Jacobi sweeps follows the selected rho. kind DXO_AMG_SMOOTH_CHEBYSHEV: the `sweeps` Jacobi sweeps before
+ *                   and after the coarse correction become the Chebyshev polynomial of `degree` (1..8) in Dinv A on
+ *                   [lower * rho, rho]: with theta = (1 + lower) rho / 2, delta = (1 - lower) rho / 2, sigma = theta / delta:
+ *                   rho_0 = 1 / sigma, d = Dinv res / theta, x += d; then rho_1 = 1 / (2 sigma - rho_0),
+ *                   d = rho_1 rho_0 d + (2 rho_1 / delta) Dinv (r - A x), x += d, rho_0 = rho_1. The post-smoothing is the same
+ *                   polynomial from the corrected x, so the cycle stays symmetric for a symmetric matrix. Chebyshev with
+ *                   DXO_AMG_RHO_INF_NORM is allowed (a wide interval). For DXO_AMG_SMOOTH_JACOBI `degree` is ignored. Unknown kinds,
+ *                   Chebyshev degree outside 1..8, rho_iters < 1, lower outside (0, 1), safety < 1: DXO_E_OPTION, nothing changes.
+ *                   Allocates nothing: the one extra vector per level was allocated at creation.
+ * dxo_amg_smoother_info : the settings (degree: `sweeps` for Jacobi) and the DEVICE address of the rho of `level` that omega was made
+ *                   from at the last setup, under either estimate (NULL on the coarsest level); any pointer may be NULL. */
+#define DXO_AMG_SMOOTH_JACOBI 0
+#define DXO_AMG_SMOOTH_CHEBYSHEV 1
+#define DXO_AMG_RHO_INF_NORM 0
+#define DXO_AMG_RHO_POWER 1
 typedef struct dxo_amg dxo_amg;
 typedef struct dxo_amg_level_info {
     int64_t n_rows, n_nodes;       /* of A_l                                              */
@@ -711,6 +734,9 @@ int dxo_amg_create_nns(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* constrai
                        int max_levels, int coarse_rows, int sweeps, dxo_amg** out);
 int dxo_amg_nns_info(dxo_ctx* ctx, const dxo_amg* amg, int level, int* bs, int* bs_coarse, int64_t* dead_columns, const double** t_val,
                      const double** b_val);
+int dxo_amg_set_smoother(dxo_ctx* ctx, dxo_amg* amg, int kind, int degree, int rho_kind, int rho_iters, double lower, double safety);
+int dxo_amg_smoother_info(dxo_ctx* ctx, const dxo_amg* amg, int level, int* kind, int* degree, int* rho_kind, int* rho_iters,
+                          const double** rho);
 
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is

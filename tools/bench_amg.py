@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Standalone timing of the multigrid preconditioner (csrc/amg.hip; not a bench.py leg).
-    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm]
+    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG]
 Systems (distorted meshes, the lower side clamped so that the matrices are regular):
   p2       ("grad", "grad", 2) on P2 triangles with C = I + 0.3 N(0, 1) per point (1291 per side: 10^7 points), as tools/bench_krylov.py
   q2hex    ("eps", "eps", 3) on Q2 hexahedra (40^3 boxes), the same kind of C
@@ -10,6 +10,9 @@ to one SpMV beside the model 2 + 3 (c - 1) (c the operator complexity), rows per
 `maxiter` iterations) with block Jacobi and with the cycle (iterations, ms; the cycle's total adds one setup).
 --rbm adds, for the two elasticity-type systems and an ("eps", "eps", 2) system p2eps on the p2 mesh, the same figures for the hierarchy
 with the rigid-body modes as near-null space (keys ending in _rbm; symbolic_ms_rbm includes the tentative prolongators).
+--cheby DEG adds, for every hierarchy measured (those of --rbm included), the figures of two more relaxations on the same object in the
+same run, beside the default's (|Dinv A|_inf, damped Jacobi): power_jacobi (rho from the power iteration, Jacobi) and power_cheby<DEG>
+(that rho, Chebyshev of degree DEG): setup ms, apply ms, rho per level, and the GMRES(30) solve (iterations, ms, ms_with_setup).
 Timing: warm-up, then 5 batches timed with HIP events on the launch stream, the MEDIAN batch reported (tools/bench_krylov._batches).
 Prints one JSON line."""
 from __future__ import annotations
@@ -23,7 +26,8 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 
-def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000, rbm: bool = False) -> dict:
+def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000, rbm: bool = False,
+         cheby: int = 0) -> dict:
     import numpy as np
     import torch
 
@@ -43,6 +47,16 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
     def timed(fn, per_batch):
         ms, _ = _batches(torch, stream, fn, per_batch=per_batch, warm=2)
         return round(ms, 4)
+
+    def relaxations(amg, A, b, x, y, r, suffix):
+        for key, kw in (("power_jacobi", {"rho": "power"}), (f"power_cheby{cheby}", {"smoother": "chebyshev", "degree": cheby, "rho": "power"})):
+            amg.set_smoother(**kw).setup()
+            f = {"setup_ms": timed(lambda: amg.setup(), 3), "apply_ms": timed(lambda: amg.apply(x, y), 20), "rho": amg.rho}
+            gmres(A, b, M=amg, rtol=1e-8, maxiter=30)                        # warm-up
+            out = gmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
+            f.update({"iterations": out.iterations, "converged": out.converged, "residual": out.residual, "ms": round(out.ms, 2),
+                      "ms_with_setup": round(out.ms + f["setup_ms"], 2)})
+            r[key + suffix] = f
 
     def system(tag, m, test, trial, bs, Cd, bnd):
         dm = DeviceMesh.from_synthetic(m, ctx=ctx)
@@ -73,6 +87,8 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                     r[f"gmres30_{name}"] = {"iterations": out.iterations, "converged": out.converged, "residual": out.residual,
                                             "ms": round(out.ms, 2)}
                 r["gmres30_amg"]["ms_with_setup"] = round(r["gmres30_amg"]["ms"] + r["setup_ms"], 2)
+                if cheby:
+                    relaxations(amg, A, b, x, y, r, "")
                 amg.close()
                 if rbm and bs == m.gdim:
                     amg = A.amg(bcs, near_nullspace=rigid_body_modes(m.node_x, ctx=ctx))
@@ -86,6 +102,8 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                     out = gmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
                     r["gmres30_amg_rbm"] = {"iterations": out.iterations, "converged": out.converged, "residual": out.residual,
                                             "ms": round(out.ms, 2), "ms_with_setup": round(out.ms + r["setup_ms_rbm"], 2)}
+                    if cheby:
+                        relaxations(amg, A, b, x, y, r, "_rbm")
                     amg.close()
             stream.synchronize()
             res["systems"][tag] = r
@@ -135,7 +153,12 @@ if __name__ == "__main__":
     rbm = "--rbm" in args
     if rbm:
         args.remove("--rbm")
-    r = main(*(int(a) for a in args), rbm=rbm)
+    cheby = 0
+    if "--cheby" in args:
+        i = args.index("--cheby")
+        cheby = int(args[i + 1])
+        del args[i:i + 2]
+    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby)
     line = json.dumps(r)
     print(line)
     if out_file:
