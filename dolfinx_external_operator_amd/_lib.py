@@ -205,6 +205,9 @@ _SIGNATURES = {
     "dxo_amg_set_smoother": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
     "dxo_amg_smoother_info": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(_P)]),
+    "dxo_amg_create_soc": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "dxo_amg_soc_info": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_double), C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                   C.POINTER(_P), C.POINTER(_P)]),
     "dxo_krylov_cg": (C.c_int, [_P, _P, C.POINTER(KrylovOp), C.POINTER(KrylovPc), _P, _P, C.c_double, C.c_double, C.c_int, C.c_int,
                                 C.POINTER(KrylovInfo)]),
     "dxo_mesh_set_facet_geometry": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

@@ -36,6 +36,17 @@
 // level, free during a setup; the setup still waits once, at its end. Chebyshev smoothing: amg_cheby0 (the first step from x = 0, no
 // SpMV) and amg_cheby_sweep (d = c1 d + c2 Dinv (r - A x), x_out = x + d; d in place, x between xa and xb as the Jacobi sweeps) with
 // the pairs (c1, c2) read from the device like omega; the post-smoothing is the same polynomial started from the corrected x.
+//
+// Strength of connection (dxo_amg_create_soc with theta > 0). Block (i, j) is strong when |A_ij|_F^2 >= theta^2 |A_ii|_F |A_jj|_F or
+// the same holds for (j, i): amg_diag_norm writes |A_ii|_F per node, amg_strength (a lane group per node, a lane per block, the
+// transposed block found by search) one byte per block. Creation then interleaves with the numeric phase level by level: the mask of
+// level l comes to the host, the aggregates are made on the strong graph, P gets the pattern (strong graph) x (aggregates) while A P
+// and P^T A P keep the full graph, and the numeric kernels of level l give the matrix of level l + 1 for the next mask (one wait per
+// level, at creation only; the relaxation is the default one there). The masks are frozen: dxo_amg_setup reuses them. The
+// prolongator is smoothed with the filtered matrix A^F (weak blocks added onto the diagonal block of their row, never stored):
+// amg_lump forms the lumped diagonal blocks and their inverses dinv_f (a block that fails the test of invert_block: the inverse of
+// A_ii, counted; a node without a strong neighbour: zero, its row of P is its row of T), amg_rho / amg_power_step estimate the rho_F
+// of Dinv_F A^F given the mask, omega_F = (4/3) / rho_F, and amg_build_p skips the weak blocks. The sweeps keep A, Dinv and rho.
 #include "krylov_internal.h"
 
 #include <algorithm>
@@ -87,6 +98,12 @@ struct amg_level {
     uint8_t* dead_a = nullptr;         // [n_agg] dead columns of an aggregate
     int tl = 8;                        // lanes per aggregate of amg_tentative
     int64_t dead = 0;                  // dead columns of T (host, after creation)
+    // strength of connection only (absent on the coarsest level)
+    uint8_t* strong = nullptr;         // [nnzb] 1: a strong block, in the order of the block pattern; frozen at creation
+    double* diag_f = nullptr;          // [n_nodes][bs][bs] the diagonal blocks of the filtered matrix
+    double* dinv_f = nullptr;          // [n_nodes][bs][bs] their inverses (A_ii's after a failed test; zero: the node is not smoothed)
+    uint8_t* unlumped = nullptr;       // [n_nodes] 1: the lumped block failed the test
+    int64_t n_strong = 0;              // strong blocks (host)
 };
 
 }  // namespace
@@ -110,6 +127,11 @@ struct dxo_amg {
     double* rho = nullptr;             // [levels] the estimate omega was made from
     double* cheb = nullptr;            // [levels][AMG_CHEB_STRIDE] the pairs (c1, c2) of the Chebyshev steps
     double* scal = nullptr;            // power iteration: [0] 1 / |w|, the scale of the next step, [1] |w|
+    // strength of connection (dxo_amg_create_soc with theta > 0)
+    double theta = 0.0;
+    double* omega_f = nullptr;         // [levels] omega of the filtered prolongator smoothing
+    double* rho_f = nullptr;           // [levels] the estimate of Dinv_F A^F it was made from
+    double* cheb_f = nullptr;          // [AMG_CHEB_STRIDE] where amg_power_norm leaves the pairs of rho_F: not used
 };
 
 namespace {
@@ -139,10 +161,12 @@ __device__ __forceinline__ int64_t amg_find(const int32_t* __restrict__ col, int
 }
 
 // ---- numeric phase
-// part[block] = max over the block's nodes of the absolute row sums of Dinv A
+// part[block] = max over the block's nodes of the absolute row sums of Dinv A; with `strong`, of Dinv_F A^F (dinv is then dinv_f)
 template <int BS, int LW>
-__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_rho(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const double* __restrict__ values,
-                                                         const double* __restrict__ dinv, double* __restrict__ part) {
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_rho(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                         const double* __restrict__ values, const double* __restrict__ dinv,
+                                                         const uint8_t* __restrict__ strong, const double* __restrict__ diag_f,
+                                                         double* __restrict__ part) {
     __shared__ double lds[DXO_AMG_BLOCK / 64];
     constexpr int NPB = DXO_AMG_BLOCK / LW;
     const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
@@ -158,11 +182,20 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_rho(int64_t n_nodes, const 
 #pragma unroll
             for (int j = 0; j < BS; ++j) D[i][j] = dinv[node * BS * BS + i * BS + j];
         for (int k = lane; k < R.nnb; k += LW) {
+            const double* ab = values + R.r0 + (int64_t)k * BS;
+            int64_t ld = R.len;
+            if (strong) {                                      // the filtered matrix: no weak blocks, the lumped diagonal block
+                if (!strong[R.r0 / (BS * BS) + k]) continue;
+                if (col[R.r0 + (int64_t)k * BS] == node * BS) {
+                    ab = diag_f + node * BS * BS;
+                    ld = BS;
+                }
+            }
             double a[BS][BS];
 #pragma unroll
             for (int i = 0; i < BS; ++i)
 #pragma unroll
-                for (int j = 0; j < BS; ++j) a[i][j] = values[R.r0 + i * R.len + (int64_t)k * BS + j];
+                for (int j = 0; j < BS; ++j) a[i][j] = ab[i * ld + j];
 #pragma unroll
             for (int i = 0; i < BS; ++i)
 #pragma unroll
@@ -239,6 +272,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_init(int64_t n_rows, 
 template <int BS, int LW>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_step(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                                 const double* __restrict__ values, const double* __restrict__ dinv,
+                                                                const uint8_t* __restrict__ strong, const double* __restrict__ diag_f,
                                                                 const double* __restrict__ scal, const double* __restrict__ v,
                                                                 double* __restrict__ w, double* __restrict__ part) {
     __shared__ double lds[DXO_AMG_BLOCK / 64];
@@ -253,12 +287,21 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_step(int64_t n_nodes,
         const NodeRow<BS> R(row_ptr, node);
         for (int k = lane; k < R.nnb; k += LW) {
             const int64_t c = col[R.r0 + (int64_t)k * BS];
+            const double* ab = values + R.r0 + (int64_t)k * BS;
+            int64_t ld = R.len;
+            if (strong) {                                      // as in amg_rho
+                if (!strong[R.r0 / (BS * BS) + k]) continue;
+                if (c == node * BS) {
+                    ab = diag_f + node * BS * BS;
+                    ld = BS;
+                }
+            }
             double xb[BS];
 #pragma unroll
             for (int j = 0; j < BS; ++j) xb[j] = sc * v[c + j];
 #pragma unroll
             for (int i = 0; i < BS; ++i) {
-                const double* a = values + R.r0 + i * R.len + (int64_t)k * BS;
+                const double* a = ab + i * ld;
 #pragma unroll
                 for (int j = 0; j < BS; ++j) acc[i] = fma(a[j], xb[j], acc[i]);
             }
@@ -339,13 +382,15 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_row_mask(int64_t n_rows, co
 }
 
 // P = T - omega Dinv (A T), one thread per block (i, a): the neighbours j of i with aggregate a, ascending. NNS: the block of T of
-// node j is t_val[j] (BSR x BSC); otherwise an identity without the masked dofs (BSR == BSC)
+// node j is t_val[j] (BSR x BSC); otherwise an identity without the masked dofs (BSR == BSC). With `strong`:
+// P = T - omega_F Dinv_F (A^F T), dinv and omega being dinv_f and omega_F
 template <int BSR, int BSC, bool NNS>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_p(int64_t p_blocks, const int32_t* __restrict__ p_row, const int32_t* __restrict__ p_col,
                                                              const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                              const double* __restrict__ values, const double* __restrict__ dinv,
                                                              const int32_t* __restrict__ agg, const uint8_t* __restrict__ mask,
                                                              const double* __restrict__ t_val, const double* __restrict__ omega,
+                                                             const uint8_t* __restrict__ strong, const double* __restrict__ diag_f,
                                                              double* __restrict__ p_val) {
     static_assert(NNS || BSR == BSC, "an identity per node needs square blocks");
     const int64_t e = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
@@ -361,6 +406,15 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_p(int64_t p_blocks, c
     for (int k = 0; k < R.nnb; ++k) {
         const int64_t j = col[R.r0 + (int64_t)k * BSR] / BSR;
         if (agg[j] != a) continue;
+        const double* ab = values + R.r0 + (int64_t)k * BSR;
+        int64_t ld = R.len;
+        if (strong) {                                          // A^F T: no weak blocks, the lumped diagonal block (dinv is dinv_f)
+            if (!strong[R.r0 / (BSR * BSR) + k]) continue;
+            if (j == i) {
+                ab = diag_f + i * BSR * BSR;
+                ld = BSR;
+            }
+        }
         if constexpr (NNS) {
 #pragma unroll
             for (int q = 0; q < BSR; ++q) {
@@ -369,7 +423,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_p(int64_t p_blocks, c
                 for (int c = 0; c < BSC; ++c) tq[c] = t_val[(j * BSR + q) * BSC + c];
 #pragma unroll
                 for (int r = 0; r < BSR; ++r) {
-                    const double v = values[R.r0 + r * R.len + (int64_t)k * BSR + q];
+                    const double v = ab[r * ld + q];
 #pragma unroll
                     for (int c = 0; c < BSC; ++c) acc[r][c] = fma(v, tq[c], acc[r][c]);
                 }
@@ -379,7 +433,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_p(int64_t p_blocks, c
             for (int c = 0; c < BSC; ++c) {
                 if (mask[j * BSR + c]) continue;
 #pragma unroll
-                for (int r = 0; r < BSR; ++r) acc[r][c] += values[R.r0 + r * R.len + (int64_t)k * BSR + c];
+                for (int r = 0; r < BSR; ++r) acc[r][c] += ab[r * ld + c];
             }
         }
     }
@@ -490,31 +544,15 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_c(int64_t c_blocks, c
 // ---- the block inverses of a level of block size 6: Gauss-Jordan on [A | I] with partial pivoting (the lowest row among equals),
 // one thread per node. Rows are exchanged by compare-and-select over static indices, so the 72 doubles stay in registers. A block
 // with |det| <= 1e-14 of the product of its row norms (the rule of dxo_csr_block_jacobi) gets a zero inverse and raises the flag.
-__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_bj6(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                                         const double* __restrict__ values, double* __restrict__ inv, int* __restrict__ singular) {
+// M = [A | I] on entry, [. | A^-1] on return; false for a zero, NaN or nearly singular block
+__device__ __forceinline__ bool amg_gj6(double (&M)[6][12]) {
     constexpr int BS = 6;
-    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
-    if (node >= n_nodes) return;
-    const NodeRow<BS> R(row_ptr, node);
-    int lo = 0, hi = R.nnb - 1;
-    const int64_t self = node * BS;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (col[R.r0 + (int64_t)mid * BS] < self) lo = mid + 1;
-        else hi = mid;
-    }
-    bool ok = hi >= 0 && col[R.r0 + (int64_t)lo * BS] == self;
-    double M[BS][2 * BS];
     double had = 1.0, det = 1.0;
 #pragma unroll
     for (int i = 0; i < BS; ++i) {
         double n2 = 0.0;
 #pragma unroll
-        for (int j = 0; j < BS; ++j) {
-            M[i][j] = ok ? values[R.r0 + i * R.len + (int64_t)lo * BS + j] : 0.0;
-            M[i][BS + j] = i == j ? 1.0 : 0.0;
-            n2 = fma(M[i][j], M[i][j], n2);
-        }
+        for (int j = 0; j < BS; ++j) n2 = fma(M[i][j], M[i][j], n2);
         had *= sqrt(n2);
     }
 #pragma unroll
@@ -552,13 +590,157 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_bj6(int64_t n_nodes, const 
             for (int c = k; c < 2 * BS; ++c) M[i][c] = fma(-fct, M[k][c], M[i][c]);
         }
     }
-    ok = ok && fabs(det) > 1e-14 * had;     // false for a zero, NaN or nearly singular block
+    return fabs(det) > 1e-14 * had;
+}
+
+// position of the block of column `node` among the blocks of a node's row (its own: the diagonal block), or -1
+template <int BS>
+__device__ __forceinline__ int amg_block_pos(const NodeRow<BS>& R, const int32_t* __restrict__ col, int64_t node) {
+    int lo = 0, hi = R.nnb - 1;
+    const int64_t self = node * BS;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (col[R.r0 + (int64_t)mid * BS] < self) lo = mid + 1;
+        else hi = mid;
+    }
+    return hi >= 0 && col[R.r0 + (int64_t)lo * BS] == self ? lo : -1;
+}
+
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_bj6(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                         const double* __restrict__ values, double* __restrict__ inv, int* __restrict__ singular) {
+    constexpr int BS = 6;
+    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (node >= n_nodes) return;
+    const NodeRow<BS> R(row_ptr, node);
+    const int lo = amg_block_pos<BS>(R, col, node);
+    bool ok = lo >= 0;
+    double M[BS][2 * BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) {
+            M[i][j] = ok ? values[R.r0 + i * R.len + (int64_t)lo * BS + j] : 0.0;
+            M[i][BS + j] = i == j ? 1.0 : 0.0;
+        }
+    ok = amg_gj6(M) && ok;
     double* out = inv + node * BS * BS;
 #pragma unroll
     for (int i = 0; i < BS; ++i)
 #pragma unroll
         for (int j = 0; j < BS; ++j) out[i * BS + j] = ok ? M[i][BS + j] : 0.0;
     if (!ok) singular[0] = 1;     // every writer stores the same word
+}
+
+// ---- strength of connection
+// the sum of the squares of a block, entry by entry in row-major order
+template <int BS>
+__device__ __forceinline__ double amg_block_norm2(const double* __restrict__ a, int64_t ld) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) s = fma(a[i * ld + j], a[i * ld + j], s);
+    return s;
+}
+
+// dn[node] = |A_ii|_F (0 without a diagonal block)
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_diag_norm(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                               const double* __restrict__ values, double* __restrict__ dn) {
+    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (node >= n_nodes) return;
+    const NodeRow<BS> R(row_ptr, node);
+    const int lo = amg_block_pos<BS>(R, col, node);
+    dn[node] = lo >= 0 ? sqrt(amg_block_norm2<BS>(values + R.r0 + (int64_t)lo * BS, R.len)) : 0.0;
+}
+
+// strong[block] = |A_ij|_F^2 >= th2 |A_ii|_F |A_jj|_F, or the same for the transposed block (found by search in row j; absent: the
+// one-sided test). LW lanes own a node, a lane its blocks k = lane, lane + LW, ...; diagonal blocks are strong
+template <int BS, int LW>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_strength(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                              const double* __restrict__ values, const double* __restrict__ dn, double th2,
+                                                              uint8_t* __restrict__ strong) {
+    constexpr int NPB = DXO_AMG_BLOCK / LW;
+    const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
+    const int lane = threadIdx.x % LW;
+    if (node >= n_nodes) return;
+    const NodeRow<BS> R(row_ptr, node);
+    const int64_t b0 = R.r0 / (BS * BS);
+    const double di = dn[node];
+    for (int k = lane; k < R.nnb; k += LW) {
+        const int64_t j = col[R.r0 + (int64_t)k * BS] / BS;
+        bool st = j == node;
+        if (!st) {
+            const double bound = th2 * (di * dn[j]);
+            st = amg_block_norm2<BS>(values + R.r0 + (int64_t)k * BS, R.len) >= bound;
+            if (!st) {
+                const NodeRow<BS> Rj(row_ptr, j);
+                const int t = amg_block_pos<BS>(Rj, col, node);      // the block (j, node)
+                if (t >= 0) st = amg_block_norm2<BS>(values + Rj.r0 + (int64_t)t * BS, Rj.len) >= bound;
+            }
+        }
+        strong[b0 + k] = st ? 1 : 0;
+    }
+}
+
+// the lumped diagonal block A_ii + the weak blocks of the row in ascending order, and its inverse. A block that fails the test of
+// invert_block takes the inverse of A_ii (dinv) and is marked; a node without a strong off-diagonal block gets a zero inverse (its
+// lumped block is a near-zero row sum): it is not smoothed
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_lump(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                          const double* __restrict__ values, const uint8_t* __restrict__ strong,
+                                                          const double* __restrict__ dinv, double* __restrict__ diag_f,
+                                                          double* __restrict__ dinv_f, uint8_t* __restrict__ unlumped) {
+    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (node >= n_nodes) return;
+    const NodeRow<BS> R(row_ptr, node);
+    const int64_t b0 = R.r0 / (BS * BS);
+    const int lo = amg_block_pos<BS>(R, col, node);
+    double a[BS][BS];
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) a[i][j] = lo >= 0 ? values[R.r0 + i * R.len + (int64_t)lo * BS + j] : 0.0;
+    int n_strong = 0;
+    for (int k = 0; k < R.nnb; ++k) {
+        if (k == lo) continue;
+        if (strong[b0 + k]) {
+            ++n_strong;
+            continue;
+        }
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) a[i][j] += values[R.r0 + i * R.len + (int64_t)k * BS + j];
+    }
+    double b[BS][BS];
+    bool ok;
+    if constexpr (BS == 6) {
+        double M[BS][2 * BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) {
+                M[i][j] = a[i][j];
+                M[i][BS + j] = i == j ? 1.0 : 0.0;
+            }
+        ok = amg_gj6(M);
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) b[i][j] = M[i][BS + j];
+    } else {
+        ok = invert_block<BS>(a, b);
+    }
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) {
+            const int64_t o = node * BS * BS + i * BS + j;
+            diag_f[o] = a[i][j];
+            dinv_f[o] = n_strong == 0 ? 0.0 : (ok ? b[i][j] : dinv[o]);
+        }
+    unlumped[node] = n_strong > 0 && !ok ? 1 : 0;
 }
 
 // ---- the near-null space, at creation
@@ -1009,26 +1191,57 @@ void cheby_launch(const amg_level& v, const double* c, const double* r, const do
     else amg_no_shape(v.bs, v.bs);
 }
 
+// filtered: the operator is Dinv_F A^F (the level's mask, lumped diagonal blocks and dinv_f) instead of Dinv A
 template <int BS>
-void power_bs(const amg_level& v, const double* scal, const double* x, double* w, double* part, hipStream_t s) {
+void power_bs(const amg_level& v, bool filtered, const double* scal, const double* x, double* w, double* part, hipStream_t s) {
     const dim3 b(DXO_AMG_BLOCK);
+    const double* dinv = filtered ? v.dinv_f : v.dinv;
+    const uint8_t* strong = filtered ? v.strong : nullptr;
     if (v.lw == 8)
-        hipLaunchKernelGGL((amg_power_step<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv,
-                           scal, x, w, part);
+        hipLaunchKernelGGL((amg_power_step<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dinv,
+                           strong, v.diag_f, scal, x, w, part);
     else
         hipLaunchKernelGGL((amg_power_step<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values,
-                           v.dinv, scal, x, w, part);
+                           dinv, strong, v.diag_f, scal, x, w, part);
 }
 
 template <int BS>
-void rho_bs(const amg_level& v, double* part, hipStream_t s) {
+void rho_bs(const amg_level& v, bool filtered, double* part, hipStream_t s) {
     const dim3 b(DXO_AMG_BLOCK);
-    if (v.lw == 8) hipLaunchKernelGGL((amg_rho<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.values, v.dinv, part);
-    else hipLaunchKernelGGL((amg_rho<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.values, v.dinv, part);
+    const double* dinv = filtered ? v.dinv_f : v.dinv;
+    const uint8_t* strong = filtered ? v.strong : nullptr;
+    if (v.lw == 8)
+        hipLaunchKernelGGL((amg_rho<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dinv, strong,
+                           v.diag_f, part);
+    else
+        hipLaunchKernelGGL((amg_rho<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dinv,
+                           strong, v.diag_f, part);
 }
 
-#define AMG_P_ARGS amg_grid(v.p_blocks), dim3(DXO_AMG_BLOCK), 0, s, v.p_blocks, v.p_row, v.p_col, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, v.agg, v.mask, \
-                   v.t_val, omega, v.p_val
+template <int BS>
+void strength_bs(const amg_level& v, const double* dn, double th2, uint8_t* strong, hipStream_t s) {
+    const dim3 b(DXO_AMG_BLOCK);
+    hipLaunchKernelGGL(amg_diag_norm<BS>, amg_grid(v.n_nodes), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, const_cast<double*>(dn));
+    if (v.lw == 8)
+        hipLaunchKernelGGL((amg_strength<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dn, th2,
+                           strong);
+    else
+        hipLaunchKernelGGL((amg_strength<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dn,
+                           th2, strong);
+}
+
+// |A_ii|_F of every node into dn, then the mask
+void strength_launch(const amg_level& v, double* dn, double th2, uint8_t* strong, hipStream_t s) {
+    if (v.bs == 1) strength_bs<1>(v, dn, th2, strong, s);
+    else if (v.bs == 2) strength_bs<2>(v, dn, th2, strong, s);
+    else if (v.bs == 3) strength_bs<3>(v, dn, th2, strong, s);
+    else if (v.bs == 6) strength_bs<6>(v, dn, th2, strong, s);
+    else amg_no_shape(v.bs, v.bs);
+}
+
+#define AMG_P_ARGS amg_grid(v.p_blocks), dim3(DXO_AMG_BLOCK), 0, s, v.p_blocks, v.p_row, v.p_col, v.A->d_row_ptr, v.A->d_col, v.values, v.strong ? v.dinv_f : v.dinv, v.agg, \
+                   v.mask, v.t_val, omega, v.strong, v.diag_f, v.p_val
+// omega: omega_F of the level if it carries a mask
 void build_p_launch(const amg_level& v, bool nns, const double* omega, hipStream_t s) {
     if (!nns) {
         if (v.bs == 1) hipLaunchKernelGGL((amg_build_p<1, 1, false>), AMG_P_ARGS);
@@ -1137,15 +1350,16 @@ void sort_unique(std::vector<int32_t>& v) {
     v.erase(std::unique(v.begin(), v.end()), v.end());
 }
 
-HostTransfer transfer_of(const HostGraph& g, const std::vector<int32_t>& agg, int64_t na) {
+// gp: the graph P is smoothed with (the strong graph; g itself without strength of connection)
+HostTransfer transfer_of(const HostGraph& gp, const HostGraph& g, const std::vector<int32_t>& agg, int64_t na) {
     HostTransfer t;
     const int64_t n = g.n;
     std::vector<int32_t> tmp;
     t.p_ptr.assign((size_t)n + 1, 0);
     for (int64_t i = 0; i < n; ++i) {                    // P: the aggregates of the neighbours
         tmp.clear();
-        for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1]; ++e)
-            if (agg[(size_t)g.nb[(size_t)e]] >= 0) tmp.push_back(agg[(size_t)g.nb[(size_t)e]]);
+        for (int64_t e = gp.ptr[(size_t)i]; e < gp.ptr[(size_t)i + 1]; ++e)
+            if (agg[(size_t)gp.nb[(size_t)e]] >= 0) tmp.push_back(agg[(size_t)gp.nb[(size_t)e]]);
         sort_unique(tmp);
         t.p_col.insert(t.p_col.end(), tmp.begin(), tmp.end());
         t.p_row.insert(t.p_row.end(), tmp.size(), (int32_t)i);
@@ -1257,9 +1471,123 @@ void nodes_of_aggregates(const std::vector<int32_t>& agg, int64_t na, std::vecto
         if (agg[i] >= 0) node[(size_t)fill[(size_t)agg[i]]++] = (int32_t)i;
 }
 
-// k: columns of the near-null space (every coarse level then has block size k), 0: none (every level keeps the block size)
+bool amg_misaligned(const void* p) { return ((uintptr_t)p & 7u) != 0; }
+
+// the near-null space at creation: B_0 = the caller's B with the rows of constrained dofs zero, ...
+int amg_nns_first(dxo_ctx* ctx, dxo_amg* amg, const amg_level& f, const double* B, hipStream_t s) {
+    if (f.n_rows > 0) {
+        DXO_HIP(ctx, hipMemcpyAsync(f.b_val, B, (size_t)(f.n_rows * amg->k) * sizeof(double), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(amg_zero_rows, amg_grid(f.n_rows), dim3(DXO_AMG_BLOCK), 0, s, f.n_rows, amg->k, f.mask, f.b_val);
+    }
+    return DXO_OK;
+}
+
+// ... then level by level T_l and B_{l+1} ...
+int amg_nns_level(dxo_ctx* ctx, dxo_amg* amg, const amg_level& v, double* b_next, hipStream_t s) {
+    const double tol = std::pow(10.0, -(double)ctx->amg_rank_tol);
+    DXO_HIP(ctx, hipMemsetAsync(v.t_val, 0, (size_t)(v.n_nodes * v.bs * amg->k) * sizeof(double), s));      // nodes without an aggregate
+    if (v.n_agg > 0) tentative_launch(v, b_next, tol, s);
+    return DXO_OK;
+}
+
+// ... and the dead columns of every level, after a wait
+int amg_nns_dead(dxo_ctx* ctx, dxo_amg* amg, hipStream_t s) {
+    const int nl = (int)amg->L.size();
+    DXO_HIP(ctx, hipGetLastError());
+    DXO_HIP(ctx, hipStreamSynchronize(s));
+    for (int l = 0; l + 1 < nl; ++l) {
+        amg_level& v = amg->L[(size_t)l];
+        std::vector<uint8_t> d((size_t)v.n_agg);
+        if (v.n_agg > 0) DXO_HIP(ctx, hipMemcpy(d.data(), v.dead_a, d.size(), hipMemcpyDeviceToHost));
+        v.dead = 0;
+        for (uint8_t x : d) v.dead += x;
+    }
+    return DXO_OK;
+}
+
+int amg_near_nullspace(dxo_ctx* ctx, dxo_amg* amg, const double* B, hipStream_t s) {
+    int rc = amg_nns_first(ctx, amg, amg->L[0], B, s);
+    for (int l = 0; rc == DXO_OK && l + 1 < (int)amg->L.size(); ++l) rc = amg_nns_level(ctx, amg, amg->L[(size_t)l], amg->L[(size_t)l + 1].b_val, s);
+    return rc == DXO_OK ? amg_nns_dead(ctx, amg, s) : rc;
+}
+
+// rho, omega = (4/3) / rho and (unfiltered only) the Chebyshev pairs of a level from the estimate chosen by dxo_amg_set_smoother;
+// filtered: of Dinv_F A^F, for the prolongator smoothing alone
+void amg_estimate_rho(dxo_amg* amg, const amg_level& v, bool filtered, double* rho, double* omega, double* cheb, hipStream_t s) {
+    const dim3 B(DXO_AMG_BLOCK);
+    const int bs = v.bs;
+    if (amg->rho_kind == DXO_AMG_RHO_POWER) {
+        // v_0 in xa, then w = Dinv A (v / |v|) back and forth between xa and xb: the cycle's vectors are free during a setup
+        double *from = v.xa, *to = v.xb;
+        hipLaunchKernelGGL(amg_power_init, amg_grid(v.n_rows), B, 0, s, v.n_rows, from, amg->part);
+        hipLaunchKernelGGL(amg_power_norm, dim3(1), B, 0, s, amg->part, init_parts(v), 0, amg->safety, amg->lower, amg->degree, amg->scal, rho, omega,
+                           cheb);
+        for (int it = 0; it < amg->rho_iters; ++it) {
+            if (bs == 1) power_bs<1>(v, filtered, amg->scal, from, to, amg->part, s);
+            else if (bs == 2) power_bs<2>(v, filtered, amg->scal, from, to, amg->part, s);
+            else if (bs == 3) power_bs<3>(v, filtered, amg->scal, from, to, amg->part, s);
+            else if (bs == 6) power_bs<6>(v, filtered, amg->scal, from, to, amg->part, s);
+            else amg_no_shape(bs, bs);
+            hipLaunchKernelGGL(amg_power_norm, dim3(1), B, 0, s, amg->part, rho_parts(v), it + 1 == amg->rho_iters ? 1 : 0, amg->safety, amg->lower,
+                               amg->degree, amg->scal, rho, omega, cheb);
+            std::swap(from, to);
+        }
+    } else {
+        if (bs == 1) rho_bs<1>(v, filtered, amg->part, s);
+        else if (bs == 2) rho_bs<2>(v, filtered, amg->part, s);
+        else if (bs == 3) rho_bs<3>(v, filtered, amg->part, s);
+        else if (bs == 6) rho_bs<6>(v, filtered, amg->part, s);
+        else amg_no_shape(bs, bs);
+        hipLaunchKernelGGL(amg_omega, dim3(1), B, 0, s, amg->part, rho_parts(v), omega, rho);
+        if (!filtered && amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV)
+            hipLaunchKernelGGL(amg_cheby_coeffs, dim3(1), dim3(64), 0, s, rho, amg->lower, amg->degree, cheb);
+    }
+}
+
+// the numeric phase of level l: from the values of v to those of the next level c
+void amg_setup_level(dxo_amg* amg, int l, const amg_level& v, const amg_level& c, hipStream_t s) {
+    const dim3 B(DXO_AMG_BLOCK);
+    const bool nns = amg->k > 0;
+    const int bs = v.bs;
+    if (bs == 6) hipLaunchKernelGGL(amg_bj6, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, amg->flag);
+    else dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
+    const double* omega_p = amg->omega + l;
+    if (v.strong) {
+        AMG_BS(bs, amg_lump, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.strong, v.dinv, v.diag_f, v.dinv_f,
+               v.unlumped);
+        amg_estimate_rho(amg, v, true, amg->rho_f + l, amg->omega_f + l, amg->cheb_f, s);
+        omega_p = amg->omega_f + l;
+    }
+    amg_estimate_rho(amg, v, false, amg->rho + l, amg->omega + l, amg->cheb + (size_t)l * AMG_CHEB_STRIDE, s);
+    build_p_launch(v, nns, omega_p, s);
+    AMG_PAIR(bs, v.bsc, amg_build_ap, amg_grid(v.ap_blocks), B, 0, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr,
+             v.p_col, v.p_val, v.ap_val);
+    double* cv = const_cast<double*>(c.values);
+    AMG_PAIR(bs, v.bsc, amg_build_c, amg_grid(v.c_blocks), B, 0, s, v.c_blocks, v.c_row, v.c_bptr, c.A->d_row_ptr, c.A->d_col, v.pt_ptr, v.pt_blk, v.p_row,
+             v.p_val, v.ap_ptr, v.ap_col, v.ap_val, cv);
+    // the values-dependent mask belongs to the identity form of T; with a near-null space T is fixed at creation
+    if (!nns) hipLaunchKernelGGL(amg_row_mask, amg_grid(c.n_rows), B, 0, s, c.n_rows, c.A->d_row_ptr, c.A->d_col, c.values, c.mask);
+}
+
+// the strong part of a node graph: mask[e] per entry of g
+HostGraph strong_graph(const HostGraph& g, const std::vector<uint8_t>& mask) {
+    HostGraph gs;
+    gs.n = g.n;
+    gs.ptr.assign((size_t)g.n + 1, 0);
+    for (int64_t i = 0; i < g.n; ++i) {
+        for (int64_t e = g.ptr[(size_t)i]; e < g.ptr[(size_t)i + 1]; ++e)
+            if (mask[(size_t)e]) gs.nb.push_back(g.nb[(size_t)e]);
+        gs.ptr[(size_t)i + 1] = (int64_t)gs.nb.size();
+    }
+    return gs;
+}
+
+// k: columns of the near-null space (every coarse level then has block size k), 0: none (every level keeps the block size).
+// theta > 0 (strength of connection): `values` is the matrix and Bnns the near-null space (k > 0); every level is followed by its
+// numeric phase, whose coarse matrix gives the mask of the next level
 int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, int max_levels,
-              int coarse_rows, int k) {
+              int coarse_rows, int k, double theta = 0.0, const double* values = nullptr, const double* Bnns = nullptr, hipStream_t s = nullptr) {
+    const bool soc = theta > 0.0;
     int bs = csr->bs;
     const int bsc = k > 0 ? k : bs;
     Uploader U{ctx, amg, who};
@@ -1292,18 +1620,54 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
     if (k > 0) lev.b_val = U.alloc<double>((size_t)(lev.n_rows * k));
     const int64_t nnzb0 = std::max<int64_t>(1, lev.nnzb * bs * bs);
     int64_t total = 0;
+    if (soc) {
+        // what the numeric phase needs, before the number of levels is known: every level keeps at most 0.8 of its parent's rows
+        max_levels = std::min(max_levels, 128);
+        amg->part_cap = (lev.n_nodes + 7) / 8 + 1;     // no level has more nodes than the first, and at least 8 nodes go to a workgroup
+        amg->omega = U.alloc<double>((size_t)max_levels);
+        amg->rho = U.alloc<double>((size_t)max_levels);
+        amg->cheb = U.alloc<double>((size_t)max_levels * AMG_CHEB_STRIDE);
+        amg->omega_f = U.alloc<double>((size_t)max_levels);
+        amg->rho_f = U.alloc<double>((size_t)max_levels);
+        amg->cheb_f = U.alloc<double>(AMG_CHEB_STRIDE);
+        amg->scal = U.alloc<double>(2);
+        amg->part = U.alloc<double>((size_t)amg->part_cap);
+        amg->flag = U.alloc<int>(4);
+        if (U.rc != DXO_OK) return U.rc;
+        DXO_HIP(ctx, hipMemsetAsync(amg->flag, 0, 4 * sizeof(int), s));
+        lev.values = values;
+        if (k > 0) {
+            const int rc = amg_nns_first(ctx, amg, lev, Bnns, s);
+            if (rc != DXO_OK) return rc;
+        }
+    }
     for (;;) {
         lev.lw = lanes_for(lev.nnzb, lev.n_nodes);
         total += lev.nnzb * bs * bs;
         bool last = lev.n_rows <= coarse_rows || (int)amg->L.size() + 1 >= max_levels;
         std::vector<int32_t> agg;
         int64_t na = 0;
-        if (!last) {
-            na = aggregate(g, active, agg);
-            last = na == 0 || (double)(na * bsc) > 0.8 * (double)lev.n_rows;
-        }
         lev.r = U.alloc<double>((size_t)lev.n_rows);
         lev.xa = U.alloc<double>((size_t)lev.n_rows);
+        HostGraph gs;
+        uint8_t* d_strong = nullptr;
+        int64_t n_strong = 0;
+        if (!last && soc) {
+            // |A_ii|_F in xa (free until the first cycle), the mask to the host: the one wait of this level
+            d_strong = U.alloc<uint8_t>((size_t)lev.nnzb);
+            if (U.rc != DXO_OK) return U.rc;
+            std::vector<uint8_t> hmask((size_t)lev.nnzb);
+            strength_launch(lev, lev.xa, theta * theta, d_strong, s);
+            DXO_HIP(ctx, hipGetLastError());
+            if (lev.nnzb > 0) DXO_HIP(ctx, hipMemcpyAsync(hmask.data(), d_strong, hmask.size(), hipMemcpyDeviceToHost, s));
+            DXO_HIP(ctx, hipStreamSynchronize(s));
+            for (uint8_t m : hmask) n_strong += m;
+            gs = strong_graph(g, hmask);
+        }
+        if (!last) {
+            na = aggregate(soc ? gs : g, active, agg);
+            last = na == 0 || (double)(na * bsc) > 0.8 * (double)lev.n_rows;
+        }
         if (last) {
             amg->L.push_back(lev);
             break;
@@ -1312,7 +1676,14 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
         lev.t = U.alloc<double>((size_t)lev.n_rows);
         lev.d = U.alloc<double>((size_t)lev.n_rows);
         lev.dinv = U.alloc<double>((size_t)(lev.n_nodes * bs * bs));
-        HostTransfer t = transfer_of(g, agg, na);
+        HostTransfer t = transfer_of(soc ? gs : g, g, agg, na);
+        if (soc) {
+            lev.strong = d_strong;
+            lev.n_strong = n_strong;
+            lev.diag_f = U.alloc<double>((size_t)(lev.n_nodes * bs * bs));
+            lev.dinv_f = U.alloc<double>((size_t)(lev.n_nodes * bs * bs));
+            lev.unlumped = U.alloc<uint8_t>((size_t)lev.n_nodes);
+        }
         lev.n_agg = na;
         lev.p_blocks = (int64_t)t.p_col.size();
         lev.ap_blocks = (int64_t)t.ap_col.size();
@@ -1366,6 +1737,17 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
             amg->L.push_back(c);       // owned: freed with the object
             return U.rc;
         }
+        if (soc) {
+            const amg_level& v = amg->L.back();
+            if (k > 0) {
+                const int rc = amg_nns_level(ctx, amg, v, c.b_val, s);
+                if (rc != DXO_OK) {
+                    amg->L.push_back(c);
+                    return rc;
+                }
+            }
+            if (v.n_nodes > 0) amg_setup_level(amg, (int)amg->L.size() - 1, v, c, s);
+        }
         lev = c;
         bs = bsc;
         g = std::move(t.coarse);
@@ -1380,44 +1762,26 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
                  (long long)amg->nc, (long long)AMG_MAX_DENSE);
         return dxo_fail(ctx, DXO_E_SIZE, msg);
     }
-    for (const amg_level& v : amg->L) amg->part_cap = std::max({amg->part_cap, rho_parts(v), init_parts(v)});
-    amg->omega = U.alloc<double>(amg->L.size());
-    amg->rho = U.alloc<double>(amg->L.size());
-    amg->cheb = U.alloc<double>(amg->L.size() * AMG_CHEB_STRIDE);
-    amg->scal = U.alloc<double>(2);
-    amg->part = U.alloc<double>((size_t)amg->part_cap);
-    amg->flag = U.alloc<int>(4);
+    if (!soc) {
+        for (const amg_level& v : amg->L) amg->part_cap = std::max({amg->part_cap, rho_parts(v), init_parts(v)});
+        amg->omega = U.alloc<double>(amg->L.size());
+        amg->rho = U.alloc<double>(amg->L.size());
+        amg->cheb = U.alloc<double>(amg->L.size() * AMG_CHEB_STRIDE);
+        amg->scal = U.alloc<double>(2);
+        amg->part = U.alloc<double>((size_t)amg->part_cap);
+        amg->flag = U.alloc<int>(4);
+    } else {
+        for (const amg_level& v : amg->L)
+            if (std::max(rho_parts(v), init_parts(v)) > amg->part_cap) return dxo_fail(ctx, DXO_E_SIZE, "amg.hip: a level outgrew the partials of the first");
+        int h = 0;
+        DXO_HIP(ctx, hipGetLastError());
+        DXO_HIP(ctx, hipMemcpyAsync(&h, amg->flag, sizeof h, hipMemcpyDeviceToHost, s));
+        DXO_HIP(ctx, hipStreamSynchronize(s));
+        if (h) return dxo_fail(ctx, DXO_E_SINGULAR, (std::string(who) + ": a diagonal block of a level is singular").c_str());
+    }
     amg->dense[0] = U.alloc<double>((size_t)(2 * amg->nc * amg->nc));
     amg->dense[1] = U.alloc<double>((size_t)(2 * amg->nc * amg->nc));
     return U.rc;
-}
-
-bool amg_misaligned(const void* p) { return ((uintptr_t)p & 7u) != 0; }
-
-// B_0 = the caller's B with the rows of constrained dofs zero, then level by level T_l and B_{l+1}; once, at creation
-int amg_near_nullspace(dxo_ctx* ctx, dxo_amg* amg, const double* B, hipStream_t s) {
-    const int k = amg->k, nl = (int)amg->L.size();
-    const double tol = std::pow(10.0, -(double)ctx->amg_rank_tol);
-    amg_level& f = amg->L[0];
-    if (f.n_rows > 0) {
-        DXO_HIP(ctx, hipMemcpyAsync(f.b_val, B, (size_t)(f.n_rows * k) * sizeof(double), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(amg_zero_rows, amg_grid(f.n_rows), dim3(DXO_AMG_BLOCK), 0, s, f.n_rows, k, f.mask, f.b_val);
-    }
-    for (int l = 0; l + 1 < nl; ++l) {
-        amg_level& v = amg->L[(size_t)l];
-        DXO_HIP(ctx, hipMemsetAsync(v.t_val, 0, (size_t)(v.n_nodes * v.bs * k) * sizeof(double), s));      // nodes without an aggregate
-        if (v.n_agg > 0) tentative_launch(v, amg->L[(size_t)l + 1].b_val, tol, s);
-    }
-    DXO_HIP(ctx, hipGetLastError());
-    DXO_HIP(ctx, hipStreamSynchronize(s));
-    for (int l = 0; l + 1 < nl; ++l) {
-        amg_level& v = amg->L[(size_t)l];
-        std::vector<uint8_t> d((size_t)v.n_agg);
-        if (v.n_agg > 0) DXO_HIP(ctx, hipMemcpy(d.data(), v.dead_a, d.size(), hipMemcpyDeviceToHost));
-        v.dead = 0;
-        for (uint8_t x : d) v.dead += x;
-    }
-    return DXO_OK;
 }
 
 }  // namespace
@@ -1492,7 +1856,7 @@ namespace {
 
 // the symbolic phase and, with a near-null space (k > 0, B on the device), T and B of every level
 int amg_create(dxo_ctx* ctx, const char* who, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, const double* Bnns, int k,
-               int max_levels, int coarse_rows, int sweeps, dxo_amg** out) {
+               int max_levels, int coarse_rows, int sweeps, dxo_amg** out, double theta = 0.0, const double* values = nullptr) {
     if (n_constrained < 0 || max_levels < 1 || coarse_rows < 1 || sweeps < 1)
         return dxo_fail(ctx, DXO_E_SIZE, (std::string(who) + ": n_constrained < 0, or max_levels, coarse_rows or sweeps < 1").c_str());
     DXO_HIP(ctx, hipSetDevice(ctx->device));
@@ -1504,8 +1868,9 @@ int amg_create(dxo_ctx* ctx, const char* who, const dxo_csr* csr, const int32_t*
     a->bs = csr->bs;
     a->sweeps = sweeps;
     a->k = k;
-    int rc = amg_build(ctx, who, a, csr, constrained, n_constrained, max_levels, coarse_rows, k);
-    if (rc == DXO_OK && k > 0) rc = amg_near_nullspace(ctx, a, Bnns, s);
+    a->theta = theta;
+    int rc = amg_build(ctx, who, a, csr, constrained, n_constrained, max_levels, coarse_rows, k, theta, values, Bnns, s);
+    if (rc == DXO_OK && k > 0) rc = theta > 0.0 ? amg_nns_dead(ctx, a, s) : amg_near_nullspace(ctx, a, Bnns, s);
     if (rc != DXO_OK) {
         amg_free(a);
         return rc;
@@ -1537,6 +1902,47 @@ extern "C" int dxo_amg_create_nns(dxo_ctx* ctx, const dxo_csr* csr, const int32_
         return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create_nns: (bs, n_modes) must be (2, 3) or (3, 6)");
     if (amg_misaligned(B)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_amg_create_nns: B must be 8-byte aligned");
     return amg_create(ctx, "dxo_amg_create_nns", csr, constrained, n_constrained, B, n_modes, max_levels, coarse_rows, sweeps, out);
+}
+
+extern "C" int dxo_amg_create_soc(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const int32_t* constrained, int64_t n_constrained,
+                                  const double* B, int n_modes, double theta, int max_levels, int coarse_rows, int sweeps, dxo_amg** out) {
+    if (!ctx || !out) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    *out = nullptr;
+    if (!csr || !values || (n_constrained > 0 && !constrained) || (n_modes != 0 && !B))
+        return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_create_soc: NULL argument");
+    if (!(theta >= 0.0 && theta < 1.0)) return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_create_soc: theta must lie in [0, 1)");
+    if (csr->bs < 1 || csr->bs > 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create_soc: bs must be 1, 2 or 3");
+    if (n_modes != 0 && !((csr->bs == 2 && n_modes == 3) || (csr->bs == 3 && n_modes == 6)))
+        return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create_soc: (bs, n_modes) must be (2, 3) or (3, 6), or n_modes 0");
+    if (amg_misaligned(values) || (n_modes != 0 && amg_misaligned(B)))
+        return dxo_fail(ctx, DXO_E_ALIGN, "dxo_amg_create_soc: values and B must be 8-byte aligned");
+    return amg_create(ctx, "dxo_amg_create_soc", csr, constrained, n_constrained, n_modes ? B : nullptr, n_modes, max_levels, coarse_rows, sweeps, out,
+                      theta, values);
+}
+
+extern "C" int dxo_amg_soc_info(dxo_ctx* ctx, const dxo_amg* amg, int level, double* theta, const uint8_t** strong, int64_t* n_strong_blocks,
+                                int64_t* n_unlumped_nodes, const double** dinv_f, const double** omega_f) {
+    if (!ctx || !amg) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (level < 0 || level >= (int)amg->L.size()) return dxo_fail(ctx, DXO_E_SIZE, "dxo_amg_soc_info: no such level");
+    const amg_level& v = amg->L[(size_t)level];
+    if (theta) *theta = amg->theta;
+    if (strong) *strong = v.strong;
+    if (n_strong_blocks) *n_strong_blocks = v.strong ? v.n_strong : v.nnzb;
+    if (dinv_f) *dinv_f = v.dinv_f;
+    if (omega_f) *omega_f = v.strong ? amg->omega_f + level : nullptr;
+    if (n_unlumped_nodes) {
+        *n_unlumped_nodes = 0;
+        if (v.strong && v.n_nodes > 0) {      // the marks of the last setup: a wait and a copy
+            std::vector<uint8_t> h((size_t)v.n_nodes);
+            DXO_HIP(ctx, hipSetDevice(amg->device));
+            DXO_HIP(ctx, hipStreamSynchronize(dxo_launch_stream(ctx)));
+            DXO_HIP(ctx, hipMemcpy(h.data(), v.unlumped, h.size(), hipMemcpyDeviceToHost));
+            for (uint8_t m : h) *n_unlumped_nodes += m;
+        }
+    }
+    return DXO_OK;
 }
 
 extern "C" int dxo_rigid_body_modes(dxo_ctx* ctx, const double* x, int64_t n_nodes, int gdim, double* B) {
@@ -1620,7 +2026,6 @@ extern "C" int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values) {
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     amg->ready = false;
     const int nl = (int)amg->L.size();
-    const bool nns = amg->k > 0;
     const dim3 B(DXO_AMG_BLOCK);
     amg->L[0].values = values;
     int rc = dxo_device_begin(ctx, s);
@@ -1630,44 +2035,7 @@ extern "C" int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values) {
         amg_level& v = amg->L[(size_t)l];
         amg_level& c = amg->L[(size_t)l + 1];
         if (v.n_nodes == 0) continue;
-        const int bs = v.bs;
-        if (bs == 6) hipLaunchKernelGGL(amg_bj6, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, amg->flag);
-        else dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
-        double* cheb = amg->cheb + (size_t)l * AMG_CHEB_STRIDE;
-        if (amg->rho_kind == DXO_AMG_RHO_POWER) {
-            // v_0 in xa, then w = Dinv A (v / |v|) back and forth between xa and xb: the cycle's vectors are free during a setup
-            double *from = v.xa, *to = v.xb;
-            hipLaunchKernelGGL(amg_power_init, amg_grid(v.n_rows), B, 0, s, v.n_rows, from, amg->part);
-            hipLaunchKernelGGL(amg_power_norm, dim3(1), B, 0, s, amg->part, init_parts(v), 0, amg->safety, amg->lower, amg->degree, amg->scal,
-                               amg->rho + l, amg->omega + l, cheb);
-            for (int it = 0; it < amg->rho_iters; ++it) {
-                if (bs == 1) power_bs<1>(v, amg->scal, from, to, amg->part, s);
-                else if (bs == 2) power_bs<2>(v, amg->scal, from, to, amg->part, s);
-                else if (bs == 3) power_bs<3>(v, amg->scal, from, to, amg->part, s);
-                else if (bs == 6) power_bs<6>(v, amg->scal, from, to, amg->part, s);
-                else amg_no_shape(bs, bs);
-                hipLaunchKernelGGL(amg_power_norm, dim3(1), B, 0, s, amg->part, rho_parts(v), it + 1 == amg->rho_iters ? 1 : 0, amg->safety,
-                                   amg->lower, amg->degree, amg->scal, amg->rho + l, amg->omega + l, cheb);
-                std::swap(from, to);
-            }
-        } else {
-            if (bs == 1) rho_bs<1>(v, amg->part, s);
-            else if (bs == 2) rho_bs<2>(v, amg->part, s);
-            else if (bs == 3) rho_bs<3>(v, amg->part, s);
-            else if (bs == 6) rho_bs<6>(v, amg->part, s);
-            else amg_no_shape(bs, bs);
-            hipLaunchKernelGGL(amg_omega, dim3(1), B, 0, s, amg->part, rho_parts(v), amg->omega + l, amg->rho + l);
-            if (amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV)
-                hipLaunchKernelGGL(amg_cheby_coeffs, dim3(1), dim3(64), 0, s, amg->rho + l, amg->lower, amg->degree, cheb);
-        }
-        build_p_launch(v, nns, amg->omega + l, s);
-        AMG_PAIR(bs, v.bsc, amg_build_ap, amg_grid(v.ap_blocks), B, 0, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr,
-                 v.p_col, v.p_val, v.ap_val);
-        double* cv = const_cast<double*>(c.values);
-        AMG_PAIR(bs, v.bsc, amg_build_c, amg_grid(v.c_blocks), B, 0, s, v.c_blocks, v.c_row, v.c_bptr, c.A->d_row_ptr, c.A->d_col, v.pt_ptr, v.pt_blk,
-                 v.p_row, v.p_val, v.ap_ptr, v.ap_col, v.ap_val, cv);
-        // the values-dependent mask belongs to the identity form of T; with a near-null space T is fixed at creation
-        if (!nns) hipLaunchKernelGGL(amg_row_mask, amg_grid(c.n_rows), B, 0, s, c.n_rows, c.A->d_row_ptr, c.A->d_col, c.values, c.mask);
+        amg_setup_level(amg, l, v, c, s);
     }
     const amg_level& c = amg->L.back();
     const int64_t n = amg->nc;

@@ -127,46 +127,6 @@ __global__ __launch_bounds__(DXO_KR_BLOCK) void csr_spmv(int64_t n_nodes, const 
 
 // ---- block Jacobi
 template <int BS>
-__device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (&b)[BS][BS]) {
-    double had = 1.0;
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < BS; ++j) s += a[i][j] * a[i][j];
-        had *= sqrt(s);
-    }
-    double det;
-    if constexpr (BS == 1) {
-        det = a[0][0];
-        b[0][0] = 1.0 / det;
-    } else if constexpr (BS == 2) {
-        det = a[0][0] * a[1][1] - a[0][1] * a[1][0];
-        const double id = 1.0 / det;
-        b[0][0] = a[1][1] * id;
-        b[0][1] = -a[0][1] * id;
-        b[1][0] = -a[1][0] * id;
-        b[1][1] = a[0][0] * id;
-    } else {
-        const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1];
-        const double c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2];
-        const double c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];
-        det = a[0][0] * c00 + a[0][1] * c01 + a[0][2] * c02;
-        const double id = 1.0 / det;
-        b[0][0] = c00 * id;
-        b[1][0] = c01 * id;
-        b[2][0] = c02 * id;
-        b[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) * id;
-        b[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) * id;
-        b[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) * id;
-        b[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) * id;
-        b[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) * id;
-        b[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) * id;
-    }
-    return fabs(det) > 1e-14 * had;     // false for a zero, NaN or nearly singular block
-}
-
-template <int BS>
 __global__ __launch_bounds__(DXO_KR_BLOCK) void bj_setup(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                          const double* __restrict__ values, double* __restrict__ inv, int* __restrict__ singular) {
     const int64_t node = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x;

@@ -125,13 +125,26 @@ class AMG:
     bound). `smoother`: "jacobi" (`sweeps` damped block-Jacobi sweeps) or "chebyshev" (the polynomial of `degree` in Dinv A on
     [lower rho, rho] before and after the coarse correction; `degree` None: `sweeps`, at most 8). The defaults rho_iters 10,
     lower 0.1 and safety 1.1 are the customary rule (PETSc's), not measurements on this library. With the default smoother and rho
-    the object is the one of earlier versions bit for bit."""
+    the object is the one of earlier versions bit for bit.
+
+    `strength`: the threshold theta of the strength of connection, in [0, 1) (dxo_amg_create_soc). 0 (the default): every stored
+    block is a connection, the object of earlier versions. theta > 0: block (i, j) is strong when
+    |A_ij|_F^2 >= theta^2 |A_ii|_F |A_jj|_F for (i, j) or (j, i); the aggregates are made on the strong graph and the prolongator is
+    smoothed with the filtered matrix (weak blocks lumped onto the diagonal), which is what anisotropic operators and stretched
+    cells need (0.25 is customary for scalar problems). The masks, and with them the aggregates and all patterns, are made from the
+    values of the matrix at construction and are frozen there: setup() reuses them for new values, and set_smoother() changes the
+    relaxation but not the coarsening (the construction itself coarsens with the default relaxation)."""
 
     def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None,
                  smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10, lower: float = 0.1,
-                 safety: float = 1.1):
+                 safety: float = 1.1, strength: float = 0.0):
         torch = _torch()
         import numpy as np
+
+        strength = float(strength)
+        if not 0.0 <= strength < 1.0:          # NaN fails both comparisons
+            raise ValueError("AMG: strength must lie in [0, 1)")
+        self.strength = strength
 
         self.ctx, self.A, self.bs, self.n = A.pattern.ctx, A, A.pattern.bs, A.pattern.n_rows
         self.device = A.values.device
@@ -149,7 +162,11 @@ class AMG:
         _use_current_stream(self.ctx)
         bcp = C.c_void_p(bc.data_ptr()) if bc.numel() else None
         self.n_modes = 0
-        if near_nullspace is None:
+        if near_nullspace is None and strength > 0.0:
+            rc = self.ctx.lib.dxo_amg_create_soc(self.ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), bcp, int(bc.numel()), None, 0, strength,
+                                                 int(max_levels), int(coarse_rows), int(sweeps), C.byref(h))
+            self.ctx.check(rc, "dxo_amg_create_soc")
+        elif near_nullspace is None:
             rc = self.ctx.lib.dxo_amg_create(self.ctx._h, A.pattern._h, bcp, int(bc.numel()), int(max_levels), int(coarse_rows), int(sweeps),
                                              C.byref(h))
             self.ctx.check(rc, "dxo_amg_create")
@@ -161,9 +178,15 @@ class AMG:
                 raise ValueError(f"AMG: near_nullspace must be a float64 CUDA tensor of shape ({self.n}, {k}) on {self.device} "
                                  f"(bs 2: 3 vectors, bs 3: 6 vectors; this matrix has bs {self.bs})")
             B = B.contiguous()
-            rc = self.ctx.lib.dxo_amg_create_nns(self.ctx._h, A.pattern._h, bcp, int(bc.numel()), C.c_void_p(B.data_ptr()), k, int(max_levels),
-                                                 int(coarse_rows), int(sweeps), C.byref(h))
-            self.ctx.check(rc, "dxo_amg_create_nns")
+            if strength > 0.0:
+                rc = self.ctx.lib.dxo_amg_create_soc(self.ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), bcp, int(bc.numel()),
+                                                     C.c_void_p(B.data_ptr()), k, strength, int(max_levels), int(coarse_rows), int(sweeps),
+                                                     C.byref(h))
+                self.ctx.check(rc, "dxo_amg_create_soc")
+            else:
+                rc = self.ctx.lib.dxo_amg_create_nns(self.ctx._h, A.pattern._h, bcp, int(bc.numel()), C.c_void_p(B.data_ptr()), k,
+                                                     int(max_levels), int(coarse_rows), int(sweeps), C.byref(h))
+                self.ctx.check(rc, "dxo_amg_create_nns")
             self.n_modes = k
         self._h = h
         self._fin = weakref.finalize(self, self.ctx.lib.dxo_amg_destroy, None, h)
@@ -250,16 +273,52 @@ class AMG:
                                                      C.byref(b)), "dxo_amg_nns_info")
         return bs.value, bsc.value, dead.value, t.value, b.value
 
+    def _soc(self, level: int, count: bool = False):
+        """(theta, mask pointer, strong blocks, unlumped nodes or None, dinv_f pointer, omega_F pointer) of a level
+        (dxo_amg_soc_info)."""
+        th, st, ns, nu, df, of = C.c_double(), C.c_void_p(), C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.dxo_amg_soc_info(self.ctx._h, self._h, int(level), C.byref(th), C.byref(st), C.byref(ns),
+                                                     C.byref(nu) if count else None, C.byref(df), C.byref(of)), "dxo_amg_soc_info")
+        return th.value, st.value, ns.value, (nu.value if count else None), df.value, of.value
+
     @property
     def levels(self) -> list:
-        """Per level: rows, block nonzeros, the block size and omega (None on the coarsest level). Reading omega synchronises the
+        """Per level: rows, block nonzeros, the block size, omega (None on the coarsest level) and omega_f, the omega of the filtered
+        prolongator smoothing (None without strength of connection and on the coarsest level). Reading them synchronises the
         stream."""
         out = []
         for l in range(self.n_levels):
             i = self._info(l)
             om = float(self._array(i.omega, 1, "<f8")[0]) if i.omega else None
-            out.append({"rows": int(i.n_rows), "nodes": int(i.n_nodes), "block_nnz": int(i.nnz_blocks), "omega": om, "bs": self._nns(l)[0]})
+            of = self._soc(l)[5]
+            out.append({"rows": int(i.n_rows), "nodes": int(i.n_nodes), "block_nnz": int(i.nnz_blocks), "omega": om, "bs": self._nns(l)[0],
+                        "omega_f": float(self._array(of, 1, "<f8")[0]) if of else None})
         return out
+
+    def strong_mask(self, level: int):
+        """A NumPy bool per block of `level`, in the CSR order of its block pattern: the strong blocks, frozen at construction (all
+        True without strength of connection and on the coarsest level)."""
+        import numpy as np
+
+        i = self._info(level)
+        st = self._soc(level)[1]
+        if not st:
+            return np.ones(int(i.nnz_blocks), dtype=bool)
+        return self._array(st, i.nnz_blocks, "|u1").astype(bool)
+
+    @property
+    def unlumped_nodes(self) -> list:
+        """Per level but the coarsest: the nodes whose lumped diagonal block failed the singularity test at the last setup, so
+        that the filtered smoothing used the inverse of A_ii for them (0 without strength of connection)."""
+        return [self._soc(l, count=True)[3] for l in range(self.n_levels - 1)]
+
+    def level_dinv_f(self, level: int):
+        """The inverses of the lumped diagonal blocks of `level`, (nodes, bs, bs): those of A_ii where the lumped block failed the
+        test, zero for a node without a strong neighbour. Empty without strength of connection and on the coarsest level."""
+        i = self._info(level)
+        bs = self._nns(level)[0]
+        df = self._soc(level)[4]
+        return self._array(df, i.n_nodes * bs * bs if df else 0, "<f8").reshape(-1, bs, bs)
 
     def _smoother_info(self, level: int):
         """(kind, degree, rho kind, rho_iters, rho pointer) of a level (dxo_amg_smoother_info)."""

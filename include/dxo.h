@@ -699,7 +699,33 @@ int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const d
  *                   Chebyshev degree outside 1..8, rho_iters < 1, lower outside (0, 1), safety < 1: DXO_E_OPTION, nothing changes.
  *                   Allocates nothing: the one extra vector per level was allocated at creation.
  * dxo_amg_smoother_info : the settings (degree: `sweeps` for Jacobi) and the DEVICE address of the rho of `level` that omega was made
- *                   from at the last setup, under either estimate (NULL on the coarsest level); any pointer may be NULL. */
+ *                   from at the last setup, under either estimate (NULL on the coarsest level); any pointer may be NULL.
+ *
+ * Strength of connection (anisotropic operators, stretched cells): coarsen only along strong couplings.
+ * dxo_amg_create_soc : dxo_amg_create (B NULL, n_modes 0) or dxo_amg_create_nns with the threshold theta and the matrix `values`
+ *                   (DEVICE, on the pattern of csr). theta == 0: the object of those two calls bit for bit, `values` is not read.
+ *                   theta > 0: block (i, j), i != j, of a level is strong when |A_ij|_F^2 >= theta^2 |A_ii|_F |A_jj|_F or the same
+ *                   holds for (j, i) (an absent transposed block: the one-sided test); the squares are summed entry by entry in
+ *                   row-major order and compared in double. Diagonal blocks are strong. The aggregates are those of the three
+ *                   passes on the strong graph (a node without a strong neighbour founds an aggregate of its own in pass 1), P has
+ *                   the pattern (strong graph) x (aggregates), A P and P^T A P are built from the full graph. Because the mask of a
+ *                   coarse level needs the coarse matrix, creation runs the numeric phase of every level as it goes (one
+ *                   synchronisation per level, here only), with the default relaxation (Jacobi, infinity norm). The masks, the
+ *                   aggregates and all patterns are frozen at creation: dxo_amg_setup (still required before the first apply, still
+ *                   device-only, allocation-free and single-wait) reuses them for new values, and a later dxo_amg_set_smoother
+ *                   changes omega but not the masks. In every setup the prolongator is P = T - omega_F Dinv_F A^F T with A^F the
+ *                   matrix without its weak blocks, each added onto the diagonal block of its row in ascending column order (never
+ *                   stored), Dinv_F the inverses of those lumped blocks, omega_F = (4/3) / rho_F and rho_F the selected estimate
+ *                   (infinity norm or power iteration) of Dinv_F A^F. A lumped block that fails the singularity test of
+ *                   dxo_csr_block_jacobi is replaced by A_ii in Dinv_F for that node (counted); a node without a strong
+ *                   off-diagonal block is not smoothed: its row of P is its row of T. The sweeps and the Chebyshev smoother keep A,
+ *                   Dinv and rho. The stopping rules are those of dxo_amg_create; a theta that leaves nothing strong gives one
+ *                   level (DXO_E_SIZE above 4096 rows). theta < 0, >= 1 or not finite: DXO_E_OPTION; values NULL: DXO_E_NULL;
+ *                   values or B misaligned: DXO_E_ALIGN; a singular diagonal block met on the way: DXO_E_SINGULAR.
+ * dxo_amg_soc_info : theta, the DEVICE mask of `level` (one uint8 per block, in the order of the level's block pattern), its number
+ *                   of strong blocks, the nodes whose lumped block failed the test at the last setup (waits for the stream), and
+ *                   the DEVICE arrays dinv_f [n_nodes][bs][bs] and omega_F (one double). Any pointer may be NULL. On an object made
+ *                   without strength, and on the coarsest level: NULL arrays, every block strong, 0 nodes; theta is the object's. */
 #define DXO_AMG_SMOOTH_JACOBI 0
 #define DXO_AMG_SMOOTH_CHEBYSHEV 1
 #define DXO_AMG_RHO_INF_NORM 0
@@ -737,6 +763,10 @@ int dxo_amg_nns_info(dxo_ctx* ctx, const dxo_amg* amg, int level, int* bs, int* 
 int dxo_amg_set_smoother(dxo_ctx* ctx, dxo_amg* amg, int kind, int degree, int rho_kind, int rho_iters, double lower, double safety);
 int dxo_amg_smoother_info(dxo_ctx* ctx, const dxo_amg* amg, int level, int* kind, int* degree, int* rho_kind, int* rho_iters,
                           const double** rho);
+int dxo_amg_create_soc(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const int32_t* constrained, int64_t n_constrained,
+                       const double* B, int n_modes, double theta, int max_levels, int coarse_rows, int sweeps, dxo_amg** out);
+int dxo_amg_soc_info(dxo_ctx* ctx, const dxo_amg* amg, int level, double* theta, const uint8_t** strong, int64_t* n_strong_blocks,
+                     int64_t* n_unlumped_nodes, const double** dinv_f, const double** omega_f);
 
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is

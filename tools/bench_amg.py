@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Standalone timing of the multigrid preconditioner (csrc/amg.hip; not a bench.py leg).
-    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG]
+    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG] [--strength THETA[,THETA...]]
 Systems (distorted meshes, the lower side clamped so that the matrices are regular):
   p2       ("grad", "grad", 2) on P2 triangles with C = I + 0.3 N(0, 1) per point (1291 per side: 10^7 points), as tools/bench_krylov.py
   q2hex    ("eps", "eps", 3) on Q2 hexahedra (40^3 boxes), the same kind of C
+  aniso_*  ("grad", "grad", 1) with C = diag(1, 1e-3) on the heat meshes (P1, Dirichlet boundary), only with --strength
   heat_*   the heat-type Jacobian of tools/bench_krylov.py (P1, ("grad", "value_grad"), Dirichlet boundary) at two sizes (256, 1024)
 Per system: dxo_csr_spmv ms, dxo_bilinear_assemble ms, the symbolic phase (host, once), dxo_amg_setup ms, dxo_amg_apply ms and its ratio
 to one SpMV beside the model 2 + 3 (c - 1) (c the operator complexity), rows per level, and one GMRES(30) solve to rtol 1e-8 (at most
@@ -13,6 +14,10 @@ with the rigid-body modes as near-null space (keys ending in _rbm; symbolic_ms_r
 --cheby DEG adds, for every hierarchy measured (those of --rbm included), the figures of two more relaxations on the same object in the
 same run, beside the default's (|Dinv A|_inf, damped Jacobi): power_jacobi (rho from the power iteration, Jacobi) and power_cheby<DEG>
 (that rho, Chebyshev of degree DEG): setup ms, apply ms, rho per level, and the GMRES(30) solve (iterations, ms, ms_with_setup).
+--strength adds, for every hierarchy measured (those of --rbm included) and every THETA, the hierarchy with strength-of-connection
+coarsening and filtered prolongator smoothing (keys ending in _soc<THETA>): creation ms (it includes the numeric phase of every level),
+rows per level, operator complexity, setup ms, apply ms, the nodes that fell back to A_ii, and the GMRES(30) solve; with --cheby DEG the
+solve is repeated with power_cheby<DEG> on that hierarchy.
 Timing: warm-up, then 5 batches timed with HIP events on the launch stream, the MEDIAN batch reported (tools/bench_krylov._batches).
 Prints one JSON line."""
 from __future__ import annotations
@@ -27,7 +32,7 @@ if str(ROOT) not in sys.path:
 
 
 def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000, rbm: bool = False,
-         cheby: int = 0) -> dict:
+         cheby: int = 0, strengths: tuple = ()) -> dict:
     import numpy as np
     import torch
 
@@ -57,6 +62,22 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
             f.update({"iterations": out.iterations, "converged": out.converged, "residual": out.residual, "ms": round(out.ms, 2),
                       "ms_with_setup": round(out.ms + f["setup_ms"], 2)})
             r[key + suffix] = f
+
+    def with_strength(A, bcs, nns, b, x, y, r, suffix):
+        for theta in strengths:
+            amg = A.amg(bcs, near_nullspace=nns, strength=theta)
+            f = {"creation_ms": round(amg.build_ms, 1), "setup_ms": timed(lambda: amg.setup(), 3), "apply_ms": timed(lambda: amg.apply(x, y), 20),
+                 "rows": [d["rows"] for d in amg.levels], "operator_complexity": round(amg.operator_complexity, 4),
+                 "unlumped_nodes": amg.unlumped_nodes}
+            relax = [("gmres30", {})] + ([(f"gmres30_power_cheby{cheby}", {"smoother": "chebyshev", "degree": cheby, "rho": "power"})] if cheby else [])
+            for key, kw in relax:
+                if kw:
+                    amg.set_smoother(**kw).setup()
+                gmres(A, b, M=amg, rtol=1e-8, maxiter=30)                    # warm-up
+                out = gmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
+                f[key] = {"iterations": out.iterations, "converged": out.converged, "residual": out.residual, "ms": round(out.ms, 2)}
+            r[f"amg{suffix}_soc{theta:g}"] = f
+            amg.close()
 
     def system(tag, m, test, trial, bs, Cd, bnd):
         dm = DeviceMesh.from_synthetic(m, ctx=ctx)
@@ -90,6 +111,7 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                 if cheby:
                     relaxations(amg, A, b, x, y, r, "")
                 amg.close()
+                with_strength(A, bcs, None, b, x, y, r, "")
                 if rbm and bs == m.gdim:
                     amg = A.amg(bcs, near_nullspace=rigid_body_modes(m.node_x, ctx=ctx))
                     r["symbolic_ms_rbm"] = round(amg.build_ms, 1)
@@ -105,6 +127,7 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                     if cheby:
                         relaxations(amg, A, b, x, y, r, "_rbm")
                     amg.close()
+                    with_strength(A, bcs, rigid_body_modes(m.node_x, ctx=ctx), b, x, y, r, "_rbm")
             stream.synchronize()
             res["systems"][tag] = r
             print(tag, json.dumps(r), file=sys.stderr, flush=True)
@@ -126,6 +149,9 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
         Cb[:, 0, 1] = Cb[:, 1, 2] = 1.0 + 0.5 * np.random.Generator(np.random.PCG64(0)).random(npts)
         bnd = np.flatnonzero((m.node_x.min(axis=1) < 1e-12) | (m.node_x.max(axis=1) > 1 - 1e-12))
         system(f"heat_{n}", m, "grad", "value_grad", 1, torch.from_numpy(Cb.reshape(-1)).to(dev), bnd)
+        if strengths:
+            Ca = np.broadcast_to(np.diag([1.0, 1e-3]), (npts, 2, 2)).copy()
+            system(f"aniso_{n}", m, "grad", "grad", 1, torch.from_numpy(Ca.reshape(-1)).to(dev), bnd)
     cases = [("p2", "triangle", (n_side, n_side), "grad", "grad", 2), ("q2hex", "hexahedron", (n_hex, n_hex, n_hex), "eps", "eps", 3)]
     if rbm:
         cases.append(("p2eps", "triangle", (n_side, n_side), "eps", "eps", 2))
@@ -158,7 +184,12 @@ if __name__ == "__main__":
         i = args.index("--cheby")
         cheby = int(args[i + 1])
         del args[i:i + 2]
-    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby)
+    strengths = ()
+    if "--strength" in args:
+        i = args.index("--strength")
+        strengths = tuple(float(t) for t in args[i + 1].split(","))
+        del args[i:i + 2]
+    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby, strengths=strengths)
     line = json.dumps(r)
     print(line)
     if out_file:
