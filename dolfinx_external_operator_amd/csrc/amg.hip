@@ -15,26 +15,28 @@
 // buffers (every workgroup finds the pivot of the step itself, so a step needs no grid-wide wait). No atomics: a setup is
 // bit-reproducible. The host waits once, at the end, for one flag word.
 //
-// Apply (dxo_amg_cycle): per level x = omega Dinv r, then x <- x + omega Dinv (r - A x) in the lane-group shape of csr_spmv (LW lanes
-// own a node, fixed xor-butterfly) with the update in the epilogue, t = r - A x by the same kernel, r_c = P^T t gathered through the
+// Apply (dxo_amg_cycle): per level x = omega Dinv r (amg_first_step), then x <- x + omega Dinv (r - A x) with A x by the row_product of
+// krylov_internal.h, which csr_spmv is made of too (LW lanes own a node, fixed xor-butterfly), and the update in the epilogue,
+// t = r - A x by the same kernel, r_c = P^T t gathered through the
 // transposed incidence in ascending fine-node order, x += P x_c, the same sweeps again; the coarsest level is one dense product.
 //
 // With a near-null space (dxo_amg_create_nns: B [n_rows][k], the rigid-body modes of dxo_rigid_body_modes, k = 3 for bs 2 and 6 for
-// bs 3) the tentative prolongator is not an identity per node: after the symbolic phase, once, amg_tentative orthonormalises the rows of
-// B of every aggregate (ascending node order; Gram-Schmidt in column order with a second pass; a lane group owns an aggregate, column
+// bs 3) the tentative prolongator is not an identity per node: at creation, as soon as a level has its aggregates, amg_tentative
+// orthonormalises the rows of B of every aggregate (ascending node order; Gram-Schmidt in column order with a second pass; a lane group owns an aggregate, column
 // products by the xor-butterfly), keeps the Q factors as the blocks of T ([n_nodes][bs_l][k]) and the R factors as the B of the next
 // level. A column that keeps no more than rank_tol of its norm is dead: its Q column and its row of the next B are zero, so it stays out
 // on every coarser level and its coarse diagonal entry, exactly zero, becomes 1. Every coarse level then has block size k; the kernels
 // of P, A P, P^T A P, restriction and prolongation take <BSR, BSC> (rows of the level, rows of the next), and the levels of block
-// size 6 invert their diagonal blocks by Gauss-Jordan with partial pivoting in registers (rows exchanged by compare-and-select).
+// size 6 invert their diagonal blocks by the kernel and the invert_block of the others (there: Gauss-Jordan with partial pivoting in
+// registers, rows exchanged by compare-and-select).
 // T and B depend on B_0, the aggregates and the constraints alone: dxo_amg_setup does not touch them.
 //
 // The relaxation (dxo_amg_set_smoother; the default is what is described above). rho from the power iteration: amg_power_init writes
-// the fixed start vector, amg_power_step forms w = Dinv (A (s v)) in the shape of amg_sweep together with the workgroup's partial of
+// the fixed start vector, amg_power_step forms w = Dinv (A (s v)) by row_product together with the workgroup's partial of
 // |w|^2, and the one-workgroup amg_power_norm adds the partials in a fixed order and leaves s = 1 / |w| on the device for the next step;
 // after the last step it stores rho = safety |w|, omega = (4/3) / rho and the level's Chebyshev pairs. The vectors are xa and xb of the
-// level, free during a setup; the setup still waits once, at its end. Chebyshev smoothing: amg_cheby0 (the first step from x = 0, no
-// SpMV) and amg_cheby_sweep (d = c1 d + c2 Dinv (r - A x), x_out = x + d; d in place, x between xa and xb as the Jacobi sweeps) with
+// level, free during a setup; the setup still waits once, at its end. Chebyshev smoothing: amg_first_step with the first c2 (the step
+// from x = 0, no SpMV, d = x) and amg_cheby_sweep (d = c1 d + c2 Dinv (r - A x), x_out = x + d; d in place, x between xa and xb as the Jacobi sweeps) with
 // the pairs (c1, c2) read from the device like omega; the post-smoothing is the same polynomial started from the corrected x.
 //
 // Strength of connection (dxo_amg_create_soc with theta > 0). Block (i, j) is strong when |A_ij|_F^2 >= theta^2 |A_ii|_F |A_jj|_F or
@@ -46,7 +48,13 @@
 // prolongator is smoothed with the filtered matrix A^F (weak blocks added onto the diagonal block of their row, never stored):
 // amg_lump forms the lumped diagonal blocks and their inverses dinv_f (a block that fails the test of invert_block: the inverse of
 // A_ii, counted; a node without a strong neighbour: zero, its row of P is its row of T), amg_rho / amg_power_step estimate the rho_F
-// of Dinv_F A^F given the mask, omega_F = (4/3) / rho_F, and amg_build_p skips the weak blocks. The sweeps keep A, Dinv and rho.
+// of Dinv_F A^F given the mask, omega_F = (4/3) / rho_F, and amg_build_p skips the weak blocks (all three through amg_filtered_block).
+// The sweeps keep A, Dinv and rho.
+//
+// Host side. Run-time shapes reach the templates through one dispatcher (with_int / with_pairs and their named lists: with_bs,
+// with_level, with_pair, with_square, with_nns_pair), so a kernel's argument list is written once. amg_build allocates the device scalars
+// of every level once, before the level loop, and walks read pattern -> [strength mask] -> aggregates -> transfer tables -> coarse
+// level -> [T and B] -> [numeric phase] per level, the bracketed stages on the hierarchies that have them.
 #include "krylov_internal.h"
 
 #include <algorithm>
@@ -54,6 +62,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #ifndef DXO_AMG_BLOCK
 #define DXO_AMG_BLOCK 256
@@ -137,17 +146,6 @@ struct dxo_amg {
 namespace {
 
 // ---- device helpers
-template <int BS>
-struct NodeRow {
-    int64_t r0, len;
-    int nnb;
-    __device__ __forceinline__ NodeRow(const int64_t* __restrict__ row_ptr, int64_t node) {
-        r0 = row_ptr[node * BS];
-        len = row_ptr[node * BS + 1] - r0;
-        nnb = (int)(len / BS);
-    }
-};
-
 // position of v in the ascending run col[lo, hi), or -1
 __device__ __forceinline__ int64_t amg_find(const int32_t* __restrict__ col, int64_t lo, int64_t hi, int32_t v) {
     while (lo < hi) {
@@ -158,6 +156,25 @@ __device__ __forceinline__ int64_t amg_find(const int32_t* __restrict__ col, int
         else return mid;
     }
     return -1;
+}
+
+// block k of a node's row in the matrix the prolongator is smoothed with. Without a mask (strong == nullptr) that is A: the stored
+// block. With one it is the filtered matrix A^F: false for a weak block (skip it), and the diagonal block (`diagonal`, looked at only
+// with a mask) is the lumped one, diag_f[node] with leading dimension BS
+template <int BS>
+__device__ __forceinline__ bool amg_filtered_block(const NodeRow<BS>& R, int k, int64_t node, bool diagonal, const double* __restrict__ values,
+                                                   const uint8_t* __restrict__ strong, const double* __restrict__ diag_f, const double*& ab,
+                                                   int64_t& ld) {
+    ab = values + R.r0 + (int64_t)k * BS;
+    ld = R.len;
+    if (strong) {
+        if (!strong[R.r0 / (BS * BS) + k]) return false;
+        if (diagonal) {
+            ab = diag_f + node * BS * BS;
+            ld = BS;
+        }
+    }
+    return true;
 }
 
 // ---- numeric phase
@@ -182,15 +199,9 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_rho(int64_t n_nodes, const 
 #pragma unroll
             for (int j = 0; j < BS; ++j) D[i][j] = dinv[node * BS * BS + i * BS + j];
         for (int k = lane; k < R.nnb; k += LW) {
-            const double* ab = values + R.r0 + (int64_t)k * BS;
-            int64_t ld = R.len;
-            if (strong) {                                      // the filtered matrix: no weak blocks, the lumped diagonal block
-                if (!strong[R.r0 / (BS * BS) + k]) continue;
-                if (col[R.r0 + (int64_t)k * BS] == node * BS) {
-                    ab = diag_f + node * BS * BS;
-                    ld = BS;
-                }
-            }
+            const double* ab;
+            int64_t ld;
+            if (!amg_filtered_block<BS>(R, k, node, strong && col[R.r0 + (int64_t)k * BS] == node * BS, values, strong, diag_f, ab, ld)) continue;
             double a[BS][BS];
 #pragma unroll
             for (int i = 0; i < BS; ++i)
@@ -268,7 +279,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_init(int64_t n_rows, 
     if (threadIdx.x == 0) part[blockIdx.x] = q;
 }
 
-// w = Dinv (A (s v)) with s = scal[0], in the lane-group shape of amg_sweep, and the workgroup's partial of |w|^2
+// w = Dinv (A (s v)) with s = scal[0] by row_product, and the workgroup's partial of |w|^2; with `strong`, w = Dinv_F (A^F (s v))
 template <int BS, int LW>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_step(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                                 const double* __restrict__ values, const double* __restrict__ dinv,
@@ -279,38 +290,11 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_power_step(int64_t n_nodes,
     constexpr int NPB = DXO_AMG_BLOCK / LW;
     const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
     const int lane = threadIdx.x % LW;
-    const double sc = scal[0];
     double acc[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
-    if (node < n_nodes) {
-        const NodeRow<BS> R(row_ptr, node);
-        for (int k = lane; k < R.nnb; k += LW) {
-            const int64_t c = col[R.r0 + (int64_t)k * BS];
-            const double* ab = values + R.r0 + (int64_t)k * BS;
-            int64_t ld = R.len;
-            if (strong) {                                      // as in amg_rho
-                if (!strong[R.r0 / (BS * BS) + k]) continue;
-                if (c == node * BS) {
-                    ab = diag_f + node * BS * BS;
-                    ld = BS;
-                }
-            }
-            double xb[BS];
-#pragma unroll
-            for (int j = 0; j < BS; ++j) xb[j] = sc * v[c + j];
-#pragma unroll
-            for (int i = 0; i < BS; ++i) {
-                const double* a = ab + i * ld;
-#pragma unroll
-                for (int j = 0; j < BS; ++j) acc[i] = fma(a[j], xb[j], acc[i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int off = LW / 2; off > 0; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    row_product<BS, LW, true>(n_nodes, node, lane, row_ptr, col, values, v, scal[0], acc,
+                              [&](const NodeRow<BS>& R, int k, int64_t c, const double*& ab, int64_t& ld) {
+                                  return amg_filtered_block<BS>(R, k, node, c == node * BS, values, strong, diag_f, ab, ld);
+                              });
     double q = 0.0;
     if (node < n_nodes && lane == 0) {
 #pragma unroll
@@ -406,15 +390,9 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_p(int64_t p_blocks, c
     for (int k = 0; k < R.nnb; ++k) {
         const int64_t j = col[R.r0 + (int64_t)k * BSR] / BSR;
         if (agg[j] != a) continue;
-        const double* ab = values + R.r0 + (int64_t)k * BSR;
-        int64_t ld = R.len;
-        if (strong) {                                          // A^F T: no weak blocks, the lumped diagonal block (dinv is dinv_f)
-            if (!strong[R.r0 / (BSR * BSR) + k]) continue;
-            if (j == i) {
-                ab = diag_f + i * BSR * BSR;
-                ld = BSR;
-            }
-        }
+        const double* ab;
+        int64_t ld;
+        if (!amg_filtered_block<BSR>(R, k, i, j == i, values, strong, diag_f, ab, ld)) continue;      // A^F T (dinv is dinv_f)
         if constexpr (NNS) {
 #pragma unroll
             for (int q = 0; q < BSR; ++q) {
@@ -541,96 +519,6 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_c(int64_t c_blocks, c
         }
 }
 
-// ---- the block inverses of a level of block size 6: Gauss-Jordan on [A | I] with partial pivoting (the lowest row among equals),
-// one thread per node. Rows are exchanged by compare-and-select over static indices, so the 72 doubles stay in registers. A block
-// with |det| <= 1e-14 of the product of its row norms (the rule of dxo_csr_block_jacobi) gets a zero inverse and raises the flag.
-// M = [A | I] on entry, [. | A^-1] on return; false for a zero, NaN or nearly singular block
-__device__ __forceinline__ bool amg_gj6(double (&M)[6][12]) {
-    constexpr int BS = 6;
-    double had = 1.0, det = 1.0;
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-        double n2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < BS; ++j) n2 = fma(M[i][j], M[i][j], n2);
-        had *= sqrt(n2);
-    }
-#pragma unroll
-    for (int k = 0; k < BS; ++k) {
-        int p = k;
-        double best = fabs(M[k][k]);
-#pragma unroll
-        for (int i = k + 1; i < BS; ++i) {
-            const double v = fabs(M[i][k]);
-            if (v > best) {
-                best = v;
-                p = i;
-            }
-        }
-#pragma unroll
-        for (int i = k + 1; i < BS; ++i) {
-            const bool sw = p == i;
-#pragma unroll
-            for (int c = k; c < 2 * BS; ++c) {
-                const double x = M[k][c], y = M[i][c];
-                M[k][c] = sw ? y : x;
-                M[i][c] = sw ? x : y;
-            }
-        }
-        if (p != k) det = -det;
-        const double piv = M[k][k];
-        det *= piv;
-#pragma unroll
-        for (int c = k; c < 2 * BS; ++c) M[k][c] = M[k][c] / piv;
-#pragma unroll
-        for (int i = 0; i < BS; ++i) {
-            if (i == k) continue;
-            const double fct = M[i][k];
-#pragma unroll
-            for (int c = k; c < 2 * BS; ++c) M[i][c] = fma(-fct, M[k][c], M[i][c]);
-        }
-    }
-    return fabs(det) > 1e-14 * had;
-}
-
-// position of the block of column `node` among the blocks of a node's row (its own: the diagonal block), or -1
-template <int BS>
-__device__ __forceinline__ int amg_block_pos(const NodeRow<BS>& R, const int32_t* __restrict__ col, int64_t node) {
-    int lo = 0, hi = R.nnb - 1;
-    const int64_t self = node * BS;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (col[R.r0 + (int64_t)mid * BS] < self) lo = mid + 1;
-        else hi = mid;
-    }
-    return hi >= 0 && col[R.r0 + (int64_t)lo * BS] == self ? lo : -1;
-}
-
-__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_bj6(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                                         const double* __restrict__ values, double* __restrict__ inv, int* __restrict__ singular) {
-    constexpr int BS = 6;
-    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
-    if (node >= n_nodes) return;
-    const NodeRow<BS> R(row_ptr, node);
-    const int lo = amg_block_pos<BS>(R, col, node);
-    bool ok = lo >= 0;
-    double M[BS][2 * BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i)
-#pragma unroll
-        for (int j = 0; j < BS; ++j) {
-            M[i][j] = ok ? values[R.r0 + i * R.len + (int64_t)lo * BS + j] : 0.0;
-            M[i][BS + j] = i == j ? 1.0 : 0.0;
-        }
-    ok = amg_gj6(M) && ok;
-    double* out = inv + node * BS * BS;
-#pragma unroll
-    for (int i = 0; i < BS; ++i)
-#pragma unroll
-        for (int j = 0; j < BS; ++j) out[i * BS + j] = ok ? M[i][BS + j] : 0.0;
-    if (!ok) singular[0] = 1;     // every writer stores the same word
-}
-
 // ---- strength of connection
 // the sum of the squares of a block, entry by entry in row-major order
 template <int BS>
@@ -650,7 +538,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_diag_norm(int64_t n_nodes, 
     const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
     if (node >= n_nodes) return;
     const NodeRow<BS> R(row_ptr, node);
-    const int lo = amg_block_pos<BS>(R, col, node);
+    const int lo = block_pos<BS>(R, col, node);
     dn[node] = lo >= 0 ? sqrt(amg_block_norm2<BS>(values + R.r0 + (int64_t)lo * BS, R.len)) : 0.0;
 }
 
@@ -675,7 +563,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_strength(int64_t n_nodes, c
             st = amg_block_norm2<BS>(values + R.r0 + (int64_t)k * BS, R.len) >= bound;
             if (!st) {
                 const NodeRow<BS> Rj(row_ptr, j);
-                const int t = amg_block_pos<BS>(Rj, col, node);      // the block (j, node)
+                const int t = block_pos<BS>(Rj, col, node);      // the block (j, node)
                 if (t >= 0) st = amg_block_norm2<BS>(values + Rj.r0 + (int64_t)t * BS, Rj.len) >= bound;
             }
         }
@@ -695,7 +583,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_lump(int64_t n_nodes, const
     if (node >= n_nodes) return;
     const NodeRow<BS> R(row_ptr, node);
     const int64_t b0 = R.r0 / (BS * BS);
-    const int lo = amg_block_pos<BS>(R, col, node);
+    const int lo = block_pos<BS>(R, col, node);
     double a[BS][BS];
 #pragma unroll
     for (int i = 0; i < BS; ++i)
@@ -714,24 +602,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_lump(int64_t n_nodes, const
             for (int j = 0; j < BS; ++j) a[i][j] += values[R.r0 + i * R.len + (int64_t)k * BS + j];
     }
     double b[BS][BS];
-    bool ok;
-    if constexpr (BS == 6) {
-        double M[BS][2 * BS];
-#pragma unroll
-        for (int i = 0; i < BS; ++i)
-#pragma unroll
-            for (int j = 0; j < BS; ++j) {
-                M[i][j] = a[i][j];
-                M[i][BS + j] = i == j ? 1.0 : 0.0;
-            }
-        ok = amg_gj6(M);
-#pragma unroll
-        for (int i = 0; i < BS; ++i)
-#pragma unroll
-            for (int j = 0; j < BS; ++j) b[i][j] = M[i][BS + j];
-    } else {
-        ok = invert_block<BS>(a, b);
-    }
+    const bool ok = invert_block<BS>(a, b);
 #pragma unroll
     for (int i = 0; i < BS; ++i)
 #pragma unroll
@@ -933,13 +804,14 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_dense_apply(int64_t n, cons
 }
 
 // ---- the cycle
-// x = omega Dinv r: the first sweep, from x = 0
+// x = scale[0] Dinv r, and d = x if d is given: the first step of a smoother from x = 0 (no SpMV). Jacobi: scale is omega; Chebyshev:
+// the c2 of the first pair, and d the direction
 template <int BS>
-__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_jacobi0(int64_t n_nodes, const double* __restrict__ dinv, const double* __restrict__ omega,
-                                                             const double* __restrict__ r, double* __restrict__ x) {
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_first_step(int64_t n_nodes, const double* __restrict__ dinv, const double* __restrict__ scale,
+                                                                const double* __restrict__ r, double* __restrict__ d, double* __restrict__ x) {
     const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
     if (node >= n_nodes) return;
-    const double om = omega[0];
+    const double sc = scale[0];
     double rb[BS];
 #pragma unroll
     for (int j = 0; j < BS; ++j) rb[j] = r[node * BS + j];
@@ -948,11 +820,13 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_jacobi0(int64_t n_nodes, co
         double s = 0.0;
 #pragma unroll
         for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], rb[j], s);
-        x[node * BS + i] = om * s;
+        const double v = sc * s;
+        if (d) d[node * BS + i] = v;
+        x[node * BS + i] = v;
     }
 }
 
-// RESID: out = r - A x; otherwise out = x + omega Dinv (r - A x). LW lanes own a node (the shape of csr_spmv). out may be r: a node's
+// RESID: out = r - A x; otherwise out = x + omega Dinv (r - A x). LW lanes own a node (A x by row_product). out may be r: a node's
 // entries of r are read by its own lane 0 only, before it writes.
 template <int BS, int LW, bool RESID>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_sweep(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
@@ -963,27 +837,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_sweep(int64_t n_nodes, cons
     const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
     const int lane = threadIdx.x % LW;
     double acc[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
-    if (node < n_nodes) {
-        const NodeRow<BS> R(row_ptr, node);
-        for (int k = lane; k < R.nnb; k += LW) {
-            const int64_t c = col[R.r0 + (int64_t)k * BS];
-            double xb[BS];
-#pragma unroll
-            for (int j = 0; j < BS; ++j) xb[j] = x[c + j];
-#pragma unroll
-            for (int i = 0; i < BS; ++i) {
-                const double* v = values + R.r0 + i * R.len + (int64_t)k * BS;
-#pragma unroll
-                for (int j = 0; j < BS; ++j) acc[i] = fma(v[j], xb[j], acc[i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int off = LW / 2; off > 0; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    row_product<BS, LW>(n_nodes, node, lane, row_ptr, col, values, x, acc);
     if (node < n_nodes && lane == 0) {
         double d[BS];
 #pragma unroll
@@ -1004,28 +858,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_sweep(int64_t n_nodes, cons
     }
 }
 
-// d = c2 Dinv r, x = d with (c1, c2) = c[0..1]: the first Chebyshev step of the pre-smoothing, from x = 0
-template <int BS>
-__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_cheby0(int64_t n_nodes, const double* __restrict__ dinv, const double* __restrict__ c,
-                                                            const double* __restrict__ r, double* __restrict__ d, double* __restrict__ x) {
-    const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
-    if (node >= n_nodes) return;
-    const double c2 = c[1];
-    double rb[BS];
-#pragma unroll
-    for (int j = 0; j < BS; ++j) rb[j] = r[node * BS + j];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], rb[j], s);
-        const double dn = c2 * s;
-        d[node * BS + i] = dn;
-        x[node * BS + i] = dn;
-    }
-}
-
-// d = c1 d + c2 Dinv (r - A x), out = x + d with (c1, c2) = c[0..1], in the lane-group shape of amg_sweep. d is updated in place: a
+// d = c1 d + c2 Dinv (r - A x), out = x + d with (c1, c2) = c[0..1], A x by row_product as in amg_sweep. d is updated in place: a
 // node's entries are touched by its own lane 0 only. With c1 == 0 (the first step of the post-smoothing) d is not read. out may be r,
 // as in amg_sweep.
 template <int BS, int LW>
@@ -1037,27 +870,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_cheby_sweep(int64_t n_nodes
     const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
     const int lane = threadIdx.x % LW;
     double acc[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
-    if (node < n_nodes) {
-        const NodeRow<BS> R(row_ptr, node);
-        for (int k = lane; k < R.nnb; k += LW) {
-            const int64_t cb = col[R.r0 + (int64_t)k * BS];
-            double xb[BS];
-#pragma unroll
-            for (int j = 0; j < BS; ++j) xb[j] = x[cb + j];
-#pragma unroll
-            for (int i = 0; i < BS; ++i) {
-                const double* v = values + R.r0 + i * R.len + (int64_t)k * BS;
-#pragma unroll
-                for (int j = 0; j < BS; ++j) acc[i] = fma(v[j], xb[j], acc[i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int off = LW / 2; off > 0; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    row_product<BS, LW>(n_nodes, node, lane, row_ptr, col, values, x, acc);
     if (node < n_nodes && lane == 0) {
         const double c1 = c[0], c2 = c[1];
         double res[BS];
@@ -1122,157 +935,70 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_prolong(int64_t n_nodes, co
 }
 
 // ---- host: launch helpers
-// a level shape without an instantiation is a defect of this file, not of the caller: the entry points admit (1..3) and the pairs below
-[[noreturn]] inline void amg_no_shape(int bsr, int bsc) {
-    fprintf(stderr, "amg.hip: no kernel instantiation for block sizes (%d, %d)\n", bsr, bsc);
+// a shape without an instantiation is a defect of this file, not of the caller: the entry points admit (1..3) and the lists below
+[[noreturn]] inline void amg_no_shape(int a, int b) {
+    fprintf(stderr, "amg.hip: no kernel instantiation for the shape (%d, %d)\n", a, b);
     std::abort();
 }
 
 inline dim3 amg_grid(int64_t items, int per_block = DXO_AMG_BLOCK) { return dim3((unsigned)std::max<int64_t>(1, (items + per_block - 1) / per_block)); }
 
-#define AMG_BS(bs, kernel, ...)                                               \
-    do {                                                                      \
-        if ((bs) == 1) hipLaunchKernelGGL(kernel<1>, __VA_ARGS__);            \
-        else if ((bs) == 2) hipLaunchKernelGGL(kernel<2>, __VA_ARGS__);       \
-        else if ((bs) == 3) hipLaunchKernelGGL(kernel<3>, __VA_ARGS__);       \
-        else if ((bs) == 6) hipLaunchKernelGGL(kernel<6>, __VA_ARGS__);       \
-        else amg_no_shape((bs), (bs));                                        \
-    } while (0)
+// one workgroup per `per_block` items
+template <class... P, class... Args>
+void amg_launch(void (*kernel)(P...), int64_t items, int per_block, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, amg_grid(items, per_block), dim3(DXO_AMG_BLOCK), 0, s, args...);
+}
 
-// (rows of the level, rows of the next): square without a near-null space, (2, 3) -> (3, 3) and (3, 6) -> (6, 6) with one
-#define AMG_PAIR(bsr, bsc, kernel, ...)                                                    \
-    do {                                                                                   \
-        const int pair_ = (bsr) * 8 + (bsc);                                               \
-        if (pair_ == 9) hipLaunchKernelGGL((kernel<1, 1>), __VA_ARGS__);                   \
-        else if (pair_ == 18) hipLaunchKernelGGL((kernel<2, 2>), __VA_ARGS__);             \
-        else if (pair_ == 27) hipLaunchKernelGGL((kernel<3, 3>), __VA_ARGS__);             \
-        else if (pair_ == 19) hipLaunchKernelGGL((kernel<2, 3>), __VA_ARGS__);             \
-        else if (pair_ == 30) hipLaunchKernelGGL((kernel<3, 6>), __VA_ARGS__);             \
-        else if (pair_ == 54) hipLaunchKernelGGL((kernel<6, 6>), __VA_ARGS__);             \
-        else amg_no_shape((bsr), (bsc));                                                   \
-    } while (0)
+// from run-time shapes to compile-time ones: f(constant...) for the entry of the list that matches, amg_no_shape for none. The lists
+// are the instantiations of this file
+template <int N>
+using int_c = std::integral_constant<int, N>;
 
-template <int BS, bool RESID>
-void sweep_bs(const amg_level& v, const double* omega, const double* r, const double* x, double* out, hipStream_t s) {
-    const dim3 b(DXO_AMG_BLOCK);
-    if (v.lw == 8)
-        hipLaunchKernelGGL((amg_sweep<BS, 8, RESID>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv,
-                           omega, r, x, out);
-    else
-        hipLaunchKernelGGL((amg_sweep<BS, 32, RESID>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values,
-                           v.dinv, omega, r, x, out);
+template <int... Ns, class F>
+void with_int(int v, F&& f) {
+    if (!((v == Ns && (f(int_c<Ns>{}), true)) || ...)) amg_no_shape(v, v);
+}
+
+constexpr int amg_pair(int bsr, int bsc) { return bsr * 8 + bsc; }
+
+template <int... Ps, class F>
+void with_pairs(int bsr, int bsc, F&& f) {
+    if (!((amg_pair(bsr, bsc) == Ps && (f(int_c<Ps / 8>{}, int_c<Ps % 8>{}), true)) || ...)) amg_no_shape(bsr, bsc);
+}
+
+template <class F>
+void with_bs(int bs, F&& f) { with_int<1, 2, 3, 6>(bs, f); }
+
+// (rows of the level, rows of the next): with a near-null space (2, 3) -> (3, 3) and (3, 6) -> (6, 6), square without one
+template <class F>
+void with_nns_pair(int bsr, int bsc, F&& f) { with_pairs<amg_pair(2, 3), amg_pair(3, 3), amg_pair(3, 6), amg_pair(6, 6)>(bsr, bsc, f); }
+
+template <class F>
+void with_square(int bsr, int bsc, F&& f) { with_pairs<amg_pair(1, 1), amg_pair(2, 2), amg_pair(3, 3)>(bsr, bsc, f); }
+
+template <class F>
+void with_pair(int bsr, int bsc, F&& f) {
+    if (bsr == bsc && bsr <= 3) with_square(bsr, bsc, f);
+    else with_nns_pair(bsr, bsc, f);
+}
+
+// (block size, lanes per node) of the lane-group kernels of a level
+template <class F>
+void with_level(const amg_level& v, F&& f) {
+    with_bs(v.bs, [&](auto BS) { with_int<8, 32>(v.lw, [&](auto LW) { f(BS, LW); }); });
 }
 
 template <bool RESID>
-void sweep_launch(int bs, const amg_level& v, const double* omega, const double* r, const double* x, double* out, hipStream_t s) {
-    if (bs == 1) sweep_bs<1, RESID>(v, omega, r, x, out, s);
-    else if (bs == 2) sweep_bs<2, RESID>(v, omega, r, x, out, s);
-    else if (bs == 3) sweep_bs<3, RESID>(v, omega, r, x, out, s);
-    else if (bs == 6) sweep_bs<6, RESID>(v, omega, r, x, out, s);
-    else amg_no_shape(bs, bs);
+void sweep(const amg_level& v, const double* omega, const double* r, const double* x, double* out, hipStream_t s) {
+    with_level(v, [&](auto BS, auto LW) {
+        amg_launch(amg_sweep<BS, LW, RESID>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, omega, r, x, out);
+    });
 }
 
-template <int BS>
-void cheby_bs(const amg_level& v, const double* c, const double* r, const double* x, double* out, hipStream_t s) {
-    const dim3 b(DXO_AMG_BLOCK);
-    if (v.lw == 8)
-        hipLaunchKernelGGL((amg_cheby_sweep<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv,
-                           c, r, x, v.d, out);
-    else
-        hipLaunchKernelGGL((amg_cheby_sweep<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values,
-                           v.dinv, c, r, x, v.d, out);
-}
-
-void cheby_launch(const amg_level& v, const double* c, const double* r, const double* x, double* out, hipStream_t s) {
-    if (v.bs == 1) cheby_bs<1>(v, c, r, x, out, s);
-    else if (v.bs == 2) cheby_bs<2>(v, c, r, x, out, s);
-    else if (v.bs == 3) cheby_bs<3>(v, c, r, x, out, s);
-    else if (v.bs == 6) cheby_bs<6>(v, c, r, x, out, s);
-    else amg_no_shape(v.bs, v.bs);
-}
-
-// filtered: the operator is Dinv_F A^F (the level's mask, lumped diagonal blocks and dinv_f) instead of Dinv A
-template <int BS>
-void power_bs(const amg_level& v, bool filtered, const double* scal, const double* x, double* w, double* part, hipStream_t s) {
-    const dim3 b(DXO_AMG_BLOCK);
-    const double* dinv = filtered ? v.dinv_f : v.dinv;
-    const uint8_t* strong = filtered ? v.strong : nullptr;
-    if (v.lw == 8)
-        hipLaunchKernelGGL((amg_power_step<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dinv,
-                           strong, v.diag_f, scal, x, w, part);
-    else
-        hipLaunchKernelGGL((amg_power_step<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values,
-                           dinv, strong, v.diag_f, scal, x, w, part);
-}
-
-template <int BS>
-void rho_bs(const amg_level& v, bool filtered, double* part, hipStream_t s) {
-    const dim3 b(DXO_AMG_BLOCK);
-    const double* dinv = filtered ? v.dinv_f : v.dinv;
-    const uint8_t* strong = filtered ? v.strong : nullptr;
-    if (v.lw == 8)
-        hipLaunchKernelGGL((amg_rho<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dinv, strong,
-                           v.diag_f, part);
-    else
-        hipLaunchKernelGGL((amg_rho<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dinv,
-                           strong, v.diag_f, part);
-}
-
-template <int BS>
-void strength_bs(const amg_level& v, const double* dn, double th2, uint8_t* strong, hipStream_t s) {
-    const dim3 b(DXO_AMG_BLOCK);
-    hipLaunchKernelGGL(amg_diag_norm<BS>, amg_grid(v.n_nodes), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, const_cast<double*>(dn));
-    if (v.lw == 8)
-        hipLaunchKernelGGL((amg_strength<BS, 8>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 8), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dn, th2,
-                           strong);
-    else
-        hipLaunchKernelGGL((amg_strength<BS, 32>), amg_grid(v.n_nodes, DXO_AMG_BLOCK / 32), b, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dn,
-                           th2, strong);
-}
-
-// |A_ii|_F of every node into dn, then the mask
-void strength_launch(const amg_level& v, double* dn, double th2, uint8_t* strong, hipStream_t s) {
-    if (v.bs == 1) strength_bs<1>(v, dn, th2, strong, s);
-    else if (v.bs == 2) strength_bs<2>(v, dn, th2, strong, s);
-    else if (v.bs == 3) strength_bs<3>(v, dn, th2, strong, s);
-    else if (v.bs == 6) strength_bs<6>(v, dn, th2, strong, s);
-    else amg_no_shape(v.bs, v.bs);
-}
-
-#define AMG_P_ARGS amg_grid(v.p_blocks), dim3(DXO_AMG_BLOCK), 0, s, v.p_blocks, v.p_row, v.p_col, v.A->d_row_ptr, v.A->d_col, v.values, v.strong ? v.dinv_f : v.dinv, v.agg, \
-                   v.mask, v.t_val, omega, v.strong, v.diag_f, v.p_val
-// omega: omega_F of the level if it carries a mask
-void build_p_launch(const amg_level& v, bool nns, const double* omega, hipStream_t s) {
-    if (!nns) {
-        if (v.bs == 1) hipLaunchKernelGGL((amg_build_p<1, 1, false>), AMG_P_ARGS);
-        else if (v.bs == 2) hipLaunchKernelGGL((amg_build_p<2, 2, false>), AMG_P_ARGS);
-        else if (v.bs == 3) hipLaunchKernelGGL((amg_build_p<3, 3, false>), AMG_P_ARGS);
-        else amg_no_shape(v.bs, v.bsc);
-    } else if (v.bs == 2 && v.bsc == 3) hipLaunchKernelGGL((amg_build_p<2, 3, true>), AMG_P_ARGS);
-    else if (v.bs == 3 && v.bsc == 3) hipLaunchKernelGGL((amg_build_p<3, 3, true>), AMG_P_ARGS);
-    else if (v.bs == 3 && v.bsc == 6) hipLaunchKernelGGL((amg_build_p<3, 6, true>), AMG_P_ARGS);
-    else if (v.bs == 6 && v.bsc == 6) hipLaunchKernelGGL((amg_build_p<6, 6, true>), AMG_P_ARGS);
-    else amg_no_shape(v.bs, v.bsc);
-}
-#undef AMG_P_ARGS
-
-template <int BSR, int K>
-void tentative_bs(const amg_level& v, double* b_next, double tol, hipStream_t s) {
-    const dim3 b(DXO_AMG_BLOCK);
-#define AMG_T_ARGS(lg) amg_grid(v.n_agg, DXO_AMG_BLOCK / lg), b, 0, s, v.n_agg, v.agg_ptr, v.agg_node, v.b_val, tol, v.t_val, b_next, v.dead_a
-    if (v.tl == 8) hipLaunchKernelGGL((amg_tentative<BSR, K, 8>), AMG_T_ARGS(8));
-    else if (v.tl == 16) hipLaunchKernelGGL((amg_tentative<BSR, K, 16>), AMG_T_ARGS(16));
-    else if (v.tl == 32) hipLaunchKernelGGL((amg_tentative<BSR, K, 32>), AMG_T_ARGS(32));
-    else hipLaunchKernelGGL((amg_tentative<BSR, K, 64>), AMG_T_ARGS(64));
-#undef AMG_T_ARGS
-}
-
-void tentative_launch(const amg_level& v, double* b_next, double tol, hipStream_t s) {
-    if (v.bs == 2 && v.bsc == 3) tentative_bs<2, 3>(v, b_next, tol, s);
-    else if (v.bs == 3 && v.bsc == 3) tentative_bs<3, 3>(v, b_next, tol, s);
-    else if (v.bs == 3 && v.bsc == 6) tentative_bs<3, 6>(v, b_next, tol, s);
-    else if (v.bs == 6 && v.bsc == 6) tentative_bs<6, 6>(v, b_next, tol, s);
-    else amg_no_shape(v.bs, v.bsc);
+void cheby_step(const amg_level& v, const double* c, const double* r, const double* x, double* out, hipStream_t s) {
+    with_level(v, [&](auto BS, auto LW) {
+        amg_launch(amg_cheby_sweep<BS, LW>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, c, r, x, v.d, out);
+    });
 }
 
 int64_t rho_parts(const amg_level& v) { return std::max<int64_t>(1, (v.n_nodes + DXO_AMG_BLOCK / v.lw - 1) / (DXO_AMG_BLOCK / v.lw)); }
@@ -1482,11 +1208,16 @@ int amg_nns_first(dxo_ctx* ctx, dxo_amg* amg, const amg_level& f, const double* 
     return DXO_OK;
 }
 
-// ... then level by level T_l and B_{l+1} ...
+// ... then level by level T_l and B_{l+1}, as soon as the aggregates of level l are known ...
 int amg_nns_level(dxo_ctx* ctx, dxo_amg* amg, const amg_level& v, double* b_next, hipStream_t s) {
     const double tol = std::pow(10.0, -(double)ctx->amg_rank_tol);
     DXO_HIP(ctx, hipMemsetAsync(v.t_val, 0, (size_t)(v.n_nodes * v.bs * amg->k) * sizeof(double), s));      // nodes without an aggregate
-    if (v.n_agg > 0) tentative_launch(v, b_next, tol, s);
+    if (v.n_agg > 0)
+        with_nns_pair(v.bs, v.bsc, [&](auto BSR, auto K) {
+            with_int<8, 16, 32, 64>(v.tl, [&](auto LG) {
+                amg_launch(amg_tentative<BSR, K, LG>, v.n_agg, DXO_AMG_BLOCK / LG, s, v.n_agg, v.agg_ptr, v.agg_node, v.b_val, tol, v.t_val, b_next, v.dead_a);
+            });
+        });
     return DXO_OK;
 }
 
@@ -1505,17 +1236,12 @@ int amg_nns_dead(dxo_ctx* ctx, dxo_amg* amg, hipStream_t s) {
     return DXO_OK;
 }
 
-int amg_near_nullspace(dxo_ctx* ctx, dxo_amg* amg, const double* B, hipStream_t s) {
-    int rc = amg_nns_first(ctx, amg, amg->L[0], B, s);
-    for (int l = 0; rc == DXO_OK && l + 1 < (int)amg->L.size(); ++l) rc = amg_nns_level(ctx, amg, amg->L[(size_t)l], amg->L[(size_t)l + 1].b_val, s);
-    return rc == DXO_OK ? amg_nns_dead(ctx, amg, s) : rc;
-}
-
 // rho, omega = (4/3) / rho and (unfiltered only) the Chebyshev pairs of a level from the estimate chosen by dxo_amg_set_smoother;
 // filtered: of Dinv_F A^F, for the prolongator smoothing alone
 void amg_estimate_rho(dxo_amg* amg, const amg_level& v, bool filtered, double* rho, double* omega, double* cheb, hipStream_t s) {
     const dim3 B(DXO_AMG_BLOCK);
-    const int bs = v.bs;
+    const double* dinv = filtered ? v.dinv_f : v.dinv;
+    const uint8_t* strong = filtered ? v.strong : nullptr;
     if (amg->rho_kind == DXO_AMG_RHO_POWER) {
         // v_0 in xa, then w = Dinv A (v / |v|) back and forth between xa and xb: the cycle's vectors are free during a setup
         double *from = v.xa, *to = v.xb;
@@ -1523,21 +1249,18 @@ void amg_estimate_rho(dxo_amg* amg, const amg_level& v, bool filtered, double* r
         hipLaunchKernelGGL(amg_power_norm, dim3(1), B, 0, s, amg->part, init_parts(v), 0, amg->safety, amg->lower, amg->degree, amg->scal, rho, omega,
                            cheb);
         for (int it = 0; it < amg->rho_iters; ++it) {
-            if (bs == 1) power_bs<1>(v, filtered, amg->scal, from, to, amg->part, s);
-            else if (bs == 2) power_bs<2>(v, filtered, amg->scal, from, to, amg->part, s);
-            else if (bs == 3) power_bs<3>(v, filtered, amg->scal, from, to, amg->part, s);
-            else if (bs == 6) power_bs<6>(v, filtered, amg->scal, from, to, amg->part, s);
-            else amg_no_shape(bs, bs);
+            with_level(v, [&](auto BS, auto LW) {
+                amg_launch(amg_power_step<BS, LW>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dinv, strong, v.diag_f,
+                           amg->scal, from, to, amg->part);
+            });
             hipLaunchKernelGGL(amg_power_norm, dim3(1), B, 0, s, amg->part, rho_parts(v), it + 1 == amg->rho_iters ? 1 : 0, amg->safety, amg->lower,
                                amg->degree, amg->scal, rho, omega, cheb);
             std::swap(from, to);
         }
     } else {
-        if (bs == 1) rho_bs<1>(v, filtered, amg->part, s);
-        else if (bs == 2) rho_bs<2>(v, filtered, amg->part, s);
-        else if (bs == 3) rho_bs<3>(v, filtered, amg->part, s);
-        else if (bs == 6) rho_bs<6>(v, filtered, amg->part, s);
-        else amg_no_shape(bs, bs);
+        with_level(v, [&](auto BS, auto LW) {
+            amg_launch(amg_rho<BS, LW>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, dinv, strong, v.diag_f, amg->part);
+        });
         hipLaunchKernelGGL(amg_omega, dim3(1), B, 0, s, amg->part, rho_parts(v), omega, rho);
         if (!filtered && amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV)
             hipLaunchKernelGGL(amg_cheby_coeffs, dim3(1), dim3(64), 0, s, rho, amg->lower, amg->degree, cheb);
@@ -1546,27 +1269,32 @@ void amg_estimate_rho(dxo_amg* amg, const amg_level& v, bool filtered, double* r
 
 // the numeric phase of level l: from the values of v to those of the next level c
 void amg_setup_level(dxo_amg* amg, int l, const amg_level& v, const amg_level& c, hipStream_t s) {
-    const dim3 B(DXO_AMG_BLOCK);
     const bool nns = amg->k > 0;
-    const int bs = v.bs;
-    if (bs == 6) hipLaunchKernelGGL(amg_bj6, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, amg->flag);
-    else dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
+    dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
     const double* omega_p = amg->omega + l;
     if (v.strong) {
-        AMG_BS(bs, amg_lump, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.strong, v.dinv, v.diag_f, v.dinv_f,
-               v.unlumped);
+        with_bs(v.bs, [&](auto BS) {
+            amg_launch(amg_lump<BS>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.strong, v.dinv, v.diag_f, v.dinv_f,
+                       v.unlumped);
+        });
         amg_estimate_rho(amg, v, true, amg->rho_f + l, amg->omega_f + l, amg->cheb_f, s);
-        omega_p = amg->omega_f + l;
+        omega_p = amg->omega_f + l;      // P is smoothed with the filtered matrix: dinv_f and omega_F
     }
     amg_estimate_rho(amg, v, false, amg->rho + l, amg->omega + l, amg->cheb + (size_t)l * AMG_CHEB_STRIDE, s);
-    build_p_launch(v, nns, omega_p, s);
-    AMG_PAIR(bs, v.bsc, amg_build_ap, amg_grid(v.ap_blocks), B, 0, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr,
-             v.p_col, v.p_val, v.ap_val);
-    double* cv = const_cast<double*>(c.values);
-    AMG_PAIR(bs, v.bsc, amg_build_c, amg_grid(v.c_blocks), B, 0, s, v.c_blocks, v.c_row, v.c_bptr, c.A->d_row_ptr, c.A->d_col, v.pt_ptr, v.pt_blk, v.p_row,
-             v.p_val, v.ap_ptr, v.ap_col, v.ap_val, cv);
+    auto build_p = [&](auto BSR, auto BSC, auto NNS) {
+        amg_launch(amg_build_p<BSR, BSC, NNS>, v.p_blocks, DXO_AMG_BLOCK, s, v.p_blocks, v.p_row, v.p_col, v.A->d_row_ptr, v.A->d_col, v.values,
+                   v.strong ? v.dinv_f : v.dinv, v.agg, v.mask, v.t_val, omega_p, v.strong, v.diag_f, v.p_val);
+    };
+    if (nns) with_nns_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) { build_p(BSR, BSC, std::true_type{}); });
+    else with_square(v.bs, v.bsc, [&](auto BSR, auto BSC) { build_p(BSR, BSC, std::false_type{}); });
+    with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
+        amg_launch(amg_build_ap<BSR, BSC>, v.ap_blocks, DXO_AMG_BLOCK, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr,
+                   v.p_col, v.p_val, v.ap_val);
+        amg_launch(amg_build_c<BSR, BSC>, v.c_blocks, DXO_AMG_BLOCK, s, v.c_blocks, v.c_row, v.c_bptr, c.A->d_row_ptr, c.A->d_col, v.pt_ptr, v.pt_blk,
+                   v.p_row, v.p_val, v.ap_ptr, v.ap_col, v.ap_val, const_cast<double*>(c.values));
+    });
     // the values-dependent mask belongs to the identity form of T; with a near-null space T is fixed at creation
-    if (!nns) hipLaunchKernelGGL(amg_row_mask, amg_grid(c.n_rows), B, 0, s, c.n_rows, c.A->d_row_ptr, c.A->d_col, c.values, c.mask);
+    if (!nns) hipLaunchKernelGGL(amg_row_mask, amg_grid(c.n_rows), dim3(DXO_AMG_BLOCK), 0, s, c.n_rows, c.A->d_row_ptr, c.A->d_col, c.values, c.mask);
 }
 
 // the strong part of a node graph: mask[e] per entry of g
@@ -1582,69 +1310,146 @@ HostGraph strong_graph(const HostGraph& g, const std::vector<uint8_t>& mask) {
     return gs;
 }
 
-// k: columns of the near-null space (every coarse level then has block size k), 0: none (every level keeps the block size).
-// theta > 0 (strength of connection): `values` is the matrix and Bnns the near-null space (k > 0); every level is followed by its
-// numeric phase, whose coarse matrix gives the mask of the next level
-int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, int max_levels,
-              int coarse_rows, int k, double theta = 0.0, const double* values = nullptr, const double* Bnns = nullptr, hipStream_t s = nullptr) {
-    const bool soc = theta > 0.0;
-    int bs = csr->bs;
-    const int bsc = k > 0 ? k : bs;
-    Uploader U{ctx, amg, who};
+// what the three creators ask for
+struct amg_options {
+    int max_levels = 0, coarse_rows = 0, sweeps = 1;
+    int k = 0;                         // columns of the near-null space (every coarse level then has block size k); 0: none (every level
+    const double* B = nullptr;         // keeps the block size). B: the near-null space [n_rows][k] on the device
+    double theta = 0.0;                // strength of connection: > 0 with `values`, the matrix; every level is then followed by its numeric
+    const double* values = nullptr;    // phase, whose coarse matrix gives the mask of the next level
+};
+
+// the pattern and the constraints on the host: the node graph, the constrained dofs, the nodes with a free dof
+int amg_read_pattern(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, HostGraph& g, std::vector<uint8_t>& mask,
+                     std::vector<uint8_t>& active) {
     std::vector<int64_t> row_ptr((size_t)csr->n_rows + 1);
     std::vector<int32_t> col((size_t)csr->nnz);
     DXO_HIP(ctx, hipMemcpy(row_ptr.data(), csr->d_row_ptr, row_ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (csr->nnz > 0) DXO_HIP(ctx, hipMemcpy(col.data(), csr->d_col, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<uint8_t> mask((size_t)csr->n_rows, 0);
+    mask.assign((size_t)csr->n_rows, 0);
     if (n_constrained > 0) {
         std::vector<int32_t> dofs((size_t)n_constrained);
         DXO_HIP(ctx, hipMemcpy(dofs.data(), constrained, dofs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (int32_t d : dofs)
             if (d >= 0 && d < csr->n_rows) mask[(size_t)d] = 1;
     }
-    HostGraph g = graph_of(row_ptr, col, csr->n_nodes, bs);
-    std::vector<uint8_t> active((size_t)g.n, 1);
+    g = graph_of(row_ptr, col, csr->n_nodes, csr->bs);
+    active.assign((size_t)g.n, 1);
     for (int64_t i = 0; i < g.n; ++i) {
         bool all = true;
-        for (int r = 0; r < bs; ++r) all = all && mask[(size_t)(i * bs + r)];
+        for (int r = 0; r < csr->bs; ++r) all = all && mask[(size_t)(i * csr->bs + r)];
         active[(size_t)i] = all ? 0 : 1;
     }
+    return DXO_OK;
+}
+
+// the strength mask of a level from its values: |A_ii|_F in xa (free until the first cycle), the mask on the device and, after the
+// one wait of this level, on the host as the strong graph
+int amg_strength_mask(dxo_ctx* ctx, Uploader& U, const amg_level& v, const HostGraph& g, double theta, hipStream_t s, uint8_t*& d_strong,
+                      int64_t& n_strong, HostGraph& gs) {
+    d_strong = U.alloc<uint8_t>((size_t)v.nnzb);
+    if (U.rc != DXO_OK) return U.rc;
+    std::vector<uint8_t> hmask((size_t)v.nnzb);
+    with_level(v, [&](auto BS, auto LW) {
+        amg_launch(amg_diag_norm<BS>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.xa);
+        amg_launch(amg_strength<BS, LW>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.xa, theta * theta, d_strong);
+    });
+    DXO_HIP(ctx, hipGetLastError());
+    if (v.nnzb > 0) DXO_HIP(ctx, hipMemcpyAsync(hmask.data(), d_strong, hmask.size(), hipMemcpyDeviceToHost, s));
+    DXO_HIP(ctx, hipStreamSynchronize(s));
+    n_strong = 0;
+    for (uint8_t m : hmask) n_strong += m;
+    gs = strong_graph(g, hmask);
+    return DXO_OK;
+}
+
+// the tables and the value arrays of the transfer from a level to the next, on the device
+void amg_upload_transfer(Uploader& U, amg_level& v, const HostTransfer& t, const std::vector<int32_t>& agg, int64_t na) {
+    v.n_agg = na;
+    v.p_blocks = (int64_t)t.p_col.size();
+    v.ap_blocks = (int64_t)t.ap_col.size();
+    v.c_blocks = (int64_t)t.c_row.size();
+    v.agg = U.up(agg);
+    v.p_ptr = U.up(t.p_ptr);
+    v.p_col = U.up(t.p_col);
+    v.p_row = U.up(t.p_row);
+    v.pt_ptr = U.up(t.pt_ptr);
+    v.pt_blk = U.up(t.pt_blk);
+    v.ap_ptr = U.up(t.ap_ptr);
+    v.ap_col = U.up(t.ap_col);
+    v.ap_row = U.up(t.ap_row);
+    v.c_bptr = U.up(t.c_bptr);
+    v.c_row = U.up(t.c_row);
+    v.p_val = U.alloc<double>((size_t)(v.p_blocks * v.bs * v.bsc));
+    v.ap_val = U.alloc<double>((size_t)(v.ap_blocks * v.bs * v.bsc));
+}
+
+// the coarse level of a node graph: a dxo_csr without a mesh, its values and its B (k > 0) or mask
+amg_level amg_coarse_level(Uploader& U, const HostGraph& coarse, int bsc, int k) {
+    std::vector<int64_t> crp;
+    std::vector<int32_t> ccol;
+    rows_of(coarse, bsc, crp, ccol);
+    amg_level c;
+    c.own = new dxo_csr;
+    c.own->bs = bsc;
+    c.own->n_nodes = coarse.n;
+    c.own->n_rows = coarse.n * bsc;
+    c.own->nnz = crp.back();
+    c.own->d_row_ptr = U.up(crp);
+    c.own->d_col = U.up(ccol);
+    c.A = c.own;
+    c.n_nodes = coarse.n;
+    c.n_rows = coarse.n * bsc;
+    c.nnzb = (int64_t)coarse.nb.size();
+    c.bs = c.bsc = bsc;
+    c.values = U.alloc<double>((size_t)c.own->nnz);
+    if (k > 0) c.b_val = U.alloc<double>((size_t)(c.n_rows * k));      // T is fixed at creation: no values-dependent mask
+    else c.mask = U.alloc<uint8_t>((size_t)c.n_rows);
+    return c;
+}
+
+// the symbolic phase, level by level; with a near-null space T_l and B_{l+1} follow the aggregates of level l at once, and a level
+// with a strength mask is followed by its numeric phase, which gives the matrix the next mask is made from
+int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained,
+              const amg_options& opt, hipStream_t s) {
+    const bool soc = opt.theta > 0.0;
+    const int k = opt.k, bsc = k > 0 ? k : csr->bs;
+    Uploader U{ctx, amg, who};
+    HostGraph g;
+    std::vector<uint8_t> mask, active;
+    int rc = amg_read_pattern(ctx, csr, constrained, n_constrained, g, mask, active);
+    if (rc != DXO_OK) return rc;
     amg_level lev;
     lev.A = csr;
     lev.n_nodes = csr->n_nodes;
     lev.n_rows = csr->n_rows;
     lev.nnzb = (int64_t)g.nb.size();
     lev.mask = U.up(mask);
-    lev.bs = bs;
+    lev.bs = csr->bs;
     lev.bsc = bsc;
+    lev.values = opt.values;
     if (k > 0) lev.b_val = U.alloc<double>((size_t)(lev.n_rows * k));
-    const int64_t nnzb0 = std::max<int64_t>(1, lev.nnzb * bs * bs);
+    const int64_t nnzb0 = std::max<int64_t>(1, lev.nnzb * lev.bs * lev.bs);
     int64_t total = 0;
-    if (soc) {
-        // what the numeric phase needs, before the number of levels is known: every level keeps at most 0.8 of its parent's rows
-        max_levels = std::min(max_levels, 128);
-        amg->part_cap = (lev.n_nodes + 7) / 8 + 1;     // no level has more nodes than the first, and at least 8 nodes go to a workgroup
-        amg->omega = U.alloc<double>((size_t)max_levels);
-        amg->rho = U.alloc<double>((size_t)max_levels);
-        amg->cheb = U.alloc<double>((size_t)max_levels * AMG_CHEB_STRIDE);
-        amg->omega_f = U.alloc<double>((size_t)max_levels);
-        amg->rho_f = U.alloc<double>((size_t)max_levels);
-        amg->cheb_f = U.alloc<double>(AMG_CHEB_STRIDE);
-        amg->scal = U.alloc<double>(2);
-        amg->part = U.alloc<double>((size_t)amg->part_cap);
-        amg->flag = U.alloc<int>(4);
-        if (U.rc != DXO_OK) return U.rc;
-        DXO_HIP(ctx, hipMemsetAsync(amg->flag, 0, 4 * sizeof(int), s));
-        lev.values = values;
-        if (k > 0) {
-            const int rc = amg_nns_first(ctx, amg, lev, Bnns, s);
-            if (rc != DXO_OK) return rc;
-        }
-    }
+    // what the numeric phase needs, before the number of levels is known: every level keeps at most 0.8 of its parent's rows
+    const int max_levels = std::min(opt.max_levels, 128);
+    amg->part_cap = (lev.n_nodes + 7) / 8 + 1;     // no level has more nodes than the first, and at least 8 nodes go to a workgroup
+    amg->omega = U.alloc<double>((size_t)max_levels);
+    amg->rho = U.alloc<double>((size_t)max_levels);
+    amg->cheb = U.alloc<double>((size_t)max_levels * AMG_CHEB_STRIDE);
+    amg->omega_f = U.alloc<double>((size_t)max_levels);
+    amg->rho_f = U.alloc<double>((size_t)max_levels);
+    amg->cheb_f = U.alloc<double>(AMG_CHEB_STRIDE);
+    amg->scal = U.alloc<double>(2);
+    amg->part = U.alloc<double>((size_t)amg->part_cap);
+    amg->flag = U.alloc<int>(4);
+    if (U.rc != DXO_OK) return U.rc;
+    DXO_HIP(ctx, hipMemsetAsync(amg->flag, 0, 4 * sizeof(int), s));
+    if (k > 0 && (rc = amg_nns_first(ctx, amg, lev, opt.B, s)) != DXO_OK) return rc;
     for (;;) {
         lev.lw = lanes_for(lev.nnzb, lev.n_nodes);
-        total += lev.nnzb * bs * bs;
-        bool last = lev.n_rows <= coarse_rows || (int)amg->L.size() + 1 >= max_levels;
+        total += lev.nnzb * lev.bs * lev.bs;
+        bool last = lev.n_rows <= opt.coarse_rows || (int)amg->L.size() + 1 >= max_levels;
         std::vector<int32_t> agg;
         int64_t na = 0;
         lev.r = U.alloc<double>((size_t)lev.n_rows);
@@ -1652,20 +1457,10 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
         HostGraph gs;
         uint8_t* d_strong = nullptr;
         int64_t n_strong = 0;
-        if (!last && soc) {
-            // |A_ii|_F in xa (free until the first cycle), the mask to the host: the one wait of this level
-            d_strong = U.alloc<uint8_t>((size_t)lev.nnzb);
-            if (U.rc != DXO_OK) return U.rc;
-            std::vector<uint8_t> hmask((size_t)lev.nnzb);
-            strength_launch(lev, lev.xa, theta * theta, d_strong, s);
-            DXO_HIP(ctx, hipGetLastError());
-            if (lev.nnzb > 0) DXO_HIP(ctx, hipMemcpyAsync(hmask.data(), d_strong, hmask.size(), hipMemcpyDeviceToHost, s));
-            DXO_HIP(ctx, hipStreamSynchronize(s));
-            for (uint8_t m : hmask) n_strong += m;
-            gs = strong_graph(g, hmask);
-        }
+        if (!last && soc && (rc = amg_strength_mask(ctx, U, lev, g, opt.theta, s, d_strong, n_strong, gs)) != DXO_OK) return rc;
+        const HostGraph& gp = d_strong ? gs : g;      // the graph of the aggregates and of the pattern of P
         if (!last) {
-            na = aggregate(soc ? gs : g, active, agg);
+            na = aggregate(gp, active, agg);
             last = na == 0 || (double)(na * bsc) > 0.8 * (double)lev.n_rows;
         }
         if (last) {
@@ -1675,81 +1470,36 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
         lev.xb = U.alloc<double>((size_t)lev.n_rows);
         lev.t = U.alloc<double>((size_t)lev.n_rows);
         lev.d = U.alloc<double>((size_t)lev.n_rows);
-        lev.dinv = U.alloc<double>((size_t)(lev.n_nodes * bs * bs));
-        HostTransfer t = transfer_of(soc ? gs : g, g, agg, na);
-        if (soc) {
+        lev.dinv = U.alloc<double>((size_t)(lev.n_nodes * lev.bs * lev.bs));
+        HostTransfer t = transfer_of(gp, g, agg, na);
+        if (d_strong) {
             lev.strong = d_strong;
             lev.n_strong = n_strong;
-            lev.diag_f = U.alloc<double>((size_t)(lev.n_nodes * bs * bs));
-            lev.dinv_f = U.alloc<double>((size_t)(lev.n_nodes * bs * bs));
+            lev.diag_f = U.alloc<double>((size_t)(lev.n_nodes * lev.bs * lev.bs));
+            lev.dinv_f = U.alloc<double>((size_t)(lev.n_nodes * lev.bs * lev.bs));
             lev.unlumped = U.alloc<uint8_t>((size_t)lev.n_nodes);
         }
-        lev.n_agg = na;
-        lev.p_blocks = (int64_t)t.p_col.size();
-        lev.ap_blocks = (int64_t)t.ap_col.size();
-        lev.c_blocks = (int64_t)t.c_row.size();
-        lev.agg = U.up(agg);
-        lev.p_ptr = U.up(t.p_ptr);
-        lev.p_col = U.up(t.p_col);
-        lev.p_row = U.up(t.p_row);
-        lev.pt_ptr = U.up(t.pt_ptr);
-        lev.pt_blk = U.up(t.pt_blk);
-        lev.ap_ptr = U.up(t.ap_ptr);
-        lev.ap_col = U.up(t.ap_col);
-        lev.ap_row = U.up(t.ap_row);
-        lev.c_bptr = U.up(t.c_bptr);
-        lev.c_row = U.up(t.c_row);
-        lev.p_val = U.alloc<double>((size_t)(lev.p_blocks * bs * bsc));
-        lev.ap_val = U.alloc<double>((size_t)(lev.ap_blocks * bs * bsc));
+        amg_upload_transfer(U, lev, t, agg, na);
         if (k > 0) {
             std::vector<int64_t> aptr;
             std::vector<int32_t> anode;
             nodes_of_aggregates(agg, na, aptr, anode);
-            lev.tl = tentative_lanes((int64_t)anode.size() * bs, na);
+            lev.tl = tentative_lanes((int64_t)anode.size() * lev.bs, na);
             lev.agg_ptr = U.up(aptr);
             lev.agg_node = U.up(anode);
-            lev.t_val = U.alloc<double>((size_t)(lev.n_nodes * bs * k));
+            lev.t_val = U.alloc<double>((size_t)(lev.n_nodes * lev.bs * k));
             lev.dead_a = U.alloc<uint8_t>((size_t)na);
         }
         amg->L.push_back(lev);
-        // the coarse level: a dxo_csr without a mesh
-        std::vector<int64_t> crp;
-        std::vector<int32_t> ccol;
-        rows_of(t.coarse, bsc, crp, ccol);
-        amg_level c;
-        c.own = new dxo_csr;
-        c.own->bs = bsc;
-        c.own->n_nodes = na;
-        c.own->n_rows = na * bsc;
-        c.own->nnz = crp.back();
-        c.own->d_row_ptr = U.up(crp);
-        c.own->d_col = U.up(ccol);
-        c.A = c.own;
-        c.n_nodes = na;
-        c.n_rows = na * bsc;
-        c.nnzb = (int64_t)t.coarse.nb.size();
-        c.bs = c.bsc = bsc;
-        double* cv = U.alloc<double>((size_t)c.own->nnz);
-        c.values = cv;
-        if (k > 0) c.b_val = U.alloc<double>((size_t)(c.n_rows * k));      // T is fixed at creation: no values-dependent mask
-        else c.mask = U.alloc<uint8_t>((size_t)c.n_rows);
-        if (U.rc != DXO_OK) {
+        const amg_level c = amg_coarse_level(U, t.coarse, bsc, k);
+        rc = U.rc;
+        if (rc == DXO_OK && k > 0) rc = amg_nns_level(ctx, amg, lev, c.b_val, s);
+        if (rc != DXO_OK) {
             amg->L.push_back(c);       // owned: freed with the object
-            return U.rc;
+            return rc;
         }
-        if (soc) {
-            const amg_level& v = amg->L.back();
-            if (k > 0) {
-                const int rc = amg_nns_level(ctx, amg, v, c.b_val, s);
-                if (rc != DXO_OK) {
-                    amg->L.push_back(c);
-                    return rc;
-                }
-            }
-            if (v.n_nodes > 0) amg_setup_level(amg, (int)amg->L.size() - 1, v, c, s);
-        }
+        if (lev.strong && lev.n_nodes > 0) amg_setup_level(amg, (int)amg->L.size() - 1, lev, c, s);
         lev = c;
-        bs = bsc;
         g = std::move(t.coarse);
         active.assign((size_t)g.n, 1);
     }
@@ -1762,17 +1512,9 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
                  (long long)amg->nc, (long long)AMG_MAX_DENSE);
         return dxo_fail(ctx, DXO_E_SIZE, msg);
     }
-    if (!soc) {
-        for (const amg_level& v : amg->L) amg->part_cap = std::max({amg->part_cap, rho_parts(v), init_parts(v)});
-        amg->omega = U.alloc<double>(amg->L.size());
-        amg->rho = U.alloc<double>(amg->L.size());
-        amg->cheb = U.alloc<double>(amg->L.size() * AMG_CHEB_STRIDE);
-        amg->scal = U.alloc<double>(2);
-        amg->part = U.alloc<double>((size_t)amg->part_cap);
-        amg->flag = U.alloc<int>(4);
-    } else {
-        for (const amg_level& v : amg->L)
-            if (std::max(rho_parts(v), init_parts(v)) > amg->part_cap) return dxo_fail(ctx, DXO_E_SIZE, "amg.hip: a level outgrew the partials of the first");
+    for (const amg_level& v : amg->L)      // a defect of the sizing rule above, not of the caller
+        if (std::max(rho_parts(v), init_parts(v)) > amg->part_cap) return dxo_fail(ctx, DXO_E_SIZE, "amg.hip: a level outgrew the partials of the first");
+    if (soc) {                             // the numeric phases that ran: their one flag word
         int h = 0;
         DXO_HIP(ctx, hipGetLastError());
         DXO_HIP(ctx, hipMemcpyAsync(&h, amg->flag, sizeof h, hipMemcpyDeviceToHost, s));
@@ -1814,15 +1556,18 @@ void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipSt
         const double* om = amg->omega + l;
         const double* ch = amg->cheb + (size_t)l * AMG_CHEB_STRIDE;
         double *cur = v.xa, *other = v.xb;
-        if (cheby) AMG_BS(v.bs, amg_cheby0, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.dinv, ch, rin, v.d, cur);
-        else AMG_BS(v.bs, amg_jacobi0, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.dinv, om, rin, cur);
+        with_bs(v.bs, [&](auto BS) {      // from x = 0: omega Dinv r, or c2 Dinv r into the direction as well
+            amg_launch(amg_first_step<BS>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.dinv, cheby ? ch + 1 : om, rin, cheby ? v.d : nullptr, cur);
+        });
         for (int k = 1; k < nu; ++k) {
-            if (cheby) cheby_launch(v, ch + 2 * k, rin, cur, other, s);
-            else sweep_launch<false>(v.bs, v, om, rin, cur, other, s);
+            if (cheby) cheby_step(v, ch + 2 * k, rin, cur, other, s);
+            else sweep<false>(v, om, rin, cur, other, s);
             std::swap(cur, other);
         }
-        sweep_launch<true>(v.bs, v, om, rin, cur, v.t, s);
-        AMG_PAIR(v.bs, v.bsc, amg_restrict, amg_grid(v.n_agg), B, 0, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, v.p_val, v.t, amg->L[(size_t)l + 1].r);
+        sweep<true>(v, om, rin, cur, v.t, s);
+        with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
+            amg_launch(amg_restrict<BSR, BSC>, v.n_agg, DXO_AMG_BLOCK, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, v.p_val, v.t, amg->L[(size_t)l + 1].r);
+        });
         v.cur = cur;
     }
     amg_level& c = amg->L.back();
@@ -1839,11 +1584,13 @@ void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipSt
         const double* om = amg->omega + l;
         double* cur = v.cur;
         double* other = cur == v.xa ? v.xb : v.xa;
-        AMG_PAIR(v.bs, v.bsc, amg_prolong, amg_grid(v.n_nodes), B, 0, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, amg->L[(size_t)l + 1].cur, cur);
+        with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
+            amg_launch(amg_prolong<BSR, BSC>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, amg->L[(size_t)l + 1].cur, cur);
+        });
         for (int k = 0; k < nu; ++k) {
             double* out = (l == 0 && k == nu - 1) ? z : other;      // the last sweep of the fine level writes the result
-            if (cheby) cheby_launch(v, amg->cheb + (size_t)l * AMG_CHEB_STRIDE + 2 * k, rin, cur, out, s);
-            else sweep_launch<false>(v.bs, v, om, rin, cur, out, s);
+            if (cheby) cheby_step(v, amg->cheb + (size_t)l * AMG_CHEB_STRIDE + 2 * k, rin, cur, out, s);
+            else sweep<false>(v, om, rin, cur, out, s);
             other = cur;
             cur = out;
         }
@@ -1854,10 +1601,10 @@ void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipSt
 // ---- C ABI
 namespace {
 
-// the symbolic phase and, with a near-null space (k > 0, B on the device), T and B of every level
-int amg_create(dxo_ctx* ctx, const char* who, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, const double* Bnns, int k,
-               int max_levels, int coarse_rows, int sweeps, dxo_amg** out, double theta = 0.0, const double* values = nullptr) {
-    if (n_constrained < 0 || max_levels < 1 || coarse_rows < 1 || sweeps < 1)
+// the hierarchy and, with a near-null space, the dead columns of T of every level
+int amg_create(dxo_ctx* ctx, const char* who, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, const amg_options& opt,
+               dxo_amg** out) {
+    if (n_constrained < 0 || opt.max_levels < 1 || opt.coarse_rows < 1 || opt.sweeps < 1)
         return dxo_fail(ctx, DXO_E_SIZE, (std::string(who) + ": n_constrained < 0, or max_levels, coarse_rows or sweeps < 1").c_str());
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = dxo_launch_stream(ctx);
@@ -1866,11 +1613,11 @@ int amg_create(dxo_ctx* ctx, const char* who, const dxo_csr* csr, const int32_t*
     dxo_amg* a = new dxo_amg;
     a->device = ctx->device;
     a->bs = csr->bs;
-    a->sweeps = sweeps;
-    a->k = k;
-    a->theta = theta;
-    int rc = amg_build(ctx, who, a, csr, constrained, n_constrained, max_levels, coarse_rows, k, theta, values, Bnns, s);
-    if (rc == DXO_OK && k > 0) rc = theta > 0.0 ? amg_nns_dead(ctx, a, s) : amg_near_nullspace(ctx, a, Bnns, s);
+    a->sweeps = opt.sweeps;
+    a->k = opt.k;
+    a->theta = opt.theta;
+    int rc = amg_build(ctx, who, a, csr, constrained, n_constrained, opt, s);
+    if (rc == DXO_OK && opt.k > 0) rc = amg_nns_dead(ctx, a, s);
     if (rc != DXO_OK) {
         amg_free(a);
         return rc;
@@ -1889,7 +1636,9 @@ extern "C" int dxo_amg_create(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* c
     *out = nullptr;
     if (!csr || (n_constrained > 0 && !constrained)) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_create: NULL argument");
     if (csr->bs < 1 || csr->bs > 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create: bs must be 1, 2 or 3");
-    return amg_create(ctx, "dxo_amg_create", csr, constrained, n_constrained, nullptr, 0, max_levels, coarse_rows, sweeps, out);
+    amg_options opt;
+    opt.max_levels = max_levels, opt.coarse_rows = coarse_rows, opt.sweeps = sweeps;
+    return amg_create(ctx, "dxo_amg_create", csr, constrained, n_constrained, opt, out);
 }
 
 extern "C" int dxo_amg_create_nns(dxo_ctx* ctx, const dxo_csr* csr, const int32_t* constrained, int64_t n_constrained, const double* B, int n_modes,
@@ -1901,7 +1650,10 @@ extern "C" int dxo_amg_create_nns(dxo_ctx* ctx, const dxo_csr* csr, const int32_
     if (!((csr->bs == 2 && n_modes == 3) || (csr->bs == 3 && n_modes == 6)))
         return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create_nns: (bs, n_modes) must be (2, 3) or (3, 6)");
     if (amg_misaligned(B)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_amg_create_nns: B must be 8-byte aligned");
-    return amg_create(ctx, "dxo_amg_create_nns", csr, constrained, n_constrained, B, n_modes, max_levels, coarse_rows, sweeps, out);
+    amg_options opt;
+    opt.max_levels = max_levels, opt.coarse_rows = coarse_rows, opt.sweeps = sweeps;
+    opt.k = n_modes, opt.B = B;
+    return amg_create(ctx, "dxo_amg_create_nns", csr, constrained, n_constrained, opt, out);
 }
 
 extern "C" int dxo_amg_create_soc(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const int32_t* constrained, int64_t n_constrained,
@@ -1917,8 +1669,11 @@ extern "C" int dxo_amg_create_soc(dxo_ctx* ctx, const dxo_csr* csr, const double
         return dxo_fail(ctx, DXO_E_DIM, "dxo_amg_create_soc: (bs, n_modes) must be (2, 3) or (3, 6), or n_modes 0");
     if (amg_misaligned(values) || (n_modes != 0 && amg_misaligned(B)))
         return dxo_fail(ctx, DXO_E_ALIGN, "dxo_amg_create_soc: values and B must be 8-byte aligned");
-    return amg_create(ctx, "dxo_amg_create_soc", csr, constrained, n_constrained, n_modes ? B : nullptr, n_modes, max_levels, coarse_rows, sweeps, out,
-                      theta, values);
+    amg_options opt;
+    opt.max_levels = max_levels, opt.coarse_rows = coarse_rows, opt.sweeps = sweeps;
+    opt.k = n_modes, opt.B = n_modes ? B : nullptr;
+    if (theta > 0.0) opt.theta = theta, opt.values = values;      // theta == 0: dxo_amg_create_nns / dxo_amg_create
+    return amg_create(ctx, "dxo_amg_create_soc", csr, constrained, n_constrained, opt, out);
 }
 
 extern "C" int dxo_amg_soc_info(dxo_ctx* ctx, const dxo_amg* amg, int level, double* theta, const uint8_t** strong, int64_t* n_strong_blocks,

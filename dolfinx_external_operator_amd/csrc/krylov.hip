@@ -7,8 +7,8 @@
 // entries of x at it and the bs contiguous values of each of the node's bs rows, and keeps bs sums. A fixed xor-butterfly over the
 // LW lanes then adds them. Index traffic is 4 B per bs^2 nonzeros; no atomics: the result is bit-reproducible.
 //
-// Block Jacobi: one thread per node finds the diagonal block (binary search for the node's own column run), inverts it in closed
-// form (bs <= 3) and writes inv[node][bs][bs]. A block whose |det| is at most 1e-14 of the product of its row norms (Hadamard's bound)
+// Block Jacobi: one thread per node finds the diagonal block (binary search for the node's own column run), inverts it (invert_block:
+// in closed form for bs <= 3; bs 6 is reached by the multigrid levels alone) and writes inv[node][bs][bs]. A block whose |det| is at most 1e-14 of the product of its row norms (Hadamard's bound)
 // is singular: its inverse is written as zero, a flag is raised and the call returns DXO_E_SINGULAR after its one synchronisation.
 //
 // Restarted GMRES(m), right preconditioning, classical Gram-Schmidt with one reorthogonalisation pass (option "krylov_reorth",
@@ -93,29 +93,7 @@ __global__ __launch_bounds__(DXO_KR_BLOCK) void csr_spmv(int64_t n_nodes, const 
     const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
     const int lane = threadIdx.x % LW;
     double acc[BS];
-#pragma unroll
-    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
-    if (node < n_nodes) {
-        const int64_t r0 = row_ptr[node * BS];
-        const int64_t len = row_ptr[node * BS + 1] - r0;      // BS * neighbours
-        const int nnb = (int)(len / BS);
-        for (int k = lane; k < nnb; k += LW) {
-            const int64_t c = col[r0 + (int64_t)k * BS];
-            double xb[BS];
-#pragma unroll
-            for (int j = 0; j < BS; ++j) xb[j] = x[c + j];
-#pragma unroll
-            for (int i = 0; i < BS; ++i) {
-                const double* v = values + r0 + i * len + (int64_t)k * BS;
-#pragma unroll
-                for (int j = 0; j < BS; ++j) acc[i] = fma(v[j], xb[j], acc[i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int off = LW / 2; off > 0; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+    row_product<BS, LW>(n_nodes, node, lane, row_ptr, col, values, x, acc);
     if (node < n_nodes && lane == 0) {
 #pragma unroll
         for (int i = 0; i < BS; ++i) {
@@ -131,29 +109,25 @@ __global__ __launch_bounds__(DXO_KR_BLOCK) void bj_setup(int64_t n_nodes, const 
                                                          const double* __restrict__ values, double* __restrict__ inv, int* __restrict__ singular) {
     const int64_t node = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x;
     if (node >= n_nodes) return;
-    const int64_t r0 = row_ptr[node * BS];
-    const int64_t len = row_ptr[node * BS + 1] - r0;
-    int lo = 0, hi = (int)(len / BS) - 1;
-    const int64_t self = node * BS;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (col[r0 + (int64_t)mid * BS] < self) lo = mid + 1;
-        else hi = mid;
-    }
-    double a[BS][BS], b[BS][BS];
-    bool ok = hi >= 0 && col[r0 + (int64_t)lo * BS] == self;     // an empty row has no block to read
-    if (ok) {
+    const NodeRow<BS> R(row_ptr, node);
+    const int lo = block_pos<BS>(R, col, node);
+    double* out = inv + node * BS * BS;
+    bool ok = false;
+    if (lo >= 0) {
+        double a[BS][BS], b[BS][BS];
 #pragma unroll
         for (int i = 0; i < BS; ++i)
 #pragma unroll
-            for (int j = 0; j < BS; ++j) a[i][j] = values[r0 + i * len + (int64_t)lo * BS + j];
+            for (int j = 0; j < BS; ++j) a[i][j] = values[R.r0 + i * R.len + (int64_t)lo * BS + j];
         ok = invert_block<BS>(a, b);
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) out[i * BS + j] = ok ? b[i][j] : 0.0;
+    } else {      // an absent block is not read: a zero inverse and the flag, which is also what inverting a block of zeros ends with
+#pragma unroll
+        for (int i = 0; i < BS * BS; ++i) out[i] = 0.0;
     }
-    double* out = inv + node * BS * BS;
-#pragma unroll
-    for (int i = 0; i < BS; ++i)
-#pragma unroll
-        for (int j = 0; j < BS; ++j) out[i * BS + j] = ok ? b[i][j] : 0.0;
     if (!ok) singular[0] = 1;     // every writer stores the same word
 }
 
@@ -686,7 +660,8 @@ void dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* in
     const dim3 g((unsigned)((csr->n_nodes + DXO_KR_BLOCK - 1) / DXO_KR_BLOCK)), b(DXO_KR_BLOCK);
     if (csr->bs == 1) hipLaunchKernelGGL(bj_setup<1>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
     else if (csr->bs == 2) hipLaunchKernelGGL(bj_setup<2>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
-    else hipLaunchKernelGGL(bj_setup<3>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+    else if (csr->bs == 3) hipLaunchKernelGGL(bj_setup<3>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
+    else hipLaunchKernelGGL(bj_setup<6>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);      // a multigrid level
 }
 
 extern "C" int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y) {

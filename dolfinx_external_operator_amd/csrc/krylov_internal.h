@@ -1,51 +1,193 @@
-// krylov_internal.h — launchers shared between krylov.hip and amg.hip (device pointers, explicit stream, no locking, no event bracket).
+// krylov_internal.h — what krylov.hip and amg.hip share. Device code: the row of a node in the csr.h layout (NodeRow), the search for
+// a block in it (block_pos), the lane-group row product behind every SpMV-shaped kernel of the two files (row_product) and the
+// inverse of a diagonal block with its singularity test (invert_block: closed form up to bs 3, Gauss-Jordan in registers for bs 6).
+// Host code: the launchers one file calls in the other (device pointers, explicit stream, no locking, no event bracket).
 #pragma once
 
 #include "csr.h"
 
-// the closed-form inverse of a diagonal block (bs <= 3) and its singularity test, for dxo_csr_block_jacobi (krylov.hip) and the lumped
-// diagonal blocks of the filtered prolongator smoothing (amg.hip)
+// the run of a node's rows in the csr.h layout: the bs rows of a node share their columns, row i of block k starts at
+// r0 + i * len + k * BS
 template <int BS>
-__device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (&b)[BS][BS]) {
-    double had = 1.0;
-#pragma unroll
-    for (int i = 0; i < BS; ++i) {
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < BS; ++j) s += a[i][j] * a[i][j];
-        had *= sqrt(s);
+struct NodeRow {
+    int64_t r0, len;      // first entry of the node's first row; entries per row = BS * neighbours
+    int nnb;              // neighbour blocks
+    __device__ __forceinline__ NodeRow(const int64_t* __restrict__ row_ptr, int64_t node) {
+        r0 = row_ptr[node * BS];
+        len = row_ptr[node * BS + 1] - r0;
+        nnb = (int)(len / BS);
     }
-    double det;
-    if constexpr (BS == 1) {
-        det = a[0][0];
-        b[0][0] = 1.0 / det;
-    } else if constexpr (BS == 2) {
-        det = a[0][0] * a[1][1] - a[0][1] * a[1][0];
-        const double id = 1.0 / det;
-        b[0][0] = a[1][1] * id;
-        b[0][1] = -a[0][1] * id;
-        b[1][0] = -a[1][0] * id;
-        b[1][1] = a[0][0] * id;
-    } else {
-        const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1];
-        const double c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2];
-        const double c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];
-        det = a[0][0] * c00 + a[0][1] * c01 + a[0][2] * c02;
-        const double id = 1.0 / det;
-        b[0][0] = c00 * id;
-        b[1][0] = c01 * id;
-        b[2][0] = c02 * id;
-        b[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) * id;
-        b[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) * id;
-        b[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) * id;
-        b[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) * id;
-        b[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) * id;
-        b[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) * id;
+};
+
+// position of the block of column `node` among the blocks of a node's row (its own: the diagonal block), or -1 (an empty row has
+// no block to read)
+template <int BS>
+__device__ __forceinline__ int block_pos(const NodeRow<BS>& R, const int32_t* __restrict__ col, int64_t node) {
+    int lo = 0, hi = R.nnb - 1;
+    const int64_t self = node * BS;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (col[R.r0 + (int64_t)mid * BS] < self) lo = mid + 1;
+        else hi = mid;
     }
-    return fabs(det) > 1e-14 * had;     // false for a zero, NaN or nearly singular block
+    return hi >= 0 && col[R.r0 + (int64_t)lo * BS] == self ? lo : -1;
 }
 
-// krylov.hip: the block-inverse kernel of dxo_csr_block_jacobi without its wait; a singular block raises flag[0]
+// acc = (A x)_node over a group of LW lanes: lane l takes the blocks k = l, l + LW, ... in ascending order (one column index per
+// block, the BS entries of x at it, fma(v[j], xb[j], acc[i]) with j innermost), then the xor-butterfly from LW / 2 down leaves the
+// sums on every lane. All lanes of a group call it; those of a node >= n_nodes add nothing. pick(R, k, c, ab, ld), c the first column
+// of block k, may skip the block (false) or replace its pointer and leading dimension; SCALED: x is taken as sx x.
+template <int BS, int LW, bool SCALED = false, class Pick>
+__device__ __forceinline__ void row_product(int64_t n_nodes, int64_t node, int lane, const int64_t* __restrict__ row_ptr,
+                                            const int32_t* __restrict__ col, const double* __restrict__ values, const double* __restrict__ x,
+                                            double sx, double (&acc)[BS], Pick pick) {
+#pragma unroll
+    for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+    if (node < n_nodes) {
+        const NodeRow<BS> R(row_ptr, node);
+        for (int k = lane; k < R.nnb; k += LW) {
+            const int64_t c = col[R.r0 + (int64_t)k * BS];
+            const double* ab = values + R.r0 + (int64_t)k * BS;
+            int64_t ld = R.len;
+            if (!pick(R, k, c, ab, ld)) continue;
+            double xb[BS];
+#pragma unroll
+            for (int j = 0; j < BS; ++j) xb[j] = SCALED ? sx * x[c + j] : x[c + j];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) {
+                const double* v = ab + i * ld;
+#pragma unroll
+                for (int j = 0; j < BS; ++j) acc[i] = fma(v[j], xb[j], acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = LW / 2; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < BS; ++i) acc[i] += __shfl_xor(acc[i], off, LW);
+}
+
+// the matrix as it is stored: every block, x unscaled
+template <int BS, int LW>
+__device__ __forceinline__ void row_product(int64_t n_nodes, int64_t node, int lane, const int64_t* __restrict__ row_ptr,
+                                            const int32_t* __restrict__ col, const double* __restrict__ values, const double* __restrict__ x,
+                                            double (&acc)[BS]) {
+    row_product<BS, LW>(n_nodes, node, lane, row_ptr, col, values, x, 1.0, acc, [](const NodeRow<BS>&, int, int64_t, const double*&, int64_t&) { return true; });
+}
+
+// Gauss-Jordan on [A | I] with partial pivoting (the lowest row among equals). Rows are exchanged by compare-and-select over static
+// indices, so the 72 doubles stay in registers. M = [A | I] on entry, [. | A^-1] on return; false for a zero, NaN or nearly singular
+// block (the rule of invert_block)
+__device__ __forceinline__ bool gj6(double (&M)[6][12]) {
+    constexpr int BS = 6;
+    double had = 1.0, det = 1.0;
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+        double n2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) n2 = fma(M[i][j], M[i][j], n2);
+        had *= sqrt(n2);
+    }
+#pragma unroll
+    for (int k = 0; k < BS; ++k) {
+        int p = k;
+        double best = fabs(M[k][k]);
+#pragma unroll
+        for (int i = k + 1; i < BS; ++i) {
+            const double v = fabs(M[i][k]);
+            if (v > best) {
+                best = v;
+                p = i;
+            }
+        }
+#pragma unroll
+        for (int i = k + 1; i < BS; ++i) {
+            const bool sw = p == i;
+#pragma unroll
+            for (int c = k; c < 2 * BS; ++c) {
+                const double x = M[k][c], y = M[i][c];
+                M[k][c] = sw ? y : x;
+                M[i][c] = sw ? x : y;
+            }
+        }
+        if (p != k) det = -det;
+        const double piv = M[k][k];
+        det *= piv;
+#pragma unroll
+        for (int c = k; c < 2 * BS; ++c) M[k][c] = M[k][c] / piv;
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            if (i == k) continue;
+            const double fct = M[i][k];
+#pragma unroll
+            for (int c = k; c < 2 * BS; ++c) M[i][c] = fma(-fct, M[k][c], M[i][c]);
+        }
+    }
+    return fabs(det) > 1e-14 * had;
+}
+
+// the inverse of a diagonal block and its singularity test (|det| at most 1e-14 of the product of the row norms: false), for
+// dxo_csr_block_jacobi, the block-Jacobi inverses of the multigrid levels and the lumped diagonal blocks of the filtered prolongator
+// smoothing: in closed form for bs <= 3, by gj6 for the coarse levels of block size 6
+template <int BS>
+__device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (&b)[BS][BS]) {
+    static_assert(BS <= 3 || BS == 6, "no inverse for this block size");
+    if constexpr (BS == 6) {
+        double M[BS][2 * BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) {
+                M[i][j] = a[i][j];
+                M[i][BS + j] = i == j ? 1.0 : 0.0;
+            }
+        const bool ok = gj6(M);
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) b[i][j] = M[i][BS + j];
+        return ok;
+    } else {
+        double had = 1.0;
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < BS; ++j) s += a[i][j] * a[i][j];
+            had *= sqrt(s);
+        }
+        double det;
+        if constexpr (BS == 1) {
+            det = a[0][0];
+            b[0][0] = 1.0 / det;
+        } else if constexpr (BS == 2) {
+            det = a[0][0] * a[1][1] - a[0][1] * a[1][0];
+            const double id = 1.0 / det;
+            b[0][0] = a[1][1] * id;
+            b[0][1] = -a[0][1] * id;
+            b[1][0] = -a[1][0] * id;
+            b[1][1] = a[0][0] * id;
+        } else {
+            const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1];
+            const double c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2];
+            const double c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];
+            det = a[0][0] * c00 + a[0][1] * c01 + a[0][2] * c02;
+            const double id = 1.0 / det;
+            b[0][0] = c00 * id;
+            b[1][0] = c01 * id;
+            b[2][0] = c02 * id;
+            b[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) * id;
+            b[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) * id;
+            b[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) * id;
+            b[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) * id;
+            b[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) * id;
+            b[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) * id;
+        }
+        return fabs(det) > 1e-14 * had;     // false for a zero, NaN or nearly singular block
+    }
+}
+
+// krylov.hip: the block-inverse kernel of dxo_csr_block_jacobi without its wait, for bs 1, 2, 3 and 6; a singular block raises flag[0]
 void dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv, int* flag, hipStream_t s);
 
 // amg.hip: the checks of a DXO_PC_AMG preconditioner against the operator, and one V-cycle z = V(r) on the stream
