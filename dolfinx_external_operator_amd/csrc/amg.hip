@@ -1270,7 +1270,7 @@ void amg_estimate_rho(dxo_amg* amg, const amg_level& v, bool filtered, double* r
 // the numeric phase of level l: from the values of v to those of the next level c
 void amg_setup_level(dxo_amg* amg, int l, const amg_level& v, const amg_level& c, hipStream_t s) {
     const bool nns = amg->k > 0;
-    dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);
+    (void)dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);      // a level has block size 1, 2, 3 or 6 (with_bs)
     const double* omega_p = amg->omega + l;
     if (v.strong) {
         with_bs(v.bs, [&](auto BS) {

@@ -374,21 +374,37 @@ int spmv_lanes(const dxo_ctx* ctx, const dxo_csr* A) {
     return lw;
 }
 
-void spmv_launch(const dxo_ctx* ctx, const dxo_csr* A, const double* values, double alpha, const double* x, double beta, double* y, hipStream_t s) {
-    if (A->n_nodes == 0) return;
+// a block size without a kernel is refused, never served by the kernel of another one
+int bs_refused(dxo_ctx* ctx, const char* who, const char* takes, int bs) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: no kernel for block size %d (%s)", who, bs, takes);
+    return dxo_fail(ctx, DXO_E_DIM, msg);
+}
+
+// bs 1, 2, 3: the patterns of dxo_csr_create; 6: the pattern of a multigrid level (dxo_amg_info hands its dxo_csr out)
+int spmv_launch(dxo_ctx* ctx, const char* who, const dxo_csr* A, const double* values, double alpha, const double* x, double beta, double* y,
+                hipStream_t s) {
+    if (A->bs != 1 && A->bs != 2 && A->bs != 3 && A->bs != 6) return bs_refused(ctx, who, "the product takes 1, 2, 3 or 6", A->bs);
+    if (A->n_nodes == 0) return DXO_OK;
     const int lw = spmv_lanes(ctx, A);
     if (A->bs == 1) spmv_bs<1>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
     else if (A->bs == 2) spmv_bs<2>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
-    else spmv_bs<3>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
+    else if (A->bs == 3) spmv_bs<3>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
+    else spmv_bs<6>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
+    return DXO_OK;
 }
 
-void bj_apply_launch(const dxo_ctx* ctx, int bs, int64_t n, const double* inv, const double* r, double* z, hipStream_t s) {
+// bs 1, 2, 3 (kr_validate and dxo_block_jacobi_apply let nothing else through: the levels of block size 6 apply their inverses
+// inside the sweeps of amg.hip)
+int bj_apply_launch(dxo_ctx* ctx, const char* who, int bs, int64_t n, const double* inv, const double* r, double* z, hipStream_t s) {
+    if (bs < 1 || bs > 3) return bs_refused(ctx, who, "block Jacobi takes 1, 2 or 3", bs);
     const int64_t nn = n / bs;
-    if (nn == 0) return;
+    if (nn == 0) return DXO_OK;
     const dim3 g(kr_grid(ctx, nn, 8)), b(DXO_KR_BLOCK);
     if (bs == 1) hipLaunchKernelGGL(bj_apply<1>, g, b, 0, s, nn, inv, r, z);
     else if (bs == 2) hipLaunchKernelGGL(bj_apply<2>, g, b, 0, s, nn, inv, r, z);
     else hipLaunchKernelGGL(bj_apply<3>, g, b, 0, s, nn, inv, r, z);
+    return DXO_OK;
 }
 
 bool misaligned(const void* p) { return ((uintptr_t)p & 7u) != 0; }
@@ -401,10 +417,7 @@ struct KrCall {
     const dxo_krylov_pc* pc;
     hipStream_t s;
     int apply(const double* v, double* out) {
-        if (op->csr) {
-            spmv_launch(ctx, op->csr, op->values, 1.0, v, 0.0, out, s);
-            return DXO_OK;
-        }
+        if (op->csr) return spmv_launch(ctx, "dxo_krylov", op->csr, op->values, 1.0, v, 0.0, out, s);
         const int rc = op->apply(op->user, v, out);
         if (rc != DXO_OK) {
             char msg[128];
@@ -413,16 +426,16 @@ struct KrCall {
         }
         return DXO_OK;
     }
-    void precond(const double* r, double* z) {
+    int precond(const double* r, double* z) {
         if (!pc || pc->kind == DXO_PC_NONE) {
-            (void)hipMemcpyAsync(z, r, (size_t)ws->n * sizeof(double), hipMemcpyDeviceToDevice, s);
-            return;
+            DXO_HIP(ctx, hipMemcpyAsync(z, r, (size_t)ws->n * sizeof(double), hipMemcpyDeviceToDevice, s));
+            return DXO_OK;
         }
         if (pc->kind == DXO_PC_AMG) {
             dxo_amg_cycle(ctx, (dxo_amg*)pc->inv, r, z, s);
-            return;
+            return DXO_OK;
         }
-        bj_apply_launch(ctx, pc->kind == DXO_PC_JACOBI ? 1 : pc->bs, ws->n, pc->inv, r, z, s);
+        return bj_apply_launch(ctx, "dxo_krylov", pc->kind == DXO_PC_JACOBI ? 1 : pc->bs, ws->n, pc->inv, r, z, s);
     }
     // part[0..nb) = partials of (a, b); reduce into out (norm: sqrt and inverse into out[0], out[1])
     void dot_partials(const double* a, const double* b, double* part) {
@@ -458,6 +471,8 @@ int kr_validate(dxo_ctx* ctx, const char* who, dxo_krylov* ws, const dxo_krylov_
                  (long long)(op->csr ? op->csr->n_rows : op->n), (long long)ws->n);
         return dxo_fail(ctx, DXO_E_SIZE, msg);
     }
+    if (op->csr && op->csr->bs != 1 && op->csr->bs != 2 && op->csr->bs != 3 && op->csr->bs != 6)
+        return bs_refused(ctx, who, "the product takes 1, 2, 3 or 6", op->csr->bs);
     if (pc && pc->kind == DXO_PC_AMG) {      // pc->inv carries the dxo_amg*
         if (pc->n != ws->n) {
             snprintf(msg, sizeof msg, "%s: the preconditioner covers %lld rows, the operator has %lld", who, (long long)pc->n, (long long)ws->n);
@@ -539,7 +554,7 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
         for (int j = 0; j < m && total + j < max_it; ++j) {
             double* w = ws->V() + (int64_t)(j + 1) * ws->ld;
             double* h = sc + (int64_t)j * (m + 1);
-            K.precond(ws->V() + (int64_t)j * ws->ld, ws->Z());
+            if ((rc = K.precond(ws->V() + (int64_t)j * ws->ld, ws->Z())) != DXO_OK) return rc;
             if ((rc = K.apply(ws->Z(), w)) != DXO_OK) return rc;
             kr_multidot_launch(K, j + 1, w);
             hipLaunchKernelGGL(kr_reduce, dim3(j + 1), B, 0, s, ws->part, ws->nb, h, (double*)nullptr, 0, (double*)nullptr);
@@ -566,7 +581,7 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
         if (k > 0) {
             hipLaunchKernelGGL(kr_trisolve, dim3(1), dim3(64), 0, s, sc, k, m, ws->o_g(), ws->o_y());
             hipLaunchKernelGGL(kr_combine, G, B, 0, s, n, ws->V(), ws->ld, k, sc + ws->o_y(), ws->T());
-            K.precond(ws->T(), ws->Z());
+            if ((rc = K.precond(ws->T(), ws->Z())) != DXO_OK) return rc;
             hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ONE, 1.0, ws->Z(), x);
         }
         if (k == 0) break;
@@ -604,7 +619,7 @@ int cg_impl(KrCall& K, const double* b, double* x, double rtol, double atol, int
     if (beta > tol && max_it > 0) {
         info->restarts = 1;
         hipLaunchKernelGGL(kr_cycle_init, One, dim3(64), 0, s, ws->sc, st, 0, ws->o_g(), ws->o_s());
-        K.precond(r, z);
+        if ((rc = K.precond(r, z)) != DXO_OK) return rc;
         DXO_HIP(ctx, hipMemcpyAsync(p, z, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
         K.dot_partials(r, z, ws->part);
         hipLaunchKernelGGL(kr_cg_scalar, One, B, 0, s, ws->part, ws->nb, S, st, 0, 0, tol);
@@ -617,7 +632,7 @@ int cg_impl(KrCall& K, const double* b, double* x, double rtol, double atol, int
             hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ALPHA, -1.0, q, r);
             K.dot_partials(r, r, ws->part);
             hipLaunchKernelGGL(kr_cg_scalar, One, B, 0, s, ws->part, ws->nb, S, st, 2, it, tol);
-            K.precond(r, z);
+            if ((rc = K.precond(r, z)) != DXO_OK) return rc;
             K.dot_partials(r, z, ws->part);
             hipLaunchKernelGGL(kr_cg_scalar, One, B, 0, s, ws->part, ws->nb, S, st, 3, it, tol);
             hipLaunchKernelGGL(kr_xpay, G, B, 0, s, n, z, S + S_BETA, p);
@@ -655,13 +670,15 @@ int kr_solve(dxo_ctx* ctx, const char* who, kr_solver solver, dxo_krylov* ws, co
 
 }  // namespace
 
-void dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv, int* flag, hipStream_t s) {
-    if (csr->n_nodes == 0) return;
+int dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv, int* flag, hipStream_t s) {
+    if (csr->bs != 1 && csr->bs != 2 && csr->bs != 3 && csr->bs != 6) return DXO_E_DIM;
+    if (csr->n_nodes == 0) return DXO_OK;
     const dim3 g((unsigned)((csr->n_nodes + DXO_KR_BLOCK - 1) / DXO_KR_BLOCK)), b(DXO_KR_BLOCK);
     if (csr->bs == 1) hipLaunchKernelGGL(bj_setup<1>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
     else if (csr->bs == 2) hipLaunchKernelGGL(bj_setup<2>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
     else if (csr->bs == 3) hipLaunchKernelGGL(bj_setup<3>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
     else hipLaunchKernelGGL(bj_setup<6>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);      // a multigrid level
+    return DXO_OK;
 }
 
 extern "C" int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y) {
@@ -673,8 +690,9 @@ extern "C" int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* valu
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     int rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    spmv_launch(ctx, csr, values, alpha, x, beta, y, s);
-    return dxo_device_end(ctx, s);
+    rc = spmv_launch(ctx, "dxo_csr_spmv", csr, values, alpha, x, beta, y, s);
+    const int end = dxo_device_end(ctx, s);
+    return rc != DXO_OK ? rc : end;
 }
 
 extern "C" int dxo_csr_block_jacobi(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double* inv) {
@@ -682,13 +700,14 @@ extern "C" int dxo_csr_block_jacobi(dxo_ctx* ctx, const dxo_csr* csr, const doub
     DXO_LOCK(ctx);
     if (!csr || !values || !inv) return dxo_fail(ctx, DXO_E_NULL, "dxo_csr_block_jacobi: NULL argument");
     if (misaligned(values) || misaligned(inv)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_csr_block_jacobi: arrays must be 8-byte aligned");
+    if (csr->bs != 1 && csr->bs != 2 && csr->bs != 3 && csr->bs != 6) return bs_refused(ctx, "dxo_csr_block_jacobi", "the block inverse takes 1, 2, 3 or 6", csr->bs);
     if (csr->n_nodes == 0) return DXO_OK;
     hipStream_t s = dxo_launch_stream(ctx);
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     int* flag = (int*)dxo_scratch(ctx, s, 16);
     if (!flag) return dxo_fail(ctx, DXO_E_SIZE, "dxo_csr_block_jacobi: scratch allocation failed");
     DXO_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int), s));
-    dxo_kr_bj_setup_launch(csr, values, inv, flag, s);
+    (void)dxo_kr_bj_setup_launch(csr, values, inv, flag, s);      // the block size was checked above
     int h = 0;
     DXO_HIP(ctx, hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s));
     DXO_HIP(ctx, hipStreamSynchronize(s));
@@ -707,8 +726,9 @@ extern "C" int dxo_block_jacobi_apply(dxo_ctx* ctx, int bs, int64_t n, const dou
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     int rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    bj_apply_launch(ctx, bs, n, inv, r, z, s);
-    return dxo_device_end(ctx, s);
+    rc = bj_apply_launch(ctx, "dxo_block_jacobi_apply", bs, n, inv, r, z, s);
+    const int end = dxo_device_end(ctx, s);
+    return rc != DXO_OK ? rc : end;
 }
 
 extern "C" int dxo_krylov_create(dxo_ctx* ctx, int64_t n, int restart, dxo_krylov** out) {

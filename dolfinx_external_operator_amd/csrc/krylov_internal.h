@@ -187,8 +187,9 @@ __device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (
     }
 }
 
-// krylov.hip: the block-inverse kernel of dxo_csr_block_jacobi without its wait, for bs 1, 2, 3 and 6; a singular block raises flag[0]
-void dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv, int* flag, hipStream_t s);
+// krylov.hip: the block-inverse kernel of dxo_csr_block_jacobi without its wait, for bs 1, 2, 3 and 6 (DXO_E_DIM and no launch for any
+// other); a singular block raises flag[0]
+int dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv, int* flag, hipStream_t s);
 
 // amg.hip: the checks of a DXO_PC_AMG preconditioner against the operator, and one V-cycle z = V(r) on the stream
 int dxo_amg_pc_check(dxo_ctx* ctx, const char* who, const dxo_amg* amg, const dxo_csr* op_csr, int bs, int64_t n);
