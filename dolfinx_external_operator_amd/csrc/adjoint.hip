@@ -31,6 +31,8 @@
 // measured slower; profiles/r05_patch_form.txt) lives in scripts/exp/adjoint_patch*.h and is compiled only with -DDXO_EXPERIMENTS.
 // Kernel variants that were measured and not shipped (contraction across the lanes as well, lane = cell tangent action) live in
 // scripts/exp/adjoint_variants.h and are compiled only with -DDXO_EXPERIMENTS.
+// What the kernels share is one function each: pull_back, group_cells, gather_vertices, point_jacobian (operand_core.h), store_entry,
+// sym_products / sym_dot (below); on the host consumer_grid, is_q2_hex .. is_p2_tri and wave_region.
 #include "dxo_common.h"
 #include "operand_core.h"
 #include "adjoint_cell.h"
@@ -46,24 +48,9 @@
 
 #include <atomic>
 
-// experiment switches (scripts/exp/ab_adjoint.py builds variants with -D...)
-#ifndef DXO_TA_NT
-#define DXO_TA_NT 0          // non-temporal loads of the tangent rows
-#endif
-#ifndef DXO_TA_PIPE
-#define DXO_TA_PIPE 1        // register-pipelined dof gather
-#endif
-#ifndef DXO_TA_EARLY_C
-#define DXO_TA_EARLY_C 1     // request the tangent row before the contraction
-#endif
-#ifndef DXO_ADJ_PAD
-#define DXO_ADJ_PAD 1        // odd per-point stride of the parked tensors
-#endif
+// tuning knobs (scripts/exp/ab_adjoint.py builds variants with -D...)
 #ifndef DXO_TA_WAVES
 #define DXO_TA_WAVES 2
-#endif
-#ifndef DXO_TA_RS
-#define DXO_TA_RS 1          // Q2 hexahedra: scatter phase in registers with a DPP reduce-scatter (scatter_rs)
 #endif
 #ifdef DXO_EXPERIMENTS       // variants that were measured and not shipped (scripts/exp/adjoint_variants.h)
 #ifndef DXO_TA_C8_FORWARD
@@ -89,16 +76,43 @@
 #ifndef DXO_TA_VM_WAVES
 #define DXO_TA_VM_WAVES 2    // waves per SIMD of the state-based tangent action (3: 45 registers spilled on hexahedra)
 #endif
-#ifndef DXO_TA_STAGE
-#define DXO_TA_STAGE 1       // tangent rows requested lane-linear and passed through LDS (TangentRows) instead of row-per-lane loads
-#endif
 
 namespace {
 
-template <bool NT>
-__device__ __forceinline__ dxo_f64x2 ta_load(const dxo_f64x2* p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
+// ---- helpers every consumer kernel shares (the geometry-only gather, J^-1 and the pull-back live in operand_core.h)
+
+// one element-vector entry (local node a of `cell`, BS components): two-pass form fe[a][cell][i], summed per node afterwards
+// (node_sum) — the cells of a wave group are consecutive, so each local node's entries leave as one contiguous run per group,
+// and in node_sum neighbouring nodes (same local role in neighbouring cells) read neighbouring addresses — or, fe == nullptr,
+// added to `out` through the dofmap with fp64 hardware atomics
+template <int BS>
+__device__ __forceinline__ void store_entry(const OperandDev& m, double* fe, double* out, int64_t cell, int a, int nd, const double (&o)[BS]) {
+    if (fe) {
+#pragma unroll
+        for (int i = 0; i < BS; ++i) fe[((int64_t)a * m.num_cells_fe + cell) * BS + i] = o[i];
+    } else {
+        const int64_t node = m.dofmap[cell * nd + a];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) unsafeAtomicAdd(out + node * BS + i, o[i]);
+    }
+}
+
+// phase 2 of the diagonals: the products z_k z_kk (k <= kk) of a node's N reference derivatives, and their sum against one
+// symmetrised matrix P (N (N + 1) / 2 numbers, the off-diagonal ones already doubled)
+template <int N>
+__device__ __forceinline__ void sym_products(const double (&z)[N], double (&pp)[N * (N + 1) / 2]) {
+    int slot = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+        for (int kk = k; kk < N; ++kk) pp[slot++] = z[k] * z[kk];
+}
+template <int NS1>
+__device__ __forceinline__ double sym_dot(const double (&pp)[NS1], const double* P) {
+    double t = 0.0;
+#pragma unroll
+    for (int s = 0; s < NS1; ++s) t += pp[s] * P[s];
+    return t;
 }
 
 // ---- the tangent rows of a wave group, coalesced. A lane needs the D*D entries of ITS point; asking for them row-per-lane makes
@@ -127,7 +141,7 @@ struct TangentRows {
 #pragma unroll
             for (int k = 0; k < LPC; ++k) {
                 const int u = c * TR_PC * CV + k * DXO_WAVE + lane;
-                r[c][k] = u < npts * CV ? ta_load<DXO_TA_NT != 0>(base + u) : dxo_f64x2{1.0, 0.5};
+                r[c][k] = u < npts * CV ? base[u] : dxo_f64x2{1.0, 0.5};
             }
     }
     // t = C_row e for this lane's point straight from the staged rows (the row never sits in registers)
@@ -212,19 +226,11 @@ __device__ __forceinline__ void adjoint_scatter(const OperandDev& m, const doubl
     // per-point stride: an ODD number of doubles. Phase 2's lanes read the same slot of up to three different cells at once
     // (cell stride = nq points); with the natural stride 12 (hexahedra: 8 x 12 doubles = 192 dwords = 0 mod 64 banks) those
     // reads collided on one bank — a quarter of the kernel's LDS cycles were conflict cycles (profiles/r04_device_loop_sq.json)
-    constexpr int PT = DXO_ADJ_PAD ? ((BS * (G + 1)) | 1) : BS * (G + 1);
+    constexpr int PT = (BS * (G + 1)) | 1;
     if (active) {
 #pragma unroll
-        for (int i = 0; i < BS; ++i) {
-            Tm[lane * PT + i] = scale * vh[i];
-#pragma unroll
-            for (int k = 0; k < G; ++k) {
-                double t = 0.0;
-#pragma unroll
-                for (int j = 0; j < G; ++j) t += gh[i][j] * K[k][j];
-                Tm[lane * PT + BS + i * G + k] = scale * t;
-            }
-        }
+        for (int i = 0; i < BS; ++i) Tm[lane * PT + i] = scale * vh[i];
+        pull_back<G, BS>(gh, K, scale, *reinterpret_cast<double (*)[BS][G]>(Tm + lane * PT + BS));
     }
     op_fence();
     const int nd = m.ndofs, nq = m.nq;
@@ -245,18 +251,7 @@ __device__ __forceinline__ void adjoint_scatter(const OperandDev& m, const doubl
                 acc[i] += t;
             }
         }
-        const int64_t cell = cells ? (int64_t)cells[c0 + c] : c0 + c;
-        if (fe) {        // two-pass form: the element vector entry, summed per node afterwards (node_sum).
-            // Layout fe[a][cell][i]: the cells of a wave group are consecutive, so each local node's entries leave as one
-            // contiguous run per group, and in node_sum neighbouring nodes (same local role in neighbouring cells) read
-            // neighbouring addresses.
-#pragma unroll
-            for (int i = 0; i < BS; ++i) fe[((int64_t)a * m.num_cells_fe + cell) * BS + i] = acc[i];
-        } else {
-            const int64_t node = m.dofmap[cell * nd + a];
-#pragma unroll
-            for (int i = 0; i < BS; ++i) unsafeAtomicAdd(out + node * BS + i, acc[i]);
-        }
+        store_entry<BS>(m, fe, out, cells ? (int64_t)cells[c0 + c] : c0 + c, a, nd, acc);
     }
     op_fence();
 }
@@ -281,18 +276,8 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_adjoint(OperandDev m, const
     for (int64_t grp = walk.first; grp < walk.end; grp += walk.stride) {
         const int64_t c0 = grp * cpw;
         const int ncell = (n_cells - c0 < cpw) ? (int)(n_cells - c0) : cpw;
-        // only the geometry is needed
-        {
-            const int ng = m.ngeom, sx = op_odd(ng * G);
-            double* X = W + cpw * op_odd(m.ndofs * BS);
-            for (int idx = lane; idx < ncell * ng; idx += DXO_WAVE) {
-                const int c = idx / ng, v = idx - c * ng;
-                const int64_t cell = cells ? (int64_t)cells[c0 + c] : c0 + c;
-                const int64_t node = m.geom_dofmap[cell * ng + v];
-#pragma unroll
-                for (int j = 0; j < G; ++j) X[c * sx + v * G + j] = m.x[node * G + j];
-            }
-        }
+        double* X = W + cpw * op_odd(m.ndofs * BS);      // only the geometry is needed
+        gather_vertices<G>(m, X, cells, c0, ncell, lane);
         op_fence();
         const int c = lane / m.nq, q = lane - c * m.nq;
         const bool active = c < ncell;
@@ -309,19 +294,7 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_adjoint(OperandDev m, const
         }
         if (active) {
             const OperandLayout<G> L(m);
-            const double* dpsi = tab + L.o_dpsi + q * L.sdpsi;
-            const double* Xc = W + cpw * op_odd(m.ndofs * BS) + c * L.sx;
-            double J[G][G];
-#pragma unroll
-            for (int j = 0; j < G; ++j)
-#pragma unroll
-                for (int k = 0; k < G; ++k) J[j][k] = 0.0;
-            for (int v = 0; v < m.ngeom; ++v)
-#pragma unroll
-                for (int j = 0; j < G; ++j)
-#pragma unroll
-                    for (int k = 0; k < G; ++k) J[j][k] += Xc[v * G + j] * dpsi[v * G + k];
-            const double det = invert<G>(J, K);
+            const double det = point_jacobian<G>(tab + L.o_dpsi + q * L.sdpsi, X + c * L.sx, m.ngeom, K);
             scale = wq[q] * fabs(det);
             double s[D];
             const double* Sp = S + ((c0 + c) * m.nq + q) * D;
@@ -333,9 +306,6 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_adjoint(OperandDev m, const
     }
 }
 
-#ifndef DXO_NS_WIDE
-#define DXO_NS_WIDE 1    // node_sum: 16-byte index and element-vector loads
-#endif
 #ifndef DXO_C8_ADJ_BLOCKS_PER_CU
 #define DXO_C8_ADJ_BLOCKS_PER_CU 32   // operand_adjoint_c8 grid; 4 / 8 / 16 / 32 / 64 / uncapped workgroups per CU: 0.780 / 0.754 / 0.742 / 0.718 / 0.725 / 0.818 ms per call
 #endif
@@ -389,18 +359,13 @@ __global__ __launch_bounds__(DXO_BLOCK) void node_sum(int64_t n_nodes, const int
             double f[U][BS];
             // the kernel is bound by the ISSUE of its scattered loads (SQ_WAIT_INST_ANY 0.49 of the wave cycles): the four indices are
             // one 16-byte load (4-byte aligned: the array is padded by U - 1 entries), an entry's BS doubles one or two loads
-#if DXO_NS_WIDE
             const NodeEnt4 i4 = *reinterpret_cast<const NodeEnt4*>(ent + e);
 #pragma unroll
             for (int k = 0; k < U; ++k) idx[k] = e + k < e1 ? i4[k] : 0u;
-#else
-#pragma unroll
-            for (int k = 0; k < U; ++k) idx[k] = e + k < e1 ? ent[e + k] : 0u;
-#endif
 #pragma unroll
             for (int k = 0; k < U; ++k) {
                 const double* src = fe + (int64_t)idx[k] * BS;
-                if constexpr (BS >= 2 && DXO_NS_WIDE) {
+                if constexpr (BS >= 2) {
                     const NodeF64x2 v = *reinterpret_cast<const NodeF64x2*>(src);
                     f[k][0] = v.x;
                     f[k][1] = v.y;
@@ -445,14 +410,9 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_adjoint_c8(OperandDev m, co
     const int64_t n_groups = (n_cells + cpw - 1) / cpw;
     const GroupWalk walk = xcd_group_walk(n_groups, DXO_BLOCK / DXO_WAVE, wave);
     const int64_t stride = walk.stride;
-    auto cells_in = [&](int64_t g) -> int {
-        if (g >= walk.end) return 0;
-        const int64_t left = n_cells - g * cpw;
-        return left < cpw ? (int)left : cpw;
-    };
     const double w_l = wq[lane & 7];
     const int c_l = lane >> 3, q_l = lane & 7;
-    auto vertex_index = [&](int64_t g) -> int32_t { return c_l < cells_in(g) ? m.geom_dofmap[(g * cpw + c_l) * 8 + q_l] : -1; };
+    auto vertex_index = [&](int64_t g) -> int32_t { return c_l < group_cells(walk, n_cells, cpw, g) ? m.geom_dofmap[(g * cpw + c_l) * 8 + q_l] : -1; };
     auto vertex = [&](int32_t xn, double (&xv)[3]) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) xv[j] = xn >= 0 ? m.x[(int64_t)xn * 3 + j] : 0.0;
@@ -464,7 +424,7 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_adjoint_c8(OperandDev m, co
     xn = vertex_index(grp + stride);
     for (; grp < walk.end; grp += stride) {
         const int64_t c0 = grp * cpw;
-        const int ncell = cells_in(grp);
+        const int ncell = group_cells(walk, n_cells, cpw, grp);
         const bool has_point = c_l < ncell;
         dxo_f64x2 s2[3];
         {
@@ -491,15 +451,7 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_adjoint_c8(OperandDev m, co
             }
         const int64_t cell = c0 + c_l;
         c8_scatter<ND, DXO_C8_ADJ_UT>(L, T, [&](int a, const double (&o)[3]) {
-            if (!has_point) return;
-            if (fe) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) fe[((int64_t)a * m.num_cells_fe + cell) * 3 + i] = o[i];
-            } else {
-                const int64_t node = m.dofmap[cell * ND + a];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) unsafeAtomicAdd(out + node * 3 + i, o[i]);
-            }
+            if (has_point) store_entry<3>(m, fe, out, cell, a, ND, o);
         });
     }
 }
@@ -513,6 +465,8 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_adjoint_c8(OperandDev m, co
 constexpr int C8M_FTAB = 0;
 #endif
 
+// The walk is operand_adjoint_c8's, written out a second time: every shared form that was tried (a callable tail, a bool MF parameter, even
+// group_cells() for the lambda) moved this kernel's register allocation (210 -> 208 VGPRs at 27 nodes, 44 -> 41 SGPRs at 8).
 template <int ND>
 __global__ __launch_bounds__(DXO_BLOCK) void operand_adjoint_c8_mfma(OperandDev m, const double* __restrict__ wq, const double* __restrict__ S,
                                                                      int64_t n_cells, double* __restrict__ out, double* __restrict__ fe) {
@@ -605,10 +559,9 @@ __global__ __launch_bounds__(DXO_BLOCK, (MF && ND_CT != 27) ? DXO_TA_GM_WAVES : 
                                                               const double* __restrict__ v, int64_t n_cells,
                                                               double* __restrict__ out, double* __restrict__ fe) {
     constexpr int D = G == 2 ? 4 : 6;
-    constexpr int CV = D * D / 2;        // 16-byte pieces of a point's tangent
     // cells of 8 points and at most 32 nodes (launched so only for nq = 8): the scatter phase runs in registers, a DPP
     // reduce-scatter over the cell's 8 lanes (cell8_dpp.h) instead of parked tensors and 96 LDS reads per (cell, node) pair
-    constexpr bool RS = DXO_TA_RS && G == 3 && ND_CT > 0 && ND_CT <= C8_NODES && NG_CT == 8;
+    constexpr bool RS = G == 3 && ND_CT > 0 && ND_CT <= C8_NODES && NG_CT == 8;
     // MF on the other standard elements (scatter_mfma.h): P2 tetrahedra with the 4-point rule, P2 triangles with the 3-point rule
     constexpr bool GMF = MF && !RS && ND_CT > 0;
     constexpr int NQ_GM = G == 3 ? 4 : 3;
@@ -632,45 +585,29 @@ __global__ __launch_bounds__(DXO_BLOCK, (MF && ND_CT != 27) ? DXO_TA_GM_WAVES : 
     const int64_t n_groups = (n_cells + cpw - 1) / cpw;
     const GroupWalk walk = xcd_group_walk(n_groups, DXO_BLOCK / DXO_WAVE, wave);
     const int64_t stride = walk.stride;
-    auto cells_in = [&](int64_t g) -> int {
-        if (g >= walk.end) return 0;
-        const int64_t left = n_cells - g * cpw;
-        return left < cpw ? (int)left : cpw;
-    };
-    const bool piped = DXO_TA_PIPE && operand_can_pipe(m);
+    const bool piped = operand_can_pipe(m);
     OperandPipe<G, G> pf;
     int64_t grp = walk.first;
     if (piped) {
-        pipe_load_indices<G, G>(m, pf, grp * cpw, cells_in(grp), lane);
+        pipe_load_indices<G, G>(m, pf, grp * cpw, group_cells(walk, n_cells, cpw, grp), lane);
         pipe_load_values<G, G>(m, pf, v);
-        pipe_load_indices<G, G>(m, pf, (grp + stride) * cpw, cells_in(grp + stride), lane);
+        pipe_load_indices<G, G>(m, pf, (grp + stride) * cpw, group_cells(walk, n_cells, cpw, grp + stride), lane);
     }
     const int q_l = lane - (lane / m.nq) * m.nq;
     const double w_l = lane < cpw * m.nq ? wq[q_l] : 0.0;
     for (; grp < walk.end; grp += stride) {
         const int64_t c0 = grp * cpw;
-        const int ncell = cells_in(grp);
+        const int ncell = group_cells(walk, n_cells, cpw, grp);
         const bool has_point = lane < ncell * m.nq;
         // the tangent of this lane's point: requested now, used after the contraction
-#if DXO_TA_STAGE
         TangentRows<D> rows;
         VmPoint<D> vp;
         if constexpr (VM) vp.request(vs, c0 * m.nq + lane, has_point);
-#if DXO_TA_EARLY_C
-        if constexpr (!VM) rows.request(C_tang, c0 * m.nq, ncell * m.nq, lane);
-#endif
-#else
-        dxo_f64x2 Cq[CV];
-        const dxo_f64x2* Cp = reinterpret_cast<const dxo_f64x2*>(C_tang + (c0 * m.nq + lane) * (D * D));
-#if DXO_TA_EARLY_C
-#pragma unroll
-        for (int k = 0; k < CV; ++k) Cq[k] = has_point ? ta_load<DXO_TA_NT != 0>(Cp + k) : dxo_f64x2{0.0, 0.0};
-#endif
-#endif
+        else rows.request(C_tang, c0 * m.nq, ncell * m.nq, lane);
         if (piped) {
             pipe_commit<G, G>(m, pf, W, ncell, lane);
             pipe_load_values<G, G>(m, pf, v);
-            pipe_load_indices<G, G>(m, pf, (grp + 2 * stride) * cpw, cells_in(grp + 2 * stride), lane);
+            pipe_load_indices<G, G>(m, pf, (grp + 2 * stride) * cpw, group_cells(walk, n_cells, cpw, grp + 2 * stride), lane);
         } else {
             operand_gather<G, G>(m, W, v, nullptr, c0, ncell, lane);
         }
@@ -693,7 +630,6 @@ __global__ __launch_bounds__(DXO_BLOCK, (MF && ND_CT != 27) ? DXO_TA_GM_WAVES : 
             for (int j = 0; j < G; ++j) gh[i][j] = 0.0;
         }
         double t[D];
-#if DXO_TA_STAGE
         if (!active) {
 #pragma unroll
             for (int k = 0; k < D; ++k) e[k] = 0.0;
@@ -703,37 +639,14 @@ __global__ __launch_bounds__(DXO_BLOCK, (MF && ND_CT != 27) ? DXO_TA_GM_WAVES : 
             vp.state(vs, nrm, a, b);
             vm_tangent_times<D>(vs.c, nrm, a, b, e, t);
         } else {
-#if !DXO_TA_EARLY_C
-            rows.request(C_tang, c0 * m.nq, ncell * m.nq, lane);
-#endif
             rows.times(W, lane, e, t);     // compute_geo has fenced: the gather buffer is free, the parked tensors are not written yet
         }
         if (active) {
             scale = w_l * fabs(det);
             dual_tensor<G, G, DXO_OPERAND_EPS_MANDEL>(t, vh, gh);
         }
-#else
-        if (active) {
-            scale = w_l * fabs(det);
-#if !DXO_TA_EARLY_C
-#pragma unroll
-            for (int k = 0; k < CV; ++k) Cq[k] = ta_load<DXO_TA_NT != 0>(Cp + k);
-#endif
-#pragma unroll
-            for (int r = 0; r < D; ++r) {
-                double acc = 0.0;
-#pragma unroll
-                for (int cc = 0; cc < D; cc += 2) {
-                    const dxo_f64x2 c2 = Cq[(r * D + cc) / 2];
-                    acc += c2.x * e[cc];
-                    acc += c2.y * e[cc + 1];
-                }
-                t[r] = acc;
-            }
-            dual_tensor<G, G, DXO_OPERAND_EPS_MANDEL>(t, vh, gh);
-        }
-#endif
         if constexpr (RS) {
+            // the pull-back written out: through pull_back() the register allocation of the C_tang-rows instantiations changes
             double T[3][3];
 #pragma unroll
             for (int i = 0; i < 3; ++i)
@@ -753,27 +666,11 @@ __global__ __launch_bounds__(DXO_BLOCK, (MF && ND_CT != 27) ? DXO_TA_GM_WAVES : 
             }
             const int64_t cell = c0 + (lane >> 3);
             c8_scatter<ND_CT, VM ? DXO_TA_VM_UT : 1>(L8, T, [&](int a, const double (&o)[3]) {
-                if (!active) return;
-                if (fe) {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) fe[((int64_t)a * m.num_cells_fe + cell) * 3 + i] = o[i];
-                } else {
-                    const int64_t node = m.dofmap[cell * ND_CT + a];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) unsafeAtomicAdd(out + node * 3 + i, o[i]);
-                }
+                if (active) store_entry<3>(m, fe, out, cell, a, ND_CT, o);
             });
         } else if constexpr (GMF) {
             double T[G][G];
-#pragma unroll
-            for (int i = 0; i < G; ++i)
-#pragma unroll
-                for (int k = 0; k < G; ++k) {
-                    double tt = 0.0;
-#pragma unroll
-                    for (int j = 0; j < G; ++j) tt += gh[i][j] * K[k][j];
-                    T[i][k] = scale * tt;          // scale = 0 and gh = 0 for lanes without a point
-                }
+            pull_back<G, G>(gh, K, scale, T);          // scale = 0 and gh = 0 for lanes without a point
             gm_scatter<G, ND_CT, NQ_GM>(m, tabP, W, lane, T, c0, ncell, fe, out);      // compute_geo / rows.times have fenced: the wave's region is free
         } else {
             adjoint_scatter<G, G>(m, tab, Tm, active, lane, vh, gh, K, scale, c0, ncell, nullptr, out, fe);
@@ -804,7 +701,7 @@ __global__ __launch_bounds__(DXO_BLOCK, 2) void tangent_diag(OperandDev m, const
     constexpr int NS1 = G * (G + 1) / 2;            // unique entries of one symmetrised matrix
     constexpr int PT = (G * NS1) | 1;               // odd per-point stride (bank spread across cells)
     constexpr double r2 = 0.70710678118654752440;
-    constexpr bool RS = DXO_TA_RS && G == 3 && (ND_CT == 27 || ND_CT == 8);
+    constexpr bool RS = G == 3 && (ND_CT == 27 || ND_CT == 8);
     // MF on P2 tetrahedra (4-point rule) / P2 triangles (3-point rule): scatter_mfma.h, rows (q, pair) in passes of three pairs
     constexpr bool GMF = MF && !RS && ND_CT > 0;
     constexpr int NQ_GM = G == 3 ? 4 : 3;
@@ -825,7 +722,7 @@ __global__ __launch_bounds__(DXO_BLOCK, 2) void tangent_diag(OperandDev m, const
     const int cpw = m.cells_per_wave, nd = m.ndofs, nq = m.nq, ng = m.ngeom;
     const int sx = op_odd(ng * G);
     double* X = W;
-    double* Pm = X + ((cpw * sx + 1) & ~1);          // [point][PT]; even offset: the slice also stages the tangent rows (16-byte units)
+    double* Pm = X + op_even(cpw * sx);             // [point][PT]; even offset: the slice also stages the tangent rows (16-byte units)
     const int64_t n_groups = (n_cells + cpw - 1) / cpw;
     const GroupWalk walk = xcd_group_walk(n_groups, DXO_BLOCK / DXO_WAVE, wave);
     const int c_l = lane / nq, q_l = lane - c_l * nq;
@@ -836,7 +733,6 @@ __global__ __launch_bounds__(DXO_BLOCK, 2) void tangent_diag(OperandDev m, const
         const bool has_point = c_l < ncell;
         dxo_f64x2 Cq[CV];
         double vn[D], va = 0.0, vb = 0.0;       // VM: the point's tangent state
-#if DXO_TA_STAGE
         TangentRows<D> rows;
         if constexpr (VM) {
             VmPoint<D> vp;
@@ -846,38 +742,14 @@ __global__ __launch_bounds__(DXO_BLOCK, 2) void tangent_diag(OperandDev m, const
             rows.request(C_tang, c0 * nq, ncell * nq, lane);
             rows.deliver(Pm, lane, Cq);          // the parked matrices of the last group have been consumed (fence at the loop's end)
         }
-#else
-        {
-            const dxo_f64x2* Cp = reinterpret_cast<const dxo_f64x2*>(C_tang + (c0 * nq + lane) * (D * D));
-#pragma unroll
-            for (int k = 0; k < CV; ++k) Cq[k] = has_point ? ta_load<DXO_TA_NT != 0>(Cp + k) : dxo_f64x2{0.0, 0.0};
-        }
-#endif
-        for (int idx = lane; idx < ncell * ng; idx += DXO_WAVE) {
-            const int c = idx / ng, v = idx - c * ng;
-            const int64_t node = m.geom_dofmap[(c0 + c) * ng + v];
-#pragma unroll
-            for (int j = 0; j < G; ++j) X[c * sx + v * G + j] = m.x[node * G + j];
-        }
+        gather_vertices<G>(m, X, nullptr, c0, ncell, lane);
         op_fence();
         double NSr[G * NS1];             // RS: this point's matrices stay in registers
 #pragma unroll
         for (int k = 0; k < G * NS1; ++k) NSr[k] = 0.0;
         if (has_point) {
-            const double* dpsi = tab + L.o_dpsi + q_l * L.sdpsi;
-            const double* Xc = X + c_l * sx;
-            double J[G][G], K[G][G];
-#pragma unroll
-            for (int j = 0; j < G; ++j)
-#pragma unroll
-                for (int k = 0; k < G; ++k) J[j][k] = 0.0;
-            for (int v = 0; v < ng; ++v)
-#pragma unroll
-                for (int j = 0; j < G; ++j)
-#pragma unroll
-                    for (int k = 0; k < G; ++k) J[j][k] += Xc[v * G + j] * dpsi[v * G + k];
-            const double det = invert<G>(J, K);
-            const double scale = w_l * fabs(det);
+            double K[G][G];
+            const double scale = w_l * fabs(point_jacobian<G>(tab + L.o_dpsi + q_l * L.sdpsi, X + c_l * sx, ng, K));
             auto Cat = [&](int r, int cc) -> double {
                 if constexpr (VM) return c_elas_ij(vs.c, r, cc) - va * (vn[r] * vn[cc]) - vb * dev_ij(r, cc);
                 const dxo_f64x2 c2 = Cq[(r * D + cc) / 2];
@@ -969,35 +841,18 @@ __global__ __launch_bounds__(DXO_BLOCK, 2) void tangent_diag(OperandDev m, const
                     const double* r = L8.row(j, t);
                     const dxo_f64x2 a = *reinterpret_cast<const dxo_f64x2*>(r);
                     const double d[3] = {a.x, a.y, r[2]};
-                    int slot = 0;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-#pragma unroll
-                        for (int kk = k; kk < 3; ++kk) pp[j][slot++] = d[k] * d[kk];
+                    sym_products<3>(d, pp[j]);
                 }
                 double o[3];
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
                     double pj[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        double tt = 0.0;
-#pragma unroll
-                        for (int s2 = 0; s2 < NS1; ++s2) tt += pp[j][s2] * NSr[i * NS1 + s2];
-                        pj[j] = tt;
-                    }
+                    for (int j = 0; j < 8; ++j) pj[j] = sym_dot<NS1>(pp[j], NSr + i * NS1);
                     o[i] = c8_reduce_scatter(pj);
                 }
                 const int a = L8.node0 + t;
-                if (!has_point || a >= ND_CT) continue;
-                if (fe) {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) fe[((int64_t)a * m.num_cells_fe + cell) * 3 + i] = o[i];
-                } else {
-                    const int64_t node = m.dofmap[cell * ND_CT + a];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) unsafeAtomicAdd(out + node * 3 + i, o[i]);
-                }
+                if (has_point && a < ND_CT) store_entry<3>(m, fe, out, cell, a, ND_CT, o);
             }
             op_fence();      // the staging slice (Pm) is rewritten by the next group's tangent rows
             continue;
@@ -1014,59 +869,57 @@ __global__ __launch_bounds__(DXO_BLOCK, 2) void tangent_diag(OperandDev m, const
                 double d[G], pp[NS1];
 #pragma unroll
                 for (int k = 0; k < G; ++k) d[k] = dp[k];
-                int slot = 0;
+                int slot = 0;      // the products written out: through sym_products() tangent_diag<3, 0, false, false> takes two registers more
 #pragma unroll
                 for (int k = 0; k < G; ++k)
 #pragma unroll
                     for (int kk = k; kk < G; ++kk) pp[slot++] = d[k] * d[kk];
 #pragma unroll
-                for (int i = 0; i < G; ++i) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int s2 = 0; s2 < NS1; ++s2) t += pp[s2] * P[i * NS1 + s2];
-                    acc[i] += t;
-                }
+                for (int i = 0; i < G; ++i) acc[i] += sym_dot<NS1>(pp, P + i * NS1);
             }
-            const int64_t cell = c0 + c;
-            if (fe) {
-#pragma unroll
-                for (int i = 0; i < G; ++i) fe[((int64_t)a * m.num_cells_fe + cell) * G + i] = acc[i];
-            } else {
-                const int64_t node = m.dofmap[cell * nd + a];
-#pragma unroll
-                for (int i = 0; i < G; ++i) unsafeAtomicAdd(out + node * G + i, acc[i]);
-            }
+            store_entry<G>(m, fe, out, c0 + c, a, nd, acc);
         }
         op_fence();
     }
 }
 
+// ---- host side of the kernels' LDS layouts: doubles of a wave's region
+int gather_doubles(const OperandDev& v, int G, int BS) { return v.cells_per_wave * (op_odd(v.ndofs * BS) + op_odd(v.ngeom * G)); }   // operand_gather: dofs, vertices
+int vertex_doubles(const OperandDev& v, int G) { return op_even(v.cells_per_wave * op_odd(v.ngeom * G)); }     // gather_vertices; what follows is 16-byte aligned
+int parked_doubles(int G, int BS) { return DXO_WAVE * ((BS * (G + 1)) | 1); }                                  // adjoint_scatter's tensors (odd per-point stride)
+int tangent_stage(int G) { return G == 2 ? TangentRows<4>::LDS_DOUBLES : TangentRows<6>::LDS_DOUBLES; }        // TR_PC * (D * D + 2)
+// at least the staging space of the rows that pass through the region (TangentRows, BlockRows), and even: every wave's region starts on
+// a 16-byte boundary
+int wave_region(int wd, int stage) { return op_even(wd < stage ? stage : wd); }
+
 int diag_lds_wave(const dxo_mesh* m) {
-    const OperandDev& v = m->dev;
     const int G = m->gdim;
-    const int D = G == 2 ? 4 : 6;
-    int park = DXO_WAVE * ((G * (G * (G + 1) / 2)) | 1);
-    if (park < TR_PC * (D * D + 2)) park = TR_PC * (D * D + 2);      // the parked-matrix slice doubles as the staging space of the tangent rows
-    int wd = ((v.cells_per_wave * op_odd(v.ngeom * G) + 1) & ~1) + park;
-    return (wd + 1) & ~1;
+    const int park = DXO_WAVE * ((G * (G * (G + 1) / 2)) | 1);
+    // the parked-matrix slice doubles as the staging space of the tangent rows
+    return op_even(vertex_doubles(m->dev, G) + wave_region(park, tangent_stage(G)));
 }
 
-// tangent_apply with the register scatter parks nothing: the gather buffer, or the staging space of the tangent rows
-int apply_rs_lds_wave(const dxo_mesh* m) {
-    const OperandDev& v = m->dev;
-    const int G = m->gdim, D = G == 2 ? 4 : 6;
-    int wd = v.cells_per_wave * (op_odd(v.ndofs * G) + op_odd(v.ngeom * G));
-    if (wd < TR_PC * (D * D + 2)) wd = TR_PC * (D * D + 2);
-    return (wd + 1) & ~1;
-}
-
+// tangent_apply stages the tangent rows through the whole region (TangentRows)
 int adjoint_lds_wave(const dxo_mesh* m) {
-    const OperandDev& v = m->dev;
     const int G = m->gdim;
-    int wd = v.cells_per_wave * (op_odd(v.ndofs * G) + op_odd(v.ngeom * G)) + DXO_WAVE * (DXO_ADJ_PAD ? ((G * (G + 1)) | 1) : G * (G + 1));
-    const int D = G == 2 ? 4 : 6;
-    if (wd < TR_PC * (D * D + 2)) wd = TR_PC * (D * D + 2);          // tangent_apply stages the tangent rows through the whole region (TangentRows)
-    return (wd + 1) & ~1;
+    return wave_region(gather_doubles(m->dev, G, G) + parked_doubles(G, G), tangent_stage(G));
+}
+
+// ---- the standard elements the compile-time forms of the kernels are launched for: the field's element, the geometry's and the rule
+bool is_hex8(const dxo_mesh* m, int nd) { return m->gdim == 3 && m->dev.ndofs == nd && m->dev.ngeom == 8 && m->dev.nq == 8; }
+bool is_q2_hex(const dxo_mesh* m) { return is_hex8(m, 27); }      // Q2 hexahedra, 2x2x2 rule
+bool is_q1_hex(const dxo_mesh* m) { return is_hex8(m, 8); }       // Q1 hexahedra, 2x2x2 rule
+bool is_p2_tet(const dxo_mesh* m) { return m->gdim == 3 && m->dev.ndofs == 10 && m->dev.ngeom == 4 && m->dev.nq == 4; }     // 4-point rule
+bool is_p2_tri(const dxo_mesh* m) { return m->gdim == 2 && m->dev.ndofs == 6 && m->dev.ngeom == 3 && m->dev.nq == 3; }      // 3-point rule
+
+// grid of the persistent element kernels: one workgroup (four waves) per four wave groups, at most blocks_per_cu per compute unit, whole
+// rounds over the 8 XCDs (xcd_group_walk)
+int64_t wave_groups(const dxo_mesh* m, int64_t n_cells) { return (n_cells + m->dev.cells_per_wave - 1) / m->dev.cells_per_wave; }
+int consumer_grid(const dxo_ctx* ctx, int64_t n_groups, int blocks_per_cu) {
+    int64_t blocks = (n_groups + 3) / 4;
+    const int64_t cap = (int64_t)ctx->compute_units * blocks_per_cu;
+    if (blocks > cap) blocks = cap;
+    return (int)((blocks + 7) / 8 * 8);
 }
 
 // transposed dofmap on the device, built once per mesh from the host copy of the dofmap
@@ -1121,22 +974,20 @@ void launch_node_sum(const dxo_ctx* ctx, const dxo_mesh* m, int bs, double* out,
     const int64_t cap = (int64_t)ctx->compute_units * DXO_NS_BLOCKS_PER_CU;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    if (bs == 1) hipLaunchKernelGGL(node_sum<1>, dim3((int)blocks), dim3(DXO_BLOCK), 0, s, m->num_field_nodes, m->d_node_ptr, m->d_node_ent, m->d_fe, out, (int)(ctx->consumer_overwrite != 0));
-    else if (bs == 2) hipLaunchKernelGGL(node_sum<2>, dim3((int)blocks), dim3(DXO_BLOCK), 0, s, m->num_field_nodes, m->d_node_ptr, m->d_node_ent, m->d_fe, out, (int)(ctx->consumer_overwrite != 0));
-    else hipLaunchKernelGGL(node_sum<3>, dim3((int)blocks), dim3(DXO_BLOCK), 0, s, m->num_field_nodes, m->d_node_ptr, m->d_node_ent, m->d_fe, out, (int)(ctx->consumer_overwrite != 0));
+#define DXO_NS_LAUNCH(BS) hipLaunchKernelGGL(node_sum<BS>, dim3((int)blocks), dim3(DXO_BLOCK), 0, s, m->num_field_nodes, m->d_node_ptr, m->d_node_ent, m->d_fe, out, (int)(ctx->consumer_overwrite != 0))
+    if (bs == 1) DXO_NS_LAUNCH(1);
+    else if (bs == 2) DXO_NS_LAUNCH(2);
+    else DXO_NS_LAUNCH(3);
+#undef DXO_NS_LAUNCH
 }
 
 template <int G, int BS, int KIND>
 void launch_adjoint(const dxo_ctx* ctx, const dxo_mesh* m, const double* S, const int32_t* cells, int64_t n_cells,
                     double* out, double* fe, hipStream_t s) {
     const int wd = adjoint_lds_wave(m);
-    const int64_t n_groups = (n_cells + m->dev.cells_per_wave - 1) / m->dev.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;
+    const int blocks = consumer_grid(ctx, wave_groups(m, n_cells), 8);
     const size_t shm = (size_t)(m->dev.table_doubles + 4 * wd) * sizeof(double);
-    hipLaunchKernelGGL((operand_adjoint<G, BS, KIND>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, m->dev, m->d_wq, wd, S,
+    hipLaunchKernelGGL((operand_adjoint<G, BS, KIND>), dim3(blocks), dim3(DXO_BLOCK), shm, s, m->dev, m->d_wq, wd, S,
                        cells, n_cells, out, fe);
 }
 
@@ -1206,8 +1057,9 @@ extern "C" int dxo_operand_adjoint(dxo_ctx* ctx, dxo_mesh* mesh, int kind, int b
         return dxo_fail(ctx, DXO_E_SIZE, "dxo_operand_adjoint: element too large for the LDS budget");
     hipStream_t s = dxo_launch_stream(ctx);
     DXO_HIP(ctx, hipSetDevice(ctx->device));
-    const bool c8 = kind == DXO_OPERAND_EPS_MANDEL && ctx->adjoint_cell && !cells && n_cells == mesh->num_cells && mesh->gdim == 3 && bs == 3 &&
-                    mesh->dev.nq == 8 && mesh->dev.ngeom == 8 && (mesh->dev.ndofs == 27 || mesh->dev.ndofs == 8) && (((uintptr_t)S & 15u) == 0);
+    // hexahedra with the 2x2x2 rule, whole mesh: the forms whose contraction runs across the cell's lanes
+    const bool c8 = kind == DXO_OPERAND_EPS_MANDEL && ctx->adjoint_cell && !cells && n_cells == mesh->num_cells && bs == 3 &&
+                    (is_q2_hex(mesh) || is_q1_hex(mesh)) && (((uintptr_t)S & 15u) == 0);
 #ifdef DXO_EXPERIMENTS
     if (c8 && use_patches(ctx, mesh, bs, cells, n_cells)) {
         // hexahedra with the 2x2x2 rule, patch form: the entries meet in LDS, only patch-boundary partials travel (adjoint_patch.h)
@@ -1227,20 +1079,17 @@ extern "C" int dxo_operand_adjoint(dxo_ctx* ctx, dxo_mesh* mesh, int kind, int b
     if (rc != DXO_OK) return rc;
     rc = clear_for_atomics(ctx, mesh, bs, out, fe, s);
     if (rc != DXO_OK) return rc;
-    if (kind == DXO_OPERAND_EPS_MANDEL && ctx->adjoint_cell && !cells && n_cells == mesh->num_cells && mesh->gdim == 3 && bs == 3 &&
-        mesh->dev.nq == 8 && mesh->dev.ngeom == 8 && (mesh->dev.ndofs == 27 || mesh->dev.ndofs == 8) && (((uintptr_t)S & 15u) == 0)) {
-        // hexahedra with the 2x2x2 rule: contraction across the cell's lanes, nothing staged in LDS (operand_adjoint_c8)
-        const int64_t n_groups = (n_cells + 7) / 8;
-        int64_t blocks = (n_groups + 3) / 4;
-        const int64_t cap = (int64_t)ctx->compute_units * DXO_C8_ADJ_BLOCKS_PER_CU;
-        if (blocks > cap) blocks = cap;
-        blocks = (blocks + 7) / 8 * 8;
+    if (c8) {
+        // contraction across the cell's lanes, nothing staged in LDS (operand_adjoint_c8)
+        const int blocks = consumer_grid(ctx, (n_cells + 7) / 8, DXO_C8_ADJ_BLOCKS_PER_CU);
         const size_t shm = (size_t)(C8_LDS + (ctx->adjoint_mfma ? (DXO_BLOCK / DXO_WAVE) * C8M_WAVE : 0)) * sizeof(double);
+#define DXO_C8_LAUNCH(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, S, n_cells, out, fe)
         if (ctx->adjoint_mfma) {      // the contraction on the f64 matrix pipe
-            if (mesh->dev.ndofs == 27) hipLaunchKernelGGL((operand_adjoint_c8_mfma<27>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, S, n_cells, out, fe);
-            else                       hipLaunchKernelGGL((operand_adjoint_c8_mfma<8>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, S, n_cells, out, fe);
-        } else if (mesh->dev.ndofs == 27) hipLaunchKernelGGL((operand_adjoint_c8<27>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, S, n_cells, out, fe);
-        else                       hipLaunchKernelGGL((operand_adjoint_c8<8>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, S, n_cells, out, fe);
+            if (mesh->dev.ndofs == 27) DXO_C8_LAUNCH(operand_adjoint_c8_mfma<27>);
+            else                       DXO_C8_LAUNCH(operand_adjoint_c8_mfma<8>);
+        } else if (mesh->dev.ndofs == 27) DXO_C8_LAUNCH(operand_adjoint_c8<27>);
+        else                              DXO_C8_LAUNCH(operand_adjoint_c8<8>);
+#undef DXO_C8_LAUNCH
         if (fe) launch_node_sum(ctx, mesh, bs, out, s);
         return dxo_device_end(ctx, s);
     }
@@ -1258,21 +1107,20 @@ extern "C" int dxo_operand_adjoint(dxo_ctx* ctx, dxo_mesh* mesh, int kind, int b
 namespace {
 
 // shared body of dxo_tangent_diagonal / dxo_tangent_diagonal_vm (vs == nullptr: rows of C_tang)
-int tangent_diagonal_impl(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, const VmStateSrc* vs, double* out, const char* who) {
+int tangent_diagonal_impl(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, const VmStateSrc* vs, double* out) {
     if (!mesh) return dxo_fail(ctx, DXO_E_NULL, "dxo_tangent_diagonal: mesh is NULL");
     if (!mesh->d_wq) return dxo_fail(ctx, DXO_E_OPTION, "dxo_tangent_diagonal: quadrature weights not set (dxo_mesh_set_weights)");
     if (mesh->num_cells == 0) return DXO_OK;
     if ((!vs && !C_tang) || (vs && (!vs->sigma || !vs->dp)) || !out) return dxo_fail(ctx, DXO_E_NULL, "dxo_tangent_diagonal: NULL array");
     if (((uintptr_t)(vs ? (const void*)vs->sigma : (const void*)C_tang) & 15u) != 0)
         return dxo_fail(ctx, DXO_E_ALIGN, "dxo_tangent_diagonal: C_tang / sigma must be 16-byte aligned");
-    (void)who;
-    const bool rs = DXO_TA_RS && mesh->gdim == 3 && mesh->dev.ndofs == 27 && mesh->dev.ngeom == 8 && mesh->dev.nq == 8;   // Q2 hexahedra, 2x2x2 rule
+    const bool rs = is_q2_hex(mesh);
     // MFMA form: the wave's slice is the vertex buffer + the staged matrices of c8m_contract (state-based), or the staging space of the
     // tangent rows, which also holds them (C_tang rows: 66 KB per workgroup with the product tables — above the 64 KB a launch gets without asking)
     // scatter_mfma.h: P2 tetrahedra (4-point rule) and P2 triangles (3-point rule), state-based form
-    const bool gm_tet = vs && ctx->adjoint_mfma && mesh->gdim == 3 && mesh->dev.ndofs == 10 && mesh->dev.ngeom == 4 && mesh->dev.nq == 4;
-    const bool gm_tri = vs && ctx->adjoint_mfma && mesh->gdim == 2 && mesh->dev.ndofs == 6 && mesh->dev.ngeom == 3 && mesh->dev.nq == 3;
-    const bool q1 = vs && ctx->adjoint_mfma && DXO_TA_RS && mesh->gdim == 3 && mesh->dev.ndofs == 8 && mesh->dev.ngeom == 8 && mesh->dev.nq == 8;   // Q1 hexahedra, state-based
+    const bool gm_tet = vs && ctx->adjoint_mfma && is_p2_tet(mesh);
+    const bool gm_tri = vs && ctx->adjoint_mfma && is_p2_tri(mesh);
+    const bool q1 = vs && ctx->adjoint_mfma && is_q1_hex(mesh);      // state-based form only
     bool mf = (rs || q1) && ctx->adjoint_mfma;
     if (mf && !vs) {
         // the C_tang-rows form needs the raised launch limit of its one instantiation; a runtime that refuses it gets the DPP form
@@ -1287,13 +1135,10 @@ int tangent_diagonal_impl(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, co
         }
         if (refused.load() & bit) mf = false;
     }
-    int wd = (mf && vs) ? ((mesh->dev.cells_per_wave * op_odd(mesh->dev.ngeom * 3) + 1) & ~1) + C8M_WAVE : diag_lds_wave(mesh);
+    int wd = (mf && vs) ? vertex_doubles(mesh->dev, 3) + C8M_WAVE : diag_lds_wave(mesh);
     const int gm_stage = gm_tet ? GmShape<3, 10, 4, 3>::STAGE : gm_tri ? GmShape<2, 6, 3, 3>::STAGE : 0;
     const int gm_tab = gm_tet ? 2 * GmShape<3, 10, 4, 3>::ATAB : gm_tri ? GmShape<2, 6, 3, 3>::ATAB : 0;
-    if (gm_stage) {      // the staging slice behind the vertex buffer
-        const int need = ((mesh->dev.cells_per_wave * op_odd(mesh->dev.ngeom * mesh->gdim) + 1) & ~1) + gm_stage;
-        if (wd < need) wd = (need + 1) & ~1;
-    }
+    if (gm_stage) wd = wave_region(wd, vertex_doubles(mesh->dev, mesh->gdim) + gm_stage);      // the staging slice behind the vertex buffer
     const size_t shm = (size_t)(mesh->dev.table_doubles + 4 * wd + ((rs || q1) ? (mf ? 2 * 12 * DXO_WAVE : C8_LDS) : gm_tab)) * sizeof(double);
     if (shm > (mf && !vs ? 80 : 64) * 1024) return dxo_fail(ctx, DXO_E_SIZE, "dxo_tangent_diagonal: element too large for the LDS budget");
     hipStream_t s = dxo_launch_stream(ctx);
@@ -1303,14 +1148,10 @@ int tangent_diagonal_impl(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, co
     if (rc != DXO_OK) return rc;
     rc = clear_for_atomics(ctx, mesh, mesh->gdim, out, fe, s);
     if (rc != DXO_OK) return rc;
-    const int64_t n_groups = (mesh->num_cells + mesh->dev.cells_per_wave - 1) / mesh->dev.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * (vs ? DXO_TD_VM_BLOCKS_PER_CU : DXO_TD_BLOCKS_PER_CU);
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;
+    const int blocks = consumer_grid(ctx, wave_groups(mesh, mesh->num_cells), vs ? DXO_TD_VM_BLOCKS_PER_CU : DXO_TD_BLOCKS_PER_CU);
     const VmStateSrc none{};
     const VmStateSrc& src = vs ? *vs : none;
-#define DXO_DIAG_LAUNCH(...) hipLaunchKernelGGL((tangent_diag<__VA_ARGS__>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C_tang, src, mesh->num_cells, out, fe)
+#define DXO_DIAG_LAUNCH(...) hipLaunchKernelGGL((tangent_diag<__VA_ARGS__>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C_tang, src, mesh->num_cells, out, fe)
     if (gm_tri)          { DXO_DIAG_LAUNCH(2, 6, true, true); }
     else if (gm_tet)     { DXO_DIAG_LAUNCH(3, 10, true, true); }
     else if (mesh->gdim == 2) { if (vs) DXO_DIAG_LAUNCH(2, 0, true); else DXO_DIAG_LAUNCH(2, 0, false); }
@@ -1331,18 +1172,18 @@ int tangent_apply_impl(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, const
     if ((!vs && !C_tang) || (vs && (!vs->sigma || !vs->dp)) || !v || !out) return dxo_fail(ctx, DXO_E_NULL, "dxo_tangent_apply: NULL array");
     if (((uintptr_t)(vs ? (const void*)vs->sigma : (const void*)C_tang) & 15u) != 0)
         return dxo_fail(ctx, DXO_E_ALIGN, "dxo_tangent_apply: C_tang / sigma must be 16-byte aligned");
-    const bool rs = DXO_TA_RS && mesh->gdim == 3 && mesh->dev.ndofs == 27 && mesh->dev.ngeom == 8 && mesh->dev.nq == 8;   // Q2 hexahedra, 2x2x2 rule
+    const bool rs = is_q2_hex(mesh);
     const bool c8 = rs && DXO_TA_C8_FORWARD && !vs;
-    // Q1 hexahedra with the 2x2x2 rule, state-based form: the same kernel with 8 nodes (matrix-pipe scatter only)
-    const bool q1 = vs && ctx->adjoint_mfma && DXO_TA_RS && mesh->gdim == 3 && mesh->dev.ndofs == 8 && mesh->dev.ngeom == 8 && mesh->dev.nq == 8;
-    // the state form stages nothing: its wave region is the gather buffer (and the parked tensors where the scatter uses them)
-    int wd = (rs || q1) ? (vs ? ((mesh->dev.cells_per_wave * (op_odd(mesh->dev.ndofs * 3) + op_odd(mesh->dev.ngeom * 3)) + 1) & ~1) : apply_rs_lds_wave(mesh))
-                        : adjoint_lds_wave(mesh);
+    // Q1 hexahedra, state-based form: the same kernel with 8 nodes (matrix-pipe scatter only)
+    const bool q1 = vs && ctx->adjoint_mfma && is_q1_hex(mesh);
+    // the register scatter parks nothing: the wave's region is the gather buffer, or the staging space of the tangent rows (the state form
+    // stages nothing)
+    int wd = (rs || q1) ? wave_region(gather_doubles(mesh->dev, 3, 3), vs ? 0 : tangent_stage(3)) : adjoint_lds_wave(mesh);
     if (q1 && wd < C8M_WAVE) wd = C8M_WAVE;      // c8m_contract stages T in the wave's region
     // scatter_mfma.h: P2 tetrahedra (4-point rule) and P2 triangles (3-point rule), state-based form (with the tangent rows' registers on top the
     // compile-time element costs more than the scatter gains: 0.511 against 0.503 ms on triangles, 1.135 / 1.106 on tetrahedra)
-    const bool gm_tet = vs && ctx->adjoint_mfma && mesh->gdim == 3 && mesh->dev.ndofs == 10 && mesh->dev.ngeom == 4 && mesh->dev.nq == 4;
-    const bool gm_tri = vs && ctx->adjoint_mfma && mesh->gdim == 2 && mesh->dev.ndofs == 6 && mesh->dev.ngeom == 3 && mesh->dev.nq == 3;
+    const bool gm_tet = vs && ctx->adjoint_mfma && is_p2_tet(mesh);
+    const bool gm_tri = vs && ctx->adjoint_mfma && is_p2_tri(mesh);
     const int gm_tab = gm_tet ? GmShape<3, 10, 4>::ATAB : gm_tri ? GmShape<2, 6, 3>::ATAB : 0;
     const size_t shm = c8 ? (size_t)(C8_LDS + 4 * TangentRows<6>::LDS_DOUBLES) * sizeof(double)
                           : (size_t)(mesh->dev.table_doubles + 4 * wd + ((rs || q1) ? (ctx->adjoint_mfma ? 12 * DXO_WAVE + C8M_FTAB : C8_LDS) : gm_tab)) * sizeof(double);
@@ -1354,19 +1195,15 @@ int tangent_apply_impl(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, const
     if (rc != DXO_OK) return rc;
     rc = clear_for_atomics(ctx, mesh, mesh->gdim, out, fe, s);
     if (rc != DXO_OK) return rc;
-    const int64_t n_groups = (mesh->num_cells + mesh->dev.cells_per_wave - 1) / mesh->dev.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * (vs ? DXO_TA_VM_BLOCKS_PER_CU : DXO_TA_BLOCKS_PER_CU);
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;
+    const int blocks = consumer_grid(ctx, wave_groups(mesh, mesh->num_cells), vs ? DXO_TA_VM_BLOCKS_PER_CU : DXO_TA_BLOCKS_PER_CU);
     const VmStateSrc none{};
     const VmStateSrc& src = vs ? *vs : none;
-#define DXO_APPLY_LAUNCH(...) hipLaunchKernelGGL((tangent_apply<__VA_ARGS__>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C_tang, src, v, mesh->num_cells, out, fe)
+#define DXO_APPLY_LAUNCH(...) hipLaunchKernelGGL((tangent_apply<__VA_ARGS__>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C_tang, src, v, mesh->num_cells, out, fe)
 #ifdef DXO_EXPERIMENTS
     if (!vs && DXO_TANGENT_CELL && fe && ctx->adjoint_cell && launch_tangent_cell(ctx, mesh, C_tang, v, fe, s)) {
         // lane = cell form for P2 triangles — correct, but 0.61 against 0.55-0.58 ms per 10^7 points for the wave-group kernel
     } else if (c8)
-        hipLaunchKernelGGL((tangent_apply_c8<27>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, C_tang, v, mesh->num_cells, out, fe);
+        hipLaunchKernelGGL((tangent_apply_c8<27>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, C_tang, v, mesh->num_cells, out, fe);
     else
 #endif
     if (gm_tri)               { DXO_APPLY_LAUNCH(2, 6, 3, true, true); }
@@ -1423,7 +1260,7 @@ extern "C" int dxo_von_mises_residual(dxo_ctx* ctx, const dxo_vm_params* prm, dx
 extern "C" int dxo_tangent_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, double* out) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
-    return tangent_diagonal_impl(ctx, mesh, C_tang, nullptr, out, "dxo_tangent_diagonal");
+    return tangent_diagonal_impl(ctx, mesh, C_tang, nullptr, out);
 }
 
 extern "C" int dxo_tangent_apply(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, const double* v, double* out) {
@@ -1447,7 +1284,7 @@ extern "C" int dxo_tangent_diagonal_vm(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_v
     DXO_LOCK(ctx);
     VmStateSrc vs;
     if (!vm_state_src(ctx, mesh, prm, sigma, dp, vs)) return DXO_E_NULL;
-    return tangent_diagonal_impl(ctx, mesh, nullptr, &vs, out, "dxo_tangent_diagonal_vm");
+    return tangent_diagonal_impl(ctx, mesh, nullptr, &vs, out);
 }
 
 // dxo_bilinear_apply / dxo_bilinear_diagonal: the same two operators for a general pair of linear operand kinds (bilinear.h)

@@ -137,30 +137,25 @@ __global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_apply(Operan
     const int64_t n_groups = (n_cells + cpw - 1) / cpw;
     const GroupWalk walk = xcd_group_walk(n_groups, DXO_BLOCK / DXO_WAVE, wave);
     const int64_t stride = walk.stride;
-    auto cells_in = [&](int64_t g) -> int {
-        if (g >= walk.end) return 0;
-        const int64_t left = n_cells - g * cpw;
-        return left < cpw ? (int)left : cpw;
-    };
     const bool piped = operand_can_pipe(m);
     OperandPipe<G, BS> pf;
     int64_t grp = walk.first;
     if (piped) {
-        pipe_load_indices<G, BS>(m, pf, grp * cpw, cells_in(grp), lane);
+        pipe_load_indices<G, BS>(m, pf, grp * cpw, group_cells(walk, n_cells, cpw, grp), lane);
         pipe_load_values<G, BS>(m, pf, v);
-        pipe_load_indices<G, BS>(m, pf, (grp + stride) * cpw, cells_in(grp + stride), lane);
+        pipe_load_indices<G, BS>(m, pf, (grp + stride) * cpw, group_cells(walk, n_cells, cpw, grp + stride), lane);
     }
     const int q_l = lane - (lane / m.nq) * m.nq;
     const double w_l = lane < cpw * m.nq ? wq[q_l] : 0.0;
     for (; grp < walk.end; grp += stride) {
         const int64_t c0 = grp * cpw;
-        const int ncell = cells_in(grp);
+        const int ncell = group_cells(walk, n_cells, cpw, grp);
         BlockRows<DT, DR> rows;
         rows.begin(C, c0 * m.nq, ncell * m.nq, lane);
         if (piped) {
             pipe_commit<G, BS>(m, pf, W, ncell, lane);
             pipe_load_values<G, BS>(m, pf, v);
-            pipe_load_indices<G, BS>(m, pf, (grp + 2 * stride) * cpw, cells_in(grp + 2 * stride), lane);
+            pipe_load_indices<G, BS>(m, pf, (grp + 2 * stride) * cpw, group_cells(walk, n_cells, cpw, grp + 2 * stride), lane);
         } else {
             operand_gather<G, BS>(m, W, v, nullptr, c0, ncell, lane);
         }
@@ -215,7 +210,7 @@ __global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_diag(Operand
     const int cpw = m.cells_per_wave, nd = m.ndofs, nq = m.nq, ng = m.ngeom;
     const int sx = op_odd(ng * G);
     double* X = W;
-    double* Pm = X + ((cpw * sx + 1) & ~1);          // staging of the C blocks, then the parked matrices [point][PT]
+    double* Pm = X + op_even(cpw * sx);             // staging of the C blocks, then the parked matrices [point][PT]
     const int64_t n_groups = (n_cells + cpw - 1) / cpw;
     const GroupWalk walk = xcd_group_walk(n_groups, DXO_BLOCK / DXO_WAVE, wave);
     const int c_l = lane / nq, q_l = lane - c_l * nq;
@@ -226,33 +221,14 @@ __global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_diag(Operand
         const bool has_point = c_l < ncell;
         BlockRows<DT, DR> rows;
         rows.begin(C, c0 * nq, ncell * nq, lane);
-        for (int idx = lane; idx < ncell * ng; idx += DXO_WAVE) {
-            const int c = idx / ng, vv = idx - c * ng;
-            const int64_t node = m.geom_dofmap[(c0 + c) * ng + vv];
-#pragma unroll
-            for (int j = 0; j < G; ++j) X[c * sx + vv * G + j] = m.x[node * G + j];
-        }
+        gather_vertices<G>(m, X, nullptr, c0, ncell, lane);
         op_fence();
         double K[G][G], scale = 0.0;
 #pragma unroll
         for (int j = 0; j < G; ++j)
 #pragma unroll
             for (int k = 0; k < G; ++k) K[j][k] = 0.0;
-        if (has_point) {
-            const double* dpsi = tab + L.o_dpsi + q_l * L.sdpsi;
-            const double* Xc = X + c_l * sx;
-            double J[G][G];
-#pragma unroll
-            for (int j = 0; j < G; ++j)
-#pragma unroll
-                for (int k = 0; k < G; ++k) J[j][k] = 0.0;
-            for (int vv = 0; vv < ng; ++vv)
-#pragma unroll
-                for (int j = 0; j < G; ++j)
-#pragma unroll
-                    for (int k = 0; k < G; ++k) J[j][k] += Xc[vv * G + j] * dpsi[vv * G + k];
-            scale = w_l * fabs(invert<G>(J, K));
-        }
+        if (has_point) scale = w_l * fabs(point_jacobian<G>(tab + L.o_dpsi + q_l * L.sdpsi, X + c_l * sx, ng, K));
         double NSr[BS * NS1];
 #pragma unroll
         for (int k = 0; k < BS * NS1; ++k) NSr[k] = 0.0;
@@ -330,28 +306,11 @@ __global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_diag(Operand
                 if constexpr (Z0 == 0) z[0] = tab[q * L.sphi + a];
 #pragma unroll
                 for (int k = 0; k < G; ++k) z[1 + k - Z0] = dp[k];
-                int slot = 0;
+                sym_products<NZ>(z, pp);
 #pragma unroll
-                for (int k = 0; k < NZ; ++k)
-#pragma unroll
-                    for (int kk = k; kk < NZ; ++kk) pp[slot++] = z[k] * z[kk];
-#pragma unroll
-                for (int i = 0; i < BS; ++i) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int s2 = 0; s2 < NS1; ++s2) t += pp[s2] * P[i * NS1 + s2];
-                    acc[i] += t;
-                }
+                for (int i = 0; i < BS; ++i) acc[i] += sym_dot<NS1>(pp, P + i * NS1);
             }
-            const int64_t cell = c0 + c;
-            if (fe) {
-#pragma unroll
-                for (int i = 0; i < BS; ++i) fe[((int64_t)a * m.num_cells_fe + cell) * BS + i] = acc[i];
-            } else {
-                const int64_t node = m.dofmap[cell * nd + a];
-#pragma unroll
-                for (int i = 0; i < BS; ++i) unsafeAtomicAdd(out + node * BS + i, acc[i]);
-            }
+            store_entry<BS>(m, fe, out, c0 + c, a, nd, acc);
         }
         op_fence();      // the parked matrices are overwritten by the next group's staged blocks
     }
@@ -362,17 +321,12 @@ template <int G, int BS, int TEST, int TRIAL>
 struct Bilinear {
     using Rows = BlockRows<OperandShape<G, BS, TEST>::D, OperandShape<G, BS, TRIAL>::D>;
     static int lds_wave(const dxo_mesh* mesh, bool diag) {
-        const OperandDev& d = mesh->dev;
-        int wd;
         if (diag) {
             constexpr int NZ = G + 1 - ((op_has_value<TEST>() || op_has_value<TRIAL>()) ? 0 : 1);
             const int park = DXO_WAVE * ((BS * NZ * (NZ + 1) / 2) | 1);
-            wd = ((d.cells_per_wave * op_odd(d.ngeom * G) + 1) & ~1) + (park > Rows::LDS_DOUBLES ? park : Rows::LDS_DOUBLES);
-        } else {
-            wd = d.cells_per_wave * (op_odd(d.ndofs * BS) + op_odd(d.ngeom * G)) + DXO_WAVE * (DXO_ADJ_PAD ? ((BS * (G + 1)) | 1) : BS * (G + 1));
-            if (wd < Rows::LDS_DOUBLES) wd = Rows::LDS_DOUBLES;
+            return op_even(vertex_doubles(mesh->dev, G) + (park > Rows::LDS_DOUBLES ? park : Rows::LDS_DOUBLES));
         }
-        return (wd + 1) & ~1;        // even: every wave's region starts on a 16-byte boundary
+        return wave_region(gather_doubles(mesh->dev, G, BS) + parked_doubles(G, BS), Rows::LDS_DOUBLES);
     }
     static void launch(const dxo_mesh* mesh, bool diag, int wd, int blocks, size_t shm, const double* C, const double* v, double* out,
                        double* fe, hipStream_t s) {
@@ -452,12 +406,7 @@ int bilinear_impl(dxo_ctx* ctx, dxo_mesh* mesh, int test, int trial, int bs, con
     if (rc != DXO_OK) return rc;
     rc = clear_for_atomics(ctx, mesh, bs, out, fe, s);
     if (rc != DXO_OK) return rc;
-    const int64_t n_groups = (mesh->num_cells + mesh->dev.cells_per_wave - 1) / mesh->dev.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * DXO_BL_BLOCKS_PER_CU;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;
-    ops.launch(mesh, diag, wd, (int)blocks, shm, C, v, out, fe, s);
+    ops.launch(mesh, diag, wd, consumer_grid(ctx, wave_groups(mesh, mesh->num_cells), DXO_BL_BLOCKS_PER_CU), shm, C, v, out, fe, s);
     if (fe) launch_node_sum(ctx, mesh, bs, out, s);
     return dxo_device_end(ctx, s);
 }

@@ -178,10 +178,26 @@ __device__ __forceinline__ void dual_tensor(const double (&s)[OperandShape<G, BS
     }
 }
 
+// the dual tensor pulled back to reference gradients: T[i][k] = scale * sum_j gh[i][j] K[k][j] (K = J^-1, scale = w |det J|)
+template <int G, int BS>
+__device__ __forceinline__ void pull_back(const double (&gh)[BS][G], const double (&K)[G][G], double scale, double (&T)[BS][G]) {
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            double t = 0.0;
+#pragma unroll
+            for (int j = 0; j < G; ++j) t += gh[i][j] * K[k][j];
+            T[i][k] = scale * t;
+        }
+}
+
 // ---- LDS layout. Lanes of one wave read, in the same instruction, the SAME slot of up to 64/nq different cells
 // (U, X) or of nq different points (tables): a per-cell / per-point stride that is an ODD number of doubles sends
 // those addresses to different banks (an even stride such as 24 doubles = 48 dwords collides 4-way on 32 banks).
 __device__ __host__ __forceinline__ int op_odd(int n) { return n | 1; }
+// an EVEN number of doubles: what follows starts on a 16-byte boundary again
+__device__ __host__ __forceinline__ int op_even(int n) { return (n + 1) & ~1; }
 
 template <int G>
 struct OperandLayout {
@@ -226,6 +242,13 @@ __device__ __forceinline__ GroupWalk xcd_group_walk(int64_t n_groups, int waves_
     return {begin + (int64_t)local * waves_per_block + wave, end, (int64_t)per_xcd * waves_per_block};
 }
 
+// cells of wave group g: cpw, fewer in the mesh's last group, none past the end of the walk (the look-ahead of the pipelines)
+__device__ __forceinline__ int group_cells(const GroupWalk& walk, int64_t n_cells, int cpw, int64_t g) {
+    if (g >= walk.end) return 0;
+    const int64_t left = n_cells - g * cpw;
+    return left < cpw ? (int)left : cpw;
+}
+
 // ---- gather of one wave-group's dofs and vertex coordinates into the wave's LDS buffer W
 template <int G, int BS>
 __device__ __forceinline__ void operand_gather(const OperandDev& m, double* W, const double* __restrict__ u,
@@ -248,6 +271,35 @@ __device__ __forceinline__ void operand_gather(const OperandDev& m, double* W, c
 #pragma unroll
         for (int j = 0; j < G; ++j) X[c * sx + v * G + j] = m.x[node * G + j];
     }
+}
+
+// ---- the geometry-only kernels: the group's vertices -> X ([ncell] x op_odd(ngeom * G)), then J^-1 and det J of a point from its cell's
+// dpsi rows and its cell's slice Xc of X
+template <int G>
+__device__ __forceinline__ void gather_vertices(const OperandDev& m, double* X, const int32_t* __restrict__ cells, int64_t c0, int ncell, int lane) {
+    const int ng = m.ngeom, sx = op_odd(ng * G);
+    for (int idx = lane; idx < ncell * ng; idx += DXO_WAVE) {
+        const int c = idx / ng, v = idx - c * ng;
+        const int64_t cell = cells ? (int64_t)cells[c0 + c] : c0 + c;
+        const int64_t node = m.geom_dofmap[cell * ng + v];
+#pragma unroll
+        for (int j = 0; j < G; ++j) X[c * sx + v * G + j] = m.x[node * G + j];
+    }
+}
+
+template <int G>
+__device__ __forceinline__ double point_jacobian(const double* dpsi, const double* Xc, int ng, double (&K)[G][G]) {   // returns det J
+    double J[G][G];
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+#pragma unroll
+        for (int k = 0; k < G; ++k) J[j][k] = 0.0;
+    for (int v = 0; v < ng; ++v)
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+#pragma unroll
+            for (int k = 0; k < G; ++k) J[j][k] += Xc[v * G + j] * dpsi[v * G + k];
+    return invert<G>(J, K);
 }
 
 // ---- the same gather as a two-deep register pipeline (entity list absent, at most OP_GI*64 dof slots and
