@@ -90,9 +90,14 @@ class KrylovOp(C.Structure):
 
 
 class KrylovPc(C.Structure):
-    """dxo_krylov_pc: DXO_PC_NONE (0), DXO_PC_JACOBI (1, inv [n]), DXO_PC_BLOCK_JACOBI (2, inv [n/bs][bs][bs]) or DXO_PC_AMG (3, inv
-    carries the dxo_amg handle)."""
+    """dxo_krylov_pc: DXO_PC_NONE (0), DXO_PC_JACOBI (1, inv [n]), DXO_PC_BLOCK_JACOBI (2, inv [n/bs][bs][bs]), DXO_PC_AMG (3, inv
+    carries the dxo_amg handle) or DXO_PC_CALLBACK (4, inv carries the address of a KrylovCallback)."""
     _fields_ = [("kind", C.c_int), ("bs", C.c_int), ("n", C.c_int64), ("inv", _P)]
+
+
+class KrylovCallback(C.Structure):
+    """dxo_krylov_callback: the function and user pointer of a DXO_PC_CALLBACK preconditioner."""
+    _fields_ = [("apply", KRYLOV_APPLY_FN), ("user", _P)]
 
 
 class KrylovInfo(C.Structure):
@@ -210,6 +215,10 @@ _SIGNATURES = {
                                    C.POINTER(_P), C.POINTER(_P)]),
     "dxo_krylov_cg": (C.c_int, [_P, _P, C.POINTER(KrylovOp), C.POINTER(KrylovPc), _P, _P, C.c_double, C.c_double, C.c_int, C.c_int,
                                 C.POINTER(KrylovInfo)]),
+    "dxo_krylov_fgmres": (C.c_int, [_P, _P, C.POINTER(KrylovOp), C.POINTER(KrylovPc), _P, _P, C.c_double, C.c_double, C.c_int, C.c_int,
+                                    C.POINTER(KrylovInfo)]),
+    "dxo_amg_set_cycle": (C.c_int, [_P, _P, C.c_int]),
+    "dxo_amg_cycle_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "dxo_mesh_set_facet_geometry": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "dxo_facet_set_create": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "dxo_facet_set_destroy": (C.c_int, [_P, _P]),

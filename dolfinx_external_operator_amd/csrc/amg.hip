@@ -51,6 +51,17 @@
 // of Dinv_F A^F given the mask, omega_F = (4/3) / rho_F, and amg_build_p skips the weak blocks (all three through amg_filtered_block).
 // The sweeps keep A, Dinv and rho.
 //
+// The K-cycle (dxo_amg_set_cycle with DXO_AMG_CYCLE_K). The cycle is a recursion over the cycle body B_l of a level (pre-smoothing,
+// restriction, the solve of the next level, prolongation, post-smoothing: amg_body). The V-cycle solves the next level by its body, once.
+// The K-cycle solves every intermediate level l (1 <= l <= levels - 2) by two GCR steps preconditioned with B_l (amg_solve_level):
+// c1 = B_l(r), v1 = A_l c1 (the SpMV of krylov.hip), the partials of (v1, v1) and (v1, r) in one pass (amg_k_dots, a fixed grid per
+// level), a one-workgroup kernel that adds them in a fixed order and leaves a1 / rho1 on the device (amg_k_scalar),
+// r1 = r - (a1 / rho1) v1 (amg_k_residual), c2 = B_l(r1), v2 = A_l c2, the partials of (v2, v2), (v2, v1), (v2, r1), the two
+// coefficients of x with their guards (rho1 == 0: x = 0; rho2 not finite or <= 1e-14 (v2, v2): x = (a1 / rho1) c1) and
+// x = co1 c1 + co2 c2 (amg_k_combine). Both steps always run: no host read, no skipped launch, so an apply stays capture-safe and
+// bit-reproducible. The two calls of B_l share xa, xb, t, d of the level and everything below it, so B_l writes its result straight
+// into c1 (then c2) of the level's K vectors, which nothing else touches. Level 0 runs B_0 alone: the Krylov method is its acceleration.
+//
 // Host side. Run-time shapes reach the templates through one dispatcher (with_int / with_pairs and their named lists: with_bs,
 // with_level, with_pair, with_square, with_nns_pair), so a kernel's argument list is written once. amg_build allocates the device scalars
 // of every level once, before the level loop, and walks read pattern -> [strength mask] -> aggregates -> transfer tables -> coarse
@@ -98,7 +109,10 @@ struct amg_level {
     // vectors [n_rows]
     double *r = nullptr, *xa = nullptr, *xb = nullptr, *t = nullptr;
     double* d = nullptr;               // the Chebyshev direction (absent on the coarsest)
-    double* cur = nullptr;             // the iterate of the running cycle
+    // the K-cycle (dxo_amg_set_cycle; intermediate levels only): [n_rows] each, the partials [3][knb] and the coefficients
+    double *kc1 = nullptr, *kv1 = nullptr, *kc2 = nullptr, *kv2 = nullptr, *kr1 = nullptr;
+    double *kpart = nullptr, *kco = nullptr;
+    int knb = 0;                       // workgroups of amg_k_dots on this level = partials per product
     // near-null space path only
     double* b_val = nullptr;           // [n_rows][k] B of this level
     double* t_val = nullptr;           // [n_nodes][bs][k] blocks of T (absent on the coarsest)
@@ -141,6 +155,7 @@ struct dxo_amg {
     double* omega_f = nullptr;         // [levels] omega of the filtered prolongator smoothing
     double* rho_f = nullptr;           // [levels] the estimate of Dinv_F A^F it was made from
     double* cheb_f = nullptr;          // [AMG_CHEB_STRIDE] where amg_power_norm leaves the pairs of rho_F: not used
+    int cycle = DXO_AMG_CYCLE_V;       // dxo_amg_set_cycle
 };
 
 namespace {
@@ -934,6 +949,89 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_prolong(int64_t n_nodes, co
     for (int r = 0; r < BSR; ++r) x[i * BSR + r] += acc[r];
 }
 
+// ---- the K-cycle
+constexpr int AMG_K_MAX_PARTS = 1024;
+enum { KCO_RHO1 = 0, KCO_A1 = 1, KCO_ALPHA1 = 2, KCO_X1 = 3, KCO_X2 = 4, KCO_COUNT = 8 };
+
+// part[q * gridDim.x + block] = the workgroup's share of (w, w) (q = 0), (w, a) (q = 1) and, with b, (w, b) (q = 2); w is read once.
+// The grid is fixed for a level and the rows are taken with its stride, so the terms a thread adds, and their order, are fixed
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_k_dots(int64_t n, const double* __restrict__ w, const double* __restrict__ a,
+                                                            const double* __restrict__ b, double* __restrict__ part) {
+    __shared__ double lds[3][DXO_AMG_BLOCK / 64];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * DXO_AMG_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double wi = w[i];
+        s0 = fma(wi, wi, s0);
+        s1 = fma(wi, a[i], s1);
+        if (b) s2 = fma(wi, b[i], s2);
+    }
+    s0 = amg_block_sum(s0, lds[0]);
+    s1 = amg_block_sum(s1, lds[1]);
+    s2 = amg_block_sum(s2, lds[2]);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = s0;
+        part[(int64_t)gridDim.x + blockIdx.x] = s1;
+        part[2 * (int64_t)gridDim.x + blockIdx.x] = s2;
+    }
+}
+
+// one workgroup: the sums of the partials (a thread's in ascending order, then amg_block_sum) and the coefficients of the GCR step.
+// step 1: rho1 = (v1, v1), a1 = (v1, r), alpha1 = a1 / rho1 (0 with rho1 == 0). step 2: beta = (v2, v2), g = (v2, v1), a2 = (v2, r1),
+// rho2 = beta - g g / rho1 and x = X1 c1 + X2 c2: (0, 0) with rho1 == 0, (alpha1, 0) when rho2 is not finite or at most 1e-14 beta
+// (the second direction depends on the first: the rule of the singular diagonal block), else (alpha1 - g a2 / (rho1 rho2), a2 / rho2)
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_k_scalar(const double* __restrict__ part, int nb, int step, double* __restrict__ co) {
+    __shared__ double lds[3][DXO_AMG_BLOCK / 64];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = threadIdx.x; i < nb; i += DXO_AMG_BLOCK) {
+        s0 += part[i];
+        s1 += part[nb + i];
+        s2 += part[2 * nb + i];
+    }
+    s0 = amg_block_sum(s0, lds[0]);
+    s1 = amg_block_sum(s1, lds[1]);
+    s2 = amg_block_sum(s2, lds[2]);
+    if (threadIdx.x != 0) return;
+    if (step == 1) {
+        co[KCO_RHO1] = s0;
+        co[KCO_A1] = s1;
+        co[KCO_ALPHA1] = s0 == 0.0 ? 0.0 : s1 / s0;
+        return;
+    }
+    const double rho1 = co[KCO_RHO1], alpha1 = co[KCO_ALPHA1], beta = s0, g = s1, a2 = s2;
+    double x1 = 0.0, x2 = 0.0;
+    if (rho1 != 0.0) {
+        const double rho2 = beta - g * g / rho1;
+        if (!std::isfinite(rho2) || rho2 <= 1e-14 * beta) {
+            x1 = alpha1;
+        } else {
+            x1 = alpha1 - g * a2 / (rho1 * rho2);
+            x2 = a2 / rho2;
+        }
+    }
+    co[KCO_X1] = x1;
+    co[KCO_X2] = x2;
+}
+
+// r1 = r - alpha1 v1
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_k_residual(int64_t n, const double* __restrict__ co, const double* __restrict__ r,
+                                                                const double* __restrict__ v1, double* __restrict__ r1) {
+    const double alpha = co[KCO_ALPHA1];
+    const int64_t stride = (int64_t)gridDim.x * DXO_AMG_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x; i < n; i += stride) r1[i] = fma(-alpha, v1[i], r[i]);
+}
+
+// c1 <- X1 c1 + X2 c2 in place; a zero coefficient leaves its vector out, so that the guards give exactly 0 and exactly alpha1 c1
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_k_combine(int64_t n, const double* __restrict__ co, double* __restrict__ c1,
+                                                               const double* __restrict__ c2) {
+    const double x1 = co[KCO_X1], x2 = co[KCO_X2];
+    const int64_t stride = (int64_t)gridDim.x * DXO_AMG_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double t = x1 != 0.0 ? x1 * c1[i] : 0.0;
+        c1[i] = x2 != 0.0 ? fma(x2, c2[i], t) : t;
+    }
+}
+
 // ---- host: launch helpers
 // a shape without an instantiation is a defect of this file, not of the caller: the entry points admit (1..3) and the lists below
 [[noreturn]] inline void amg_no_shape(int a, int b) {
@@ -1544,58 +1642,93 @@ int dxo_amg_pc_check(dxo_ctx* ctx, const char* who, const dxo_amg* amg, const dx
     return DXO_OK;
 }
 
-void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipStream_t s) {
-    (void)ctx;
-    const bool cheby = amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV;
-    const int nl = (int)amg->L.size(), nu = cheby ? amg->degree : amg->sweeps;
-    const dim3 B(DXO_AMG_BLOCK);
-    if (amg->L[0].n_rows == 0) return;
-    for (int l = 0; l + 1 < nl; ++l) {
-        amg_level& v = amg->L[(size_t)l];
-        const double* rin = l == 0 ? r : v.r;
-        const double* om = amg->omega + l;
-        const double* ch = amg->cheb + (size_t)l * AMG_CHEB_STRIDE;
-        double *cur = v.xa, *other = v.xb;
-        with_bs(v.bs, [&](auto BS) {      // from x = 0: omega Dinv r, or c2 Dinv r into the direction as well
-            amg_launch(amg_first_step<BS>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.dinv, cheby ? ch + 1 : om, rin, cheby ? v.d : nullptr, cur);
-        });
-        for (int k = 1; k < nu; ++k) {
-            if (cheby) cheby_step(v, ch + 2 * k, rin, cur, other, s);
-            else sweep<false>(v, om, rin, cur, other, s);
-            std::swap(cur, other);
-        }
-        sweep<true>(v, om, rin, cur, v.t, s);
-        with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
-            amg_launch(amg_restrict<BSR, BSC>, v.n_agg, DXO_AMG_BLOCK, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, v.p_val, v.t, amg->L[(size_t)l + 1].r);
-        });
-        v.cur = cur;
+namespace {
+
+struct CycleRun {
+    dxo_ctx* ctx;
+    dxo_amg* amg;
+    hipStream_t s;
+    bool cheby;
+    int nl, nu;                        // levels; sweeps or the Chebyshev degree
+};
+
+const double* amg_solve_level(const CycleRun& C, int l, const double* rin);
+
+// the cycle body of level l: B_l(rin). The result lies in `out` if one is given (the last sweep of the post-smoothing writes it
+// there), in xa or xb of the level otherwise; the coarsest level is the dense product into xa
+const double* amg_body(const CycleRun& C, int l, const double* rin, double* out) {
+    dxo_amg* amg = C.amg;
+    const hipStream_t s = C.s;
+    amg_level& v = amg->L[(size_t)l];
+    if (l == C.nl - 1) {
+        const double* W = amg->dense[amg->nc % 2];
+        hipLaunchKernelGGL(amg_dense_apply, amg_grid(amg->nc, DXO_AMG_BLOCK / 64), dim3(DXO_AMG_BLOCK), 0, s, amg->nc, W, rin, v.xa);
+        return v.xa;
     }
-    amg_level& c = amg->L.back();
-    const double* W = amg->dense[amg->nc % 2];
-    hipLaunchKernelGGL(amg_dense_apply, amg_grid(amg->nc, DXO_AMG_BLOCK / 64), B, 0, s, amg->nc, W, nl == 1 ? r : c.r, c.xa);
-    c.cur = c.xa;
-    if (nl == 1) {
-        (void)hipMemcpyAsync(z, c.xa, (size_t)c.n_rows * sizeof(double), hipMemcpyDeviceToDevice, s);
+    const double* om = amg->omega + l;
+    const double* ch = amg->cheb + (size_t)l * AMG_CHEB_STRIDE;
+    double *cur = v.xa, *other = v.xb;
+    with_bs(v.bs, [&](auto BS) {      // from x = 0: omega Dinv r, or c2 Dinv r into the direction as well
+        amg_launch(amg_first_step<BS>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.dinv, C.cheby ? ch + 1 : om, rin, C.cheby ? v.d : nullptr, cur);
+    });
+    for (int k = 1; k < C.nu; ++k) {
+        if (C.cheby) cheby_step(v, ch + 2 * k, rin, cur, other, s);
+        else sweep<false>(v, om, rin, cur, other, s);
+        std::swap(cur, other);
+    }
+    sweep<true>(v, om, rin, cur, v.t, s);
+    with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
+        amg_launch(amg_restrict<BSR, BSC>, v.n_agg, DXO_AMG_BLOCK, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, v.p_val, v.t, amg->L[(size_t)l + 1].r);
+    });
+    const double* xc = amg_solve_level(C, l + 1, amg->L[(size_t)l + 1].r);
+    with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
+        amg_launch(amg_prolong<BSR, BSC>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, xc, cur);
+    });
+    for (int k = 0; k < C.nu; ++k) {
+        double* to = (out && k == C.nu - 1) ? out : other;      // the last sweep writes the result where the caller wants it
+        if (C.cheby) cheby_step(v, ch + 2 * k, rin, cur, to, s);
+        else sweep<false>(v, om, rin, cur, to, s);
+        other = cur;
+        cur = to;
+    }
+    return cur;
+}
+
+// the solution of A_l x = rin the level above prolongs. V-cycle, and the coarsest level of either cycle: the body, once. K-cycle on
+// an intermediate level: two GCR steps preconditioned by the body
+const double* amg_solve_level(const CycleRun& C, int l, const double* rin) {
+    dxo_amg* amg = C.amg;
+    const hipStream_t s = C.s;
+    if (amg->cycle != DXO_AMG_CYCLE_K || l == C.nl - 1) return amg_body(C, l, rin, nullptr);
+    amg_level& v = amg->L[(size_t)l];
+    const dim3 G((unsigned)v.knb), B(DXO_AMG_BLOCK), One(1);
+    amg_body(C, l, rin, v.kc1);
+    (void)dxo_kr_spmv_launch(C.ctx, v.A, v.values, v.kc1, v.kv1, s);      // a level has block size 1, 2, 3 or 6
+    hipLaunchKernelGGL(amg_k_dots, G, B, 0, s, v.n_rows, v.kv1, rin, (const double*)nullptr, v.kpart);
+    hipLaunchKernelGGL(amg_k_scalar, One, B, 0, s, v.kpart, v.knb, 1, v.kco);
+    hipLaunchKernelGGL(amg_k_residual, G, B, 0, s, v.n_rows, v.kco, rin, v.kv1, v.kr1);
+    amg_body(C, l, v.kr1, v.kc2);      // reuses xa, xb, t, d of this level and everything below: c1 and v1 are safe in the K vectors
+    (void)dxo_kr_spmv_launch(C.ctx, v.A, v.values, v.kc2, v.kv2, s);
+    hipLaunchKernelGGL(amg_k_dots, G, B, 0, s, v.n_rows, v.kv2, v.kv1, v.kr1, v.kpart);
+    hipLaunchKernelGGL(amg_k_scalar, One, B, 0, s, v.kpart, v.knb, 2, v.kco);
+    hipLaunchKernelGGL(amg_k_combine, G, B, 0, s, v.n_rows, v.kco, v.kc1, v.kc2);
+    return v.kc1;
+}
+
+}  // namespace
+
+bool dxo_amg_cycle_is_k(const dxo_amg* amg) { return amg->cycle == DXO_AMG_CYCLE_K; }
+
+void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipStream_t s) {
+    const bool cheby = amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV;
+    const CycleRun C{ctx, amg, s, cheby, (int)amg->L.size(), cheby ? amg->degree : amg->sweeps};
+    if (amg->L[0].n_rows == 0) return;
+    if (C.nl == 1) {
+        const double* x = amg_body(C, 0, r, nullptr);
+        (void)hipMemcpyAsync(z, x, (size_t)amg->L[0].n_rows * sizeof(double), hipMemcpyDeviceToDevice, s);
         return;
     }
-    for (int l = nl - 2; l >= 0; --l) {
-        amg_level& v = amg->L[(size_t)l];
-        const double* rin = l == 0 ? r : v.r;
-        const double* om = amg->omega + l;
-        double* cur = v.cur;
-        double* other = cur == v.xa ? v.xb : v.xa;
-        with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
-            amg_launch(amg_prolong<BSR, BSC>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, amg->L[(size_t)l + 1].cur, cur);
-        });
-        for (int k = 0; k < nu; ++k) {
-            double* out = (l == 0 && k == nu - 1) ? z : other;      // the last sweep of the fine level writes the result
-            if (cheby) cheby_step(v, amg->cheb + (size_t)l * AMG_CHEB_STRIDE + 2 * k, rin, cur, out, s);
-            else sweep<false>(v, om, rin, cur, out, s);
-            other = cur;
-            cur = out;
-        }
-        v.cur = cur;
-    }
+    amg_body(C, 0, r, z);      // level 0 is one body in either cycle: the Krylov method outside is its acceleration
 }
 
 // ---- C ABI
@@ -1760,6 +1893,49 @@ extern "C" int dxo_amg_smoother_info(dxo_ctx* ctx, const dxo_amg* amg, int level
     if (rho_kind) *rho_kind = amg->rho_kind;
     if (rho_iters) *rho_iters = amg->rho_iters;
     if (rho) *rho = level + 1 < (int)amg->L.size() ? amg->rho + level : nullptr;
+    return DXO_OK;
+}
+
+extern "C" int dxo_amg_set_cycle(dxo_ctx* ctx, dxo_amg* amg, int kind) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!amg) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_set_cycle: NULL argument");
+    if (kind != DXO_AMG_CYCLE_V && kind != DXO_AMG_CYCLE_K) return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_set_cycle: unknown cycle");
+    if (kind == DXO_AMG_CYCLE_K) {      // the K vectors of the intermediate levels, once; dxo_amg_apply stays allocation-free
+        DXO_HIP(ctx, hipSetDevice(amg->device));
+        Uploader U{ctx, amg, "dxo_amg_set_cycle"};
+        for (size_t l = 1; l + 1 < amg->L.size(); ++l) {
+            amg_level& v = amg->L[l];
+            if (v.kco) continue;
+            const int knb = (int)std::min<int64_t>(AMG_K_MAX_PARTS, std::max<int64_t>(1, (v.n_rows + DXO_AMG_BLOCK - 1) / DXO_AMG_BLOCK));
+            double* vec = U.alloc<double>((size_t)(5 * v.n_rows));
+            double* part = U.alloc<double>((size_t)(3 * knb));
+            double* co = U.alloc<double>(KCO_COUNT);
+            if (U.rc != DXO_OK) return U.rc;      // what was allocated goes with the object; the cycle is unchanged
+            DXO_HIP(ctx, hipMemset(co, 0, KCO_COUNT * sizeof(double)));
+            v.kc1 = vec, v.kv1 = vec + v.n_rows, v.kc2 = vec + 2 * v.n_rows, v.kv2 = vec + 3 * v.n_rows, v.kr1 = vec + 4 * v.n_rows;
+            v.kpart = part;
+            v.knb = knb;
+            v.kco = co;
+        }
+    }
+    amg->cycle = kind;
+    return DXO_OK;
+}
+
+extern "C" int dxo_amg_cycle_info(dxo_ctx* ctx, const dxo_amg* amg, int* kind, int64_t* visits) {
+    if (!amg) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    const int nl = (int)amg->L.size();
+    if (kind) *kind = amg->cycle;
+    if (visits) {
+        *visits = nl;      // V: every level once
+        if (amg->cycle == DXO_AMG_CYCLE_K && nl >= 2) {      // K: level l 2^l times, the coarsest as often as the level above it
+            *visits = 0;
+            for (int l = 0; l + 1 < nl; ++l) *visits += (int64_t)1 << l;
+            *visits += (int64_t)1 << (nl - 2);
+        }
+    }
     return DXO_OK;
 }
 

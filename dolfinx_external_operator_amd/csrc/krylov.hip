@@ -20,6 +20,10 @@
 // steps only; the solution update uses the recorded step, so steps run past it change nothing. Every reduction has a fixed shape
 // (fixed grid for a workspace, fixed butterflies, fixed order across waves): a solve is bit-reproducible.
 // CG runs on the same kernels; once its residual test passes on the device, alpha is 0 for the steps that follow.
+//
+// Flexible GMRES (dxo_krylov_fgmres) is the same sequence with z_j = M v_j kept in a second basis Z [m][ld]: w = A z_j, and the update
+// at the end of a cycle is x += sum_j y_j z_j (kr_combine on Z), with no further preconditioner call. M may therefore change from
+// step to step (a callback that iterates, the K-cycle of amg.hip). Z is allocated at the first flexible solve on a workspace.
 #include "csr.h"
 #include "dxo_common.h"
 #include "krylov_internal.h"
@@ -38,6 +42,7 @@ struct dxo_krylov {
     int m = 0;                 // restart length
     int nb = 0;                // workgroups of the row kernels = partials per product (fixed for the workspace)
     double* vec = nullptr;     // [m + 1 + 4][ld]: the basis V, then Z, R, T, Q
+    double* zb = nullptr;      // [m][ld]: the preconditioned basis of dxo_krylov_fgmres, absent until its first solve here
     double* part = nullptr;    // [m + 2][nb] per-block partials (the last row: |w|^2)
     double* sc = nullptr;      // small state (offsets below)
     int* st = nullptr;         // status words
@@ -435,6 +440,16 @@ struct KrCall {
             dxo_amg_cycle(ctx, (dxo_amg*)pc->inv, r, z, s);
             return DXO_OK;
         }
+        if (pc->kind == DXO_PC_CALLBACK) {
+            const dxo_krylov_callback* cb = (const dxo_krylov_callback*)pc->inv;
+            const int rc = cb->apply(cb->user, r, z);
+            if (rc != DXO_OK) {
+                char msg[128];
+                snprintf(msg, sizeof msg, "dxo_krylov: the preconditioner callback returned %d", rc);
+                return dxo_fail(ctx, rc < 0 ? rc : DXO_E_OPTION, msg);
+            }
+            return DXO_OK;
+        }
         return bj_apply_launch(ctx, "dxo_krylov", pc->kind == DXO_PC_JACOBI ? 1 : pc->bs, ws->n, pc->inv, r, z, s);
     }
     // part[0..nb) = partials of (a, b); reduce into out (norm: sqrt and inverse into out[0], out[1])
@@ -460,8 +475,8 @@ struct KrCall {
     }
 };
 
-int kr_validate(dxo_ctx* ctx, const char* who, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
-                double rtol, double atol, int max_it, int check_every) {
+int kr_validate(dxo_ctx* ctx, const char* who, bool flexible, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b,
+                double* x, double rtol, double atol, int max_it, int check_every) {
     char msg[256];
     if (!ws || !op || !b || !x) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": NULL argument").c_str());
     if (!op->csr && !op->apply) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the operator has neither a matrix nor a callback").c_str());
@@ -480,6 +495,15 @@ int kr_validate(dxo_ctx* ctx, const char* who, dxo_krylov* ws, const dxo_krylov_
         }
         const int rc = dxo_amg_pc_check(ctx, who, (const dxo_amg*)pc->inv, op->csr, pc->bs, pc->n);
         if (rc != DXO_OK) return rc;
+        if (!flexible && dxo_amg_cycle_is_k((const dxo_amg*)pc->inv))
+            return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": a K-cycle is not a fixed linear operator: use dxo_krylov_fgmres").c_str());
+    } else if (pc && pc->kind == DXO_PC_CALLBACK) {      // pc->inv carries a dxo_krylov_callback*
+        const dxo_krylov_callback* cb = (const dxo_krylov_callback*)pc->inv;
+        if (!cb || !cb->apply) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the preconditioner has no callback").c_str());
+        if (pc->n != ws->n) {
+            snprintf(msg, sizeof msg, "%s: the preconditioner covers %lld rows, the operator has %lld", who, (long long)pc->n, (long long)ws->n);
+            return dxo_fail(ctx, DXO_E_SIZE, msg);
+        }
     } else if (pc && pc->kind != DXO_PC_NONE) {
         if (pc->kind != DXO_PC_JACOBI && pc->kind != DXO_PC_BLOCK_JACOBI) return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": unknown preconditioner kind").c_str());
         if (!pc->inv) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the preconditioner has no inverse").c_str());
@@ -514,6 +538,8 @@ void kr_multidot_launch(const KrCall& K, int nk, const double* w) {
     else hipLaunchKernelGGL((kr_multidot<64>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
 }
 
+// FLEX: z_j = M v_j goes to row j of the second basis and the update combines those rows; otherwise one Z and M once more at the update
+template <bool FLEX>
 int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
     dxo_ctx* ctx = K.ctx;
     dxo_krylov* ws = K.ws;
@@ -554,8 +580,9 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
         for (int j = 0; j < m && total + j < max_it; ++j) {
             double* w = ws->V() + (int64_t)(j + 1) * ws->ld;
             double* h = sc + (int64_t)j * (m + 1);
-            if ((rc = K.precond(ws->V() + (int64_t)j * ws->ld, ws->Z())) != DXO_OK) return rc;
-            if ((rc = K.apply(ws->Z(), w)) != DXO_OK) return rc;
+            double* zj = FLEX ? ws->zb + (int64_t)j * ws->ld : ws->Z();
+            if ((rc = K.precond(ws->V() + (int64_t)j * ws->ld, zj)) != DXO_OK) return rc;
+            if ((rc = K.apply(zj, w)) != DXO_OK) return rc;
             kr_multidot_launch(K, j + 1, w);
             hipLaunchKernelGGL(kr_reduce, dim3(j + 1), B, 0, s, ws->part, ws->nb, h, (double*)nullptr, 0, (double*)nullptr);
             hipLaunchKernelGGL(kr_update, G, B, 0, s, n, ws->V(), ws->ld, j + 1, h, w, npart);
@@ -580,9 +607,14 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
         total += k;
         if (k > 0) {
             hipLaunchKernelGGL(kr_trisolve, dim3(1), dim3(64), 0, s, sc, k, m, ws->o_g(), ws->o_y());
-            hipLaunchKernelGGL(kr_combine, G, B, 0, s, n, ws->V(), ws->ld, k, sc + ws->o_y(), ws->T());
-            if ((rc = K.precond(ws->T(), ws->Z())) != DXO_OK) return rc;
-            hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ONE, 1.0, ws->Z(), x);
+            if constexpr (FLEX) {
+                hipLaunchKernelGGL(kr_combine, G, B, 0, s, n, ws->zb, ws->ld, k, sc + ws->o_y(), ws->T());
+                hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ONE, 1.0, ws->T(), x);
+            } else {
+                hipLaunchKernelGGL(kr_combine, G, B, 0, s, n, ws->V(), ws->ld, k, sc + ws->o_y(), ws->T());
+                if ((rc = K.precond(ws->T(), ws->Z())) != DXO_OK) return rc;
+                hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ONE, 1.0, ws->Z(), x);
+            }
         }
         if (k == 0) break;
     }
@@ -653,15 +685,27 @@ int cg_impl(KrCall& K, const double* b, double* x, double rtol, double atol, int
 
 typedef int (*kr_solver)(KrCall&, const double*, double*, double, double, int, int, dxo_krylov_info*);
 
-int kr_solve(dxo_ctx* ctx, const char* who, kr_solver solver, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b,
+int kr_solve(dxo_ctx* ctx, const char* who, kr_solver solver, bool flexible, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b,
              double* x, double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = kr_validate(ctx, who, ws, op, pc, b, x, rtol, atol, max_it, check_every);
+    int rc = kr_validate(ctx, who, flexible, ws, op, pc, b, x, rtol, atol, max_it, check_every);
     if (rc != DXO_OK) return rc;
     dxo_krylov_info local;
     dxo_krylov_info* inf = info ? info : &local;
     *inf = dxo_krylov_info{};
     DXO_HIP(ctx, hipSetDevice(ctx->device));
+    if (flexible && !ws->zb) {      // the second basis: at the first flexible solve, kept with the workspace
+        const size_t bytes = (size_t)ws->m * ws->ld * sizeof(double);
+        hipError_t e = hipMalloc((void**)&ws->zb, bytes);
+        if (e == hipSuccess && (e = hipMemset(ws->zb, 0, bytes)) != hipSuccess) {
+            (void)hipFree(ws->zb);
+            ws->zb = nullptr;
+        }
+        if (e != hipSuccess) {
+            ws->zb = nullptr;
+            return dxo_hip_fail(ctx, e, "dxo_krylov_fgmres: second basis");
+        }
+    }
     KrCall K{ctx, ws, op, pc, dxo_launch_stream(ctx)};
     rc = solver(K, b, x, rtol, atol, max_it, check_every, inf);
     inf->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -679,6 +723,10 @@ int dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv
     else if (csr->bs == 3) hipLaunchKernelGGL(bj_setup<3>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
     else hipLaunchKernelGGL(bj_setup<6>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);      // a multigrid level
     return DXO_OK;
+}
+
+int dxo_kr_spmv_launch(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const double* x, double* y, hipStream_t s) {
+    return spmv_launch(ctx, "dxo_amg_apply", csr, values, 1.0, x, 0.0, y, s);
 }
 
 extern "C" int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y) {
@@ -768,7 +816,7 @@ extern "C" int dxo_krylov_destroy(dxo_ctx* ctx, dxo_krylov* ws) {
     DXO_LOCK(ctx);
     if (ctx) (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {(void*)ws->vec, (void*)ws->part, (void*)ws->sc, (void*)ws->st})
+    for (void* p : {(void*)ws->vec, (void*)ws->zb, (void*)ws->part, (void*)ws->sc, (void*)ws->st})
         if (p) (void)hipFree(p);
     delete ws;
     return DXO_OK;
@@ -778,12 +826,19 @@ extern "C" int dxo_krylov_gmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_o
                                 double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
-    return kr_solve(ctx, "dxo_krylov_gmres", gmres_impl, ws, op, pc, b, x, rtol, atol, max_it, check_every, info);
+    return kr_solve(ctx, "dxo_krylov_gmres", gmres_impl<false>, false, ws, op, pc, b, x, rtol, atol, max_it, check_every, info);
 }
 
 extern "C" int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
                              double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
-    return kr_solve(ctx, "dxo_krylov_cg", cg_impl, ws, op, pc, b, x, rtol, atol, max_it, check_every, info);
+    return kr_solve(ctx, "dxo_krylov_cg", cg_impl, false, ws, op, pc, b, x, rtol, atol, max_it, check_every, info);
+}
+
+extern "C" int dxo_krylov_fgmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
+                                 double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    return kr_solve(ctx, "dxo_krylov_fgmres", gmres_impl<true>, true, ws, op, pc, b, x, rtol, atol, max_it, check_every, info);
 }

@@ -191,6 +191,11 @@ __device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (
 // other); a singular block raises flag[0]
 int dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv, int* flag, hipStream_t s);
 
-// amg.hip: the checks of a DXO_PC_AMG preconditioner against the operator, and one V-cycle z = V(r) on the stream
+// krylov.hip: y = A x by the kernel of dxo_csr_spmv (bs 1, 2, 3, 6), for the coarse operators of the K-cycle
+int dxo_kr_spmv_launch(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const double* x, double* y, hipStream_t s);
+
+// amg.hip: the checks of a DXO_PC_AMG preconditioner against the operator, one cycle z = M(r) on the stream (V or K, as set by
+// dxo_amg_set_cycle), and whether that cycle is the K-cycle (not a fixed linear operator: flexible GMRES only)
 int dxo_amg_pc_check(dxo_ctx* ctx, const char* who, const dxo_amg* amg, const dxo_csr* op_csr, int bs, int64_t n);
 void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipStream_t s);
+bool dxo_amg_cycle_is_k(const dxo_amg* amg);

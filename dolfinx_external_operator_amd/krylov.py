@@ -1,4 +1,4 @@
-"""Linear solves on the device (csrc/krylov.hip): CSR SpMV, block Jacobi, restarted GMRES and CG.
+"""Linear solves on the device (csrc/krylov.hip): CSR SpMV, block Jacobi, restarted GMRES, flexible GMRES and CG.
 
 All vectors are contiguous float64 CUDA tensors on the context's device. The calls run on torch's current stream of that device,
 which they make the context's stream (the convention of the examples and tests: ctx.set_stream(torch.cuda.current_stream())), so
@@ -11,11 +11,12 @@ import ctypes as C
 import weakref
 from dataclasses import dataclass
 
-from ._lib import KRYLOV_APPLY_FN, AmgLevelInfo, KrylovInfo, KrylovOp, KrylovPc, _CudaArrayView
+from ._lib import KRYLOV_APPLY_FN, AmgLevelInfo, KrylovCallback, KrylovInfo, KrylovOp, KrylovPc, _CudaArrayView
 
-PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI, PC_AMG = 0, 1, 2, 3
+PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI, PC_AMG, PC_CALLBACK = 0, 1, 2, 3, 4
 _SMOOTHERS = {"jacobi": 0, "chebyshev": 1}           # DXO_AMG_SMOOTH_*
 _RHO_KINDS = {"inf-norm": 0, "power": 1}             # DXO_AMG_RHO_*
+_CYCLES = {"V": 0, "K": 1}                           # DXO_AMG_CYCLE_*
 
 
 def _torch():
@@ -38,7 +39,7 @@ def _use_current_stream(ctx) -> None:
 
 @dataclass
 class KrylovResult:
-    """What gmres / cg return: the solution, the iterations up to the converged step, the true relative residual |b - A x| / |b|,
+    """What gmres / fgmres / cg return: the solution, the iterations up to the converged step, the true relative residual |b - A x| / |b|,
     whether it met the tolerance, whether the iteration broke down, the cycles started and the wall ms of the solve."""
     x: object
     iterations: int
@@ -108,7 +109,8 @@ def rigid_body_modes(x, ctx=None):
 
 
 class AMG:
-    """Smoothed-aggregation multigrid preconditioner of an assembled matrix (dxo_amg_*, csrc/amg.hip), applied as one V-cycle.
+    """Smoothed-aggregation multigrid preconditioner of an assembled matrix (dxo_amg_*, csrc/amg.hip), applied as one V-cycle, or as
+    one K-cycle (`cycle`, below).
 
     The constructor runs the symbolic phase on the host (aggregates and the patterns of every level, once per pattern) and the first
     setup(). After the values of the matrix changed (a Newton iteration: the same DeviceCSR, or another on the same pattern) call
@@ -133,14 +135,21 @@ class AMG:
     smoothed with the filtered matrix (weak blocks lumped onto the diagonal), which is what anisotropic operators and stretched
     cells need (0.25 is customary for scalar problems). The masks, and with them the aggregates and all patterns, are made from the
     values of the matrix at construction and are frozen there: setup() reuses them for new values, and set_smoother() changes the
-    relaxation but not the coarsening (the construction itself coarsens with the default relaxation)."""
+    relaxation but not the coarsening (the construction itself coarsens with the default relaxation).
+
+    `cycle`: "V" (the default) or "K" (dxo_amg_set_cycle; set_cycle() changes it later, at once and without a setup, on any of the
+    hierarchies above). The K-cycle solves the coarse equation of every level between the finest and the coarsest by two GCR steps
+    preconditioned by the cycle of that level, so level l is visited 2^l times (`visits`). It is not a fixed linear operator: pass it
+    to fgmres; gmres and cg raise ValueError (DXO_E_OPTION). With at most two levels it is the V-cycle bit for bit."""
 
     def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None,
                  smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10, lower: float = 0.1,
-                 safety: float = 1.1, strength: float = 0.0):
+                 safety: float = 1.1, strength: float = 0.0, cycle: str = "V"):
         torch = _torch()
         import numpy as np
 
+        if cycle not in _CYCLES:
+            raise ValueError(f"AMG: cycle must be one of {sorted(_CYCLES)}")
         strength = float(strength)
         if not 0.0 <= strength < 1.0:          # NaN fails both comparisons
             raise ValueError("AMG: strength must lie in [0, 1)")
@@ -197,6 +206,8 @@ class AMG:
         self._lower, self._safety = 0.1, 1.1
         if relax[0] or relax[2]:         # the defaults call nothing that earlier versions did not call
             self._set_smoother(*relax)
+        if cycle != "V":
+            self.set_cycle(cycle)
         self.setup()
 
     def _relaxation(self, smoother, degree, rho, rho_iters, lower, safety) -> tuple:
@@ -221,6 +232,30 @@ class AMG:
         self._set_smoother(*self._relaxation(smoother, degree, rho, rho_iters, lower, safety))
         return self
 
+    def set_cycle(self, cycle: str = "V") -> "AMG":
+        """"V" or "K" (dxo_amg_set_cycle): takes effect at the next apply, no setup() needed. The first "K" allocates the vectors of
+        the two GCR steps on the intermediate levels."""
+        if cycle not in _CYCLES:
+            raise ValueError(f"AMG: cycle must be one of {sorted(_CYCLES)}")
+        self.ctx.check(self.ctx.lib.dxo_amg_set_cycle(self.ctx._h, self._h, _CYCLES[cycle]), "dxo_amg_set_cycle")
+        return self
+
+    def _cycle_info(self) -> tuple:
+        kind, visits = C.c_int(), C.c_int64()
+        self.ctx.check(self.ctx.lib.dxo_amg_cycle_info(self.ctx._h, self._h, C.byref(kind), C.byref(visits)), "dxo_amg_cycle_info")
+        return {v: k for k, v in _CYCLES.items()}[kind.value], int(visits.value)
+
+    @property
+    def cycle(self) -> str:
+        """"V" or "K"."""
+        return self._cycle_info()[0]
+
+    @property
+    def visits(self) -> int:
+        """Level visits of one apply: the levels for "V"; for "K" 2^l per level l but the coarsest, which is visited as often as
+        the level above it."""
+        return self._cycle_info()[1]
+
     def close(self) -> None:
         self._fin()
 
@@ -237,7 +272,7 @@ class AMG:
         return self
 
     def apply(self, r, out=None):
-        """out = V(r), one V-cycle (dxo_amg_apply); returns out."""
+        """out = M(r), one cycle (dxo_amg_apply; V, or K after set_cycle("K")); returns out."""
         torch = _torch()
         _check_vec(r, self.n, self.device, "AMG.apply: r")
         if out is None:
@@ -503,15 +538,35 @@ def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxit
         if M.n != n or M.inv.device != dev:
             raise ValueError(f"{entry}: the preconditioner covers {M.n} rows on {M.inv.device}, the operator has {n} on {dev}")
         pc = M._pc()
-    elif isinstance(M, AMG):
-        if M.n != n or M.device != dev or not isinstance(A, DeviceCSR) or A.pattern.bs != M.bs:
+    elif isinstance(M, AMG):      # on a callable A (matrix-free, or a lagged matrix behind M) the block size is the multigrid's
+        if M.n != n or M.device != dev or (isinstance(A, DeviceCSR) and A.pattern.bs != M.bs):
             raise ValueError(f"{entry}: the multigrid preconditioner covers {M.n} rows (bs {M.bs}) on {M.device}, the operator has {n} on {dev}")
         pc = M._pc()
     elif isinstance(M, torch.Tensor):
         _check_vec(M, n, dev, f"{entry}: M (inverse diagonal)")
         pc = KrylovPc(PC_JACOBI, 1, n, C.c_void_p(M.data_ptr()))
+    elif callable(M):
+        mviews: dict = {}
+
+        def mview(ptr: int):
+            t = mviews.get(ptr)
+            if t is None:
+                t = mviews[ptr] = torch.as_tensor(_CudaArrayView(ctx, ptr, n, "<f8"), device=dev)
+            return t
+
+        def mcb(_user, r, out):
+            try:
+                M(mview(r), mview(out))
+                return 0
+            except BaseException as e:      # noqa: BLE001 — re-raised after the solve returns
+                failure.append(e)
+                return 1
+
+        mcb = KRYLOV_APPLY_FN(mcb)
+        mstruct = KrylovCallback(mcb, None)      # both stay referenced until the solve has returned
+        pc = KrylovPc(PC_CALLBACK, 1, n, C.cast(C.pointer(mstruct), C.c_void_p))
     else:
-        raise TypeError(f"{entry}: M must be None, a BlockJacobi, an AMG or a tensor holding an inverse diagonal")
+        raise TypeError(f"{entry}: M must be None, a BlockJacobi, an AMG, a tensor holding an inverse diagonal or a callable (r, out)")
     if maxiter is None:
         maxiter = max(1000, 10 * restart)
     ws = _workspace(ctx, n, restart)
@@ -532,16 +587,32 @@ def gmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: fl
 
     A: a DeviceCSR, or a callable (v, out) that sets out = A v on the device (e.g. DeviceMesh.bilinear_apply with option
     consumer_overwrite = 1; `ctx` then names the context, default_context() otherwise). M: None, a BlockJacobi, an AMG (one V-cycle
-    per iteration; A must then be a DeviceCSR), or a float64 CUDA tensor holding an inverse diagonal (1 / bilinear_diagonal for the matrix-free path). x: the initial guess, overwritten with the
+    per iteration; with a callable A the multigrid of an assembled, possibly lagged, matrix of the same size), a float64 CUDA tensor
+    holding an inverse diagonal (1 / bilinear_diagonal for the matrix-free path), or a callable (r, out) that sets out = M r on the
+    device; an exception in it is re-raised after the solve. M must be a fixed linear operator here, the same at every call: M is
+    applied once more to the combination at the end of a cycle. One that varies (an inner iteration, an AMG with the K-cycle,
+    which raises ValueError here) belongs to fgmres. x: the initial guess, overwritten with the
     solution (zeros if None). Converged when |b - A x| <= max(rtol |b|, atol); not converging within maxiter gives converged False,
     not an exception."""
     return _solve("dxo_krylov_gmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx)
 
 
+def fgmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: float = 0.0, maxiter: int | None = None,
+           check_every: int = 8, ctx=None) -> KrylovResult:
+    """Solve A x = b by flexible GMRES(restart) on the device (dxo_krylov_fgmres), with the arguments and the stopping rule of gmres.
+
+    M need not be a fixed linear operator: it may differ from step to step (a callable that runs an inner solve, an AMG with the
+    K-cycle). The preconditioned vectors z_j = M v_j are kept in a second basis (restart more vectors, allocated at the first
+    flexible solve of a size) and the solution is updated with them, so M is called once per iteration and never at the update.
+    With a fixed M it takes the iterations of gmres."""
+    return _solve("dxo_krylov_fgmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx)
+
+
 def cg(A, b, x=None, M=None, rtol: float = 1e-10, atol: float = 0.0, maxiter: int | None = None, check_every: int = 8,
        ctx=None) -> KrylovResult:
-    """Preconditioned conjugate gradients for symmetric positive definite A and M, same arguments as gmres (dxo_krylov_cg)."""
+    """Preconditioned conjugate gradients for symmetric positive definite A and M, same arguments as gmres (dxo_krylov_cg). M must
+    be a fixed linear operator (a callable that varies between calls, or an AMG with the K-cycle, has no place here: fgmres)."""
     return _solve("dxo_krylov_cg", A, b, x, M, 1, rtol, atol, maxiter, check_every, ctx)
 
 
-__all__ = ["AMG", "BlockJacobi", "KrylovResult", "cg", "csr_matvec", "gmres", "rigid_body_modes"]
+__all__ = ["AMG", "BlockJacobi", "KrylovResult", "cg", "csr_matvec", "fgmres", "gmres", "rigid_body_modes"]

@@ -590,11 +590,20 @@ int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n
  *                   0 iterations. Not converging within max_it is NOT an error: info->converged = 0. Every reduction has a fixed
  *                   shape: a solve is bit-reproducible.
  * dxo_krylov_cg   : preconditioned CG on the same kernels and arguments (A and M symmetric positive definite).
+ * dxo_krylov_fgmres : flexible GMRES(restart): the arguments, stopping rule, check_every protocol, breakdown handling and info of
+ *                   dxo_krylov_gmres. It keeps z_j = M v_j in a second basis Z [restart][ld], forms w = A z_j and updates
+ *                   x += sum_j y_j z_j at the end of a cycle, with no further preconditioner call. M may therefore differ from step
+ *                   to step (an inner iteration, a K-cycle); dxo_krylov_gmres and dxo_krylov_cg need a fixed linear M. With a fixed
+ *                   M it takes the iterations of dxo_krylov_gmres. The second basis (restart * ld doubles) is allocated at the first
+ *                   flexible solve on a workspace and freed with it: a workspace that serves only gmres / cg keeps today's memory.
  * Operator: a CSR matrix (csr + values) or a callback that SETS out = A v on the context's stream (e.g. dxo_bilinear_apply with option
  * "consumer_overwrite" = 1). The callback runs on the calling thread while the context's (recursive) lock is held, so it may call
  * other dxo_* entry points on the same context; a nonzero return ends the solve with that code. Preconditioner: NULL or kind
  * DXO_PC_NONE, DXO_PC_JACOBI (inv [n]) or DXO_PC_BLOCK_JACOBI (inv [n/bs][bs][bs], bs equal to the pattern's).
- * DXO_PC_AMG: a dxo_amg (below) after dxo_amg_setup, applied as one V-cycle.
+ * DXO_PC_AMG: a dxo_amg (below) after dxo_amg_setup, applied as one cycle; with the K-cycle (dxo_amg_set_cycle) in dxo_krylov_fgmres
+ * only: DXO_E_OPTION in the other two.
+ * DXO_PC_CALLBACK: inv carries a dxo_krylov_callback* whose function SETS out = M v on the context's stream, under the rules of the
+ * operator callback; a nonzero return ends the solve with that code. A NULL struct or function: DXO_E_NULL. bs is ignored.
  * Errors: NULL arguments DXO_E_NULL; operator, matrix, workspace and preconditioner sizes that differ, n not a multiple of bs, max_it < 0 or
  * check_every < 1 DXO_E_SIZE; a preconditioner of another block size DXO_E_DIM; arrays not 8-byte aligned DXO_E_ALIGN; negative
  * tolerances or an unknown preconditioner kind DXO_E_OPTION. */
@@ -602,6 +611,7 @@ int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n
 #define DXO_PC_JACOBI 1
 #define DXO_PC_BLOCK_JACOBI 2
 #define DXO_PC_AMG 3               /* dxo_krylov_pc::inv carries the dxo_amg* (cast to const double*), bs and n as for block Jacobi */
+#define DXO_PC_CALLBACK 4          /* dxo_krylov_pc::inv carries a dxo_krylov_callback* (cast to const double*), n as above        */
 typedef struct dxo_krylov dxo_krylov;
 typedef int (*dxo_krylov_apply_fn)(void* user, const double* v, double* out);
 typedef struct dxo_krylov_op {
@@ -611,6 +621,10 @@ typedef struct dxo_krylov_op {
     dxo_krylov_apply_fn apply;     /* or, with csr NULL, this callback                    */
     void* user;                    /* passed to apply                                     */
 } dxo_krylov_op;
+typedef struct dxo_krylov_callback {
+    dxo_krylov_apply_fn apply;     /* sets out = M v                                      */
+    void* user;                    /* passed to apply                                     */
+} dxo_krylov_callback;
 typedef struct dxo_krylov_pc {
     int kind;                      /* DXO_PC_*                                            */
     int bs;                        /* DXO_PC_BLOCK_JACOBI: block size (1, 2, 3)           */
@@ -634,6 +648,8 @@ int dxo_krylov_gmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, cons
                      double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info);
 int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
                   double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info);
+int dxo_krylov_fgmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
+                      double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info);
 
 /* ---- smoothed-aggregation multigrid preconditioner (csrc/amg.hip), DEVICE memory only ---------------------------
  * A V-cycle for a matrix on a dxo_csr pattern; the block size bs (1, 2, 3) is the same on every level, so every level is a matrix in
@@ -725,11 +741,28 @@ int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const d
  * dxo_amg_soc_info : theta, the DEVICE mask of `level` (one uint8 per block, in the order of the level's block pattern), its number
  *                   of strong blocks, the nodes whose lumped block failed the test at the last setup (waits for the stream), and
  *                   the DEVICE arrays dinv_f [n_nodes][bs][bs] and omega_F (one double). Any pointer may be NULL. On an object made
- *                   without strength, and on the coarsest level: NULL arrays, every block strong, 0 nodes; theta is the object's. */
+ *                   without strength, and on the coarsest level: NULL arrays, every block strong, 0 nodes; theta is the object's.
+ *
+ * The cycle (every object starts with DXO_AMG_CYCLE_V):
+ * dxo_amg_set_cycle : DXO_AMG_CYCLE_V or DXO_AMG_CYCLE_K, on any hierarchy and relaxation; it takes effect at once, without a setup.
+ *                   K-cycle: level 0 runs one cycle body B_0 (pre-smoothing, restriction, coarse solve, prolongation,
+ *                   post-smoothing), the coarsest level keeps its dense solve, and on every level l between them A_l x = r is
+ *                   solved by exactly two GCR steps preconditioned by B_l: c1 = B_l(r), v1 = A_l c1, rho1 = (v1, v1), a1 = (v1, r),
+ *                   r1 = r - (a1 / rho1) v1, c2 = B_l(r1), v2 = A_l c2, g = (v2, v1), beta = (v2, v2), a2 = (v2, r1),
+ *                   rho2 = beta - g g / rho1, x = (a1 / rho1 - g a2 / (rho1 rho2)) c1 + (a2 / rho2) c2. rho1 == 0: x = 0; rho2 not
+ *                   finite or <= 1e-14 beta: x = (a1 / rho1) c1. Both steps always run (no early exit after the first), the
+ *                   coefficients stay on the device: dxo_amg_apply remains capture-safe, allocation-free and bit-reproducible, but
+ *                   is no longer a linear operator, so dxo_krylov_gmres / dxo_krylov_cg refuse the object (DXO_E_OPTION) and
+ *                   dxo_krylov_fgmres takes it. With at most two levels K is V bit for bit. The first DXO_AMG_CYCLE_K allocates
+ *                   five vectors per intermediate level. An unknown kind: DXO_E_OPTION, nothing changes.
+ * dxo_amg_cycle_info : the kind, and the level visits of one apply: the levels for V; for K 2^l per level l but the coarsest, which
+ *                   is visited as often as the level above it. Any pointer may be NULL. */
 #define DXO_AMG_SMOOTH_JACOBI 0
 #define DXO_AMG_SMOOTH_CHEBYSHEV 1
 #define DXO_AMG_RHO_INF_NORM 0
 #define DXO_AMG_RHO_POWER 1
+#define DXO_AMG_CYCLE_V 0
+#define DXO_AMG_CYCLE_K 1
 typedef struct dxo_amg dxo_amg;
 typedef struct dxo_amg_level_info {
     int64_t n_rows, n_nodes;       /* of A_l                                              */
@@ -767,6 +800,8 @@ int dxo_amg_create_soc(dxo_ctx* ctx, const dxo_csr* csr, const double* values, c
                        const double* B, int n_modes, double theta, int max_levels, int coarse_rows, int sweeps, dxo_amg** out);
 int dxo_amg_soc_info(dxo_ctx* ctx, const dxo_amg* amg, int level, double* theta, const uint8_t** strong, int64_t* n_strong_blocks,
                      int64_t* n_unlumped_nodes, const double** dinv_f, const double** omega_f);
+int dxo_amg_set_cycle(dxo_ctx* ctx, dxo_amg* amg, int kind);
+int dxo_amg_cycle_info(dxo_ctx* ctx, const dxo_amg* amg, int* kind, int64_t* visits);
 
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is

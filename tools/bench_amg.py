@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Standalone timing of the multigrid preconditioner (csrc/amg.hip; not a bench.py leg).
-    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG] [--strength THETA[,THETA...]]
+    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG] [--strength THETA[,THETA...]] [--cycle K]
 Systems (distorted meshes, the lower side clamped so that the matrices are regular):
   p2       ("grad", "grad", 2) on P2 triangles with C = I + 0.3 N(0, 1) per point (1291 per side: 10^7 points), as tools/bench_krylov.py
   q2hex    ("eps", "eps", 3) on Q2 hexahedra (40^3 boxes), the same kind of C
@@ -18,6 +18,9 @@ same run, beside the default's (|Dinv A|_inf, damped Jacobi): power_jacobi (rho 
 coarsening and filtered prolongator smoothing (keys ending in _soc<THETA>): creation ms (it includes the numeric phase of every level),
 rows per level, operator complexity, setup ms, apply ms, the nodes that fell back to A_ii, and the GMRES(30) solve; with --cheby DEG the
 solve is repeated with power_cheby<DEG> on that hierarchy.
+--cycle K adds, for every hierarchy and relaxation measured without --strength (the default's, those of --rbm and of --cheby), the
+K-cycle on the same object in the same run (key "kcycle" inside the figures of the V-cycle / GMRES(30) line): apply ms, the level visits
+of one apply, and one FGMRES(30) solve to rtol 1e-8 (iterations, ms; the setup is the V-cycle's).
 Timing: warm-up, then 5 batches timed with HIP events on the launch stream, the MEDIAN batch reported (tools/bench_krylov._batches).
 Prints one JSON line."""
 from __future__ import annotations
@@ -32,11 +35,11 @@ if str(ROOT) not in sys.path:
 
 
 def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000, rbm: bool = False,
-         cheby: int = 0, strengths: tuple = ()) -> dict:
+         cheby: int = 0, strengths: tuple = (), cycle: str = "V") -> dict:
     import numpy as np
     import torch
 
-    from dolfinx_external_operator_amd import Context, DeviceMesh, gmres, rigid_body_modes
+    from dolfinx_external_operator_amd import Context, DeviceMesh, fgmres, gmres, rigid_body_modes
     from tools.bench_krylov import _batches
     from tools.synthetic import structured_mesh
 
@@ -53,6 +56,17 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
         ms, _ = _batches(torch, stream, fn, per_batch=per_batch, warm=2)
         return round(ms, 4)
 
+    def kcycle(amg, A, b, x, y, setup_ms):
+        """The K-cycle of the hierarchy as it stands, under FGMRES(30); the object is a V-cycle again afterwards."""
+        amg.set_cycle("K")
+        f = {"apply_ms": timed(lambda: amg.apply(x, y), 20), "visits": amg.visits}
+        fgmres(A, b, M=amg, rtol=1e-8, maxiter=30)                           # warm-up (and the second basis)
+        out = fgmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
+        f.update({"iterations": out.iterations, "converged": out.converged, "residual": out.residual, "ms": round(out.ms, 2),
+                  "ms_with_setup": round(out.ms + setup_ms, 2)})
+        amg.set_cycle("V")
+        return f
+
     def relaxations(amg, A, b, x, y, r, suffix):
         for key, kw in (("power_jacobi", {"rho": "power"}), (f"power_cheby{cheby}", {"smoother": "chebyshev", "degree": cheby, "rho": "power"})):
             amg.set_smoother(**kw).setup()
@@ -61,6 +75,8 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
             out = gmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
             f.update({"iterations": out.iterations, "converged": out.converged, "residual": out.residual, "ms": round(out.ms, 2),
                       "ms_with_setup": round(out.ms + f["setup_ms"], 2)})
+            if cycle == "K":
+                f["kcycle"] = kcycle(amg, A, b, x, y, f["setup_ms"])
             r[key + suffix] = f
 
     def with_strength(A, bcs, nns, b, x, y, r, suffix):
@@ -108,6 +124,8 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                     r[f"gmres30_{name}"] = {"iterations": out.iterations, "converged": out.converged, "residual": out.residual,
                                             "ms": round(out.ms, 2)}
                 r["gmres30_amg"]["ms_with_setup"] = round(r["gmres30_amg"]["ms"] + r["setup_ms"], 2)
+                if cycle == "K":
+                    r["gmres30_amg"]["kcycle"] = kcycle(amg, A, b, x, y, r["setup_ms"])
                 if cheby:
                     relaxations(amg, A, b, x, y, r, "")
                 amg.close()
@@ -124,6 +142,8 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                     out = gmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
                     r["gmres30_amg_rbm"] = {"iterations": out.iterations, "converged": out.converged, "residual": out.residual,
                                             "ms": round(out.ms, 2), "ms_with_setup": round(out.ms + r["setup_ms_rbm"], 2)}
+                    if cycle == "K":
+                        r["gmres30_amg_rbm"]["kcycle"] = kcycle(amg, A, b, x, y, r["setup_ms_rbm"])
                     if cheby:
                         relaxations(amg, A, b, x, y, r, "_rbm")
                     amg.close()
@@ -189,7 +209,12 @@ if __name__ == "__main__":
         i = args.index("--strength")
         strengths = tuple(float(t) for t in args[i + 1].split(","))
         del args[i:i + 2]
-    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby, strengths=strengths)
+    cycle = "V"
+    if "--cycle" in args:
+        i = args.index("--cycle")
+        cycle = args[i + 1]
+        del args[i:i + 2]
+    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby, strengths=strengths, cycle=cycle)
     line = json.dumps(r)
     print(line)
     if out_file:
