@@ -219,6 +219,8 @@ _SIGNATURES = {
                                     C.POINTER(KrylovInfo)]),
     "dxo_amg_set_cycle": (C.c_int, [_P, _P, C.c_int]),
     "dxo_amg_cycle_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "dxo_amg_set_precision": (C.c_int, [_P, _P, C.c_int]),
+    "dxo_amg_precision_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "dxo_mesh_set_facet_geometry": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "dxo_facet_set_create": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "dxo_facet_set_destroy": (C.c_int, [_P, _P]),

@@ -62,6 +62,15 @@
 // bit-reproducible. The two calls of B_l share xa, xb, t, d of the level and everything below it, so B_l writes its result straight
 // into c1 (then c2) of the level's K vectors, which nothing else touches. Level 0 runs B_0 alone: the Krylov method is its acceleration.
 //
+// Single precision (dxo_amg_set_precision with DXO_AMG_PRECISION_FP32). The numeric phase above stays double to its end; a setup then
+// casts the values, Dinv and P of every level but the coarsest to float (amg_narrow, one launch per array, before the one wait; a
+// finite entry that overflows raises flag[2]). The kernels of the cycle take their scalar as a template parameter, and so does
+// row_product: the float cycle is the launch sequence of the V-cycle on the copies (level_view picks the arrays), with float
+// vectors and v_fma_f32 in the same order. omega and the Chebyshev pairs are read as double and narrowed in the kernel, and the dense
+// inverse of the coarsest level stays double (amg_dense_apply widens its right-hand side). r and z stay double: one amg_narrow of r
+// on entry (12 B per row, repaid by the 2 nu + 1 kernels of level 0 that then read 4 B of r per row instead of 8), and the last
+// post-sweep of level 0 writes z in double (its TO). The K-cycle stays double: the two settings exclude each other.
+//
 // Host side. Run-time shapes reach the templates through one dispatcher (with_int / with_pairs and their named lists: with_bs,
 // with_level, with_pair, with_square, with_nns_pair), so a kernel's argument list is written once. amg_build allocates the device scalars
 // of every level once, before the level loop, and walks read pattern -> [strength mask] -> aggregates -> transfer tables -> coarse
@@ -127,6 +136,28 @@ struct amg_level {
     double* dinv_f = nullptr;          // [n_nodes][bs][bs] their inverses (A_ii's after a failed test; zero: the node is not smoothed)
     uint8_t* unlumped = nullptr;       // [n_nodes] 1: the lumped block failed the test
     int64_t n_strong = 0;              // strong blocks (host)
+    // single precision (dxo_amg_set_precision): the copies a setup casts (absent on the coarsest level) and the cycle's vectors
+    float *values32 = nullptr, *dinv32 = nullptr, *p_val32 = nullptr;
+    float *r32 = nullptr, *xa32 = nullptr, *xb32 = nullptr, *t32 = nullptr, *d32 = nullptr;
+};
+
+// what the cycle reads and writes on a level, in the scalar T of the cycle
+template <class T>
+struct level_view;
+
+template <>
+struct level_view<double> {
+    const double *values, *dinv, *p_val;
+    double *r, *xa, *xb, *t, *d;
+    explicit level_view(const amg_level& v) : values(v.values), dinv(v.dinv), p_val(v.p_val), r(v.r), xa(v.xa), xb(v.xb), t(v.t), d(v.d) {}
+};
+
+template <>
+struct level_view<float> {
+    const float *values, *dinv, *p_val;
+    float *r, *xa, *xb, *t, *d;
+    explicit level_view(const amg_level& v)
+        : values(v.values32), dinv(v.dinv32), p_val(v.p_val32), r(v.r32), xa(v.xa32), xb(v.xb32), t(v.t32), d(v.d32) {}
 };
 
 }  // namespace
@@ -138,7 +169,7 @@ struct dxo_amg {
     double* omega = nullptr;           // [levels]
     double* part = nullptr;            // partial maxima of the rho pass
     int64_t part_cap = 0;
-    int* flag = nullptr;               // [0] singular diagonal block, [1] zero pivot
+    int* flag = nullptr;               // [0] singular diagonal block, [1] zero pivot, [2] 1 + the first level a cast overflowed on
     double* dense[2] = {nullptr, nullptr};   // [nc][2 nc] each: [W | B], B ends as the inverse
     int64_t nc = 0;                    // rows of the coarsest level
     bool ready = false;
@@ -156,6 +187,8 @@ struct dxo_amg {
     double* rho_f = nullptr;           // [levels] the estimate of Dinv_F A^F it was made from
     double* cheb_f = nullptr;          // [AMG_CHEB_STRIDE] where amg_power_norm leaves the pairs of rho_F: not used
     int cycle = DXO_AMG_CYCLE_V;       // dxo_amg_set_cycle
+    int precision = DXO_AMG_PRECISION_FP64;      // dxo_amg_set_precision
+    int64_t fp32_bytes = 0;            // of the single-precision copies and vectors; 0: never allocated
 };
 
 namespace {
@@ -616,6 +649,10 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_lump(int64_t n_nodes, const
 #pragma unroll
             for (int j = 0; j < BS; ++j) a[i][j] += values[R.r0 + i * R.len + (int64_t)k * BS + j];
     }
+#pragma unroll
+    for (int i = 0; i < BS; ++i)      // stored before the inversion, which then holds the scaled block alone
+#pragma unroll
+        for (int j = 0; j < BS; ++j) diag_f[node * BS * BS + i * BS + j] = a[i][j];
     double b[BS][BS];
     const bool ok = invert_block<BS>(a, b);
 #pragma unroll
@@ -623,7 +660,6 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_lump(int64_t n_nodes, const
 #pragma unroll
         for (int j = 0; j < BS; ++j) {
             const int64_t o = node * BS * BS + i * BS + j;
-            diag_f[o] = a[i][j];
             dinv_f[o] = n_strong == 0 ? 0.0 : (ok ? b[i][j] : dinv[o]);
         }
     unlumped[node] = n_strong > 0 && !ok ? 1 : 0;
@@ -803,39 +839,59 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_dense_step(int64_t n, int64
     }
 }
 
-// x = B r with B the right half of W: one wave per row
-__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_dense_apply(int64_t n, const double* __restrict__ W, const double* __restrict__ r,
-                                                                 double* __restrict__ x) {
+// x = B r with B the right half of W: one wave per row. B and the sums are double under either precision of the cycle: a float r is
+// widened entry by entry and the result narrowed once
+template <class T>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_dense_apply(int64_t n, const double* __restrict__ W, const T* __restrict__ r,
+                                                                 T* __restrict__ x) {
     const int64_t row = (int64_t)blockIdx.x * (DXO_AMG_BLOCK / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     double s = 0.0;
     if (row < n) {
         const double* b = W + row * 2 * n + n;
-        for (int64_t c = lane; c < n; c += 64) s = fma(b[c], r[c], s);
+        for (int64_t c = lane; c < n; c += 64) s = fma(b[c], (double)r[c], s);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if (row < n && lane == 0) x[row] = s;
+    if (row < n && lane == 0) x[row] = (T)s;
+}
+
+// out = (float) in, entry by entry (grid-stride). With a flag (the copies of a setup): a finite double that leaves the range of
+// float stores `mark` there unless an earlier level already has (every thread of a launch stores the same word, and the launches of
+// the levels follow each other on the stream: no atomics). Underflow to zero is not an error. Without one: the right-hand side of a cycle
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_narrow(int64_t n, const double* __restrict__ in, float* __restrict__ out, int* flag, int mark) {
+    const int64_t stride = (int64_t)gridDim.x * DXO_AMG_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double v = in[i];
+        const float f = (float)v;
+        out[i] = f;
+        if (flag && std::isfinite(v) && !std::isfinite(f) && flag[2] == 0) flag[2] = mark;
+    }
 }
 
 // ---- the cycle
+// The kernels of the cycle take the scalar T of the level's matrix, inverses, prolongator and vectors: double, or float for the
+// single-precision cycle (dxo_amg_set_precision), where every fma below is v_fma_f32 in the same order. omega and the Chebyshev
+// pairs stay double on the device and are narrowed here. TO, the scalar of a sweep's result, differs from T in one place: the last
+// post-sweep of level 0 of the float cycle writes the caller's double z.
+//
 // x = scale[0] Dinv r, and d = x if d is given: the first step of a smoother from x = 0 (no SpMV). Jacobi: scale is omega; Chebyshev:
 // the c2 of the first pair, and d the direction
-template <int BS>
-__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_first_step(int64_t n_nodes, const double* __restrict__ dinv, const double* __restrict__ scale,
-                                                                const double* __restrict__ r, double* __restrict__ d, double* __restrict__ x) {
+template <int BS, class T>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_first_step(int64_t n_nodes, const T* __restrict__ dinv, const double* __restrict__ scale,
+                                                                const T* __restrict__ r, T* __restrict__ d, T* __restrict__ x) {
     const int64_t node = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
     if (node >= n_nodes) return;
-    const double sc = scale[0];
-    double rb[BS];
+    const T sc = (T)scale[0];
+    T rb[BS];
 #pragma unroll
     for (int j = 0; j < BS; ++j) rb[j] = r[node * BS + j];
 #pragma unroll
     for (int i = 0; i < BS; ++i) {
-        double s = 0.0;
+        T s = 0.0;
 #pragma unroll
         for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], rb[j], s);
-        const double v = sc * s;
+        const T v = sc * s;
         if (d) d[node * BS + i] = v;
         x[node * BS + i] = v;
     }
@@ -843,31 +899,31 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_first_step(int64_t n_nodes,
 
 // RESID: out = r - A x; otherwise out = x + omega Dinv (r - A x). LW lanes own a node (A x by row_product). out may be r: a node's
 // entries of r are read by its own lane 0 only, before it writes.
-template <int BS, int LW, bool RESID>
+template <int BS, int LW, bool RESID, class T, class TO>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_sweep(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                                           const double* __restrict__ values, const double* __restrict__ dinv,
-                                                           const double* __restrict__ omega, const double* r, const double* __restrict__ x,
-                                                           double* out) {
+                                                           const T* __restrict__ values, const T* __restrict__ dinv,
+                                                           const double* __restrict__ omega, const T* r, const T* __restrict__ x,
+                                                           TO* out) {
     constexpr int NPB = DXO_AMG_BLOCK / LW;
     const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
     const int lane = threadIdx.x % LW;
-    double acc[BS];
+    T acc[BS];
     row_product<BS, LW>(n_nodes, node, lane, row_ptr, col, values, x, acc);
     if (node < n_nodes && lane == 0) {
-        double d[BS];
+        T d[BS];
 #pragma unroll
         for (int i = 0; i < BS; ++i) d[i] = r[node * BS + i] - acc[i];
         if constexpr (RESID) {
 #pragma unroll
-            for (int i = 0; i < BS; ++i) out[node * BS + i] = d[i];
+            for (int i = 0; i < BS; ++i) out[node * BS + i] = (TO)d[i];
         } else {
-            const double om = omega[0];
+            const T om = (T)omega[0];
 #pragma unroll
             for (int i = 0; i < BS; ++i) {
-                double s = 0.0;
+                T s = 0.0;
 #pragma unroll
                 for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], d[j], s);
-                out[node * BS + i] = fma(om, s, x[node * BS + i]);
+                out[node * BS + i] = (TO)fma(om, s, x[node * BS + i]);
             }
         }
     }
@@ -876,41 +932,41 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_sweep(int64_t n_nodes, cons
 // d = c1 d + c2 Dinv (r - A x), out = x + d with (c1, c2) = c[0..1], A x by row_product as in amg_sweep. d is updated in place: a
 // node's entries are touched by its own lane 0 only. With c1 == 0 (the first step of the post-smoothing) d is not read. out may be r,
 // as in amg_sweep.
-template <int BS, int LW>
+template <int BS, int LW, class T, class TO>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_cheby_sweep(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                                                 const double* __restrict__ values, const double* __restrict__ dinv,
-                                                                 const double* __restrict__ c, const double* r, const double* __restrict__ x,
-                                                                 double* __restrict__ d, double* out) {
+                                                                 const T* __restrict__ values, const T* __restrict__ dinv,
+                                                                 const double* __restrict__ c, const T* r, const T* __restrict__ x,
+                                                                 T* __restrict__ d, TO* out) {
     constexpr int NPB = DXO_AMG_BLOCK / LW;
     const int64_t node = (int64_t)blockIdx.x * NPB + threadIdx.x / LW;
     const int lane = threadIdx.x % LW;
-    double acc[BS];
+    T acc[BS];
     row_product<BS, LW>(n_nodes, node, lane, row_ptr, col, values, x, acc);
     if (node < n_nodes && lane == 0) {
-        const double c1 = c[0], c2 = c[1];
-        double res[BS];
+        const T c1 = (T)c[0], c2 = (T)c[1];
+        T res[BS];
 #pragma unroll
         for (int i = 0; i < BS; ++i) res[i] = r[node * BS + i] - acc[i];
 #pragma unroll
         for (int i = 0; i < BS; ++i) {
-            double s = 0.0;
+            T s = 0.0;
 #pragma unroll
             for (int j = 0; j < BS; ++j) s = fma(dinv[node * BS * BS + i * BS + j], res[j], s);
-            const double dn = fma(c2, s, c1 != 0.0 ? c1 * d[node * BS + i] : 0.0);
+            const T dn = fma(c2, s, c1 != T(0) ? c1 * d[node * BS + i] : T(0));
             d[node * BS + i] = dn;
-            out[node * BS + i] = x[node * BS + i] + dn;
+            out[node * BS + i] = (TO)(x[node * BS + i] + dn);
         }
     }
 }
 
 // r_c[a] = sum over the blocks (i, a) of P, ascending i, of P_ia^T t_i
-template <int BSR, int BSC>
+template <int BSR, int BSC, class T>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_restrict(int64_t n_agg, const int64_t* __restrict__ pt_ptr, const int64_t* __restrict__ pt_blk,
-                                                              const int32_t* __restrict__ p_row, const double* __restrict__ p_val,
-                                                              const double* __restrict__ t, double* __restrict__ rc) {
+                                                              const int32_t* __restrict__ p_row, const T* __restrict__ p_val,
+                                                              const T* __restrict__ t, T* __restrict__ rc) {
     const int64_t a = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
     if (a >= n_agg) return;
-    double acc[BSC];
+    T acc[BSC];
 #pragma unroll
     for (int c = 0; c < BSC; ++c) acc[c] = 0.0;
     for (int64_t e = pt_ptr[a]; e < pt_ptr[a + 1]; ++e) {
@@ -918,7 +974,7 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_restrict(int64_t n_agg, con
         const int64_t i = p_row[pb];
 #pragma unroll
         for (int q = 0; q < BSR; ++q) {
-            const double tv = t[i * BSR + q];
+            const T tv = t[i * BSR + q];
 #pragma unroll
             for (int c = 0; c < BSC; ++c) acc[c] = fma(p_val[pb * BSR * BSC + q * BSC + c], tv, acc[c]);
         }
@@ -928,19 +984,19 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_restrict(int64_t n_agg, con
 }
 
 // x_i += sum over the blocks of row i of P, ascending aggregate, of P_ia xc_a
-template <int BSR, int BSC>
+template <int BSR, int BSC, class T>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_prolong(int64_t n_nodes, const int64_t* __restrict__ p_ptr, const int32_t* __restrict__ p_col,
-                                                             const double* __restrict__ p_val, const double* __restrict__ xc, double* __restrict__ x) {
+                                                             const T* __restrict__ p_val, const T* __restrict__ xc, T* __restrict__ x) {
     const int64_t i = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
     if (i >= n_nodes) return;
-    double acc[BSR];
+    T acc[BSR];
 #pragma unroll
     for (int r = 0; r < BSR; ++r) acc[r] = 0.0;
     for (int64_t e = p_ptr[i]; e < p_ptr[i + 1]; ++e) {
         const int64_t a = p_col[e];
 #pragma unroll
         for (int c = 0; c < BSC; ++c) {
-            const double v = xc[a * BSC + c];
+            const T v = xc[a * BSC + c];
 #pragma unroll
             for (int r = 0; r < BSR; ++r) acc[r] = fma(p_val[e * BSR * BSC + r * BSC + c], v, acc[r]);
         }
@@ -1086,16 +1142,21 @@ void with_level(const amg_level& v, F&& f) {
     with_bs(v.bs, [&](auto BS) { with_int<8, 32>(v.lw, [&](auto LW) { f(BS, LW); }); });
 }
 
-template <bool RESID>
-void sweep(const amg_level& v, const double* omega, const double* r, const double* x, double* out, hipStream_t s) {
+template <bool RESID, class T, class TO>
+void sweep(const amg_level& v, const double* omega, const T* r, const T* x, TO* out, hipStream_t s) {
+    const level_view<T> w(v);
     with_level(v, [&](auto BS, auto LW) {
-        amg_launch(amg_sweep<BS, LW, RESID>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, omega, r, x, out);
+        amg_launch(amg_sweep<BS, LW, RESID, T, TO>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, w.values, w.dinv, omega, r, x,
+                   out);
     });
 }
 
-void cheby_step(const amg_level& v, const double* c, const double* r, const double* x, double* out, hipStream_t s) {
+template <class T, class TO>
+void cheby_step(const amg_level& v, const double* c, const T* r, const T* x, TO* out, hipStream_t s) {
+    const level_view<T> w(v);
     with_level(v, [&](auto BS, auto LW) {
-        amg_launch(amg_cheby_sweep<BS, LW>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.dinv, c, r, x, v.d, out);
+        amg_launch(amg_cheby_sweep<BS, LW, T, TO>, v.n_nodes, DXO_AMG_BLOCK / LW, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, w.values, w.dinv, c, r, x, w.d,
+                   out);
     });
 }
 
@@ -1652,68 +1713,85 @@ struct CycleRun {
     int nl, nu;                        // levels; sweeps or the Chebyshev degree
 };
 
-const double* amg_solve_level(const CycleRun& C, int l, const double* rin);
+template <class T>
+const T* amg_solve_level(const CycleRun& C, int l, const T* rin);
 
-// the cycle body of level l: B_l(rin). The result lies in `out` if one is given (the last sweep of the post-smoothing writes it
-// there), in xa or xb of the level otherwise; the coarsest level is the dense product into xa
-const double* amg_body(const CycleRun& C, int l, const double* rin, double* out) {
+// the cycle body of level l in the scalar T: B_l(rin). The result lies in `out` (always double: the caller's z, or a K vector) if one
+// is given, and nothing is returned then: the last sweep of the post-smoothing writes it there. Otherwise it lies in xa or xb of the
+// level; the coarsest level is the dense product into xa
+template <class T>
+const T* amg_body(const CycleRun& C, int l, const T* rin, double* out) {
     dxo_amg* amg = C.amg;
     const hipStream_t s = C.s;
     amg_level& v = amg->L[(size_t)l];
+    const level_view<T> w(v);
     if (l == C.nl - 1) {
         const double* W = amg->dense[amg->nc % 2];
-        hipLaunchKernelGGL(amg_dense_apply, amg_grid(amg->nc, DXO_AMG_BLOCK / 64), dim3(DXO_AMG_BLOCK), 0, s, amg->nc, W, rin, v.xa);
-        return v.xa;
+        hipLaunchKernelGGL(amg_dense_apply<T>, amg_grid(amg->nc, DXO_AMG_BLOCK / 64), dim3(DXO_AMG_BLOCK), 0, s, amg->nc, W, rin, w.xa);
+        return w.xa;
     }
     const double* om = amg->omega + l;
     const double* ch = amg->cheb + (size_t)l * AMG_CHEB_STRIDE;
-    double *cur = v.xa, *other = v.xb;
+    T *cur = w.xa, *other = w.xb;
     with_bs(v.bs, [&](auto BS) {      // from x = 0: omega Dinv r, or c2 Dinv r into the direction as well
-        amg_launch(amg_first_step<BS>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.dinv, C.cheby ? ch + 1 : om, rin, C.cheby ? v.d : nullptr, cur);
+        amg_launch(amg_first_step<BS, T>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, w.dinv, C.cheby ? ch + 1 : om, rin, C.cheby ? w.d : (T*)nullptr, cur);
     });
     for (int k = 1; k < C.nu; ++k) {
-        if (C.cheby) cheby_step(v, ch + 2 * k, rin, cur, other, s);
-        else sweep<false>(v, om, rin, cur, other, s);
+        if (C.cheby) cheby_step(v, ch + 2 * k, rin, (const T*)cur, other, s);
+        else sweep<false>(v, om, rin, (const T*)cur, other, s);
         std::swap(cur, other);
     }
-    sweep<true>(v, om, rin, cur, v.t, s);
+    sweep<true>(v, om, rin, (const T*)cur, w.t, s);
+    const level_view<T> wc(amg->L[(size_t)l + 1]);
     with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
-        amg_launch(amg_restrict<BSR, BSC>, v.n_agg, DXO_AMG_BLOCK, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, v.p_val, v.t, amg->L[(size_t)l + 1].r);
+        amg_launch(amg_restrict<BSR, BSC, T>, v.n_agg, DXO_AMG_BLOCK, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, w.p_val, (const T*)w.t, wc.r);
     });
-    const double* xc = amg_solve_level(C, l + 1, amg->L[(size_t)l + 1].r);
+    const T* xc = amg_solve_level<T>(C, l + 1, wc.r);
     with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
-        amg_launch(amg_prolong<BSR, BSC>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.p_ptr, v.p_col, v.p_val, xc, cur);
+        amg_launch(amg_prolong<BSR, BSC, T>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.p_ptr, v.p_col, w.p_val, xc, cur);
     });
     for (int k = 0; k < C.nu; ++k) {
-        double* to = (out && k == C.nu - 1) ? out : other;      // the last sweep writes the result where the caller wants it
-        if (C.cheby) cheby_step(v, ch + 2 * k, rin, cur, to, s);
-        else sweep<false>(v, om, rin, cur, to, s);
-        other = cur;
-        cur = to;
+        if (out && k == C.nu - 1) {      // the last sweep writes the result where the caller wants it
+            if (C.cheby) cheby_step(v, ch + 2 * k, rin, (const T*)cur, out, s);
+            else sweep<false>(v, om, rin, (const T*)cur, out, s);
+            return nullptr;
+        }
+        if (C.cheby) cheby_step(v, ch + 2 * k, rin, (const T*)cur, other, s);
+        else sweep<false>(v, om, rin, (const T*)cur, other, s);
+        std::swap(cur, other);
     }
     return cur;
 }
 
 // the solution of A_l x = rin the level above prolongs. V-cycle, and the coarsest level of either cycle: the body, once. K-cycle on
-// an intermediate level: two GCR steps preconditioned by the body
-const double* amg_solve_level(const CycleRun& C, int l, const double* rin) {
+// an intermediate level (double only: dxo_amg_set_cycle and dxo_amg_set_precision exclude each other): two GCR steps preconditioned
+// by the body
+template <class T>
+const T* amg_solve_level(const CycleRun& C, int l, const T* rin) {
     dxo_amg* amg = C.amg;
-    const hipStream_t s = C.s;
-    if (amg->cycle != DXO_AMG_CYCLE_K || l == C.nl - 1) return amg_body(C, l, rin, nullptr);
-    amg_level& v = amg->L[(size_t)l];
-    const dim3 G((unsigned)v.knb), B(DXO_AMG_BLOCK), One(1);
-    amg_body(C, l, rin, v.kc1);
-    (void)dxo_kr_spmv_launch(C.ctx, v.A, v.values, v.kc1, v.kv1, s);      // a level has block size 1, 2, 3 or 6
-    hipLaunchKernelGGL(amg_k_dots, G, B, 0, s, v.n_rows, v.kv1, rin, (const double*)nullptr, v.kpart);
-    hipLaunchKernelGGL(amg_k_scalar, One, B, 0, s, v.kpart, v.knb, 1, v.kco);
-    hipLaunchKernelGGL(amg_k_residual, G, B, 0, s, v.n_rows, v.kco, rin, v.kv1, v.kr1);
-    amg_body(C, l, v.kr1, v.kc2);      // reuses xa, xb, t, d of this level and everything below: c1 and v1 are safe in the K vectors
-    (void)dxo_kr_spmv_launch(C.ctx, v.A, v.values, v.kc2, v.kv2, s);
-    hipLaunchKernelGGL(amg_k_dots, G, B, 0, s, v.n_rows, v.kv2, v.kv1, v.kr1, v.kpart);
-    hipLaunchKernelGGL(amg_k_scalar, One, B, 0, s, v.kpart, v.knb, 2, v.kco);
-    hipLaunchKernelGGL(amg_k_combine, G, B, 0, s, v.n_rows, v.kco, v.kc1, v.kc2);
-    return v.kc1;
+    if (amg->cycle != DXO_AMG_CYCLE_K || l == C.nl - 1) return amg_body<T>(C, l, rin, nullptr);
+    if constexpr (std::is_same_v<T, double>) {
+        const hipStream_t s = C.s;
+        amg_level& v = amg->L[(size_t)l];
+        const dim3 G((unsigned)v.knb), B(DXO_AMG_BLOCK), One(1);
+        amg_body<double>(C, l, rin, v.kc1);
+        (void)dxo_kr_spmv_launch(C.ctx, v.A, v.values, v.kc1, v.kv1, s);      // a level has block size 1, 2, 3 or 6
+        hipLaunchKernelGGL(amg_k_dots, G, B, 0, s, v.n_rows, v.kv1, rin, (const double*)nullptr, v.kpart);
+        hipLaunchKernelGGL(amg_k_scalar, One, B, 0, s, v.kpart, v.knb, 1, v.kco);
+        hipLaunchKernelGGL(amg_k_residual, G, B, 0, s, v.n_rows, v.kco, rin, v.kv1, v.kr1);
+        amg_body<double>(C, l, v.kr1, v.kc2);      // reuses xa, xb, t, d of this level and everything below: c1 and v1 are safe in the K vectors
+        (void)dxo_kr_spmv_launch(C.ctx, v.A, v.values, v.kc2, v.kv2, s);
+        hipLaunchKernelGGL(amg_k_dots, G, B, 0, s, v.n_rows, v.kv2, v.kv1, v.kr1, v.kpart);
+        hipLaunchKernelGGL(amg_k_scalar, One, B, 0, s, v.kpart, v.knb, 2, v.kco);
+        hipLaunchKernelGGL(amg_k_combine, G, B, 0, s, v.n_rows, v.kco, v.kc1, v.kc2);
+        return v.kc1;
+    } else {
+        amg_no_shape(-1, -1);      // unreachable: a float cycle is a V-cycle
+    }
 }
+
+// the grid of amg_narrow: one thread per entry up to a cap, the stride of the loop beyond it
+dim3 narrow_grid(int64_t n) { return dim3((unsigned)std::min<int64_t>(1 << 16, std::max<int64_t>(1, (n + DXO_AMG_BLOCK - 1) / DXO_AMG_BLOCK))); }
 
 }  // namespace
 
@@ -1723,12 +1801,18 @@ void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipSt
     const bool cheby = amg->smooth_kind == DXO_AMG_SMOOTH_CHEBYSHEV;
     const CycleRun C{ctx, amg, s, cheby, (int)amg->L.size(), cheby ? amg->degree : amg->sweeps};
     if (amg->L[0].n_rows == 0) return;
-    if (C.nl == 1) {
-        const double* x = amg_body(C, 0, r, nullptr);
+    if (C.nl == 1) {                 // one dense product, in double under either precision
+        const double* x = amg_body<double>(C, 0, r, nullptr);
         (void)hipMemcpyAsync(z, x, (size_t)amg->L[0].n_rows * sizeof(double), hipMemcpyDeviceToDevice, s);
         return;
     }
-    amg_body(C, 0, r, z);      // level 0 is one body in either cycle: the Krylov method outside is its acceleration
+    if (amg->precision == DXO_AMG_PRECISION_FP32) {      // the V-cycle in float: r is narrowed once (so r may be z), the last sweep writes z
+        const amg_level& v = amg->L[0];
+        hipLaunchKernelGGL(amg_narrow, narrow_grid(v.n_rows), dim3(DXO_AMG_BLOCK), 0, s, v.n_rows, r, v.r32, (int*)nullptr, 0);
+        amg_body<float>(C, 0, v.r32, z);
+        return;
+    }
+    amg_body<double>(C, 0, r, z);      // level 0 is one body in either cycle: the Krylov method outside is its acceleration
 }
 
 // ---- C ABI
@@ -1901,6 +1985,8 @@ extern "C" int dxo_amg_set_cycle(dxo_ctx* ctx, dxo_amg* amg, int kind) {
     DXO_LOCK(ctx);
     if (!amg) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_set_cycle: NULL argument");
     if (kind != DXO_AMG_CYCLE_V && kind != DXO_AMG_CYCLE_K) return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_set_cycle: unknown cycle");
+    if (kind == DXO_AMG_CYCLE_K && amg->precision == DXO_AMG_PRECISION_FP32)
+        return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_set_cycle: the K-cycle runs in double only (dxo_amg_set_precision selected DXO_AMG_PRECISION_FP32)");
     if (kind == DXO_AMG_CYCLE_K) {      // the K vectors of the intermediate levels, once; dxo_amg_apply stays allocation-free
         DXO_HIP(ctx, hipSetDevice(amg->device));
         Uploader U{ctx, amg, "dxo_amg_set_cycle"};
@@ -1936,6 +2022,51 @@ extern "C" int dxo_amg_cycle_info(dxo_ctx* ctx, const dxo_amg* amg, int* kind, i
             *visits += (int64_t)1 << (nl - 2);
         }
     }
+    return DXO_OK;
+}
+
+extern "C" int dxo_amg_set_precision(dxo_ctx* ctx, dxo_amg* amg, int kind) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!amg) return dxo_fail(ctx, DXO_E_NULL, "dxo_amg_set_precision: NULL argument");
+    if (kind != DXO_AMG_PRECISION_FP64 && kind != DXO_AMG_PRECISION_FP32) return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_set_precision: unknown precision");
+    if (kind == amg->precision) return DXO_OK;
+    if (kind == DXO_AMG_PRECISION_FP32 && amg->cycle == DXO_AMG_CYCLE_K)
+        return dxo_fail(ctx, DXO_E_OPTION, "dxo_amg_set_precision: single precision runs the V-cycle only (dxo_amg_set_cycle selected DXO_AMG_CYCLE_K)");
+    const size_t nl = amg->L.size();
+    if (kind == DXO_AMG_PRECISION_FP32 && amg->fp32_bytes == 0 && nl > 1) {      // the copies and the vectors, once; one level: a dense product
+        DXO_HIP(ctx, hipSetDevice(amg->device));
+        Uploader U{ctx, amg, "dxo_amg_set_precision"};
+        int64_t entries = 0;
+        for (size_t l = 0; l < nl; ++l) {
+            amg_level& v = amg->L[l];
+            const bool last = l + 1 == nl;
+            const int64_t nv = last ? 0 : v.A->nnz, nd = last ? 0 : v.n_nodes * v.bs * v.bs, np = last ? 0 : v.p_blocks * v.bs * v.bsc;
+            v.r32 = U.alloc<float>((size_t)v.n_rows);
+            v.xa32 = U.alloc<float>((size_t)v.n_rows);
+            entries += 2 * v.n_rows;
+            if (last) break;
+            v.xb32 = U.alloc<float>((size_t)v.n_rows);
+            v.t32 = U.alloc<float>((size_t)v.n_rows);
+            v.d32 = U.alloc<float>((size_t)v.n_rows);
+            v.values32 = U.alloc<float>((size_t)nv);
+            v.dinv32 = U.alloc<float>((size_t)nd);
+            v.p_val32 = U.alloc<float>((size_t)np);
+            entries += 3 * v.n_rows + nv + nd + np;
+        }
+        if (U.rc != DXO_OK) return U.rc;      // what was allocated goes with the object; the precision is unchanged
+        amg->fp32_bytes = entries * (int64_t)sizeof(float);
+    }
+    amg->ready = false;      // the copies are those of the last single-precision setup, if any
+    amg->precision = kind;
+    return DXO_OK;
+}
+
+extern "C" int dxo_amg_precision_info(dxo_ctx* ctx, const dxo_amg* amg, int* kind, int64_t* fp32_bytes) {
+    if (!amg) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (kind) *kind = amg->precision;
+    if (fp32_bytes) *fp32_bytes = amg->fp32_bytes;
     return DXO_OK;
 }
 
@@ -1975,12 +2106,26 @@ extern "C" int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values) {
         for (int64_t k = 0; k < n; ++k)
             hipLaunchKernelGGL(amg_dense_step, dim3((unsigned)n), B, 0, s, n, k, amg->dense[k % 2], amg->dense[(k + 1) % 2], amg->flag);
     }
-    int h[2] = {0, 0};
+    if (amg->precision == DXO_AMG_PRECISION_FP32)      // all of the above is double; the cycle's copies, before the one wait
+        for (int l = 0; l + 1 < nl; ++l) {
+            const amg_level& v = amg->L[(size_t)l];
+            const int64_t len[3] = {v.A->nnz, v.n_nodes * v.bs * v.bs, v.p_blocks * v.bs * v.bsc};
+            const double* from[3] = {v.values, v.dinv, v.p_val};
+            float* to[3] = {v.values32, v.dinv32, v.p_val32};
+            for (int q = 0; q < 3; ++q)
+                if (len[q] > 0) hipLaunchKernelGGL(amg_narrow, narrow_grid(len[q]), B, 0, s, len[q], from[q], to[q], amg->flag, l + 1);
+        }
+    int h[3] = {0, 0, 0};
     DXO_HIP(ctx, hipMemcpyAsync(h, amg->flag, sizeof h, hipMemcpyDeviceToHost, s));
     DXO_HIP(ctx, hipStreamSynchronize(s));
     rc = dxo_device_end(ctx, s);
     if (h[0]) return dxo_fail(ctx, DXO_E_SINGULAR, "dxo_amg_setup: a diagonal block of a level is singular");
     if (h[1]) return dxo_fail(ctx, DXO_E_SINGULAR, "dxo_amg_setup: zero pivot in the coarsest matrix");
+    if (h[2]) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "dxo_amg_setup: a finite entry of level %d leaves the range of float (DXO_AMG_PRECISION_FP32)", h[2] - 1);
+        return dxo_fail(ctx, DXO_E_OPTION, msg);
+    }
     if (rc != DXO_OK) return rc;
     amg->ready = true;
     return DXO_OK;

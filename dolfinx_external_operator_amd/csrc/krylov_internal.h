@@ -36,26 +36,27 @@ __device__ __forceinline__ int block_pos(const NodeRow<BS>& R, const int32_t* __
 // acc = (A x)_node over a group of LW lanes: lane l takes the blocks k = l, l + LW, ... in ascending order (one column index per
 // block, the BS entries of x at it, fma(v[j], xb[j], acc[i]) with j innermost), then the xor-butterfly from LW / 2 down leaves the
 // sums on every lane. All lanes of a group call it; those of a node >= n_nodes add nothing. pick(R, k, c, ab, ld), c the first column
-// of block k, may skip the block (false) or replace its pointer and leading dimension; SCALED: x is taken as sx x.
-template <int BS, int LW, bool SCALED = false, class Pick>
+// of block k, may skip the block (false) or replace its pointer and leading dimension; SCALED: x is taken as sx x. T is the scalar of
+// the values, of x and of the sums: double everywhere but in the single-precision multigrid cycle (float: the fma is v_fma_f32).
+template <int BS, int LW, bool SCALED = false, class T, class Pick>
 __device__ __forceinline__ void row_product(int64_t n_nodes, int64_t node, int lane, const int64_t* __restrict__ row_ptr,
-                                            const int32_t* __restrict__ col, const double* __restrict__ values, const double* __restrict__ x,
-                                            double sx, double (&acc)[BS], Pick pick) {
+                                            const int32_t* __restrict__ col, const T* __restrict__ values, const T* __restrict__ x,
+                                            T sx, T (&acc)[BS], Pick pick) {
 #pragma unroll
     for (int i = 0; i < BS; ++i) acc[i] = 0.0;
     if (node < n_nodes) {
         const NodeRow<BS> R(row_ptr, node);
         for (int k = lane; k < R.nnb; k += LW) {
             const int64_t c = col[R.r0 + (int64_t)k * BS];
-            const double* ab = values + R.r0 + (int64_t)k * BS;
+            const T* ab = values + R.r0 + (int64_t)k * BS;
             int64_t ld = R.len;
             if (!pick(R, k, c, ab, ld)) continue;
-            double xb[BS];
+            T xb[BS];
 #pragma unroll
             for (int j = 0; j < BS; ++j) xb[j] = SCALED ? sx * x[c + j] : x[c + j];
 #pragma unroll
             for (int i = 0; i < BS; ++i) {
-                const double* v = ab + i * ld;
+                const T* v = ab + i * ld;
 #pragma unroll
                 for (int j = 0; j < BS; ++j) acc[i] = fma(v[j], xb[j], acc[i]);
             }
@@ -68,11 +69,11 @@ __device__ __forceinline__ void row_product(int64_t n_nodes, int64_t node, int l
 }
 
 // the matrix as it is stored: every block, x unscaled
-template <int BS, int LW>
+template <int BS, int LW, class T>
 __device__ __forceinline__ void row_product(int64_t n_nodes, int64_t node, int lane, const int64_t* __restrict__ row_ptr,
-                                            const int32_t* __restrict__ col, const double* __restrict__ values, const double* __restrict__ x,
-                                            double (&acc)[BS]) {
-    row_product<BS, LW>(n_nodes, node, lane, row_ptr, col, values, x, 1.0, acc, [](const NodeRow<BS>&, int, int64_t, const double*&, int64_t&) { return true; });
+                                            const int32_t* __restrict__ col, const T* __restrict__ values, const T* __restrict__ x,
+                                            T (&acc)[BS]) {
+    row_product<BS, LW>(n_nodes, node, lane, row_ptr, col, values, x, T(1), acc, [](const NodeRow<BS>&, int, int64_t, const T*&, int64_t&) { return true; });
 }
 
 // Gauss-Jordan on [A | I] with partial pivoting (the lowest row among equals). Rows are exchanged by compare-and-select over static
@@ -128,9 +129,35 @@ __device__ __forceinline__ bool gj6(double (&M)[6][12]) {
 
 // the inverse of a diagonal block and its singularity test (|det| at most 1e-14 of the product of the row norms: false), for
 // dxo_csr_block_jacobi, the block-Jacobi inverses of the multigrid levels and the lumped diagonal blocks of the filtered prolongator
-// smoothing: in closed form for bs <= 3, by gj6 for the coarse levels of block size 6
+// smoothing: in closed form for bs <= 3, by gj6 for the coarse levels of block size 6. The test and the inverse do not depend on the
+// scale of the block: it is inverted as 2^-e a, e the exponent of its largest entry, and the result multiplied by 2^-e. Both
+// scalings are exact, so wherever the determinant and the squared row norms of `a` itself neither overflow nor underflow the
+// result is the one of the unscaled arithmetic bit for bit; entries of 1e300 or 1e-300 no longer count as singular.
 template <int BS>
-__device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (&b)[BS][BS]) {
+__device__ __forceinline__ bool invert_block_scaled(const double (&a0)[BS][BS], double s, double (&b)[BS][BS]);
+
+template <int BS>
+__device__ __forceinline__ bool invert_block(const double (&a0)[BS][BS], double (&b)[BS][BS]) {
+    double m = 0.0;
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) m = fmax(m, fabs(a0[i][j]));
+    int e = 0;
+    if (m > 0.0 && m <= 1.7976931348623157e308) (void)frexp(m, &e);      // a zero, NaN or infinite block: as it is
+    e = e > 1000 ? 1000 : (e < -1000 ? -1000 : e);                        // 2^-e stays a normal number
+    const double s = ldexp(1.0, -e);
+    const bool ok = invert_block_scaled<BS>(a0, s, b);
+#pragma unroll
+    for (int i = 0; i < BS; ++i)
+#pragma unroll
+        for (int j = 0; j < BS; ++j) b[i][j] *= s;
+    return ok;
+}
+
+// the inverse of s a0 and its singularity test
+template <int BS>
+__device__ __forceinline__ bool invert_block_scaled(const double (&a0)[BS][BS], double s, double (&b)[BS][BS]) {
     static_assert(BS <= 3 || BS == 6, "no inverse for this block size");
     if constexpr (BS == 6) {
         double M[BS][2 * BS];
@@ -138,7 +165,7 @@ __device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (
         for (int i = 0; i < BS; ++i)
 #pragma unroll
             for (int j = 0; j < BS; ++j) {
-                M[i][j] = a[i][j];
+                M[i][j] = a0[i][j] * s;
                 M[i][BS + j] = i == j ? 1.0 : 0.0;
             }
         const bool ok = gj6(M);
@@ -148,13 +175,18 @@ __device__ __forceinline__ bool invert_block(const double (&a)[BS][BS], double (
             for (int j = 0; j < BS; ++j) b[i][j] = M[i][BS + j];
         return ok;
     } else {
+        double a[BS][BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) a[i][j] = a0[i][j] * s;
         double had = 1.0;
 #pragma unroll
         for (int i = 0; i < BS; ++i) {
-            double s = 0.0;
+            double n2 = 0.0;
 #pragma unroll
-            for (int j = 0; j < BS; ++j) s += a[i][j] * a[i][j];
-            had *= sqrt(s);
+            for (int j = 0; j < BS; ++j) n2 += a[i][j] * a[i][j];
+            had *= sqrt(n2);
         }
         double det;
         if constexpr (BS == 1) {

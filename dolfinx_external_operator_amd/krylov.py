@@ -17,6 +17,7 @@ PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI, PC_AMG, PC_CALLBACK = 0, 1, 2, 3, 4
 _SMOOTHERS = {"jacobi": 0, "chebyshev": 1}           # DXO_AMG_SMOOTH_*
 _RHO_KINDS = {"inf-norm": 0, "power": 1}             # DXO_AMG_RHO_*
 _CYCLES = {"V": 0, "K": 1}                           # DXO_AMG_CYCLE_*
+_PRECISIONS = {"fp64": 0, "fp32": 1}                 # DXO_AMG_PRECISION_*
 
 
 def _torch():
@@ -140,16 +141,26 @@ class AMG:
     `cycle`: "V" (the default) or "K" (dxo_amg_set_cycle; set_cycle() changes it later, at once and without a setup, on any of the
     hierarchies above). The K-cycle solves the coarse equation of every level between the finest and the coarsest by two GCR steps
     preconditioned by the cycle of that level, so level l is visited 2^l times (`visits`). It is not a fixed linear operator: pass it
-    to fgmres; gmres and cg raise ValueError (DXO_E_OPTION). With at most two levels it is the V-cycle bit for bit."""
+    to fgmres; gmres and cg raise ValueError (DXO_E_OPTION). With at most two levels it is the V-cycle bit for bit.
+
+    `precision`: "fp64" (the default, the object of earlier versions bit for bit) or "fp32" (dxo_amg_set_precision;
+    set_precision() changes it later, for the next setup()). setup() stays double throughout and then casts the values, the block
+    inverses and the prolongator of every level but the coarsest to float; apply() runs the same V-cycle on these copies with float
+    vectors and arithmetic, the coarsest dense solve in double, r and the result double as before. The cycle is then a fixed linear
+    operator up to single-precision rounding (about 1e-7 relative to the fp64 cycle): it may be passed to gmres, cg and fgmres, whose
+    own arithmetic stays double; fgmres is the recommended partner. `fp32_bytes`: what the copies take. A finite entry beyond the
+    range of float makes setup() raise ValueError. Not with cycle="K" (ValueError, in either order)."""
 
     def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None,
                  smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10, lower: float = 0.1,
-                 safety: float = 1.1, strength: float = 0.0, cycle: str = "V"):
+                 safety: float = 1.1, strength: float = 0.0, cycle: str = "V", precision: str = "fp64"):
         torch = _torch()
         import numpy as np
 
         if cycle not in _CYCLES:
             raise ValueError(f"AMG: cycle must be one of {sorted(_CYCLES)}")
+        if precision not in _PRECISIONS:
+            raise ValueError(f"AMG: precision must be one of {sorted(_PRECISIONS)}")
         strength = float(strength)
         if not 0.0 <= strength < 1.0:          # NaN fails both comparisons
             raise ValueError("AMG: strength must lie in [0, 1)")
@@ -208,6 +219,8 @@ class AMG:
             self._set_smoother(*relax)
         if cycle != "V":
             self.set_cycle(cycle)
+        if precision != "fp64":
+            self.set_precision(precision)
         self.setup()
 
     def _relaxation(self, smoother, degree, rho, rho_iters, lower, safety) -> tuple:
@@ -239,6 +252,30 @@ class AMG:
             raise ValueError(f"AMG: cycle must be one of {sorted(_CYCLES)}")
         self.ctx.check(self.ctx.lib.dxo_amg_set_cycle(self.ctx._h, self._h, _CYCLES[cycle]), "dxo_amg_set_cycle")
         return self
+
+    def set_precision(self, precision: str = "fp64") -> "AMG":
+        """"fp64" or "fp32" (dxo_amg_set_precision) for the next setup(): apply() and the solvers raise ValueError (DXO_E_OPTION) until
+        then, unless the object already has this precision. The first "fp32" allocates the single-precision copies and vectors
+        (`fp32_bytes`); they stay with the object. "fp32" on a K-cycle raises ValueError."""
+        if precision not in _PRECISIONS:
+            raise ValueError(f"AMG: precision must be one of {sorted(_PRECISIONS)}")
+        self.ctx.check(self.ctx.lib.dxo_amg_set_precision(self.ctx._h, self._h, _PRECISIONS[precision]), "dxo_amg_set_precision")
+        return self
+
+    def _precision_info(self) -> tuple:
+        kind, nbytes = C.c_int(), C.c_int64()
+        self.ctx.check(self.ctx.lib.dxo_amg_precision_info(self.ctx._h, self._h, C.byref(kind), C.byref(nbytes)), "dxo_amg_precision_info")
+        return {v: k for k, v in _PRECISIONS.items()}[kind.value], int(nbytes.value)
+
+    @property
+    def precision(self) -> str:
+        """"fp64" or "fp32"."""
+        return self._precision_info()[0]
+
+    @property
+    def fp32_bytes(self) -> int:
+        """Bytes of the single-precision copies and vectors; 0 if "fp32" was never selected (or the hierarchy has one level)."""
+        return self._precision_info()[1]
 
     def _cycle_info(self) -> tuple:
         kind, visits = C.c_int(), C.c_int64()
@@ -591,7 +628,8 @@ def gmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: fl
     holding an inverse diagonal (1 / bilinear_diagonal for the matrix-free path), or a callable (r, out) that sets out = M r on the
     device; an exception in it is re-raised after the solve. M must be a fixed linear operator here, the same at every call: M is
     applied once more to the combination at the end of a cycle. One that varies (an inner iteration, an AMG with the K-cycle,
-    which raises ValueError here) belongs to fgmres. x: the initial guess, overwritten with the
+    which raises ValueError here) belongs to fgmres. An AMG with precision="fp32" is a fixed linear operator up to single-precision
+    rounding and is accepted; it may cost one more restart to reach tolerances below about 1e-7. x: the initial guess, overwritten with the
     solution (zeros if None). Converged when |b - A x| <= max(rtol |b|, atol); not converging within maxiter gives converged False,
     not an exception."""
     return _solve("dxo_krylov_gmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx)
@@ -604,14 +642,16 @@ def fgmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: f
     M need not be a fixed linear operator: it may differ from step to step (a callable that runs an inner solve, an AMG with the
     K-cycle). The preconditioned vectors z_j = M v_j are kept in a second basis (restart more vectors, allocated at the first
     flexible solve of a size) and the solution is updated with them, so M is called once per iteration and never at the update.
-    With a fixed M it takes the iterations of gmres."""
+    With a fixed M it takes the iterations of gmres. It is the recommended partner of an AMG with precision="fp32": the update uses the
+    stored z_j, so the single-precision rounding of the cycle never enters the solution a second time."""
     return _solve("dxo_krylov_fgmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx)
 
 
 def cg(A, b, x=None, M=None, rtol: float = 1e-10, atol: float = 0.0, maxiter: int | None = None, check_every: int = 8,
        ctx=None) -> KrylovResult:
     """Preconditioned conjugate gradients for symmetric positive definite A and M, same arguments as gmres (dxo_krylov_cg). M must
-    be a fixed linear operator (a callable that varies between calls, or an AMG with the K-cycle, has no place here: fgmres)."""
+    be a fixed linear operator (a callable that varies between calls, or an AMG with the K-cycle, has no place here: fgmres). An AMG
+    with precision="fp32" is accepted: it is symmetric up to single-precision rounding, and the residual is recomputed at the end."""
     return _solve("dxo_krylov_cg", A, b, x, M, 1, rtol, atol, maxiter, check_every, ctx)
 
 

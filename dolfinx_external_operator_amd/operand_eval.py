@@ -533,17 +533,19 @@ class DeviceCSR:
 
     def amg(self, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None,
             smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10, lower: float = 0.1,
-            safety: float = 1.1, strength: float = 0.0, cycle: str = "V") -> "AMG":
+            safety: float = 1.1, strength: float = 0.0, cycle: str = "V", precision: str = "fp64") -> "AMG":
         """A smoothed-aggregation multigrid preconditioner of this matrix (krylov.AMG: the symbolic phase and the first setup), for
         krylov.gmres / krylov.cg. `constrained`: the dofs given as bcs to bilinear_assemble. `near_nullspace`: a float64 CUDA tensor
         (n_rows, k), e.g. krylov.rigid_body_modes(x) for elasticity (k = 3 for bs 2, 6 for bs 3). `smoother` ("jacobi" or "chebyshev" of `degree`), `rho`
         ("inf-norm" or "power") and rho_iters, lower, safety: the relaxation, see krylov.AMG; the defaults 10 / 0.1 / 1.1 are the
         customary rule, not measurements. `strength`: the threshold of the strength of connection in [0, 1), 0 for none
         (anisotropic operators: 0.25); the masks are made from the present values and frozen. `cycle`: "V", or "K" for the K-cycle
-        (for krylov.fgmres only). After the values changed: `.setup()`."""
+        (for krylov.fgmres only). `precision`: "fp64", or "fp32" for a V-cycle on single-precision copies of the levels (the setup
+        stays double; krylov.fgmres is its recommended partner). After the values changed: `.setup()`."""
         from .krylov import AMG
 
-        return AMG(self, constrained, max_levels, coarse_rows, sweeps, near_nullspace, smoother, degree, rho, rho_iters, lower, safety, strength, cycle)
+        return AMG(self, constrained, max_levels, coarse_rows, sweeps, near_nullspace, smoother, degree, rho, rho_iters, lower, safety, strength, cycle,
+                   precision)
 
 
 class DeviceOperand:

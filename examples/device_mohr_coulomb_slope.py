@@ -7,7 +7,7 @@ A 1.2 x 1.0 rectangle of P2 triangles, bottom and right edges clamped, body forc
     sigma, C_tang = MC(eps(Du), sigma_n)        dxo_mohr_coulomb_field (mem = DEVICE)
     R = adjoint(eps, sigma) - adjoint(value, q) dxo_operand_adjoint, zero on the clamped dofs
     J = assembled (eps, eps) form with C_tang   dxo_bilinear_assemble + dxo_csr_dirichlet (identity rows)
-    solve J dDu = -R                            gmres with block Jacobi (dxo_krylov_gmres), --solver amg: gmres with the multigrid cycle (amg-rbm: with the rigid-body modes as its near-null space, amg-cheby: those modes, the power estimate of rho and Chebyshev smoothing of degree 2, amg-soc: those modes and strength-of-connection coarsening with theta 0.1, the masks of the first Newton iteration kept, amg-k: amg-rbm with the K-cycle, under flexible GMRES), --solver lu: splu on the host
+    solve J dDu = -R                            gmres with block Jacobi (dxo_krylov_gmres), --solver amg: gmres with the multigrid cycle (amg-rbm: with the rigid-body modes as its near-null space, amg-cheby: those modes, the power estimate of rho and Chebyshev smoothing of degree 2, amg-soc: those modes and strength-of-connection coarsening with theta 0.1, the masks of the first Newton iteration kept, amg-k: amg-rbm with the K-cycle, under flexible GMRES, amg-fp32: amg-cheby with the cycle in single precision, under flexible GMRES), --solver lu: splu on the host
     Du += dDu
 and at the end of a load step u += Du, sigma_n <- sigma. C_tang is the derivative through the return map and is not symmetric in
 general, hence GMRES. Newton stops at |R| <= max(1e-8, 1e-8 |R_0|) (the demo's snes_atol / snes_rtol). Each step starts from
@@ -16,7 +16,7 @@ Du = 0, where the return map has no tangent: with deps = 0 its initial residual 
 the same reason, :639-646). The first Newton iteration of a step therefore uses the elastic tangent, the others C_tang. A step
 whose GMRES or Newton does not converge is reported and ends the loading.
 
-    python3 examples/device_mohr_coulomb_slope.py [--n 25] [--steps K] [--solver gmres|amg|amg-rbm|amg-cheby|amg-soc|amg-k|lu]
+    python3 examples/device_mohr_coulomb_slope.py [--n 25] [--steps K] [--solver gmres|amg|amg-rbm|amg-cheby|amg-soc|amg-k|amg-fp32|lu]
 """
 import argparse
 import pathlib
@@ -111,13 +111,15 @@ def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: 
                 d = torch.from_numpy(scipy.sparse.linalg.splu(S).solve(rhs.cpu().numpy())).to(dev)
             else:
                 try:
-                    if solver in ("amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k"):     # the symbolic phase once, the numeric setup at every Newton iteration
+                    if solver in ("amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k", "amg-fp32"):     # the symbolic phase once, the numeric setup at every Newton iteration
                         if amg is None:
                             relax = {"smoother": "chebyshev", "degree": 2, "rho": "power"} if solver == "amg-cheby" else {}
                             if solver == "amg-soc":
                                 relax = {"strength": 0.1}
                             if solver == "amg-k":
                                 relax = {"cycle": "K"}
+                            if solver == "amg-fp32":
+                                relax = {"smoother": "chebyshev", "degree": 2, "rho": "power", "precision": "fp32"}
                             amg = A.amg(bcs, near_nullspace=rigid_body_modes(x, ctx=ctx) if solver != "amg" else None, **relax)
                         else:
                             amg.setup(A)
@@ -127,7 +129,7 @@ def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: 
                 except ValueError as e:          # DXO_E_SINGULAR: a node whose tangent blocks vanish
                     failed = f"preconditioner setup failed at load {load:.3f} (step {i}, Newton iteration {it}): {e}"
                     break
-                out = (fgmres if solver == "amg-k" else gmres)(A, rhs, M=M, restart=restart, rtol=lin_rtol, maxiter=lin_maxiter)
+                out = (fgmres if solver in ("amg-k", "amg-fp32") else gmres)(A, rhs, M=M, restart=restart, rtol=lin_rtol, maxiter=lin_maxiter)
                 lin_its.append(out.iterations)
                 if not out.converged:
                     failed = f"GMRES did not converge at load {load:.3f} (step {i}): {out.iterations} iterations, relative residual {out.residual:.2e}"
@@ -168,6 +170,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--n", type=int, default=25, help="cells per side (the demo: 25)")
     ap.add_argument("--steps", type=int, default=None, help="first K load steps only")
-    ap.add_argument("--solver", choices=["gmres", "amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k", "lu"], default="gmres")
+    ap.add_argument("--solver", choices=["gmres", "amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k", "amg-fp32", "lu"], default="gmres")
     a = ap.parse_args()
     main(a.n, a.steps, a.solver)

@@ -756,7 +756,30 @@ int dxo_krylov_fgmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, con
  *                   dxo_krylov_fgmres takes it. With at most two levels K is V bit for bit. The first DXO_AMG_CYCLE_K allocates
  *                   five vectors per intermediate level. An unknown kind: DXO_E_OPTION, nothing changes.
  * dxo_amg_cycle_info : the kind, and the level visits of one apply: the levels for V; for K 2^l per level l but the coarsest, which
- *                   is visited as often as the level above it. Any pointer may be NULL. */
+ *                   is visited as often as the level above it. Any pointer may be NULL.
+ *
+ * The precision of the cycle (every object starts with DXO_AMG_PRECISION_FP64, which is all of the above bit for bit):
+ * dxo_amg_set_precision : the scalar of the cycle for the NEXT dxo_amg_setup; until then dxo_amg_apply and the Krylov calls answer
+ *                   DXO_E_OPTION (setting the kind the object already has does nothing). DXO_AMG_PRECISION_FP32: dxo_amg_setup stays
+ *                   double to its end (inverses, omega, rho, the Chebyshev pairs, P, A P, P^T A P, the dense inverse, the strength
+ *                   and near-null-space paths) and then casts, per level but the coarsest, the level's values (level 0: the
+ *                   caller's), dinv and the values of P to float, before its one synchronisation. A finite entry that leaves the
+ *                   range of float: DXO_E_OPTION with the level in the message; underflow to zero is not an error. dxo_amg_apply then
+ *                   runs the launch sequence of the V-cycle with these copies, float vectors and float fused multiply-adds in the
+ *                   same order; omega and the Chebyshev pairs are read as double and narrowed; the coarsest level keeps its double
+ *                   dense inverse (right-hand side widened, result narrowed). r and z stay double: r is narrowed by one pass on
+ *                   entry (r may still be z) and the last post-smoothing sweep of level 0 writes z. No host read, no allocation, no
+ *                   atomics: capture-safe and bit-reproducible as before, and a fixed linear operator up to single-precision
+ *                   rounding, so dxo_krylov_gmres, dxo_krylov_cg and dxo_krylov_fgmres all take it (their own arithmetic stays
+ *                   double; dxo_krylov_fgmres is the natural partner, dxo_krylov_gmres may spend one more restart below 1e-7).
+ *                   A hierarchy of one level is its dense product in double under either kind. The first
+ *                   DXO_AMG_PRECISION_FP32 allocates the copies and five float vectors per level (two on the coarsest); they stay
+ *                   with the object. The K-cycle is double only: DXO_AMG_PRECISION_FP32 on an object with DXO_AMG_CYCLE_K, and
+ *                   dxo_amg_set_cycle(DXO_AMG_CYCLE_K) on an object with DXO_AMG_PRECISION_FP32, answer DXO_E_OPTION and change
+ *                   nothing. An unknown kind: DXO_E_OPTION.
+ * dxo_amg_precision_info : the kind, and the bytes of the single-precision copies and vectors (0 if none were ever allocated). Any
+ *                   pointer may be NULL. */
+enum { DXO_AMG_PRECISION_FP64 = 0, DXO_AMG_PRECISION_FP32 = 1 };
 #define DXO_AMG_SMOOTH_JACOBI 0
 #define DXO_AMG_SMOOTH_CHEBYSHEV 1
 #define DXO_AMG_RHO_INF_NORM 0
@@ -802,6 +825,8 @@ int dxo_amg_soc_info(dxo_ctx* ctx, const dxo_amg* amg, int level, double* theta,
                      int64_t* n_unlumped_nodes, const double** dinv_f, const double** omega_f);
 int dxo_amg_set_cycle(dxo_ctx* ctx, dxo_amg* amg, int kind);
 int dxo_amg_cycle_info(dxo_ctx* ctx, const dxo_amg* amg, int* kind, int64_t* visits);
+int dxo_amg_set_precision(dxo_ctx* ctx, dxo_amg* amg, int kind);
+int dxo_amg_precision_info(dxo_ctx* ctx, const dxo_amg* amg, int* kind, int64_t* fp32_bytes);
 
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is

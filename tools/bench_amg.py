@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Standalone timing of the multigrid preconditioner (csrc/amg.hip; not a bench.py leg).
-    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG] [--strength THETA[,THETA...]] [--cycle K]
+    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG] [--strength THETA[,THETA...]] [--cycle K] [--precision fp32]
 Systems (distorted meshes, the lower side clamped so that the matrices are regular):
   p2       ("grad", "grad", 2) on P2 triangles with C = I + 0.3 N(0, 1) per point (1291 per side: 10^7 points), as tools/bench_krylov.py
   q2hex    ("eps", "eps", 3) on Q2 hexahedra (40^3 boxes), the same kind of C
@@ -21,6 +21,9 @@ solve is repeated with power_cheby<DEG> on that hierarchy.
 --cycle K adds, for every hierarchy and relaxation measured without --strength (the default's, those of --rbm and of --cheby), the
 K-cycle on the same object in the same run (key "kcycle" inside the figures of the V-cycle / GMRES(30) line): apply ms, the level visits
 of one apply, and one FGMRES(30) solve to rtol 1e-8 (iterations, ms; the setup is the V-cycle's).
+--precision fp32 adds, for the same hierarchies and relaxations as --cycle K, the single-precision cycle on the same object in the same
+run (key "fp32" beside "kcycle"): setup ms (the double setup plus the casts), apply ms, and one FGMRES(30) solve to rtol 1e-8
+(iterations, ms, ms with setup); the object is back in double, set up, afterwards.
 Timing: warm-up, then 5 batches timed with HIP events on the launch stream, the MEDIAN batch reported (tools/bench_krylov._batches).
 Prints one JSON line."""
 from __future__ import annotations
@@ -35,7 +38,7 @@ if str(ROOT) not in sys.path:
 
 
 def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000, rbm: bool = False,
-         cheby: int = 0, strengths: tuple = (), cycle: str = "V") -> dict:
+         cheby: int = 0, strengths: tuple = (), cycle: str = "V", precision: str = "fp64") -> dict:
     import numpy as np
     import torch
 
@@ -67,6 +70,17 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
         amg.set_cycle("V")
         return f
 
+    def fp32(amg, A, b, x, y):
+        """The single-precision cycle of the hierarchy as it stands, under FGMRES(30); the object is in double again afterwards."""
+        amg.set_precision("fp32").setup()
+        f = {"setup_ms": timed(lambda: amg.setup(), 3), "apply_ms": timed(lambda: amg.apply(x, y), 20), "fp32_bytes": amg.fp32_bytes}
+        fgmres(A, b, M=amg, rtol=1e-8, maxiter=30)                           # warm-up (and the second basis)
+        out = fgmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
+        f.update({"iterations": out.iterations, "converged": out.converged, "residual": out.residual, "ms": round(out.ms, 2),
+                  "ms_with_setup": round(out.ms + f["setup_ms"], 2)})
+        amg.set_precision("fp64").setup()
+        return f
+
     def relaxations(amg, A, b, x, y, r, suffix):
         for key, kw in (("power_jacobi", {"rho": "power"}), (f"power_cheby{cheby}", {"smoother": "chebyshev", "degree": cheby, "rho": "power"})):
             amg.set_smoother(**kw).setup()
@@ -77,6 +91,8 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                       "ms_with_setup": round(out.ms + f["setup_ms"], 2)})
             if cycle == "K":
                 f["kcycle"] = kcycle(amg, A, b, x, y, f["setup_ms"])
+            if precision == "fp32":
+                f["fp32"] = fp32(amg, A, b, x, y)
             r[key + suffix] = f
 
     def with_strength(A, bcs, nns, b, x, y, r, suffix):
@@ -126,6 +142,8 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                 r["gmres30_amg"]["ms_with_setup"] = round(r["gmres30_amg"]["ms"] + r["setup_ms"], 2)
                 if cycle == "K":
                     r["gmres30_amg"]["kcycle"] = kcycle(amg, A, b, x, y, r["setup_ms"])
+                if precision == "fp32":
+                    r["gmres30_amg"]["fp32"] = fp32(amg, A, b, x, y)
                 if cheby:
                     relaxations(amg, A, b, x, y, r, "")
                 amg.close()
@@ -144,6 +162,8 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                                             "ms": round(out.ms, 2), "ms_with_setup": round(out.ms + r["setup_ms_rbm"], 2)}
                     if cycle == "K":
                         r["gmres30_amg_rbm"]["kcycle"] = kcycle(amg, A, b, x, y, r["setup_ms_rbm"])
+                    if precision == "fp32":
+                        r["gmres30_amg_rbm"]["fp32"] = fp32(amg, A, b, x, y)
                     if cheby:
                         relaxations(amg, A, b, x, y, r, "_rbm")
                     amg.close()
@@ -214,7 +234,12 @@ if __name__ == "__main__":
         i = args.index("--cycle")
         cycle = args[i + 1]
         del args[i:i + 2]
-    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby, strengths=strengths, cycle=cycle)
+    precision = "fp64"
+    if "--precision" in args:
+        i = args.index("--precision")
+        precision = args[i + 1]
+        del args[i:i + 2]
+    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby, strengths=strengths, cycle=cycle, precision=precision)
     line = json.dumps(r)
     print(line)
     if out_file:
