@@ -41,7 +41,8 @@
 //
 // Strength of connection (dxo_amg_create_soc with theta > 0). Block (i, j) is strong when |A_ij|_F^2 >= theta^2 |A_ii|_F |A_jj|_F or
 // the same holds for (j, i): amg_diag_norm writes |A_ii|_F per node, amg_strength (a lane group per node, a lane per block, the
-// transposed block found by search) one byte per block. Creation then interleaves with the numeric phase level by level: the mask of
+// transposed block found by search) one byte per block; both square entries scaled by a power of two, so the mask does not depend on
+// the scale of the matrix (see there). Creation then interleaves with the numeric phase level by level: the mask of
 // level l comes to the host, the aggregates are made on the strong graph, P gets the pattern (strong graph) x (aggregates) while A P
 // and P^T A P keep the full graph, and the numeric kernels of level l give the matrix of level l + 1 for the next mask (one wait per
 // level, at creation only; the relaxation is the default one there). The masks are frozen: dxo_amg_setup reuses them. The
@@ -568,18 +569,33 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_c(int64_t c_blocks, c
 }
 
 // ---- strength of connection
-// the sum of the squares of a block, entry by entry in row-major order
+// The test does not depend on the scale of the matrix: every sum of squares is formed on entries multiplied by a power of two that
+// brings them near 1 (amg_pow2_down of a reference value: exact, as in invert_block), so that neither |A_ii|_F nor the two sides of
+// the comparison leave the range of double where the entries themselves are inside it. Wherever the unscaled squares neither
+// overflow nor underflow the mask is the one of the unscaled arithmetic bit for bit.
+// 2^-e, e the exponent of m (frexp) held in +-1000 so that 2^-e is a normal number; 1 for a zero, NaN or infinite m
+__device__ __forceinline__ double amg_pow2_down(double m) {
+    int e = 0;
+    if (m > 0.0 && m <= 1.7976931348623157e308) (void)frexp(m, &e);
+    e = e > 1000 ? 1000 : (e < -1000 ? -1000 : e);
+    return ldexp(1.0, -e);
+}
+
+// the sum of the squares of s a, entry by entry in row-major order
 template <int BS>
-__device__ __forceinline__ double amg_block_norm2(const double* __restrict__ a, int64_t ld) {
-    double s = 0.0;
+__device__ __forceinline__ double amg_block_norm2(const double* __restrict__ a, int64_t ld, double s) {
+    double sum = 0.0;
 #pragma unroll
     for (int i = 0; i < BS; ++i)
 #pragma unroll
-        for (int j = 0; j < BS; ++j) s = fma(a[i * ld + j], a[i * ld + j], s);
-    return s;
+        for (int j = 0; j < BS; ++j) {
+            const double v = a[i * ld + j] * s;
+            sum = fma(v, v, sum);
+        }
+    return sum;
 }
 
-// dn[node] = |A_ii|_F (0 without a diagonal block)
+// dn[node] = |A_ii|_F (0 without a diagonal block): the norm of 2^-e A_ii, e the exponent of its largest entry, divided by 2^-e
 template <int BS>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_diag_norm(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                                const double* __restrict__ values, double* __restrict__ dn) {
@@ -587,11 +603,23 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_diag_norm(int64_t n_nodes, 
     if (node >= n_nodes) return;
     const NodeRow<BS> R(row_ptr, node);
     const int lo = block_pos<BS>(R, col, node);
-    dn[node] = lo >= 0 ? sqrt(amg_block_norm2<BS>(values + R.r0 + (int64_t)lo * BS, R.len)) : 0.0;
+    double d = 0.0;
+    if (lo >= 0) {
+        const double* a = values + R.r0 + (int64_t)lo * BS;
+        double m = 0.0;
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int j = 0; j < BS; ++j) m = fmax(m, fabs(a[i * R.len + j]));
+        const double s = amg_pow2_down(m);
+        d = sqrt(amg_block_norm2<BS>(a, R.len, s)) / s;
+    }
+    dn[node] = d;
 }
 
-// strong[block] = |A_ij|_F^2 >= th2 |A_ii|_F |A_jj|_F, or the same for the transposed block (found by search in row j; absent: the
-// one-sided test). LW lanes own a node, a lane its blocks k = lane, lane + LW, ...; diagonal blocks are strong
+// strong[block] = |s A_ij|_F^2 >= th2 (s |A_ii|_F) (s |A_jj|_F) with s = 2^-e, e the exponent of the larger of the two norms, or the
+// same for the transposed block (found by search in row j; absent: the one-sided test). LW lanes own a node, a lane its blocks
+// k = lane, lane + LW, ...; diagonal blocks are strong
 template <int BS, int LW>
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_strength(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                               const double* __restrict__ values, const double* __restrict__ dn, double th2,
@@ -607,12 +635,14 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_strength(int64_t n_nodes, c
         const int64_t j = col[R.r0 + (int64_t)k * BS] / BS;
         bool st = j == node;
         if (!st) {
-            const double bound = th2 * (di * dn[j]);
-            st = amg_block_norm2<BS>(values + R.r0 + (int64_t)k * BS, R.len) >= bound;
+            const double dj = dn[j];
+            const double s = amg_pow2_down(fmax(di, dj));
+            const double bound = th2 * ((di * s) * (dj * s));
+            st = amg_block_norm2<BS>(values + R.r0 + (int64_t)k * BS, R.len, s) >= bound;
             if (!st) {
                 const NodeRow<BS> Rj(row_ptr, j);
                 const int t = block_pos<BS>(Rj, col, node);      // the block (j, node)
-                if (t >= 0) st = amg_block_norm2<BS>(values + Rj.r0 + (int64_t)t * BS, Rj.len) >= bound;
+                if (t >= 0) st = amg_block_norm2<BS>(values + Rj.r0 + (int64_t)t * BS, Rj.len, s) >= bound;
             }
         }
         strong[b0 + k] = st ? 1 : 0;
@@ -1034,8 +1064,10 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_k_dots(int64_t n, const dou
 
 // one workgroup: the sums of the partials (a thread's in ascending order, then amg_block_sum) and the coefficients of the GCR step.
 // step 1: rho1 = (v1, v1), a1 = (v1, r), alpha1 = a1 / rho1 (0 with rho1 == 0). step 2: beta = (v2, v2), g = (v2, v1), a2 = (v2, r1),
-// rho2 = beta - g g / rho1 and x = X1 c1 + X2 c2: (0, 0) with rho1 == 0, (alpha1, 0) when rho2 is not finite or at most 1e-14 beta
-// (the second direction depends on the first: the rule of the singular diagonal block), else (alpha1 - g a2 / (rho1 rho2), a2 / rho2)
+// rho2 = beta - g (g / rho1) and x = X1 c1 + X2 c2: (0, 0) with rho1 == 0, (alpha1, 0) when rho2 is not finite or at most 1e-14 beta
+// (the second direction depends on the first: the rule of the singular diagonal block), else X2 = a2 / rho2 and
+// X1 = alpha1 - (g / rho1) X2. Only ratios of the dot products are formed, no product of two of them (that would be a fourth power
+// of |r|): the coefficients are homogeneous of degree 0 in r, bit for bit, wherever the dot products themselves are finite and normal
 __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_k_scalar(const double* __restrict__ part, int nb, int step, double* __restrict__ co) {
     __shared__ double lds[3][DXO_AMG_BLOCK / 64];
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -1057,12 +1089,13 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_k_scalar(const double* __re
     const double rho1 = co[KCO_RHO1], alpha1 = co[KCO_ALPHA1], beta = s0, g = s1, a2 = s2;
     double x1 = 0.0, x2 = 0.0;
     if (rho1 != 0.0) {
-        const double rho2 = beta - g * g / rho1;
+        const double gr = g / rho1;
+        const double rho2 = beta - g * gr;
         if (!std::isfinite(rho2) || rho2 <= 1e-14 * beta) {
             x1 = alpha1;
         } else {
-            x1 = alpha1 - g * a2 / (rho1 * rho2);
             x2 = a2 / rho2;
+            x1 = alpha1 - gr * x2;
         }
     }
     co[KCO_X1] = x1;

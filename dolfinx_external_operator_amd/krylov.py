@@ -141,7 +141,8 @@ class AMG:
     `cycle`: "V" (the default) or "K" (dxo_amg_set_cycle; set_cycle() changes it later, at once and without a setup, on any of the
     hierarchies above). The K-cycle solves the coarse equation of every level between the finest and the coarsest by two GCR steps
     preconditioned by the cycle of that level, so level l is visited 2^l times (`visits`). It is not a fixed linear operator: pass it
-    to fgmres; gmres and cg raise ValueError (DXO_E_OPTION). With at most two levels it is the V-cycle bit for bit.
+    to fgmres; gmres and cg raise ValueError (DXO_E_OPTION). With at most two levels it is the V-cycle bit for bit. It is homogeneous
+    in r (apply(2^e r) == 2^e apply(r)) as long as the squares of |r| are finite and normal, |r| roughly within 2^-500 .. 2^500.
 
     `precision`: "fp64" (the default, the object of earlier versions bit for bit) or "fp32" (dxo_amg_set_precision;
     set_precision() changes it later, for the next setup()). setup() stays double throughout and then casts the values, the block
@@ -149,7 +150,8 @@ class AMG:
     vectors and arithmetic, the coarsest dense solve in double, r and the result double as before. The cycle is then a fixed linear
     operator up to single-precision rounding (about 1e-7 relative to the fp64 cycle): it may be passed to gmres, cg and fgmres, whose
     own arithmetic stays double; fgmres is the recommended partner. `fp32_bytes`: what the copies take. A finite entry beyond the
-    range of float makes setup() raise ValueError. Not with cycle="K" (ValueError, in either order)."""
+    range of float makes setup() raise ValueError; r is narrowed to float on entry, so an |r| beyond float's range is not representable
+    (scale it). Not with cycle="K" (ValueError, in either order)."""
 
     def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None,
                  smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10, lower: float = 0.1,

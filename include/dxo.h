@@ -722,7 +722,9 @@ int dxo_krylov_fgmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, con
  *                   (DEVICE, on the pattern of csr). theta == 0: the object of those two calls bit for bit, `values` is not read.
  *                   theta > 0: block (i, j), i != j, of a level is strong when |A_ij|_F^2 >= theta^2 |A_ii|_F |A_jj|_F or the same
  *                   holds for (j, i) (an absent transposed block: the one-sided test); the squares are summed entry by entry in
- *                   row-major order and compared in double. Diagonal blocks are strong. The aggregates are those of the three
+ *                   row-major order and compared in double, on entries multiplied by a power of two (|A_ii|_F: by the exponent of
+ *                   the block's largest entry; a comparison: by that of the larger of the two norms), so the mask does not depend
+ *                   on the scale of the matrix wherever its entries are finite. Diagonal blocks are strong. The aggregates are those of the three
  *                   passes on the strong graph (a node without a strong neighbour founds an aggregate of its own in pass 1), P has
  *                   the pattern (strong graph) x (aggregates), A P and P^T A P are built from the full graph. Because the mask of a
  *                   coarse level needs the coarse matrix, creation runs the numeric phase of every level as it goes (one
@@ -749,8 +751,11 @@ int dxo_krylov_fgmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, con
  *                   post-smoothing), the coarsest level keeps its dense solve, and on every level l between them A_l x = r is
  *                   solved by exactly two GCR steps preconditioned by B_l: c1 = B_l(r), v1 = A_l c1, rho1 = (v1, v1), a1 = (v1, r),
  *                   r1 = r - (a1 / rho1) v1, c2 = B_l(r1), v2 = A_l c2, g = (v2, v1), beta = (v2, v2), a2 = (v2, r1),
- *                   rho2 = beta - g g / rho1, x = (a1 / rho1 - g a2 / (rho1 rho2)) c1 + (a2 / rho2) c2. rho1 == 0: x = 0; rho2 not
- *                   finite or <= 1e-14 beta: x = (a1 / rho1) c1. Both steps always run (no early exit after the first), the
+ *                   rho2 = beta - g (g / rho1), x2 = a2 / rho2, x = (a1 / rho1 - (g / rho1) x2) c1 + x2 c2. rho1 == 0: x = 0; rho2
+ *                   not finite or <= 1e-14 beta: x = (a1 / rho1) c1. The coefficients are ratios of dot products; no product of two
+ *                   dot products is formed. An apply is therefore homogeneous of degree one in r, bit for bit, as long as the dot
+ *                   products themselves, second powers of |r|, are finite and normal: |r| roughly within 2^-500 .. 2^500 (the
+ *                   V-cycle is linear over the whole range of double). Both steps always run (no early exit after the first), the
  *                   coefficients stay on the device: dxo_amg_apply remains capture-safe, allocation-free and bit-reproducible, but
  *                   is no longer a linear operator, so dxo_krylov_gmres / dxo_krylov_cg refuse the object (DXO_E_OPTION) and
  *                   dxo_krylov_fgmres takes it. With at most two levels K is V bit for bit. The first DXO_AMG_CYCLE_K allocates
@@ -768,7 +773,8 @@ int dxo_krylov_fgmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, con
  *                   runs the launch sequence of the V-cycle with these copies, float vectors and float fused multiply-adds in the
  *                   same order; omega and the Chebyshev pairs are read as double and narrowed; the coarsest level keeps its double
  *                   dense inverse (right-hand side widened, result narrowed). r and z stay double: r is narrowed by one pass on
- *                   entry (r may still be z) and the last post-smoothing sweep of level 0 writes z. No host read, no allocation, no
+ *                   entry (r may still be z), so an |r| beyond the range of float (about 2^-126 .. 2^127; smaller entries lose
+ *                   bits, then become 0, larger ones infinite) is not representable and must be scaled by the caller; the last post-smoothing sweep of level 0 writes z. No host read, no allocation, no
  *                   atomics: capture-safe and bit-reproducible as before, and a fixed linear operator up to single-precision
  *                   rounding, so dxo_krylov_gmres, dxo_krylov_cg and dxo_krylov_fgmres all take it (their own arithmetic stays
  *                   double; dxo_krylov_fgmres is the natural partner, dxo_krylov_gmres may spend one more restart below 1e-7).

@@ -3,7 +3,7 @@ smoothing, pinned on the CPU on top of the oracles of test_amg_oracle_cpu.py, te
 test_amg_cheby_oracle_cpu.py.
 
 strength_ref: block (i, j), i != j, is strong when |A_ij|_F^2 >= theta^2 |A_ii|_F |A_jj|_F or the same holds for (j, i); diagonal
-blocks are strong. amg_soc_ref: today's three passes on the strong graph, P on the pattern (strong graph) x (aggregates), A P and
+blocks are strong. The squares are formed on entries scaled by a power of two, so the mask does not depend on the scale of A. amg_soc_ref: today's three passes on the strong graph, P on the pattern (strong graph) x (aggregates), A P and
 P^T A P on the full graph, P = T - omega_F Dinv_F A^F T with A^F the matrix without its weak blocks, each added onto the diagonal
 block of its row, Dinv_F the inverses of the lumped blocks (A_ii's where the lumped block fails Hadamard's test, zero for a node
 without a strong neighbour) and omega_F = (4/3) / rho_F from the selected estimate of Dinv_F A^F. The sweeps keep A, Dinv and rho, so
@@ -46,17 +46,28 @@ def block_values(A, indptr, indices, bs):
     return A.data[idx], row, nb
 
 
-def strength_ref(A, indptr, indices, bs, theta):
-    """(mask per block, closest): the strong blocks, and the smallest |value / threshold - 1| over the tests that decided them."""
+def pow2_down(m):
+    """2^-e, e the exponent of m (frexp) held in +-1000; 1 for a zero, NaN or infinite m: amg_pow2_down of the device."""
+    m = np.asarray(m, dtype=np.float64)
+    ok = (m > 0.0) & np.isfinite(m)
+    e = np.where(ok, np.frexp(np.where(ok, m, 1.0))[1], 0)
+    return np.ldexp(1.0, -np.clip(e, -1000, 1000))
+
+
+def _norm2(blocks, s):
+    """The sum of the squares of s[b] blocks[b], entry by entry in row-major order."""
+    n2 = np.zeros(blocks.shape[0])
+    for v in blocks.reshape(blocks.shape[0], -1).T:
+        v = v * s
+        n2 = n2 + v * v
+    return n2
+
+
+def _decide(A, indptr, indices, bs, theta, n2, bound):
+    """(mask, closest) from the squared norms and the thresholds of every block, both in the scaling of the block."""
     blocks, row, colnode = block_values(A, indptr, indices, bs)
     ptr, nb = node_graph(indptr, indices, bs)
     n = ptr.size - 1
-    n2 = np.zeros(blocks.shape[0])
-    for v in blocks.reshape(blocks.shape[0], -1).T:              # entry by entry in row-major order
-        n2 = n2 + v * v
-    dn = np.zeros(n)
-    dn[row[row == colnode]] = np.sqrt(n2[row == colnode])
-    bound = theta * theta * (dn[row] * dn[colnode])
     N2 = sp.csr_matrix((n2, nb, ptr), shape=(n, n))
     has = sp.csr_matrix((np.ones(nb.size), nb, ptr), shape=(n, n))
     n2t = np.asarray(N2.T.tocsr()[row, colnode]).ravel() if nb.size else np.zeros(0)
@@ -67,6 +78,32 @@ def strength_ref(A, indptr, indices, bs, theta):
     if off.any():
         closest = min(np.abs(n2[off] / bound[off] - 1.0).min(), np.abs(n2t[off & present] / bound[off & present] - 1.0).min(initial=np.inf))
     return mask, closest
+
+
+def strength_ref(A, indptr, indices, bs, theta):
+    """(mask per block, closest): the strong blocks, and the smallest |value / threshold - 1| over the tests that decided them.
+    The device's range-safe arithmetic: |A_ii|_F from the block times 2^-e of its largest entry, divided by it again; block (i, j)
+    compared as |s A_ij|_F^2 >= theta^2 (s |A_ii|_F) (s |A_jj|_F) with s = 2^-e of the larger norm, the same s for (j, i)."""
+    blocks, row, colnode = block_values(A, indptr, indices, bs)
+    n = (np.asarray(indptr).size - 1) // bs
+    on = row == colnode
+    sd = pow2_down(np.abs(blocks[on]).reshape(-1, bs * bs).max(axis=1))
+    dn = np.zeros(n)
+    dn[row[on]] = np.sqrt(_norm2(blocks[on], sd)) / sd
+    s = pow2_down(np.maximum(dn[row], dn[colnode]))
+    bound = theta * theta * ((dn[row] * s) * (dn[colnode] * s))
+    return _decide(A, indptr, indices, bs, theta, _norm2(blocks, s), bound)
+
+
+def strength_unscaled_ref(A, indptr, indices, bs, theta):
+    """strength_ref in the arithmetic of earlier versions, which squares the entries as they are: |A_ij|_F^2 >= theta^2 |A_ii|_F
+    |A_jj|_F. Kept as what the range-safe form is compared against inside the range where these squares are normal numbers."""
+    blocks, row, colnode = block_values(A, indptr, indices, bs)
+    n = (np.asarray(indptr).size - 1) // bs
+    n2 = _norm2(blocks, 1.0)
+    dn = np.zeros(n)
+    dn[row[row == colnode]] = np.sqrt(n2[row == colnode])
+    return _decide(A, indptr, indices, bs, theta, n2, theta * theta * (dn[row] * dn[colnode]))
 
 
 def filtered_ref(A, indptr, indices, bs, mask):
@@ -423,6 +460,35 @@ def test_no_block_of_the_gpu_systems_lies_at_the_threshold(which):
         print(f"{which} level {l}: closest test value {L.closest:.3e} of its threshold away, {int(L.strong.sum())} of {L.strong.size} strong")
         assert L.closest > 1e3 * 4 * L.bs * L.bs * U, (which, l, L.closest)
         assert not L.strong.all() or l > 0, which
+
+
+SCALE_EXPONENTS = (996, -900, 520, -540)      # near both ends of double; where the unscaled squares first overflow / underflow
+
+
+@pytest.mark.parametrize("which", sorted(GPU_THETAS))
+def test_masks_do_not_depend_on_the_scale_of_the_matrix(which):
+    """Every level of the GPU systems: the range-safe masks at scale 1 are those of the unscaled arithmetic (same `closest` too: the
+    two sides of a comparison are scaled by the same power of two), and the masks of 2^e A are the masks of A for the four
+    exponents. The unscaled arithmetic loses the mask of level 0 at every one of them (asserted, so that the exponents stay meaningful)."""
+    m, S, bs, dofs, B = gpu_system_ref(which)
+    theta = GPU_THETAS[which]
+    levels = amg_soc_ref(S, bs, dofs, theta, B, coarse_rows=60 if bs == 1 else 20)
+    assert len(levels) >= 2
+    for l, L in enumerate(levels[:-1]):
+        old, old_closest = strength_unscaled_ref(L.A, L.indptr, L.indices, L.bs, theta)
+        new, new_closest = strength_ref(L.A, L.indptr, L.indices, L.bs, theta)
+        assert np.array_equal(new, old) and np.array_equal(new, L.strong) and new_closest == old_closest, (which, l)
+        assert not new.all() or l > 0
+        for e in SCALE_EXPONENTS:
+            As = L.A.copy()
+            As.data = np.ldexp(L.A.data, e)
+            assert np.isfinite(As.data).all() and np.array_equal(np.ldexp(As.data, -e), L.A.data)
+            scaled, closest = strength_ref(As, L.indptr, L.indices, L.bs, theta)
+            assert np.array_equal(scaled, new) and closest == new_closest, (which, l, e)
+            with np.errstate(over="ignore", invalid="ignore"):            # inf >= inf and 0 >= 0 are what it is kept for
+                lost, _ = strength_unscaled_ref(As, L.indptr, L.indices, L.bs, theta)
+            print(f"{which} level {l} scale 2^{e}: {int(new.sum())} strong of {new.size}; unscaled arithmetic {int(lost.sum())}")
+            assert l > 0 or not np.array_equal(lost, new), (which, l, e)
 
 
 def test_iteration_counts_on_the_anisotropic_systems():

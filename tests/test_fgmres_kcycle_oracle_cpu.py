@@ -122,12 +122,14 @@ def gcr2_ref(A, B, r, trace=None):
     c2 = B(r1)
     v2 = A @ c2
     g, beta, a2 = v2 @ v1, v2 @ v2, v2 @ r1
-    rho2 = beta - g * g / rho1
+    gr = g / rho1                                          # ratios only: no product of two dot products (a fourth power of |r|)
+    rho2 = beta - g * gr
     x1 = alpha1 * c1
     if not np.isfinite(rho2) or rho2 <= K_DEPENDENT * beta:
         x, hit = x1, "rho2"
     else:
-        x, hit = (alpha1 - g * a2 / (rho1 * rho2)) * c1 + (a2 / rho2) * c2, None
+        x2 = a2 / rho2
+        x, hit = (alpha1 - gr * x2) * c1 + x2 * c2, None
     if trace is not None:
         trace.append((r, x1, x, hit))
     return x
@@ -307,6 +309,25 @@ def test_guards():
 
     x = gcr2_ref(A, B, r, trace)
     assert trace[-1][3] == "rho2" and np.array_equal(x, ((v1 @ r) / (v1 @ v1)) * c1)
+
+
+@pytest.mark.parametrize("which", ["heat48", "aniso", "p2_rbm"])
+def test_the_k_cycle_is_homogeneous_in_r(which):
+    """K(2^e r) == 2^e K(r) bit for bit, finite, and without a guard at |e| up to 480: the K-cycle is not linear, but its
+    coefficients are ratios of dot products, homogeneous of degree 0, and every other step is linear. The dot products are second
+    powers of |r| (2^+-960 here, inside double); the products of two of them that earlier versions formed are not."""
+    S, _, levels = system(which)
+    assert len(levels) >= 3
+    r = np.random.Generator(np.random.PCG64(9)).normal(size=S.shape[0])
+    trace = {}
+    z = kcycle_ref(levels, r, trace)
+    assert np.isfinite(z).all() and all(rec[3] is None for recs in trace.values() for rec in recs)
+    for e in (300, -300, 400, -400, 480, -480):
+        trace = {}
+        ze = kcycle_ref(levels, np.ldexp(r, e), trace)
+        assert np.isfinite(ze).all(), (which, e)
+        assert all(rec[3] is None for recs in trace.values() for rec in recs), (which, e)
+        assert np.array_equal(ze, np.ldexp(z, e)), (which, e, np.abs(np.ldexp(ze, -e) - z).max())
 
 
 MEASURED = {"p2_rbm": (59, 52), "heat": (16, 16), "nonsym": (136, 123), "aniso": (18, 18)}
