@@ -196,6 +196,8 @@ _SIGNATURES = {
     "dxo_csr_block_jacobi": (C.c_int, [_P, _P, _P, _P]),
     "dxo_block_jacobi_apply": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P]),
     "dxo_krylov_create": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(_P)]),
+    "dxo_krylov_create_basis": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.POINTER(_P)]),
+    "dxo_krylov_basis_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(C.c_int64)]),
     "dxo_krylov_destroy": (C.c_int, [_P, _P]),
     "dxo_krylov_gmres": (C.c_int, [_P, _P, C.POINTER(KrylovOp), C.POINTER(KrylovPc), _P, _P, C.c_double, C.c_double, C.c_int, C.c_int,
                                    C.POINTER(KrylovInfo)]),
@@ -435,7 +437,7 @@ class Context:
         self._pinned: list[tuple[int, np.ndarray]] = []
         self._pool = _PinnedPool(self.lib)
         self._lock = threading.RLock()   # dxo_ctx itself also serialises its entry points (include/dxo.h)
-        self._krylov_ws: dict = {}       # krylov.py: Krylov workspaces by (n, restart), freed by close()
+        self._krylov_ws: dict = {}       # krylov.py: Krylov workspaces by (n, restart), or (n, restart, basis) for a basis other than fp64, freed by close()
 
     @classmethod
     def borrow(cls, handle: int, device: int = 0) -> "Context":

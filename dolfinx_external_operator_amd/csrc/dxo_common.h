@@ -93,6 +93,8 @@ struct dxo_ctx {
     int64_t adjoint_atomics = 0;        // adjoint kernels and dxo_bilinear_assemble: 1 = fp64 atomics into the dof vector, 0 = element vectors + node sums
     int64_t assemble_chunk_cells = 0;   // dxo_bilinear_assemble: cells per chunk of the element-matrix scratch (0: as many as fit 1 GiB)
     int64_t krylov_reorth = 1;          // dxo_krylov_gmres: 1 = classical Gram-Schmidt with one reorthogonalisation pass, 0 = one pass
+    int64_t krylov_basis_width = 4;     // Krylov solves on a DXO_KRYLOV_BASIS_FP32 workspace: consecutive rows of the float basis per thread (1, 2 or 4;
+                                        // orthogonalisation of GMRES(30), P2 1291^2: 1.65 / 1.11 / 0.82 ms against 1.88 with the double basis)
     int64_t amg_rank_tol = 10;          // dxo_amg_create_nns: a column of an aggregate's near-null space that keeps no more than 10^-value of its norm is dead
     int64_t spmv_lanes = 0;             // dxo_csr_spmv and the Krylov solves: lanes per node (8, 16, 32, 64; 0 = from the mean neighbour count)
     int64_t mc_part_points = (int64_t)1 << 30;   // Mohr-Coulomb: points per classify/Newton pass (int32 list entries)

@@ -24,6 +24,13 @@
 // Flexible GMRES (dxo_krylov_fgmres) is the same sequence with z_j = M v_j kept in a second basis Z [m][ld]: w = A z_j, and the update
 // at the end of a cycle is x += sum_j y_j z_j (kr_combine on Z), with no further preconditioner call. M may therefore change from
 // step to step (a callback that iterates, the K-cycle of amg.hip). Z is allocated at the first flexible solve on a workspace.
+//
+// Compressed basis (dxo_krylov_create_basis, DXO_KRYLOV_BASIS_FP32): the rows of V are stored as float [m + 1][ldf], everything else
+// (dot products, updates, H, the rotations, x, the second basis of the flexible solver) stays double. A new basis vector is rounded
+// once, t = (float)(w[i] hinv), written to V[j + 1] and widened back into w, which the next step hands to M and A: the vector the
+// solver works with is exactly the one it stored, so the Arnoldi relation holds for the stored basis and no row is ever widened in a
+// pass of its own. w alternates between two double vectors W0 / W1. The row kernels over a float basis (kf_*) keep the grid, the
+// per-thread row sets and the reductions of the double ones; a thread owns FW consecutive rows (option "krylov_basis_width").
 #include "csr.h"
 #include "dxo_common.h"
 #include "krylov_internal.h"
@@ -32,6 +39,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <type_traits>
 
 #ifndef DXO_KR_BLOCK
 #define DXO_KR_BLOCK 256
@@ -41,16 +49,21 @@ struct dxo_krylov {
     int64_t n = 0, ld = 0;     // vector length and its padded stride (a multiple of 32 doubles)
     int m = 0;                 // restart length
     int nb = 0;                // workgroups of the row kernels = partials per product (fixed for the workspace)
-    double* vec = nullptr;     // [m + 1 + 4][ld]: the basis V, then Z, R, T, Q
+    int basis = DXO_KRYLOV_BASIS_FP64;
+    int64_t ldf = 0;           // FP32 basis: the stride of a float row (n padded to a multiple of 64 floats: rows are 256-byte aligned)
+    float* vf = nullptr;       // FP32 basis: [m + 1][ldf]
+    double* vec = nullptr;     // FP64 basis: [m + 1 + 4][ld]: the basis V, then Z, R, T, Q; FP32 basis: [6][ld]: Z, R, T, Q, W0, W1
     double* zb = nullptr;      // [m][ld]: the preconditioned basis of dxo_krylov_fgmres, absent until its first solve here
     double* part = nullptr;    // [m + 2][nb] per-block partials (the last row: |w|^2)
     double* sc = nullptr;      // small state (offsets below)
     int* st = nullptr;         // status words
     double* V() const { return vec; }
-    double* Z() const { return vec + (int64_t)(m + 1) * ld; }
-    double* R() const { return vec + (int64_t)(m + 2) * ld; }
-    double* T() const { return vec + (int64_t)(m + 3) * ld; }
-    double* Q() const { return vec + (int64_t)(m + 4) * ld; }
+    double* Z() const { return vec + (int64_t)(basis == DXO_KRYLOV_BASIS_FP32 ? 0 : m + 1) * ld; }
+    double* R() const { return Z() + ld; }
+    double* T() const { return Z() + 2 * ld; }
+    double* Q() const { return Z() + 3 * ld; }
+    double* W(int k) const { return Z() + (int64_t)(4 + (k & 1)) * ld; }      // FP32 basis only
+    int64_t work_rows() const { return basis == DXO_KRYLOV_BASIS_FP32 ? 6 : m + 5; }
     // state layout: H [m][m + 1] (column j at j*(m+1)), g [m + 1], cs [m], sn [m], y [m], c [m + 1], scalars [16]
     int64_t o_g() const { return (int64_t)m * (m + 1); }
     int64_t o_cs() const { return o_g() + m + 1; }
@@ -240,6 +253,151 @@ __global__ __launch_bounds__(DXO_KR_BLOCK) void kr_scale(int64_t n, const double
     const double a = s[0];
     const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
     for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) y[i] = x[i] * a;
+}
+
+// ---- the same row kernels over a float basis Vf [.][ldf]. A thread owns FW consecutive rows i0 .. i0 + FW - 1 of every trip of the
+// grid: one 4 FW-byte load per basis row, FW / 2 16-byte loads of w. Row starts are aligned (ldf, ld and i0 are multiples of FW, the
+// buffers of hipMalloc); n is not, so the last group of a vector is ragged: it is loaded entry by entry and the absent entries take
+// no part. Sums run over a thread's entries in ascending order, then as in the double kernels.
+template <int FW>
+struct KfRows {
+    int64_t i0;
+    int cnt;      // entries of this group that exist: FW, or fewer at the tail
+    __device__ __forceinline__ KfRows(int64_t i, int64_t n) : i0(i), cnt(n - i >= FW ? FW : (int)(n - i)) {}
+    __device__ __forceinline__ bool full() const { return cnt == FW; }
+    template <class T>
+    __device__ __forceinline__ void load(const T* __restrict__ p, T (&v)[FW]) const {
+        if (full()) {
+            struct alignas(sizeof(T) * FW) Pack { T e[FW]; };
+            const Pack q = *reinterpret_cast<const Pack*>(p + i0);
+#pragma unroll
+            for (int c = 0; c < FW; ++c) v[c] = q.e[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < FW; ++c) v[c] = c < cnt ? p[i0 + c] : T(0);
+        }
+    }
+    template <class T>
+    __device__ __forceinline__ void store(T* __restrict__ p, const T (&v)[FW]) const {
+        if (full()) {
+            struct alignas(sizeof(T) * FW) Pack { T e[FW]; };
+            Pack q;
+#pragma unroll
+            for (int c = 0; c < FW; ++c) q.e[c] = v[c];
+            *reinterpret_cast<Pack*>(p + i0) = q;
+        } else {
+#pragma unroll
+            for (int c = 0; c < FW; ++c)
+                if (c < cnt) p[i0 + c] = v[c];
+        }
+    }
+};
+
+// part[k * nb + block] = sum over the block's rows of (double)Vf_k[i] w[i], k < nk
+template <int KMAX, int FW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kf_multidot(int64_t n, const float* __restrict__ Vf, int64_t ldf, int nk,
+                                                            const double* __restrict__ w, double* __restrict__ part) {
+    __shared__ double lds[DXO_KR_BLOCK / 64][KMAX];
+    double acc[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
+    for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
+        const KfRows<FW> g(i, n);
+        double wi[FW];
+        g.load(w, wi);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            if (k < nk) {
+                float v[FW];
+                g.load(Vf + k * ldf, v);
+#pragma unroll
+                for (int c = 0; c < FW; ++c) acc[k] = fma((double)v[c], wi[c], acc[k]);      // an absent entry adds 0 * 0
+            }
+        }
+    }
+    const int wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        if (k < nk) {
+            const double s = wave_sum(acc[k]);
+            if ((threadIdx.x & 63) == 0) lds[wv][k] = s;
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nk; k += DXO_KR_BLOCK) {
+        double s = 0.0;
+        for (int q = 0; q < DXO_KR_BLOCK / 64; ++q) s += lds[q][k];
+        part[(int64_t)k * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// w -= sum_k (double)Vf_k h_k (k ascending), and npart[block] = the block's share of |w|^2
+template <int FW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kf_update(int64_t n, const float* __restrict__ Vf, int64_t ldf, int nk, const double* __restrict__ h,
+                                                          double* __restrict__ w, double* __restrict__ npart) {
+    __shared__ double lds[DXO_KR_BLOCK / 64];
+    double acc = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
+    for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
+        const KfRows<FW> g(i, n);
+        double s[FW];
+        g.load(w, s);
+        for (int k = 0; k < nk; ++k) {
+            float v[FW];
+            g.load(Vf + k * ldf, v);
+            const double hk = h[k];
+#pragma unroll
+            for (int c = 0; c < FW; ++c) s[c] = fma(-(double)v[c], hk, s[c]);
+        }
+        g.store(w, s);
+#pragma unroll
+        for (int c = 0; c < FW; ++c) acc = fma(s[c], s[c], acc);      // absent entries are 0
+    }
+    acc = block_sum(acc, lds);
+    if (threadIdx.x == 0) npart[blockIdx.x] = acc;
+}
+
+// out = sum_k (double)Vf_k y_k (k ascending)
+template <int FW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kf_combine(int64_t n, const float* __restrict__ Vf, int64_t ldf, int nk, const double* __restrict__ y,
+                                                           double* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
+    for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
+        const KfRows<FW> g(i, n);
+        double s[FW];
+#pragma unroll
+        for (int c = 0; c < FW; ++c) s[c] = 0.0;
+        for (int k = 0; k < nk; ++k) {
+            float v[FW];
+            g.load(Vf + k * ldf, v);
+            const double yk = y[k];
+#pragma unroll
+            for (int c = 0; c < FW; ++c) s[c] = fma((double)v[c], yk, s[c]);
+        }
+        g.store(out, s);
+    }
+}
+
+// the new basis vector: t = (float)(x[i] s[0]) (round to nearest even), row[i] = t, y[i] = (double)t (y may be x)
+template <int FW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kf_scale_store(int64_t n, const double* x, const double* __restrict__ s, float* __restrict__ row,
+                                                               double* y) {
+    const double a = s[0];
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
+    for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
+        const KfRows<FW> g(i, n);
+        double xi[FW];
+        float t[FW];
+        g.load(x, xi);
+#pragma unroll
+        for (int c = 0; c < FW; ++c) {
+            t[c] = (float)(xi[c] * a);
+            xi[c] = (double)t[c];
+        }
+        g.store(row, t);
+        g.store(y, xi);
+    }
 }
 
 // y += sign * a[0] * x
@@ -538,6 +696,66 @@ void kr_multidot_launch(const KrCall& K, int nk, const double* w) {
     else hipLaunchKernelGGL((kr_multidot<64>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
 }
 
+// FW of the float-basis kernels as a compile-time constant: f(std::integral_constant<int, FW>)
+template <class F>
+void kf_width(const dxo_ctx* ctx, F f) {
+    if (ctx->krylov_basis_width == 1) f(std::integral_constant<int, 1>{});
+    else if (ctx->krylov_basis_width == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 4>{});
+}
+
+// the steps of a cycle that touch the basis, on either kind of workspace. FP64: the rows of V are the vectors themselves.
+// FP32: the vector of step j is W(j), its rounded copy row j of vf
+struct KrBasis {
+    const KrCall& K;
+    dxo_krylov* ws;
+    const dim3 G, B;
+    const bool f32;
+    explicit KrBasis(const KrCall& k) : K(k), ws(k.ws), G(k.ws->nb), B(DXO_KR_BLOCK), f32(k.ws->basis == DXO_KRYLOV_BASIS_FP32) {}
+    double* vector(int j) const { return f32 ? ws->W(j) : ws->V() + (int64_t)j * ws->ld; }
+    // vector(j) = x * s[0], stored as row j (x may be vector(j))
+    void scale_store(int j, const double* x, const double* s) const {
+        if (!f32) {
+            hipLaunchKernelGGL(kr_scale, G, B, 0, K.s, ws->n, x, s, vector(j));
+            return;
+        }
+        kf_width(K.ctx, [&](auto fw) {
+            hipLaunchKernelGGL((kf_scale_store<fw()>), G, B, 0, K.s, ws->n, x, s, ws->vf + (int64_t)j * ws->ldf, vector(j));
+        });
+    }
+    // part = partials of the products of w with rows 0 .. nk - 1
+    void multidot(int nk, const double* w) const {
+        if (!f32) {
+            kr_multidot_launch(K, nk, w);
+            return;
+        }
+        kf_width(K.ctx, [&](auto fw) {
+            constexpr int FW = fw();
+            if (nk <= 4) hipLaunchKernelGGL((kf_multidot<4, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
+            else if (nk <= 8) hipLaunchKernelGGL((kf_multidot<8, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
+            else if (nk <= 16) hipLaunchKernelGGL((kf_multidot<16, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
+            else if (nk <= 32) hipLaunchKernelGGL((kf_multidot<32, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
+            else hipLaunchKernelGGL((kf_multidot<64, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
+        });
+    }
+    // w -= sum_k row_k h_k, npart = partials of |w|^2
+    void update(int nk, const double* h, double* w, double* npart) const {
+        if (!f32) {
+            hipLaunchKernelGGL(kr_update, G, B, 0, K.s, ws->n, ws->V(), ws->ld, nk, h, w, npart);
+            return;
+        }
+        kf_width(K.ctx, [&](auto fw) { hipLaunchKernelGGL((kf_update<fw()>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, h, w, npart); });
+    }
+    // out = sum_k row_k y_k
+    void combine(int nk, const double* y, double* out) const {
+        if (!f32) {
+            hipLaunchKernelGGL(kr_combine, G, B, 0, K.s, ws->n, ws->V(), ws->ld, nk, y, out);
+            return;
+        }
+        kf_width(K.ctx, [&](auto fw) { hipLaunchKernelGGL((kf_combine<fw()>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, y, out); });
+    }
+};
+
 // FLEX: z_j = M v_j goes to row j of the second basis and the update combines those rows; otherwise one Z and M once more at the update
 template <bool FLEX>
 int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
@@ -551,6 +769,7 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
     double* npart = ws->part + (int64_t)(m + 1) * ws->nb;
     const dim3 G(ws->nb), B(DXO_KR_BLOCK);
     const bool reorth = ctx->krylov_reorth != 0;
+    const KrBasis V(K);
     // |b|
     K.norm(b, S + S_NORM);
     double bnorm = 0.0;
@@ -574,26 +793,26 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
         }
         if (total >= max_it || info->breakdown) break;
         ++info->restarts;
-        hipLaunchKernelGGL(kr_scale, G, B, 0, s, n, ws->R(), S + S_INV, ws->V());
+        V.scale_store(0, ws->R(), S + S_INV);
         hipLaunchKernelGGL(kr_cycle_init, dim3(1), dim3(64), 0, s, sc, ws->st, m, ws->o_g(), ws->o_s());
         int done = 0, status[2] = {-1, 0};
         for (int j = 0; j < m && total + j < max_it; ++j) {
-            double* w = ws->V() + (int64_t)(j + 1) * ws->ld;
+            double* w = V.vector(j + 1);
             double* h = sc + (int64_t)j * (m + 1);
             double* zj = FLEX ? ws->zb + (int64_t)j * ws->ld : ws->Z();
-            if ((rc = K.precond(ws->V() + (int64_t)j * ws->ld, zj)) != DXO_OK) return rc;
+            if ((rc = K.precond(V.vector(j), zj)) != DXO_OK) return rc;
             if ((rc = K.apply(zj, w)) != DXO_OK) return rc;
-            kr_multidot_launch(K, j + 1, w);
+            V.multidot(j + 1, w);
             hipLaunchKernelGGL(kr_reduce, dim3(j + 1), B, 0, s, ws->part, ws->nb, h, (double*)nullptr, 0, (double*)nullptr);
-            hipLaunchKernelGGL(kr_update, G, B, 0, s, n, ws->V(), ws->ld, j + 1, h, w, npart);
+            V.update(j + 1, h, w, npart);
             if (reorth) {
                 double* c = sc + ws->o_c();
-                kr_multidot_launch(K, j + 1, w);
+                V.multidot(j + 1, w);
                 hipLaunchKernelGGL(kr_reduce, dim3(j + 1), B, 0, s, ws->part, ws->nb, c, h, 0, (double*)nullptr);
-                hipLaunchKernelGGL(kr_update, G, B, 0, s, n, ws->V(), ws->ld, j + 1, c, w, npart);
+                V.update(j + 1, c, w, npart);
             }
             hipLaunchKernelGGL(kr_reduce, dim3(1), B, 0, s, npart, ws->nb, S + S_HNORM, (double*)nullptr, 1, S + S_HINV);
-            hipLaunchKernelGGL(kr_scale, G, B, 0, s, n, w, S + S_HINV, w);
+            V.scale_store(j + 1, w, S + S_HINV);
             hipLaunchKernelGGL(kr_givens, dim3(1), dim3(64), 0, s, sc, ws->st, j, m, ws->o_g(), ws->o_cs(), ws->o_sn(), ws->o_s(), tol);
             done = j + 1;
             if ((total + done) % check_every == 0 || done == m || total + done == max_it) {
@@ -611,7 +830,7 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
                 hipLaunchKernelGGL(kr_combine, G, B, 0, s, n, ws->zb, ws->ld, k, sc + ws->o_y(), ws->T());
                 hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ONE, 1.0, ws->T(), x);
             } else {
-                hipLaunchKernelGGL(kr_combine, G, B, 0, s, n, ws->V(), ws->ld, k, sc + ws->o_y(), ws->T());
+                V.combine(k, sc + ws->o_y(), ws->T());
                 if ((rc = K.precond(ws->T(), ws->Z())) != DXO_OK) return rc;
                 hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ONE, 1.0, ws->Z(), x);
             }
@@ -779,35 +998,59 @@ extern "C" int dxo_block_jacobi_apply(dxo_ctx* ctx, int bs, int64_t n, const dou
     return rc != DXO_OK ? rc : end;
 }
 
-extern "C" int dxo_krylov_create(dxo_ctx* ctx, int64_t n, int restart, dxo_krylov** out) {
+extern "C" int dxo_krylov_create_basis(dxo_ctx* ctx, int64_t n, int restart, int basis, dxo_krylov** out) {
     if (!ctx || !out) return DXO_E_NULL;
     DXO_LOCK(ctx);
     *out = nullptr;
     if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_krylov_create: n < 0");
     if (restart < 1 || restart > KR_MAX_RESTART) return dxo_fail(ctx, DXO_E_SIZE, "dxo_krylov_create: restart must lie in [1, 64]");
+    if (basis != DXO_KRYLOV_BASIS_FP64 && basis != DXO_KRYLOV_BASIS_FP32)
+        return dxo_fail(ctx, DXO_E_OPTION, "dxo_krylov_create_basis: basis must be DXO_KRYLOV_BASIS_FP64 (0) or DXO_KRYLOV_BASIS_FP32 (1)");
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     dxo_krylov* w = new dxo_krylov;
     w->n = n;
     w->m = restart;
+    w->basis = basis;
     w->ld = std::max<int64_t>(32, (n + 31) / 32 * 32);
     w->nb = kr_grid(ctx, n, 4);
+    const bool f32 = basis == DXO_KRYLOV_BASIS_FP32;
+    if (f32) w->ldf = std::max<int64_t>(64, (n + 63) / 64 * 64);
     auto fail = [&](hipError_t e, const char* what) {
-        for (void* p : {(void*)w->vec, (void*)w->part, (void*)w->sc, (void*)w->st})
+        for (void* p : {(void*)w->vec, (void*)w->vf, (void*)w->part, (void*)w->sc, (void*)w->st})
             if (p) (void)hipFree(p);
         delete w;
         return dxo_hip_fail(ctx, e, what);
     };
     hipError_t e;
-    if ((e = hipMalloc((void**)&w->vec, (size_t)(w->m + 5) * w->ld * sizeof(double))) != hipSuccess) return fail(e, "dxo_krylov_create: basis");
+    const size_t vec_bytes = (size_t)w->work_rows() * w->ld * sizeof(double), vf_bytes = (size_t)(w->m + 1) * w->ldf * sizeof(float);
+    if ((e = hipMalloc((void**)&w->vec, vec_bytes)) != hipSuccess) return fail(e, "dxo_krylov_create: basis");
+    if (f32 && (e = hipMalloc((void**)&w->vf, vf_bytes)) != hipSuccess) return fail(e, "dxo_krylov_create: float basis");
     if ((e = hipMalloc((void**)&w->part, (size_t)(w->m + 2) * w->nb * sizeof(double))) != hipSuccess) return fail(e, "dxo_krylov_create: partials");
     if ((e = hipMalloc((void**)&w->sc, (size_t)w->sc_doubles() * sizeof(double))) != hipSuccess) return fail(e, "dxo_krylov_create: state");
     if ((e = hipMalloc((void**)&w->st, 16 * sizeof(int))) != hipSuccess) return fail(e, "dxo_krylov_create: status");
     std::vector<double> init((size_t)w->sc_doubles(), 0.0);
     init[(size_t)(w->o_s() + S_ONE)] = 1.0;
     if ((e = hipMemcpy(w->sc, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "dxo_krylov_create: state");
-    if ((e = hipMemset(w->vec, 0, (size_t)(w->m + 5) * w->ld * sizeof(double))) != hipSuccess) return fail(e, "dxo_krylov_create: basis");
+    if ((e = hipMemset(w->vec, 0, vec_bytes)) != hipSuccess) return fail(e, "dxo_krylov_create: basis");
+    if (f32 && (e = hipMemset(w->vf, 0, vf_bytes)) != hipSuccess) return fail(e, "dxo_krylov_create: float basis");
     if ((e = hipMemset(w->st, 0, 16 * sizeof(int))) != hipSuccess) return fail(e, "dxo_krylov_create: status");
     *out = w;
+    return DXO_OK;
+}
+
+extern "C" int dxo_krylov_create(dxo_ctx* ctx, int64_t n, int restart, dxo_krylov** out) {
+    return dxo_krylov_create_basis(ctx, n, restart, DXO_KRYLOV_BASIS_FP64, out);
+}
+
+extern "C" int dxo_krylov_basis_info(dxo_ctx* ctx, const dxo_krylov* ws, int* basis, int64_t* basis_bytes, const void** rows, int64_t* ld) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!ws) return dxo_fail(ctx, DXO_E_NULL, "dxo_krylov_basis_info: NULL workspace");
+    const bool f32 = ws->basis == DXO_KRYLOV_BASIS_FP32;
+    if (basis) *basis = ws->basis;
+    if (basis_bytes) *basis_bytes = f32 ? (int64_t)(ws->m + 1) * ws->ldf * (int64_t)sizeof(float) : (int64_t)(ws->m + 1) * ws->ld * (int64_t)sizeof(double);
+    if (rows) *rows = f32 ? (const void*)ws->vf : (const void*)ws->vec;
+    if (ld) *ld = f32 ? ws->ldf : ws->ld;
     return DXO_OK;
 }
 
@@ -816,7 +1059,7 @@ extern "C" int dxo_krylov_destroy(dxo_ctx* ctx, dxo_krylov* ws) {
     DXO_LOCK(ctx);
     if (ctx) (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {(void*)ws->vec, (void*)ws->zb, (void*)ws->part, (void*)ws->sc, (void*)ws->st})
+    for (void* p : {(void*)ws->vec, (void*)ws->vf, (void*)ws->zb, (void*)ws->part, (void*)ws->sc, (void*)ws->st})
         if (p) (void)hipFree(p);
     delete ws;
     return DXO_OK;
@@ -833,6 +1076,8 @@ extern "C" int dxo_krylov_cg(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* 
                              double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
+    if (ws && ws->basis != DXO_KRYLOV_BASIS_FP64)
+        return dxo_fail(ctx, DXO_E_OPTION, "dxo_krylov_cg: CG keeps no basis: the workspace must be of kind DXO_KRYLOV_BASIS_FP64");
     return kr_solve(ctx, "dxo_krylov_cg", cg_impl, false, ws, op, pc, b, x, rtol, atol, max_it, check_every, info);
 }
 

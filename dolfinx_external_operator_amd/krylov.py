@@ -18,6 +18,7 @@ _SMOOTHERS = {"jacobi": 0, "chebyshev": 1}           # DXO_AMG_SMOOTH_*
 _RHO_KINDS = {"inf-norm": 0, "power": 1}             # DXO_AMG_RHO_*
 _CYCLES = {"V": 0, "K": 1}                           # DXO_AMG_CYCLE_*
 _PRECISIONS = {"fp64": 0, "fp32": 1}                 # DXO_AMG_PRECISION_*
+_BASES = {"fp64": 0, "fp32": 1}                      # DXO_KRYLOV_BASIS_*
 
 
 def _torch():
@@ -41,7 +42,9 @@ def _use_current_stream(ctx) -> None:
 @dataclass
 class KrylovResult:
     """What gmres / fgmres / cg return: the solution, the iterations up to the converged step, the true relative residual |b - A x| / |b|,
-    whether it met the tolerance, whether the iteration broke down, the cycles started and the wall ms of the solve."""
+    whether it met the tolerance, whether the iteration broke down, the cycles started, the wall ms of the solve, the storage of the
+    Krylov basis ("fp64" or "fp32") and the bytes of its rows (V alone: the second basis of fgmres, always double, is not counted;
+    0 for cg, which keeps none)."""
     x: object
     iterations: int
     residual: float
@@ -49,6 +52,8 @@ class KrylovResult:
     breakdown: bool = False
     restarts: int = 0
     ms: float = 0.0
+    basis: str = "fp64"
+    basis_bytes: int = 0
 
 
 class BlockJacobi:
@@ -504,32 +509,64 @@ def csr_matvec(A, x, y=None, alpha: float = 1.0, beta: float = 0.0):
 
 
 class _Workspace:
-    """dxo_krylov of one (n, restart). The context keeps a few of them (Context._krylov_ws) for later solves of the same size;
-    Context.close() frees them. The finalizer holds the library and the raw context handle, not the Context."""
+    """dxo_krylov of one (n, restart) and kind of basis. The context keeps a few of them (Context._krylov_ws) for later solves of the same
+    size; Context.close() frees them. The finalizer holds the library and the raw context handle, not the Context."""
 
-    def __init__(self, ctx, n: int, restart: int):
+    def __init__(self, ctx, n: int, restart: int, basis: str = "fp64"):
         h = C.c_void_p()
-        ctx.check(ctx.lib.dxo_krylov_create(ctx._h, int(n), int(restart), C.byref(h)), "dxo_krylov_create")
+        ctx.check(ctx.lib.dxo_krylov_create_basis(ctx._h, int(n), int(restart), _BASES[basis], C.byref(h)), "dxo_krylov_create_basis")
         self._h = h
+        self.ctx, self.n, self.restart = ctx, int(n), int(restart)
         self._fin = weakref.finalize(self, ctx.lib.dxo_krylov_destroy, C.c_void_p(ctx._h.value), h)
         self._fin.atexit = False   # at interpreter exit the device memory goes with the process
 
     def close(self) -> None:
         self._fin()
 
+    def basis_info(self) -> tuple:
+        """(kind, bytes of the basis rows, device pointer of row 0, row stride in elements) (dxo_krylov_basis_info)."""
+        kind, nbytes, rows, ld = C.c_int(), C.c_int64(), C.c_void_p(), C.c_int64()
+        self.ctx.check(self.ctx.lib.dxo_krylov_basis_info(self.ctx._h, self._h, C.byref(kind), C.byref(nbytes), C.byref(rows), C.byref(ld)),
+                       "dxo_krylov_basis_info")
+        return {v: k for k, v in _BASES.items()}[kind.value], int(nbytes.value), rows.value, int(ld.value)
 
-def _workspace(ctx, n: int, restart: int) -> _Workspace:
+
+def _ws_key(n: int, restart: int, basis: str) -> tuple:
+    """The cache key of a workspace: (n, restart) for the fp64 basis, as before the basis could be chosen, (n, restart, basis) for
+    any other."""
+    return (int(n), int(restart)) if basis == "fp64" else (int(n), int(restart), basis)
+
+
+def _workspace(ctx, n: int, restart: int, basis: str = "fp64") -> _Workspace:
     cache = ctx.__dict__.setdefault("_krylov_ws", {})
-    key = (int(n), int(restart))
+    key = _ws_key(n, restart, basis)
     if key not in cache:
         if len(cache) >= 4:    # a few sizes per context: the oldest basis is freed
             cache.pop(next(iter(cache))).close()
-        cache[key] = _Workspace(ctx, n, restart)
+        cache[key] = _Workspace(ctx, n, restart, basis)
     return cache[key]
 
 
-def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxiter, check_every: int, ctx=None) -> KrylovResult:
+def krylov_basis_rows(ctx, n: int, restart: int, basis: str = "fp32"):
+    """The stored basis of the last solve on the context's (n, restart, basis) workspace as a NumPy array (restart + 1, ld), float32
+    or float64 by the kind: row j is v_j in its first n entries, the padding up to the row stride ld is zero. Rows beyond the last
+    cycle's steps hold what earlier cycles left. A copy; synchronises the stream. For tests and reports."""
     torch = _torch()
+    ws = ctx.__dict__.get("_krylov_ws", {}).get(_ws_key(n, restart, basis))
+    if ws is None:
+        raise ValueError(f"krylov_basis_rows: no solve with n = {n}, restart = {restart}, basis = {basis!r} on this context")
+    kind, _, rows, ld = ws.basis_info()
+    dev = torch.device("cuda", ctx.device)
+    torch.cuda.current_stream(dev).synchronize()
+    view = _CudaArrayView(ws, rows, (int(restart) + 1) * ld, "<f4" if kind == "fp32" else "<f8")
+    return torch.as_tensor(view, device=dev).cpu().numpy().copy().reshape(int(restart) + 1, ld)
+
+
+def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxiter, check_every: int, ctx=None,
+           basis: str = "fp64") -> KrylovResult:
+    torch = _torch()
+    if not isinstance(basis, str) or basis not in _BASES:
+        raise ValueError(f"{entry}: basis must be one of {sorted(_BASES)}")
     from .operand_eval import DeviceCSR
 
     if isinstance(A, DeviceCSR):
@@ -608,7 +645,7 @@ def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxit
         raise TypeError(f"{entry}: M must be None, a BlockJacobi, an AMG, a tensor holding an inverse diagonal or a callable (r, out)")
     if maxiter is None:
         maxiter = max(1000, 10 * restart)
-    ws = _workspace(ctx, n, restart)
+    ws = _workspace(ctx, n, restart, basis)
     info = KrylovInfo()
     _use_current_stream(ctx)
     rc = getattr(ctx.lib, entry)(ctx._h, ws._h, C.byref(op), C.byref(pc), C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), float(rtol),
@@ -617,11 +654,12 @@ def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxit
         raise failure[0]
     ctx.check(rc, entry)
     return KrylovResult(x=x, iterations=int(info.iterations), residual=float(info.residual), converged=bool(info.converged),
-                        breakdown=bool(info.breakdown), restarts=int(info.restarts), ms=float(info.ms))
+                        breakdown=bool(info.breakdown), restarts=int(info.restarts), ms=float(info.ms), basis=basis,
+                        basis_bytes=0 if entry == "dxo_krylov_cg" else ws.basis_info()[1])
 
 
 def gmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: float = 0.0, maxiter: int | None = None,
-          check_every: int = 8, ctx=None) -> KrylovResult:
+          check_every: int = 8, ctx=None, basis: str = "fp64") -> KrylovResult:
     """Solve A x = b by restarted GMRES(restart) with right preconditioning on the device (dxo_krylov_gmres).
 
     A: a DeviceCSR, or a callable (v, out) that sets out = A v on the device (e.g. DeviceMesh.bilinear_apply with option
@@ -633,20 +671,33 @@ def gmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: fl
     which raises ValueError here) belongs to fgmres. An AMG with precision="fp32" is a fixed linear operator up to single-precision
     rounding and is accepted; it may cost one more restart to reach tolerances below about 1e-7. x: the initial guess, overwritten with the
     solution (zeros if None). Converged when |b - A x| <= max(rtol |b|, atol); not converging within maxiter gives converged False,
-    not an exception."""
-    return _solve("dxo_krylov_gmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx)
+    not an exception.
+
+    basis: "fp64" (the default, the solver of earlier versions bit for bit) or "fp32", a compressed basis (dxo_krylov_create_basis):
+    the Krylov vectors are stored in float, half the bytes the orthogonalisation reads and half the basis memory, while every dot
+    product, update, Hessenberg entry, rotation and x stay double, and M and A are given exactly the vector that was stored. What it
+    guarantees: the stopping test is on the double true residual b - A x, formed at every restart, so a converged result meets the
+    tolerance as with "fp64"; a solve is bit-reproducible. What it may cost: the Hessenberg estimate inside a cycle is trustworthy
+    to about 2^-24 relative to the cycle's starting residual, so one cycle cannot gain much more than seven digits on its own
+    estimate: expect at most one extra cycle at tight tolerances. Anything else raises ValueError."""
+    return _solve("dxo_krylov_gmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx, basis)
 
 
 def fgmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: float = 0.0, maxiter: int | None = None,
-           check_every: int = 8, ctx=None) -> KrylovResult:
+           check_every: int = 8, ctx=None, basis: str = "fp64") -> KrylovResult:
     """Solve A x = b by flexible GMRES(restart) on the device (dxo_krylov_fgmres), with the arguments and the stopping rule of gmres.
 
     M need not be a fixed linear operator: it may differ from step to step (a callable that runs an inner solve, an AMG with the
     K-cycle). The preconditioned vectors z_j = M v_j are kept in a second basis (restart more vectors, allocated at the first
     flexible solve of a size) and the solution is updated with them, so M is called once per iteration and never at the update.
     With a fixed M it takes the iterations of gmres. It is the recommended partner of an AMG with precision="fp32": the update uses the
-    stored z_j, so the single-precision rounding of the cycle never enters the solution a second time."""
-    return _solve("dxo_krylov_fgmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx)
+    stored z_j, so the single-precision rounding of the cycle never enters the solution a second time.
+
+    basis: as in gmres, with its guarantees (the stopping test on the double true residual) and its cost (a cycle's own estimate is
+    good to about 2^-24 of its starting residual: at most one extra cycle at tight tolerances). "fp32" compresses V only. The second
+    basis Z stays double: the z_j = M v_j are not normalised, so their range is the caller's, and Z is written once and read once
+    per cycle. `basis_bytes` of the result counts V alone."""
+    return _solve("dxo_krylov_fgmres", A, b, x, M, restart, rtol, atol, maxiter, check_every, ctx, basis)
 
 
 def cg(A, b, x=None, M=None, rtol: float = 1e-10, atol: float = 0.0, maxiter: int | None = None, check_every: int = 8,
@@ -657,4 +708,4 @@ def cg(A, b, x=None, M=None, rtol: float = 1e-10, atol: float = 0.0, maxiter: in
     return _solve("dxo_krylov_cg", A, b, x, M, 1, rtol, atol, maxiter, check_every, ctx)
 
 
-__all__ = ["AMG", "BlockJacobi", "KrylovResult", "cg", "csr_matvec", "fgmres", "gmres", "rigid_body_modes"]
+__all__ = ["AMG", "BlockJacobi", "KrylovResult", "krylov_basis_rows", "cg", "csr_matvec", "fgmres", "gmres", "rigid_body_modes"]

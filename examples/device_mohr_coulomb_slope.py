@@ -17,6 +17,7 @@ the same reason, :639-646). The first Newton iteration of a step therefore uses 
 whose GMRES or Newton does not converge is reported and ends the loading.
 
     python3 examples/device_mohr_coulomb_slope.py [--n 25] [--steps K] [--solver gmres|amg|amg-rbm|amg-cheby|amg-soc|amg-k|amg-fp32|lu]
+        [--basis fp64|fp32]   (fp32: the Krylov basis of gmres / fgmres stored in single precision, dxo_krylov_create_basis)
 """
 import argparse
 import pathlib
@@ -42,7 +43,7 @@ def load_schedule():
 
 
 def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: bool = True, restart: int = 30,
-         lin_rtol: float = 1e-10, lin_maxiter: int = 3000) -> dict:
+         lin_rtol: float = 1e-10, lin_maxiter: int = 3000, basis: str = "fp64") -> dict:
     dev = torch.device("cuda:0")
     ctx = Context(0)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -129,7 +130,8 @@ def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: 
                 except ValueError as e:          # DXO_E_SINGULAR: a node whose tangent blocks vanish
                     failed = f"preconditioner setup failed at load {load:.3f} (step {i}, Newton iteration {it}): {e}"
                     break
-                out = (fgmres if solver in ("amg-k", "amg-fp32") else gmres)(A, rhs, M=M, restart=restart, rtol=lin_rtol, maxiter=lin_maxiter)
+                out = (fgmres if solver in ("amg-k", "amg-fp32") else gmres)(A, rhs, M=M, restart=restart, rtol=lin_rtol, maxiter=lin_maxiter,
+                                                                                    basis=basis)
                 lin_its.append(out.iterations)
                 if not out.converged:
                     failed = f"GMRES did not converge at load {load:.3f} (step {i}): {out.iterations} iterations, relative residual {out.residual:.2e}"
@@ -171,5 +173,6 @@ if __name__ == "__main__":
     ap.add_argument("--n", type=int, default=25, help="cells per side (the demo: 25)")
     ap.add_argument("--steps", type=int, default=None, help="first K load steps only")
     ap.add_argument("--solver", choices=["gmres", "amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k", "amg-fp32", "lu"], default="gmres")
+    ap.add_argument("--basis", choices=["fp64", "fp32"], default="fp64", help="storage of the Krylov basis of gmres / fgmres")
     a = ap.parse_args()
-    main(a.n, a.steps, a.solver)
+    main(a.n, a.steps, a.solver, basis=a.basis)

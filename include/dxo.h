@@ -596,6 +596,22 @@ int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n
  *                   to step (an inner iteration, a K-cycle); dxo_krylov_gmres and dxo_krylov_cg need a fixed linear M. With a fixed
  *                   M it takes the iterations of dxo_krylov_gmres. The second basis (restart * ld doubles) is allocated at the first
  *                   flexible solve on a workspace and freed with it: a workspace that serves only gmres / cg keeps today's memory.
+ * dxo_krylov_create_basis : dxo_krylov_create with the storage of the basis chosen. DXO_KRYLOV_BASIS_FP64 is dxo_krylov_create.
+ *                   DXO_KRYLOV_BASIS_FP32 (a compressed basis, as in CB-GMRES) stores the basis as float [restart + 1][ldf], ldf = n
+ *                   padded to a multiple of 64 floats, and the work vectors plus two more in double; there is no double basis. Every
+ *                   dot product, update, Hessenberg entry, rotation and x stay double: a new basis vector is rounded to float once
+ *                   (round to nearest even) and that rounded vector is the one M and A see at the next step, so the Arnoldi relation
+ *                   holds for the stored basis. The stopping test is on the double true residual b - A x, formed at every restart, so
+ *                   the attainable accuracy is the one of the FP64 basis; the Hessenberg estimate inside a cycle is good to about
+ *                   2^-24 of the cycle's starting residual, so a cycle cannot gain much more than seven digits on its own estimate:
+ *                   expect at most one extra cycle at tight tolerances. The basis sees normalised vectors only: no range concern.
+ *                   dxo_krylov_gmres and dxo_krylov_fgmres take either kind; in dxo_krylov_fgmres the second basis Z stays double
+ *                   (the z_j = M v_j are not normalised: their range is the caller's). dxo_krylov_cg keeps no basis and returns
+ *                   DXO_E_OPTION on an FP32 workspace; an unknown kind: DXO_E_OPTION. Option "krylov_basis_width": rows of the
+ *                   float basis a thread owns in the row kernels (1, 2 or 4).
+ * dxo_krylov_basis_info : the kind of a workspace, the bytes of its basis rows alone ((restart + 1) * ld * the element size; the
+ *                   second basis of dxo_krylov_fgmres is not counted), the DEVICE pointer of row 0 (float or double by the kind)
+ *                   and the row stride in elements. Any out-pointer may be NULL. For tests and reports.
  * Operator: a CSR matrix (csr + values) or a callback that SETS out = A v on the context's stream (e.g. dxo_bilinear_apply with option
  * "consumer_overwrite" = 1). The callback runs on the calling thread while the context's (recursive) lock is held, so it may call
  * other dxo_* entry points on the same context; a nonzero return ends the solve with that code. Preconditioner: NULL or kind
@@ -612,6 +628,8 @@ int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n
 #define DXO_PC_BLOCK_JACOBI 2
 #define DXO_PC_AMG 3               /* dxo_krylov_pc::inv carries the dxo_amg* (cast to const double*), bs and n as for block Jacobi */
 #define DXO_PC_CALLBACK 4          /* dxo_krylov_pc::inv carries a dxo_krylov_callback* (cast to const double*), n as above        */
+#define DXO_KRYLOV_BASIS_FP64 0
+#define DXO_KRYLOV_BASIS_FP32 1
 typedef struct dxo_krylov dxo_krylov;
 typedef int (*dxo_krylov_apply_fn)(void* user, const double* v, double* out);
 typedef struct dxo_krylov_op {
@@ -643,6 +661,8 @@ int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double 
 int dxo_csr_block_jacobi(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double* inv);
 int dxo_block_jacobi_apply(dxo_ctx* ctx, int bs, int64_t n, const double* inv, const double* r, double* z);
 int dxo_krylov_create(dxo_ctx* ctx, int64_t n, int restart, dxo_krylov** out);
+int dxo_krylov_create_basis(dxo_ctx* ctx, int64_t n, int restart, int basis, dxo_krylov** out);
+int dxo_krylov_basis_info(dxo_ctx* ctx, const dxo_krylov* ws, int* basis, int64_t* basis_bytes, const void** rows, int64_t* ld);
 int dxo_krylov_destroy(dxo_ctx* ctx, dxo_krylov* ws);
 int dxo_krylov_gmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b, double* x,
                      double rtol, double atol, int max_it, int check_every, dxo_krylov_info* info);

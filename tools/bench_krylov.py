@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Standalone timing of the device linear solves (csrc/krylov.hip; not a bench.py leg).
-    python3 tools/bench_krylov.py [tri_cells_per_side] [hex_boxes_per_side] [heat_cells_per_side] [--out FILE]
+    python3 tools/bench_krylov.py [tri_cells_per_side] [hex_boxes_per_side] [heat_cells_per_side] [amg_cells_per_side] [--out FILE] [--basis fp32]
 Legs (distorted meshes, random C):
   p2_spmv / p2_apply        dxo_csr_spmv of the assembled ("grad", "grad", 2) matrix on P2 triangles (1291 per side: 10^7 points,
                             3.07e8 nonzeros) next to the matrix-free dxo_bilinear_apply of the same form
@@ -10,6 +10,12 @@ Legs (distorted meshes, random C):
                             one block-Jacobi apply: the Gram-Schmidt part (two passes, norm, scaling, Givens)
   heat_solve                one full block-Jacobi GMRES(30) solve of a heat-type Jacobian (P1, ("grad", "value_grad"), Dirichlet
                             boundary) to rtol 1e-8, at most 3000 iterations
+--basis fp32 adds, in the same run and on the same systems, the GMRES(30) legs with both kinds of Krylov basis (key "basis"): for the
+P2 and the Q2 system and per basis ("fp64", and "fp32_w1" / "fp32_w2" / "fp32_w4": the compressed basis with 1, 2 or 4 rows per
+thread, option krylov_basis_width) the ms per iteration of one cycle, the orthogonalisation part and its share, basis_bytes, and one
+solve of at most 300 iterations (iterations, true relative residual reached); `orth_ratio` = the orthogonalisation of each fp32
+width over the fp64 basis's. Then one multigrid-preconditioned ("eps", "eps", 2) solve on P2 triangles (amg_cells_per_side, default
+400; rigid-body modes, lower side clamped, as tools/bench_amg.py --rbm) to rtol 1e-8 by gmres and fgmres with both bases.
 Timing: warm-up, then 5 batches of 20 back-to-back launches timed with HIP events on the launch stream, the MEDIAN batch reported
 (tools/bench_timing.median_batch). `model_GB` of an SpMV = values + column indices (one per bs^2 block) + row pointers + x once + y;
 `frac_6p3` its rate against 6.3 TB/s achievable. Prints one JSON line.
@@ -49,10 +55,10 @@ def spmv_model_GB(nnz: int, n: int, bs: int) -> float:
     return (8 * nnz + 4 * nnz / bs ** 2 + 8 * (n // bs + 1) + 8 * n + 8 * n) / 1e9
 
 
-def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256) -> dict:
+def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_amg: int = 400, basis: str = "fp64") -> dict:
     import torch
 
-    from dolfinx_external_operator_amd import Context, DeviceMesh, gmres
+    from dolfinx_external_operator_amd import Context, DeviceMesh, fgmres, gmres, rigid_body_modes
     from tools.synthetic import structured_mesh
 
     ctx = Context(0)
@@ -73,7 +79,29 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256) -> dict:
             r["TBs"] = round(model_GB / ms, 3)
             r["frac_6p3"] = round(model_GB / ms / ACHIEVABLE_TBs, 3)
         res["legs"][name] = r
+        print(name, json.dumps(r), file=sys.stderr, flush=True)
         return ms
+
+    def solve_figures(out):
+        return {"iterations": out.iterations, "restarts": out.restarts, "converged": out.converged, "residual": out.residual,
+                "ms": round(out.ms, 2), "basis_bytes": out.basis_bytes}
+
+    def basis_legs(tag, A, M, b, t_spmv, t_pc):
+        """GMRES(30) with the fp64 basis and with the compressed one at every width, same matrix, preconditioner and right-hand side."""
+        default_width = ctx.get_option("krylov_basis_width")
+        r = {}
+        for label, kind, width in (("fp64", "fp64", default_width), ("fp32_w1", "fp32", 1), ("fp32_w2", "fp32", 2), ("fp32_w4", "fp32", 4)):
+            ctx.set_option("krylov_basis_width", width)
+            t_it = leg(f"{tag}_gmres30_cycle_{label}", lambda: gmres(A, b, x=torch.zeros_like(b), M=M, restart=30, rtol=1e-30, maxiter=30,
+                                                                     check_every=30, basis=kind), per_batch=2) / 30
+            orth = t_it - t_spmv - t_pc
+            out = gmres(A, b, M=M, restart=30, rtol=1e-8, maxiter=300, basis=kind)
+            r[label] = {"iteration_ms": round(t_it, 4), "orth_ms": round(orth, 4), "orth_share": round(orth / t_it, 3),
+                        "solve_300": solve_figures(out)}
+        ctx.set_option("krylov_basis_width", default_width)
+        r["orth_ratio"] = {k: round(r[k]["orth_ms"] / r["fp64"]["orth_ms"], 3) for k in r if k != "fp64"}
+        r["default_width"] = default_width
+        res.setdefault("basis", {})[tag] = r
 
     for tag, cell, n, test, trial, bs in (("p2", "triangle", (n_side, n_side), "grad", "grad", 2),
                                           ("q2hex", "hexahedron", (n_hex, n_hex, n_hex), "eps", "eps", 3)):
@@ -104,6 +132,14 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256) -> dict:
                     res["p2_gmres30_spmv_ms"] = round(t_spmv, 4)
                     res["p2_gmres30_pc_ms"] = round(t_pc, 4)
                     res["p2_gmres30_orth_ms"] = round(t_it - t_spmv - t_pc, 4)
+                    if basis == "fp32":
+                        basis_legs(tag, A, M, b, t_spmv, t_pc)
+                    del M, b
+                elif basis == "fp32":
+                    M = A.block_jacobi()
+                    t_pc = leg(f"{tag}_block_jacobi_apply", lambda: M.apply(x, y))
+                    b = torch.randn(nn * bs, generator=gen, device=dev, dtype=torch.float64)
+                    basis_legs(tag, A, M, b, t_spmv, t_pc)
                     del M, b
                 del A, Cd, x, y
             stream.synchronize()
@@ -134,6 +170,32 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256) -> dict:
                              "ms": round(out.ms, 2), "ms_per_iteration": round(out.ms / max(out.iterations, 1), 4)}
     finally:
         dm.close()
+
+    if basis == "fp32" and n_amg > 0:      # one multigrid-preconditioned elasticity solve with both bases
+        m = structured_mesh("triangle", (n_amg, n_amg), 2, distort=0.2, seed=0)
+        dm = DeviceMesh.from_synthetic(m, ctx=ctx)
+        try:
+            npts = m.num_cells * m.nq
+            on = np.flatnonzero(np.abs(m.node_x[:, 1] - m.node_x[:, 1].min()) < 1e-12)
+            with torch.cuda.stream(stream):
+                bcs = torch.from_numpy((on[:, None] * 2 + np.arange(2)).reshape(-1).astype(np.int32)).to(dev)
+                Cd = 0.3 * torch.randn(npts * 16, generator=gen, device=dev, dtype=torch.float64)
+                Cd.view(npts, 4, 4).add_(torch.eye(4, device=dev, dtype=torch.float64))
+                A = dm.bilinear_assemble("eps", "eps", 2, Cd.data_ptr(), dm.csr_pattern(2), bcs=bcs)
+                amg = A.amg(bcs, near_nullspace=rigid_body_modes(m.node_x, ctx=ctx))
+                b = torch.randn(A.shape[0], generator=gen, device=dev, dtype=torch.float64)
+                r = {"dofs": A.shape[0], "levels": [lv["rows"] for lv in amg.levels]}
+                for solve in (gmres, fgmres):
+                    for kind in ("fp64", "fp32"):
+                        solve(A, b, M=amg, restart=30, rtol=1e-8, maxiter=30, basis=kind)       # warm-up
+                        out = solve(A, b, M=amg, restart=30, rtol=1e-8, maxiter=3000, basis=kind)
+                        true = float((b - A.matvec(out.x)).norm() / b.norm())
+                        r[f"{solve.__name__}30_{kind}"] = {**solve_figures(out), "true_residual": true,
+                                                           "ms_per_iteration": round(out.ms / max(out.iterations, 1), 4)}
+                amg.close()
+            res["basis"]["p2eps_amg_rbm"] = r
+        finally:
+            dm.close()
     ctx.close()
     return res
 
@@ -145,7 +207,14 @@ if __name__ == "__main__":
         i = args.index("--out")
         out_file = args[i + 1]
         del args[i:i + 2]
-    r = main(*(int(a) for a in args))
+    basis = "fp64"
+    if "--basis" in args:
+        i = args.index("--basis")
+        basis = args[i + 1]
+        del args[i:i + 2]
+    if basis not in ("fp64", "fp32"):
+        raise SystemExit("--basis: fp64 or fp32")
+    r = main(*(int(a) for a in args), basis=basis)
     line = json.dumps(r)
     print(line)
     if out_file:
