@@ -72,8 +72,8 @@
 // on entry (12 B per row, repaid by the 2 nu + 1 kernels of level 0 that then read 4 B of r per row instead of 8), and the last
 // post-sweep of level 0 writes z in double (its TO). The K-cycle stays double: the two settings exclude each other.
 //
-// Host side. Run-time shapes reach the templates through one dispatcher (with_int / with_pairs and their named lists: with_bs,
-// with_level, with_pair, with_square, with_nns_pair), so a kernel's argument list is written once. amg_build allocates the device scalars
+// Host side. Run-time shapes reach the templates through one dispatcher (with_int and with_bs of krylov_internal.h, with_pairs here,
+// and their named lists: with_level, with_pair, with_square, with_nns_pair), so a kernel's argument list is written once. amg_build allocates the device scalars
 // of every level once, before the level loop, and walks read pattern -> [strength mask] -> aggregates -> transfer tables -> coarse
 // level -> [T and B] -> [numeric phase] per level, the bracketed stages on the hierarchies that have them.
 #include "krylov_internal.h"
@@ -1136,15 +1136,9 @@ void amg_launch(void (*kernel)(P...), int64_t items, int per_block, hipStream_t 
     hipLaunchKernelGGL(kernel, amg_grid(items, per_block), dim3(DXO_AMG_BLOCK), 0, s, args...);
 }
 
-// from run-time shapes to compile-time ones: f(constant...) for the entry of the list that matches, amg_no_shape for none. The lists
-// are the instantiations of this file
-template <int N>
-using int_c = std::integral_constant<int, N>;
-
-template <int... Ns, class F>
-void with_int(int v, F&& f) {
-    if (!((v == Ns && (f(int_c<Ns>{}), true)) || ...)) amg_no_shape(v, v);
-}
+// from run-time shapes to compile-time ones (with_int and with_bs of krylov_internal.h, with_pairs here): f(constant...) for the entry
+// of the list that matches, amg_no_shape for none. The lists are the instantiations of this file
+constexpr auto amg_miss = [](int v) { amg_no_shape(v, v); };
 
 constexpr int amg_pair(int bsr, int bsc) { return bsr * 8 + bsc; }
 
@@ -1152,9 +1146,6 @@ template <int... Ps, class F>
 void with_pairs(int bsr, int bsc, F&& f) {
     if (!((amg_pair(bsr, bsc) == Ps && (f(int_c<Ps / 8>{}, int_c<Ps % 8>{}), true)) || ...)) amg_no_shape(bsr, bsc);
 }
-
-template <class F>
-void with_bs(int bs, F&& f) { with_int<1, 2, 3, 6>(bs, f); }
 
 // (rows of the level, rows of the next): with a near-null space (2, 3) -> (3, 3) and (3, 6) -> (6, 6), square without one
 template <class F>
@@ -1172,7 +1163,7 @@ void with_pair(int bsr, int bsc, F&& f) {
 // (block size, lanes per node) of the lane-group kernels of a level
 template <class F>
 void with_level(const amg_level& v, F&& f) {
-    with_bs(v.bs, [&](auto BS) { with_int<8, 32>(v.lw, [&](auto LW) { f(BS, LW); }); });
+    with_bs(v.bs, [&](auto BS) { with_int<8, 32>(v.lw, [&](auto LW) { f(BS, LW); }, amg_miss); }, amg_miss);
 }
 
 template <bool RESID, class T, class TO>
@@ -1408,7 +1399,7 @@ int amg_nns_level(dxo_ctx* ctx, dxo_amg* amg, const amg_level& v, double* b_next
         with_nns_pair(v.bs, v.bsc, [&](auto BSR, auto K) {
             with_int<8, 16, 32, 64>(v.tl, [&](auto LG) {
                 amg_launch(amg_tentative<BSR, K, LG>, v.n_agg, DXO_AMG_BLOCK / LG, s, v.n_agg, v.agg_ptr, v.agg_node, v.b_val, tol, v.t_val, b_next, v.dead_a);
-            });
+            }, amg_miss);
         });
     return DXO_OK;
 }
@@ -1468,7 +1459,7 @@ void amg_setup_level(dxo_amg* amg, int l, const amg_level& v, const amg_level& c
         with_bs(v.bs, [&](auto BS) {
             amg_launch(amg_lump<BS>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.A->d_row_ptr, v.A->d_col, v.values, v.strong, v.dinv, v.diag_f, v.dinv_f,
                        v.unlumped);
-        });
+        }, amg_miss);
         amg_estimate_rho(amg, v, true, amg->rho_f + l, amg->omega_f + l, amg->cheb_f, s);
         omega_p = amg->omega_f + l;      // P is smoothed with the filtered matrix: dinv_f and omega_F
     }
@@ -1768,7 +1759,7 @@ const T* amg_body(const CycleRun& C, int l, const T* rin, double* out) {
     T *cur = w.xa, *other = w.xb;
     with_bs(v.bs, [&](auto BS) {      // from x = 0: omega Dinv r, or c2 Dinv r into the direction as well
         amg_launch(amg_first_step<BS, T>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, w.dinv, C.cheby ? ch + 1 : om, rin, C.cheby ? w.d : (T*)nullptr, cur);
-    });
+    }, amg_miss);
     for (int k = 1; k < C.nu; ++k) {
         if (C.cheby) cheby_step(v, ch + 2 * k, rin, (const T*)cur, other, s);
         else sweep<false>(v, om, rin, (const T*)cur, other, s);

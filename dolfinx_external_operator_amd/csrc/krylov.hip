@@ -22,15 +22,24 @@
 // CG runs on the same kernels; once its residual test passes on the device, alpha is 0 for the steps that follow.
 //
 // Flexible GMRES (dxo_krylov_fgmres) is the same sequence with z_j = M v_j kept in a second basis Z [m][ld]: w = A z_j, and the update
-// at the end of a cycle is x += sum_j y_j z_j (kr_combine on Z), with no further preconditioner call. M may therefore change from
+// at the end of a cycle is x += sum_j y_j z_j (kr_combine<double, 1> on Z), with no further preconditioner call. M may therefore change from
 // step to step (a callback that iterates, the K-cycle of amg.hip). Z is allocated at the first flexible solve on a workspace.
 //
 // Compressed basis (dxo_krylov_create_basis, DXO_KRYLOV_BASIS_FP32): the rows of V are stored as float [m + 1][ldf], everything else
 // (dot products, updates, H, the rotations, x, the second basis of the flexible solver) stays double. A new basis vector is rounded
 // once, t = (float)(w[i] hinv), written to V[j + 1] and widened back into w, which the next step hands to M and A: the vector the
 // solver works with is exactly the one it stored, so the Arnoldi relation holds for the stored basis and no row is ever widened in a
-// pass of its own. w alternates between two double vectors W0 / W1. The row kernels over a float basis (kf_*) keep the grid, the
-// per-thread row sets and the reductions of the double ones; a thread owns FW consecutive rows (option "krylov_basis_width").
+// pass of its own. w alternates between two double vectors W0 / W1.
+//
+// The row kernels of the Gram-Schmidt step (kr_multidot, kr_update, kr_combine, kr_scale_store) are one family over the type T of the
+// stored rows and the rows FW a thread owns per trip of the grid, instantiated for (double, 1) and (float, 1 | 2 | 4): the same grid,
+// per-thread order and reductions for both bases. FW of a float basis is the option "krylov_basis_width"; a double basis, the second
+// basis of the flexible solver and the single products of CG run (double, 1) whatever the option says. KrBasis::rows is the one
+// place that turns a workspace into (typed row pointer, stride, FW).
+//
+// Host side. Run-time shapes (block size, lanes per node, KMAX, FW) reach the templates through with_int / with_bs of
+// krylov_internal.h, so a kernel's argument list is written once and a value without an instantiation is refused, never served by
+// another kernel.
 #include "csr.h"
 #include "dxo_common.h"
 #include "krylov_internal.h"
@@ -39,6 +48,8 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
+#include <string>
 #include <type_traits>
 
 #ifndef DXO_KR_BLOCK
@@ -168,21 +179,69 @@ __global__ __launch_bounds__(DXO_KR_BLOCK) void bj_apply(int64_t n_nodes, const 
     }
 }
 
-// ---- Krylov building blocks. Row kernels run on exactly nb workgroups (grid stride): the rows a thread adds are fixed.
+// ---- Krylov building blocks. Row kernels run on exactly nb workgroups (grid stride): the rows a thread adds are fixed. They read the
+// rows of a basis stored as T [.][ld], T double (the vectors themselves) or float (the compressed basis); everything else is double.
+// A thread owns FW consecutive rows i0 .. i0 + FW - 1 of every trip of the grid: one sizeof(T) FW-byte load per basis row and as
+// many doubles of w. With FW = 1 (the only width of a double basis: its vectors are the caller's in dot_partials, aligned to 8
+// bytes and no more) a group is one entry and all of this folds to the plain loop. Row starts of wider groups are aligned (ld and
+// i0 are multiples of FW, the buffers of hipMalloc); n is not, so the last group of a vector is ragged: it is loaded entry by entry
+// and the absent entries take no part. Sums run over a thread's entries in ascending order, then over the wave and across waves.
+template <int FW>
+struct KrRows {
+    int64_t i0;
+    int cnt;      // entries of this group that exist: FW, or fewer at the tail
+    __device__ __forceinline__ KrRows(int64_t i, int64_t n) : i0(i), cnt(n - i >= FW ? FW : (int)(n - i)) {}
+    __device__ __forceinline__ bool full() const { return cnt == FW; }
+    template <class T>
+    __device__ __forceinline__ void load(const T* __restrict__ p, T (&v)[FW]) const {
+        if (full()) {
+            struct alignas(sizeof(T) * FW) Pack { T e[FW]; };
+            const Pack q = *reinterpret_cast<const Pack*>(p + i0);
+#pragma unroll
+            for (int c = 0; c < FW; ++c) v[c] = q.e[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < FW; ++c) v[c] = c < cnt ? p[i0 + c] : T(0);
+        }
+    }
+    template <class T>
+    __device__ __forceinline__ void store(T* __restrict__ p, const T (&v)[FW]) const {
+        if (full()) {
+            struct alignas(sizeof(T) * FW) Pack { T e[FW]; };
+            Pack q;
+#pragma unroll
+            for (int c = 0; c < FW; ++c) q.e[c] = v[c];
+            *reinterpret_cast<Pack*>(p + i0) = q;
+        } else {
+#pragma unroll
+            for (int c = 0; c < FW; ++c)
+                if (c < cnt) p[i0 + c] = v[c];
+        }
+    }
+};
+
 // part[k * nb + block] = sum over the block's rows of V_k[i] w[i], k < nk; w is read once for all nk products
-template <int KMAX>
-__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_multidot(int64_t n, const double* __restrict__ V, int64_t ld, int nk,
+template <int KMAX, class T, int FW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_multidot(int64_t n, const T* __restrict__ V, int64_t ld, int nk,
                                                             const double* __restrict__ w, double* __restrict__ part) {
     __shared__ double lds[DXO_KR_BLOCK / 64][KMAX];
     double acc[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
-    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) {
-        const double wi = w[i];
+    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
+    for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
+        const KrRows<FW> g(i, n);
+        double wi[FW];
+        g.load(w, wi);
 #pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k < nk) acc[k] = fma(V[k * ld + i], wi, acc[k]);
+        for (int k = 0; k < KMAX; ++k) {
+            if (k < nk) {
+                T v[FW];
+                g.load(V + k * ld, v);
+#pragma unroll
+                for (int c = 0; c < FW; ++c) acc[k] = fma((double)v[c], wi[c], acc[k]);      // an absent entry adds 0 * 0
+            }
+        }
     }
     const int wv = threadIdx.x >> 6;
 #pragma unroll
@@ -220,132 +279,20 @@ __global__ __launch_bounds__(DXO_KR_BLOCK) void kr_reduce(const double* __restri
         }
     }
 }
-
 // w -= sum_k V_k h_k (k ascending), and npart[block] = the block's share of |w|^2
-__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_update(int64_t n, const double* __restrict__ V, int64_t ld, int nk, const double* __restrict__ h,
-                                                          double* __restrict__ w, double* __restrict__ npart) {
-    __shared__ double lds[DXO_KR_BLOCK / 64];
-    double acc = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
-    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) {
-        double s = w[i];
-        for (int k = 0; k < nk; ++k) s = fma(-V[k * ld + i], h[k], s);
-        w[i] = s;
-        acc = fma(s, s, acc);
-    }
-    acc = block_sum(acc, lds);
-    if (threadIdx.x == 0) npart[blockIdx.x] = acc;
-}
-
-// out = sum_k V_k y_k (k ascending)
-__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_combine(int64_t n, const double* __restrict__ V, int64_t ld, int nk, const double* __restrict__ y,
-                                                           double* __restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
-    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) {
-        double s = 0.0;
-        for (int k = 0; k < nk; ++k) s = fma(V[k * ld + i], y[k], s);
-        out[i] = s;
-    }
-}
-
-// y = x * s[0] (in place allowed)
-__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_scale(int64_t n, const double* x, const double* __restrict__ s, double* y) {
-    const double a = s[0];
-    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK;
-    for (int64_t i = (int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x; i < n; i += stride) y[i] = x[i] * a;
-}
-
-// ---- the same row kernels over a float basis Vf [.][ldf]. A thread owns FW consecutive rows i0 .. i0 + FW - 1 of every trip of the
-// grid: one 4 FW-byte load per basis row, FW / 2 16-byte loads of w. Row starts are aligned (ldf, ld and i0 are multiples of FW, the
-// buffers of hipMalloc); n is not, so the last group of a vector is ragged: it is loaded entry by entry and the absent entries take
-// no part. Sums run over a thread's entries in ascending order, then as in the double kernels.
-template <int FW>
-struct KfRows {
-    int64_t i0;
-    int cnt;      // entries of this group that exist: FW, or fewer at the tail
-    __device__ __forceinline__ KfRows(int64_t i, int64_t n) : i0(i), cnt(n - i >= FW ? FW : (int)(n - i)) {}
-    __device__ __forceinline__ bool full() const { return cnt == FW; }
-    template <class T>
-    __device__ __forceinline__ void load(const T* __restrict__ p, T (&v)[FW]) const {
-        if (full()) {
-            struct alignas(sizeof(T) * FW) Pack { T e[FW]; };
-            const Pack q = *reinterpret_cast<const Pack*>(p + i0);
-#pragma unroll
-            for (int c = 0; c < FW; ++c) v[c] = q.e[c];
-        } else {
-#pragma unroll
-            for (int c = 0; c < FW; ++c) v[c] = c < cnt ? p[i0 + c] : T(0);
-        }
-    }
-    template <class T>
-    __device__ __forceinline__ void store(T* __restrict__ p, const T (&v)[FW]) const {
-        if (full()) {
-            struct alignas(sizeof(T) * FW) Pack { T e[FW]; };
-            Pack q;
-#pragma unroll
-            for (int c = 0; c < FW; ++c) q.e[c] = v[c];
-            *reinterpret_cast<Pack*>(p + i0) = q;
-        } else {
-#pragma unroll
-            for (int c = 0; c < FW; ++c)
-                if (c < cnt) p[i0 + c] = v[c];
-        }
-    }
-};
-
-// part[k * nb + block] = sum over the block's rows of (double)Vf_k[i] w[i], k < nk
-template <int KMAX, int FW>
-__global__ __launch_bounds__(DXO_KR_BLOCK) void kf_multidot(int64_t n, const float* __restrict__ Vf, int64_t ldf, int nk,
-                                                            const double* __restrict__ w, double* __restrict__ part) {
-    __shared__ double lds[DXO_KR_BLOCK / 64][KMAX];
-    double acc[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
-    for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
-        const KfRows<FW> g(i, n);
-        double wi[FW];
-        g.load(w, wi);
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            if (k < nk) {
-                float v[FW];
-                g.load(Vf + k * ldf, v);
-#pragma unroll
-                for (int c = 0; c < FW; ++c) acc[k] = fma((double)v[c], wi[c], acc[k]);      // an absent entry adds 0 * 0
-            }
-        }
-    }
-    const int wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (k < nk) {
-            const double s = wave_sum(acc[k]);
-            if ((threadIdx.x & 63) == 0) lds[wv][k] = s;
-        }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < nk; k += DXO_KR_BLOCK) {
-        double s = 0.0;
-        for (int q = 0; q < DXO_KR_BLOCK / 64; ++q) s += lds[q][k];
-        part[(int64_t)k * gridDim.x + blockIdx.x] = s;
-    }
-}
-
-// w -= sum_k (double)Vf_k h_k (k ascending), and npart[block] = the block's share of |w|^2
-template <int FW>
-__global__ __launch_bounds__(DXO_KR_BLOCK) void kf_update(int64_t n, const float* __restrict__ Vf, int64_t ldf, int nk, const double* __restrict__ h,
+template <class T, int FW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_update(int64_t n, const T* __restrict__ V, int64_t ld, int nk, const double* __restrict__ h,
                                                           double* __restrict__ w, double* __restrict__ npart) {
     __shared__ double lds[DXO_KR_BLOCK / 64];
     double acc = 0.0;
     const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
     for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
-        const KfRows<FW> g(i, n);
+        const KrRows<FW> g(i, n);
         double s[FW];
         g.load(w, s);
         for (int k = 0; k < nk; ++k) {
-            float v[FW];
-            g.load(Vf + k * ldf, v);
+            T v[FW];
+            g.load(V + k * ld, v);
             const double hk = h[k];
 #pragma unroll
             for (int c = 0; c < FW; ++c) s[c] = fma(-(double)v[c], hk, s[c]);
@@ -358,19 +305,19 @@ __global__ __launch_bounds__(DXO_KR_BLOCK) void kf_update(int64_t n, const float
     if (threadIdx.x == 0) npart[blockIdx.x] = acc;
 }
 
-// out = sum_k (double)Vf_k y_k (k ascending)
-template <int FW>
-__global__ __launch_bounds__(DXO_KR_BLOCK) void kf_combine(int64_t n, const float* __restrict__ Vf, int64_t ldf, int nk, const double* __restrict__ y,
+// out = sum_k V_k y_k (k ascending)
+template <class T, int FW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_combine(int64_t n, const T* __restrict__ V, int64_t ld, int nk, const double* __restrict__ y,
                                                            double* __restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
     for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
-        const KfRows<FW> g(i, n);
+        const KrRows<FW> g(i, n);
         double s[FW];
 #pragma unroll
         for (int c = 0; c < FW; ++c) s[c] = 0.0;
         for (int k = 0; k < nk; ++k) {
-            float v[FW];
-            g.load(Vf + k * ldf, v);
+            T v[FW];
+            g.load(V + k * ld, v);
             const double yk = y[k];
 #pragma unroll
             for (int c = 0; c < FW; ++c) s[c] = fma((double)v[c], yk, s[c]);
@@ -379,24 +326,27 @@ __global__ __launch_bounds__(DXO_KR_BLOCK) void kf_combine(int64_t n, const floa
     }
 }
 
-// the new basis vector: t = (float)(x[i] s[0]) (round to nearest even), row[i] = t, y[i] = (double)t (y may be x)
-template <int FW>
-__global__ __launch_bounds__(DXO_KR_BLOCK) void kf_scale_store(int64_t n, const double* x, const double* __restrict__ s, float* __restrict__ row,
-                                                               double* y) {
+// the new basis vector: t = (T)(x[i] s[0]) (float: round to nearest even), row[i] = t, and for a float basis y[i] = (double)t as
+// well (y may be x). A double row is the vector itself: one store, y is not touched, and row may be x, so it is not __restrict__
+template <class T>
+using KrRowOut = std::conditional_t<std::is_same_v<T, double>, double*, T* __restrict__>;
+
+template <class T, int FW>
+__global__ __launch_bounds__(DXO_KR_BLOCK) void kr_scale_store(int64_t n, const double* x, const double* __restrict__ s, KrRowOut<T> row, double* y) {
     const double a = s[0];
     const int64_t stride = (int64_t)gridDim.x * DXO_KR_BLOCK * FW;
     for (int64_t i = ((int64_t)blockIdx.x * DXO_KR_BLOCK + threadIdx.x) * FW; i < n; i += stride) {
-        const KfRows<FW> g(i, n);
+        const KrRows<FW> g(i, n);
         double xi[FW];
-        float t[FW];
+        T t[FW];
         g.load(x, xi);
 #pragma unroll
         for (int c = 0; c < FW; ++c) {
-            t[c] = (float)(xi[c] * a);
+            t[c] = (T)(xi[c] * a);
             xi[c] = (double)t[c];
         }
         g.store(row, t);
-        g.store(y, xi);
+        if constexpr (!std::is_same_v<T, double>) g.store(y, xi);
     }
 }
 
@@ -517,16 +467,11 @@ int kr_grid(const dxo_ctx* ctx, int64_t n, int per_cu) {
     return blocks < 1 ? 1 : (int)blocks;
 }
 
-template <int BS>
-void spmv_bs(int lw, int64_t n_nodes, const dxo_csr* A, const double* values, double alpha, const double* x, double beta, double* y, hipStream_t s) {
-    auto grid = [&](int per) { return dim3((unsigned)((n_nodes + per - 1) / per)); };
-    switch (lw) {
-        case 8: hipLaunchKernelGGL((csr_spmv<BS, 8>), grid(DXO_KR_BLOCK / 8), dim3(DXO_KR_BLOCK), 0, s, n_nodes, A->d_row_ptr, A->d_col, values, alpha, x, beta, y); break;
-        case 16: hipLaunchKernelGGL((csr_spmv<BS, 16>), grid(DXO_KR_BLOCK / 16), dim3(DXO_KR_BLOCK), 0, s, n_nodes, A->d_row_ptr, A->d_col, values, alpha, x, beta, y); break;
-        case 32: hipLaunchKernelGGL((csr_spmv<BS, 32>), grid(DXO_KR_BLOCK / 32), dim3(DXO_KR_BLOCK), 0, s, n_nodes, A->d_row_ptr, A->d_col, values, alpha, x, beta, y); break;
-        default: hipLaunchKernelGGL((csr_spmv<BS, 64>), grid(DXO_KR_BLOCK / 64), dim3(DXO_KR_BLOCK), 0, s, n_nodes, A->d_row_ptr, A->d_col, values, alpha, x, beta, y); break;
-    }
-}
+// a value that the checks of this file let through and no list below holds: a defect here, not of the caller
+const auto kr_no_shape = [](int v) {
+    fprintf(stderr, "krylov.hip: no kernel instantiation for %d\n", v);
+    std::abort();
+};
 
 // lanes per node: the option, or the smallest of 8 / 16 / 32 / 64 that covers the mean neighbour count
 int spmv_lanes(const dxo_ctx* ctx, const dxo_csr* A) {
@@ -544,30 +489,40 @@ int bs_refused(dxo_ctx* ctx, const char* who, const char* takes, int bs) {
     return dxo_fail(ctx, DXO_E_DIM, msg);
 }
 
-// bs 1, 2, 3: the patterns of dxo_csr_create; 6: the pattern of a multigrid level (dxo_amg_info hands its dxo_csr out)
+// the block sizes of the product and of the block inverse are those of with_bs: 1, 2, 3 the patterns of dxo_csr_create, 6 the pattern
+// of a multigrid level (dxo_amg_info hands its dxo_csr out)
+#define KR_BS_LIST "1, 2, 3 or 6"
+constexpr char SPMV_TAKES[] = "the product takes " KR_BS_LIST;
+
+bool has_bs(int bs) {
+    bool found = true;
+    with_bs(bs, [](auto) {}, [&](int) { found = false; });
+    return found;
+}
+
 int spmv_launch(dxo_ctx* ctx, const char* who, const dxo_csr* A, const double* values, double alpha, const double* x, double beta, double* y,
                 hipStream_t s) {
-    if (A->bs != 1 && A->bs != 2 && A->bs != 3 && A->bs != 6) return bs_refused(ctx, who, "the product takes 1, 2, 3 or 6", A->bs);
+    if (!has_bs(A->bs)) return bs_refused(ctx, who, SPMV_TAKES, A->bs);
     if (A->n_nodes == 0) return DXO_OK;
-    const int lw = spmv_lanes(ctx, A);
-    if (A->bs == 1) spmv_bs<1>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
-    else if (A->bs == 2) spmv_bs<2>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
-    else if (A->bs == 3) spmv_bs<3>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
-    else spmv_bs<6>(lw, A->n_nodes, A, values, alpha, x, beta, y, s);
+    with_bs(A->bs, [&](auto BS) {
+        with_int<8, 16, 32, 64>(spmv_lanes(ctx, A), [&](auto LW) {
+            constexpr int NPB = DXO_KR_BLOCK / LW;      // nodes per workgroup
+            hipLaunchKernelGGL((csr_spmv<BS, LW>), dim3((unsigned)((A->n_nodes + NPB - 1) / NPB)), dim3(DXO_KR_BLOCK), 0, s, A->n_nodes, A->d_row_ptr,
+                               A->d_col, values, alpha, x, beta, y);
+        }, kr_no_shape);
+    }, kr_no_shape);
     return DXO_OK;
 }
 
 // bs 1, 2, 3 (kr_validate and dxo_block_jacobi_apply let nothing else through: the levels of block size 6 apply their inverses
 // inside the sweeps of amg.hip)
 int bj_apply_launch(dxo_ctx* ctx, const char* who, int bs, int64_t n, const double* inv, const double* r, double* z, hipStream_t s) {
-    if (bs < 1 || bs > 3) return bs_refused(ctx, who, "block Jacobi takes 1, 2 or 3", bs);
-    const int64_t nn = n / bs;
-    if (nn == 0) return DXO_OK;
-    const dim3 g(kr_grid(ctx, nn, 8)), b(DXO_KR_BLOCK);
-    if (bs == 1) hipLaunchKernelGGL(bj_apply<1>, g, b, 0, s, nn, inv, r, z);
-    else if (bs == 2) hipLaunchKernelGGL(bj_apply<2>, g, b, 0, s, nn, inv, r, z);
-    else hipLaunchKernelGGL(bj_apply<3>, g, b, 0, s, nn, inv, r, z);
-    return DXO_OK;
+    int rc = DXO_OK;
+    with_int<1, 2, 3>(bs, [&](auto BS) {
+        const int64_t nn = n / BS;
+        if (nn > 0) hipLaunchKernelGGL(bj_apply<BS>, dim3(kr_grid(ctx, nn, 8)), dim3(DXO_KR_BLOCK), 0, s, nn, inv, r, z);
+    }, [&](int) { rc = bs_refused(ctx, who, "block Jacobi takes 1, 2 or 3", bs); });
+    return rc;
 }
 
 bool misaligned(const void* p) { return ((uintptr_t)p & 7u) != 0; }
@@ -612,7 +567,7 @@ struct KrCall {
     }
     // part[0..nb) = partials of (a, b); reduce into out (norm: sqrt and inverse into out[0], out[1])
     void dot_partials(const double* a, const double* b, double* part) {
-        hipLaunchKernelGGL((kr_multidot<1>), dim3(ws->nb), dim3(DXO_KR_BLOCK), 0, s, ws->n, a, ws->ld, 1, b, part);
+        hipLaunchKernelGGL((kr_multidot<1, double, 1>), dim3(ws->nb), dim3(DXO_KR_BLOCK), 0, s, ws->n, a, ws->ld, 1, b, part);
     }
     void norm(const double* a, double* out) {
         dot_partials(a, a, ws->part);
@@ -631,77 +586,74 @@ struct KrCall {
         norm(ws->R(), ws->sc + ws->o_s() + S_NORM);
         return read(beta, ws->sc + ws->o_s() + S_NORM, sizeof(double));
     }
+    // the opening of every solver: *bnorm = |b| and *tol = max(rtol |b|, atol). b = 0 is solved here: x = 0, converged, *bnorm = 0
+    int begin(const double* b, double* x, double rtol, double atol, dxo_krylov_info* info, double* bnorm, double* tol) {
+        double* S = ws->sc + ws->o_s();
+        norm(b, S + S_NORM);
+        const int rc = read(bnorm, S + S_NORM, sizeof(double));
+        if (rc != DXO_OK) return rc;
+        if (*bnorm == 0.0) {
+            DXO_HIP(ctx, hipMemsetAsync(x, 0, (size_t)ws->n * sizeof(double), s));
+            DXO_HIP(ctx, hipStreamSynchronize(s));
+            info->converged = 1;
+        }
+        *tol = std::max(rtol * *bnorm, atol);
+        return DXO_OK;
+    }
 };
 
 int kr_validate(dxo_ctx* ctx, const char* who, bool flexible, dxo_krylov* ws, const dxo_krylov_op* op, const dxo_krylov_pc* pc, const double* b,
                 double* x, double rtol, double atol, int max_it, int check_every) {
     char msg[256];
-    if (!ws || !op || !b || !x) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": NULL argument").c_str());
-    if (!op->csr && !op->apply) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the operator has neither a matrix nor a callback").c_str());
-    if (op->csr && !op->values) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the operator's matrix has no values").c_str());
+    auto fail = [&](int code, const char* what) { return dxo_fail(ctx, code, (std::string(who) + ": " + what).c_str()); };
+    if (!ws || !op || !b || !x) return fail(DXO_E_NULL, "NULL argument");
+    if (!op->csr && !op->apply) return fail(DXO_E_NULL, "the operator has neither a matrix nor a callback");
+    if (op->csr && !op->values) return fail(DXO_E_NULL, "the operator's matrix has no values");
     if (op->n != ws->n || (op->csr && op->csr->n_rows != ws->n)) {
-        snprintf(msg, sizeof msg, "%s: operator size %lld (matrix rows %lld) differs from the workspace's %lld", who, (long long)op->n,
+        snprintf(msg, sizeof msg, "operator size %lld (matrix rows %lld) differs from the workspace's %lld", (long long)op->n,
                  (long long)(op->csr ? op->csr->n_rows : op->n), (long long)ws->n);
-        return dxo_fail(ctx, DXO_E_SIZE, msg);
+        return fail(DXO_E_SIZE, msg);
     }
-    if (op->csr && op->csr->bs != 1 && op->csr->bs != 2 && op->csr->bs != 3 && op->csr->bs != 6)
-        return bs_refused(ctx, who, "the product takes 1, 2, 3 or 6", op->csr->bs);
-    if (pc && pc->kind == DXO_PC_AMG) {      // pc->inv carries the dxo_amg*
-        if (pc->n != ws->n) {
-            snprintf(msg, sizeof msg, "%s: the preconditioner covers %lld rows, the operator has %lld", who, (long long)pc->n, (long long)ws->n);
-            return dxo_fail(ctx, DXO_E_SIZE, msg);
-        }
-        const int rc = dxo_amg_pc_check(ctx, who, (const dxo_amg*)pc->inv, op->csr, pc->bs, pc->n);
-        if (rc != DXO_OK) return rc;
-        if (!flexible && dxo_amg_cycle_is_k((const dxo_amg*)pc->inv))
-            return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": a K-cycle is not a fixed linear operator: use dxo_krylov_fgmres").c_str());
-    } else if (pc && pc->kind == DXO_PC_CALLBACK) {      // pc->inv carries a dxo_krylov_callback*
+    if (op->csr && !has_bs(op->csr->bs)) return bs_refused(ctx, who, SPMV_TAKES, op->csr->bs);
+    if (pc && pc->kind != DXO_PC_NONE) {
+        // pc->inv carries the dxo_amg*, a dxo_krylov_callback* or the inverses
         const dxo_krylov_callback* cb = (const dxo_krylov_callback*)pc->inv;
-        if (!cb || !cb->apply) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the preconditioner has no callback").c_str());
-        if (pc->n != ws->n) {
-            snprintf(msg, sizeof msg, "%s: the preconditioner covers %lld rows, the operator has %lld", who, (long long)pc->n, (long long)ws->n);
-            return dxo_fail(ctx, DXO_E_SIZE, msg);
+        if (pc->kind == DXO_PC_CALLBACK) {
+            if (!cb || !cb->apply) return fail(DXO_E_NULL, "the preconditioner has no callback");
+        } else if (pc->kind != DXO_PC_AMG) {
+            if (pc->kind != DXO_PC_JACOBI && pc->kind != DXO_PC_BLOCK_JACOBI) return fail(DXO_E_OPTION, "unknown preconditioner kind");
+            if (!pc->inv) return fail(DXO_E_NULL, "the preconditioner has no inverse");
+            if (misaligned(pc->inv)) return fail(DXO_E_ALIGN, "the preconditioner's inverse is not 8-byte aligned");
         }
-    } else if (pc && pc->kind != DXO_PC_NONE) {
-        if (pc->kind != DXO_PC_JACOBI && pc->kind != DXO_PC_BLOCK_JACOBI) return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": unknown preconditioner kind").c_str());
-        if (!pc->inv) return dxo_fail(ctx, DXO_E_NULL, (std::string(who) + ": the preconditioner has no inverse").c_str());
-        if (misaligned(pc->inv)) return dxo_fail(ctx, DXO_E_ALIGN, (std::string(who) + ": the preconditioner's inverse is not 8-byte aligned").c_str());
         if (pc->n != ws->n) {
-            snprintf(msg, sizeof msg, "%s: the preconditioner covers %lld rows, the operator has %lld", who, (long long)pc->n, (long long)ws->n);
-            return dxo_fail(ctx, DXO_E_SIZE, msg);
+            snprintf(msg, sizeof msg, "the preconditioner covers %lld rows, the operator has %lld", (long long)pc->n, (long long)ws->n);
+            return fail(DXO_E_SIZE, msg);
         }
-        if (pc->kind == DXO_PC_BLOCK_JACOBI) {
-            if (pc->bs < 1 || pc->bs > 3) return dxo_fail(ctx, DXO_E_DIM, (std::string(who) + ": block Jacobi takes bs 1, 2 or 3").c_str());
+        if (pc->kind == DXO_PC_AMG) {
+            const int rc = dxo_amg_pc_check(ctx, who, (const dxo_amg*)pc->inv, op->csr, pc->bs, pc->n);
+            if (rc != DXO_OK) return rc;
+            if (!flexible && dxo_amg_cycle_is_k((const dxo_amg*)pc->inv))
+                return fail(DXO_E_OPTION, "a K-cycle is not a fixed linear operator: use dxo_krylov_fgmres");
+        } else if (pc->kind == DXO_PC_BLOCK_JACOBI) {
+            if (pc->bs < 1 || pc->bs > 3) return fail(DXO_E_DIM, "block Jacobi takes bs 1, 2 or 3");
             if (op->csr && op->csr->bs != pc->bs) {
-                snprintf(msg, sizeof msg, "%s: block Jacobi of bs %d on a pattern of bs %d", who, pc->bs, op->csr->bs);
-                return dxo_fail(ctx, DXO_E_DIM, msg);
+                snprintf(msg, sizeof msg, "block Jacobi of bs %d on a pattern of bs %d", pc->bs, op->csr->bs);
+                return fail(DXO_E_DIM, msg);
             }
-            if (ws->n % pc->bs != 0) return dxo_fail(ctx, DXO_E_SIZE, (std::string(who) + ": n is not a multiple of the preconditioner's bs").c_str());
+            if (ws->n % pc->bs != 0) return fail(DXO_E_SIZE, "n is not a multiple of the preconditioner's bs");
         }
     }
-    if ((op->values && misaligned(op->values)) || misaligned(b) || misaligned(x))
-        return dxo_fail(ctx, DXO_E_ALIGN, (std::string(who) + ": arrays must be 8-byte aligned").c_str());
-    if (max_it < 0 || check_every < 1) return dxo_fail(ctx, DXO_E_SIZE, (std::string(who) + ": max_it < 0 or check_every < 1").c_str());
-    if (!(rtol >= 0.0) || !(atol >= 0.0)) return dxo_fail(ctx, DXO_E_OPTION, (std::string(who) + ": negative or NaN tolerance").c_str());
+    if ((op->values && misaligned(op->values)) || misaligned(b) || misaligned(x)) return fail(DXO_E_ALIGN, "arrays must be 8-byte aligned");
+    if (max_it < 0 || check_every < 1) return fail(DXO_E_SIZE, "max_it < 0 or check_every < 1");
+    if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail(DXO_E_OPTION, "negative or NaN tolerance");
     return DXO_OK;
 }
 
-void kr_multidot_launch(const KrCall& K, int nk, const double* w) {
-    dxo_krylov* ws = K.ws;
-    const dim3 g(ws->nb), b(DXO_KR_BLOCK);
-    if (nk <= 4) hipLaunchKernelGGL((kr_multidot<4>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
-    else if (nk <= 8) hipLaunchKernelGGL((kr_multidot<8>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
-    else if (nk <= 16) hipLaunchKernelGGL((kr_multidot<16>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
-    else if (nk <= 32) hipLaunchKernelGGL((kr_multidot<32>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
-    else hipLaunchKernelGGL((kr_multidot<64>), g, b, 0, K.s, ws->n, ws->V(), ws->ld, nk, w, ws->part);
-}
-
-// FW of the float-basis kernels as a compile-time constant: f(std::integral_constant<int, FW>)
-template <class F>
-void kf_width(const dxo_ctx* ctx, F f) {
-    if (ctx->krylov_basis_width == 1) f(std::integral_constant<int, 1>{});
-    else if (ctx->krylov_basis_width == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 4>{});
+// the smallest KMAX of kr_multidot that holds nk products
+int kr_kmax(int nk) {
+    int kmax = 4;
+    while (kmax < nk) kmax *= 2;
+    return kmax;
 }
 
 // the steps of a cycle that touch the basis, on either kind of workspace. FP64: the rows of V are the vectors themselves.
@@ -713,46 +665,42 @@ struct KrBasis {
     const bool f32;
     explicit KrBasis(const KrCall& k) : K(k), ws(k.ws), G(k.ws->nb), B(DXO_KR_BLOCK), f32(k.ws->basis == DXO_KRYLOV_BASIS_FP32) {}
     double* vector(int j) const { return f32 ? ws->W(j) : ws->V() + (int64_t)j * ws->ld; }
+    // f(rows, ld, FW): the stored rows with their type and stride, and the rows per thread of their kernels: a float basis takes FW
+    // from the option "krylov_basis_width", a double one has FW = 1 alone
+    template <class F>
+    void rows(F f) const {
+        if (f32) with_int<1, 2, 4>((int)K.ctx->krylov_basis_width, [&](auto FW) { f(ws->vf, ws->ldf, FW); }, kr_no_shape);
+        else f(ws->V(), ws->ld, int_c<1>{});
+    }
     // vector(j) = x * s[0], stored as row j (x may be vector(j))
     void scale_store(int j, const double* x, const double* s) const {
-        if (!f32) {
-            hipLaunchKernelGGL(kr_scale, G, B, 0, K.s, ws->n, x, s, vector(j));
-            return;
-        }
-        kf_width(K.ctx, [&](auto fw) {
-            hipLaunchKernelGGL((kf_scale_store<fw()>), G, B, 0, K.s, ws->n, x, s, ws->vf + (int64_t)j * ws->ldf, vector(j));
+        rows([&](auto* V, int64_t ld, auto FW) {
+            using T = std::remove_pointer_t<decltype(V)>;
+            hipLaunchKernelGGL((kr_scale_store<T, FW>), G, B, 0, K.s, ws->n, x, s, V + (int64_t)j * ld, vector(j));
         });
     }
     // part = partials of the products of w with rows 0 .. nk - 1
     void multidot(int nk, const double* w) const {
-        if (!f32) {
-            kr_multidot_launch(K, nk, w);
-            return;
-        }
-        kf_width(K.ctx, [&](auto fw) {
-            constexpr int FW = fw();
-            if (nk <= 4) hipLaunchKernelGGL((kf_multidot<4, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
-            else if (nk <= 8) hipLaunchKernelGGL((kf_multidot<8, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
-            else if (nk <= 16) hipLaunchKernelGGL((kf_multidot<16, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
-            else if (nk <= 32) hipLaunchKernelGGL((kf_multidot<32, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
-            else hipLaunchKernelGGL((kf_multidot<64, FW>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, w, ws->part);
+        rows([&](auto* V, int64_t ld, auto FW) {
+            using T = std::remove_pointer_t<decltype(V)>;
+            with_int<4, 8, 16, 32, 64>(kr_kmax(nk), [&](auto KMAX) {
+                hipLaunchKernelGGL((kr_multidot<KMAX, T, FW>), G, B, 0, K.s, ws->n, V, ld, nk, w, ws->part);
+            }, kr_no_shape);
         });
     }
     // w -= sum_k row_k h_k, npart = partials of |w|^2
     void update(int nk, const double* h, double* w, double* npart) const {
-        if (!f32) {
-            hipLaunchKernelGGL(kr_update, G, B, 0, K.s, ws->n, ws->V(), ws->ld, nk, h, w, npart);
-            return;
-        }
-        kf_width(K.ctx, [&](auto fw) { hipLaunchKernelGGL((kf_update<fw()>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, h, w, npart); });
+        rows([&](auto* V, int64_t ld, auto FW) {
+            using T = std::remove_pointer_t<decltype(V)>;
+            hipLaunchKernelGGL((kr_update<T, FW>), G, B, 0, K.s, ws->n, V, ld, nk, h, w, npart);
+        });
     }
     // out = sum_k row_k y_k
     void combine(int nk, const double* y, double* out) const {
-        if (!f32) {
-            hipLaunchKernelGGL(kr_combine, G, B, 0, K.s, ws->n, ws->V(), ws->ld, nk, y, out);
-            return;
-        }
-        kf_width(K.ctx, [&](auto fw) { hipLaunchKernelGGL((kf_combine<fw()>), G, B, 0, K.s, ws->n, ws->vf, ws->ldf, nk, y, out); });
+        rows([&](auto* V, int64_t ld, auto FW) {
+            using T = std::remove_pointer_t<decltype(V)>;
+            hipLaunchKernelGGL((kr_combine<T, FW>), G, B, 0, K.s, ws->n, V, ld, nk, y, out);
+        });
     }
 };
 
@@ -770,18 +718,9 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
     const dim3 G(ws->nb), B(DXO_KR_BLOCK);
     const bool reorth = ctx->krylov_reorth != 0;
     const KrBasis V(K);
-    // |b|
-    K.norm(b, S + S_NORM);
-    double bnorm = 0.0;
-    int rc = K.read(&bnorm, S + S_NORM, sizeof(double));
-    if (rc != DXO_OK) return rc;
-    if (bnorm == 0.0) {
-        DXO_HIP(ctx, hipMemsetAsync(x, 0, (size_t)n * sizeof(double), s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));
-        info->converged = 1;
-        return DXO_OK;
-    }
-    const double tol = std::max(rtol * bnorm, atol);
+    double bnorm = 0.0, tol = 0.0;
+    int rc = K.begin(b, x, rtol, atol, info, &bnorm, &tol);
+    if (rc != DXO_OK || bnorm == 0.0) return rc;
     int total = 0;
     double beta = 0.0;
     for (;;) {
@@ -827,7 +766,7 @@ int gmres_impl(KrCall& K, const double* b, double* x, double rtol, double atol, 
         if (k > 0) {
             hipLaunchKernelGGL(kr_trisolve, dim3(1), dim3(64), 0, s, sc, k, m, ws->o_g(), ws->o_y());
             if constexpr (FLEX) {
-                hipLaunchKernelGGL(kr_combine, G, B, 0, s, n, ws->zb, ws->ld, k, sc + ws->o_y(), ws->T());
+                hipLaunchKernelGGL((kr_combine<double, 1>), G, B, 0, s, n, ws->zb, ws->ld, k, sc + ws->o_y(), ws->T());
                 hipLaunchKernelGGL(kr_axpy, G, B, 0, s, n, S + S_ONE, 1.0, ws->T(), x);
             } else {
                 V.combine(k, sc + ws->o_y(), ws->T());
@@ -849,17 +788,9 @@ int cg_impl(KrCall& K, const double* b, double* x, double rtol, double atol, int
     double* S = ws->sc + ws->o_s();
     int* st = ws->st;
     const dim3 G(ws->nb), B(DXO_KR_BLOCK), One(1);
-    K.norm(b, S + S_NORM);
-    double bnorm = 0.0;
-    int rc = K.read(&bnorm, S + S_NORM, sizeof(double));
-    if (rc != DXO_OK) return rc;
-    if (bnorm == 0.0) {
-        DXO_HIP(ctx, hipMemsetAsync(x, 0, (size_t)n * sizeof(double), s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));
-        info->converged = 1;
-        return DXO_OK;
-    }
-    const double tol = std::max(rtol * bnorm, atol);
+    double bnorm = 0.0, tol = 0.0;
+    int rc = K.begin(b, x, rtol, atol, info, &bnorm, &tol);
+    if (rc != DXO_OK || bnorm == 0.0) return rc;
     double* r = ws->R();
     double* z = ws->Z();
     double* p = ws->T();
@@ -934,14 +865,13 @@ int kr_solve(dxo_ctx* ctx, const char* who, kr_solver solver, bool flexible, dxo
 }  // namespace
 
 int dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv, int* flag, hipStream_t s) {
-    if (csr->bs != 1 && csr->bs != 2 && csr->bs != 3 && csr->bs != 6) return DXO_E_DIM;
-    if (csr->n_nodes == 0) return DXO_OK;
-    const dim3 g((unsigned)((csr->n_nodes + DXO_KR_BLOCK - 1) / DXO_KR_BLOCK)), b(DXO_KR_BLOCK);
-    if (csr->bs == 1) hipLaunchKernelGGL(bj_setup<1>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
-    else if (csr->bs == 2) hipLaunchKernelGGL(bj_setup<2>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
-    else if (csr->bs == 3) hipLaunchKernelGGL(bj_setup<3>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);
-    else hipLaunchKernelGGL(bj_setup<6>, g, b, 0, s, csr->n_nodes, csr->d_row_ptr, csr->d_col, values, inv, flag);      // a multigrid level
-    return DXO_OK;
+    int rc = DXO_OK;
+    with_bs(csr->bs, [&](auto BS) {
+        if (csr->n_nodes == 0) return;
+        hipLaunchKernelGGL(bj_setup<BS>, dim3((unsigned)((csr->n_nodes + DXO_KR_BLOCK - 1) / DXO_KR_BLOCK)), dim3(DXO_KR_BLOCK), 0, s, csr->n_nodes,
+                           csr->d_row_ptr, csr->d_col, values, inv, flag);
+    }, [&](int) { rc = DXO_E_DIM; });
+    return rc;
 }
 
 int dxo_kr_spmv_launch(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const double* x, double* y, hipStream_t s) {
@@ -967,7 +897,7 @@ extern "C" int dxo_csr_block_jacobi(dxo_ctx* ctx, const dxo_csr* csr, const doub
     DXO_LOCK(ctx);
     if (!csr || !values || !inv) return dxo_fail(ctx, DXO_E_NULL, "dxo_csr_block_jacobi: NULL argument");
     if (misaligned(values) || misaligned(inv)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_csr_block_jacobi: arrays must be 8-byte aligned");
-    if (csr->bs != 1 && csr->bs != 2 && csr->bs != 3 && csr->bs != 6) return bs_refused(ctx, "dxo_csr_block_jacobi", "the block inverse takes 1, 2, 3 or 6", csr->bs);
+    if (!has_bs(csr->bs)) return bs_refused(ctx, "dxo_csr_block_jacobi", "the block inverse takes " KR_BS_LIST, csr->bs);
     if (csr->n_nodes == 0) return DXO_OK;
     hipStream_t s = dxo_launch_stream(ctx);
     DXO_HIP(ctx, hipSetDevice(ctx->device));

@@ -1,6 +1,7 @@
 """The entry points of the compressed Krylov basis in the built library, the header and the binding (not gpu)."""
 import ctypes as C
 import inspect
+import re
 
 from test_abi import header_functions
 
@@ -16,8 +17,10 @@ def test_library_header_and_binding_carry_the_new_symbols(hip_library):
         assert name in declared_symbols(), name
     assert hip_library.dxo_abi_version() == 2                      # symbols were added, no struct changed
     blob = __import__("dolfinx_external_operator_amd._lib", fromlist=["LIB_PATH"]).LIB_PATH.read_bytes()
-    for kernel in (b"kf_multidot", b"kf_update", b"kf_combine", b"kf_scale_store"):
-        assert kernel in blob, kernel
+    # the float instantiations of the four row kernels, <T = float, FW> in their mangled names: kr_multidot<KMAX, f, FW> for some
+    # KMAX and FW, the other three as <f, FW>
+    for kernel in (rb"11kr_multidotILi\d+EfLi\d+EE", rb"9kr_updateIfLi\d+EE", rb"10kr_combineIfLi\d+EE", rb"14kr_scale_storeIfLi\d+EE"):
+        assert re.search(kernel, blob), kernel
 
 
 def test_argument_errors_without_a_device(hip_library):

@@ -198,6 +198,40 @@ def test_cg_on_an_spd_system(ctx, meshes):
     assert again.iterations == out.iterations and np.array_equal(again.x.cpu().numpy(), out.x.cpu().numpy())
 
 
+def test_fp64_basis_ignores_krylov_basis_width(ctx, meshes):
+    """The row kernels of a double basis are launched through the dispatch of the float ones and take one row per thread there,
+    whatever the option krylov_basis_width says: a width that leaked into them would regroup a thread's rows, the sums would change
+    their order and the bits below would differ. n = 257 is one full workgroup and a ragged tail. The operator is the leading
+    257 x 257 block of the matrix of test_cg_on_an_spd_system (symmetric positive definite like it), applied by a callback."""
+    from dolfinx_external_operator_amd import cg, gmres
+
+    torch = _torch(ctx)
+    m = structured_mesh("quadrilateral", (12, 10), 2, distort=0.1, seed=1)
+    A = _assemble(ctx, meshes(m), "eps", "eps", 2, elastic_C(m), bcs=bottom_dofs(m, 2))
+    n = 257
+    Ad = _cuda(A.to_scipy().tocsr()[:n, :n].toarray()).view(n, n)
+    b = _cuda(np.random.Generator(np.random.PCG64(10)).normal(size=n))
+
+    def apply(v, out):
+        torch.sum(Ad * v, dim=1, out=out)
+
+    saved = ctx.get_option("krylov_basis_width")
+    runs = []
+    try:
+        for width in (1, 2, 4):
+            ctx.set_option("krylov_basis_width", width)
+            g = gmres(apply, b, restart=8, rtol=1e-10, maxiter=400, ctx=ctx)
+            c = cg(apply, b, rtol=1e-10, maxiter=400, ctx=ctx)
+            assert g.basis == "fp64" and g.iterations > 8 and c.iterations > 1, (width, g.iterations, c.iterations)
+            runs.append((g, c))
+    finally:
+        ctx.set_option("krylov_basis_width", saved)
+    for pair in runs[1:]:
+        for r, first in zip(pair, runs[0]):
+            assert (r.iterations, r.restarts, r.residual, r.converged) == (first.iterations, first.restarts, first.residual, first.converged)
+            assert torch.equal(r.x, first.x)
+
+
 def test_matrix_free_operator_agrees_with_the_csr_path(ctx, meshes):
     """A callback that re-enters the library (dxo_bilinear_apply on the same context) as the operator."""
     from dolfinx_external_operator_amd import gmres

@@ -269,7 +269,7 @@ def test_block_inverses_are_the_inverses_of_the_blocks(case):
 # ---- known answers: operators whose GMRES / CG history is known in closed form (tests/test_krylov_known_answers_gpu.py runs the
 # same families on the device)
 U = float(np.finfo(float).eps) / 2                       # unit roundoff of float64
-SHIFT_D = (1, 2, 4, 5, 8, 9, 16, 17, 32, 33, 63, 64)      # both sides of every KMAX switch of kr_multidot_launch (4 / 8 / 16 / 32 / 64)
+SHIFT_D = (1, 2, 4, 5, 8, 9, 16, 17, 32, 33, 63, 64)      # both sides of every KMAX switch of kr_kmax (4 / 8 / 16 / 32 / 64)
 F2_C, F2_S, F2_D = 1.0, 0.8, 80                         # A = c I + s P on cycles longer than the longest restart
 GRID_CAP_256CU = 256 * 4 * 256                          # rows one trip of the row kernels covers on 256 compute units
 # (q, t) of the F2 sizes: n = 80 q + t = 80, 2480, 255, 256, 257, 70 003 (more than 256 partials), just above the grid cap of 256
