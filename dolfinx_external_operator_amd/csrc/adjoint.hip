@@ -32,9 +32,9 @@
 // Kernel variants that were measured and not shipped (contraction across the lanes as well, lane = cell tangent action) live in
 // scripts/exp/adjoint_variants.h and are compiled only with -DDXO_EXPERIMENTS.
 // What the kernels share is one function each: pull_back, group_cells, gather_vertices, point_jacobian (operand_core.h), store_entry,
-// sym_products / sym_dot (below); on the host consumer_grid, is_q2_hex .. is_p2_tri and wave_region.
+// sym_products / sym_dot (below); on the host wave_group_grid (form_host.h), is_q2_hex .. is_p2_tri and wave_region.
 #include "dxo_common.h"
-#include "operand_core.h"
+#include "form_host.h"
 #include "adjoint_cell.h"
 #include "cell8_dpp.h"
 #include "cell8_mfma.h"
@@ -912,28 +912,18 @@ bool is_q1_hex(const dxo_mesh* m) { return is_hex8(m, 8); }       // Q1 hexahedr
 bool is_p2_tet(const dxo_mesh* m) { return m->gdim == 3 && m->dev.ndofs == 10 && m->dev.ngeom == 4 && m->dev.nq == 4; }     // 4-point rule
 bool is_p2_tri(const dxo_mesh* m) { return m->gdim == 2 && m->dev.ndofs == 6 && m->dev.ngeom == 3 && m->dev.nq == 3; }      // 3-point rule
 
-// grid of the persistent element kernels: one workgroup (four waves) per four wave groups, at most blocks_per_cu per compute unit, whole
-// rounds over the 8 XCDs (xcd_group_walk)
-int64_t wave_groups(const dxo_mesh* m, int64_t n_cells) { return (n_cells + m->dev.cells_per_wave - 1) / m->dev.cells_per_wave; }
-int consumer_grid(const dxo_ctx* ctx, int64_t n_groups, int blocks_per_cu) {
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * blocks_per_cu;
-    if (blocks > cap) blocks = cap;
-    return (int)((blocks + 7) / 8 * 8);
-}
-
 // transposed dofmap on the device, built once per mesh from the host copy of the dofmap
 int ensure_transpose(dxo_ctx* ctx, dxo_mesh* m) {
     if (m->d_node_ptr) return DXO_OK;
-    const int64_t nc = m->num_cells, nd = m->dev.ndofs, nn = m->num_field_nodes;
+    const int64_t nc = m->num_cells, nd = m->dev.ndofs;
     if (nc * nd >= ((int64_t)1 << 32)) return DXO_E_SIZE;      // uint32 entries; the caller falls back to atomics
-    std::vector<int64_t> ptr((size_t)nn + 1, 0);
-    for (int64_t e = 0; e < nc * nd; ++e) ++ptr[(size_t)m->h_dofmap[(size_t)e] + 1];
-    for (int64_t n = 0; n < nn; ++n) ptr[(size_t)n + 1] += ptr[(size_t)n];
-    std::vector<uint32_t> ent((size_t)(nc * nd));
-    std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
-    for (int64_t e = 0; e < nc * nd; ++e)      // visited in ascending (cell, a): a fixed order per node; stored as the fe index a*nc + cell
-        ent[(size_t)fill[(size_t)m->h_dofmap[(size_t)e]]++] = (uint32_t)((e % nd) * nc + e / nd);
+    std::vector<int64_t> ptr;
+    std::vector<uint32_t> ent;
+    // visited in ascending (cell, a): a fixed order per node; stored as the fe index a*nc + cell
+    if (!transpose_incidence(nc * nd, m->num_field_nodes, [&](int64_t e) { return m->h_dofmap[(size_t)e]; },
+                             [&](int64_t e) { return (e % nd) * nc + e / nd; }, ptr, ent))
+        return DXO_E_SIZE;      // not reached: dxo_mesh_create refuses a dofmap entry outside the nodes
+    // both allocations, then both copies: the other order moves d_node_ent and costs node_sum's callers 2 % (profiles/form_fold_resources.txt)
     DXO_HIP(ctx, hipMalloc((void**)&m->d_node_ptr, ptr.size() * sizeof(int64_t)));
     DXO_HIP(ctx, hipMalloc((void**)&m->d_node_ent, (ent.size() + 4) * sizeof(uint32_t)));   // + 4: node_sum reads four indices at a time
     DXO_HIP(ctx, hipMemcpy(m->d_node_ptr, ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -951,13 +941,9 @@ int ensure_transpose(dxo_ctx* ctx, dxo_mesh* m) {
 double* two_pass_buffer(dxo_ctx* ctx, dxo_mesh* m, int bs, const int32_t* cells, int64_t n_cells) {
     if (ctx->adjoint_atomics || cells || n_cells != m->num_cells) return nullptr;
     if (ensure_transpose(ctx, m) != DXO_OK) return nullptr;
-    const size_t need = (size_t)m->num_cells * m->dev.ndofs * bs * sizeof(double);
-    if (m->fe_cap < need) {
-        if (m->d_fe) (void)hipFree(m->d_fe);
-        m->d_fe = nullptr;
-        m->fe_cap = 0;
-        if (hipMalloc((void**)&m->d_fe, need) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        m->fe_cap = need;
+    if (device_buf_try((void**)&m->d_fe, &m->fe_cap, (size_t)m->num_cells * m->dev.ndofs * bs * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
     }
     return m->d_fe;
 }
@@ -970,45 +956,20 @@ int clear_for_atomics(dxo_ctx* ctx, const dxo_mesh* m, int bs, double* out, cons
 }
 
 void launch_node_sum(const dxo_ctx* ctx, const dxo_mesh* m, int bs, double* out, hipStream_t s) {
-    int64_t blocks = (m->num_field_nodes + DXO_BLOCK - 1) / DXO_BLOCK;
-    const int64_t cap = (int64_t)ctx->compute_units * DXO_NS_BLOCKS_PER_CU;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-#define DXO_NS_LAUNCH(BS) hipLaunchKernelGGL(node_sum<BS>, dim3((int)blocks), dim3(DXO_BLOCK), 0, s, m->num_field_nodes, m->d_node_ptr, m->d_node_ent, m->d_fe, out, (int)(ctx->consumer_overwrite != 0))
-    if (bs == 1) DXO_NS_LAUNCH(1);
-    else if (bs == 2) DXO_NS_LAUNCH(2);
-    else DXO_NS_LAUNCH(3);
-#undef DXO_NS_LAUNCH
+    with_node_bs(bs, [&](auto BS) {
+        hipLaunchKernelGGL(node_sum<BS>, dim3(capped_grid(ctx, m->num_field_nodes, DXO_BLOCK, DXO_NS_BLOCKS_PER_CU)), dim3(DXO_BLOCK), 0, s,
+                           m->num_field_nodes, m->d_node_ptr, m->d_node_ent, m->d_fe, out, (int)(ctx->consumer_overwrite != 0));
+    });
 }
 
 template <int G, int BS, int KIND>
 void launch_adjoint(const dxo_ctx* ctx, const dxo_mesh* m, const double* S, const int32_t* cells, int64_t n_cells,
                     double* out, double* fe, hipStream_t s) {
     const int wd = adjoint_lds_wave(m);
-    const int blocks = consumer_grid(ctx, wave_groups(m, n_cells), 8);
+    const int blocks = wave_group_grid(ctx, wave_groups(m->dev, n_cells), 8);
     const size_t shm = (size_t)(m->dev.table_doubles + 4 * wd) * sizeof(double);
     hipLaunchKernelGGL((operand_adjoint<G, BS, KIND>), dim3(blocks), dim3(DXO_BLOCK), shm, s, m->dev, m->d_wq, wd, S,
                        cells, n_cells, out, fe);
-}
-
-template <int G, int BS>
-int dispatch_adjoint(const dxo_ctx* ctx, const dxo_mesh* m, int kind, const double* S, const int32_t* cells,
-                     int64_t n_cells, double* out, double* fe, hipStream_t s) {
-    switch (kind) {
-        case DXO_OPERAND_VALUE: launch_adjoint<G, BS, DXO_OPERAND_VALUE>(ctx, m, S, cells, n_cells, out, fe, s); return DXO_OK;
-        case DXO_OPERAND_GRAD: launch_adjoint<G, BS, DXO_OPERAND_GRAD>(ctx, m, S, cells, n_cells, out, fe, s); return DXO_OK;
-        case DXO_OPERAND_VALUE_GRAD: launch_adjoint<G, BS, DXO_OPERAND_VALUE_GRAD>(ctx, m, S, cells, n_cells, out, fe, s); return DXO_OK;
-        case DXO_OPERAND_EPS_MANDEL:
-            if constexpr (BS == G) { launch_adjoint<G, BS, DXO_OPERAND_EPS_MANDEL>(ctx, m, S, cells, n_cells, out, fe, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DEFGRAD:
-            if constexpr (BS == G) { launch_adjoint<G, BS, DXO_OPERAND_DEFGRAD>(ctx, m, S, cells, n_cells, out, fe, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DIV:
-            if constexpr (BS == G) { launch_adjoint<G, BS, DXO_OPERAND_DIV>(ctx, m, S, cells, n_cells, out, fe, s); return DXO_OK; }
-            return DXO_E_DIM;
-    }
-    return DXO_E_OPTION;
 }
 
 }  // namespace
@@ -1044,7 +1005,7 @@ extern "C" int dxo_operand_adjoint(dxo_ctx* ctx, dxo_mesh* mesh, int kind, int b
     DXO_LOCK(ctx);
     if (!mesh) return dxo_fail(ctx, DXO_E_NULL, "dxo_operand_adjoint: mesh is NULL");
     if (!mesh->d_wq) return dxo_fail(ctx, DXO_E_OPTION, "dxo_operand_adjoint: quadrature weights not set (dxo_mesh_set_weights)");
-    if (kind == DXO_OPERAND_CAUCHY_GREEN || kind == DXO_OPERAND_I1 || kind == DXO_OPERAND_DETF)
+    if (op_is_nonlinear(kind))
         return dxo_fail(ctx, DXO_E_OPTION, "dxo_operand_adjoint: a nonlinear operand (C, I1, det F) has no adjoint — its linearisation is a form UFL derives on the reference side");
     const int D = dxo_operand_value_size(mesh->gdim, bs, kind);
     if (D == DXO_E_OPTION) return dxo_fail(ctx, DXO_E_OPTION, "dxo_operand_adjoint: unknown operand kind");
@@ -1081,7 +1042,7 @@ extern "C" int dxo_operand_adjoint(dxo_ctx* ctx, dxo_mesh* mesh, int kind, int b
     if (rc != DXO_OK) return rc;
     if (c8) {
         // contraction across the cell's lanes, nothing staged in LDS (operand_adjoint_c8)
-        const int blocks = consumer_grid(ctx, (n_cells + 7) / 8, DXO_C8_ADJ_BLOCKS_PER_CU);
+        const int blocks = wave_group_grid(ctx, (n_cells + 7) / 8, DXO_C8_ADJ_BLOCKS_PER_CU);
         const size_t shm = (size_t)(C8_LDS + (ctx->adjoint_mfma ? (DXO_BLOCK / DXO_WAVE) * C8M_WAVE : 0)) * sizeof(double);
 #define DXO_C8_LAUNCH(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, S, n_cells, out, fe)
         if (ctx->adjoint_mfma) {      // the contraction on the f64 matrix pipe
@@ -1097,8 +1058,9 @@ extern "C" int dxo_operand_adjoint(dxo_ctx* ctx, dxo_mesh* mesh, int kind, int b
         launch_node_sum(ctx, mesh, bs, out, s);      // lane = cell form (adjoint_cell.h) for the standard elements
         return dxo_device_end(ctx, s);
     }
-    if (mesh->gdim == 2) rc = bs == 1 ? dispatch_adjoint<2, 1>(ctx, mesh, kind, S, cells, n_cells, out, fe, s) : dispatch_adjoint<2, 2>(ctx, mesh, kind, S, cells, n_cells, out, fe, s);
-    else                 rc = bs == 1 ? dispatch_adjoint<3, 1>(ctx, mesh, kind, S, cells, n_cells, out, fe, s) : dispatch_adjoint<3, 3>(ctx, mesh, kind, S, cells, n_cells, out, fe, s);
+    rc = with_form_shape(mesh->gdim, bs, [&](auto G, auto BS) {
+        return with_operand_kind<G, BS, true>(kind, [&](auto KIND) { launch_adjoint<G, BS, KIND>(ctx, mesh, S, cells, n_cells, out, fe, s); });
+    });
     if (rc != DXO_OK) return dxo_fail(ctx, rc, "dxo_operand_adjoint: unsupported (gdim, bs, kind)");
     if (fe) launch_node_sum(ctx, mesh, bs, out, s);
     return dxo_device_end(ctx, s);
@@ -1148,7 +1110,7 @@ int tangent_diagonal_impl(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, co
     if (rc != DXO_OK) return rc;
     rc = clear_for_atomics(ctx, mesh, mesh->gdim, out, fe, s);
     if (rc != DXO_OK) return rc;
-    const int blocks = consumer_grid(ctx, wave_groups(mesh, mesh->num_cells), vs ? DXO_TD_VM_BLOCKS_PER_CU : DXO_TD_BLOCKS_PER_CU);
+    const int blocks = wave_group_grid(ctx, wave_groups(mesh->dev, mesh->num_cells), vs ? DXO_TD_VM_BLOCKS_PER_CU : DXO_TD_BLOCKS_PER_CU);
     const VmStateSrc none{};
     const VmStateSrc& src = vs ? *vs : none;
 #define DXO_DIAG_LAUNCH(...) hipLaunchKernelGGL((tangent_diag<__VA_ARGS__>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C_tang, src, mesh->num_cells, out, fe)
@@ -1195,7 +1157,7 @@ int tangent_apply_impl(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, const
     if (rc != DXO_OK) return rc;
     rc = clear_for_atomics(ctx, mesh, mesh->gdim, out, fe, s);
     if (rc != DXO_OK) return rc;
-    const int blocks = consumer_grid(ctx, wave_groups(mesh, mesh->num_cells), vs ? DXO_TA_VM_BLOCKS_PER_CU : DXO_TA_BLOCKS_PER_CU);
+    const int blocks = wave_group_grid(ctx, wave_groups(mesh->dev, mesh->num_cells), vs ? DXO_TA_VM_BLOCKS_PER_CU : DXO_TA_BLOCKS_PER_CU);
     const VmStateSrc none{};
     const VmStateSrc& src = vs ? *vs : none;
 #define DXO_APPLY_LAUNCH(...) hipLaunchKernelGGL((tangent_apply<__VA_ARGS__>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C_tang, src, v, mesh->num_cells, out, fe)

@@ -8,7 +8,7 @@
 #pragma once
 
 #include "dxo_common.h"
-#include "operand_core.h"
+#include "form_host.h"
 
 namespace {
 
@@ -203,11 +203,9 @@ __global__ __launch_bounds__(DXO_BLOCK) void tangent_cell(const double* __restri
 #ifdef DXO_EXPERIMENTS
 inline bool launch_tangent_cell(const dxo_ctx* ctx, const dxo_mesh* m, const double* C_tang, const double* v, double* fe, hipStream_t s) {
     const OperandDev& d = m->dev;
-    int64_t blocks = (m->num_cells + DXO_BLOCK - 1) / DXO_BLOCK;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
+    const int blocks = capped_grid(ctx, m->num_cells, DXO_BLOCK, 8);
     if (m->gdim == 2 && d.ndofs == 6 && d.nq == 3 && d.ngeom == 3) {      // P2 triangles, 3-point rule (the reference demos)
-        hipLaunchKernelGGL((tangent_cell<2, 6, 3, 3>), dim3((int)blocks), dim3(DXO_BLOCK), 0, s, d.dphi, d.dpsi, m->d_wq, d.x, d.geom_dofmap,
+        hipLaunchKernelGGL((tangent_cell<2, 6, 3, 3>), dim3(blocks), dim3(DXO_BLOCK), 0, s, d.dphi, d.dpsi, m->d_wq, d.x, d.geom_dofmap,
                            d.dofmap, C_tang, v, m->num_cells, fe);
         return true;
     }
@@ -221,12 +219,10 @@ inline bool launch_tangent_cell(const dxo_ctx* ctx, const dxo_mesh* m, const dou
 #endif
 inline bool launch_adjoint_cell_eps(const dxo_ctx* ctx, const dxo_mesh* m, const double* S, double* fe, hipStream_t s) {
     const OperandDev& v = m->dev;
-    int64_t blocks = (m->num_cells + DXO_BLOCK - 1) / DXO_BLOCK;
-    const int64_t cap = (int64_t)ctx->compute_units * DXO_AC_BLOCKS_PER_CU;
-    if (blocks > cap) blocks = cap;
+    const int blocks = capped_grid(ctx, m->num_cells, DXO_BLOCK, DXO_AC_BLOCKS_PER_CU);
 #define DXO_CELL_CASE(G_, ND_, NQ_, NG_)                                                                                 \
     if (m->gdim == G_ && v.ndofs == ND_ && v.nq == NQ_ && v.ngeom == NG_) {                                               \
-        hipLaunchKernelGGL((adjoint_cell_eps<G_, ND_, NQ_, NG_>), dim3((int)blocks), dim3(DXO_BLOCK), 0, s, v.dphi, v.dpsi, \
+        hipLaunchKernelGGL((adjoint_cell_eps<G_, ND_, NQ_, NG_>), dim3(blocks), dim3(DXO_BLOCK), 0, s, v.dphi, v.dpsi,      \
                            m->d_wq, v.x, v.geom_dofmap, S, m->num_cells, fe);                                            \
         return true;                                                                                                      \
     }

@@ -23,7 +23,7 @@
 // reproducible to rounding only). Option "consumer_overwrite" = 1 clears `values` first (SET instead of accumulate).
 #include "csr.h"
 #include "dxo_common.h"
-#include "operand_core.h"
+#include "form_host.h"
 #include "operand_coef.h"
 
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
@@ -280,46 +280,11 @@ struct Assemble {
     }
 };
 
-template <int G, int BS, int TEST, int TRIAL>
-AssembleOps assemble_ops() {
-    return {&Assemble<G, BS, TEST, TRIAL>::lds_bytes, &Assemble<G, BS, TEST, TRIAL>::launch};
-}
-
-// the pairs of dxo_bilinear_apply; DEFGRAD is taken as its linearisation, GRAD
-template <int G>
-AssembleOps assemble_select_g(int bs, int test, int trial) {
-    constexpr int V = DXO_OPERAND_VALUE, GR = DXO_OPERAND_GRAD, VG = DXO_OPERAND_VALUE_GRAD, EPS = DXO_OPERAND_EPS_MANDEL;
-    if (bs == G) {
-        if (test == GR && trial == GR) return assemble_ops<G, G, GR, GR>();
-        if (test == EPS && trial == EPS) return assemble_ops<G, G, EPS, EPS>();
-    } else if (bs == 1) {
-        if (test == GR && trial == VG) return assemble_ops<G, 1, GR, VG>();
-        if (test == GR && trial == GR) return assemble_ops<G, 1, GR, GR>();
-        if (test == V && trial == V) return assemble_ops<G, 1, V, V>();
-        if (test == VG && trial == VG) return assemble_ops<G, 1, VG, VG>();
-    }
-    return {};
-}
-
-int grid_blocks(const dxo_ctx* ctx, int64_t work, int per_block) {
-    int64_t blocks = (work + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)ctx->compute_units * DXO_AS_BLOCKS_PER_CU;
-    if (blocks > cap) blocks = cap;
-    return blocks < 1 ? 1 : (int)blocks;
-}
+int grid_blocks(const dxo_ctx* ctx, int64_t work, int per_block) { return capped_grid(ctx, work, per_block, DXO_AS_BLOCKS_PER_CU); }
 
 void csr_free(dxo_csr* c) {
-    for (void* p : {(void*)c->d_row_ptr, (void*)c->d_col, (void*)c->d_inc_ptr, (void*)c->d_inc, (void*)c->d_pos, (void*)c->d_mask,
-                    (void*)c->d_ae})
-        if (p) (void)hipFree(p);
+    free_all({c->d_row_ptr, c->d_col, c->d_inc_ptr, c->d_inc, c->d_pos, c->d_mask, c->d_ae});
     delete c;
-}
-
-template <class T>
-int upload(dxo_ctx* ctx, T** dst, const std::vector<T>& src, size_t extra = 0) {
-    DXO_HIP(ctx, hipMalloc((void**)dst, (src.size() + extra) * sizeof(T) + 16));
-    if (!src.empty()) DXO_HIP(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return DXO_OK;
 }
 
 int csr_build(dxo_ctx* ctx, dxo_csr* c, const dxo_mesh* mesh) {
@@ -327,18 +292,10 @@ int csr_build(dxo_ctx* ctx, dxo_csr* c, const dxo_mesh* mesh) {
     const std::vector<int32_t>& dm = mesh->h_dofmap;
     if ((int64_t)dm.size() != nc * nd) return dxo_fail(ctx, DXO_E_DIM, "dxo_csr_create: the mesh keeps no host dofmap");
     // incidences, ascending (cell, a) per node
-    std::vector<int64_t> inc_ptr((size_t)nn + 1, 0);
-    for (int64_t e = 0; e < nc * nd; ++e) {
-        const int32_t n = dm[(size_t)e];
-        if (n < 0 || n >= nn) return dxo_fail(ctx, DXO_E_SIZE, "dxo_csr_create: dofmap entry out of range");
-        ++inc_ptr[(size_t)n + 1];
-    }
-    for (int64_t n = 0; n < nn; ++n) inc_ptr[(size_t)n + 1] += inc_ptr[(size_t)n];
-    std::vector<uint32_t> inc((size_t)(nc * nd));
-    {
-        std::vector<int64_t> fill(inc_ptr.begin(), inc_ptr.end() - 1);
-        for (int64_t e = 0; e < nc * nd; ++e) inc[(size_t)fill[(size_t)dm[(size_t)e]]++] = (uint32_t)e;
-    }
+    std::vector<int64_t> inc_ptr;
+    std::vector<uint32_t> inc;
+    if (!transpose_incidence(nc * nd, nn, [&](int64_t e) { return dm[(size_t)e]; }, [](int64_t e) { return e; }, inc_ptr, inc))
+        return dxo_fail(ctx, DXO_E_SIZE, "dxo_csr_create: dofmap entry out of range");
     // sorted neighbour nodes per node
     std::vector<int64_t> nb_ptr((size_t)nn + 1, 0);
     std::vector<int32_t> nb;
@@ -381,55 +338,38 @@ int csr_build(dxo_ctx* ctx, dxo_csr* c, const dxo_mesh* mesh) {
             for (int64_t b = 0; b < nd; ++b)
                 pos[(size_t)((cell * nd + a) * nd + b)] = (uint16_t)(std::lower_bound(lo, hi, dm[(size_t)(cell * nd + b)]) - lo);
         }
-    int rc;
-    if ((rc = upload(ctx, &c->d_row_ptr, row_ptr)) != DXO_OK) return rc;
-    if ((rc = upload(ctx, &c->d_col, col)) != DXO_OK) return rc;
-    if ((rc = upload(ctx, &c->d_inc_ptr, inc_ptr)) != DXO_OK) return rc;
-    if ((rc = upload(ctx, &c->d_inc, inc)) != DXO_OK) return rc;
-    if ((rc = upload(ctx, &c->d_pos, pos)) != DXO_OK) return rc;
+    // + 16 bytes: kernels read whole vectors past the end
+    int rc = to_device(ctx, &c->d_row_ptr, row_ptr, 16);
+    if (rc == DXO_OK) rc = to_device(ctx, &c->d_col, col, 16);
+    if (rc == DXO_OK) rc = to_device(ctx, &c->d_inc_ptr, inc_ptr, 16);
+    if (rc == DXO_OK) rc = to_device(ctx, &c->d_inc, inc, 16);
+    if (rc == DXO_OK) rc = to_device(ctx, &c->d_pos, pos, 16);
+    if (rc != DXO_OK) return rc;
     DXO_HIP(ctx, hipMalloc((void**)&c->d_mask, (size_t)c->n_rows + 16));
     return DXO_OK;
 }
 
 int assemble_impl(dxo_ctx* ctx, dxo_mesh* mesh, dxo_csr* csr, int test, int trial, int bs, const double* C, double* values) {
     const char* who = "dxo_bilinear_assemble";
-    char msg[320];
     if (!mesh || !csr || !C || !values) return dxo_fail(ctx, DXO_E_NULL, "dxo_bilinear_assemble: NULL argument");
-    auto nonlinear = [](int k) { return k == DXO_OPERAND_CAUCHY_GREEN || k == DXO_OPERAND_I1 || k == DXO_OPERAND_DETF; };
-    if (nonlinear(test) || nonlinear(trial)) {
-        snprintf(msg, sizeof msg, "%s: a nonlinear operand (C, I1, det F) has no bilinear form — pass its linearisation's block", who);
-        return dxo_fail(ctx, DXO_E_OPTION, msg);
-    }
-    const int t = test == DXO_OPERAND_DEFGRAD ? DXO_OPERAND_GRAD : test, r = trial == DXO_OPERAND_DEFGRAD ? DXO_OPERAND_GRAD : trial;
-    const bool defgrad_ok = (test != DXO_OPERAND_DEFGRAD && trial != DXO_OPERAND_DEFGRAD) || bs == mesh->gdim;
-    const AssembleOps ops = !defgrad_ok ? AssembleOps{} : mesh->gdim == 2 ? assemble_select_g<2>(bs, t, r) : assemble_select_g<3>(bs, t, r);
-    if (!ops.launch) {
-        snprintf(msg, sizeof msg, "%s: unsupported pair (test kind %d, trial kind %d, bs %d) on gdim %d: bs = gdim takes (grad|F, grad|F) and "
-                 "(eps, eps); bs = 1 takes (grad, value_grad), (grad, grad), (value, value), (value_grad, value_grad)", who, test, trial, bs, mesh->gdim);
-        return dxo_fail(ctx, DXO_E_OPTION, msg);
-    }
-    if (!mesh->d_wq) {
-        snprintf(msg, sizeof msg, "%s: quadrature weights not set (dxo_mesh_set_weights)", who);
-        return dxo_fail(ctx, DXO_E_OPTION, msg);
-    }
+    AssembleOps ops;
+    int rc = bilinear_pair_check(ctx, who, mesh, test, trial, bs, ops, [](auto G, auto BS, auto T, auto R) {
+        return AssembleOps{&Assemble<G, BS, T, R>::lds_bytes, &Assemble<G, BS, T, R>::launch};
+    });
+    if (rc != DXO_OK) return rc;
     if (csr->mesh != mesh || csr->bs != bs) {
+        char msg[320];
         snprintf(msg, sizeof msg, "%s: the pattern was made for another mesh or block size (pattern bs %d, call bs %d)", who, csr->bs, bs);
         return dxo_fail(ctx, DXO_E_DIM, msg);
     }
-    if (((uintptr_t)C & 15u) != 0) {
-        snprintf(msg, sizeof msg, "%s: C must be 16-byte aligned", who);
-        return dxo_fail(ctx, DXO_E_ALIGN, msg);
-    }
+    if (((uintptr_t)C & 15u) != 0) return fail_who(ctx, DXO_E_ALIGN, who, "C must be 16-byte aligned");
     const int nd = mesh->dev.ndofs;
     int cpb = DXO_AS_BLOCK / (nd * nd);
     if (cpb < 1) cpb = 1;
     if (cpb > 64) cpb = 64;
     while (cpb > 1 && ops.lds_bytes(mesh, cpb) > 64 * 1024) cpb /= 2;
     const size_t shm = ops.lds_bytes(mesh, cpb);
-    if (shm > 64 * 1024) {
-        snprintf(msg, sizeof msg, "%s: element too large for the LDS budget", who);
-        return dxo_fail(ctx, DXO_E_SIZE, msg);
-    }
+    if (shm > 64 * 1024) return fail_who(ctx, DXO_E_SIZE, who, "element too large for the LDS budget");
     hipStream_t s = dxo_launch_stream(ctx);
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t nc = mesh->num_cells;
@@ -438,14 +378,11 @@ int assemble_impl(dxo_ctx* ctx, dxo_mesh* mesh, dxo_csr* csr, int test, int tria
     if (chunk > nc) chunk = nc;
     if (chunk < 1) chunk = 1;
     const bool atomics = ctx->adjoint_atomics != 0;
-    if (!atomics && nc > 0 && csr->ae_cap < (size_t)chunk * cell_bytes) {     // the first call (or a larger chunk) allocates the scratch
-        if (csr->d_ae) DXO_HIP(ctx, hipFree(csr->d_ae));
-        csr->d_ae = nullptr;
-        csr->ae_cap = 0;
-        DXO_HIP(ctx, hipMalloc((void**)&csr->d_ae, (size_t)chunk * cell_bytes));
-        csr->ae_cap = (size_t)chunk * cell_bytes;
+    if (!atomics && nc > 0) {      // the first call (or a larger chunk) allocates the scratch
+        rc = device_buf(ctx, (void**)&csr->d_ae, &csr->ae_cap, (size_t)chunk * cell_bytes);
+        if (rc != DXO_OK) return rc;
     }
-    int rc = dxo_device_begin(ctx, s);
+    rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
     if (ctx->consumer_overwrite) DXO_HIP(ctx, hipMemsetAsync(values, 0, (size_t)csr->nnz * sizeof(double), s));
     if (nc > 0) {
@@ -456,9 +393,10 @@ int assemble_impl(dxo_ctx* ctx, dxo_mesh* mesh, dxo_csr* csr, int test, int tria
             for (int64_t c0 = 0; c0 < nc; c0 += chunk) {
                 const int64_t c1 = std::min(nc, c0 + chunk);
                 ops.launch(mesh, csr, cpb, grid_blocks(ctx, (c1 - c0 + cpb - 1) / cpb, 1), shm, C, c0, c1, csr->d_ae, values, s);
-                auto rows = bs == 1 ? assemble_rows<1> : bs == 2 ? assemble_rows<2> : assemble_rows<3>;
-                hipLaunchKernelGGL(rows, dim3(rblocks), dim3(DXO_AS_BLOCK), 0, s, csr->n_nodes, nd, csr->d_inc_ptr, csr->d_inc, csr->d_row_ptr,
-                                   csr->d_pos, csr->d_ae, c0, c1, values);
+                with_node_bs(bs, [&](auto BS) {
+                    hipLaunchKernelGGL(assemble_rows<BS>, dim3(rblocks), dim3(DXO_AS_BLOCK), 0, s, csr->n_nodes, nd, csr->d_inc_ptr, csr->d_inc,
+                                       csr->d_row_ptr, csr->d_pos, csr->d_ae, c0, c1, values);
+                });
             }
         }
     }

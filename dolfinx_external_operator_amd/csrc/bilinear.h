@@ -342,71 +342,28 @@ struct BilinearOps {
     void (*launch)(const dxo_mesh*, bool, int, int, size_t, const double*, const double*, double*, double*, hipStream_t) = nullptr;
 };
 
-template <int G, int BS, int TEST, int TRIAL>
-BilinearOps bilinear_ops() {
-    return {&Bilinear<G, BS, TEST, TRIAL>::lds_wave, &Bilinear<G, BS, TEST, TRIAL>::launch};
-}
-
-// the supported pairs (include/dxo.h); DEFGRAD is taken as its linearisation, GRAD
-template <int G>
-BilinearOps bilinear_select_g(int bs, int test, int trial) {
-    constexpr int V = DXO_OPERAND_VALUE, GR = DXO_OPERAND_GRAD, VG = DXO_OPERAND_VALUE_GRAD, EPS = DXO_OPERAND_EPS_MANDEL;
-    if (bs == G) {
-        if (test == GR && trial == GR) return bilinear_ops<G, G, GR, GR>();
-        if (test == EPS && trial == EPS) return bilinear_ops<G, G, EPS, EPS>();
-    } else if (bs == 1) {
-        if (test == GR && trial == VG) return bilinear_ops<G, 1, GR, VG>();
-        if (test == GR && trial == GR) return bilinear_ops<G, 1, GR, GR>();
-        if (test == V && trial == V) return bilinear_ops<G, 1, V, V>();
-        if (test == VG && trial == VG) return bilinear_ops<G, 1, VG, VG>();
-    }
-    return {};
-}
-
 int bilinear_impl(dxo_ctx* ctx, dxo_mesh* mesh, int test, int trial, int bs, const double* C, const double* v, double* out, bool diag) {
     const char* who = diag ? "dxo_bilinear_diagonal" : "dxo_bilinear_apply";
-    char msg[256];
     if (!mesh) return dxo_fail(ctx, DXO_E_NULL, diag ? "dxo_bilinear_diagonal: mesh is NULL" : "dxo_bilinear_apply: mesh is NULL");
-    auto nonlinear = [](int k) { return k == DXO_OPERAND_CAUCHY_GREEN || k == DXO_OPERAND_I1 || k == DXO_OPERAND_DETF; };
-    if (nonlinear(test) || nonlinear(trial)) {
-        snprintf(msg, sizeof msg, "%s: a nonlinear operand (C, I1, det F) has no bilinear form — pass its linearisation's block", who);
-        return dxo_fail(ctx, DXO_E_OPTION, msg);
-    }
-    const int t = test == DXO_OPERAND_DEFGRAD ? DXO_OPERAND_GRAD : test, r = trial == DXO_OPERAND_DEFGRAD ? DXO_OPERAND_GRAD : trial;
-    const bool defgrad_ok = (test != DXO_OPERAND_DEFGRAD && trial != DXO_OPERAND_DEFGRAD) || bs == mesh->gdim;
-    const BilinearOps ops = !defgrad_ok ? BilinearOps{} : mesh->gdim == 2 ? bilinear_select_g<2>(bs, t, r) : bilinear_select_g<3>(bs, t, r);
-    if (!ops.launch) {
-        snprintf(msg, sizeof msg, "%s: unsupported pair (test kind %d, trial kind %d, bs %d) on gdim %d: bs = gdim takes (grad|F, grad|F) and "
-                 "(eps, eps); bs = 1 takes (grad, value_grad), (grad, grad), (value, value), (value_grad, value_grad)", who, test, trial, bs, mesh->gdim);
-        return dxo_fail(ctx, DXO_E_OPTION, msg);
-    }
-    if (!mesh->d_wq) {
-        snprintf(msg, sizeof msg, "%s: quadrature weights not set (dxo_mesh_set_weights)", who);
-        return dxo_fail(ctx, DXO_E_OPTION, msg);
-    }
+    BilinearOps ops;
+    int rc = bilinear_pair_check(ctx, who, mesh, test, trial, bs, ops, [](auto G, auto BS, auto T, auto R) {
+        return BilinearOps{&Bilinear<G, BS, T, R>::lds_wave, &Bilinear<G, BS, T, R>::launch};
+    });
+    if (rc != DXO_OK) return rc;
     if (mesh->num_cells == 0) return DXO_OK;
-    if (!C || !out || (!diag && !v)) {
-        snprintf(msg, sizeof msg, "%s: NULL array", who);
-        return dxo_fail(ctx, DXO_E_NULL, msg);
-    }
-    if (((uintptr_t)C & 15u) != 0) {
-        snprintf(msg, sizeof msg, "%s: C must be 16-byte aligned", who);
-        return dxo_fail(ctx, DXO_E_ALIGN, msg);
-    }
+    if (!C || !out || (!diag && !v)) return fail_who(ctx, DXO_E_NULL, who, "NULL array");
+    if (((uintptr_t)C & 15u) != 0) return fail_who(ctx, DXO_E_ALIGN, who, "C must be 16-byte aligned");
     const int wd = ops.lds_wave(mesh, diag);
     const size_t shm = (size_t)(mesh->dev.table_doubles + (DXO_BLOCK / DXO_WAVE) * wd) * sizeof(double);
-    if (shm > 64 * 1024) {
-        snprintf(msg, sizeof msg, "%s: element too large for the LDS budget", who);
-        return dxo_fail(ctx, DXO_E_SIZE, msg);
-    }
+    if (shm > 64 * 1024) return fail_who(ctx, DXO_E_SIZE, who, "element too large for the LDS budget");
     hipStream_t s = dxo_launch_stream(ctx);
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     double* fe = two_pass_buffer(ctx, mesh, bs, nullptr, mesh->num_cells);
-    int rc = dxo_device_begin(ctx, s);
+    rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
     rc = clear_for_atomics(ctx, mesh, bs, out, fe, s);
     if (rc != DXO_OK) return rc;
-    ops.launch(mesh, diag, wd, consumer_grid(ctx, wave_groups(mesh, mesh->num_cells), DXO_BL_BLOCKS_PER_CU), shm, C, v, out, fe, s);
+    ops.launch(mesh, diag, wd, wave_group_grid(ctx, wave_groups(mesh->dev, mesh->num_cells), DXO_BL_BLOCKS_PER_CU), shm, C, v, out, fe, s);
     if (fe) launch_node_sum(ctx, mesh, bs, out, s);
     return dxo_device_end(ctx, s);
 }

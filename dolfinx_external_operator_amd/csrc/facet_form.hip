@@ -13,7 +13,7 @@
 //   facet_node_sum: lane = touched node, adds the node's entries of fe in ascending entity order (the set's transposed incidence).
 // No atomics: the result is bit-reproducible. The calls always accumulate into out.
 #include "dxo_common.h"
-#include "operand_core.h"
+#include "facet_tabs.h"
 
 #include <algorithm>
 
@@ -32,34 +32,6 @@ struct dxo_facet_set {
 namespace {
 
 constexpr int FACET_PRESSURE = -1;   // facet_element's "kind" for the pressure load
-
-// the facet tables and geometry of a mesh, as device pointers
-template <int G>
-struct FacetTabs {
-    int nqf, nd, ng;
-    const double* phi;      // [nf][nqf][nd]
-    const double* dphi;     // [nf][nqf][nd][G]
-    const double* dpsi;     // [nf][nqf][ng][G]
-    const double* w;        // [nqf]
-    const double* nref;     // [nf][G]
-    const double* jref;     // [nf][G][G-1]
-};
-
-template <int G>
-FacetTabs<G> facet_tabs(const dxo_mesh* m) {
-    const size_t nd = (size_t)m->dev.ndofs, nf = (size_t)m->n_local_facets, nqf = (size_t)m->nq_facet;
-    FacetTabs<G> t;
-    t.nqf = (int)nqf;
-    t.nd = (int)nd;
-    t.ng = m->dev.ngeom;
-    t.phi = m->d_facet_tab;
-    t.dphi = t.phi + nf * nqf * nd;
-    t.dpsi = t.dphi + nf * nqf * nd * G;
-    t.w = m->d_facet_geom;
-    t.nref = t.w + nqf;
-    t.jref = t.nref + nf * G;
-    return t;
-}
 
 // J^-1 (K), the outward unit normal and the point measure at point q of facet f of `cell`
 template <int G>
@@ -231,110 +203,60 @@ __global__ __launch_bounds__(DXO_BLOCK) void facet_node_sum(int64_t n_touched, c
     }
 }
 
-int grid(const dxo_ctx* ctx, int64_t units) {
-    int64_t blocks = std::max<int64_t>(1, (units + DXO_BLOCK - 1) / DXO_BLOCK);
-    return (int)std::min<int64_t>(blocks, (int64_t)ctx->compute_units * 8);
-}
-
 template <int G, int BS, int KIND>
 void launch_element(const dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, const double* S, double scale, hipStream_t s) {
     constexpr int PW = (KIND != FACET_PRESSURE && KIND != DXO_OPERAND_VALUE) ? BS * (1 + G) : BS;
     const FacetTabs<G> t = facet_tabs<G>(m);
     const int epb = DXO_BLOCK / t.nqf;
-    int64_t blocks = (set->n + epb - 1) / epb;
-    blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)ctx->compute_units * 8));
     const size_t shm = (size_t)epb * t.nqf * PW * sizeof(double);
-    hipLaunchKernelGGL((facet_element<G, BS, KIND>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents, set->n, S, scale,
-                       set->d_fe);
+    hipLaunchKernelGGL((facet_element<G, BS, KIND>), dim3(capped_grid(ctx, set->n, epb, 8)), dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents,
+                       set->n, S, scale, set->d_fe);
 }
 
 void launch_node_sum(const dxo_ctx* ctx, const dxo_facet_set* set, int bs, double* out, hipStream_t s) {
-    const int blocks = grid(ctx, set->n_touched);
-    if (bs == 1) hipLaunchKernelGGL(facet_node_sum<1>, dim3(blocks), dim3(DXO_BLOCK), 0, s, set->n_touched, set->d_tnode, set->d_tptr, set->d_tent, set->d_fe, out);
-    else if (bs == 2) hipLaunchKernelGGL(facet_node_sum<2>, dim3(blocks), dim3(DXO_BLOCK), 0, s, set->n_touched, set->d_tnode, set->d_tptr, set->d_tent, set->d_fe, out);
-    else hipLaunchKernelGGL(facet_node_sum<3>, dim3(blocks), dim3(DXO_BLOCK), 0, s, set->n_touched, set->d_tnode, set->d_tptr, set->d_tent, set->d_fe, out);
-}
-
-template <int G, int BS>
-int dispatch_adjoint(const dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, int kind, const double* S, hipStream_t s) {
-    switch (kind) {
-        case DXO_OPERAND_VALUE: launch_element<G, BS, DXO_OPERAND_VALUE>(ctx, m, set, S, 1.0, s); return DXO_OK;
-        case DXO_OPERAND_GRAD: launch_element<G, BS, DXO_OPERAND_GRAD>(ctx, m, set, S, 1.0, s); return DXO_OK;
-        case DXO_OPERAND_VALUE_GRAD: launch_element<G, BS, DXO_OPERAND_VALUE_GRAD>(ctx, m, set, S, 1.0, s); return DXO_OK;
-        case DXO_OPERAND_EPS_MANDEL:
-            if constexpr (BS == G) { launch_element<G, BS, DXO_OPERAND_EPS_MANDEL>(ctx, m, set, S, 1.0, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DEFGRAD:
-            if constexpr (BS == G) { launch_element<G, BS, DXO_OPERAND_DEFGRAD>(ctx, m, set, S, 1.0, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DIV:
-            if constexpr (BS == G) { launch_element<G, BS, DXO_OPERAND_DIV>(ctx, m, set, S, 1.0, s); return DXO_OK; }
-            return DXO_E_DIM;
-    }
-    return DXO_E_OPTION;
+    with_node_bs(bs, [&](auto BS) {
+        hipLaunchKernelGGL(facet_node_sum<BS>, dim3(capped_grid(ctx, set->n_touched, DXO_BLOCK, 8)), dim3(DXO_BLOCK), 0, s, set->n_touched,
+                           set->d_tnode, set->d_tptr, set->d_tent, set->d_fe, out);
+    });
 }
 
 // checks shared by the three calls; DXO_OK when the set may be used on the mesh
 int facet_ready(dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, const char* who) {
-    char buf[160];
-    if (!m || !set) {
-        std::snprintf(buf, sizeof buf, "%s: mesh or facet set is NULL", who);
-        return dxo_fail(ctx, DXO_E_NULL, buf);
-    }
-    if (!m->d_facet_tab || !m->d_facet_geom) {
-        std::snprintf(buf, sizeof buf, "%s: facet tables or facet geometry not set (dxo_mesh_set_facet_tables, dxo_mesh_set_facet_geometry)", who);
-        return dxo_fail(ctx, DXO_E_OPTION, buf);
-    }
-    if (set->mesh != m) {
-        std::snprintf(buf, sizeof buf, "%s: the facet set was created on another mesh", who);
-        return dxo_fail(ctx, DXO_E_DIM, buf);
-    }
-    if (m->nf_geom != m->n_local_facets || m->nq_geom != m->nq_facet || set->nf > m->n_local_facets || m->nq_facet > DXO_BLOCK) {
-        std::snprintf(buf, sizeof buf, "%s: facet tables, facet geometry and facet set disagree on (n_local_facets, nq)", who);
-        return dxo_fail(ctx, DXO_E_DIM, buf);
-    }
+    if (!m || !set) return fail_who(ctx, DXO_E_NULL, who, "mesh or facet set is NULL");
+    if (!m->d_facet_tab || !m->d_facet_geom)
+        return fail_who(ctx, DXO_E_OPTION, who, "facet tables or facet geometry not set (dxo_mesh_set_facet_tables, dxo_mesh_set_facet_geometry)");
+    if (set->mesh != m) return fail_who(ctx, DXO_E_DIM, who, "the facet set was created on another mesh");
+    if (m->nf_geom != m->n_local_facets || m->nq_geom != m->nq_facet || set->nf > m->n_local_facets || m->nq_facet > DXO_BLOCK)
+        return fail_who(ctx, DXO_E_DIM, who, "facet tables, facet geometry and facet set disagree on (n_local_facets, nq)");
     return DXO_OK;
 }
 
 void set_free(dxo_facet_set* set) {
-    if (set->d_ents) (void)hipFree(set->d_ents);
-    if (set->d_fe) (void)hipFree(set->d_fe);
-    if (set->d_tnode) (void)hipFree(set->d_tnode);
-    if (set->d_tptr) (void)hipFree(set->d_tptr);
-    if (set->d_tent) (void)hipFree(set->d_tent);
+    free_all({set->d_ents, set->d_fe, set->d_tnode, set->d_tptr, set->d_tent});
     delete set;
 }
 
 int set_build(dxo_ctx* ctx, dxo_facet_set* set, const dxo_mesh* m, const int32_t* ents) {
     const int64_t n = set->n, nd = set->nd;
-    const std::vector<int32_t>& dm = m->h_dofmap;
-    // transposed incidence over the touched nodes: entries visited in ascending (entity, a)
-    std::vector<int64_t> count((size_t)m->num_field_nodes + 1, 0);
-    for (int64_t e = 0; e < n; ++e)
-        for (int64_t a = 0; a < nd; ++a) ++count[(size_t)dm[(size_t)(ents[2 * e] * nd + a)] + 1];
+    // transposed incidence, entries visited in ascending (entity, a), kept for the touched nodes alone
+    std::vector<int64_t> ptr, tptr(1, 0);
+    std::vector<uint32_t> tent;
+    if (!transpose_incidence(n * nd, m->num_field_nodes, [&](int64_t i) { return m->h_dofmap[(size_t)(ents[2 * (i / nd)] * nd + i % nd)]; },
+                             [](int64_t i) { return i; }, ptr, tent))
+        return dxo_fail(ctx, DXO_E_SIZE, "dxo_facet_set_create: dofmap entry out of range");      // not reached: dxo_mesh_create refuses it
     std::vector<int32_t> tnode;
-    std::vector<int64_t> slot((size_t)m->num_field_nodes, -1), tptr(1, 0);
     for (int64_t v = 0; v < m->num_field_nodes; ++v)
-        if (count[(size_t)v + 1]) {
-            slot[(size_t)v] = tptr.back();
+        if (ptr[(size_t)v + 1] > ptr[(size_t)v]) {
             tnode.push_back((int32_t)v);
-            tptr.push_back(tptr.back() + count[(size_t)v + 1]);
+            tptr.push_back(ptr[(size_t)v + 1]);
         }
-    std::vector<uint32_t> tent((size_t)(n * nd));
-    for (int64_t e = 0; e < n; ++e)
-        for (int64_t a = 0; a < nd; ++a) tent[(size_t)slot[(size_t)dm[(size_t)(ents[2 * e] * nd + a)]]++] = (uint32_t)(e * nd + a);
     set->n_touched = (int64_t)tnode.size();
-    const size_t G = (size_t)m->gdim;
-    DXO_HIP(ctx, hipMalloc((void**)&set->d_ents, (size_t)n * 2 * sizeof(int32_t)));
-    DXO_HIP(ctx, hipMalloc((void**)&set->d_fe, (size_t)(n * nd) * G * sizeof(double)));
-    DXO_HIP(ctx, hipMalloc((void**)&set->d_tnode, tnode.size() * sizeof(int32_t)));
-    DXO_HIP(ctx, hipMalloc((void**)&set->d_tptr, tptr.size() * sizeof(int64_t)));
-    DXO_HIP(ctx, hipMalloc((void**)&set->d_tent, tent.size() * sizeof(uint32_t)));
-    DXO_HIP(ctx, hipMemcpy(set->d_ents, ents, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
-    DXO_HIP(ctx, hipMemcpy(set->d_tnode, tnode.data(), tnode.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    DXO_HIP(ctx, hipMemcpy(set->d_tptr, tptr.data(), tptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    DXO_HIP(ctx, hipMemcpy(set->d_tent, tent.data(), tent.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return DXO_OK;
+    DXO_HIP(ctx, hipMalloc((void**)&set->d_fe, (size_t)(n * nd) * m->gdim * sizeof(double)));
+    int rc = to_device(ctx, &set->d_ents, ents, (size_t)n * 2);
+    if (rc == DXO_OK) rc = to_device(ctx, &set->d_tnode, tnode);
+    if (rc == DXO_OK) rc = to_device(ctx, &set->d_tptr, tptr);
+    if (rc == DXO_OK) rc = to_device(ctx, &set->d_tent, tent);
+    return rc;
 }
 
 }  // namespace
@@ -370,9 +292,7 @@ extern "C" int dxo_facet_set_create(dxo_ctx* ctx, dxo_mesh* m, const int32_t* en
     if (!m->d_facet_tab) return dxo_fail(ctx, DXO_E_OPTION, "dxo_facet_set_create: call dxo_mesh_set_facet_tables first");
     if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_facet_set_create: n < 0");
     if (n * m->dev.ndofs >= ((int64_t)1 << 32)) return dxo_fail(ctx, DXO_E_SIZE, "dxo_facet_set_create: 2^32 or more (entity, dof) entries");
-    for (int64_t i = 0; i < n; ++i)
-        if (entities[2 * i] < 0 || entities[2 * i] >= m->num_cells || entities[2 * i + 1] < 0 || entities[2 * i + 1] >= m->n_local_facets)
-            return dxo_fail(ctx, DXO_E_SIZE, "dxo_facet_set_create: entity outside [0, num_cells) x [0, n_local_facets)");
+    if (!facet_entities_ok(m, entities, n)) return dxo_fail(ctx, DXO_E_SIZE, "dxo_facet_set_create: entity outside [0, num_cells) x [0, n_local_facets)");
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     dxo_facet_set* set = new dxo_facet_set;
     set->mesh = m;
@@ -409,9 +329,10 @@ extern "C" int dxo_eval_facet_geometry(dxo_ctx* ctx, dxo_mesh* m, const dxo_face
     hipStream_t s = dxo_launch_stream(ctx);
     rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    const int blocks = grid(ctx, set->n * m->nq_facet);
-    if (m->gdim == 2) hipLaunchKernelGGL(facet_geometry<2>, dim3(blocks), dim3(DXO_BLOCK), 0, s, m->dev, facet_tabs<2>(m), set->d_ents, set->n, normals, dS);
-    else              hipLaunchKernelGGL(facet_geometry<3>, dim3(blocks), dim3(DXO_BLOCK), 0, s, m->dev, facet_tabs<3>(m), set->d_ents, set->n, normals, dS);
+    with_gdim(m->gdim, [&](auto G) {
+        hipLaunchKernelGGL(facet_geometry<G>, dim3(capped_grid(ctx, set->n * m->nq_facet, DXO_BLOCK, 8)), dim3(DXO_BLOCK), 0, s, m->dev,
+                           facet_tabs<G>(m), set->d_ents, set->n, normals, dS);
+    });
     return dxo_device_end(ctx, s);
 }
 
@@ -420,8 +341,7 @@ extern "C" int dxo_facet_adjoint(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set*
     DXO_LOCK(ctx);
     int rc = facet_ready(ctx, m, set, "dxo_facet_adjoint");
     if (rc != DXO_OK) return rc;
-    if (kind == DXO_OPERAND_CAUCHY_GREEN || kind == DXO_OPERAND_I1 || kind == DXO_OPERAND_DETF)
-        return dxo_fail(ctx, DXO_E_OPTION, "dxo_facet_adjoint: a nonlinear operand (C, I1, det F) has no adjoint");
+    if (op_is_nonlinear(kind)) return dxo_fail(ctx, DXO_E_OPTION, "dxo_facet_adjoint: a nonlinear operand (C, I1, det F) has no adjoint");
     const int D = dxo_operand_value_size(m->gdim, bs, kind);
     if (D == DXO_E_OPTION) return dxo_fail(ctx, DXO_E_OPTION, "dxo_facet_adjoint: unknown operand kind");
     if (D < 0 || (bs != 1 && bs != m->gdim)) return dxo_fail(ctx, DXO_E_DIM, "dxo_facet_adjoint: block size does not fit the operand kind / gdim (bs = 1 or gdim)");
@@ -431,8 +351,9 @@ extern "C" int dxo_facet_adjoint(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set*
     hipStream_t s = dxo_launch_stream(ctx);
     rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    if (m->gdim == 2) rc = bs == 1 ? dispatch_adjoint<2, 1>(ctx, m, set, kind, S, s) : dispatch_adjoint<2, 2>(ctx, m, set, kind, S, s);
-    else              rc = bs == 1 ? dispatch_adjoint<3, 1>(ctx, m, set, kind, S, s) : dispatch_adjoint<3, 3>(ctx, m, set, kind, S, s);
+    rc = with_form_shape(m->gdim, bs, [&](auto G, auto BS) {
+        return with_operand_kind<G, BS, true>(kind, [&](auto KIND) { launch_element<G, BS, KIND>(ctx, m, set, S, 1.0, s); });
+    });
     if (rc != DXO_OK) return dxo_fail(ctx, rc, "dxo_facet_adjoint: unsupported (gdim, bs, kind)");
     launch_node_sum(ctx, set, bs, out, s);
     return dxo_device_end(ctx, s);
@@ -449,8 +370,7 @@ extern "C" int dxo_facet_pressure(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set
     hipStream_t s = dxo_launch_stream(ctx);
     rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    if (m->gdim == 2) launch_element<2, 2, FACET_PRESSURE>(ctx, m, set, p, scale, s);
-    else              launch_element<3, 3, FACET_PRESSURE>(ctx, m, set, p, scale, s);
+    with_gdim(m->gdim, [&](auto G) { launch_element<G, G, FACET_PRESSURE>(ctx, m, set, p, scale, s); });
     launch_node_sum(ctx, set, m->gdim, out, s);
     return dxo_device_end(ctx, s);
 }

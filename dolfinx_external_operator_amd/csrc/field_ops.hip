@@ -17,7 +17,7 @@
 // = operand launch + constitutive launch on the chunk's stream.
 #include "dxo_common.h"
 #include "hyper_core.h"
-#include "operand_core.h"
+#include "form_host.h"
 
 namespace {
 
@@ -88,13 +88,9 @@ int isi_field_launch(dxo_ctx* ctx, const IsiFieldLaunch& L, int64_t cell0, int64
     wd = (wd + 1) & ~1;
     const size_t shm = (size_t)(m.table_doubles + 4 * wd) * sizeof(double);
     if (shm > 64 * 1024) return dxo_fail(ctx, DXO_E_SIZE, "dxo_isihara_field: element too large for the LDS budget");
-    const int64_t n_groups = (n_cells + m.cells_per_wave - 1) / m.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;
-    if (ctx->nontemporal != 0) hipLaunchKernelGGL(isihara_field<true>, dim3((int)blocks), dim3(DXO_BLOCK), shm, s, L.prm, m, wd, cell0, n_cells, L.d_u, dP, P);
-    else hipLaunchKernelGGL(isihara_field<false>, dim3((int)blocks), dim3(DXO_BLOCK), shm, s, L.prm, m, wd, cell0, n_cells, L.d_u, dP, P);
+    const int blocks = wave_group_grid(ctx, wave_groups(m, n_cells), 8);
+    if (ctx->nontemporal != 0) hipLaunchKernelGGL(isihara_field<true>, dim3(blocks), dim3(DXO_BLOCK), shm, s, L.prm, m, wd, cell0, n_cells, L.d_u, dP, P);
+    else hipLaunchKernelGGL(isihara_field<false>, dim3(blocks), dim3(DXO_BLOCK), shm, s, L.prm, m, wd, cell0, n_cells, L.d_u, dP, P);
     return DXO_OK;
 }
 
@@ -107,13 +103,8 @@ int isi_field_chunk(dxo_ctx* ctx, void* user, int64_t n_chunk, void* const*, voi
 
 int upload_u(dxo_ctx* ctx, dxo_mesh* mesh, const double* u) {
     const size_t ub = (size_t)mesh->num_field_nodes * mesh->gdim * sizeof(double);
-    if (mesh->u_cap < ub) {
-        if (mesh->d_u) DXO_HIP(ctx, hipFree(mesh->d_u));
-        mesh->d_u = nullptr;
-        mesh->u_cap = 0;
-        DXO_HIP(ctx, hipMalloc((void**)&mesh->d_u, ub));
-        mesh->u_cap = ub;
-    }
+    const int rc = device_buf(ctx, (void**)&mesh->d_u, &mesh->u_cap, ub);
+    if (rc != DXO_OK) return rc;
     DXO_HIP(ctx, hipMemcpy(mesh->d_u, u, ub, hipMemcpyHostToDevice));
     return DXO_OK;
 }

@@ -6,7 +6,7 @@
 // kind VALUE_GRAD) and applies k = 1/(A + B T), q = -k sigma, dq/dT = B k^2 sigma, dq/dsigma = -k I; the results leave
 // through the wave's LDS slice in output order. The operand arrays never exist in memory.
 #include "dxo_common.h"
-#include "operand_core.h"
+#include "form_host.h"
 
 namespace {
 
@@ -76,16 +76,10 @@ int heat_field_launch(dxo_ctx* ctx, const HeatFieldLaunch& L, int64_t cell0, int
     if (n_cells == 0) return DXO_OK;
     const OperandDev& m = L.mesh->dev;
     const size_t shm = (size_t)(m.table_doubles + 4 * m.wave_doubles) * sizeof(double);
-    const int64_t n_groups = (n_cells + m.cells_per_wave - 1) / m.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;
-    if (L.mesh->gdim == 2)
-        hipLaunchKernelGGL(heat_field<2>, dim3((int)blocks), dim3(DXO_BLOCK), shm, s, L.A, L.B, m, cell0, n_cells, L.d_T, q, dqdT, dqds);
-    else
-        hipLaunchKernelGGL(heat_field<3>, dim3((int)blocks), dim3(DXO_BLOCK), shm, s, L.A, L.B, m, cell0, n_cells, L.d_T, q, dqdT, dqds);
-    return DXO_OK;
+    return with_gdim(L.mesh->gdim, [&](auto G) {
+        hipLaunchKernelGGL(heat_field<G>, dim3(wave_group_grid(ctx, wave_groups(m, n_cells), 8)), dim3(DXO_BLOCK), shm, s, L.A, L.B, m, cell0, n_cells,
+                           L.d_T, q, dqdT, dqds);
+    });
 }
 
 int heat_field_chunk(dxo_ctx* ctx, void* user, int64_t n_chunk, void* const*, void* const* d_out, hipStream_t s) {
@@ -124,13 +118,8 @@ extern "C" int dxo_heat_field(dxo_ctx* ctx, double A, double B, dxo_mesh* mesh, 
         return dxo_device_end(ctx, s);
     }
     const size_t tb = (size_t)mesh->num_field_nodes * sizeof(double);
-    if (mesh->u_cap < tb) {
-        if (mesh->d_u) DXO_HIP(ctx, hipFree(mesh->d_u));
-        mesh->d_u = nullptr;
-        mesh->u_cap = 0;
-        DXO_HIP(ctx, hipMalloc((void**)&mesh->d_u, tb));
-        mesh->u_cap = tb;
-    }
+    const int rc = device_buf(ctx, (void**)&mesh->d_u, &mesh->u_cap, tb);
+    if (rc != DXO_OK) return rc;
     DXO_HIP(ctx, hipMemcpy(mesh->d_u, T_dofs, tb, hipMemcpyHostToDevice));
     L.d_T = mesh->d_u;
     const size_t sd = sizeof(double) * (size_t)nq;

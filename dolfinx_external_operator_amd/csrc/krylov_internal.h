@@ -1,23 +1,12 @@
 // krylov_internal.h — what krylov.hip and amg.hip share. Device code: the row of a node in the csr.h layout (NodeRow), the search for
 // a block in it (block_pos), the lane-group row product behind every SpMV-shaped kernel of the two files (row_product) and the
 // inverse of a diagonal block with its singularity test (invert_block: closed form up to bs 3, Gauss-Jordan in registers for bs 6).
-// Host code: the dispatcher from run-time shapes to template arguments (with_int, with_bs) and the launchers one file calls in the
+// Host code: the block-size list of the dispatcher from run-time shapes to template arguments (with_bs over with_int of form_host.h) and the launchers one file calls in the
 // other (device pointers, explicit stream, no locking, no event bracket).
 #pragma once
 
 #include "csr.h"
-
-#include <type_traits>
-
-// from a run-time value to a compile-time one: f(int_c<N>) for the entry N of the list that equals v, miss(v) for none. A list is the
-// set of instantiations of its caller, so a kernel's argument list is written once
-template <int N>
-using int_c = std::integral_constant<int, N>;
-
-template <int... Ns, class F, class Miss>
-void with_int(int v, F&& f, Miss&& miss) {
-    if (!((v == Ns && (f(int_c<Ns>{}), true)) || ...)) miss(v);
-}
+#include "form_host.h"      // int_c, with_int
 
 // the block sizes with an SpMV and a block inverse: 1, 2, 3 of the patterns of dxo_csr_create, 6 of a multigrid level
 template <class F, class Miss>

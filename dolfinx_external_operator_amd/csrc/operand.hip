@@ -17,7 +17,7 @@
 // lane accumulates Gref = sum_a u_a (x) dphi_a(q), multiplies by J^-1, and the wave writes its points in output
 // order through LDS (consecutive 8-byte words per store instruction). No __syncthreads inside the cell loop.
 #include "dxo_common.h"
-#include "operand_core.h"
+#include "form_host.h"
 #include "operand_cell.h"
 
 namespace {
@@ -92,61 +92,22 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_eval(OperandDev m, const do
 namespace {
 
 template <int G, int BS, int KIND>
-void launch_operand_dev(const dxo_ctx* ctx, const OperandDev& dev, const double* u, const int32_t* cells, int64_t n_cells,
-                        double* out, hipStream_t s) {
-    const int64_t n_groups = (n_cells + dev.cells_per_wave - 1) / dev.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;      // whole rounds over the 8 XCDs (xcd_group_walk)
+void launch_operand(const dxo_ctx* ctx, const OperandDev& dev, const double* u, const int32_t* cells, int64_t n_cells, double* out,
+                    hipStream_t s) {
+    const int blocks = wave_group_grid(ctx, wave_groups(dev, n_cells), 8);
     const size_t shm = (size_t)(dev.table_doubles + 4 * dev.wave_doubles) * sizeof(double);
-    hipLaunchKernelGGL((operand_eval<G, BS, KIND>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, dev, u, cells, n_cells, out);
-}
-
-template <int G, int BS, int KIND>
-void launch_operand(const dxo_ctx* ctx, const dxo_mesh* m, const double* u, const int32_t* cells, int64_t n_cells,
-                    double* out, hipStream_t s) {
-    const int64_t n_groups = (n_cells + m->dev.cells_per_wave - 1) / m->dev.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;      // whole rounds over the 8 XCDs (xcd_group_walk)
-    const size_t shm = (size_t)(m->dev.table_doubles + 4 * m->dev.wave_doubles) * sizeof(double);
-    hipLaunchKernelGGL((operand_eval<G, BS, KIND>), dim3((int)blocks), dim3(DXO_BLOCK), shm, s, m->dev, u, cells, n_cells, out);
+    hipLaunchKernelGGL((operand_eval<G, BS, KIND>), dim3(blocks), dim3(DXO_BLOCK), shm, s, dev, u, cells, n_cells, out);
 }
 
 template <int G, int BS>
-int dispatch_kind(const dxo_ctx* ctx, const dxo_mesh* m, int kind, const double* u, const int32_t* cells,
-                  int64_t n_cells, double* out, hipStream_t s) {
-    switch (kind) {
-        case DXO_OPERAND_VALUE: launch_operand<G, BS, DXO_OPERAND_VALUE>(ctx, m, u, cells, n_cells, out, s); return DXO_OK;
-        case DXO_OPERAND_GRAD: launch_operand<G, BS, DXO_OPERAND_GRAD>(ctx, m, u, cells, n_cells, out, s); return DXO_OK;
-        case DXO_OPERAND_VALUE_GRAD: launch_operand<G, BS, DXO_OPERAND_VALUE_GRAD>(ctx, m, u, cells, n_cells, out, s); return DXO_OK;
-        case DXO_OPERAND_EPS_MANDEL:
-            if constexpr (BS == G) {
-                // standard elements, all cells: lane = cell kernel (registers + scalar tables, no LDS in the contraction)
-                if (!cells && ctx->operand_cell && launch_operand_cell_eps(ctx, m, u, n_cells, out, s)) return DXO_OK;
-                launch_operand<G, BS, DXO_OPERAND_EPS_MANDEL>(ctx, m, u, cells, n_cells, out, s);
-                return DXO_OK;
-            }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DEFGRAD:
-            if constexpr (BS == G) { launch_operand<G, BS, DXO_OPERAND_DEFGRAD>(ctx, m, u, cells, n_cells, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_CAUCHY_GREEN:
-            if constexpr (BS == G) { launch_operand<G, BS, DXO_OPERAND_CAUCHY_GREEN>(ctx, m, u, cells, n_cells, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_I1:
-            if constexpr (BS == G) { launch_operand<G, BS, DXO_OPERAND_I1>(ctx, m, u, cells, n_cells, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DETF:
-            if constexpr (BS == G) { launch_operand<G, BS, DXO_OPERAND_DETF>(ctx, m, u, cells, n_cells, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DIV:
-            if constexpr (BS == G) { launch_operand<G, BS, DXO_OPERAND_DIV>(ctx, m, u, cells, n_cells, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-    }
-    return DXO_E_OPTION;
+int dispatch_kind(const dxo_ctx* ctx, const dxo_mesh* m, int kind, const double* u, const int32_t* cells, int64_t n_cells, double* out,
+                  hipStream_t s) {
+    return with_operand_kind<G, BS, false>(kind, [&](auto KIND) {
+        // standard elements, all cells: lane = cell kernel (registers + scalar tables, no LDS in the contraction)
+        if constexpr (KIND == DXO_OPERAND_EPS_MANDEL)
+            if (!cells && ctx->operand_cell && launch_operand_cell_eps(ctx, m, u, n_cells, out, s)) return;
+        launch_operand<G, BS, KIND>(ctx, m->dev, u, cells, n_cells, out, s);
+    });
 }
 
 // A Lagrange field of ANY block size (the reference evaluates whatever `fem.Expression` is handed: test/test_nested_ex_op.py:113-118 uses a
@@ -161,20 +122,10 @@ int dispatch_components(const dxo_ctx* ctx, const dxo_mesh* m, int kind, int bs,
     dev.out_stride = kind == DXO_OPERAND_VALUE ? bs : kind == DXO_OPERAND_GRAD ? bs * G : bs * (1 + G);
     for (int c = 0; c < bs; ++c) {
         if (kind == DXO_OPERAND_VALUE || kind == DXO_OPERAND_VALUE_GRAD)
-            launch_operand_dev<G, 1, DXO_OPERAND_VALUE>(ctx, dev, u + c, cells, n_cells, out + c, s);
+            launch_operand<G, 1, DXO_OPERAND_VALUE>(ctx, dev, u + c, cells, n_cells, out + c, s);
         if (kind == DXO_OPERAND_GRAD || kind == DXO_OPERAND_VALUE_GRAD)
-            launch_operand_dev<G, 1, DXO_OPERAND_GRAD>(ctx, dev, u + c, cells, n_cells, out + (kind == DXO_OPERAND_GRAD ? 0 : bs) + c * G, s);
+            launch_operand<G, 1, DXO_OPERAND_GRAD>(ctx, dev, u + c, cells, n_cells, out + (kind == DXO_OPERAND_GRAD ? 0 : bs) + c * G, s);
     }
-    return DXO_OK;
-}
-
-int ensure(dxo_ctx* ctx, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return DXO_OK;
-    if (*p) DXO_HIP(ctx, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    DXO_HIP(ctx, hipMalloc(p, bytes));
-    *cap = bytes;
     return DXO_OK;
 }
 
@@ -190,17 +141,12 @@ int dxo_operand_launch_range(dxo_ctx* ctx, const dxo_mesh* mesh, int kind, int b
     dev.geom_dofmap += cell0 * dev.ngeom;
     const int G = mesh->gdim;
     if (bs != G) return DXO_E_DIM;
-    if (kind == DXO_OPERAND_EPS_MANDEL) {
-        if (G == 2) launch_operand_dev<2, 2, DXO_OPERAND_EPS_MANDEL>(ctx, dev, u_dev, nullptr, n_cells, out_dev, s);
-        else launch_operand_dev<3, 3, DXO_OPERAND_EPS_MANDEL>(ctx, dev, u_dev, nullptr, n_cells, out_dev, s);
-        return DXO_OK;
-    }
-    if (kind == DXO_OPERAND_DEFGRAD) {
-        if (G == 2) launch_operand_dev<2, 2, DXO_OPERAND_DEFGRAD>(ctx, dev, u_dev, nullptr, n_cells, out_dev, s);
-        else launch_operand_dev<3, 3, DXO_OPERAND_DEFGRAD>(ctx, dev, u_dev, nullptr, n_cells, out_dev, s);
-        return DXO_OK;
-    }
-    return DXO_E_OPTION;
+    if (kind != DXO_OPERAND_EPS_MANDEL && kind != DXO_OPERAND_DEFGRAD) return DXO_E_OPTION;
+    return with_gdim(G, [&](auto GD) {
+        with_int<DXO_OPERAND_EPS_MANDEL, DXO_OPERAND_DEFGRAD>(kind, [&](auto KIND) {
+            launch_operand<GD, GD, KIND>(ctx, dev, u_dev, nullptr, n_cells, out_dev, s);
+        }, [](int) {});
+    });
 }
 
 extern "C" int dxo_operand_value_size(int gdim, int bs, int kind) {
@@ -298,20 +244,8 @@ extern "C" int dxo_mesh_destroy(dxo_ctx* ctx, dxo_mesh* m) {
     if (!m) return DXO_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    if (m->blob) (void)hipFree(m->blob);
-    if (m->d_u) (void)hipFree(m->d_u);
-    if (m->d_cells) (void)hipFree(m->d_cells);
-    if (m->d_out) (void)hipFree(m->d_out);
-    if (m->d_facet_tab) (void)hipFree(m->d_facet_tab);
-    if (m->d_facet_geom) (void)hipFree(m->d_facet_geom);
-    if (m->d_ents) (void)hipFree(m->d_ents);
-    if (m->d_wq) (void)hipFree(m->d_wq);
-    if (m->d_psi) (void)hipFree(m->d_psi);
-    if (m->d_node_ptr) (void)hipFree(m->d_node_ptr);
-    if (m->d_node_ent) (void)hipFree(m->d_node_ent);
-    if (m->d_fe) (void)hipFree(m->d_fe);
-    if (m->patch.blob) (void)hipFree(m->patch.blob);
-    if (m->patch.dev.bpart) (void)hipFree(m->patch.dev.bpart);
+    free_all({m->blob, m->d_u, m->d_cells, m->d_out, m->d_facet_tab, m->d_facet_geom, m->d_ents, m->d_wq, m->d_psi, m->d_node_ptr, m->d_node_ent,
+              m->d_fe, m->patch.blob, m->patch.dev.bpart});
     delete m;
     return DXO_OK;
 }
@@ -358,29 +292,19 @@ extern "C" int dxo_eval_coordinate(dxo_ctx* ctx, dxo_mesh* m, int mem, const int
     double* dout = out;
     const size_t out_bytes = (size_t)n_cells * dev.nq * G * sizeof(double);
     if (mem == DXO_MEM_HOST) {
-        if (cells) {
-            for (int64_t i = 0; i < n_cells; ++i)
-                if (cells[i] < 0 || cells[i] >= m->num_cells) return dxo_fail(ctx, DXO_E_SIZE, "dxo_eval_coordinate: entity outside [0, num_cells)");
-            int rc = ensure(ctx, (void**)&m->d_cells, &m->cells_cap, (size_t)n_cells * sizeof(int32_t));
-            if (rc != DXO_OK) return rc;
-            DXO_HIP(ctx, hipMemcpyAsync(m->d_cells, cells, (size_t)n_cells * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            dc = m->d_cells;
-        }
-        int rc = ensure(ctx, (void**)&m->d_out, &m->out_cap, out_bytes);
+        if (!cells_ok(m, cells, n_cells)) return dxo_fail(ctx, DXO_E_SIZE, "dxo_eval_coordinate: entity outside [0, num_cells)");
+        int rc = cells ? stage_in(ctx, &m->d_cells, &m->cells_cap, cells, (size_t)n_cells, s, &dc) : DXO_OK;
+        if (rc == DXO_OK) rc = device_buf(ctx, (void**)&m->d_out, &m->out_cap, out_bytes);
         if (rc != DXO_OK) return rc;
         dout = m->d_out;
     }
     int rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    if (G == 2) launch_operand_dev<2, 2, DXO_OPERAND_VALUE>(ctx, dev, dev.x, dc, n_cells, dout, s);
-    else        launch_operand_dev<3, 3, DXO_OPERAND_VALUE>(ctx, dev, dev.x, dc, n_cells, dout, s);
+    rc = with_gdim(G, [&](auto GD) { launch_operand<GD, GD, DXO_OPERAND_VALUE>(ctx, dev, dev.x, dc, n_cells, dout, s); });
+    if (rc != DXO_OK) return rc;
     rc = dxo_device_end(ctx, s);
     if (rc != DXO_OK) return rc;
-    if (mem == DXO_MEM_HOST) {
-        DXO_HIP(ctx, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return DXO_OK;
+    return mem == DXO_MEM_HOST ? stage_out(ctx, out, dout, out_bytes, s) : DXO_OK;
 }
 
 extern "C" int dxo_eval_operand(dxo_ctx* ctx, dxo_mesh* m, int kind, int bs, int mem, const double* u,
@@ -404,35 +328,19 @@ extern "C" int dxo_eval_operand(dxo_ctx* ctx, dxo_mesh* m, int kind, int bs, int
     double* dout = out;
     const size_t out_bytes = (size_t)n_cells * m->dev.nq * D * sizeof(double);
     if (mem == DXO_MEM_HOST) {
-        if (cells)
-            for (int64_t i = 0; i < n_cells; ++i)
-                if (cells[i] < 0 || cells[i] >= m->num_cells) return dxo_fail(ctx, DXO_E_SIZE, "dxo_eval_operand: entity outside [0, num_cells)");
-        const size_t ub = (size_t)m->num_field_nodes * bs * sizeof(double);
-        int rc = ensure(ctx, (void**)&m->d_u, &m->u_cap, ub);
-        if (rc != DXO_OK) return rc;
-        DXO_HIP(ctx, hipMemcpyAsync(m->d_u, u, ub, hipMemcpyHostToDevice, s));
-        du = m->d_u;
-        if (cells) {
-            rc = ensure(ctx, (void**)&m->d_cells, &m->cells_cap, (size_t)n_cells * sizeof(int32_t));
-            if (rc != DXO_OK) return rc;
-            DXO_HIP(ctx, hipMemcpyAsync(m->d_cells, cells, (size_t)n_cells * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            dc = m->d_cells;
-        }
-        rc = ensure(ctx, (void**)&m->d_out, &m->out_cap, out_bytes);
+        if (!cells_ok(m, cells, n_cells)) return dxo_fail(ctx, DXO_E_SIZE, "dxo_eval_operand: entity outside [0, num_cells)");
+        int rc = stage_in(ctx, &m->d_u, &m->u_cap, u, (size_t)m->num_field_nodes * bs, s, &du);
+        if (rc == DXO_OK && cells) rc = stage_in(ctx, &m->d_cells, &m->cells_cap, cells, (size_t)n_cells, s, &dc);
+        if (rc == DXO_OK) rc = device_buf(ctx, (void**)&m->d_out, &m->out_cap, out_bytes);
         if (rc != DXO_OK) return rc;
         dout = m->d_out;
     }
     int rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    if (bs != 1 && bs != m->gdim) rc = m->gdim == 2 ? dispatch_components<2>(ctx, m, kind, bs, du, dc, n_cells, dout, s) : dispatch_components<3>(ctx, m, kind, bs, du, dc, n_cells, dout, s);
-    else if (m->gdim == 2) rc = bs == 1 ? dispatch_kind<2, 1>(ctx, m, kind, du, dc, n_cells, dout, s) : dispatch_kind<2, 2>(ctx, m, kind, du, dc, n_cells, dout, s);
-    else              rc = bs == 1 ? dispatch_kind<3, 1>(ctx, m, kind, du, dc, n_cells, dout, s) : dispatch_kind<3, 3>(ctx, m, kind, du, dc, n_cells, dout, s);
+    if (bs != 1 && bs != m->gdim) with_gdim(m->gdim, [&](auto G) { rc = dispatch_components<G>(ctx, m, kind, bs, du, dc, n_cells, dout, s); });
+    else rc = with_form_shape(m->gdim, bs, [&](auto G, auto BS) { return dispatch_kind<G, BS>(ctx, m, kind, du, dc, n_cells, dout, s); });
     if (rc != DXO_OK) return dxo_fail(ctx, rc, "dxo_eval_operand: unsupported (gdim, bs, kind)");
     rc = dxo_device_end(ctx, s);
     if (rc != DXO_OK) return rc;
-    if (mem == DXO_MEM_HOST) {
-        DXO_HIP(ctx, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return DXO_OK;
+    return mem == DXO_MEM_HOST ? stage_out(ctx, out, dout, out_bytes, s) : DXO_OK;
 }

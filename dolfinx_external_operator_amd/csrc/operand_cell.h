@@ -19,7 +19,7 @@
 #pragma once
 
 #include "dxo_common.h"
-#include "operand_core.h"
+#include "form_host.h"
 
 namespace {
 
@@ -152,20 +152,11 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_cell_eps(OperandDev m, cons
     X_(2, 6, 3, 3)   /* P2 triangles, 3-point rule (the reference demos) */ \
     X_(2, 9, 4, 4)   /* Q2 quadrilaterals */
 
-inline int cell_grid(const dxo_ctx* ctx, int64_t n_cells) {
-    const int64_t n_groups = (n_cells + DXO_WAVE - 1) / DXO_WAVE;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;      // whole rounds over the 8 XCDs (xcd_group_walk)
-    return (int)blocks;
-}
-
 // true if a specialised kernel was launched
 inline bool launch_operand_cell_eps(const dxo_ctx* ctx, const dxo_mesh* mesh, const double* u, int64_t n_cells, double* out,
                                     hipStream_t s) {
     const OperandDev& v = mesh->dev;
-    const int grid = cell_grid(ctx, n_cells);
+    const int grid = wave_group_grid(ctx, (n_cells + DXO_WAVE - 1) / DXO_WAVE, 8);      // a wave group = 64 cells
 #define DXO_CASE(G_, ND_, NQ_, NG_)                                                                                      \
     if (mesh->gdim == G_ && v.ndofs == ND_ && v.nq == NQ_ && v.ngeom == NG_) {                                            \
         hipLaunchKernelGGL((operand_cell_eps<G_, ND_, NQ_, NG_>), dim3(grid), dim3(DXO_BLOCK), 0, s, v, u, n_cells, out); \

@@ -13,7 +13,7 @@
 // Boundary integrals touch O(N^((d-1)/d)) points — this is not a bandwidth kernel: one lane per (entity, point),
 // dofs gathered through the dofmap and tables read straight from global memory (they stay in L1 / L2).
 #include "dxo_common.h"
-#include "operand_core.h"
+#include "facet_tabs.h"
 
 namespace {
 
@@ -88,19 +88,12 @@ __global__ __launch_bounds__(DXO_BLOCK) void operand_eval_facets(OperandDev m, i
 template <int G, int BS, int KIND>
 void launch_facets(const dxo_ctx* ctx, const dxo_mesh* m, const double* u, const int32_t* ents, int64_t n, double* out, hipStream_t s,
                    int u_stride = 0, int out_stride = 0) {
-    const size_t nd = (size_t)m->dev.ndofs, nf = (size_t)m->n_local_facets, nqf = (size_t)m->nq_facet;
-    const double* phi_f = m->d_facet_tab;
-    const double* dphi_f = phi_f + nf * nqf * nd;
-    const double* dpsi_f = dphi_f + nf * nqf * nd * G;
-    int64_t blocks = (n * (int64_t)nqf + DXO_BLOCK - 1) / DXO_BLOCK;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
+    const FacetTabs<G> t = facet_tabs<G>(m);
     OperandDev dev = m->dev;
     dev.u_stride = u_stride;
     dev.out_stride = out_stride;
-    hipLaunchKernelGGL((operand_eval_facets<G, BS, KIND>), dim3((int)blocks), dim3(DXO_BLOCK), 0, s, dev, (int)nqf, phi_f, dphi_f,
-                       dpsi_f, u, ents, n, out);
+    hipLaunchKernelGGL((operand_eval_facets<G, BS, KIND>), dim3(capped_grid(ctx, n * t.nqf, DXO_BLOCK, 8)), dim3(DXO_BLOCK), 0, s, dev, t.nqf,
+                       t.phi, t.dphi, t.dpsi, u, ents, n, out);
 }
 
 // any block size for the per-component kinds, as dispatch_components of operand.hip: one scalar launch per component
@@ -120,40 +113,7 @@ int dispatch_facet_components(const dxo_ctx* ctx, const dxo_mesh* m, int kind, i
 template <int G, int BS>
 int dispatch_facets(const dxo_ctx* ctx, const dxo_mesh* m, int kind, const double* u, const int32_t* ents, int64_t n, double* out,
                     hipStream_t s) {
-    switch (kind) {
-        case DXO_OPERAND_VALUE: launch_facets<G, BS, DXO_OPERAND_VALUE>(ctx, m, u, ents, n, out, s); return DXO_OK;
-        case DXO_OPERAND_GRAD: launch_facets<G, BS, DXO_OPERAND_GRAD>(ctx, m, u, ents, n, out, s); return DXO_OK;
-        case DXO_OPERAND_VALUE_GRAD: launch_facets<G, BS, DXO_OPERAND_VALUE_GRAD>(ctx, m, u, ents, n, out, s); return DXO_OK;
-        case DXO_OPERAND_EPS_MANDEL:
-            if constexpr (BS == G) { launch_facets<G, BS, DXO_OPERAND_EPS_MANDEL>(ctx, m, u, ents, n, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DEFGRAD:
-            if constexpr (BS == G) { launch_facets<G, BS, DXO_OPERAND_DEFGRAD>(ctx, m, u, ents, n, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_CAUCHY_GREEN:
-            if constexpr (BS == G) { launch_facets<G, BS, DXO_OPERAND_CAUCHY_GREEN>(ctx, m, u, ents, n, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_I1:
-            if constexpr (BS == G) { launch_facets<G, BS, DXO_OPERAND_I1>(ctx, m, u, ents, n, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DETF:
-            if constexpr (BS == G) { launch_facets<G, BS, DXO_OPERAND_DETF>(ctx, m, u, ents, n, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-        case DXO_OPERAND_DIV:
-            if constexpr (BS == G) { launch_facets<G, BS, DXO_OPERAND_DIV>(ctx, m, u, ents, n, out, s); return DXO_OK; }
-            return DXO_E_DIM;
-    }
-    return DXO_E_OPTION;
-}
-
-int ensure_buf(dxo_ctx* ctx, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return DXO_OK;
-    if (*p) DXO_HIP(ctx, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    DXO_HIP(ctx, hipMalloc(p, bytes));
-    *cap = bytes;
-    return DXO_OK;
+    return with_operand_kind<G, BS, false>(kind, [&](auto KIND) { launch_facets<G, BS, KIND>(ctx, m, u, ents, n, out, s); });
 }
 
 }  // namespace
@@ -201,33 +161,20 @@ extern "C" int dxo_eval_operand_facets(dxo_ctx* ctx, dxo_mesh* m, int kind, int 
     double* dout = out;
     const size_t out_bytes = (size_t)n_entities * m->nq_facet * D * sizeof(double);
     if (mem == DXO_MEM_HOST) {
-        for (int64_t i = 0; i < n_entities; ++i)
-            if (entities[2 * i] < 0 || entities[2 * i] >= m->num_cells || entities[2 * i + 1] < 0 || entities[2 * i + 1] >= m->n_local_facets)
-                return dxo_fail(ctx, DXO_E_SIZE, "dxo_eval_operand_facets: entity outside [0, num_cells) x [0, n_local_facets)");
-        const size_t ub = (size_t)m->num_field_nodes * bs * sizeof(double);
-        int rc = ensure_buf(ctx, (void**)&m->d_u, &m->u_cap, ub);
-        if (rc != DXO_OK) return rc;
-        DXO_HIP(ctx, hipMemcpyAsync(m->d_u, u, ub, hipMemcpyHostToDevice, s));
-        du = m->d_u;
-        rc = ensure_buf(ctx, (void**)&m->d_ents, &m->ents_cap, (size_t)n_entities * 2 * sizeof(int32_t));
-        if (rc != DXO_OK) return rc;
-        DXO_HIP(ctx, hipMemcpyAsync(m->d_ents, entities, (size_t)n_entities * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        de = m->d_ents;
-        rc = ensure_buf(ctx, (void**)&m->d_out, &m->out_cap, out_bytes);
+        if (!facet_entities_ok(m, entities, n_entities))
+            return dxo_fail(ctx, DXO_E_SIZE, "dxo_eval_operand_facets: entity outside [0, num_cells) x [0, n_local_facets)");
+        int rc = stage_in(ctx, &m->d_u, &m->u_cap, u, (size_t)m->num_field_nodes * bs, s, &du);
+        if (rc == DXO_OK) rc = stage_in(ctx, &m->d_ents, &m->ents_cap, entities, (size_t)n_entities * 2, s, &de);
+        if (rc == DXO_OK) rc = device_buf(ctx, (void**)&m->d_out, &m->out_cap, out_bytes);
         if (rc != DXO_OK) return rc;
         dout = m->d_out;
     }
     int rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    if (bs != 1 && bs != m->gdim) rc = m->gdim == 2 ? dispatch_facet_components<2>(ctx, m, kind, bs, du, de, n_entities, dout, s) : dispatch_facet_components<3>(ctx, m, kind, bs, du, de, n_entities, dout, s);
-    else if (m->gdim == 2) rc = bs == 1 ? dispatch_facets<2, 1>(ctx, m, kind, du, de, n_entities, dout, s) : dispatch_facets<2, 2>(ctx, m, kind, du, de, n_entities, dout, s);
-    else              rc = bs == 1 ? dispatch_facets<3, 1>(ctx, m, kind, du, de, n_entities, dout, s) : dispatch_facets<3, 3>(ctx, m, kind, du, de, n_entities, dout, s);
+    if (bs != 1 && bs != m->gdim) with_gdim(m->gdim, [&](auto G) { rc = dispatch_facet_components<G>(ctx, m, kind, bs, du, de, n_entities, dout, s); });
+    else rc = with_form_shape(m->gdim, bs, [&](auto G, auto BS) { return dispatch_facets<G, BS>(ctx, m, kind, du, de, n_entities, dout, s); });
     if (rc != DXO_OK) return dxo_fail(ctx, rc, "dxo_eval_operand_facets: unsupported (gdim, bs, kind)");
     rc = dxo_device_end(ctx, s);
     if (rc != DXO_OK) return rc;
-    if (mem == DXO_MEM_HOST) {
-        DXO_HIP(ctx, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return DXO_OK;
+    return mem == DXO_MEM_HOST ? stage_out(ctx, out, dout, out_bytes, s) : DXO_OK;
 }
