@@ -113,6 +113,11 @@ class AmgLevelInfo(C.Structure):
                 ("p_values", _P), ("ap_blocks", C.c_int64), ("ap_ptr", _P), ("ap_col", _P)]
 
 
+class AmgTransfer(C.Structure):
+    """dxo_amg_transfer: the given first transfer of dxo_amg_create_transfer (host arrays)."""
+    _fields_ = [("n_coarse", C.c_int64), ("ptr", _P), ("col", _P), ("w", _P), ("coarse_to_fine", _P)]
+
+
 _SIGNATURES = {
     "dxo_abi_version": (C.c_int, []),
     "dxo_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -223,6 +228,9 @@ _SIGNATURES = {
     "dxo_amg_cycle_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "dxo_amg_set_precision": (C.c_int, [_P, _P, C.c_int]),
     "dxo_amg_precision_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "dxo_amg_create_transfer": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int, C.c_double, C.POINTER(AmgTransfer), C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(_P)]),
+    "dxo_amg_transfer_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P)]),
     "dxo_mesh_set_facet_geometry": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "dxo_facet_set_create": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "dxo_facet_set_destroy": (C.c_int, [_P, _P]),

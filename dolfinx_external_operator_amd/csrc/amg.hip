@@ -72,6 +72,17 @@
 // on entry (12 B per row, repaid by the 2 nu + 1 kernels of level 0 that then read 4 B of r per row instead of 8), and the last
 // post-sweep of level 0 writes z in double (its TO). The K-cycle stays double: the two settings exclude each other.
 //
+// A given first transfer (dxo_amg_create_transfer; quadratic elements). The prolongator of level 0 is a nodal interpolation the caller
+// hands over, P = W (x) I_bs without the constrained dofs, instead of a smoothed aggregation: level 1 is then the degree-1 space on the
+// same cells. Its blocks are diagonal, so they are kept as p_diag [p_blocks][bs] (filled on the host at creation from W and the two
+// constraint masks; frozen), the symbolic tables come from transfer_tables on the given rows of P, and the numeric phase of level 0
+// is the block inverses, rho and omega for its sweeps, then amg_build_ap_w / amg_build_c_w (the kernels of A P and P^T (A P) with a
+// column and a row scaling in place of the block products): no amg_build_p, no mask kernels. Level 1 is a finest level in all but
+// where its matrix comes from: its mask is the constraints of the nodes coarse_to_fine, nodes with every dof constrained join no
+// aggregate, its B is the rows of the zeroed B_0 at those nodes (amg_gather_b), and strength of connection starts there. The cycle
+// of level 0 restricts and prolongs with amg_restrict_w / amg_prolong_w, one thread per dof (8 or 4 bytes of P per dof and block where
+// the block form reads bs^2 values; consecutive lanes read consecutive entries of the vectors).
+//
 // Host side. Run-time shapes reach the templates through one dispatcher (with_int and with_bs of krylov_internal.h, with_pairs here,
 // and their named lists: with_level, with_pair, with_square, with_nns_pair), so a kernel's argument list is written once. amg_build allocates the device scalars
 // of every level once, before the level loop, and walks read pattern -> [strength mask] -> aggregates -> transfer tables -> coarse
@@ -140,6 +151,11 @@ struct amg_level {
     // single precision (dxo_amg_set_precision): the copies a setup casts (absent on the coarsest level) and the cycle's vectors
     float *values32 = nullptr, *dinv32 = nullptr, *p_val32 = nullptr;
     float *r32 = nullptr, *xa32 = nullptr, *xb32 = nullptr, *t32 = nullptr, *d32 = nullptr;
+    // a given nodal transfer (dxo_amg_create_transfer; level 0 only): P = W (x) I_bs without the constrained dofs, kept as the
+    // diagonals of its blocks. p_val, agg and the near-null-space and strength arrays of the level are absent then
+    double* p_diag = nullptr;          // [p_blocks][bs], frozen at creation
+    float* p_diag32 = nullptr;
+    int32_t* ctf = nullptr;            // [n_agg] the node of this level a node of the next one is
 };
 
 // what the cycle reads and writes on a level, in the scalar T of the cycle
@@ -148,17 +164,18 @@ struct level_view;
 
 template <>
 struct level_view<double> {
-    const double *values, *dinv, *p_val;
+    const double *values, *dinv, *p_val, *p_diag;
     double *r, *xa, *xb, *t, *d;
-    explicit level_view(const amg_level& v) : values(v.values), dinv(v.dinv), p_val(v.p_val), r(v.r), xa(v.xa), xb(v.xb), t(v.t), d(v.d) {}
+    explicit level_view(const amg_level& v)
+        : values(v.values), dinv(v.dinv), p_val(v.p_val), p_diag(v.p_diag), r(v.r), xa(v.xa), xb(v.xb), t(v.t), d(v.d) {}
 };
 
 template <>
 struct level_view<float> {
-    const float *values, *dinv, *p_val;
+    const float *values, *dinv, *p_val, *p_diag;
     float *r, *xa, *xb, *t, *d;
     explicit level_view(const amg_level& v)
-        : values(v.values32), dinv(v.dinv32), p_val(v.p_val32), r(v.r32), xa(v.xa32), xb(v.xb32), t(v.t32), d(v.d32) {}
+        : values(v.values32), dinv(v.dinv32), p_val(v.p_val32), p_diag(v.p_diag32), r(v.r32), xa(v.xa32), xb(v.xb32), t(v.t32), d(v.d32) {}
 };
 
 }  // namespace
@@ -566,6 +583,94 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_c(int64_t c_blocks, c
             if (a == b && r == c && v == 0.0) v = 1.0;
             c_val[R.r0 + r * R.len + k * BSC + c] = v;
         }
+}
+
+// ---- a given nodal transfer (dxo_amg_create_transfer): every block of P is diagonal, p_diag[block][BS], so the two products of the
+// Galerkin matrix scale the columns and then the rows of the blocks of A. The patterns, the order of the sums and the search for the
+// source blocks are those of amg_build_ap / amg_build_c.
+// (A P)(i, a) = sum over the neighbours j of i, ascending, of A_ij diag(p_ja)
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_ap_w(int64_t ap_blocks, const int32_t* __restrict__ ap_row, const int32_t* __restrict__ ap_col,
+                                                                const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                                const double* __restrict__ values, const int64_t* __restrict__ p_ptr,
+                                                                const int32_t* __restrict__ p_col, const double* __restrict__ p_diag,
+                                                                double* __restrict__ ap_val) {
+    const int64_t e = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (e >= ap_blocks) return;
+    const int64_t i = ap_row[e];
+    const int32_t a = ap_col[e];
+    const NodeRow<BS> R(row_ptr, i);
+    double acc[BS][BS];
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) acc[r][c] = 0.0;
+    for (int k = 0; k < R.nnb; ++k) {
+        const int64_t j = col[R.r0 + (int64_t)k * BS] / BS;
+        const int64_t f = amg_find(p_col, p_ptr[j], p_ptr[j + 1], a);
+        if (f < 0) continue;
+        double pd[BS];
+#pragma unroll
+        for (int c = 0; c < BS; ++c) pd[c] = p_diag[f * BS + c];
+#pragma unroll
+        for (int r = 0; r < BS; ++r)
+#pragma unroll
+            for (int c = 0; c < BS; ++c) acc[r][c] = fma(values[R.r0 + r * R.len + (int64_t)k * BS + c], pd[c], acc[r][c]);
+    }
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) ap_val[e * BS * BS + r * BS + c] = acc[r][c];
+}
+
+// A_c(a, b) = sum over the blocks (i, a) of P, ascending i, of diag(p_ia) (A P)_ib; an exactly zero diagonal entry becomes 1
+template <int BS>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_build_c_w(int64_t c_blocks, const int32_t* __restrict__ c_row, const int64_t* __restrict__ c_bptr,
+                                                               const int64_t* __restrict__ c_row_ptr, const int32_t* __restrict__ c_col,
+                                                               const int64_t* __restrict__ pt_ptr, const int64_t* __restrict__ pt_blk,
+                                                               const int32_t* __restrict__ p_row, const double* __restrict__ p_diag,
+                                                               const int64_t* __restrict__ ap_ptr, const int32_t* __restrict__ ap_col,
+                                                               const double* __restrict__ ap_val, double* __restrict__ c_val) {
+    const int64_t g = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (g >= c_blocks) return;
+    const int64_t a = c_row[g];
+    const int64_t k = g - c_bptr[a];
+    const NodeRow<BS> R(c_row_ptr, a);
+    const int32_t b = c_col[R.r0 + k * BS] / BS;
+    double acc[BS][BS];
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) acc[r][c] = 0.0;
+    for (int64_t e = pt_ptr[a]; e < pt_ptr[a + 1]; ++e) {
+        const int64_t pb = pt_blk[e];
+        const int64_t i = p_row[pb];
+        const int64_t f = amg_find(ap_col, ap_ptr[i], ap_ptr[i + 1], b);
+        if (f < 0) continue;
+#pragma unroll
+        for (int r = 0; r < BS; ++r) {
+            const double p = p_diag[pb * BS + r];
+#pragma unroll
+            for (int c = 0; c < BS; ++c) acc[r][c] = fma(p, ap_val[f * BS * BS + r * BS + c], acc[r][c]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+        for (int c = 0; c < BS; ++c) {
+            double v = acc[r][c];
+            if (a == b && r == c && v == 0.0) v = 1.0;
+            c_val[R.r0 + r * R.len + k * BS + c] = v;
+        }
+}
+
+// B of the level below a given transfer: the rows of the (already zeroed) B of this level at the nodes the coarse nodes are
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_gather_b(int64_t n_rows_c, int bs, int k, const int32_t* __restrict__ ctf,
+                                                              const double* __restrict__ B, double* __restrict__ Bc) {
+    const int64_t row = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (row >= n_rows_c) return;
+    const int64_t src = (int64_t)ctf[row / bs] * bs + row % bs;
+    for (int c = 0; c < k; ++c) Bc[row * k + c] = B[src * k + c];
 }
 
 // ---- strength of connection
@@ -1035,6 +1140,38 @@ __global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_prolong(int64_t n_nodes, co
     for (int r = 0; r < BSR; ++r) x[i * BSR + r] += acc[r];
 }
 
+// The transfers of a given nodal transfer, one thread per dof: consecutive lanes read consecutive entries of p_diag, t and x, where
+// a thread per node would stride them by BS.
+// r_c[a][c] = sum over the blocks (i, a) of P, ascending i, of p_diag[block][c] t_i[c]
+template <int BS, class T>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_restrict_w(int64_t n_rows_c, const int64_t* __restrict__ pt_ptr, const int64_t* __restrict__ pt_blk,
+                                                                const int32_t* __restrict__ p_row, const T* __restrict__ p_diag,
+                                                                const T* __restrict__ t, T* __restrict__ rc) {
+    const int64_t g = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (g >= n_rows_c) return;
+    const int64_t a = g / BS;
+    const int c = (int)(g % BS);
+    T acc = 0.0;
+    for (int64_t e = pt_ptr[a]; e < pt_ptr[a + 1]; ++e) {
+        const int64_t pb = pt_blk[e];
+        acc = fma(p_diag[pb * BS + c], t[(int64_t)p_row[pb] * BS + c], acc);
+    }
+    rc[g] = acc;
+}
+
+// x_i[r] += sum over the blocks of row i of P, ascending coarse node, of p_diag[block][r] xc_a[r]
+template <int BS, class T>
+__global__ __launch_bounds__(DXO_AMG_BLOCK) void amg_prolong_w(int64_t n_rows, const int64_t* __restrict__ p_ptr, const int32_t* __restrict__ p_col,
+                                                               const T* __restrict__ p_diag, const T* __restrict__ xc, T* __restrict__ x) {
+    const int64_t g = (int64_t)blockIdx.x * DXO_AMG_BLOCK + threadIdx.x;
+    if (g >= n_rows) return;
+    const int64_t i = g / BS;
+    const int r = (int)(g % BS);
+    T acc = 0.0;
+    for (int64_t e = p_ptr[i]; e < p_ptr[i + 1]; ++e) acc = fma(p_diag[e * BS + r], xc[(int64_t)p_col[e] * BS + r], acc);
+    x[g] += acc;
+}
+
 // ---- the K-cycle
 constexpr int AMG_K_MAX_PARTS = 1024;
 enum { KCO_RHO1 = 0, KCO_A1 = 1, KCO_ALPHA1 = 2, KCO_X1 = 3, KCO_X2 = 4, KCO_COUNT = 8 };
@@ -1259,21 +1396,10 @@ void sort_unique(std::vector<int32_t>& v) {
     v.erase(std::unique(v.begin(), v.end()), v.end());
 }
 
-// gp: the graph P is smoothed with (the strong graph; g itself without strength of connection)
-HostTransfer transfer_of(const HostGraph& gp, const HostGraph& g, const std::vector<int32_t>& agg, int64_t na) {
-    HostTransfer t;
+// the tables that follow from the rows of P (p_ptr, p_col, p_row of t, na columns) and the graph g of the matrix
+void transfer_tables(HostTransfer& t, const HostGraph& g, int64_t na) {
     const int64_t n = g.n;
     std::vector<int32_t> tmp;
-    t.p_ptr.assign((size_t)n + 1, 0);
-    for (int64_t i = 0; i < n; ++i) {                    // P: the aggregates of the neighbours
-        tmp.clear();
-        for (int64_t e = gp.ptr[(size_t)i]; e < gp.ptr[(size_t)i + 1]; ++e)
-            if (agg[(size_t)gp.nb[(size_t)e]] >= 0) tmp.push_back(agg[(size_t)gp.nb[(size_t)e]]);
-        sort_unique(tmp);
-        t.p_col.insert(t.p_col.end(), tmp.begin(), tmp.end());
-        t.p_row.insert(t.p_row.end(), tmp.size(), (int32_t)i);
-        t.p_ptr[(size_t)i + 1] = (int64_t)t.p_col.size();
-    }
     t.pt_ptr.assign((size_t)na + 1, 0);                  // its transposed incidence, ascending block = ascending fine node
     for (int32_t a : t.p_col) ++t.pt_ptr[(size_t)a + 1];
     for (int64_t a = 0; a < na; ++a) t.pt_ptr[(size_t)a + 1] += t.pt_ptr[(size_t)a];
@@ -1309,6 +1435,36 @@ HostTransfer transfer_of(const HostGraph& gp, const HostGraph& g, const std::vec
         t.coarse.ptr[(size_t)a + 1] = (int64_t)t.coarse.nb.size();
     }
     t.c_bptr = t.coarse.ptr;
+}
+
+// gp: the graph P is smoothed with (the strong graph; g itself without strength of connection)
+HostTransfer transfer_of(const HostGraph& gp, const HostGraph& g, const std::vector<int32_t>& agg, int64_t na) {
+    HostTransfer t;
+    const int64_t n = g.n;
+    std::vector<int32_t> tmp;
+    t.p_ptr.assign((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {                    // P: the aggregates of the neighbours
+        tmp.clear();
+        for (int64_t e = gp.ptr[(size_t)i]; e < gp.ptr[(size_t)i + 1]; ++e)
+            if (agg[(size_t)gp.nb[(size_t)e]] >= 0) tmp.push_back(agg[(size_t)gp.nb[(size_t)e]]);
+        sort_unique(tmp);
+        t.p_col.insert(t.p_col.end(), tmp.begin(), tmp.end());
+        t.p_row.insert(t.p_row.end(), tmp.size(), (int32_t)i);
+        t.p_ptr[(size_t)i + 1] = (int64_t)t.p_col.size();
+    }
+    transfer_tables(t, g, na);
+    return t;
+}
+
+// the rows of P as the caller gave them (dxo_amg_create_transfer; validated there)
+HostTransfer transfer_given(const HostGraph& g, const dxo_amg_transfer& w) {
+    HostTransfer t;
+    t.p_ptr.assign(w.ptr, w.ptr + g.n + 1);
+    t.p_col.assign(w.col, w.col + w.ptr[g.n]);
+    t.p_row.resize(t.p_col.size());
+    for (int64_t i = 0; i < g.n; ++i)
+        for (int64_t e = w.ptr[i]; e < w.ptr[i + 1]; ++e) t.p_row[(size_t)e] = (int32_t)i;
+    transfer_tables(t, g, w.n_coarse);
     return t;
 }
 
@@ -1412,7 +1568,7 @@ int amg_nns_dead(dxo_ctx* ctx, dxo_amg* amg, hipStream_t s) {
     for (int l = 0; l + 1 < nl; ++l) {
         amg_level& v = amg->L[(size_t)l];
         std::vector<uint8_t> d((size_t)v.n_agg);
-        if (v.n_agg > 0) DXO_HIP(ctx, hipMemcpy(d.data(), v.dead_a, d.size(), hipMemcpyDeviceToHost));
+        if (v.n_agg > 0 && v.dead_a) DXO_HIP(ctx, hipMemcpy(d.data(), v.dead_a, d.size(), hipMemcpyDeviceToHost));      // none: a given transfer
         v.dead = 0;
         for (uint8_t x : d) v.dead += x;
     }
@@ -1454,6 +1610,16 @@ void amg_estimate_rho(dxo_amg* amg, const amg_level& v, bool filtered, double* r
 void amg_setup_level(dxo_amg* amg, int l, const amg_level& v, const amg_level& c, hipStream_t s) {
     const bool nns = amg->k > 0;
     (void)dxo_kr_bj_setup_launch(v.A, v.values, v.dinv, amg->flag, s);      // a level has block size 1, 2, 3 or 6 (with_bs)
+    if (v.p_diag) {      // a given transfer: P is frozen, and the mask of the next level with it; the level keeps what it smooths with
+        amg_estimate_rho(amg, v, false, amg->rho + l, amg->omega + l, amg->cheb + (size_t)l * AMG_CHEB_STRIDE, s);
+        with_square(v.bs, v.bsc, [&](auto BS, auto) {
+            amg_launch(amg_build_ap_w<BS>, v.ap_blocks, DXO_AMG_BLOCK, s, v.ap_blocks, v.ap_row, v.ap_col, v.A->d_row_ptr, v.A->d_col, v.values, v.p_ptr,
+                       v.p_col, v.p_diag, v.ap_val);
+            amg_launch(amg_build_c_w<BS>, v.c_blocks, DXO_AMG_BLOCK, s, v.c_blocks, v.c_row, v.c_bptr, c.A->d_row_ptr, c.A->d_col, v.pt_ptr, v.pt_blk,
+                       v.p_row, v.p_diag, v.ap_ptr, v.ap_col, v.ap_val, const_cast<double*>(c.values));
+        });
+        return;
+    }
     const double* omega_p = amg->omega + l;
     if (v.strong) {
         with_bs(v.bs, [&](auto BS) {
@@ -1500,6 +1666,7 @@ struct amg_options {
     const double* B = nullptr;         // keeps the block size). B: the near-null space [n_rows][k] on the device
     double theta = 0.0;                // strength of connection: > 0 with `values`, the matrix; every level is then followed by its numeric
     const double* values = nullptr;    // phase, whose coarse matrix gives the mask of the next level
+    const dxo_amg_transfer* first = nullptr;      // the given transfer of level 0 (host arrays, validated); strength then starts on level 1
 };
 
 // the pattern and the constraints on the host: the node graph, the constrained dofs, the nodes with a free dof
@@ -1547,12 +1714,12 @@ int amg_strength_mask(dxo_ctx* ctx, Uploader& U, const amg_level& v, const HostG
 }
 
 // the tables and the value arrays of the transfer from a level to the next, on the device
-void amg_upload_transfer(Uploader& U, amg_level& v, const HostTransfer& t, const std::vector<int32_t>& agg, int64_t na) {
+void amg_upload_transfer(Uploader& U, amg_level& v, const HostTransfer& t, const std::vector<int32_t>& agg, int64_t na, bool given) {
     v.n_agg = na;
     v.p_blocks = (int64_t)t.p_col.size();
     v.ap_blocks = (int64_t)t.ap_col.size();
     v.c_blocks = (int64_t)t.c_row.size();
-    v.agg = U.up(agg);
+    if (!given) v.agg = U.up(agg);
     v.p_ptr = U.up(t.p_ptr);
     v.p_col = U.up(t.p_col);
     v.p_row = U.up(t.p_row);
@@ -1563,12 +1730,13 @@ void amg_upload_transfer(Uploader& U, amg_level& v, const HostTransfer& t, const
     v.ap_row = U.up(t.ap_row);
     v.c_bptr = U.up(t.c_bptr);
     v.c_row = U.up(t.c_row);
-    v.p_val = U.alloc<double>((size_t)(v.p_blocks * v.bs * v.bsc));
+    if (!given) v.p_val = U.alloc<double>((size_t)(v.p_blocks * v.bs * v.bsc));      // given: p_diag, filled by the caller
     v.ap_val = U.alloc<double>((size_t)(v.ap_blocks * v.bs * v.bsc));
 }
 
-// the coarse level of a node graph: a dxo_csr without a mesh, its values and its B (k > 0) or mask
-amg_level amg_coarse_level(Uploader& U, const HostGraph& coarse, int bsc, int k) {
+// the coarse level of a node graph: a dxo_csr without a mesh, its values and its B (k > 0) or mask. `fixed`: the level below a given
+// transfer, whose mask is the constraints of its nodes, known now (kept beside B too: it is a finest level in all but its matrix)
+amg_level amg_coarse_level(Uploader& U, const HostGraph& coarse, int bsc, int k, const std::vector<uint8_t>* fixed = nullptr) {
     std::vector<int64_t> crp;
     std::vector<int32_t> ccol;
     rows_of(coarse, bsc, crp, ccol);
@@ -1587,7 +1755,8 @@ amg_level amg_coarse_level(Uploader& U, const HostGraph& coarse, int bsc, int k)
     c.bs = c.bsc = bsc;
     c.values = U.alloc<double>((size_t)c.own->nnz);
     if (k > 0) c.b_val = U.alloc<double>((size_t)(c.n_rows * k));      // T is fixed at creation: no values-dependent mask
-    else c.mask = U.alloc<uint8_t>((size_t)c.n_rows);
+    if (fixed) c.mask = U.up(*fixed);
+    else if (k == 0) c.mask = U.alloc<uint8_t>((size_t)c.n_rows);
     return c;
 }
 
@@ -1640,9 +1809,13 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
         HostGraph gs;
         uint8_t* d_strong = nullptr;
         int64_t n_strong = 0;
-        if (!last && soc && (rc = amg_strength_mask(ctx, U, lev, g, opt.theta, s, d_strong, n_strong, gs)) != DXO_OK) return rc;
+        const bool given = opt.first && amg->L.empty();      // level 0 of dxo_amg_create_transfer: no mask, no aggregates
+        if (!last && !given && soc && (rc = amg_strength_mask(ctx, U, lev, g, opt.theta, s, d_strong, n_strong, gs)) != DXO_OK) return rc;
         const HostGraph& gp = d_strong ? gs : g;      // the graph of the aggregates and of the pattern of P
-        if (!last) {
+        if (!last && given) {
+            na = opt.first->n_coarse;                  // below the 0.8 of the stagnation rule: checked with the arrays
+            lev.bsc = lev.bs;
+        } else if (!last) {
             na = aggregate(gp, active, agg);
             last = na == 0 || (double)(na * bsc) > 0.8 * (double)lev.n_rows;
         }
@@ -1654,7 +1827,7 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
         lev.t = U.alloc<double>((size_t)lev.n_rows);
         lev.d = U.alloc<double>((size_t)lev.n_rows);
         lev.dinv = U.alloc<double>((size_t)(lev.n_nodes * lev.bs * lev.bs));
-        HostTransfer t = transfer_of(gp, g, agg, na);
+        HostTransfer t = given ? transfer_given(g, *opt.first) : transfer_of(gp, g, agg, na);
         if (d_strong) {
             lev.strong = d_strong;
             lev.n_strong = n_strong;
@@ -1662,8 +1835,23 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
             lev.dinv_f = U.alloc<double>((size_t)(lev.n_nodes * lev.bs * lev.bs));
             lev.unlumped = U.alloc<uint8_t>((size_t)lev.n_nodes);
         }
-        amg_upload_transfer(U, lev, t, agg, na);
-        if (k > 0) {
+        amg_upload_transfer(U, lev, t, agg, na, given);
+        std::vector<uint8_t> mask_c;                   // given: the constraints of the coarse nodes, those of the nodes they are
+        if (given) {
+            const dxo_amg_transfer& w = *opt.first;
+            const int bs = lev.bs;
+            mask_c.resize((size_t)(na * bs));
+            for (int64_t v = 0; v < na; ++v)
+                for (int c = 0; c < bs; ++c) mask_c[(size_t)(v * bs + c)] = mask[(size_t)((int64_t)w.coarse_to_fine[v] * bs + c)];
+            std::vector<double> pd((size_t)(lev.p_blocks * bs));
+            for (int64_t i = 0; i < lev.n_nodes; ++i)
+                for (int64_t e = w.ptr[i]; e < w.ptr[i + 1]; ++e)
+                    for (int c = 0; c < bs; ++c)
+                        pd[(size_t)(e * bs + c)] = w.w[e] * (mask[(size_t)(i * bs + c)] ? 0.0 : 1.0) * (mask_c[(size_t)((int64_t)w.col[e] * bs + c)] ? 0.0 : 1.0);
+            lev.p_diag = U.up(pd);
+            lev.ctf = U.up(std::vector<int32_t>(w.coarse_to_fine, w.coarse_to_fine + na));
+        }
+        if (k > 0 && !given) {
             std::vector<int64_t> aptr;
             std::vector<int32_t> anode;
             nodes_of_aggregates(agg, na, aptr, anode);
@@ -1674,17 +1862,26 @@ int amg_build(dxo_ctx* ctx, const char* who, dxo_amg* amg, const dxo_csr* csr, c
             lev.dead_a = U.alloc<uint8_t>((size_t)na);
         }
         amg->L.push_back(lev);
-        const amg_level c = amg_coarse_level(U, t.coarse, bsc, k);
+        amg_level c = given ? amg_coarse_level(U, t.coarse, lev.bs, k, &mask_c) : amg_coarse_level(U, t.coarse, bsc, k);
+        if (given) c.bsc = bsc;        // the first level of the aggregation
         rc = U.rc;
-        if (rc == DXO_OK && k > 0) rc = amg_nns_level(ctx, amg, lev, c.b_val, s);
+        if (rc == DXO_OK && k > 0 && !given) rc = amg_nns_level(ctx, amg, lev, c.b_val, s);
+        if (rc == DXO_OK && k > 0 && given && c.n_rows > 0)      // degree-1 functions reproduce the rigid-body modes: B_1 is B_0 at the coarse nodes
+            hipLaunchKernelGGL(amg_gather_b, amg_grid(c.n_rows), dim3(DXO_AMG_BLOCK), 0, s, c.n_rows, lev.bs, k, lev.ctf, lev.b_val, c.b_val);
         if (rc != DXO_OK) {
             amg->L.push_back(c);       // owned: freed with the object
             return rc;
         }
-        if (lev.strong && lev.n_nodes > 0) amg_setup_level(amg, (int)amg->L.size() - 1, lev, c, s);
+        if ((lev.strong || (given && soc)) && lev.n_nodes > 0) amg_setup_level(amg, (int)amg->L.size() - 1, lev, c, s);
         lev = c;
         g = std::move(t.coarse);
         active.assign((size_t)g.n, 1);
+        if (given)                     // as on a finest level: a node all of whose dofs are constrained joins no aggregate
+            for (int64_t v = 0; v < g.n; ++v) {
+                bool all = true;
+                for (int r = 0; r < lev.bs; ++r) all = all && mask_c[(size_t)(v * lev.bs + r)];
+                active[(size_t)v] = all ? 0 : 1;
+            }
     }
     if (U.rc != DXO_OK) return U.rc;
     amg->complexity = (double)total / (double)nnzb0;
@@ -1767,13 +1964,24 @@ const T* amg_body(const CycleRun& C, int l, const T* rin, double* out) {
     }
     sweep<true>(v, om, rin, (const T*)cur, w.t, s);
     const level_view<T> wc(amg->L[(size_t)l + 1]);
-    with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
-        amg_launch(amg_restrict<BSR, BSC, T>, v.n_agg, DXO_AMG_BLOCK, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, w.p_val, (const T*)w.t, wc.r);
-    });
+    const int64_t nrc = v.n_agg * v.bsc;
+    if (v.p_diag)
+        with_square(v.bs, v.bsc, [&](auto BS, auto) {
+            amg_launch(amg_restrict_w<BS, T>, nrc, DXO_AMG_BLOCK, s, nrc, v.pt_ptr, v.pt_blk, v.p_row, w.p_diag, (const T*)w.t, wc.r);
+        });
+    else
+        with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
+            amg_launch(amg_restrict<BSR, BSC, T>, v.n_agg, DXO_AMG_BLOCK, s, v.n_agg, v.pt_ptr, v.pt_blk, v.p_row, w.p_val, (const T*)w.t, wc.r);
+        });
     const T* xc = amg_solve_level<T>(C, l + 1, wc.r);
-    with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
-        amg_launch(amg_prolong<BSR, BSC, T>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.p_ptr, v.p_col, w.p_val, xc, cur);
-    });
+    if (v.p_diag)
+        with_square(v.bs, v.bsc, [&](auto BS, auto) {
+            amg_launch(amg_prolong_w<BS, T>, v.n_rows, DXO_AMG_BLOCK, s, v.n_rows, v.p_ptr, v.p_col, w.p_diag, xc, cur);
+        });
+    else
+        with_pair(v.bs, v.bsc, [&](auto BSR, auto BSC) {
+            amg_launch(amg_prolong<BSR, BSC, T>, v.n_nodes, DXO_AMG_BLOCK, s, v.n_nodes, v.p_ptr, v.p_col, w.p_val, xc, cur);
+        });
     for (int k = 0; k < C.nu; ++k) {
         if (out && k == C.nu - 1) {      // the last sweep writes the result where the caller wants it
             if (C.cheby) cheby_step(v, ch + 2 * k, rin, (const T*)cur, out, s);
@@ -1915,6 +2123,69 @@ extern "C" int dxo_amg_create_soc(dxo_ctx* ctx, const dxo_csr* csr, const double
     opt.k = n_modes, opt.B = n_modes ? B : nullptr;
     if (theta > 0.0) opt.theta = theta, opt.values = values;      // theta == 0: dxo_amg_create_nns / dxo_amg_create
     return amg_create(ctx, "dxo_amg_create_soc", csr, constrained, n_constrained, opt, out);
+}
+
+extern "C" int dxo_amg_create_transfer(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const int32_t* constrained, int64_t n_constrained,
+                                       const double* B, int n_modes, double theta, const dxo_amg_transfer* first, int max_levels, int coarse_rows,
+                                       int sweeps, dxo_amg** out) {
+    if (!first) return dxo_amg_create_soc(ctx, csr, values, constrained, n_constrained, B, n_modes, theta, max_levels, coarse_rows, sweeps, out);
+    if (!ctx || !out) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    *out = nullptr;
+    const char* who = "dxo_amg_create_transfer";
+    auto fail = [&](int code, const char* what) { return dxo_fail(ctx, code, (std::string(who) + ": " + what).c_str()); };
+    if (!csr || !values || (n_constrained > 0 && !constrained) || (n_modes != 0 && !B) || !first->ptr || !first->col || !first->w || !first->coarse_to_fine)
+        return fail(DXO_E_NULL, "NULL argument");
+    if (!(theta >= 0.0 && theta < 1.0)) return fail(DXO_E_OPTION, "theta must lie in [0, 1)");
+    if (csr->bs < 1 || csr->bs > 3) return fail(DXO_E_DIM, "bs must be 1, 2 or 3");
+    if (n_modes != 0 && !((csr->bs == 2 && n_modes == 3) || (csr->bs == 3 && n_modes == 6)))
+        return fail(DXO_E_DIM, "(bs, n_modes) must be (2, 3) or (3, 6), or n_modes 0");
+    if (amg_misaligned(values) || (n_modes != 0 && amg_misaligned(B))) return fail(DXO_E_ALIGN, "values and B must be 8-byte aligned");
+    // the given transfer, host arrays
+    const int64_t n = csr->n_nodes, nc = first->n_coarse;
+    if (nc < 1 || (double)(nc * csr->bs) > 0.8 * (double)csr->n_rows)
+        return fail(DXO_E_SIZE, "n_coarse must be at least 1 and at most 0.8 of the nodes (the stagnation rule)");
+    if (first->ptr[0] != 0) return fail(DXO_E_SIZE, "ptr[0] must be 0");
+    for (int64_t i = 0; i < n; ++i) {
+        if (first->ptr[i + 1] <= first->ptr[i]) return fail(DXO_E_SIZE, "every node needs at least one entry (ptr must increase)");
+        for (int64_t e = first->ptr[i]; e < first->ptr[i + 1]; ++e) {
+            if (first->col[e] < 0 || first->col[e] >= nc) return fail(DXO_E_SIZE, "a column lies outside [0, n_coarse)");
+            if (e > first->ptr[i] && first->col[e] <= first->col[e - 1]) return fail(DXO_E_OPTION, "the columns of a row must ascend");
+            if (!std::isfinite(first->w[e])) return fail(DXO_E_OPTION, "a weight is not finite");
+        }
+    }
+    {
+        std::vector<uint8_t> seen((size_t)n, 0);
+        for (int64_t v = 0; v < nc; ++v) {
+            const int64_t i = first->coarse_to_fine[v];
+            if (i < 0 || i >= n) return fail(DXO_E_SIZE, "coarse_to_fine lies outside [0, n_nodes)");
+            if (seen[(size_t)i]) return fail(DXO_E_OPTION, "coarse_to_fine names a node twice");
+            seen[(size_t)i] = 1;
+            const int64_t e = first->ptr[i];
+            if (first->ptr[i + 1] != e + 1 || first->col[e] != v || first->w[e] != 1.0)
+                return fail(DXO_E_OPTION, "the row of coarse_to_fine[v] must be the single entry (v, 1)");
+        }
+    }
+    amg_options opt;
+    opt.max_levels = max_levels, opt.coarse_rows = coarse_rows, opt.sweeps = sweeps;
+    opt.k = n_modes, opt.B = n_modes ? B : nullptr;
+    opt.first = first;
+    if (theta > 0.0) opt.theta = theta, opt.values = values;
+    return amg_create(ctx, who, csr, constrained, n_constrained, opt, out);
+}
+
+extern "C" int dxo_amg_transfer_info(dxo_ctx* ctx, const dxo_amg* amg, int* present, int64_t* n_coarse, int64_t* p_blocks, const double** p_diag,
+                                     const int32_t** coarse_to_fine) {
+    if (!amg) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    const amg_level& v = amg->L[0];
+    const bool on = v.p_diag != nullptr;
+    if (present) *present = on ? 1 : 0;
+    if (n_coarse) *n_coarse = on ? v.n_agg : 0;
+    if (p_blocks) *p_blocks = on ? v.p_blocks : 0;
+    if (p_diag) *p_diag = v.p_diag;
+    if (coarse_to_fine) *coarse_to_fine = v.ctf;
+    return DXO_OK;
 }
 
 extern "C" int dxo_amg_soc_info(dxo_ctx* ctx, const dxo_amg* amg, int level, double* theta, const uint8_t** strong, int64_t* n_strong_blocks,
@@ -2065,7 +2336,8 @@ extern "C" int dxo_amg_set_precision(dxo_ctx* ctx, dxo_amg* amg, int kind) {
         for (size_t l = 0; l < nl; ++l) {
             amg_level& v = amg->L[l];
             const bool last = l + 1 == nl;
-            const int64_t nv = last ? 0 : v.A->nnz, nd = last ? 0 : v.n_nodes * v.bs * v.bs, np = last ? 0 : v.p_blocks * v.bs * v.bsc;
+            const int64_t nv = last ? 0 : v.A->nnz, nd = last ? 0 : v.n_nodes * v.bs * v.bs;
+            const int64_t np = last ? 0 : v.p_blocks * v.bs * (v.p_diag ? 1 : v.bsc);      // a given transfer: the diagonals of its blocks
             v.r32 = U.alloc<float>((size_t)v.n_rows);
             v.xa32 = U.alloc<float>((size_t)v.n_rows);
             entries += 2 * v.n_rows;
@@ -2075,7 +2347,7 @@ extern "C" int dxo_amg_set_precision(dxo_ctx* ctx, dxo_amg* amg, int kind) {
             v.d32 = U.alloc<float>((size_t)v.n_rows);
             v.values32 = U.alloc<float>((size_t)nv);
             v.dinv32 = U.alloc<float>((size_t)nd);
-            v.p_val32 = U.alloc<float>((size_t)np);
+            (v.p_diag ? v.p_diag32 : v.p_val32) = U.alloc<float>((size_t)np);
             entries += 3 * v.n_rows + nv + nd + np;
         }
         if (U.rc != DXO_OK) return U.rc;      // what was allocated goes with the object; the precision is unchanged
@@ -2133,9 +2405,9 @@ extern "C" int dxo_amg_setup(dxo_ctx* ctx, dxo_amg* amg, const double* values) {
     if (amg->precision == DXO_AMG_PRECISION_FP32)      // all of the above is double; the cycle's copies, before the one wait
         for (int l = 0; l + 1 < nl; ++l) {
             const amg_level& v = amg->L[(size_t)l];
-            const int64_t len[3] = {v.A->nnz, v.n_nodes * v.bs * v.bs, v.p_blocks * v.bs * v.bsc};
-            const double* from[3] = {v.values, v.dinv, v.p_val};
-            float* to[3] = {v.values32, v.dinv32, v.p_val32};
+            const int64_t len[3] = {v.A->nnz, v.n_nodes * v.bs * v.bs, v.p_blocks * v.bs * (v.p_diag ? 1 : v.bsc)};
+            const double* from[3] = {v.values, v.dinv, v.p_diag ? v.p_diag : v.p_val};
+            float* to[3] = {v.values32, v.dinv32, v.p_diag ? v.p_diag32 : v.p_val32};
             for (int q = 0; q < 3; ++q)
                 if (len[q] > 0) hipLaunchKernelGGL(amg_narrow, narrow_grid(len[q]), B, 0, s, len[q], from[q], to[q], amg->flag, l + 1);
         }

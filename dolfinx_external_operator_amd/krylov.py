@@ -156,11 +156,18 @@ class AMG:
     operator up to single-precision rounding (about 1e-7 relative to the fp64 cycle): it may be passed to gmres, cg and fgmres, whose
     own arithmetic stays double; fgmres is the recommended partner. `fp32_bytes`: what the copies take. A finite entry beyond the
     range of float makes setup() raise ValueError; r is narrowed to float on entry, so an |r| beyond float's range is not representable
-    (scale it). Not with cycle="K" (ValueError, in either order)."""
+    (scale it). Not with cycle="K" (ValueError, in either order).
+
+    `first_transfer`: a NodalTransfer (DeviceMesh.vertex_transfer(psi_nodes)) for matrices of quadratic elements
+    (dxo_amg_create_transfer). The prolongator of level 0 is then this nodal interpolation, P = W (x) I_bs without the constrained
+    dofs: level 1 is the degree-1 space on the same cells (A_1 = P^T A P, recomputed by every setup()) and the aggregation, the
+    near-null space and `strength` start there, on a matrix whose nodes have 27 neighbours instead of up to 125. Level 0 keeps its
+    relaxation; its P is stored as block diagonals (the property `first_transfer`), frozen at construction. Every other keyword composes
+    with it. None (the default): the object of earlier versions."""
 
     def __init__(self, A, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None,
                  smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10, lower: float = 0.1,
-                 safety: float = 1.1, strength: float = 0.0, cycle: str = "V", precision: str = "fp64"):
+                 safety: float = 1.1, strength: float = 0.0, cycle: str = "V", precision: str = "fp64", first_transfer=None):
         torch = _torch()
         import numpy as np
 
@@ -189,7 +196,21 @@ class AMG:
         _use_current_stream(self.ctx)
         bcp = C.c_void_p(bc.data_ptr()) if bc.numel() else None
         self.n_modes = 0
-        if near_nullspace is None and strength > 0.0:
+        if first_transfer is not None:
+            from ._lib import AmgTransfer
+
+            t, k, B = first_transfer, 0, None
+            if t.ptr.size != self.n // self.bs + 1:
+                raise ValueError(f"AMG: first_transfer has {t.ptr.size - 1} rows, the matrix {self.n // self.bs} nodes")
+            if near_nullspace is not None:
+                B, k = self._near_nullspace(near_nullspace)
+            desc = AmgTransfer(t.n_coarse, t.ptr.ctypes.data, t.col.ctypes.data, t.w.ctypes.data, t.coarse_to_fine.ctypes.data)
+            rc = self.ctx.lib.dxo_amg_create_transfer(self.ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), bcp, int(bc.numel()),
+                                                      C.c_void_p(B.data_ptr()) if k else None, k, strength, C.byref(desc), int(max_levels),
+                                                      int(coarse_rows), int(sweeps), C.byref(h))
+            self.ctx.check(rc, "dxo_amg_create_transfer")
+            self.n_modes = k
+        elif near_nullspace is None and strength > 0.0:
             rc = self.ctx.lib.dxo_amg_create_soc(self.ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), bcp, int(bc.numel()), None, 0, strength,
                                                  int(max_levels), int(coarse_rows), int(sweeps), C.byref(h))
             self.ctx.check(rc, "dxo_amg_create_soc")
@@ -198,13 +219,7 @@ class AMG:
                                              C.byref(h))
             self.ctx.check(rc, "dxo_amg_create")
         else:
-            B = near_nullspace
-            k = {2: 3, 3: 6}.get(self.bs)
-            if not (isinstance(B, torch.Tensor) and B.dtype == torch.float64 and B.is_cuda and B.device == self.device and B.dim() == 2
-                    and k is not None and tuple(B.shape) == (self.n, k)):
-                raise ValueError(f"AMG: near_nullspace must be a float64 CUDA tensor of shape ({self.n}, {k}) on {self.device} "
-                                 f"(bs 2: 3 vectors, bs 3: 6 vectors; this matrix has bs {self.bs})")
-            B = B.contiguous()
+            B, k = self._near_nullspace(near_nullspace)
             if strength > 0.0:
                 rc = self.ctx.lib.dxo_amg_create_soc(self.ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), bcp, int(bc.numel()),
                                                      C.c_void_p(B.data_ptr()), k, strength, int(max_levels), int(coarse_rows), int(sweeps),
@@ -229,6 +244,16 @@ class AMG:
         if precision != "fp64":
             self.set_precision(precision)
         self.setup()
+
+    def _near_nullspace(self, B) -> tuple:
+        """(B contiguous, k) of a valid near-null space of this matrix."""
+        torch = _torch()
+        k = {2: 3, 3: 6}.get(self.bs)
+        if not (isinstance(B, torch.Tensor) and B.dtype == torch.float64 and B.is_cuda and B.device == self.device and B.dim() == 2
+                and k is not None and tuple(B.shape) == (self.n, k)):
+            raise ValueError(f"AMG: near_nullspace must be a float64 CUDA tensor of shape ({self.n}, {k}) on {self.device} "
+                             f"(bs 2: 3 vectors, bs 3: 6 vectors; this matrix has bs {self.bs})")
+        return B.contiguous(), k
 
     def _relaxation(self, smoother, degree, rho, rho_iters, lower, safety) -> tuple:
         if smoother not in _SMOOTHERS or rho not in _RHO_KINDS:
@@ -268,6 +293,24 @@ class AMG:
             raise ValueError(f"AMG: precision must be one of {sorted(_PRECISIONS)}")
         self.ctx.check(self.ctx.lib.dxo_amg_set_precision(self.ctx._h, self._h, _PRECISIONS[precision]), "dxo_amg_set_precision")
         return self
+
+    def _transfer_info(self) -> tuple:
+        on, nc, pb, pd, ctf = C.c_int(), C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.dxo_amg_transfer_info(self.ctx._h, self._h, C.byref(on), C.byref(nc), C.byref(pb), C.byref(pd), C.byref(ctf)),
+                       "dxo_amg_transfer_info")
+        return bool(on.value), int(nc.value), int(pb.value), pd.value, ctf.value
+
+    @property
+    def first_transfer(self):
+        """None, or what level 0 keeps of the given transfer: {"n_coarse", "p_blocks", "p_diag"}, p_diag a float64 CUDA tensor view
+        (p_blocks, bs) of the block diagonals of P (the weights without the constrained dofs; alive as long as this object)."""
+        on, nc, pb, pd, _ = self._transfer_info()
+        if not on:
+            return None
+        torch = _torch()
+        view = torch.as_tensor(_CudaArrayView(self, pd, pb * self.bs, "<f8"), device=self.device).view(pb, self.bs) if pb else \
+            torch.empty((0, self.bs), dtype=torch.float64, device=self.device)
+        return {"n_coarse": nc, "p_blocks": pb, "p_diag": view}
 
     def _precision_info(self) -> tuple:
         kind, nbytes = C.c_int(), C.c_int64()
@@ -451,13 +494,18 @@ class AMG:
     def prolongator(self, level: int):
         """P_level (rows of `level`, rows of `level + 1`) as a scipy.sparse.bsr_matrix with bs x bs_coarse blocks (explicit zeros
         kept)."""
+        import numpy as np
         import scipy.sparse
 
         i = self._info(level)
         if not i.p_ptr:
             raise ValueError(f"AMG.prolongator: level {level} is the coarsest")
         bs, bsc = self._nns(level)[:2]
-        data = self._array(i.p_values, i.p_blocks * bs * bsc, "<f8").reshape(-1, bs, bsc)
+        if not i.p_values:               # a given transfer: the diagonals of the blocks
+            pd = self._array(self._transfer_info()[3], i.p_blocks * bs, "<f8").reshape(-1, bs)
+            data = pd[:, :, None] * np.eye(bs)[None]
+        else:
+            data = self._array(i.p_values, i.p_blocks * bs * bsc, "<f8").reshape(-1, bs, bsc)
         return scipy.sparse.bsr_matrix((data, self._array(i.p_col, i.p_blocks, "<i4"), self._array(i.p_ptr, i.n_nodes + 1, "<i8")),
                                        shape=(i.n_rows, i.n_aggregates * bsc))
 

@@ -70,6 +70,7 @@ class DeviceMesh:
         h = C.c_void_p()
         self.ctx.check(self.ctx.lib.dxo_mesh_create(self.ctx._h, C.byref(d), C.byref(h)), "dxo_mesh_create")
         self._h = h
+        self._dofmap, self._geom_dofmap = dofmap, geom_dofmap      # host arrays, for vertex_transfer
         if psi is not None:     # values of the coordinate element at the points: the operand `x` (set_coordinate_values)
             self.set_coordinate_values(psi)
 
@@ -118,6 +119,15 @@ class DeviceMesh:
         """From a DOLFINx function space and reference quadrature points (see `tables_from_dolfinx`). DOLFINx is not
         installed on the GPU box; tests drive this with stand-in objects that follow basix's documented layouts."""
         return cls(**cls.tables_from_dolfinx(V, quadrature_points), **kw)
+
+    def vertex_transfer(self, psi_nodes) -> "NodalTransfer":
+        """The nodal interpolation from the degree-1 space on the same cells to this mesh's field space, for
+        DeviceCSR.amg(first_transfer=...): host NumPy, once per mesh. `psi_nodes` (ndofs per cell, ngeom): the degree-1 coordinate
+        element tabulated at the field element's reference nodes (tools.synthetic.coordinate_element_at_nodes; on DOLFINx the
+        coordinate element at V.element.interpolation_points). Coarse nodes are the geometry nodes; entries with |psi| <= 1e-14 are
+        dropped; a node shared by several cells must get the same row from each (ValueError otherwise). A degree-1 field, where every
+        row would be a single 1, is refused."""
+        return vertex_transfer(self._dofmap, self._geom_dofmap, psi_nodes, self.num_field_nodes)
 
     def value_size(self, kind: str, bs: int) -> int:
         r = self.ctx.lib.dxo_operand_value_size(self.gdim, int(bs), KINDS[kind])
@@ -420,6 +430,62 @@ class DeviceMesh:
             pass
 
 
+class NodalTransfer:
+    """W of a nodal interpolation in CSR form: row i holds the coarse nodes `col` (ascending) and weights `w` of fine node i;
+    `coarse_to_fine[v]` is the fine node that coarse node v is (its row is the single entry (v, 1)). The argument `first_transfer`
+    of DeviceCSR.amg (dxo_amg_transfer)."""
+
+    def __init__(self, n_coarse, ptr, col, w, coarse_to_fine):
+        self.n_coarse = int(n_coarse)
+        self.ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+        self.col = np.ascontiguousarray(col, dtype=np.int32)
+        self.w = np.ascontiguousarray(w, dtype=np.float64)
+        self.coarse_to_fine = np.ascontiguousarray(coarse_to_fine, dtype=np.int32)
+
+    def to_scipy(self):
+        import scipy.sparse
+
+        return scipy.sparse.csr_matrix((self.w, self.col, self.ptr), shape=(self.ptr.size - 1, self.n_coarse))
+
+
+def vertex_transfer(dofmap, geom_dofmap, psi_nodes, num_field_nodes: int | None = None) -> NodalTransfer:
+    """DeviceMesh.vertex_transfer on plain arrays: dofmap (cells, ndofs), geom_dofmap (cells, ngeom), psi_nodes (ndofs, ngeom)."""
+    dofmap = np.asarray(dofmap, dtype=np.int64)
+    geom = np.asarray(geom_dofmap, dtype=np.int64)
+    psi = np.asarray(psi_nodes, dtype=np.float64)
+    nc, nd = dofmap.shape
+    if psi.shape != (nd, geom.shape[1]) or geom.shape[0] != nc:
+        raise ValueError("vertex_transfer: psi_nodes must have the shape (dofs per cell, geometry nodes per cell)")
+    if nd <= geom.shape[1]:
+        raise ValueError("vertex_transfer: the field has no more nodes per cell than the geometry (degree 1): there is nothing to coarsen")
+    n = int(num_field_nodes) if num_field_nodes is not None else int(dofmap.max()) + 1
+    n_coarse = int(geom.max()) + 1
+    a, v = np.nonzero(np.abs(psi) > 1e-14)                    # the same local entries in every cell
+    rows = dofmap[:, a].reshape(-1)
+    cols = geom[:, v].reshape(-1)
+    vals = np.broadcast_to(psi[a, v], (nc, a.size)).reshape(-1)
+    key = rows * n_coarse + cols
+    order = np.argsort(key, kind="stable")
+    key, vals = key[order], vals[order]
+    first = np.concatenate([[True], key[1:] != key[:-1]])
+    start = np.flatnonzero(first)
+    group = np.cumsum(first) - 1
+    if np.abs(vals - vals[start][group]).max(initial=0.0) > 1e-12:
+        raise ValueError("vertex_transfer: the cells that share a node disagree on its weights")
+    ukey, w = key[start], vals[start]
+    r, c = ukey // n_coarse, ukey % n_coarse
+    counts = np.bincount(r, minlength=n)
+    if (counts == 0).any():
+        raise ValueError("vertex_transfer: a field node belongs to no cell")
+    ptr = np.concatenate([[0], np.cumsum(counts)])
+    single = np.flatnonzero((counts == 1) & (w[ptr[:-1]] == 1.0))       # the fine nodes that are coarse nodes
+    ctf = -np.ones(n_coarse, dtype=np.int64)
+    ctf[c[ptr[single]]] = single
+    if (ctf < 0).any() or np.unique(ctf).size != n_coarse:
+        raise ValueError("vertex_transfer: not every geometry node is a field node with the weight 1")
+    return NodalTransfer(n_coarse, ptr, c, w, ctf)
+
+
 class CsrPattern:
     """dxo_csr: the CSR pattern of one Lagrange field with block size bs on a DeviceMesh. Rows and columns are the blocked dofs
     node*bs + i; a row holds the columns of every node that shares a cell with its node, sorted, diagonal included (DOLFINx's layout for
@@ -533,7 +599,7 @@ class DeviceCSR:
 
     def amg(self, constrained=None, max_levels: int = 10, coarse_rows: int = 512, sweeps: int = 1, near_nullspace=None,
             smoother: str = "jacobi", degree: int | None = None, rho: str = "inf-norm", rho_iters: int = 10, lower: float = 0.1,
-            safety: float = 1.1, strength: float = 0.0, cycle: str = "V", precision: str = "fp64") -> "AMG":
+            safety: float = 1.1, strength: float = 0.0, cycle: str = "V", precision: str = "fp64", first_transfer=None) -> "AMG":
         """A smoothed-aggregation multigrid preconditioner of this matrix (krylov.AMG: the symbolic phase and the first setup), for
         krylov.gmres / krylov.cg. `constrained`: the dofs given as bcs to bilinear_assemble. `near_nullspace`: a float64 CUDA tensor
         (n_rows, k), e.g. krylov.rigid_body_modes(x) for elasticity (k = 3 for bs 2, 6 for bs 3). `smoother` ("jacobi" or "chebyshev" of `degree`), `rho`
@@ -541,11 +607,13 @@ class DeviceCSR:
         customary rule, not measurements. `strength`: the threshold of the strength of connection in [0, 1), 0 for none
         (anisotropic operators: 0.25); the masks are made from the present values and frozen. `cycle`: "V", or "K" for the K-cycle
         (for krylov.fgmres only). `precision`: "fp64", or "fp32" for a V-cycle on single-precision copies of the levels (the setup
-        stays double; krylov.fgmres is its recommended partner). After the values changed: `.setup()`."""
+        stays double; krylov.fgmres is its recommended partner). `first_transfer`: a NodalTransfer (DeviceMesh.vertex_transfer) for
+        matrices of quadratic elements: level 1 is then the degree-1 space on the same cells and the aggregation starts there, see
+        krylov.AMG. After the values changed: `.setup()`."""
         from .krylov import AMG
 
         return AMG(self, constrained, max_levels, coarse_rows, sweeps, near_nullspace, smoother, degree, rho, rho_iters, lower, safety, strength, cycle,
-                   precision)
+                   precision, first_transfer)
 
 
 class DeviceOperand:

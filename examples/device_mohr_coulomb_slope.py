@@ -7,7 +7,7 @@ A 1.2 x 1.0 rectangle of P2 triangles, bottom and right edges clamped, body forc
     sigma, C_tang = MC(eps(Du), sigma_n)        dxo_mohr_coulomb_field (mem = DEVICE)
     R = adjoint(eps, sigma) - adjoint(value, q) dxo_operand_adjoint, zero on the clamped dofs
     J = assembled (eps, eps) form with C_tang   dxo_bilinear_assemble + dxo_csr_dirichlet (identity rows)
-    solve J dDu = -R                            gmres with block Jacobi (dxo_krylov_gmres), --solver amg: gmres with the multigrid cycle (amg-rbm: with the rigid-body modes as its near-null space, amg-cheby: those modes, the power estimate of rho and Chebyshev smoothing of degree 2, amg-soc: those modes and strength-of-connection coarsening with theta 0.1, the masks of the first Newton iteration kept, amg-k: amg-rbm with the K-cycle, under flexible GMRES, amg-fp32: amg-cheby with the cycle in single precision, under flexible GMRES), --solver lu: splu on the host
+    solve J dDu = -R                            gmres with block Jacobi (dxo_krylov_gmres), --solver amg: gmres with the multigrid cycle (amg-rbm: with the rigid-body modes as its near-null space, amg-cheby: those modes, the power estimate of rho and Chebyshev smoothing of degree 2, amg-soc: those modes and strength-of-connection coarsening with theta 0.1, the masks of the first Newton iteration kept, amg-k: amg-rbm with the K-cycle, under flexible GMRES, amg-fp32: amg-cheby with the cycle in single precision, under flexible GMRES, amg-p: amg-cheby with the p-coarsening first level, the degree-1 space on the same cells, in front of the aggregation: the mesh here is quadratic), --solver lu: splu on the host
     Du += dDu
 and at the end of a load step u += Du, sigma_n <- sigma. C_tang is the derivative through the return map and is not symmetric in
 general, hence GMRES. Newton stops at |R| <= max(1e-8, 1e-8 |R_0|) (the demo's snes_atol / snes_rtol). Each step starts from
@@ -16,7 +16,7 @@ Du = 0, where the return map has no tangent: with deps = 0 its initial residual 
 the same reason, :639-646). The first Newton iteration of a step therefore uses the elastic tangent, the others C_tang. A step
 whose GMRES or Newton does not converge is reported and ends the loading.
 
-    python3 examples/device_mohr_coulomb_slope.py [--n 25] [--steps K] [--solver gmres|amg|amg-rbm|amg-cheby|amg-soc|amg-k|amg-fp32|lu]
+    python3 examples/device_mohr_coulomb_slope.py [--n 25] [--steps K] [--solver gmres|amg|amg-rbm|amg-cheby|amg-soc|amg-k|amg-fp32|amg-p|lu]
         [--basis fp64|fp32]   (fp32: the Krylov basis of gmres / fgmres stored in single precision, dxo_krylov_create_basis)
 """
 import argparse
@@ -31,7 +31,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from dolfinx_external_operator_amd import MEM_DEVICE, Context, DeviceMesh, McParams, fgmres, gmres, rigid_body_modes  # noqa: E402
-from tools.synthetic import structured_mesh  # noqa: E402
+from tools.synthetic import coordinate_element_at_nodes, structured_mesh  # noqa: E402
 
 E, NU, COH, PHI, PSI, THETA_T = 6778.0, 0.25, 3.45, 30 * np.pi / 180, 30 * np.pi / 180, 26 * np.pi / 180
 L, H, GAMMA = 1.2, 1.0, 1.0
@@ -112,7 +112,7 @@ def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: 
                 d = torch.from_numpy(scipy.sparse.linalg.splu(S).solve(rhs.cpu().numpy())).to(dev)
             else:
                 try:
-                    if solver in ("amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k", "amg-fp32"):     # the symbolic phase once, the numeric setup at every Newton iteration
+                    if solver in ("amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k", "amg-fp32", "amg-p"):     # the symbolic phase once, the numeric setup at every Newton iteration
                         if amg is None:
                             relax = {"smoother": "chebyshev", "degree": 2, "rho": "power"} if solver == "amg-cheby" else {}
                             if solver == "amg-soc":
@@ -121,6 +121,9 @@ def main(n: int = 25, steps: int | None = None, solver: str = "gmres", verbose: 
                                 relax = {"cycle": "K"}
                             if solver == "amg-fp32":
                                 relax = {"smoother": "chebyshev", "degree": 2, "rho": "power", "precision": "fp32"}
+                            if solver == "amg-p":    # the recommended relaxation, and level 1 the P1 space on the same triangles
+                                relax = {"smoother": "chebyshev", "degree": 2, "rho": "power",
+                                         "first_transfer": dm.vertex_transfer(coordinate_element_at_nodes(mesh.cell, mesh.degree))}
                             amg = A.amg(bcs, near_nullspace=rigid_body_modes(x, ctx=ctx) if solver != "amg" else None, **relax)
                         else:
                             amg.setup(A)
@@ -172,7 +175,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--n", type=int, default=25, help="cells per side (the demo: 25)")
     ap.add_argument("--steps", type=int, default=None, help="first K load steps only")
-    ap.add_argument("--solver", choices=["gmres", "amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k", "amg-fp32", "lu"], default="gmres")
+    ap.add_argument("--solver", choices=["gmres", "amg", "amg-rbm", "amg-cheby", "amg-soc", "amg-k", "amg-fp32", "amg-p", "lu"], default="gmres",
+                    help="amg-p: amg-cheby with the p-coarsening first level (quadratic meshes only; this one is)")
     ap.add_argument("--basis", choices=["fp64", "fp32"], default="fp64", help="storage of the Krylov basis of gmres / fgmres")
     a = ap.parse_args()
     main(a.n, a.steps, a.solver, basis=a.basis)

@@ -804,7 +804,29 @@ int dxo_krylov_fgmres(dxo_ctx* ctx, dxo_krylov* ws, const dxo_krylov_op* op, con
  *                   dxo_amg_set_cycle(DXO_AMG_CYCLE_K) on an object with DXO_AMG_PRECISION_FP32, answer DXO_E_OPTION and change
  *                   nothing. An unknown kind: DXO_E_OPTION.
  * dxo_amg_precision_info : the kind, and the bytes of the single-precision copies and vectors (0 if none were ever allocated). Any
- *                   pointer may be NULL. */
+ *                   pointer may be NULL.
+ *
+ * A given first transfer (quadratic elements: coarsen in the polynomial degree before aggregating):
+ * dxo_amg_create_transfer : dxo_amg_create_soc with the prolongator of level 0 given as a nodal interpolation P = W (x) I_bs
+ *                   (`first`, HOST arrays, copied; NULL: dxo_amg_create_soc exactly). W [n_nodes][n_coarse] in CSR form: row i holds
+ *                   the coarse nodes (ascending) and weights of fine node i; coarse node v IS the fine node coarse_to_fine[v], whose
+ *                   row is the single entry (v, 1). Level 0 keeps all a level smooths with (dinv, rho, omega, the Chebyshev pairs);
+ *                   its P is stored as the diagonals of its blocks, p_diag [p_blocks][bs] = w_iv keep(i, c) keep(coarse_to_fine[v], c)
+ *                   with keep 0 for a constrained dof, frozen here; a setup forms A_1 = P^T A P on the symbolic pattern of the
+ *                   product (an exactly zero diagonal entry becomes 1) and builds no P, mask or filtered matrix on level 0. Level 1
+ *                   is treated as a finest level: its constrained set is that of the nodes coarse_to_fine (a node with all dofs
+ *                   constrained joins no aggregate, the mask of T is this set, not a values-dependent one), its near-null space is
+ *                   the rows of the zeroed B at coarse_to_fine (exact for rigid-body modes under a degree-1 interpolation), and
+ *                   theta takes effect from level 1. Levels 1... are bit for bit the hierarchy the library builds from A_1 and that
+ *                   set. dxo_amg_set_smoother, dxo_amg_set_cycle and dxo_amg_set_precision apply as before (single precision: a float
+ *                   copy of p_diag). In dxo_amg_level_info of level 0 aggregate and p_values are NULL and n_aggregates is n_coarse;
+ *                   dxo_amg_nns_info reports bs_coarse = bs there. If level 0 is already the coarsest (n_rows <= coarse_rows,
+ *                   max_levels 1) the transfer is checked and not used. Errors beyond those of dxo_amg_create_soc: a NULL array
+ *                   DXO_E_NULL; n_coarse < 1 or n_coarse * bs above 0.8 n_rows (the stagnation rule), ptr[0] != 0, a node without an
+ *                   entry, a column or a coarse_to_fine outside its range: DXO_E_SIZE; columns of a row not ascending, a weight not
+ *                   finite, coarse_to_fine naming a node twice, a row of coarse_to_fine[v] other than {(v, 1.0)}: DXO_E_OPTION.
+ * dxo_amg_transfer_info : whether level 0 carries a given transfer, its coarse nodes and blocks, and the DEVICE arrays p_diag
+ *                   [p_blocks][bs] and coarse_to_fine [n_coarse] (0 / NULL without one). Any pointer may be NULL. */
 enum { DXO_AMG_PRECISION_FP64 = 0, DXO_AMG_PRECISION_FP32 = 1 };
 #define DXO_AMG_SMOOTH_JACOBI 0
 #define DXO_AMG_SMOOTH_CHEBYSHEV 1
@@ -853,6 +875,18 @@ int dxo_amg_set_cycle(dxo_ctx* ctx, dxo_amg* amg, int kind);
 int dxo_amg_cycle_info(dxo_ctx* ctx, const dxo_amg* amg, int* kind, int64_t* visits);
 int dxo_amg_set_precision(dxo_ctx* ctx, dxo_amg* amg, int kind);
 int dxo_amg_precision_info(dxo_ctx* ctx, const dxo_amg* amg, int* kind, int64_t* fp32_bytes);
+typedef struct dxo_amg_transfer {  /* host arrays, copied at creation                       */
+    int64_t n_coarse;              /* coarse nodes                                           */
+    const int64_t* ptr;            /* [n_nodes + 1] rows of W                                */
+    const int32_t* col;            /* coarse nodes of a row, ascending                       */
+    const double* w;               /* weights                                                */
+    const int32_t* coarse_to_fine; /* [n_coarse] the fine node a coarse node is              */
+} dxo_amg_transfer;
+int dxo_amg_create_transfer(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const int32_t* constrained, int64_t n_constrained,
+                            const double* B, int n_modes, double theta, const dxo_amg_transfer* first, int max_levels, int coarse_rows,
+                            int sweeps, dxo_amg** out);
+int dxo_amg_transfer_info(dxo_ctx* ctx, const dxo_amg* amg, int* present, int64_t* n_coarse, int64_t* p_blocks, const double** p_diag,
+                          const int32_t** coarse_to_fine);
 
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is

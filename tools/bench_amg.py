@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Standalone timing of the multigrid preconditioner (csrc/amg.hip; not a bench.py leg).
-    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG] [--strength THETA[,THETA...]] [--cycle K] [--precision fp32]
+    python3 tools/bench_amg.py [tri_cells_per_side] [hex_boxes_per_side] [heat_small] [heat_large] [--out FILE] [--rbm] [--cheby DEG] [--strength THETA[,THETA...]] [--cycle K] [--precision fp32] [--ptransfer] [--hex-rule 27]
 Systems (distorted meshes, the lower side clamped so that the matrices are regular):
   p2       ("grad", "grad", 2) on P2 triangles with C = I + 0.3 N(0, 1) per point (1291 per side: 10^7 points), as tools/bench_krylov.py
   q2hex    ("eps", "eps", 3) on Q2 hexahedra (40^3 boxes), the same kind of C
@@ -24,6 +24,12 @@ of one apply, and one FGMRES(30) solve to rtol 1e-8 (iterations, ms; the setup i
 --precision fp32 adds, for the same hierarchies and relaxations as --cycle K, the single-precision cycle on the same object in the same
 run (key "fp32" beside "kcycle"): setup ms (the double setup plus the casts), apply ms, and one FGMRES(30) solve to rtol 1e-8
 (iterations, ms, ms with setup); the object is back in double, set up, afterwards.
+--ptransfer adds, for every hierarchy of a quadratic system measured without --strength (the default's and that of --rbm), the hierarchy
+with the p-coarsening first level (DeviceMesh.vertex_transfer, first_transfer=; keys amg_p and amg_rbm_p): symbolic ms, rows per level,
+operator complexity, setup ms, apply ms and the GMRES(30) solve; with --cheby DEG the solve is repeated with power_cheby<DEG>.
+--hex-rule 27 adds the system q2hex27 beside q2hex: the same mesh tabulated at the 27-point Gauss rule, with the constant isotropic
+elasticity tensor (lambda 1, mu 0.7). q2hex itself is assembled with the 8-point rule, which under-integrates the 27-node element
+(spurious zero-energy modes): no preconditioner makes it converge, see DESIGN 9.5.
 Timing: warm-up, then 5 batches timed with HIP events on the launch stream, the MEDIAN batch reported (tools/bench_krylov._batches).
 Prints one JSON line."""
 from __future__ import annotations
@@ -38,13 +44,14 @@ if str(ROOT) not in sys.path:
 
 
 def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: int = 1024, maxiter: int = 3000, rbm: bool = False,
-         cheby: int = 0, strengths: tuple = (), cycle: str = "V", precision: str = "fp64") -> dict:
+         cheby: int = 0, strengths: tuple = (), cycle: str = "V", precision: str = "fp64", ptransfer: bool = False,
+         hex_rule: int = 8) -> dict:
     import numpy as np
     import torch
 
     from dolfinx_external_operator_amd import Context, DeviceMesh, fgmres, gmres, rigid_body_modes
     from tools.bench_krylov import _batches
-    from tools.synthetic import structured_mesh
+    from tools.synthetic import coordinate_element_at_nodes, gauss_tensor_rule, structured_mesh, with_rule
 
     ctx = Context(0)
     stream = torch.cuda.Stream()
@@ -111,6 +118,30 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
             r[f"amg{suffix}_soc{theta:g}"] = f
             amg.close()
 
+    def with_ptransfer(dm, m, A, bcs, nns, b, x, y, r, suffix):
+        if not ptransfer or m.degree != 2:
+            return
+        try:
+            amg = A.amg(bcs, near_nullspace=nns, first_transfer=dm.vertex_transfer(coordinate_element_at_nodes(m.cell, 2)))
+        except ValueError as e:              # a singular level: reported, the other figures of the run stand
+            r[f"amg{suffix}_p"] = {"error": str(e)}
+            return
+        f = {"symbolic_ms": round(amg.build_ms, 1), "setup_ms": timed(lambda: amg.setup(), 3), "apply_ms": timed(lambda: amg.apply(x, y), 20),
+             "rows": [d["rows"] for d in amg.levels], "operator_complexity": round(amg.operator_complexity, 4)}
+        relax = [("gmres30", {})] + ([(f"gmres30_power_cheby{cheby}", {"smoother": "chebyshev", "degree": cheby, "rho": "power"})] if cheby else [])
+        for key, kw in relax:
+            g = {}
+            if kw:
+                amg.set_smoother(**kw).setup()
+                g = {"setup_ms": timed(lambda: amg.setup(), 3), "apply_ms": timed(lambda: amg.apply(x, y), 20)}
+            gmres(A, b, M=amg, rtol=1e-8, maxiter=30)                        # warm-up
+            out = gmres(A, b, M=amg, restart=30, rtol=1e-8, maxiter=maxiter)
+            g.update({"iterations": out.iterations, "converged": out.converged, "residual": out.residual, "ms": round(out.ms, 2),
+                      "ms_with_setup": round(out.ms + g.get("setup_ms", f["setup_ms"]), 2)})
+            f[key] = g
+        r[f"amg{suffix}_p"] = f
+        amg.close()
+
     def system(tag, m, test, trial, bs, Cd, bnd):
         dm = DeviceMesh.from_synthetic(m, ctx=ctx)
         try:
@@ -147,6 +178,7 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                 if cheby:
                     relaxations(amg, A, b, x, y, r, "")
                 amg.close()
+                with_ptransfer(dm, m, A, bcs, None, b, x, y, r, "")
                 with_strength(A, bcs, None, b, x, y, r, "")
                 if rbm and bs == m.gdim:
                     amg = A.amg(bcs, near_nullspace=rigid_body_modes(m.node_x, ctx=ctx))
@@ -167,6 +199,7 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
                     if cheby:
                         relaxations(amg, A, b, x, y, r, "_rbm")
                     amg.close()
+                    with_ptransfer(dm, m, A, bcs, rigid_body_modes(m.node_x, ctx=ctx), b, x, y, r, "_rbm")
                     with_strength(A, bcs, rigid_body_modes(m.node_x, ctx=ctx), b, x, y, r, "_rbm")
             stream.synchronize()
             res["systems"][tag] = r
@@ -205,6 +238,12 @@ def main(n_side: int = 1291, n_hex: int = 40, n_heat: int = 256, n_heat_large: i
         Cd = 0.3 * torch.randn(npts * D * D, generator=gen, device=dev, dtype=torch.float64)
         Cd.view(npts, D, D).add_(torch.eye(D, device=dev, dtype=torch.float64))
         system(tag, m, test, trial, bs, Cd, lower_side(m, bs))
+        if tag == "q2hex" and hex_rule == 27:
+            m27 = with_rule(m, *gauss_tensor_rule(cell, 3))
+            Ce = torch.zeros(6, 6, device=dev, dtype=torch.float64)
+            Ce[:3, :3] = 1.0
+            Ce += 1.4 * torch.eye(6, device=dev, dtype=torch.float64)
+            system("q2hex27", m27, test, trial, bs, Ce.expand(m27.num_cells * m27.nq, 6, 6).contiguous().view(-1), lower_side(m27, bs))
     ctx.close()
     return res
 
@@ -239,7 +278,18 @@ if __name__ == "__main__":
         i = args.index("--precision")
         precision = args[i + 1]
         del args[i:i + 2]
-    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby, strengths=strengths, cycle=cycle, precision=precision)
+    ptransfer = "--ptransfer" in args
+    if ptransfer:
+        args.remove("--ptransfer")
+    hex_rule = 8
+    if "--hex-rule" in args:
+        i = args.index("--hex-rule")
+        hex_rule = int(args[i + 1])
+        del args[i:i + 2]
+        if hex_rule not in (8, 27):
+            raise SystemExit("--hex-rule takes 8 or 27")
+    r = main(*(int(a) for a in args), rbm=rbm, cheby=cheby, strengths=strengths, cycle=cycle, precision=precision, ptransfer=ptransfer,
+             hex_rule=hex_rule)
     line = json.dumps(r)
     print(line)
     if out_file:

@@ -132,6 +132,12 @@ class SyntheticMesh:
         return np.einsum("qv,cvj->cqj", psi, self.x[self.geom_dofmap])
 
 
+def coordinate_element_at_nodes(cell: str, degree: int = 2) -> np.ndarray:
+    """(ndofs per cell, ngeom): the degree-1 coordinate element tabulated at the reference nodes of the Lagrange element of `degree`,
+    what places the field nodes in `structured_mesh` and what DeviceMesh.vertex_transfer takes."""
+    return LagrangeElement(cell, 1).tabulate(LagrangeElement(cell, degree).nodes)[0]
+
+
 _MESH_CACHE: dict = {}
 
 
@@ -213,7 +219,7 @@ def structured_mesh(cell: str, n: tuple[int, ...], degree: int = 2, distort: flo
     phi, dphi = fe.tabulate(points)
     psi, dpsi = geo.tabulate(points)
     # physical position of field nodes: image of the reference nodes under each cell's map (shared nodes agree)
-    psi_nodes, _ = geo.tabulate(fe.nodes)
+    psi_nodes = coordinate_element_at_nodes(cell, degree)
     node_x = np.zeros((int(np.prod(fshape)), gdim))
     node_x[dm.reshape(-1)] = np.einsum("av,cvj->caj", psi_nodes, x[geom]).reshape(-1, gdim)
     return SyntheticMesh(cell, gdim, degree, np.ascontiguousarray(x), geom, dm, node_x, points, phi, dphi, dpsi, weights, psi)
