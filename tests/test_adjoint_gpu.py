@@ -252,7 +252,8 @@ def test_matrix_free_diagonal(ctx, cell, n):
                                            ("triangle", (5, 4), 2), ("quadrilateral", (4, 3), 2)])
 def test_lane_per_cell_kernel_equals_wave_group_kernel(ctx, cell, n, degree):
     """The standard elements take the lane = cell kernel for the virtual work of eps (adjoint_cell.h); switching it off
-    (option adjoint_cell = 0) must give the same vector to rounding."""
+    (option adjoint_cell = 0) must give the same vector to rounding.
+    tests/test_consumer_reference_gpu.py pins BOTH sides of this comparison to a long-double reference, dof by dof, on every element."""
     from dolfinx_external_operator_amd import DeviceMesh
 
     m = structured_mesh(cell, n, degree, distort=0.2, seed=12)
@@ -326,7 +327,8 @@ def test_matrix_pipe_scatter_equals_the_dpp_scatter_on_hexahedra(ctx, n, degree,
     equal to rounding, identical bits run to run; cell counts that are not a multiple of 8, Q1 and Q2, the atomics form.
     This test compares HIP with HIP (two forms of the scatter). What pins the DEFAULT (matrix-pipe) form to the NumPy oracle are the
     tests above, which run with the library's defaults: test_adjoint_identity_patch_test_and_oracle (adjointness, patch test, oracle on
-    all four cell types), test_matrix_free_tangent / _diagonal (oracle) and the Newton-Krylov convergence test."""
+    all four cell types), test_matrix_free_tangent / _diagonal (oracle) and the Newton-Krylov convergence test.
+    tests/test_consumer_reference_gpu.py pins BOTH sides of this comparison to a long-double reference, dof by dof, on every element."""
     import torch
 
     from dolfinx_external_operator_amd import DeviceMesh, VmParams
@@ -378,7 +380,8 @@ def test_matrix_pipe_scatter_equals_the_dpp_scatter_on_hexahedra(ctx, n, degree,
 def test_matrix_pipe_scatter_on_p2_triangles_and_tetrahedra(ctx, cell, n, atomics):
     """scatter_mfma.h: on P2 triangles (3-point rule) and P2 tetrahedra (4-point rule) the state-based tangent action and diagonal form the element vectors
     of a wave's 21 / 16 cells as 6 / 9 v_mfma_f64_16x16x4_f64 (option adjoint_mfma = 1, the default) instead of the lane = (cell, node) loop
-    over tensors parked in LDS (0): equal to rounding, identical bits run to run, ragged last groups, the atomics form."""
+    over tensors parked in LDS (0): equal to rounding, identical bits run to run, ragged last groups, the atomics form.
+    tests/test_consumer_reference_gpu.py pins BOTH sides of this comparison to a long-double reference, dof by dof, on every element."""
     import torch
 
     from dolfinx_external_operator_amd import DeviceMesh, VmParams
