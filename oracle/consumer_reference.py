@@ -140,6 +140,28 @@ def vm_tangent_from_state(prm, sigma, dp, dtype=LD):
     return C, C_mag
 
 
+def numpy_expand_tangent(sigma, dp, d, E=70e3, nu=0.3):
+    """Float64 NumPy statement of the tangent-from-state formulas (dxo_vm_expand_tangent), the dp = -0.0 mark of the reference's
+    0/0 point included: stand-in for the HIP rebuild kernel in the CPU-only gather test (tests/test_sharding.py), itself checked
+    against the oracle's tangent there."""
+    lmbda, mu = E * nu / ((1 + nu) * (1 - 2 * nu)), E / (2 * (1 + nu))
+    Et = E / 100.0
+    H = E * Et / (E - Et)
+    sigma = sigma.reshape(-1, d)
+    one = np.zeros(d)
+    one[:3] = 1.0
+    C_el = lmbda * np.outer(one, one) + 2 * mu * np.eye(d)
+    dev = np.eye(d) - np.outer(one, one) / 3.0
+    s = sigma @ dev.T
+    seq = np.sqrt(1.5 * np.sum(s * s, axis=1))
+    with np.errstate(all="ignore"):
+        beta = 3 * mu * dp / (seq + 3 * mu * dp)
+        n = s / seq[:, None] * (dp > 0)[:, None]
+    a = 3 * mu * (3 * mu / (3 * mu + H) - beta)
+    a = np.where((dp == 0.0) & np.signbit(dp), np.nan, a)     # the producer's mark -> the reference's NaN tangent
+    return C_el[None] - a[:, None, None] * n[:, :, None] * n[:, None, :] - (2 * mu * beta)[:, None, None] * dev[None]
+
+
 def worst_ratio(got, ref, mag, extra=None):
     """max_k |got[k] - ref[k]| / (2^-53 * mag[k] (+ extra[k])) in long double; entries with a zero scale must agree exactly (-> inf
     if one does not). The componentwise figure every bound of the consumer tests is stated in."""

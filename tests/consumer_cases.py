@@ -35,7 +35,7 @@ def element_name(case):
     return f"{case[0]} {'PQ'[case[0] in ('quadrilateral', 'hexahedron')]}{case[1]}" + (f" gauss{case[3]}" if case[3] else "")
 
 
-# von Mises parameters of the state-based forms (H as tests/test_sharding.py::numpy_expand_tangent fixes it: E_t = E / 100)
+# von Mises parameters of the state-based forms (H as oracle/consumer_reference.py::numpy_expand_tangent fixes it: E_t = E / 100)
 VM = types.SimpleNamespace(E=70e3, nu=0.3, sigma_0=250.0, H=70e3 * 700.0 / (70e3 - 700.0))
 
 # What float64 NumPy loses against long double, in units of 2^-53 * mag[k], worst dof of every mesh of ALL_CASES; rounded up from the
@@ -43,7 +43,7 @@ VM = types.SimpleNamespace(E=70e3, nu=0.3, sigma_0=250.0, H=70e3 * 700.0 / (70e3
 # quadrilaterals: J is a difference of coordinates of size 1 at a spacing of 1 / 13, which mag does not see and every float64 evaluation,
 # the kernels' included, loses alike:
 #   apply / force: oracle.operand_oracle.tangent_apply / operand_adjoint;  diag: the float64 twin of ref_tangent_diagonal;
-#   apply_vm / diag_vm: the same two fed the float64 tangent-from-state (tests/test_sharding.py::numpy_expand_tangent)
+#   apply_vm / diag_vm: the same two fed the float64 tangent-from-state (oracle/consumer_reference.py::numpy_expand_tangent)
 C_REF = {"apply": 7.7, "force": 15.0, "diag": 17.2, "apply_vm": 6.4, "diag_vm": 19.4}
 MARGIN = 8.0      # another summation order, fused multiply-adds; no other justification
 

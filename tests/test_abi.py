@@ -1,18 +1,11 @@
 """The C-ABI library: builds for gfx950, loads, exports what include/dxo.h declares (not gpu)."""
 import ctypes as C
-import pathlib
 import re
 import subprocess
 
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-HEADER = ROOT / "include" / "dxo.h"
-
-
-def header_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    return sorted(set(re.findall(r"\b(dxo_[a-z_0-9]+)\s*\(", text)))
+from abi_header import ROOT, header_functions
 
 
 def test_header_declares_the_path():

@@ -10,13 +10,10 @@ import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg
 
-from test_amg_cheby_oracle_cpu import amg_cheby_ref, cg_with_cheby, gmres_with_cheby, power_rho_ref, vcycle_cheby_ref
-from test_amg_gpu import _same_csr, _system
-from test_amg_nns_gpu import _nns_system
-from test_amg_oracle_cpu import U, block_diag, coarse_mask_ref, forward_bound, prolongator_ref, rho_ref, tentative_ref
-from test_bilinear_gpu import _cuda
-from test_krylov_gpu import _assemble, _torch, meshes  # noqa: F401  (meshes is a fixture)
-from test_krylov_oracle_cpu import bottom_dofs, elastic_C
+from oracle.amg_oracle import (U, amg_ref, block_diag, cg_with_cycle, coarse_mask_ref, cycle_ref, forward_bound, gmres_with_cycle,
+                               power_rho_ref, prolongator_ref, rho_ref, same_csr, tentative_ref)
+from oracle.krylov_oracle import bottom_dofs, elastic_C
+from solver_cases import _assemble, _assembled_system, _cuda, _nns_system, _torch, meshes  # noqa: F401  (meshes is a fixture)
 from tools.synthetic import structured_mesh
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +37,7 @@ CHEBY_CYCLE_TOL = 1.3e-12
 def _case(ctx, meshes, which, rbm):
     """(DeviceCSR, bs, constrained dofs, near-null space on the device or None, SPD?)"""
     if which == "heat":
-        A, bs, bcs = _system(ctx, meshes, "heat")
+        A, bs, bcs = _assembled_system(ctx, meshes, "heat")
         return A, bs, bcs, None, False
     from dolfinx_external_operator_amd import rigid_body_modes
 
@@ -49,7 +46,7 @@ def _case(ctx, meshes, which, rbm):
 
 
 def _reference(S, bs, bcs, B, **kw):
-    return amg_cheby_ref(S, bs, bcs, near_nullspace=None if B is None else B.cpu().numpy(), coarse_rows=COARSE_ROWS, **kw)
+    return amg_ref(S, bs, bcs, smoother="chebyshev", rho="power", near_nullspace=None if B is None else B.cpu().numpy(), coarse_rows=COARSE_ROWS, **kw)
 
 
 @pytest.mark.parametrize("which,rbm", CASES, ids=IDS)
@@ -109,7 +106,7 @@ def test_rho_hierarchy_and_cycle_match_the_oracle(ctx, meshes, which, rbm):
         for _ in range(3):
             r = rng.normal(size=S.shape[0])
             z = amg.apply(_cuda(r)).cpu().numpy()
-            zr = vcycle_cheby_ref(ref, r)
+            zr = cycle_ref(ref, r)
             assert np.isfinite(z).all()
             worst = max(worst, np.linalg.norm(z - zr) / np.linalg.norm(zr))
         buf = _cuda(r)
@@ -134,11 +131,11 @@ def test_iteration_counts_match_the_oracle_and_beat_the_default(ctx, meshes, whi
     if spd:
         out = cg(A, _cuda(b), M=amg, rtol=1e-10, maxiter=5000)
         old = cg(A, _cuda(b), M=default, rtol=1e-10, maxiter=5000)
-        _, its, conv = cg_with_cheby(S, b, levels, rtol=1e-10, maxiter=5000)
+        _, its, conv = cg_with_cycle(S, b, levels, rtol=1e-10, maxiter=5000)
     else:
         out = gmres(A, _cuda(b), M=amg, restart=30, rtol=1e-10, maxiter=5000)
         old = gmres(A, _cuda(b), M=default, restart=30, rtol=1e-10, maxiter=5000)
-        _, its, conv, _ = gmres_with_cheby(S, b, levels, m=30, rtol=1e-10, maxiter=5000)
+        _, its, conv, _ = gmres_with_cycle(S, b, levels, m=30, rtol=1e-10, maxiter=5000)
     print(f"{which} rbm {rbm}: {'CG' if spd else 'GMRES(30)'} iterations with Chebyshev 2 on the power estimate {out.iterations} "
           f"(oracle {its}), default {old.iterations}")
     assert out.converged and old.converged and conv
@@ -160,7 +157,7 @@ def _snapshot(a):
 
 
 def _same(p, q):
-    return (all(_same_csr(a, b) for a, b in zip(p[0], q[0]))
+    return (all(same_csr(a, b) for a, b in zip(p[0], q[0]))
             and all(np.array_equal(a.data, b.data) and np.array_equal(a.indices, b.indices) for a, b in zip(p[1], q[1]))
             and p[2] == q[2] and p[3] == q[3])
 
@@ -264,8 +261,8 @@ def test_switching_the_smoother(ctx, meshes, hip_library):
     wide = amg.set_smoother("chebyshev", degree=2).setup()
     assert wide is amg and _same(_snapshot(amg), snap_jacobi)                   # rho, omega, P and the coarse matrices are unchanged
     S = A.to_scipy()
-    ref = amg_cheby_ref(S, 2, bcs, rho="inf-norm", degree=2, coarse_rows=COARSE_ROWS, sweeps=2)
-    zw, zr = amg.apply(r).cpu().numpy(), vcycle_cheby_ref(ref, r.cpu().numpy())
+    ref = amg_ref(S, 2, bcs, smoother="chebyshev", rho="inf-norm", degree=2, coarse_rows=COARSE_ROWS, sweeps=2)
+    zw, zr = amg.apply(r).cpu().numpy(), cycle_ref(ref, r.cpu().numpy())
     assert np.linalg.norm(zw - zr) <= CHEBY_CYCLE_TOL * np.linalg.norm(zr)
 
 

@@ -1,117 +1,18 @@
 """The NumPy / SciPy yardstick of dxo_amg_set_smoother (csrc/amg.hip): the power-iteration estimate of rho and Chebyshev smoothing,
-pinned on the CPU on top of the oracles of test_amg_oracle_cpu.py and test_amg_nns_oracle_cpu.py.
+pinned on the CPU (oracle/amg_oracle.py).
 
 power_rho_ref: rho = safety |w_m| after m steps w_k = Dinv A (w_{k-1} / |w_{k-1}|) from the fixed start vector
 w_0[i] = 0.5 + ((uint32)(i * 2654435761) >> 8) * 2^-24, which is exact in float64. cheby_ref: the polynomial of degree k in Dinv A on
-[lower rho, rho], by the recurrence of the device. amg_cheby_ref builds the hierarchy with amg_ref / amg_nns_ref, whose rho (and with
-it omega of the prolongator smoothing) then comes from the selected estimate; vcycle_cheby_ref is the cycle with the selected
-smoother before and after the coarse correction."""
-import contextlib
-
+[lower rho, rho], by the recurrence of the device. amg_ref(rho="power") takes rho (and with it omega of the prolongator smoothing)
+from the selected estimate; cycle_ref runs the selected smoother before and after the coarse correction."""
 import numpy as np
 import pytest
 import scipy.sparse.linalg
 
-import test_amg_nns_oracle_cpu as nns_oracle
-import test_amg_oracle_cpu as amg_oracle
-from test_amg_oracle_cpu import amg_ref, apply_block, block_diag, callable_preconditioners, rho_ref, vcycle_ref
-from test_krylov_oracle_cpu import bottom_dofs, boundary_dofs, cg_ref, eps_matrix, gmres_ref, heat_matrix, to_pattern_csr
-
-RHO_ITERS, LOWER, SAFETY = 10, 0.1, 1.1        # the customary rule (PETSc's), the defaults of the library
-
-
-def start_vector(n):
-    i = np.arange(n, dtype=np.uint64)
-    return 0.5 + (((i * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
-
-
-def power_rho_ref(A, Dinv, iters=RHO_ITERS, safety=SAFETY):
-    """safety |w_iters|; 0 for a zero matrix."""
-    w = start_vector(A.shape[0])
-    lam = np.sqrt(w @ w)
-    for _ in range(iters):
-        s = 1.0 / lam if lam > 0.0 else 0.0
-        w = apply_block(Dinv, A @ (s * w))
-        lam = np.sqrt(w @ w)
-    return safety * lam
-
-
-def cheby_pairs(rho, lower, degree):
-    """(c1, c2) of the steps d = c1 d + c2 Dinv (r - A x), x += d."""
-    if not rho > 0.0:
-        return [(0.0, 0.0)] * degree
-    a = lower * rho
-    theta, delta = 0.5 * (a + rho), 0.5 * (rho - a)
-    sigma = theta / delta
-    r0 = 1.0 / sigma
-    out = [(0.0, 1.0 / theta)]
-    for _ in range(1, degree):
-        r1 = 1.0 / (2.0 * sigma - r0)
-        out.append((r1 * r0, 2.0 * r1 / delta))
-        r0 = r1
-    return out
-
-
-def cheby_ref(A, Dinv, rho, lower, degree, r, x=None):
-    """x after the Chebyshev polynomial of `degree` in Dinv A on [lower rho, rho], started from x (None: zero)."""
-    x = np.zeros_like(r) if x is None else x.copy()
-    d = np.zeros_like(r)
-    for c1, c2 in cheby_pairs(rho, lower, degree):
-        d = c1 * d + c2 * apply_block(Dinv, r - A @ x)
-        x = x + d
-    return x
-
-
-@contextlib.contextmanager
-def rho_source(kind, iters, safety):
-    """Inside, amg_ref and amg_nns_ref take rho (and with it omega) from the power iteration if kind == "power"."""
-    if kind != "power":
-        yield
-        return
-    plain = amg_oracle.rho_ref, nns_oracle.rho_ref
-    amg_oracle.rho_ref = nns_oracle.rho_ref = lambda A, Dinv: (power_rho_ref(A, Dinv, iters, safety), None)
-    try:
-        yield
-    finally:
-        amg_oracle.rho_ref, nns_oracle.rho_ref = plain
-
-
-def amg_cheby_ref(S, bs, constrained=(), near_nullspace=None, smoother="chebyshev", degree=None, rho="power", rho_iters=RHO_ITERS,
-                  lower=LOWER, safety=SAFETY, **kw):
-    """The levels of amg_ref (amg_nns_ref with a near-null space) under the selected rho, each with smoother, degree and lower."""
-    with rho_source(rho, rho_iters, safety):
-        levels = amg_ref(S, bs, constrained, **kw) if near_nullspace is None else nns_oracle.amg_nns_ref(S, bs, constrained, near_nullspace, **kw)
-    for L in levels:
-        L.smoother, L.degree, L.lower = smoother, (L.sweeps if degree is None else degree), lower
-    return levels
-
-
-def smooth_ref(L, r, x=None):
-    if L.smoother == "chebyshev":
-        return cheby_ref(L.A, L.Dinv, L.rho, L.lower, L.degree, r, x)
-    x = np.zeros_like(r) if x is None else x
-    for _ in range(L.sweeps):
-        x = x + L.omega * apply_block(L.Dinv, r - L.A @ x)
-    return x
-
-
-def vcycle_cheby_ref(levels, r, l=0):
-    L = levels[l]
-    if l == len(levels) - 1:
-        return L.dense_inverse @ r
-    x = smooth_ref(L, r)
-    x = x + L.P @ vcycle_cheby_ref(levels, L.P.T @ (r - L.A @ x), l + 1)
-    return smooth_ref(L, r, x)
-
-
-def gmres_with_cheby(S, b, levels, **kw):
-    with callable_preconditioners():
-        return gmres_ref(S, b, inv=lambda r: vcycle_cheby_ref(levels, r), **kw)
-
-
-def cg_with_cheby(S, b, levels, **kw):
-    with callable_preconditioners():
-        return cg_ref(S, b, inv=lambda r: vcycle_cheby_ref(levels, r), **kw)
+from oracle.amg_oracle import (LOWER, U, amg_ref, apply_block, block_diag, cg_with_cycle, cheby_ref, cycle_ref, gmres_with_cycle,
+                               power_rho_ref, rho_ref, rigid_body_modes_ref, start_vector)
+from oracle.krylov_oracle import bottom_dofs, boundary_dofs, eps_matrix, heat_matrix, to_pattern_csr
+from solver_cases import eps_spd
 
 
 def eps_system(nonsym_seed):
@@ -132,8 +33,8 @@ def test_jacobi_with_the_inf_norm_is_the_cycle_of_today():
     S, bs, dofs = eps_system(3)
     r = np.random.Generator(np.random.PCG64(4)).normal(size=S.shape[0])
     for sweeps in (1, 2):
-        levels = amg_cheby_ref(S, bs, dofs, smoother="jacobi", rho="inf-norm", coarse_rows=60, sweeps=sweeps)
-        assert np.array_equal(vcycle_cheby_ref(levels, r), vcycle_ref(amg_ref(S, bs, dofs, coarse_rows=60, sweeps=sweeps), r))
+        levels = amg_ref(S, bs, dofs, smoother="jacobi", rho="inf-norm", coarse_rows=60, sweeps=sweeps)
+        assert np.array_equal(cycle_ref(levels, r), cycle_ref(amg_ref(S, bs, dofs, coarse_rows=60, sweeps=sweeps), r))
 
 
 def test_degree_one_is_a_damped_jacobi_sweep():
@@ -141,20 +42,20 @@ def test_degree_one_is_a_damped_jacobi_sweep():
     S, bs, dofs = eps_system(3)
     rng = np.random.Generator(np.random.PCG64(6))
     r, x0 = rng.normal(size=(2, S.shape[0]))
-    L = amg_cheby_ref(S, bs, dofs, coarse_rows=60)[0]
+    L = amg_ref(S, bs, dofs, smoother="chebyshev", rho="power", coarse_rows=60)[0]
     for lower in (0.1, 0.3):
         omega = 2.0 / ((1.0 + lower) * L.rho)
         for start in (None, x0):
             x = np.zeros_like(r) if start is None else start
             want = x + omega * apply_block(L.Dinv, r - L.A @ x)
             got = cheby_ref(L.A, L.Dinv, L.rho, lower, 1, r, start)
-            assert np.linalg.norm(got - want) <= 8 * amg_oracle.U * np.linalg.norm(want), lower
+            assert np.linalg.norm(got - want) <= 8 * U * np.linalg.norm(want), lower
     # and the whole cycle of degree 1 is the Jacobi cycle with that omega
-    levels = amg_cheby_ref(S, bs, dofs, degree=1, coarse_rows=60)
-    jac = amg_cheby_ref(S, bs, dofs, smoother="jacobi", coarse_rows=60)
+    levels = amg_ref(S, bs, dofs, smoother="chebyshev", rho="power", degree=1, coarse_rows=60)
+    jac = amg_ref(S, bs, dofs, rho="power", smoother="jacobi", coarse_rows=60)
     for Lj in jac[:-1]:
         Lj.omega = 2.0 / ((1.0 + LOWER) * Lj.rho)       # the sweeps only: P keeps the omega it was built with
-    z, zj = vcycle_cheby_ref(levels, r), vcycle_cheby_ref(jac, r)
+    z, zj = cycle_ref(levels, r), cycle_ref(jac, r)
     assert np.linalg.norm(z - zj) <= 1e-13 * np.linalg.norm(zj)
 
 
@@ -179,15 +80,15 @@ def test_cycle_is_linear_and_symmetric_for_an_spd_matrix():
     m, A = eps_matrix(nonsym_seed=None)
     S = to_pattern_csr(m, A, 2)
     for degree in (1, 2, 3):
-        levels = amg_cheby_ref(S, 2, bottom_dofs(m, 2), degree=degree, coarse_rows=30)
+        levels = amg_ref(S, 2, bottom_dofs(m, 2), smoother="chebyshev", rho="power", degree=degree, coarse_rows=30)
         assert len(levels) >= 2
         r1, r2 = rng.normal(size=(2, S.shape[0]))
-        z1, z2 = vcycle_cheby_ref(levels, r1), vcycle_cheby_ref(levels, r2)
-        z = vcycle_cheby_ref(levels, 2.5 * r1 + r2)
+        z1, z2 = cycle_ref(levels, r1), cycle_ref(levels, r2)
+        z = cycle_ref(levels, 2.5 * r1 + r2)
         assert np.linalg.norm(z - (2.5 * z1 + z2)) <= 1e-13 * np.linalg.norm(z)
         assert abs(r2 @ z1 - r1 @ z2) <= 1e-12 * (np.linalg.norm(r1) * np.linalg.norm(z2))
         assert r1 @ z1 > 0 and r2 @ z2 > 0
-        x, its, conv = cg_with_cheby(S, r1, levels, rtol=1e-10)
+        x, its, conv = cg_with_cycle(S, r1, levels, rtol=1e-10)
         assert conv
         assert np.linalg.norm(x - scipy.sparse.linalg.spsolve(S.tocsc(), r1)) <= 1e-8 * np.linalg.norm(x)
 
@@ -207,7 +108,7 @@ def test_power_estimate_against_the_true_radius():
     factor is 0.9 and not 1."""
     smallest = np.inf
     for name, S, bs, dofs, coarse_rows in _radius_cases():
-        levels = amg_cheby_ref(S, bs, dofs, coarse_rows=coarse_rows)
+        levels = amg_ref(S, bs, dofs, smoother="chebyshev", rho="power", coarse_rows=coarse_rows)
         assert len(levels) >= 3, name
         checked = 0
         for l, L in enumerate(levels[:-1]):
@@ -231,15 +132,15 @@ def test_chebyshev_with_the_power_estimate_needs_fewer_iterations(spd):
     S, bs, dofs = eps_system(None if spd else 3)
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
     ref = scipy.sparse.linalg.spsolve(S.tocsc(), b)
-    cheb = amg_cheby_ref(S, bs, dofs, degree=3, coarse_rows=60)
-    jac = amg_cheby_ref(S, bs, dofs, smoother="jacobi", rho="inf-norm", sweeps=3, coarse_rows=60)
-    jac_power = amg_cheby_ref(S, bs, dofs, smoother="jacobi", sweeps=3, coarse_rows=60)
+    cheb = amg_ref(S, bs, dofs, smoother="chebyshev", rho="power", degree=3, coarse_rows=60)
+    jac = amg_ref(S, bs, dofs, smoother="jacobi", rho="inf-norm", sweeps=3, coarse_rows=60)
+    jac_power = amg_ref(S, bs, dofs, rho="power", smoother="jacobi", sweeps=3, coarse_rows=60)
     counts = []
     for levels in (cheb, jac_power, jac):
         if spd:
-            x, its, conv = cg_with_cheby(S, b, levels, rtol=1e-8, maxiter=3000)
+            x, its, conv = cg_with_cycle(S, b, levels, rtol=1e-8, maxiter=3000)
         else:
-            x, its, conv, _ = gmres_with_cheby(S, b, levels, m=30, rtol=1e-8, maxiter=3000)
+            x, its, conv, _ = gmres_with_cycle(S, b, levels, m=30, rtol=1e-8, maxiter=3000)
         assert conv and np.linalg.norm(x - ref) <= 1e-5 * np.linalg.norm(ref)
         counts.append(its)
     print(f"eps 14 x 14 {'CG' if spd else 'GMRES(30)'}: Chebyshev 3 / power {counts[0]}, Jacobi 3 / power {counts[1]}, "
@@ -249,15 +150,15 @@ def test_chebyshev_with_the_power_estimate_needs_fewer_iterations(spd):
 
 def test_near_nullspace_levels_take_the_same_smoother():
     """Rigid-body modes: coarse levels of block size 3; the estimate and the polynomial run on them as on any level."""
-    m, S, dofs = nns_oracle.eps_spd((10, 10))
-    B = nns_oracle.rigid_body_modes_ref(m.node_x)
-    levels = amg_cheby_ref(S, 2, dofs, near_nullspace=B, degree=2, coarse_rows=40)
+    m, S, dofs = eps_spd((10, 10))
+    B = rigid_body_modes_ref(m.node_x)
+    levels = amg_ref(S, 2, dofs, smoother="chebyshev", rho="power", near_nullspace=B, degree=2, coarse_rows=40)
     assert len(levels) >= 3 and [L.bs for L in levels] == [2] + [3] * (len(levels) - 1)
     for L in levels[:-1]:
         assert L.rho == power_rho_ref(L.A, L.Dinv) and L.Dinv.shape[1] == L.bs
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
-    _, its, conv = cg_with_cheby(S, b, levels, rtol=1e-8, maxiter=2000)
-    plain = nns_oracle.amg_nns_ref(S, 2, dofs, B, coarse_rows=40, sweeps=2)
-    _, its_plain, conv_plain = amg_oracle.cg_with_cycle(S, b, plain, rtol=1e-8, maxiter=2000)
+    _, its, conv = cg_with_cycle(S, b, levels, rtol=1e-8, maxiter=2000)
+    plain = amg_ref(S, 2, dofs, near_nullspace=B, coarse_rows=40, sweeps=2)
+    _, its_plain, conv_plain = cg_with_cycle(S, b, plain, rtol=1e-8, maxiter=2000)
     print(f"eps 10 x 10 with rigid-body modes, CG: Chebyshev 2 / power {its}, Jacobi 2 / inf-norm {its_plain} iterations")
     assert conv and conv_plain and its < its_plain

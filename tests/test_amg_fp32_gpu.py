@@ -9,18 +9,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_amg_fp32_oracle_cpu import vcycle_f32_ref
-from test_amg_kcycle_gpu import CASES, _device_levels, _hierarchy
-from test_bilinear_gpu import _cuda
-from test_fgmres_kcycle_oracle_cpu import vcycle_any_ref
-from test_krylov_gpu import _torch, meshes  # noqa: F401  (meshes is a fixture)
+from oracle.amg_oracle import cycle_ref
+from solver_cases import (CASES, NOT_DOUBLE, SAME_FORMULAS, _case_hierarchy, _cuda, _device_levels, _heat, _torch,
+                          meshes)  # noqa: F401  (meshes is a fixture)
 
 pytestmark = pytest.mark.gpu
 
 SYMMETRIC = ("p2_rbm", "hex_bar", "aniso_soc")      # eps/eps and grad/grad; the heat Jacobian (grad / value_grad) is not counted
-# e_dev <= SAME_FORMULAS e_ref: the device and the oracle evaluate the same formulas in float32 in different summation orders (a rule
-# for that reordering, not a measurement); e_dev >= NOT_DOUBLE e_ref: a cycle that silently ran in double would sit orders below
-SAME_FORMULAS, NOT_DOUBLE = 8.0, 0.05
 
 
 def _fp32_bytes(amg):
@@ -39,7 +34,7 @@ def _fp32_bytes(amg):
 @pytest.mark.parametrize("which", list(CASES))
 def test_fp32_cycle_matches_the_float32_oracle_on_the_device_levels(ctx, meshes, which):
     torch = _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which, precision="fp32")
+    A, amg = _case_hierarchy(ctx, meshes, which, precision="fp32")
     n_levels, sizes = CASES[which]
     assert amg.n_levels == n_levels and [d["bs"] for d in amg.levels] == sizes, (which, amg.levels)
     assert amg.precision == "fp32" and amg.cycle == "V"
@@ -51,8 +46,8 @@ def test_fp32_cycle_matches_the_float32_oracle_on_the_device_levels(ctx, meshes,
         zd = amg.apply(_cuda(r))
         assert zd.dtype == torch.float64
         z_dev = zd.cpu().numpy()
-        z64 = vcycle_any_ref(levels, r)
-        z32 = vcycle_f32_ref(levels, r).astype(np.float64)
+        z64 = cycle_ref(levels, r)
+        z32 = cycle_ref(levels, r, precision="fp32").astype(np.float64)
         e_ref = np.linalg.norm(z32 - z64) / np.linalg.norm(z64)
         e_dev = np.linalg.norm(z_dev - z64) / np.linalg.norm(z64)
         print(f"{which}: FP32_SEEN e_dev / e_ref {e_dev / e_ref:.3f} (e_dev {e_dev:.3e}, e_ref {e_ref:.3e})")
@@ -74,7 +69,7 @@ def test_solvers_take_the_fp32_hierarchy(ctx, meshes, which):
     from dolfinx_external_operator_amd import cg, fgmres, gmres
 
     _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which, precision="fp32")
+    A, amg = _case_hierarchy(ctx, meshes, which, precision="fp32")
     S = A.to_scipy()
     asym = abs(S - S.T).max() / abs(S).max()
     assert asym <= 1e-12 or which not in SYMMETRIC, (which, asym)
@@ -101,11 +96,11 @@ def test_solvers_take_the_fp32_hierarchy(ctx, meshes, which):
 @pytest.mark.parametrize("which", ["heat48", "hex_bar", "heat48_cheby"])
 def test_switching(ctx, meshes, which):
     torch = _torch(ctx)
-    A, default = _hierarchy(ctx, meshes, which)
+    A, default = _case_hierarchy(ctx, meshes, which)
     r = _cuda(np.random.Generator(np.random.PCG64(1)).normal(size=A.shape[0]))
     z_default = default.apply(r).clone()
     assert default.precision == "fp64" and default.fp32_bytes == 0
-    _, spelled = _hierarchy(ctx, meshes, which, precision="fp64")
+    _, spelled = _case_hierarchy(ctx, meshes, which, precision="fp64")
     assert spelled.fp32_bytes == 0 and torch.equal(spelled.apply(r), z_default)
     assert default.set_precision("fp64") is default                                # the kind it has: nothing happens, no setup needed
     assert torch.equal(default.apply(r), z_default)
@@ -126,7 +121,7 @@ def test_a_setup_refreshes_the_copies(ctx, meshes, which):
     from dolfinx_external_operator_amd.operand_eval import DeviceCSR
 
     torch = _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which, precision="fp32")
+    A, amg = _case_hierarchy(ctx, meshes, which, precision="fp32")
     r = _cuda(np.random.Generator(np.random.PCG64(3)).normal(size=A.shape[0]))
     z = amg.apply(r).clone()
     A2 = DeviceCSR(A.pattern, 2.0 * A.values)
@@ -138,10 +133,10 @@ def test_a_setup_refreshes_the_copies(ctx, meshes, which):
 @pytest.mark.parametrize("which", ["heat48", "hex_bar", "heat48_cheby"])
 def test_reproducibility(ctx, meshes, which):
     torch = _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which, precision="fp32")
+    A, amg = _case_hierarchy(ctx, meshes, which, precision="fp32")
     r = _cuda(np.random.Generator(np.random.PCG64(1)).normal(size=A.shape[0]))
     z32 = amg.apply(r).clone()
-    _, twin = _hierarchy(ctx, meshes, which, precision="fp32")
+    _, twin = _case_hierarchy(ctx, meshes, which, precision="fp32")
     assert torch.equal(twin.apply(r), z32)                                         # two objects built alike
     amg.setup()
     assert torch.equal(amg.apply(r), z32)                                          # two setups of one object
@@ -165,7 +160,7 @@ def test_reproducibility(ctx, meshes, which):
 def test_errors(ctx, meshes, hip_library):
     torch = _torch(ctx)
     lib, h = hip_library, ctx._h
-    A, amg = _hierarchy(ctx, meshes, "heat48")
+    A, amg = _case_hierarchy(ctx, meshes, "heat48")
     r = _cuda(np.random.Generator(np.random.PCG64(1)).normal(size=A.shape[0]))
     z = amg.apply(r).clone()
     for bad in ("fp16", "FP32", None, 32):
@@ -197,13 +192,12 @@ def test_errors(ctx, meshes, hip_library):
     amg.apply(r)                                                                   # still ready: the refused call changed nothing
     assert torch.equal(amg.set_cycle("V").apply(r), z)
     with pytest.raises(ValueError, match="DXO_E_OPTION.*dxo_amg_set_cycle"):
-        _hierarchy(ctx, meshes, "heat48", cycle="K", precision="fp32")
+        _case_hierarchy(ctx, meshes, "heat48", cycle="K", precision="fp32")
     assert torch.equal(amg.set_precision("fp32").setup().apply(r), z32)
 
 
 def _scaled(ctx, meshes, scale):
     from dolfinx_external_operator_amd.operand_eval import DeviceCSR
-    from test_amg_kcycle_gpu import _heat
 
     A, bcs = _heat(ctx, meshes, 48)
     return DeviceCSR(A.pattern, scale * A.values), bcs

@@ -1,7 +1,7 @@
-"""NumPy oracle of the single-precision multigrid cycle (dxo_amg_set_precision with DXO_AMG_PRECISION_FP32), built on the oracles of
-test_fgmres_kcycle_oracle_cpu.py (imported, not edited), and what it promises (not gpu).
+"""NumPy oracle of the single-precision multigrid cycle (dxo_amg_set_precision with DXO_AMG_PRECISION_FP32), cycle_ref of
+oracle/amg_oracle.py with precision="fp32", and what it promises (not gpu).
 
-vcycle_f32_ref is the walk of vcycle_any_ref with A, Dinv, P and every vector of every level but the coarsest in numpy.float32, for the
+It is the walk of the float64 cycle with A, Dinv, P and every vector of every level but the coarsest in numpy.float32, for the
 Jacobi sweeps and for the Chebyshev polynomial; omega and the Chebyshev pairs are made in double and narrowed once; the coarsest level
 widens its right-hand side, multiplies by the float64 dense inverse and narrows the result. The hierarchy itself (Dinv, omega, rho, P,
 the coarse matrices, the dense inverse) is the float64 one: only the cycle is narrowed, as on the device.
@@ -20,11 +20,10 @@ import copy
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
-from test_amg_cheby_oracle_cpu import cheby_pairs
-from test_amg_oracle_cpu import apply_block
-from test_fgmres_kcycle_oracle_cpu import fgmres_ref, system, vcycle_any_ref
+from oracle.amg_oracle import cycle_ref
+from oracle.krylov_oracle import fgmres_ref
+from solver_cases import system
 
 SYSTEMS = ["heat", "heat48", "p2_rbm", "nonsym", "aniso"]
 # |z32 - z64| / |z64| of one cycle. Below: a float32 walk that silently ran in float64 would differ by rounding of the final cast
@@ -32,51 +31,11 @@ SYSTEMS = ["heat", "heat48", "p2_rbm", "nonsym", "aniso"]
 # at most some tens of terms, each a few 6e-8 relative to its terms; 1e-5 is two orders over that roundoff.
 F32_LOW, F32_HIGH = 1e-9, 1e-5
 
-_F32 = {}      # id(level) -> (level, A, Dinv, P, P^T) in float32: the levels themselves stay untouched
-
-
-def _narrowed(L):
-    hit = _F32.get(id(L))
-    if hit is None or hit[0] is not L:
-        P = sp.csr_matrix(L.P).astype(np.float32)
-        hit = _F32[id(L)] = (L, sp.csr_matrix(L.A).astype(np.float32), np.asarray(L.Dinv).astype(np.float32), P, sp.csr_matrix(P.T))
-    return hit[1:]
-
-
-def smooth_f32_ref(L, r, x=None):
-    """smooth_ref of test_fgmres_kcycle_oracle_cpu.py in float32: the coefficients are made in double and narrowed once."""
-    A, Dinv, _, _ = _narrowed(L)
-    x = np.zeros_like(r) if x is None else x
-    if getattr(L, "smoother", "jacobi") == "chebyshev":
-        d = np.zeros_like(r)
-        for c1, c2 in cheby_pairs(L.rho, L.lower, L.degree):
-            d = np.float32(c1) * d + np.float32(c2) * apply_block(Dinv, r - A @ x)
-            x = x + d
-        return x
-    om = np.float32(L.omega)
-    for _ in range(L.sweeps):
-        x = x + om * apply_block(Dinv, r - A @ x)
-    return x
-
-
-def vcycle_f32_ref(levels, r, l=0):
-    """z = V(r) with the cycle in float32 and the coarsest level in float64; r is narrowed on entry, the result is float32."""
-    L = levels[l]
-    r = np.asarray(r).astype(np.float32)
-    if l == len(levels) - 1:
-        return (L.dense_inverse @ r.astype(np.float64)).astype(np.float32)
-    _, _, P, PT = _narrowed(L)
-    x = smooth_f32_ref(L, r)
-    x = x + P @ vcycle_f32_ref(levels, PT @ (r - _narrowed(L)[0] @ x), l + 1)
-    x = smooth_f32_ref(L, r, x)
-    assert x.dtype == np.float32, x.dtype
-    return x
-
 
 def f32_deviation(levels, r):
     """(|z32 - z64| / |z64|, z32, z64) of one cycle on r."""
-    z64 = vcycle_any_ref(levels, r)
-    z32 = vcycle_f32_ref(levels, r)
+    z64 = cycle_ref(levels, r)
+    z32 = cycle_ref(levels, r, precision="fp32")
     return np.linalg.norm(z32.astype(np.float64) - z64) / np.linalg.norm(z64), z32, z64
 
 
@@ -91,7 +50,7 @@ def test_the_float32_walk_is_float32_and_close_to_the_float64_walk(which):
         assert z32.dtype == np.float32 and z64.dtype == np.float64 and np.isfinite(z32).all()
         assert F32_LOW < e < F32_HIGH, (which, e)
         seen.append(e)
-    assert not vcycle_f32_ref(levels, np.zeros(S.shape[0])).any()
+    assert not cycle_ref(levels, np.zeros(S.shape[0]), precision="fp32").any()
     print(f"{which}: rows {S.shape[0]} / {len(levels)} levels, |z32 - z64| / |z64| {max(seen):.2e}")
 
 
@@ -112,8 +71,8 @@ def test_fgmres_takes_the_float32_cycle(which):
     """FGMRES(30) to rtol 1e-10 converges on the true residual (fgmres_ref recomputes b - A x in float64 at every restart) with the
     float32 walk as M, in the iterations of the float64 walk +- 2 (equal on all five when this was written)."""
     S, b, levels = system(which)
-    out64 = fgmres_ref(S, b, M=lambda r, j: vcycle_any_ref(levels, r), m=30, rtol=1e-10, maxiter=2000)
-    out32 = fgmres_ref(S, b, M=lambda r, j: vcycle_f32_ref(levels, r).astype(np.float64), m=30, rtol=1e-10, maxiter=2000)
+    out64 = fgmres_ref(S, b, M=lambda r, j: cycle_ref(levels, r), m=30, rtol=1e-10, maxiter=2000)
+    out32 = fgmres_ref(S, b, M=lambda r, j: cycle_ref(levels, r, precision="fp32").astype(np.float64), m=30, rtol=1e-10, maxiter=2000)
     (x64, its64, conv64, res64), (x32, its32, conv32, res32) = out64[:4], out32[:4]
     print(f"{which}: FGMRES(30) iterations fp64 / fp32 cycle {its64} / {its32}, true residuals {res64:.5e} / {res32:.5e}")
     assert conv64 and conv32

@@ -4,79 +4,16 @@ graph, K -> V, two levels), the guards, and the Krylov methods that take it and 
 import numpy as np
 import pytest
 
-from test_amg_gpu import _system
-from test_amg_nns_gpu import _nns_system
-from test_amg_oracle_cpu import Level
-from test_amg_soc_gpu import _aniso
-from test_assemble_oracle_cpu import heat_setting
-from test_bilinear_gpu import _cuda
-from test_fgmres_kcycle_oracle_cpu import fgmres_with_kcycle, k_visits, kcycle_ref, vcycle_any_ref
-from test_krylov_gpu import _assemble, _torch, meshes  # noqa: F401  (meshes is a fixture)
-from test_krylov_oracle_cpu import boundary_dofs
+from oracle.amg_oracle import cycle_ref, fgmres_with_cycle, k_visits
+from solver_cases import (CASES, K_CYCLE_TOL, _assembled_system, _case_hierarchy, _cuda, _device_levels, _torch,
+                          meshes)  # noqa: F401  (meshes is a fixture)
 
 pytestmark = pytest.mark.gpu
-
-# which -> (levels, block sizes): a scalar P1 system of 2401 rows on four levels (a K solve calls a K solve), P2 triangles 14 x 14
-# eps/eps with rigid-body modes, the 32 x 3 x 3 hexahedron bar, Chebyshev degree 2 on the power estimate, strength of connection 0.25
-CASES = {"heat48": (4, [1, 1, 1, 1]), "p2_rbm": (3, [2, 3, 3]), "hex_bar": (3, [3, 6, 6]), "heat48_cheby": (4, [1, 1, 1, 1]),
-         "aniso_soc": (4, [1, 1, 1, 1])}
-# The K-cycle against kcycle_ref on the device's own levels, relative to |z|. Not derivable: the coefficients divide by rho1 and
-# rho2, sums that the device adds in another order. The rule is 100 x the largest K_CYCLE_SEEN the first test prints on an MI355X
-# (the rule of CYCLE_TOL in test_amg_gpu.py). Measured on an MI355X with the ratio form of the coefficients: heat48 5.2e-16,
-# heat48_cheby 8.6e-16, aniso_soc 1.3e-15, p2_rbm 5.2e-15, hex_bar 4.5e-14 (4.471e-14). That is more than the V-cycle's 2e-13 that
-# stood here before the first run, and it comes from hex_bar alone: on the hierarchies with rigid-body modes the V-cycle itself is
-# up to 1.3e-14 |z| from its oracle (test_amg_nns_gpu.py; rows of 6 x 6 blocks summed in another order), the K solve of level 1
-# runs that body twice, the second time on r1 = r - alpha1 v1, which is smaller than its two terms, so what the first body deviates
-# by arrives magnified by |r| / |r1|, and x1 = alpha1 - (g / rho1) x2 is a difference again
-K_CYCLE_TOL = 4.5e-12
-
-
-def _heat(ctx, meshes, nx):
-    m, dqdT, dqds, _ = heat_setting(nx)
-    Cb = np.concatenate([dqdT[..., None], dqds], axis=-1).reshape(m.num_cells * m.nq, 2, 3)
-    bcs = boundary_dofs(m, 1)
-    return _assemble(ctx, meshes(m), "grad", "value_grad", 1, -Cb, bcs=bcs), bcs
-
-
-def _case_system(ctx, meshes, which):
-    """(DeviceCSR, constrained dofs, the keywords of its hierarchy) of a case."""
-    from dolfinx_external_operator_amd import rigid_body_modes
-
-    if which in ("heat48", "heat48_cheby"):
-        A, bcs = _heat(ctx, meshes, 48)
-        return A, bcs, dict(coarse_rows=10, **(dict(smoother="chebyshev", degree=2, rho="power") if which == "heat48_cheby" else {}))
-    if which == "aniso_soc":
-        A, bcs = _aniso(ctx, meshes, "quadrilateral")
-        return A, bcs, dict(coarse_rows=10, strength=0.25)
-    A, bs, bcs, x, _ = _nns_system(ctx, meshes, "p2_eps" if which == "p2_rbm" else "hex_bar")
-    return A, bcs, dict(coarse_rows=20 if which == "p2_rbm" else 40, near_nullspace=rigid_body_modes(x, ctx=ctx))
-
-
-def _hierarchy(ctx, meshes, which, **kw):
-    """(DeviceCSR, AMG): the hierarchy of a case with the keywords of the constructor on top (cycle=...)."""
-    A, bcs, base = _case_system(ctx, meshes, which)
-    return A, A.amg(bcs, **base, **kw)
-
-
-def _device_levels(amg):
-    """The hierarchy on the device as the Level list the oracle cycles walk."""
-    dev, rhos, sm = amg.levels, amg.rho, amg.smoother
-    levels = []
-    for l in range(amg.n_levels):
-        L = Level()
-        L.A, L.n_rows, L.bs, L.sweeps = amg.level_matrix(l), dev[l]["rows"], dev[l]["bs"], amg.sweeps
-        L.smoother, L.degree, L.lower = sm["smoother"], sm["degree"], sm["lower"]
-        if l + 1 < amg.n_levels:
-            L.Dinv, L.omega, L.rho, L.P = amg.level_dinv(l), dev[l]["omega"], rhos[l], amg.prolongator(l).tocsr()
-        levels.append(L)
-    levels[-1].dense_inverse = np.linalg.inv(levels[-1].A.toarray())
-    return levels
-
 
 @pytest.mark.parametrize("which", list(CASES))
 def test_k_cycle_matches_the_oracle_on_the_device_levels(ctx, meshes, which):
     torch = _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which, cycle="K")
+    A, amg = _case_hierarchy(ctx, meshes, which, cycle="K")
     n_levels, sizes = CASES[which]
     assert amg.n_levels == n_levels and [d["bs"] for d in amg.levels] == sizes, (which, amg.levels)
     assert amg.cycle == "K"
@@ -88,11 +25,11 @@ def test_k_cycle_matches_the_oracle_on_the_device_levels(ctx, meshes, which):
     for _ in range(3):
         r = rng.normal(size=A.shape[0])
         z = amg.apply(_cuda(r)).cpu().numpy()
-        zr = kcycle_ref(levels, r, None, visits)
+        zr = cycle_ref(levels, r, "K", visits=visits)
         assert np.isfinite(z).all()
         worst = max(worst, np.linalg.norm(z - zr) / np.linalg.norm(zr))
     assert sum(visits) == 3 * amg.visits
-    zv = vcycle_any_ref(levels, r)
+    zv = cycle_ref(levels, r)
     print(f"{which}: K_CYCLE_SEEN {worst:.3e} |z| (K against V on this right-hand side: {np.linalg.norm(zr - zv) / np.linalg.norm(zv):.3e})")
     assert worst <= K_CYCLE_TOL, (which, worst)
     buf = _cuda(r)
@@ -107,7 +44,7 @@ def test_k_cycle_matches_the_oracle_on_the_device_levels(ctx, meshes, which):
 @pytest.mark.parametrize("which", ["heat48", "hex_bar", "heat48_cheby"])
 def test_bit_identity(ctx, meshes, which):
     torch = _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which)
+    A, amg = _case_hierarchy(ctx, meshes, which)
     assert amg.cycle == "V" and amg.visits == amg.n_levels
     r = _cuda(np.random.Generator(np.random.PCG64(1)).normal(size=A.shape[0]))
     z_v = amg.apply(r).clone()
@@ -116,7 +53,7 @@ def test_bit_identity(ctx, meshes, which):
     assert not torch.equal(z_k, z_v)
     for _ in range(2):
         assert torch.equal(amg.apply(r), z_k)                                     # two applies
-    _, fresh = _hierarchy(ctx, meshes, which, cycle="K")
+    _, fresh = _case_hierarchy(ctx, meshes, which, cycle="K")
     assert torch.equal(fresh.apply(r), z_k)                                       # set at creation or afterwards
     z = torch.zeros_like(r)
     s = torch.cuda.Stream()
@@ -137,13 +74,13 @@ def test_bit_identity(ctx, meshes, which):
     assert amg.cycle == "K" and torch.equal(amg.apply(r), z_k)                    # a setup keeps the cycle
     amg.set_cycle("V")
     assert amg.cycle == "V" and torch.equal(amg.apply(r), z_v)                    # and back: the default object bit for bit
-    _, default = _hierarchy(ctx, meshes, which)
+    _, default = _case_hierarchy(ctx, meshes, which)
     assert torch.equal(default.apply(r), z_v)
 
 
 def test_k_on_two_levels_and_on_one_is_v(ctx, meshes):
     torch = _torch(ctx)
-    A, bs, bcs = _system(ctx, meshes, "heat")
+    A, bs, bcs = _assembled_system(ctx, meshes, "heat")
     r = _cuda(np.random.Generator(np.random.PCG64(2)).normal(size=A.shape[0]))
     for coarse_rows, n_levels in ((60, 2), (400, 1)):
         v, k = A.amg(bcs, coarse_rows=coarse_rows), A.amg(bcs, coarse_rows=coarse_rows, cycle="K")
@@ -156,7 +93,7 @@ def test_krylov_methods_take_it_or_refuse_it(ctx, meshes, which):
     from dolfinx_external_operator_amd import cg, fgmres, gmres
 
     _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which, cycle="K")
+    A, amg = _case_hierarchy(ctx, meshes, which, cycle="K")
     S = A.to_scipy()
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
     bd = _cuda(b)
@@ -164,7 +101,7 @@ def test_krylov_methods_take_it_or_refuse_it(ctx, meshes, which):
         with pytest.raises(ValueError, match="DXO_E_OPTION.*K-cycle"):
             solve(A, bd, M=amg)
     out = fgmres(A, bd, M=amg, restart=30, rtol=1e-8)
-    _, its, conv, *_ = fgmres_with_kcycle(S, b, _device_levels(amg), m=30, rtol=1e-8)
+    _, its, conv, *_ = fgmres_with_cycle(S, b, _device_levels(amg), "K", m=30, rtol=1e-8)
     v = gmres(A, bd, M=amg.set_cycle("V"), restart=30, rtol=1e-8)                 # the same object, as a V-cycle again
     print(f"{which}: FGMRES(30) + K {out.iterations} iterations (oracle {its}) x {k_visits(amg.n_levels)} visits, "
           f"GMRES(30) + V {v.iterations} x {amg.n_levels}")
@@ -177,7 +114,7 @@ def test_errors(ctx, meshes, hip_library):
     import ctypes as C
 
     lib, h = hip_library, ctx._h
-    A, bs, bcs = _system(ctx, meshes, "heat")
+    A, bs, bcs = _assembled_system(ctx, meshes, "heat")
     amg = A.amg(bcs, coarse_rows=10)
     for bad in ("W", "k", None):
         with pytest.raises(ValueError, match="AMG: cycle"):

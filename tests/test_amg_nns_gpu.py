@@ -9,13 +9,10 @@ import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg
 
-from test_amg_gpu import _same_csr, _system
-from test_amg_nns_oracle_cpu import (amg_nns_ref, check_tentative, dead_case, elastic_C3, rigid_body_modes_ref, tentative_nns_ref)
-from test_amg_oracle_cpu import (U, block_diag, cg_with_cycle, forward_bound, gmres_with_cycle, operator_complexity, prolongator_ref,
-                                 rho_ref, vcycle_ref)
-from test_bilinear_gpu import _cuda
-from test_krylov_gpu import _assemble, _torch, meshes  # noqa: F401  (meshes is a fixture)
-from test_krylov_oracle_cpu import block_jacobi_ref, bottom_dofs, elastic_C
+from oracle.amg_oracle import (U, amg_ref, block_diag, cg_with_cycle, check_tentative, cycle_ref, forward_bound, gmres_with_cycle,
+                               operator_complexity, prolongator_ref, rho_ref, rigid_body_modes_ref, same_csr, tentative_nns_ref)
+from oracle.krylov_oracle import block_jacobi_ref, bottom_dofs, elastic_C
+from solver_cases import _assemble, _cuda, _nns_system, _torch, meshes  # noqa: F401  (meshes is a fixture)
 from tools.synthetic import structured_mesh
 
 pytestmark = pytest.mark.gpu
@@ -31,23 +28,6 @@ QR_TOL = 5e-14
 # the cycle against the oracle cycle, relative to |z|; the same run: 1.3e-14 (p2_eps), 5.0e-15 (hyperelastic), 2.0e-15 (hex_eps),
 # 2.6e-16 (dead). 100 x the largest (the rule of CYCLE_TOL in test_amg_gpu.py).
 CYCLE_TOL = 1.4e-12
-
-
-def _nns_system(ctx, meshes, which):
-    """(DeviceCSR, bs, constrained dofs, node coordinates, SPD?)"""
-    if which == "p2_eps":
-        m = structured_mesh("triangle", (14, 14), 2, distort=0.15, seed=5)
-        bcs = bottom_dofs(m, 2)
-        return _assemble(ctx, meshes(m), "eps", "eps", 2, elastic_C(m), bcs=bcs), 2, bcs, m.node_x, True
-    if which == "hyperelastic":
-        A, bs, bcs = _system(ctx, meshes, "hyperelastic")
-        return A, bs, bcs, structured_mesh("triangle", (10, 10), 2, distort=0.1, seed=3).node_x, False
-    if which in ("hex_eps", "hex_bar"):      # the bar: 22 nodes and 3 aggregates on the level of block size 6 (the cube: 8 and 1)
-        m = structured_mesh("hexahedron", (4, 4, 4) if which == "hex_eps" else (32, 3, 3), 1, distort=0.1, seed=2)
-        bcs = bottom_dofs(m, 3)
-        return _assemble(ctx, meshes(m), "eps", "eps", 3, elastic_C3(m.num_cells * m.nq), bcs=bcs), 3, bcs, m.node_x, True
-    m, _, bcs = dead_case()
-    return _assemble(ctx, meshes(m), "eps", "eps", 2, elastic_C(m), bcs=bcs), 2, bcs, m.node_x, True
 
 
 def _hierarchy(ctx, A, bcs, x, **kw):
@@ -83,7 +63,7 @@ def test_hierarchy_and_cycle_match_the_oracle(ctx, meshes, which):
     amg, Bd, coarse_rows = _hierarchy(ctx, A, bcs, x)
     B0 = Bd.cpu().numpy()
     assert np.array_equal(B0, rigid_body_modes_ref(x))
-    ref = amg_nns_ref(S, bs, bcs, B0, coarse_rows=coarse_rows)
+    ref = amg_ref(S, bs, bcs, near_nullspace=B0, coarse_rows=coarse_rows)
     dev = amg.levels
     assert amg.n_levels == len(ref) >= 3, (which, amg.n_levels, len(ref))          # so level 1 (block size k) smooths and transfers
     if which == "hex_bar":
@@ -166,7 +146,7 @@ def test_hierarchy_and_cycle_match_the_oracle(ctx, meshes, which):
     for _ in range(3):
         r = rng.normal(size=S.shape[0])
         z = amg.apply(_cuda(r)).cpu().numpy()
-        zr = vcycle_ref(ref, r)
+        zr = cycle_ref(ref, r)
         assert np.isfinite(z).all()
         worst = max(worst, np.linalg.norm(z - zr) / np.linalg.norm(zr))
     print(f"{which}: CYCLE_SEEN {worst:.3e} |z|")
@@ -175,8 +155,8 @@ def test_hierarchy_and_cycle_match_the_oracle(ctx, meshes, which):
     amg.apply(buf, out=buf)                                                      # r may be z
     assert np.array_equal(buf.cpu().numpy(), z)
     two, _, _ = _hierarchy(ctx, A, bcs, x, sweeps=2, coarse_rows=coarse_rows)
-    ref2 = amg_nns_ref(S, bs, bcs, B0, coarse_rows=coarse_rows, sweeps=2)
-    z2, zr2 = two.apply(_cuda(r)).cpu().numpy(), vcycle_ref(ref2, r)
+    ref2 = amg_ref(S, bs, bcs, near_nullspace=B0, coarse_rows=coarse_rows, sweeps=2)
+    z2, zr2 = two.apply(_cuda(r)).cpu().numpy(), cycle_ref(ref2, r)
     assert np.linalg.norm(z2 - zr2) <= CYCLE_TOL * np.linalg.norm(zr2)
     if which == "dead":
         from dolfinx_external_operator_amd import cg
@@ -197,7 +177,7 @@ def test_iteration_counts_match_the_oracle_and_beat_the_translations(ctx, meshes
     xref = scipy.sparse.linalg.spsolve(S.tocsc(), b)
     amg, Bd, coarse_rows = _hierarchy(ctx, A, bcs, x)
     plain = A.amg(bcs, coarse_rows=coarse_rows)
-    levels = amg_nns_ref(S, bs, bcs, Bd.cpu().numpy(), coarse_rows=coarse_rows)
+    levels = amg_ref(S, bs, bcs, near_nullspace=Bd.cpu().numpy(), coarse_rows=coarse_rows)
     if spd:
         out = cg(A, _cuda(b), M=amg, rtol=1e-10, maxiter=5000)
         old = cg(A, _cuda(b), M=plain, rtol=1e-10, maxiter=5000)
@@ -229,9 +209,9 @@ def test_bit_reproducible_capture_safe_and_setup_keeps_t(ctx, meshes):
                 [d["omega"] for d in a.levels])
 
     def same(p, q):
-        return (all(_same_csr(a, b) for a, b in zip(p[0], q[0]))
+        return (all(same_csr(a, b) for a, b in zip(p[0], q[0]))
                 and all(np.array_equal(a.data, b.data) and np.array_equal(a.indices, b.indices) for a, b in zip(p[1], q[1]))
-                and all(_same_csr(a, b) for a, b in zip(p[2], q[2])) and all(np.array_equal(a, b) for a, b in zip(p[3], q[3]))
+                and all(same_csr(a, b) for a, b in zip(p[2], q[2])) and all(np.array_equal(a, b) for a, b in zip(p[3], q[3]))
                 and p[4] == q[4])
 
     first = snapshot(amg)
@@ -267,8 +247,8 @@ def test_bit_reproducible_capture_safe_and_setup_keeps_t(ctx, meshes):
     fresh, _, _ = _hierarchy(ctx, Bm, bcs, m.node_x)
     now, new = snapshot(amg), snapshot(fresh)
     assert same(now, new)
-    assert all(_same_csr(a, b) for a, b in zip(first[2], now[2])) and all(np.array_equal(a, b) for a, b in zip(first[3], now[3]))
-    assert not all(_same_csr(a, b) for a, b in zip(first[0], now[0]))
+    assert all(same_csr(a, b) for a, b in zip(first[2], now[2])) and all(np.array_equal(a, b) for a, b in zip(first[3], now[3]))
+    assert not all(same_csr(a, b) for a, b in zip(first[0], now[0]))
     after = amg.apply(r)
     assert torch.equal(after, fresh.apply(r)) and not torch.equal(after, z_first)
 

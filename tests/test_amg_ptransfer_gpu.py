@@ -8,19 +8,12 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from test_amg_cheby_oracle_cpu import cg_with_cheby, gmres_with_cheby, vcycle_cheby_ref
-from test_amg_fp32_gpu import NOT_DOUBLE, SAME_FORMULAS
-from test_amg_fp32_oracle_cpu import vcycle_f32_ref
-from test_amg_gpu import CYCLE_TOL, _same_csr
-from test_amg_kcycle_gpu import K_CYCLE_TOL, _device_levels
-from test_amg_nns_oracle_cpu import elastic_C3
-from test_amg_oracle_cpu import U, forward_bound, operator_complexity
-from test_amg_ptransfer_oracle_cpu import COARSE_ROWS, amg_p_ref, p_diag_ref, vertex_transfer_ref
-from test_assemble_oracle_cpu import apply_bcs, dense_ref
-from test_bilinear_gpu import _cuda
-from test_fgmres_kcycle_oracle_cpu import kcycle_ref, vcycle_any_ref
-from test_krylov_gpu import _assemble, _torch, meshes  # noqa: F401  (meshes is a fixture)
-from test_krylov_oracle_cpu import bottom_dofs, elastic_C, to_pattern_csr
+from oracle.amg_oracle import (amg_ref, cg_with_cycle, cycle_ref, forward_bound, gmres_with_cycle, operator_complexity, p_diag_ref,
+                               same_csr, vertex_transfer_ref)
+from oracle.form_oracle import apply_bcs, dense_ref
+from oracle.krylov_oracle import bottom_dofs, elastic_C, elastic_C3, to_pattern_csr
+from solver_cases import (COARSE_ROWS, CYCLE_TOL, K_CYCLE_TOL, NOT_DOUBLE, SAME_FORMULAS, _assemble, _cuda, _device_levels, _torch,
+                          meshes)  # noqa: F401  (meshes is a fixture)
 from tools.synthetic import coordinate_element_at_nodes, gauss_tensor_rule, structured_mesh, with_rule
 
 pytestmark = pytest.mark.gpu
@@ -102,7 +95,7 @@ def test_hierarchy_matches_the_oracle(ctx, meshes, which):
     assert np.array_equal(t.w, W.data) and np.array_equal(t.coarse_to_fine, ctf)
     S = A.to_scipy()
     amg = A.amg(dofs, coarse_rows=COARSE_ROWS, first_transfer=t)
-    ref = amg_p_ref(S, bs, dofs, W, ctf, coarse_rows=COARSE_ROWS)
+    ref = amg_ref(S, bs, dofs, first_transfer=(W, ctf), coarse_rows=COARSE_ROWS)
     info = amg.first_transfer
     mask = np.zeros(S.shape[0], dtype=bool)
     mask[dofs] = True
@@ -150,7 +143,7 @@ def test_cycle_matches_the_oracle(ctx, meshes, which, variant, rbm):
     m, dm, A, bs, dofs, t, W, ctf = _system(ctx, meshes, which)
     kw, okw = _kw(ctx, m, variant, rbm)
     amg = A.amg(dofs, first_transfer=t, **kw)
-    ref = amg_p_ref(A.to_scipy(), bs, dofs, W, ctf, **okw)
+    ref = amg_ref(A.to_scipy(), bs, dofs, first_transfer=(W, ctf), **okw)
     assert [d["rows"] for d in amg.levels] == [L.n_rows for L in ref]
     if rbm:
         assert np.array_equal(amg.near_nullspace(1), ref[1].B)                     # the rows of the zeroed B_0 at the coarse nodes
@@ -159,7 +152,7 @@ def test_cycle_matches_the_oracle(ctx, meshes, which, variant, rbm):
     for _ in range(3):
         r = rng.normal(size=A.shape[0])
         z = amg.apply(_cuda(r)).cpu().numpy()
-        zr = vcycle_cheby_ref(ref, r)
+        zr = cycle_ref(ref, r)
         worst = max(worst, np.linalg.norm(z - zr) / np.linalg.norm(zr))
     print(f"{which} {variant} rbm={rbm}: cycle deviation from the oracle {worst:.3e} |z|")
     assert worst <= CYCLE_TOL, (which, variant, rbm, worst)
@@ -177,16 +170,16 @@ def test_iteration_counts_follow_the_oracle(ctx, meshes, which):
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
     amg = A.amg(dofs, coarse_rows=COARSE_ROWS, first_transfer=t)
     plain = A.amg(dofs, coarse_rows=COARSE_ROWS)
-    ref = amg_p_ref(S, bs, dofs, W, ctf, coarse_rows=COARSE_ROWS)
+    ref = amg_ref(S, bs, dofs, first_transfer=(W, ctf), coarse_rows=COARSE_ROWS)
     out = cg(A, _cuda(b), M=amg, rtol=1e-8, maxiter=600)
-    _, its, conv = cg_with_cheby(S, b, ref, rtol=1e-8, maxiter=600)
+    _, its, conv = cg_with_cycle(S, b, ref, rtol=1e-8, maxiter=600)
     out_plain = cg(A, _cuda(b), M=plain, rtol=1e-8, maxiter=600)
     print(f"{which}: CG iterations with the p level {out.iterations} (oracle {its}), plain hierarchy {out_plain.iterations}")
     assert out.converged and conv and abs(out.iterations - its) <= 2, (which, out.iterations, its)
     assert np.linalg.norm(b - S @ out.x.cpu().numpy()) <= 1.01e-8 * np.linalg.norm(b)
     if which in ("tri65", "tri88_scalar"):
         g = gmres(A, _cuda(b), M=amg, restart=30, rtol=1e-8, maxiter=600)
-        _, gits, gconv, _ = gmres_with_cheby(S, b, ref, m=30, rtol=1e-8, maxiter=600)
+        _, gits, gconv, _ = gmres_with_cycle(S, b, ref, m=30, rtol=1e-8, maxiter=600)
         print(f"{which}: GMRES(30) iterations with the p level {g.iterations} (oracle {gits})")
         assert g.converged and gconv and abs(g.iterations - gits) <= 2, (which, g.iterations, gits)
 
@@ -202,7 +195,7 @@ def test_bit_identity_and_frozen_weights(ctx, meshes, which):
         return [a.level_matrix(l) for l in range(a.n_levels)], [a.prolongator(l) for l in range(a.n_levels - 1)], [d["omega"] for d in a.levels]
 
     first, other = snapshot(amg), snapshot(twin)
-    assert all(_same_csr(a, b) for a, b in zip(first[0], other[0])) and first[2] == other[2]          # two creations
+    assert all(same_csr(a, b) for a, b in zip(first[0], other[0])) and first[2] == other[2]          # two creations
     assert all(np.array_equal(a.data, b.data) for a, b in zip(first[1], other[1]))
     pd = amg.first_transfer["p_diag"].clone()
     r = _cuda(np.random.Generator(np.random.PCG64(1)).normal(size=A.shape[0]))
@@ -212,11 +205,11 @@ def test_bit_identity_and_frozen_weights(ctx, meshes, which):
     A.values.mul_(3.0)
     amg.setup()
     assert torch.equal(amg.first_transfer["p_diag"], pd)                           # setup() leaves the weights alone
-    assert not _same_csr(amg.level_matrix(1), first[0][1])
+    assert not same_csr(amg.level_matrix(1), first[0][1])
     A.values.copy_(keep)
     amg.setup()
     again = snapshot(amg)
-    assert all(_same_csr(a, b) for a, b in zip(first[0], again[0])) and first[2] == again[2]          # two setups
+    assert all(same_csr(a, b) for a, b in zip(first[0], again[0])) and first[2] == again[2]          # two setups
     assert torch.equal(amg.first_transfer["p_diag"], pd) and torch.equal(amg.apply(r), z_first)
     z = torch.zeros_like(r)
     s = torch.cuda.Stream()
@@ -256,7 +249,7 @@ def _assert_levels_below_are(amg, direct):
     assert amg.n_levels == direct.n_levels + 1
     dev, ddev, rho, drho = amg.levels, direct.levels, amg.rho, direct.rho
     for l in range(direct.n_levels):
-        assert _same_csr(amg.level_matrix(l + 1), direct.level_matrix(l)), l
+        assert same_csr(amg.level_matrix(l + 1), direct.level_matrix(l)), l
         assert dev[l + 1]["omega"] == ddev[l]["omega"] and rho[l + 1] == drho[l] and dev[l + 1]["bs"] == ddev[l]["bs"]
         if l + 1 < direct.n_levels:
             assert np.array_equal(amg.aggregates(l + 1), direct.aggregates(l))
@@ -329,8 +322,8 @@ def test_fp32_cycle_against_the_float32_oracle(ctx, meshes, which):
         zd = amg.apply(_cuda(r))
         assert zd.dtype == torch.float64
         z_dev = zd.cpu().numpy()
-        z64 = vcycle_any_ref(levels, r)
-        z32 = vcycle_f32_ref(levels, r).astype(np.float64)
+        z64 = cycle_ref(levels, r)
+        z32 = cycle_ref(levels, r, precision="fp32").astype(np.float64)
         e_ref = np.linalg.norm(z32 - z64) / np.linalg.norm(z64)
         e_dev = np.linalg.norm(z_dev - z64) / np.linalg.norm(z64)
         print(f"{which}: FP32_SEEN e_dev / e_ref {e_dev / e_ref:.3f} (e_dev {e_dev:.3e}, e_ref {e_ref:.3e})")
@@ -350,7 +343,7 @@ def test_k_cycle_on_a_p_hierarchy(ctx, meshes):
     levels = _device_levels(amg)
     r = np.random.Generator(np.random.PCG64(12)).normal(size=A.shape[0])
     z = amg.apply(_cuda(r))
-    zr = kcycle_ref(levels, r)
+    zr = cycle_ref(levels, r, "K")
     dev = np.linalg.norm(z.cpu().numpy() - zr) / np.linalg.norm(zr)
     print(f"hex333: K_CYCLE_SEEN {dev:.3e} |z|")
     assert dev <= K_CYCLE_TOL

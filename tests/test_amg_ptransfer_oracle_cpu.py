@@ -1,11 +1,10 @@
 """The NumPy / SciPy yardstick of dxo_amg_create_transfer (csrc/amg.hip): a p-coarsening first level for quadratic elements.
 
 vertex_transfer_ref is the nodal interpolation W from the degree-1 space on the same cells, cell by cell from the two dofmaps and the
-coordinate element tabulated at the field element's nodes. amg_p_ref is the hierarchy: level 0 keeps Dinv, rho and omega of a level of
-test_amg_oracle_cpu.py; its P is kron(W, I_bs) with the rows of constrained fine dofs and the columns of the coarse dofs constrained at
-their own node zero; A_1 = P^T A P on the symbolic pattern of the product; the levels below are amg_ref / amg_nns_ref / amg_cheby_ref of
-A_1 with the constraints of the coarse nodes (and the rows of the zeroed B at those nodes). The level objects carry what vcycle_ref and
-vcycle_cheby_ref read, so the cycle is those functions.
+coordinate element tabulated at the field element's nodes. amg_ref(first_transfer=(W, coarse_to_fine)) is the hierarchy: level 0 keeps
+Dinv, rho and omega of any level; its P is kron(W, I_bs) with the rows of constrained fine dofs and the columns of the coarse dofs
+constrained at their own node zero; A_1 = P^T A P on the symbolic pattern of the product; the levels below are the hierarchy of A_1
+with the constraints of the coarse nodes (and the rows of the zeroed B at those nodes). Both are in oracle/amg_oracle.py.
 
 The iteration counts pinned here are the experiment the feature was specified with: CG to rtol 1e-8 on eps / eps isotropic elasticity,
 bottom clamped, distort 0.1, seed 2, coarse_rows 60, a PCG64(1) normal right-hand side."""
@@ -13,88 +12,12 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import test_amg_oracle_cpu as amg_oracle
-from test_amg_cheby_oracle_cpu import amg_cheby_ref, cg_with_cheby, rho_source
-from test_amg_nns_oracle_cpu import elastic_C3, rigid_body_modes_ref
-from test_amg_oracle_cpu import (Level, _ones, active_nodes, coarse_ref, expand_pattern, node_graph, on_pattern, operator_complexity)
-from test_assemble_oracle_cpu import apply_bcs, dense_ref, pattern_ref
-from test_krylov_oracle_cpu import block_jacobi_ref, bottom_dofs, cg_ref, elastic_C, to_pattern_csr
+from oracle.amg_oracle import (amg_ref, cg_with_cycle, expand_pattern, node_graph, operator_complexity, power_rho_ref,
+                               rigid_body_modes_ref, transfer_patterns, vertex_transfer_ref)
+from oracle.form_oracle import apply_bcs, dense_ref, pattern_ref
+from oracle.krylov_oracle import bottom_dofs, elastic_C, elastic_C3, to_pattern_csr
+from solver_cases import COARSE_ROWS
 from tools.synthetic import coordinate_element_at_nodes, gauss_tensor_rule, structured_mesh, with_rule
-
-COARSE_ROWS = 60
-
-
-# ---- the oracle
-def vertex_transfer_ref(m):
-    """(W scipy CSR [field nodes][geometry nodes] with sorted rows, coarse_to_fine) of a SyntheticMesh, entry by entry."""
-    psi = coordinate_element_at_nodes(m.cell, m.degree)
-    n, nc = m.node_x.shape[0], m.x.shape[0]
-    rows = [dict() for _ in range(n)]
-    for cell in range(m.num_cells):
-        for a, i in enumerate(m.dofmap[cell]):
-            for v, g in enumerate(m.geom_dofmap[cell]):
-                if abs(psi[a, v]) > 1e-14:
-                    assert rows[i].setdefault(int(g), psi[a, v]) == psi[a, v]        # the cells that share a node agree
-    ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])])
-    col = np.array([g for r in rows for g in sorted(r)], dtype=np.int32)
-    w = np.array([r[g] for r in rows for g in sorted(r)])
-    W = sp.csr_matrix((w, col, ptr), shape=(n, nc))
-    ctf = -np.ones(nc, dtype=np.int64)
-    for i, r in enumerate(rows):
-        if len(r) == 1 and next(iter(r.values())) == 1.0:
-            ctf[next(iter(r))] = i
-    assert (ctf >= 0).all()
-    return W, ctf.astype(np.int32)
-
-
-def p_diag_ref(W, ctf, mask, bs):
-    """[blocks of W][bs]: w_iv keep(i, c) keep(coarse_to_fine[v], c)."""
-    keep = ~np.asarray(mask, dtype=bool).reshape(-1, bs)
-    rows = np.repeat(np.arange(W.shape[0]), np.diff(W.indptr))
-    return W.data[:, None] * keep[rows] * keep[ctf[W.indices]]
-
-
-def transfer_patterns(ptr, nb, W):
-    """Block patterns of P (that of W), A P and P^T A P + I from integer products."""
-    n = ptr.size - 1
-    G = sp.csr_matrix((np.ones(nb.size, dtype=np.int64), nb, ptr), shape=(n, n))
-    Pp = _ones(W).astype(np.int64)
-    APp = _ones(G @ Pp)
-    Cp = _ones(Pp.T @ APp + sp.identity(W.shape[1], dtype=np.int64, format="csr"))
-    for M in (Pp, APp, Cp):
-        M.sort_indices()
-    return Pp, APp, Cp
-
-
-def amg_p_ref(S, bs, constrained, W, ctf, near_nullspace=None, smoother="jacobi", degree=None, rho="inf-norm", max_levels=10,
-              coarse_rows=512, sweeps=1, **kw):
-    """The hierarchy with the p level first; the keywords of amg_cheby_ref. A matrix that is its own coarsest level: that hierarchy."""
-    opts = dict(near_nullspace=near_nullspace, smoother=smoother, degree=degree, rho=rho, coarse_rows=coarse_rows, sweeps=sweeps, **kw)
-    A = S.tocsr()
-    if A.shape[0] <= coarse_rows or max_levels <= 1:
-        return amg_cheby_ref(S, bs, constrained, max_levels=max_levels, **opts)
-    mask, _ = active_nodes(A.shape[0], bs, constrained)
-    mask1 = mask.reshape(-1, bs)[ctf].reshape(-1)
-    L = Level()
-    L.A, L.indptr, L.indices, L.bs, L.mask, L.sweeps = A, A.indptr.astype(np.int64), A.indices.astype(np.int32), bs, mask, sweeps
-    L.n_rows, L.agg, L.n_agg, L.bs_coarse = A.shape[0], None, W.shape[1], bs
-    ptr, nb = node_graph(L.indptr, L.indices, bs)
-    L.Pp, L.APp, L.Cp = transfer_patterns(ptr, nb, W)
-    L.Dinv = block_jacobi_ref(A, bs)
-    with rho_source(rho, kw.get("rho_iters", 10), kw.get("safety", 1.1)):
-        L.rho, _ = amg_oracle.rho_ref(A, L.Dinv)
-    L.omega = (4.0 / 3.0) / L.rho
-    L.p_diag = p_diag_ref(W, ctf, mask, bs)
-    L.P = sp.bsr_matrix((L.p_diag[:, :, None] * np.eye(bs)[None], W.indices, W.indptr), shape=(A.shape[0], W.shape[1] * bs)).tocsr()
-    L.smoother, L.degree, L.lower = smoother, (sweeps if degree is None else degree), kw.get("lower", 0.1)
-    cptr, cidx = expand_pattern(L.Cp, bs)
-    A1 = on_pattern(coarse_ref(A, L.P), cptr, cidx, (W.shape[1] * bs,) * 2)
-    if near_nullspace is not None:
-        B0 = np.array(near_nullspace, dtype=np.float64)
-        B0[mask] = 0.0
-        L.B = B0
-        opts["near_nullspace"] = B0.reshape(-1, bs, B0.shape[1])[ctf].reshape(-1, B0.shape[1])
-    return [L] + amg_cheby_ref(A1, bs, np.flatnonzero(mask1), max_levels=max_levels - 1, **opts)
 
 
 # ---- the systems of the experiment
@@ -149,7 +72,7 @@ def hierarchies(name, variant):
     kw = dict(VARIANTS[variant], coarse_rows=COARSE_ROWS)
     if variant == "cheby_rbm":
         kw["near_nullspace"] = rigid_body_modes_ref(m.node_x)
-    return amg_cheby_ref(S, bs, dofs, **kw), amg_p_ref(S, bs, dofs, W, ctf, **kw)
+    return amg_ref(S, bs, dofs, **kw), amg_ref(S, bs, dofs, first_transfer=(W, ctf), **kw)
 
 
 # ---- tests
@@ -221,7 +144,7 @@ def test_masked_transfer_and_level_one_constraints():
     left = np.flatnonzero(np.abs(m0.node_x[:, 0]) < 1e-12) * 2               # the horizontal component on x = 0
     m, S, dofs = elasticity("triangle", (6, 5), 2, extra=left)
     W, ctf = vertex_transfer_ref(m)
-    levels = amg_p_ref(S, 2, dofs, W, ctf, coarse_rows=COARSE_ROWS)
+    levels = amg_ref(S, 2, dofs, first_transfer=(W, ctf), coarse_rows=COARSE_ROWS)
     L0, L1 = levels[0], levels[1]
     mask = np.zeros(S.shape[0], dtype=bool)
     mask[dofs] = True
@@ -232,7 +155,7 @@ def test_masked_transfer_and_level_one_constraints():
     d = L1.A.diagonal()
     assert (d[mask1] == 1.0).all() and not abs(L1.A[np.flatnonzero(mask1)]).sum() - mask1.sum()
     assert np.array_equal(L1.mask, mask1)
-    direct = amg_oracle.amg_ref(L1.A, 2, np.flatnonzero(mask1), coarse_rows=COARSE_ROWS)
+    direct = amg_ref(L1.A, 2, np.flatnonzero(mask1), coarse_rows=COARSE_ROWS)
     assert len(direct) == len(levels) - 1
     for a, b in zip(direct, levels[1:]):
         assert np.array_equal(a.A.toarray(), b.A.toarray())
@@ -247,7 +170,7 @@ def test_masked_transfer_and_level_one_constraints():
 def test_rigid_body_modes_of_level_one_are_those_of_its_nodes():
     m, S, bs, dofs, W, ctf, _ = case("p2_tri14")
     B = rigid_body_modes_ref(m.node_x)
-    levels = amg_p_ref(S, bs, dofs, W, ctf, near_nullspace=B, coarse_rows=COARSE_ROWS)
+    levels = amg_ref(S, bs, dofs, first_transfer=(W, ctf), near_nullspace=B, coarse_rows=COARSE_ROWS)
     B1 = rigid_body_modes_ref(m.x)
     on = np.zeros(S.shape[0], dtype=bool)
     on[dofs] = True
@@ -265,7 +188,7 @@ def test_iteration_table(name, variant):
     plain, with_p = hierarchies(name, variant)
     its = []
     for levels in (plain, with_p):
-        x, n, conv = cg_with_cheby(S, b, levels, rtol=1e-8, maxiter=600)
+        x, n, conv = cg_with_cycle(S, b, levels, rtol=1e-8, maxiter=600)
         assert conv and np.linalg.norm(b - S @ x) <= 1.01e-8 * np.linalg.norm(b)
         its.append(n)
     rows = [[L.n_rows for L in h] for h in (plain, with_p)]
@@ -284,14 +207,13 @@ def test_the_p_level_gives_the_iterations_of_the_degree_one_problem():
         cell, n, bs, _ = CASES[name]
         m1, S1, dofs1 = elasticity(cell, n, bs, degree=1)
         b1 = np.random.Generator(np.random.PCG64(1)).normal(size=S1.shape[0])
-        _, its1, conv = cg_with_cheby(S1, b1, amg_cheby_ref(S1, bs, dofs1, **VARIANTS["jacobi"], coarse_rows=COARSE_ROWS), rtol=1e-8, maxiter=600)
+        _, its1, conv = cg_with_cycle(S1, b1, amg_ref(S1, bs, dofs1, **VARIANTS["jacobi"], coarse_rows=COARSE_ROWS), rtol=1e-8, maxiter=600)
         assert conv and abs(its1 - q1_its) <= 2, (name, its1)
         _, S, _, _, _, _, b = case(name)
         lv = hierarchies(name, "jacobi")[1]
-        with rho_source("power", 10, 1.1):                       # the true rho on level 0 alone
-            lv[0].rho, _ = amg_oracle.rho_ref(lv[0].A, lv[0].Dinv)
+        lv[0].rho = power_rho_ref(lv[0].A, lv[0].Dinv, 10, 1.1)  # the true rho on level 0 alone
         lv[0].omega = (4.0 / 3.0) / lv[0].rho
-        _, its2, conv = cg_with_cheby(S, b, lv, rtol=1e-8, maxiter=600)
+        _, its2, conv = cg_with_cycle(S, b, lv, rtol=1e-8, maxiter=600)
         print(f"{name}: Q1 alone {its1}, Q2 with the p level and the power rho on level 0 {its2}")
         assert conv and abs(its2 - its1) <= 3, (name, its1, its2)
 
@@ -304,12 +226,12 @@ def test_the_eight_point_rule_under_integrates_the_q2_hexahedron():
     W, ctf = vertex_transfer_ref(m8)
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S8.shape[0])
     for kw in (VARIANTS["jacobi"], VARIANTS["cheby"]):
-        for levels in (amg_cheby_ref(S8, 3, dofs, coarse_rows=COARSE_ROWS, **kw), amg_p_ref(S8, 3, dofs, W, ctf, coarse_rows=COARSE_ROWS, **kw)):
-            _, its, conv = cg_with_cheby(S8, b, levels, rtol=1e-8, maxiter=600)
+        for levels in (amg_ref(S8, 3, dofs, coarse_rows=COARSE_ROWS, **kw), amg_ref(S8, 3, dofs, first_transfer=(W, ctf), coarse_rows=COARSE_ROWS, **kw)):
+            _, its, conv = cg_with_cycle(S8, b, levels, rtol=1e-8, maxiter=600)
             assert not conv and its == 600
     _, S27, _, dofs27, _, _, b27 = case("q2_hex3")
     assert np.array_equal(dofs27, dofs)
-    _, its, conv = cg_with_cheby(S27, b27, hierarchies("q2_hex3", "jacobi")[0], rtol=1e-8, maxiter=600)
+    _, its, conv = cg_with_cycle(S27, b27, hierarchies("q2_hex3", "jacobi")[0], rtol=1e-8, maxiter=600)
     assert conv and abs(its - 68) <= 2
     # the cause, not only the symptom: the free-free 8-point matrix has more zero-energy modes than the 6 rigid-body modes
     m = structured_mesh("hexahedron", (1, 1, 1), 2)

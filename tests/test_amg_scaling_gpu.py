@@ -14,12 +14,9 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from test_amg_cheby_oracle_cpu import cheby_pairs, cheby_ref
-from test_amg_kcycle_gpu import CASES, _case_system, _hierarchy
-from test_amg_oracle_cpu import U
-from test_amg_soc_gpu import GPU_THETAS, _snapshot, _system
-from test_bilinear_gpu import _cuda
-from test_krylov_gpu import _torch, meshes  # noqa: F401  (meshes is a fixture)
+from oracle.amg_oracle import U, cheby_pairs, cheby_ref
+from solver_cases import (CASES, GPU_THETAS, _case_hierarchy, _case_system, _cuda, _soc_snapshot, _soc_system, _torch,
+                          meshes)  # noqa: F401  (meshes is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -43,14 +40,14 @@ def _case(ctx, meshes, which):
     """(DeviceCSR, constrained dofs, keywords): the cases of test_amg_kcycle_gpu.py and the systems of test_amg_soc_gpu.py."""
     if which in CASES:
         return _case_system(ctx, meshes, which)
-    A, bs, bcs, B, cr = _system(ctx, meshes, which)
+    A, bs, bcs, B, cr = _soc_system(ctx, meshes, which)
     return A, bcs, dict(coarse_rows=cr, near_nullspace=B, strength=GPU_THETAS[which])
 
 
 def _state(amg, r):
     nl = amg.n_levels
     dev = amg.levels
-    return dict(snapshot=_snapshot(amg), shape=[(d["rows"], d["bs"]) for d in dev], rho=amg.rho, unlumped=amg.unlumped_nodes,
+    return dict(snapshot=_soc_snapshot(amg), shape=[(d["rows"], d["bs"]) for d in dev], rho=amg.rho, unlumped=amg.unlumped_nodes,
                 dinv=[amg.level_dinv(l) for l in range(nl - 1)], dinv_f=[amg.level_dinv_f(l) for l in range(nl - 1)],
                 z=amg.apply(r).clone())
 
@@ -103,7 +100,7 @@ RHS_LAW = ([("jacobi", w, {}, (900, -900)) for w in ("heat48", "p2_rbm", "hex_ba
 @pytest.mark.parametrize("variant,which,kw,exponents", RHS_LAW, ids=[f"{v}-{w}" for v, w, _, _ in RHS_LAW])
 def test_right_hand_side_law(ctx, meshes, variant, which, kw, exponents):
     torch = _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which, **kw)
+    A, amg = _case_hierarchy(ctx, meshes, which, **kw)
     assert amg.n_levels >= 3
     r = _cuda(np.random.Generator(np.random.PCG64(6)).normal(size=A.shape[0]))
     z = amg.apply(r).clone()

@@ -7,77 +7,40 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from test_amg_cheby_oracle_cpu import cg_with_cheby
-from test_amg_oracle_cpu import (U, amg_ref, block_diag, cg_with_cycle, coarse_mask_ref, forward_bound, gmres_with_cycle, prolongator_ref,
-                                 rho_ref, tentative_ref, vcycle_ref)
-from test_amg_soc_oracle_cpu import (GPU_THETAS, THETA, amg_soc_cheby_ref, amg_soc_ref, filtered_ref, lumped_inverse_ref, strength_ref)
-from test_bilinear_gpu import _cuda
 from dolfinx_external_operator_amd._lib import ERRORS
-from test_krylov_gpu import _assemble, _elastic_C3, _torch, meshes  # noqa: F401  (meshes is a fixture)
-from test_krylov_oracle_cpu import bottom_dofs, boundary_dofs, elastic_C
+from oracle.amg_oracle import (U, amg_ref, block_diag, cg_with_cycle, coarse_mask_ref, cycle_ref, filtered_ref, forward_bound,
+                               gmres_with_cycle, lumped_inverse_ref, prolongator_ref, rho_ref, same_csr, strength_ref, tentative_ref)
+from oracle.krylov_oracle import boundary_dofs
+from solver_cases import (CYCLE_TOL, GPU_THETAS, THETA, _aniso, _assemble, _cuda, _soc_snapshot, _soc_system, _torch,
+                          meshes)  # noqa: F401  (meshes is a fixture)
 from tools.synthetic import structured_mesh
 
 pytestmark = pytest.mark.gpu
 
 SYSTEMS = sorted(GPU_THETAS)
-CYCLE_TOL = 2e-13            # the figure of tests/test_amg_gpu.py for Jacobi sweeps
 CYCLE_TOL_CHEBY = 1.3e-12    # the figure of tests/test_amg_cheby_gpu.py for Chebyshev smoothing
-
-
-def _aniso(ctx, meshes, cell, n=24, eps=1e-3, distort=None):
-    m = structured_mesh(cell, (n, n), 1, distort=(0.0 if cell == "quadrilateral" else 0.1) if distort is None else distort, seed=2)
-    Cb = np.broadcast_to(np.diag([1.0, eps]), (m.num_cells * m.nq, 2, 2)).copy()
-    bcs = boundary_dofs(m, 1)
-    return _assemble(ctx, meshes(m), "grad", "grad", 1, Cb, bcs=bcs), bcs
-
-
-def _system(ctx, meshes, which):
-    """(DeviceCSR, bs, constrained dofs, near-null space or None, coarse_rows): the systems of gpu_system_ref, assembled on the
-    device."""
-    from dolfinx_external_operator_amd.krylov import rigid_body_modes
-
-    if which in ("aniso_quad", "aniso_tri"):
-        A, bcs = _aniso(ctx, meshes, "quadrilateral" if which == "aniso_quad" else "triangle")
-        return A, 1, bcs, None, 60
-    if which == "p2_tri_rbm":
-        m = structured_mesh("triangle", (6, 5), 2, distort=0.1, seed=2)
-        bcs = bottom_dofs(m, 2)
-        return _assemble(ctx, meshes(m), "eps", "eps", 2, elastic_C(m), bcs=bcs), 2, bcs, rigid_body_modes(m.node_x, ctx=ctx), 20
-    m = structured_mesh("hexahedron", (3, 2, 3), 1, distort=0.1, seed=2)
-    bcs = bottom_dofs(m, 3)
-    return _assemble(ctx, meshes(m), "eps", "eps", 3, _elastic_C3(m.num_cells * m.nq), bcs=bcs), 3, bcs, rigid_body_modes(m.node_x, ctx=ctx), 20
 
 
 def _np(B):
     return None if B is None else B.cpu().numpy()
 
 
-def _same_csr(A, B):
-    return A.shape == B.shape and np.array_equal(A.indptr, B.indptr) and np.array_equal(A.indices, B.indices) and np.array_equal(A.data, B.data)
-
-
-def _snapshot(amg):
-    return ([amg.level_matrix(l) for l in range(amg.n_levels)], [amg.prolongator(l) for l in range(amg.n_levels - 1)],
-            [amg.strong_mask(l) for l in range(amg.n_levels)], [amg.aggregates(l) for l in range(amg.n_levels - 1)],
-            [(d["omega"], d["omega_f"]) for d in amg.levels])
-
-
 def _same_snapshot(a, b, masks_only=False):
     same = all(np.array_equal(x, y) for x, y in zip(a[2], b[2])) and all(np.array_equal(x, y) for x, y in zip(a[3], b[3]))
     if masks_only:
         return same
-    return (same and all(_same_csr(x, y) for x, y in zip(a[0], b[0])) and a[4] == b[4]
+    return (same and all(same_csr(x, y) for x, y in zip(a[0], b[0])) and a[4] == b[4]
             and all(np.array_equal(x.data, y.data) and np.array_equal(x.indices, y.indices) for x, y in zip(a[1], b[1])))
 
 
 @pytest.mark.parametrize("which", SYSTEMS)
 def test_hierarchy_and_cycle_match_the_oracle(ctx, meshes, which):
     torch = _torch(ctx)
-    A, bs0, bcs, B, cr = _system(ctx, meshes, which)
+    A, bs0, bcs, B, cr = _soc_system(ctx, meshes, which)
     theta = GPU_THETAS[which]
     S = A.to_scipy()
     amg = A.amg(bcs, coarse_rows=cr, near_nullspace=B, strength=theta)
-    ref = amg_soc_ref(S, bs0, bcs, theta, _np(B), coarse_rows=cr)
+    ref = amg_ref(S, bs0, bcs, near_nullspace=_np(B), strength=theta, coarse_rows=cr)
     dev = amg.levels
     assert amg.strength == theta
     assert amg.n_levels == len(ref) >= 2, (which, amg.n_levels, len(ref))
@@ -149,7 +112,7 @@ def test_hierarchy_and_cycle_match_the_oracle(ctx, meshes, which):
     for _ in range(3):
         r = rng.normal(size=S.shape[0])
         z = amg.apply(_cuda(r)).cpu().numpy()
-        zr = vcycle_ref(ref, r)
+        zr = cycle_ref(ref, r)
         worst = max(worst, np.linalg.norm(z - zr) / np.linalg.norm(zr))
     print(f"{which}: cycle deviation from the oracle {worst:.3e} |z|")
     assert worst <= CYCLE_TOL, (which, worst)
@@ -160,12 +123,12 @@ def test_hierarchy_and_cycle_match_the_oracle(ctx, meshes, which):
 def test_iteration_counts_match_the_oracle(ctx, meshes, which):
     from dolfinx_external_operator_amd import cg, gmres
 
-    A, bs, bcs, B, cr = _system(ctx, meshes, which)
+    A, bs, bcs, B, cr = _soc_system(ctx, meshes, which)
     theta = GPU_THETAS[which]
     S = A.to_scipy()
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
     amg = A.amg(bcs, coarse_rows=cr, near_nullspace=B, strength=theta)
-    ref = amg_soc_ref(S, bs, bcs, theta, _np(B), coarse_rows=cr)
+    ref = amg_ref(S, bs, bcs, near_nullspace=_np(B), strength=theta, coarse_rows=cr)
     if bs == 1:
         out = cg(A, _cuda(b), M=amg, rtol=1e-8, maxiter=2000)
         _, its, conv = cg_with_cycle(S, b, ref, rtol=1e-8, maxiter=2000)
@@ -184,7 +147,7 @@ def test_iteration_counts_match_the_oracle(ctx, meshes, which):
 
 @pytest.mark.parametrize("which", ["aniso_tri", "p2_tri_rbm"])
 def test_strength_zero_is_the_object_of_earlier_versions(ctx, meshes, which):
-    A, bs, bcs, B, cr = _system(ctx, meshes, which)
+    A, bs, bcs, B, cr = _soc_system(ctx, meshes, which)
     r = _cuda(np.random.Generator(np.random.PCG64(3)).normal(size=A.shape[0]))
     today = A.amg(bcs, coarse_rows=cr, near_nullspace=B)
     zero = A.amg(bcs, coarse_rows=cr, near_nullspace=B, strength=0.0)
@@ -206,24 +169,24 @@ def test_strength_zero_is_the_object_of_earlier_versions(ctx, meshes, which):
     finally:
         ctx.lib.dxo_amg_destroy(ctx._h, h)
     assert zero.strength == 0.0 and zero.n_levels == today.n_levels >= 2
-    assert _same_snapshot(_snapshot(today), _snapshot(zero))
+    assert _same_snapshot(_soc_snapshot(today), _soc_snapshot(zero))
     assert all(d["omega_f"] is None for d in zero.levels) and zero.strong_mask(0).all() and zero.unlumped_nodes == [0] * (zero.n_levels - 1)
     assert np.array_equal(zero.apply(r).cpu().numpy(), today.apply(r).cpu().numpy())
 
 
 def test_creation_setup_and_replay_are_bit_reproducible(ctx, meshes):
     torch = _torch(ctx)
-    A, bs, bcs, B, cr = _system(ctx, meshes, "aniso_tri")
+    A, bs, bcs, B, cr = _soc_system(ctx, meshes, "aniso_tri")
     amg = A.amg(bcs, coarse_rows=cr, strength=THETA)
     other = A.amg(bcs, coarse_rows=cr, strength=THETA)
     assert amg.n_levels >= 3
-    first = _snapshot(amg)
-    assert _same_snapshot(first, _snapshot(other))                    # two creations
+    first = _soc_snapshot(amg)
+    assert _same_snapshot(first, _soc_snapshot(other))                    # two creations
     r = _cuda(np.random.Generator(np.random.PCG64(1)).normal(size=A.shape[0]))
     z_first = amg.apply(r).clone()
     assert torch.equal(other.apply(r), z_first)
     amg.setup()
-    assert _same_snapshot(first, _snapshot(amg))                      # two setups
+    assert _same_snapshot(first, _soc_snapshot(amg))                      # two setups
     assert torch.equal(amg.apply(r), z_first)
     z = torch.zeros_like(r)
     s = torch.cuda.Stream()
@@ -251,40 +214,39 @@ def test_setup_with_new_values_keeps_the_masks_and_the_aggregates(ctx, meshes):
     A = _assemble(ctx, dm, "grad", "grad", 1, Cb, bcs=bcs)
     A2 = _assemble(ctx, dm, "grad", "grad", 1, Cb * np.array([[1.0, 1.0], [1.0, 300.0]]), bcs=bcs)      # a milder anisotropy
     amg = A.amg(bcs, coarse_rows=60, strength=THETA)
-    first = _snapshot(amg)
+    first = _soc_snapshot(amg)
     amg.setup(A2)
-    second = _snapshot(amg)
+    second = _soc_snapshot(amg)
     assert _same_snapshot(first, second, masks_only=True)
     assert all(np.array_equal(x.indices, y.indices) for x, y in zip(first[1], second[1]))
     assert not np.array_equal(first[1][0].data, second[1][0].data)
-    ref = amg_soc_ref(A2.to_scipy(), 1, bcs, THETA, coarse_rows=60, frozen=amg_soc_ref(A.to_scipy(), 1, bcs, THETA, coarse_rows=60))
+    ref = amg_ref(A2.to_scipy(), 1, bcs, strength=THETA, coarse_rows=60, frozen=amg_ref(A.to_scipy(), 1, bcs, strength=THETA, coarse_rows=60))
     r = np.random.Generator(np.random.PCG64(2)).normal(size=A.shape[0])
-    z, zr = amg.apply(_cuda(r)).cpu().numpy(), vcycle_ref(ref, r)
+    z, zr = amg.apply(_cuda(r)).cpu().numpy(), cycle_ref(ref, r)
     assert np.linalg.norm(z - zr) <= CYCLE_TOL * np.linalg.norm(zr)
 
 
 def test_chebyshev_and_power_iteration_on_a_strength_hierarchy(ctx, meshes):
     from dolfinx_external_operator_amd import cg
-    from test_amg_cheby_oracle_cpu import vcycle_cheby_ref
 
-    A, bs, bcs, B, cr = _system(ctx, meshes, "aniso_tri")
+    A, bs, bcs, B, cr = _soc_system(ctx, meshes, "aniso_tri")
     S = A.to_scipy()
     amg = A.amg(bcs, coarse_rows=cr, strength=THETA)
     masks = [amg.strong_mask(l) for l in range(amg.n_levels)]
     amg.set_smoother("chebyshev", degree=2, rho="power")
     amg.setup()
     assert all(np.array_equal(a, amg.strong_mask(l)) for l, a in enumerate(masks))
-    ref = amg_soc_cheby_ref(S, 1, bcs, THETA, degree=2, coarse_rows=cr)
+    ref = amg_ref(S, 1, bcs, strength=THETA, smoother="chebyshev", rho="power", degree=2, coarse_rows=cr)
     assert [d["rows"] for d in amg.levels] == [L.n_rows for L in ref]
     for d, L in zip(amg.levels[:-1], ref[:-1]):
         assert abs(d["omega_f"] - L.omega_f) <= 1e-10 * L.omega_f and abs(d["omega"] - L.omega) <= 1e-10 * L.omega
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
-    z, zr = amg.apply(_cuda(b)).cpu().numpy(), vcycle_cheby_ref(ref, b)
+    z, zr = amg.apply(_cuda(b)).cpu().numpy(), cycle_ref(ref, b)
     dev = np.linalg.norm(z - zr) / np.linalg.norm(zr)
     print(f"aniso_tri, Chebyshev 2 with power rho: cycle deviation from the oracle {dev:.3e} |z|")
     assert dev <= CYCLE_TOL_CHEBY
     out = cg(A, _cuda(b), M=amg, rtol=1e-8, maxiter=2000)
-    _, its, conv = cg_with_cheby(S, b, ref, rtol=1e-8, maxiter=2000)
+    _, its, conv = cg_with_cycle(S, b, ref, rtol=1e-8, maxiter=2000)
     print(f"aniso_tri, Chebyshev 2 with power rho: CG iterations {out.iterations} (oracle {its})")
     assert out.converged and conv and abs(out.iterations - its) <= 2, (out.iterations, its)
 
@@ -327,7 +289,7 @@ def test_small_and_ragged_node_counts_and_a_lone_node(ctx, meshes, n):
         torch.cuda.synchronize()
         S = A.to_scipy()
     amg = A.amg(bcs, coarse_rows=3, strength=THETA)
-    ref = amg_soc_ref(S, 1, bcs, THETA, coarse_rows=3)
+    ref = amg_ref(S, 1, bcs, strength=THETA, coarse_rows=3)
     assert [x["rows"] for x in amg.levels] == [L.n_rows for L in ref]
     for l, L in enumerate(ref[:-1]):
         assert np.array_equal(amg.strong_mask(l), L.strong) and np.array_equal(amg.aggregates(l), L.agg)
@@ -336,14 +298,14 @@ def test_small_and_ragged_node_counts_and_a_lone_node(ctx, meshes, n):
         P = amg.prolongator(0).tocsr()
         assert P[lone].nnz == 1 and P[lone].sum() == 1.0
     r = np.random.Generator(np.random.PCG64(5)).normal(size=S.shape[0])
-    z, zr = amg.apply(_cuda(r)).cpu().numpy(), vcycle_ref(ref, r)
+    z, zr = amg.apply(_cuda(r)).cpu().numpy(), cycle_ref(ref, r)
     assert np.linalg.norm(z - zr) <= CYCLE_TOL * np.linalg.norm(zr)
     out = cg(A, _cuda(r), M=amg, rtol=1e-8)
     assert out.converged
 
 
 def test_error_codes(ctx, meshes):
-    A, bs, bcs, B, cr = _system(ctx, meshes, "aniso_tri")
+    A, bs, bcs, B, cr = _soc_system(ctx, meshes, "aniso_tri")
     for bad in (-0.1, 1.0, float("nan")):
         with pytest.raises(ValueError):
             A.amg(bcs, strength=bad)

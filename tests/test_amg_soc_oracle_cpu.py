@@ -1,13 +1,13 @@
 """The NumPy / SciPy yardstick of dxo_amg_create_soc (csrc/amg.hip): strength-of-connection coarsening and filtered prolongator
-smoothing, pinned on the CPU on top of the oracles of test_amg_oracle_cpu.py, test_amg_nns_oracle_cpu.py and
-test_amg_cheby_oracle_cpu.py.
+smoothing, pinned on the CPU (oracle/amg_oracle.py).
 
 strength_ref: block (i, j), i != j, is strong when |A_ij|_F^2 >= theta^2 |A_ii|_F |A_jj|_F or the same holds for (j, i); diagonal
-blocks are strong. The squares are formed on entries scaled by a power of two, so the mask does not depend on the scale of A. amg_soc_ref: today's three passes on the strong graph, P on the pattern (strong graph) x (aggregates), A P and
+blocks are strong. The squares are formed on entries scaled by a power of two, so the mask does not depend on the scale of A.
+amg_ref(strength=theta): today's three passes on the strong graph, P on the pattern (strong graph) x (aggregates), A P and
 P^T A P on the full graph, P = T - omega_F Dinv_F A^F T with A^F the matrix without its weak blocks, each added onto the diagonal
 block of its row, Dinv_F the inverses of the lumped blocks (A_ii's where the lumped block fails Hadamard's test, zero for a node
 without a strong neighbour) and omega_F = (4/3) / rho_F from the selected estimate of Dinv_F A^F. The sweeps keep A, Dinv and rho, so
-the cycles are vcycle_ref / vcycle_cheby_ref. `frozen` takes the masks and aggregates of an earlier hierarchy, as dxo_amg_setup does.
+the cycle is cycle_ref. `frozen` takes the masks and aggregates of an earlier hierarchy, as dxo_amg_setup does.
 
 Measured here (CG, rtol 1e-8, coarse_rows 60, theta 0.25, one Jacobi sweep, C = diag(1, 1e-3), 625 dofs); the figures are printed by
 test_iteration_counts_on_the_anisotropic_systems:
@@ -20,231 +20,15 @@ import pytest
 import scipy.sparse as sp
 import scipy.sparse.csgraph
 
-import test_amg_cheby_oracle_cpu as cheby_oracle
-import test_amg_nns_oracle_cpu as nns_oracle
-import test_amg_oracle_cpu as amg_oracle
-from test_amg_oracle_cpu import (MAX_DENSE, U, Level, _ones, active_nodes, aggregate_ref, amg_ref, block_diag, cg_with_cycle, coarse_mask_ref,
-                                 coarse_ref, node_graph, on_pattern, operator_complexity, prolongator_ref, tentative_ref, vcycle_ref)
-from test_assemble_oracle_cpu import apply_bcs, dense_ref
-from test_krylov_oracle_cpu import block_jacobi_ref, bottom_dofs, boundary_dofs, elastic_C, to_pattern_csr
+from oracle.amg_oracle import (U, amg_ref, cg_with_cycle, cycle_ref, filtered_ref, lumped_inverse_ref, node_graph, on_pattern, ones_pattern,
+                               operator_complexity, rigid_body_modes_ref, same_csr, strength_ref, strength_unscaled_ref)
+from oracle.form_oracle import apply_bcs, dense_ref
+from oracle.krylov_oracle import bottom_dofs, boundary_dofs, elastic_C, elastic_C3, to_pattern_csr
+from solver_cases import GPU_THETAS, THETA, cached_aniso
 from tools.synthetic import structured_mesh
-
-THETA = 0.25
-
-
-# ---- the measure
-def block_values(A, indptr, indices, bs):
-    """(blocks [nnzb][bs][bs], node of every block, its column node) of a matrix on a csr.h pattern, in the order of the pattern."""
-    ptr, nb = node_graph(indptr, indices, bs)
-    n = ptr.size - 1
-    row = np.repeat(np.arange(n), np.diff(ptr))
-    k = np.arange(nb.size) - ptr[row]
-    base = np.asarray(indptr, dtype=np.int64)[row * bs]
-    ln = np.asarray(indptr, dtype=np.int64)[row * bs + 1] - base
-    r, c = np.arange(bs)[None, :, None], np.arange(bs)[None, None, :]
-    idx = base[:, None, None] + r * ln[:, None, None] + k[:, None, None] * bs + c
-    return A.data[idx], row, nb
-
-
-def pow2_down(m):
-    """2^-e, e the exponent of m (frexp) held in +-1000; 1 for a zero, NaN or infinite m: amg_pow2_down of the device."""
-    m = np.asarray(m, dtype=np.float64)
-    ok = (m > 0.0) & np.isfinite(m)
-    e = np.where(ok, np.frexp(np.where(ok, m, 1.0))[1], 0)
-    return np.ldexp(1.0, -np.clip(e, -1000, 1000))
-
-
-def _norm2(blocks, s):
-    """The sum of the squares of s[b] blocks[b], entry by entry in row-major order."""
-    n2 = np.zeros(blocks.shape[0])
-    for v in blocks.reshape(blocks.shape[0], -1).T:
-        v = v * s
-        n2 = n2 + v * v
-    return n2
-
-
-def _decide(A, indptr, indices, bs, theta, n2, bound):
-    """(mask, closest) from the squared norms and the thresholds of every block, both in the scaling of the block."""
-    blocks, row, colnode = block_values(A, indptr, indices, bs)
-    ptr, nb = node_graph(indptr, indices, bs)
-    n = ptr.size - 1
-    N2 = sp.csr_matrix((n2, nb, ptr), shape=(n, n))
-    has = sp.csr_matrix((np.ones(nb.size), nb, ptr), shape=(n, n))
-    n2t = np.asarray(N2.T.tocsr()[row, colnode]).ravel() if nb.size else np.zeros(0)
-    present = np.asarray(has.T.tocsr()[row, colnode]).ravel() > 0 if nb.size else np.zeros(0, dtype=bool)
-    mask = (n2 >= bound) | (present & (n2t >= bound)) | (row == colnode)
-    off = (row != colnode) & (bound > 0.0)
-    closest = np.inf
-    if off.any():
-        closest = min(np.abs(n2[off] / bound[off] - 1.0).min(), np.abs(n2t[off & present] / bound[off & present] - 1.0).min(initial=np.inf))
-    return mask, closest
-
-
-def strength_ref(A, indptr, indices, bs, theta):
-    """(mask per block, closest): the strong blocks, and the smallest |value / threshold - 1| over the tests that decided them.
-    The device's range-safe arithmetic: |A_ii|_F from the block times 2^-e of its largest entry, divided by it again; block (i, j)
-    compared as |s A_ij|_F^2 >= theta^2 (s |A_ii|_F) (s |A_jj|_F) with s = 2^-e of the larger norm, the same s for (j, i)."""
-    blocks, row, colnode = block_values(A, indptr, indices, bs)
-    n = (np.asarray(indptr).size - 1) // bs
-    on = row == colnode
-    sd = pow2_down(np.abs(blocks[on]).reshape(-1, bs * bs).max(axis=1))
-    dn = np.zeros(n)
-    dn[row[on]] = np.sqrt(_norm2(blocks[on], sd)) / sd
-    s = pow2_down(np.maximum(dn[row], dn[colnode]))
-    bound = theta * theta * ((dn[row] * s) * (dn[colnode] * s))
-    return _decide(A, indptr, indices, bs, theta, _norm2(blocks, s), bound)
-
-
-def strength_unscaled_ref(A, indptr, indices, bs, theta):
-    """strength_ref in the arithmetic of earlier versions, which squares the entries as they are: |A_ij|_F^2 >= theta^2 |A_ii|_F
-    |A_jj|_F. Kept as what the range-safe form is compared against inside the range where these squares are normal numbers."""
-    blocks, row, colnode = block_values(A, indptr, indices, bs)
-    n = (np.asarray(indptr).size - 1) // bs
-    n2 = _norm2(blocks, 1.0)
-    dn = np.zeros(n)
-    dn[row[row == colnode]] = np.sqrt(n2[row == colnode])
-    return _decide(A, indptr, indices, bs, theta, n2, theta * theta * (dn[row] * dn[colnode]))
-
-
-def filtered_ref(A, indptr, indices, bs, mask):
-    """(A^F as CSR, the lumped diagonal blocks [n][bs][bs], A's own [n][bs][bs], strong off-diagonal blocks per node)."""
-    blocks, row, colnode = block_values(A, indptr, indices, bs)
-    n = (np.asarray(indptr).size - 1) // bs
-    diag = np.zeros((n, bs, bs))
-    diag[row[row == colnode]] = blocks[row == colnode]
-    lumped = diag.copy()
-    weak = ~mask
-    np.add.at(lumped, row[weak], blocks[weak])                    # in the order of the pattern: ascending column
-    n_strong = np.bincount(row[mask & (row != colnode)], minlength=n)
-    keep = mask & (row != colnode)
-    AF = sp.bsr_matrix((blocks[keep], colnode[keep], np.concatenate([[0], np.cumsum(np.bincount(row[keep], minlength=n))])),
-                       shape=A.shape).tocsr() + block_diag(lumped)
-    return AF.tocsr(), lumped, diag, n_strong
-
-
-def lumped_inverse_ref(lumped, diag, n_strong):
-    """(Dinv_F [n][bs][bs], nodes that fell back to A_ii): Hadamard's test of dxo_csr_block_jacobi on the lumped blocks."""
-    n = lumped.shape[0]
-    out = np.zeros_like(lumped)
-    fell = np.zeros(n, dtype=bool)
-    for i in np.flatnonzero(n_strong > 0):
-        had = np.prod(np.sqrt((lumped[i] ** 2).sum(axis=1)))
-        ok = abs(np.linalg.det(lumped[i])) > 1e-14 * had
-        out[i] = np.linalg.inv(lumped[i] if ok else diag[i])
-        fell[i] = not ok
-    return out, fell
-
-
-def soc_patterns(ptr, nb, mask, agg, na):
-    """Block patterns of P (strong graph x aggregates), A P and P^T A P (full graph) from integer products."""
-    n = ptr.size - 1
-    G = sp.csr_matrix((np.ones(nb.size, dtype=np.int64), nb, ptr), shape=(n, n))
-    Gs = sp.csr_matrix((mask.astype(np.int64), nb, ptr), shape=(n, n))
-    Gs.eliminate_zeros()
-    on = np.flatnonzero(agg >= 0)
-    Tg = sp.csr_matrix((np.ones(on.size, dtype=np.int64), (on, agg[on])), shape=(n, na))
-    Pp = _ones(Gs @ Tg)
-    APp = _ones(G @ Pp)
-    Cp = _ones(Pp.T @ APp + sp.identity(na, dtype=np.int64, format="csr"))
-    out = []
-    for M in (Pp, APp, Cp):
-        M = M.tocsr()
-        M.sort_indices()
-        out.append(M)
-    return out
-
-
-def strong_graph_ref(ptr, nb, mask):
-    n = ptr.size - 1
-    row = np.repeat(np.arange(n), np.diff(ptr))
-    return np.concatenate([[0], np.cumsum(np.bincount(row[mask], minlength=n))]), nb[mask]
-
-
-def amg_soc_ref(S, bs, constrained, theta, near_nullspace=None, max_levels=10, coarse_rows=512, sweeps=1, filtered=True, frozen=None,
-                rank_tol=nns_oracle.RANK_TOL):
-    """The hierarchy with the threshold theta: a list of Level as amg_ref / amg_nns_ref make them, with strong (mask per block),
-    closest, AF, lumped, Dinv_f, fell (nodes that fell back to A_ii), n_strong_off, rho_f and omega_f but for the last.
-    filtered False: the aggregates of the strong graph with P smoothed by the full matrix. frozen: the levels of an earlier call whose
-    masks and aggregates are reused, as dxo_amg_setup reuses those of the creation."""
-    levels = []
-    A = S.tocsr()
-    indptr, indices = A.indptr.astype(np.int64), A.indices.astype(np.int32)
-    mask, active = active_nodes(A.shape[0], bs, constrained)
-    k = 0 if near_nullspace is None else near_nullspace.shape[1]
-    if k:
-        B = np.array(near_nullspace, dtype=np.float64)
-        B[mask] = 0.0
-    while True:
-        L = Level()
-        L.A, L.indptr, L.indices, L.bs, L.mask, L.sweeps = A, indptr, indices, bs, mask, sweeps
-        L.n_rows = A.shape[0]
-        if k:
-            L.B = B
-        levels.append(L)
-        bsc = k if k else bs
-        last = L.n_rows <= coarse_rows or len(levels) >= max_levels
-        if frozen is not None:
-            last = len(levels) == len(frozen)
-        if not last:
-            ptr, nb = node_graph(indptr, indices, bs)
-            if frozen is None:
-                strong, closest = strength_ref(A, indptr, indices, bs, theta)
-                agg, na = aggregate_ref(*strong_graph_ref(ptr, nb, strong), active)
-                last = na == 0 or na * bsc > 0.8 * L.n_rows
-            else:
-                F = frozen[len(levels) - 1]
-                strong, closest, agg, na = F.strong, F.closest, F.agg, F.n_agg
-        if last:
-            break
-        L.strong, L.closest, L.agg, L.n_agg, L.bs_coarse = strong, closest, agg, na, bsc
-        L.Pp, L.APp, L.Cp = soc_patterns(ptr, nb, strong if filtered else np.ones_like(strong), agg, na)
-        L.Dinv = block_jacobi_ref(A, bs)
-        L.rho, _ = amg_oracle.rho_ref(A, L.Dinv)
-        L.omega = (4.0 / 3.0) / L.rho
-        L.AF, L.lumped, diag, L.n_strong_off = filtered_ref(A, indptr, indices, bs, strong)
-        L.Dinv_f, L.fell = lumped_inverse_ref(L.lumped, diag, L.n_strong_off)
-        L.rho_f, _ = amg_oracle.rho_ref(L.AF, L.Dinv_f)
-        L.omega_f = (4.0 / 3.0) / L.rho_f if L.rho_f > 0.0 else 0.0
-        if k:
-            L.T, B, L.dead = nns_oracle.tentative_nns_ref(agg, na, B, bs, rank_tol)
-        else:
-            L.T = tentative_ref(agg, mask, bs, na)
-        pptr, pidx = nns_oracle.expand_rect(L.Pp, bs, bsc)
-        exact = prolongator_ref(L.AF, L.Dinv_f, L.omega_f, L.T) if filtered else prolongator_ref(A, L.Dinv, L.omega, L.T)
-        L.P = on_pattern(exact, pptr, pidx, (L.n_rows, na * bsc))
-        indptr, indices = nns_oracle.expand_rect(L.Cp, bsc, bsc)
-        A = on_pattern(coarse_ref(A, L.P), indptr, indices, (na * bsc, na * bsc))
-        mask = coarse_mask_ref(A)
-        bs = bsc
-        active = np.ones(na, dtype=bool)
-    if levels[-1].n_rows > MAX_DENSE:
-        raise ValueError("coarsest level too large for the dense solve")
-    levels[-1].dense_inverse = np.linalg.inv(levels[-1].A.toarray())
-    return levels
-
-
-def amg_soc_cheby_ref(S, bs, constrained, theta, near_nullspace=None, smoother="chebyshev", degree=None, rho="power",
-                      rho_iters=cheby_oracle.RHO_ITERS, lower=cheby_oracle.LOWER, safety=cheby_oracle.SAFETY, **kw):
-    """The hierarchy of the creation (default relaxation) set up again under the selected relaxation with its masks frozen; for
-    vcycle_cheby_ref."""
-    frozen = amg_soc_ref(S, bs, constrained, theta, near_nullspace, **kw)
-    with cheby_oracle.rho_source(rho, rho_iters, safety):
-        levels = amg_soc_ref(S, bs, constrained, theta, near_nullspace, frozen=frozen, **kw)
-    for L in levels:
-        L.smoother, L.degree, L.lower = smoother, (L.sweeps if degree is None else degree), lower
-    return levels
 
 
 # ---- the systems
-def aniso_system(cell, n=24, eps=1e-3):
-    """(mesh, S on the device pattern, constrained dofs): grad/grad with C = diag(1, eps), Dirichlet boundary; the quadrilaterals
-    uniform, the triangles distorted by 0.1 (seed 2)."""
-    m = structured_mesh(cell, (n, n), 1, distort=0.0 if cell == "quadrilateral" else 0.1, seed=2)
-    C = np.broadcast_to(np.diag([1.0, eps]), (m.num_cells * m.nq, 2, 2)).copy()
-    dofs = boundary_dofs(m, 1)
-    return m, to_pattern_csr(m, apply_bcs(dense_ref(m, "grad", "grad", 1, C), dofs, 1.0), 1), dofs
-
-
 def isotropic_q1_system(n=20):
     """Q1 on uniform squares with C = I: every neighbour at a_ii / 8, so theta = 0.25 leaves nothing strong; (n - 1)^2 interior nodes
     of (n + 1)^2 are more than 0.8 of the rows from n = 18 on."""
@@ -254,41 +38,28 @@ def isotropic_q1_system(n=20):
     return m, to_pattern_csr(m, apply_bcs(dense_ref(m, "grad", "grad", 1, C), dofs, 1.0), 1), dofs
 
 
-_CACHE = {}
-
-
-def cached_aniso(cell, n=24, eps=1e-3):
-    if (cell, n, eps) not in _CACHE:
-        _CACHE[(cell, n, eps)] = aniso_system(cell, n, eps)
-    return _CACHE[(cell, n, eps)]
-
-
 def eps_rbm_system(cell="triangle", n=(6, 5), degree=2):
     """(mesh, S, constrained dofs, rigid-body modes): eps/eps with the isotropic C, clamped at the bottom."""
     m = structured_mesh(cell, n, degree, distort=0.1, seed=2)
     g = m.gdim
     dofs = bottom_dofs(m, g)
-    C = elastic_C(m) if g == 2 else nns_oracle.elastic_C3(m.num_cells * m.nq)
+    C = elastic_C(m) if g == 2 else elastic_C3(m.num_cells * m.nq)
     S = to_pattern_csr(m, apply_bcs(dense_ref(m, "eps", "eps", g, C), dofs, 1.0), g)
-    return m, S, dofs, nns_oracle.rigid_body_modes_ref(m.node_x)
-
-
-def same_csr(A, B):
-    return A.shape == B.shape and np.array_equal(A.indptr, B.indptr) and np.array_equal(A.indices, B.indices) and np.array_equal(A.data, B.data)
+    return m, S, dofs, rigid_body_modes_ref(m.node_x)
 
 
 # ---- tests
 def test_theta_zero_is_the_hierarchy_of_today():
     m, S, dofs = cached_aniso("triangle", 12)
-    for ref, soc in ((amg_ref(S, 1, dofs, coarse_rows=6), amg_soc_ref(S, 1, dofs, 0.0, coarse_rows=6)),):
+    for ref, soc in ((amg_ref(S, 1, dofs, coarse_rows=6), amg_ref(S, 1, dofs, strength=0.0, filtered=True, coarse_rows=6)),):
         assert len(ref) == len(soc) >= 3
         for a, b in zip(ref, soc):
             assert same_csr(a.A, b.A)
         for a, b in zip(ref[:-1], soc[:-1]):
             assert b.strong.all() and np.array_equal(a.agg, b.agg) and same_csr(a.P, b.P) and a.omega == b.omega_f
     m, S, dofs, B = eps_rbm_system()
-    ref = nns_oracle.amg_nns_ref(S, 2, dofs, B, coarse_rows=20)
-    soc = amg_soc_ref(S, 2, dofs, 0.0, B, coarse_rows=20)
+    ref = amg_ref(S, 2, dofs, near_nullspace=B, coarse_rows=20)
+    soc = amg_ref(S, 2, dofs, near_nullspace=B, strength=0.0, filtered=True, coarse_rows=20)
     assert len(ref) == len(soc) >= 2
     for a, b in zip(ref, soc):
         assert same_csr(a.A, b.A)
@@ -299,7 +70,7 @@ def test_theta_zero_is_the_hierarchy_of_today():
 @pytest.mark.parametrize("theta", [0.05, 0.25, 0.6])
 def test_mask_is_symmetric_with_a_strong_diagonal(theta):
     for _, S, bs, dofs, B in _systems():
-        levels = amg_soc_ref(S, bs, dofs, theta, B, coarse_rows=20)
+        levels = amg_ref(S, bs, dofs, near_nullspace=B, strength=theta, coarse_rows=20)
         for L in levels[:-1]:
             ptr, nb = node_graph(L.indptr, L.indices, L.bs)
             n = ptr.size - 1
@@ -328,10 +99,10 @@ def test_mask_on_the_uniform_stencils():
     strong, _ = strength_ref(S, S.indptr, S.indices, 1, THETA)
     ptr, nb = node_graph(S.indptr, S.indices, 1)
     assert np.array_equal(strong, np.repeat(np.arange(ptr.size - 1), np.diff(ptr)) == nb)
-    levels = amg_soc_ref(S, 1, dofs, THETA, coarse_rows=10)
+    levels = amg_ref(S, 1, dofs, strength=THETA, coarse_rows=10)
     assert len(levels) == 1                                              # every node alone, 361 of 441: the 0.8 rule stops at once
     r = np.arange(S.shape[0], dtype=float)
-    assert np.allclose(S @ vcycle_ref(levels, r), r, atol=1e-9 * np.abs(r).max())
+    assert np.allclose(S @ cycle_ref(levels, r), r, atol=1e-9 * np.abs(r).max())
 
 
 def _systems():
@@ -343,7 +114,7 @@ def _systems():
 
 def test_filtered_matrix_keeps_the_row_sums_and_the_strong_pattern():
     for name, S, bs, dofs, B in _systems():
-        for L in amg_soc_ref(S, bs, dofs, THETA, B, coarse_rows=20)[:-1]:
+        for L in amg_ref(S, bs, dofs, near_nullspace=B, strength=THETA, coarse_rows=20)[:-1]:
             b = L.bs
             n = L.n_rows // b
             E = sp.kron(np.ones((n, 1)), np.eye(b), format="csr")            # block row sums, component by component
@@ -355,7 +126,7 @@ def test_filtered_matrix_keeps_the_row_sums_and_the_strong_pattern():
             Gs.eliminate_zeros()
             pat = sp.kron(Gs, np.ones((b, b)), format="csr")
             assert abs(L.AF).multiply(pat).sum() == abs(L.AF).sum(), name     # nothing outside the strong graph
-            assert (L.Pp != _ones(Gs @ _ones(sp.csr_matrix((np.ones((L.agg >= 0).sum()), (np.flatnonzero(L.agg >= 0), L.agg[L.agg >= 0])),
+            assert (L.Pp != ones_pattern(Gs @ ones_pattern(sp.csr_matrix((np.ones((L.agg >= 0).sum()), (np.flatnonzero(L.agg >= 0), L.agg[L.agg >= 0])),
                                                              shape=(n, L.n_agg))))).nnz == 0
 
 
@@ -368,7 +139,7 @@ def test_a_node_without_a_strong_neighbour_keeps_its_row_of_t():
     lone = free[free.size // 2]
     d = S.indptr[lone] + np.flatnonzero(S.indices[S.indptr[lone]:S.indptr[lone + 1]] == lone)[0]
     S.data[d] *= 100.0
-    levels = amg_soc_ref(S, 1, dofs, THETA, coarse_rows=20)
+    levels = amg_ref(S, 1, dofs, strength=THETA, coarse_rows=20)
     L = levels[0]
     assert L.n_strong_off[lone] == 0 and (L.agg == L.agg[lone]).sum() == 1
     assert not L.Dinv_f[lone].any() and not L.fell[lone]
@@ -409,7 +180,7 @@ def test_a_near_singular_lumped_block_falls_back_and_is_counted():
 def test_every_aggregate_is_connected_in_the_strong_graph():
     for name, S, bs, dofs, B in _systems():
         for theta in (0.1, THETA):
-            for L in amg_soc_ref(S, bs, dofs, theta, B, coarse_rows=20)[:-1]:
+            for L in amg_ref(S, bs, dofs, near_nullspace=B, strength=theta, coarse_rows=20)[:-1]:
                 ptr, nb = node_graph(L.indptr, L.indices, L.bs)
                 n = ptr.size - 1
                 Gs = sp.csr_matrix((L.strong.astype(np.int64), nb, ptr), shape=(n, n))
@@ -421,20 +192,17 @@ def test_every_aggregate_is_connected_in_the_strong_graph():
 
 def test_frozen_masks_reproduce_the_hierarchy_and_survive_new_values():
     m, S, dofs = cached_aniso("triangle", 12)
-    first = amg_soc_ref(S, 1, dofs, THETA, coarse_rows=6)
-    again = amg_soc_ref(S, 1, dofs, THETA, coarse_rows=6, frozen=first)
+    first = amg_ref(S, 1, dofs, strength=THETA, coarse_rows=6)
+    again = amg_ref(S, 1, dofs, strength=THETA, coarse_rows=6, frozen=first)
     assert len(first) == len(again) >= 3
     for a, b in zip(first[:-1], again[:-1]):
         assert same_csr(a.P, b.P) and same_csr(a.A, b.A)
     S2 = S.copy()
     S2.data = S.data * (1.0 + 0.05 * np.cos(np.arange(S.data.size)))
-    other = amg_soc_ref(S2, 1, dofs, THETA, coarse_rows=6, frozen=first)
+    other = amg_ref(S2, 1, dofs, strength=THETA, coarse_rows=6, frozen=first)
     for a, b in zip(first[:-1], other[:-1]):
         assert np.array_equal(a.agg, b.agg) and np.array_equal(a.strong, b.strong) and np.array_equal(a.P.indices, b.P.indices)
         assert not np.array_equal(a.P.data, b.P.data)
-
-
-GPU_THETAS = {"aniso_quad": THETA, "aniso_tri": THETA, "p2_tri_rbm": 0.1, "hex_rbm": 0.1}
 
 
 def gpu_system_ref(which):
@@ -454,7 +222,7 @@ def test_no_block_of_the_gpu_systems_lies_at_the_threshold(which):
     """The condition under which the device mask must equal the oracle's exactly: no test value within 4 K u of its threshold, K the
     bs^2 terms of a block norm (far from it: the closest is printed)."""
     m, S, bs, dofs, B = gpu_system_ref(which)
-    levels = amg_soc_ref(S, bs, dofs, GPU_THETAS[which], B, coarse_rows=60 if bs == 1 else 20)
+    levels = amg_ref(S, bs, dofs, near_nullspace=B, strength=GPU_THETAS[which], coarse_rows=60 if bs == 1 else 20)
     assert len(levels) >= 2
     for l, L in enumerate(levels[:-1]):
         print(f"{which} level {l}: closest test value {L.closest:.3e} of its threshold away, {int(L.strong.sum())} of {L.strong.size} strong")
@@ -472,7 +240,7 @@ def test_masks_do_not_depend_on_the_scale_of_the_matrix(which):
     exponents. The unscaled arithmetic loses the mask of level 0 at every one of them (asserted, so that the exponents stay meaningful)."""
     m, S, bs, dofs, B = gpu_system_ref(which)
     theta = GPU_THETAS[which]
-    levels = amg_soc_ref(S, bs, dofs, theta, B, coarse_rows=60 if bs == 1 else 20)
+    levels = amg_ref(S, bs, dofs, near_nullspace=B, strength=theta, coarse_rows=60 if bs == 1 else 20)
     assert len(levels) >= 2
     for l, L in enumerate(levels[:-1]):
         old, old_closest = strength_unscaled_ref(L.A, L.indptr, L.indices, L.bs, theta)
@@ -496,8 +264,8 @@ def test_iteration_counts_on_the_anisotropic_systems():
         m, S, dofs = cached_aniso(cell)
         b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
         plain = amg_ref(S, 1, dofs, coarse_rows=60)
-        soc = amg_soc_ref(S, 1, dofs, THETA, coarse_rows=60)
-        full = amg_soc_ref(S, 1, dofs, THETA, coarse_rows=60, filtered=False)
+        soc = amg_ref(S, 1, dofs, strength=THETA, coarse_rows=60)
+        full = amg_ref(S, 1, dofs, strength=THETA, coarse_rows=60, filtered=False)
         _, its0, conv0 = cg_with_cycle(S, b, plain, rtol=1e-8)
         x, its1, conv1 = cg_with_cycle(S, b, soc, rtol=1e-8)
         _, its2, conv2 = cg_with_cycle(S, b, full, rtol=1e-8)
@@ -513,11 +281,11 @@ def test_iteration_counts_on_the_anisotropic_systems():
 def test_chebyshev_and_power_iteration_on_a_strength_hierarchy():
     m, S, dofs = cached_aniso("triangle")
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
-    levels = amg_soc_cheby_ref(S, 1, dofs, THETA, degree=2, coarse_rows=60)
-    jac = amg_soc_ref(S, 1, dofs, THETA, coarse_rows=60)
+    levels = amg_ref(S, 1, dofs, strength=THETA, smoother="chebyshev", rho="power", degree=2, coarse_rows=60)
+    jac = amg_ref(S, 1, dofs, strength=THETA, coarse_rows=60)
     for a, c in zip(jac[:-1], levels[:-1]):
         assert np.array_equal(a.strong, c.strong) and np.array_equal(a.agg, c.agg)
         assert 0.0 < c.rho_f != a.rho_f and c.omega_f == (4.0 / 3.0) / c.rho_f  # omega_F follows the selected estimate
-    x, its, conv = cheby_oracle.cg_with_cheby(S, b, levels, rtol=1e-8)
+    x, its, conv = cg_with_cycle(S, b, levels, rtol=1e-8)
     _, its_j, _ = cg_with_cycle(S, b, jac, rtol=1e-8)
     assert conv and its <= its_j

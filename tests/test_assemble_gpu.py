@@ -7,8 +7,9 @@ import sys
 import numpy as np
 import pytest
 
-from test_assemble_oracle_cpu import apply_bcs, csr_to_dense, dense_by_probes, dense_ref, heat_setting, pattern_ref
-from test_bilinear_gpu import CELLS, PAIRS, _cuda, _value_size, _zeros
+from oracle.form_oracle import apply_bcs, csr_to_dense, dense_by_probes, dense_ref, heat_setting, pattern_ref
+from oracle.operand_oracle import DEFGRAD, GRAD, VALUE
+from solver_cases import CELLS, PAIRS, _cuda, _value_size, _zeros
 from tools.synthetic import structured_mesh
 
 pytestmark = pytest.mark.gpu
@@ -271,7 +272,6 @@ def test_error_paths(ctx):
     import torch
 
     from dolfinx_external_operator_amd import DeviceMesh
-    from oracle.operand_oracle import DEFGRAD, GRAD, VALUE
 
     m = structured_mesh("triangle", (2, 2), 2)
     other = structured_mesh("triangle", (2, 2), 2)

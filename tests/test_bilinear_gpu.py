@@ -6,26 +6,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_bilinear_oracle_cpu import bilinear_diag_ref, bilinear_ref, diagonal_by_probes, node_colours
+from oracle.form_oracle import bilinear_diag_ref, bilinear_ref, diagonal_by_probes, node_colours
+from solver_cases import CELLS, PAIRS, _cuda, _value_size, _zeros
 from tools.synthetic import structured_mesh
 
 pytestmark = pytest.mark.gpu
-CELLS = {"triangle": (4, 3), "quadrilateral": (3, 3), "tetrahedron": (2, 2, 1), "hexahedron": (2, 1, 2)}
-# (test, trial, bs is gdim)
-PAIRS = [("grad", "grad", True), ("F", "grad", True), ("grad", "F", True), ("F", "F", True), ("eps", "eps", True),
-         ("grad", "value_grad", False), ("grad", "grad", False), ("value", "value", False), ("value_grad", "value_grad", False)]
-
-
-def _cuda(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)).cuda()
-
-
-def _zeros(n):
-    import torch
-
-    return torch.zeros(n, dtype=torch.float64, device="cuda")
 
 
 def device_apply(ctx, dm, test, trial, bs, Cd, v, n):
@@ -46,10 +31,6 @@ def device_diag(ctx, dm, test, trial, bs, Cd, n):
     dm.bilinear_diagonal(test, trial, bs, Cd.data_ptr(), out.data_ptr())
     torch.cuda.synchronize()
     return out.cpu().numpy()
-
-
-def _value_size(kind, G, bs):
-    return {"value": bs, "grad": bs * G, "F": G * G, "value_grad": bs * (1 + G), "eps": 4 if G == 2 else 6}[kind]
 
 
 @pytest.mark.parametrize("cell", list(CELLS))

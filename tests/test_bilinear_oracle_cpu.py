@@ -7,57 +7,10 @@ the central finite difference of the hyperelastic residual inner(grad v, P(I + g
 symmetry for the Isihara tangent, and the heat demo's explicit Jacobian form (demo_nonlinear_heat_equation_part2.py:328-329)."""
 import numpy as np
 
+from oracle.form_oracle import bilinear_diag_ref, bilinear_ref, tables
 from oracle.icnn_oracle import isihara_stress_tangent
-from oracle.operand_oracle import DEFGRAD, EPS_MANDEL, GRAD, VALUE, VALUE_GRAD, eval_operand, operand_adjoint, tangent_apply
+from oracle.operand_oracle import DEFGRAD, GRAD, VALUE, eval_operand, operand_adjoint, tangent_apply
 from tools.synthetic import structured_mesh
-
-KIND_ID = {"value": VALUE, "grad": GRAD, "eps": EPS_MANDEL, "F": DEFGRAD, "value_grad": VALUE_GRAD}
-
-
-def _tables(m):
-    return m.dofmap, m.geom_dofmap, m.x, m.phi, m.dphi, m.dpsi
-
-
-def bilinear_ref(m, test, trial, bs, C, v):
-    """sum_q w |det J| B_test^T C B_trial v, C of shape (n_points, D_test, D_trial). "F" is taken as its linearisation, grad."""
-    trial_id = GRAD if trial == "F" else KIND_ID[trial]
-    e = eval_operand(trial_id, bs, v, *_tables(m))                                 # (nc, nq, D_trial)
-    nc, nq, dr = e.shape
-    t = np.einsum("cqrs,cqs->cqr", np.asarray(C).reshape(nc, nq, -1, dr), e)
-    return operand_adjoint(KIND_ID[test], bs, t, m.weights, *_tables(m), m.node_x.shape[0])
-
-
-def node_colours(m):
-    """Greedy colouring of the field nodes: two nodes of one cell never share a colour."""
-    nn = m.node_x.shape[0]
-    cells_of = [[] for _ in range(nn)]
-    for c, nodes in enumerate(m.dofmap):
-        for a in nodes:
-            cells_of[a].append(c)
-    colour = -np.ones(nn, dtype=np.int64)
-    for a in range(nn):
-        taken = {colour[b] for c in cells_of[a] for b in m.dofmap[c]}
-        k = 0
-        while k in taken:
-            k += 1
-        colour[a] = k
-    return colour
-
-
-def diagonal_by_probes(apply, n_nodes, bs, colour):
-    """diag(K) from K applied to sums of unit vectors: the nodes of one colour share no cell, so (K sum_j e_j)_i = K_ii on them."""
-    diag = np.zeros((n_nodes, bs))
-    for k in range(colour.max() + 1):
-        sel = colour == k
-        for i in range(bs):
-            v = np.zeros((n_nodes, bs))
-            v[sel, i] = 1.0
-            diag[sel, i] = apply(v.reshape(-1)).reshape(n_nodes, bs)[sel, i]
-    return diag.reshape(-1)
-
-
-def bilinear_diag_ref(m, test, trial, bs, C):
-    return diagonal_by_probes(lambda v: bilinear_ref(m, test, trial, bs, C, v), m.node_x.shape[0], bs, node_colours(m))
 
 
 def _hyper_setup(seed=0):
@@ -66,12 +19,12 @@ def _hyper_setup(seed=0):
     u = 0.01 * rng.normal(size=m.node_x.shape[0] * 2)         # det F > 0 everywhere
 
     def tangent(uu):
-        F = eval_operand(DEFGRAD, 2, uu, *_tables(m)).reshape(-1, 4)
+        F = eval_operand(DEFGRAD, 2, uu, *tables(m)).reshape(-1, 4)
         return isihara_stress_tangent(F)
 
     def residual(uu):
         _, P = tangent(uu)
-        return operand_adjoint(DEFGRAD, 2, P.reshape(m.num_cells, m.nq, 4), m.weights, *_tables(m), m.node_x.shape[0])
+        return operand_adjoint(DEFGRAD, 2, P.reshape(m.num_cells, m.nq, 4), m.weights, *tables(m), m.node_x.shape[0])
 
     return m, rng, u, tangent, residual
 
@@ -101,7 +54,7 @@ def test_eps_pair_is_tangent_apply():
     rng = np.random.Generator(np.random.PCG64(2))
     C = rng.normal(size=(m.num_cells * m.nq, 4, 4))
     v = rng.normal(size=m.node_x.shape[0] * 2)
-    ref = tangent_apply(C, v, m.weights, *_tables(m), m.node_x.shape[0])
+    ref = tangent_apply(C, v, m.weights, *tables(m), m.node_x.shape[0])
     assert np.abs(bilinear_ref(m, "eps", "eps", 2, C, v) - ref).max() <= 1e-13 * np.abs(ref).max()
 
 
@@ -112,8 +65,8 @@ def _heat_setup():
     T = m.node_x[:, 0] ** 2 + m.node_x[:, 1]
 
     def flux(TT):
-        Tq = eval_operand(VALUE, 1, TT, *_tables(m))[..., 0]
-        s = eval_operand(GRAD, 1, TT, *_tables(m))
+        Tq = eval_operand(VALUE, 1, TT, *tables(m))[..., 0]
+        s = eval_operand(GRAD, 1, TT, *tables(m))
         k = 1.0 / (A + B * Tq)
         return Tq, s, k
 
@@ -130,15 +83,15 @@ def test_heat_action_is_the_explicit_jacobian_form():
     That = rng.normal(size=T.size)
     act = bilinear_ref(m, "grad", "value_grad", 1, Cb, That)
     # J_manual = inner(B k^2 sigma T_hat, grad T~) dx + inner(-k I grad T_hat, grad T~) dx
-    Th = eval_operand(VALUE, 1, That, *_tables(m))
-    gTh = eval_operand(GRAD, 1, That, *_tables(m))
+    Th = eval_operand(VALUE, 1, That, *tables(m))
+    gTh = eval_operand(GRAD, 1, That, *tables(m))
     S = B * k[..., None] ** 2 * s * Th - k[..., None] * gTh
-    manual = operand_adjoint(GRAD, 1, S, m.weights, *_tables(m), m.node_x.shape[0])
+    manual = operand_adjoint(GRAD, 1, S, m.weights, *tables(m), m.node_x.shape[0])
     assert np.abs(act - manual).max() <= 1e-13 * np.abs(manual).max()
     # and the derivative of the flux residual inner(q, grad T~) dx
     def residual(TT):
         _, ss, kk = flux(TT)
-        return operand_adjoint(GRAD, 1, -kk[..., None] * ss, m.weights, *_tables(m), m.node_x.shape[0])
+        return operand_adjoint(GRAD, 1, -kk[..., None] * ss, m.weights, *tables(m), m.node_x.shape[0])
     h = 1e-6
     fd = (residual(T + h * That) - residual(T - h * That)) / (2 * h)
     assert np.abs(act - fd).max() <= 1e-7 * np.abs(act).max()

@@ -8,13 +8,11 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from test_amg_nns_oracle_cpu import elastic_C3
-from test_assemble_oracle_cpu import pattern_ref
-from test_bilinear_gpu import _cuda
-from test_block_inverse_oracle_cpu import (ACCEPTED, DENSE_CASES, U, adversarial_blocks, cofactor_bound, exact_inverse, gj_exchanges,
-                                           node_blocks, refined_solve, values_with_blocks, zero_diagonal_system)
-from test_krylov_gpu import _assemble, _torch, meshes  # noqa: F401  (meshes is a fixture)
-from test_krylov_oracle_cpu import bottom_dofs
+from oracle.block_inverse_oracle import (ACCEPTED, DENSE_CASES, U, adversarial_blocks, cofactor_bound, exact_inverse, gj_exchanges,
+                                         node_blocks, refined_solve, values_with_blocks, zero_diagonal_system)
+from oracle.form_oracle import pattern_ref
+from oracle.krylov_oracle import bottom_dofs, elastic_C3
+from solver_cases import _assemble, _cuda, _torch, meshes  # noqa: F401  (meshes is a fixture)
 from tools.synthetic import structured_mesh
 
 pytestmark = pytest.mark.gpu

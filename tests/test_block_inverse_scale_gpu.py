@@ -6,9 +6,7 @@ exactly with a power of two as long as nothing leaves the range of double, so om
 import numpy as np
 import pytest
 
-from test_amg_kcycle_gpu import _hierarchy
-from test_bilinear_gpu import _cuda
-from test_krylov_gpu import _torch, meshes  # noqa: F401  (meshes is a fixture)
+from solver_cases import _case_hierarchy, _cuda, _torch, meshes  # noqa: F401  (meshes is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +16,7 @@ def test_the_setup_commutes_with_a_power_of_two(ctx, meshes, which):
     from dolfinx_external_operator_amd.operand_eval import DeviceCSR
 
     torch = _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, which)
+    A, amg = _case_hierarchy(ctx, meshes, which)
     r = _cuda(np.random.Generator(np.random.PCG64(4)).normal(size=A.shape[0]))
     z = amg.apply(r).clone()
     dinv = [amg.level_dinv(l) for l in range(amg.n_levels - 1)]

@@ -14,7 +14,7 @@ from tools.synthetic import structured_mesh
 def float64_ratios(case):
     """Worst componentwise distance of float64 NumPy from the long-double reference on one mesh, per entry point, in units of
     2^-53 * mag[k]."""
-    from test_sharding import numpy_expand_tangent
+    from oracle.consumer_reference import numpy_expand_tangent
 
     m = build_mesh(case)
     x = make_inputs(case, m)
@@ -113,10 +113,10 @@ def test_tangent_from_state_equals_the_c_port_of_the_reference(oracle, d):
     """vm_tangent_from_state fed the (sigma, dp) the oracle fixture's von Mises returns (the C port of the reference's statements,
     pinned by the goldens) against the C_tang of the same call. The port forms the tangent from the TRIAL state, the closed form from
     the returned one: equal in exact arithmetic. Tolerance, measured here: 8 times the distance of the float64 closed form
-    (tests/test_sharding.py::numpy_expand_tangent) from the long-double one, max over all entries — measured 3.5e-10 (d = 4) and
+    (oracle/consumer_reference.py::numpy_expand_tangent) from the long-double one, max over all entries — measured 3.5e-10 (d = 4) and
     3.0e-10 (d = 6) on entries up to 9.4e4, the port's own distance 4.6e-11 / 3.5e-11. Elastic points: C_elas, bit for bit."""
     from conftest import vm_inputs
-    from test_sharding import numpy_expand_tangent
+    from oracle.consumer_reference import numpy_expand_tangent
 
     deps, sigma_n, p = vm_inputs(3000, d, seed=11)
     deps[:1000] *= 0.2          # a third of the points stays elastic

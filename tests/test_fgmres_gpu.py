@@ -7,11 +7,8 @@ F1_RES_TOL: 100 x the float64 oracle's own deviation from the closed form)."""
 import numpy as np
 import pytest
 
-from test_amg_gpu import _system
-from test_bilinear_gpu import _cuda
-from test_krylov_gpu import _torch, meshes  # noqa: F401  (meshes is a fixture)
-from test_krylov_known_answers_gpu import F1_RES_TOL, F1_X_TOL, _shift
-from test_krylov_oracle_cpu import U, cycle_rhs, cyclic_shift_src, precond_diagonal, shift_solution
+from oracle.krylov_oracle import U, cycle_rhs, cyclic_shift_src, precond_diagonal, shift_solution
+from solver_cases import F1_RES_TOL, F1_X_TOL, _assembled_system, _cuda, _shift, _torch, meshes  # noqa: F401  (meshes is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -75,7 +72,7 @@ def test_fixed_preconditioners_take_the_iterations_of_gmres(ctx, meshes):  # noq
     from dolfinx_external_operator_amd import fgmres, gmres
 
     torch = _torch(ctx)
-    A, bs, bcs = _system(ctx, meshes, "heat")
+    A, bs, bcs = _assembled_system(ctx, meshes, "heat")
     S = A.to_scipy()
     b = np.random.Generator(np.random.PCG64(1)).normal(size=S.shape[0])
     bd = _cuda(b)
@@ -102,7 +99,7 @@ def test_multigrid_on_a_callable_operator(ctx, meshes):  # noqa: F811
     from dolfinx_external_operator_amd import cg, fgmres, gmres
 
     torch = _torch(ctx)
-    A, bs, bcs = _system(ctx, meshes, "spd_quad")
+    A, bs, bcs = _assembled_system(ctx, meshes, "spd_quad")
     amg = A.amg(bcs, coarse_rows=40)
     bd = _cuda(np.random.Generator(np.random.PCG64(2)).normal(size=A.shape[0]))
 
@@ -218,7 +215,7 @@ def test_one_workspace_serves_gmres_and_fgmres_in_either_order(ctx, meshes):  # 
     from dolfinx_external_operator_amd import fgmres, gmres
 
     torch = _torch(ctx)
-    A, bs, bcs = _system(ctx, meshes, "heat")
+    A, bs, bcs = _assembled_system(ctx, meshes, "heat")
     n, restart = A.shape[0], 17
     M = A.block_jacobi()
     bd = _cuda(np.random.Generator(np.random.PCG64(4)).normal(size=n))

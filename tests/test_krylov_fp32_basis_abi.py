@@ -3,7 +3,7 @@ import ctypes as C
 import inspect
 import re
 
-from test_abi import header_functions
+from abi_header import header_functions
 
 NEW = ("dxo_krylov_create_basis", "dxo_krylov_basis_info")
 

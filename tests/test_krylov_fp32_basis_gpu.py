@@ -12,11 +12,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_amg_kcycle_gpu import _hierarchy
-from test_krylov_fp32_basis_oracle_cpu import REF_CB_F2_RES, REF_CB_F2_X, gmres_cb_ref, unit_rhs
-from test_krylov_gpu import _cuda, _system, _torch, meshes  # noqa: F401  (meshes is a fixture)
-from test_krylov_known_answers_gpu import _f2, _grid_cap, _reorth, _shift, _shifted
-from test_krylov_oracle_cpu import F2_D, F2_MAIN, MARGIN, cycle_rhs, cyclic_shift_src, shifted_op, shifted_residual, xdev
+from oracle.krylov_oracle import (F2_D, F2_MAIN, MARGIN, REF_CB_F2_RES, REF_CB_F2_X, cyclic_shift_src, gmres_cb_ref, shifted_op,
+                                  shifted_residual, unit_rhs, xdev)
+from solver_cases import (_case_hierarchy, _cuda, _f2, _grid_cap, _krylov_system, _reorth, _shift, _torch,
+                          meshes)  # noqa: F401  (meshes is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -193,7 +192,7 @@ def test_the_stored_basis_is_normalised_and_orthogonal_to_float_rounding(ctx, me
         out = gmres(dev, _cuda(b), restart=64, rtol=0.0, maxiter=k, ctx=ctx, basis="fp32")
         assert _flags(out) == (k, 1, False, False)
         _check_stored(ctx, out, b.size, 64, k)
-    A, bs = _system(ctx, meshes, "hex_eps")
+    A, bs = _krylov_system(ctx, meshes, "hex_eps")
     rhs = _cuda(np.random.Generator(np.random.PCG64(8)).normal(size=A.shape[0]))
     for solve in (gmres, fgmres):
         out = solve(A, rhs.clone(), M=A.block_jacobi(), restart=30, rtol=0.0, maxiter=30, basis="fp32")
@@ -227,7 +226,7 @@ def test_assembled_systems_converge_on_the_true_residual(ctx, meshes, which):  #
     from dolfinx_external_operator_amd import fgmres, gmres
 
     _torch(ctx)
-    A, bs = _system(ctx, meshes, which)
+    A, bs = _krylov_system(ctx, meshes, which)
     b = _cuda(np.random.Generator(np.random.PCG64(8)).normal(size=A.shape[0]))
     M = A.block_jacobi()
     _both_bases(gmres, A, b, M, which)
@@ -239,7 +238,7 @@ def test_multigrid_preconditioned_solves_converge_on_the_true_residual(ctx, mesh
     from dolfinx_external_operator_amd import fgmres, gmres
 
     _torch(ctx)
-    A, amg = _hierarchy(ctx, meshes, "heat48", precision=precision)
+    A, amg = _case_hierarchy(ctx, meshes, "heat48", precision=precision)
     b = _cuda(np.random.Generator(np.random.PCG64(1)).normal(size=A.shape[0]))
     for solve in (gmres, fgmres):
         _both_bases(solve, A, b, amg, f"heat48 AMG {precision}")
@@ -251,7 +250,7 @@ def test_the_basis_sees_normalised_vectors_whatever_the_scale_of_b(ctx, meshes):
 
     torch = _torch(ctx)
     src, b, D, dev = _f2(torch, *F2_MAIN)
-    A, bs = _system(ctx, meshes, "heat")
+    A, bs = _krylov_system(ctx, meshes, "heat")
     rhs = np.random.Generator(np.random.PCG64(8)).normal(size=A.shape[0])
     cases = (("F2", lambda v, **kw: gmres(dev, v, restart=30, ctx=ctx, **kw), b),
              ("heat gmres", lambda v, **kw: gmres(A, v, M=A.block_jacobi(), **kw), rhs),
@@ -271,7 +270,7 @@ def test_two_solves_are_bit_identical(ctx, meshes):  # noqa: F811
     from dolfinx_external_operator_amd import fgmres, gmres
 
     torch = _torch(ctx)
-    A, bs = _system(ctx, meshes, "hyperelastic")              # 41 cycles: a long history to repeat bit for bit
+    A, bs = _krylov_system(ctx, meshes, "hyperelastic")              # 41 cycles: a long history to repeat bit for bit
     M = A.block_jacobi()
     b = _cuda(np.random.Generator(np.random.PCG64(6)).normal(size=A.shape[0]))
     for solve in (gmres, fgmres):
@@ -293,7 +292,7 @@ def test_fgmres_takes_the_iterations_of_gmres_with_a_fixed_preconditioner(ctx, m
     from dolfinx_external_operator_amd import fgmres, gmres
 
     _torch(ctx)
-    A, bs = _system(ctx, meshes, which)
+    A, bs = _krylov_system(ctx, meshes, which)
     M = A.block_jacobi()
     b = _cuda(np.random.Generator(np.random.PCG64(8)).normal(size=A.shape[0]))
     g, f = gmres(A, b, M=M, rtol=1e-10, basis="fp32"), fgmres(A, b, M=M, rtol=1e-10, basis="fp32")

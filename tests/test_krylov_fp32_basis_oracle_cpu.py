@@ -7,103 +7,12 @@ stays float64. On a family whose basis vectors are unit vectors it must be gmres
 residual with at most one cycle more. Its own deviation from the long-double answers of F2 is measured here and recorded as
 REF_CB_F2_*; tests/test_krylov_fp32_basis_gpu.py holds the device to MARGIN x these."""
 import numpy as np
-import pytest
 
-from test_krylov_oracle_cpu import (F2_D, F2_MAIN, SHIFT_D, U, _f2, apply_pc, block_jacobi_ref, cyclic_shift_src, eps_matrix, gmres_ref,
-                                    heat_matrix, shift_op, shifted_op, shifted_residual, to_pattern_csr, xdev)
+from oracle.krylov_oracle import (F2_D, F2_MAIN, REF_CB_F2_RES, REF_CB_F2_X, SHIFT_D, U, block_jacobi_ref, cyclic_shift_src, eps_matrix,
+                                  f2_problem, gmres_cb_ref, gmres_ref, heat_matrix, same, shift_op, shifted_op, shifted_residual,
+                                  to_pattern_csr, unit_rhs, xdev)
 
-# gmres_cb_ref against the long-double answers of F2 (n = 2965, restart 64, k = 1..64), measured by
-# test_reference_deviation_of_the_compressed_basis below, which prints them (-s): the residual against the closed form, relative,
-# 2.2e-3 (at k = 64); x_k against gmres_ref in long double, max|dx| / max|x|, 5.8e-8. Both are the rounding of v_0: the cycle solves
-# for beta v_0 with v_0 = fl32(r / beta), so the part beta (r / beta - v_0) of the residual, about 2^-24 |r|, is not touched by this
-# cycle. At k = 64 the closed form has fallen to 3.8e-7 of |r| and that part is a visible share of it: this is the "seven digits per
-# cycle" of the option, seen on a known answer. The constants are round upper bounds.
-REF_CB_F2_RES, REF_CB_F2_X = 3e-3, 1e-7
 U32 = 2.0 ** -24                                        # unit roundoff of float32
-
-
-def f32(v):
-    """v rounded to float32 (nearest even) and widened again."""
-    return v.astype(np.float32).astype(np.float64)
-
-
-def gmres_cb_ref(A, b, x0=None, inv=None, m=30, rtol=1e-10, atol=0.0, maxiter=1000, reorth=True, full=False, basis=None):
-    """gmres_ref (float64) with the basis stored in float32. `basis`: a list that receives the stored rows of the last cycle."""
-    n = b.size
-    x = np.zeros(n) if x0 is None else x0.astype(float).copy()
-    bnorm = np.linalg.norm(b)
-    total, breakdown, cycles = 0, False, 0
-
-    def result(x, conv, res):
-        return (x, total, conv, res, breakdown, cycles) if full else (x, total, conv, res)
-
-    if bnorm == 0.0:
-        return result(np.zeros(n), True, 0.0)
-    tol = max(rtol * bnorm, atol)
-    while True:
-        r = b - A @ x
-        beta = np.linalg.norm(r)
-        if beta <= tol:
-            return result(x, True, beta / bnorm)
-        if total >= maxiter or breakdown:
-            return result(x, False, beta / bnorm)
-        cycles += 1
-        V = np.zeros((m + 1, n))
-        H = np.zeros((m + 1, m))
-        cs, sn, g = np.zeros(m), np.zeros(m), np.zeros(m + 1)
-        V[0] = f32(r / beta)
-        g[0] = beta
-        k = 0
-        for j in range(m):
-            if total + j >= maxiter:
-                break
-            w = A @ apply_pc(inv, V[j])
-            h = V[: j + 1] @ w
-            w = w - V[: j + 1].T @ h
-            if reorth:
-                c = V[: j + 1] @ w
-                w = w - V[: j + 1].T @ c
-                h = h + c
-            hn = np.linalg.norm(w)
-            V[j + 1] = f32(w / hn) if hn > 0 else 0.0
-            col = np.concatenate([h, [hn]])
-            for i in range(j):
-                t = cs[i] * col[i] + sn[i] * col[i + 1]
-                col[i + 1] = -sn[i] * col[i] + cs[i] * col[i + 1]
-                col[i] = t
-            rr = np.hypot(col[j], hn)
-            cs[j], sn[j] = (col[j] / rr, hn / rr) if rr > 0 else (1.0, 0.0)
-            col[j], col[j + 1] = rr, 0.0
-            H[: j + 2, j] = col
-            g[j + 1] = -sn[j] * g[j]
-            g[j] = cs[j] * g[j]
-            k = j + 1
-            if not hn > 0:
-                breakdown = True
-            if abs(g[j + 1]) <= tol or not hn > 0:
-                break
-        if basis is not None:
-            basis[:] = [V.astype(np.float32)]
-        if k == 0:
-            return result(x, False, beta / bnorm)
-        y = np.zeros(k)
-        for i in range(k - 1, -1, -1):
-            s = g[i] - H[i, i + 1: k] @ y[i + 1:]
-            y[i] = s / H[i, i] if H[i, i] != 0 else 0.0
-        x = x + apply_pc(inv, V[:k].T @ y)
-        total += k
-
-
-def unit_rhs(n, s):
-    """0.25 e_s: |b| and b / |b| are exact, and so is every basis vector of a permutation."""
-    b = np.zeros(n)
-    b[s] = 0.25
-    return b
-
-
-def same(a, b):
-    """Two results of the oracles, bit for bit."""
-    return all(np.array_equal(np.asarray(p), np.asarray(q)) for p, q in zip(a, b)) and len(a) == len(b)
 
 
 def test_unit_vector_bases_give_gmres_ref_bit_for_bit():
@@ -135,7 +44,7 @@ def _systems():
 
 def test_it_converges_on_the_true_residual_with_at_most_one_cycle_more():
     rtol = 1e-10
-    src, b, A = _f2(*F2_MAIN)
+    src, b, A = f2_problem(*F2_MAIN)
     for m in (30, 64):
         x, its, conv, res = gmres_cb_ref(A, b, m=m, rtol=rtol, maxiter=2000)
         _, its64, conv64, _ = gmres_ref(A, b, m=m, rtol=rtol, maxiter=2000)
@@ -168,7 +77,7 @@ def test_it_converges_on_the_true_residual_with_at_most_one_cycle_more():
 def test_reference_deviation_of_the_compressed_basis():
     """gmres_cb_ref against the closed form (residual) and against gmres_ref in long double (x_k) on F2: what REF_CB_F2_* bound."""
     L = np.longdouble
-    src, b, A = _f2(*F2_MAIN)
+    src, b, A = f2_problem(*F2_MAIN)
     worst_r = worst_x = 0.0
     for k in range(1, 65):
         x, its, conv, res, brk, cycles = gmres_cb_ref(A, b, m=64, rtol=0.0, maxiter=k, full=True)

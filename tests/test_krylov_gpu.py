@@ -5,55 +5,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_assemble_oracle_cpu import heat_setting
-from test_bilinear_gpu import CELLS, _cuda, _value_size
-from test_krylov_oracle_cpu import block_jacobi_ref, bottom_dofs, boundary_dofs, cg_ref, elastic_C, gmres_ref
+from oracle.krylov_oracle import block_jacobi_ref, bottom_dofs, cg_ref, elastic_C, elastic_C3, gmres_ref
+from solver_cases import CELLS, _assemble, _cuda, _krylov_system, _torch, _value_size, meshes  # noqa: F401  (meshes is a fixture)
 from tools.synthetic import structured_mesh
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch(ctx):
-    import torch
-
-    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
-    return torch
-
-
-def _assemble(ctx, dm, test, trial, bs, Cb, bcs=None):
-    torch = _torch(ctx)
-    bt = None if bcs is None else torch.from_numpy(np.asarray(bcs, dtype=np.int32)).cuda()
-    Cd = _cuda(Cb)                  # kept alive until the assembly has run
-    A = dm.bilinear_assemble(test, trial, bs, Cd.data_ptr(), dm.csr_pattern(bs), bcs=bt)
-    torch.cuda.synchronize()
-    return A
-
-
-def _elastic_C3(n_points, seed=None):
-    lam, mu = 1.0, 0.7
-    Ce = np.zeros((6, 6))
-    Ce[:3, :3] = lam
-    Ce[np.arange(6), np.arange(6)] += 2 * mu
-    Cb = np.broadcast_to(Ce, (n_points, 6, 6)).copy()
-    if seed is not None:
-        Cb += 0.3 * np.random.Generator(np.random.PCG64(seed)).normal(size=Cb.shape)
-    return Cb
-
-
-@pytest.fixture
-def meshes(ctx):
-    from dolfinx_external_operator_amd import DeviceMesh
-
-    made = []
-
-    def make(m):
-        dm = DeviceMesh.from_synthetic(m, ctx=ctx)
-        made.append(dm)
-        return dm
-
-    yield make
-    for dm in made:
-        dm.close()
 
 
 # ---- SpMV
@@ -98,7 +54,7 @@ def test_block_jacobi_matches_numpy(ctx, meshes, cell, n):
     m = structured_mesh(cell, n, 2, distort=0.15, seed=5)
     dm = meshes(m)
     G = m.gdim
-    for bs, Cb, pair in ((G, elastic_C(m, 3) if G == 2 else _elastic_C3(m.num_cells * m.nq, 3), ("eps", "eps")),
+    for bs, Cb, pair in ((G, elastic_C(m, 3) if G == 2 else elastic_C3(m.num_cells * m.nq, 3), ("eps", "eps")),
                          (1, np.random.Generator(np.random.PCG64(2)).normal(size=(m.num_cells * m.nq, G, 1 + G)), ("grad", "value_grad"))):
         bcs = bottom_dofs(m, bs)
         A = _assemble(ctx, dm, *pair, bs, Cb, bcs=bcs)
@@ -123,38 +79,13 @@ def test_zeroed_block_is_singular(ctx, meshes):
         A.block_jacobi()
 
 
-# ---- GMRES on assembled systems
-def _system(ctx, meshes, which):
-    """(DeviceCSR, bs) of the named system, with Dirichlet rows."""
-    torch = _torch(ctx)
-    if which == "heat":
-        m, dqdT, dqds, _ = heat_setting(16)
-        Cb = np.concatenate([dqdT[..., None], dqds], axis=-1).reshape(m.num_cells * m.nq, 2, 3)
-        return _assemble(ctx, meshes(m), "grad", "value_grad", 1, -Cb, bcs=boundary_dofs(m, 1)), 1
-    if which == "hyperelastic":
-        from dolfinx_external_operator_amd import MEM_DEVICE, IsiharaParams
-
-        m = structured_mesh("triangle", (10, 10), 2, distort=0.1, seed=3)
-        dm = meshes(m)
-        npts = m.num_cells * m.nq
-        u = torch.from_numpy((0.08 * m.node_x * m.node_x[:, 1:2]).reshape(-1).copy()).cuda()
-        dP, P = torch.zeros(npts * 16, dtype=torch.float64, device="cuda"), torch.zeros(npts * 4, dtype=torch.float64, device="cuda")
-        ctx.isihara_field(IsiharaParams(0.5, 1.0, 1.0, 1.5), dm._h, MEM_DEVICE, u.data_ptr(), dP.data_ptr(), P.data_ptr())
-        torch.cuda.synchronize()
-        return _assemble(ctx, dm, "grad", "grad", 2, dP.cpu().numpy().reshape(npts, 4, 4), bcs=bottom_dofs(m, 2)), 2
-    m = structured_mesh("hexahedron", (4, 3, 3), 1, distort=0.1, seed=2)
-    Cb = _elastic_C3(m.num_cells * m.nq)
-    Cb[:, :3, 3:] += 0.2                                  # a non-symmetric coupling
-    return _assemble(ctx, meshes(m), "eps", "eps", 3, Cb, bcs=bottom_dofs(m, 3)), 3
-
-
 @pytest.mark.parametrize("which", ["heat", "hyperelastic", "hex_eps"])
 def test_gmres_on_assembled_systems(ctx, meshes, which):
     import scipy.sparse.linalg
 
     from dolfinx_external_operator_amd import gmres
 
-    A, bs = _system(ctx, meshes, which)
+    A, bs = _krylov_system(ctx, meshes, which)
     S = A.to_scipy()
     b = np.random.Generator(np.random.PCG64(8)).normal(size=S.shape[0])
     ref = scipy.sparse.linalg.spsolve(S.tocsc(), b)
@@ -273,7 +204,7 @@ def test_reproducible_early_exits_and_overshoot(ctx, meshes):
     from dolfinx_external_operator_amd import gmres
 
     torch = _torch(ctx)
-    A, bs = _system(ctx, meshes, "hyperelastic")
+    A, bs = _krylov_system(ctx, meshes, "hyperelastic")
     M = A.block_jacobi()
     b = _cuda(np.random.Generator(np.random.PCG64(6)).normal(size=A.shape[0]))
     x0 = _cuda(np.random.Generator(np.random.PCG64(7)).normal(size=A.shape[0]))

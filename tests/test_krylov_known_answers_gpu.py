@@ -10,61 +10,13 @@ by the order of the sums. Nothing else of the families is left out."""
 import numpy as np
 import pytest
 
-from test_krylov_gpu import _cuda, _system, _torch, meshes  # noqa: F401  (meshes: the fixture of the CSR cross-check)
-from test_krylov_oracle_cpu import (F2_C, F2_D, F2_MAIN, F2_S, MARGIN, REF_F1_RES, REF_F1_X, REF_F2_RES, REF_F2_X, SHIFT_D, U,
-                                    FnOperator, alternating_diag, block_jacobi_ref, cg_ref, cycle_rhs, cyclic_shift_src, exact_breakdown_rhs,
-                                    gmres_ref, late_zero_op, nilpotent_op, precond_diagonal, repeated_diag, shift_solution,
-                                    shifted_atol, shifted_op, shifted_residual, xdev)
+from oracle.krylov_oracle import (F2_D, F2_MAIN, MARGIN, SHIFT_D, U, FnOperator, alternating_diag, block_jacobi_ref, cg_ref, cycle_rhs,
+                                  cyclic_shift_src, exact_breakdown_rhs, gmres_ref, late_zero_op, nilpotent_op, repeated_diag,
+                                  shift_solution, shifted_atol, shifted_op, shifted_residual, xdev)
+from solver_cases import (F1_RES_TOL, F1_X_TOL, F2_RES_TOL, F2_X_TOL, _cuda, _f2, _grid_cap, _krylov_system, _reorth, _shift, _torch,
+                          meshes)  # noqa: F401  (meshes: the fixture of the CSR cross-check)
 
 pytestmark = pytest.mark.gpu
-
-# The device against the closed forms and the float64 oracle. Not derivable as one constant (the device adds its dot products over
-# nb partials with FMA, in another order than NumPy), so: MARGIN = 100 x the oracle's own deviation from the long-double answers,
-# REF_* in test_krylov_oracle_cpu.py, measured there as 4.5e-16 max|b| / 3.6e-16 (F1: x, residual at termination) and 6.5e-16
-# relative / 5.2e-16 max|x| (F2: residual, x_k) and rounded up to 6e-16 / 4e-16 / 1e-15 / 1e-15. Measured on an MI355X (256 CUs),
-# the largest over all cases the tests below print: F1 x 4.4e-16 max|b|, F1 residual 3.1e-16, F2 residual 7.0e-16 relative,
-# F2 x_k 5.2e-16 max|x|. One wrong rotation or Hessenberg entry changes these by O(1).
-F1_X_TOL, F1_RES_TOL = MARGIN * REF_F1_X, MARGIN * REF_F1_RES
-F2_RES_TOL, F2_X_TOL = MARGIN * REF_F2_RES, MARGIN * REF_F2_X
-
-
-def _grid_cap(torch):
-    """Rows that one trip of the row kernels covers: nb = min(ceil(n / 256), 4 CUs) workgroups of 256."""
-    return 256 * 4 * torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _index(torch, src):
-    return torch.from_numpy(src.astype(np.int64)).cuda()
-
-
-def _shift(torch, src):
-    s = _index(torch, src)
-    return lambda v, out: torch.index_select(v, 0, s, out=out)
-
-
-def _shifted(torch, src, D=None):
-    """c I + s P, or (c I + s P) diag(D), rounded as tests/test_krylov_oracle_cpu.py::shifted_op rounds it."""
-    s = _index(torch, src)
-    tmp = torch.empty(src.size, dtype=torch.float64, device="cuda")
-
-    def apply(v, out):
-        if D is not None:
-            v = torch.mul(v, D, out=tmp)
-        torch.index_select(v, 0, s, out=out)
-        out.mul_(F2_S).add_(v, alpha=F2_C)
-
-    return apply
-
-
-def _reorth(ctx, value):
-    class Scope:
-        def __enter__(self):
-            ctx.set_option("krylov_reorth", value)
-
-        def __exit__(self, *exc):
-            ctx.set_option("krylov_reorth", 1)
-
-    return Scope()
 
 
 # ---- F1
@@ -126,13 +78,6 @@ def test_cyclic_shift_terminates_at_step_d(ctx, d):
 
 
 # ---- F2
-def _f2(torch, q, t, precond=False):
-    src, b = cyclic_shift_src(F2_D, q, t), cycle_rhs(F2_D, q, t, seed=q)
-    D = precond_diagonal(b.size) if precond else None
-    dev = _shifted(torch, src, None if D is None else _cuda(D))
-    return src, b, D, dev
-
-
 def _f2_step(gmres, ctx, dev, src, b, D, k, restart=64, closed=True, worst=None):
     """k steps on the device against the oracle's k steps (x_k) and the closed form (residual)."""
     torch = _torch(ctx)
@@ -334,7 +279,7 @@ def test_csr_gmres_follows_the_oracle_step_by_step(ctx, meshes):  # noqa: F811
     on either side, is 1e-4 of it."""
     from dolfinx_external_operator_amd import gmres
 
-    A, bs = _system(ctx, meshes, "hex_eps")
+    A, bs = _krylov_system(ctx, meshes, "hex_eps")
     S = A.to_scipy()
     b = np.random.Generator(np.random.PCG64(8)).normal(size=S.shape[0])
     inv = block_jacobi_ref(S, bs)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from dolfinx_external_operator_amd.sharding import CellBlockPartition
+from oracle.consumer_reference import numpy_expand_tangent
 
 
 def test_partition_covers_every_cell_once():
@@ -86,28 +87,6 @@ def test_two_rank_gloo_gather_reassembles_the_flat_coefficient_vectors(oracle, n
         pr.join(timeout=180)
         assert pr.exitcode == 0
     assert dict(ret) == {0: True, 1: True}
-
-
-def numpy_expand_tangent(sigma, dp, d, E=70e3, nu=0.3):
-    """NumPy statement of the tangent-from-state formulas (dxo_vm_expand_tangent), the dp = -0.0 mark of the reference's
-    0/0 point included: stand-in for the HIP rebuild kernel in the CPU-only gather test, itself checked against the
-    oracle's tangent below."""
-    lmbda, mu = E * nu / ((1 + nu) * (1 - 2 * nu)), E / (2 * (1 + nu))
-    Et = E / 100.0
-    H = E * Et / (E - Et)
-    sigma = sigma.reshape(-1, d)
-    one = np.zeros(d)
-    one[:3] = 1.0
-    C_el = lmbda * np.outer(one, one) + 2 * mu * np.eye(d)
-    dev = np.eye(d) - np.outer(one, one) / 3.0
-    s = sigma @ dev.T
-    seq = np.sqrt(1.5 * np.sum(s * s, axis=1))
-    with np.errstate(all="ignore"):
-        beta = 3 * mu * dp / (seq + 3 * mu * dp)
-        n = s / seq[:, None] * (dp > 0)[:, None]
-    a = 3 * mu * (3 * mu / (3 * mu + H) - beta)
-    a = np.where((dp == 0.0) & np.signbit(dp), np.nan, a)     # the producer's mark -> the reference's NaN tangent
-    return C_el[None] - a[:, None, None] * n[:, :, None] * n[:, None, :] - (2 * mu * beta)[:, None, None] * dev[None]
 
 
 def test_numpy_expand_matches_oracle_tangent(oracle):
