@@ -874,44 +874,62 @@ GATHER_NONE, GATHER_FULL, GATHER_COMPACT, GATHER_COMPACT_DIRECT, GATHER_COMPACT_
 MGPU_ID_BYTES = 128
 
 
-class VmState:
+class _DeviceState:
+    """What VmState and McState share: create, finalizer, close, commit and pointers of a dxo_*_state, from the prefix of its entry
+    points and the names of its arrays (the results of `<prefix>_pointers`, in its order)."""
+
+    _PREFIX: str = ""
+    _ARRAYS: tuple = ()
+
+    def __init__(self, ctx: "Context", *shape: int):
+        self.ctx = ctx
+        h = _P()
+        ctx.check(getattr(ctx.lib, self._PREFIX + "_create")(ctx._h, *shape, C.byref(h)), self._PREFIX + "_create")
+        self._h = h
+        self._fin = weakref.finalize(self, _DeviceState._destroy, ctx, self._PREFIX, h)
+
+    @staticmethod
+    def _destroy(ctx, prefix, h):
+        getattr(ctx.lib, prefix + "_destroy")(ctx._h, h)   # with a closed context (NULL) the library still frees the device block
+
+    def _do(self, what: str, *args) -> None:
+        name = f"{self._PREFIX}_{what}"
+        self.ctx.check(getattr(self.ctx.lib, name)(self.ctx._h, self._h, *args), name)
+
+    def close(self) -> None:
+        self._fin()
+
+    def commit(self) -> None:
+        self._do("commit")
+
+    def pointers(self) -> dict:
+        out = [C.c_void_p() for _ in self._ARRAYS]
+        self._do("pointers", *(C.byref(o) for o in out))
+        return dict(zip(self._ARRAYS, (o.value for o in out)))
+
+
+class VmState(_DeviceState):
     """dxo_vm_state: sigma_n, p (and the last call's sigma, dp) resident on the context's GPU.
 
     upload(sigma_n, p) once and after any change of the caller's arrays other than the load-step update;
     call(...) = dxo_von_mises_state; commit() = `p += dp; sigma_n <- sigma` on the device
     (demo_plasticity_von_mises.py:564-565)."""
 
+    _PREFIX, _ARRAYS = "dxo_vm_state", ("sigma_n", "p", "sigma", "dp")
+
     def __init__(self, ctx: "Context", d: int, n: int):
-        self.ctx, self.d, self.n = ctx, int(d), int(n)
-        h = C.c_void_p()
-        ctx.check(ctx.lib.dxo_vm_state_create(ctx._h, self.d, self.n, C.byref(h)), "dxo_vm_state_create")
-        self._h = h
-        self._fin = weakref.finalize(self, VmState._destroy, ctx, h)
-
-    @staticmethod
-    def _destroy(ctx, h):
-        ctx.lib.dxo_vm_state_destroy(ctx._h, h)   # with a closed context (NULL) the library still frees the device block
-
-    def close(self) -> None:
-        self._fin()
+        self.d, self.n = int(d), int(n)
+        super().__init__(ctx, self.d, self.n)
 
     def upload(self, sigma_n, p, mem: int = MEM_HOST) -> None:
-        self.ctx.check(self.ctx.lib.dxo_vm_state_upload(self.ctx._h, self._h, int(mem), _ptr(sigma_n), _ptr(p)), "dxo_vm_state_upload")
+        self._do("upload", int(mem), _ptr(sigma_n), _ptr(p))
 
     def download(self, sigma_n=None, p=None, mem: int = MEM_HOST):
         if mem == MEM_HOST:
             sigma_n = np.empty(self.n * self.d) if sigma_n is None else sigma_n
             p = np.empty(self.n) if p is None else p
-        self.ctx.check(self.ctx.lib.dxo_vm_state_download(self.ctx._h, self._h, int(mem), _ptr(sigma_n), _ptr(p)), "dxo_vm_state_download")
+        self._do("download", int(mem), _ptr(sigma_n), _ptr(p))
         return sigma_n, p
-
-    def commit(self) -> None:
-        self.ctx.check(self.ctx.lib.dxo_vm_state_commit(self.ctx._h, self._h), "dxo_vm_state_commit")
-
-    def pointers(self) -> dict:
-        out = [C.c_void_p() for _ in range(4)]
-        self.ctx.check(self.ctx.lib.dxo_vm_state_pointers(self.ctx._h, self._h, *(C.byref(o) for o in out)), "dxo_vm_state_pointers")
-        return dict(zip(("sigma_n", "p", "sigma", "dp"), (o.value for o in out)))
 
     def call(self, prm: VmParams, mem: int, deps, C_tang, sigma=None, dp=None) -> None:
         rc = self.ctx.lib.dxo_von_mises_state(self.ctx._h, C.byref(prm), self._h, int(mem), _ptr(deps), _ptr(C_tang), _ptr(sigma), _ptr(dp))
@@ -923,39 +941,23 @@ class VmState:
         self.ctx.check(rc, "dxo_von_mises_field_state")
 
 
-class McState:
+class McState(_DeviceState):
     """dxo_mc_state: device mirror of the Mohr-Coulomb history variable sigma_n plus the stress of the last call."""
 
+    _PREFIX, _ARRAYS = "dxo_mc_state", ("sigma_n", "sigma")
+
     def __init__(self, ctx: "Context", n: int):
-        self.ctx, self.n = ctx, int(n)
-        h = _P()
-        ctx.check(ctx.lib.dxo_mc_state_create(ctx._h, self.n, C.byref(h)), "dxo_mc_state_create")
-        self._h = h
-        self._fin = weakref.finalize(self, McState._destroy, ctx, h)
-
-    @staticmethod
-    def _destroy(ctx, h):
-        ctx.lib.dxo_mc_state_destroy(ctx._h, h)   # with a closed context (NULL) the library still frees the device block
-
-    def close(self) -> None:
-        self._fin()
+        self.n = int(n)
+        super().__init__(ctx, self.n)
 
     def upload(self, sigma_n, mem: int = MEM_HOST) -> None:
-        self.ctx.check(self.ctx.lib.dxo_mc_state_upload(self.ctx._h, self._h, int(mem), _ptr(sigma_n)), "dxo_mc_state_upload")
+        self._do("upload", int(mem), _ptr(sigma_n))
 
     def download(self, sigma_n=None, mem: int = MEM_HOST):
         if mem == MEM_HOST and sigma_n is None:
             sigma_n = np.empty(self.n * 4)
-        self.ctx.check(self.ctx.lib.dxo_mc_state_download(self.ctx._h, self._h, int(mem), _ptr(sigma_n)), "dxo_mc_state_download")
+        self._do("download", int(mem), _ptr(sigma_n))
         return sigma_n
-
-    def commit(self) -> None:
-        self.ctx.check(self.ctx.lib.dxo_mc_state_commit(self.ctx._h, self._h), "dxo_mc_state_commit")
-
-    def pointers(self) -> dict:
-        out = [C.c_void_p() for _ in range(2)]
-        self.ctx.check(self.ctx.lib.dxo_mc_state_pointers(self.ctx._h, self._h, *(C.byref(o) for o in out)), "dxo_mc_state_pointers")
-        return dict(zip(("sigma_n", "sigma"), (o.value for o in out)))
 
     def call(self, prm: McParams, mem: int, deps, C_tang, sigma=None, niter=None, yielding=None, norm_res=None, dlambda=None) -> None:
         rc = self.ctx.lib.dxo_mohr_coulomb_state(self.ctx._h, C.byref(prm), self._h, int(mem), _ptr(deps), _ptr(C_tang), _ptr(sigma),

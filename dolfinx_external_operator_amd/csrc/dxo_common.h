@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -153,6 +154,13 @@ inline int dxo_fail(dxo_ctx* c, int code, const char* what) {
     return code;
 }
 
+// dxo_fail with the message "<who>: <what>"
+inline int fail_who(dxo_ctx* ctx, int code, const char* who, const char* what) {
+    char msg[320];
+    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return dxo_fail(ctx, code, msg);
+}
+
 inline int dxo_hip_fail(dxo_ctx* c, hipError_t e, const char* where) {
     if (c) {
         char buf[512];
@@ -179,15 +187,25 @@ struct dxo_span {
     void* dev = nullptr;
 };
 
-// Device mirror of the von Mises history variables plus the results of the last call (include/dxo.h, dxo_vm_state_*):
-// ONE allocation, [sigma_n n*d | sigma n*d | p n | dp n] doubles, every part on a 256-byte border.
-struct dxo_vm_state {
-    int d = 0;
+// What the resident-state objects share (include/dxo.h, dxo_vm_state_* / dxo_mc_state_*): n points, ONE allocation carved into arrays
+// that each start on a 256-byte border, and the two flags of the upload / call / commit protocol. The helpers on it follow the
+// pipeline's declarations below (dxo_state_*).
+struct dxo_state_core {
     int64_t n = 0;
     void* blob = nullptr;
+    bool uploaded = false;     // the history arrays hold data
+    bool has_result = false;   // the result arrays hold the results of a call made after the last upload / commit
+};
+
+// Device mirror of the von Mises history variables plus the results of the last call: [sigma_n n*d | sigma n*d | p n | dp n] doubles.
+struct dxo_vm_state : dxo_state_core {
+    int d = 0;
     double *sigma_n = nullptr, *sigma = nullptr, *p = nullptr, *dp = nullptr;
-    bool uploaded = false;     // sigma_n / p hold data
-    bool has_result = false;   // sigma / dp hold the results of a call made after the last upload / commit
+};
+
+// Device mirror of the Mohr-Coulomb history variable plus the stress of the last call: [sigma_n n*4 | sigma n*4] doubles.
+struct dxo_mc_state : dxo_state_core {
+    double *sigma_n = nullptr, *sigma = nullptr;
 };
 
 // Launch callback for the chunked host pipeline: device pointers of the chunk, in the same
@@ -250,11 +268,99 @@ bool dxo_vmf_residual_eligible(const dxo_mesh* mesh);
 int dxo_vmf_residual_launch(dxo_ctx* ctx, const dxo_vm_params* prm, const dxo_mesh* mesh, const double* u, const double* sigma_n,
                             const double* p, double* sigma, double* dp, double* fe, hipStream_t s);
 
-// Device mirror of the Mohr-Coulomb history variable plus the stress of the last call (include/dxo.h, dxo_mc_state_*):
-// ONE allocation, [sigma_n n*4 | sigma n*4] doubles.
-struct dxo_mc_state {
-    int64_t n = 0;
-    void* blob = nullptr;
-    double *sigma_n = nullptr, *sigma = nullptr;
-    bool uploaded = false, has_result = false;
+// ---- host-side pieces the Mohr-Coulomb entry points share (mohr_coulomb.hip, field_ops.hip)
+// the spans of the optional outputs, in the order the chunk callbacks read them; `unit` = points per pipeline unit (1, or nq for cells)
+static inline void dxo_mc_optional_outputs(std::vector<dxo_span>& out, size_t unit, int32_t* niter, double* yielding, double* norm_res, double* dlambda) {
+    if (niter) out.push_back({nullptr, niter, sizeof(int32_t) * unit});
+    for (double* a : {yielding, norm_res, dlambda})
+        if (a) out.push_back({nullptr, a, sizeof(double) * unit});
+}
+
+// a16: the arrays the kernels access in 16-byte vectors (on the device path; `what16` names them), a8: the other double arrays
+static inline int dxo_mc_check_align(dxo_ctx* ctx, const char* who, int mem, uintptr_t a16, const char* what16, uintptr_t a8, const int32_t* niter) {
+    if (mem == DXO_MEM_DEVICE && (a16 & 15u)) return fail_who(ctx, DXO_E_ALIGN, who, what16);
+    if ((a16 & 7u) || (a8 & 7u) || ((uintptr_t)niter & 3u)) return fail_who(ctx, DXO_E_ALIGN, who, "misaligned array");
+    return DXO_OK;
+}
+
+// ---- the resident-state core (dxo_state_core above): what dxo_vm_state_* and dxo_mc_state_* do, written once. `who` is the entry
+// point's name, the head of its messages; the entry point has refused a NULL state (its parts are named through it).
+// one array of a state: where its device pointer is kept, and doubles per point
+struct dxo_state_part {
+    double** dev;
+    int width;
 };
+// allocate and carve: the parts in the order given, each rounded up to 256 bytes, 256 bytes spare behind the last
+static inline int dxo_state_alloc(dxo_ctx* ctx, dxo_state_core* st, int64_t n, std::initializer_list<dxo_state_part> parts) {
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    size_t bytes = 256;
+    for (const auto& p : parts) bytes += up((size_t)n * p.width * sizeof(double));
+    DXO_HIP(ctx, hipMalloc(&st->blob, bytes));
+    st->n = n;
+    char* b = static_cast<char*>(st->blob);
+    for (const auto& p : parts) {
+        *p.dev = reinterpret_cast<double*>(b);
+        b += up((size_t)n * p.width * sizeof(double));
+    }
+    return DXO_OK;
+}
+
+// free the block, behind the context's pending work when there is a context (a closed one is NULL: the block is still freed)
+static inline void dxo_state_free(dxo_ctx* ctx, dxo_state_core* st) {
+    DXO_LOCK(ctx);
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        (void)dxo_ctx_synchronize(ctx);
+    }
+    if (st->blob) (void)hipFree(st->blob);
+}
+
+// one array of a copy: the state's side, the caller's side (NULL: skipped), doubles per point
+struct dxo_state_copy {
+    double* dev;
+    const double* user;
+    int width;
+};
+// the copies of an upload (`in`) or a download between the caller's arrays in `mem` and the state, then ONE stream synchronise (the
+// pipeline's streams read the mirror next)
+static inline int dxo_state_copies(dxo_ctx* ctx, const dxo_state_core* st, int mem, bool in, std::initializer_list<dxo_state_copy> parts) {
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    if (st->n == 0) return DXO_OK;
+    const hipMemcpyKind k = mem != DXO_MEM_HOST ? hipMemcpyDeviceToDevice : (in ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost);
+    hipStream_t s = dxo_launch_stream(ctx);
+    for (const auto& p : parts) {
+        if (!p.user) continue;
+        double* user = const_cast<double*>(p.user);
+        DXO_HIP(ctx, hipMemcpyAsync(in ? p.dev : user, in ? user : p.dev, (size_t)st->n * p.width * sizeof(double), k, s));
+    }
+    DXO_HIP(ctx, hipStreamSynchronize(s));
+    return DXO_OK;
+}
+
+static inline int dxo_state_upload(dxo_ctx* ctx, const char* who, dxo_state_core* st, int mem, std::initializer_list<dxo_state_copy> parts) {
+    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return fail_who(ctx, DXO_E_MEM, who, "bad mem");
+    for (const auto& p : parts)
+        if (st->n > 0 && !p.user) return fail_who(ctx, DXO_E_NULL, who, "NULL array");
+    const int rc = dxo_state_copies(ctx, st, mem, true, parts);
+    if (rc != DXO_OK) return rc;
+    st->uploaded = true;
+    st->has_result = false;
+    return DXO_OK;
+}
+
+static inline int dxo_state_download(dxo_ctx* ctx, const char* who, const dxo_state_core* st, int mem, std::initializer_list<dxo_state_copy> parts) {
+    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return fail_who(ctx, DXO_E_MEM, who, "bad mem");
+    if (!st->uploaded) return fail_who(ctx, DXO_E_SIZE, who, "nothing has been uploaded");
+    return dxo_state_copies(ctx, st, mem, false, parts);
+}
+
+// the commit guard: true = there is a result to commit; false = return *rc (OK for an empty state — a rank without cells has nothing
+// to update —, DXO_E_SIZE when no call has left a result)
+static inline bool dxo_state_can_commit(dxo_ctx* ctx, const char* who, const dxo_state_core* st, int* rc) {
+    if (!st) *rc = fail_who(ctx, DXO_E_NULL, who, "state is NULL");
+    else if (st->n == 0) *rc = DXO_OK;
+    else if (!st->has_result) *rc = fail_who(ctx, DXO_E_SIZE, who, "no call since the last upload / commit — nothing to commit");
+    else return true;
+    return false;
+}

@@ -101,14 +101,6 @@ int isi_field_chunk(dxo_ctx* ctx, void* user, int64_t n_chunk, void* const*, voi
     return isi_field_launch(ctx, L, cell0, n_chunk, (double*)d_out[0], (double*)d_out[1], s);
 }
 
-int upload_u(dxo_ctx* ctx, dxo_mesh* mesh, const double* u) {
-    const size_t ub = (size_t)mesh->num_field_nodes * mesh->gdim * sizeof(double);
-    const int rc = device_buf(ctx, (void**)&mesh->d_u, &mesh->u_cap, ub);
-    if (rc != DXO_OK) return rc;
-    DXO_HIP(ctx, hipMemcpy(mesh->d_u, u, ub, hipMemcpyHostToDevice));
-    return DXO_OK;
-}
-
 struct FieldOp {
     dxo_mesh* mesh;
     const double* d_u;
@@ -150,7 +142,7 @@ int run_field_op(dxo_ctx* ctx, FieldOp& L, int mem, const double* u, const std::
         if (rc != DXO_OK) return rc;
         return dxo_device_end(ctx, s);
     }
-    int rc = upload_u(ctx, L.mesh, u);
+    int rc = upload_u(ctx, L.mesh, u, L.mesh->gdim);
     if (rc != DXO_OK) return rc;
     L.d_u = L.mesh->d_u;
     return dxo_run_host_pipeline(ctx, nc, in, out, field_op_chunk, &L, L.mesh->dev.nq);
@@ -175,10 +167,10 @@ extern "C" int dxo_mohr_coulomb_field(dxo_ctx* ctx, const dxo_mc_params* prm, dx
     if (prm->nitermax < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mohr_coulomb_field: nitermax < 0");
     if (mesh->num_cells == 0) return DXO_OK;
     if (!u || !sigma_n || !C_tang || !sigma) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb_field: NULL array");
-    const uintptr_t a16 = (uintptr_t)sigma_n | (uintptr_t)C_tang | (uintptr_t)sigma;
-    const uintptr_t a8 = (uintptr_t)u | (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda;
-    if (mem == DXO_MEM_DEVICE && (a16 & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_mohr_coulomb_field: device sigma_n, C_tang, sigma must be 16-byte aligned");
-    if ((a16 & 7u) || (a8 & 7u) || ((uintptr_t)niter & 3u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_mohr_coulomb_field: misaligned array");
+    const int arc = dxo_mc_check_align(ctx, "dxo_mohr_coulomb_field", mem, (uintptr_t)sigma_n | (uintptr_t)C_tang | (uintptr_t)sigma,
+                                       "device sigma_n, C_tang, sigma must be 16-byte aligned",
+                                       (uintptr_t)u | (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda, niter);
+    if (arc != DXO_OK) return arc;
     const bool has[4] = {niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
     const dxo_mc_params P = *prm;
     FieldOp L{mesh, nullptr, DXO_OPERAND_EPS_MANDEL};
@@ -193,11 +185,9 @@ extern "C" int dxo_mohr_coulomb_field(dxo_ctx* ctx, const dxo_mc_params* prm, dx
     const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
     std::vector<dxo_span> in = {{sigma_n, nullptr, 4 * sd}};
     std::vector<dxo_span> out = {{nullptr, C_tang, 16 * sd}, {nullptr, sigma, 4 * sd}};
+    dxo_mc_optional_outputs(out, (size_t)mesh->dev.nq, niter, yielding, norm_res, dlambda);
     std::vector<void*> dout = {C_tang, sigma};
-    if (niter) { out.push_back({nullptr, niter, sizeof(int32_t) * (size_t)mesh->dev.nq}); dout.push_back(niter); }
-    if (yielding) { out.push_back({nullptr, yielding, sd}); dout.push_back(yielding); }
-    if (norm_res) { out.push_back({nullptr, norm_res, sd}); dout.push_back(norm_res); }
-    if (dlambda) { out.push_back({nullptr, dlambda, sd}); dout.push_back(dlambda); }
+    for (size_t k = 2; k < out.size(); ++k) dout.push_back((void*)out[k].out);
     void* din[1] = {const_cast<double*>(sigma_n)};
     return run_field_op(ctx, L, mem, u, in, out, din, dout.data());
 }
@@ -248,7 +238,7 @@ extern "C" int dxo_isihara_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dx
         if (rc != DXO_OK) return rc;
         return dxo_device_end(ctx, s);
     }
-    int rc = upload_u(ctx, mesh, u);
+    int rc = upload_u(ctx, mesh, u, mesh->gdim);
     if (rc != DXO_OK) return rc;
     L.d_u = mesh->d_u;
     const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;

@@ -73,13 +73,6 @@ bool with_bilinear_pair(int bs, int test, int trial, F&& f) {
            is(int_c<1>{}, int_c<GR>{}, int_c<GR>{}) || is(int_c<1>{}, int_c<V>{}, int_c<V>{}) || is(int_c<1>{}, int_c<VG>{}, int_c<VG>{});
 }
 
-// dxo_fail with the message "<who>: <what>"
-inline int fail_who(dxo_ctx* ctx, int code, const char* who, const char* what) {
-    char msg[320];
-    std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return dxo_fail(ctx, code, msg);
-}
-
 // the opening of dxo_bilinear_apply / _diagonal / _assemble: the nonlinear kinds refused, DEFGRAD taken as its linearisation GRAD, the
 // pair looked up (ops = select(int_c<G>, int_c<BS>, int_c<TEST>, int_c<TRIAL>)), the quadrature weights present
 template <class Ops, class Select>
@@ -133,6 +126,15 @@ inline hipError_t device_buf_try(void** p, size_t* cap, size_t bytes) {
 
 inline int device_buf(dxo_ctx* ctx, void** p, size_t* cap, size_t bytes) {
     DXO_HIP(ctx, device_buf_try(p, cap, bytes));
+    return DXO_OK;
+}
+
+// the dof vector of a host caller (`components` values per field node) into the mesh's grow-only staging buffer d_u, whole
+static inline int upload_u(dxo_ctx* ctx, dxo_mesh* mesh, const double* u, int components) {
+    const size_t ub = (size_t)mesh->num_field_nodes * components * sizeof(double);
+    const int rc = device_buf(ctx, (void**)&mesh->d_u, &mesh->u_cap, ub);
+    if (rc != DXO_OK) return rc;
+    DXO_HIP(ctx, hipMemcpy(mesh->d_u, u, ub, hipMemcpyHostToDevice));
     return DXO_OK;
 }
 

@@ -117,10 +117,8 @@ extern "C" int dxo_heat_field(dxo_ctx* ctx, double A, double B, dxo_mesh* mesh, 
         if (rc != DXO_OK) return rc;
         return dxo_device_end(ctx, s);
     }
-    const size_t tb = (size_t)mesh->num_field_nodes * sizeof(double);
-    const int rc = device_buf(ctx, (void**)&mesh->d_u, &mesh->u_cap, tb);
+    const int rc = upload_u(ctx, mesh, T_dofs, 1);
     if (rc != DXO_OK) return rc;
-    DXO_HIP(ctx, hipMemcpy(mesh->d_u, T_dofs, tb, hipMemcpyHostToDevice));
     L.d_T = mesh->d_u;
     const size_t sd = sizeof(double) * (size_t)nq;
     std::vector<dxo_span> in;

@@ -646,6 +646,42 @@ int mc_chunk(dxo_ctx* ctx, void* user, int64_t m, void* const* d_in, void* const
                      yl, nr, dl, s);
 }
 
+McLaunch mc_make_launch(const dxo_mc_params* prm, const int32_t* niter, const double* yielding, const double* norm_res, const double* dlambda) {
+    return McLaunch{mc::make_const(prm->E, prm->nu, prm->c, prm->phi, prm->psi, prm->theta_T, prm->a, prm->tol, prm->nitermax),
+                    niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
+}
+
+// The launch behind dxo_mohr_coulomb and dxo_mohr_coulomb_state, their argument checks done. `st` is the mirror or NULL. With a mirror
+// the kernels read sigma_n from it and write sigma into it: the device path copies sigma out only where the caller gives an array, the
+// host path requires it. has_result is cleared first and set on success alone.
+int mc_run(dxo_ctx* ctx, const char* who, const dxo_mc_params* prm, int64_t n, int mem, const double* deps, const double* sigma_n, double* C_tang,
+           double* sigma, int32_t* niter, double* yielding, double* norm_res, double* dlambda, dxo_mc_state* st) {
+    McLaunch L = mc_make_launch(prm, niter, yielding, norm_res, dlambda);
+    const size_t sd = sizeof(double);
+    if (st) {
+        DXO_HIP(ctx, hipSetDevice(ctx->device));
+        st->has_result = false;
+    }
+    int rc;
+    if (mem == DXO_MEM_DEVICE) {
+        hipStream_t s = dxo_launch_stream(ctx);
+        rc = dxo_device_begin(ctx, s);
+        if (rc != DXO_OK) return rc;
+        rc = mc_launch(ctx, L, n, deps, st ? st->sigma_n : sigma_n, C_tang, st ? st->sigma : sigma, niter, yielding, norm_res, dlambda, s);
+        if (rc != DXO_OK) return rc;
+        if (st && sigma) DXO_HIP(ctx, hipMemcpyAsync(sigma, st->sigma, (size_t)n * 4 * sd, hipMemcpyDeviceToDevice, s));
+        rc = dxo_device_end(ctx, s);
+    } else {
+        if (st && !sigma) return fail_who(ctx, DXO_E_NULL, who, "host sigma is required");
+        std::vector<dxo_span> in = {{deps, nullptr, 4 * sd}, {sigma_n, nullptr, 4 * sd, st ? st->sigma_n : nullptr}};
+        std::vector<dxo_span> out = {{nullptr, C_tang, 16 * sd}, {nullptr, sigma, 4 * sd, st ? st->sigma : nullptr}};
+        dxo_mc_optional_outputs(out, 1, niter, yielding, norm_res, dlambda);
+        rc = dxo_run_host_pipeline(ctx, n, in, out, mc_chunk, &L);
+    }
+    if (st && rc == DXO_OK) st->has_result = true;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" int dxo_mohr_coulomb(dxo_ctx* ctx, const dxo_mc_params* prm, int64_t n, int mem, const double* deps,
@@ -658,37 +694,17 @@ extern "C" int dxo_mohr_coulomb(dxo_ctx* ctx, const dxo_mc_params* prm, int64_t 
     if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_mohr_coulomb: bad mem");
     if (n > 0 && (!deps || !sigma_n || !C_tang || !sigma)) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb: NULL array");
     if (prm->nitermax < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mohr_coulomb: nitermax < 0");
-    const uintptr_t a16 = (uintptr_t)deps | (uintptr_t)sigma_n | (uintptr_t)C_tang | (uintptr_t)sigma;
-    const uintptr_t a8 = (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda;
-    if (mem == DXO_MEM_DEVICE && (a16 & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_mohr_coulomb: deps/sigma_n/C_tang/sigma must be 16-byte aligned");
-    if ((a16 & 7u) || (a8 & 7u) || ((uintptr_t)niter & 3u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_mohr_coulomb: misaligned array");
-    McLaunch L{mc::make_const(prm->E, prm->nu, prm->c, prm->phi, prm->psi, prm->theta_T, prm->a, prm->tol, prm->nitermax),
-               niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = mc_launch(ctx, L, n, deps, sigma_n, C_tang, sigma, niter, yielding, norm_res, dlambda, s);
-        if (rc != DXO_OK) return rc;
-        return dxo_device_end(ctx, s);
-    }
-    const size_t sd = sizeof(double);
-    std::vector<dxo_span> in = {{deps, nullptr, 4 * sd}, {sigma_n, nullptr, 4 * sd}};
-    std::vector<dxo_span> out = {{nullptr, C_tang, 16 * sd}, {nullptr, sigma, 4 * sd}};
-    if (niter) out.push_back({nullptr, niter, sizeof(int32_t)});
-    if (yielding) out.push_back({nullptr, yielding, sd});
-    if (norm_res) out.push_back({nullptr, norm_res, sd});
-    if (dlambda) out.push_back({nullptr, dlambda, sd});
-    return dxo_run_host_pipeline(ctx, n, in, out, mc_chunk, &L);
+    const int rc = dxo_mc_check_align(ctx, "dxo_mohr_coulomb", mem, (uintptr_t)deps | (uintptr_t)sigma_n | (uintptr_t)C_tang | (uintptr_t)sigma,
+                                      "deps/sigma_n/C_tang/sigma must be 16-byte aligned", (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda, niter);
+    if (rc != DXO_OK) return rc;
+    return mc_run(ctx, "dxo_mohr_coulomb", prm, n, mem, deps, sigma_n, C_tang, sigma, niter, yielding, norm_res, dlambda, nullptr);
 }
 
 // internal: the kernels on device pointers and an explicit stream (field_ops.hip)
 int dxo_mc_launch_device(dxo_ctx* ctx, const dxo_mc_params* prm, int64_t n, const double* deps, const double* sigma_n,
                          double* C_tang, double* sigma, int32_t* niter, double* yielding, double* norm_res, double* dlambda,
                          hipStream_t s) {
-    McLaunch L{mc::make_const(prm->E, prm->nu, prm->c, prm->phi, prm->psi, prm->theta_T, prm->a, prm->tol, prm->nitermax),
-               niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
-    return mc_launch(ctx, L, n, deps, sigma_n, C_tang, sigma, niter, yielding, norm_res, dlambda, s);
+    return mc_launch(ctx, mc_make_launch(prm, niter, yielding, norm_res, dlambda), n, deps, sigma_n, C_tang, sigma, niter, yielding, norm_res, dlambda, s);
 }
 
 // ------------------------------------------------------------------ history variable resident on the device
@@ -702,29 +718,16 @@ extern "C" int dxo_mc_state_create(dxo_ctx* ctx, int64_t n, dxo_mc_state** out) 
     if (!out) return dxo_fail(ctx, DXO_E_NULL, "dxo_mc_state_create: out is NULL");
     *out = nullptr;
     if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mc_state_create: n < 0");
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t bs = ((size_t)n * 4 * sizeof(double) + 255) / 256 * 256;
-    void* blob = nullptr;
-    DXO_HIP(ctx, hipMalloc(&blob, 2 * bs + 256));
     dxo_mc_state* st = new dxo_mc_state;
-    st->n = n;
-    st->blob = blob;
-    st->sigma_n = reinterpret_cast<double*>(blob);
-    st->sigma = reinterpret_cast<double*>(static_cast<char*>(blob) + bs);
-    *out = st;
-    return DXO_OK;
+    const int rc = dxo_state_alloc(ctx, st, n, {{&st->sigma_n, 4}, {&st->sigma, 4}});
+    if (rc == DXO_OK) *out = st;
+    else delete st;
+    return rc;
 }
 
 extern "C" void dxo_mc_state_destroy(dxo_ctx* ctx, dxo_mc_state* st) {
     if (!st) return;
-    if (ctx) {
-        DXO_LOCK(ctx);
-        (void)hipSetDevice(ctx->device);
-        (void)dxo_ctx_synchronize(ctx);
-        if (st->blob) (void)hipFree(st->blob);
-    } else if (st->blob) {
-        (void)hipFree(st->blob);
-    }
+    dxo_state_free(ctx, st);
     delete st;
 }
 
@@ -732,34 +735,14 @@ extern "C" int dxo_mc_state_upload(dxo_ctx* ctx, dxo_mc_state* st, int mem, cons
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
     if (!st) return dxo_fail(ctx, DXO_E_NULL, "dxo_mc_state_upload: state is NULL");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_mc_state_upload: bad mem");
-    if (st->n > 0 && !sigma_n) return dxo_fail(ctx, DXO_E_NULL, "dxo_mc_state_upload: NULL array");
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = dxo_launch_stream(ctx);
-    if (st->n > 0) {
-        DXO_HIP(ctx, hipMemcpyAsync(st->sigma_n, sigma_n, (size_t)st->n * 4 * sizeof(double),
-                                    mem == DXO_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));   // the next call may read the mirror from any of the pipeline's streams
-    }
-    st->uploaded = true;
-    st->has_result = false;
-    return DXO_OK;
+    return dxo_state_upload(ctx, "dxo_mc_state_upload", st, mem, {{st->sigma_n, sigma_n, 4}});
 }
 
 extern "C" int dxo_mc_state_download(dxo_ctx* ctx, dxo_mc_state* st, int mem, double* sigma_n) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
     if (!st) return dxo_fail(ctx, DXO_E_NULL, "dxo_mc_state_download: state is NULL");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_mc_state_download: bad mem");
-    if (!st->uploaded) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mc_state_download: nothing has been uploaded");
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = dxo_launch_stream(ctx);
-    if (st->n > 0 && sigma_n) {
-        DXO_HIP(ctx, hipMemcpyAsync(sigma_n, st->sigma_n, (size_t)st->n * 4 * sizeof(double),
-                                    mem == DXO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return DXO_OK;
+    return dxo_state_download(ctx, "dxo_mc_state_download", st, mem, {{st->sigma_n, sigma_n, 4}});
 }
 
 extern "C" int dxo_mc_state_pointers(dxo_ctx* ctx, dxo_mc_state* st, double** sigma_n, double** sigma) {
@@ -774,10 +757,8 @@ extern "C" int dxo_mc_state_pointers(dxo_ctx* ctx, dxo_mc_state* st, double** si
 extern "C" int dxo_mc_state_commit(dxo_ctx* ctx, dxo_mc_state* st) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
-    if (!st) return dxo_fail(ctx, DXO_E_NULL, "dxo_mc_state_commit: state is NULL");
-    if (st->n == 0) return DXO_OK;   // an empty partition has nothing to update
-    if (!st->has_result)
-        return dxo_fail(ctx, DXO_E_SIZE, "dxo_mc_state_commit: no call since the last upload / commit — nothing to commit");
+    int rc;
+    if (!dxo_state_can_commit(ctx, "dxo_mc_state_commit", st, &rc)) return rc;
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = dxo_launch_stream(ctx);
     // sigma_n <- sigma (:728): a device-to-device copy at HBM speed (64 B per point)
@@ -796,39 +777,12 @@ extern "C" int dxo_mohr_coulomb_state(dxo_ctx* ctx, const dxo_mc_params* prm, dx
     if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_mohr_coulomb_state: bad mem");
     if (!st->uploaded) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mohr_coulomb_state: dxo_mc_state_upload has not been called");
     if (prm->nitermax < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mohr_coulomb_state: nitermax < 0");
-    const int64_t n = st->n;
-    if (n == 0) return DXO_OK;
+    if (st->n == 0) return DXO_OK;
     if (!deps || !C_tang) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb_state: NULL array");
-    const uintptr_t a16 = (uintptr_t)deps | (uintptr_t)C_tang | (uintptr_t)sigma;
-    const uintptr_t a8 = (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda;
-    if (mem == DXO_MEM_DEVICE && (a16 & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_mohr_coulomb_state: deps/C_tang/sigma must be 16-byte aligned");
-    if ((a16 & 7u) || (a8 & 7u) || ((uintptr_t)niter & 3u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_mohr_coulomb_state: misaligned array");
-    McLaunch L{mc::make_const(prm->E, prm->nu, prm->c, prm->phi, prm->psi, prm->theta_T, prm->a, prm->tol, prm->nitermax),
-               niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    st->has_result = false;
-    const size_t sd = sizeof(double);
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = mc_launch(ctx, L, n, deps, st->sigma_n, C_tang, st->sigma, niter, yielding, norm_res, dlambda, s);
-        if (rc != DXO_OK) return rc;
-        if (sigma) DXO_HIP(ctx, hipMemcpyAsync(sigma, st->sigma, (size_t)n * 4 * sd, hipMemcpyDeviceToDevice, s));
-        rc = dxo_device_end(ctx, s);
-        if (rc == DXO_OK) st->has_result = true;
-        return rc;
-    }
-    if (!sigma) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb_state: host sigma is required");
-    std::vector<dxo_span> in = {{deps, nullptr, 4 * sd}, {nullptr, nullptr, 4 * sd, st->sigma_n}};
-    std::vector<dxo_span> out = {{nullptr, C_tang, 16 * sd}, {nullptr, sigma, 4 * sd, st->sigma}};
-    if (niter) out.push_back({nullptr, niter, sizeof(int32_t)});
-    if (yielding) out.push_back({nullptr, yielding, sd});
-    if (norm_res) out.push_back({nullptr, norm_res, sd});
-    if (dlambda) out.push_back({nullptr, dlambda, sd});
-    const int rc = dxo_run_host_pipeline(ctx, n, in, out, mc_chunk, &L);
-    if (rc == DXO_OK) st->has_result = true;
-    return rc;
+    const int rc = dxo_mc_check_align(ctx, "dxo_mohr_coulomb_state", mem, (uintptr_t)deps | (uintptr_t)C_tang | (uintptr_t)sigma,
+                                      "deps/C_tang/sigma must be 16-byte aligned", (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda, niter);
+    if (rc != DXO_OK) return rc;
+    return mc_run(ctx, "dxo_mohr_coulomb_state", prm, st->n, mem, deps, nullptr, C_tang, sigma, niter, yielding, norm_res, dlambda, st);
 }
 
 extern "C" int dxo_mc_summary(dxo_ctx* ctx, int64_t n, const int32_t* niter, const double* yielding, const double* norm_res,

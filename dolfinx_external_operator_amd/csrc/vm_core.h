@@ -3,6 +3,7 @@
 #pragma once
 
 #include "dxo_common.h"
+#include "vm_host.h"
 
 namespace {
 
@@ -257,5 +258,48 @@ __device__ __forceinline__ void vm_store_tangent_rows(const VmConst& c, double* 
     }
 }
 
+// ------------------------------------------------------------------ host side shared by the point and the field entry points
+// The host half of a DXO_MEM_HOST call with option "vm_host_tangent" = 1 (vm_host.h): of the 344 B/point (d = 6) the kernel produces, 288
+// are the tangent, and the tangent is a function of the returned state. PCIe, not HBM, bounds a host call, so only (sigma, dp) cross the
+// link and the caller's C_tang is filled by the context's host threads from each chunk as it lands. A launch record (VmLaunch,
+// FieldLaunch) carries the caller's arrays, whole; C_tang set = the device writes no tangent (the (sigma, dp)-only form of the kernels).
+struct VmHostHalf {
+    const double* sigma = nullptr;
+    double* dp = nullptr;
+    double* C_tang = nullptr;
+};
+
+// post hook of the host pipeline over a POINT range: C_tang of points [first, first + m) from the (sigma, dp) that have just landed
+int vm_host_rebuild_points(dxo_ctx* ctx, const VmConst& c, int d, const VmHostHalf& h, int64_t first, int64_t m) {
+    const double* sg = h.sigma + first * d;
+    double* dp = h.dp + first;
+    double* Ct = h.C_tang + first * d * d;
+    const VmHostConst hc{c.lmbda, c.mu2, c.mu3, c.ratio};
+    dxo_host_parallel_for(ctx, m, 512, [&](int64_t b, int64_t e) {
+        if (d == 4) vm_host_rebuild_range<4>(hc, sg, dp, Ct, b, e);
+        else vm_host_rebuild_range<6>(hc, sg, dp, Ct, b, e);
+    });
+    return DXO_OK;
+}
+
+// The host branch of dxo_von_mises, _state, _field and _field_state: `n` units of `unit` points each (1: points; nq: cells) through the
+// chunked pipeline. The outputs are the caller's three arrays; sigma and dp may have a device mirror (dxo_vm_state), where the kernel
+// writes them and whence they are copied. Copy mode: all three cross the link. Rebuild mode (the option, from vm_rebuild_min_points
+// on): (c, h) of the launch record behind `user` are set, the tangent span is empty and `rebuild` fills C_tang. Its chunks are smaller
+// than the copy mode's: the un-overlapped tail of the call is the rebuild of the last DXO_HOST_SLOTS chunks.
+int vm_host_run(dxo_ctx* ctx, int64_t n, int unit, int d, const std::vector<dxo_span>& in, double* C_tang, double* sigma, double* dp,
+                double* dev_sigma, double* dev_dp, dxo_chunk_launch launch, dxo_chunk_post rebuild, void* user, VmConst& c, VmHostHalf& h) {
+    const size_t sd = sizeof(double) * (size_t)unit;
+    std::vector<dxo_span> out = {{nullptr, C_tang, d * d * sd}, {nullptr, sigma, d * sd, dev_sigma}, {nullptr, dp, sd, dev_dp}};
+    if (!ctx->vm_host_tangent || n * unit < ctx->vm_rebuild_min_points) return dxo_run_host_pipeline(ctx, n, in, out, launch, user, unit, nullptr, true);
+    h = {sigma, dp, C_tang};
+    c.mark_indeterminate = 1;   // with a mirror the mark (dp = -0.0) stays in the mirror's dp: p + (-0.0) == p at the commit
+    out[0] = {nullptr, nullptr, 0};
+    const int64_t saved_chunk = ctx->host_chunk_points;
+    if (ctx->host_chunk_points > ctx->vm_rebuild_chunk_points) ctx->host_chunk_points = ctx->vm_rebuild_chunk_points;
+    const int rc = dxo_run_host_pipeline(ctx, n, in, out, launch, user, unit, rebuild, true);
+    ctx->host_chunk_points = saved_chunk;
+    return rc;
+}
 
 }  // namespace

@@ -29,7 +29,6 @@
 
 #include "dxo_common.h"
 #include "vm_core.h"
-#include "vm_host.h"
 
 #ifndef DXO_VM_NT_LOADS
 #define DXO_VM_NT_LOADS 0    // non-temporal input loads (scripts/exp/vmtile_ab.py)
@@ -214,10 +213,7 @@ struct VmLaunch {
     VmConst c;
     int d;
     int shape = -1;   // >= 0: launch shape forced by a calibration (0 one tile per wave, k persistent workgroups per CU)
-    // host half of the DXO_MEM_HOST pipeline with option "vm_host_tangent" = 1 (see vm_host_rebuild)
-    const double* h_sigma = nullptr;
-    double* h_dp = nullptr;
-    double* h_C_tang = nullptr;
+    VmHostHalf h;     // host half of the DXO_MEM_HOST pipeline with option "vm_host_tangent" = 1 (vm_core.h)
 };
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -270,7 +266,7 @@ int vm_chunk(dxo_ctx* ctx, void* user, int64_t m, void* const* d_in, void* const
     const VmLaunch& L = *static_cast<const VmLaunch*>(user);
     // host-rebuild mode (option vm_host_tangent): the tangent is rebuilt from (sigma, dp) on the host, so the device writes none — the
     // (sigma, dp)-only form of the kernel: 160 instead of 448 B/point of stores, and on the small path no tangent crosses PCIe
-    double* C_tang = L.h_C_tang ? nullptr : (double*)d_out[0];
+    double* C_tang = L.h.C_tang ? nullptr : (double*)d_out[0];
     return vm_launch(ctx, L, m, (const double*)d_in[0], (const double*)d_in[1], (const double*)d_in[2], C_tang, (double*)d_out[1], (double*)d_out[2], s);
 }
 
@@ -380,26 +376,42 @@ int vm_expand_chunk(dxo_ctx* ctx, void* user, int64_t m, void* const* d_in, void
     return vm_expand_launch(ctx, L, m, (const double*)d_in[0], (const double*)d_in[1], (double*)d_out[0], s);
 }
 
-// ------------------------------------------------------------------ host half: tangent from (sigma, dp) on the CPU
-// DXO_MEM_HOST with option "vm_host_tangent" = 1: of the 344 B/point (d = 6) the kernel produces, 288 are the
-// tangent, and the tangent is a function of the returned state (vm_tangent_state above). PCIe, not HBM, bounds a
-// host call, so only (sigma, dp) cross the link (56 B/point) and the caller's C_tang array is filled by the
-// context's host threads from the chunk that has just landed while the next chunks are still in flight. Same
-// formulas and operation order as vm_tangent_state / vm_store_tangent; streaming (non-temporal) stores because the
-// array is write-only here and larger than any cache. Product code of the host pipeline, not a CPU fallback: the
-// return map itself always runs on the GPU.
+// post hook of the host pipeline (vm_host_run): the chunk's first point and point count
 int vm_host_rebuild(dxo_ctx* ctx, void* user, int64_t first, int64_t m) {
     const VmLaunch& L = *static_cast<const VmLaunch*>(user);
-    const int d = L.d;
-    const double* sg = L.h_sigma + first * d;
-    double* dp = L.h_dp + first;
-    double* Ct = L.h_C_tang + first * d * d;
-    const VmHostConst hc{L.c.lmbda, L.c.mu2, L.c.mu3, L.c.ratio};
-    dxo_host_parallel_for(ctx, m, 512, [&](int64_t b, int64_t e) {
-        if (d == 4) vm_host_rebuild_range<4>(hc, sg, dp, Ct, b, e);
-        else vm_host_rebuild_range<6>(hc, sg, dp, Ct, b, e);
-    });
-    return DXO_OK;
+    return vm_host_rebuild_points(ctx, L.c, L.d, L.h, first, m);
+}
+
+// The launch behind dxo_von_mises and dxo_von_mises_state, their argument checks done. `st` is the mirror or NULL. With a mirror the
+// kernel reads (sigma_n, p) from it and writes (sigma, dp) into it: the device path copies them out only where the caller gives an
+// array, the host path requires both. has_result is cleared first and set on success alone. Without a mirror the device path honours
+// option vm_mark_indeterminate; C_tang may be NULL on either device path.
+int vm_run(dxo_ctx* ctx, const char* who, const dxo_vm_params* prm, int d, int64_t n, int mem, const double* deps, const double* sigma_n,
+           const double* p, double* C_tang, double* sigma, double* dp, dxo_vm_state* st) {
+    VmLaunch L{make_const(*prm), d};
+    const size_t sd = sizeof(double);
+    if (st) {
+        DXO_HIP(ctx, hipSetDevice(ctx->device));
+        st->has_result = false;
+    }
+    int rc;
+    if (mem == DXO_MEM_DEVICE) {
+        hipStream_t s = dxo_launch_stream(ctx);
+        rc = dxo_device_begin(ctx, s);
+        if (rc != DXO_OK) return rc;
+        if (!st) L.c.mark_indeterminate = ctx->vm_mark_indeterminate != 0;
+        rc = vm_launch(ctx, L, n, deps, st ? st->sigma_n : sigma_n, st ? st->p : p, C_tang, st ? st->sigma : sigma, st ? st->dp : dp, s);
+        if (rc != DXO_OK) return rc;
+        if (st && sigma) DXO_HIP(ctx, hipMemcpyAsync(sigma, st->sigma, (size_t)n * d * sd, hipMemcpyDeviceToDevice, s));
+        if (st && dp) DXO_HIP(ctx, hipMemcpyAsync(dp, st->dp, (size_t)n * sd, hipMemcpyDeviceToDevice, s));
+        rc = dxo_device_end(ctx, s);
+    } else {
+        if (st && (!sigma || !dp)) return fail_who(ctx, DXO_E_NULL, who, "host sigma / dp are required");
+        std::vector<dxo_span> in = {{deps, nullptr, d * sd}, {sigma_n, nullptr, d * sd, st ? st->sigma_n : nullptr}, {p, nullptr, sd, st ? st->p : nullptr}};
+        rc = vm_host_run(ctx, n, 1, d, in, C_tang, sigma, dp, st ? st->sigma : nullptr, st ? st->dp : nullptr, vm_chunk, vm_host_rebuild, &L, L.c, L.h);
+    }
+    if (st && rc == DXO_OK) st->has_result = true;
+    return rc;
 }
 
 }  // namespace
@@ -445,35 +457,7 @@ extern "C" int dxo_von_mises(dxo_ctx* ctx, const dxo_vm_params* prm, int d, int6
     const uintptr_t all = (uintptr_t)deps | (uintptr_t)sigma_n | (uintptr_t)p | (uintptr_t)C_tang |
                           (uintptr_t)sigma | (uintptr_t)dp;
     if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_von_mises: arrays must be 8-byte aligned");
-    VmLaunch L{make_const(*prm), d};
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        L.c.mark_indeterminate = ctx->vm_mark_indeterminate != 0;
-        rc = vm_launch(ctx, L, n, deps, sigma_n, p, C_tang, sigma, dp, s);
-        if (rc != DXO_OK) return rc;
-        return dxo_device_end(ctx, s);
-    }
-    const size_t sd = sizeof(double);
-    std::vector<dxo_span> in = {{deps, nullptr, d * sd}, {sigma_n, nullptr, d * sd}, {p, nullptr, sd}};
-    if (ctx->vm_host_tangent && n >= ctx->vm_rebuild_min_points) {
-        // (sigma, dp) over PCIe, C_tang rebuilt by the host threads from each chunk as it lands (vm_host_rebuild)
-        L.h_sigma = sigma;
-        L.h_dp = dp;
-        L.h_C_tang = C_tang;
-        L.c.mark_indeterminate = 1;
-        std::vector<dxo_span> out = {{nullptr, nullptr, 0}, {nullptr, sigma, d * sd}, {nullptr, dp, sd}};      // no tangent on the device side (vm_chunk)
-        // smaller chunks than the copy mode: the host half of a chunk runs on the calling thread between two enqueues,
-        // so the un-overlapped tail of the call is the rebuild of the last DXO_HOST_SLOTS chunks
-        const int64_t saved_chunk = ctx->host_chunk_points;
-        if (ctx->host_chunk_points > ctx->vm_rebuild_chunk_points) ctx->host_chunk_points = ctx->vm_rebuild_chunk_points;
-        const int rc = dxo_run_host_pipeline(ctx, n, in, out, vm_chunk, &L, 1, vm_host_rebuild, true);
-        ctx->host_chunk_points = saved_chunk;
-        return rc;
-    }
-    std::vector<dxo_span> out = {{nullptr, C_tang, d * d * sd}, {nullptr, sigma, d * sd}, {nullptr, dp, sd}};
-    return dxo_run_host_pipeline(ctx, n, in, out, vm_chunk, &L, 1, nullptr, true);
+    return vm_run(ctx, "dxo_von_mises", prm, d, n, mem, deps, sigma_n, p, C_tang, sigma, dp, nullptr);
 }
 
 // ------------------------------------------------------------------ output block calibrated with the kernel itself
@@ -567,34 +551,17 @@ extern "C" int dxo_vm_state_create(dxo_ctx* ctx, int d, int64_t n, dxo_vm_state*
     *out = nullptr;
     if (d != 4 && d != 6) return dxo_fail(ctx, DXO_E_DIM, "dxo_vm_state_create: d must be 4 or 6");
     if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_vm_state_create: n < 0");
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t bs = up((size_t)n * d * sizeof(double)), bp = up((size_t)n * sizeof(double));
-    void* blob = nullptr;
-    DXO_HIP(ctx, hipMalloc(&blob, 2 * bs + 2 * bp + 256));
     dxo_vm_state* st = new dxo_vm_state;
     st->d = d;
-    st->n = n;
-    st->blob = blob;
-    char* b = static_cast<char*>(blob);
-    st->sigma_n = reinterpret_cast<double*>(b);
-    st->sigma = reinterpret_cast<double*>(b + bs);
-    st->p = reinterpret_cast<double*>(b + 2 * bs);
-    st->dp = reinterpret_cast<double*>(b + 2 * bs + bp);
-    *out = st;
-    return DXO_OK;
+    const int rc = dxo_state_alloc(ctx, st, n, {{&st->sigma_n, d}, {&st->sigma, d}, {&st->p, 1}, {&st->dp, 1}});
+    if (rc == DXO_OK) *out = st;
+    else delete st;
+    return rc;
 }
 
 extern "C" void dxo_vm_state_destroy(dxo_ctx* ctx, dxo_vm_state* st) {
     if (!st) return;
-    if (ctx) {
-        DXO_LOCK(ctx);
-        (void)hipSetDevice(ctx->device);
-        (void)dxo_ctx_synchronize(ctx);
-        if (st->blob) (void)hipFree(st->blob);
-    } else if (st->blob) {
-        (void)hipFree(st->blob);
-    }
+    dxo_state_free(ctx, st);
     delete st;
 }
 
@@ -602,36 +569,14 @@ extern "C" int dxo_vm_state_upload(dxo_ctx* ctx, dxo_vm_state* st, int mem, cons
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
     if (!st) return dxo_fail(ctx, DXO_E_NULL, "dxo_vm_state_upload: state is NULL");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_vm_state_upload: bad mem");
-    if (st->n > 0 && (!sigma_n || !p)) return dxo_fail(ctx, DXO_E_NULL, "dxo_vm_state_upload: NULL array");
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = dxo_launch_stream(ctx);
-    const hipMemcpyKind k = mem == DXO_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    if (st->n > 0) {
-        DXO_HIP(ctx, hipMemcpyAsync(st->sigma_n, sigma_n, (size_t)st->n * st->d * sizeof(double), k, s));
-        DXO_HIP(ctx, hipMemcpyAsync(st->p, p, (size_t)st->n * sizeof(double), k, s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));   // the next call may read the mirror from any of the pipeline's streams
-    }
-    st->uploaded = true;
-    st->has_result = false;
-    return DXO_OK;
+    return dxo_state_upload(ctx, "dxo_vm_state_upload", st, mem, {{st->sigma_n, sigma_n, st->d}, {st->p, p, 1}});
 }
 
 extern "C" int dxo_vm_state_download(dxo_ctx* ctx, dxo_vm_state* st, int mem, double* sigma_n, double* p) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
     if (!st) return dxo_fail(ctx, DXO_E_NULL, "dxo_vm_state_download: state is NULL");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_vm_state_download: bad mem");
-    if (!st->uploaded) return dxo_fail(ctx, DXO_E_SIZE, "dxo_vm_state_download: nothing has been uploaded");
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = dxo_launch_stream(ctx);
-    const hipMemcpyKind k = mem == DXO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (st->n > 0) {
-        if (sigma_n) DXO_HIP(ctx, hipMemcpyAsync(sigma_n, st->sigma_n, (size_t)st->n * st->d * sizeof(double), k, s));
-        if (p) DXO_HIP(ctx, hipMemcpyAsync(p, st->p, (size_t)st->n * sizeof(double), k, s));
-        DXO_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return DXO_OK;
+    return dxo_state_download(ctx, "dxo_vm_state_download", st, mem, {{st->sigma_n, sigma_n, st->d}, {st->p, p, 1}});
 }
 
 extern "C" int dxo_vm_state_pointers(dxo_ctx* ctx, dxo_vm_state* st, double** sigma_n, double** p, double** sigma, double** dp) {
@@ -652,47 +597,11 @@ extern "C" int dxo_von_mises_state(dxo_ctx* ctx, const dxo_vm_params* prm, dxo_v
     if (!prm || !st) return dxo_fail(ctx, DXO_E_NULL, "dxo_von_mises_state: NULL params or state");
     if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_von_mises_state: bad mem");
     if (!st->uploaded) return dxo_fail(ctx, DXO_E_SIZE, "dxo_von_mises_state: dxo_vm_state_upload has not been called");
-    const int d = st->d;
-    const int64_t n = st->n;
-    if (n == 0) return DXO_OK;
+    if (st->n == 0) return DXO_OK;
     if (!deps || !C_tang) return dxo_fail(ctx, DXO_E_NULL, "dxo_von_mises_state: NULL array");
     if (((uintptr_t)deps | (uintptr_t)C_tang | (uintptr_t)sigma | (uintptr_t)dp) & 7u)
         return dxo_fail(ctx, DXO_E_ALIGN, "dxo_von_mises_state: arrays must be 8-byte aligned");
-    VmLaunch L{make_const(*prm), d};
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    st->has_result = false;
-    const size_t sd = sizeof(double);
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = vm_launch(ctx, L, n, deps, st->sigma_n, st->p, C_tang, st->sigma, st->dp, s);
-        if (rc != DXO_OK) return rc;
-        if (sigma) DXO_HIP(ctx, hipMemcpyAsync(sigma, st->sigma, (size_t)n * d * sd, hipMemcpyDeviceToDevice, s));
-        if (dp) DXO_HIP(ctx, hipMemcpyAsync(dp, st->dp, (size_t)n * sd, hipMemcpyDeviceToDevice, s));
-        rc = dxo_device_end(ctx, s);
-        if (rc == DXO_OK) st->has_result = true;
-        return rc;
-    }
-    if (!sigma || !dp) return dxo_fail(ctx, DXO_E_NULL, "dxo_von_mises_state: host sigma / dp are required");
-    std::vector<dxo_span> in = {{deps, nullptr, d * sd}, {nullptr, nullptr, d * sd, st->sigma_n}, {nullptr, nullptr, sd, st->p}};
-    int rc;
-    if (ctx->vm_host_tangent && n >= ctx->vm_rebuild_min_points) {
-        L.h_sigma = sigma;
-        L.h_dp = dp;
-        L.h_C_tang = C_tang;
-        L.c.mark_indeterminate = 1;   // the mark (dp = -0.0) stays in the mirror's dp: p + (-0.0) == p at the commit
-        std::vector<dxo_span> out = {{nullptr, nullptr, 0}, {nullptr, sigma, d * sd, st->sigma}, {nullptr, dp, sd, st->dp}};
-        const int64_t saved_chunk = ctx->host_chunk_points;
-        if (ctx->host_chunk_points > ctx->vm_rebuild_chunk_points) ctx->host_chunk_points = ctx->vm_rebuild_chunk_points;
-        rc = dxo_run_host_pipeline(ctx, n, in, out, vm_chunk, &L, 1, vm_host_rebuild, true);
-        ctx->host_chunk_points = saved_chunk;
-    } else {
-        std::vector<dxo_span> out = {{nullptr, C_tang, d * d * sd}, {nullptr, sigma, d * sd, st->sigma}, {nullptr, dp, sd, st->dp}};
-        rc = dxo_run_host_pipeline(ctx, n, in, out, vm_chunk, &L, 1, nullptr, true);
-    }
-    if (rc == DXO_OK) st->has_result = true;
-    return rc;
+    return vm_run(ctx, "dxo_von_mises_state", prm, st->d, st->n, mem, deps, nullptr, nullptr, C_tang, sigma, dp, st);
 }
 
 // ------------------------------------------------------------------ history update
@@ -787,11 +696,9 @@ extern "C" int dxo_vm_clear_marks(dxo_ctx* ctx, int64_t n, double* dp) {
 extern "C" int dxo_vm_state_commit(dxo_ctx* ctx, dxo_vm_state* st) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
-    if (!st) return dxo_fail(ctx, DXO_E_NULL, "dxo_vm_state_commit: state is NULL");
-    if (st->n == 0) return DXO_OK;   // an empty partition (a rank without cells) has nothing to update: not an error
-    if (!st->has_result)
-        return dxo_fail(ctx, DXO_E_SIZE, "dxo_vm_state_commit: no call since the last upload / commit — nothing to commit");
-    int rc = dxo_vm_commit_state(ctx, st->d, st->n, st->p, st->dp, st->sigma_n, st->sigma);
+    int rc;
+    if (!dxo_state_can_commit(ctx, "dxo_vm_state_commit", st, &rc)) return rc;
+    rc = dxo_vm_commit_state(ctx, st->d, st->n, st->p, st->dp, st->sigma_n, st->sigma);
     if (rc != DXO_OK) return rc;
     DXO_HIP(ctx, hipStreamSynchronize(dxo_launch_stream(ctx)));   // the pipeline's streams read the mirror next
     st->has_result = false;

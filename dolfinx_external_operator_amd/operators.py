@@ -300,73 +300,84 @@ def make_von_mises(sigma_n, p, *, E: float = 70e3, nu: float = 0.3, sigma_0: flo
             return _like(deps, C_tang_, sigma_, dp_)
         return C_tang_, sigma_, dp_   # :352 (flat already)
 
-    def sigma_external(derivatives):
-        if derivatives == (1,):
-            return C_tang_impl
-        raise NotImplementedError(f"No external function is defined for the requested derivative {derivatives}.")
-
     def arena(n_points: int, d: int):
         """(C_tang, sigma, dp) as flat CUDA tensors inside the context's output arena (placement-calibrated device
         memory owned by the dxo_ctx, dxo_output_arena): the persistent coefficient buffers of a solver."""
         return _ctx().vm_output_tensors(n_points, d)
 
+    sigma_external = _plasticity_external("make_von_mises", C_tang_impl, prm, holder, ("C_tang", "sigma", "dp"), mirror)
+    sigma_external.context = _ctx
+    sigma_external.arena = arena
+    return sigma_external
+
+
+def _plasticity_external(factory: str, C_tang_impl, prm, holder: dict, names, mirror):
+    """The external function of the two plasticity factories: the `derivatives == (1,)` closure over `C_tang_impl` with bind, params,
+    commit_state, state_changed and check_state attached. Runs once, when the factory is called."""
+    def sigma_external(derivatives):
+        if derivatives == (1,):
+            return C_tang_impl
+        raise NotImplementedError(f"No external function is defined for the requested derivative {derivatives}.")
+
     def _need_mirror():
         if mirror is None:
-            raise RuntimeError('make_von_mises(..., state="resident") keeps a device mirror; this operator re-reads its state at every call')
+            raise RuntimeError(f'{factory}(..., state="resident") keeps a device mirror; this operator re-reads its state at every call')
         return mirror
 
     def bind(operator=None, *extras):
-        holder["targets"] = _bind_targets(("C_tang", "sigma", "dp"), operator, extras)
+        """One-line form of `outputs=`: element 0 of the result lands in `operator.ref_coefficient`'s storage (the
+        reference's assignment, external_operator.py:441, then finds source == destination), the others in the holders given."""
+        holder["targets"] = _bind_targets(names, operator, extras)
         holder["out"] = None          # rebuilt with the new targets at the next call
         return sigma_external
 
     sigma_external.bind = bind
     sigma_external.params = prm
-    sigma_external.context = _ctx
-    sigma_external.arena = arena
     sigma_external.commit_state = lambda: _need_mirror().commit()
     sigma_external.state_changed = lambda: _need_mirror().invalidate()
     sigma_external.check_state = lambda: _need_mirror().check()
     return sigma_external
 
 
-class _StateMirror:
-    """Host-side bookkeeping of a dxo_vm_state for make_von_mises(state="resident")."""
+class _Mirror:
+    """Host-side bookkeeping of a resident device state (dxo_vm_state, dxo_mc_state) for the plasticity factories: a tuple of holders
+    (the caller's history arrays), a factory for the device state, when the holders are uploaded and the sampled tripwire."""
 
     SAMPLES = 2048
 
-    def __init__(self, sigma_n_holder, p_holder):
-        self.holders = (sigma_n_holder, p_holder)
-        self.state = None            # _lib.VmState
+    def __init__(self, names, holders, make_state, tripped: str):
+        self.names, self.holders, self.tripped = names, holders, tripped
+        self.make_state = make_state   # (ctx, *shape) -> _lib.VmState / _lib.McState
+        self.state = None
+        self.shape = None
         self.fresh = False           # mirror == holders as far as we know
-        self.samples = None          # (sigma_n samples, p samples) taken when the mirror was last known to match
+        self.samples = None          # the holders' samples taken when the mirror was last known to match
         self.resample = False
 
-    def _take(self, sigma_n_, p_):
+    def _take(self, *arrays):
         """The tripwire's samples as BYTES (bit patterns, NaNs included): comparing two byte strings costs 2 us where
         np.array_equal(..., equal_nan=True) on the same 2 x 2048 entries costs 30 — a third of a call at the demos' sizes."""
-        ks = max(sigma_n_.size // self.SAMPLES, 1)
-        kp = max(p_.size // self.SAMPLES, 1)
-        return sigma_n_[::ks].tobytes(), p_[::kp].tobytes()
+        return tuple(a.reshape(-1)[::max(a.size // self.SAMPLES, 1)].tobytes() for a in arrays)
 
-    def sync(self, c: Context, d: int, n: int, sigma_n_, p_):
-        """The VmState to call, uploaded first if the mirror is not known to match the holders."""
-        if self.state is None or self.state.ctx is not c or self.state.d != d or self.state.n != n:
+    def sync(self, c: Context, *args):
+        """sync(ctx, *shape, *arrays), shape = (d, n) with (sigma_n, p) or (n,) with (sigma_n,): the device state to call, uploaded
+        first if the mirror is not known to match the holders."""
+        k = len(args) - len(self.holders)
+        shape, arrays = args[:k], args[k:]
+        if self.state is None or self.state.ctx is not c or self.shape != shape:
             if self.state is not None:
                 self.state.close()
-            self.state, self.fresh = c.vm_state(d, n), False
-        if self.fresh and not self.resample:
-            if self._take(sigma_n_, p_) != self.samples:
-                import warnings
+            self.state, self.shape, self.fresh = self.make_state(c, *shape), shape, False
+        if self.fresh and not self.resample and self._take(*arrays) != self.samples:
+            import warnings
 
-                warnings.warn("make_von_mises(state='resident'): sigma_n / p changed without commit_state() / state_changed(); "
-                              "re-uploading them", RuntimeWarning, stacklevel=4)
-                self.fresh = False
+            warnings.warn(self.tripped, RuntimeWarning, stacklevel=4)
+            self.fresh = False
         if not self.fresh:
-            self.state.upload(sigma_n_, p_)
+            self.state.upload(*arrays)
             self.fresh, self.resample = True, True
         if self.resample:
-            self.samples, self.resample = self._take(sigma_n_, p_), False
+            self.samples, self.resample = self._take(*arrays), False
         return self.state
 
     def commit(self):
@@ -381,10 +392,22 @@ class _StateMirror:
     def check(self) -> float:
         if self.state is None:
             raise RuntimeError("no call has been made yet")
-        sn, pp = self.state.download()
-        hs = _as_f64_host(_state_array(self.holders[0]), "sigma_n").reshape(-1)
-        hp = _as_f64_host(_state_array(self.holders[1]), "p").reshape(-1)
-        return float(max(np.max(np.abs(sn - hs), initial=0.0), np.max(np.abs(pp - hp), initial=0.0)))
+        got = self.state.download()
+        got = got if isinstance(got, tuple) else (got,)
+        want = (_as_f64_host(_state_array(h), name).reshape(-1) for h, name in zip(self.holders, self.names))
+        return float(max(np.max(np.abs(g - w), initial=0.0) for g, w in zip(got, want)))
+
+
+def _StateMirror(sigma_n_holder, p_holder):
+    """The mirror of make_von_mises(state="resident"): sync(ctx, d, n, sigma_n, p) -> _lib.VmState."""
+    return _Mirror(("sigma_n", "p"), (sigma_n_holder, p_holder), lambda c, d, n: c.vm_state(d, n),
+                   "make_von_mises(state='resident'): sigma_n / p changed without commit_state() / state_changed(); re-uploading them")
+
+
+def _McMirror(sigma_n_holder):
+    """The mirror of make_mohr_coulomb(state="resident"): sync(ctx, n, sigma_n) -> _lib.McState."""
+    return _Mirror(("sigma_n",), (sigma_n_holder,), lambda c, n: c.mc_state(n),
+                   "make_mohr_coulomb(state='resident'): sigma_n changed without commit_state() / state_changed(); re-uploading it")
 
 
 def _check_device_operand(c: Context, deps) -> None:
@@ -729,82 +752,9 @@ def make_mohr_coulomb(sigma_n, *, E: float = 6778.0, nu: float = 0.25, c: float 
                         "max_norm_res": float(np.nanmax(norm_res)) if np.isfinite(norm_res).any() else float("nan")})
         return _like(deps, C_tang.reshape(-1), sigma.reshape(-1))     # :593
 
-    def sigma_external(derivatives):
-        if derivatives == (1,):
-            return C_tang_impl
-        raise NotImplementedError(f"No external function is defined for the requested derivative {derivatives}.")
-
-    def _need_mirror():
-        if mirror is None:
-            raise RuntimeError('make_mohr_coulomb(..., state="resident") keeps a device mirror; this operator re-reads its state at every call')
-        return mirror
-
-    def bind(operator=None, *extras):
-        """One-line form of `outputs=`: element 0 of the result lands in `operator.ref_coefficient`'s storage (the
-        reference's assignment, external_operator.py:441, then finds source == destination), sigma in the holder given."""
-        holder["targets"] = _bind_targets(("C_tang", "sigma"), operator, extras)
-        holder["out"] = None
-        return sigma_external
-
-    sigma_external.bind = bind
-    sigma_external.params = prm
+    sigma_external = _plasticity_external("make_mohr_coulomb", C_tang_impl, prm, holder, ("C_tang", "sigma"), mirror)
     sigma_external.last_state = None
-    sigma_external.commit_state = lambda: _need_mirror().commit()
-    sigma_external.state_changed = lambda: _need_mirror().invalidate()
-    sigma_external.check_state = lambda: _need_mirror().check()
     return sigma_external
-
-
-class _McMirror:
-    """Host-side bookkeeping of a dxo_mc_state for make_mohr_coulomb(state="resident"): same protocol and the same
-    sampled tripwire as _StateMirror."""
-
-    SAMPLES = 2048
-
-    def __init__(self, sigma_n_holder):
-        self.holder = sigma_n_holder
-        self.state = None            # _lib.McState
-        self.fresh = False
-        self.samples = None
-        self.resample = False
-
-    def _take(self, sigma_n_):
-        flat = sigma_n_.reshape(-1)
-        return flat[::max(flat.size // self.SAMPLES, 1)].tobytes()      # compared as bytes (see _StateMirror._take)
-
-    def sync(self, cx: Context, n: int, sigma_n_):
-        if self.state is None or self.state.ctx is not cx or self.state.n != n:
-            if self.state is not None:
-                self.state.close()
-            self.state, self.fresh = cx.mc_state(n), False
-        if self.fresh and not self.resample and self._take(sigma_n_) != self.samples:
-            import warnings
-
-            warnings.warn("make_mohr_coulomb(state='resident'): sigma_n changed without commit_state() / state_changed(); "
-                          "re-uploading it", RuntimeWarning, stacklevel=4)
-            self.fresh = False
-        if not self.fresh:
-            self.state.upload(sigma_n_)
-            self.fresh, self.resample = True, True
-        if self.resample:
-            self.samples, self.resample = self._take(sigma_n_), False
-        return self.state
-
-    def commit(self):
-        if self.state is None or not self.fresh:
-            return
-        self.state.commit()
-        self.resample = True
-
-    def invalidate(self):
-        self.fresh = False
-
-    def check(self) -> float:
-        if self.state is None:
-            raise RuntimeError("no call has been made yet")
-        sn = self.state.download()
-        hs = _as_f64_host(_state_array(self.holder), "sigma_n").reshape(-1)
-        return float(np.max(np.abs(sn - hs), initial=0.0))
 
 
 def _mohr_coulomb_device(cx: Context, prm: McParams, deps, sigma_n, diagnostics: bool, on_summary, fn):

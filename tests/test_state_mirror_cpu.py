@@ -1,21 +1,26 @@
-"""Host-side bookkeeping of make_von_mises(state="resident") without a GPU: `_StateMirror` against a recording stand-in for
-`_lib.VmState` — when the holders are uploaded, when they are not, what commit_state / state_changed do, and the sampled
-tripwire. The device side of the same protocol is tests/test_vm_state_gpu.py."""
+"""Host-side bookkeeping of make_von_mises(state="resident") and make_mohr_coulomb(state="resident") without a GPU: `_StateMirror`
+and `_McMirror` against recording stand-ins for `_lib.VmState` / `_lib.McState` — when the holders are uploaded, when they are not,
+what commit_state / state_changed do, and the sampled tripwire. The device side of the same protocol is tests/test_vm_state_gpu.py
+and tests/test_return_map_entries_gpu.py."""
 import warnings
 
 import numpy as np
 import pytest
 
-from dolfinx_external_operator_amd.operators import _StateMirror
+from dolfinx_external_operator_amd.operators import _McMirror, _StateMirror
 
 
 class _FakeState:
-    def __init__(self, ctx, d, n):
-        self.ctx, self.d, self.n = ctx, d, n
+    """Stand-in for VmState (shape = (d, n), uploads of (sigma_n, p)) and McState (shape = (n,), uploads of (sigma_n,))."""
+
+    def __init__(self, ctx, *shape):
+        self.ctx, self.n = ctx, shape[-1]
+        if len(shape) == 2:
+            self.d = shape[0]
         self.uploads, self.commits, self.closed = [], 0, False
 
-    def upload(self, sigma_n, p):
-        self.uploads.append((sigma_n.copy(), p.copy()))
+    def upload(self, *arrays):
+        self.uploads.append(tuple(a.copy() for a in arrays))
 
     def commit(self):
         self.commits += 1
@@ -32,61 +37,96 @@ class _FakeCtx:
         self.states.append(_FakeState(self, d, n))
         return self.states[-1]
 
+    def mc_state(self, n):
+        self.states.append(_FakeState(self, n))
+        return self.states[-1]
 
-def test_upload_once_then_commit_then_tripwire():
-    n, d = 10_000, 6
+
+class _Form:
+    """One return map's mirror: its constructor, the leading arguments of sync() and how many holders it has."""
+
+    def __init__(self, name):
+        self.name = name
+        self.d = 6 if name == "vm" else 4
+
+    def arrays(self, n, rng=None):
+        """The holders of n points: (sigma_n, p) or (sigma_n,); zeros without a generator."""
+        if rng is None:
+            sigma_n, p = np.zeros(n * self.d), np.zeros(n)
+        else:
+            sigma_n, p = rng.normal(size=n * self.d), np.abs(rng.normal(size=n))
+        return (sigma_n, p) if self.name == "vm" else (sigma_n,)
+
+    def mirror(self, arrays):
+        return _StateMirror(*arrays) if self.name == "vm" else _McMirror(*arrays)
+
+    def sync(self, m, c, n, arrays):
+        return m.sync(c, self.d, n, *arrays) if self.name == "vm" else m.sync(c, n, *arrays)
+
+
+@pytest.fixture(params=["vm", "mc"])
+def form(request):
+    return _Form(request.param)
+
+
+def test_upload_once_then_commit_then_tripwire(form):
+    n = 10_000
     rng = np.random.Generator(np.random.PCG64(1))
-    sigma_n, p = rng.normal(size=n * d), np.abs(rng.normal(size=n))
+    arrays = form.arrays(n, rng)
+    sigma_n, last = arrays[0], arrays[-1]               # last: p (von Mises) or sigma_n itself (Mohr-Coulomb)
     c = _FakeCtx()
-    m = _StateMirror(sigma_n, p)
+    m = form.mirror(arrays)
     m.commit()                                          # nothing on the device yet: a no-op, not an error
-    st = m.sync(c, d, n, sigma_n, p)
+    st = form.sync(m, c, n, arrays)
     assert len(st.uploads) == 1 and len(c.states) == 1
     with warnings.catch_warnings():
         warnings.simplefilter("error")
         for _ in range(3):                              # Newton iterations of one load step: no traffic
-            assert m.sync(c, d, n, sigma_n, p) is st
+            assert form.sync(m, c, n, arrays) is st
     assert len(st.uploads) == 1
     sigma_n *= 1.01                                     # the reference's load-step update on the host ...
-    p += 0.5
+    if last is not sigma_n:
+        last += 0.5
     m.commit()                                          # ... announced: device-side commit, no upload, no warning
     with warnings.catch_warnings():
         warnings.simplefilter("error")
-        m.sync(c, d, n, sigma_n, p)
-        m.sync(c, d, n, sigma_n, p)
+        form.sync(m, c, n, arrays)
+        form.sync(m, c, n, arrays)
     assert st.commits == 1 and len(st.uploads) == 1
     sigma_n[::7] += 1.0                                 # changed behind the operator's back: tripwire -> warn + upload
     with pytest.warns(RuntimeWarning, match="re-uploading"):
-        m.sync(c, d, n, sigma_n, p)
+        form.sync(m, c, n, arrays)
     assert len(st.uploads) == 2 and np.array_equal(st.uploads[-1][0], sigma_n)
-    p[5] = 9.0                                          # a single entry the samples may miss: announced by the caller
+    assert len(st.uploads[-1]) == len(arrays)
+    last[5] = 9.0                                       # a single entry the samples may miss: announced by the caller
     m.invalidate()
     with warnings.catch_warnings():
         warnings.simplefilter("error")
-        m.sync(c, d, n, sigma_n, p)
-    assert len(st.uploads) == 3 and st.uploads[-1][1][5] == 9.0
+        form.sync(m, c, n, arrays)
+    assert len(st.uploads) == 3 and st.uploads[-1][-1][5] == 9.0
 
 
-def test_a_new_batch_size_or_context_gets_a_new_mirror():
+def test_a_new_batch_size_or_context_gets_a_new_mirror(form):
     c1, c2 = _FakeCtx(), _FakeCtx()
-    a, b = np.zeros(600), np.zeros(100)
-    m = _StateMirror(a, b)
-    s1 = m.sync(c1, 6, 100, a, b)
-    a2, b2 = np.zeros(1200), np.zeros(200)
-    s2 = m.sync(c1, 6, 200, a2, b2)
+    small = form.arrays(100)
+    m = form.mirror(small)
+    s1 = form.sync(m, c1, 100, small)
+    large = form.arrays(200)
+    s2 = form.sync(m, c1, 200, large)
     assert s2 is not s1 and s1.closed and len(s2.uploads) == 1
-    s3 = m.sync(c2, 6, 200, a2, b2)
+    s3 = form.sync(m, c2, 200, large)
     assert s3 is not s2 and s2.closed and s3.ctx is c2 and len(s3.uploads) == 1
     with pytest.raises(RuntimeError, match="no call"):
-        _StateMirror(a, b).check()
+        form.mirror(small).check()
 
 
-def test_nan_state_does_not_trip_the_wire():
-    a, b = np.full(600, np.nan), np.zeros(100)
+def test_nan_state_does_not_trip_the_wire(form):
+    arrays = form.arrays(100)
+    arrays[0][:] = np.nan
     c = _FakeCtx()
-    m = _StateMirror(a, b)
-    st = m.sync(c, 6, 100, a, b)
+    m = form.mirror(arrays)
+    st = form.sync(m, c, 100, arrays)
     with warnings.catch_warnings():
         warnings.simplefilter("error")
-        m.sync(c, 6, 100, a, b)                          # NaN == NaN for the comparison of samples
+        form.sync(m, c, 100, arrays)                     # NaN == NaN for the comparison of samples
     assert len(st.uploads) == 1
