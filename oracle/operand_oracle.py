@@ -11,6 +11,9 @@ Parity status: UNPINNED against DOLFINx (not executable here; the reference's ow
 test/test_operands_evaluation.py:55-66, compares against Expression.eval itself). Pinned instead by known answers:
 polynomial fields of the element's degree are represented exactly, so their analytic gradients at the physical
 quadrature points are the expected output (tests/test_operand_eval.py).
+Pinned componentwise by oracle/operand_reference.py, its long-double restatement: tests/test_operand_reference_cpu.py measures what
+this float64 oracle loses against it entry by entry (tests/operand_cases.py C_REF), tests/test_operand_reference_gpu.py holds the HIP
+kernels to 8 times that.
 """
 from __future__ import annotations
 
