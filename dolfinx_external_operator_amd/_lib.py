@@ -237,6 +237,9 @@ _SIGNATURES = {
     "dxo_eval_facet_geometry": (C.c_int, [_P, _P, _P, _P, _P]),
     "dxo_facet_adjoint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "dxo_facet_pressure": (C.c_int, [_P, _P, _P, _P, C.c_double, _P]),
+    "dxo_facet_bilinear_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "dxo_facet_bilinear_diagonal": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "dxo_facet_bilinear_assemble": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dxo_tangent_apply_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P, _P]),
     "dxo_von_mises_residual": (C.c_int, [_P, C.POINTER(VmParams), _P, _P, _P, _P, _P, _P, _P]),
     "dxo_tangent_diagonal_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P]),

@@ -41,7 +41,7 @@
 
 namespace {
 
-constexpr int64_t AS_AUTO_SCRATCH_BYTES = (int64_t)1 << 30;   // option assemble_chunk_cells = 0: element matrices of a chunk <= 1 GiB
+constexpr int64_t AS_AUTO_SCRATCH_BYTES = DXO_AS_AUTO_SCRATCH_BYTES;   // option assemble_chunk_cells = 0 (csr.h)
 
 template <int G, int BS, int TEST, int TRIAL>
 struct AsShape {

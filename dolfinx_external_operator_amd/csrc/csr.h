@@ -4,6 +4,9 @@
 
 #include "dxo_common.h"
 
+// option assemble_chunk_cells = 0: the element matrices of a chunk (of cells, assemble.hip; of facet entities, facet_form.hip) <= 1 GiB
+constexpr int64_t DXO_AS_AUTO_SCRATCH_BYTES = (int64_t)1 << 30;
+
 struct dxo_csr {
     const dxo_mesh* mesh = nullptr;
     int bs = 0, nd = 0;

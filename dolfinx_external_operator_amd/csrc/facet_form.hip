@@ -12,6 +12,8 @@
 //                   Phase 2, lane = (entity, local dof): the fixed-order sum over the entity's points into fe[entity][a][i].
 //   facet_node_sum: lane = touched node, adds the node's entries of fe in ascending entity order (the set's transposed incidence).
 // No atomics: the result is bit-reproducible. The calls always accumulate into out.
+// The Jacobian of a state-dependent boundary term (dxo_facet_bilinear_apply / _diagonal / _assemble) is at the end of the file.
+#include "csr.h"
 #include "dxo_common.h"
 #include "facet_tabs.h"
 
@@ -27,6 +29,8 @@ struct dxo_facet_set {
     int32_t* d_tnode = nullptr;      // [n_touched] the nodes, ascending
     int64_t* d_tptr = nullptr;       // [n_touched + 1]
     uint32_t* d_tent = nullptr;      // [n * nd] entries e * nd + a of each node, ascending entity order
+    double* d_ae = nullptr;          // element-matrix scratch of one chunk of entities (dxo_facet_bilinear_assemble), grow-only
+    size_t ae_cap = 0;
 };
 
 namespace {
@@ -232,7 +236,7 @@ int facet_ready(dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, const
 }
 
 void set_free(dxo_facet_set* set) {
-    free_all({set->d_ents, set->d_fe, set->d_tnode, set->d_tptr, set->d_tent});
+    free_all({set->d_ents, set->d_fe, set->d_tnode, set->d_tptr, set->d_tent, set->d_ae});
     delete set;
 }
 
@@ -372,5 +376,396 @@ extern "C" int dxo_facet_pressure(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set
     if (rc != DXO_OK) return rc;
     with_gdim(m->gdim, [&](auto G) { launch_element<G, G, FACET_PRESSURE>(ctx, m, set, p, scale, s); });
     launch_node_sum(ctx, set, m->gdim, out, s);
+    return dxo_device_end(ctx, s);
+}
+
+// ---- bilinear forms on the set's facets: the Jacobian of a boundary term g(operand(u)) . v ds,
+//   K[(a,i),(b,j)] = sum_e sum_q dS_eq phi_a(x_eq) sum_r C_eq[i][r] (B_trial,eq)_r,(b,j),   C [n][nq][BS][D_trial]
+// with dS and the tables those of dxo_facet_adjoint. The test side is the value; row i of the point's block is an operand value of the
+// trial kind, so its dual data (vh[BS], T[BS][G] = dS * dual_tensor of C[i][:] pulled back to reference gradients) is the row of K:
+//   K[(a,i),(b,j)] = sum_q phi_a (vh_i[j] phi_b + sum_k T_i[j][k] dphi_b,k).
+//   apply    facet_bilinear_element<.., false>: lane = (entity, point) forms the trial operand of v and parks dS C w; lane = (entity,
+//            local dof) sums over the points into the set's fe; facet_node_sum finishes (two launches, as the loads).
+//   diagonal facet_bilinear_element<.., true>: parks (vh_i[i], T_i[i][:]), then phi_a (vh_i[i] phi_a + sum_k T_i[i][k] dphi_a,k).
+//   assemble two passes per chunk of entities, as assemble.hip: facet_assemble_elem parks the point's BS x BS x NZ block and lane =
+//            (entity, a, b) writes ae[e][a*BS+i][b*BS+j]; facet_assemble_rows, lane = (touched node, component), walks the node's
+//            incidences in ascending entity order and adds into values through row_ptr / pos. Every value is the same chain of
+//            additions whatever the chunk size.
+// No atomics; the calls always accumulate.
+namespace {
+
+template <int KIND>
+constexpr bool fb_value() { return KIND == DXO_OPERAND_VALUE || KIND == DXO_OPERAND_VALUE_GRAD; }
+template <int KIND>
+constexpr bool fb_grad() { return KIND != DXO_OPERAND_VALUE; }
+// parked doubles per (i, j): the value slot where the kind has one, G reference-gradient slots where it has a gradient
+template <int G, int KIND>
+constexpr int fb_nz() { return (fb_value<KIND>() ? 1 : 0) + (fb_grad<KIND>() ? G : 0); }
+
+constexpr int FB_LDS_DOUBLES = 64 * 1024 / 8;
+
+// the dual data of one row of the point's block: vh = dS * value part, T = dS * gradient part pulled back to reference gradients
+template <int G, int BS, int KIND>
+__device__ __forceinline__ void fb_row_dual(const double* __restrict__ Crow, const double (&K)[G][G], double ds, double (&vh)[BS],
+                                            double (&T)[BS][G]) {
+    constexpr int D = OperandShape<G, BS, KIND>::D;
+    double s[D], gh[BS][G];
+#pragma unroll
+    for (int k = 0; k < D; ++k) s[k] = Crow[k];
+    dual_tensor<G, BS, KIND>(s, vh, gh);
+#pragma unroll
+    for (int i = 0; i < BS; ++i) vh[i] *= ds;
+    pull_back<G, BS>(gh, K, ds, T);
+}
+
+// element vectors of K v (DIAG = false) or of diag K (DIAG = true) into fe[e][a][i]
+template <int G, int BS, int KIND, bool DIAG>
+__global__ __launch_bounds__(DXO_BLOCK) void facet_bilinear_element(OperandDev m, FacetTabs<G> t, const int32_t* __restrict__ ents,
+                                                                    int64_t n, const double* __restrict__ C,
+                                                                    const double* __restrict__ v, double* __restrict__ fe) {
+    constexpr int D = OperandShape<G, BS, KIND>::D, NZ = fb_nz<G, KIND>();
+    constexpr int PW = DIAG ? BS * NZ : BS;               // doubles parked per point
+    extern __shared__ double lds[];
+    const int nqf = t.nqf, nd = t.nd;
+    const int epb = DXO_BLOCK / nqf;                      // entities per workgroup and round
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < n; e0 += (int64_t)gridDim.x * epb) {
+        const int ne = (int)(n - e0 < epb ? n - e0 : epb);
+        if ((int)threadIdx.x < ne * nqf) {
+            const int le = threadIdx.x / nqf, q = threadIdx.x - le * nqf;
+            const int64_t e = e0 + le;
+            const int64_t cell = ents[2 * e];
+            const int f = ents[2 * e + 1];
+            double K[G][G], nrm[G], ds;
+            facet_point_geometry<G>(m, t, cell, f, q, K, nrm, ds);
+            const double* Cp = C + (e * nqf + q) * (int64_t)(BS * D);
+            double* P = lds + threadIdx.x * PW;
+            if constexpr (DIAG) {
+#pragma unroll
+                for (int i = 0; i < BS; ++i) {
+                    double vh[BS], T[BS][G];
+                    fb_row_dual<G, BS, KIND>(Cp + i * D, K, ds, vh, T);
+                    int z = 0;
+                    if constexpr (fb_value<KIND>()) P[i * NZ + z++] = vh[i];
+                    if constexpr (fb_grad<KIND>()) {
+#pragma unroll
+                        for (int k = 0; k < G; ++k) P[i * NZ + z + k] = T[i][k];
+                    }
+                }
+            } else {
+                // the trial operand of v at the point, as operand_eval_facets forms it
+                const size_t row = ((size_t)f * nqf + q) * nd;
+                double val[BS], gref[BS][G];
+#pragma unroll
+                for (int i = 0; i < BS; ++i) {
+                    val[i] = 0.0;
+#pragma unroll
+                    for (int k = 0; k < G; ++k) gref[i][k] = 0.0;
+                }
+                for (int a = 0; a < nd; ++a) {
+                    const int64_t node = m.dofmap[cell * nd + a];
+                    double va[BS];
+#pragma unroll
+                    for (int i = 0; i < BS; ++i) va[i] = v[node * BS + i];
+                    if constexpr (fb_value<KIND>()) {
+                        const double ph = t.phi[row + a];
+#pragma unroll
+                        for (int i = 0; i < BS; ++i) val[i] += va[i] * ph;
+                    }
+                    if constexpr (fb_grad<KIND>()) {
+#pragma unroll
+                        for (int k = 0; k < G; ++k) {
+                            const double dk = t.dphi[(row + a) * G + k];
+#pragma unroll
+                            for (int i = 0; i < BS; ++i) gref[i][k] += va[i] * dk;
+                        }
+                    }
+                }
+                double g[BS][G];
+#pragma unroll
+                for (int i = 0; i < BS; ++i)
+#pragma unroll
+                    for (int j = 0; j < G; ++j) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int k = 0; k < G; ++k) s += gref[i][k] * K[k][j];
+                        g[i][j] = s;
+                    }
+                double o[D];
+                shape_operand<G, BS, KIND>(val, g, o);
+#pragma unroll
+                for (int i = 0; i < BS; ++i) {
+                    double w = 0.0;
+#pragma unroll
+                    for (int r = 0; r < D; ++r) w += Cp[i * D + r] * o[r];
+                    P[i] = ds * w;
+                }
+            }
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < ne * nd; idx += blockDim.x) {
+            const int le = idx / nd, a = idx - le * nd;
+            const int64_t e = e0 + le;
+            const int f = ents[2 * e + 1];
+            double acc[BS];
+#pragma unroll
+            for (int i = 0; i < BS; ++i) acc[i] = 0.0;
+            for (int q = 0; q < nqf; ++q) {
+                const double* P = lds + (le * nqf + q) * PW;
+                const size_t row = ((size_t)f * nqf + q) * nd + a;
+                const double ph = t.phi[row];
+                if constexpr (!DIAG) {
+#pragma unroll
+                    for (int i = 0; i < BS; ++i) acc[i] += P[i] * ph;
+                } else {
+                    double za[NZ];
+                    int z = 0;
+                    if constexpr (fb_value<KIND>()) za[z++] = ph;
+                    if constexpr (fb_grad<KIND>()) {
+#pragma unroll
+                        for (int k = 0; k < G; ++k) za[z + k] = t.dphi[row * G + k];
+                    }
+#pragma unroll
+                    for (int i = 0; i < BS; ++i) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int zz = 0; zz < NZ; ++zz) s += P[i * NZ + zz] * za[zz];
+                        acc[i] += ph * s;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < BS; ++i) fe[(e * nd + a) * BS + i] = acc[i];
+        }
+        __syncthreads();     // the next round overwrites the parked points
+    }
+}
+
+// parked doubles per point of the assembly: the BS x BS x NZ block, odd stride (bank spread across points)
+template <int G, int BS, int KIND>
+constexpr int fb_block_stride() { return (BS * BS * fb_nz<G, KIND>()) | 1; }
+
+// pass 1: the element matrices of the entities [e_begin, e_end) into ae[e - e_begin][a*BS + i][b*BS + j]; epb entities per round
+template <int G, int BS, int KIND>
+__global__ __launch_bounds__(DXO_BLOCK) void facet_assemble_elem(OperandDev m, FacetTabs<G> t, const int32_t* __restrict__ ents,
+                                                                 int64_t e_begin, int64_t e_end, int epb, const double* __restrict__ C,
+                                                                 double* __restrict__ ae) {
+    constexpr int D = OperandShape<G, BS, KIND>::D, NZ = fb_nz<G, KIND>(), PS = fb_block_stride<G, BS, KIND>();
+    extern __shared__ double lds[];
+    const int nqf = t.nqf, nd = t.nd, ndb = nd * BS;
+    for (int64_t e0 = e_begin + (int64_t)blockIdx.x * epb; e0 < e_end; e0 += (int64_t)gridDim.x * epb) {
+        const int ne = (int)(e_end - e0 < epb ? e_end - e0 : epb);
+        if ((int)threadIdx.x < ne * nqf) {               // epb * nqf <= DXO_BLOCK
+            const int le = threadIdx.x / nqf, q = threadIdx.x - le * nqf;
+            const int64_t e = e0 + le;
+            double K[G][G], nrm[G], ds;
+            facet_point_geometry<G>(m, t, ents[2 * e], ents[2 * e + 1], q, K, nrm, ds);
+            const double* Cp = C + (e * nqf + q) * (int64_t)(BS * D);
+            double* P = lds + threadIdx.x * PS;
+#pragma unroll
+            for (int i = 0; i < BS; ++i) {
+                double vh[BS], T[BS][G];
+                fb_row_dual<G, BS, KIND>(Cp + i * D, K, ds, vh, T);
+#pragma unroll
+                for (int j = 0; j < BS; ++j) {
+                    double* Pij = P + (i * BS + j) * NZ;
+                    int z = 0;
+                    if constexpr (fb_value<KIND>()) Pij[z++] = vh[j];
+                    if constexpr (fb_grad<KIND>()) {
+#pragma unroll
+                        for (int k = 0; k < G; ++k) Pij[z + k] = T[j][k];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < ne * nd * nd; idx += blockDim.x) {
+            const int le = idx / (nd * nd), ab = idx - le * nd * nd, a = ab / nd, b = ab - a * nd;
+            const int64_t e = e0 + le;
+            const int f = ents[2 * e + 1];
+            double acc[BS][BS];
+#pragma unroll
+            for (int i = 0; i < BS; ++i)
+#pragma unroll
+                for (int j = 0; j < BS; ++j) acc[i][j] = 0.0;
+            for (int q = 0; q < nqf; ++q) {
+                const double* P = lds + (le * nqf + q) * PS;
+                const size_t row = ((size_t)f * nqf + q) * nd;
+                const double pa = t.phi[row + a];
+                double zb[NZ];
+                int z = 0;
+                if constexpr (fb_value<KIND>()) zb[z++] = t.phi[row + b];
+                if constexpr (fb_grad<KIND>()) {
+#pragma unroll
+                    for (int k = 0; k < G; ++k) zb[z + k] = t.dphi[(row + b) * G + k];
+                }
+#pragma unroll
+                for (int i = 0; i < BS; ++i)
+#pragma unroll
+                    for (int j = 0; j < BS; ++j) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int zz = 0; zz < NZ; ++zz) s += P[(i * BS + j) * NZ + zz] * zb[zz];
+                        acc[i][j] += pa * s;
+                    }
+            }
+            double* dst = ae + ((e - e_begin) * ndb + (int64_t)a * BS) * ndb + b * BS;
+#pragma unroll
+            for (int i = 0; i < BS; ++i)
+#pragma unroll
+                for (int j = 0; j < BS; ++j) dst[(int64_t)i * ndb + j] = acc[i][j];
+        }
+        __syncthreads();     // the next round overwrites the parked blocks
+    }
+}
+
+// pass 2: one lane per (touched node, component) adds the rows of the chunk's entities [e_begin, e_end) in ascending entity order
+template <int BS>
+__global__ __launch_bounds__(DXO_BLOCK) void facet_assemble_rows(int64_t n_touched, int nd, const int32_t* __restrict__ tnode,
+                                                                 const int64_t* __restrict__ tptr, const uint32_t* __restrict__ tent,
+                                                                 const int32_t* __restrict__ ents, const int64_t* __restrict__ row_ptr,
+                                                                 const uint16_t* __restrict__ pos, const double* __restrict__ ae,
+                                                                 int64_t e_begin, int64_t e_end, double* __restrict__ values) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int ndb = nd * BS;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_touched * BS; r += stride) {
+        const int64_t t = r / BS;
+        const int i = (int)(r - t * BS);
+        const int64_t j0 = tptr[t], j1 = tptr[t + 1];
+        if (j0 == j1 || (int64_t)(tent[j1 - 1] / nd) < e_begin || (int64_t)(tent[j0] / nd) >= e_end) continue;
+        double* row = values + row_ptr[(int64_t)tnode[t] * BS + i];
+        for (int64_t j = j0; j < j1; ++j) {
+            const uint32_t ent = tent[j];
+            const int64_t e = ent / nd;
+            if (e < e_begin) continue;
+            if (e >= e_end) break;
+            const int a = (int)(ent - e * nd);
+            const double* src = ae + ((e - e_begin) * ndb + (int64_t)a * BS + i) * ndb;
+            const uint16_t* pp = pos + ((int64_t)ents[2 * e] * nd + a) * nd;
+            for (int b = 0; b < nd; ++b) {
+                double* dst = row + (int64_t)pp[b] * BS;
+#pragma unroll
+                for (int jj = 0; jj < BS; ++jj) dst[jj] += src[b * BS + jj];
+            }
+        }
+    }
+}
+
+// f(int_c<G>, int_c<BS>, int_c<KIND>) for the trial kinds and shapes of the facet forms (DEFGRAD has been replaced by GRAD)
+template <class F>
+int with_facet_trial(int gdim, int bs, int kind, F&& f) {
+    return with_form_shape(gdim, bs, [&](auto G, auto BS) {
+        int rc = DXO_E_OPTION;
+        auto any = [&](auto K) { f(G, BS, K); rc = DXO_OK; };
+        auto vec = [&](auto K) {
+            if constexpr (decltype(BS)::value == decltype(G)::value) any(K);
+            else rc = DXO_E_DIM;
+        };
+        with_int<DXO_OPERAND_VALUE, DXO_OPERAND_GRAD, DXO_OPERAND_VALUE_GRAD>(
+            kind, any, [&](int) { with_int<DXO_OPERAND_EPS_MANDEL, DXO_OPERAND_DIV>(kind, vec, [](int) {}); });
+        return rc;
+    });
+}
+
+// the opening of the three calls: facet_ready, the test kind, the trial kind (*kind = the kind the kernels take) and the block size
+int facet_bilinear_ready(dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, int test, int trial, int bs, const char* who, int* kind) {
+    const int rc = facet_ready(ctx, m, set, who);
+    if (rc != DXO_OK) return rc;
+    if (test != DXO_OPERAND_VALUE) return fail_who(ctx, DXO_E_OPTION, who, "the test kind must be DXO_OPERAND_VALUE (a boundary residual g . v ds)");
+    if (op_is_nonlinear(trial)) return fail_who(ctx, DXO_E_OPTION, who, "a nonlinear trial operand (C, I1, det F) has no bilinear form — pass its linearisation's block");
+    const int D = dxo_operand_value_size(m->gdim, bs, trial);
+    if (D == DXO_E_OPTION) return fail_who(ctx, DXO_E_OPTION, who, "unknown trial operand kind");
+    if (D < 0 || (bs != 1 && bs != m->gdim)) return fail_who(ctx, DXO_E_DIM, who, "block size does not fit the trial kind / gdim (bs = 1 or gdim)");
+    *kind = trial == DXO_OPERAND_DEFGRAD ? DXO_OPERAND_GRAD : trial;
+    // the shape lookup the launches repeat: a miss is reported here, before dxo_device_begin
+    const int shape = with_facet_trial(m->gdim, bs, *kind, [](auto, auto, auto) {});
+    if (shape != DXO_OK) return fail_who(ctx, shape, who, "unsupported (gdim, bs, trial kind)");
+    return DXO_OK;
+}
+
+// dxo_facet_bilinear_apply (v != NULL) and dxo_facet_bilinear_diagonal (v == NULL, diag)
+int facet_bilinear_vector(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set* set, int test, int trial, int bs, const double* C, const double* v,
+                          bool diag, double* out, const char* who) {
+    int kind = 0;
+    int rc = facet_bilinear_ready(ctx, m, set, test, trial, bs, who, &kind);
+    if (rc != DXO_OK) return rc;
+    if (set->n == 0) return DXO_OK;
+    if (!C || !out || (!diag && !v)) return fail_who(ctx, DXO_E_NULL, who, "NULL array");
+    if (((uintptr_t)C | (uintptr_t)v | (uintptr_t)out) & 7u) return fail_who(ctx, DXO_E_ALIGN, who, "arrays must be 8-byte aligned");
+    hipStream_t s = dxo_launch_stream(ctx);
+    rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    with_facet_trial(m->gdim, bs, kind, [&](auto G, auto BS, auto KIND) {
+        const FacetTabs<G> t = facet_tabs<G>(m);
+        const int epb = DXO_BLOCK / t.nqf;
+        const dim3 grid(capped_grid(ctx, set->n, epb, 8));
+        if (diag) {
+            const size_t shm = (size_t)epb * t.nqf * BS * fb_nz<G, KIND>() * sizeof(double);
+            hipLaunchKernelGGL((facet_bilinear_element<G, BS, KIND, true>), grid, dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents, set->n, C, v,
+                               set->d_fe);
+        } else {
+            const size_t shm = (size_t)epb * t.nqf * BS * sizeof(double);
+            hipLaunchKernelGGL((facet_bilinear_element<G, BS, KIND, false>), grid, dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents, set->n, C, v,
+                               set->d_fe);
+        }
+    });
+    launch_node_sum(ctx, set, bs, out, s);
+    return dxo_device_end(ctx, s);
+}
+
+}  // namespace
+
+extern "C" int dxo_facet_bilinear_apply(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set* set, int test_kind, int trial_kind, int bs,
+                                        const double* C, const double* v, double* out) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    return facet_bilinear_vector(ctx, m, set, test_kind, trial_kind, bs, C, v, false, out, "dxo_facet_bilinear_apply");
+}
+
+extern "C" int dxo_facet_bilinear_diagonal(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set* set, int test_kind, int trial_kind, int bs,
+                                           const double* C, double* out) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    return facet_bilinear_vector(ctx, m, set, test_kind, trial_kind, bs, C, nullptr, true, out, "dxo_facet_bilinear_diagonal");
+}
+
+extern "C" int dxo_facet_bilinear_assemble(dxo_ctx* ctx, dxo_mesh* m, dxo_facet_set* set, dxo_csr* csr, int test_kind, int trial_kind, int bs,
+                                           const double* C, double* values) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    const char* who = "dxo_facet_bilinear_assemble";
+    if (!csr) return fail_who(ctx, DXO_E_NULL, who, "pattern is NULL");
+    int kind = 0;
+    int rc = facet_bilinear_ready(ctx, m, set, test_kind, trial_kind, bs, who, &kind);
+    if (rc != DXO_OK) return rc;
+    if (csr->mesh != m || csr->bs != bs) return fail_who(ctx, DXO_E_DIM, who, "the pattern was made for another mesh or block size");
+    if (set->n == 0) return DXO_OK;
+    if (!C || !values) return fail_who(ctx, DXO_E_NULL, who, "NULL array");
+    if (((uintptr_t)C | (uintptr_t)values) & 7u) return fail_who(ctx, DXO_E_ALIGN, who, "arrays must be 8-byte aligned");
+    const int nd = set->nd, nqf = m->nq_facet;
+    int ps = 0;
+    with_facet_trial(m->gdim, bs, kind, [&](auto G, auto BS, auto KIND) { ps = fb_block_stride<G, BS, KIND>(); });
+    if (nqf * ps > FB_LDS_DOUBLES) return fail_who(ctx, DXO_E_SIZE, who, "facet rule too large for the LDS budget");
+    const int epb = std::min(DXO_BLOCK / nqf, FB_LDS_DOUBLES / (nqf * ps));      // the parked blocks of a round stay within 64 KiB
+    const size_t ent_bytes = (size_t)nd * bs * nd * bs * sizeof(double);
+    int64_t chunk = ctx->assemble_chunk_cells > 0 ? ctx->assemble_chunk_cells : std::max<int64_t>(1, DXO_AS_AUTO_SCRATCH_BYTES / (int64_t)ent_bytes);
+    if (chunk > set->n) chunk = set->n;
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    rc = device_buf(ctx, (void**)&set->d_ae, &set->ae_cap, (size_t)chunk * ent_bytes);      // the first call (or a larger chunk) allocates
+    if (rc != DXO_OK) return rc;
+    hipStream_t s = dxo_launch_stream(ctx);
+    rc = dxo_device_begin(ctx, s);
+    if (rc != DXO_OK) return rc;
+    const int rblocks = capped_grid(ctx, set->n_touched * bs, DXO_BLOCK, 8);
+    for (int64_t e0 = 0; e0 < set->n; e0 += chunk) {
+        const int64_t e1 = std::min(set->n, e0 + chunk);
+        with_facet_trial(m->gdim, bs, kind, [&](auto G, auto BS, auto KIND) {
+            hipLaunchKernelGGL((facet_assemble_elem<G, BS, KIND>), dim3(capped_grid(ctx, e1 - e0, epb, 8)), dim3(DXO_BLOCK),
+                               (size_t)epb * nqf * ps * sizeof(double), s, m->dev, facet_tabs<G>(m), set->d_ents, e0, e1, epb, C, set->d_ae);
+        });
+        with_node_bs(bs, [&](auto BS) {
+            hipLaunchKernelGGL(facet_assemble_rows<BS>, dim3(rblocks), dim3(DXO_BLOCK), 0, s, set->n_touched, nd, set->d_tnode, set->d_tptr,
+                               set->d_tent, set->d_ents, csr->d_row_ptr, csr->d_pos, set->d_ae, e0, e1, values);
+        });
+    }
     return dxo_device_end(ctx, s);
 }

@@ -207,6 +207,35 @@ class DeviceMesh:
         self.ctx.check(rc, "dxo_eval_operand_facets")
         return out
 
+    def evaluate_facets_device(self, kind: str, bs: int, u, entities, out=None):
+        """evaluate_facets on the device, asynchronous on the context's stream: u a float64 CUDA tensor of num_field_nodes * bs entries,
+        entities an int32 CUDA tensor (n, 2) of (cell, local facet) pairs (e.g. a CUDA copy of FacetSet.entities; the device path does
+        not range-check them, as dxo_eval_operand_facets says), out a float64 CUDA tensor of n * nq_facet * value_size entries or None
+        for a new one. Returns out, shaped (n, nq_facet, value_size) when it was made here."""
+        import torch
+
+        D = self.value_size(kind, bs)
+        if not hasattr(self, "nq_facet"):
+            raise ValueError("evaluate_facets_device: facet tables not set (set_facet_tables)")
+        dev = torch.device("cuda", self.ctx.device)
+
+        def ok(t, dtype):
+            return isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.is_contiguous()
+
+        if not ok(u, torch.float64) or u.numel() != self.num_field_nodes * bs:
+            raise ValueError(f"evaluate_facets_device: u must be a contiguous float64 CUDA tensor of {self.num_field_nodes * bs} entries")
+        if not ok(entities, torch.int32) or entities.ndim != 2 or entities.shape[1] != 2:
+            raise ValueError("evaluate_facets_device: entities must be a contiguous int32 CUDA tensor of shape (n, 2): (cell, local facet)")
+        n = entities.shape[0]
+        if out is None:
+            out = torch.empty((n, self.nq_facet, D), dtype=torch.float64, device=dev)
+        if not ok(out, torch.float64) or out.numel() != n * self.nq_facet * D:
+            raise ValueError(f"evaluate_facets_device: out must be a contiguous float64 CUDA tensor of {n * self.nq_facet * D} entries")
+        rc = self.ctx.lib.dxo_eval_operand_facets(self.ctx._h, self._h, KINDS[kind], int(bs), MEM_DEVICE, C.c_void_p(u.data_ptr()),
+                                                  C.c_void_p(entities.data_ptr()), n, C.c_void_p(out.data_ptr()))
+        self.ctx.check(rc, "dxo_eval_operand_facets")
+        return out
+
     def evaluate_device(self, kind: str, bs: int, u_ptr: int, n_cells: int, out_ptr: int, cells_ptr: int | None = None) -> None:
         """Raw device pointers, asynchronous on the context's stream."""
         rc = self.ctx.lib.dxo_eval_operand(self.ctx._h, self._h, KINDS[kind], int(bs), MEM_DEVICE, C.c_void_p(u_ptr),
@@ -385,6 +414,56 @@ class DeviceMesh:
         rc = self.ctx.lib.dxo_facet_pressure(self.ctx._h, self._h, facet_set._h, None if p_ptr is None else C.c_void_p(p_ptr), float(scale),
                                              C.c_void_p(out_ptr))
         self.ctx.check(rc, "dxo_facet_pressure")
+
+    # trial kinds of the facet bilinear forms: the linear kinds, "F" standing for its linearisation, grad
+    FACET_BILINEAR_TRIALS = FACET_ADJOINT_KINDS
+
+    def _facet_bilinear_kinds(self, who: str, test: str, trial: str, bs: int) -> tuple[int, int]:
+        if test != "value":
+            raise ValueError(f"{who}: the test kind must be 'value' (a boundary residual g . v ds), not {test!r}")
+        if trial not in self.FACET_BILINEAR_TRIALS:
+            raise ValueError(f"{who}: trial kind {trial!r} has no bilinear form; linear kinds: {self.FACET_BILINEAR_TRIALS}")
+        if int(bs) not in (1, self.gdim) or (trial in ("eps", "div", "F") and int(bs) != self.gdim):
+            raise ValueError(f"{who}: bs = {bs} does not fit trial kind {trial!r} on gdim {self.gdim} (bs = 1 or gdim; eps / div / F: gdim)")
+        return KINDS[test], KINDS[trial]
+
+    def facet_bilinear_apply(self, trial: str, bs: int, C_ptr: int, v_ptr: int, facet_set: "FacetSet", out_ptr: int, test: str = "value") -> None:
+        """out += K v with K[(a,i),(b,j)] = sum_e sum_q dS phi_a sum_r C[i][r] (B_trial)_r,(b,j) over the set's facets
+        (dxo_facet_bilinear_apply; DEVICE pointers, C (n, nq_facet, bs, value_size(trial, bs))): the action of the Jacobian of a boundary
+        term g(operand(u)) . v ds with C = dg/d operand — ("value", 1) with C = dg/dT is a Robin term. Always accumulates."""
+        t, r = self._facet_bilinear_kinds("facet_bilinear_apply", test, trial, bs)
+        rc = self.ctx.lib.dxo_facet_bilinear_apply(self.ctx._h, self._h, facet_set._h, t, r, int(bs), C.c_void_p(C_ptr), C.c_void_p(v_ptr),
+                                                   C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_facet_bilinear_apply")
+
+    def facet_bilinear_diagonal(self, trial: str, bs: int, C_ptr: int, facet_set: "FacetSet", out_ptr: int, test: str = "value") -> None:
+        """out += diag of the same operator as facet_bilinear_apply (dxo_facet_bilinear_diagonal; DEVICE pointers). Always accumulates."""
+        t, r = self._facet_bilinear_kinds("facet_bilinear_diagonal", test, trial, bs)
+        rc = self.ctx.lib.dxo_facet_bilinear_diagonal(self.ctx._h, self._h, facet_set._h, t, r, int(bs), C.c_void_p(C_ptr), C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_facet_bilinear_diagonal")
+
+    def facet_bilinear_assemble(self, trial: str, bs: int, C_ptr: int, facet_set: "FacetSet", pattern: "CsrPattern", values=None, bcs=None,
+                                diagonal: float = 1.0, test: str = "value") -> "DeviceCSR":
+        """The operator of facet_bilinear_apply ASSEMBLED on `pattern` (dxo_facet_bilinear_assemble): values += K, always accumulated.
+        `values` and `bcs` as in bilinear_assemble: with values=A.values the boundary term is added to a cell matrix, and the Dirichlet
+        pass (dxo_csr_dirichlet) runs after it — so assemble the cell form without bcs and pass them here."""
+        import torch
+
+        t, r = self._facet_bilinear_kinds("facet_bilinear_assemble", test, trial, bs)
+        if values is None:
+            values = torch.zeros(pattern.nnz, dtype=torch.float64, device=torch.device("cuda", self.ctx.device))
+        if not (values.dtype == torch.float64 and values.is_cuda and values.is_contiguous() and values.numel() == pattern.nnz):
+            raise ValueError(f"facet_bilinear_assemble: values must be a contiguous float64 CUDA tensor of {pattern.nnz} entries")
+        rc = self.ctx.lib.dxo_facet_bilinear_assemble(self.ctx._h, self._h, facet_set._h, pattern._h, t, r, int(bs), C.c_void_p(C_ptr),
+                                                      C.c_void_p(values.data_ptr()))
+        self.ctx.check(rc, "dxo_facet_bilinear_assemble")
+        if bcs is not None:
+            if not (bcs.dtype == torch.int32 and bcs.is_cuda and bcs.is_contiguous()):
+                raise ValueError("facet_bilinear_assemble: bcs must be a contiguous int32 CUDA tensor")
+            rc = self.ctx.lib.dxo_csr_dirichlet(self.ctx._h, pattern._h, C.c_void_p(bcs.data_ptr()), int(bcs.numel()), float(diagonal),
+                                                C.c_void_p(values.data_ptr()))
+            self.ctx.check(rc, "dxo_csr_dirichlet")
+        return DeviceCSR(pattern, values)
 
     def tangent_apply_vm(self, prm, sigma_ptr: int, dp_ptr: int, v_ptr: int, out_ptr: int) -> None:
         """out += K v with the von Mises consistent tangent formed per point from the operator's returned (sigma, dp) — no C_tang

@@ -923,6 +923,34 @@ int dxo_eval_facet_geometry(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_set* s
 int dxo_facet_adjoint(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_set* set, int kind, int bs, const double* S, double* out);
 int dxo_facet_pressure(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_set* set, const double* p, double scale, double* out);
 
+/* ---- bilinear forms on boundary facets: the Jacobian of a boundary term g(operand(u)) . v ds --------------------------
+ * The derivative of a state-dependent boundary load with respect to u, int (dg/d operand . operand(u_hat)) . v ds (a convective or
+ * radiative flux, an elastic foundation, a traction that depends on u or grad u):
+ *   K[(a,i),(b,j)] = sum_e sum_q dS_eq phi_a(x_eq) sum_r C_eq[i][r] (B_trial,eq)_r,(b,j)
+ * over the set's entities, dS and the facet tables exactly those of dxo_facet_adjoint. All pointers are DEVICE pointers, 8-byte aligned
+ * (DXO_E_ALIGN otherwise). C [n][nq_facet][bs][D_trial] row-major, D_trial = dxo_operand_value_size(gdim, bs, trial_kind).
+ * test_kind must be DXO_OPERAND_VALUE (any other: DXO_E_OPTION). trial_kind: the linear kinds of dxo_facet_adjoint with its block sizes
+ * (VALUE, GRAD, VALUE_GRAD with bs = 1 or gdim; EPS_MANDEL, DIV, DEFGRAD — taken as its linearisation, grad — with bs = gdim);
+ * nonlinear kinds DXO_E_OPTION, a block size that does not fit DXO_E_DIM.
+ *   dxo_facet_bilinear_apply    : out += K v
+ *   dxo_facet_bilinear_diagonal : out += diag K
+ *   dxo_facet_bilinear_assemble : values += K on a pattern of dxo_csr_create(mesh, bs) (of another mesh or block size: DXO_E_DIM)
+ * Like the other facet calls they ALWAYS accumulate ("consumer_overwrite" and "adjoint_atomics" do not apply: the facet term goes on
+ * top of a cell term), use no atomics and are bit-reproducible: apply and diagonal write element vectors to the set's scratch and
+ * finish with the node sums of dxo_facet_adjoint; assemble writes the element matrices of a chunk of entities (option
+ * "assemble_chunk_cells" entities, 0 = as many as fit 1 GiB) to a grow-only scratch of the set that the first call allocates, then one
+ * lane per (touched node, component) adds that row's entries in ascending entity order: every value is the same chain of additions
+ * whatever the chunk size. After that first call they allocate and synchronise nothing (capture-safe). An empty set: DXO_OK, nothing
+ * touched. dxo_facet_bilinear_assemble parks nq_facet blocks of bs * bs * (1 | gdim | 1 + gdim) doubles (rounded up to odd) per entity
+ * in LDS: a facet rule so large that ONE entity exceeds 64 KiB (nq_facet >= 222 with value_grad, bs = gdim = 3) is refused with
+ * DXO_E_SIZE. The other checks and codes are those of dxo_facet_adjoint. */
+int dxo_facet_bilinear_apply(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_set* set, int test_kind, int trial_kind, int bs, const double* C,
+                             const double* v, double* out);
+int dxo_facet_bilinear_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_set* set, int test_kind, int trial_kind, int bs,
+                                const double* C, double* out);
+int dxo_facet_bilinear_assemble(dxo_ctx* ctx, dxo_mesh* mesh, dxo_facet_set* set, dxo_csr* csr, int test_kind, int trial_kind, int bs,
+                                const double* C, double* values);
+
 /* ---- coefficient assigners on the device, DEVICE memory only --------------------------
  * One scatter for the reference's three dofmap assigners (src/dolfinx_external_operator/external_operator.py):
  * _assign_non_mixed :286-287, _assign_mixed_2d :292-311, _assign_mixed_3d :313-335. For cell c, point p < n_pts,
