@@ -16,9 +16,9 @@
 //     reference derivatives (z = (phi, grad phi); the zero coefficients are compile-time and never formed), parked in LDS.
 //     Phase 2, thread = (cell, a, b): the BS x BS block A[(a,i),(b,j)] = sum_q z_a,q^T M_q[i][j] z_b,q from the element
 //     tables in LDS, written to the chunk's scratch ae[cell][a*BS + i][b*BS + j].
-//   pass 2, assemble_rows: one thread per row adds the row's entries of the chunk's cells in ascending cell order (the fixed
-//     order of the incidences). Every value is therefore the same chain of additions whatever the chunk size (option
-//     "assemble_chunk_cells"): chunk k + 1 continues the chains chunk k left in `values`.
+//   pass 2, assemble_rows<.., CellRows> (csr.h, the row pass facet_form.hip shares): one thread per row adds the row's entries of
+//     the chunk's cells in ascending cell order (the fixed order of the incidences). Every value is therefore the same chain of
+//     additions whatever the chunk size (option "assemble_chunk_cells"): chunk k + 1 continues the chains chunk k left in `values`.
 // Option "adjoint_atomics" = 1: pass 1 adds its blocks straight into `values` with fp64 atomics (one launch, no scratch,
 // reproducible to rounding only). Option "consumer_overwrite" = 1 clears `values` first (SET instead of accumulate).
 #include "csr.h"
@@ -40,8 +40,6 @@
 #endif
 
 namespace {
-
-constexpr int64_t AS_AUTO_SCRATCH_BYTES = DXO_AS_AUTO_SCRATCH_BYTES;   // option assemble_chunk_cells = 0 (csr.h)
 
 template <int G, int BS, int TEST, int TRIAL>
 struct AsShape {
@@ -204,37 +202,6 @@ __global__ __launch_bounds__(DXO_AS_BLOCK) void assemble_elem(OperandDev m, cons
     }
 }
 
-// pass 2: one thread per row (node n, component i) adds the entries of the chunk's cells [c_begin, c_end) in ascending cell order
-template <int BS>
-__global__ __launch_bounds__(DXO_AS_BLOCK) void assemble_rows(int64_t n_nodes, int nd, const int64_t* __restrict__ inc_ptr,
-                                                              const uint32_t* __restrict__ inc, const int64_t* __restrict__ row_ptr,
-                                                              const uint16_t* __restrict__ pos, const double* __restrict__ ae,
-                                                              int64_t c_begin, int64_t c_end, double* __restrict__ values) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int ndb = nd * BS;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_nodes * BS; r += stride) {
-        const int64_t n = r / BS;
-        const int i = (int)(r - n * BS);
-        const int64_t e0 = inc_ptr[n], e1 = inc_ptr[n + 1];
-        if (e0 == e1 || (int64_t)(inc[e1 - 1] / nd) < c_begin || (int64_t)(inc[e0] / nd) >= c_end) continue;
-        double* row = values + row_ptr[r];
-        for (int64_t e = e0; e < e1; ++e) {
-            const uint32_t ent = inc[e];
-            const int64_t cell = ent / nd;
-            if (cell < c_begin) continue;
-            if (cell >= c_end) break;
-            const int a = (int)(ent - cell * nd);
-            const double* src = ae + ((cell - c_begin) * ndb + (int64_t)a * BS + i) * ndb;
-            const uint16_t* pp = pos + (int64_t)ent * nd;
-            for (int b = 0; b < nd; ++b) {
-                double* dst = row + (int64_t)pp[b] * BS;
-#pragma unroll
-                for (int j = 0; j < BS; ++j) dst[j] += src[b * BS + j];
-            }
-        }
-    }
-}
-
 __global__ __launch_bounds__(DXO_AS_BLOCK) void dirichlet_mark(const int32_t* __restrict__ dofs, int64_t n_dofs, int64_t n_rows,
                                                                uint8_t* __restrict__ mask) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -374,33 +341,31 @@ int assemble_impl(dxo_ctx* ctx, dxo_mesh* mesh, dxo_csr* csr, int test, int tria
     DXO_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t nc = mesh->num_cells;
     const size_t cell_bytes = (size_t)nd * bs * nd * bs * sizeof(double);
-    int64_t chunk = ctx->assemble_chunk_cells > 0 ? ctx->assemble_chunk_cells : std::max<int64_t>(1, AS_AUTO_SCRATCH_BYTES / (int64_t)cell_bytes);
-    if (chunk > nc) chunk = nc;
-    if (chunk < 1) chunk = 1;
-    const bool atomics = ctx->adjoint_atomics != 0;
-    if (!atomics && nc > 0) {      // the first call (or a larger chunk) allocates the scratch
-        rc = device_buf(ctx, (void**)&csr->d_ae, &csr->ae_cap, (size_t)chunk * cell_bytes);
+    auto begin = [&]() -> int {
+        const int rc = dxo_device_begin(ctx, s);
         if (rc != DXO_OK) return rc;
-    }
-    rc = dxo_device_begin(ctx, s);
-    if (rc != DXO_OK) return rc;
-    if (ctx->consumer_overwrite) DXO_HIP(ctx, hipMemsetAsync(values, 0, (size_t)csr->nnz * sizeof(double), s));
-    if (nc > 0) {
-        if (atomics) {
-            ops.launch(mesh, csr, cpb, grid_blocks(ctx, (nc + cpb - 1) / cpb, 1), shm, C, 0, nc, nullptr, values, s);
-        } else {
-            const int rblocks = grid_blocks(ctx, csr->n_rows, DXO_AS_BLOCK);
-            for (int64_t c0 = 0; c0 < nc; c0 += chunk) {
-                const int64_t c1 = std::min(nc, c0 + chunk);
+        if (ctx->consumer_overwrite) DXO_HIP(ctx, hipMemsetAsync(values, 0, (size_t)csr->nnz * sizeof(double), s));
+        return DXO_OK;
+    };
+    if (ctx->adjoint_atomics || nc == 0) {
+        rc = begin();
+        if (rc == DXO_OK && nc > 0) ops.launch(mesh, csr, cpb, grid_blocks(ctx, (nc + cpb - 1) / cpb, 1), shm, C, 0, nc, nullptr, values, s);
+    } else {
+        const int rblocks = grid_blocks(ctx, csr->n_rows, DXO_AS_BLOCK);
+        const CellRows rows{csr->n_nodes, csr->d_inc_ptr, csr->d_inc};
+        rc = assemble_two_pass(
+            ctx, nc, cell_bytes, &csr->d_ae, &csr->ae_cap, begin,
+            [&](int64_t c0, int64_t c1) {
                 ops.launch(mesh, csr, cpb, grid_blocks(ctx, (c1 - c0 + cpb - 1) / cpb, 1), shm, C, c0, c1, csr->d_ae, values, s);
+            },
+            [&](int64_t c0, int64_t c1) {
                 with_node_bs(bs, [&](auto BS) {
-                    hipLaunchKernelGGL(assemble_rows<BS>, dim3(rblocks), dim3(DXO_AS_BLOCK), 0, s, csr->n_nodes, nd, csr->d_inc_ptr, csr->d_inc,
-                                       csr->d_row_ptr, csr->d_pos, csr->d_ae, c0, c1, values);
+                    hipLaunchKernelGGL((assemble_rows<BS, DXO_AS_BLOCK, CellRows>), dim3(rblocks), dim3(DXO_AS_BLOCK), 0, s, rows, nd, csr->d_row_ptr,
+                                       csr->d_pos, csr->d_ae, c0, c1, values);
                 });
-            }
-        }
+            });
     }
-    return dxo_device_end(ctx, s);
+    return rc != DXO_OK ? rc : dxo_device_end(ctx, s);
 }
 
 }  // namespace

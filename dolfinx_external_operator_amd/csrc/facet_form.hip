@@ -6,9 +6,10 @@
 // rebuilds it), J_f = J J_ref_f, dS = w_q sqrt(det(J_f^T J_f)), n = J^-T n_ref / |J^-T n_ref|. J^-T maps a covector, so n is outward
 // for either sign of det J (J v points out of the cell when v points out of the reference cell, and n . J v = n_ref . v / |.|).
 //
-// Boundary work is O(N^((d-1)/d)): this is not a bandwidth kernel. Every call is two launches:
-//   facet_element : a workgroup takes floor(256 / nq) entities. Phase 1, lane = (entity, point): geometry and the point's dual data
-//                   (vh[BS], T[BS][G] = dS * the dual tensor pulled back to reference gradients; for the pressure vh = dS p n) into LDS.
+// Boundary work is O(N^((d-1)/d)): this is not a bandwidth kernel. Every call that ends in a dof vector is two launches:
+//   facet_element<.., MODE>: a workgroup takes floor(256 / nq) entities. Phase 1, lane = (entity, point): geometry and what the mode parks
+//                   in LDS (FE_LOAD: vh[BS], T[BS][G] = dS * the dual tensor pulled back to reference gradients; FE_PRESSURE: dS p n;
+//                   FE_APPLY and FE_DIAG: see the bilinear forms below).
 //                   Phase 2, lane = (entity, local dof): the fixed-order sum over the entity's points into fe[entity][a][i].
 //   facet_node_sum: lane = touched node, adds the node's entries of fe in ascending entity order (the set's transposed incidence).
 // No atomics: the result is bit-reproducible. The calls always accumulate into out.
@@ -16,6 +17,7 @@
 #include "csr.h"
 #include "dxo_common.h"
 #include "facet_tabs.h"
+#include "operand_coef.h"
 
 #include <algorithm>
 
@@ -34,8 +36,6 @@ struct dxo_facet_set {
 };
 
 namespace {
-
-constexpr int FACET_PRESSURE = -1;   // facet_element's "kind" for the pressure load
 
 // J^-1 (K), the outward unit normal and the point measure at point q of facet f of `cell`
 template <int G>
@@ -112,13 +112,54 @@ __global__ __launch_bounds__(DXO_BLOCK) void facet_geometry(OperandDev m, FacetT
     }
 }
 
-// element vectors of the entities: fe[e][a][i] = sum_q (vh_q[i] phi_a + sum_k T_q[i][k] dphi_a,k) at the entity's facet points.
-// KIND: a linear operand kind (S [n][nq][D]) or FACET_PRESSURE (p [n][nq] or NULL, vh = scale p n dS, no gradient part).
+// what facet_element forms: the load of a linear operand kind (A = S [n][nq][D]), the pressure load (A = p [n][nq] or NULL), K v or diag K
+// of a bilinear form (A = C [n][nq][BS][D])
+enum FacetMode { FE_LOAD, FE_PRESSURE, FE_APPLY, FE_DIAG };
+
+// slots per (i, j) of a bilinear form's dual data: the value slot where the kind has one, G reference-gradient slots where it has a gradient
+template <int G, int KIND>
+constexpr int facet_nz() { return (op_has_value<KIND>() ? 1 : 0) + (op_has_grad<KIND>() ? G : 0); }
+
+// doubles a point parks: a load (vh[BS], T[BS][G]) or vh alone, the diagonal its BS slot groups, the pressure and apply BS values
+template <int G, int BS, int KIND, FacetMode MODE>
+constexpr int facet_parked() { return MODE == FE_DIAG ? BS * facet_nz<G, KIND>() : (MODE == FE_LOAD && op_has_grad<KIND>()) ? BS * (1 + G) : BS; }
+
+// the dual data of an operand value s[D] at a point: vh = dS * value part, T = dS * gradient part pulled back to reference gradients
 template <int G, int BS, int KIND>
+__device__ __forceinline__ void facet_dual(const double* __restrict__ sp, const double (&K)[G][G], double ds, double (&vh)[BS],
+                                           double (&T)[BS][G]) {
+    constexpr int D = OperandShape<G, BS, KIND>::D;
+    double s[D], gh[BS][G];
+#pragma unroll
+    for (int k = 0; k < D; ++k) s[k] = sp[k];
+    dual_tensor<G, BS, KIND>(s, vh, gh);
+#pragma unroll
+    for (int i = 0; i < BS; ++i) vh[i] *= ds;
+    pull_back<G, BS>(gh, K, ds, T);
+}
+
+// the slot vector (phi, dphi[:]) of a dof, row = (f * nqf + q) * nd + dof of the facet tables
+template <int G, int KIND>
+__device__ __forceinline__ void facet_dof_slots(const FacetTabs<G>& t, size_t row, double (&z)[facet_nz<G, KIND>()]) {
+    int n = 0;
+    if constexpr (op_has_value<KIND>()) z[n++] = t.phi[row];
+    if constexpr (op_has_grad<KIND>()) {
+#pragma unroll
+        for (int k = 0; k < G; ++k) z[n + k] = t.dphi[row * G + k];
+    }
+}
+
+// element vectors of the entities into fe[e][a][i], summed over the entity's facet points in a fixed order:
+//   FE_LOAD      sum_q (vh_q[i] phi_a + sum_k T_q[i][k] dphi_a,k), (vh, T) the dual data of S_q
+//   FE_PRESSURE  sum_q scale dS p_q n_i phi_a
+//   FE_APPLY     sum_q dS (C_q w_q)[i] phi_a, w_q the trial operand of v at the point
+//   FE_DIAG      sum_q phi_a (vh_i[i] phi_a + sum_k T_i[i][k] dphi_a,k), (vh_i, T_i) the dual data of row i of C_q
+template <int G, int BS, int KIND, FacetMode MODE>
 __global__ __launch_bounds__(DXO_BLOCK) void facet_element(OperandDev m, FacetTabs<G> t, const int32_t* __restrict__ ents, int64_t n,
-                                                           const double* __restrict__ S, double scale, double* __restrict__ fe) {
-    constexpr bool GRAD_PART = KIND != FACET_PRESSURE && KIND != DXO_OPERAND_VALUE;
-    constexpr int PW = GRAD_PART ? BS * (1 + G) : BS;    // doubles parked per point
+                                                           const double* __restrict__ A, const double* __restrict__ v, double scale,
+                                                           double* __restrict__ fe) {
+    constexpr int NZ = facet_nz<G, KIND>(), PW = facet_parked<G, BS, KIND, MODE>();
+    constexpr bool GRAD_SUM = PW == BS * (1 + G);        // a load with a gradient part
     extern __shared__ double lds[];
     const int nqf = t.nqf, nd = t.nd;
     const int epb = DXO_BLOCK / nqf;                      // entities per workgroup and round
@@ -127,32 +168,93 @@ __global__ __launch_bounds__(DXO_BLOCK) void facet_element(OperandDev m, FacetTa
         if ((int)threadIdx.x < ne * nqf) {
             const int le = threadIdx.x / nqf, q = threadIdx.x - le * nqf;
             const int64_t e = e0 + le;
+            const int64_t cell = ents[2 * e];
+            const int f = ents[2 * e + 1];
             double K[G][G], nrm[G], ds;
-            facet_point_geometry<G>(m, t, ents[2 * e], ents[2 * e + 1], q, K, nrm, ds);
+            facet_point_geometry<G>(m, t, cell, f, q, K, nrm, ds);
             double* P = lds + threadIdx.x * PW;
-            if constexpr (KIND == FACET_PRESSURE) {
-                const double pv = scale * ds * (S ? S[e * nqf + q] : 1.0);
+            if constexpr (MODE == FE_PRESSURE) {
+                const double pv = scale * ds * (A ? A[e * nqf + q] : 1.0);
 #pragma unroll
                 for (int i = 0; i < G; ++i) P[i] = pv * nrm[i];
             } else {
                 constexpr int D = OperandShape<G, BS, KIND>::D;
-                double s[D], vh[BS], gh[BS][G];
+                const double* Ap = A + (e * nqf + q) * (int64_t)((MODE == FE_LOAD ? 1 : BS) * D);
+                if constexpr (MODE == FE_LOAD) {
+                    double s[D], vh[BS], gh[BS][G];
 #pragma unroll
-                for (int k = 0; k < D; ++k) s[k] = S[(e * nqf + q) * D + k];
-                dual_tensor<G, BS, KIND>(s, vh, gh);
+                    for (int k = 0; k < D; ++k) s[k] = Ap[k];
+                    dual_tensor<G, BS, KIND>(s, vh, gh);
 #pragma unroll
-                for (int i = 0; i < BS; ++i) P[i] = ds * vh[i];
-                if constexpr (GRAD_PART) {
-                    // pulled back to reference gradients: T[i][k] = dS sum_j gh[i][j] K[k][j]
+                    for (int i = 0; i < BS; ++i) P[i] = ds * vh[i];
+                    if constexpr (GRAD_SUM) {
+                        double T[BS][G];
+                        pull_back<G, BS>(gh, K, ds, T);
+#pragma unroll
+                        for (int i = 0; i < BS; ++i)
+#pragma unroll
+                            for (int k = 0; k < G; ++k) P[BS + i * G + k] = T[i][k];
+                    }
+                } else if constexpr (MODE == FE_DIAG) {
+#pragma unroll
+                    for (int i = 0; i < BS; ++i) {
+                        double vh[BS], T[BS][G];
+                        facet_dual<G, BS, KIND>(Ap + i * D, K, ds, vh, T);
+                        int z = 0;
+                        if constexpr (op_has_value<KIND>()) P[i * NZ + z++] = vh[i];
+                        if constexpr (op_has_grad<KIND>()) {
+#pragma unroll
+                            for (int k = 0; k < G; ++k) P[i * NZ + z + k] = T[i][k];
+                        }
+                    }
+                } else {
+                    // the trial operand of v at the point, as operand_eval_facets forms it
+                    const size_t row = ((size_t)f * nqf + q) * nd;
+                    double val[BS], gref[BS][G];
+#pragma unroll
+                    for (int i = 0; i < BS; ++i) {
+                        val[i] = 0.0;
+#pragma unroll
+                        for (int k = 0; k < G; ++k) gref[i][k] = 0.0;
+                    }
+                    for (int a = 0; a < nd; ++a) {
+                        const int64_t node = m.dofmap[cell * nd + a];
+                        double va[BS];
+#pragma unroll
+                        for (int i = 0; i < BS; ++i) va[i] = v[node * BS + i];
+                        if constexpr (op_has_value<KIND>()) {
+                            const double ph = t.phi[row + a];
+#pragma unroll
+                            for (int i = 0; i < BS; ++i) val[i] += va[i] * ph;
+                        }
+                        if constexpr (op_has_grad<KIND>()) {
+#pragma unroll
+                            for (int k = 0; k < G; ++k) {
+                                const double dk = t.dphi[(row + a) * G + k];
+#pragma unroll
+                                for (int i = 0; i < BS; ++i) gref[i][k] += va[i] * dk;
+                            }
+                        }
+                    }
+                    double g[BS][G];
 #pragma unroll
                     for (int i = 0; i < BS; ++i)
 #pragma unroll
-                        for (int k = 0; k < G; ++k) {
-                            double v = 0.0;
+                        for (int j = 0; j < G; ++j) {
+                            double s = 0.0;
 #pragma unroll
-                            for (int j = 0; j < G; ++j) v += gh[i][j] * K[k][j];
-                            P[BS + i * G + k] = ds * v;
+                            for (int k = 0; k < G; ++k) s += gref[i][k] * K[k][j];
+                            g[i][j] = s;
                         }
+                    double o[D];
+                    shape_operand<G, BS, KIND>(val, g, o);
+#pragma unroll
+                    for (int i = 0; i < BS; ++i) {
+                        double w = 0.0;
+#pragma unroll
+                        for (int r = 0; r < D; ++r) w += Ap[i * D + r] * o[r];
+                        P[i] = ds * w;
+                    }
                 }
             }
         }
@@ -168,14 +270,26 @@ __global__ __launch_bounds__(DXO_BLOCK) void facet_element(OperandDev m, FacetTa
                 const double* P = lds + (le * nqf + q) * PW;
                 const size_t row = ((size_t)f * nqf + q) * nd + a;
                 const double ph = t.phi[row];
+                if constexpr (MODE == FE_DIAG) {
+                    double za[NZ];
+                    facet_dof_slots<G, KIND>(t, row, za);
 #pragma unroll
-                for (int i = 0; i < BS; ++i) acc[i] += P[i] * ph;
-                if constexpr (GRAD_PART) {
+                    for (int i = 0; i < BS; ++i) {
+                        double s = 0.0;
 #pragma unroll
-                    for (int k = 0; k < G; ++k) {
-                        const double dk = t.dphi[row * G + k];
+                        for (int z = 0; z < NZ; ++z) s += P[i * NZ + z] * za[z];
+                        acc[i] += ph * s;
+                    }
+                } else {
 #pragma unroll
-                        for (int i = 0; i < BS; ++i) acc[i] += P[BS + i * G + k] * dk;
+                    for (int i = 0; i < BS; ++i) acc[i] += P[i] * ph;
+                    if constexpr (GRAD_SUM) {
+#pragma unroll
+                        for (int k = 0; k < G; ++k) {
+                            const double dk = t.dphi[row * G + k];
+#pragma unroll
+                            for (int i = 0; i < BS; ++i) acc[i] += P[BS + i * G + k] * dk;
+                        }
                     }
                 }
             }
@@ -207,14 +321,14 @@ __global__ __launch_bounds__(DXO_BLOCK) void facet_node_sum(int64_t n_touched, c
     }
 }
 
-template <int G, int BS, int KIND>
-void launch_element(const dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, const double* S, double scale, hipStream_t s) {
-    constexpr int PW = (KIND != FACET_PRESSURE && KIND != DXO_OPERAND_VALUE) ? BS * (1 + G) : BS;
+// the launch of facet_element into the set's fe: epb entities per workgroup and round, their parked points in dynamic LDS
+template <int G, int BS, int KIND, FacetMode MODE>
+void launch_element(const dxo_ctx* ctx, const dxo_mesh* m, const dxo_facet_set* set, const double* A, const double* v, double scale, hipStream_t s) {
     const FacetTabs<G> t = facet_tabs<G>(m);
     const int epb = DXO_BLOCK / t.nqf;
-    const size_t shm = (size_t)epb * t.nqf * PW * sizeof(double);
-    hipLaunchKernelGGL((facet_element<G, BS, KIND>), dim3(capped_grid(ctx, set->n, epb, 8)), dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents,
-                       set->n, S, scale, set->d_fe);
+    const size_t shm = (size_t)epb * t.nqf * facet_parked<G, BS, KIND, MODE>() * sizeof(double);
+    hipLaunchKernelGGL((facet_element<G, BS, KIND, MODE>), dim3(capped_grid(ctx, set->n, epb, 8)), dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents,
+                       set->n, A, v, scale, set->d_fe);
 }
 
 void launch_node_sum(const dxo_ctx* ctx, const dxo_facet_set* set, int bs, double* out, hipStream_t s) {
@@ -274,15 +388,9 @@ extern "C" int dxo_mesh_set_facet_geometry(dxo_ctx* ctx, dxo_mesh* m, int n_loca
     if (n_local_facets != m->n_local_facets || nq != m->nq_facet)
         return dxo_fail(ctx, DXO_E_DIM, "dxo_mesh_set_facet_geometry: n_local_facets / nq differ from the facet tables'");
     const size_t G = (size_t)m->gdim, nf = (size_t)n_local_facets, n_w = (size_t)nq, n_n = nf * G, n_j = nf * G * (G - 1);
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    DXO_HIP(ctx, hipDeviceSynchronize());
-    if (m->d_facet_geom) DXO_HIP(ctx, hipFree(m->d_facet_geom));
-    m->d_facet_geom = nullptr;
     m->nf_geom = m->nq_geom = 0;
-    DXO_HIP(ctx, hipMalloc((void**)&m->d_facet_geom, (n_w + n_n + n_j) * sizeof(double)));
-    DXO_HIP(ctx, hipMemcpy(m->d_facet_geom, weights, n_w * sizeof(double), hipMemcpyHostToDevice));
-    DXO_HIP(ctx, hipMemcpy(m->d_facet_geom + n_w, ref_normals, n_n * sizeof(double), hipMemcpyHostToDevice));
-    DXO_HIP(ctx, hipMemcpy(m->d_facet_geom + n_w + n_n, ref_jacobians, n_j * sizeof(double), hipMemcpyHostToDevice));
+    const int rc = upload_slab(ctx, &m->d_facet_geom, {{weights, n_w}, {ref_normals, n_n}, {ref_jacobians, n_j}});
+    if (rc != DXO_OK) return rc;
     m->nf_geom = n_local_facets;
     m->nq_geom = nq;
     return DXO_OK;
@@ -356,7 +464,7 @@ extern "C" int dxo_facet_adjoint(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set*
     rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
     rc = with_form_shape(m->gdim, bs, [&](auto G, auto BS) {
-        return with_operand_kind<G, BS, true>(kind, [&](auto KIND) { launch_element<G, BS, KIND>(ctx, m, set, S, 1.0, s); });
+        return with_operand_kind<G, BS, true>(kind, [&](auto KIND) { launch_element<G, BS, KIND, FE_LOAD>(ctx, m, set, S, nullptr, 1.0, s); });
     });
     if (rc != DXO_OK) return dxo_fail(ctx, rc, "dxo_facet_adjoint: unsupported (gdim, bs, kind)");
     launch_node_sum(ctx, set, bs, out, s);
@@ -374,7 +482,7 @@ extern "C" int dxo_facet_pressure(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set
     hipStream_t s = dxo_launch_stream(ctx);
     rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
-    with_gdim(m->gdim, [&](auto G) { launch_element<G, G, FACET_PRESSURE>(ctx, m, set, p, scale, s); });
+    with_gdim(m->gdim, [&](auto G) { launch_element<G, G, DXO_OPERAND_VALUE, FE_PRESSURE>(ctx, m, set, p, nullptr, scale, s); });
     launch_node_sum(ctx, set, m->gdim, out, s);
     return dxo_device_end(ctx, s);
 }
@@ -384,172 +492,28 @@ extern "C" int dxo_facet_pressure(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set
 // with dS and the tables those of dxo_facet_adjoint. The test side is the value; row i of the point's block is an operand value of the
 // trial kind, so its dual data (vh[BS], T[BS][G] = dS * dual_tensor of C[i][:] pulled back to reference gradients) is the row of K:
 //   K[(a,i),(b,j)] = sum_q phi_a (vh_i[j] phi_b + sum_k T_i[j][k] dphi_b,k).
-//   apply    facet_bilinear_element<.., false>: lane = (entity, point) forms the trial operand of v and parks dS C w; lane = (entity,
+//   apply    facet_element<.., FE_APPLY>: lane = (entity, point) forms the trial operand of v and parks dS C w; lane = (entity,
 //            local dof) sums over the points into the set's fe; facet_node_sum finishes (two launches, as the loads).
-//   diagonal facet_bilinear_element<.., true>: parks (vh_i[i], T_i[i][:]), then phi_a (vh_i[i] phi_a + sum_k T_i[i][k] dphi_a,k).
+//   diagonal facet_element<.., FE_DIAG>: parks (vh_i[i], T_i[i][:]), then phi_a (vh_i[i] phi_a + sum_k T_i[i][k] dphi_a,k).
 //   assemble two passes per chunk of entities, as assemble.hip: facet_assemble_elem parks the point's BS x BS x NZ block and lane =
-//            (entity, a, b) writes ae[e][a*BS+i][b*BS+j]; facet_assemble_rows, lane = (touched node, component), walks the node's
+//            (entity, a, b) writes ae[e][a*BS+i][b*BS+j]; assemble_rows<.., FacetRows> (csr.h), lane = (touched node, component), walks the node's
 //            incidences in ascending entity order and adds into values through row_ptr / pos. Every value is the same chain of
 //            additions whatever the chunk size.
 // No atomics; the calls always accumulate.
 namespace {
 
-template <int KIND>
-constexpr bool fb_value() { return KIND == DXO_OPERAND_VALUE || KIND == DXO_OPERAND_VALUE_GRAD; }
-template <int KIND>
-constexpr bool fb_grad() { return KIND != DXO_OPERAND_VALUE; }
-// parked doubles per (i, j): the value slot where the kind has one, G reference-gradient slots where it has a gradient
-template <int G, int KIND>
-constexpr int fb_nz() { return (fb_value<KIND>() ? 1 : 0) + (fb_grad<KIND>() ? G : 0); }
-
 constexpr int FB_LDS_DOUBLES = 64 * 1024 / 8;
-
-// the dual data of one row of the point's block: vh = dS * value part, T = dS * gradient part pulled back to reference gradients
-template <int G, int BS, int KIND>
-__device__ __forceinline__ void fb_row_dual(const double* __restrict__ Crow, const double (&K)[G][G], double ds, double (&vh)[BS],
-                                            double (&T)[BS][G]) {
-    constexpr int D = OperandShape<G, BS, KIND>::D;
-    double s[D], gh[BS][G];
-#pragma unroll
-    for (int k = 0; k < D; ++k) s[k] = Crow[k];
-    dual_tensor<G, BS, KIND>(s, vh, gh);
-#pragma unroll
-    for (int i = 0; i < BS; ++i) vh[i] *= ds;
-    pull_back<G, BS>(gh, K, ds, T);
-}
-
-// element vectors of K v (DIAG = false) or of diag K (DIAG = true) into fe[e][a][i]
-template <int G, int BS, int KIND, bool DIAG>
-__global__ __launch_bounds__(DXO_BLOCK) void facet_bilinear_element(OperandDev m, FacetTabs<G> t, const int32_t* __restrict__ ents,
-                                                                    int64_t n, const double* __restrict__ C,
-                                                                    const double* __restrict__ v, double* __restrict__ fe) {
-    constexpr int D = OperandShape<G, BS, KIND>::D, NZ = fb_nz<G, KIND>();
-    constexpr int PW = DIAG ? BS * NZ : BS;               // doubles parked per point
-    extern __shared__ double lds[];
-    const int nqf = t.nqf, nd = t.nd;
-    const int epb = DXO_BLOCK / nqf;                      // entities per workgroup and round
-    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < n; e0 += (int64_t)gridDim.x * epb) {
-        const int ne = (int)(n - e0 < epb ? n - e0 : epb);
-        if ((int)threadIdx.x < ne * nqf) {
-            const int le = threadIdx.x / nqf, q = threadIdx.x - le * nqf;
-            const int64_t e = e0 + le;
-            const int64_t cell = ents[2 * e];
-            const int f = ents[2 * e + 1];
-            double K[G][G], nrm[G], ds;
-            facet_point_geometry<G>(m, t, cell, f, q, K, nrm, ds);
-            const double* Cp = C + (e * nqf + q) * (int64_t)(BS * D);
-            double* P = lds + threadIdx.x * PW;
-            if constexpr (DIAG) {
-#pragma unroll
-                for (int i = 0; i < BS; ++i) {
-                    double vh[BS], T[BS][G];
-                    fb_row_dual<G, BS, KIND>(Cp + i * D, K, ds, vh, T);
-                    int z = 0;
-                    if constexpr (fb_value<KIND>()) P[i * NZ + z++] = vh[i];
-                    if constexpr (fb_grad<KIND>()) {
-#pragma unroll
-                        for (int k = 0; k < G; ++k) P[i * NZ + z + k] = T[i][k];
-                    }
-                }
-            } else {
-                // the trial operand of v at the point, as operand_eval_facets forms it
-                const size_t row = ((size_t)f * nqf + q) * nd;
-                double val[BS], gref[BS][G];
-#pragma unroll
-                for (int i = 0; i < BS; ++i) {
-                    val[i] = 0.0;
-#pragma unroll
-                    for (int k = 0; k < G; ++k) gref[i][k] = 0.0;
-                }
-                for (int a = 0; a < nd; ++a) {
-                    const int64_t node = m.dofmap[cell * nd + a];
-                    double va[BS];
-#pragma unroll
-                    for (int i = 0; i < BS; ++i) va[i] = v[node * BS + i];
-                    if constexpr (fb_value<KIND>()) {
-                        const double ph = t.phi[row + a];
-#pragma unroll
-                        for (int i = 0; i < BS; ++i) val[i] += va[i] * ph;
-                    }
-                    if constexpr (fb_grad<KIND>()) {
-#pragma unroll
-                        for (int k = 0; k < G; ++k) {
-                            const double dk = t.dphi[(row + a) * G + k];
-#pragma unroll
-                            for (int i = 0; i < BS; ++i) gref[i][k] += va[i] * dk;
-                        }
-                    }
-                }
-                double g[BS][G];
-#pragma unroll
-                for (int i = 0; i < BS; ++i)
-#pragma unroll
-                    for (int j = 0; j < G; ++j) {
-                        double s = 0.0;
-#pragma unroll
-                        for (int k = 0; k < G; ++k) s += gref[i][k] * K[k][j];
-                        g[i][j] = s;
-                    }
-                double o[D];
-                shape_operand<G, BS, KIND>(val, g, o);
-#pragma unroll
-                for (int i = 0; i < BS; ++i) {
-                    double w = 0.0;
-#pragma unroll
-                    for (int r = 0; r < D; ++r) w += Cp[i * D + r] * o[r];
-                    P[i] = ds * w;
-                }
-            }
-        }
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < ne * nd; idx += blockDim.x) {
-            const int le = idx / nd, a = idx - le * nd;
-            const int64_t e = e0 + le;
-            const int f = ents[2 * e + 1];
-            double acc[BS];
-#pragma unroll
-            for (int i = 0; i < BS; ++i) acc[i] = 0.0;
-            for (int q = 0; q < nqf; ++q) {
-                const double* P = lds + (le * nqf + q) * PW;
-                const size_t row = ((size_t)f * nqf + q) * nd + a;
-                const double ph = t.phi[row];
-                if constexpr (!DIAG) {
-#pragma unroll
-                    for (int i = 0; i < BS; ++i) acc[i] += P[i] * ph;
-                } else {
-                    double za[NZ];
-                    int z = 0;
-                    if constexpr (fb_value<KIND>()) za[z++] = ph;
-                    if constexpr (fb_grad<KIND>()) {
-#pragma unroll
-                        for (int k = 0; k < G; ++k) za[z + k] = t.dphi[row * G + k];
-                    }
-#pragma unroll
-                    for (int i = 0; i < BS; ++i) {
-                        double s = 0.0;
-#pragma unroll
-                        for (int zz = 0; zz < NZ; ++zz) s += P[i * NZ + zz] * za[zz];
-                        acc[i] += ph * s;
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < BS; ++i) fe[(e * nd + a) * BS + i] = acc[i];
-        }
-        __syncthreads();     // the next round overwrites the parked points
-    }
-}
 
 // parked doubles per point of the assembly: the BS x BS x NZ block, odd stride (bank spread across points)
 template <int G, int BS, int KIND>
-constexpr int fb_block_stride() { return (BS * BS * fb_nz<G, KIND>()) | 1; }
+constexpr int fb_block_stride() { return (BS * BS * facet_nz<G, KIND>()) | 1; }
 
 // pass 1: the element matrices of the entities [e_begin, e_end) into ae[e - e_begin][a*BS + i][b*BS + j]; epb entities per round
 template <int G, int BS, int KIND>
 __global__ __launch_bounds__(DXO_BLOCK) void facet_assemble_elem(OperandDev m, FacetTabs<G> t, const int32_t* __restrict__ ents,
                                                                  int64_t e_begin, int64_t e_end, int epb, const double* __restrict__ C,
                                                                  double* __restrict__ ae) {
-    constexpr int D = OperandShape<G, BS, KIND>::D, NZ = fb_nz<G, KIND>(), PS = fb_block_stride<G, BS, KIND>();
+    constexpr int D = OperandShape<G, BS, KIND>::D, NZ = facet_nz<G, KIND>(), PS = fb_block_stride<G, BS, KIND>();
     extern __shared__ double lds[];
     const int nqf = t.nqf, nd = t.nd, ndb = nd * BS;
     for (int64_t e0 = e_begin + (int64_t)blockIdx.x * epb; e0 < e_end; e0 += (int64_t)gridDim.x * epb) {
@@ -564,13 +528,13 @@ __global__ __launch_bounds__(DXO_BLOCK) void facet_assemble_elem(OperandDev m, F
 #pragma unroll
             for (int i = 0; i < BS; ++i) {
                 double vh[BS], T[BS][G];
-                fb_row_dual<G, BS, KIND>(Cp + i * D, K, ds, vh, T);
+                facet_dual<G, BS, KIND>(Cp + i * D, K, ds, vh, T);
 #pragma unroll
                 for (int j = 0; j < BS; ++j) {
                     double* Pij = P + (i * BS + j) * NZ;
                     int z = 0;
-                    if constexpr (fb_value<KIND>()) Pij[z++] = vh[j];
-                    if constexpr (fb_grad<KIND>()) {
+                    if constexpr (op_has_value<KIND>()) Pij[z++] = vh[j];
+                    if constexpr (op_has_grad<KIND>()) {
 #pragma unroll
                         for (int k = 0; k < G; ++k) Pij[z + k] = T[j][k];
                     }
@@ -592,12 +556,7 @@ __global__ __launch_bounds__(DXO_BLOCK) void facet_assemble_elem(OperandDev m, F
                 const size_t row = ((size_t)f * nqf + q) * nd;
                 const double pa = t.phi[row + a];
                 double zb[NZ];
-                int z = 0;
-                if constexpr (fb_value<KIND>()) zb[z++] = t.phi[row + b];
-                if constexpr (fb_grad<KIND>()) {
-#pragma unroll
-                    for (int k = 0; k < G; ++k) zb[z + k] = t.dphi[(row + b) * G + k];
-                }
+                facet_dof_slots<G, KIND>(t, row + b, zb);
 #pragma unroll
                 for (int i = 0; i < BS; ++i)
 #pragma unroll
@@ -615,38 +574,6 @@ __global__ __launch_bounds__(DXO_BLOCK) void facet_assemble_elem(OperandDev m, F
                 for (int j = 0; j < BS; ++j) dst[(int64_t)i * ndb + j] = acc[i][j];
         }
         __syncthreads();     // the next round overwrites the parked blocks
-    }
-}
-
-// pass 2: one lane per (touched node, component) adds the rows of the chunk's entities [e_begin, e_end) in ascending entity order
-template <int BS>
-__global__ __launch_bounds__(DXO_BLOCK) void facet_assemble_rows(int64_t n_touched, int nd, const int32_t* __restrict__ tnode,
-                                                                 const int64_t* __restrict__ tptr, const uint32_t* __restrict__ tent,
-                                                                 const int32_t* __restrict__ ents, const int64_t* __restrict__ row_ptr,
-                                                                 const uint16_t* __restrict__ pos, const double* __restrict__ ae,
-                                                                 int64_t e_begin, int64_t e_end, double* __restrict__ values) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int ndb = nd * BS;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_touched * BS; r += stride) {
-        const int64_t t = r / BS;
-        const int i = (int)(r - t * BS);
-        const int64_t j0 = tptr[t], j1 = tptr[t + 1];
-        if (j0 == j1 || (int64_t)(tent[j1 - 1] / nd) < e_begin || (int64_t)(tent[j0] / nd) >= e_end) continue;
-        double* row = values + row_ptr[(int64_t)tnode[t] * BS + i];
-        for (int64_t j = j0; j < j1; ++j) {
-            const uint32_t ent = tent[j];
-            const int64_t e = ent / nd;
-            if (e < e_begin) continue;
-            if (e >= e_end) break;
-            const int a = (int)(ent - e * nd);
-            const double* src = ae + ((e - e_begin) * ndb + (int64_t)a * BS + i) * ndb;
-            const uint16_t* pp = pos + ((int64_t)ents[2 * e] * nd + a) * nd;
-            for (int b = 0; b < nd; ++b) {
-                double* dst = row + (int64_t)pp[b] * BS;
-#pragma unroll
-                for (int jj = 0; jj < BS; ++jj) dst[jj] += src[b * BS + jj];
-            }
-        }
     }
 }
 
@@ -695,18 +622,8 @@ int facet_bilinear_vector(dxo_ctx* ctx, dxo_mesh* m, const dxo_facet_set* set, i
     rc = dxo_device_begin(ctx, s);
     if (rc != DXO_OK) return rc;
     with_facet_trial(m->gdim, bs, kind, [&](auto G, auto BS, auto KIND) {
-        const FacetTabs<G> t = facet_tabs<G>(m);
-        const int epb = DXO_BLOCK / t.nqf;
-        const dim3 grid(capped_grid(ctx, set->n, epb, 8));
-        if (diag) {
-            const size_t shm = (size_t)epb * t.nqf * BS * fb_nz<G, KIND>() * sizeof(double);
-            hipLaunchKernelGGL((facet_bilinear_element<G, BS, KIND, true>), grid, dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents, set->n, C, v,
-                               set->d_fe);
-        } else {
-            const size_t shm = (size_t)epb * t.nqf * BS * sizeof(double);
-            hipLaunchKernelGGL((facet_bilinear_element<G, BS, KIND, false>), grid, dim3(DXO_BLOCK), shm, s, m->dev, t, set->d_ents, set->n, C, v,
-                               set->d_fe);
-        }
+        if (diag) launch_element<G, BS, KIND, FE_DIAG>(ctx, m, set, C, v, 0.0, s);
+        else launch_element<G, BS, KIND, FE_APPLY>(ctx, m, set, C, v, 0.0, s);
     });
     launch_node_sum(ctx, set, bs, out, s);
     return dxo_device_end(ctx, s);
@@ -747,25 +664,23 @@ extern "C" int dxo_facet_bilinear_assemble(dxo_ctx* ctx, dxo_mesh* m, dxo_facet_
     if (nqf * ps > FB_LDS_DOUBLES) return fail_who(ctx, DXO_E_SIZE, who, "facet rule too large for the LDS budget");
     const int epb = std::min(DXO_BLOCK / nqf, FB_LDS_DOUBLES / (nqf * ps));      // the parked blocks of a round stay within 64 KiB
     const size_t ent_bytes = (size_t)nd * bs * nd * bs * sizeof(double);
-    int64_t chunk = ctx->assemble_chunk_cells > 0 ? ctx->assemble_chunk_cells : std::max<int64_t>(1, DXO_AS_AUTO_SCRATCH_BYTES / (int64_t)ent_bytes);
-    if (chunk > set->n) chunk = set->n;
     DXO_HIP(ctx, hipSetDevice(ctx->device));
-    rc = device_buf(ctx, (void**)&set->d_ae, &set->ae_cap, (size_t)chunk * ent_bytes);      // the first call (or a larger chunk) allocates
-    if (rc != DXO_OK) return rc;
     hipStream_t s = dxo_launch_stream(ctx);
-    rc = dxo_device_begin(ctx, s);
-    if (rc != DXO_OK) return rc;
     const int rblocks = capped_grid(ctx, set->n_touched * bs, DXO_BLOCK, 8);
-    for (int64_t e0 = 0; e0 < set->n; e0 += chunk) {
-        const int64_t e1 = std::min(set->n, e0 + chunk);
-        with_facet_trial(m->gdim, bs, kind, [&](auto G, auto BS, auto KIND) {
-            hipLaunchKernelGGL((facet_assemble_elem<G, BS, KIND>), dim3(capped_grid(ctx, e1 - e0, epb, 8)), dim3(DXO_BLOCK),
-                               (size_t)epb * nqf * ps * sizeof(double), s, m->dev, facet_tabs<G>(m), set->d_ents, e0, e1, epb, C, set->d_ae);
+    const FacetRows rows{set->n_touched, set->d_tptr, set->d_tent, set->d_tnode, set->d_ents};
+    rc = assemble_two_pass(
+        ctx, set->n, ent_bytes, &set->d_ae, &set->ae_cap, [&] { return dxo_device_begin(ctx, s); },
+        [&](int64_t e0, int64_t e1) {
+            with_facet_trial(m->gdim, bs, kind, [&](auto G, auto BS, auto KIND) {
+                hipLaunchKernelGGL((facet_assemble_elem<G, BS, KIND>), dim3(capped_grid(ctx, e1 - e0, epb, 8)), dim3(DXO_BLOCK),
+                                   (size_t)epb * nqf * ps * sizeof(double), s, m->dev, facet_tabs<G>(m), set->d_ents, e0, e1, epb, C, set->d_ae);
+            });
+        },
+        [&](int64_t e0, int64_t e1) {
+            with_node_bs(bs, [&](auto BS) {
+                hipLaunchKernelGGL((assemble_rows<BS, DXO_BLOCK, FacetRows>), dim3(rblocks), dim3(DXO_BLOCK), 0, s, rows, nd, csr->d_row_ptr,
+                                   csr->d_pos, set->d_ae, e0, e1, values);
+            });
         });
-        with_node_bs(bs, [&](auto BS) {
-            hipLaunchKernelGGL(facet_assemble_rows<BS>, dim3(rblocks), dim3(DXO_BLOCK), 0, s, set->n_touched, nd, set->d_tnode, set->d_tptr,
-                               set->d_tent, set->d_ents, csr->d_row_ptr, csr->d_pos, set->d_ae, e0, e1, values);
-        });
-    }
-    return dxo_device_end(ctx, s);
+    return rc != DXO_OK ? rc : dxo_device_end(ctx, s);
 }

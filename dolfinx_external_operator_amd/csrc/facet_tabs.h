@@ -1,6 +1,6 @@
 // facet_tabs.h — what operand_facet.hip and facet_form.hip share: the facet tables and facet geometry of a mesh as device pointers.
 // The gather of the cell's Jacobian at a facet point stays written out in operand_eval_facets and in facet_point_geometry: behind
-// a shared function, in each of seven formulations tried, facet_element<3, *, VALUE_GRAD> changed its registers, and in six its occupancy
+// a shared function, in each of seven formulations tried, facet_element<3, *, VALUE_GRAD, FE_LOAD> changed its registers, and in six its occupancy
 // (profiles/form_fold_resources.txt).
 #pragma once
 

@@ -1,11 +1,12 @@
 // form_host.h — the host side every form file shares: from a mesh, an operand kind and a block size to a launch. The dispatchers from
 // run-time shapes to template arguments (with_int and the lists built on it), the table of bilinear pairs, the two grid forms, the
-// grow-only device buffers and uploads, the transposed incidence, and the staging of host arrays around a launch. Host code only: no
-// kernel is instantiated by including it.
+// grow-only device buffers and uploads, the chunk rule and chunk loop of the two-pass assemblies, the slab of the facet-table setters, the
+// transposed incidence, and the staging of host arrays around a launch. Host code only: no kernel is instantiated by including it.
 #pragma once
 
 #include "operand_core.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <initializer_list>
 #include <type_traits>
@@ -126,6 +127,51 @@ inline hipError_t device_buf_try(void** p, size_t* cap, size_t bytes) {
 
 inline int device_buf(dxo_ctx* ctx, void** p, size_t* cap, size_t bytes) {
     DXO_HIP(ctx, device_buf_try(p, cap, bytes));
+    return DXO_OK;
+}
+
+// option assemble_chunk_cells = 0: the element matrices of a chunk (of cells, assemble.hip; of facet entities, facet_form.hip) <= 1 GiB
+constexpr int64_t DXO_AS_AUTO_SCRATCH_BYTES = (int64_t)1 << 30;
+
+// entities per chunk of a two-pass assembly of n entities with ent_bytes of element matrix each, within [1, n]
+inline int64_t assemble_chunk(const dxo_ctx* ctx, size_t ent_bytes, int64_t n) {
+    const int64_t chunk = ctx->assemble_chunk_cells > 0 ? ctx->assemble_chunk_cells : DXO_AS_AUTO_SCRATCH_BYTES / (int64_t)ent_bytes;
+    return std::max<int64_t>(1, std::min(chunk, n));
+}
+
+// the two passes of an assembly over n entities, chunk by chunk: the grow-only scratch (*ae, *cap) takes one chunk's element matrices (the
+// first call, or a larger chunk, allocates), begin() opens the launches, then elem(e0, e1) and rows(e0, e1) per chunk [e0, e1)
+template <class Begin, class Elem, class Rows>
+int assemble_two_pass(dxo_ctx* ctx, int64_t n, size_t ent_bytes, double** ae, size_t* cap, Begin&& begin, Elem&& elem, Rows&& rows) {
+    const int64_t chunk = assemble_chunk(ctx, ent_bytes, n);
+    int rc = device_buf(ctx, (void**)ae, cap, (size_t)chunk * ent_bytes);
+    if (rc == DXO_OK) rc = begin();
+    if (rc != DXO_OK) return rc;
+    for (int64_t e0 = 0; e0 < n; e0 += chunk) {
+        const int64_t e1 = std::min(n, e0 + chunk);
+        elem(e0, e1);
+        rows(e0, e1);
+    }
+    return DXO_OK;
+}
+
+// a new device slab holding the host arrays `parts` (pointer, doubles) back to back, in place of *slab. The device is drained first: a
+// queued launch may still read the old slab. The caller keeps the slab's dimensions at zero until this returns DXO_OK
+struct host_part {
+    const double* p;
+    size_t n;
+};
+inline int upload_slab(dxo_ctx* ctx, double** slab, const host_part (&parts)[3]) {
+    DXO_HIP(ctx, hipSetDevice(ctx->device));
+    DXO_HIP(ctx, hipDeviceSynchronize());
+    if (*slab) DXO_HIP(ctx, hipFree(*slab));
+    *slab = nullptr;
+    DXO_HIP(ctx, hipMalloc((void**)slab, (parts[0].n + parts[1].n + parts[2].n) * sizeof(double)));
+    size_t at = 0;
+    for (const host_part& h : parts) {
+        DXO_HIP(ctx, hipMemcpy(*slab + at, h.p, h.n * sizeof(double), hipMemcpyHostToDevice));
+        at += h.n;
+    }
     return DXO_OK;
 }
 

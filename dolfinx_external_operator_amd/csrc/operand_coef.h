@@ -23,5 +23,7 @@ __device__ __forceinline__ constexpr double op_coef(int r, int i, int z) {
 
 template <int KIND>
 constexpr bool op_has_value() { return KIND == DXO_OPERAND_VALUE || KIND == DXO_OPERAND_VALUE_GRAD; }
+template <int KIND>
+constexpr bool op_has_grad() { return KIND != DXO_OPERAND_VALUE; }
 
 }  // namespace

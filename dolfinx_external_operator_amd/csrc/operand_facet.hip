@@ -126,15 +126,9 @@ extern "C" int dxo_mesh_set_facet_tables(dxo_ctx* ctx, dxo_mesh* m, int n_local_
     if (n_local_facets < 1 || n_local_facets > 6 || nq < 1) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mesh_set_facet_tables: 1..6 local facets, nq >= 1");
     const size_t G = (size_t)m->gdim, nf = (size_t)n_local_facets, n_phi = nf * nq * m->dev.ndofs, n_dphi = n_phi * G,
                  n_dpsi = nf * nq * m->dev.ngeom * G;
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    DXO_HIP(ctx, hipDeviceSynchronize());
-    if (m->d_facet_tab) DXO_HIP(ctx, hipFree(m->d_facet_tab));
-    m->d_facet_tab = nullptr;
     m->n_local_facets = m->nq_facet = 0;
-    DXO_HIP(ctx, hipMalloc((void**)&m->d_facet_tab, (n_phi + n_dphi + n_dpsi) * sizeof(double)));
-    DXO_HIP(ctx, hipMemcpy(m->d_facet_tab, phi, n_phi * sizeof(double), hipMemcpyHostToDevice));
-    DXO_HIP(ctx, hipMemcpy(m->d_facet_tab + n_phi, dphi, n_dphi * sizeof(double), hipMemcpyHostToDevice));
-    DXO_HIP(ctx, hipMemcpy(m->d_facet_tab + n_phi + n_dphi, dpsi, n_dpsi * sizeof(double), hipMemcpyHostToDevice));
+    const int rc = upload_slab(ctx, &m->d_facet_tab, {{phi, n_phi}, {dphi, n_dphi}, {dpsi, n_dpsi}});
+    if (rc != DXO_OK) return rc;
     m->n_local_facets = n_local_facets;
     m->nq_facet = nq;
     return DXO_OK;

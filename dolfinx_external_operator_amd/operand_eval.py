@@ -345,19 +345,27 @@ class DeviceMesh:
         B_test^T C B_trial, C a DEVICE pointer as for bilinear_apply. `values`: a float64 CUDA tensor of pattern.nnz entries, accumulated
         into (SET with option consumer_overwrite); None: a new zero tensor. `bcs`: an int32 CUDA tensor of constrained dofs, whose rows and
         columns are then zeroed and whose diagonal is set to `diagonal` (dxo_csr_dirichlet), as assemble_matrix(J, bcs) does."""
+        t, r = self._bilinear_kinds(test, trial, bs)
+
+        def assemble(values_ptr):
+            rc = self.ctx.lib.dxo_bilinear_assemble(self.ctx._h, self._h, pattern._h, t, r, int(bs), C.c_void_p(C_ptr), values_ptr)
+            self.ctx.check(rc, "dxo_bilinear_assemble")
+
+        return self._assemble_on("bilinear_assemble", pattern, values, bcs, diagonal, assemble)
+
+    def _assemble_on(self, who: str, pattern: "CsrPattern", values, bcs, diagonal: float, assemble) -> "DeviceCSR":
+        """The values / bcs half of the two *_assemble methods: `values` checked (None: a new zero tensor), assemble(pointer to them), then
+        the Dirichlet pass over `bcs` (dxo_csr_dirichlet) unless it is None."""
         import torch
 
-        t, r = self._bilinear_kinds(test, trial, bs)
         if values is None:
             values = torch.zeros(pattern.nnz, dtype=torch.float64, device=torch.device("cuda", self.ctx.device))
         if not (values.dtype == torch.float64 and values.is_cuda and values.is_contiguous() and values.numel() == pattern.nnz):
-            raise ValueError(f"bilinear_assemble: values must be a contiguous float64 CUDA tensor of {pattern.nnz} entries")
-        rc = self.ctx.lib.dxo_bilinear_assemble(self.ctx._h, self._h, pattern._h, t, r, int(bs), C.c_void_p(C_ptr),
-                                                C.c_void_p(values.data_ptr()))
-        self.ctx.check(rc, "dxo_bilinear_assemble")
+            raise ValueError(f"{who}: values must be a contiguous float64 CUDA tensor of {pattern.nnz} entries")
+        assemble(C.c_void_p(values.data_ptr()))
         if bcs is not None:
             if not (bcs.dtype == torch.int32 and bcs.is_cuda and bcs.is_contiguous()):
-                raise ValueError("bilinear_assemble: bcs must be a contiguous int32 CUDA tensor")
+                raise ValueError(f"{who}: bcs must be a contiguous int32 CUDA tensor")
             rc = self.ctx.lib.dxo_csr_dirichlet(self.ctx._h, pattern._h, C.c_void_p(bcs.data_ptr()), int(bcs.numel()), float(diagonal),
                                                 C.c_void_p(values.data_ptr()))
             self.ctx.check(rc, "dxo_csr_dirichlet")
@@ -398,13 +406,17 @@ class DeviceMesh:
 
     FACET_ADJOINT_KINDS = ("value", "grad", "value_grad", "eps", "div", "F")
 
+    def _facet_kind_check(self, who: str, what: str, form: str, kind: str, bs: int) -> None:
+        """The (kind, bs) a facet form admits: a linear kind at bs = 1 or gdim, the kinds of a vector field at gdim alone."""
+        if kind not in self.FACET_ADJOINT_KINDS:
+            raise ValueError(f"{who}: {what} {kind!r} has no {form}; linear kinds: {self.FACET_ADJOINT_KINDS}")
+        if int(bs) not in (1, self.gdim) or (kind in ("eps", "div", "F") and int(bs) != self.gdim):
+            raise ValueError(f"{who}: bs = {bs} does not fit {what} {kind!r} on gdim {self.gdim} (bs = 1 or gdim; eps / div / F: gdim)")
+
     def facet_adjoint(self, kind: str, bs: int, S_ptr: int, facet_set: "FacetSet", out_ptr: int) -> None:
         """out += sum_e sum_q dS B^T S over the set's facets (dxo_facet_adjoint; DEVICE pointers, S (n, nq, value_size)): the assembled
         vector of inner(S, operand(v)) ds. ("value", gdim) with S = t is a traction load. Always accumulates."""
-        if kind not in self.FACET_ADJOINT_KINDS:
-            raise ValueError(f"facet_adjoint: kind {kind!r} has no adjoint; linear kinds: {self.FACET_ADJOINT_KINDS}")
-        if int(bs) not in (1, self.gdim) or (kind in ("eps", "div", "F") and int(bs) != self.gdim):
-            raise ValueError(f"facet_adjoint: bs = {bs} does not fit kind {kind!r} on gdim {self.gdim} (bs = 1 or gdim; eps / div / F: gdim)")
+        self._facet_kind_check("facet_adjoint", "kind", "adjoint", kind, bs)
         rc = self.ctx.lib.dxo_facet_adjoint(self.ctx._h, self._h, facet_set._h, KINDS[kind], int(bs), C.c_void_p(S_ptr), C.c_void_p(out_ptr))
         self.ctx.check(rc, "dxo_facet_adjoint")
 
@@ -421,10 +433,7 @@ class DeviceMesh:
     def _facet_bilinear_kinds(self, who: str, test: str, trial: str, bs: int) -> tuple[int, int]:
         if test != "value":
             raise ValueError(f"{who}: the test kind must be 'value' (a boundary residual g . v ds), not {test!r}")
-        if trial not in self.FACET_BILINEAR_TRIALS:
-            raise ValueError(f"{who}: trial kind {trial!r} has no bilinear form; linear kinds: {self.FACET_BILINEAR_TRIALS}")
-        if int(bs) not in (1, self.gdim) or (trial in ("eps", "div", "F") and int(bs) != self.gdim):
-            raise ValueError(f"{who}: bs = {bs} does not fit trial kind {trial!r} on gdim {self.gdim} (bs = 1 or gdim; eps / div / F: gdim)")
+        self._facet_kind_check(who, "trial kind", "bilinear form", trial, bs)
         return KINDS[test], KINDS[trial]
 
     def facet_bilinear_apply(self, trial: str, bs: int, C_ptr: int, v_ptr: int, facet_set: "FacetSet", out_ptr: int, test: str = "value") -> None:
@@ -447,23 +456,13 @@ class DeviceMesh:
         """The operator of facet_bilinear_apply ASSEMBLED on `pattern` (dxo_facet_bilinear_assemble): values += K, always accumulated.
         `values` and `bcs` as in bilinear_assemble: with values=A.values the boundary term is added to a cell matrix, and the Dirichlet
         pass (dxo_csr_dirichlet) runs after it — so assemble the cell form without bcs and pass them here."""
-        import torch
-
         t, r = self._facet_bilinear_kinds("facet_bilinear_assemble", test, trial, bs)
-        if values is None:
-            values = torch.zeros(pattern.nnz, dtype=torch.float64, device=torch.device("cuda", self.ctx.device))
-        if not (values.dtype == torch.float64 and values.is_cuda and values.is_contiguous() and values.numel() == pattern.nnz):
-            raise ValueError(f"facet_bilinear_assemble: values must be a contiguous float64 CUDA tensor of {pattern.nnz} entries")
-        rc = self.ctx.lib.dxo_facet_bilinear_assemble(self.ctx._h, self._h, facet_set._h, pattern._h, t, r, int(bs), C.c_void_p(C_ptr),
-                                                      C.c_void_p(values.data_ptr()))
-        self.ctx.check(rc, "dxo_facet_bilinear_assemble")
-        if bcs is not None:
-            if not (bcs.dtype == torch.int32 and bcs.is_cuda and bcs.is_contiguous()):
-                raise ValueError("facet_bilinear_assemble: bcs must be a contiguous int32 CUDA tensor")
-            rc = self.ctx.lib.dxo_csr_dirichlet(self.ctx._h, pattern._h, C.c_void_p(bcs.data_ptr()), int(bcs.numel()), float(diagonal),
-                                                C.c_void_p(values.data_ptr()))
-            self.ctx.check(rc, "dxo_csr_dirichlet")
-        return DeviceCSR(pattern, values)
+
+        def assemble(values_ptr):
+            rc = self.ctx.lib.dxo_facet_bilinear_assemble(self.ctx._h, self._h, facet_set._h, pattern._h, t, r, int(bs), C.c_void_p(C_ptr), values_ptr)
+            self.ctx.check(rc, "dxo_facet_bilinear_assemble")
+
+        return self._assemble_on("facet_bilinear_assemble", pattern, values, bcs, diagonal, assemble)
 
     def tangent_apply_vm(self, prm, sigma_ptr: int, dp_ptr: int, v_ptr: int, out_ptr: int) -> None:
         """out += K v with the von Mises consistent tangent formed per point from the operator's returned (sigma, dp) — no C_tang

@@ -6,7 +6,7 @@ mag from oracle/facet_reference.py (long double); entries with mag = 0 must be e
 what float64 NumPy itself loses against long double on these meshes, rules, lists and inputs (measured and asserted in
 test_facet_reference_cpu.py), and the kernels get MARGIN = 8 times that, as in consumer_cases.py.
 
-Workgroup rounds (csrc/facet_form.hip). The vector kernels (facet_element, facet_bilinear_element) take DXO_BLOCK / nq entities per
+Workgroup rounds (csrc/facet_form.hip). The vector kernels (facet_element in its four modes) take DXO_BLOCK / nq entities per
 workgroup and round, facet_assemble_elem min(DXO_BLOCK / nq, FB_LDS_DOUBLES / (nq * PS)) with PS = (bs * bs * NZ) | 1 parked doubles
 per point; vector_epb / assembly_epb restate the two formulas and check_rounds() asserts, for every (rule, trial, bs), that the case
 list holds a list shorter than a round, one longer than a round with a ragged tail, and one that is a whole number (> 1) of rounds.
@@ -120,13 +120,13 @@ def float64_oracles_at(case):
 
 # ------------------------------------------------------------------------------------------------ workgroup rounds
 def vector_epb(nq):
-    """Entities per workgroup and round of facet_element / facet_bilinear_element: epb = DXO_BLOCK / nqf."""
+    """Entities per workgroup and round of facet_element (every mode): epb = DXO_BLOCK / nqf."""
     return DXO_BLOCK // nq
 
 
 def assembly_epb(nq, G, trial, bs):
     """The same of facet_assemble_elem: min(DXO_BLOCK / nqf, FB_LDS_DOUBLES / (nqf * ps)), ps = fb_block_stride = (BS * BS * NZ) | 1,
-    NZ = fb_nz = one value slot where the kind has a value, G gradient slots where it has a gradient ("F" runs as "grad")."""
+    NZ = facet_nz = one value slot where the kind has a value, G gradient slots where it has a gradient ("F" runs as "grad")."""
     nz = (1 if trial in ("value", "value_grad") else 0) + (G if trial != "value" else 0)
     return min(DXO_BLOCK // nq, FB_LDS_DOUBLES // (nq * ((bs * bs * nz) | 1)))
 

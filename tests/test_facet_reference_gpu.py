@@ -7,7 +7,7 @@ Bound, for EVERY entry k: |got[k] - (r0[k] + ref[k])| <= c * 2^-53 * mag[k] + t[
 before the call (all these calls accumulate; the geometry call overwrites: r0 = 0), mag[k] the same sum as ref[k] with the absolute
 value of every factor and term, c = MARGIN * C_REF[entry] (facet_reference_cases.py): 8 times what float64 NumPy itself loses against
 long double on these cases. t = 1 for the dof vectors, because facet_node_sum forms a node's sum in a register and adds it to `out`
-once; for dxo_facet_bilinear_assemble t[k] is the number of entity contributions to entry k, because facet_assemble_rows adds every
+once; for dxo_facet_bilinear_assemble t[k] is the number of entity contributions to entry k, because assemble_rows (csr.h) adds every
 entity's row straight into `values` (dst[jj] += src[...] inside its loop over the node's incidences), one rounding against what the
 entry holds each time. Entries with mag = 0 — untouched nodes, pattern entries no entity reaches — hold r0 exactly. c is not tuned on
 the kernels; the ratios they show on the MI355X are in profiles/facet_reference_ratios.txt."""
