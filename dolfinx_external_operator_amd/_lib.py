@@ -240,6 +240,10 @@ _SIGNATURES = {
     "dxo_facet_bilinear_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "dxo_facet_bilinear_diagonal": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dxo_facet_bilinear_assemble": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "dxo_eval_cell_measure": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "dxo_integrate": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    "dxo_facet_integrate": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P]),
+    "dxo_operand_moments": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
     "dxo_tangent_apply_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P, _P]),
     "dxo_von_mises_residual": (C.c_int, [_P, C.POINTER(VmParams), _P, _P, _P, _P, _P, _P, _P]),
     "dxo_tangent_diagonal_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P]),

@@ -245,7 +245,7 @@ extern "C" int dxo_mesh_destroy(dxo_ctx* ctx, dxo_mesh* m) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     free_all({m->blob, m->d_u, m->d_cells, m->d_out, m->d_facet_tab, m->d_facet_geom, m->d_ents, m->d_wq, m->d_psi, m->d_node_ptr, m->d_node_ent,
-              m->d_fe, m->patch.blob, m->patch.dev.bpart});
+              m->d_fe, m->patch.blob, m->patch.dev.bpart, m->d_fn_part});
     delete m;
     return DXO_OK;
 }

@@ -528,7 +528,9 @@ struct dxo_mesh {
     double* d_out = nullptr;    // staging for host-resident outputs
     size_t out_cap = 0;
     double* d_psi = nullptr;    // [nq][ngeom] values of the coordinate element at the quadrature points (dxo_mesh_set_coordinate_values)
-    double* d_wq = nullptr;     // quadrature weights (dxo_mesh_set_weights), needed by the adjoint kernels only
+    double* d_wq = nullptr;     // quadrature weights (dxo_mesh_set_weights), needed by the adjoint kernels and the functionals
+    double* d_fn_part = nullptr; // functional.hip: partial sums [n_out][n_groups] of the last cell functional, grow-only
+    size_t fn_cap = 0;
     // codim-1 evaluation (dxo_mesh_set_facet_tables / dxo_eval_operand_facets): tables per LOCAL facet of the cell
     int n_local_facets = 0, nq_facet = 0;
     double* d_facet_tab = nullptr;      // phi_f [nf][nqf][ndofs] | dphi_f [nf][nqf][ndofs][G] | dpsi_f [nf][nqf][ngeom][G]

@@ -427,6 +427,115 @@ class DeviceMesh:
                                              C.c_void_p(out_ptr))
         self.ctx.check(rc, "dxo_facet_pressure")
 
+    # ---- scalar functionals (csrc/functional.hip): CUDA tensors in, CUDA tensors out, nothing synchronised — the caller's .item() /
+    # .cpu() does. Results are SET, bit-reproducible and independent of the launch shape.
+    INTEGRATE_SIZES = (1, 2, 3, 4, 6, 9)
+
+    def _functional_tensor(self, who: str, name: str, t, dtype, shape, optional: bool = False):
+        """`t` checked as a contiguous CUDA tensor of this context's device with `dtype` and `shape` (None entries: any extent)."""
+        import torch
+
+        if t is None and optional:
+            return None
+        dev = torch.device("cuda", self.ctx.device)
+        ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.is_contiguous() and t.ndim == len(shape) and \
+            all(s is None or s == e for s, e in zip(shape, t.shape))
+        if not ok:
+            want = "(" + ", ".join("n" if s is None else str(s) for s in shape) + ("," if len(shape) == 1 else "") + ")"
+            raise ValueError(f"{who}: {name} must be a contiguous {str(dtype).replace('torch.', '')} CUDA tensor of shape {want} on {dev}")
+        return t
+
+    def _functional_cells(self, who: str, cells):
+        import torch
+
+        cells = self._functional_tensor(who, "cells", cells, torch.int32, (None,), optional=True)
+        return cells, (self.num_cells if cells is None else cells.shape[0]), (None if cells is None else C.c_void_p(cells.data_ptr()))
+
+    def _functional_out(self, who: str, out, n: int):
+        import torch
+
+        if out is None:
+            return torch.empty((n,), dtype=torch.float64, device=torch.device("cuda", self.ctx.device))
+        return self._functional_tensor(who, "out", out, torch.float64, (n,))
+
+    def cell_measure(self, cells=None, out=None):
+        """dx = w |det J| at the quadrature points of `cells` (an int32 CUDA tensor (n,), None: all cells), a float64 CUDA tensor
+        (n, nq) (dxo_eval_cell_measure): the cell counterpart of the dS of facet_geometry. Needs set_weights."""
+        import torch
+
+        cells, n, cptr = self._functional_cells("cell_measure", cells)
+        if out is None:
+            out = torch.empty((n, self.nq), dtype=torch.float64, device=torch.device("cuda", self.ctx.device))
+        self._functional_tensor("cell_measure", "out", out, torch.float64, (n, self.nq))
+        rc = self.ctx.lib.dxo_eval_cell_measure(self.ctx._h, self._h, cptr, n, C.c_void_p(out.data_ptr()))
+        self.ctx.check(rc, "dxo_eval_cell_measure")
+        return out
+
+    def integrate(self, f, g=None, cells=None, out=None):
+        """The integrals over `cells` (None: all) of quadrature data f, a float64 CUDA tensor (n, nq, D) indexed by position in the
+        list, as evaluate / Expression.eval lay it out (dxo_integrate). g = None: the D integrals of the components, a (D,) tensor, D in
+        INTEGRATE_SIZES; g shaped like f: the pairing int f : g dx, a (1,) tensor, any D (g may be f: int |f|^2 dx)."""
+        import torch
+
+        cells, n, cptr = self._functional_cells("integrate", cells)
+        if isinstance(f, torch.Tensor) and f.ndim == 2:
+            f = f.unsqueeze(2)
+        if isinstance(g, torch.Tensor) and g.ndim == 2:
+            g = g.unsqueeze(2)
+        f = self._functional_tensor("integrate", "f", f, torch.float64, (n, self.nq, None))
+        D = f.shape[2]
+        g = self._functional_tensor("integrate", "g", g, torch.float64, (n, self.nq, D), optional=True)
+        if D < 1 or (g is None and D not in self.INTEGRATE_SIZES):
+            raise ValueError(f"integrate: f (n, nq, D) has D = {D}; without g the value sizes {self.INTEGRATE_SIZES} are served")
+        out = self._functional_out("integrate", out, D if g is None else 1)
+        # an empty tensor has no address, and a NULL g would select the per-component form: `out` stands in (nothing is read at n = 0)
+        fp, gp = (out.data_ptr(), None if g is None else out.data_ptr()) if n == 0 else (f.data_ptr(), None if g is None else g.data_ptr())
+        rc = self.ctx.lib.dxo_integrate(self.ctx._h, self._h, cptr, n, D, C.c_void_p(fp), None if gp is None else C.c_void_p(gp),
+                                        C.c_void_p(out.data_ptr()))
+        self.ctx.check(rc, "dxo_integrate")
+        return out
+
+    def facet_integrate(self, f, facet_set: "FacetSet", g=None, out=None):
+        """integrate over the facets of `facet_set` with dS (dxo_facet_integrate): f a float64 CUDA tensor (n, nq_facet, D), e.g. torch
+        arithmetic on evaluate_facets_device. Needs set_facet_geometry."""
+        import torch
+
+        if not hasattr(self, "nq_facet"):
+            raise ValueError("facet_integrate: facet tables not set (set_facet_tables)")
+        if isinstance(f, torch.Tensor) and f.ndim == 2:
+            f = f.unsqueeze(2)
+        if isinstance(g, torch.Tensor) and g.ndim == 2:
+            g = g.unsqueeze(2)
+        f = self._functional_tensor("facet_integrate", "f", f, torch.float64, (facet_set.n, self.nq_facet, None))
+        D = f.shape[2]
+        g = self._functional_tensor("facet_integrate", "g", g, torch.float64, (facet_set.n, self.nq_facet, D), optional=True)
+        if D < 1 or (g is None and D not in self.INTEGRATE_SIZES):
+            raise ValueError(f"facet_integrate: f (n, nq_facet, D) has D = {D}; without g the value sizes {self.INTEGRATE_SIZES} are served")
+        out = self._functional_out("facet_integrate", out, D if g is None else 1)
+        empty = facet_set.n == 0      # as in integrate: `out` stands in for the addresses of empty tensors
+        fp, gp = (out.data_ptr(), None if g is None else out.data_ptr()) if empty else (f.data_ptr(), None if g is None else g.data_ptr())
+        rc = self.ctx.lib.dxo_facet_integrate(self.ctx._h, self._h, facet_set._h, D, C.c_void_p(fp), None if gp is None else C.c_void_p(gp),
+                                              C.c_void_p(out.data_ptr()))
+        self.ctx.check(rc, "dxo_facet_integrate")
+        return out
+
+    def operand_moments(self, kind: str, bs: int, u, cells=None, out=None):
+        """The fused form (dxo_operand_moments): the operand `kind` of the dofs u (a float64 CUDA tensor of num_field_nodes * bs
+        entries, bs = 1 or gdim) is formed in registers and never written. Returns a (D + 1,) tensor: [int operand_k dx for k < D,
+        int |operand|^2 dx]. "value": mean and squared L2 norm; "grad": squared H1 seminorm; "detF": deformed volume; "div": outflow."""
+        import torch
+
+        D = self.value_size(kind, bs)
+        if bs not in (1, self.gdim):
+            raise ValueError(f"operand_moments: block size {bs} has no fused form (bs = 1 or gdim = {self.gdim})")
+        cells, n, cptr = self._functional_cells("operand_moments", cells)
+        u = self._functional_tensor("operand_moments", "u", u, torch.float64, (self.num_field_nodes * bs,))
+        out = self._functional_out("operand_moments", out, D + 1)
+        rc = self.ctx.lib.dxo_operand_moments(self.ctx._h, self._h, KINDS[kind], int(bs), C.c_void_p(u.data_ptr()), cptr, n,
+                                              C.c_void_p(out.data_ptr()))
+        self.ctx.check(rc, "dxo_operand_moments")
+        return out
+
     # trial kinds of the facet bilinear forms: the linear kinds, "F" standing for its linearisation, grad
     FACET_BILINEAR_TRIALS = FACET_ADJOINT_KINDS
 

@@ -951,6 +951,43 @@ int dxo_facet_bilinear_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_facet_se
 int dxo_facet_bilinear_assemble(dxo_ctx* ctx, dxo_mesh* mesh, dxo_facet_set* set, dxo_csr* csr, int test_kind, int trial_kind, int bs,
                                 const double* C, double* values);
 
+/* ---- scalar functionals (rank-0 forms): quadrature data reduced to numbers on the device ------------------------------
+ * The reference's `fem.assemble_scalar`: J = g(u) * ds and f(u * u) * dx over a cell subset with their derivatives
+ * (test/test_codim_external_operator.py), and the error norm sqrt(assemble_scalar((u - u_UFL)**2 * dx)) that ends
+ * demo_hyperelasticity.py (:817). All array pointers are DEVICE pointers, 8-byte aligned (DXO_E_ALIGN otherwise; `cells` 4-byte)
+ * and non-NULL where a length above zero makes them needed (DXO_E_NULL otherwise; `out` always). Asynchronous on the context's stream.
+ * dxo_eval_cell_measure : dx[n_cells][nq] = w_q |det J|, the cell counterpart of dS (dxo_eval_facet_geometry). cells / n_cells as for
+ *     dxo_eval_operand: an entity list (not range-checked), or NULL for the cells [0, n_cells) (n_cells < 0: all).
+ * dxo_integrate : f [n_cells][nq][D], indexed by POSITION in the list — the layout Expression.eval / dxo_eval_operand write.
+ *     g == NULL: out[k] = sum_c sum_q w_q |det J| f[c][q][k] for k < D, the integrals of the D components, for the value sizes this
+ *                library's operators produce, D = 1, 2, 3, 4, 6, 9 (any other: DXO_E_DIM).
+ *     g != NULL, shaped like f: out[0] = sum_c sum_q w_q |det J| sum_k f_k g_k, the pairing int f : g dx, any D in 1 .. 2^24
+ *                (g == f is allowed: int |f|^2 dx).
+ * dxo_facet_integrate : the same two forms over a facet set with dS, f [n][nq_facet][D]. The checks are dxo_facet_adjoint's: facet
+ *     geometry not set DXO_E_OPTION; a set created on another mesh, or tables / geometry changed to another (nf, nq): DXO_E_DIM.
+ * dxo_operand_moments : the fused form — the operand is formed from the dofs u in registers and never written:
+ *     out[k] = int operand_k(u) dx for k < D, out[D] = int |operand(u)|^2 dx, D = dxo_operand_value_size(gdim, bs, kind), out D + 1
+ *     doubles. Every kind dxo_eval_operand takes, at bs = 1 or gdim; other block sizes DXO_E_DIM (the per-component launches have
+ *     no fused form), an unknown kind DXO_E_OPTION. VALUE: the mean of u and the squared L2 norm (of a difference field: the demo's
+ *     error norm); GRAD: the squared H1 seminorm; DETF: the deformed volume; DIV: the net outflow.
+ * The cell calls need dxo_mesh_set_weights (DXO_E_OPTION otherwise). |det J|, not det J: a mirrored mesh integrates to the same
+ * value. A list may repeat a cell; it is then counted as often, as dxo_eval_operand evaluates it as often.
+ * `out` is SET, never accumulated (option "consumer_overwrite" does not apply), and an empty list or set gives exactly +0.0 in every
+ * entry: a functional over nothing is 0.
+ * No atomics, bit-reproducible, and the bits do not depend on the launch shape or the device's compute-unit count: every GROUP — the
+ * floor(64 / nq) consecutive cells of the list one wave takes, or floor(64 / nq_facet) consecutive entities (one for a rule of 64
+ * points or more) — sums its points in a fixed lane order and writes one partial per output to a scratch [n_out][n_groups]; a second
+ * kernel, one workgroup per output, adds the partials in a fixed order (lane t of 256 takes groups t, t + 256, ... ascending, then a
+ * fixed LDS tree joins the lanes). The scratch is grow-only and owned by the mesh (cell calls) or the facet set (facet call): the
+ * first call of a size allocates it; after that the calls allocate and synchronise nothing (capture-safe). A mesh whose vertices
+ * and parked values exceed the 64 KiB LDS budget is refused with DXO_E_SIZE. */
+int dxo_eval_cell_measure(dxo_ctx* ctx, dxo_mesh* mesh, const int32_t* cells, int64_t n_cells, double* dx);
+int dxo_integrate(dxo_ctx* ctx, dxo_mesh* mesh, const int32_t* cells, int64_t n_cells, int D, const double* f, const double* g,
+                  double* out);
+int dxo_facet_integrate(dxo_ctx* ctx, dxo_mesh* mesh, dxo_facet_set* set, int D, const double* f, const double* g, double* out);
+int dxo_operand_moments(dxo_ctx* ctx, dxo_mesh* mesh, int kind, int bs, const double* u, const int32_t* cells, int64_t n_cells,
+                        double* out);
+
 /* ---- coefficient assigners on the device, DEVICE memory only --------------------------
  * One scatter for the reference's three dofmap assigners (src/dolfinx_external_operator/external_operator.py):
  * _assign_non_mixed :286-287, _assign_mixed_2d :292-311, _assign_mixed_3d :313-335. For cell c, point p < n_pts,
