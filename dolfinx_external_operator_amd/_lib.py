@@ -192,12 +192,15 @@ _SIGNATURES = {
     "dxo_tangent_diagonal": (C.c_int, [_P, _P, _P, _P]),
     "dxo_bilinear_apply": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "dxo_bilinear_diagonal": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "dxo_bilinear_apply_t": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "dxo_csr_create": (C.c_int, [_P, _P, C.c_int, C.POINTER(_P)]),
     "dxo_csr_destroy": (C.c_int, [_P, _P]),
     "dxo_csr_info": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_double)]),
     "dxo_bilinear_assemble": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "dxo_csr_dirichlet": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, _P]),
     "dxo_csr_spmv": (C.c_int, [_P, _P, _P, C.c_double, _P, C.c_double, _P]),
+    "dxo_csr_transpose": (C.c_int, [_P, _P, _P, _P]),
+    "dxo_csr_spmv_t": (C.c_int, [_P, _P, _P, C.c_double, _P, C.c_double, _P]),
     "dxo_csr_block_jacobi": (C.c_int, [_P, _P, _P, _P]),
     "dxo_block_jacobi_apply": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P]),
     "dxo_krylov_create": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(_P)]),

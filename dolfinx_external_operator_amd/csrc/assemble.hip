@@ -250,7 +250,7 @@ struct Assemble {
 int grid_blocks(const dxo_ctx* ctx, int64_t work, int per_block) { return capped_grid(ctx, work, per_block, DXO_AS_BLOCKS_PER_CU); }
 
 void csr_free(dxo_csr* c) {
-    free_all({c->d_row_ptr, c->d_col, c->d_inc_ptr, c->d_inc, c->d_pos, c->d_mask, c->d_ae});
+    free_all({c->d_row_ptr, c->d_col, c->d_inc_ptr, c->d_inc, c->d_pos, c->d_mask, c->d_mirror, c->d_ae});
     delete c;
 }
 

@@ -3,6 +3,7 @@
 // geometry, dual_tensor, adjoint_scatter and the two-pass scatter (element vectors fe + node_sum).
 //   out[dof]  += sum_q w_q |det J_q| B_test,q^T C_q B_trial,q v           C_q: [D_test][D_trial] row-major fp64 per point
 //   diag[dof] += sum_q w_q |det J_q| (B_test,q^T C_q B_trial,q)_(dof,dof)
+//   out[dof]  += sum_q w_q |det J_q| B_trial,q^T C_q^T B_test,q v         the transposed action (dxo_bilinear_apply_t), same C
 // dxo_tangent_apply is the pair (eps, eps) with bs = gdim; the finite-strain Jacobian of the hyperelasticity demo is (grad, grad) with
 // C = dP/dF, the heat demo's Jacobian (grad, value_grad) with bs = 1 and C = [dq/dT | dq/dsigma].
 #pragma once
@@ -116,15 +117,36 @@ struct BlockRows {
             }
         });
     }
+    // t = C^T e for the lane's point: the same staged block, read once in the same order, t[c] += R[r * DR + c] e[r]
+    __device__ __forceinline__ void times_t(double* S, int lane, const double (&e)[DT], double (&t)[DR]) {
+#pragma unroll
+        for (int i = 0; i < DR; ++i) t[i] = 0.0;
+        for_each(S, lane, [&](const double* R) {
+            const unit* Ru = reinterpret_cast<const unit*>(R);
+#pragma unroll
+            for (int u = 0; u < UPP; ++u) {
+                const unit c = Ru[u];
+                if constexpr (U == 2) {
+                    t[(2 * u) % DR] += c.x * e[(2 * u) / DR];
+                    t[(2 * u + 1) % DR] += c.y * e[(2 * u + 1) / DR];
+                } else {
+                    t[u % DR] += c * e[u / DR];
+                }
+            }
+        });
+    }
 };
 
 // K v: gather v, the trial operand e = B_trial v per point, t = C e through the staged blocks, scatter B_test^T t (adjoint_scatter).
 // The shape of tangent_apply's general form (register-pipelined gather, C requested before the contraction).
-template <int G, int BS, int TEST, int TRIAL>
+// TRANS: K^T v with the roles of the kinds swapped on the same blocks: e = B_test v, t = C^T e, scatter B_trial^T t.
+template <int G, int BS, int TEST, int TRIAL, bool TRANS = false>
 __global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_apply(OperandDev m, const double* __restrict__ wq, int lds_wave,
                                                                          const double* __restrict__ C, const double* __restrict__ v,
                                                                          int64_t n_cells, double* __restrict__ out, double* __restrict__ fe) {
     constexpr int DT = OperandShape<G, BS, TEST>::D, DR = OperandShape<G, BS, TRIAL>::D;
+    constexpr int KIN = TRANS ? TEST : TRIAL, KOUT = TRANS ? TRIAL : TEST;      // the kind of the operand of v, the kind scattered
+    constexpr int DIN = TRANS ? DT : DR, DOUT = TRANS ? DR : DT;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* tab = lds;
     operand_load_tables<G>(m, tab);
@@ -159,18 +181,19 @@ __global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_apply(Operan
         } else {
             operand_gather<G, BS>(m, W, v, nullptr, c0, ncell, lane);
         }
-        double e[DR], K[G][G], det = 0.0;
+        double e[DIN], K[G][G], det = 0.0;
 #pragma unroll
         for (int i = 0; i < G; ++i)
 #pragma unroll
             for (int j = 0; j < G; ++j) K[i][j] = 0.0;
-        const bool active = operand_compute_geo<G, BS, TRIAL>(m, tab, W, ncell, lane, e, K, det);
+        const bool active = operand_compute_geo<G, BS, KIN>(m, tab, W, ncell, lane, e, K, det);
         if (!active) {
 #pragma unroll
-            for (int k = 0; k < DR; ++k) e[k] = 0.0;
+            for (int k = 0; k < DIN; ++k) e[k] = 0.0;
         }
-        double t[DT];
-        rows.times(W, lane, e, t);      // compute_geo has fenced: the gather buffer is free, the parked tensors are not written yet
+        double t[DOUT];
+        if constexpr (TRANS) rows.times_t(W, lane, e, t);
+        else rows.times(W, lane, e, t);      // compute_geo has fenced: the gather buffer is free, the parked tensors are not written yet
         double vh[BS], gh[BS][G], scale = 0.0;
 #pragma unroll
         for (int i = 0; i < BS; ++i) {
@@ -180,7 +203,7 @@ __global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_apply(Operan
         }
         if (active) {
             scale = w_l * fabs(det);
-            dual_tensor<G, BS, TEST>(t, vh, gh);
+            dual_tensor<G, BS, KOUT>(t, vh, gh);
         }
         adjoint_scatter<G, BS>(m, tab, Tm, active, lane, vh, gh, K, scale, c0, ncell, nullptr, out, fe);
     }
@@ -316,21 +339,24 @@ __global__ __launch_bounds__(DXO_BLOCK, DXO_BL_WAVES) void bilinear_diag(Operand
     }
 }
 
-// host side: LDS per wave and launch of one (G, BS, TEST, TRIAL)
+// host side: LDS per wave and launch of one (G, BS, TEST, TRIAL), for the action, the diagonal or the transposed action
+enum { BL_APPLY = 0, BL_DIAG = 1, BL_APPLY_T = 2 };
 template <int G, int BS, int TEST, int TRIAL>
 struct Bilinear {
     using Rows = BlockRows<OperandShape<G, BS, TEST>::D, OperandShape<G, BS, TRIAL>::D>;
-    static int lds_wave(const dxo_mesh* mesh, bool diag) {
-        if (diag) {
+    static int lds_wave(const dxo_mesh* mesh, int mode) {
+        if (mode == BL_DIAG) {
             constexpr int NZ = G + 1 - ((op_has_value<TEST>() || op_has_value<TRIAL>()) ? 0 : 1);
             const int park = DXO_WAVE * ((BS * NZ * (NZ + 1) / 2) | 1);
             return op_even(vertex_doubles(mesh->dev, G) + (park > Rows::LDS_DOUBLES ? park : Rows::LDS_DOUBLES));
         }
         return wave_region(gather_doubles(mesh->dev, G, BS) + parked_doubles(G, BS), Rows::LDS_DOUBLES);
     }
-    static void launch(const dxo_mesh* mesh, bool diag, int wd, int blocks, size_t shm, const double* C, const double* v, double* out,
+    static void launch(const dxo_mesh* mesh, int mode, int wd, int blocks, size_t shm, const double* C, const double* v, double* out,
                        double* fe, hipStream_t s) {
-        if (diag) hipLaunchKernelGGL((bilinear_diag<G, BS, TEST, TRIAL>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C,
+        if (mode == BL_APPLY_T) hipLaunchKernelGGL((bilinear_apply<G, BS, TEST, TRIAL, true>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq,
+                                                   wd, C, v, mesh->num_cells, out, fe);
+        else if (mode == BL_DIAG) hipLaunchKernelGGL((bilinear_diag<G, BS, TEST, TRIAL>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C,
                                      mesh->num_cells, out, fe);
         else hipLaunchKernelGGL((bilinear_apply<G, BS, TEST, TRIAL>), dim3(blocks), dim3(DXO_BLOCK), shm, s, mesh->dev, mesh->d_wq, wd, C, v,
                                 mesh->num_cells, out, fe);
@@ -338,13 +364,14 @@ struct Bilinear {
 };
 
 struct BilinearOps {
-    int (*lds_wave)(const dxo_mesh*, bool) = nullptr;
-    void (*launch)(const dxo_mesh*, bool, int, int, size_t, const double*, const double*, double*, double*, hipStream_t) = nullptr;
+    int (*lds_wave)(const dxo_mesh*, int) = nullptr;
+    void (*launch)(const dxo_mesh*, int, int, int, size_t, const double*, const double*, double*, double*, hipStream_t) = nullptr;
 };
 
-int bilinear_impl(dxo_ctx* ctx, dxo_mesh* mesh, int test, int trial, int bs, const double* C, const double* v, double* out, bool diag) {
-    const char* who = diag ? "dxo_bilinear_diagonal" : "dxo_bilinear_apply";
-    if (!mesh) return dxo_fail(ctx, DXO_E_NULL, diag ? "dxo_bilinear_diagonal: mesh is NULL" : "dxo_bilinear_apply: mesh is NULL");
+int bilinear_impl(dxo_ctx* ctx, dxo_mesh* mesh, int test, int trial, int bs, const double* C, const double* v, double* out, int mode) {
+    const bool diag = mode == BL_DIAG;
+    const char* who = diag ? "dxo_bilinear_diagonal" : mode == BL_APPLY_T ? "dxo_bilinear_apply_t" : "dxo_bilinear_apply";
+    if (!mesh) return fail_who(ctx, DXO_E_NULL, who, "mesh is NULL");
     BilinearOps ops;
     int rc = bilinear_pair_check(ctx, who, mesh, test, trial, bs, ops, [](auto G, auto BS, auto T, auto R) {
         return BilinearOps{&Bilinear<G, BS, T, R>::lds_wave, &Bilinear<G, BS, T, R>::launch};
@@ -353,7 +380,7 @@ int bilinear_impl(dxo_ctx* ctx, dxo_mesh* mesh, int test, int trial, int bs, con
     if (mesh->num_cells == 0) return DXO_OK;
     if (!C || !out || (!diag && !v)) return fail_who(ctx, DXO_E_NULL, who, "NULL array");
     if (((uintptr_t)C & 15u) != 0) return fail_who(ctx, DXO_E_ALIGN, who, "C must be 16-byte aligned");
-    const int wd = ops.lds_wave(mesh, diag);
+    const int wd = ops.lds_wave(mesh, mode);
     const size_t shm = (size_t)(mesh->dev.table_doubles + (DXO_BLOCK / DXO_WAVE) * wd) * sizeof(double);
     if (shm > 64 * 1024) return fail_who(ctx, DXO_E_SIZE, who, "element too large for the LDS budget");
     hipStream_t s = dxo_launch_stream(ctx);
@@ -363,7 +390,7 @@ int bilinear_impl(dxo_ctx* ctx, dxo_mesh* mesh, int test, int trial, int bs, con
     if (rc != DXO_OK) return rc;
     rc = clear_for_atomics(ctx, mesh, bs, out, fe, s);
     if (rc != DXO_OK) return rc;
-    ops.launch(mesh, diag, wd, wave_group_grid(ctx, wave_groups(mesh->dev, mesh->num_cells), DXO_BL_BLOCKS_PER_CU), shm, C, v, out, fe, s);
+    ops.launch(mesh, mode, wd, wave_group_grid(ctx, wave_groups(mesh->dev, mesh->num_cells), DXO_BL_BLOCKS_PER_CU), shm, C, v, out, fe, s);
     if (fe) launch_node_sum(ctx, mesh, bs, out, s);
     return dxo_device_end(ctx, s);
 }
@@ -374,11 +401,18 @@ extern "C" int dxo_bilinear_apply(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, i
                                   double* out) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
-    return bilinear_impl(ctx, mesh, test_kind, trial_kind, bs, C, v, out, false);
+    return bilinear_impl(ctx, mesh, test_kind, trial_kind, bs, C, v, out, BL_APPLY);
+}
+
+extern "C" int dxo_bilinear_apply_t(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, const double* v,
+                                    double* out) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    return bilinear_impl(ctx, mesh, test_kind, trial_kind, bs, C, v, out, BL_APPLY_T);
 }
 
 extern "C" int dxo_bilinear_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, double* out) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
-    return bilinear_impl(ctx, mesh, test_kind, trial_kind, bs, C, nullptr, out, true);
+    return bilinear_impl(ctx, mesh, test_kind, trial_kind, bs, C, nullptr, out, BL_DIAG);
 }

@@ -15,6 +15,8 @@ struct dxo_csr {
     uint32_t* d_inc = nullptr;         // cell * nd + a, ascending cell per node
     uint16_t* d_pos = nullptr;         // [n_cells][nd][nd] column block of b's node in the rows of a's node
     uint8_t* d_mask = nullptr;         // [n_rows] constrained dofs of the last dxo_csr_dirichlet
+    uint16_t* d_mirror = nullptr;      // [nnz / bs^2] transpose.hip: position of a block's row node in the rows of its column node
+    int mirror_state = 0;              // 0: not built yet, 1: built, -1: built and the pattern found not structurally symmetric
     double* d_ae = nullptr;            // element-matrix scratch of one chunk
     size_t ae_cap = 0;
     double build_ms = 0.0;

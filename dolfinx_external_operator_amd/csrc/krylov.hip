@@ -878,6 +878,8 @@ int dxo_kr_spmv_launch(dxo_ctx* ctx, const dxo_csr* csr, const double* values, c
     return spmv_launch(ctx, "dxo_amg_apply", csr, values, 1.0, x, 0.0, y, s);
 }
 
+int dxo_kr_spmv_lanes(const dxo_ctx* ctx, const dxo_csr* csr) { return spmv_lanes(ctx, csr); }
+
 extern "C" int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y) {
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);

@@ -232,6 +232,10 @@ int dxo_kr_bj_setup_launch(const dxo_csr* csr, const double* values, double* inv
 // krylov.hip: y = A x by the kernel of dxo_csr_spmv (bs 1, 2, 3, 6), for the coarse operators of the K-cycle
 int dxo_kr_spmv_launch(dxo_ctx* ctx, const dxo_csr* csr, const double* values, const double* x, double* y, hipStream_t s);
 
+// krylov.hip: the lanes per node dxo_csr_spmv takes on this pattern (option "spmv_lanes", or from the mean neighbour count), for the
+// transposed product of transpose.hip
+int dxo_kr_spmv_lanes(const dxo_ctx* ctx, const dxo_csr* csr);
+
 // amg.hip: the checks of a DXO_PC_AMG preconditioner against the operator, one cycle z = M(r) on the stream (V or K, as set by
 // dxo_amg_set_cycle), and whether that cycle is the K-cycle (not a fixed linear operator: flexible GMRES only)
 int dxo_amg_pc_check(dxo_ctx* ctx, const char* who, const dxo_amg* amg, const dxo_csr* op_csr, int bs, int64_t n);

@@ -539,8 +539,9 @@ class AMG:
         return self._array(b, i.n_rows * self.n_modes, "<f8").reshape(-1, self.n_modes)
 
 
-def csr_matvec(A, x, y=None, alpha: float = 1.0, beta: float = 0.0):
-    """y = alpha A x + beta y on the device (dxo_csr_spmv); with beta == 0, y is not read. Returns y."""
+def csr_matvec(A, x, y=None, alpha: float = 1.0, beta: float = 0.0, transpose: bool = False):
+    """y = alpha A x + beta y on the device (dxo_csr_spmv); with beta == 0, y is not read. Returns y. transpose=True:
+    y = alpha A^T x + beta y (dxo_csr_spmv_t), bit for bit the product with DeviceCSR.transpose()'s matrix."""
     torch = _torch()
     ctx, n = A.pattern.ctx, A.pattern.n_rows
     _check_vec(x, n, A.values.device, "matvec: x")
@@ -550,9 +551,10 @@ def csr_matvec(A, x, y=None, alpha: float = 1.0, beta: float = 0.0):
         y = torch.empty_like(x)
     _check_vec(y, n, A.values.device, "matvec: y")
     _use_current_stream(ctx)
-    rc = ctx.lib.dxo_csr_spmv(ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), float(alpha), C.c_void_p(x.data_ptr()), float(beta),
-                              C.c_void_p(y.data_ptr()))
-    ctx.check(rc, "dxo_csr_spmv")
+    spmv, name = (ctx.lib.dxo_csr_spmv_t, "dxo_csr_spmv_t") if transpose else (ctx.lib.dxo_csr_spmv, "dxo_csr_spmv")
+    rc = spmv(ctx._h, A.pattern._h, C.c_void_p(A.values.data_ptr()), float(alpha), C.c_void_p(x.data_ptr()), float(beta),
+              C.c_void_p(y.data_ptr()))
+    ctx.check(rc, name)
     return y
 
 

@@ -326,6 +326,15 @@ class DeviceMesh:
         rc = self.ctx.lib.dxo_bilinear_apply(self.ctx._h, self._h, t, r, int(bs), C.c_void_p(C_ptr), C.c_void_p(v_ptr), C.c_void_p(out_ptr))
         self.ctx.check(rc, "dxo_bilinear_apply")
 
+    def bilinear_apply_t(self, test: str, trial: str, bs: int, C_ptr: int, v_ptr: int, out_ptr: int) -> None:
+        """out += sum_q w |det J| B_trial^T C^T B_test v (dxo_bilinear_apply_t): the action of the TRANSPOSE of bilinear_apply's operator,
+        for adjoint solves. (test, trial), C and its layout are those of the forward call; nothing is transposed by the caller. The
+        diagonal of the transpose is bilinear_diagonal. The transposed boundary-facet action has no call of its own: it composes from
+        evaluate_facets_device("value", v), a pointwise C^T product and facet_adjoint of the trial kind."""
+        t, r = self._bilinear_kinds(test, trial, bs)
+        rc = self.ctx.lib.dxo_bilinear_apply_t(self.ctx._h, self._h, t, r, int(bs), C.c_void_p(C_ptr), C.c_void_p(v_ptr), C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_bilinear_apply_t")
+
     def bilinear_diagonal(self, test: str, trial: str, bs: int, C_ptr: int, out_ptr: int) -> None:
         """out += diag of the same operator as bilinear_apply (DEVICE pointers): Jacobi preconditioner."""
         t, r = self._bilinear_kinds(test, trial, bs)
@@ -771,11 +780,35 @@ class DeviceCSR:
         indptr, indices, values = self.to_numpy()
         return scipy.sparse.csr_matrix((values, indices, indptr), shape=self.shape)
 
-    def matvec(self, x, y=None, alpha: float = 1.0, beta: float = 0.0):
-        """y = alpha A x + beta y on the device (dxo_csr_spmv, BLAS semantics: with beta == 0, y is not read); returns y."""
+    def matvec(self, x, y=None, alpha: float = 1.0, beta: float = 0.0, transpose: bool = False):
+        """y = alpha A x + beta y on the device (dxo_csr_spmv, BLAS semantics: with beta == 0, y is not read); returns y.
+        transpose=True: y = alpha A^T x + beta y without forming A^T (dxo_csr_spmv_t), bit for bit the product of `transpose()`'s
+        matrix. `gmres(lambda v, out: A.matvec(v, out, transpose=True), ...)` is the copy-free route to an adjoint solve; a one-off
+        product pays scattered reads, so many products on one matrix are better served by `transpose()` once."""
         from .krylov import csr_matvec
 
-        return csr_matvec(self, x, y, alpha, beta)
+        return csr_matvec(self, x, y, alpha, beta, transpose)
+
+    def transpose(self, out=None) -> "DeviceCSR":
+        """A^T on the same pattern (dxo_csr_transpose): the pattern is structurally symmetric, so only the values are permuted, exactly.
+        out=None: a new values tensor; out=self.values: in place; any other float64 CUDA tensor of nnz entries that does not overlap
+        the values: written to. The transposed matrix keeps the row pointers, columns and Dirichlet mask, so block Jacobi and the
+        multigrid apply unchanged: an in-place transpose followed by `amg.setup()` reuses the hierarchy's symbolic phase for the
+        adjoint solve (strength masks stay the frozen ones). dxo_csr_dirichlet commutes with transposition: rows and columns are
+        both zeroed."""
+        import torch
+
+        pat = self.pattern
+        if out is None:
+            out = torch.empty_like(self.values)
+        if not (out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.numel() == pat.nnz):
+            raise ValueError(f"transpose: out must be a contiguous float64 CUDA tensor of {pat.nnz} entries")
+        from .krylov import _use_current_stream
+
+        _use_current_stream(pat.ctx)
+        rc = pat.ctx.lib.dxo_csr_transpose(pat.ctx._h, pat._h, C.c_void_p(self.values.data_ptr()), C.c_void_p(out.data_ptr()))
+        pat.ctx.check(rc, "dxo_csr_transpose")
+        return self if out is self.values else DeviceCSR(pat, out)
 
     def block_jacobi(self) -> "BlockJacobi":
         """The inverses of the bs x bs diagonal blocks (dxo_csr_block_jacobi) as a preconditioner for krylov.gmres / krylov.cg.

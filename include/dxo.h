@@ -541,9 +541,15 @@ int dxo_tangent_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, const double* C_tang, dou
  * Any other pair, and the nonlinear kinds (C, I1, det F), return DXO_E_OPTION with a message in dxo_last_error. The quadrature weights
  * must be set (dxo_mesh_set_weights; DXO_E_OPTION otherwise). `out` is accumulated into, or SET with option "consumer_overwrite" = 1;
  * option "adjoint_atomics" as for dxo_tangent_apply (default: element vectors + node sums, bit-reproducible). The first call on a mesh
- * allocates the element-vector buffer; later calls allocate nothing (capture-safe). */
+ * allocates the element-vector buffer; later calls allocate nothing (capture-safe).
+ *   dxo_bilinear_apply_t  : out[dof] += sum_q w_q |det J_q| B_trial,q^T C_q^T B_test,q v, the action of the TRANSPOSED operator (adjoint
+ * solves). (test_kind, trial_kind), the C array and its layout [n][D_test][D_trial] are those of the forward call: the caller
+ * transposes nothing, the kernel reads t = C^T e from the same staged block. The pair table, the DEFGRAD rule, the checks and the
+ * options "consumer_overwrite" and "adjoint_atomics" are those of dxo_bilinear_apply; two-pass scatter, bit-reproducible. The diagonal
+ * of the transpose is the diagonal: dxo_bilinear_diagonal serves both. */
 int dxo_bilinear_apply(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, const double* v, double* out);
 int dxo_bilinear_diagonal(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, double* out);
+int dxo_bilinear_apply_t(dxo_ctx* ctx, dxo_mesh* mesh, int test_kind, int trial_kind, int bs, const double* C, const double* v, double* out);
 /* The same bilinear form ASSEMBLED into a sparse matrix on the device: what the demos hand to their LU solve,
  * assemble_matrix(J_replaced, bcs) (demo_plasticity_von_mises.py:422-434, demo_plasticity_mohr_coulomb.py:662-675,
  * demo_hyperelasticity.py:560-573; the heat demo compares assembled matrices, demo_nonlinear_heat_equation_part2.py:313-335).
@@ -576,6 +582,22 @@ int dxo_csr_dirichlet(dxo_ctx* ctx, dxo_csr* csr, const int32_t* dofs, int64_t n
  *                   read). A group of lanes owns one node and forms all bs rows of it, reading one column index per neighbouring node;
  *                   no atomics, bit-reproducible. Option "spmv_lanes": lanes per node (8, 16, 32, 64; default 0 = from the mean
  *                   neighbour count). Capture-safe.
+ * dxo_csr_transpose : values_t[(n,i),(m,j)] = values[(m,j),(n,i)] on the SAME pattern (csrc/transpose.hip): the pattern of
+ *                   dxo_csr_create is structurally symmetric, so the transposed matrix keeps the row pointers, columns, Dirichlet mask,
+ *                   block-Jacobi layout and multigrid symbolic phase, and only the values are permuted. Pure data movement: exact.
+ *                   values_t == values transposes in place (each off-diagonal block pair is exchanged by the one thread that owns the
+ *                   smaller node, a diagonal block is transposed by its own thread); any other overlap is the caller's error. One
+ *                   grid-stride kernel, deterministic. dxo_csr_dirichlet commutes with it (rows and columns are both zeroed).
+ * dxo_csr_spmv_t  : y = alpha A^T x + beta y without forming A^T (BLAS semantics: with beta == 0, y is not read), in the lane-group
+ *                   shape and with the option "spmv_lanes" of dxo_csr_spmv: a lane reads the mirrored block of each of its neighbour
+ *                   blocks in the rows of the neighbour and performs the fused multiply-adds of dxo_csr_spmv on the transposed values
+ *                   in the same order, so the result equals dxo_csr_spmv of dxo_csr_transpose's output bit for bit. No atomics.
+ *                   Both calls share the MIRROR MAP of the pattern (for block k of node n, the position of n among the blocks of the
+ *                   column node's row; uint16 per block), built on the device at the first of these calls on a pattern and kept in
+ *                   the dxo_csr: that first call allocates and synchronises once, later calls allocate and synchronise nothing
+ *                   (capture-safe). Patterns of dxo_csr_create (bs 1, 2, 3) only: a pattern without a mesh (a multigrid level)
+ *                   answers DXO_E_DIM, a pattern found not structurally symmetric DXO_E_OPTION with a message; NULL and alignment
+ *                   errors as dxo_csr_spmv.
  * dxo_csr_block_jacobi : inv[n_rows/bs][bs][bs] = the inverses of the bs x bs diagonal blocks (closed form, bs <= 3; bs = 1 is point
  *                   Jacobi). A Dirichlet row of dxo_csr_dirichlet keeps its block invertible. A block with |det| <= 1e-14 of the product
  *                   of its row norms gets a zero inverse and the call returns DXO_E_SINGULAR; it synchronises the stream once for that.
@@ -658,6 +680,8 @@ typedef struct dxo_krylov_info {
     double ms;                     /* wall time of the solve                              */
 } dxo_krylov_info;
 int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y);
+int dxo_csr_transpose(dxo_ctx* ctx, dxo_csr* csr, const double* values, double* values_t);
+int dxo_csr_spmv_t(dxo_ctx* ctx, dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y);
 int dxo_csr_block_jacobi(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double* inv);
 int dxo_block_jacobi_apply(dxo_ctx* ctx, int bs, int64_t n, const double* inv, const double* r, double* z);
 int dxo_krylov_create(dxo_ctx* ctx, int64_t n, int restart, dxo_krylov** out);
