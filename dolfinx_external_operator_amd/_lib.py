@@ -166,6 +166,7 @@ _SIGNATURES = {
     "dxo_mohr_coulomb_field": (C.c_int, [_P, C.POINTER(McParams), _P, C.c_int] + [_P] * 8),
     "dxo_icnn_field": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
     "dxo_isihara_field": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, C.c_int, _P, _P, _P]),
+    "dxo_isihara3_field": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, C.c_int, _P, _P, _P]),
     "dxo_conductivity": (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, C.c_int, _P, _P, _P]),
     "dxo_mc_summary": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "dxo_icnn_create": (C.c_int, [_P, C.POINTER(IcnnWeights), C.POINTER(_P)]),
@@ -252,6 +253,7 @@ _SIGNATURES = {
     "dxo_tangent_diagonal_vm": (C.c_int, [_P, _P, C.POINTER(VmParams), _P, _P, _P]),
     "dxo_heat_field": (C.c_int, [_P, C.c_double, C.c_double, _P, C.c_int, _P, _P, _P, _P]),
     "dxo_isihara": (C.c_int, [_P, C.POINTER(IsiharaParams), C.c_int64, C.c_int, _P, _P, _P]),
+    "dxo_isihara3": (C.c_int, [_P, C.POINTER(IsiharaParams), C.c_int64, C.c_int, _P, _P, _P]),
     "dxo_mgpu_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "dxo_mgpu_create_local": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "dxo_mgpu_von_mises_host": (C.c_int, [_P, C.POINTER(VmParams), C.c_int, C.c_int64] + [_P] * 6),
@@ -614,6 +616,11 @@ class Context:
         self.check(self.lib.dxo_isihara_field(self._h, C.byref(prm), mesh_handle, int(mem), _ptr(u), _ptr(dP), _ptr(P)),
                    "dxo_isihara_field")
 
+    def isihara3_field(self, prm: "IsiharaParams", mesh_handle, mem: int, u, dP, P) -> None:
+        """dxo_isihara3_field: F = I + grad u (3x3) of a gdim = 3 mesh -> dP[n][9][9], P[n][9]."""
+        self.check(self.lib.dxo_isihara3_field(self._h, C.byref(prm), mesh_handle, int(mem), _ptr(u), _ptr(dP), _ptr(P)),
+                   "dxo_isihara3_field")
+
     def conductivity(self, A: float, B: float, n: int, mem: int, T, k, dkdT) -> None:
         self.check(self.lib.dxo_conductivity(self._h, float(A), float(B), int(n), int(mem), _ptr(T), _ptr(k), _ptr(dkdT)),
                    "dxo_conductivity")
@@ -678,6 +685,11 @@ class Context:
     def isihara(self, prm: "IsiharaParams", n: int, mem: int, F, dP, P) -> None:
         rc = self.lib.dxo_isihara(self._h, C.byref(prm), int(n), int(mem), _ptr(F), _ptr(dP), _ptr(P))
         self.check(rc, "dxo_isihara")
+
+    def isihara3(self, prm: "IsiharaParams", n: int, mem: int, F, dP, P) -> None:
+        """dxo_isihara3: F[n][9] -> dP[n][9][9], P[n][9], the 3-D form of the energy."""
+        rc = self.lib.dxo_isihara3(self._h, C.byref(prm), int(n), int(mem), _ptr(F), _ptr(dP), _ptr(P))
+        self.check(rc, "dxo_isihara3")
 
     def assign(self, desc: "AssignDesc", flat_dofs, values, coeff, coeff_size: int) -> None:
         """Device pointers (ints) or objects with .ctypes — dxo_assign works on device memory only."""

@@ -787,15 +787,16 @@ def _mohr_coulomb_device(cx: Context, prm: McParams, deps, sigma_n, diagnostics:
     return C_tang, sigma                                             # :593
 
 
-def _P_device(cx: Context, Fvals, launch):
-    """Shared zero-copy wrapper of the two hyperelastic operators: F (.., 2, 2) CUDA tensor -> (dP, P) CUDA tensors."""
+def _P_device(cx: Context, Fvals, launch, d: int = 4):
+    """Shared zero-copy wrapper of the hyperelastic operators: F (.., 2, 2) CUDA tensor (d = 4; (.., 3, 3) with d = 9) -> (dP, P)
+    CUDA tensors."""
     torch = _torch_stream(cx, Fvals)
     if Fvals.dtype != torch.float64:
         raise TypeError(f"Fvals: operand arrays are fp64 (the network itself runs in fp32 or fp64), got {Fvals.dtype}")
-    F = Fvals.contiguous().reshape(-1, 4)                            # :452
+    F = Fvals.contiguous().reshape(-1, d)                            # :452
     n = F.shape[0]
-    dP = torch.empty(n * 16, dtype=torch.float64, device=F.device)
-    P = torch.empty(n * 4, dtype=torch.float64, device=F.device)
+    dP = torch.empty(n * d * d, dtype=torch.float64, device=F.device)
+    P = torch.empty(n * d, dtype=torch.float64, device=F.device)
     launch(n, F.data_ptr(), dP.data_ptr(), P.data_ptr())
     return dP, P                                                     # :456
 
@@ -856,7 +857,7 @@ def make_icnn(state_dict, *, precision: str = "fp32", ctx: Context | None = None
 
 
 def make_isihara(*, c1: float = 0.5, c2: float = 1.0, c3: float = 1.0, c4: float = 1.5, ctx: Context | None = None,
-                 device: int = 0, reuse_outputs: bool = False, outputs=None, device_outputs: str = "fresh") -> Callable:
+                 device: int = 0, reuse_outputs: bool = False, outputs=None, device_outputs: str = "fresh", dim: int = 2) -> Callable:
     """The analytic Isihara model behind the same `P_external` contract as `make_icnn`.
 
     The reference states it in UFL only (demo_hyperelasticity.py:686-703, `P = ufl.diff(W_Isihara, F_)`) and
@@ -868,17 +869,46 @@ def make_isihara(*, c1: float = 0.5, c2: float = 1.0, c3: float = 1.0, c4: float
     reference's callbacks return new arrays. "arena" (opt-in) — batches whose outputs exceed the arena's threshold are written
     into ONE persistent block of the library's output arena, chosen at the first such call by timing this kernel on the
     candidate blocks (the operator is HBM-bound: where its 160 bytes per point land decides 10-15 % of its rate); the returned
-    tensors then ALIAS across calls (the next call overwrites them) and may be chunk-backed memory that must not go to RCCL."""
+    tensors then ALIAS across calls (the next call overwrites them) and may be chunk-backed memory that must not go to RCCL.
+
+    dim = 3: the full 3-D form of the same energy (I1 = tr C, I2 = (I1^2 - tr C^2) / 2; dxo_isihara3) for `Fvals` (num_cells, nq, 3, 3)
+    (or anything reshaping to (-1, 9)): flat dP (n * 81, the [n][9][9] block of the ("grad", "grad", bs = 3) bilinear pair) and P (n * 9).
+    c3 = 0 is the compressible Mooney-Rivlin solid, c2 = c3 = 0 the neo-Hookean one. NumPy arrays, CUDA tensors and a lazy "F" operand of
+    a gdim = 3 mesh are taken (the lazy operand by the fused kernel, dxo_isihara3_field); the output arena is not available for dim = 3.
+    A lazy "F" operand of a mesh whose gdim differs from `dim` raises ValueError."""
     if device_outputs not in ("arena", "fresh"):
         raise ValueError('device_outputs must be "arena" or "fresh"')
+    if dim not in (2, 3):
+        raise ValueError("dim must be 2 (plane strain, F 2x2) or 3 (F 3x3)")
+    if dim == 3 and device_outputs == "arena":
+        raise ValueError('device_outputs = "arena" is not available for dim = 3')
     prm = IsiharaParams(float(c1), float(c2), float(c3), float(c4))
     holder = {"ctx": ctx, "out": None, "targets": outputs, "dev_out": None}
+
+    def dP_dF_3d(Fvals):
+        cx = holder["ctx"]
+        if _is_device_tensor(Fvals):
+            return _P_device(cx, Fvals, lambda n, F, dP, P: cx.isihara3(prm, n, MEM_DEVICE, F, dP, P), 9)
+        if isinstance(Fvals, LazyOperand) and Fvals.kind == "F" and Fvals.mesh.ctx is cx:
+            n = Fvals.shape[0] * Fvals.shape[1]      # F = I + grad u formed in the registers of the kernel (dxo_isihara3_field)
+            dP, P = holder["out"].get("dP", n * 81), holder["out"].get("P", n * 9)
+            cx.isihara3_field(prm, Fvals.mesh._h, MEM_HOST, Fvals.u, dP, P)
+            return dP.reshape(-1), P.reshape(-1)
+        F = _as_f64_host(Fvals, "Fvals").reshape(-1, 9)
+        n = F.shape[0]
+        dP, P = holder["out"].get("dP", n * 81), holder["out"].get("P", n * 9)
+        cx.isihara3(prm, n, MEM_HOST, F, dP, P)
+        return _like(Fvals, dP.reshape(-1), P.reshape(-1))
 
     def dP_dF_impl(Fvals):
         if holder["ctx"] is None:
             holder["ctx"] = default_context(device)
         if holder["out"] is None:
             holder["out"] = _Outputs(holder["ctx"], reuse_outputs, dict(zip(("dP", "P"), holder["targets"])) if holder["targets"] is not None else None)
+        if isinstance(Fvals, LazyOperand) and Fvals.kind == "F" and Fvals.mesh.gdim != dim:
+            raise ValueError(f"make_isihara(dim={dim}): the operand is the deformation gradient of a gdim = {Fvals.mesh.gdim} mesh")
+        if dim == 3:
+            return dP_dF_3d(Fvals)
         if _is_device_tensor(Fvals):
             cx = holder["ctx"]
             launch = lambda n, F, dP, P: cx.isihara(prm, n, MEM_DEVICE, F, dP, P)   # noqa: E731

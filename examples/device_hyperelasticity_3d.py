@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""A finite-strain Newton solve in three dimensions in which quadrature data never leaves the GPU: a unit cube of the Isihara solid,
+clamped at the bottom, compressed and twisted at the top. The 3-D counterpart of examples/device_hyperelasticity.py.
+
+Per Newton iteration:
+
+    dP, P = Isihara(I + grad u)                  dxo_isihara3_field (operand and model in one launch, fp64; F is 3x3, dP [n][9][9])
+    R = sum w|J| grad(v) : P  on the free dofs   dxo_operand_adjoint, kind "F", bs = 3
+    assembled (the default):
+      J = (grad, grad) form with dP              dxo_bilinear_assemble on the CSR pattern of the mesh, Dirichlet rows and columns
+      M = smoothed-aggregation multigrid         DeviceCSR.amg(near_nullspace = the six rigid-body modes); symbolic phase once
+      solve J d = -R                             cg (or gmres)
+    --matrix-free:
+      K v: dxo_bilinear_apply("grad", "grad", 3, dP), diag(K): dxo_bilinear_diagonal, Jacobi-preconditioned cg
+    u += d
+Only dof vectors are touched outside the kernels; they are torch CUDA tensors.
+
+Mesh: P2 tetrahedra with the 4-point rule (the default), or --hex: Q2 hexahedra with the 27-point Gauss rule (the 8-point rule
+under-integrates the Q2 stiffness matrix: it is singular). Load: the top face moves down by `compress` and turns about
+the cube's axis by `twist` radians, both reached over `steps` equal load steps; a step's predictor moves every node by the
+homogeneous field that meets both faces. The model is fp64 and the tangent exact, so Newton converges quadratically.
+Needs an MI355X.    python3 examples/device_hyperelasticity_3d.py [--n 6] [--hex] [--matrix-free] [--solver cg|gmres]
+"""
+import argparse
+import pathlib
+import sys
+import time
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from dolfinx_external_operator_amd import MEM_DEVICE, Context, DeviceMesh, IsiharaParams, cg, gmres, rigid_body_modes  # noqa: E402
+from tools.synthetic import gauss_tensor_rule, structured_mesh, with_rule  # noqa: E402
+
+MAX_NEWTON = 20      # a load step that needs more has failed
+
+
+def predictor(x: np.ndarray, compress: float, twist: float) -> np.ndarray:
+    """u(x) of the homogeneous compression and twist: the section at height z moves down by compress * z and turns by twist * z"""
+    ang = twist * x[:, 2]
+    dx, dy = x[:, 0] - 0.5, x[:, 1] - 0.5
+    u = np.zeros_like(x)
+    u[:, 0] = np.cos(ang) * dx - np.sin(ang) * dy - dx
+    u[:, 1] = np.sin(ang) * dx + np.cos(ang) * dy - dy
+    u[:, 2] = -compress * x[:, 2]
+    return u
+
+
+def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float = 0.4, hexahedra: bool = False, matrix_free: bool = False,
+         solver: str = "cg", verbose: bool = True, c=(0.5, 1.0, 1.0, 1.5)) -> dict:
+    """Returns the per-step Newton residual histories, the linear iteration counts and the final displacement (`u`, host array).
+    Raises RuntimeError if a load step does not converge within MAX_NEWTON iterations or a linear solve fails."""
+    dev = torch.device("cuda:0")
+    ctx = Context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    ctx.set_option("consumer_overwrite", 1)      # residual / matvec / diagonal / assembly calls SET their output
+    if hexahedra:
+        mesh = structured_mesh("hexahedron", (n_side,) * 3, degree=2)
+        mesh = with_rule(mesh, *gauss_tensor_rule("hexahedron", 3))
+    else:
+        mesh = structured_mesh("tetrahedron", (n_side,) * 3, degree=2)
+    dm = DeviceMesh.from_synthetic(mesh, ctx=ctx)
+    prm = IsiharaParams(*c)
+    G = 3
+    x = mesh.node_x
+    nn, npts = x.shape[0], mesh.num_cells * mesh.nq
+    bottom, top = x[:, 2] < 1e-12, x[:, 2] > 1 - 1e-12
+    fixed = np.zeros((nn, G), dtype=bool)
+    fixed[bottom] = True
+    fixed[top] = True
+    free = torch.from_numpy(~fixed.reshape(-1)).to(dev)
+    bcs = torch.from_numpy(np.flatnonzero(fixed.reshape(-1)).astype(np.int32)).to(dev)
+
+    f64 = dict(dtype=torch.float64, device=dev)
+    u = torch.zeros(nn * G, **f64)
+    dP, P = torch.zeros(npts * 81, **f64), torch.zeros(npts * 9, **f64)
+    R, Kv, diag = (torch.zeros(nn * G, **f64) for _ in range(3))
+    state = {}
+    krylov = {"cg": cg, "gmres": gmres}[solver]
+
+    def residual():
+        """(dP, P) at the current u and the assembled inner(grad v, P) dx on the free dofs"""
+        ctx.isihara3_field(prm, dm._h, MEM_DEVICE, u.data_ptr(), dP.data_ptr(), P.data_ptr())
+        dm.adjoint("F", G, P.data_ptr(), R.data_ptr())
+        return torch.where(free, R, torch.zeros_like(R))
+
+    def solve_assembled(b):
+        if "pattern" not in state:
+            state["pattern"] = dm.csr_pattern(G)
+            state["values"] = torch.zeros(state["pattern"].nnz, **f64)
+        A = dm.bilinear_assemble("grad", "grad", G, dP.data_ptr(), state["pattern"], values=state["values"], bcs=bcs, diagonal=1.0)
+        if "amg" not in state:
+            state["amg"] = A.amg(bcs, near_nullspace=rigid_body_modes(x, ctx=ctx))
+        else:
+            state["amg"].setup(A)
+        return krylov(A, b, M=state["amg"], rtol=1e-12, maxiter=400)
+
+    def jacobian_times(v, out):
+        """out = K v with the Dirichlet rows and columns of the assembled form: identity on the fixed dofs"""
+        vm = torch.where(free, v, torch.zeros_like(v))
+        dm.bilinear_apply("grad", "grad", G, dP.data_ptr(), vm.data_ptr(), Kv.data_ptr())
+        out.copy_(torch.where(free, Kv, v))
+
+    def solve_matrix_free(b):
+        dm.bilinear_diagonal("grad", "grad", G, dP.data_ptr(), diag.data_ptr())
+        minv = torch.where(free, 1.0 / diag, torch.ones_like(diag))
+        return krylov(jacobian_times, b, M=minv, rtol=1e-12, maxiter=20000, ctx=ctx)
+
+    report = {"cells": mesh.num_cells, "points": npts, "dofs": nn * G, "matrix_free": matrix_free, "solver": solver, "steps": []}
+    prev = np.zeros_like(x)
+    for k in range(1, steps + 1):
+        lam = k / steps
+        now = predictor(x, lam * compress, lam * twist)
+        u += torch.from_numpy((now - prev).reshape(-1)).to(dev)
+        prev = now
+        history, lin_its, t0 = [], [], time.perf_counter()
+        while True:
+            res = residual()
+            rn = float(torch.linalg.norm(res))
+            history.append(rn)
+            if not np.isfinite(rn):
+                raise RuntimeError(f"load step {k}: the residual is not finite (det F <= 0 at a quadrature point)")
+            if rn <= 1e-10 * history[0]:
+                break
+            if len(history) > MAX_NEWTON:
+                raise RuntimeError(f"load step {k} did not converge in {MAX_NEWTON} Newton iterations: |R| = " + " ".join(f"{r:.2e}" for r in history))
+            sol = (solve_matrix_free if matrix_free else solve_assembled)(-res)
+            if not sol.converged:
+                raise RuntimeError(f"load step {k}, Newton iteration {len(history)}: the linear solve did not converge "
+                                   f"({sol.iterations} iterations, relative residual {sol.residual:.2e})")
+            lin_its.append(sol.iterations)
+            u += sol.x
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        report["steps"].append({"load": lam, "newton_residuals": history, "linear_iterations": lin_its, "seconds": dt})
+        if verbose:
+            print(f"load {lam:.3f}: {len(history) - 1} Newton its, residuals " + " ".join(f"{r:.2e}" for r in history)
+                  + f", {solver} its {lin_its}, {dt * 1e3:.0f} ms")
+    report["u"] = u.cpu().numpy()
+    dm.close()
+    ctx.close()
+    return report
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--n", type=int, default=6, help="cells per side")
+    ap.add_argument("--steps", type=int, default=3, help="load steps")
+    ap.add_argument("--hex", action="store_true", help="Q2 hexahedra with the 27-point rule instead of P2 tetrahedra")
+    ap.add_argument("--matrix-free", action="store_true", help="Jacobi-preconditioned Krylov solve on bilinear_apply, nothing assembled")
+    ap.add_argument("--solver", choices=["cg", "gmres"], default="cg")
+    a = ap.parse_args()
+    main(a.n, steps=a.steps, hexahedra=a.hex, matrix_free=a.matrix_free, solver=a.solver)

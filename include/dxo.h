@@ -1084,6 +1084,20 @@ int dxo_icnn_field(dxo_ctx* ctx, const dxo_icnn* model, int precision, dxo_mesh*
 int dxo_isihara_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, int mem, const double* u,
                       double* dP, double* P);
 
+/* The analytic Isihara energy for a 3x3 deformation gradient, the full 3-D form of dxo_isihara's:
+ *   W = c1 (I1bar-3) + c2 (I2bar-3) + c3 (I1bar-3)^2 + c4 (J-1)^2,  I1bar = J^(-2/3) I1, I2bar = J^(-4/3) I2,
+ *   I1 = tr C, I2 = (I1^2 - tr C^2) / 2, C = F^T F, J = det F
+ * (for F = [[F_2, 0], [0, 1]] its in-plane stress and tangent are dxo_isihara's). c3 = 0 is the compressible Mooney-Rivlin solid,
+ * c2 = c3 = 0 the neo-Hookean one. F[n][9] row-major (F_ia at 3 i + a) -> dP[n][9][9] (dP_i/dF_j, symmetric: a Hessian), P[n][9],
+ * fp64 throughout; det F <= 0 -> NaN in all 90 outputs of the point. dP is the [n][9][9] block of the ("grad", "grad", bs = 3)
+ * bilinear pair and P the operand of the internal force. Checks and error codes as dxo_isihara; device arrays 16-byte aligned.
+ *   dxo_isihara3_field   F = I + grad u formed in the registers of the same kernel from the dof vector u (num_field_nodes*3 doubles)
+ *                        of a gdim = 3 mesh (DXO_E_DIM otherwise); any element dxo_mesh_create accepts. Checks as dxo_isihara_field. */
+int dxo_isihara3(dxo_ctx* ctx, const dxo_isihara_params* prm, int64_t n, int mem,
+                 const double* F, double* dP, double* P);
+int dxo_isihara3_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, int mem, const double* u,
+                       double* dP, double* P);
+
 /* ---- multi-GPU: cell-block sharding + RCCL all-gather inside the library (BASELINE north_star) ----
  * The reference splits only by MPI mesh partition and never gathers quadrature data
  * (src/dolfinx_external_operator/external_operator.py:365-371, 445). Here ONE coefficient vector's quadrature points
