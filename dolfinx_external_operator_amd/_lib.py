@@ -173,6 +173,9 @@ _SIGNATURES = {
     "dxo_icnn_destroy": (C.c_int, [_P, _P]),
     "dxo_icnn_correction": (C.c_int, [_P, _P, _P]),
     "dxo_icnn_eval": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P]),
+    "dxo_icnn3_eval": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P]),
+    "dxo_icnn3_field": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "dxo_icnn3_correction": (C.c_int, [_P, _P, _P]),
     "dxo_mesh_create": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "dxo_mesh_destroy": (C.c_int, [_P, _P]),
     "dxo_operand_value_size": (C.c_int, [C.c_int, C.c_int, C.c_int]),
@@ -681,6 +684,21 @@ class Context:
     def icnn_eval(self, model: int, precision: int, n: int, mem: int, F, dP, P) -> None:
         rc = self.lib.dxo_icnn_eval(self._h, _P(model), int(precision), int(n), int(mem), _ptr(F), _ptr(dP), _ptr(P))
         self.check(rc, "dxo_icnn_eval")
+
+    def icnn3_eval(self, model: int, precision: int, n: int, mem: int, F, dP, P) -> None:
+        """dxo_icnn3_eval: F[n][9] -> dP[n][9][9], P[n][9], the network on the invariants of a 3x3 F."""
+        rc = self.lib.dxo_icnn3_eval(self._h, _P(model), int(precision), int(n), int(mem), _ptr(F), _ptr(dP), _ptr(P))
+        self.check(rc, "dxo_icnn3_eval")
+
+    def icnn3_field(self, model: int, precision: int, mesh_handle, mem: int, u, dP, P) -> None:
+        """dxo_icnn3_field: F = I + grad u (3x3) of a gdim = 3 mesh, then the network kernel."""
+        self.check(self.lib.dxo_icnn3_field(self._h, _P(model), int(precision), mesh_handle, int(mem), _ptr(u), _ptr(dP), _ptr(P)),
+                   "dxo_icnn3_field")
+
+    def icnn3_correction(self, model: int) -> np.ndarray:
+        out = np.empty(9)
+        self.check(self.lib.dxo_icnn3_correction(self._h, _P(model), _ptr(out)), "dxo_icnn3_correction")
+        return out
 
     def isihara(self, prm: "IsiharaParams", n: int, mem: int, F, dP, P) -> None:
         rc = self.lib.dxo_isihara(self._h, C.byref(prm), int(n), int(mem), _ptr(F), _ptr(dP), _ptr(P))

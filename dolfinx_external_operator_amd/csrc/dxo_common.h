@@ -82,6 +82,7 @@ struct dxo_ctx {
     int64_t mc_variant = 2;             // 0: lane = point; 1: classify + compacted Newton with lane refill (two kernels); 2: both in one persistent kernel
     int64_t mc_blocks_per_cu = 3;       // persistent Newton workgroups per CU (2: 1.39 ms, 3: 1.36, 4: 1.36 at 10^7 points)
     int64_t icnn_variant = 2;           // fp32 network: 0 VALU lane-per-point kernel; wave-per-64-points MFMA kernels: 1 fp32-input MFMA, 2 split-bf16 MFMA
+    int64_t icnn3_store = 0;            // 3-D default network kernel: 0 every lane stores its own 648-byte row (3.8 ms per 10^7 points), 1 outputs staged through LDS in output order (4.2 ms)
     int64_t adjoint_cell = 1;           // virtual work of eps on the standard elements: lane = cell kernel (0: wave-group kernel)
     int64_t operand_cell = 1;           // dxo_eval_operand, eps on the 2-D standard elements: lane = cell kernel (operand_cell.h); 0: wave-group kernel
     int64_t vm_residual_fused = 0;      // dxo_von_mises_residual on Q2 hexahedra: 1 = one kernel (stress scattered from registers, cell8_mfma.h; round 5: 1.11 against
@@ -261,6 +262,8 @@ int dxo_mc_launch_device(dxo_ctx* ctx, const dxo_mc_params* prm, int64_t n, cons
                          hipStream_t s);
 int dxo_icnn_launch_device(dxo_ctx* ctx, const dxo_icnn* m, int precision, int64_t n, const double* F, double* dP, double* P,
                            hipStream_t s);
+int dxo_icnn3_launch_device(dxo_ctx* ctx, const dxo_icnn* m, int precision, int64_t n, const double* F, double* dP, double* P,
+                            hipStream_t s);
 int dxo_isihara_launch_device(dxo_ctx* ctx, const dxo_isihara_params* prm, int64_t n, const double* F, double* dP, double* P,
                               hipStream_t s);
 // vm_field.hip: fused strain + return map + element vectors of the returned stress (fe[node][cell][i]) — dxo_von_mises_residual

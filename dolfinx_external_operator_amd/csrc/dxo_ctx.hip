@@ -173,6 +173,7 @@ static int64_t* option_slot(dxo_ctx* c, const char* key) {
     if (!std::strcmp(key, "mc_blocks_per_cu")) return &c->mc_blocks_per_cu;
     if (!std::strcmp(key, "mc_waves_per_simd")) return &c->mc_waves_per_simd;
     if (!std::strcmp(key, "icnn_variant")) return &c->icnn_variant;
+    if (!std::strcmp(key, "icnn3_store")) return &c->icnn3_store;
     if (!std::strcmp(key, "adjoint_atomics")) return &c->adjoint_atomics;
     if (!std::strcmp(key, "assemble_chunk_cells")) return &c->assemble_chunk_cells;
     if (!std::strcmp(key, "krylov_reorth")) return &c->krylov_reorth;
@@ -220,6 +221,7 @@ int dxo_ctx_set_option(dxo_ctx* c, const char* key, int64_t value) {
     if (value < 0) return dxo_fail(c, DXO_E_OPTION, "option value must be >= 0");
     if (slot == &c->icnn_variant && value > dxo_icnn_variant_max())
         return dxo_fail(c, DXO_E_OPTION, "icnn_variant: 0 (VALU), 1 (fp32 MFMA), 2 (split-bf16 MFMA); 3 and 4 exist only in a -DDXO_EXPERIMENTS build (scripts/exp/icnn_variants.h)");
+    if (slot == &c->icnn3_store && value > 1) return dxo_fail(c, DXO_E_OPTION, "icnn3_store: 0 (one row per lane) or 1 (staged through LDS, output order)");
     if (slot == &c->adjoint_patch && value != 0 && !dxo_adjoint_patch_available())
         return dxo_fail(c, DXO_E_OPTION, "adjoint_patch: the patch form exists only in a -DDXO_EXPERIMENTS build (scripts/exp/adjoint_patch.h)");
     if (slot == &c->assign_plan_form && value > 2) return dxo_fail(c, DXO_E_OPTION, "assign_plan_form: 0 (both, the first apply chooses), 1 (dof order), 2 (source order)");

@@ -108,13 +108,14 @@ struct FieldOp {
     int64_t next_cell = 0;
     // the consumer: (ctx, staged operand, n points, chunk inputs, chunk outputs, stream)
     std::function<int(dxo_ctx*, const double*, int64_t, void* const*, void* const*, hipStream_t)> consume;
+    int width = 4;          // doubles of the staged operand per point (9: the 3x3 F of a gdim = 3 mesh)
 };
 
 int field_op_launch(dxo_ctx* ctx, FieldOp& L, int64_t cell0, int64_t n_cells, void* const* d_in, void* const* d_out, hipStream_t s) {
     if (n_cells == 0) return DXO_OK;
     const int nq = L.mesh->dev.nq;
     const int64_t n = n_cells * nq;
-    double* stage = static_cast<double*>(dxo_stage(ctx, s, (size_t)n * 4 * sizeof(double)));
+    double* stage = static_cast<double*>(dxo_stage(ctx, s, (size_t)n * L.width * sizeof(double)));
     if (!stage) return dxo_hip_fail(ctx, hipErrorOutOfMemory, "field operator: staging buffer");
     int rc = dxo_operand_launch_range(ctx, L.mesh, L.kind, L.mesh->gdim, L.d_u, cell0, n_cells, stage, s);
     if (rc != DXO_OK) return dxo_fail(ctx, rc, "field operator: operand kernel");
@@ -212,6 +213,33 @@ extern "C" int dxo_icnn_field(dxo_ctx* ctx, const dxo_icnn* model, int precision
     const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
     std::vector<dxo_span> in;
     std::vector<dxo_span> out = {{nullptr, dP, 16 * sd}, {nullptr, P, 4 * sd}};
+    void* dout[2] = {dP, P};
+    return run_field_op(ctx, L, mem, u, in, out, nullptr, dout);
+}
+
+// the 3-D network operator: F = I + grad u (3x3) of a gdim = 3 mesh into the staging buffer, then dxo_icnn3_eval's kernel
+extern "C" int dxo_icnn3_field(dxo_ctx* ctx, const dxo_icnn* model, int precision, dxo_mesh* mesh, int mem, const double* u,
+                               double* dP, double* P) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!model) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_field: model is NULL");
+    if (!mesh) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_field: mesh is NULL");
+    if (mesh->gdim != 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_icnn3_field: F is 3x3, the mesh must have gdim = 3");
+    if (precision != 0 && precision != 1) return dxo_fail(ctx, DXO_E_OPTION, "dxo_icnn3_field: precision must be 0 (fp32 network) or 1 (fp64)");
+    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_icnn3_field: bad mem");
+    if (mesh->num_cells == 0) return DXO_OK;
+    if (!u || !dP || !P) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_field: NULL array");
+    const uintptr_t all = (uintptr_t)u | (uintptr_t)dP | (uintptr_t)P;
+    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn3_field: arrays must be 8-byte aligned");
+    if (mem == DXO_MEM_DEVICE && (((uintptr_t)dP | (uintptr_t)P) & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn3_field: device dP, P must be 16-byte aligned");
+    FieldOp L{mesh, nullptr, DXO_OPERAND_DEFGRAD};
+    L.width = 9;
+    L.consume = [model, precision](dxo_ctx* c, const double* F, int64_t n, void* const*, void* const* d_out, hipStream_t s) {
+        return dxo_icnn3_launch_device(c, model, precision, n, F, (double*)d_out[0], (double*)d_out[1], s);
+    };
+    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
+    std::vector<dxo_span> in;
+    std::vector<dxo_span> out = {{nullptr, dP, 81 * sd}, {nullptr, P, 9 * sd}};
     void* dout[2] = {dP, P};
     return run_field_op(ctx, L, mem, u, in, out, nullptr, dout);
 }

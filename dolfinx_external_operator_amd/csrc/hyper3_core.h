@@ -110,6 +110,118 @@ __device__ __forceinline__ void isihara3_tangent(const Isi3Point& q, double (&H)
         }
 }
 
+// ---- the general form: W any function of (t, s, D), given by its nine partials at the point (the network of icnn.hip, whose feature
+// K2 is linear in s and whose Hessian couples all three features, so W_ts and W_ss do not vanish):
+//   P_I  = 2 W_t F_I + W_s gs_I + W_D gD_I
+//   H_IJ = 2 W_t d_IJ + W_s d2s + W_D d2D + 4 W_tt F_I F_J + 2 W_ts (F_I gs_J + gs_I F_J) + 2 W_tD (F_I gD_J + gD_I F_J)
+//          + W_ss gs_I gs_J + W_sD (gs_I gD_J + gD_I gs_J) + W_DD gD_I gD_J.
+// A stress correction P += h F, H_IJ += h d_IJ (a multiple of the identity) rides in 2 W_t.
+struct Hyper3W { double t, s, D, tt, ts, tD, ss, sD, DD; };
+
+// t = F:F, s = C:C, D = det F
+__device__ __forceinline__ void hyper3_generators(const double (&F)[9], double& t, double& s, double& D) {
+    double C[6];   // 00 01 02 11 12 22
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) C[k++] = F[a] * F[b] + F[3 + a] * F[3 + b] + F[6 + a] * F[6 + b];
+    t = C[0] + C[3] + C[5];
+    s = C[0] * C[0] + C[3] * C[3] + C[5] * C[5] + 2.0 * (C[1] * C[1] + C[2] * C[2] + C[4] * C[4]);
+    D = F[0] * (F[4] * F[8] - F[5] * F[7]) + F[1] * (F[5] * F[6] - F[3] * F[8]) + F[2] * (F[3] * F[7] - F[4] * F[6]);
+}
+
+struct Gen3Point {
+    double F[9], gs[9], gD[9];
+    double Wt2, Ws4, WD, Wtt4, Wts2, WtD2, Wss, WsD, WDD;
+};
+
+__device__ __forceinline__ void hyper3_general_stress(const Hyper3W& w, double h, const double (&F)[9], Gen3Point& q, double (&P)[9]) {
+    double C[3][3];   // F^T F
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) C[a][b] = C[b][a] = F[a] * F[b] + F[3 + a] * F[3 + b] + F[6 + a] * F[6 + b];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int b = (a + 1) % 3, c = (a + 2) % 3;
+            q.F[3 * i + a] = F[3 * i + a];
+            q.gs[3 * i + a] = 4.0 * (F[3 * i] * C[0][a] + F[3 * i + 1] * C[1][a] + F[3 * i + 2] * C[2][a]);
+            q.gD[3 * i + a] = F[3 * j + b] * F[3 * k + c] - F[3 * j + c] * F[3 * k + b];
+        }
+    }
+    q.Wt2 = 2.0 * w.t + h;
+    q.Ws4 = 4.0 * w.s;
+    q.WD = w.D;
+    q.Wtt4 = 4.0 * w.tt;
+    q.Wts2 = 2.0 * w.ts;
+    q.WtD2 = 2.0 * w.tD;
+    q.Wss = w.ss;
+    q.WsD = w.sD;
+    q.WDD = w.DD;
+#pragma unroll
+    for (int I = 0; I < 9; ++I) P[I] = q.Wt2 * F[I] + w.s * q.gs[I] + q.WD * q.gD[I];
+}
+
+// 4 W_s C_ab and 4 W_s (F F^T)_ab, the six unique entries of each (00 01 02 11 12 22): the d_ij C_ab and (F F^T)_ij d_ab terms of d2s
+struct Gen3Sums { double c[6], g[6]; };
+__host__ __device__ constexpr int hyper3_sym3(int a, int b) { return a <= b ? a * 3 - a * (a - 1) / 2 + (b - a) : hyper3_sym3(b, a); }
+
+__device__ __forceinline__ void hyper3_general_sums(const Gen3Point& q, Gen3Sums& m) {
+    const double (&f)[9] = q.F;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) {
+            m.c[hyper3_sym3(a, b)] = q.Ws4 * (f[a] * f[b] + f[3 + a] * f[3 + b] + f[6 + a] * f[6 + b]);
+            m.g[hyper3_sym3(a, b)] = q.Ws4 * (f[3 * a] * f[3 * b] + f[3 * a + 1] * f[3 * b + 1] + f[3 * a + 2] * f[3 * b + 2]);
+        }
+}
+
+// entry (I, J), I <= J, of the general tangent
+__device__ __forceinline__ double hyper3_general_entry(const Gen3Point& q, const Gen3Sums& m, int I, int J) {
+    const int i = I / 3, a = I % 3, j = J / 3, b = J % 3;
+    const double FI = q.F[I], FJ = q.F[J], sI = q.gs[I], sJ = q.gs[J], dI = q.gD[I], dJ = q.gD[J];
+    double h = fma(q.Wtt4, FI * FJ,
+                   fma(q.Wts2, fma(FI, sJ, sI * FJ),
+                       fma(q.WtD2, fma(FI, dJ, dI * FJ),
+                           fma(q.Wss, sI * sJ,
+                               fma(q.WsD, fma(sI, dJ, dI * sJ), fma(q.WDD, dI * dJ, q.Ws4 * (q.F[3 * i + b] * q.F[3 * j + a])))))));
+    if (I == J) h += q.Wt2;
+    if (i != j && a != b) h = fma(q.WD * (double)(hyper3_eps(i, j, 3 - i - j) * hyper3_eps(a, b, 3 - a - b)), q.F[3 * (3 - i - j) + (3 - a - b)], h);
+    if (i == j) h += m.c[hyper3_sym3(a, b)];
+    if (a == b) h += m.g[hyper3_sym3(i, j)];
+    return h;
+}
+
+// the 45 unique entries (for the staged stores of hyper3_store_tangent)
+__device__ __forceinline__ void hyper3_general_tangent(const Gen3Point& q, double (&H)[HYPER3_SYM]) {
+    Gen3Sums m;
+    hyper3_general_sums(q, m);
+#pragma unroll
+    for (int I = 0; I < 9; ++I)
+#pragma unroll
+        for (int J = I; J < 9; ++J) H[hyper3_tri(I, J)] = hyper3_general_entry(q, m, I, J);
+}
+
+// the same entries, each stored to both of its places in the point's own row dPp[81] the moment it exists: nothing but the point's 27
+// doubles, its coefficients and the twelve sums waits in registers
+__device__ __forceinline__ void hyper3_general_tangent_rows(const Gen3Point& q, double* __restrict__ dPp) {
+    Gen3Sums m;
+    hyper3_general_sums(q, m);
+#pragma unroll
+    for (int I = 0; I < 9; ++I)
+#pragma unroll
+        for (int J = I; J < 9; ++J) {
+            const double h = hyper3_general_entry(q, m, I, J);
+            dPp[I * 9 + J] = h;
+            if (J != I) dPp[J * 9 + I] = h;
+        }
+}
+
 // ---- output-ordered stores. A point's tangent is 81 doubles and its stress 9, both odd: a run of points starts 16-byte aligned only
 // at an even point and ends on a single double when it holds an odd number of them. The wave stages a run in its LDS buffer X at the
 // PARITY of the run's global address (in doubles), so a pair of doubles that is 16-byte aligned in memory is 16-byte aligned in LDS
@@ -153,6 +265,25 @@ __device__ __forceinline__ void hyper3_store_stress(double* X, int lane, int npt
     op_fence();
     hyper3_store_run<NT>(X, P, npts * 9, lane);
     op_fence();
+}
+
+// the stresses in passes of pp points, for a buffer X smaller than a whole wave's (at least pp * 9 + 2 doubles)
+template <bool NT>
+__device__ __forceinline__ void hyper3_store_stress_passes(double* X, int pp, int lane, int npts, const double (&Pv)[9],
+                                                           double* __restrict__ P) {
+    for (int q0 = 0; q0 < npts; q0 += pp) {
+        const int nrun = npts - q0 < pp ? npts - q0 : pp;
+        double* g = P + (int64_t)q0 * 9;
+        const int r = lane - q0;
+        if (r >= 0 && r < nrun) {
+            double* Xr = X + hyper3_parity(g) + r * 9;
+#pragma unroll
+            for (int I = 0; I < 9; ++I) Xr[I] = Pv[I];
+        }
+        op_fence();
+        hyper3_store_run<NT>(X, g, nrun * 9, lane);
+        op_fence();
+    }
 }
 
 template <bool NT>

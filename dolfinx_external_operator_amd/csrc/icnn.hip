@@ -25,10 +25,15 @@
 //   1            icnn_mfma_f32: the same GEMMs on v_mfma_f32_32x32x2_f32 (exact fp32; 4.1 ms, 0.62 of that pipe's peak); cross-check
 //   0            icnn_point: lane per point on the vector pipe, weights through the scalar path (s_load into SGPRs); the
 //                fp64-network path of BASELINE config 5's tolerance study and the cross-check of both MFMA kernels
+//
+// 3-D (dxo_icnn3_eval, DIM = 3 of the same three kernels): the same network on the invariants of a full 3x3 F. Only what comes before
+// the network (9 doubles in, 3 features out) and after it (P[9], dP[81] out, through the general form of hyper3_core.h) differs; see
+// icnn3_features / icnn3_partials below and DESIGN.md 8. 792 B/point: 3.8 ms per 10^7 points against 2.7 for the 2-D kernel.
 #include <cmath>
 
 #include "dxo_common.h"
 #include "hyper_core.h"
+#include "hyper3_core.h"
 
 namespace {
 
@@ -52,6 +57,7 @@ struct dxo_icnn_impl {
     void* dev = nullptr;  // one slab holding both precisions
     IcnnDev<float> f32;
     IcnnDev<double> f64;
+    double H3 = 0.0;      // 3-D: the correction is H = H3 I (analytically zero: K1, K2, K3 are stationary at F = I)
 };
 
 template <typename T> __device__ __forceinline__ T t_exp(T x);
@@ -81,11 +87,95 @@ struct IcnnSmall {  // by-value kernel argument: lands in SGPRs
     double H[4];
 };
 
+// ------------------------------------------------------------------ 3-D: the same network on the invariants of a full 3x3 F
+// I1 = t, I2 = (t^2 - s) / 2, I3 = D^2 with the generators t = F:F, s = C:C, D = det F of hyper3_core.h and m = |D|^(-2/3):
+//   K1 = m t - 3,  K2 = m^2 (t^2 - s) / 2 - 3,  K3 = (|D| - 1)^2
+// (for F = [[F_2, 0], [0, 1]] these are the plane-strain statements of :263-283). |D| and its sign as in 2-D: det F < 0 is finite.
+__device__ __forceinline__ void icnn3_features(const double (&F)[9], double (&K)[3]) {
+    double t, s, D;
+    hyper3_generators(F, t, s, D);
+    const double aD = fabs(D);
+    const double m = hyper_pow_m23(aD), nn = m * m;
+    K[0] = m * t - 3.0; K[1] = 0.5 * nn * (t * t - s) - 3.0; K[2] = (aD - 1.0) * (aD - 1.0);
+}
+
+// chain rule to the generators: W_a = sum_k g_k K_k,a, W_ab = sum_k g_k K_k,ab + sum_kl hx_kl K_k,a K_l,b for a, b in {t, s, D};
+// g = grad_x y, hx = hess_x y packed (00, 01, 02, 11, 12, 22). The partials of K that do not vanish:
+//   K1: _t = m, _D = -2/3 m t / D, _tD = -2/3 m / D, _DD = 10/9 m t / D^2
+//   K2 (q = t^2 - s): _t = nn t, _s = -nn / 2, _D = -2/3 nn q / D, _tt = nn, _tD = -4/3 nn t / D, _sD = 2/3 nn / D, _DD = 14/9 nn q / D^2
+//   K3: _D = 2 (|D| - 1) sign D, _DD = 2
+template <typename T>
+__device__ __forceinline__ void icnn3_partials(const double (&F)[9], const T* g, const T* hx, Hyper3W& w) {
+    double t, s, D;
+    hyper3_generators(F, t, s, D);
+    const double aD = fabs(D), sg = D < 0.0 ? -1.0 : 1.0, iD = 1.0 / D;
+    const double m = hyper_pow_m23(aD), nn = m * m, q = t * t - s;
+    const double K1t = m, K1D = (-2.0 / 3.0) * m * t * iD;
+    const double K2t = nn * t, K2s = -0.5 * nn, K2D = (-2.0 / 3.0) * nn * q * iD;
+    const double K3D = 2.0 * (aD - 1.0) * sg;
+    const double g0 = (double)g[0], g1 = (double)g[1], g2 = (double)g[2];
+    const double h00 = (double)hx[0], h01 = (double)hx[1], h02 = (double)hx[2], h11 = (double)hx[3], h12 = (double)hx[4], h22 = (double)hx[5];
+    const double ut0 = h00 * K1t + h01 * K2t, ut1 = h01 * K1t + h11 * K2t, ut2 = h02 * K1t + h12 * K2t;   // hx K_,t
+    const double uD0 = h00 * K1D + h01 * K2D + h02 * K3D, uD1 = h01 * K1D + h11 * K2D + h12 * K3D,
+                 uD2 = h02 * K1D + h12 * K2D + h22 * K3D;                                                  // hx K_,D
+    w.t = g0 * K1t + g1 * K2t;
+    w.s = g1 * K2s;
+    w.D = g0 * K1D + g1 * K2D + g2 * K3D;
+    w.tt = g1 * nn + ut0 * K1t + ut1 * K2t;
+    w.ts = ut1 * K2s;
+    w.ss = h11 * K2s * K2s;
+    w.tD = g0 * (-2.0 / 3.0) * m * iD + g1 * (-4.0 / 3.0) * nn * t * iD + ut0 * K1D + ut1 * K2D + ut2 * K3D;
+    w.sD = g1 * (2.0 / 3.0) * nn * iD + uD1 * K2s;
+    w.DD = g0 * (10.0 / 9.0) * m * t * iD * iD + g1 * (14.0 / 9.0) * nn * q * iD * iD + 2.0 * g2 + uD0 * K1D + uD1 * K2D + uD2 * K3D;
+}
+
+// one point, stored by its own lane: P[9], dP[81] (each lane a 648-byte row: the plain form of the cross-check kernels, and the
+// comparison the staged stores of the default kernel are measured against). F is read again here: it does not wait in registers
+// through the network. hc: the scalar of the stress correction H = hc I.
+template <typename T>
+__device__ __forceinline__ void icnn3_point_out(const double* __restrict__ Fp, const T* g, const T* hx, double hc,
+                                                double* __restrict__ dPp, double* __restrict__ Pp) {
+    double Fv[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Fv[k] = Fp[k];
+    Hyper3W w;
+    icnn3_partials(Fv, g, hx, w);
+    Gen3Point q;
+    double Pv[9];
+    hyper3_general_stress(w, hc, Fv, q, Pv);
+#pragma unroll
+    for (int I = 0; I < 9; ++I) Pp[I] = Pv[I];
+    hyper3_general_tangent_rows(q, dPp);
+}
+
+// a wave's 64 points (lane = point, `npts` of them real; the others recompute the last point and store nothing) through the wave's
+// LDS buffer X of ICNN3_STAGE doubles: runs of consecutive doubles, 1 KiB per store instruction (hyper3_core.h)
+constexpr int ICNN3_PP = 7;                          // points per tangent pass
+constexpr int ICNN3_STAGE = 576;                     // doubles per wave: >= 7 * 81 + 2 and >= 32 * 9 + 2
+template <typename T>
+__device__ __forceinline__ void icnn3_tile_out(const double* __restrict__ Fp, const T* g, const T* hx, double hc, double* X, int lane,
+                                               int npts, double* __restrict__ dP0, double* __restrict__ P0) {
+    double Fv[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Fv[k] = Fp[k];
+    Hyper3W w;
+    icnn3_partials(Fv, g, hx, w);
+    Gen3Point q;
+    {
+        double Pv[9];
+        hyper3_general_stress(w, hc, Fv, q, Pv);
+        hyper3_store_stress_passes<false>(X, 32, lane, npts, Pv, P0);
+    }
+    double H[HYPER3_SYM];
+    hyper3_general_tangent(q, H);
+    hyper3_store_tangent<false>(X, ICNN3_PP, lane, npts, H, dP0);
+}
+
 // The weight arrays are separate `const T* __restrict__` kernel arguments on purpose: only then can the
 // compiler prove they are never written and fetch them through the scalar path (s_load -> SGPR operands).
 // Passed as pointers inside a struct they were loaded with per-lane global_load_dwordx4 (64x redundant,
 // 256 VGPRs for one weight row, h1/u spilled to scratch).
-template <typename T>
+template <typename T, int DIM>
 __global__ __launch_bounds__(DXO_BLOCK) void icnn_point(const T* __restrict__ wA1, const T* __restrict__ wW2B,
                                                         const T* __restrict__ wS2, const T* __restrict__ ww3,
                                                         IcnnSmall<T> small, int64_t n, const double* __restrict__ F,
@@ -94,21 +184,30 @@ __global__ __launch_bounds__(DXO_BLOCK) void icnn_point(const T* __restrict__ wA
         {wA1, wW2B, wS2, ww3, small.s3, small.H};
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
-        const dxo_f64x2 f01 = reinterpret_cast<const dxo_f64x2*>(F + p * 4)[0];
-        const dxo_f64x2 f23 = reinterpret_cast<const dxo_f64x2*>(F + p * 4)[1];
-        const double Fv[4] = {f01.x, f01.y, f23.x, f23.y};
-        // ---- features and their (t, D) partials, fp64 (:263-283)
-        const double t = Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3];
-        const double D = Fv[0] * Fv[3] - Fv[1] * Fv[2];
-        const double aD = fabs(D), sg = D < 0.0 ? -1.0 : 1.0, iD = 1.0 / D;
-        const double m = pow(aD, -2.0 / 3.0), nn = m * m;
-        const double K[3] = {(t + 1.0) * m - 3.0, (t + D * D) * nn - 3.0, (aD - 1.0) * (aD - 1.0)};
-        const double kt[3] = {m, nn, 0.0};
-        const double kD[3] = {(t + 1.0) * (-2.0 / 3.0) * m * iD, 2.0 * D * nn + (t + D * D) * (-4.0 / 3.0) * nn * iD,
-                              2.0 * (aD - 1.0) * sg};
-        const double ktD[3] = {(-2.0 / 3.0) * m * iD, (-4.0 / 3.0) * nn * iD, 0.0};
-        const double kDD[3] = {(t + 1.0) * (10.0 / 9.0) * m * iD * iD,
-                               -(10.0 / 3.0) * nn + (28.0 / 9.0) * (t + D * D) * nn * iD * iD, 2.0};
+        double K[3];
+        double Fv[4], kt[3], kD[3], ktD[3], kDD[3];   // DIM == 2 only: F and the (t, D) partials, carried to the chain rule
+        if constexpr (DIM == 2) {
+            const dxo_f64x2 f01 = reinterpret_cast<const dxo_f64x2*>(F + p * 4)[0];
+            const dxo_f64x2 f23 = reinterpret_cast<const dxo_f64x2*>(F + p * 4)[1];
+            Fv[0] = f01.x; Fv[1] = f01.y; Fv[2] = f23.x; Fv[3] = f23.y;
+            // ---- features and their (t, D) partials, fp64 (:263-283)
+            const double t = Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3];
+            const double D = Fv[0] * Fv[3] - Fv[1] * Fv[2];
+            const double aD = fabs(D), sg = D < 0.0 ? -1.0 : 1.0, iD = 1.0 / D;
+            const double m = pow(aD, -2.0 / 3.0), nn = m * m;
+            K[0] = (t + 1.0) * m - 3.0; K[1] = (t + D * D) * nn - 3.0; K[2] = (aD - 1.0) * (aD - 1.0);
+            kt[0] = m; kt[1] = nn; kt[2] = 0.0;
+            kD[0] = (t + 1.0) * (-2.0 / 3.0) * m * iD; kD[1] = 2.0 * D * nn + (t + D * D) * (-4.0 / 3.0) * nn * iD;
+            kD[2] = 2.0 * (aD - 1.0) * sg;
+            ktD[0] = (-2.0 / 3.0) * m * iD; ktD[1] = (-4.0 / 3.0) * nn * iD; ktD[2] = 0.0;
+            kDD[0] = (t + 1.0) * (10.0 / 9.0) * m * iD * iD;
+            kDD[1] = -(10.0 / 3.0) * nn + (28.0 / 9.0) * (t + D * D) * nn * iD * iD; kDD[2] = 2.0;
+        } else {   // the invariants of the full 3x3 F; its partials are formed after the network (icnn3_point_out)
+            double F3[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) F3[k] = F[p * 9 + k];
+            icnn3_features(F3, K);
+        }
         const T x0 = (T)K[0], x1 = (T)K[1], x2 = (T)K[2];   // the `.float()` of :286 when T = float
         // ---- layer 1 (layer 0 folded in): h1 = phi(a1), u = phi'(a1)
         T h1[NH], u[NH], beta[NH];
@@ -164,7 +263,8 @@ __global__ __launch_bounds__(DXO_BLOCK) void icnn_point(const T* __restrict__ wA
             hx[3] += c * A1v * A1v; hx[4] += c * A1v * A2; hx[5] += c * A2 * A2;
         }
         T y1v[3] = {y1[0], y1[1], y1[2]};
-        icnn_chain(Fv, kt, kD, ktD, kDD, y1v, hx, w.H, dP + p * 16, P + p * 4);
+        if constexpr (DIM == 2) icnn_chain(Fv, kt, kD, ktD, kDD, y1v, hx, w.H, dP + p * 16, P + p * 4);
+        else icnn3_point_out(F + p * 9, y1v, hx, w.H[0], dP + p * 81, P + p * 9);
     }
 }
 
@@ -227,7 +327,54 @@ __device__ __forceinline__ void softplus3_mfma(float a, float& sp, float& s1, fl
     s2 = s1 * r;
 }
 
-template <int WAVES>
+// the lane's own point of a tile, clamped to the last point: tail lanes recompute it and never store. 2-D: requested one tile
+// ahead and carried through the GEMM phases. 3-D: read where it is used, before and again after the GEMM phases: 18 registers
+// through them are more than the kernels have left.
+template <int DIM>
+__device__ __forceinline__ void icnn_fetch_F(const double* __restrict__ F, int64_t tile, int lane, int64_t n, dxo_f64x2& f01,
+                                             dxo_f64x2& f23) {
+    if constexpr (DIM == 2) {
+        const int64_t p = tile * 64 + lane < n ? tile * 64 + lane : n - 1;
+        f01 = reinterpret_cast<const dxo_f64x2*>(F + p * 4)[0];
+        f23 = reinterpret_cast<const dxo_f64x2*>(F + p * 4)[1];
+    }
+}
+
+// the lane index formed where it is used: two instructions instead of a register that waits through the GEMM phases (the default
+// kernel has none to spare); volatile, or it is hoisted out of the tile loop again
+__device__ __forceinline__ int icnn_lane_here() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
+// 3-D: the tile's first point (wave-uniform: the tile counter is) and the lane's point within the tile (tail lanes: the last one),
+// so that the addresses are a scalar base plus a 32-bit lane offset formed where they are used: nothing 64-bit per lane waits
+// through the GEMM phases
+struct Icnn3Tile {
+    int64_t p0;   // uniform
+    int npts;     // uniform
+    int lc;       // min(lane, npts - 1)
+};
+
+__device__ __forceinline__ Icnn3Tile icnn3_tile(int64_t tile, int lane, int64_t n) {
+    Icnn3Tile t;
+    t.p0 = tile * 64;
+    t.npts = n - t.p0 < 64 ? (int)(n - t.p0) : 64;
+    t.lc = lane < t.npts ? lane : t.npts - 1;
+    return t;
+}
+
+__device__ __forceinline__ void icnn3_load_features(const double* __restrict__ F, const Icnn3Tile& t, float& x0, float& x1, float& x2) {
+    const double* Fp = F + t.p0 * 9 + t.lc * 9;
+    double F3[9], K[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) F3[k] = Fp[k];
+    icnn3_features(F3, K);
+    x0 = (float)K[0]; x1 = (float)K[1]; x2 = (float)K[2];
+}
+
+template <int WAVES, int DIM>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_f32(const float* __restrict__ wT1, const float* __restrict__ wW2,
                                                         const float* __restrict__ wT2, IcnnSmall<float> small, int64_t n,
                                                         const double* __restrict__ F, double* __restrict__ dP,
@@ -262,18 +409,18 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_f32(const flo
 
     const int64_t n_tiles = (n + 63) / 64;
     const int64_t tile_step = (int64_t)gridDim.x * WAVES;
-    int64_t tile = (int64_t)blockIdx.x * WAVES + wave;
+    // 3-D: a uniform wave index, so that the tile counter and the bases derived from it live in scalar registers
+    const int wave_u = DIM == 3 ? __builtin_amdgcn_readfirstlane(wave) : wave;
+    int64_t tile = (int64_t)blockIdx.x * WAVES + wave_u;
     // the lane's own point of the NEXT tile is requested one tile ahead: its latency runs under this tile's GEMMs
     dxo_f64x2 f01n{1.0, 0.0}, f23n{0.0, 1.0};
-    if (tile < n_tiles) {
-        const int64_t pl0 = tile * 64 + lane < n ? tile * 64 + lane : n - 1;
-        f01n = reinterpret_cast<const dxo_f64x2*>(F + pl0 * 4)[0];
-        f23n = reinterpret_cast<const dxo_f64x2*>(F + pl0 * 4)[1];
-    }
+    if (tile < n_tiles) icnn_fetch_F<DIM>(F, tile, lane, n, f01n, f23n);
     for (; tile < n_tiles; tile += tile_step) {
         const int64_t pidx = tile * 64 + lane;
         float x0, x1, x2;
-        {
+        if constexpr (DIM == 3) {
+            icnn3_load_features(F, icnn3_tile(tile, icnn_lane_here(), n), x0, x1, x2);
+        } else {
             const double Fv[4] = {f01n.x, f01n.y, f23n.x, f23n.y};   // tail lanes recompute the last point, never store
             const double t = Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3];
             const double D = Fv[0] * Fv[3] - Fv[1] * Fv[2];
@@ -284,12 +431,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_f32(const flo
             keep[4 * 64] = t; keep[5 * 64] = D; keep[6 * 64] = m; keep[7 * 64] = nn; keep[8 * 64] = iD;
             asm volatile("" ::: "memory");   // the values are re-read from LDS below, not carried in registers
         }
-        if (tile + tile_step < n_tiles) {
-            const int64_t pn = (tile + tile_step) * 64 + lane;
-            const int64_t pln = pn < n ? pn : n - 1;
-            f01n = reinterpret_cast<const dxo_f64x2*>(F + pln * 4)[0];
-            f23n = reinterpret_cast<const dxo_f64x2*>(F + pln * 4)[1];
-        }
+        if (tile + tile_step < n_tiles) icnn_fetch_F<DIM>(F, tile + tile_step, lane, n, f01n, f23n);
         const float xp0 = xor32(x0), xp1 = xor32(x1), xp2 = xor32(x2);
 #pragma unroll 1
         for (int tt = 0; tt < 2; ++tt) {
@@ -393,7 +535,15 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_f32(const flo
             }
         }
         asm volatile("" ::: "memory");
-        if (pidx < n) {
+        if constexpr (DIM == 3) {
+            float mine[9];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) mine[q] = minep[q * 64];
+            const float y1f[3] = {mine[0] + small.s3[0], mine[1] + small.s3[1], mine[2] + small.s3[2]};
+            const Icnn3Tile t = icnn3_tile(tile, lane, n);
+            if (lane < t.npts)
+                icnn3_point_out(F + t.p0 * 9 + lane * 9, y1f, mine + 3, small.H[0], dP + t.p0 * 81 + lane * 81, P + t.p0 * 9 + lane * 9);
+        } else if (pidx < n) {
             const double Fk[4] = {keep[0 * 64], keep[1 * 64], keep[2 * 64], keep[3 * 64]};
             const double t = keep[4 * 64], D = keep[5 * 64], m = keep[6 * 64], nn = keep[7 * 64], iD = keep[8 * 64];
             const double aD = fabs(D), sg = D < 0.0 ? -1.0 : 1.0;
@@ -544,7 +694,11 @@ __device__ __forceinline__ icnn_f2p icnn_fma2_p(icnn_f2p a, icnn_f2p b, icnn_f2p
 
 #define DXO_ICNN_PINP(x) asm volatile("" : "+v"(x));
 
-template <int WAVES>
+// 3-D (DIM == 3): only what comes before and after the GEMM phases differs. STAGED: the 90 results of a point leave in output order
+// through the wave's LDS buffer — what is left of the 160 KiB beside the weight fragments, with the nine sums' slots inside it
+// (they are in registers by then): ICNN3_STAGE doubles per wave, seven points per tangent pass. Otherwise every lane stores its
+// own 648-byte row.
+template <int WAVES, int DIM, bool STAGED = false>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_bf16x3_packed(const float* __restrict__ wT1, const float* __restrict__ wW2,
                                                         const float* __restrict__ wT2, IcnnSmall<float> small, int64_t n,
                                                         const double* __restrict__ F, double* __restrict__ dP,
@@ -562,8 +716,16 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_bf16x3_packed
     __shared__ __attribute__((aligned(16))) float sP1[32 * 8];    // A1x A1y A1z d1
     __shared__ __attribute__((aligned(16))) float sP3[32 * 12];   // the six products A1_k A1_l / 6
     __shared__ __attribute__((aligned(16))) float sP2[32 * 12];   // S2x S2y S2z c2 w3/6, 0
-    __shared__ float sMine[WAVES * 9 * 64];
-    float* minep = sMine + wave * (9 * 64) + lane;
+    float* minep;
+    double* stage0 = nullptr;   // STAGED: the staging buffers, one per wave
+    if constexpr (STAGED) {
+        __shared__ __attribute__((aligned(16))) double sStage[WAVES * ICNN3_STAGE];
+        stage0 = sStage;
+        minep = reinterpret_cast<float*>(sStage + wave * ICNN3_STAGE) + lane;
+    } else {
+        __shared__ float sMine[WAVES * 9 * 64];
+        minep = sMine + wave * (9 * 64) + lane;
+    }
     for (int e = threadIdx.x; e < 2 * 4 * 64 * 8; e += BLOCK) {
         const int i = e & 7, l = (e >> 3) & 63, st = (e >> 9) & 3, t = e >> 11;
         const int row = icnn_row(st >> 1, 8 * (st & 1) + i) + 4 * (l >> 5);
@@ -599,18 +761,18 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_bf16x3_packed
 
     const int64_t n_tiles = (n + 63) / 64;
     const int64_t tile_step = (int64_t)gridDim.x * WAVES;
-    int64_t tile = (int64_t)blockIdx.x * WAVES + wave;
+    // 3-D: a uniform wave index, so that the tile counter and the bases derived from it live in scalar registers
+    const int wave_u = DIM == 3 ? __builtin_amdgcn_readfirstlane(wave) : wave;
+    int64_t tile = (int64_t)blockIdx.x * WAVES + wave_u;
     dxo_f64x2 f01n{1.0, 0.0}, f23n{0.0, 1.0};
-    if (tile < n_tiles) {
-        const int64_t pl0 = tile * 64 + lane < n ? tile * 64 + lane : n - 1;
-        f01n = reinterpret_cast<const dxo_f64x2*>(F + pl0 * 4)[0];
-        f23n = reinterpret_cast<const dxo_f64x2*>(F + pl0 * 4)[1];
-    }
+    if (tile < n_tiles) icnn_fetch_F<DIM>(F, tile, lane, n, f01n, f23n);
     for (; tile < n_tiles; tile += tile_step) {
         const int64_t pidx = tile * 64 + lane;
         const dxo_f64x2 f01 = f01n, f23 = f23n;
         float x0, x1, x2;
-        {
+        if constexpr (DIM == 3) {
+            icnn3_load_features(F, icnn3_tile(tile, icnn_lane_here(), n), x0, x1, x2);
+        } else {
             const double Fv[4] = {f01.x, f01.y, f23.x, f23.y};   // tail lanes recompute the last point, never store
             const double t = Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3];
             const double D = Fv[0] * Fv[3] - Fv[1] * Fv[2];
@@ -618,12 +780,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_bf16x3_packed
             const double m = hyper_pow_m23(aD), nn = m * m;
             x0 = (float)((t + 1.0) * m - 3.0); x1 = (float)((t + D * D) * nn - 3.0); x2 = (float)((aD - 1.0) * (aD - 1.0));
         }
-        if (tile + tile_step < n_tiles) {
-            const int64_t pn = (tile + tile_step) * 64 + lane;
-            const int64_t pln = pn < n ? pn : n - 1;
-            f01n = reinterpret_cast<const dxo_f64x2*>(F + pln * 4)[0];
-            f23n = reinterpret_cast<const dxo_f64x2*>(F + pln * 4)[1];
-        }
+        if (tile + tile_step < n_tiles) icnn_fetch_F<DIM>(F, tile + tile_step, lane, n, f01n, f23n);
         const float xp0 = xor32(x0), xp1 = xor32(x1), xp2 = xor32(x2);
 #pragma unroll 1
         for (int tt = 0; tt < 2; ++tt) {
@@ -745,7 +902,23 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_bf16x3_packed
             }
         }
         asm volatile("" ::: "memory");
-        if (pidx < n) {
+        if constexpr (DIM == 3) {
+            float mine[9];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) mine[q] = minep[q * 64];
+            const float y1f[3] = {mine[0] + small.s3[0], mine[1] + small.s3[1], mine[2] + small.s3[2]};
+            // what the stores derive from the lane index is formed HERE: hoisted out of the tile loop, a dozen addresses would wait
+            // through the GEMM phases (in scratch)
+            const int ln = icnn_lane_here();
+            const Icnn3Tile t = icnn3_tile(tile, ln, n);
+            if constexpr (STAGED) {
+                op_fence();   // every lane has its nine sums before the slots become the staging buffer
+                double* X = stage0 + wave_u * ICNN3_STAGE;
+                icnn3_tile_out(F + t.p0 * 9 + t.lc * 9, y1f, mine + 3, small.H[0], X, ln, t.npts, dP + t.p0 * 81, P + t.p0 * 9);
+            } else if (ln < t.npts) {
+                icnn3_point_out(F + t.p0 * 9 + ln * 9, y1f, mine + 3, small.H[0], dP + t.p0 * 81 + ln * 81, P + t.p0 * 9 + ln * 9);
+            }
+        } else if (pidx < n) {
             // the fp64 feature derivatives are formed here, after the GEMM phases (they would occupy 18 registers through them)
             const double Fk[4] = {f01.x, f01.y, f23.x, f23.y};
             const double t = Fk[0] * Fk[0] + Fk[1] * Fk[1] + Fk[2] * Fk[2] + Fk[3] * Fk[3];
@@ -777,7 +950,7 @@ void launch_icnn(const IcnnDev<T>& m, int blocks, hipStream_t s, int64_t n, cons
     IcnnSmall<T> small;
     for (int k = 0; k < 3; ++k) small.s3[k] = m.s3[k];
     for (int k = 0; k < 4; ++k) small.H[k] = m.H[k];
-    hipLaunchKernelGGL((icnn_point<T>), dim3(blocks), dim3(DXO_BLOCK), 0, s, m.A1, m.W2B, m.S2, m.w3, small, n, F, dP, P);
+    hipLaunchKernelGGL((icnn_point<T, 2>), dim3(blocks), dim3(DXO_BLOCK), 0, s, m.A1, m.W2B, m.S2, m.w3, small, n, F, dP, P);
 }
 
 double softplus_host(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
@@ -811,9 +984,9 @@ int icnn_launch(dxo_ctx* ctx, const IcnnLaunch& L, int64_t n, const double* F, d
         } else
 #endif
         if (ctx->icnn_variant != 1)   // 2: split-bf16 products phase after phase, two waves per SIMD; 1: fp32-input MFMA
-            hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8>), dim3((int)mb), dim3(512), 0, s, L.m->f32.T1, L.m->f32.W2, L.m->f32.T2, small, n, F, dP, P);
+            hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8, 2>), dim3((int)mb), dim3(512), 0, s, L.m->f32.T1, L.m->f32.W2, L.m->f32.T2, small, n, F, dP, P);
         else
-            hipLaunchKernelGGL((icnn_mfma_f32<8>), dim3((int)mb), dim3(512), 0, s, L.m->f32.T1, L.m->f32.W2, L.m->f32.T2, small, n, F, dP, P);
+            hipLaunchKernelGGL((icnn_mfma_f32<8, 2>), dim3((int)mb), dim3(512), 0, s, L.m->f32.T1, L.m->f32.W2, L.m->f32.T2, small, n, F, dP, P);
         return DXO_OK;
     }
     if (L.precision == 0) launch_icnn<float>(L.m->f32, (int)blocks, s, n, F, dP, P);
@@ -824,6 +997,50 @@ int icnn_launch(dxo_ctx* ctx, const IcnnLaunch& L, int64_t n, const double* F, d
 int icnn_chunk(dxo_ctx* ctx, void* user, int64_t m, void* const* d_in, void* const* d_out, hipStream_t s) {
     const IcnnLaunch& L = *static_cast<const IcnnLaunch*>(user);
     return icnn_launch(ctx, L, m, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], s);
+}
+
+// the 3-D forms: F[n][9] -> dP[n][81], P[n][9]; same grids, the scalar of the correction H = h I in IcnnSmall::H[0]
+template <typename T>
+void launch_icnn3(const IcnnDev<T>& m, double h3, int blocks, hipStream_t s, int64_t n, const double* F, double* dP, double* P) {
+    IcnnSmall<T> small;
+    for (int k = 0; k < 3; ++k) small.s3[k] = m.s3[k];
+    small.H[0] = h3;
+    small.H[1] = small.H[2] = small.H[3] = 0.0;
+    hipLaunchKernelGGL((icnn_point<T, 3>), dim3(blocks), dim3(DXO_BLOCK), 0, s, m.A1, m.W2B, m.S2, m.w3, small, n, F, dP, P);
+}
+
+int icnn3_launch(dxo_ctx* ctx, const IcnnLaunch& L, int64_t n, const double* F, double* dP, double* P, hipStream_t s) {
+    if (n == 0) return DXO_OK;
+    int64_t blocks = (n + DXO_BLOCK - 1) / DXO_BLOCK;
+    const int64_t cap = (int64_t)ctx->compute_units * 8;
+    if (blocks > cap) blocks = cap;
+    if (L.precision == 1) {
+        launch_icnn3<double>(L.m->f64, L.m->H3, (int)blocks, s, n, F, dP, P);
+        return DXO_OK;
+    }
+    if (ctx->icnn_variant == 0) {
+        launch_icnn3<float>(L.m->f32, L.m->H3, (int)blocks, s, n, F, dP, P);
+        return DXO_OK;
+    }
+    IcnnSmall<float> small;
+    for (int k = 0; k < 3; ++k) small.s3[k] = L.m->f32.s3[k];
+    small.H[0] = L.m->H3;
+    small.H[1] = small.H[2] = small.H[3] = 0.0;
+    int64_t mb = (n + 8 * 64 - 1) / (8 * 64);
+    if (mb > ctx->compute_units) mb = ctx->compute_units;
+    const IcnnDev<float>& w = L.m->f32;
+    if (ctx->icnn_variant == 1)
+        hipLaunchKernelGGL((icnn_mfma_f32<8, 3>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
+    else if (ctx->icnn3_store != 0)   // variants 3 and 4 of an experiments build have no 3-D form: the default kernel answers
+        hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8, 3, true>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
+    else
+        hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8, 3, false>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
+    return DXO_OK;
+}
+
+int icnn3_chunk(dxo_ctx* ctx, void* user, int64_t m, void* const* d_in, void* const* d_out, hipStream_t s) {
+    const IcnnLaunch& L = *static_cast<const IcnnLaunch*>(user);
+    return icnn3_launch(ctx, L, m, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], s);
 }
 
 // ------------------------------------------------------------------ analytic Isihara energy (demo_hyperelasticity.py:686-703)
@@ -1007,17 +1224,20 @@ extern "C" int dxo_icnn_create(dxo_ctx* ctx, const dxo_icnn_weights* w, dxo_icnn
         m->f32.s3[k] = (float)s3;
     }
     // ---- H correction (:362-381): H_flat = -P_NN(F = I), with the fp32 network like the reference
+    // and its 3-D form from the 3-D kernel at F = I_3: every diagonal stress is the same expression there and the shears are exact
+    // zeros, so H is a multiple of the identity and P0_3[0] carries it
     double *dF = nullptr, *ddP = nullptr, *dPp = nullptr;
-    const double FI[4] = {1.0, 0.0, 0.0, 1.0};
-    double P0[4] = {0, 0, 0, 0};
-    e = hipMalloc(&dF, (4 + 16 + 4) * sizeof(double));
+    const double FI[4 + 9] = {1.0, 0.0, 0.0, 1.0, /* I_3 */ 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    double P0[4 + 9] = {0, 0, 0, 0};
+    e = hipMalloc(&dF, (14 + 82 + 13) * sizeof(double));   // every block at an even offset: the 2-D kernel stores pairs
     if (e == hipSuccess) {
-        ddP = dF + 4;
-        dPp = ddP + 16;
+        ddP = dF + 14;
+        dPp = ddP + 82;
         e = hipMemcpy(dF, FI, sizeof FI, hipMemcpyHostToDevice);
     }
     if (e == hipSuccess) {
         launch_icnn<float>(m->f32, 1, ctx->stream, (int64_t)1, dF, ddP, dPp);
+        launch_icnn3<float>(m->f32, 0.0, 1, ctx->stream, (int64_t)1, dF + 4, ddP, dPp + 4);
         e = hipStreamSynchronize(ctx->stream);
     }
     if (e == hipSuccess) e = hipMemcpy(P0, dPp, sizeof P0, hipMemcpyDeviceToHost);
@@ -1031,6 +1251,7 @@ extern "C" int dxo_icnn_create(dxo_ctx* ctx, const dxo_icnn_weights* w, dxo_icnn
         m->f32.H[k] = -(double)(float)P0[k];
         m->f64.H[k] = m->f32.H[k];
     }
+    m->H3 = -(double)(float)P0[4];
     *out = m;
     return DXO_OK;
 }
@@ -1091,4 +1312,46 @@ extern "C" int dxo_icnn_eval(dxo_ctx* ctx, const dxo_icnn* m, int precision, int
     std::vector<dxo_span> in = {{F, nullptr, 4 * sd}};
     std::vector<dxo_span> out = {{nullptr, dP, 16 * sd}, {nullptr, P, 4 * sd}};
     return dxo_run_host_pipeline(ctx, n, in, out, icnn_chunk, &L);
+}
+
+// ---- the 3-D operator: the same model, the invariants of a full 3x3 F
+int dxo_icnn3_launch_device(dxo_ctx* ctx, const dxo_icnn* m, int precision, int64_t n, const double* F, double* dP, double* P,
+                            hipStream_t s) {
+    IcnnLaunch L{m, precision};
+    return icnn3_launch(ctx, L, n, F, dP, P, s);
+}
+
+extern "C" int dxo_icnn3_correction(dxo_ctx* ctx, const dxo_icnn* m, double* H9) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!m || !H9) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_correction: NULL argument");
+    for (int k = 0; k < 9; ++k) H9[k] = (k % 4 == 0) ? m->H3 : 0.0;
+    return DXO_OK;
+}
+
+extern "C" int dxo_icnn3_eval(dxo_ctx* ctx, const dxo_icnn* m, int precision, int64_t n, int mem, const double* F,
+                              double* dP, double* P) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!m) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_eval: model is NULL");
+    if (precision != 0 && precision != 1) return dxo_fail(ctx, DXO_E_OPTION, "dxo_icnn3_eval: precision must be 0 (fp32 network) or 1 (fp64)");
+    if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_icnn3_eval: n < 0");
+    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_icnn3_eval: bad mem");
+    if (n > 0 && (!F || !dP || !P)) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_eval: NULL array");
+    const uintptr_t all = (uintptr_t)F | (uintptr_t)dP | (uintptr_t)P;
+    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn3_eval: arrays must be 8-byte aligned");
+    if (mem == DXO_MEM_DEVICE && (all & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn3_eval: device arrays must be 16-byte aligned");
+    IcnnLaunch L{m, precision};
+    if (mem == DXO_MEM_DEVICE) {
+        hipStream_t s = dxo_launch_stream(ctx);
+        int rc = dxo_device_begin(ctx, s);
+        if (rc != DXO_OK) return rc;
+        rc = icnn3_launch(ctx, L, n, F, dP, P, s);
+        if (rc != DXO_OK) return rc;
+        return dxo_device_end(ctx, s);
+    }
+    const size_t sd = sizeof(double);
+    std::vector<dxo_span> in = {{F, nullptr, 9 * sd}};
+    std::vector<dxo_span> out = {{nullptr, dP, 81 * sd}, {nullptr, P, 9 * sd}};
+    return dxo_run_host_pipeline(ctx, n, in, out, icnn3_chunk, &L);
 }

@@ -802,7 +802,7 @@ def _P_device(cx: Context, Fvals, launch, d: int = 4):
 
 
 def make_icnn(state_dict, *, precision: str = "fp32", ctx: Context | None = None, device: int = 0,
-              reuse_outputs: bool = False, outputs=None) -> Callable:
+              reuse_outputs: bool = False, outputs=None, dim: int = 2) -> Callable:
     """`P_external` of the hyperelasticity demo (demo_hyperelasticity.py:459-466) on the GPU.
 
     `external_function((1,))(Fvals) -> (dP, P)`, flat arrays in the reference's order (:456); other
@@ -811,8 +811,16 @@ def make_icnn(state_dict, *, precision: str = "fp32", ctx: Context | None = None
     them or with '__' for '.'), e.g. `torch.load("Isihara_noise=high.pth")` (:314).
     precision "fp32" evaluates the network in fp32 like the reference (:286); "fp64" is the tolerance-study
     variant (BASELINE config 5). The stress correction H (:362-381) is computed once at creation.
+
+    dim = 3: the same weights on the invariants of a full 3x3 F (dxo_icnn3_eval: K1, K2, K3 of C = F^T F, which the reference writes
+    out for F = [[F_2, 0], [0, 1]]) for `Fvals` (num_cells, nq, 3, 3) (or anything reshaping to (-1, 9)): flat dP (n * 81, the
+    [n][9][9] block of the ("grad", "grad", bs = 3) bilinear pair) and P (n * 9); `.correction()` returns 9 values. NumPy arrays, CUDA
+    tensors and a lazy "F" operand of a gdim = 3 mesh are taken (the lazy operand by dxo_icnn3_field). A lazy "F" operand of a mesh
+    whose gdim differs from `dim` raises ValueError.
     """
     prec = {"fp32": 0, "fp64": 1}[precision]
+    if dim not in (2, 3):
+        raise ValueError("dim must be 2 (plane strain, F 2x2) or 3 (F 3x3)")
     holder = {"ctx": ctx, "model": None, "out": None, "targets": outputs}
 
     def _model():
@@ -824,8 +832,26 @@ def make_icnn(state_dict, *, precision: str = "fp32", ctx: Context | None = None
             holder["out"] = _Outputs(holder["ctx"], reuse_outputs, dict(zip(("dP", "P"), holder["targets"])) if holder["targets"] is not None else None)
         return holder["ctx"], holder["model"]
 
+    def dP_dF_3d(cx, model, Fvals):
+        if _is_device_tensor(Fvals):
+            return _P_device(cx, Fvals, lambda n, F, dP, P: cx.icnn3_eval(model, prec, n, MEM_DEVICE, F, dP, P), 9)
+        if isinstance(Fvals, LazyOperand) and Fvals.kind == "F" and Fvals.mesh.ctx is cx:
+            n = Fvals.shape[0] * Fvals.shape[1]      # F = I + grad u on the device in front of the network kernel (dxo_icnn3_field)
+            dP, P = holder["out"].get("dP", n * 81), holder["out"].get("P", n * 9)
+            cx.icnn3_field(model, prec, Fvals.mesh._h, MEM_HOST, Fvals.u, dP, P)
+            return dP.reshape(-1), P.reshape(-1)
+        F = _as_f64_host(Fvals, "Fvals").reshape(-1, 9)
+        n = F.shape[0]
+        dP, P = holder["out"].get("dP", n * 81), holder["out"].get("P", n * 9)
+        cx.icnn3_eval(model, prec, n, MEM_HOST, F, dP, P)
+        return _like(Fvals, dP.reshape(-1), P.reshape(-1))
+
     def dP_dF_impl(Fvals):
         cx, model = _model()
+        if isinstance(Fvals, LazyOperand) and Fvals.kind == "F" and Fvals.mesh.gdim != dim:
+            raise ValueError(f"make_icnn(dim={dim}): the operand is the deformation gradient of a gdim = {Fvals.mesh.gdim} mesh")
+        if dim == 3:
+            return dP_dF_3d(cx, model, Fvals)
         if _is_device_tensor(Fvals):
             return _P_device(cx, Fvals, lambda n, F, dP, P: cx.icnn_eval(model, prec, n, MEM_DEVICE, F, dP, P))
         if isinstance(Fvals, LazyOperand) and Fvals.kind == "F" and Fvals.mesh.ctx is cx and Fvals.mesh.gdim == 2:
@@ -852,7 +878,7 @@ def make_icnn(state_dict, *, precision: str = "fp32", ctx: Context | None = None
         return P_external
 
     P_external.bind = bind
-    P_external.correction = lambda: _model()[0].icnn_correction(_model()[1])
+    P_external.correction = lambda: (_model()[0].icnn3_correction if dim == 3 else _model()[0].icnn_correction)(_model()[1])
     return P_external
 
 

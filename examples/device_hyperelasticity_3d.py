@@ -19,7 +19,13 @@ Mesh: P2 tetrahedra with the 4-point rule (the default), or --hex: Q2 hexahedra 
 under-integrates the Q2 stiffness matrix: it is singular). Load: the top face moves down by `compress` and turns about
 the cube's axis by `twist` radians, both reached over `steps` equal load steps; a step's predictor moves every node by the
 homogeneous field that meets both faces. The model is fp64 and the tangent exact, so Newton converges quadratically.
+--model icnn --weights FILE: the constitutive law is the input-convex network of the reference's demo instead (dxo_icnn3_field: the
+operand kernel, then the network kernel on the invariants of the 3x3 F). FILE is the model's state_dict, a torch file
+(`Isihara_noise=high.pth`) or an .npz with '__' for '.' in the keys. --precision fp64 (the default here) evaluates the network in
+fp64, so that stress and tangent are consistent to fp64 rounding and the residual can fall by the ten decades the Newton loop asks
+for; with fp32, the reference's network precision, the stress carries fp32 rounding (about 1e-7) and the loop's tolerance may be out of reach.
 Needs an MI355X.    python3 examples/device_hyperelasticity_3d.py [--n 6] [--hex] [--matrix-free] [--solver cg|gmres]
+                                                                   [--model isihara|icnn] [--weights FILE] [--precision fp32|fp64]
 """
 import argparse
 import pathlib
@@ -49,8 +55,18 @@ def predictor(x: np.ndarray, compress: float, twist: float) -> np.ndarray:
     return u
 
 
+def load_state_dict(path):
+    """the network's state_dict from a torch file or an .npz (keys with '__' for '.')"""
+    if path is None:
+        raise ValueError("--model icnn needs --weights FILE (the state_dict of the trained network)")
+    if str(path).endswith(".npz"):
+        return dict(np.load(path))
+    return torch.load(path, map_location="cpu")
+
+
 def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float = 0.4, hexahedra: bool = False, matrix_free: bool = False,
-         solver: str = "cg", verbose: bool = True, c=(0.5, 1.0, 1.0, 1.5)) -> dict:
+         solver: str = "cg", verbose: bool = True, c=(0.5, 1.0, 1.0, 1.5), model: str = "isihara", weights=None,
+         precision: str = "fp64") -> dict:
     """Returns the per-step Newton residual histories, the linear iteration counts and the final displacement (`u`, host array).
     Raises RuntimeError if a load step does not converge within MAX_NEWTON iterations or a linear solve fails."""
     dev = torch.device("cuda:0")
@@ -64,6 +80,10 @@ def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float =
         mesh = structured_mesh("tetrahedron", (n_side,) * 3, degree=2)
     dm = DeviceMesh.from_synthetic(mesh, ctx=ctx)
     prm = IsiharaParams(*c)
+    if model not in ("isihara", "icnn"):
+        raise ValueError('model must be "isihara" or "icnn"')
+    net = ctx.icnn_create(load_state_dict(weights)) if model == "icnn" else None
+    net_precision = {"fp32": 0, "fp64": 1}[precision]
     G = 3
     x = mesh.node_x
     nn, npts = x.shape[0], mesh.num_cells * mesh.nq
@@ -83,7 +103,10 @@ def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float =
 
     def residual():
         """(dP, P) at the current u and the assembled inner(grad v, P) dx on the free dofs"""
-        ctx.isihara3_field(prm, dm._h, MEM_DEVICE, u.data_ptr(), dP.data_ptr(), P.data_ptr())
+        if net is None:
+            ctx.isihara3_field(prm, dm._h, MEM_DEVICE, u.data_ptr(), dP.data_ptr(), P.data_ptr())
+        else:
+            ctx.icnn3_field(net, net_precision, dm._h, MEM_DEVICE, u.data_ptr(), dP.data_ptr(), P.data_ptr())
         dm.adjoint("F", G, P.data_ptr(), R.data_ptr())
         return torch.where(free, R, torch.zeros_like(R))
 
@@ -109,7 +132,7 @@ def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float =
         minv = torch.where(free, 1.0 / diag, torch.ones_like(diag))
         return krylov(jacobian_times, b, M=minv, rtol=1e-12, maxiter=20000, ctx=ctx)
 
-    report = {"cells": mesh.num_cells, "points": npts, "dofs": nn * G, "matrix_free": matrix_free, "solver": solver, "steps": []}
+    report = {"cells": mesh.num_cells, "points": npts, "dofs": nn * G, "matrix_free": matrix_free, "solver": solver, "model": model, "steps": []}
     prev = np.zeros_like(x)
     for k in range(1, steps + 1):
         lam = k / steps
@@ -140,6 +163,8 @@ def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float =
             print(f"load {lam:.3f}: {len(history) - 1} Newton its, residuals " + " ".join(f"{r:.2e}" for r in history)
                   + f", {solver} its {lin_its}, {dt * 1e3:.0f} ms")
     report["u"] = u.cpu().numpy()
+    if net is not None:
+        ctx.icnn_destroy(net)
     dm.close()
     ctx.close()
     return report
@@ -152,5 +177,8 @@ if __name__ == "__main__":
     ap.add_argument("--hex", action="store_true", help="Q2 hexahedra with the 27-point rule instead of P2 tetrahedra")
     ap.add_argument("--matrix-free", action="store_true", help="Jacobi-preconditioned Krylov solve on bilinear_apply, nothing assembled")
     ap.add_argument("--solver", choices=["cg", "gmres"], default="cg")
+    ap.add_argument("--model", choices=["isihara", "icnn"], default="isihara", help="the analytic energy (default) or the trained network")
+    ap.add_argument("--weights", help="--model icnn: the network's state_dict (torch file or .npz)")
+    ap.add_argument("--precision", choices=["fp32", "fp64"], default="fp64", help="--model icnn: precision of the network")
     a = ap.parse_args()
-    main(a.n, steps=a.steps, hexahedra=a.hex, matrix_free=a.matrix_free, solver=a.solver)
+    main(a.n, steps=a.steps, hexahedra=a.hex, matrix_free=a.matrix_free, solver=a.solver, model=a.model, weights=a.weights, precision=a.precision)

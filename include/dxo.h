@@ -1098,6 +1098,26 @@ int dxo_isihara3(dxo_ctx* ctx, const dxo_isihara_params* prm, int64_t n, int mem
 int dxo_isihara3_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, int mem, const double* u,
                        double* dP, double* P);
 
+/* The network operator for a 3x3 deformation gradient: the SAME dxo_icnn model (one weight set serves both dimensions) evaluated
+ * on the invariants of the full C = F^T F,
+ *   K1 = I1 I3^(-1/3) - 3,  K2 = I2 I3^(-2/3) - 3,  K3 = (sqrt(I3) - 1)^2,  I1 = tr C, I2 = (I1^2 - tr C^2) / 2, I3 = (det F)^2,
+ * which the reference writes out for F = [[F_2, 0], [0, 1]] (demo_hyperelasticity.py:263-283): the in-plane stress and tangent of an
+ * embedded plane-strain F are dxo_icnn_eval's (up to the correction, which differs in the last bits of zero), the out-of-plane shear
+ * stresses are exactly 0 and P_33 is not. I/O as dxo_isihara3: F[n][9] row-major -> dP[n][9][9] (symmetric), P[n][9]; precision as
+ * dxo_icnn_eval; kernels by "icnn_variant" as in 2-D (0, 1, 2), the default one's stores by "icnn3_store" (0 — the default — one
+ * 648-byte row per lane, 1 staged through LDS in output order: measured slower, profiles/icnn3_bench.txt). det F < 0 is finite (sqrt(I3) = |det F|, as the reference), det F = 0
+ * gives non-finite values in that point's outputs only.
+ *   dxo_icnn3_correction  H9[9]: the stress correction H = -P_NN(F = I) of :362-381 (P += F H, dP_(ia)(jc) += d_ij H_ca). In 3-D it is a
+ *                         multiple of the identity and analytically zero (K1, K2, K3 are stationary at F = I): rounding of create().
+ *   dxo_icnn3_field       F = I + grad u of a gdim = 3 mesh (DXO_E_DIM otherwise) into the context's staging buffer, then the network
+ *                         kernel: the two-launch form of dxo_icnn_field; bit-identical to dxo_eval_operand + dxo_icnn3_eval.
+ * Checks and error codes as dxo_isihara3 / dxo_isihara3_field, plus DXO_E_OPTION for a precision other than 0 or 1. */
+int dxo_icnn3_eval(dxo_ctx* ctx, const dxo_icnn* model, int precision, int64_t n, int mem,
+                   const double* F, double* dP, double* P);
+int dxo_icnn3_field(dxo_ctx* ctx, const dxo_icnn* model, int precision, dxo_mesh* mesh, int mem, const double* u,
+                    double* dP, double* P);
+int dxo_icnn3_correction(dxo_ctx* ctx, const dxo_icnn* model, double* H9);
+
 /* ---- multi-GPU: cell-block sharding + RCCL all-gather inside the library (BASELINE north_star) ----
  * The reference splits only by MPI mesh partition and never gathers quadrature data
  * (src/dolfinx_external_operator/external_operator.py:365-371, 445). Here ONE coefficient vector's quadrature points
