@@ -106,6 +106,17 @@ def test_tangent_has_major_symmetry(ctx, reference_1000):
     assert np.abs(dPg - dPg.transpose(0, 2, 1)).max() <= 1e-13 * np.abs(dPg).max()
 
 
+def test_tangent_has_major_symmetry_point_by_point(ctx, reference_1000):
+    """the same figure with every point's own max |dP_p| for a scale: the large points of the batch no longer set the tolerance of the
+    small ones"""
+    dPg, _ = run_host(ctx, reference_1000[0])
+    asym = np.abs(dPg - dPg.transpose(0, 2, 1)).reshape(dPg.shape[0], -1).max(axis=1)
+    scale = np.abs(dPg).reshape(dPg.shape[0], -1).max(axis=1)
+    worst = int(np.argmax(asym / scale))
+    print(f"worst point {worst}: {asym[worst] / scale[worst]:.2e} of its own max |dP|")
+    assert np.all(asym <= 1e-13 * scale), (worst, asym[worst], scale[worst])
+
+
 # ------------------------------------------------------------------------------------------------------------ the fused form
 def _mesh(name):
     cell, n, degree, rule = {
