@@ -164,6 +164,8 @@ _SIGNATURES = {
     "dxo_mc_state_pointers": (C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(_P)]),
     "dxo_mohr_coulomb_state": (C.c_int, [_P, C.POINTER(McParams), _P, C.c_int] + [_P] * 7),
     "dxo_mohr_coulomb_field": (C.c_int, [_P, C.POINTER(McParams), _P, C.c_int] + [_P] * 8),
+    "dxo_mohr_coulomb3": (C.c_int, [_P, C.POINTER(McParams), C.c_int64, C.c_int] + [_P] * 8),
+    "dxo_mohr_coulomb3_field": (C.c_int, [_P, C.POINTER(McParams), _P, C.c_int] + [_P] * 8),
     "dxo_icnn_field": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
     "dxo_isihara_field": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, C.c_int, _P, _P, _P]),
     "dxo_isihara3_field": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, C.c_int, _P, _P, _P]),
@@ -610,6 +612,19 @@ class Context:
         rc = self.lib.dxo_mohr_coulomb_field(self._h, C.byref(prm), mesh_handle, int(mem), _ptr(u), _ptr(sigma_n), _ptr(C_tang),
                                              _ptr(sigma), _ptr(niter), _ptr(yielding), _ptr(norm_res), _ptr(dlambda))
         self.check(rc, "dxo_mohr_coulomb_field")
+
+    def mohr_coulomb3(self, prm: McParams, n: int, mem: int, deps, sigma_n, C_tang, sigma, niter=None, yielding=None,
+                      norm_res=None, dlambda=None) -> None:
+        """dxo_mohr_coulomb3: six Mandel components, deps / sigma_n [n][6] -> C_tang [n][6][6], sigma [n][6]."""
+        rc = self.lib.dxo_mohr_coulomb3(self._h, C.byref(prm), int(n), int(mem), _ptr(deps), _ptr(sigma_n), _ptr(C_tang),
+                                        _ptr(sigma), _ptr(niter), _ptr(yielding), _ptr(norm_res), _ptr(dlambda))
+        self.check(rc, "dxo_mohr_coulomb3")
+
+    def mohr_coulomb3_field(self, prm: McParams, mesh_handle, mem: int, u, sigma_n, C_tang, sigma, niter=None, yielding=None,
+                            norm_res=None, dlambda=None) -> None:
+        rc = self.lib.dxo_mohr_coulomb3_field(self._h, C.byref(prm), mesh_handle, int(mem), _ptr(u), _ptr(sigma_n), _ptr(C_tang),
+                                              _ptr(sigma), _ptr(niter), _ptr(yielding), _ptr(norm_res), _ptr(dlambda))
+        self.check(rc, "dxo_mohr_coulomb3_field")
 
     def icnn_field(self, model: int, precision: int, mesh_handle, mem: int, u, dP, P) -> None:
         self.check(self.lib.dxo_icnn_field(self._h, _P(model), int(precision), mesh_handle, int(mem), _ptr(u), _ptr(dP), _ptr(P)),

@@ -260,6 +260,9 @@ int dxo_operand_launch_range(dxo_ctx* ctx, const dxo_mesh* mesh, int kind, int b
 int dxo_mc_launch_device(dxo_ctx* ctx, const dxo_mc_params* prm, int64_t n, const double* deps, const double* sigma_n,
                          double* C_tang, double* sigma, int32_t* niter, double* yielding, double* norm_res, double* dlambda,
                          hipStream_t s);
+int dxo_mc3_launch_device(dxo_ctx* ctx, const dxo_mc_params* prm, int64_t n, const double* deps, const double* sigma_n,
+                          double* C_tang, double* sigma, int32_t* niter, double* yielding, double* norm_res, double* dlambda,
+                          hipStream_t s);
 int dxo_icnn_launch_device(dxo_ctx* ctx, const dxo_icnn* m, int precision, int64_t n, const double* F, double* dP, double* P,
                            hipStream_t s);
 int dxo_icnn3_launch_device(dxo_ctx* ctx, const dxo_icnn* m, int precision, int64_t n, const double* F, double* dP, double* P,

@@ -193,6 +193,45 @@ extern "C" int dxo_mohr_coulomb_field(dxo_ctx* ctx, const dxo_mc_params* prm, dx
     return run_field_op(ctx, L, mem, u, in, out, din, dout.data());
 }
 
+// the 3-D return map: eps(Du) of a gdim = 3 mesh (six Mandel components) into the staging buffer, then dxo_mohr_coulomb3's kernels
+extern "C" int dxo_mohr_coulomb3_field(dxo_ctx* ctx, const dxo_mc_params* prm, dxo_mesh* mesh, int mem, const double* u,
+                                       const double* sigma_n, double* C_tang, double* sigma, int32_t* niter, double* yielding,
+                                       double* norm_res, double* dlambda) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!prm) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb3_field: params is NULL");
+    if (!mesh) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb3_field: mesh is NULL");
+    if (mesh->gdim != 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_mohr_coulomb3_field: the strain has six components, the mesh must have gdim = 3");
+    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_mohr_coulomb3_field: bad mem");
+    if (prm->nitermax < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mohr_coulomb3_field: nitermax < 0");
+    if (mesh->num_cells == 0) return DXO_OK;
+    if (!u || !sigma_n || !C_tang || !sigma) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb3_field: NULL array");
+    const int arc = dxo_mc_check_align(ctx, "dxo_mohr_coulomb3_field", mem, (uintptr_t)sigma_n | (uintptr_t)C_tang | (uintptr_t)sigma,
+                                       "device sigma_n, C_tang, sigma must be 16-byte aligned",
+                                       (uintptr_t)u | (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda, niter);
+    if (arc != DXO_OK) return arc;
+    const bool has[4] = {niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
+    const dxo_mc_params P = *prm;
+    FieldOp L{mesh, nullptr, DXO_OPERAND_EPS_MANDEL};
+    L.width = 6;
+    L.consume = [P, has](dxo_ctx* c, const double* deps, int64_t n, void* const* d_in, void* const* d_out, hipStream_t s) {
+        int o = 2;
+        int32_t* it = has[0] ? (int32_t*)d_out[o++] : nullptr;
+        double* yl = has[1] ? (double*)d_out[o++] : nullptr;
+        double* nr = has[2] ? (double*)d_out[o++] : nullptr;
+        double* dl = has[3] ? (double*)d_out[o++] : nullptr;
+        return dxo_mc3_launch_device(c, &P, n, deps, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], it, yl, nr, dl, s);
+    };
+    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
+    std::vector<dxo_span> in = {{sigma_n, nullptr, 6 * sd}};
+    std::vector<dxo_span> out = {{nullptr, C_tang, 36 * sd}, {nullptr, sigma, 6 * sd}};
+    dxo_mc_optional_outputs(out, (size_t)mesh->dev.nq, niter, yielding, norm_res, dlambda);
+    std::vector<void*> dout = {C_tang, sigma};
+    for (size_t k = 2; k < out.size(); ++k) dout.push_back((void*)out[k].out);
+    void* din[1] = {const_cast<double*>(sigma_n)};
+    return run_field_op(ctx, L, mem, u, in, out, din, dout.data());
+}
+
 extern "C" int dxo_icnn_field(dxo_ctx* ctx, const dxo_icnn* model, int precision, dxo_mesh* mesh, int mem, const double* u,
                               double* dP, double* P) {
     if (!ctx) return DXO_E_NULL;

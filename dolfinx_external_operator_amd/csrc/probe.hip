@@ -61,6 +61,7 @@ extern "C" int dxo_stream_probe(dxo_ctx* ctx, int read_chunks, int write_chunks,
         if (read_chunks == 13 && write_chunks == 43) launch<13, 43>(ctx, n_tiles, src, dst, s);
         else if (read_chunks == 9 && write_chunks == 21) launch<9, 21>(ctx, n_tiles, src, dst, s);
         else if (read_chunks == 8 && write_chunks == 20) launch<8, 20>(ctx, n_tiles, src, dst, s);
+        else if (read_chunks == 6 && write_chunks == 21) launch<6, 21>(ctx, n_tiles, src, dst, s);
         else if (read_chunks == 3 && write_chunks == 8) launch<3, 8>(ctx, n_tiles, src, dst, s);
         else if (read_chunks == 1 && write_chunks == 1) launch<1, 1>(ctx, n_tiles, src, dst, s);
         else if (read_chunks == 4 && write_chunks == 4) launch<4, 4>(ctx, n_tiles, src, dst, s);

@@ -683,7 +683,7 @@ def make_mohr_coulomb(sigma_n, *, E: float = 6778.0, nu: float = 0.25, c: float 
                       phi: float = 30 * np.pi / 180, psi: float = 30 * np.pi / 180, theta_T: float = 26 * np.pi / 180,
                       a: float | None = None, tol: float = 1e-8, Nitermax: int = 200, diagnostics: bool = True,
                       on_summary: Callable | None = None, ctx: Context | None = None, device: int = 0,
-                      reuse_outputs: bool = False, outputs=None, state: str = "host") -> Callable:
+                      reuse_outputs: bool = False, outputs=None, state: str = "host", dim: int = 2) -> Callable:
     """`sigma_external` of the Mohr-Coulomb demo (demo_plasticity_mohr_coulomb.py:604-608) on the GPU.
 
     `external_function((1,))(deps) -> (C_tang, sigma)`, flat arrays, the reference's order (:593); any other
@@ -705,7 +705,18 @@ def make_mohr_coulomb(sigma_n, *, E: float = 6778.0, nu: float = 0.25, c: float 
                                          array: the same assignment on the device, no transfer;
       external_function.state_changed()  after ANY other change of the holder: re-upload at the next call;
       external_function.check_state()    max |mirror - holder| (tests, debugging).
+
+    dim = 3: the same model on the six-component Mandel strain (xx, yy, zz, sqrt2 xy, sqrt2 xz, sqrt2 yz) of a 3-D problem
+    (dxo_mohr_coulomb3): `deps` is (num_cells, nq, 6) (or anything reshaping to (-1, 6)), `sigma_n` six values per point, and the
+    result is flat C_tang (n * 36, the [n][6][6] block of the ("eps", "eps", bs = 3) bilinear pair) and sigma (n * 6). NumPy arrays,
+    CUDA tensors and a lazy "eps" operand of a gdim = 3 mesh are taken (the lazy operand by dxo_mohr_coulomb3_field). A lazy "eps"
+    operand of a mesh whose gdim differs from `dim` raises ValueError, and so does dim = 3 with state = "resident".
     """
+    if dim not in (2, 3):
+        raise ValueError("dim must be 2 (plane strain, four Mandel components) or 3 (six)")
+    if dim == 3 and state == "resident":
+        raise ValueError('make_mohr_coulomb(dim=3): state="resident" is plane strain only')
+    d = 4 if dim == 2 else 6
     if a is None:
         a = 0.26 * c / np.tan(phi)   # :116
     prm = McParams(float(E), float(nu), float(c), float(phi), float(psi), float(theta_T), float(a), float(tol),
@@ -722,29 +733,32 @@ def make_mohr_coulomb(sigma_n, *, E: float = 6778.0, nu: float = 0.25, c: float 
         if holder["out"] is None:
             holder["out"] = _Outputs(cx, reuse_outputs, dict(zip(("C_tang", "sigma"), holder["targets"])) if holder["targets"] is not None else None)
         if _is_device_tensor(deps):
-            return _mohr_coulomb_device(cx, prm, deps, _state_array(sigma_n), diagnostics, on_summary, sigma_external)
-        lazy = isinstance(deps, LazyOperand) and deps.kind == "eps" and deps.mesh.ctx is cx and deps.mesh.gdim == 2 and mirror is None
+            return _mohr_coulomb_device(cx, prm, deps, _state_array(sigma_n), diagnostics, on_summary, sigma_external, d)
+        if isinstance(deps, LazyOperand) and deps.kind == "eps" and deps.mesh.gdim != dim:
+            raise ValueError(f"make_mohr_coulomb(dim={dim}): the operand is the strain of a gdim = {deps.mesh.gdim} mesh")
+        lazy = isinstance(deps, LazyOperand) and deps.kind == "eps" and deps.mesh.ctx is cx and deps.mesh.gdim == dim and mirror is None
         if lazy:
             n = deps.shape[0] * deps.shape[1]
         else:
-            deps_ = _as_f64_host(deps, "deps").reshape((-1, 4))            # :578
+            deps_ = _as_f64_host(deps, "deps").reshape((-1, d))            # :578
             n = deps_.shape[0]
-        sigma_n_ = _as_f64_host(_state_array(sigma_n), "sigma_n").reshape((-1, 4))   # :579
+        sigma_n_ = _as_f64_host(_state_array(sigma_n), "sigma_n").reshape((-1, d))   # :579
         if sigma_n_.shape[0] != n:
             raise ValueError(f"state size mismatch: sigma_n has {sigma_n_.shape[0]} points, deps {n}")
-        C_tang = holder["out"].get("C_tang", n * 16)
-        sigma = holder["out"].get("sigma", n * 4)
+        C_tang = holder["out"].get("C_tang", n * d * d)
+        sigma = holder["out"].get("sigma", n * d)
         if diagnostics or on_summary is not None:
             niter = np.empty(n, dtype=np.int32)
             yielding, norm_res, dlambda = np.empty(n), np.empty(n), np.empty(n)
         else:
             niter = yielding = norm_res = dlambda = None
         if lazy:      # operand still unevaluated: eps(Du) on the device in front of the Newton kernels
-            cx.mohr_coulomb_field(prm, deps.mesh._h, MEM_HOST, deps.u, sigma_n_, C_tang, sigma, niter, yielding, norm_res, dlambda)
+            (cx.mohr_coulomb_field if dim == 2 else cx.mohr_coulomb3_field)(prm, deps.mesh._h, MEM_HOST, deps.u, sigma_n_, C_tang, sigma,
+                                                                            niter, yielding, norm_res, dlambda)
         elif mirror is not None:
             mirror.sync(cx, n, sigma_n_).call(prm, MEM_HOST, deps_, C_tang, sigma, niter, yielding, norm_res, dlambda)
         else:
-            cx.mohr_coulomb(prm, n, MEM_HOST, deps_, sigma_n_, C_tang, sigma, niter, yielding, norm_res, dlambda)
+            (cx.mohr_coulomb if dim == 2 else cx.mohr_coulomb3)(prm, n, MEM_HOST, deps_, sigma_n_, C_tang, sigma, niter, yielding, norm_res, dlambda)
         sigma_external.last_state = (niter, yielding, norm_res, dlambda)
         if on_summary is not None and n > 0:
             unique_iters, counts = np.unique(niter, return_counts=True)   # :584
@@ -757,19 +771,19 @@ def make_mohr_coulomb(sigma_n, *, E: float = 6778.0, nu: float = 0.25, c: float 
     return sigma_external
 
 
-def _mohr_coulomb_device(cx: Context, prm: McParams, deps, sigma_n, diagnostics: bool, on_summary, fn):
+def _mohr_coulomb_device(cx: Context, prm: McParams, deps, sigma_n, diagnostics: bool, on_summary, fn, d: int = 4):
     """Zero-copy Mohr-Coulomb: CUDA tensors in/out; the per-point diagnostics stay on the device
     (`external_function.last_state` holds CUDA tensors) and the summary the reference prints at every call
     (demo_plasticity_mohr_coulomb.py:584-591) is reduced on the GPU by dxo_mc_summary."""
     torch = _torch_stream(cx, deps)
     if deps.dtype != torch.float64:
         raise TypeError(f"deps: the HIP kernels are fp64, got {deps.dtype}")
-    deps = deps.contiguous().reshape(-1, 4)                          # :578
+    deps = deps.contiguous().reshape(-1, d)                          # :578
     n = deps.shape[0]
-    sigma_n = _dev_f64(sigma_n, "sigma_n", n * 4)                   # :579
+    sigma_n = _dev_f64(sigma_n, "sigma_n", n * d)                   # :579
     dev = deps.device
-    C_tang = torch.empty(n * 16, dtype=torch.float64, device=dev)
-    sigma = torch.empty(n * 4, dtype=torch.float64, device=dev)
+    C_tang = torch.empty(n * d * d, dtype=torch.float64, device=dev)
+    sigma = torch.empty(n * d, dtype=torch.float64, device=dev)
     if diagnostics or on_summary is not None:
         niter = torch.empty(n, dtype=torch.int32, device=dev)
         yielding, norm_res, dlambda = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
@@ -777,7 +791,7 @@ def _mohr_coulomb_device(cx: Context, prm: McParams, deps, sigma_n, diagnostics:
     else:
         niter = yielding = norm_res = dlambda = None
         aux = (None, None, None, None)
-    cx.mohr_coulomb(prm, n, MEM_DEVICE, deps.data_ptr(), sigma_n.data_ptr(), C_tang.data_ptr(), sigma.data_ptr(), *aux)
+    (cx.mohr_coulomb if d == 4 else cx.mohr_coulomb3)(prm, n, MEM_DEVICE, deps.data_ptr(), sigma_n.data_ptr(), C_tang.data_ptr(), sigma.data_ptr(), *aux)
     fn.last_state = (niter, yielding, norm_res, dlambda)
     if on_summary is not None and n > 0:
         smry = cx.mc_summary(n, niter, yielding, norm_res, nbins=int(prm.nitermax) + 1)

@@ -318,6 +318,20 @@ int dxo_mohr_coulomb(dxo_ctx* ctx, const dxo_mc_params* prm, int64_t n, int mem,
                      double* C_tang, double* sigma,
                      int32_t* niter, double* yielding, double* norm_res, double* dlambda);
 
+/* The same model for a six-component strain, the full 3-D form of dxo_mohr_coulomb: Mandel order
+ * (xx, yy, zz, sqrt2 xy, sqrt2 xz, sqrt2 yz), the order of the `eps` operand of a gdim = 3 mesh.
+ *   deps [n][6], sigma_n [n][6] (in);  C_tang [n][6][6] = d sigma / d deps through the Newton iterations, sigma [n][6] (out);
+ *   the same dxo_mc_params, the same optional diagnostics (dxo_mc_summary works on them), the same checks and error codes.
+ * The surface is a function of I1, J2 = s:s / 2 and J3 = det s; with zero out-of-plane shears in deps and sigma_n the in-plane
+ * entries are dxo_mohr_coulomb's. C_tang is the [n][6][6] block of the ("eps", "eps", bs = 3) bilinear pair and of
+ * tangent_apply, sigma the operand of the internal force. Kernels: classification (elastic points finished at HBM speed) +
+ * compacted Newton with lane refill; ctx option "mc_variant" = 0 selects the plain lane-per-point kernel (bit-identical),
+ * "mc_part_points" the points per classify / Newton pass. DXO_MEM_DEVICE needs 16-byte aligned deps/sigma_n/C_tang/sigma. */
+int dxo_mohr_coulomb3(dxo_ctx* ctx, const dxo_mc_params* prm, int64_t n, int mem,
+                      const double* deps, const double* sigma_n,
+                      double* C_tang, double* sigma,
+                      int32_t* niter, double* yielding, double* norm_res, double* dlambda);
+
 /* History variable resident on the device, the Mohr-Coulomb counterpart of dxo_vm_state: the
  * reference's callback re-reads sigma_n from a closure-captured host array at every call
  * (demo_plasticity_mohr_coulomb.py:579) although it changes only at the end of a load step
@@ -1083,6 +1097,12 @@ int dxo_icnn_field(dxo_ctx* ctx, const dxo_icnn* model, int precision, dxo_mesh*
                    double* dP, double* P);
 int dxo_isihara_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, int mem, const double* u,
                       double* dP, double* P);
+/* dxo_mohr_coulomb3 with the operand formed on the device: eps(Du) of a gdim = 3 mesh (six Mandel components) into the
+ * staging buffer, then dxo_mohr_coulomb3's kernels. u: num_field_nodes*3 doubles; sigma_n and the outputs cover all cells,
+ * n = num_cells*nq points. Bit-identical to dxo_eval_operand followed by dxo_mohr_coulomb3. A mesh with gdim != 3: DXO_E_DIM. */
+int dxo_mohr_coulomb3_field(dxo_ctx* ctx, const dxo_mc_params* prm, dxo_mesh* mesh, int mem, const double* u,
+                            const double* sigma_n, double* C_tang, double* sigma, int32_t* niter, double* yielding,
+                            double* norm_res, double* dlambda);
 
 /* The analytic Isihara energy for a 3x3 deformation gradient, the full 3-D form of dxo_isihara's:
  *   W = c1 (I1bar-3) + c2 (I2bar-3) + c3 (I1bar-3)^2 + c4 (J-1)^2,  I1bar = J^(-2/3) I1, I2bar = J^(-4/3) I2,
@@ -1203,7 +1223,7 @@ int dxo_mgpu_von_mises_host(dxo_mgpu* g, const dxo_vm_params* prm, int d, int64_
  * Moves data with no arithmetic in the read : write mix of a constitutive kernel, lane-linear 16-byte
  * accesses: n_tiles tiles, each 64 lanes x read_chunks 16-byte loads and 64 x write_chunks 16-byte
  * stores. Supported mixes (read, write): (13,43) von Mises d=6, (9,21) von Mises d=4, (8,20)
- * Mohr-Coulomb, (3,8) heat, (1,1) and (4,4) plain copy. src needs n_tiles*read_chunks*1024 bytes, dst
+ * Mohr-Coulomb, (6,21) Mohr-Coulomb on six components, (3,8) heat, (1,1) and (4,4) plain copy. src needs n_tiles*read_chunks*1024 bytes, dst
  * n_tiles*write_chunks*1024 bytes. bench.py reports its GB/s beside the 8 TB/s spec peak. */
 int dxo_stream_probe(dxo_ctx* ctx, int read_chunks, int write_chunks, int64_t n_tiles,
                      const void* src, void* dst);
