@@ -169,6 +169,9 @@ _SIGNATURES = {
     "dxo_icnn_field": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
     "dxo_isihara_field": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, C.c_int, _P, _P, _P]),
     "dxo_isihara3_field": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, C.c_int, _P, _P, _P]),
+    "dxo_isihara3_residual": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, _P, _P]),
+    "dxo_isihara3_tangent_apply": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, _P, _P, _P]),
+    "dxo_isihara3_tangent_diagonal": (C.c_int, [_P, C.POINTER(IsiharaParams), _P, _P, _P]),
     "dxo_conductivity": (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, C.c_int, _P, _P, _P]),
     "dxo_mc_summary": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "dxo_icnn_create": (C.c_int, [_P, C.POINTER(IcnnWeights), C.POINTER(_P)]),

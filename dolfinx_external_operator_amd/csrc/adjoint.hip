@@ -1251,3 +1251,6 @@ extern "C" int dxo_tangent_diagonal_vm(dxo_ctx* ctx, dxo_mesh* mesh, const dxo_v
 
 // dxo_bilinear_apply / dxo_bilinear_diagonal: the same two operators for a general pair of linear operand kinds (bilinear.h)
 #include "bilinear.h"
+
+// dxo_isihara3_residual / _tangent_apply / _tangent_diagonal: the 3-D hyperelastic consumers as functions of u alone (hyper3_form.h)
+#include "hyper3_form.h"

@@ -110,6 +110,48 @@ __device__ __forceinline__ void isihara3_tangent(const Isi3Point& q, double (&H)
         }
 }
 
+// t = H : dF without H, the H_IJ formula above contracted with dF term by term (the array-free action, hyper3_form.h):
+//   t_I = 2 W_t dF_I + W_s d2s[dF]_I + W_D d2D[dF]_I + 4 W_tt F_I (F:dF) + 2 W_tD (F_I (gD:dF) + gD_I (F:dF)) + W_DD gD_I (gD:dF)
+//         + W_sD (gs_I (gD:dF) + gD_I (gs:dF)),
+//   d2s[dF] = 4 (dF C + F dF^T F + F F^T dF) = 4 (dF C + F (N + N^T)), N = dF^T F;   d2D[dF]_ia = e_ijk e_abc dF_jb F_kc,
+// the directional derivative of the cofactor. About 150 flops from the point's 27 doubles and 7 coefficients.
+// det F <= 0: the coefficients are NaN, and 2 W_t dF_I alone makes every t_I NaN, also where dF = 0.
+__device__ __forceinline__ void isihara3_tangent_times(const Isi3Point& q, const double (&dF)[9], double (&t)[9]) {
+    const double (&F)[9] = q.F;
+    double fd = 0.0, dd = 0.0, sd = 0.0;      // F:dF, gD:dF, gs:dF
+#pragma unroll
+    for (int I = 0; I < 9; ++I) {
+        fd = fma(F[I], dF[I], fd);
+        dd = fma(q.gD[I], dF[I], dd);
+        sd = fma(q.gs[I], dF[I], sd);
+    }
+    double C[3][3], S[3][3];      // F^T F; N + N^T
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) {
+            C[a][b] = C[b][a] = F[a] * F[b] + F[3 + a] * F[3 + b] + F[6 + a] * F[6 + b];
+            S[a][b] = S[b][a] = (dF[a] * F[b] + dF[3 + a] * F[3 + b] + dF[6 + a] * F[6 + b]) +
+                                (dF[b] * F[a] + dF[3 + b] * F[3 + a] + dF[6 + b] * F[6 + a]);
+        }
+    const double cF = fma(q.Wtt4, fd, q.WtD2 * dd);                          // of F_I
+    const double cD = fma(q.WtD2, fd, fma(q.WDD, dd, q.WsD * sd));           // of gD_I
+    const double cs = q.WsD * dd;                                            // of gs_I
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int b = (a + 1) % 3, c = (a + 2) % 3, I = 3 * i + a;
+            const double d2s = (dF[3 * i] * C[0][a] + dF[3 * i + 1] * C[1][a] + dF[3 * i + 2] * C[2][a]) +
+                               (F[3 * i] * S[0][a] + F[3 * i + 1] * S[1][a] + F[3 * i + 2] * S[2][a]);
+            const double d2D = (dF[3 * j + b] * F[3 * k + c] - dF[3 * j + c] * F[3 * k + b]) +
+                               (F[3 * j + b] * dF[3 * k + c] - F[3 * j + c] * dF[3 * k + b]);
+            t[I] = fma(q.Wt2, dF[I], fma(q.Ws4, d2s, fma(q.WD, d2D, fma(cF, F[I], fma(cD, q.gD[I], cs * q.gs[I])))));
+        }
+    }
+}
+
 // ---- the general form: W any function of (t, s, D), given by its nine partials at the point (the network of icnn.hip, whose feature
 // K2 is linear in s and whose Hessian couples all three features, so W_ts and W_ss do not vanish):
 //   P_I  = 2 W_t F_I + W_s gs_I + W_D gD_I

@@ -602,6 +602,24 @@ class DeviceMesh:
                                                  (u_ptr, sigma_n_ptr, p_ptr, sigma_ptr, dp_ptr, R_ptr)))
         self.ctx.check(rc, "dxo_von_mises_residual")
 
+    def isihara3_residual(self, prm, u_ptr: int, R_ptr: int) -> None:
+        """R += sum_q w|J| B^T P(I + grad u) of the 3-D Isihara model, stress formed per point from the dof vector — no P array
+        (dxo_isihara3_residual; DEVICE pointers, gdim = 3): isihara3_field followed by adjoint("F", 3) without the 720 bytes per point."""
+        rc = self.ctx.lib.dxo_isihara3_residual(self.ctx._h, C.byref(prm), self._h, C.c_void_p(u_ptr), C.c_void_p(R_ptr))
+        self.ctx.check(rc, "dxo_isihara3_residual")
+
+    def isihara3_tangent_apply(self, prm, u_ptr: int, v_ptr: int, out_ptr: int) -> None:
+        """out += K(u) v with dP/dF : grad v formed per point from the dof vectors u and v — no dP array (dxo_isihara3_tangent_apply;
+        DEVICE pointers): bilinear_apply("grad", "grad", 3, dP, v) without the 648 bytes per point read at every matvec."""
+        rc = self.ctx.lib.dxo_isihara3_tangent_apply(self.ctx._h, C.byref(prm), self._h, C.c_void_p(u_ptr), C.c_void_p(v_ptr),
+                                                     C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_isihara3_tangent_apply")
+
+    def isihara3_tangent_diagonal(self, prm, u_ptr: int, out_ptr: int) -> None:
+        """out += diag(K(u)) from the dof vector (dxo_isihara3_tangent_diagonal): Jacobi preconditioner of the same operator."""
+        rc = self.ctx.lib.dxo_isihara3_tangent_diagonal(self.ctx._h, C.byref(prm), self._h, C.c_void_p(u_ptr), C.c_void_p(out_ptr))
+        self.ctx.check(rc, "dxo_isihara3_tangent_diagonal")
+
     def heat(self, A: float, B: float, T_dofs, q=None, dqdT=None, dqdsigma=None, mem: int = MEM_HOST) -> None:
         """dxo_heat_field: T and grad T of a scalar field + the heat-flux kernels in one launch (all cells)."""
         def ptr(a):

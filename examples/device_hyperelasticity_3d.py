@@ -12,6 +12,9 @@ Per Newton iteration:
       solve J d = -R                             cg (or gmres)
     --matrix-free:
       K v: dxo_bilinear_apply("grad", "grad", 3, dP), diag(K): dxo_bilinear_diagonal, Jacobi-preconditioned cg
+    --matrix-free --recompute (--model isihara only): no quadrature array at all. R, K v and diag(K) are formed from u alone,
+      F = I + grad u and the model evaluated again in the registers of every call (dxo_isihara3_residual,
+      dxo_isihara3_tangent_apply, dxo_isihara3_tangent_diagonal): dP [n][9][9] and P [n][9], 720 bytes per point, are never allocated
     u += d
 Only dof vectors are touched outside the kernels; they are torch CUDA tensors.
 
@@ -24,7 +27,7 @@ operand kernel, then the network kernel on the invariants of the 3x3 F). FILE is
 (`Isihara_noise=high.pth`) or an .npz with '__' for '.' in the keys. --precision fp64 (the default here) evaluates the network in
 fp64, so that stress and tangent are consistent to fp64 rounding and the residual can fall by the ten decades the Newton loop asks
 for; with fp32, the reference's network precision, the stress carries fp32 rounding (about 1e-7) and the loop's tolerance may be out of reach.
-Needs an MI355X.    python3 examples/device_hyperelasticity_3d.py [--n 6] [--hex] [--matrix-free] [--solver cg|gmres]
+Needs an MI355X.    python3 examples/device_hyperelasticity_3d.py [--n 6] [--hex] [--matrix-free [--recompute]] [--solver cg|gmres]
                                                                    [--model isihara|icnn] [--weights FILE] [--precision fp32|fp64]
 """
 import argparse
@@ -66,9 +69,12 @@ def load_state_dict(path):
 
 def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float = 0.4, hexahedra: bool = False, matrix_free: bool = False,
          solver: str = "cg", verbose: bool = True, c=(0.5, 1.0, 1.0, 1.5), model: str = "isihara", weights=None,
-         precision: str = "fp64") -> dict:
-    """Returns the per-step Newton residual histories, the linear iteration counts and the final displacement (`u`, host array).
+         precision: str = "fp64", recompute: bool = False) -> dict:
+    """Returns the per-step Newton residual histories, the linear iteration counts, the bytes of quadrature data held
+    (`quadrature_bytes`: dP and P, 720 per point; 0 with `recompute`) and the final displacement (`u`, host array).
     Raises RuntimeError if a load step does not converge within MAX_NEWTON iterations or a linear solve fails."""
+    if recompute and not (matrix_free and model == "isihara"):
+        raise ValueError("recompute needs matrix_free and the analytic model (--matrix-free --model isihara)")
     dev = torch.device("cuda:0")
     ctx = Context(0)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -96,13 +102,16 @@ def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float =
 
     f64 = dict(dtype=torch.float64, device=dev)
     u = torch.zeros(nn * G, **f64)
-    dP, P = torch.zeros(npts * 81, **f64), torch.zeros(npts * 9, **f64)
+    dP, P = (None, None) if recompute else (torch.zeros(npts * 81, **f64), torch.zeros(npts * 9, **f64))
     R, Kv, diag = (torch.zeros(nn * G, **f64) for _ in range(3))
     state = {}
     krylov = {"cg": cg, "gmres": gmres}[solver]
 
     def residual():
-        """(dP, P) at the current u and the assembled inner(grad v, P) dx on the free dofs"""
+        """(dP, P) at the current u and the assembled inner(grad v, P) dx on the free dofs; with recompute, the latter from u alone"""
+        if recompute:
+            dm.isihara3_residual(prm, u.data_ptr(), R.data_ptr())
+            return torch.where(free, R, torch.zeros_like(R))
         if net is None:
             ctx.isihara3_field(prm, dm._h, MEM_DEVICE, u.data_ptr(), dP.data_ptr(), P.data_ptr())
         else:
@@ -124,15 +133,24 @@ def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float =
     def jacobian_times(v, out):
         """out = K v with the Dirichlet rows and columns of the assembled form: identity on the fixed dofs"""
         vm = torch.where(free, v, torch.zeros_like(v))
-        dm.bilinear_apply("grad", "grad", G, dP.data_ptr(), vm.data_ptr(), Kv.data_ptr())
+        if recompute:
+            dm.isihara3_tangent_apply(prm, u.data_ptr(), vm.data_ptr(), Kv.data_ptr())
+        else:
+            dm.bilinear_apply("grad", "grad", G, dP.data_ptr(), vm.data_ptr(), Kv.data_ptr())
         out.copy_(torch.where(free, Kv, v))
 
     def solve_matrix_free(b):
-        dm.bilinear_diagonal("grad", "grad", G, dP.data_ptr(), diag.data_ptr())
+        if recompute:
+            dm.isihara3_tangent_diagonal(prm, u.data_ptr(), diag.data_ptr())
+        else:
+            dm.bilinear_diagonal("grad", "grad", G, dP.data_ptr(), diag.data_ptr())
         minv = torch.where(free, 1.0 / diag, torch.ones_like(diag))
         return krylov(jacobian_times, b, M=minv, rtol=1e-12, maxiter=20000, ctx=ctx)
 
-    report = {"cells": mesh.num_cells, "points": npts, "dofs": nn * G, "matrix_free": matrix_free, "solver": solver, "model": model, "steps": []}
+    report = {"cells": mesh.num_cells, "points": npts, "dofs": nn * G, "matrix_free": matrix_free, "solver": solver, "model": model, "recompute": recompute,
+              "quadrature_bytes": sum(t.numel() * t.element_size() for t in (dP, P) if t is not None), "steps": []}
+    if verbose:
+        print(f"{npts} points, quadrature data held: {report['quadrature_bytes']} bytes ({'none' if recompute else '720 per point: dP [n][9][9] and P [n][9]'})")
     prev = np.zeros_like(x)
     for k in range(1, steps + 1):
         lam = k / steps
@@ -176,9 +194,14 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=3, help="load steps")
     ap.add_argument("--hex", action="store_true", help="Q2 hexahedra with the 27-point rule instead of P2 tetrahedra")
     ap.add_argument("--matrix-free", action="store_true", help="Jacobi-preconditioned Krylov solve on bilinear_apply, nothing assembled")
+    ap.add_argument("--recompute", action="store_true", help="with --matrix-free --model isihara: residual, K v and diag(K) from u alone, "
+                    "no quadrature array (dP, P) is allocated")
     ap.add_argument("--solver", choices=["cg", "gmres"], default="cg")
     ap.add_argument("--model", choices=["isihara", "icnn"], default="isihara", help="the analytic energy (default) or the trained network")
     ap.add_argument("--weights", help="--model icnn: the network's state_dict (torch file or .npz)")
     ap.add_argument("--precision", choices=["fp32", "fp64"], default="fp64", help="--model icnn: precision of the network")
     a = ap.parse_args()
-    main(a.n, steps=a.steps, hexahedra=a.hex, matrix_free=a.matrix_free, solver=a.solver, model=a.model, weights=a.weights, precision=a.precision)
+    if a.recompute and not (a.matrix_free and a.model == "isihara"):
+        ap.error("--recompute is valid only with --matrix-free and --model isihara")
+    main(a.n, steps=a.steps, hexahedra=a.hex, matrix_free=a.matrix_free, solver=a.solver, model=a.model, weights=a.weights, precision=a.precision,
+         recompute=a.recompute)

@@ -1117,6 +1117,22 @@ int dxo_isihara3(dxo_ctx* ctx, const dxo_isihara_params* prm, int64_t n, int mem
                  const double* F, double* dP, double* P);
 int dxo_isihara3_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, int mem, const double* u,
                        double* dP, double* P);
+/* The three consumers of dxo_isihara3_field's outputs as functions of the dof vector u alone, WITHOUT the quadrature arrays: the model
+ * has no history, so F = I + grad u, the stress and the tangent's action are formed again in the registers of every call (the action
+ * dP/dF : grad v costs about 150 flops per point and never forms the 45-entry Hessian) and dP[n][9][9], P[n][9] (720 B per point) need
+ * not exist. For a matrix-free Newton-Krylov solve on a gdim = 3 mesh, bs = 3:
+ *   dxo_isihara3_residual          R   (+)= sum_q w|det J| B^T P(I + grad u)                  = dxo_isihara3_field + dxo_operand_adjoint("F")
+ *   dxo_isihara3_tangent_apply     out (+)= sum_q w|det J| B^T (dP/dF(I + grad u) : grad v)  = ... + dxo_bilinear_apply(grad, grad, 3)
+ *   dxo_isihara3_tangent_diagonal  the diagonal of the same operator                        = ... + dxo_bilinear_diagonal(grad, grad, 3)
+ * to rounding (the contractions run in another order). Consumer semantics as dxo_bilinear_apply: DEVICE pointers only, u / v / R / out
+ * num_field_nodes*3 doubles, out += (SET with option consumer_overwrite), two passes without atomics where the mesh allows them,
+ * bit-reproducible, capture-safe; weights from dxo_mesh_set_weights. det F <= 0 at a point: NaN in every dof of its cell, as the array
+ * route. DXO_E_NULL for a NULL params, mesh or array, DXO_E_DIM for gdim != 3, DXO_E_OPTION without weights, DXO_E_ALIGN for an array
+ * not 8-byte aligned, DXO_E_SIZE for an element too large for the LDS budget (no mesh the array route accepts); num_cells == 0: DXO_OK. */
+int dxo_isihara3_residual(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, const double* u, double* R);
+int dxo_isihara3_tangent_apply(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, const double* u, const double* v,
+                               double* out);
+int dxo_isihara3_tangent_diagonal(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, const double* u, double* out);
 
 /* The network operator for a 3x3 deformation gradient: the SAME dxo_icnn model (one weight set serves both dimensions) evaluated
  * on the invariants of the full C = F^T F,
