@@ -10,7 +10,7 @@ SRCS    := $(wildcard $(CSRC)/*.hip)
 OBJS    := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 FLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Iinclude -I$(CSRC)
 
-# icnn.hip: no SLP re-packing of the neuron-pair fp32 arithmetic into v_pk_*_f32 (see the comment at icnn_f2 there)
+# icnn.hip: no SLP re-packing of the neuron-pair fp32 arithmetic into v_pk_*_f32 (see the comment at icnn_f2 in scripts/exp/icnn_variants.h)
 $(OBJDIR)/icnn.o: FLAGS += -fno-slp-vectorize
 
 all: $(LIB)

@@ -43,7 +43,8 @@ def hip_flags() -> list[str]:
 
 
 # per-file flags on top of hip_flags(). icnn.hip: the SLP vectoriser must not re-pack the neuron-pair fp32 arithmetic into
-# v_pk_*_f32 (a packed fp32 instruction beside a running MFMA stalls ~20 cycles, see the comment at icnn_f2)
+# v_pk_*_f32 (a packed fp32 instruction beside a running MFMA stalls ~20 cycles, see the comment at icnn_f2 in
+# scripts/exp/icnn_variants.h)
 EXTRA_FLAGS = {"icnn.hip": ["-fno-slp-vectorize"]}
 
 

@@ -16,8 +16,7 @@
 // Host arrays: the field vector goes up whole, cells stream through the chunked pipeline (units of CELLS), every chunk
 // = operand launch + constitutive launch on the chunk's stream.
 #include "dxo_common.h"
-#include "hyper_core.h"
-#include "form_host.h"
+#include "hyper_host.h"
 
 namespace {
 
@@ -73,13 +72,6 @@ __global__ __launch_bounds__(DXO_BLOCK) void isihara_field(IsiPrm prm, OperandDe
     }
 }
 
-struct IsiFieldLaunch {
-    IsiPrm prm;
-    dxo_mesh* mesh;
-    const double* d_u;
-    int64_t next_cell = 0;
-};
-
 int isi_field_launch(dxo_ctx* ctx, const IsiFieldLaunch& L, int64_t cell0, int64_t n_cells, double* dP, double* P, hipStream_t s) {
     if (n_cells == 0) return DXO_OK;
     const OperandDev& m = L.mesh->dev;
@@ -92,13 +84,6 @@ int isi_field_launch(dxo_ctx* ctx, const IsiFieldLaunch& L, int64_t cell0, int64
     if (ctx->nontemporal != 0) hipLaunchKernelGGL(isihara_field<true>, dim3(blocks), dim3(DXO_BLOCK), shm, s, L.prm, m, wd, cell0, n_cells, L.d_u, dP, P);
     else hipLaunchKernelGGL(isihara_field<false>, dim3(blocks), dim3(DXO_BLOCK), shm, s, L.prm, m, wd, cell0, n_cells, L.d_u, dP, P);
     return DXO_OK;
-}
-
-int isi_field_chunk(dxo_ctx* ctx, void* user, int64_t n_chunk, void* const*, void* const* d_out, hipStream_t s) {
-    IsiFieldLaunch& L = *static_cast<IsiFieldLaunch*>(user);
-    const int64_t cell0 = L.next_cell;
-    L.next_cell += n_chunk;
-    return isi_field_launch(ctx, L, cell0, n_chunk, (double*)d_out[0], (double*)d_out[1], s);
 }
 
 struct FieldOp {
@@ -149,10 +134,65 @@ int run_field_op(dxo_ctx* ctx, FieldOp& L, int mem, const double* u, const std::
     return dxo_run_host_pipeline(ctx, nc, in, out, field_op_chunk, &L, L.mesh->dev.nq);
 }
 
-const char* check_mesh_2d(const dxo_mesh* mesh) {
-    if (!mesh) return "mesh is NULL";
-    if (mesh->gdim != 2) return "the operator is plane strain / 2-D (Mandel length 4, F 2x2): the mesh must have gdim = 2";
-    return nullptr;
+// ---- the 2-D and 3-D forms of an entry share one body: the widths, the 3-D mesh text and the launcher behind them differ
+int mc_field(dxo_ctx* ctx, const char* who, int dim, const dxo_mc_params* prm, dxo_mesh* mesh, int mem, const double* u, const double* sigma_n,
+             double* C_tang, double* sigma, int32_t* niter, double* yielding, double* norm_res, double* dlambda) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!prm) return fail_who(ctx, DXO_E_NULL, who, "params is NULL");
+    const int mrc = field_check_mesh(ctx, who, dim, mesh, "the strain has six components, the mesh must have gdim = 3");
+    if (mrc != DXO_OK) return mrc;
+    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return fail_who(ctx, DXO_E_MEM, who, "bad mem");
+    if (prm->nitermax < 0) return fail_who(ctx, DXO_E_SIZE, who, "nitermax < 0");
+    if (mesh->num_cells == 0) return DXO_OK;
+    if (!u || !sigma_n || !C_tang || !sigma) return fail_who(ctx, DXO_E_NULL, who, "NULL array");
+    const int arc = dxo_mc_check_align(ctx, who, mem, (uintptr_t)sigma_n | (uintptr_t)C_tang | (uintptr_t)sigma,
+                                       "device sigma_n, C_tang, sigma must be 16-byte aligned",
+                                       (uintptr_t)u | (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda, niter);
+    if (arc != DXO_OK) return arc;
+    const bool has[4] = {niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
+    const dxo_mc_params P = *prm;
+    const auto launch = dim == 2 ? dxo_mc_launch_device : dxo_mc3_launch_device;
+    const int width = dim == 2 ? 4 : 6;       // Mandel components of the strain and the stress
+    FieldOp L{mesh, nullptr, DXO_OPERAND_EPS_MANDEL};
+    L.width = width;
+    L.consume = [P, has, launch](dxo_ctx* c, const double* deps, int64_t n, void* const* d_in, void* const* d_out, hipStream_t s) {
+        int o = 2;
+        int32_t* it = has[0] ? (int32_t*)d_out[o++] : nullptr;
+        double* yl = has[1] ? (double*)d_out[o++] : nullptr;
+        double* nr = has[2] ? (double*)d_out[o++] : nullptr;
+        double* dl = has[3] ? (double*)d_out[o++] : nullptr;
+        return launch(c, &P, n, deps, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], it, yl, nr, dl, s);
+    };
+    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
+    std::vector<dxo_span> in = {{sigma_n, nullptr, width * sd}};
+    std::vector<dxo_span> out = {{nullptr, C_tang, width * width * sd}, {nullptr, sigma, width * sd}};
+    dxo_mc_optional_outputs(out, (size_t)mesh->dev.nq, niter, yielding, norm_res, dlambda);
+    std::vector<void*> dout = {C_tang, sigma};
+    for (size_t k = 2; k < out.size(); ++k) dout.push_back((void*)out[k].out);
+    void* din[1] = {const_cast<double*>(sigma_n)};
+    return run_field_op(ctx, L, mem, u, in, out, din, dout.data());
+}
+
+// F = I + grad u into the staging buffer, then the network kernel of dxo_icnn_eval / dxo_icnn3_eval
+int icnn_field(dxo_ctx* ctx, const char* who, int dim, const dxo_icnn* model, int precision, dxo_mesh* mesh, int mem, const double* u,
+               double* dP, double* P) {
+    if (!ctx) return DXO_E_NULL;
+    DXO_LOCK(ctx);
+    if (!model) return fail_who(ctx, DXO_E_NULL, who, "model is NULL");
+    const int rc = hyper_field_check(ctx, who, dim, mesh, mem, u, dP, P, precision);
+    if (rc != DXO_OK || mesh->num_cells == 0) return rc;
+    const auto launch = dim == 2 ? dxo_icnn_launch_device : dxo_icnn3_launch_device;
+    FieldOp L{mesh, nullptr, DXO_OPERAND_DEFGRAD};
+    L.width = dim * dim;
+    L.consume = [model, precision, launch](dxo_ctx* c, const double* F, int64_t n, void* const*, void* const* d_out, hipStream_t s) {
+        return launch(c, model, precision, n, F, (double*)d_out[0], (double*)d_out[1], s);
+    };
+    const size_t row = sizeof(double) * (size_t)mesh->dev.nq * dim * dim;
+    std::vector<dxo_span> in;
+    std::vector<dxo_span> out = {{nullptr, dP, row * dim * dim}, {nullptr, P, row}};
+    void* dout[2] = {dP, P};
+    return run_field_op(ctx, L, mem, u, in, out, nullptr, dout);
 }
 
 }  // namespace
@@ -160,127 +200,25 @@ const char* check_mesh_2d(const dxo_mesh* mesh) {
 extern "C" int dxo_mohr_coulomb_field(dxo_ctx* ctx, const dxo_mc_params* prm, dxo_mesh* mesh, int mem, const double* u,
                                       const double* sigma_n, double* C_tang, double* sigma, int32_t* niter, double* yielding,
                                       double* norm_res, double* dlambda) {
-    if (!ctx) return DXO_E_NULL;
-    DXO_LOCK(ctx);
-    if (!prm) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb_field: params is NULL");
-    if (const char* why = check_mesh_2d(mesh)) return dxo_fail(ctx, mesh ? DXO_E_DIM : DXO_E_NULL, why);
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_mohr_coulomb_field: bad mem");
-    if (prm->nitermax < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mohr_coulomb_field: nitermax < 0");
-    if (mesh->num_cells == 0) return DXO_OK;
-    if (!u || !sigma_n || !C_tang || !sigma) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb_field: NULL array");
-    const int arc = dxo_mc_check_align(ctx, "dxo_mohr_coulomb_field", mem, (uintptr_t)sigma_n | (uintptr_t)C_tang | (uintptr_t)sigma,
-                                       "device sigma_n, C_tang, sigma must be 16-byte aligned",
-                                       (uintptr_t)u | (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda, niter);
-    if (arc != DXO_OK) return arc;
-    const bool has[4] = {niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
-    const dxo_mc_params P = *prm;
-    FieldOp L{mesh, nullptr, DXO_OPERAND_EPS_MANDEL};
-    L.consume = [P, has](dxo_ctx* c, const double* deps, int64_t n, void* const* d_in, void* const* d_out, hipStream_t s) {
-        int o = 2;
-        int32_t* it = has[0] ? (int32_t*)d_out[o++] : nullptr;
-        double* yl = has[1] ? (double*)d_out[o++] : nullptr;
-        double* nr = has[2] ? (double*)d_out[o++] : nullptr;
-        double* dl = has[3] ? (double*)d_out[o++] : nullptr;
-        return dxo_mc_launch_device(c, &P, n, deps, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], it, yl, nr, dl, s);
-    };
-    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
-    std::vector<dxo_span> in = {{sigma_n, nullptr, 4 * sd}};
-    std::vector<dxo_span> out = {{nullptr, C_tang, 16 * sd}, {nullptr, sigma, 4 * sd}};
-    dxo_mc_optional_outputs(out, (size_t)mesh->dev.nq, niter, yielding, norm_res, dlambda);
-    std::vector<void*> dout = {C_tang, sigma};
-    for (size_t k = 2; k < out.size(); ++k) dout.push_back((void*)out[k].out);
-    void* din[1] = {const_cast<double*>(sigma_n)};
-    return run_field_op(ctx, L, mem, u, in, out, din, dout.data());
+    return mc_field(ctx, "dxo_mohr_coulomb_field", 2, prm, mesh, mem, u, sigma_n, C_tang, sigma, niter, yielding, norm_res, dlambda);
 }
 
 // the 3-D return map: eps(Du) of a gdim = 3 mesh (six Mandel components) into the staging buffer, then dxo_mohr_coulomb3's kernels
 extern "C" int dxo_mohr_coulomb3_field(dxo_ctx* ctx, const dxo_mc_params* prm, dxo_mesh* mesh, int mem, const double* u,
                                        const double* sigma_n, double* C_tang, double* sigma, int32_t* niter, double* yielding,
                                        double* norm_res, double* dlambda) {
-    if (!ctx) return DXO_E_NULL;
-    DXO_LOCK(ctx);
-    if (!prm) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb3_field: params is NULL");
-    if (!mesh) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb3_field: mesh is NULL");
-    if (mesh->gdim != 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_mohr_coulomb3_field: the strain has six components, the mesh must have gdim = 3");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_mohr_coulomb3_field: bad mem");
-    if (prm->nitermax < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_mohr_coulomb3_field: nitermax < 0");
-    if (mesh->num_cells == 0) return DXO_OK;
-    if (!u || !sigma_n || !C_tang || !sigma) return dxo_fail(ctx, DXO_E_NULL, "dxo_mohr_coulomb3_field: NULL array");
-    const int arc = dxo_mc_check_align(ctx, "dxo_mohr_coulomb3_field", mem, (uintptr_t)sigma_n | (uintptr_t)C_tang | (uintptr_t)sigma,
-                                       "device sigma_n, C_tang, sigma must be 16-byte aligned",
-                                       (uintptr_t)u | (uintptr_t)yielding | (uintptr_t)norm_res | (uintptr_t)dlambda, niter);
-    if (arc != DXO_OK) return arc;
-    const bool has[4] = {niter != nullptr, yielding != nullptr, norm_res != nullptr, dlambda != nullptr};
-    const dxo_mc_params P = *prm;
-    FieldOp L{mesh, nullptr, DXO_OPERAND_EPS_MANDEL};
-    L.width = 6;
-    L.consume = [P, has](dxo_ctx* c, const double* deps, int64_t n, void* const* d_in, void* const* d_out, hipStream_t s) {
-        int o = 2;
-        int32_t* it = has[0] ? (int32_t*)d_out[o++] : nullptr;
-        double* yl = has[1] ? (double*)d_out[o++] : nullptr;
-        double* nr = has[2] ? (double*)d_out[o++] : nullptr;
-        double* dl = has[3] ? (double*)d_out[o++] : nullptr;
-        return dxo_mc3_launch_device(c, &P, n, deps, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], it, yl, nr, dl, s);
-    };
-    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
-    std::vector<dxo_span> in = {{sigma_n, nullptr, 6 * sd}};
-    std::vector<dxo_span> out = {{nullptr, C_tang, 36 * sd}, {nullptr, sigma, 6 * sd}};
-    dxo_mc_optional_outputs(out, (size_t)mesh->dev.nq, niter, yielding, norm_res, dlambda);
-    std::vector<void*> dout = {C_tang, sigma};
-    for (size_t k = 2; k < out.size(); ++k) dout.push_back((void*)out[k].out);
-    void* din[1] = {const_cast<double*>(sigma_n)};
-    return run_field_op(ctx, L, mem, u, in, out, din, dout.data());
+    return mc_field(ctx, "dxo_mohr_coulomb3_field", 3, prm, mesh, mem, u, sigma_n, C_tang, sigma, niter, yielding, norm_res, dlambda);
 }
 
 extern "C" int dxo_icnn_field(dxo_ctx* ctx, const dxo_icnn* model, int precision, dxo_mesh* mesh, int mem, const double* u,
                               double* dP, double* P) {
-    if (!ctx) return DXO_E_NULL;
-    DXO_LOCK(ctx);
-    if (!model) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn_field: model is NULL");
-    if (const char* why = check_mesh_2d(mesh)) return dxo_fail(ctx, mesh ? DXO_E_DIM : DXO_E_NULL, why);
-    if (precision != 0 && precision != 1) return dxo_fail(ctx, DXO_E_OPTION, "dxo_icnn_field: precision must be 0 (fp32 network) or 1 (fp64)");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_icnn_field: bad mem");
-    if (mesh->num_cells == 0) return DXO_OK;
-    if (!u || !dP || !P) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn_field: NULL array");
-    const uintptr_t all = (uintptr_t)u | (uintptr_t)dP | (uintptr_t)P;
-    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn_field: arrays must be 8-byte aligned");
-    if (mem == DXO_MEM_DEVICE && (((uintptr_t)dP | (uintptr_t)P) & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn_field: device dP, P must be 16-byte aligned");
-    FieldOp L{mesh, nullptr, DXO_OPERAND_DEFGRAD};
-    L.consume = [model, precision](dxo_ctx* c, const double* F, int64_t n, void* const*, void* const* d_out, hipStream_t s) {
-        return dxo_icnn_launch_device(c, model, precision, n, F, (double*)d_out[0], (double*)d_out[1], s);
-    };
-    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
-    std::vector<dxo_span> in;
-    std::vector<dxo_span> out = {{nullptr, dP, 16 * sd}, {nullptr, P, 4 * sd}};
-    void* dout[2] = {dP, P};
-    return run_field_op(ctx, L, mem, u, in, out, nullptr, dout);
+    return icnn_field(ctx, "dxo_icnn_field", 2, model, precision, mesh, mem, u, dP, P);
 }
 
-// the 3-D network operator: F = I + grad u (3x3) of a gdim = 3 mesh into the staging buffer, then dxo_icnn3_eval's kernel
+// the 3-D network operator: F = I + grad u (3x3) of a gdim = 3 mesh
 extern "C" int dxo_icnn3_field(dxo_ctx* ctx, const dxo_icnn* model, int precision, dxo_mesh* mesh, int mem, const double* u,
                                double* dP, double* P) {
-    if (!ctx) return DXO_E_NULL;
-    DXO_LOCK(ctx);
-    if (!model) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_field: model is NULL");
-    if (!mesh) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_field: mesh is NULL");
-    if (mesh->gdim != 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_icnn3_field: F is 3x3, the mesh must have gdim = 3");
-    if (precision != 0 && precision != 1) return dxo_fail(ctx, DXO_E_OPTION, "dxo_icnn3_field: precision must be 0 (fp32 network) or 1 (fp64)");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_icnn3_field: bad mem");
-    if (mesh->num_cells == 0) return DXO_OK;
-    if (!u || !dP || !P) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_field: NULL array");
-    const uintptr_t all = (uintptr_t)u | (uintptr_t)dP | (uintptr_t)P;
-    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn3_field: arrays must be 8-byte aligned");
-    if (mem == DXO_MEM_DEVICE && (((uintptr_t)dP | (uintptr_t)P) & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn3_field: device dP, P must be 16-byte aligned");
-    FieldOp L{mesh, nullptr, DXO_OPERAND_DEFGRAD};
-    L.width = 9;
-    L.consume = [model, precision](dxo_ctx* c, const double* F, int64_t n, void* const*, void* const* d_out, hipStream_t s) {
-        return dxo_icnn3_launch_device(c, model, precision, n, F, (double*)d_out[0], (double*)d_out[1], s);
-    };
-    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
-    std::vector<dxo_span> in;
-    std::vector<dxo_span> out = {{nullptr, dP, 81 * sd}, {nullptr, P, 9 * sd}};
-    void* dout[2] = {dP, P};
-    return run_field_op(ctx, L, mem, u, in, out, nullptr, dout);
+    return icnn_field(ctx, "dxo_icnn3_field", 3, model, precision, mesh, mem, u, dP, P);
 }
 
 extern "C" int dxo_isihara_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, int mem, const double* u,
@@ -288,28 +226,7 @@ extern "C" int dxo_isihara_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dx
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
     if (!prm) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara_field: params is NULL");
-    if (const char* why = check_mesh_2d(mesh)) return dxo_fail(ctx, mesh ? DXO_E_DIM : DXO_E_NULL, why);
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_isihara_field: bad mem");
-    if (mesh->num_cells == 0) return DXO_OK;
-    if (!u || !dP || !P) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara_field: NULL array");
-    const uintptr_t all = (uintptr_t)u | (uintptr_t)dP | (uintptr_t)P;
-    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_isihara_field: arrays must be 8-byte aligned");
-    if (mem == DXO_MEM_DEVICE && (((uintptr_t)dP | (uintptr_t)P) & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_isihara_field: device dP, P must be 16-byte aligned");
-    IsiFieldLaunch L{IsiPrm{prm->c1, prm->c2, prm->c3, prm->c4}, mesh, u, 0};
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = isi_field_launch(ctx, L, 0, mesh->num_cells, dP, P, s);
-        if (rc != DXO_OK) return rc;
-        return dxo_device_end(ctx, s);
-    }
-    int rc = upload_u(ctx, mesh, u, mesh->gdim);
-    if (rc != DXO_OK) return rc;
-    L.d_u = mesh->d_u;
-    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
-    std::vector<dxo_span> in;
-    std::vector<dxo_span> out = {{nullptr, dP, 16 * sd}, {nullptr, P, 4 * sd}};
-    return dxo_run_host_pipeline(ctx, mesh->num_cells, in, out, isi_field_chunk, &L, mesh->dev.nq, nullptr, true);
+    const int rc = hyper_field_check(ctx, "dxo_isihara_field", 2, mesh, mem, u, dP, P);
+    if (rc != DXO_OK || mesh->num_cells == 0) return rc;
+    return isi_field_run(ctx, IsiFieldLaunch{IsiPrm{prm->c1, prm->c2, prm->c3, prm->c4}, mesh, u, isi_field_launch}, 2, mem, dP, P);
 }

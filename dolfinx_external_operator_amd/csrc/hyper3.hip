@@ -11,7 +11,7 @@
 // dxo_mesh_create accepts leaves room for pp >= 9.
 #include "dxo_common.h"
 #include "hyper3_core.h"
-#include "form_host.h"
+#include "hyper_host.h"
 
 namespace {
 
@@ -100,14 +100,7 @@ __global__ __launch_bounds__(DXO_BLOCK, H3_WAVES) void isihara3_field(IsiPrm prm
     }
 }
 
-struct Isi3FieldLaunch {
-    IsiPrm prm;
-    dxo_mesh* mesh;
-    const double* d_u;
-    int64_t next_cell = 0;
-};
-
-int isi3_field_launch(dxo_ctx* ctx, const Isi3FieldLaunch& L, int64_t cell0, int64_t n_cells, double* dP, double* P, hipStream_t s) {
+int isi3_field_launch(dxo_ctx* ctx, const IsiFieldLaunch& L, int64_t cell0, int64_t n_cells, double* dP, double* P, hipStream_t s) {
     if (n_cells == 0) return DXO_OK;
     const OperandDev& m = L.mesh->dev;
     // the largest pass that fits beside the tables; dxo_mesh_create keeps 64 * 12 doubles per wave free, more than h3_buf(9)
@@ -123,13 +116,6 @@ int isi3_field_launch(dxo_ctx* ctx, const Isi3FieldLaunch& L, int64_t cell0, int
     return DXO_OK;
 }
 
-int isi3_field_chunk(dxo_ctx* ctx, void* user, int64_t n_chunk, void* const*, void* const* d_out, hipStream_t s) {
-    Isi3FieldLaunch& L = *static_cast<Isi3FieldLaunch*>(user);
-    const int64_t cell0 = L.next_cell;
-    L.next_cell += n_chunk;
-    return isi3_field_launch(ctx, L, cell0, n_chunk, (double*)d_out[0], (double*)d_out[1], s);
-}
-
 }  // namespace
 
 extern "C" int dxo_isihara3(dxo_ctx* ctx, const dxo_isihara_params* prm, int64_t n, int mem, const double* F, double* dP,
@@ -137,25 +123,8 @@ extern "C" int dxo_isihara3(dxo_ctx* ctx, const dxo_isihara_params* prm, int64_t
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
     if (!prm) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara3: params is NULL");
-    if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_isihara3: n < 0");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_isihara3: bad mem");
-    if (n > 0 && (!F || !dP || !P)) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara3: NULL array");
-    const uintptr_t all = (uintptr_t)F | (uintptr_t)dP | (uintptr_t)P;
-    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_isihara3: arrays must be 8-byte aligned");
-    if (mem == DXO_MEM_DEVICE && (all & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_isihara3: device arrays must be 16-byte aligned");
     IsiPrm k{prm->c1, prm->c2, prm->c3, prm->c4};
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = isihara3_launch(ctx, k, n, F, dP, P, s);
-        if (rc != DXO_OK) return rc;
-        return dxo_device_end(ctx, s);
-    }
-    const size_t sd = sizeof(double);
-    std::vector<dxo_span> in = {{F, nullptr, 9 * sd}};
-    std::vector<dxo_span> out = {{nullptr, dP, 81 * sd}, {nullptr, P, 9 * sd}};
-    return dxo_run_host_pipeline(ctx, n, in, out, isihara3_chunk, &k, 1, nullptr, true);
+    return hyper_array_entry(ctx, "dxo_isihara3", n, mem, F, dP, P, 3, isihara3_chunk, &k, true);
 }
 
 extern "C" int dxo_isihara3_field(dxo_ctx* ctx, const dxo_isihara_params* prm, dxo_mesh* mesh, int mem, const double* u,
@@ -163,29 +132,7 @@ extern "C" int dxo_isihara3_field(dxo_ctx* ctx, const dxo_isihara_params* prm, d
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
     if (!prm) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara3_field: params is NULL");
-    if (!mesh) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara3_field: mesh is NULL");
-    if (mesh->gdim != 3) return dxo_fail(ctx, DXO_E_DIM, "dxo_isihara3_field: F is 3x3, the mesh must have gdim = 3");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_isihara3_field: bad mem");
-    if (mesh->num_cells == 0) return DXO_OK;
-    if (!u || !dP || !P) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara3_field: NULL array");
-    const uintptr_t all = (uintptr_t)u | (uintptr_t)dP | (uintptr_t)P;
-    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_isihara3_field: arrays must be 8-byte aligned");
-    if (mem == DXO_MEM_DEVICE && (((uintptr_t)dP | (uintptr_t)P) & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_isihara3_field: device dP, P must be 16-byte aligned");
-    Isi3FieldLaunch L{IsiPrm{prm->c1, prm->c2, prm->c3, prm->c4}, mesh, u, 0};
-    DXO_HIP(ctx, hipSetDevice(ctx->device));
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = isi3_field_launch(ctx, L, 0, mesh->num_cells, dP, P, s);
-        if (rc != DXO_OK) return rc;
-        return dxo_device_end(ctx, s);
-    }
-    int rc = upload_u(ctx, mesh, u, mesh->gdim);
-    if (rc != DXO_OK) return rc;
-    L.d_u = mesh->d_u;
-    const size_t sd = sizeof(double) * (size_t)mesh->dev.nq;
-    std::vector<dxo_span> in;
-    std::vector<dxo_span> out = {{nullptr, dP, 81 * sd}, {nullptr, P, 9 * sd}};
-    return dxo_run_host_pipeline(ctx, mesh->num_cells, in, out, isi3_field_chunk, &L, mesh->dev.nq, nullptr, true);
+    const int rc = hyper_field_check(ctx, "dxo_isihara3_field", 3, mesh, mem, u, dP, P);
+    if (rc != DXO_OK || mesh->num_cells == 0) return rc;
+    return isi_field_run(ctx, IsiFieldLaunch{IsiPrm{prm->c1, prm->c2, prm->c3, prm->c4}, mesh, u, isi3_field_launch}, 3, mem, dP, P);
 }

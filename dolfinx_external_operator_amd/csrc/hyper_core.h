@@ -72,23 +72,45 @@ __device__ __forceinline__ void icnn_chain(const double (&Fv)[4], const double (
     }
 }
 
+// ---- the plane-strain features x = (K1, K2, K3) (:263-283) in the generators t = |F|^2 and D = det F, and their partials. The power
+// m = |D|^(-2/3) and nn = m^2 are passed in: icnn_point and icnn_mfma_f32 form m with the library pow, the default kernel and the analytic
+// model with hyper_pow_m23, and every result is pinned bit for bit to its own.
+__device__ __forceinline__ double hyper2_t(const double (&Fv)[4]) { return Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3]; }
+__device__ __forceinline__ double hyper2_det(const double (&Fv)[4]) { return Fv[0] * Fv[3] - Fv[1] * Fv[2]; }
+
+//   K1 = (t + 1) m - 3,  K2 = (t + D^2) m^2 - 3,  K3 = (|D| - 1)^2, each rounded to T where it is formed (the `.float()` of :286)
+template <typename T>
+__device__ __forceinline__ void hyper2_features(double t, double D, double m, double nn, T (&x)[3]) {
+    const double aD = fabs(D);
+    x[0] = (T)((t + 1.0) * m - 3.0); x[1] = (T)((t + D * D) * nn - 3.0); x[2] = (T)((aD - 1.0) * (aD - 1.0));
+}
+
+// K_,t  K_,D  K_,tD  K_,DD with iD = 1 / D. K3 = (J - 1)^2 with J = sJ D: the network's J is |det F| (J = |D|, sJ = sign D), the
+// analytic model's is det F (J = D, sJ = 1).
+__device__ __forceinline__ void hyper2_partials(double t, double D, double m, double nn, double iD, double J, double sJ, double (&kt)[3],
+                                                double (&kD)[3], double (&ktD)[3], double (&kDD)[3]) {
+    kt[0] = m; kt[1] = nn; kt[2] = 0.0;
+    kD[0] = (t + 1.0) * (-2.0 / 3.0) * m * iD; kD[1] = 2.0 * D * nn + (t + D * D) * (-4.0 / 3.0) * nn * iD;
+    kD[2] = 2.0 * (J - 1.0) * sJ;
+    ktD[0] = (-2.0 / 3.0) * m * iD; ktD[1] = (-4.0 / 3.0) * nn * iD; ktD[2] = 0.0;
+    kDD[0] = (t + 1.0) * (10.0 / 9.0) * m * iD * iD;
+    kDD[1] = -(10.0 / 3.0) * nn + (28.0 / 9.0) * (t + D * D) * nn * iD * iD; kDD[2] = 2.0;
+}
+
 // ---- analytic Isihara energy (demo_hyperelasticity.py:686-703): W = c1 (I1bar - 3) + c2 (I2bar - 3) + c3 (I1bar - 3)^2 + c4 (J - 1)^2,
 // a quadratic in the SAME features the network sees, so P and dP/dF come out of the chain rule above with
 // grad_x W = (c1 + 2 c3 K1, c2, c4), hess_x W = diag(2 c3, 0, 0). UFL's J = det F: for det F <= 0 the real power is NaN.
 struct IsiPrm { double c1, c2, c3, c4; };
 
 __device__ __forceinline__ void isihara_point(const IsiPrm& prm, const double (&Fv)[4], double* __restrict__ dPp, double* __restrict__ Pp) {
+    // t and D written out: through hyper2_t / hyper2_det the compiler orders isihara_tile's and isihara_field's instructions differently
     const double t = Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3];
     const double D = Fv[0] * Fv[3] - Fv[1] * Fv[2];
     const double iD = 1.0 / D;
     const double m = D > 0.0 ? hyper_pow_m23(D) : __builtin_nan(""), nn = m * m;
     const double K1 = (t + 1.0) * m - 3.0;
-    const double kt[3] = {m, nn, 0.0};
-    const double kD[3] = {(t + 1.0) * (-2.0 / 3.0) * m * iD, 2.0 * D * nn + (t + D * D) * (-4.0 / 3.0) * nn * iD,
-                          2.0 * (D - 1.0)};
-    const double ktD[3] = {(-2.0 / 3.0) * m * iD, (-4.0 / 3.0) * nn * iD, 0.0};
-    const double kDD[3] = {(t + 1.0) * (10.0 / 9.0) * m * iD * iD,
-                           -(10.0 / 3.0) * nn + (28.0 / 9.0) * (t + D * D) * nn * iD * iD, 2.0};
+    double kt[3], kD[3], ktD[3], kDD[3];
+    hyper2_partials(t, D, m, nn, iD, D, 1.0, kt, kD, ktD, kDD);
     const double y1[3] = {prm.c1 + 2.0 * prm.c3 * K1, prm.c2, prm.c4};
     const double hx[6] = {2.0 * prm.c3, 0.0, 0.0, 0.0, 0.0, 0.0};
     const double Hzero[4] = {0.0, 0.0, 0.0, 0.0};

@@ -34,6 +34,7 @@
 #include "dxo_common.h"
 #include "hyper_core.h"
 #include "hyper3_core.h"
+#include "hyper_host.h"
 
 namespace {
 
@@ -191,17 +192,11 @@ __global__ __launch_bounds__(DXO_BLOCK) void icnn_point(const T* __restrict__ wA
             const dxo_f64x2 f23 = reinterpret_cast<const dxo_f64x2*>(F + p * 4)[1];
             Fv[0] = f01.x; Fv[1] = f01.y; Fv[2] = f23.x; Fv[3] = f23.y;
             // ---- features and their (t, D) partials, fp64 (:263-283)
-            const double t = Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3];
-            const double D = Fv[0] * Fv[3] - Fv[1] * Fv[2];
+            const double t = hyper2_t(Fv), D = hyper2_det(Fv);
             const double aD = fabs(D), sg = D < 0.0 ? -1.0 : 1.0, iD = 1.0 / D;
             const double m = pow(aD, -2.0 / 3.0), nn = m * m;
-            K[0] = (t + 1.0) * m - 3.0; K[1] = (t + D * D) * nn - 3.0; K[2] = (aD - 1.0) * (aD - 1.0);
-            kt[0] = m; kt[1] = nn; kt[2] = 0.0;
-            kD[0] = (t + 1.0) * (-2.0 / 3.0) * m * iD; kD[1] = 2.0 * D * nn + (t + D * D) * (-4.0 / 3.0) * nn * iD;
-            kD[2] = 2.0 * (aD - 1.0) * sg;
-            ktD[0] = (-2.0 / 3.0) * m * iD; ktD[1] = (-4.0 / 3.0) * nn * iD; ktD[2] = 0.0;
-            kDD[0] = (t + 1.0) * (10.0 / 9.0) * m * iD * iD;
-            kDD[1] = -(10.0 / 3.0) * nn + (28.0 / 9.0) * (t + D * D) * nn * iD * iD; kDD[2] = 2.0;
+            hyper2_features(t, D, m, nn, K);
+            hyper2_partials(t, D, m, nn, iD, aD, sg, kt, kD, ktD, kDD);
         } else {   // the invariants of the full 3x3 F; its partials are formed after the network (icnn3_point_out)
             double F3[9];
 #pragma unroll
@@ -290,8 +285,8 @@ __device__ __forceinline__ void icnn_lds_fence() {   // wave-private LDS: only t
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ------------------------------------------------------------------ fp32 MFMA kernel, round 3 (variant 1, default)
-// Same five GEMMs per 64-point wave tile as icnn_mfma above, restructured so that NOTHING is parked in LDS and no
+// ------------------------------------------------------------------ fp32 MFMA kernel, round 3 (icnn_variant = 1; the default is variant 2 below)
+// Same five GEMMs per 64-point wave tile as round 2's kernel, restructured so that NOTHING is parked in LDS and no
 // softplus is evaluated twice. Per half-tile of 32 points (lane l = (h = l >> 5, p = l & 31), both halves work on
 // the same 32 points, each on half of the neurons):
 //   phase 1  K-step s = (it, q) of the four forward GEMMs covers the layer-1 neurons i_h(s) = 32 it + (q & 3) + 8 (q >> 2)
@@ -422,11 +417,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_f32(const flo
             icnn3_load_features(F, icnn3_tile(tile, icnn_lane_here(), n), x0, x1, x2);
         } else {
             const double Fv[4] = {f01n.x, f01n.y, f23n.x, f23n.y};   // tail lanes recompute the last point, never store
-            const double t = Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3];
-            const double D = Fv[0] * Fv[3] - Fv[1] * Fv[2];
+            const double t = hyper2_t(Fv), D = hyper2_det(Fv);
+            float x[3];
             const double aD = fabs(D), iD = 1.0 / D;
             const double m = pow(aD, -2.0 / 3.0), nn = m * m;
-            x0 = (float)((t + 1.0) * m - 3.0); x1 = (float)((t + D * D) * nn - 3.0); x2 = (float)((aD - 1.0) * (aD - 1.0));
+            hyper2_features(t, D, m, nn, x);
+            x0 = x[0]; x1 = x[1]; x2 = x[2];
             keep[0 * 64] = Fv[0]; keep[1 * 64] = Fv[1]; keep[2 * 64] = Fv[2]; keep[3 * 64] = Fv[3];
             keep[4 * 64] = t; keep[5 * 64] = D; keep[6 * 64] = m; keep[7 * 64] = nn; keep[8 * 64] = iD;
             asm volatile("" ::: "memory");   // the values are re-read from LDS below, not carried in registers
@@ -550,12 +546,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_f32(const flo
             float mine[9];
 #pragma unroll
             for (int q = 0; q < 9; ++q) mine[q] = minep[q * 64];
-            const double kt[3] = {m, nn, 0.0};
-            const double kD[3] = {(t + 1.0) * (-2.0 / 3.0) * m * iD, 2.0 * D * nn + (t + D * D) * (-4.0 / 3.0) * nn * iD,
-                                  2.0 * (aD - 1.0) * sg};
-            const double ktD[3] = {(-2.0 / 3.0) * m * iD, (-4.0 / 3.0) * nn * iD, 0.0};
-            const double kDD[3] = {(t + 1.0) * (10.0 / 9.0) * m * iD * iD,
-                                   -(10.0 / 3.0) * nn + (28.0 / 9.0) * (t + D * D) * nn * iD * iD, 2.0};
+            double kt[3], kD[3], ktD[3], kDD[3];
+            hyper2_partials(t, D, m, nn, iD, aD, sg, kt, kD, ktD, kDD);
             const float y1f[3] = {mine[0] + small.s3[0], mine[1] + small.s3[1], mine[2] + small.s3[2]};
             icnn_chain(Fk, kt, kD, ktD, kDD, y1f, mine + 3, small.H, dP + pidx * 16, P + pidx * 4);
         }
@@ -588,21 +580,6 @@ __device__ __forceinline__ f32x16 icnn_mfma_bf16(icnn_u32x4 a, icnn_u32x4 b, f32
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(icnn_bf16x8, a), __builtin_bit_cast(icnn_bf16x8, b), c, 0, 0, 0);
 }
 
-// A neuron PAIR's two fp32 values. A plain struct with scalar operators, NOT an ext_vector_type: <2 x float> arithmetic becomes
-// v_pk_{fma,mul,add}_f32, and a packed fp32 instruction issued beside a running MFMA stalls ~20 cycles
-// (profiles/r05_mfma_gap_probe.txt: one v_pk_fma_f32 per 32-cycle MFMA gap: 52 cycles per MFMA; six v_fma_f32: 37;
-// MI355X_MICROARCH.md: "packed f32 VALU ... an anti-lever beside MFMAs"). The arithmetic is identical (IEEE fp32 either way);
-// this translation unit is built with -fno-slp-vectorize so that the compiler does not re-pack adjacent scalar operations
-// (_build.py, Makefile).
-struct icnn_f2 {
-    float x, y;
-};
-__device__ __forceinline__ icnn_f2 operator+(icnn_f2 a, icnn_f2 b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ icnn_f2 operator-(icnn_f2 a, icnn_f2 b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ icnn_f2 operator*(icnn_f2 a, icnn_f2 b) { return {a.x * b.x, a.y * b.y}; }
-__device__ __forceinline__ icnn_f2 operator+(icnn_f2 a, float b) { return {a.x + b, a.y + b}; }
-__device__ __forceinline__ icnn_f2 operator*(icnn_f2 a, float b) { return {a.x * b, a.y * b}; }
-
 __device__ __forceinline__ IcnnSplit icnn_pack(const IcnnSplitW& w) {
     IcnnSplit o;
     o.h = icnn_u32x4{w.h[0], w.h[1], w.h[2], w.h[3]};
@@ -610,34 +587,6 @@ __device__ __forceinline__ IcnnSplit icnn_pack(const IcnnSplitW& w) {
     o.l = icnn_u32x4{w.l[0], w.l[1], w.l[2], w.l[3]};
     return o;
 }
-
-// one B-fragment dword (two consecutive k: the neuron pair) of each part from a pair of fp32 values
-__device__ __forceinline__ void icnn_split_pair(icnn_f2 v, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned vx = __float_as_uint(v.x), vy = __float_as_uint(v.y);
-    h = __builtin_amdgcn_perm(vy, vx, 0x07060302u);
-    const icnn_f2 vh = {__uint_as_float(vx & 0xffff0000u), __uint_as_float(vy & 0xffff0000u)};
-    const icnn_f2 r = v - vh;
-    const unsigned rx = __float_as_uint(r.x), ry = __float_as_uint(r.y);
-    m = __builtin_amdgcn_perm(ry, rx, 0x07060302u);
-    const icnn_f2 rh = {__uint_as_float(rx & 0xffff0000u), __uint_as_float(ry & 0xffff0000u)};
-    const icnn_f2 q = r - rh;
-    l = __builtin_amdgcn_perm(__float_as_uint(q.y), __float_as_uint(q.x), 0x07060302u);
-}
-
-// softplus, softplus', softplus'' of two pre-activations: softplus3_mfma's operations, the multiplies and adds as packed fp32
-__device__ __forceinline__ void softplus3_pk(icnn_f2 a, icnn_f2& sp, icnn_f2& s1, icnn_f2& s2) {
-    const icnn_f2 am = {fminf(a.x, 80.0f), fminf(a.y, 80.0f)};
-    const icnn_f2 t = am * 1.4426950408889634f;
-    const icnn_f2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-    const icnn_f2 ope = e + 1.0f;
-    const icnn_f2 r = {__builtin_amdgcn_rcpf(ope.x), __builtin_amdgcn_rcpf(ope.y)};
-    const icnn_f2 l = icnn_f2{__builtin_amdgcn_logf(ope.x), __builtin_amdgcn_logf(ope.y)} * 0.6931471805599453f;
-    sp = icnn_f2{fmaxf(l.x, a.x), fmaxf(l.y, a.y)};
-    s1 = e * r;
-    s2 = s1 * r;
-}
-
-__device__ __forceinline__ icnn_f2 icnn_fma2(icnn_f2 a, icnn_f2 b, icnn_f2 c) { return {__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)}; }
 
 // c0, c1 += A[jt] (split) x B (split): the six products with a weight above 2^-24, smallest first, accumulators alternating
 __device__ __forceinline__ void icnn_mma6(const IcnnSplit (&A)[2], const IcnnSplit& B, f32x16& c0, f32x16& c1) {
@@ -648,12 +597,6 @@ __device__ __forceinline__ void icnn_mma6(const IcnnSplit (&A)[2], const IcnnSpl
     c0 = icnn_mfma_bf16(A[0].h, B.m, c0); c1 = icnn_mfma_bf16(A[1].h, B.m, c1);
     c0 = icnn_mfma_bf16(A[0].h, B.h, c0); c1 = icnn_mfma_bf16(A[1].h, B.h, c1);
 }
-
-// not `volatile`: a volatile asm orders every LDS read around it and would pin the table reads between the pins
-#define DXO_ICNN_PIN2(PAIR_) asm("" : "+v"((PAIR_).x), "+v"((PAIR_).y));
-#ifndef DXO_ICNN_PIPE_AGPR
-#define DXO_ICNN_PIPE_AGPR false
-#endif
 
 // ------------------------------------------------------------------ split-bf16 kernel, phases in sequence, PACKED fp32 vector arithmetic (icnn_variant = 2, the default)
 // Rounds 3-4's kernel, unchanged: two waves per SIMD, every neuron pair's arithmetic as v_pk_{fma,mul,add}_f32. A packed fp32
@@ -774,11 +717,11 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_bf16x3_packed
             icnn3_load_features(F, icnn3_tile(tile, icnn_lane_here(), n), x0, x1, x2);
         } else {
             const double Fv[4] = {f01.x, f01.y, f23.x, f23.y};   // tail lanes recompute the last point, never store
-            const double t = Fv[0] * Fv[0] + Fv[1] * Fv[1] + Fv[2] * Fv[2] + Fv[3] * Fv[3];
-            const double D = Fv[0] * Fv[3] - Fv[1] * Fv[2];
-            const double aD = fabs(D);
-            const double m = hyper_pow_m23(aD), nn = m * m;
-            x0 = (float)((t + 1.0) * m - 3.0); x1 = (float)((t + D * D) * nn - 3.0); x2 = (float)((aD - 1.0) * (aD - 1.0));
+            const double t = hyper2_t(Fv), D = hyper2_det(Fv);
+            float x[3];
+            const double m = hyper_pow_m23(fabs(D));
+            hyper2_features(t, D, m, m * m, x);
+            x0 = x[0]; x1 = x[1]; x2 = x[2];
         }
         if (tile + tile_step < n_tiles) icnn_fetch_F<DIM>(F, tile + tile_step, lane, n, f01n, f23n);
         const float xp0 = xor32(x0), xp1 = xor32(x1), xp2 = xor32(x2);
@@ -921,19 +864,14 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_bf16x3_packed
         } else if (pidx < n) {
             // the fp64 feature derivatives are formed here, after the GEMM phases (they would occupy 18 registers through them)
             const double Fk[4] = {f01.x, f01.y, f23.x, f23.y};
-            const double t = Fk[0] * Fk[0] + Fk[1] * Fk[1] + Fk[2] * Fk[2] + Fk[3] * Fk[3];
-            const double D = Fk[0] * Fk[3] - Fk[1] * Fk[2];
+            const double t = hyper2_t(Fk), D = hyper2_det(Fk);
             const double aD = fabs(D), sg = D < 0.0 ? -1.0 : 1.0, iD = 1.0 / D;
             const double m = hyper_pow_m23(aD), nn = m * m;
             float mine[9];
 #pragma unroll
             for (int q = 0; q < 9; ++q) mine[q] = minep[q * 64];
-            const double kt[3] = {m, nn, 0.0};
-            const double kD[3] = {(t + 1.0) * (-2.0 / 3.0) * m * iD, 2.0 * D * nn + (t + D * D) * (-4.0 / 3.0) * nn * iD,
-                                  2.0 * (aD - 1.0) * sg};
-            const double ktD[3] = {(-2.0 / 3.0) * m * iD, (-4.0 / 3.0) * nn * iD, 0.0};
-            const double kDD[3] = {(t + 1.0) * (10.0 / 9.0) * m * iD * iD,
-                                   -(10.0 / 3.0) * nn + (28.0 / 9.0) * (t + D * D) * nn * iD * iD, 2.0};
+            double kt[3], kD[3], ktD[3], kDD[3];
+            hyper2_partials(t, D, m, nn, iD, aD, sg, kt, kD, ktD, kDD);
             const float y1f[3] = {mine[0] + small.s3[0], mine[1] + small.s3[1], mine[2] + small.s3[2]};
             icnn_chain(Fk, kt, kD, ktD, kDD, y1f, mine + 3, small.H, dP + pidx * 16, P + pidx * 4);
         }
@@ -945,102 +883,83 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void icnn_mfma_bf16x3_packed
 #include "../../scripts/exp/icnn_variants.h"
 #endif
 
-template <typename T>
-void launch_icnn(const IcnnDev<T>& m, int blocks, hipStream_t s, int64_t n, const double* F, double* dP, double* P) {
-    IcnnSmall<T> small;
-    for (int k = 0; k < 3; ++k) small.s3[k] = m.s3[k];
-    for (int k = 0; k < 4; ++k) small.H[k] = m.H[k];
-    hipLaunchKernelGGL((icnn_point<T, 2>), dim3(blocks), dim3(DXO_BLOCK), 0, s, m.A1, m.W2B, m.S2, m.w3, small, n, F, dP, P);
-}
+// The kernels stand in the code object in the order in which this unit first names them. They are named here once, in the order they had
+// when every launch was a function of its own, so that the object does not move with the host code below (a change that leaves the kernels
+// alone is checked by comparing the units' assembly).
+[[maybe_unused]] const void* const icnn_kernel_order[] = {
+#ifdef DXO_EXPERIMENTS
+    (const void*)icnn_mfma_bf16x3_hybrid<4>, (const void*)icnn_mfma_bf16x3_pipe<4>,
+#endif
+    (const void*)icnn_mfma_bf16x3_packed<8, 2, false>, (const void*)icnn_mfma_f32<8, 2>, (const void*)icnn_point<float, 2>,
+    (const void*)icnn_point<double, 2>, (const void*)icnn_point<double, 3>, (const void*)icnn_point<float, 3>,
+    (const void*)icnn_mfma_f32<8, 3>, (const void*)icnn_mfma_bf16x3_packed<8, 3, true>, (const void*)icnn_mfma_bf16x3_packed<8, 3, false>};
 
 double softplus_host(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
+
+// the by-value kernel argument. 2-D: the four entries of H_flat; 3-D: the scalar h3 of the correction H = h3 I in H[0]
+template <typename T>
+IcnnSmall<T> icnn_small(const IcnnDev<T>& w, int dim, double h3) {
+    IcnnSmall<T> small;
+    for (int k = 0; k < 3; ++k) small.s3[k] = w.s3[k];
+    for (int k = 0; k < 4; ++k) small.H[k] = dim == 2 ? w.H[k] : (k == 0 ? h3 : 0.0);
+    return small;
+}
+
+template <typename T, int DIM>
+void icnn_point_launch(const IcnnDev<T>& w, double h3, int blocks, hipStream_t s, int64_t n, const double* F, double* dP, double* P) {
+    hipLaunchKernelGGL((icnn_point<T, DIM>), dim3(blocks), dim3(DXO_BLOCK), 0, s, w.A1, w.W2B, w.S2, w.w3, icnn_small(w, DIM, h3), n, F, dP, P);
+}
 
 struct IcnnLaunch {
     const dxo_icnn_impl* m;
     int precision;
+    int dim;    // 2: F[n][4] -> dP[n][16], P[n][4];  3: F[n][9] -> dP[n][81], P[n][9]
 };
 
+template <int DIM>
 int icnn_launch(dxo_ctx* ctx, const IcnnLaunch& L, int64_t n, const double* F, double* dP, double* P, hipStream_t s) {
     if (n == 0) return DXO_OK;
     int64_t blocks = (n + DXO_BLOCK - 1) / DXO_BLOCK;
     const int64_t cap = (int64_t)ctx->compute_units * 8;
     if (blocks > cap) blocks = cap;
-    if (L.precision == 0 && ctx->icnn_variant != 0) {
-        // MFMA kernel: one wave = 64 points, persistent grid of one 8-wave workgroup per CU (two waves per SIMD: the register
-        // budget of 256 per lane is what the 128 + 32 accumulator registers need)
-        IcnnSmall<float> small;
-        for (int k = 0; k < 3; ++k) small.s3[k] = L.m->f32.s3[k];
-        for (int k = 0; k < 4; ++k) small.H[k] = L.m->f32.H[k];
-        int64_t mb = (n + 8 * 64 - 1) / (8 * 64);
-        if (mb > ctx->compute_units) mb = ctx->compute_units;
-#ifdef DXO_EXPERIMENTS
-        if (ctx->icnn_variant == 4 || ctx->icnn_variant == 3) {   // scripts/exp/icnn_variants.h: one 4-wave workgroup per CU (one wave per SIMD)
-            int64_t mp = (n + 4 * 64 - 1) / (4 * 64);
-            if (mp > ctx->compute_units) mp = ctx->compute_units;
-            if (ctx->icnn_variant == 4)
-                hipLaunchKernelGGL((icnn_mfma_bf16x3_hybrid<4>), dim3((int)mp), dim3(256), 0, s, L.m->f32.T1, L.m->f32.W2, L.m->f32.T2, small, n, F, dP, P);
-            else
-                hipLaunchKernelGGL((icnn_mfma_bf16x3_pipe<4>), dim3((int)mp), dim3(256), 0, s, L.m->f32.T1, L.m->f32.W2, L.m->f32.T2, small, n, F, dP, P);
-        } else
-#endif
-        if (ctx->icnn_variant != 1)   // 2: split-bf16 products phase after phase, two waves per SIMD; 1: fp32-input MFMA
-            hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8, 2>), dim3((int)mb), dim3(512), 0, s, L.m->f32.T1, L.m->f32.W2, L.m->f32.T2, small, n, F, dP, P);
-        else
-            hipLaunchKernelGGL((icnn_mfma_f32<8, 2>), dim3((int)mb), dim3(512), 0, s, L.m->f32.T1, L.m->f32.W2, L.m->f32.T2, small, n, F, dP, P);
+    if (L.precision != 0) {
+        icnn_point_launch<double, DIM>(L.m->f64, L.m->H3, (int)blocks, s, n, F, dP, P);
         return DXO_OK;
     }
-    if (L.precision == 0) launch_icnn<float>(L.m->f32, (int)blocks, s, n, F, dP, P);
-    else launch_icnn<double>(L.m->f64, (int)blocks, s, n, F, dP, P);
+    const IcnnDev<float>& w = L.m->f32;
+    if (ctx->icnn_variant == 0) {
+        icnn_point_launch<float, DIM>(w, L.m->H3, (int)blocks, s, n, F, dP, P);
+        return DXO_OK;
+    }
+    // MFMA kernel: one wave = 64 points, persistent grid of one 8-wave workgroup per CU (two waves per SIMD: the register
+    // budget of 256 per lane is what the 128 + 32 accumulator registers need)
+    const IcnnSmall<float> small = icnn_small(w, DIM, L.m->H3);
+    int64_t mb = (n + 8 * 64 - 1) / (8 * 64);
+    if (mb > ctx->compute_units) mb = ctx->compute_units;
+#ifdef DXO_EXPERIMENTS
+    // scripts/exp/icnn_variants.h: one 4-wave workgroup per CU (one wave per SIMD). They have no 3-D form: there the default kernel answers
+    if (DIM == 2 && (ctx->icnn_variant == 4 || ctx->icnn_variant == 3)) {
+        int64_t mp = (n + 4 * 64 - 1) / (4 * 64);
+        if (mp > ctx->compute_units) mp = ctx->compute_units;
+        if (ctx->icnn_variant == 4)
+            hipLaunchKernelGGL((icnn_mfma_bf16x3_hybrid<4>), dim3((int)mp), dim3(256), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
+        else
+            hipLaunchKernelGGL((icnn_mfma_bf16x3_pipe<4>), dim3((int)mp), dim3(256), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
+        return DXO_OK;
+    }
+#endif
+    if (ctx->icnn_variant == 1)   // fp32-input MFMA; otherwise 2: split-bf16 products phase after phase, two waves per SIMD
+        hipLaunchKernelGGL((icnn_mfma_f32<8, DIM>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
+    else if (DIM == 3 && ctx->icnn3_store != 0)
+        hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8, 3, true>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
+    else
+        hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8, DIM, false>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
     return DXO_OK;
 }
 
 int icnn_chunk(dxo_ctx* ctx, void* user, int64_t m, void* const* d_in, void* const* d_out, hipStream_t s) {
     const IcnnLaunch& L = *static_cast<const IcnnLaunch*>(user);
-    return icnn_launch(ctx, L, m, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], s);
-}
-
-// the 3-D forms: F[n][9] -> dP[n][81], P[n][9]; same grids, the scalar of the correction H = h I in IcnnSmall::H[0]
-template <typename T>
-void launch_icnn3(const IcnnDev<T>& m, double h3, int blocks, hipStream_t s, int64_t n, const double* F, double* dP, double* P) {
-    IcnnSmall<T> small;
-    for (int k = 0; k < 3; ++k) small.s3[k] = m.s3[k];
-    small.H[0] = h3;
-    small.H[1] = small.H[2] = small.H[3] = 0.0;
-    hipLaunchKernelGGL((icnn_point<T, 3>), dim3(blocks), dim3(DXO_BLOCK), 0, s, m.A1, m.W2B, m.S2, m.w3, small, n, F, dP, P);
-}
-
-int icnn3_launch(dxo_ctx* ctx, const IcnnLaunch& L, int64_t n, const double* F, double* dP, double* P, hipStream_t s) {
-    if (n == 0) return DXO_OK;
-    int64_t blocks = (n + DXO_BLOCK - 1) / DXO_BLOCK;
-    const int64_t cap = (int64_t)ctx->compute_units * 8;
-    if (blocks > cap) blocks = cap;
-    if (L.precision == 1) {
-        launch_icnn3<double>(L.m->f64, L.m->H3, (int)blocks, s, n, F, dP, P);
-        return DXO_OK;
-    }
-    if (ctx->icnn_variant == 0) {
-        launch_icnn3<float>(L.m->f32, L.m->H3, (int)blocks, s, n, F, dP, P);
-        return DXO_OK;
-    }
-    IcnnSmall<float> small;
-    for (int k = 0; k < 3; ++k) small.s3[k] = L.m->f32.s3[k];
-    small.H[0] = L.m->H3;
-    small.H[1] = small.H[2] = small.H[3] = 0.0;
-    int64_t mb = (n + 8 * 64 - 1) / (8 * 64);
-    if (mb > ctx->compute_units) mb = ctx->compute_units;
-    const IcnnDev<float>& w = L.m->f32;
-    if (ctx->icnn_variant == 1)
-        hipLaunchKernelGGL((icnn_mfma_f32<8, 3>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
-    else if (ctx->icnn3_store != 0)   // variants 3 and 4 of an experiments build have no 3-D form: the default kernel answers
-        hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8, 3, true>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
-    else
-        hipLaunchKernelGGL((icnn_mfma_bf16x3_packed<8, 3, false>), dim3((int)mb), dim3(512), 0, s, w.T1, w.W2, w.T2, small, n, F, dP, P);
-    return DXO_OK;
-}
-
-int icnn3_chunk(dxo_ctx* ctx, void* user, int64_t m, void* const* d_in, void* const* d_out, hipStream_t s) {
-    const IcnnLaunch& L = *static_cast<const IcnnLaunch*>(user);
-    return icnn3_launch(ctx, L, m, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], s);
+    return (L.dim == 2 ? icnn_launch<2> : icnn_launch<3>)(ctx, L, m, (const double*)d_in[0], (double*)d_out[0], (double*)d_out[1], s);
 }
 
 // ------------------------------------------------------------------ analytic Isihara energy (demo_hyperelasticity.py:686-703)
@@ -1128,25 +1047,8 @@ extern "C" int dxo_isihara(dxo_ctx* ctx, const dxo_isihara_params* prm, int64_t 
     if (!ctx) return DXO_E_NULL;
     DXO_LOCK(ctx);
     if (!prm) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara: params is NULL");
-    if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_isihara: n < 0");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_isihara: bad mem");
-    if (n > 0 && (!F || !dP || !P)) return dxo_fail(ctx, DXO_E_NULL, "dxo_isihara: NULL array");
-    const uintptr_t all = (uintptr_t)F | (uintptr_t)dP | (uintptr_t)P;
-    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_isihara: arrays must be 8-byte aligned");
-    if (mem == DXO_MEM_DEVICE && (all & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_isihara: device arrays must be 16-byte aligned");
     IsiPrm k{prm->c1, prm->c2, prm->c3, prm->c4};
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = isihara_launch(ctx, k, n, F, dP, P, s);
-        if (rc != DXO_OK) return rc;
-        return dxo_device_end(ctx, s);
-    }
-    const size_t sd = sizeof(double);
-    std::vector<dxo_span> in = {{F, nullptr, 4 * sd}};
-    std::vector<dxo_span> out = {{nullptr, dP, 16 * sd}, {nullptr, P, 4 * sd}};
-    return dxo_run_host_pipeline(ctx, n, in, out, isihara_chunk, &k, 1, nullptr, true);
+    return hyper_array_entry(ctx, "dxo_isihara", n, mem, F, dP, P, 2, isihara_chunk, &k, true);
 }
 
 struct dxo_icnn : dxo_icnn_impl {};
@@ -1236,8 +1138,8 @@ extern "C" int dxo_icnn_create(dxo_ctx* ctx, const dxo_icnn_weights* w, dxo_icnn
         e = hipMemcpy(dF, FI, sizeof FI, hipMemcpyHostToDevice);
     }
     if (e == hipSuccess) {
-        launch_icnn<float>(m->f32, 1, ctx->stream, (int64_t)1, dF, ddP, dPp);
-        launch_icnn3<float>(m->f32, 0.0, 1, ctx->stream, (int64_t)1, dF + 4, ddP, dPp + 4);
+        icnn_point_launch<float, 2>(m->f32, 0.0, 1, ctx->stream, (int64_t)1, dF, ddP, dPp);
+        icnn_point_launch<float, 3>(m->f32, 0.0, 1, ctx->stream, (int64_t)1, dF + 4, ddP, dPp + 4);
         e = hipStreamSynchronize(ctx->stream);
     }
     if (e == hipSuccess) e = hipMemcpy(P0, dPp, sizeof P0, hipMemcpyDeviceToHost);
@@ -1259,8 +1161,7 @@ extern "C" int dxo_icnn_create(dxo_ctx* ctx, const dxo_icnn_weights* w, dxo_icnn
 // internal: the kernels on device pointers and an explicit stream (field_ops.hip)
 int dxo_icnn_launch_device(dxo_ctx* ctx, const dxo_icnn* m, int precision, int64_t n, const double* F, double* dP, double* P,
                            hipStream_t s) {
-    IcnnLaunch L{m, precision};
-    return icnn_launch(ctx, L, n, F, dP, P, s);
+    return icnn_launch<2>(ctx, IcnnLaunch{m, precision, 2}, n, F, dP, P, s);
 }
 
 int dxo_isihara_launch_device(dxo_ctx* ctx, const dxo_isihara_params* prm, int64_t n, const double* F, double* dP, double* P,
@@ -1293,32 +1194,14 @@ extern "C" int dxo_icnn_eval(dxo_ctx* ctx, const dxo_icnn* m, int precision, int
     DXO_LOCK(ctx);
     if (!m) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn_eval: model is NULL");
     if (precision != 0 && precision != 1) return dxo_fail(ctx, DXO_E_OPTION, "dxo_icnn_eval: precision must be 0 (fp32 network) or 1 (fp64)");
-    if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_icnn_eval: n < 0");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_icnn_eval: bad mem");
-    if (n > 0 && (!F || !dP || !P)) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn_eval: NULL array");
-    const uintptr_t all = (uintptr_t)F | (uintptr_t)dP | (uintptr_t)P;
-    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn_eval: arrays must be 8-byte aligned");
-    if (mem == DXO_MEM_DEVICE && (all & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn_eval: device arrays must be 16-byte aligned");
-    IcnnLaunch L{m, precision};
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = icnn_launch(ctx, L, n, F, dP, P, s);
-        if (rc != DXO_OK) return rc;
-        return dxo_device_end(ctx, s);
-    }
-    const size_t sd = sizeof(double);
-    std::vector<dxo_span> in = {{F, nullptr, 4 * sd}};
-    std::vector<dxo_span> out = {{nullptr, dP, 16 * sd}, {nullptr, P, 4 * sd}};
-    return dxo_run_host_pipeline(ctx, n, in, out, icnn_chunk, &L);
+    IcnnLaunch L{m, precision, 2};
+    return hyper_array_entry(ctx, "dxo_icnn_eval", n, mem, F, dP, P, 2, icnn_chunk, &L, false);
 }
 
 // ---- the 3-D operator: the same model, the invariants of a full 3x3 F
 int dxo_icnn3_launch_device(dxo_ctx* ctx, const dxo_icnn* m, int precision, int64_t n, const double* F, double* dP, double* P,
                             hipStream_t s) {
-    IcnnLaunch L{m, precision};
-    return icnn3_launch(ctx, L, n, F, dP, P, s);
+    return icnn_launch<3>(ctx, IcnnLaunch{m, precision, 3}, n, F, dP, P, s);
 }
 
 extern "C" int dxo_icnn3_correction(dxo_ctx* ctx, const dxo_icnn* m, double* H9) {
@@ -1335,23 +1218,6 @@ extern "C" int dxo_icnn3_eval(dxo_ctx* ctx, const dxo_icnn* m, int precision, in
     DXO_LOCK(ctx);
     if (!m) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_eval: model is NULL");
     if (precision != 0 && precision != 1) return dxo_fail(ctx, DXO_E_OPTION, "dxo_icnn3_eval: precision must be 0 (fp32 network) or 1 (fp64)");
-    if (n < 0) return dxo_fail(ctx, DXO_E_SIZE, "dxo_icnn3_eval: n < 0");
-    if (mem != DXO_MEM_HOST && mem != DXO_MEM_DEVICE) return dxo_fail(ctx, DXO_E_MEM, "dxo_icnn3_eval: bad mem");
-    if (n > 0 && (!F || !dP || !P)) return dxo_fail(ctx, DXO_E_NULL, "dxo_icnn3_eval: NULL array");
-    const uintptr_t all = (uintptr_t)F | (uintptr_t)dP | (uintptr_t)P;
-    if (all & 7u) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn3_eval: arrays must be 8-byte aligned");
-    if (mem == DXO_MEM_DEVICE && (all & 15u)) return dxo_fail(ctx, DXO_E_ALIGN, "dxo_icnn3_eval: device arrays must be 16-byte aligned");
-    IcnnLaunch L{m, precision};
-    if (mem == DXO_MEM_DEVICE) {
-        hipStream_t s = dxo_launch_stream(ctx);
-        int rc = dxo_device_begin(ctx, s);
-        if (rc != DXO_OK) return rc;
-        rc = icnn3_launch(ctx, L, n, F, dP, P, s);
-        if (rc != DXO_OK) return rc;
-        return dxo_device_end(ctx, s);
-    }
-    const size_t sd = sizeof(double);
-    std::vector<dxo_span> in = {{F, nullptr, 9 * sd}};
-    std::vector<dxo_span> out = {{nullptr, dP, 81 * sd}, {nullptr, P, 9 * sd}};
-    return dxo_run_host_pipeline(ctx, n, in, out, icnn3_chunk, &L);
+    IcnnLaunch L{m, precision, 3};
+    return hyper_array_entry(ctx, "dxo_icnn3_eval", n, mem, F, dP, P, 3, icnn_chunk, &L, false);
 }

@@ -7,6 +7,55 @@
 //   icnn_mfma_bf16x3_hybrid (icnn_variant 4)  scalar operands inside phase 1's MFMAs, packed phases 2 and 3: bit-identical, 2.93 ms
 #pragma once
 
+// A neuron PAIR's two fp32 values. A plain struct with scalar operators, NOT an ext_vector_type: <2 x float> arithmetic becomes
+// v_pk_{fma,mul,add}_f32, and a packed fp32 instruction issued beside a running MFMA stalls ~20 cycles
+// (profiles/r05_mfma_gap_probe.txt: one v_pk_fma_f32 per 32-cycle MFMA gap: 52 cycles per MFMA; six v_fma_f32: 37;
+// MI355X_MICROARCH.md: "packed f32 VALU ... an anti-lever beside MFMAs"). The arithmetic is identical (IEEE fp32 either way);
+// csrc/icnn.hip is built with -fno-slp-vectorize so that the compiler does not re-pack adjacent scalar operations
+// (_build.py, Makefile, build_variant.py). The shipped kernel works on icnn_f2p, the packed type, with the _p twins of what follows.
+struct icnn_f2 {
+    float x, y;
+};
+__device__ __forceinline__ icnn_f2 operator+(icnn_f2 a, icnn_f2 b) { return {a.x + b.x, a.y + b.y}; }
+__device__ __forceinline__ icnn_f2 operator-(icnn_f2 a, icnn_f2 b) { return {a.x - b.x, a.y - b.y}; }
+__device__ __forceinline__ icnn_f2 operator*(icnn_f2 a, icnn_f2 b) { return {a.x * b.x, a.y * b.y}; }
+__device__ __forceinline__ icnn_f2 operator+(icnn_f2 a, float b) { return {a.x + b, a.y + b}; }
+__device__ __forceinline__ icnn_f2 operator*(icnn_f2 a, float b) { return {a.x * b, a.y * b}; }
+
+// one B-fragment dword (two consecutive k: the neuron pair) of each part from a pair of fp32 values
+__device__ __forceinline__ void icnn_split_pair(icnn_f2 v, unsigned& h, unsigned& m, unsigned& l) {
+    const unsigned vx = __float_as_uint(v.x), vy = __float_as_uint(v.y);
+    h = __builtin_amdgcn_perm(vy, vx, 0x07060302u);
+    const icnn_f2 vh = {__uint_as_float(vx & 0xffff0000u), __uint_as_float(vy & 0xffff0000u)};
+    const icnn_f2 r = v - vh;
+    const unsigned rx = __float_as_uint(r.x), ry = __float_as_uint(r.y);
+    m = __builtin_amdgcn_perm(ry, rx, 0x07060302u);
+    const icnn_f2 rh = {__uint_as_float(rx & 0xffff0000u), __uint_as_float(ry & 0xffff0000u)};
+    const icnn_f2 q = r - rh;
+    l = __builtin_amdgcn_perm(__float_as_uint(q.y), __float_as_uint(q.x), 0x07060302u);
+}
+
+// softplus, softplus', softplus'' of two pre-activations: softplus3_mfma's operations on both halves of the pair
+__device__ __forceinline__ void softplus3_pk(icnn_f2 a, icnn_f2& sp, icnn_f2& s1, icnn_f2& s2) {
+    const icnn_f2 am = {fminf(a.x, 80.0f), fminf(a.y, 80.0f)};
+    const icnn_f2 t = am * 1.4426950408889634f;
+    const icnn_f2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+    const icnn_f2 ope = e + 1.0f;
+    const icnn_f2 r = {__builtin_amdgcn_rcpf(ope.x), __builtin_amdgcn_rcpf(ope.y)};
+    const icnn_f2 l = icnn_f2{__builtin_amdgcn_logf(ope.x), __builtin_amdgcn_logf(ope.y)} * 0.6931471805599453f;
+    sp = icnn_f2{fmaxf(l.x, a.x), fmaxf(l.y, a.y)};
+    s1 = e * r;
+    s2 = s1 * r;
+}
+
+__device__ __forceinline__ icnn_f2 icnn_fma2(icnn_f2 a, icnn_f2 b, icnn_f2 c) { return {__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)}; }
+
+// not `volatile`: a volatile asm orders every LDS read around it and would pin the table reads between the pins
+#define DXO_ICNN_PIN2(PAIR_) asm("" : "+v"((PAIR_).x), "+v"((PAIR_).y));
+#ifndef DXO_ICNN_PIPE_AGPR
+#define DXO_ICNN_PIPE_AGPR false
+#endif
+
 // ---- the phases of one half-tile (32 points, both half-waves on the same points, each on half of the neurons) as device
 // functions with SCALAR fp32 arithmetic, for icnn_mfma_bf16x3_pipe, which runs phase 1 of the NEXT half-tile beside phases 2 of
 // this one. The arithmetic (operations and their order per accumulator) is that of icnn_mfma_bf16x3_packed, bit for bit.
