@@ -6,7 +6,7 @@ ARCH    ?= gfx950
 CSRC    := dolfinx_external_operator_amd/csrc
 OBJDIR  := dolfinx_external_operator_amd/build
 LIB     := dolfinx_external_operator_amd/libdxo_hip.so
-SRCS    := $(wildcard $(CSRC)/*.hip)
+SRCS    := $(wildcard $(CSRC)/*.hip)      # every translation unit, pmg.hip (dxo_pmg_*) included
 OBJS    := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 FLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Iinclude -I$(CSRC)
 

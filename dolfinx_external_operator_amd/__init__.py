@@ -16,7 +16,7 @@ from .evaluation import (
 )
 from .device_assign import DeviceAssigner
 from .operand_eval import CsrPattern, DeviceCSR, DeviceMesh, FacetSet, DeviceOperand, LazyOperand, NodalTransfer, vertex_transfer
-from .krylov import AMG, BlockJacobi, KrylovResult, cg, fgmres, gmres, krylov_basis_rows, rigid_body_modes
+from .krylov import AMG, PMG, BlockJacobi, KrylovResult, cg, fgmres, gmres, krylov_basis_rows, rigid_body_modes
 from .operators import make_conductivity, make_heat, make_icnn, make_isihara, make_mohr_coulomb, make_von_mises, von_mises_commit_state
 
 __version__ = "0.1.0"
@@ -27,6 +27,6 @@ __all__ = [
     "make_von_mises", "make_heat", "make_conductivity", "make_mohr_coulomb", "make_icnn", "make_isihara", "McParams", "IsiharaParams", "von_mises_commit_state",
     "QuadratureExternalOperator", "MixedExternalOperator", "Operand", "Coefficient",
     "evaluate_operands", "evaluate_external_operators", "get_unrolled_dofmap", "DeviceMesh", "NodalTransfer", "vertex_transfer", "CsrPattern", "DeviceCSR", "FacetSet", "DeviceOperand", "LazyOperand", "AssignDesc",
-    "AMG", "BlockJacobi", "KrylovResult", "gmres", "fgmres", "cg", "rigid_body_modes", "krylov_basis_rows",
+    "AMG", "PMG", "BlockJacobi", "KrylovResult", "gmres", "fgmres", "cg", "rigid_body_modes", "krylov_basis_rows",
     "MultiGpu", "GATHER_NONE", "GATHER_FULL", "GATHER_COMPACT", "GATHER_COMPACT_DIRECT", "GATHER_COMPACT_PIPELINED",
 ]

@@ -18,7 +18,7 @@ INCLUDE = ROOT / "include"
 LIB = PKG / "libdxo_hip.so"
 ARCH = "gfx950"
 
-HIP_SOURCES = ["dxo_ctx.hip", "von_mises.hip", "heat.hip", "probe.hip", "mohr_coulomb.hip", "icnn.hip", "operand.hip", "vm_field.hip", "assign.hip", "heat_field.hip", "adjoint.hip", "arena.hip", "mgpu.hip", "operand_facet.hip", "field_ops.hip", "assemble.hip", "facet_form.hip", "krylov.hip", "amg.hip", "functional.hip", "transpose.hip", "hyper3.hip", "mohr_coulomb3.hip"]
+HIP_SOURCES = ["dxo_ctx.hip", "von_mises.hip", "heat.hip", "probe.hip", "mohr_coulomb.hip", "icnn.hip", "operand.hip", "vm_field.hip", "assign.hip", "heat_field.hip", "adjoint.hip", "arena.hip", "mgpu.hip", "operand_facet.hip", "field_ops.hip", "assemble.hip", "facet_form.hip", "krylov.hip", "amg.hip", "functional.hip", "transpose.hip", "hyper3.hip", "mohr_coulomb3.hip", "pmg.hip"]
 
 
 def _hipcc() -> str:

@@ -91,7 +91,8 @@ class KrylovOp(C.Structure):
 
 class KrylovPc(C.Structure):
     """dxo_krylov_pc: DXO_PC_NONE (0), DXO_PC_JACOBI (1, inv [n]), DXO_PC_BLOCK_JACOBI (2, inv [n/bs][bs][bs]), DXO_PC_AMG (3, inv
-    carries the dxo_amg handle) or DXO_PC_CALLBACK (4, inv carries the address of a KrylovCallback)."""
+    carries the dxo_amg handle), DXO_PC_CALLBACK (4, inv carries the address of a KrylovCallback) or DXO_PC_PMG (5, inv carries the
+    dxo_pmg handle)."""
     _fields_ = [("kind", C.c_int), ("bs", C.c_int), ("n", C.c_int64), ("inv", _P)]
 
 
@@ -243,6 +244,15 @@ _SIGNATURES = {
     "dxo_amg_create_transfer": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int, C.c_double, C.POINTER(AmgTransfer), C.c_int, C.c_int, C.c_int,
                                           C.POINTER(_P)]),
     "dxo_amg_transfer_info": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P)]),
+    "dxo_pmg_create": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(AmgTransfer), _P, C.c_int64, C.POINTER(_P)]),
+    "dxo_pmg_destroy": (C.c_int, [_P, _P]),
+    "dxo_pmg_set_smoother": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "dxo_pmg_setup": (C.c_int, [_P, _P, C.POINTER(KrylovOp), _P, C.POINTER(KrylovPc)]),
+    "dxo_pmg_apply": (C.c_int, [_P, _P, _P, _P]),
+    "dxo_pmg_restrict": (C.c_int, [_P, _P, _P, _P]),
+    "dxo_pmg_prolong": (C.c_int, [_P, _P, _P, _P]),
+    "dxo_pmg_info": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P),
+                               C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "dxo_mesh_set_facet_geometry": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "dxo_facet_set_create": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "dxo_facet_set_destroy": (C.c_int, [_P, _P]),

@@ -553,6 +553,7 @@ struct KrCall {
             dxo_amg_cycle(ctx, (dxo_amg*)pc->inv, r, z, s);
             return DXO_OK;
         }
+        if (pc->kind == DXO_PC_PMG) return dxo_pmg_cycle(ctx, (dxo_pmg*)pc->inv, r, z, s);
         if (pc->kind == DXO_PC_CALLBACK) {
             const dxo_krylov_callback* cb = (const dxo_krylov_callback*)pc->inv;
             const int rc = cb->apply(cb->user, r, z);
@@ -616,11 +617,11 @@ int kr_validate(dxo_ctx* ctx, const char* who, bool flexible, dxo_krylov* ws, co
     }
     if (op->csr && !has_bs(op->csr->bs)) return bs_refused(ctx, who, SPMV_TAKES, op->csr->bs);
     if (pc && pc->kind != DXO_PC_NONE) {
-        // pc->inv carries the dxo_amg*, a dxo_krylov_callback* or the inverses
+        // pc->inv carries the dxo_amg*, the dxo_pmg*, a dxo_krylov_callback* or the inverses
         const dxo_krylov_callback* cb = (const dxo_krylov_callback*)pc->inv;
         if (pc->kind == DXO_PC_CALLBACK) {
             if (!cb || !cb->apply) return fail(DXO_E_NULL, "the preconditioner has no callback");
-        } else if (pc->kind != DXO_PC_AMG) {
+        } else if (pc->kind != DXO_PC_AMG && pc->kind != DXO_PC_PMG) {
             if (pc->kind != DXO_PC_JACOBI && pc->kind != DXO_PC_BLOCK_JACOBI) return fail(DXO_E_OPTION, "unknown preconditioner kind");
             if (!pc->inv) return fail(DXO_E_NULL, "the preconditioner has no inverse");
             if (misaligned(pc->inv)) return fail(DXO_E_ALIGN, "the preconditioner's inverse is not 8-byte aligned");
@@ -629,7 +630,10 @@ int kr_validate(dxo_ctx* ctx, const char* who, bool flexible, dxo_krylov* ws, co
             snprintf(msg, sizeof msg, "the preconditioner covers %lld rows, the operator has %lld", (long long)pc->n, (long long)ws->n);
             return fail(DXO_E_SIZE, msg);
         }
-        if (pc->kind == DXO_PC_AMG) {
+        if (pc->kind == DXO_PC_PMG) {
+            const int rc = dxo_pmg_pc_check(ctx, who, (const dxo_pmg*)pc->inv, op->csr, pc->n);
+            if (rc != DXO_OK) return rc;
+        } else if (pc->kind == DXO_PC_AMG) {
             const int rc = dxo_amg_pc_check(ctx, who, (const dxo_amg*)pc->inv, op->csr, pc->bs, pc->n);
             if (rc != DXO_OK) return rc;
             if (!flexible && dxo_amg_cycle_is_k((const dxo_amg*)pc->inv))
@@ -879,6 +883,10 @@ int dxo_kr_spmv_launch(dxo_ctx* ctx, const dxo_csr* csr, const double* values, c
 }
 
 int dxo_kr_spmv_lanes(const dxo_ctx* ctx, const dxo_csr* csr) { return spmv_lanes(ctx, csr); }
+
+int dxo_kr_bj_apply_launch(dxo_ctx* ctx, const char* who, int bs, int64_t n, const double* inv, const double* r, double* z, hipStream_t s) {
+    return bj_apply_launch(ctx, who, bs, n, inv, r, z, s);
+}
 
 extern "C" int dxo_csr_spmv(dxo_ctx* ctx, const dxo_csr* csr, const double* values, double alpha, const double* x, double beta, double* y) {
     if (!ctx) return DXO_E_NULL;

@@ -236,8 +236,18 @@ int dxo_kr_spmv_launch(dxo_ctx* ctx, const dxo_csr* csr, const double* values, c
 // transposed product of transpose.hip
 int dxo_kr_spmv_lanes(const dxo_ctx* ctx, const dxo_csr* csr);
 
+// krylov.hip: z = inv r per block by the kernel of dxo_block_jacobi_apply (bs 1, 2, 3; DXO_E_DIM and no launch for any other), for the
+// coarse step of the p-multigrid
+int dxo_kr_bj_apply_launch(dxo_ctx* ctx, const char* who, int bs, int64_t n, const double* inv, const double* r, double* z, hipStream_t s);
+
 // amg.hip: the checks of a DXO_PC_AMG preconditioner against the operator, one cycle z = M(r) on the stream (V or K, as set by
 // dxo_amg_set_cycle), and whether that cycle is the K-cycle (not a fixed linear operator: flexible GMRES only)
 int dxo_amg_pc_check(dxo_ctx* ctx, const char* who, const dxo_amg* amg, const dxo_csr* op_csr, int bs, int64_t n);
 void dxo_amg_cycle(dxo_ctx* ctx, dxo_amg* amg, const double* r, double* z, hipStream_t s);
 bool dxo_amg_cycle_is_k(const dxo_amg* amg);
+
+// pmg.hip: the checks of a DXO_PC_PMG preconditioner against the operator, and one cycle z = M(r) on the stream (nonzero: a callback of
+// the object failed)
+struct dxo_pmg;
+int dxo_pmg_pc_check(dxo_ctx* ctx, const char* who, const dxo_pmg* pmg, const dxo_csr* op_csr, int64_t n);
+int dxo_pmg_cycle(dxo_ctx* ctx, dxo_pmg* pmg, const double* r, double* z, hipStream_t s);

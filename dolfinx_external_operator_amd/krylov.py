@@ -13,7 +13,7 @@ from dataclasses import dataclass
 
 from ._lib import KRYLOV_APPLY_FN, AmgLevelInfo, KrylovCallback, KrylovInfo, KrylovOp, KrylovPc, _CudaArrayView
 
-PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI, PC_AMG, PC_CALLBACK = 0, 1, 2, 3, 4
+PC_NONE, PC_JACOBI, PC_BLOCK_JACOBI, PC_AMG, PC_CALLBACK, PC_PMG = 0, 1, 2, 3, 4, 5
 _SMOOTHERS = {"jacobi": 0, "chebyshev": 1}           # DXO_AMG_SMOOTH_*
 _RHO_KINDS = {"inf-norm": 0, "power": 1}             # DXO_AMG_RHO_*
 _CYCLES = {"V": 0, "K": 1}                           # DXO_AMG_CYCLE_*
@@ -539,6 +539,219 @@ class AMG:
         return self._array(b, i.n_rows * self.n_modes, "<f8").reshape(-1, self.n_modes)
 
 
+class PMG:
+    """Two-level p-multigrid preconditioner whose fine level is an operator, not a matrix (dxo_pmg_*, csrc/pmg.hip): for the
+    matrix-free and array-free solves of quadratic elements, where DeviceCSR.amg(first_transfer=...) would need the assembled matrix.
+
+    One apply: the Chebyshev polynomial of `degree` in Dinv A on [lower rho, rho] from zero, the residual restricted to the degree-1
+    space on the same cells by `transfer` (a NodalTransfer: DeviceMesh.vertex_transfer), a preconditioner of the degree-1 matrix,
+    prolongation, the same polynomial again: 2 degree operator calls (`matvecs_per_apply`). A fixed linear operator, symmetric for a
+    symmetric A and coarse preconditioner: pass it as M to gmres, cg or fgmres.
+
+    The constructor runs the symbolic part (dxo_pmg_create). `bs`: dofs per node (1, 2, 3); `constrained`: the dofs given to
+    bilinear_assemble(bcs=...) (an int32 CUDA tensor, or anything numpy converts), None for none. `coarse_constrained` is then the
+    Dirichlet set of the coarse matrix: assemble the degree-1 matrix on DeviceMesh.vertex_mesh(...) with bcs=pmg.coarse_constrained.
+    `degree`, `rho_iters`, `lower`, `safety`: the smoother, as in AMG (dxo_pmg_set_smoother; set_smoother() changes it for the next
+    setup())."""
+
+    def __init__(self, transfer, bs: int, constrained=None, ctx=None, degree: int = 2, rho_iters: int = 10, lower: float = 0.1,
+                 safety: float = 1.1):
+        torch = _torch()
+        import numpy as np
+
+        from ._lib import AmgTransfer
+
+        if ctx is None:
+            from ._lib import default_context
+
+            ctx = default_context()
+        self.ctx, self.bs = ctx, int(bs)
+        self.device = torch.device("cuda", ctx.device)
+        self.n_nodes = int(transfer.ptr.size) - 1
+        self.n = self.n_nodes * self.bs
+        if constrained is None:
+            bc = torch.empty(0, dtype=torch.int32, device=self.device)
+        elif isinstance(constrained, torch.Tensor):
+            bc = constrained.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            bc = torch.from_numpy(np.ascontiguousarray(constrained, dtype=np.int32)).to(self.device)
+        t = transfer
+        desc = AmgTransfer(t.n_coarse, t.ptr.ctypes.data, t.col.ctypes.data, t.w.ctypes.data, t.coarse_to_fine.ctypes.data)
+        h = C.c_void_p()
+        _use_current_stream(ctx)
+        rc = ctx.lib.dxo_pmg_create(ctx._h, self.n_nodes, self.bs, C.byref(desc), C.c_void_p(bc.data_ptr()) if bc.numel() else None,
+                                    int(bc.numel()), C.byref(h))
+        ctx.check(rc, "dxo_pmg_create")
+        self._h = h
+        self._fin = weakref.finalize(self, ctx.lib.dxo_pmg_destroy, None, h)
+        self._fin.atexit = False
+        self.transfer = transfer
+        self._A = self._dinv = self._coarse = None
+        self._keep: tuple = ()
+        self._failure: list = []
+        if (int(degree), int(rho_iters), float(lower), float(safety)) != (2, 10, 0.1, 1.1):
+            self.set_smoother(degree, rho_iters, lower, safety)
+
+    def set_smoother(self, degree: int = 2, rho_iters: int = 10, lower: float = 0.1, safety: float = 1.1) -> "PMG":
+        """The Chebyshev degree (1..8), the steps of the power iteration, and the interval [lower rho, rho] with rho = safety times the
+        estimate (dxo_pmg_set_smoother). Takes effect at the next setup(); apply() and the solvers raise ValueError (DXO_E_OPTION)
+        until then."""
+        rc = self.ctx.lib.dxo_pmg_set_smoother(self.ctx._h, self._h, int(degree), int(rho_iters), float(lower), float(safety))
+        self.ctx.check(rc, "dxo_pmg_set_smoother")
+        return self
+
+    def _callback(self, f, n: int):
+        """A C callback (v, out) -> f(tensor view of v, tensor view of out) on vectors of n entries; an exception is kept for
+        _raise()."""
+        torch = _torch()
+        views: dict = {}
+        ctx, dev, failure = self.ctx, self.device, self._failure
+
+        def view(ptr: int):
+            t = views.get(ptr)
+            if t is None:
+                t = views[ptr] = torch.as_tensor(_CudaArrayView(ctx, ptr, n, "<f8"), device=dev)
+            return t
+
+        def cb(_user, v, out):
+            try:
+                f(view(v), view(out))
+                return 0
+            except BaseException as e:      # noqa: BLE001 — re-raised when the call into the library has returned
+                failure.append(e)
+                return 1
+
+        return KRYLOV_APPLY_FN(cb)
+
+    def _raise(self) -> None:
+        if self._failure:
+            e = self._failure[0]
+            self._failure.clear()
+            raise e
+
+    def setup(self, A, dinv, coarse) -> "PMG":
+        """The numeric part (dxo_pmg_setup): rho of Dinv A by `rho_iters` operator calls and the Chebyshev pairs, both left on the
+        device (no synchronisation). `A`: a DeviceCSR, or a callable (v, out) that sets out = A v, the identity on constrained dofs.
+        `dinv`: a float64 CUDA tensor, the inverse diagonal with 1 on constrained dofs. `coarse`: an AMG (V-cycle), a BlockJacobi, or
+        a callable (r, out) on the n_coarse vectors. The object keeps references to all three; call setup() again when the operator
+        changed (a Newton iteration)."""
+        from .operand_eval import DeviceCSR
+
+        _check_vec(dinv, self.n, self.device, "PMG.setup: dinv")
+        keep = []
+        if isinstance(A, DeviceCSR):
+            op = KrylovOp(A.pattern.n_rows, A.pattern._h, C.c_void_p(A.values.data_ptr()), KRYLOV_APPLY_FN(), None)
+        elif callable(A):
+            cb = self._callback(A, self.n)
+            keep.append(cb)
+            op = KrylovOp(self.n, None, None, cb, None)
+        else:
+            raise TypeError("PMG.setup: A must be a DeviceCSR or a callable (v, out) that sets out = A v")
+        if isinstance(coarse, (AMG, BlockJacobi)):
+            pc = coarse._pc()
+        elif callable(coarse):
+            ccb = self._callback(coarse, self.n_coarse)
+            cstruct = KrylovCallback(ccb, None)
+            keep += [ccb, cstruct]
+            pc = KrylovPc(PC_CALLBACK, 1, self.n_coarse, C.cast(C.pointer(cstruct), C.c_void_p))
+        else:
+            raise TypeError("PMG.setup: coarse must be an AMG, a BlockJacobi or a callable (r, out)")
+        _use_current_stream(self.ctx)
+        rc = self.ctx.lib.dxo_pmg_setup(self.ctx._h, self._h, C.byref(op), C.c_void_p(dinv.data_ptr()), C.byref(pc))
+        self._raise()
+        self.ctx.check(rc, "dxo_pmg_setup")
+        self._A, self._dinv, self._coarse, self._keep = A, dinv, coarse, tuple(keep)
+        return self
+
+    def _call(self, name: str, fn, a, na: int, out, nout: int):
+        torch = _torch()
+        _check_vec(a, na, self.device, f"PMG.{name}: input")
+        if out is None:
+            out = torch.empty(nout, dtype=torch.float64, device=self.device)
+        _check_vec(out, nout, self.device, f"PMG.{name}: out")
+        _use_current_stream(self.ctx)
+        rc = fn(self.ctx._h, self._h, C.c_void_p(a.data_ptr()), C.c_void_p(out.data_ptr()))
+        self._raise()
+        self.ctx.check(rc, "dxo_pmg_" + name)
+        return out
+
+    def apply(self, r, out=None):
+        """out = M r, one cycle (dxo_pmg_apply); out may be r. Returns out."""
+        return self._call("apply", self.ctx.lib.dxo_pmg_apply, r, self.n, out, self.n)
+
+    def restrict(self, r, out=None):
+        """out = P^T r on the n_coarse vector (dxo_pmg_restrict): sums over the fine nodes in ascending order."""
+        return self._call("restrict", self.ctx.lib.dxo_pmg_restrict, r, self.n, out, self.n_coarse)
+
+    def prolong(self, e, out=None):
+        """out = P e on the fine vector (dxo_pmg_prolong): sums over the coarse nodes in ascending order."""
+        return self._call("prolong", self.ctx.lib.dxo_pmg_prolong, e, self.n_coarse, out, self.n)
+
+    def _info(self) -> dict:
+        nc, pb, pd, cb, ncb, rho, pairs, deg, mv = (C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(),
+                                                    C.c_int(), C.c_int64())
+        rc = self.ctx.lib.dxo_pmg_info(self.ctx._h, self._h, C.byref(nc), C.byref(pb), C.byref(pd), C.byref(cb), C.byref(ncb), C.byref(rho),
+                                       C.byref(pairs), C.byref(deg), C.byref(mv))
+        self.ctx.check(rc, "dxo_pmg_info")
+        return {"n_coarse": int(nc.value), "p_blocks": int(pb.value), "p_diag": pd.value, "c_bc": cb.value, "n_c_bc": int(ncb.value),
+                "rho": rho.value, "pairs": pairs.value, "degree": int(deg.value), "matvecs": int(mv.value)}
+
+    def _tensor(self, ptr, n: int, typestr: str, dtype):
+        torch = _torch()
+        if not n:
+            return torch.empty(0, dtype=dtype, device=self.device)
+        return torch.as_tensor(_CudaArrayView(self, ptr, int(n), typestr), device=self.device)
+
+    @property
+    def n_coarse(self) -> int:
+        """Rows of the coarse space: coarse nodes times bs (dxo_pmg_info)."""
+        return self._info()["n_coarse"]
+
+    @property
+    def degree(self) -> int:
+        return self._info()["degree"]
+
+    @property
+    def matvecs_per_apply(self) -> int:
+        """Operator calls of one apply: 2 degree."""
+        return self._info()["matvecs"]
+
+    @property
+    def coarse_constrained(self):
+        """The constrained dofs of the coarse space, an int32 CUDA tensor (a view, alive as long as this object): dof (v, c) iff the
+        fine dof (coarse_to_fine[v], c) is constrained. The `bcs` of the coarse assembly."""
+        torch = _torch()
+        i = self._info()
+        return self._tensor(i["c_bc"], i["n_c_bc"], "<i4", torch.int32)
+
+    @property
+    def p_diag(self):
+        """(p_blocks, bs): the diagonals of the blocks of P, a float64 CUDA tensor view."""
+        torch = _torch()
+        i = self._info()
+        return self._tensor(i["p_diag"], i["p_blocks"] * self.bs, "<f8", torch.float64).view(-1, self.bs)
+
+    @property
+    def pairs(self):
+        """(degree, 2): the pairs (c1, c2) of the Chebyshev steps of the last setup, a float64 CUDA tensor view (no synchronisation)."""
+        torch = _torch()
+        i = self._info()
+        return self._tensor(i["pairs"], 2 * i["degree"], "<f8", torch.float64).view(-1, 2)
+
+    @property
+    def rho(self) -> float:
+        """The estimate of the spectral radius of Dinv A of the last setup, times `safety`. Reading it synchronises."""
+        torch = _torch()
+        return float(self._tensor(self._info()["rho"], 1, "<f8", torch.float64).cpu()[0])
+
+    def _pc(self) -> KrylovPc:
+        return KrylovPc(PC_PMG, self.bs, self.n, C.c_void_p(self._h.value))
+
+    def close(self) -> None:
+        """Frees the device memory (dxo_pmg_destroy)."""
+        self._fin()
+
+
 def csr_matvec(A, x, y=None, alpha: float = 1.0, beta: float = 0.0, transpose: bool = False):
     """y = alpha A x + beta y on the device (dxo_csr_spmv); with beta == 0, y is not read. Returns y. transpose=True:
     y = alpha A^T x + beta y (dxo_csr_spmv_t), bit for bit the product with DeviceCSR.transpose()'s matrix."""
@@ -668,6 +881,10 @@ def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxit
         if M.n != n or M.device != dev or (isinstance(A, DeviceCSR) and A.pattern.bs != M.bs):
             raise ValueError(f"{entry}: the multigrid preconditioner covers {M.n} rows (bs {M.bs}) on {M.device}, the operator has {n} on {dev}")
         pc = M._pc()
+    elif isinstance(M, PMG):
+        if M.n != n or M.device != dev:
+            raise ValueError(f"{entry}: the p-multigrid preconditioner covers {M.n} rows on {M.device}, the operator has {n} on {dev}")
+        pc = M._pc()
     elif isinstance(M, torch.Tensor):
         _check_vec(M, n, dev, f"{entry}: M (inverse diagonal)")
         pc = KrylovPc(PC_JACOBI, 1, n, C.c_void_p(M.data_ptr()))
@@ -692,7 +909,7 @@ def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxit
         mstruct = KrylovCallback(mcb, None)      # both stay referenced until the solve has returned
         pc = KrylovPc(PC_CALLBACK, 1, n, C.cast(C.pointer(mstruct), C.c_void_p))
     else:
-        raise TypeError(f"{entry}: M must be None, a BlockJacobi, an AMG, a tensor holding an inverse diagonal or a callable (r, out)")
+        raise TypeError(f"{entry}: M must be None, a BlockJacobi, an AMG, a PMG, a tensor holding an inverse diagonal or a callable (r, out)")
     if maxiter is None:
         maxiter = max(1000, 10 * restart)
     ws = _workspace(ctx, n, restart, basis)
@@ -702,6 +919,8 @@ def _solve(entry: str, A, b, x, M, restart: int, rtol: float, atol: float, maxit
                                  float(atol), int(maxiter), int(check_every), C.byref(info))
     if failure:
         raise failure[0]
+    if isinstance(M, PMG):
+        M._raise()
     ctx.check(rc, entry)
     return KrylovResult(x=x, iterations=int(info.iterations), residual=float(info.residual), converged=bool(info.converged),
                         breakdown=bool(info.breakdown), restarts=int(info.restarts), ms=float(info.ms), basis=basis,
@@ -715,7 +934,8 @@ def gmres(A, b, x=None, M=None, restart: int = 30, rtol: float = 1e-10, atol: fl
     A: a DeviceCSR, or a callable (v, out) that sets out = A v on the device (e.g. DeviceMesh.bilinear_apply with option
     consumer_overwrite = 1; `ctx` then names the context, default_context() otherwise). M: None, a BlockJacobi, an AMG (one V-cycle
     per iteration; with a callable A the multigrid of an assembled, possibly lagged, matrix of the same size), a float64 CUDA tensor
-    holding an inverse diagonal (1 / bilinear_diagonal for the matrix-free path), or a callable (r, out) that sets out = M r on the
+    holding an inverse diagonal (1 / bilinear_diagonal for the matrix-free path), a PMG after its setup() (the p-multigrid of the
+    matrix-free path, DXO_PC_PMG), or a callable (r, out) that sets out = M r on the
     device; an exception in it is re-raised after the solve. M must be a fixed linear operator here, the same at every call: M is
     applied once more to the combination at the end of a cycle. One that varies (an inner iteration, an AMG with the K-cycle,
     which raises ValueError here) belongs to fgmres. An AMG with precision="fp32" is a fixed linear operator up to single-precision
@@ -758,4 +978,4 @@ def cg(A, b, x=None, M=None, rtol: float = 1e-10, atol: float = 0.0, maxiter: in
     return _solve("dxo_krylov_cg", A, b, x, M, 1, rtol, atol, maxiter, check_every, ctx)
 
 
-__all__ = ["AMG", "BlockJacobi", "KrylovResult", "krylov_basis_rows", "cg", "csr_matvec", "fgmres", "gmres", "rigid_body_modes"]
+__all__ = ["AMG", "PMG", "BlockJacobi", "KrylovResult", "krylov_basis_rows", "cg", "csr_matvec", "fgmres", "gmres", "rigid_body_modes"]

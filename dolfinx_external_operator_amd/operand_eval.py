@@ -71,6 +71,7 @@ class DeviceMesh:
         self.ctx.check(self.ctx.lib.dxo_mesh_create(self.ctx._h, C.byref(d), C.byref(h)), "dxo_mesh_create")
         self._h = h
         self._dofmap, self._geom_dofmap = dofmap, geom_dofmap      # host arrays, for vertex_transfer
+        self._x = x                                                # and for vertex_mesh
         if psi is not None:     # values of the coordinate element at the points: the operand `x` (set_coordinate_values)
             self.set_coordinate_values(psi)
 
@@ -128,6 +129,25 @@ class DeviceMesh:
         dropped; a node shared by several cells must get the same row from each (ValueError otherwise). A degree-1 field, where every
         row would be a single 1, is refused."""
         return vertex_transfer(self._dofmap, self._geom_dofmap, psi_nodes, self.num_field_nodes)
+
+    def vertex_mesh(self, psi, dpsi, weights=None) -> "DeviceMesh":
+        """The degree-1 mesh on the same cells, whose nodes ARE the geometry nodes: the coarse numbering of vertex_transfer, on which
+        the coarse matrix of a krylov.PMG is assembled. `psi` (nq, ngeom) and `dpsi` (nq, ngeom, gdim): the coordinate element at a
+        quadrature rule of the caller's choice, which may be coarser than this mesh's (phi = psi, dphi = dpsi, dofmap = geom_dofmap);
+        `weights` (nq,): the rule's weights (set_weights). A mesh whose field is already of degree 1 raises ValueError, as
+        vertex_transfer does."""
+        if self._dofmap.shape[1] <= self._geom_dofmap.shape[1]:
+            raise ValueError("vertex_mesh: the field has no more nodes per cell than the geometry (degree 1): there is nothing to coarsen")
+        psi = np.ascontiguousarray(psi, dtype=np.float64)
+        dpsi = np.ascontiguousarray(dpsi, dtype=np.float64)
+        ng = self._geom_dofmap.shape[1]
+        if psi.ndim != 2 or psi.shape[1] != ng or dpsi.shape != (psi.shape[0], ng, self.gdim):
+            raise ValueError("vertex_mesh: psi (nq, ngeom) and dpsi (nq, ngeom, gdim) of the coordinate element")
+        vm = DeviceMesh(gdim=self.gdim, phi=psi, dphi=dpsi, dpsi=dpsi, dofmap=self._geom_dofmap, geom_dofmap=self._geom_dofmap, x=self._x,
+                        num_field_nodes=self._x.shape[0], ctx=self.ctx, psi=psi)
+        if weights is not None:
+            vm.set_weights(weights)
+        return vm
 
     def value_size(self, kind: str, bs: int) -> int:
         r = self.ctx.lib.dxo_operand_value_size(self.gdim, int(bs), KINDS[kind])

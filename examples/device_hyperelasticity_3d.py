@@ -15,6 +15,15 @@ Per Newton iteration:
     --matrix-free --recompute (--model isihara only): no quadrature array at all. R, K v and diag(K) are formed from u alone,
       F = I + grad u and the model evaluated again in the registers of every call (dxo_isihara3_residual,
       dxo_isihara3_tangent_apply, dxo_isihara3_tangent_diagonal): dP [n][9][9] and P [n][9], 720 bytes per point, are never allocated
+    --matrix-free --pc pmg: the Krylov solve is preconditioned by a two-level p-multigrid on the operator (krylov.PMG, dxo_pmg_*) in
+      place of point Jacobi: Chebyshev smoothing with K v and diag(K) alone, and a coarse correction on the degree-1 space of the same
+      cells. Per Newton iteration the coarse u_c = u[coarse_to_fine] is an injection, dxo_isihara3_field (the model's field call) runs on the degree-1
+      companion mesh (DeviceMesh.vertex_mesh; the 1-point rule on tetrahedra, the 8-point rule on hexahedra), dxo_bilinear_assemble
+      gives the degree-1 matrix with the coarse Dirichlet set of the PMG, and a smoothed-aggregation multigrid with the six
+      rigid-body modes of the vertices (symbolic phase once) is the coarse preconditioner. With --recompute the coarse dP array is
+      the one quadrature array this route still holds: 81 doubles per coarse point, against 4 (tetrahedra) or 27 (hexahedra) fine
+      points per cell, a quarter or 8/27 of the fine dP array, before the per-point data of P (`coarse_bytes` in the report also
+      counts the coarse P, the coarse matrix and the values of the hierarchy below it)
     u += d
 Only dof vectors are touched outside the kernels; they are torch CUDA tensors.
 
@@ -28,7 +37,7 @@ operand kernel, then the network kernel on the invariants of the 3x3 F). FILE is
 fp64, so that stress and tangent are consistent to fp64 rounding and the residual can fall by the ten decades the Newton loop asks
 for; with fp32, the reference's network precision, the stress carries fp32 rounding (about 1e-7) and the loop's tolerance may be out of reach.
 Needs an MI355X.    python3 examples/device_hyperelasticity_3d.py [--n 6] [--hex] [--matrix-free [--recompute]] [--solver cg|gmres]
-                                                                   [--model isihara|icnn] [--weights FILE] [--precision fp32|fp64]
+                                                                   [--pc jacobi|pmg] [--model isihara|icnn] [--weights FILE] [--precision fp32|fp64]
 """
 import argparse
 import pathlib
@@ -41,8 +50,8 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from dolfinx_external_operator_amd import MEM_DEVICE, Context, DeviceMesh, IsiharaParams, cg, gmres, rigid_body_modes  # noqa: E402
-from tools.synthetic import gauss_tensor_rule, structured_mesh, with_rule  # noqa: E402
+from dolfinx_external_operator_amd import MEM_DEVICE, PMG, Context, DeviceMesh, IsiharaParams, cg, gmres, rigid_body_modes  # noqa: E402
+from tools.synthetic import coordinate_element_at_nodes, gauss_tensor_rule, structured_mesh, vertex_companion, with_rule  # noqa: E402
 
 MAX_NEWTON = 20      # a load step that needs more has failed
 
@@ -69,12 +78,18 @@ def load_state_dict(path):
 
 def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float = 0.4, hexahedra: bool = False, matrix_free: bool = False,
          solver: str = "cg", verbose: bool = True, c=(0.5, 1.0, 1.0, 1.5), model: str = "isihara", weights=None,
-         precision: str = "fp64", recompute: bool = False) -> dict:
+         precision: str = "fp64", recompute: bool = False, pc: str = "jacobi") -> dict:
     """Returns the per-step Newton residual histories, the linear iteration counts, the bytes of quadrature data held
-    (`quadrature_bytes`: dP and P, 720 per point; 0 with `recompute`) and the final displacement (`u`, host array).
+    (`quadrature_bytes`: dP and P, 720 per point; 0 with `recompute`), the preconditioner of the matrix-free solve (`pc`), what its
+    coarse level holds (`coarse_bytes`: the coarse dP and P arrays, the coarse matrix and the values of the hierarchy below it; 0
+    with "jacobi") and the final displacement (`u`, host array).
     Raises RuntimeError if a load step does not converge within MAX_NEWTON iterations or a linear solve fails."""
     if recompute and not (matrix_free and model == "isihara"):
         raise ValueError("recompute needs matrix_free and the analytic model (--matrix-free --model isihara)")
+    if pc not in ("jacobi", "pmg"):
+        raise ValueError('pc must be "jacobi" or "pmg"')
+    if pc == "pmg" and not matrix_free:
+        raise ValueError("pc pmg needs matrix_free (--matrix-free): the assembled route has the multigrid of its matrix")
     dev = torch.device("cuda:0")
     ctx = Context(0)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -139,16 +154,53 @@ def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float =
             dm.bilinear_apply("grad", "grad", G, dP.data_ptr(), vm.data_ptr(), Kv.data_ptr())
         out.copy_(torch.where(free, Kv, v))
 
+    def coarse_level():
+        """The degree-1 matrix at the injected u and its multigrid; the objects are made at the first call"""
+        if "pmg" not in state:
+            if hexahedra:
+                rule = gauss_tensor_rule("hexahedron", 2)
+            else:
+                rule = (np.array([[0.25, 0.25, 0.25]]), np.array([1.0 / 6.0]))
+            mc = vertex_companion(mesh, *rule)
+            transfer = dm.vertex_transfer(coordinate_element_at_nodes(mesh.cell, 2))
+            state["pmg"] = PMG(transfer, G, constrained=bcs, ctx=ctx)
+            state["dmc"] = dmc = dm.vertex_mesh(mc.psi, mc.dpsi, mc.weights)
+            state["ctf"] = torch.from_numpy(transfer.coarse_to_fine.astype(np.int64)).to(dev)
+            nptc = mesh.num_cells * mc.nq
+            state["dPc"], state["Pc"] = torch.zeros(nptc * 81, **f64), torch.zeros(nptc * 9, **f64)
+            state["pattern_c"] = dmc.csr_pattern(G)
+            state["values_c"] = torch.zeros(state["pattern_c"].nnz, **f64)
+        dmc = state["dmc"]
+        uc = u.view(nn, G)[state["ctf"]].reshape(-1).contiguous()
+        if net is None:
+            ctx.isihara3_field(prm, dmc._h, MEM_DEVICE, uc.data_ptr(), state["dPc"].data_ptr(), state["Pc"].data_ptr())
+        else:
+            ctx.icnn3_field(net, net_precision, dmc._h, MEM_DEVICE, uc.data_ptr(), state["dPc"].data_ptr(), state["Pc"].data_ptr())
+        Ac = dmc.bilinear_assemble("grad", "grad", G, state["dPc"].data_ptr(), state["pattern_c"], values=state["values_c"],
+                                   bcs=state["pmg"].coarse_constrained, diagonal=1.0)
+        if "amg_c" not in state:
+            state["amg_c"] = Ac.amg(state["pmg"].coarse_constrained, near_nullspace=rigid_body_modes(mesh.x, ctx=ctx))
+            amg = state["amg_c"]
+            report["coarse_bytes"] = (sum(t.numel() * t.element_size() for t in (state["dPc"], state["Pc"], state["values_c"]))
+                                      + sum(8 * d["block_nnz"] * d["bs"] ** 2 for d in amg.levels[1:]))
+        else:
+            state["amg_c"].setup(Ac)
+        return state["amg_c"]
+
     def solve_matrix_free(b):
         if recompute:
             dm.isihara3_tangent_diagonal(prm, u.data_ptr(), diag.data_ptr())
         else:
             dm.bilinear_diagonal("grad", "grad", G, dP.data_ptr(), diag.data_ptr())
         minv = torch.where(free, 1.0 / diag, torch.ones_like(diag))
+        if pc == "pmg":
+            amg = coarse_level()
+            return krylov(jacobian_times, b, M=state["pmg"].setup(jacobian_times, minv, amg), rtol=1e-12, maxiter=20000, ctx=ctx)
         return krylov(jacobian_times, b, M=minv, rtol=1e-12, maxiter=20000, ctx=ctx)
 
     report = {"cells": mesh.num_cells, "points": npts, "dofs": nn * G, "matrix_free": matrix_free, "solver": solver, "model": model, "recompute": recompute,
-              "quadrature_bytes": sum(t.numel() * t.element_size() for t in (dP, P) if t is not None), "steps": []}
+              "quadrature_bytes": sum(t.numel() * t.element_size() for t in (dP, P) if t is not None), "pc": pc if matrix_free else "amg",
+              "coarse_bytes": 0, "steps": []}
     if verbose:
         print(f"{npts} points, quadrature data held: {report['quadrature_bytes']} bytes ({'none' if recompute else '720 per point: dP [n][9][9] and P [n][9]'})")
     prev = np.zeros_like(x)
@@ -183,6 +235,9 @@ def main(n_side: int = 6, steps: int = 3, compress: float = 0.15, twist: float =
     report["u"] = u.cpu().numpy()
     if net is not None:
         ctx.icnn_destroy(net)
+    if "pmg" in state:
+        state["pmg"].close()
+        state["dmc"].close()
     dm.close()
     ctx.close()
     return report
@@ -197,11 +252,15 @@ if __name__ == "__main__":
     ap.add_argument("--recompute", action="store_true", help="with --matrix-free --model isihara: residual, K v and diag(K) from u alone, "
                     "no quadrature array (dP, P) is allocated")
     ap.add_argument("--solver", choices=["cg", "gmres"], default="cg")
+    ap.add_argument("--pc", choices=["jacobi", "pmg"], default="jacobi", help="with --matrix-free: point Jacobi (default) or the two-level "
+                    "p-multigrid on the operator")
     ap.add_argument("--model", choices=["isihara", "icnn"], default="isihara", help="the analytic energy (default) or the trained network")
     ap.add_argument("--weights", help="--model icnn: the network's state_dict (torch file or .npz)")
     ap.add_argument("--precision", choices=["fp32", "fp64"], default="fp64", help="--model icnn: precision of the network")
     a = ap.parse_args()
     if a.recompute and not (a.matrix_free and a.model == "isihara"):
         ap.error("--recompute is valid only with --matrix-free and --model isihara")
+    if a.pc == "pmg" and not a.matrix_free:
+        ap.error("--pc pmg is valid only with --matrix-free")
     main(a.n, steps=a.steps, hexahedra=a.hex, matrix_free=a.matrix_free, solver=a.solver, model=a.model, weights=a.weights, precision=a.precision,
-         recompute=a.recompute)
+         recompute=a.recompute, pc=a.pc)

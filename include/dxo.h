@@ -926,6 +926,72 @@ int dxo_amg_create_transfer(dxo_ctx* ctx, const dxo_csr* csr, const double* valu
 int dxo_amg_transfer_info(dxo_ctx* ctx, const dxo_amg* amg, int* present, int64_t* n_coarse, int64_t* p_blocks, const double** p_diag,
                           const int32_t** coarse_to_fine);
 
+/* ---- p-multigrid on an operator (csrc/pmg.hip), DEVICE memory only ------------------------------------------------
+ * A two-level cycle for quadratic elements whose finest level is an OPERATOR (a dxo_krylov_op: a matrix, or a callback such as
+ * dxo_isihara3_tangent_apply), never a matrix: Chebyshev smoothing in Dinv A with the inverse DIAGONAL alone, restriction of the
+ * residual to the degree-1 space on the same cells by a nodal interpolation (dxo_amg_transfer, DeviceMesh.vertex_transfer), any
+ * preconditioner of a matrix of that space (usually a dxo_amg of the rediscretised degree-1 matrix, which for nested Lagrange spaces,
+ * the same rule and the same coefficients is P^T A P to rounding), prolongation, and the same polynomial again. bs is 1, 2 or 3.
+ * dxo_pmg_create  : the symbolic part, host C++, once per mesh. `transfer` (HOST arrays, copied) is checked by the rules of
+ *                   dxo_amg_create_transfer with its error codes, but for the stagnation rule of the multigrid's coarsening, which
+ *                   says nothing about a transfer (n_coarse above n_nodes: DXO_E_SIZE). `constrained` is the DEVICE int32 list given to
+ *                   dxo_csr_dirichlet (NULL with n_constrained = 0; out-of-range entries are ignored). The prolongator P = W (x) I_bs
+ *                   is stored as dxo_amg_create_transfer stores it, p_diag [block][bs] = w_iv keep(i, c) keep(coarse_to_fine[v], c),
+ *                   with its transposed incidence (coarse node -> its blocks, fine nodes ascending), so that the restriction is a
+ *                   gather without atomics. The constrained dofs of the coarse space are listed too (ascending): dof (v, c) iff fine
+ *                   dof (coarse_to_fine[v], c) is constrained; hand the list to the assembly of the coarse matrix as its Dirichlet
+ *                   set. All device memory of setup and apply is allocated here: four fine vectors (x, d, t and the vector of the
+ *                   power iteration), the coarse right-hand side and correction. bs outside 1..3: DXO_E_DIM; n_nodes or
+ *                   n_constrained < 0, 2^31 dofs or more: DXO_E_SIZE.
+ * dxo_pmg_set_smoother : degree (1..8) of the Chebyshev polynomial, the steps of the power iteration, and `lower`, `safety` as in
+ *                   dxo_amg_set_smoother (defaults 2, 10, 0.1, 1.1; the same ranges, DXO_E_OPTION and nothing changes). It takes
+ *                   effect at the NEXT dxo_pmg_setup; until then dxo_pmg_apply and the Krylov calls answer DXO_E_OPTION.
+ * dxo_pmg_setup   : `fine` is the operator (csr + values, bs that of the object, or a callback that SETS out = A v), n = n_nodes * bs;
+ *                   `dinv` [n] its inverse diagonal with 1 on constrained dofs, where the operator must be the identity; `coarse` a
+ *                   preconditioner of n_coarse * bs rows: DXO_PC_AMG (V-cycle; a K-cycle: DXO_E_OPTION), DXO_PC_BLOCK_JACOBI,
+ *                   DXO_PC_JACOBI or DXO_PC_CALLBACK (the struct is copied); DXO_PC_NONE and unknown kinds: DXO_E_OPTION. rho is the
+ *                   power estimate of Dinv A documented at dxo_amg_set_smoother: w_0[i] = 0.5 + ((uint32)(i * 2654435761) >> 8) * 2^-24,
+ *                   rho_iters steps w_k = Dinv A (w_{k-1} / |w_{k-1}|), rho = safety |w_m|. |w|^2 is summed on a grid that depends on n
+ *                   alone (min(1024, ceil(n / 256)) workgroups of 256: a thread adds its entries in ascending order, then the
+ *                   xor-butterfly of the wave, then the four waves in ascending order; one workgroup adds the partials likewise), so
+ *                   rho is bit-reproducible. rho stays on the device and the `degree` pairs (c1, c2) are formed from it there by the
+ *                   recurrence at dxo_amg_set_smoother (rho not > 0: all-zero pairs): no host read, no synchronisation. Costs
+ *                   rho_iters operator calls. fine, dinv and coarse (and what they point to) are used again by every apply: they must
+ *                   stay alive and unchanged until the next setup. Sizes that differ: DXO_E_SIZE; a matrix or a coarse object of
+ *                   another block size: DXO_E_DIM; NULLs DXO_E_NULL; misaligned arrays DXO_E_ALIGN; a failing callback: its code.
+ * dxo_pmg_apply   : z = M r. (1) x = the polynomial from x = 0; its first step is d = c2 dinv r, x = d, without an operator call or a
+ *                   memset: degree - 1 calls. (2) t = A x, r_c = P^T (r - t), the subtraction inside the restriction. (3) e_c =
+ *                   coarse(r_c). (4) x += P e_c. (5) the same polynomial from the corrected x, d = c1 d + c2 dinv (r - A x),
+ *                   x += d, the last step writing z: degree calls. 2 degree operator calls in all. r may equal z. M is a fixed linear
+ *                   operator, symmetric for a symmetric A and a symmetric coarse preconditioner, homogeneous bit for bit under
+ *                   powers of two. Allocation-free, atomic-free, bit-reproducible, and capture-safe wherever the operator and the
+ *                   coarse preconditioner are. Before a successful setup: DXO_E_OPTION. Option "pmg_grid_blocks": the most
+ *                   workgroups of 256 an elementwise or transfer kernel is launched with (0, the default: 16 per compute unit;
+ *                   1..65535); beyond it a thread strides. Every entry is formed by one thread alone, so no result depends on it.
+ * dxo_pmg_restrict / dxo_pmg_prolong : the transfers alone. Restriction SETS r_c[v][c] = sum_i p_diag r[i][c] over the fine nodes of
+ *                   column v in ascending i; prolongation SETS x[i][c] = sum_v p_diag e[v][c] over the coarse nodes of row i in
+ *                   ascending v (inside the cycle it accumulates onto x in the same order).
+ * dxo_pmg_info    : the coarse rows, the blocks of P, and the DEVICE arrays p_diag [p_blocks][bs], the coarse constrained list (int32)
+ *                   with its length, rho (one double), the pairs [degree][2]; the degree set, and the operator calls of one apply
+ *                   (2 degree). Any out-pointer may be NULL.
+ * In dxo_krylov_gmres / dxo_krylov_cg / dxo_krylov_fgmres: kind DXO_PC_PMG, inv = (const double*)pmg, n that of the operator (bs is
+ * ignored); another size DXO_E_SIZE, a matrix operator of another block size DXO_E_DIM, no valid setup DXO_E_OPTION. inv is checked
+ * against the live objects of dxo_pmg_create before it is read: any other pointer under this kind is DXO_E_OPTION, as an unknown kind
+ * is (dxo_pmg_destroy answers the same for such a pointer, a second destroy included). */
+typedef struct dxo_pmg dxo_pmg;
+int dxo_pmg_create(dxo_ctx* ctx, int64_t n_nodes, int bs, const dxo_amg_transfer* transfer, const int32_t* constrained, int64_t n_constrained,
+                   dxo_pmg** out);
+int dxo_pmg_destroy(dxo_ctx* ctx, dxo_pmg* pmg);
+int dxo_pmg_set_smoother(dxo_ctx* ctx, dxo_pmg* pmg, int degree, int rho_iters, double lower, double safety);
+int dxo_pmg_setup(dxo_ctx* ctx, dxo_pmg* pmg, const dxo_krylov_op* fine, const double* dinv, const dxo_krylov_pc* coarse);
+int dxo_pmg_apply(dxo_ctx* ctx, dxo_pmg* pmg, const double* r, double* z);
+int dxo_pmg_restrict(dxo_ctx* ctx, dxo_pmg* pmg, const double* r_fine, double* r_coarse);
+int dxo_pmg_prolong(dxo_ctx* ctx, dxo_pmg* pmg, const double* e_coarse, double* x_fine);
+int dxo_pmg_info(dxo_ctx* ctx, const dxo_pmg* pmg, int64_t* n_coarse_rows, int64_t* p_blocks, const double** p_diag,
+                 const int32_t** coarse_constrained, int64_t* n_coarse_constrained, const double** rho, const double** pairs, int* degree,
+                 int64_t* matvecs_per_apply);
+#define DXO_PC_PMG 5               /* dxo_krylov_pc::inv carries the dxo_pmg* (cast to const double*), n as for the other kinds    */
+
 /* ---- boundary-facet integrals (ds) on the device: loads of a residual F = ... - inner(t, v) ds --------------------------
  * The demo's residual inner(sigma, eps(v)) dx - inner(loading * -n, v) ds(inner) (demo_plasticity_von_mises.py:249-253) is
  * dxo_operand_adjoint(EPS_MANDEL) followed by dxo_facet_pressure(scale = loading) on the facets of the tag.

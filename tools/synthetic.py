@@ -132,6 +132,19 @@ class SyntheticMesh:
         return np.einsum("qv,cvj->cqj", psi, self.x[self.geom_dofmap])
 
 
+def vertex_companion(mesh: "SyntheticMesh", points: np.ndarray | None = None, weights: np.ndarray | None = None) -> "SyntheticMesh":
+    """The degree-1 mesh on the same cells at the rule (points, weights), default the mesh's own: its field nodes are the geometry
+    nodes (dofmap = geom_dofmap, node_x = x), the coarse numbering of DeviceMesh.vertex_transfer and what DeviceMesh.vertex_mesh
+    builds on the device from `.psi`, `.dpsi` and `.weights`."""
+    import dataclasses
+
+    points = mesh.points if points is None else np.ascontiguousarray(points, dtype=np.float64)
+    weights = mesh.weights if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    psi, dpsi = LagrangeElement(mesh.cell, 1).tabulate(points)
+    return dataclasses.replace(mesh, degree=1, dofmap=mesh.geom_dofmap, node_x=mesh.x, points=points, phi=psi, dphi=dpsi, dpsi=dpsi,
+                               weights=weights, psi=psi)
+
+
 def coordinate_element_at_nodes(cell: str, degree: int = 2) -> np.ndarray:
     """(ndofs per cell, ngeom): the degree-1 coordinate element tabulated at the reference nodes of the Lagrange element of `degree`,
     what places the field nodes in `structured_mesh` and what DeviceMesh.vertex_transfer takes."""
