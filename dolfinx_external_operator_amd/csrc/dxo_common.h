@@ -98,7 +98,8 @@ struct dxo_ctx {
     int64_t krylov_basis_width = 4;     // Krylov solves on a DXO_KRYLOV_BASIS_FP32 workspace: consecutive rows of the float basis per thread (1, 2 or 4;
                                         // orthogonalisation of GMRES(30), P2 1291^2: 1.65 / 1.11 / 0.82 ms against 1.88 with the double basis)
     int64_t pmg_grid_blocks = 0;        // dxo_pmg_*: most workgroups of an elementwise or transfer kernel (0: 16 per compute unit); the results do not depend on it
-    int64_t amg_rank_tol = 10;          // dxo_amg_create_nns: a column of an aggregate's near-null space that keeps no more than 10^-value of its norm is dead
+    int64_t wave_group_blocks = 0;      // persistent element kernels (wave_group_grid, form_host.h): most workgroups (0: blocks_per_cu per compute unit); the results do not depend on it
+    int64_t amg_rank_tol = 10;         // dxo_amg_create_nns: a column of an aggregate's near-null space that keeps no more than 10^-value of its norm is dead
     int64_t spmv_lanes = 0;             // dxo_csr_spmv and the Krylov solves: lanes per node (8, 16, 32, 64; 0 = from the mean neighbour count)
     int64_t mc_part_points = (int64_t)1 << 30;   // Mohr-Coulomb: points per classify/Newton pass (int32 list entries)
     int64_t mc_waves_per_simd = 1;      // kept for option compatibility: mc_newton keeps its lane state in LDS (mc_core.h LaneLds) and

@@ -181,6 +181,7 @@ static int64_t* option_slot(dxo_ctx* c, const char* key) {
     if (!std::strcmp(key, "krylov_basis_width")) return &c->krylov_basis_width;
     if (!std::strcmp(key, "amg_rank_tol")) return &c->amg_rank_tol;
     if (!std::strcmp(key, "pmg_grid_blocks")) return &c->pmg_grid_blocks;
+    if (!std::strcmp(key, "wave_group_blocks")) return &c->wave_group_blocks;
     if (!std::strcmp(key, "adjoint_patch")) return &c->adjoint_patch;
     if (!std::strcmp(key, "adjoint_mfma")) return &c->adjoint_mfma;
     if (!std::strcmp(key, "mgpu_chunks")) return &c->mgpu_chunks;
@@ -233,7 +234,8 @@ int dxo_ctx_set_option(dxo_ctx* c, const char* key, int64_t value) {
     if (slot == &c->krylov_basis_width && value != 1 && value != 2 && value != 4)
         return dxo_fail(c, DXO_E_OPTION, "krylov_basis_width: 1, 2 or 4 rows of the float basis per thread");
     if (slot == &c->pmg_grid_blocks && (value < 0 || value > 65535)) return dxo_fail(c, DXO_E_OPTION, "pmg_grid_blocks: 0 (automatic) or 1..65535 workgroups");
-    if (slot == &c->amg_rank_tol && (value < 1 || value > 15)) return dxo_fail(c, DXO_E_OPTION, "amg_rank_tol: the exponent n of the threshold 10^-n, 1..15");
+    if (slot == &c->wave_group_blocks && (value < 0 || value > 65535)) return dxo_fail(c, DXO_E_OPTION, "wave_group_blocks: 0 (automatic) or 1..65535 workgroups");
+    if (slot == &c->amg_rank_tol &&(value < 1 || value > 15)) return dxo_fail(c, DXO_E_OPTION, "amg_rank_tol: the exponent n of the threshold 10^-n, 1..15");
     if (slot == &c->mc_blocks_per_cu && value < 1) return dxo_fail(c, DXO_E_OPTION, "mc_blocks_per_cu < 1");
     if (slot == &c->vm_rebuild_chunk_points && value < DXO_WAVE) return dxo_fail(c, DXO_E_OPTION, "vm_rebuild_chunk_points < 64");
     if (slot == &c->host_chunk_points && value < DXO_WAVE) return dxo_fail(c, DXO_E_OPTION, "host_chunk_points < 64");

@@ -96,12 +96,13 @@ int bilinear_pair_check(dxo_ctx* ctx, const char* who, const dxo_mesh* mesh, int
     return DXO_OK;
 }
 
-// grid of the persistent element kernels: one workgroup (four waves) per four wave groups, at most blocks_per_cu per compute unit, whole
-// rounds over the 8 XCDs (xcd_group_walk)
+// grid of the persistent element kernels: one workgroup (four waves) per four wave groups, at most blocks_per_cu per compute unit (option
+// "wave_group_blocks" > 0: at most that many; a cell's result does not depend on which wave forms it), whole rounds over the 8 XCDs
+// (xcd_group_walk)
 inline int64_t wave_groups(const OperandDev& v, int64_t n_cells) { return (n_cells + v.cells_per_wave - 1) / v.cells_per_wave; }
 inline int wave_group_grid(const dxo_ctx* ctx, int64_t n_groups, int blocks_per_cu) {
     int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * blocks_per_cu;
+    const int64_t cap = ctx->wave_group_blocks > 0 ? ctx->wave_group_blocks : (int64_t)ctx->compute_units * blocks_per_cu;
     if (blocks > cap) blocks = cap;
     return (int)((blocks + 7) / 8 * 8);
 }

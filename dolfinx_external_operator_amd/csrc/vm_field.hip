@@ -328,11 +328,7 @@ int field_launch(dxo_ctx* ctx, const FieldLaunch& L, int64_t cell0, int64_t n_ce
     }
     const size_t shm = (base_doubles + (dma ? slice_doubles : 0)) * sizeof(double);
     if (shm > 64 * 1024) return dxo_fail(ctx, DXO_E_SIZE, "dxo_von_mises_field: element too large for the LDS budget");
-    const int64_t n_groups = (n_cells + m.cells_per_wave - 1) / m.cells_per_wave;
-    int64_t blocks = (n_groups + 3) / 4;
-    const int64_t cap = (int64_t)ctx->compute_units * ((C_tang || fe) ? DXO_VMF_BLOCKS_PER_CU : DXO_VMF_STATE_BLOCKS_PER_CU);
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;      // whole rounds over the 8 XCDs (xcd_group_walk)
+    const int blocks = wave_group_grid(ctx, wave_groups(m, n_cells), (C_tang || fe) ? DXO_VMF_BLOCKS_PER_CU : DXO_VMF_STATE_BLOCKS_PER_CU);
     const bool nt = ctx->nontemporal != 0;
 #define DXO_VMF_LAUNCH(...)                                                                                                         \
     do {                                                                                                                            \

@@ -54,14 +54,15 @@ def build_mesh(case):
     return with_rule(m, *gauss_tensor_rule(cell, rule)) if rule else m
 
 
-def make_inputs(case, mesh):
+def make_inputs(case, mesh, seed=None):
     """Seeded caller-side data of one case: C SPD and different at every point (A A^T + 3 I), v, S, r0 ~ N(0, 1), sigma ~ N(0, 100),
     dp exactly 0.0 on about half the points and |N(0, 1e-3)| on the rest; sizes b and d: the cells of wave group 0 all elastic, those of
-    group 1 all plastic (the kernels branch per wave on neither, and must not start to without this noticing)."""
+    group 1 all plastic (the kernels branch per wave on neither, and must not start to without this noticing). seed: for a case outside
+    ALL_CASES (trip_cases.py), whose place in that list is otherwise the seed."""
     G, nn = mesh.gdim, mesh.node_x.shape[0]
     d = 4 if G == 2 else 6
     nc, nq = mesh.num_cells, mesh.nq
-    rng = np.random.Generator(np.random.PCG64(20 + ALL_CASES.index(case)))
+    rng = np.random.Generator(np.random.PCG64(20 + ALL_CASES.index(case) if seed is None else seed))
     A = rng.normal(size=(nc, nq, d, d))
     C = A @ A.transpose(0, 1, 3, 2) + 3.0 * np.eye(d)
     sigma = rng.normal(0.0, 100.0, size=(nc, nq, d))

@@ -6,6 +6,7 @@ ref and mag from oracle/hyper3_reference.py (long double) and eps = 2^-53 (2^-24
 entries with mag = 0 must be exact zeros. c is not tuned on the kernels: C_REF below is what the float64 twin of the reference loses
 against long double on the sample sets of this file, and the kernels get MARGIN = 8 times that, as in consumer_cases.py.
 """
+import concurrent.futures
 import functools
 import pathlib
 
@@ -187,7 +188,16 @@ CHUNK_MESHES = {"P1 tetrahedra (4,3,2), 7 points": ("tetrahedron", (4, 3, 2), 1,
 CHUNK_CELLS = 64
 
 
+def _trip_mesh(name):
+    """a mesh of trip_cases.CASES (many wave groups: tests/test_trips_gpu.py), taken by name like the ones above"""
+    return name not in FUSED_MESHES and name not in CHUNK_MESHES
+
+
 def fused_mesh(name):
+    if _trip_mesh(name):
+        import trip_cases
+
+        return trip_cases.mesh(name)
     cell, n, degree, rule = FUSED_MESHES[name] if name in FUSED_MESHES else CHUNK_MESHES[name]
     m = structured_mesh(cell, n, degree, distort=0.2, seed=4)
     if rule is None:
@@ -222,7 +232,8 @@ def fused_reference(model, name):
     extra is the allowance for the float64 rounding of F that tests/test_operand_reference_gpu.py grants the operand kernels,
         extra[k] = sum_j |d ref[k] / d F_j| * MARGIN * C_REF["F"] * 2^-53 * magF_j,
     with dP/dF the reference's own dP and d(dP)/dF a central difference of the long-double reference at the step 2^-20 (its
-    truncation, 2^-40 of the fourth derivative, is far below what an allowance needs)."""
+    truncation, 2^-40 of the fourth derivative, is far below what an allowance needs). On a mesh of trip_cases.CASES the C_REF["F"] is
+    trip_cases.C_REF_TRIP["F"], what the operand test grants on that mesh."""
     import operand_cases as OC
     from oracle.hyper3_reference import LD, icnn3_ref, isihara3_ref
     from oracle.operand_reference import ref_operand
@@ -230,19 +241,33 @@ def fused_reference(model, name):
 
     m = fused_mesh(name)
     u = _field(m, 0.15, 9)
+    if _trip_mesh(name):
+        import trip_cases
+
+        u = trip_cases.hyper3_field_u(name)
     F, magF = (a.reshape(-1, 9) for a in ref_operand(m, "F", 3, u))
     f = (lambda X: isihara3_ref(X, H3.DEFAULTS)) if model == "isihara3" else (lambda X: icnn3_ref(X, weights()))
     P, dP, mP, mdP = f(F)
     assert np.isfinite(np.asarray(dP, dtype=np.float64)).all()
-    cF = LD(OC.MARGIN * OC.C_REF["F"]) * LD(2.0) ** -53
+    c_ref_F = OC.C_REF["F"]
+    if _trip_mesh(name):
+        c_ref_F = trip_cases.C_REF_TRIP["F"][0]
+    cF = LD(OC.MARGIN * c_ref_F) * LD(2.0) ** -53
     extraP = np.einsum("nkj,nj->nk", np.abs(dP), magF) * cF
     h, n = LD(2.0) ** -20, F.shape[0]
     extradP = np.zeros((n, 81), dtype=LD)
-    for j in range(9):
+
+    def leg(j):          # |d(dP) / dF_j| magF_j
         Fp, Fm = F.copy(), F.copy()
         Fp[:, j] += h
         Fm[:, j] -= h
-        extradP += np.abs((f(Fp)[1] - f(Fm)[1]) / (2 * h)).reshape(n, 81) * magF[:, j:j + 1]
+        return np.abs((f(Fp)[1] - f(Fm)[1]) / (2 * h)).reshape(n, 81) * magF[:, j:j + 1]
+
+    # the nine legs are independent and NumPy releases the interpreter lock inside its loops: on the trip meshes (5000 points) the
+    # threads bring the reference from 10 s to a few; the sum is taken in the order j = 0 .. 8 as before
+    with concurrent.futures.ThreadPoolExecutor(max_workers=9) as pool:
+        for term in pool.map(leg, range(9)):
+            extradP += term
     out = (u, P, dP, mP, mdP, extraP, (extradP * cF).reshape(n, 9, 9))
     for a in out:
         a.setflags(write=False)

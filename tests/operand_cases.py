@@ -32,14 +32,15 @@ def kinds_of(gdim, bs):
     return CELL_KINDS if bs == gdim else COMPONENT_KINDS
 
 
-def fields(case, mesh, bs):
+def fields(case, mesh, bs, seed=None):
     """Seeded field vectors of one (case, block size), name -> u (num_field_nodes * bs):
       rough   N(0, 1) * 0.3 * (node spacing), so that grad u = O(1) and F = I + grad u is far from the identity;
       offset  rough + 1e6, a rigid offset: the gradient is a cancellation of terms of size 1e6 / h, and mag grows with them;
       det     size b, bs = gdim only: (A - I) x + rough with A = diag(0.05, 1[, 1]), so that det F = 0.05 + O(1) noise passes through
-              zero and is negative in some cells (asserted in test_operand_reference_cpu.py)."""
+              zero and is negative in some cells (asserted in test_operand_reference_cpu.py).
+    seed: for a case outside ALL_CASES (trip_cases.py), whose place in that list otherwise seeds the draw."""
     nn, G = mesh.node_x.shape[0], mesh.gdim
-    rng = np.random.Generator(np.random.PCG64(1000 + 10 * ALL_CASES.index(case) + bs))
+    rng = np.random.Generator(np.random.PCG64((1000 + 10 * ALL_CASES.index(case) if seed is None else seed) + bs))
     h = 1.0 / (max(case[2]) * case[1])
     rough = rng.normal(size=(nn, bs)) * (0.3 * h)
     out = {"rough": rough.reshape(-1), "offset": (rough + 1e6).reshape(-1)}
